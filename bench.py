@@ -11,9 +11,14 @@ stream s has prompt seed 1000+s and RNG seed 2000+s).  Streams are independent, 
 with no collective on the data path; one all_gather of token ids at the end of the timed region
 (SURVEY.md 8(e)).  Weights are random-init from the committed config JSONs (no checkpoints offline), so the
 accept length of the headline pair is ~0 by construction and `value` is essentially 1 token per draft+verify
-iteration; `mean_accept_len` is reported next to it, and `acceptance_sweep` repeats the same workload on a
-synthetic pair of the same two architectures whose distributions are correlated by a knob (synth.py, "Acceptance
-dial"), so that partial accepts, the all-accept branch and the bonus sample are timed too.  Rank 0 prints ONE JSON line.
+iteration; `mean_accept_len` is reported next to it.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps and reports them (with the verify-step roofline from the events
+recorded inside those steps).  --full adds what takes runs of its own: the per-op-class split of one verify step
+(--profile-classes), `acceptance_sweep` (--accept-sweep: the same workload on a synthetic pair of the same two
+architectures whose distributions are correlated by a knob, synth.py "Acceptance dial", so that partial accepts, the
+all-accept branch and the bonus sample are timed too) and `cpu_baseline` (--cpu-baseline).
+--dump-outputs DIR writes what the last timed step returned (token ids, accept lengths) as float64 .npy files.
 """
 import argparse
 import json
@@ -52,7 +57,7 @@ def parse(argv=None):
     ap.add_argument("--top-p", type=float, default=0.9)
     ap.add_argument("--rng", default="device", choices=["device", "host"],
                     help="device = on-device Philox (throughput mode); host = torch CPU generator in the reference's order")
-    ap.add_argument("--cpu-baseline", type=int, default=1, help="time the CPU oracle on a bounded sample (rank 0, N=1)")
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="with --full: time the CPU oracle on a bounded sample (rank 0, N=1)")
     ap.add_argument("--cpu-max-len", type=int, default=32)
     ap.add_argument("--cpu-budget-s", type=float, default=45.0, help="wall budget for the CPU baseline runs")
     ap.add_argument("--cpu-prompt-len", type=int, default=128)
@@ -60,16 +65,32 @@ def parse(argv=None):
                     help="throughput mode (SURVEY 8(f)): this many prompt streams decode in lockstep per step and share every "
                          "weight pass (speculative_sampling_batch); 1 = the single-stream path of BASELINE configs[1].  "
                          "BASELINE configs[3] (64 streams over 8 GPUs) is `--gpus 8 --streams-per-gpu 8 --steps 1`")
-    ap.add_argument("--profile-classes", type=int, default=1, help="per-op-class HIP-event timing of one verify step")
+    ap.add_argument("--profile-classes", type=int, default=1, help="with --full: per-op-class HIP-event timing of one verify step")
     ap.add_argument("--accept-sweep", type=int, default=1,
-                    help="after the headline, time the same workload on the acceptance-dial pair at each --sweep-sigmas (N=1)")
+                    help="with --full: after the headline, time the same workload on the acceptance-dial pair at each --sweep-sigmas (N=1)")
     ap.add_argument("--sweep-sigmas", default="0,0.04,0.08,0.16,0.32,1.0")
     ap.add_argument("--sweep-steps", type=int, default=4)
     ap.add_argument("--tp", type=int, default=1,
                     help="tensor-parallel degree of the TARGET (BASELINE config 5: --target llama-2-70b --tp 8 --kv-dtype fp8): "
                          "all --gpus ranks then decode ONE stream per step together (tp must equal gpus)")
     ap.add_argument("--kv-dtype", default="model", choices=["model", "fp8"], help="dtype of the target's KV arena")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the extras that take runs of their own: --profile-classes, "
+                         "--accept-sweep, --cpu-baseline (each still switched off by its own flag set to 0)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (token ids and accept lengths of its streams) to "
+                         "DIR/<name>.npy as float64 (per rank: DIR/rank<r>_<name>.npy when --gpus > 1)")
     return ap.parse_args(argv)
+
+
+def dump_outputs(path, outs, acc_lens, rank, world):
+    """The last timed step's results as a caller receives them: tokens_<j> = stream j's ids (prompt + generated, (1, L)),
+    accept_len_<j> = its per-iteration accept lengths; float64 holds every token id exactly."""
+    os.makedirs(path, exist_ok=True)
+    pre = f"rank{rank}_" if world > 1 else ""
+    for j, (o, acc) in enumerate(zip(outs, acc_lens)):
+        np.save(os.path.join(path, f"{pre}tokens_{j}.npy"), o.detach().cpu().numpy().astype(np.float64))
+        np.save(os.path.join(path, f"{pre}accept_len_{j}.npy"), np.asarray(acc, dtype=np.float64))
 
 
 class _stdout_to_stderr:
@@ -148,6 +169,8 @@ def stub_worker(args, rank, world):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
         stats = torch.cat([tmax, tot])
+    if args.dump_outputs and outs:
+        dump_outputs(args.dump_outputs, outs[-1:], [[0] * args.max_len], rank, world)     # (the fake step accepts nothing)
     if rank == 0:
         print(json.dumps({"metric": "stub", "value": float(stats[1]) / max(float(stats[0]), 1e-9), "unit": "tokens/s",
                           "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "new_tokens": float(stats[1]),
@@ -413,7 +436,8 @@ def main(argv=None):
                                                   gamma=args.gamma, top_k=args.top_k, top_p=args.top_p, details=True,
                                                   seeds=[2000 + stream * BS + j for j in range(BS)],
                                                   _timing=logs if isinstance(logs, dict) else None)
-            d = {"acc_len": [a for x in ds for a in x["acc_len"]], "target_call_times": sum(x["target_call_times"] for x in ds)}
+            d = {"acc_len": [a for x in ds for a in x["acc_len"]], "target_call_times": sum(x["target_call_times"] for x in ds),
+                 "acc_lens": [x["acc_len"] for x in ds]}
             new = sum(int(o.shape[1]) - int(p.shape[1]) for o, p in zip(outs, prompts))
             return outs, d, new
         prompt = prompt_of(stream).cuda()
@@ -425,6 +449,7 @@ def main(argv=None):
         out, d = speculative_sampling(prompt, dm, tm, eos_token_id=2, pad_token_id=None, max_len=args.max_len,
                                       gamma=args.gamma, top_k=args.top_k, top_p=args.top_p, details=True, rng=nz,
                                       _event_logs=logs)
+        d["acc_lens"] = [d["acc_len"]]
         return [out], d, int(out.shape[1]) - int(prompt.shape[1])
 
     # streams: rank r takes s = r, r+world, ... (round-robin)
@@ -465,6 +490,8 @@ def main(argv=None):
             tot /= world                              # every rank decoded the same streams: count them once
         elapsed, (new_tokens, acc_sum, n_iters) = float(tmax[0]), [float(x) for x in tot]
     value = new_tokens / elapsed
+    if args.dump_outputs and args.steps > 0:
+        dump_outputs(args.dump_outputs, o_list, d["acc_lens"], rank, world)
 
     # ---- verify-step roofline from the HIP events recorded inside the timed region (torch's current stream is
     # the stream every kernel was launched on).  One "launch" = one verify step = one target forward over
@@ -520,8 +547,8 @@ def main(argv=None):
         "target_prefill_avg_ms": float(np.mean(pre_ms)) if pre_ms else None,
     }
 
-    # ---- per-op-class split of one verify step (events around every launch; outside the timed region)
-    if args.profile_classes and rank == 0 and BS == 1 and TP == 1:
+    # ---- per-op-class split of one verify step (events around every launch; outside the timed region; --full)
+    if args.full and args.profile_classes and rank == 0 and BS == 1 and TP == 1:
         ses = tm.new_session(max_pos)
         toks = prompt_for(0, tcfg.vocab_size, args.prompt_len + args.gamma + 1).cuda()[0].to(torch.int32)
         done = 0
@@ -571,14 +598,14 @@ def main(argv=None):
         "roofline": roofline, "model_build_s": t_build,
     }
 
-    if (args.accept_sweep and rank == 0 and world == 1 and BS == 1 and args.kv_dtype == "model" and dcfg.arch == "llama"
-            and tcfg.arch == "llama" and not use_ckpt):
+    if (args.full and args.accept_sweep and rank == 0 and world == 1 and BS == 1 and args.kv_dtype == "model"
+            and dcfg.arch == "llama" and tcfg.arch == "llama" and not use_ckpt):
         try:
             result["acceptance_sweep"] = acceptance_sweep(args, dcfg, tcfg, max_pos)
         except Exception as e:
             result["acceptance_sweep"] = {"error": f"{type(e).__name__}: {e}"}
 
-    if args.cpu_baseline and rank == 0 and world == 1:
+    if args.full and args.cpu_baseline and rank == 0 and world == 1:
         try:
             cb = cpu_baseline(args, dcfg, tcfg, dm, tm)
             # the same bounded workload (same prompt, same max_len) on the GPU, so the two numbers are on one workload

@@ -331,6 +331,27 @@ def test_bench_launcher_propagates_rank_failure():
     assert r.returncode != 0
 
 
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the last timed step's token ids (stream s = steps - 1 in the stub) and accept lengths as
+    float64 .npy files, the same bytes from run to run with the same arguments."""
+    import json
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "0", "--prompt-len", "8", "--max-len", "4",
+                        "--dump-outputs", str(d)], {})
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])["steps"] == 3
+        assert sorted(p.name for p in d.iterdir()) == ["accept_len_0.npy", "tokens_0.npy"]
+        dumps.append({p.name: np.load(p) for p in d.iterdir()})
+    tok = dumps[0]["tokens_0.npy"]
+    assert tok.dtype == np.float64 and tok.shape == (1, 12)
+    assert np.array_equal(tok, np.arange(12, dtype=np.float64)[None] + 2)
+    assert dumps[0]["accept_len_0.npy"].dtype == np.float64
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+
+
 # --------------------------------------------------------------------------- tensor-parallel sharding (config 5)
 def _tp_gloo_worker(rank, world, port, q):
     import torch

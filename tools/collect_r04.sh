@@ -3,8 +3,8 @@
 set -o pipefail
 O=gpurun_out/r04; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-B="--cpu-baseline 0 --accept-sweep 0"
-echo "[1] default bench"; timeout -k 10 500 python bench.py > $O/bench.json 2> $O/bench.err
+B="--full --cpu-baseline 0 --accept-sweep 0"
+echo "[1] default bench"; timeout -k 10 500 python bench.py --full > $O/bench.json 2> $O/bench.err
 echo "[2] throughput"; for bs in 8 12 16; do timeout -k 10 300 python bench.py --steps 1 --warmup 1 $B --batch-streams $bs > $O/bench_throughput_b$bs.json 2>/dev/null; done
 for g in 2 8; do timeout -k 10 300 python bench.py --steps 1 --warmup 1 $B --batch-streams 8 --gamma $g > $O/bench_throughput_b8_gamma$g.json 2>/dev/null; done
 echo "[3] gamma"; for g in 2 8; do timeout -k 10 300 python bench.py --gamma $g --steps 3 $B > $O/bench_gamma$g.json 2>/dev/null; done
