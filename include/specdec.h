@@ -268,6 +268,10 @@ int sd_model_destroy(sd_model *m);
  * per-layer weight matrix to have N % 128 == 0 and K % 64 == 0, K >= 512) or 64.  sd_session_create and
  * sd_session_scratch_bytes clamp their max_rows to it. */
 int sd_model_max_rows(const sd_model *m);
+/* Rows of one call whose rows are all logit rows (a stream-batched verify pass; sd_session_forward with n_logits == n_new):
+ * at most 80 and at most sd_model_max_rows, and past 64 only when the lm_head (vocab % 128 == 0) has a many-row kernel too.
+ * Calls with fewer logit rows than rows carry at most 64 logit rows. */
+int sd_model_max_pass_rows(const sd_model *m);
 
 /* Repack a row-major bf16 [N][K] matrix (N % 16 == 0, K % 32 == 0) into the streaming layout the
  * GEMM kernels read: 1 KiB tiles [N/16][K/32][lane 0..63][8 bf16], lane = 16*(k/8 % 4) + n % 16. */
@@ -280,8 +284,8 @@ int sd_pack_activation_bf16(const void *x_rowmajor, void *x_tiled, int M, int K,
 
 /* The weight-streaming GEMM on its own (unit tests, kernel-level roofline runs):
  * part[s][m][n] = sum over k-slice s of x[m][k] * W[n][k] for a tile-packed bf16 W, then (if out != NULL)
- * out[m][n] = sum_s part[s][m][n] in fp32.  M <= 64 (<= 256 with x_tiled and N % 128 == 0: from 33 rows on the
- * LDS-tiled kernel runs).  x: plain rows (x_tiled == 0) or sd_pack_activation_bf16's
+ * out[m][n] = sum_s part[s][m][n] in fp32.  M <= 64 (<= 256 with x_tiled and N % 128 == 0: past 64 rows the balanced
+ * many-row kernel or gemm_bf16_mm runs, as in the forward).  x: plain rows (x_tiled == 0) or sd_pack_activation_bf16's
  * layout (x_tiled != 0, what the forward uses).  part must hold splits * roundup(M,16) * N floats; the split count the
  * policy chose comes back in *splits_out. */
 int sd_gemm_bf16(const void *w_packed, const void *x, int x_tiled, int M, int N, int K, float *part,

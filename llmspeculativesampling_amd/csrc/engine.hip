@@ -38,6 +38,7 @@ enum { PC_GEMM = 0, PC_ATTN, PC_NORM, PC_QKV, PC_ACT, PC_EMBED, PC_LOGITS, PC_OT
 struct sd_session {
     sd_model *m;
     int max_seq, max_rows;
+    int max_pass_rows;  // rows of a call whose rows are all logit rows (sd_model_max_pass_rows, <= max_rows)
     char *kv;        // [L][2][Hkv][max_seq][D]
     char *scratch;
     // carved scratch
@@ -157,7 +158,7 @@ extern "C" int sd_pack_weight_bf16(const void *src, void *dst, int N, int K, voi
 struct EnvTun {
     int gemm_ntw = 4, gemm_units = -1, small_path = 1, small_split_bytes = 0, tiny_split_bytes = 24576, fuse_embed_qkv = 1, head_tiles = 1;
     int attn_split_keys = 384, attn_keys_per_split = 256;
-    int gemm_mm = 1, mm_mtw = 0, mm_s = 0, prefill_attn = 1, mm_slabs_min = 24;
+    int mm_mtw = 0, mm_s = 0, prefill_attn = 1, mm_slabs_min = 24;
     int wide_qkv = 1, tp_one_slab = 1, gemm_rows = 1, cus = 0, fuse_attn_o = 1, ao_stamps = 0, ao_delay = 300, ao_gap = 100, norm_on_load = 2, rows_max = SD_ROWS_MAX;
 };
 static EnvTun g_env;
@@ -180,7 +181,6 @@ static void refresh_env() {
     g_env.ao_gap = geti("SD_AO_GAP", 100);            // ... and pause after every 8 requests
     g_env.fuse_attn_o = geti("SD_FUSE_ATTN_O", 1);    // 0: attention and the O projection as two launches (A/B runs, bit-compare tests)
     g_env.norm_on_load = geti("SD_NORM_ON_LOAD", 2);  // 0: residual+norm launches stay; 1: attention -> MLP seam only; 2: both seams (A/B runs, compare tests)
-    g_env.gemm_mm = geti("SD_GEMM_MM", 1);            // 1 (default): prefill passes the balanced kernel does not take run on gemm_bf16_mm (mm_kernels.h) instead of gemm_bf16_tiled
     g_env.prefill_attn = geti("SD_PREFILL_ATTN", 1);  // 0: prefill passes keep attn_kernel's 8-row groups (A/B runs, compare tests)
     g_env.mm_slabs_min = geti("SD_MM_SLABS_MIN", 24); // rows from which the k-slab GEMMs (O / down) of a pass take gemm_bf16_mm instead of the balanced kernel
     g_env.mm_mtw = geti("SD_MM_MTW", 0);              // (sweeps) m-tiles per wave of gemm_bf16_mm: 2 = 128-row blocks, 4 = 256-row blocks; 0 = by row count
@@ -189,7 +189,7 @@ static void refresh_env() {
     g_env.gemm_rows = geti("SD_GEMM_ROWS", 1);        // 0: 17..64-row GEMMs stay on the streaming kernel (A/B runs, bit-compare tests)
     g_env.wide_qkv = geti("SD_WIDE_QKV", 1);          // 0: a QKV projection with <= 128 n-tiles keeps one 4-wave workgroup per tile (A/B, compare tests)
     g_env.tp_one_slab = geti("SD_TP_ONE_SLAB", 1);    // 0: a shard's O / down projection keeps its k-slabs + the fold launch in front of the all-reduce (A/B)
-    g_env.rows_max = std::min(SD_ROWS_MAX, std::max(SD_STREAM_MAX_ROWS, geti("SD_GEMM_ROWS_MAX", SD_ROWS_MAX)));   // 65..this many rows take the balanced kernel, more the LDS-tiled one
+    g_env.rows_max = std::min(SD_ROWS_MAX, std::max(SD_STREAM_MAX_ROWS, geti("SD_GEMM_ROWS_MAX", SD_ROWS_MAX)));   // 65..this many rows take the balanced kernel, more gemm_bf16_mm
     if (!g_env.cus) {
         int dev = 0, n = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
@@ -258,73 +258,88 @@ static void gemm_split(int N, int K, int M, int *S_out, int *ks_per_out) {
     *ks_per_out = ks_per;
 }
 
-// Which kernel a bf16 GEMM over M rows takes and how its k-range is cut.  Prefill chunks of more than 64 rows take the
-// LDS-tiled kernel: tools/gemm_bench.py at the 13b shapes, one tiled pass over 128 / 256 rows costs 171 / 257 us per
-// layer against 324 / 648 us for 2 / 4 streaming passes of 64.  At 33..64 rows it is ~10 % ahead as a bare GEMM (qkv
-// 35.6 us against 41.1, gate/up 59.8 / 63.8) but needs slabs plus the stand-alone epilogues where the streaming kernel
-// fuses them, and the whole forward comes out even (bench.py --batch-streams 8 / 12), so those stay on the streaming
-// kernel.  Slab count: about 480 workgroups (measured optimum for all four shapes at 64, 128 and 256 rows).
+// Which kernel a bf16 GEMM over M rows takes and how its k-range is cut - route_gemm is the one place that chooses.  In
+// order of preference:
+//   * gemm_bf16_stream_w16 (sixteen waves per n-tile): a QKV projection of <= 16 rows with few n-tiles and a long k-range
+//     (a tensor-parallel shard's QKV: 80 tiles x K = 8192);
+//   * gemm_bf16_mm (mm_kernels.h, 128- or 256-row blocks): the k-slab GEMMs (O / down) of a 24..144-row pass, and every
+//     GEMM past 64 rows that the balanced kernel does not take (prefill passes past SD_ROWS_MAX rows).  A k-slab GEMM of a
+//     24..144-row pass is faster on it with 128-row blocks and 6 slabs than on the balanced kernel - 12.7 / 28.1 us against
+//     15.3 / 29.6 at 40 rows (8 streams x 5), 13.6 / 28.3 against 16.7 / 31.6 at 60, 14.7 / 30.2 against 18.0 / 36.3 at 80,
+//     18.1 / 36.2 against 19.7 / 42.5 at 132; equal at 24 - tools/mm_bench.py.  QKV and gate/up with their fused epilogues
+//     stay on the balanced kernel: 36.9 / 56.1 us against 52.0 / 60.5 at 80 rows, 44.9 / 70.1 against 50.1 / 74.7 at 132;
+//   * gemm_bf16_rows (rows_kernels.h, one workgroup per CU): 17..SD_ROWS_MAX rows when both of its plans for the shape
+//     are good;
+//   * gemm_bf16_stream: <= 64 rows, always (and the only kernel that gathers or reads row-major activations).
+// A route of kind GK_NONE has no kernel: the row limits (sd_model_max_rows, sd_model_max_pass_rows) keep such calls out.
 #define SD_MAX_FWD_ROWS 256
-struct GemmPlan { bool tiled; int S, ksp, mtw, mm; };
 struct RowsPlan { bool ok; int S, ksp, NG, grid, nwn, nwk, nld; };
 static RowsPlan rows_plan(int N, int K, int M, bool fused);
-// fused: the caller wants the GEMM's whole k-range per workgroup (QKV / activation epilogue inside the launch)
-static GemmPlan gemm_plan(int N, int K, int M, bool x_tiled = true, bool fused = false) {
-    GemmPlan p = {};
+enum GemmKind { GK_NONE = 0, GK_STREAM, GK_STREAM_W16, GK_ROWS, GK_MM };
+enum GemmNeed {
+    GN_GATHER = 1,     // X rows are gathered through the row table's xmap (the lm_head of some rows of a pass)
+    GN_ROWMAJOR = 2,   // X is plain row-major (the public sd_gemm_bf16)
+    GN_FUSED = 4,      // the QKV / activation epilogue runs in the launch: every workgroup keeps its whole k-range (X tiled)
+    GN_QKV = 8,        // ... and it is the QKV epilogue
+    GN_ONE_SLAB = 16,  // one k-slab where the shape allows it (a tensor-parallel shard's O / down projection: its [M][N]
+                       // partial then goes to the all-reduce as it is, without a fold launch in between)
+};
+struct GemmRoute { int kind, S, ksp, mtw; RowsPlan rp; };
+static GemmRoute route_gemm(int N, int K, int M, int need) {
+    GemmRoute r = {};
+    const bool fused = need & GN_FUSED, x_tiled = !(need & (GN_GATHER | GN_ROWMAJOR));
     const int KS = K / 32, Mpad = (int)align_up(M, 16);
-    static const int tiled_min = getenv("SD_GEMM_TILED_MIN") ? atoi(getenv("SD_GEMM_TILED_MIN")) : 65;
-    // (65..SD_MAX_ROWS rows - 8 streams x 9 verify rows - stay on the balanced one-workgroup-per-CU kernel, with its fused
-    //  epilogues, when both of its plans for the shape are good; prefill chunks of that size take it too)
-    // (a k-slab GEMM - O / down projection - of a 24..144-row pass is faster on gemm_bf16_mm with 128-row blocks and 6 slabs
-    //  than on the balanced kernel - 12.7 / 28.1 us against 15.3 / 29.6 at 40 rows (8 streams x 5), 13.6 / 28.3 against 16.7 /
-    //  31.6 at 60, 14.7 / 30.2 against 18.0 / 36.3 at 80, 18.1 / 36.2 against 19.7 / 42.5 at 132; equal at 24 - tools/mm_bench.py.
-    //  QKV and gate/up with their fused epilogues stay on the balanced kernel: 36.9 / 56.1 us against 52.0 / 60.5 at 80 rows,
-    //  44.9 / 70.1 against 50.1 / 74.7 at 132)
-    const bool mm_slabs = g_env.gemm_mm && !fused && M >= g_env.mm_slabs_min && (size_t)N * K >= ((size_t)16 << 20) && N / 16 / 8 < 64;
-    const bool rows_take = M > SD_STREAM_MAX_ROWS && M <= g_env.rows_max && !mm_slabs && rows_plan(N, K, M, fused).ok;
-    if (x_tiled && (M >= tiled_min || mm_slabs) && !rows_take && (N / 16) % 8 == 0 && KS % 2 == 0 && KS >= 16) {
-        p.tiled = true;
-        if (g_env.gemm_mm && (Mpad > 64 || mm_slabs)) {
-            // gemm_bf16_mm (mm_kernels.h): 256-row blocks (mtw 4) or 128-row blocks (mtw 2) x 128 columns.  Fused (the caller
-            // wants the whole k-range per block for a QKV / activation epilogue): the block shape that fills the CUs better
-            // (13b at 256 rows: gate/up 216 blocks of 256 rows, QKV 240 blocks of 128).  Otherwise 256-row blocks past 128
-            // rows and k-slabs for about one block per CU (tools/mm_bench.py: O / down 6 slabs, QKV 2).
-            const int G = g_env.cus > 0 ? g_env.cus : 256, NB = N / 16 / 8;
-            auto blocks_of = [&](int mtw) { const int BMT = 4 * mtw; return ((Mpad / 16 + BMT - 1) / BMT) * NB; };
-            auto fill = [&](int blocks) { return (double)blocks / (double)(((blocks + G - 1) / G) * G); };
-            p.mm = 1;
-            p.mtw = Mpad <= 128 ? 2 : 4;
-            if (fused && Mpad > 128 && fill(blocks_of(2)) > fill(blocks_of(4)) + 0.05) p.mtw = 2;
-            if (g_env.mm_mtw) p.mtw = g_env.mm_mtw;
-            const int blocks = blocks_of(p.mtw);
-            int S = fused ? 1 : (g_env.mm_s ? g_env.mm_s : std::max(1, (G - G / 16 + blocks / 2) / blocks));
-            S = std::min(std::min(S, 8), std::max(1, KS / 8));     // (every slab is a write + a read of Mpad x N floats)
-            p.ksp = (int)align_up((KS + S - 1) / S, 2);
-            p.S = (KS + p.ksp - 1) / p.ksp;
-            return p;
-        }
-        p.mtw = Mpad <= 64 ? 2 : 4;
-        const int MB = (Mpad / 16 + 2 * p.mtw - 1) / (2 * p.mtw), blocks = MB * (N / 16 / 8);
-        int S = std::max(1, (480 + blocks / 2) / blocks);
-        S = std::min(S, std::max(1, KS / 16));
-        p.ksp = (int)align_up((KS + S - 1) / S, 2);
-        p.S = (KS + p.ksp - 1) / p.ksp;
-        return p;
+    if ((need & GN_QKV) && g_env.wide_qkv && M <= 16 && x_tiled && N / 16 <= 128 && KS >= 128) {
+        r.kind = GK_STREAM_W16;
+        r.S = 1;
+        r.ksp = KS;
+        return r;
     }
-    gemm_split(N, K, std::min(M, 64), &p.S, &p.ksp);
-    return p;
+    const bool mm_slabs = !fused && M >= g_env.mm_slabs_min && (size_t)N * K >= ((size_t)16 << 20) && N / 16 / 8 < 64;
+    const RowsPlan rp = x_tiled ? rows_plan(N, K, M, fused) : RowsPlan{};
+    const bool rows_take = M > SD_STREAM_MAX_ROWS && M <= g_env.rows_max && !mm_slabs && rp.ok;
+    if (x_tiled && (M > SD_STREAM_MAX_ROWS || mm_slabs) && !rows_take && (N / 16) % 8 == 0 && KS % 2 == 0 && KS >= 16) {
+        // 256-row blocks (mtw 4) or 128-row blocks (mtw 2) x 128 columns.  Fused: the block shape that fills the CUs better
+        // (13b at 256 rows: gate/up 216 blocks of 256 rows, QKV 240 blocks of 128).  Otherwise 256-row blocks past 128
+        // rows and k-slabs for about one block per CU (tools/mm_bench.py: O / down 6 slabs, QKV 2).
+        const int G = g_env.cus > 0 ? g_env.cus : 256, NB = N / 16 / 8;
+        auto blocks_of = [&](int mtw) { const int BMT = 4 * mtw; return ((Mpad / 16 + BMT - 1) / BMT) * NB; };
+        auto fill = [&](int blocks) { return (double)blocks / (double)(((blocks + G - 1) / G) * G); };
+        r.kind = GK_MM;
+        r.mtw = Mpad <= 128 ? 2 : 4;
+        if (fused && Mpad > 128 && fill(blocks_of(2)) > fill(blocks_of(4)) + 0.05) r.mtw = 2;
+        if (g_env.mm_mtw) r.mtw = g_env.mm_mtw;
+        const int blocks = blocks_of(r.mtw);
+        int S = fused ? 1 : (g_env.mm_s ? g_env.mm_s : std::max(1, (G - G / 16 + blocks / 2) / blocks));
+        S = std::min(std::min(S, 8), std::max(1, KS / 8));     // (every slab is a write + a read of Mpad x N floats)
+        r.ksp = (int)align_up((KS + S - 1) / S, 2);
+        r.S = (KS + r.ksp - 1) / r.ksp;
+        return r;
+    }
+    if (rp.ok) {
+        r.kind = GK_ROWS;
+        r.rp = rp;
+        r.S = rp.S;
+        r.ksp = rp.ksp;
+        return r;
+    }
+    if (M > SD_STREAM_MAX_ROWS) return r;
+    r.kind = GK_STREAM;
+    gemm_split(N, K, M, &r.S, &r.ksp);
+    // (<= 16 rows of a shard: one workgroup per n-tile over the whole k-range still gives >= 256 workgroups at hidden >= 4096)
+    if (fused || ((need & GN_ONE_SLAB) && M <= 16 && N / 16 >= 256)) {
+        r.S = 1;
+        r.ksp = KS;
+    }
+    return r;
 }
 
-// can a GEMM with this plan run a fused QKV / activation epilogue?  (the streaming and balanced kernels: always, with
-// SB = 1; the LDS-tiled kernel: never; gemm_bf16_mm: with one slab)
-static bool fused_plan_ok(const GemmPlan &p) { return !p.tiled || (p.mm && p.S == 1); }
-
-// gemm_bf16_mm (mm_kernels.h): EPI != EPI_PART needs pl.S == 1 (the block holds the whole k-range)
+// gemm_bf16_mm (mm_kernels.h): EPI != EPI_PART needs r.S == 1 (the block holds the whole k-range)
 template <int EPI, typename H = bf16_t>
-static void launch_gemm_mm(const void *W, const void *X, float *part, int M, int Mpad, int N, int K, const GemmPlan &pl,
+static void launch_gemm_mm(const void *W, const void *X, float *part, int M, int Mpad, int N, int K, const GemmRoute &r,
                            const GemmEpiT<H> &e, hipStream_t st) {
-    const int BMT = 4 * pl.mtw, MB = (Mpad / 16 + BMT - 1) / BMT, NB = N / 16 / 8;
-    const dim3 grid(MB * NB * pl.S);
+    const int BMT = 4 * r.mtw, MB = (Mpad / 16 + BMT - 1) / BMT, NB = N / 16 / 8;
+    const dim3 grid(MB * NB * r.S);
     const size_t lds = (size_t)3 * (8 + BMT) * 2 * 1024;          // NBUF = 3 stages x KT = 2 k-tiles x (8 W + BMT X) KiB
     auto go = [&](auto kern) {
         static bool attr = false;                                 // (one flag per instantiation of this lambda = per kernel)
@@ -332,42 +347,15 @@ static void launch_gemm_mm(const void *W, const void *X, float *part, int M, int
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
             attr = true;
         }
-        hipLaunchKernelGGL(kern, grid, dim3(MM_THREADS), lds, st, (const u32x4 *)W, (const u32x4 *)X, part, M, Mpad, N, K, pl.S,
-                           pl.ksp, e);
+        hipLaunchKernelGGL(kern, grid, dim3(MM_THREADS), lds, st, (const u32x4 *)W, (const u32x4 *)X, part, M, Mpad, N, K, r.S,
+                           r.ksp, e);
     };
     // 256-row blocks hold every row of a pass (<= 256 rows): their weight tiles are read once chip-wide -> non-temporal
-    if (pl.mtw == 2) go(gemm_bf16_mm<2, EPI, H, false>);
+    if (r.mtw == 2) go(gemm_bf16_mm<2, EPI, H, false>);
     else go(gemm_bf16_mm<4, EPI, H, true>);
 }
 
-template <typename H = bf16_t>
-static void launch_gemm_tiled(const void *W, const void *X, float *part, int M, int Mpad, int N, int K,
-                              const GemmPlan &pl, hipStream_t st) {
-    if (pl.mm) {
-        GemmEpiT<H> e0 = {};
-        launch_gemm_mm<EPI_PART, H>(W, X, part, M, Mpad, N, K, pl, e0, st);
-        return;
-    }
-    const int MB = (Mpad / 16 + 2 * pl.mtw - 1) / (2 * pl.mtw), NB = N / 16 / 8;
-    const dim3 grid(MB * NB * pl.S);
-    const size_t lds = (size_t)2 * (8 + 2 * pl.mtw) * 2 * 1024;   // 2 buffers x (8 W + 2*MTW X tiles) x KT = 2 k-tiles
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_bf16_tiled<2, 4, 2, H>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_bf16_tiled<4, 4, 2, H>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        attr = true;
-    }
-    if (pl.mtw == 2)
-        hipLaunchKernelGGL((gemm_bf16_tiled<2, 4, 2, H>), grid, dim3(256), lds, st, (const u32x4 *)W, (const u32x4 *)X, part, M,
-                           Mpad, N, K, pl.S, pl.ksp);
-    else
-        hipLaunchKernelGGL((gemm_bf16_tiled<4, 4, 2, H>), grid, dim3(256), lds, st, (const u32x4 *)W, (const u32x4 *)X, part, M,
-                           Mpad, N, K, pl.S, pl.ksp);
-}
-
-// ---- 17..64 rows: the balanced one-workgroup-per-CU kernel (rows_kernels.h).  S k-slabs x NG n-groups = one workgroup per
+// ---- 17..SD_ROWS_MAX rows: the balanced one-workgroup-per-CU kernel (rows_kernels.h).  S k-slabs x NG n-groups = one workgroup per
 // CU; a fused epilogue needs S == 1.  The plan minimises (weight bytes + slab traffic) / how evenly the n-tiles divide.
 static RowsPlan rows_plan(int N, int K, int M, bool fused) {
     RowsPlan p = {};
@@ -446,15 +434,16 @@ static int launch_gemm_rows(const void *W, const void *X, float *part, int M, in
     return SD_OK;
 }
 
-static size_t gemm_part_floats(const sd_model_config &c, int N, int K, int rows) {
+// floats of the k-slabs a GEMM of an N x K weight leaves at up to `rows` rows: the largest of its routes that can run (X in
+// the tile layout, or gathered for the lm_head / OPT's project_out; fused epilogues leave no slabs)
+static size_t gemm_part_floats(const sd_model_config &c, int N, int K, int rows, bool gathered = false) {
     if (!is16(c.dtype)) return (size_t)rows * N;
     size_t best = 0;
-    for (int m = 1; m <= rows; m = (m % 16 == 0 ? m + 1 : (int)align_up(m, 16))) {       // every plan class: 1, 16, 17, 32, 33, ...
-        const GemmPlan pl = gemm_plan(N, K, m);
-        best = std::max(best, (size_t)pl.S * align_up(m, 16) * N);
-        const RowsPlan rp = rows_plan(N, K, m, false);
-        if (rp.ok) best = std::max(best, (size_t)rp.S * align_up(m, 16) * N);
-    }
+    for (int m = 1; m <= rows; ++m)
+        for (int need : {0, gathered ? GN_GATHER : 0}) {
+            const GemmRoute r = route_gemm(N, K, m, need);
+            if (r.kind != GK_NONE) best = std::max(best, (size_t)r.S * align_up(m, 16) * N);
+        }
     return best;
 }
 
@@ -496,10 +485,10 @@ static ScratchPlan plan_scratch(const sd_model_config &c, int rows) {
     pf = std::max(pf, gemm_part_floats(c, c.hidden, q_dim(c), rows));
     pf = std::max(pf, gemm_part_floats(c, gu_cols(c), c.hidden, rows));
     pf = std::max(pf, gemm_part_floats(c, c.hidden, c.inter, rows));
-    pf = std::max(pf, gemm_part_floats(c, c.vocab, ed, rows));
+    pf = std::max(pf, gemm_part_floats(c, c.vocab, ed, rows, true));
     if (ed != c.hidden) {
         pf = std::max(pf, gemm_part_floats(c, c.hidden, ed, rows));
-        pf = std::max(pf, gemm_part_floats(c, ed, c.hidden, rows));
+        pf = std::max(pf, gemm_part_floats(c, ed, c.hidden, rows, true));
     }
     p.part_floats = pf;
     p.part = take(pf * sizeof(float));
@@ -513,19 +502,34 @@ static ScratchPlan plan_scratch(const sd_model_config &c, int rows) {
     return p;
 }
 
-// Rows one sd_session_forward call may carry: 256 when every per-layer GEMM of the model can take the tiled kernel
+// The rows up to `cap` at which every GEMM of a pass has a route (X in the tile layout), at every smaller count too: the
+// per-layer shapes (+ OPT's project_in / project_out), and with `head` the lm_head of a pass whose rows are all logit rows
+static int routed_rows(const sd_model_config &c, bool head, int cap) {
+    const int ed = embed_dim(c);
+    std::vector<std::pair<int, int>> shapes = {{qkv_cols(c), c.hidden}, {c.hidden, q_dim(c)}, {gu_cols(c), c.hidden}, {c.hidden, c.inter}};
+    if (ed != c.hidden) shapes.insert(shapes.end(), {{c.hidden, ed}, {ed, c.hidden}});
+    if (head) shapes.push_back({c.vocab, ed});
+    for (int m = 1; m <= cap; ++m)
+        for (const auto &sh : shapes)
+            if (route_gemm(sh.first, sh.second, m, 0).kind == GK_NONE) return m - 1;
+    return cap;
+}
+
+// Rows one sd_session_forward call may carry: 256 when every per-layer GEMM of the model has a route at every row count
 // (or the model is fp32, whose simple GEMM has no row limit), else the streaming kernel's 64.
 extern "C" int sd_model_max_rows(const sd_model *m) {
     if (!m) return 0;
     refresh_env();
-    const sd_model_config &c = m->cfg;
-    if (!is16(c.dtype)) return SD_MAX_FWD_ROWS;
-    const int ed = embed_dim(c);
-    const int shapes[][2] = {{qkv_cols(c), c.hidden}, {c.hidden, q_dim(c)}, {gu_cols(c), c.hidden}, {c.hidden, c.inter},
-                             {c.hidden, ed}, {ed, c.hidden}};
-    for (int i = 0; i < (ed != c.hidden ? 6 : 4); ++i)
-        if (!gemm_plan(shapes[i][0], shapes[i][1], SD_MAX_FWD_ROWS).tiled) return SD_STREAM_MAX_ROWS;
-    return SD_MAX_FWD_ROWS;
+    if (!is16(m->cfg.dtype)) return SD_MAX_FWD_ROWS;
+    return routed_rows(m->cfg, false, SD_MAX_FWD_ROWS) == SD_MAX_FWD_ROWS ? SD_MAX_FWD_ROWS : SD_STREAM_MAX_ROWS;
+}
+
+// Rows of one pass whose rows are all logit rows (a stream-batched verify): at most SD_MAX_ROWS, and only as many as the
+// lm_head has a kernel for (a vocab that is not a multiple of 128 columns - OPT's 50272 - stops at the streaming kernel's 64).
+extern "C" int sd_model_max_pass_rows(const sd_model *m) {
+    if (!m) return 0;
+    const int cap = std::min(SD_MAX_ROWS, sd_model_max_rows(m));
+    return is16(m->cfg.dtype) ? routed_rows(m->cfg, true, cap) : cap;
 }
 
 extern "C" size_t sd_session_scratch_bytes(const sd_model *m, int max_rows) {
@@ -547,6 +551,7 @@ extern "C" int sd_session_create(sd_model *m, int max_seq, int max_rows, void *k
     s->max_seq = max_seq;
     max_rows = std::min(max_rows, sd_model_max_rows(m));
     s->max_rows = max_rows;
+    s->max_pass_rows = std::min(max_rows, sd_model_max_pass_rows(m));
     s->kv = (char *)kv_arena;
     s->scratch = (char *)scratch;
     const ScratchPlan p = plan_scratch(m->cfg, max_rows);
@@ -937,90 +942,82 @@ static int dispatch_gemm_bf16(const void *W, const void *X, float *part, int M, 
                         else if (ntw == 4) launch_gemm_bf16<4, EPI, 4, H>(W, X, part, M, Mpad, N, K, S, ksp, e, st);
                         else if (ntw == 2) launch_gemm_bf16<4, EPI, 2, H>(W, X, part, M, Mpad, N, K, S, ksp, e, st);
                         else launch_gemm_bf16<4, EPI, 1, H>(W, X, part, M, Mpad, N, K, S, ksp, e, st); }
-    else { sd_set_error("gemm: M=%d exceeds 64 rows per call", M); return SD_ERR_INVALID; }
+    else { sd_set_error("internal: the streaming GEMM got M=%d rows (route_gemm routes <= 64)", M); return SD_ERR_INVALID; }
     return SD_OK;
 }
 
-// X: [M][K] activations (M <= 64 per call; callers chunk), W: [N][K] weights -> split-K slabs in s->part
+// Launch a bf16 GEMM the way route_gemm routed it.  EPI_PART leaves r.S k-slabs of [Mpad][N] floats in `part`; any other
+// epilogue finishes in the launch (a route of one slab).
+template <int EPI, typename H = bf16_t>
+static int launch_gemm(const GemmRoute &r, const void *W, const void *X, float *part, int M, int N, int K, const GemmEpiT<H> &e,
+                       hipStream_t st) {
+    const int Mpad = (int)align_up(M, 16);
+    auto bad = [&] {
+        sd_set_error("internal: GEMM route %d cannot run epilogue %d (M=%d N=%d K=%d)", r.kind, EPI, M, N, K);
+        return SD_ERR_INVALID;
+    };
+    int rc = SD_OK;
+    if constexpr (EPI == EPI_HEAD) {                              // (the head's tile maxima: one m-tile of the streaming kernel)
+        if (r.kind != GK_STREAM || Mpad != 16) return bad();
+        launch_gemm_bf16<1, EPI_HEAD, 1, H>(W, X, part, M, Mpad, N, K, r.S, r.ksp, e, st);
+    } else if (r.kind == GK_STREAM)
+        rc = dispatch_gemm_bf16<EPI, H>(W, X, part, M, Mpad, N, K, r.S, r.ksp, e, st);
+    else if (r.kind == GK_ROWS)
+        rc = launch_gemm_rows<EPI, H>(W, X, part, M, Mpad, N, K, r.rp, e, st);
+    else if (r.kind == GK_MM)
+        launch_gemm_mm<EPI, H>(W, X, part, M, Mpad, N, K, r, e, st);
+    else if constexpr (EPI == EPI_QKV_ROPE || EPI == EPI_QKV_PLAIN) {
+        if (r.kind != GK_STREAM_W16) return bad();
+        hipLaunchKernelGGL((gemm_bf16_stream_w16<EPI, H, 16>), dim3(N / 16), dim3(1024), 0, st, (const u32x4 *)W, (const H *)X, M, N, K, e);
+    } else
+        return bad();
+    if (rc != SD_OK) return rc;
+    SD_LAUNCH_CHECK();
+    return SD_OK;
+}
+
+// X: [M][K] activations, W: [N][K] weights -> split-K slabs in s->part.  xtab: the lm_head's row gather (NULL: every row in
+// place); one_slab: GN_ONE_SLAB
 template <typename H = bf16_t>
-// one_slab: the caller wants the whole k-range per workgroup where the shape allows it (a tensor-parallel shard's O / down
-// projection: its [M][N] partial then goes to the all-reduce as it is, without a fold launch in between)
 static int run_gemm(sd_session *s, const void *W, const void *X, int M, int N, int K, GemmOut *go, hipStream_t st,
                     const RowTab *xtab = nullptr, bool one_slab = false) {
     const sd_model_config &c = s->m->cfg;
     ProfScope ps(s, PC_GEMM, st);
-    if (is16(c.dtype)) {
-        bool xmap_identity = true;                                // (the tiled and the balanced kernel read whole activation tiles)
-        if (xtab)
-            for (int i = 0; i < M && xmap_identity; ++i) xmap_identity = xtab->xmap[i] == i;
-        if (xmap_identity) xtab = nullptr;                        // every row in place (a verify pass): no gather
-        GemmPlan pl = gemm_plan(N, K, M, xtab == nullptr);                // a row gather (lm_head) keeps the streaming kernel
-        // (<= 16 rows of a shard: one workgroup per n-tile over the whole k-range still gives >= 256 workgroups at hidden >= 4096)
-        if (one_slab && !pl.tiled && M <= 16 && N / 16 >= 256) { pl.S = 1; pl.ksp = K / 32; }
-        const int S = pl.S, ksp = pl.ksp;
-        const int Mpad = (int)align_up(M, 16);
-        SD_REQUIRE((size_t)S * Mpad * N <= s->part_floats, "run_gemm: partial buffer too small");
-        const RowsPlan rp = xmap_identity ? rows_plan(N, K, M, false) : RowsPlan{};
-        if (pl.tiled) {
-            launch_gemm_tiled<H>(W, X, s->part, M, Mpad, N, K, pl, st);
-        } else if (rp.ok) {
-            SD_REQUIRE((size_t)rp.S * Mpad * N <= s->part_floats, "run_gemm: partial buffer too small");
-            GemmEpiT<H> e = {};
-            const int rc = launch_gemm_rows<EPI_PART, H>(W, X, s->part, M, Mpad, N, K, rp, e, st);
-            if (rc != SD_OK) return rc;
-            go->S = rp.S;
-            go->stride_s = (size_t)Mpad * N;
-            SD_LAUNCH_CHECK();
-            return SD_OK;
-        } else {
-            GemmEpiT<H> e = {};
-            if (xtab) { e.use_xmap = 1; e.tab = *xtab; }
-            const int rc = dispatch_gemm_bf16<EPI_PART, H>(W, X, s->part, M, Mpad, N, K, S, ksp, e, st);
-            if (rc != SD_OK) return rc;
-        }
-        go->S = S;
-        go->stride_s = (size_t)Mpad * N;
-    } else {
+    if (!is16(c.dtype)) {
         RowTab none = {};
         hipLaunchKernelGGL(gemm_f32_simple, dim3((N + 3) / 4), dim3(256), 0, st, (const float *)W, (const float *)X,
                            s->part, M, N, K, xtab ? *xtab : none, xtab ? 1 : 0);
+        SD_LAUNCH_CHECK();
         go->S = 1;
         go->stride_s = (size_t)M * N;
+        return SD_OK;
     }
-    SD_LAUNCH_CHECK();
+    bool xmap_identity = true;
+    if (xtab)
+        for (int i = 0; i < M && xmap_identity; ++i) xmap_identity = xtab->xmap[i] == i;
+    if (xmap_identity) xtab = nullptr;                            // every row in place (a verify pass): no gather
+    const GemmRoute r = route_gemm(N, K, M, (xtab ? GN_GATHER : 0) | (one_slab ? GN_ONE_SLAB : 0));
+    const int Mpad = (int)align_up(M, 16);
+    SD_REQUIRE(r.kind != GK_NONE, "internal: no GEMM kernel for %d rows of %d x %d (past the session's row limits)", M, N, K);
+    SD_REQUIRE((size_t)r.S * Mpad * N <= s->part_floats, "run_gemm: partial buffer too small");
+    GemmEpiT<H> e = {};
+    if (xtab) { e.use_xmap = 1; e.tab = *xtab; }
+    const int rc = launch_gemm<EPI_PART, H>(r, W, X, s->part, M, N, K, e, st);
+    if (rc != SD_OK) return rc;
+    go->S = r.S;
+    go->stride_s = (size_t)Mpad * N;
     return SD_OK;
 }
 
 // bf16 GEMM whose workgroups keep the whole k-range (SB = 1) and finish with a fused epilogue
+// (eight waves per tile for a shard's gate/up - 448 n-tiles - measured slower: 5.94 against 5.86 ms per verify)
 template <int EPI, typename H = bf16_t>
 static int run_gemm_fused(sd_session *s, const void *W, const void *X, int M, int N, int K, const GemmEpiT<H> &e,
                           hipStream_t st) {
     ProfScope ps(s, PC_GEMM, st);
-    const int Mpad = (int)align_up(M, 16);
-    // few n-tiles and a long k-range (a tensor-parallel shard's QKV: 80 tiles x K = 8192): sixteen waves per tile
-    if constexpr (EPI == EPI_QKV_ROPE || EPI == EPI_QKV_PLAIN) {
-        if (g_env.wide_qkv && M <= 16 && !e.use_xmap && !e.x_rowmajor && N / 16 <= 128 && K / 32 >= 128) {
-            hipLaunchKernelGGL((gemm_bf16_stream_w16<EPI, H, 16>), dim3(N / 16), dim3(1024), 0, st, (const u32x4 *)W, (const H *)X, M, N, K, e);
-            SD_LAUNCH_CHECK();
-            return SD_OK;
-        }
-    }
-    // a prefill pass past the balanced kernel's row count: gemm_bf16_mm with the epilogue on its accumulators
-    if (!e.use_xmap && !e.x_rowmajor) {
-        const GemmPlan pl = gemm_plan(N, K, M, true, true);
-        if (pl.tiled && pl.mm && pl.S == 1) {
-            launch_gemm_mm<EPI, H>(W, X, nullptr, M, Mpad, N, K, pl, e, st);
-            SD_LAUNCH_CHECK();
-            return SD_OK;
-        }
-    }
-    // (eight waves per tile for a shard's gate/up - 448 n-tiles - measured slower: 5.94 against 5.86 ms per verify)
-    const RowsPlan rp = (e.use_xmap || e.x_rowmajor) ? RowsPlan{} : rows_plan(N, K, M, true);
-    const int rc = rp.ok ? launch_gemm_rows<EPI, H>(W, X, nullptr, M, Mpad, N, K, rp, e, st)
-                         : dispatch_gemm_bf16<EPI, H>(W, X, nullptr, M, Mpad, N, K, 1, K / 32, e, st);
-    if (rc != SD_OK) return rc;
-    SD_LAUNCH_CHECK();
-    return SD_OK;
+    const GemmRoute r = route_gemm(N, K, M, GN_FUSED | (EPI == EPI_QKV_ROPE || EPI == EPI_QKV_PLAIN ? GN_QKV : 0));
+    SD_REQUIRE(r.kind != GK_NONE, "internal: no fused GEMM kernel for %d rows of %d x %d (past the session's row limits)", M, N, K);
+    return launch_gemm<EPI, H>(r, W, X, nullptr, M, N, K, e, st);
 }
 
 // Prefill passes (rows = consecutive positions of a stream) of a 16-bit model with head_dim 128: 16-row groups, both products
@@ -1203,8 +1200,8 @@ static int launch_gemm_xn(sd_session *s, const void *W, const void *X, int M, in
 template <typename H>
 static int launch_gemm_fin(sd_session *s, const void *W, const void *X, int M, int N, int K, const void *bias, hipStream_t st) {
     ProfScope ps(s, PC_GEMM, st);
-    const GemmPlan pl = gemm_plan(N, K, M);
-    SD_REQUIRE(!pl.tiled && M <= 16 && (size_t)pl.S * 16 * N <= s->part_floats, "k-split GEMM with residual epilogue: M=%d N=%d K=%d", M, N, K);
+    const GemmRoute pl = route_gemm(N, K, M, 0);
+    SD_REQUIRE(pl.kind == GK_STREAM && M <= 16 && (size_t)pl.S * 16 * N <= s->part_floats, "k-split GEMM with residual epilogue: M=%d N=%d K=%d", M, N, K);
     GemmEpiT<H> e = {};
     e.bias = (const H *)bias; e.res_x = (H *)s->x; e.res_h = (H *)s->h; e.res_ssq = s->ssq;
     const unsigned want = s->fin_epoch + (unsigned)(pl.S - 1) + (unsigned)s->skew_now;
@@ -1229,8 +1226,9 @@ static int head_logits(sd_session *s, const T *hl, const RowTab *xt, int n_logit
     int rc;
     const int round_t = (c.logits_bf16_round || !llama) ? round_code(c.dtype) : 0;
     const bool zero_tab = !s->head_zero_rows && s->head_zero_n > 0 && s->head_zero_n == n_logits;
+    const GemmRoute hr = route_gemm(c.vocab, ED, n_logits, GN_GATHER);
     if (is16(c.dtype) && s->want_raw_logits && (s->head_zero_rows || zero_tab) && n_logits <= 16 && c.vocab % 16 == 0 &&
-        gemm_plan(c.vocab, ED, n_logits, false).S == 1 && !gemm_plan(c.vocab, ED, n_logits, false).tiled) {
+        hr.kind == GK_STREAM && hr.S == 1) {
         GemmEpiT<H16> e = {};
         if (xt) { e.use_xmap = 1; e.tab = *xt; }
         e.tile_max = s->tile_max; e.zero_rows = s->head_zero_rows; e.zero_ld = s->head_zero_ld;
@@ -1238,8 +1236,7 @@ static int head_logits(sd_session *s, const T *hl, const RowTab *xt, int n_logit
             for (int i = 0; i < n_logits; ++i) e.zero_ptr[i] = s->head_zero_ptr[i];
         {
             ProfScope ps(s, PC_GEMM, st);
-            launch_gemm_bf16<1, EPI_HEAD, 1, H16>(m->w.lm_head, (const H16 *)hl, s->part, n_logits, 16, c.vocab, ED, 1, ED / 32, e, st);
-            SD_LAUNCH_CHECK();
+            if ((rc = launch_gemm<EPI_HEAD, H16>(hr, m->w.lm_head, hl, s->part, n_logits, c.vocab, ED, e, st)) != SD_OK) return rc;
         }
         s->last_logits = s->part; s->last_logits_ld = c.vocab; s->last_logits_round = round_t;
         s->last_tile_max = s->tile_max;
@@ -1459,7 +1456,7 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
     bool qkv0_done = false;
     if constexpr (std::is_same<T, bf16_t>::value) {
         if (g_env.fuse_embed_qkv && fused && pre && (llama || ED == H) && !tab.contig && n_new <= SMALL_MAX_ROWS && H <= 2048 &&
-            H % 32 == 0 && !gemm_plan(qkv_cols(c), H, n_new).tiled) {
+            H % 32 == 0) {
             GemmEpi e = {};
             e.out = (bf16_t *)qb; e.bias = (const bf16_t *)m->bqkv[0];
             e.cos_t = (const bf16_t *)m->w.rope_cos; e.sin_t = (const bf16_t *)m->w.rope_sin;
@@ -1517,8 +1514,8 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
 
     bool xn_d = false;                                                // layer l - 1's down projection left un-normalised rows + partials
     for (int l = 0; l < L; ++l) {
-        // qkv projection -> rope / scale -> q buffer + in-place KV append (fused into the GEMM's epilogue unless the
-        // row count takes the tiled kernel, which leaves slabs for the stand-alone epilogue)
+        // qkv projection -> rope / scale -> q buffer + in-place KV append (fused into the GEMM's epilogue with the fused
+        // weight layout, else slabs for the stand-alone epilogue)
         if (l == 0 && qkv0_done) {
         } else if (xn_d) {
             if constexpr (!std::is_same<T, float>::value) {
@@ -1530,7 +1527,7 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
                 if ((rc = launch_gemm_xn<EPI_QKV_ROPE, H16>(s, m->wqkv[l], h, n_new, qkv_cols(c), H, m->n1w[l], c.norm_eps, e, st)) != SD_OK)
                     return rc;
             }
-        } else if (fused && fused_plan_ok(gemm_plan(qkv_cols(c), H, n_new, true, true))) {
+        } else if (fused) {
             GemmEpiT<H16> e = {};
             e.out = (H16 *)qb; e.bias = (const H16 *)m->bqkv[l];
             e.cos_t = (const H16 *)m->w.rope_cos; e.sin_t = (const H16 *)m->w.rope_sin;
@@ -1552,7 +1549,7 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
         if constexpr (!std::is_same<T, float>::value) {
             if (attn_oproj_ok<T>(s, tab, s_max)) {
                 // the residual add in the O projection's epilogue, the norm in gate/up's operand load (no launch between)
-                xn_o = pre && fused && norm_on_load_ok<T>(s, tab) && !m->bo[l] && !gemm_plan(gu_cols(c), H, n_new).tiled;
+                xn_o = pre && fused && norm_on_load_ok<T>(s, tab) && !m->bo[l];
                 ProfScope ps(s, PC_ATTN, st);
                 if ((rc = launch_attn_oproj<T>(s, qb, tab, l, at, s_max, m->wo[l], xn_o, st)) != SD_OK) return rc;
                 SD_LAUNCH_CHECK();
@@ -1603,7 +1600,7 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
             }
         }
         if (xn_o) {
-        } else if (fused && fused_plan_ok(gemm_plan(gu_cols(c), H, n_new, true, true))) {
+        } else if (fused) {
             GemmEpiT<H16> e = {};
             e.out = (H16 *)ac; e.bias = (const H16 *)m->bfc1[l]; e.n_out = I;
             rc = llama ? run_gemm_fused<EPI_ACT_SILU, H16>(s, m->wgu[l], h, n_new, gu_cols(c), H, e, st)
@@ -1620,8 +1617,7 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
         // normalises on load (no residual+norm launch); the last layer keeps the launch (the final norm feeds the head)
         xn_d = false;
         if constexpr (!std::is_same<T, float>::value) {
-            xn_d = g_env.norm_on_load > 1 && pre && fused && l + 1 < L && norm_on_load_ok<T>(s, tab) && !m->bfc2[l] &&
-                   !gemm_plan(qkv_cols(c), H, n_new).tiled && !gemm_plan(H, I, n_new).tiled;
+            xn_d = g_env.norm_on_load > 1 && pre && fused && l + 1 < L && norm_on_load_ok<T>(s, tab) && !m->bfc2[l];
             if (xn_d && (rc = launch_gemm_fin<H16>(s, m->wdown[l], ac, n_new, H, I, nullptr, st)) != SD_OK) return rc;
         }
         if (xn_d) continue;
@@ -1743,10 +1739,10 @@ extern "C" int sd_session_forward(sd_session *s, const int32_t *tokens, int n_ne
     SD_REQUIRE(n_logits >= 0 && n_logits <= n_new, "sd_session_forward: n_logits=%d of n_new=%d", n_logits, n_new);
     SD_REQUIRE(n_logits == 0 || logits_out, "sd_session_forward: logits_out is null");
     // (logit rows are gathered by the streaming kernel, <= 64 rows per call, unless every row of the call is one)
-    if (n_new > s->max_rows || n_new > SD_MAX_FWD_ROWS || n_logits > (n_logits == n_new ? SD_MAX_ROWS : SD_STREAM_MAX_ROWS) ||
-        pos0 + n_new > s->max_seq) {
+    const int max_logits = n_logits == n_new ? s->max_pass_rows : SD_STREAM_MAX_ROWS;
+    if (n_new > s->max_rows || n_new > SD_MAX_FWD_ROWS || n_logits > max_logits || pos0 + n_new > s->max_seq) {
         sd_set_error("sd_session_forward: n_new=%d (max_rows %d, <=%d), n_logits=%d (<=%d), pos0+n_new=%d (max_seq %d)",
-                     n_new, s->max_rows, SD_MAX_FWD_ROWS, n_logits, SD_MAX_ROWS, pos0 + n_new, s->max_seq);
+                     n_new, s->max_rows, SD_MAX_FWD_ROWS, n_logits, max_logits, pos0 + n_new, s->max_seq);
         return SD_ERR_CAPACITY;
     }
     RowTab tab = {};
@@ -1904,6 +1900,11 @@ extern "C" int sd_batch_forward(const sd_batch_item *items, int n_items, float *
         s_max = std::max(s_max, it.pos0 + it.n_new);
     }
     SD_REQUIRE(nlog == 0 || logits_out, "sd_batch_forward: logits_out is null");
+    const int max_logits = nlog == rows ? s0->max_pass_rows : SD_STREAM_MAX_ROWS;   // (as in sd_session_forward)
+    if (nlog > max_logits) {
+        sd_set_error("sd_batch_forward: %d logit rows of %d exceed one pass (<= %d)", nlog, rows, max_logits);
+        return SD_ERR_CAPACITY;
+    }
     tab.n_rows = rows;
     tab.n_streams = n_items;
     tab.n_logit_rows = nlog;
@@ -1975,51 +1976,20 @@ extern "C" int sd_gemm_bf16(const void *w_packed, const void *x, int x_tiled, in
     refresh_env();
     SD_REQUIRE(M >= 1 && M <= SD_MAX_FWD_ROWS && N % 16 == 0 && K % 32 == 0,
                "sd_gemm_bf16: need 1<=M<=%d, N%%16==0, K%%32==0", SD_MAX_FWD_ROWS);
-    const GemmPlan pl = gemm_plan(N, K, M, x_tiled != 0);
-    int S = pl.S, ksp = pl.ksp;
+    const GemmRoute r = route_gemm(N, K, M, x_tiled ? 0 : GN_ROWMAJOR);
+    SD_REQUIRE(r.kind != GK_NONE, "sd_gemm_bf16: more than 64 rows need the tile layout (x_tiled) and N %% 128 == 0");
     const int Mpad = (int)align_up(M, 16);
-    if (pl.tiled) {
-        SD_REQUIRE((size_t)S * Mpad * N <= part_floats, "sd_gemm_bf16: part buffer needs %zu floats", (size_t)S * Mpad * N);
-        launch_gemm_tiled(w_packed, x, part, M, Mpad, N, K, pl, (hipStream_t)stream);
-        SD_LAUNCH_CHECK();
-        if (out) {
-            hipLaunchKernelGGL(reduce_f32_kernel, dim3((M * N + 255) / 256), dim3(256), 0, (hipStream_t)stream, part, S,
-                               (size_t)Mpad * N, M * N, out);
-            SD_LAUNCH_CHECK();
-        }
-        if (splits_out) *splits_out = S;
-        return SD_OK;
-    }
-    if (x_tiled) {
-        const RowsPlan rp = rows_plan(N, K, M, false);
-        if (rp.ok) {
-            SD_REQUIRE((size_t)rp.S * Mpad * N <= part_floats, "sd_gemm_bf16: part buffer needs %zu floats", (size_t)rp.S * Mpad * N);
-            GemmEpi e0 = {};
-            if (launch_gemm_rows<EPI_PART, bf16_t>(w_packed, x, part, M, Mpad, N, K, rp, e0, (hipStream_t)stream) != SD_OK)
-                return SD_ERR_INVALID;
-            SD_LAUNCH_CHECK();
-            if (out) {
-                hipLaunchKernelGGL(reduce_f32_kernel, dim3((M * N + 255) / 256), dim3(256), 0, (hipStream_t)stream, part, rp.S,
-                                   (size_t)Mpad * N, M * N, out);
-                SD_LAUNCH_CHECK();
-            }
-            if (splits_out) *splits_out = rp.S;
-            return SD_OK;
-        }
-    }
-    SD_REQUIRE(M <= SD_STREAM_MAX_ROWS, "sd_gemm_bf16: more than 64 rows need the tile layout (x_tiled) and N %% 128 == 0");
-    SD_REQUIRE((size_t)S * Mpad * N <= part_floats, "sd_gemm_bf16: part buffer needs %zu floats", (size_t)S * Mpad * N);
+    SD_REQUIRE((size_t)r.S * Mpad * N <= part_floats, "sd_gemm_bf16: part buffer needs %zu floats", (size_t)r.S * Mpad * N);
     hipStream_t st = (hipStream_t)stream;
     GemmEpi e = {};
     e.x_rowmajor = x_tiled ? 0 : 1;
-    if (dispatch_gemm_bf16<EPI_PART>(w_packed, x, part, M, Mpad, N, K, S, ksp, e, st) != SD_OK) return SD_ERR_INVALID;
-    SD_LAUNCH_CHECK();
+    if (launch_gemm<EPI_PART>(r, w_packed, x, part, M, N, K, e, st) != SD_OK) return SD_ERR_INVALID;
     if (out) {
-        hipLaunchKernelGGL(reduce_f32_kernel, dim3((M * N + 255) / 256), dim3(256), 0, st, part, S,
+        hipLaunchKernelGGL(reduce_f32_kernel, dim3((M * N + 255) / 256), dim3(256), 0, st, part, r.S,
                            (size_t)Mpad * N, M * N, out);
         SD_LAUNCH_CHECK();
     }
-    if (splits_out) *splits_out = S;
+    if (splits_out) *splits_out = r.S;
     return SD_OK;
 }
 
@@ -2332,8 +2302,9 @@ extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, i
                    "sd_spec_batch_generate: the streams' result blocks must be consecutive");
     hipStream_t st = (hipStream_t)stream;
     const int g = gamma, n_err = 3 * g + 1;
-    // streams per target pass (a 16-bit model whose GEMMs cannot take the tiled kernel carries 64 rows per forward, not 80)
-    const int pass_rows = std::min({max_rows_per_forward, streams[0].target ? streams[0].target->max_rows : max_rows_per_forward, SD_MAX_ROWS});
+    // streams per target pass (every verify row is a logit row: sd_model_max_pass_rows, 64 for a model whose lm_head or
+    // per-layer GEMMs stop at the streaming kernel)
+    const int pass_rows = std::min(max_rows_per_forward, streams[0].target ? streams[0].target->max_pass_rows : SD_MAX_ROWS);
     const int max_verify = std::max(1, pass_rows / (g + 1));
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_done = nullptr;
     if (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess ||

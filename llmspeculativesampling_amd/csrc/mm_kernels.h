@@ -4,7 +4,7 @@
 //
 //     part[sb][m][n] = sum_{k in slab sb} X[m][k] * W[n][k]        (or, with ONE slab, the fused QKV / SiLU / ReLU epilogue)
 //
-// gemm_bf16_tiled (model_kernels.h) moves every tile global -> registers -> LDS and synchronises the workgroup around each
+// The round-3 LDS-tiled kernel it replaced moved every tile global -> registers -> LDS and synchronised the workgroup around each
 // 64-column k-step with nothing in flight across the barrier: 610-650 TFLOP/s at 256 rows (a quarter of the dense bf16
 // peak).  This kernel keeps the same 1 KiB fragment tiles of W and X (both operands are stored in MFMA fragment order, so
 // one global_load_lds_dwordx4 per wave moves one tile and a lane's ds_read_b128 at 16 * lane is conflict-free), and changes

@@ -555,92 +555,6 @@ __global__ __launch_bounds__(NW * 64) void gemm_bf16_stream_w16(const u32x4 *__r
     if (threadIdx.x < 64) gemm_epilogue_fold<1, EPI, 1, 1, H>(folded, 0, (float *)nullptr, M, 16, N, 0, ntg, e, (int)threadIdx.x);
 }
 
-// ------------------------------------------------------------------------------------------
-// Many-row GEMM (prefill, wide stream batches): part[sb][m][n] = sum_{k in slab sb} X[m][k] * W[n][k]
-// One workgroup = 2 x 2 waves on a (2*NTWV n-tiles) x (2*MTW m-tiles) block of the output; per k-step (32 columns of
-// K) its W and X tiles - both already stored in MFMA fragment order, 1 KiB each - are copied once into LDS (double
-// buffered) and every wave reads the fragments of its quadrant from there, so a W tile feeds 2*MTW and an X tile
-// 2*NTWV MFMAs per global load instead of MTW / NTW in the streaming kernel.  No in-workgroup k-split: the k-range is
-// cut across workgroups (slabs) only when the block count is too small.
-// ------------------------------------------------------------------------------------------
-template <int MTW, int NTWV, int KT, typename H = bf16_t>
-__global__ __launch_bounds__(256) void gemm_bf16_tiled(const u32x4 *__restrict__ Wp, const u32x4 *__restrict__ Xp,
-                                                      float *__restrict__ part, int M, int Mpad, int N, int K, int SB,
-                                                      int ks_per_blk) {
-    constexpr int WT = 2 * NTWV, XT = 2 * MTW, TT = WT + XT;      // tiles per k-tile column: W, X, total
-    constexpr int NL = TT * KT;                                   // tiles per k-step (KT k-tiles = 32*KT columns of K)
-    constexpr int LPT = (NL + 3) / 4;                             // tile loads per wave per k-step
-    extern __shared__ __attribute__((aligned(16))) char dyn_smem[];
-    u32x4 (*sm)[NL][64] = reinterpret_cast<u32x4 (*)[NL][64]>(dyn_smem);          // [2][NL][64]
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), wn = wv & 1, wm = wv >> 1;
-    const int KS = K >> 5, NB = (N >> 4) / WT, MB = ((Mpad >> 4) + XT - 1) / XT;
-    int b = blockIdx.x;
-    const int mb = b % MB; b /= MB;                               // m-blocks of one n-block are neighbours (W reuse in L2)
-    const int nb = b % NB, sb = b / NB;
-    const int nt0 = nb * WT, mt0 = mb * XT, mt_end = Mpad >> 4;
-    const int kb0 = sb * ks_per_blk, kb1 = min(KS, kb0 + ks_per_blk);      // ks_per_blk is a multiple of KT
-    // slot i of a k-step: kk = i / TT (k-tile inside the step), tt = i % TT: tt < WT -> W tile nt0 + tt, else X tile
-    // mt0 + tt - WT; wave wv copies slots wv, wv + 4, ...
-    const u32x4 *src[LPT];
-    bool ok[LPT], isw[LPT];
-#pragma unroll
-    for (int r = 0; r < LPT; ++r) {
-        const int i = wv + 4 * r, kk = i / TT, tt = i - kk * TT;
-        isw[r] = tt < WT;
-        ok[r] = i < NL && (isw[r] || mt0 + tt - WT < mt_end);
-        src[r] = !ok[r] ? Wp : (isw[r] ? Wp + ((size_t)(nt0 + tt) * KS + kb0 + kk) * 64 + lane
-                                       : Xp + ((size_t)(mt0 + tt - WT) * KS + kb0 + kk) * 64 + lane);
-    }
-    f32x4 acc[NTWV][MTW];
-#pragma unroll
-    for (int j = 0; j < NTWV; ++j)
-#pragma unroll
-        for (int t = 0; t < MTW; ++t) acc[j][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    u32x4 stage[LPT];
-    auto fetch = [&]() {
-#pragma unroll
-        for (int r = 0; r < LPT; ++r) {
-            stage[r] = ok[r] ? (isw[r] ? __builtin_nontemporal_load(src[r]) : *src[r]) : u32x4{0u, 0u, 0u, 0u};
-            src[r] += (size_t)KT * 64;
-        }
-    };
-    auto put = [&](int buf) {
-#pragma unroll
-        for (int r = 0; r < LPT; ++r)
-            if (wv + 4 * r < NL) sm[buf][wv + 4 * r][lane] = stage[r];
-    };
-    if (kb0 < kb1) { fetch(); put(0); }
-    __syncthreads();
-    int cur = 0;
-    for (int ks = kb0; ks < kb1; ks += KT) {
-        const bool more = ks + KT < kb1;
-        if (more) fetch();                                        // next k-step's tiles travel while this one is multiplied
-#pragma unroll
-        for (int kk = 0; kk < KT; ++kk) {
-            u32x4 wf[NTWV], xf[MTW];
-#pragma unroll
-            for (int j = 0; j < NTWV; ++j) wf[j] = sm[cur][kk * TT + wn * NTWV + j][lane];
-#pragma unroll
-            for (int t = 0; t < MTW; ++t) xf[t] = sm[cur][kk * TT + WT + wm * MTW + t][lane];
-#pragma unroll
-            for (int j = 0; j < NTWV; ++j)
-#pragma unroll
-                for (int t = 0; t < MTW; ++t)
-                    acc[j][t] = mfma16<H>(wf[j], xf[t], acc[j][t]);
-        }
-        if (more) put(cur ^ 1);
-        __syncthreads();
-        cur ^= 1;
-    }
-#pragma unroll
-    for (int j = 0; j < NTWV; ++j)
-#pragma unroll
-        for (int t = 0; t < MTW; ++t) {
-            const int m = (mt0 + wm * MTW + t) * 16 + (lane & 15), n = (nt0 + wn * NTWV + j) * 16 + (lane >> 4) * 4;
-            if (m < M) *reinterpret_cast<f32x4 *>(part + ((size_t)sb * Mpad + m) * N + n) = acc[j][t];
-        }
-}
-
 // fp32 storage (parity runs on small models): one wave per output column, lanes stride K.
 __global__ __launch_bounds__(256) void gemm_f32_simple(const float *__restrict__ W, const float *__restrict__ X,
                                                       float *__restrict__ part, int M, int N, int K, RowTab tab,

@@ -335,6 +335,8 @@ class Session:
         self.model = model
         self.max_seq = int(min(max_seq, model.max_pos))
         self.max_rows = int(min(max_rows, MAX_PREFILL_ROWS, lib.sd_model_max_rows(model.handle)))
+        # rows of a stream-batched pass whose rows are all logit rows (64 where the lm_head has no many-row kernel)
+        self.max_pass_rows = int(min(MAX_ROWS_PER_FORWARD, self.max_rows, lib.sd_model_max_pass_rows(model.handle)))
         dev = model.device
         self.kv_fp8 = kv_dtype == "fp8"
         assert kv_dtype in (None, "fp8"), kv_dtype

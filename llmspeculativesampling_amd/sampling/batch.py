@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .._lib import lib, check, SdAcceptResult, SdBatchStream
-from ..engine import as_specdec_model, _stream, MAX_ROWS_PER_FORWARD, check_token_ids, same_device, batch_prefill
+from ..engine import as_specdec_model, _stream, check_token_ids, same_device, batch_prefill
 from ..noise import DeviceNoise
 from .kvcache_model import KVCacheModel
 
@@ -90,7 +90,8 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
     # the lock-step loop itself runs inside libspecdec (sd_spec_batch_generate): per iteration gamma batched draft steps,
     # the verify passes, the batched accept + residual sample, one copy of the result blocks and one wait - the
     # interpreter sees the finished token buffers and the per-iteration statistics
-    norm_ws = torch.empty(lib.sd_norm_workspace_bytes(MAX_ROWS_PER_FORWARD), dtype=torch.uint8, device=dev)
+    per_pass = streams[0].target._session.max_pass_rows
+    norm_ws = torch.empty(lib.sd_norm_workspace_bytes(per_pass), dtype=torch.uint8, device=dev)
     cu = _stream()
     arr = (SdBatchStream * B)()
     keep = []                                                     # host arrays the native loop writes into
@@ -123,7 +124,7 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
                                      streams[0].draft._probs.stride(0), int(eos_token_id), int(random_seed or 0),
                                      r_const.data_ptr() if r_const is not None else None, draft_m.norm_mode,
                                      target_m.norm_mode, d0.logits.data_ptr(), d0.logits.stride(0), t0.logits.data_ptr(),
-                                     t0.logits.stride(0), norm_ws.data_ptr(), MAX_ROWS_PER_FORWARD,
+                                     t0.logits.stride(0), norm_ws.data_ptr(), per_pass,
                                      v_ms.ctypes.data, v_n.ctypes.data, v_ctx.ctypes.data, n_log, C.byref(c_iters),
                                      C.byref(c_err), cu), "sd_spec_batch_generate")
     if c_err.value:

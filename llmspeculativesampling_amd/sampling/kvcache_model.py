@@ -14,7 +14,7 @@ from typing import Optional
 import torch
 
 from .._lib import lib, check, SdNormRow
-from ..engine import batch_forward, SpecDecModel, Session, as_specdec_model, _stream, MAX_ROWS_PER_FORWARD, MAX_LOGIT_ROWS, check_token_ids
+from ..engine import batch_forward, SpecDecModel, Session, as_specdec_model, _stream, MAX_LOGIT_ROWS, check_token_ids
 from ..noise import HostTorchNoise
 
 
@@ -244,7 +244,7 @@ class KVCacheModel:
             toks[w][cached:S0] = x[w, cached:].to(device=dev, dtype=torch.int32)
         ld_bytes = self._probs.stride(0) * 4
         st = _stream()
-        per_pass = MAX_ROWS_PER_FORWARD
+        per_pass = sess[0].max_pass_rows
         for i in range(gamma):
             upto = S0 + i
             n_new = upto - sess[0].cache_len

@@ -140,9 +140,9 @@ def multi_speculative_sampling(prefix: torch.Tensor, approx_model, target_model,
             approx_calls += 1
             approx_time += process_time_ns() - tt
             tt = process_time_ns()
-            # ---- target over every replica's uncached rows (speculative_sampling.py:1560), <= 64 rows per pass
+            # ---- target over every replica's uncached rows (speculative_sampling.py:1560), <= max_pass_rows per pass
             n_new = L + gamma - target_len
-            per_pass = max(1, MAX_ROWS_PER_FORWARD // n_new)
+            per_pass = max(1, t_ses[0].max_pass_rows // n_new)
             for a in range(0, W, per_pass):
                 grp = list(range(a, min(W, a + per_pass)))
                 for w in grp:

@@ -193,7 +193,13 @@ def test_native_bf16_iteration_bit_equals_python_loop(hip, case, capsys):
         assert 0 < sum(da["acc_len"]) < 4 * len(da["acc_len"])   # partial accepts really occur
 
 
-@pytest.mark.parametrize("case", ["perturbed_g4", "all_accept_g4", "perturbed_g8_two_passes", "seeded_g2", "split_lm_head"])
+# an OPT pair whose vocab (50272 = 3142 column tiles) has no many-row lm_head kernel: 8 streams x 9 rows verify as 7 + 1 streams
+OPT_BF16_CFG = dict(arch="opt", vocab_size=50272, hidden_size=512, ffn_dim=2048, num_hidden_layers=2, num_attention_heads=8,
+                    num_key_value_heads=8, max_position_embeddings=512, do_layer_norm_before=True)
+
+
+@pytest.mark.parametrize("case", ["perturbed_g4", "all_accept_g4", "perturbed_g8_two_passes", "seeded_g2", "split_lm_head",
+                                  "opt50272_g8"])
 def test_stream_batched_bf16_fused_tail_bit_equals_the_dense_tail(hip, case):
     """The lock-step loop's sampling tail (round 4): the draft head leaves tile maxima and clears the streams' probability
     rows (EPI_HEAD with one pointer per stream), the norm + sample runs on them without a logits copy or a candidate pass,
@@ -202,14 +208,14 @@ def test_stream_batched_bf16_fused_tail_bit_equals_the_dense_tail(hip, case):
     under the same Philox seeds every stream's tokens, accepted lengths and acceptance ratios must be bit-equal - bf16
     weights, a vocabulary wide enough for the tile path, streams of different prompt lengths, one of which stops at EOS;
     16 streams x 9 rows need two verify passes (the lists then stay off and the loop takes the dense accept)."""
-    cfg = ModelConfig(**BF16_CFG)
+    cfg = ModelConfig(**(OPT_BF16_CFG if "opt" in case else BF16_CFG))
     dsd = make_state_dict(cfg, 5, dtype=torch.bfloat16)
     tsd = dsd if case.startswith("all_accept") else \
         {k: v.to(torch.bfloat16) for k, v in perturb_state_dict({a: b.float() for a, b in dsd.items()}, 6, 0.05).items()}
     dm = hip.engine.SpecDecModel.from_state_dict(cfg, dsd, dtype=torch.bfloat16)
     tm = dm if case.startswith("all_accept") else hip.engine.SpecDecModel.from_state_dict(cfg, tsd, dtype=torch.bfloat16)
     gamma = 8 if "g8" in case else (2 if "g2" in case else 4)
-    B = 16 if "two_passes" in case else 6
+    B = 16 if "two_passes" in case else (8 if "opt" in case else 6)
     rng = np.random.default_rng(17)
     prompts = [torch.from_numpy(rng.integers(3, cfg.vocab_size, size=(1, 5 + 7 * (i % 5)))).cuda() for i in range(B)]
     seeds = [4100 + i for i in range(B)]

@@ -568,7 +568,7 @@ def test_gemm_bf16_stream_vs_fp32_reference(hip, N, K):
     ref_pack = W.view(N // 16, 16, K // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous().view(N, K)
     assert torch.equal(Wp, ref_pack)
     part = torch.empty(64 * 64 * N, dtype=torch.float32, device="cuda")
-    for M in (1, 5, 16, 17, 33, 40, 64, 100, 128, 200, 256):          # 33+: the LDS-tiled kernel when N % 128 == 0
+    for M in (1, 5, 16, 17, 33, 40, 64, 100, 128, 200, 256):          # 65+: the balanced kernel or gemm_bf16_mm
         x = torch.randn(M, K, device="cuda", generator=g).to(torch.bfloat16)
         out = torch.full((M, N), float("nan"), dtype=torch.float32, device="cuda")
         S = C.c_int(0)
@@ -586,7 +586,7 @@ def test_gemm_bf16_stream_vs_fp32_reference(hip, N, K):
         xpad[:M] = x
         assert torch.equal(xt, xpad.view(Mp // 16, 16, K // 32, 4, 8).permute(0, 2, 3, 1, 4).reshape(-1))
         if M > 64 and (N // 16) % 8 != 0:
-            continue                                                   # more than 64 rows only through the tiled kernel
+            continue                                                   # more than 64 rows only through gemm_bf16_mm
         out2 = torch.full((M, N), float("nan"), dtype=torch.float32, device="cuda")
         hip.L.check(hip.lib.sd_gemm_bf16(Wp.data_ptr(), xt.data_ptr(), 1, M, N, K, part.data_ptr(), part.numel(),
                                          out2.data_ptr(), C.byref(S), _st()))
@@ -699,8 +699,8 @@ def test_forward_long_context_split_keys_vs_oracle(hip, name, dtype):
 @pytest.mark.parametrize("arch", ["llama", "opt"])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
 def test_prefill_chunks_over_64_rows_vs_oracle(hip, dtype, arch):
-    """Single-sequence calls carry up to 256 rows (positions implicit in the row table; bf16: the LDS-tiled many-row
-    GEMM + stand-alone QKV / activation epilogues on the fused weight layout): a 230-token prompt in one call, 300 more
+    """Single-sequence calls carry up to 256 rows (positions implicit in the row table; bf16: the many-row
+    GEMMs with their fused QKV / activation epilogues): a 230-token prompt in one call, 300 more
     in two, then decode steps, against the oracle forward; and the KV rows equal those of 64-row chunks closely."""
     from llmspeculativesampling_amd.config import ModelConfig
     if arch == "llama":

@@ -8,7 +8,7 @@ No bar in this file is set from a measurement of the HIP path:
   order sit at the same distance from the fp32 truth; a kernel that drops a rounding step, a k-step or a mask entry does
   not.  The factor 1.5 is the round-2 test's (depth 2); it is kept, not re-fitted.
 * integer-valued operands make every dot product exact in fp32 in ANY summation order, so the MFMA GEMM kernels (every
-  row-count class of the streaming kernel, the LDS-tiled kernel, the balanced many-row kernel, all split-K folds) must
+  row-count class of the streaming kernel, gemm_bf16_mm, the balanced many-row kernel, all split-K folds) must
   reproduce an integer matmul bit for bit at the production shapes.
 * a toy pair whose GEMMs are exact by construction (sparse few-bit weights) runs the whole native loop through the MFMA
   kernels, the MFMA attention and the fused epilogues token for token against the oracle.
@@ -297,7 +297,7 @@ def _llama13b_layers(depth):
 @pytest.mark.parametrize("verify", [5, 9], ids=["5rows", "9rows"])
 def test_llama13b_shape_verify_at_bench_context_vs_fp32_truth(hip, verify):
     """the oracle check at the BENCH's context length.  2 layers of the 13b layer shape, a 200-row
-    prefill (the LDS-tiled prefill GEMMs, 25 attention groups) and then a 5-row and a 9-row verify at S = 205 / 209 - the
+    prefill (the gemm_bf16_mm prefill GEMMs, 25 attention groups) and then a 5-row and a 9-row verify at S = 205 / 209 - the
     fused attention + O launch with its write-through / counter hand-off (two row groups at 9 rows), both norm-on-load
     seams and the k-split down projection with the residual epilogue at 5 rows, the residual+norm launches at 9 - held to
     the fp32 truth under the 1.5x rule.  Until now that context was only ever compared with the unfused HIP path."""
@@ -315,19 +315,23 @@ def test_llama13b_shape_verify_at_bench_context_vs_fp32_truth(hip, verify):
     _assert_within_reference_error(errs, f"S~200, {verify} rows")
 
 
-@pytest.mark.parametrize("n_streams,gamma", [(8, 4), (12, 4), (8, 2), (8, 8)], ids=["40rows", "60rows", "g2_24rows", "g8_72rows"])
-def test_stream_batched_verify_13b_layer_shape_error_vs_fp32_truth(hip, n_streams, gamma):
+@pytest.mark.parametrize("n_streams,gamma,arch", [(8, 4, "llama"), (12, 4, "llama"), (8, 2, "llama"), (8, 8, "llama"), (8, 8, "opt")],
+                         ids=["40rows", "60rows", "g2_24rows", "g8_72rows", "opt_g8_72rows"])
+def test_stream_batched_verify_13b_layer_shape_error_vs_fp32_truth(hip, n_streams, gamma, arch):
     """Throughput mode at the production layer shape: 8 / 12 streams x (gamma + 1) verify
     rows - 40 / 60 rows at gamma = 4, 24 rows at gamma = 2, 72 rows at gamma = 8 (config 4's sweep) - through a 2-layer model
     with Llama-2-13b's layer shape: the balanced many-row GEMM (gemm_bf16_rows) with its fused QKV / SiLU epilogues,
     per-stream attention groups (two per stream at 9 rows), batched prefill of the prompts - against the oracle run stream
     by stream.  Bar: per stream, the HIP logits' error against an fp32 forward of the same bf16-valued weights is at most
-    1.5x the error of the reference's bf16 arithmetic (the rule of this file).  A pass carries at most
-    engine.MAX_ROWS_PER_FORWARD rows: more streams than fit go through further passes of whole streams, as the native
-    loop does."""
-    cfg = _llama13b_layers(2)
+    1.5x the error of the reference's bf16 arithmetic (the rule of this file).  A pass carries at most the session's
+    max_pass_rows: more streams than fit go through further passes of whole streams, as the native loop does - opt-13b's
+    vocab of 50272 has no many-row lm_head kernel, so its 8 x 9 rows go as 7 + 1 streams."""
+    cfg = _llama13b_layers(2) if arch == "llama" else _opt13b_layers(2)
     q = gamma + 1
-    m = hip.engine.SpecDecModel.synthetic(cfg, seed=9, dtype=torch.bfloat16, max_pos=96)
+
+    def soft_head(name, t):                                       # (OPT's tied head: see test_opt13b_config3_...)
+        return t * 0.0625 if name.endswith("embed_tokens.weight") else t
+    m = hip.engine.SpecDecModel.synthetic(cfg, seed=9, dtype=torch.bfloat16, max_pos=96, transform=soft_head if arch == "opt" else None)
     sd16 = _host_sd(m)
     sd32 = {k: v.float() for k, v in sd16.items()}
     o16, o32 = oracle.RefCausalLM(cfg, sd16), oracle.RefCausalLM(cfg, sd32)
@@ -336,7 +340,7 @@ def test_stream_batched_verify_13b_layer_shape_error_vs_fp32_truth(hip, n_stream
     seqs = [torch.from_numpy(rng.integers(3, cfg.vocab_size, size=(L + q,)).astype(np.int32)).cuda() for L in lens]
     sessions = [m.new_session(96) for _ in lens]
     hip.engine.batch_prefill(sessions, seqs, lens)
-    per_pass = max(1, hip.engine.MAX_ROWS_PER_FORWARD // q)
+    per_pass = max(1, sessions[0].max_pass_rows // q)
     got = torch.cat([hip.engine.batch_forward(sessions[a:a + per_pass], seqs[a:a + per_pass], [q] * len(sessions[a:a + per_pass]),
                                               [q] * len(sessions[a:a + per_pass])).cpu().clone()
                      for a in range(0, n_streams, per_pass)])

@@ -500,6 +500,41 @@ def test_new_entry_points_reject_null_arguments_without_a_gpu():
     assert lib.sd_cand_list_bytes(3) == 3 * (4 + 128 * 4 + 128 * 4) and lib.sd_cand_list_bytes(0) == 0
 
 
+def test_model_row_limits_follow_the_gemm_routes():
+    """sd_model_max_rows / sd_model_max_pass_rows come from the GEMM planner (no GPU: sd_model_create and both queries never
+    read the weights, so placeholder pointers do).  Every bf16 config: 256 rows per call where every per-layer GEMM has a
+    kernel at every row count (the six real configs), else 64; a pass whose rows are all logit rows also needs an lm_head
+    kernel, which OPT's vocab of 50272 (3142 column tiles, not a multiple of 8) only has up to 64 rows."""
+    import ctypes as C
+    from llmspeculativesampling_amd import _lib
+    from llmspeculativesampling_amd.config import load_config
+    lib, P = _lib.lib, 0x1000
+    names = sorted(f[:-5] for f in os.listdir(os.path.join(ROOT, "llmspeculativesampling_amd", "configs")) if f.endswith(".json"))
+    got = {}
+    for name in names:
+        cfg = load_config(name)
+        L = cfg.num_hidden_layers
+        arrays = [(C.c_void_p * L)(*([P] * L)) for _ in range(12)]
+        w = _lib.SdModelWeights()
+        w.embed = w.lm_head = w.final_norm_w = w.pos_embed = w.rope_cos = w.rope_sin = P
+        (w.wqkv, w.bqkv, w.wo, w.bo, w.w_gate_up, w.b_fc1, w.w_down, w.b_fc2, w.norm1_w, w.norm1_b, w.norm2_w,
+         w.norm2_b) = (C.cast(a, C.POINTER(C.c_void_p)) for a in arrays)
+        c = _lib.SdModelConfig(arch=cfg.arch_id, dtype=_lib.SD_BF16, vocab=cfg.vocab_size, hidden=cfg.hidden_size,
+                               inter=cfg.intermediate_size, n_layers=L, n_heads=cfg.num_attention_heads,
+                               n_kv_heads=cfg.num_key_value_heads, head_dim=cfg.head_dim, max_pos=cfg.max_position_embeddings,
+                               opt_pre_ln=int(cfg.do_layer_norm_before), opt_proj_dim=cfg.word_embed_proj_dim or cfg.hidden_size,
+                               norm_eps=1e-5, logits_bf16_round=1, fused_layout=1)
+        h = C.c_void_p()
+        _lib.check(lib.sd_model_create(C.byref(c), C.byref(w), C.byref(h)), "sd_model_create")
+        got[name] = (lib.sd_model_max_rows(h), lib.sd_model_max_pass_rows(h))
+        lib.sd_model_destroy(h)
+    want = {n: (64, 64) for n in names if n.startswith("tiny-")}
+    want.update({"llama-68m": (256, 80), "llama-2-13b": (256, 80), "llama-2-70b": (256, 80),
+                 "opt-125m": (256, 64), "opt-350m": (256, 64), "opt-13b": (256, 64)})
+    assert got == want
+    assert lib.sd_model_max_rows(None) == 0 and lib.sd_model_max_pass_rows(None) == 0
+
+
 def test_local_checkpoint_getter_and_bench_lookup(tmp_path, monkeypatch):
     """SURVEY.md 8(d) / VERDICT r2: SPECDEC_MODEL_DIR.  A checkpoint directory written by save_pretrained is read tensor by
     tensor through safetensors (nothing is executed from the files, nothing is fetched); bench.find_checkpoint resolves the
@@ -546,9 +581,10 @@ def test_host_code_under_address_sanitizer():
     env = dict(os.environ, LD_PRELOAD=rt, SD_LIBSPECDEC=lib, SD_ASAN_CHILD="1",
                ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:exitcode=23")
     sel = ("test_library_exports_every_declared_symbol or test_struct_layouts_match_header or "
-           "test_argument_errors_do_not_need_a_gpu or test_new_entry_points_reject_null_arguments_without_a_gpu")
+           "test_argument_errors_do_not_need_a_gpu or test_new_entry_points_reject_null_arguments_without_a_gpu or "
+           "test_model_row_limits_follow_the_gemm_routes")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-k", sel, "-p", "no:cacheprovider"],
                        env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     out = r.stdout + r.stderr
     assert "AddressSanitizer" not in out, out[-4000:]
-    assert r.returncode == 0 and "4 passed" in out, out[-4000:]
+    assert r.returncode == 0 and "5 passed" in out, out[-4000:]

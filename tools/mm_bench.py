@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Prefill GEMMs (145..256 rows) at the Llama-2-13b layer shapes: gemm_bf16_tiled against gemm_bf16_mm (mm_kernels.h), through the
-public one-off entry sd_gemm_bf16.  Integer-valued operands, so the result must equal an integer matmul bit for bit whatever
+"""Prefill GEMMs (145..256 rows) at the Llama-2-13b layer shapes: gemm_bf16_mm (mm_kernels.h) by block shape and slab count, and
+the balanced kernel at <= 144 rows, through the public one-off entry sd_gemm_bf16.  Integer-valued operands, so the result must equal an integer matmul bit for bit whatever
 the summation order; timings cycle through enough weight copies that nothing is served from the 256 MiB Infinity Cache.
 
     python tools/mm_bench.py [rows ...]            (default rows: 256 192 160)
@@ -72,29 +72,21 @@ if __name__ == "__main__":
         tot = {}
         for name, (N, K) in SHAPES.items():
             W, Wp, x, xt, ref = make(N, K, M)
-            setenv(SD_GEMM_MM=0, SD_MM_MTW=None, SD_MM_S=None, SD_MM_NT=None, SD_GEMM_ROWS_MAX=64, SD_MM_SLABS_MIN=1000)
-            us = run(f"M={M} {name:8s} tiled", N, K, M, Wp, xt, ref)
-            tot.setdefault("tiled", 0.0)
-            tot["tiled"] += us or 0.0
             if M <= 144:
-                setenv(SD_GEMM_ROWS_MAX=None, SD_GEMM_MM=1)      # (the engine's default planner without the k-slab GEMMs on gemm_bf16_mm)
+                setenv(SD_GEMM_ROWS_MAX=None, SD_MM_MTW=None, SD_MM_S=None, SD_MM_SLABS_MIN=1000)   # (the balanced kernel)
                 us = run(f"M={M} {name:8s} rows (balanced kernel)", N, K, M, Wp, xt, ref)
                 tot.setdefault("rows", 0.0)
                 tot["rows"] += us or 0.0
-                setenv(SD_GEMM_ROWS_MAX=64)
             best = None
             for mtw in (4, 2):
-                if mtw == 2 and False:
-                    continue
                 for S in ((0, 1, 2, 3, 4, 6) if name != "gate_up" else (0, 1, 2)):
-                    for nt in (1,):
-                        setenv(SD_GEMM_MM=1, SD_MM_MTW=mtw, SD_MM_S=S or None, SD_MM_SLABS_MIN=1)
-                        us = run(f"M={M} {name:8s} mm mtw={mtw} S={S}", N, K, M, Wp, xt, ref)
-                        if us and (best is None or us < best):
-                            best = us
+                    setenv(SD_GEMM_ROWS_MAX=64, SD_MM_MTW=mtw, SD_MM_S=S or None, SD_MM_SLABS_MIN=1)
+                    us = run(f"M={M} {name:8s} mm mtw={mtw} S={S}", N, K, M, Wp, xt, ref)
+                    if us and (best is None or us < best):
+                        best = us
             tot.setdefault("mm_best", 0.0)
             tot["mm_best"] += best or 0.0
             del W, Wp, x, xt, ref
             torch.cuda.empty_cache()
-        print(f"== M={M}: per layer tiled {tot['tiled']:.1f} us, mm (best per shape) {tot['mm_best']:.1f} us" +
+        print(f"== M={M}: per layer mm (best per shape) {tot['mm_best']:.1f} us" +
               (f", balanced rows kernel {tot['rows']:.1f} us" if "rows" in tot else ""), flush=True)
