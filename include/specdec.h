@@ -157,8 +157,8 @@ int sd_resample(const float *p_hist, const float *q_hist, long ld, int V, int32_
 
 /* sd_accept_scan + sd_resample in ONE launch whose sample works on candidate lists instead of two passes over V.
  * sd_norm_probs_lists is sd_norm_probs that also leaves, per row, the row's non-zero entries (token ids + probabilities;
- * sd_cand_list_bytes(rows) device bytes; a row gets a list when 1 <= top_k <= 64 put it through the candidate path and it
- * holds <= 128 entries, else it is marked list-less).  sd_accept_resample takes the lists of the gamma + 1 TARGET rows of
+ * sd_cand_list_bytes(rows) device bytes; a row gets a list when its kept set was decided on a sorted list - 1 <= top_k <= 64, or
+ * <= 1024 finite survivors of top-k in the general path - and holds <= 128 entries, else it is marked list-less).  sd_accept_resample takes the lists of the gamma + 1 TARGET rows of
  * the iteration (positions L-1 .. L+gamma-1, in order) or NULL; results are bit-identical to the two-kernel form, which
  * it falls back to for a list-less row.  Philox only (seed, draw_scan + i for the uniforms unless r is given; draw_resample). */
 size_t sd_cand_list_bytes(int rows);
@@ -169,6 +169,38 @@ int sd_accept_resample(const float *p_hist, const float *q_hist, long ld, int V,
                        const float *r, uint64_t philox_seed, uint64_t draw_scan, uint64_t draw_resample,
                        sd_accept_result *res, const int *err_flags, int n_err, int dtype_mode, const void *target_lists,
                        void *stream);
+
+/* TEST HOOK, not for production callers: sd_norm_probs_lists with every internal argument of the norm launch passed
+ * through, and the route each row took read back.  cand_lists may be NULL.  tile_max (or NULL): [rows][V / 16] maxima of
+ * the rows' 16-column tiles (NaN where a tile holds one) - the contract the lm_head's epilogue meets; the caller must then
+ * also hand in zero-filled output rows.  filter_only: sd_topk_topp_filter's output instead of probabilities (as that entry launches it:
+ * without workspace, tile maxima or lists).  do_sample (rows == 1): the fused sample of sd_norm_sample.  route_out (device,
+ * rows ints, required): per row an OR of SD_ROUTE_*.  The hook launches instantiations of the norm kernel of its own (the
+ * ones that record the route; production launches carry no trace of it), same source, same results;
+ * bits 16-31 hold the size of the kept set when it was decided on a sorted list. */
+enum {
+    SD_ROUTE_ENTRY_A = 0x1,         /* candidates from the 16-chunk workspace kernel */
+    SD_ROUTE_ENTRY_B = 0x2,         /* candidates from tile maxima */
+    SD_ROUTE_A_CHUNK_CAP = 0x4,     /* gave up: one chunk kept > 192 */
+    SD_ROUTE_A_TOTAL_CAP = 0x8,     /* gave up: the chunks together kept > 1024 */
+    SD_ROUTE_B_TILE_CAP = 0x10,     /* gave up: > 1024 qualifying tiles */
+    SD_ROUTE_B_CAND_CAP = 0x20,     /* gave up: > 1024 candidates inside them */
+    SD_ROUTE_A_SECOND = 0x40,       /* second-level prefilter ran on the gathered list */
+    SD_ROUTE_PREFILTER = 0x80,      /* in-kernel prefilter ran (first entry, or after A / B gave up) */
+    SD_ROUTE_PREFILTER_CAP = 0x100, /* gave up: it kept > 1024 */
+    SD_ROUTE_TOPK_BISECT = 0x200,   /* general top-k by bitwise bisection */
+    SD_ROUTE_TOPP_LIST = 0x400,     /* top-p on a sorted list */
+    SD_ROUTE_TOPP_MASS = 0x800,     /* top-p by mass bisection */
+    SD_ROUTE_CUT_IDX = 0x1000,      /* cut_idx bisection: equal logits straddle the top-p cut */
+    SD_ROUTE_STAGED = 0x2000,       /* row staged in LDS */
+    SD_ROUTE_ERROR = 0x4000,        /* error row */
+    SD_ROUTE_LIST = 0x8000          /* a candidate list was written */
+};
+int sd_norm_probs_debug(const float *logits, int rows, int V, long ld_in, float temperature, int top_k, float top_p,
+                        int bf16_round_logits, float *probs_out, long ld_out, int *err_flag, void *workspace,
+                        void *cand_lists, void *stream, const float *tile_max, int filter_only, int do_sample,
+                        const float *exp_noise, uint64_t philox_seed, uint64_t draw_index, int *tok_out, int *sample_err,
+                        int *route_out);
 
 /* sd_accept_scan + sd_resample for up to 16 independent streams in two launches (stream-batched decode).
  * Per item: its probability arenas, token buffer, prefix length L, the gamma uniforms r (or NULL: Philox
@@ -185,6 +217,11 @@ typedef struct {
     int32_t n_err;
 } sd_accept_item;
 int sd_accept_batch(const sd_accept_item *items, int n_items, long ld, int V, int gamma, int dtype_mode, void *stream);
+/* Internal (the native lock-step loop; exported so that tests can hold it to the oracle): sd_accept_resample for up to 16
+ * streams in ONE launch.  lists[i] = the candidate lists of item i's gamma + 1 target rows, or NULL (dense passes for that
+ * stream).  Device Philox only: an item with exp_noise is refused. */
+int sd_accept_resample_batch(const sd_accept_item *items, int n_items, long ld, int V, int gamma, int dtype_mode,
+                             const void *const *lists, void *stream);
 
 /* Width-w acceptance of multi_speculative_sampling(strategy="iid") (speculative_sampling.py:1592-1640, SURVEY.md 8(f)
  * rank 2): replica w drafted seq_w[L .. L+gamma); replicas are scanned in order, replica w accepts its i-th token iff

@@ -119,6 +119,9 @@ SYMBOLS = [
     ("sd_cand_list_bytes", C.c_size_t, [_I]),
     ("sd_norm_probs_lists", _I, [_VP, _I, _I, _L, _F, _I, _F, _I, _VP, _L, _VP, _VP, _VP, _VP]),
     ("sd_accept_resample", _I, [_VP, _VP, _L, _I, _VP, _I, _I, _VP, _U64, _U64, _U64, _VP, _VP, _I, _I, _VP, _VP]),
+    ("sd_norm_probs_debug", _I, [_VP, _I, _I, _L, _F, _I, _F, _I, _VP, _L, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _U64, _U64,
+                                 _VP, _VP, _VP]),                                     # test hook
+    ("sd_accept_resample_batch", _I, [C.POINTER(SdAcceptItem), _I, _L, _I, _I, _I, _VPP, _VP]),   # internal
     ("sd_spec_batch_generate", _I, [_VP, _I, _I, C.c_float, _I, C.c_float, _I, C.c_long, _I, C.c_uint64, _VP, _I, _I, _VP,
                                     C.c_long, _VP, C.c_long, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
     ("sd_spec_generate", _I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP,

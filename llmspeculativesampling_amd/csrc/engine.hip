@@ -2088,8 +2088,6 @@ size_t sd_norm_candrow_bytes(int rows);
 int sd_norm_batch_tiles(const float *logits, int n_rows, int V, long ld_in, float temperature, int top_k, float top_p,
                         int bf16_round_logits, const sd_norm_row *rows, int sample, void *workspace, const float *tile_max,
                         void *cand_lists, void *stream);
-int sd_accept_resample_batch(const sd_accept_item *items, int n_items, long ld, int V, int gamma, int dtype_mode,
-                             const void *const *lists, void *stream);
 
 // feed seq[from, upto) in chunks of at most max_rows; logits come out for the last n_logits rows, all of them from the
 // final call (a chunk never ends inside the logits rows), so that call's output slab can be handed to the norm as is

@@ -147,6 +147,7 @@ struct NormShared {
     int cidx[MAX_CAND];
     uint32_t skey[MAX_CAND];
     int sidx[MAX_CAND];
+    int route;                 // thread 0's route word (RT_*), kept here so that it costs no register (last: no offset moves)
 };
 
 // Stable descending order of the n (<= MAX_CAND) candidates in ckey/cidx by rank counting -> skey/sidx.
@@ -217,6 +218,23 @@ struct CandRow { CandHdr hdr[NB_SPLIT]; uint2 cand[NB_SPLIT][CAND_CAP]; };
 // native iteration works on instead of two passes over V.
 #define SD_CL_CAP 128
 struct CandList { int n; int idx[SD_CL_CAP]; float prob[SD_CL_CAP]; };
+// Route word of one row (test hook, SD_ROUTE_* in specdec.h): which of norm_probs_kernel's entries and give-ups it took.
+#define RT_ENTRY_A 0x1          // candidates came from norm_cand_kernel's workspace
+#define RT_ENTRY_B 0x2          // candidates came from the head's tile maxima
+#define RT_A_CHUNK_CAP 0x4      // gave up: a chunk kept > CAND_CAP
+#define RT_A_TOTAL_CAP 0x8      // gave up: the chunks together kept > MAX_CAND
+#define RT_B_TILE_CAP 0x10      // gave up: > MAX_CAND qualifying tiles
+#define RT_B_CAND_CAP 0x20      // gave up: > MAX_CAND candidates inside them
+#define RT_A_SECOND 0x40        // second-level prefilter on the gathered list ran
+#define RT_PREFILTER 0x80       // in-kernel prefilter ran
+#define RT_PREFILTER_CAP 0x100  // gave up: it kept > MAX_CAND
+#define RT_TOPK_BISECT 0x200    // general top-k (bitwise bisection) ran
+#define RT_TOPP_LIST 0x400      // top-p decided on a sorted list
+#define RT_TOPP_MASS 0x800      // top-p decided by mass bisection
+#define RT_CUT_IDX 0x1000       // cut_idx bisection ran (equal logits straddle the cut)
+#define RT_STAGED 0x2000        // the row was staged in LDS
+#define RT_ERROR 0x4000         // error row
+#define RT_LIST 0x8000          // a CandList was written; bits 16-31: size of the kept set when it is a list prefix
 
 __global__ __launch_bounds__(256) void norm_cand_kernel(const float *__restrict__ logits, long ld_in, int V,
                                                        float temperature, int top_k, int bf16_round,
@@ -300,7 +318,7 @@ __global__ __launch_bounds__(256) void norm_cand_kernel(const float *__restrict_
 // Fast path (1 <= top_k <= 64, the harness runs k = 20): three passes over the row - stage, compact, write -
 // and everything else on a candidate list of a few dozen entries in LDS.  Any other setting takes the general
 // path (bitwise bisection on the ordered key for top-k, mass bisection for a wide top-p).
-template <bool SAMPLE>
+template <bool SAMPLE, bool ROUTED = false>
 __global__ __launch_bounds__(NT) void norm_probs_kernel(const float *__restrict__ logits, long ld_in, int V,
                                                        float temperature, int top_k, float top_p, int bf16_round,
                                                        int staged, float *__restrict__ out, long ld_out,
@@ -308,7 +326,10 @@ __global__ __launch_bounds__(NT) void norm_probs_kernel(const float *__restrict_
                                                        uint64_t seed, uint64_t draw, int *__restrict__ tok_out,
                                                        int *__restrict__ samp_err, const CandRow *__restrict__ ws,
                                                        NormTab tab, int use_tab, int filter_only,
-                                                       const float *__restrict__ tile_max, CandList *__restrict__ cl_out) {
+                                                       const float *__restrict__ tile_max, CandList *__restrict__ cl_out,
+                                                       int *__restrict__ route) {
+    // route (ROUTED instantiations only - sd_norm_probs_debug's; the production ones compile without a trace of it, an
+    // argument read and one store at the end cost norm_probs_kernel<true> a VGPR): thread 0 leaves the row's route word there
     // tile_max (or NULL): the lm_head's epilogue (EPI_HEAD, model_kernels.h) left the maximum of every 16-column tile
     // of the logits row (NaN when the tile holds one) in tile_max[row][V/16] and cleared the output row; the candidates
     // for 1 <= top_k <= 64 are then found from V/16 maxima + the few tiles that can hold one, without a pass over V.
@@ -342,7 +363,10 @@ __global__ __launch_bounds__(NT) void norm_probs_kernel(const float *__restrict_
     bool fast = false;
     float m = 0.f;
     int bad = 0;
+    if (ROUTED && tid == 0) S.route = 0;
+#define ROUTE(bits) do { if (ROUTED && tid == 0) S.route |= (bits); } while (0)
     if (ws) {
+        ROUTE(RT_ENTRY_A);
         const CandRow &R = ws[row];
         // the 16 chunk headers are fetched by 16 lanes at once (a serial loop would pay 16 L2 round trips)
         if (tid < NB_SPLIT) {
@@ -379,6 +403,7 @@ __global__ __launch_bounds__(NT) void norm_probs_kernel(const float *__restrict_
             if (tid == 0) { S.n_cand = tot; S.kept = 0; }
             __syncthreads();
             if (tot > 128 && top_k <= 64) {
+                ROUTE(RT_A_SECOND);
                 // second-level prefilter on the gathered list (one candidate per thread): every chunk kept at least
                 // its own top-k, so the union is several hundred entries; the same rank-select trick cuts it to a
                 // few dozen before the O(n^2) stable sort
@@ -411,8 +436,10 @@ __global__ __launch_bounds__(NT) void norm_probs_kernel(const float *__restrict_
             m = mx;
         } else {
             bad = 0;
+            ROUTE(over ? RT_A_CHUNK_CAP : RT_A_TOTAL_CAP);
         }
     } else if (tile_max) {
+        ROUTE(RT_ENTRY_B);
         const int NTL = V >> 4;
         const float *tm = tile_max + (size_t)row * NTL;
         constexpr int TPT = 16;                                   // tiles per thread at 256 threads (V <= 65536)
@@ -474,10 +501,12 @@ __global__ __launch_bounds__(NT) void norm_probs_kernel(const float *__restrict_
             }
             __syncthreads();
             if (S.n_cand <= MAX_CAND) fast = true;               // else pathological ties: the general path below
+            else ROUTE(ntl > MAX_CAND ? RT_B_TILE_CAP : RT_B_CAND_CAP);
         }
     }
     STAMP(1);
     const bool use_lds = staged && !fast;
+    if (use_lds) ROUTE(RT_STAGED);
     auto Z = [&](int i) -> float { return use_lds ? zs[i] : load_z(i); };
 
     float mt = -INFINITY;
@@ -522,6 +551,7 @@ __global__ __launch_bounds__(NT) void norm_probs_kernel(const float *__restrict_
         if (tid == 0) {
             if (errp) *errp = 1;
             if (SAMPLE && samp_err) *samp_err = 1;
+            if (ROUTED && route) route[row] = S.route | RT_ERROR;
         }
         return;
     }
@@ -544,6 +574,7 @@ __global__ __launch_bounds__(NT) void norm_probs_kernel(const float *__restrict_
         } else if (k <= 64) {
             // ---- prefilter: a threshold t0 with at least k elements above it.  Each wave takes the k-th
             // largest of its 64 per-thread maxima (rank counting over readlanes); t0 = the largest of those.
+            ROUTE(RT_PREFILTER);
             const uint32_t mk = fkey(mt);
             int rank = 0;
 #pragma unroll 8
@@ -576,9 +607,12 @@ __global__ __launch_bounds__(NT) void norm_probs_kernel(const float *__restrict_
                 n_surv = ns;
                 n_list = n;
                 have_list = true;
+            } else {
+                ROUTE(RT_PREFILTER_CAP);
             }
         }
         if (!have_list) {
+            ROUTE(RT_TOPK_BISECT);
             // general top-k: bitwise bisection on the ordered key
             uint32_t prefix = 0u;
             for (int bit = 31; bit >= 0; --bit) {
@@ -607,34 +641,40 @@ __global__ __launch_bounds__(NT) void norm_probs_kernel(const float *__restrict_
         __syncthreads();
     };
     if (have_list) fill_ev(n_surv);
-    if (top_p > 0.0f) {
-        if (!have_list) {
-            int c = 0;
+    // The general path finishes on a list too whenever <= MAX_CAND finite entries survive top-k - with or without
+    // top-p: list mode sums the softmax denominator serially in rank order, the dense mode below through 1024 strided
+    // partials, and a row that reaches this point only because a fast entry gave up (k = 64, ties past a cap) must come
+    // out bit-identical to the same row through an entry that did not.
+    if (!have_list && (top_p > 0.0f || top_k > 0)) {
+        int c = 0;
+        for (int i = tid; i < V; i += NTX) {
+            const uint32_t kk = fkey(Z(i));
+            c += (kk >= kth && kk > neg_inf_key);
+        }
+        const int n_fin = block_sum_i(c, S.redi);
+        if (n_fin <= MAX_CAND) {
+            __syncthreads();
+            if (tid == 0) S.n_cand = 0;
+            __syncthreads();
             for (int i = tid; i < V; i += NTX) {
                 const uint32_t kk = fkey(Z(i));
-                c += (kk >= kth && kk > neg_inf_key);
-            }
-            const int n_fin = block_sum_i(c, S.redi);
-            if (n_fin <= MAX_CAND) {
-                __syncthreads();
-                if (tid == 0) S.n_cand = 0;
-                __syncthreads();
-                for (int i = tid; i < V; i += NTX) {
-                    const uint32_t kk = fkey(Z(i));
-                    if (kk >= kth && kk > neg_inf_key) {
-                        const int slot = atomicAdd(&S.n_cand, 1);
-                        S.ckey[slot] = kk;
-                        S.cidx[slot] = i;
-                    }
+                if (kk >= kth && kk > neg_inf_key) {
+                    const int slot = atomicAdd(&S.n_cand, 1);
+                    S.ckey[slot] = kk;
+                    S.cidx[slot] = i;
                 }
-                __syncthreads();
-                rank_sort(S, S.n_cand);
-                n_surv = S.n_cand;
-                have_list = true;
-                fill_ev(n_surv);
             }
+            __syncthreads();
+            rank_sort(S, S.n_cand);
+            n_surv = S.n_cand;
+            have_list = true;
+            kept = n_surv;
+            fill_ev(n_surv);
         }
+    }
+    if (top_p > 0.0f) {
         if (have_list) {
+            ROUTE(RT_TOPP_LIST);
             if (tid == 0) {
                 // entries that are already -inf carry no mass and sort last: leave them out
                 int nf = n_surv;
@@ -669,6 +709,7 @@ __global__ __launch_bounds__(NT) void norm_probs_kernel(const float *__restrict_
             // General path (no / very wide top-k): smallest existing value v* whose first tie member is kept,
             // i.e. float(mass strictly above v*) <= top_p, by bisection on the key; then how many of its tie
             // members fit.  Mass is accumulated in double like torch.cumsum does.
+            ROUTE(RT_TOPP_MASS);
             float part = 0.f;
             for (int i = tid; i < V; i += NTX) {
                 const float z = Z(i);
@@ -719,6 +760,7 @@ __global__ __launch_bounds__(NT) void norm_probs_kernel(const float *__restrict_
             cut_key = vstar;
             cut_idx = 0x7fffffff;
             if (mstar < e) {                                      // ties straddle the cut: keep the mstar lowest indices
+                ROUTE(RT_CUT_IDX);
                 int lo_i = 0, hi_i = V - 1;
                 while (lo_i < hi_i) {
                     const int mid = lo_i + ((hi_i - lo_i) >> 1);
@@ -761,7 +803,9 @@ __global__ __launch_bounds__(NT) void norm_probs_kernel(const float *__restrict_
         if (cl && !filter_only && kept <= SD_CL_CAP) {
             for (int c = tid; c < kept; c += NTX) { cl->idx[c] = S.sidx[c]; cl->prob[c] = PL(S.skey[c]); }
             if (tid == 0) cl->n = kept;                           // (same thread as the -1 above: program order)
+            ROUTE(RT_LIST);
         }
+        ROUTE(kept << 16);
         STAMP(5);
         if (SAMPLE) {
             // multinomial(p, 1) == argmax_i p_i / e_i over the support (zero-probability entries give 0 and never
@@ -824,6 +868,8 @@ __global__ __launch_bounds__(NT) void norm_probs_kernel(const float *__restrict_
     }
     STAMP(6);
     if (tid == 0 && errp) *errp = 0;
+    if (ROUTED && tid == 0 && route) route[row] = S.route;
+#undef ROUTE
     (void)n_list;
 }
 
@@ -1118,7 +1164,7 @@ static int launch_norm(const float *logits, int rows, int V, long ld_in, float t
                        int bf16_round_logits, float *probs_out, long ld_out, int *err_flag, bool do_sample,
                        const float *noise, uint64_t seed, uint64_t draw, int *tok_out, int *samp_err, void *workspace,
                        void *stream, const NormTab *tabp = nullptr, int filter_only = 0,
-                       const float *tile_max = nullptr, CandList *cl_out = nullptr) {
+                       const float *tile_max = nullptr, CandList *cl_out = nullptr, int *route = nullptr) {
     NormTab tab = {};
     const int use_tab = tabp != nullptr;
     if (tabp) tab = *tabp;
@@ -1130,6 +1176,10 @@ static int launch_norm(const float *logits, int rows, int V, long ld_in, float t
         SD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(norm_probs_kernel<false>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         SD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(norm_probs_kernel<true>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        SD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(norm_probs_kernel<false, true>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        SD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(norm_probs_kernel<true, true>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
     }
@@ -1152,15 +1202,21 @@ static int launch_norm(const float *logits, int rows, int V, long ld_in, float t
     const int nthr = tile_max ? (g_norm_tile_threads > 0 ? g_norm_tile_threads : tile_threads_env) : NT;
     const int staged_k = tile_max ? 0 : staged;
     const size_t lds_k = tile_max ? base : lds;
-    if (do_sample)
-        hipLaunchKernelGGL(norm_probs_kernel<true>, dim3(rows), dim3(nthr), lds_k, (hipStream_t)stream, logits, ld_in, V,
-                           temperature, top_k, top_p, bf16_round_logits, staged_k, probs_out, ld_out, err_flag, noise,
-                           seed, draw, tok_out, samp_err, (const CandRow *)ws, tab, use_tab, 0, tile_max, cl_out);
-    else
-        hipLaunchKernelGGL(norm_probs_kernel<false>, dim3(rows), dim3(nthr), lds_k, (hipStream_t)stream, logits, ld_in, V,
-                           temperature, top_k, top_p, bf16_round_logits, staged_k, probs_out, ld_out, err_flag,
-                           (const float *)nullptr, (uint64_t)0, (uint64_t)0, (int *)nullptr, (int *)nullptr,
-                           (const CandRow *)ws, tab, use_tab, filter_only, tile_max, cl_out);
+    const float *noise_k = do_sample ? noise : nullptr;
+    int *tok_k = do_sample ? tok_out : nullptr, *serr_k = do_sample ? samp_err : nullptr;
+    const uint64_t seed_k = do_sample ? seed : 0, draw_k = do_sample ? draw : 0;
+    const int filter_k = do_sample ? 0 : filter_only;
+#define NORM_LAUNCH(SAMPLE, ROUTED)                                                                                        \
+    hipLaunchKernelGGL((norm_probs_kernel<SAMPLE, ROUTED>), dim3(rows), dim3(nthr), lds_k, (hipStream_t)stream, logits,     \
+                       ld_in, V, temperature, top_k, top_p, bf16_round_logits, staged_k, probs_out, ld_out, err_flag,      \
+                       noise_k, seed_k, draw_k, tok_k, serr_k, (const CandRow *)ws, tab, use_tab, filter_k, tile_max,      \
+                       cl_out, route)
+    if (route) {                                                  // test hook: the instantiations that record the route
+        if (do_sample) NORM_LAUNCH(true, true); else NORM_LAUNCH(false, true);
+    } else {
+        if (do_sample) NORM_LAUNCH(true, false); else NORM_LAUNCH(false, false);
+    }
+#undef NORM_LAUNCH
     SD_LAUNCH_CHECK();
     return SD_OK;
 }
@@ -1185,6 +1241,23 @@ extern "C" int sd_norm_probs_lists(const float *logits, int rows, int V, long ld
     return launch_norm(logits, rows, V, ld_in, temperature, top_k, top_p, bf16_round_logits, probs_out, ld_out, err_flag,
                        false, nullptr, 0, 0, nullptr, nullptr, workspace, stream, nullptr, 0, nullptr,
                        static_cast<CandList *>(cand_lists));
+}
+
+// Test hook: launch_norm with everything passed through and the rows' route words read back (specdec.h).
+extern "C" int sd_norm_probs_debug(const float *logits, int rows, int V, long ld_in, float temperature, int top_k,
+                                   float top_p, int bf16_round_logits, float *probs_out, long ld_out, int *err_flag,
+                                   void *workspace, void *cand_lists, void *stream, const float *tile_max, int filter_only,
+                                   int do_sample, const float *exp_noise, uint64_t philox_seed, uint64_t draw_index,
+                                   int *tok_out, int *sample_err, int *route_out) {
+    SD_REQUIRE(logits && probs_out && rows >= 0 && V > 0, "sd_norm_probs_debug: bad arguments");
+    SD_REQUIRE(temperature != 0.0f, "sd_norm_probs_debug: temperature must be non-zero");
+    SD_REQUIRE(!do_sample || (rows == 1 && tok_out && !filter_only), "sd_norm_probs_debug: the fused sample takes one row");
+    SD_REQUIRE(route_out, "sd_norm_probs_debug: route_out is required");
+    SD_REQUIRE(!filter_only || (!workspace && !tile_max), "sd_norm_probs_debug: filter_only takes no workspace / tile maxima");
+    if (rows == 0) return SD_OK;
+    return launch_norm(logits, rows, V, ld_in, temperature, top_k, top_p, bf16_round_logits, probs_out, ld_out, err_flag,
+                       do_sample != 0, exp_noise, philox_seed, draw_index, tok_out, sample_err, workspace, stream, nullptr,
+                       filter_only, tile_max, static_cast<CandList *>(cand_lists), route_out);
 }
 
 // top_k_top_p_filter on its own (utils.py:152-179): out = logit where kept, -inf where dropped (out != logits).
@@ -1484,8 +1557,8 @@ extern "C" int sd_multi_resample(const float *p_hist, const float *q_hist, long 
 
 // The lock-step loop's accept scan + residual / bonus sample in ONE launch on the target rows' candidate lists
 // (accept_resample_body per stream; device Philox only - an item with exp_noise is refused).
-int sd_accept_resample_batch(const sd_accept_item *items, int n_items, long ld, int V, int gamma, int dtype_mode,
-                             const void *const *lists, void *stream) {
+extern "C" int sd_accept_resample_batch(const sd_accept_item *items, int n_items, long ld, int V, int gamma, int dtype_mode,
+                                        const void *const *lists, void *stream) {
     SD_REQUIRE(items && lists && n_items >= 1 && n_items <= SD_ACCEPT_BATCH, "sd_accept_resample_batch: 1..%d items", SD_ACCEPT_BATCH);
     SD_REQUIRE(gamma >= 1 && gamma <= 16 && V > 0, "sd_accept_resample_batch: bad gamma / V");
     AcceptTab t = {};
