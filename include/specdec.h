@@ -250,6 +250,31 @@ int sd_multi_resample(const float *p_hist, const float *q_hist, long ld, int V, 
                       const float *exp_noise, uint64_t philox_seed, uint64_t draw_index, sd_accept_result *res,
                       int dtype_mode, void *stream);
 
+/* Internal (the native width-w loop; exported so that tests can hold it to the pair above): sd_accept_multi followed by
+ * sd_multi_resample on the winner's rows in ONE launch - the workgroup that ran the scan picks the winner's arenas itself,
+ * so the host does not read `choice` between the two.  Device Philox only: uniforms (seed, draw_scan + k) unless r is
+ * given, sample noise (seed, draw_resample).  Writes the token at the winner's seq[n + 1] (the `seq` of sd_multi_item is
+ * written through).  `out` and that token are bit-equal to what the two-launch pair leaves. */
+int sd_multi_accept_resample(const sd_multi_item *items, int width, long ld, int V, int L, int gamma, const float *r,
+                             uint64_t philox_seed, uint64_t draw_scan, uint64_t draw_resample, sd_multi_result *out,
+                             int dtype_mode, void *stream);
+
+/* Winner broadcast of one width-w iteration (what multi_speculative_sampling does with rollback(end, choice) and the next
+ * forward's repeat(), kvcache_model.py:180-192, 390-396): ONE launch that reads choice, chosen.n and the all-accept flag
+ * from the DEVICE result block `res` (stream order is the only synchronisation) and copies, from the winner to every other
+ * replica, KV positions [draft_lo, min(L+gamma-1, n+1)) of the draft arenas, [target_lo, all_accept ? L+gamma : n+1) of
+ * the target arenas and the tokens seq[L .. n+2).  Arenas are [planes][max_seq][row_bytes] bytes (planes = n_layers * 2 *
+ * n_kv_heads, row_bytes = head_dim * element size), moved byte-wise, so any element type goes the same way.  Nothing is
+ * copied when the block does not describe this iteration (choice outside [0, width), n outside [L-1, L+gamma-1]).
+ * `items` is a host array of width <= 16 entries; seq_cap = ints each token buffer holds. */
+typedef struct {
+    void *draft_kv, *target_kv;
+    int32_t *seq;
+} sd_multi_adopt_item;
+int sd_multi_adopt(const sd_multi_adopt_item *items, int width, const sd_multi_result *res, int L, int gamma,
+                   int draft_lo, int target_lo, int draft_planes, int draft_max_seq, int draft_row_bytes,
+                   int target_planes, int target_max_seq, int target_row_bytes, int seq_cap, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Decoder model + KV arena           reference sampling/models/modeling_{llama,opt}.py,
  *                                    sampling/kvcache_model.py:141-252 (forward), :359-436 (rollback)
@@ -466,6 +491,39 @@ int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, f
                            float *target_logits, long ld_target_logits, void *norm_workspace, int max_rows_per_forward,
                            float *verify_ms_out, int32_t *verify_streams_out, float *verify_ctx_out, int max_iters_log,
                            int *n_iters_out, int *err_out, void *stream);
+/* The whole loop of multi_speculative_sampling(strategy="iid") (speculative_sampling.py:1379-1716) for the device-RNG mode,
+ * no interpreter between iterations.  `width` replicas, each with its own sessions, token buffer and probability arenas;
+ * per iteration: gamma draft steps (one pass over the draft weights for all replicas each, sampled straight into
+ * seq_w[L+i]), the target over every replica's uncached rows in passes of max_rows_per_forward / n_new replicas,
+ * sd_multi_accept_resample, sd_multi_adopt, ONE async copy of `dev_block` to `host_block` and ONE stream wait.
+ * dev_block (device) / host_block (pinned host), sd_spec_multi_block_bytes(width, gamma) bytes each: the sd_multi_result
+ * followed by the iteration's error words, int32 [width][3*gamma+1] (per replica: gamma draft norm words, gamma draft
+ * sample words, gamma+1 target norm words); the caller zeroes dev_block once.
+ * Philox position (*seed_io, *draw_io), advanced per iteration exactly as the Python loop advances it: width draws per
+ * draft step (replica w of step i: draw + i*width + w), width draws skipped for the target's discarded sample, then -
+ * after a restart at (random_seed, 0) when random_seed != 0, in which case the scan reads r_const (width*gamma device
+ * floats) instead - width*gamma uniforms, then one resample draw.
+ * host_seq (host int32, capacity >= T + gamma + 1) holds the *len_io tokens so far and receives the new ones; the loop
+ * ends when it holds T tokens, when more than ori_eos_cnt EOS are in it (the caller cuts), after max_iters iterations, or
+ * on an error: *err_out 1 = 'prob error' (a draft sample word, or the resample: then the accepted drafts ARE appended, as
+ * the reference has already cut its output there), 2 = 'norm logits error'.  Per iteration i < *n_iters_out:
+ * acc_len_out[i] (-1 for an iteration that ended on an error word: it counts as a call, its scan was not read), p_at_out / q_at_out[i*width*gamma ..] ([w][j], gamma columns), draft_ms_out / target_ms_out[i] (HIP
+ * events; any of the five may be NULL).  Limits: width <= 16, gamma <= 16, 2*width <= max_rows_per_forward (a draft
+ * step may carry two rows per replica); a violation returns SD_ERR_INVALID before anything is launched. */
+typedef struct {
+    sd_session *draft, *target;
+    int32_t *seq;                 /* device int32, seq_cap entries */
+    float *q_hist, *p_hist;       /* probability arenas by absolute position, row stride ld */
+} sd_multi_replica;
+size_t sd_spec_multi_block_bytes(int width, int gamma);
+int sd_spec_multi_generate(const sd_multi_replica *reps, int width, int gamma, float temperature, int top_k, float top_p,
+                           int V, long ld, int seq_cap, int draft_norm_mode, int target_norm_mode, float *draft_logits,
+                           long ld_draft_logits, float *target_logits, long ld_target_logits, void *norm_workspace,
+                           int max_rows_per_forward, void *dev_block, void *host_block, int32_t *host_seq, int *len_io,
+                           int T, int eos_token_id, int ori_eos_cnt, uint64_t *seed_io, uint64_t *draw_io,
+                           uint64_t random_seed, const float *r_const, int *draft_len_io, int *target_len_io,
+                           int max_iters, int32_t *acc_len_out, float *p_at_out, float *q_at_out, float *draft_ms_out,
+                           float *target_ms_out, int *n_iters_out, int *err_out, void *stream);
 /* HIP-event timing of the draft phase and the target (verify) phase of the last iteration, on the launch stream. */
 int sd_spec_timing(sd_spec *sp, int on);
 int sd_spec_last_times(sd_spec *sp, float *draft_ms, float *target_ms);

@@ -45,6 +45,15 @@ class SdMultiItem(C.Structure):
     _fields_ = [("p_hist", C.c_void_p), ("q_hist", C.c_void_p), ("seq", C.c_void_p)]
 
 
+class SdMultiAdoptItem(C.Structure):
+    _fields_ = [("draft_kv", C.c_void_p), ("target_kv", C.c_void_p), ("seq", C.c_void_p)]
+
+
+class SdMultiReplica(C.Structure):
+    _fields_ = [("draft", C.c_void_p), ("target", C.c_void_p), ("seq", C.c_void_p), ("q_hist", C.c_void_p),
+                ("p_hist", C.c_void_p)]
+
+
 class SdBatchStream(C.Structure):
     _fields_ = [("draft", C.c_void_p), ("target", C.c_void_p), ("seq", C.c_void_p), ("q_hist", C.c_void_p),
                 ("p_hist", C.c_void_p), ("err_words", C.c_void_p), ("res_dev", C.c_void_p), ("res_host", C.c_void_p),
@@ -92,6 +101,12 @@ SYMBOLS = [
     ("sd_accept_batch", _I, [C.POINTER(SdAcceptItem), _I, _L, _I, _I, _I, _VP]),
     ("sd_accept_multi", _I, [C.POINTER(SdMultiItem), _I, _L, _I, _I, _VP, _U64, _U64, _VP, _VP]),
     ("sd_multi_resample", _I, [_VP, _VP, _L, _I, _VP, _I, _VP, _U64, _U64, _VP, _I, _VP]),
+    ("sd_multi_accept_resample", _I, [C.POINTER(SdMultiItem), _I, _L, _I, _I, _I, _VP, _U64, _U64, _U64, _VP, _I, _VP]),   # internal
+    ("sd_multi_adopt", _I, [C.POINTER(SdMultiAdoptItem), _I, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP]),
+    ("sd_spec_multi_block_bytes", C.c_size_t, [_I, _I]),
+    ("sd_spec_multi_generate", _I, [C.POINTER(SdMultiReplica), _I, _I, _F, _I, _F, _I, _L, _I, _I, _I, _VP, _L, _VP, _L, _VP, _I,
+                                    _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _U64, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP,
+                                    _VP, _VP, _VP]),
     ("sd_sample", _I, [_VP, _I, _VP, _U64, _U64, _VP, _VP, _I, _VP]),
     ("sd_philox_exp", _I, [_U64, _U64, _I, _VP, _VP]),
     ("sd_philox_uniform", _I, [_U64, _U64, _I, _VP, _VP]),

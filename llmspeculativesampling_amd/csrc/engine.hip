@@ -16,6 +16,7 @@
 #include "prefill_attn.h"
 #include "fused_kernels.h"
 #include "normload_kernels.h"
+#include "multi_kernels.h"
 
 static thread_local char g_err[512] = "";
 void sd_set_error(const char *fmt, ...) {
@@ -2476,5 +2477,220 @@ extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, i
     }
     (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1); (void)hipEventDestroy(ev_done);
     *n_iters_out = iters;
+    return rc;
+}
+
+// ---- the width-w loop of sampling/multi.py in native code (reference speculative_sampling.py:1379-1716, strategy "iid")
+extern "C" int sd_multi_adopt(const sd_multi_adopt_item *items, int width, const sd_multi_result *res, int L, int gamma,
+                              int draft_lo, int target_lo, int draft_planes, int draft_max_seq, int draft_row_bytes,
+                              int target_planes, int target_max_seq, int target_row_bytes, int seq_cap, void *stream) {
+    SD_REQUIRE(items && res && width >= 1 && width <= 16, "sd_multi_adopt: 1..16 replicas");
+    SD_REQUIRE(gamma >= 1 && gamma <= 16 && L >= 1, "sd_multi_adopt: bad gamma / L");
+    SD_REQUIRE(draft_planes >= 0 && target_planes >= 0 && draft_row_bytes > 0 && target_row_bytes > 0 && draft_lo >= 0 &&
+               target_lo >= 0, "sd_multi_adopt: bad arena shape");
+    // the widest ranges the device may derive: draft [lo, L+gamma-1), target [lo, L+gamma), tokens [L, L+gamma+1)
+    SD_REQUIRE((draft_planes == 0 || L + gamma - 1 <= draft_max_seq) && (target_planes == 0 || L + gamma <= target_max_seq) &&
+               L + gamma + 1 <= seq_cap, "sd_multi_adopt: L %d + gamma %d overruns an arena (max_seq %d / %d) or a token buffer (%d)",
+               L, gamma, draft_max_seq, target_max_seq, seq_cap);
+    AdoptTab t = {};
+    for (int w = 0; w < width; ++w) {
+        SD_REQUIRE(items[w].seq && (draft_planes == 0 || items[w].draft_kv) && (target_planes == 0 || items[w].target_kv),
+                   "sd_multi_adopt: replica %d: null pointer", w);
+        t.d_kv[w] = (char *)items[w].draft_kv; t.t_kv[w] = (char *)items[w].target_kv; t.seq[w] = items[w].seq;
+    }
+    if (width == 1) return SD_OK;                                 // nobody to copy to
+    const AdoptArena d = {draft_planes, draft_max_seq, draft_row_bytes, draft_lo};
+    const AdoptArena tg = {target_planes, target_max_seq, target_row_bytes, target_lo};
+    hipLaunchKernelGGL(multi_adopt_kernel, dim3(draft_planes + target_planes + 1, width), dim3(128), 0, (hipStream_t)stream, t, width,
+                       res, L, gamma, d, tg, seq_cap);
+    SD_LAUNCH_CHECK();
+    return SD_OK;
+}
+
+static inline int kv_planes(const sd_session *s) { return s->m->cfg.n_layers * 2 * s->m->cfg.n_kv_heads; }
+static inline int kv_row_bytes(const sd_session *s) { return s->m->cfg.head_dim * (s->kv_fp8 ? 1 : (int)esize(s->m->cfg.dtype)); }
+
+extern "C" size_t sd_spec_multi_block_bytes(int width, int gamma) {
+    if (width < 1 || gamma < 1) return 0;
+    return sizeof(sd_multi_result) + sizeof(int32_t) * (size_t)width * (3 * gamma + 1);
+}
+
+extern "C" int sd_spec_multi_generate(const sd_multi_replica *reps, int width, int gamma, float temperature, int top_k,
+                                      float top_p, int V, long ld, int seq_cap, int draft_norm_mode, int target_norm_mode,
+                                      float *draft_logits, long ld_draft_logits, float *target_logits, long ld_target_logits,
+                                      void *norm_workspace, int max_rows_per_forward, void *dev_block, void *host_block,
+                                      int32_t *host_seq, int *len_io, int T, int eos_token_id, int ori_eos_cnt,
+                                      uint64_t *seed_io, uint64_t *draw_io, uint64_t random_seed, const float *r_const,
+                                      int *draft_len_io, int *target_len_io, int max_iters, int32_t *acc_len_out,
+                                      float *p_at_out, float *q_at_out, float *draft_ms_out, float *target_ms_out,
+                                      int *n_iters_out, int *err_out, void *stream) {
+    SD_REQUIRE(width >= 1 && width <= 16, "sd_spec_multi_generate: width %d outside 1..16", width);
+    SD_REQUIRE(gamma >= 1 && gamma <= 16, "sd_spec_multi_generate: gamma %d outside 1..16", gamma);
+    SD_REQUIRE(reps && draft_logits && target_logits && dev_block && host_block && host_seq && len_io && seed_io && draw_io &&
+               draft_len_io && target_len_io && n_iters_out && err_out, "sd_spec_multi_generate: null argument");
+    SD_REQUIRE(!random_seed || r_const, "sd_spec_multi_generate: random_seed needs its uniforms (r_const)");
+    SD_REQUIRE(V > 0 && ld >= V, "sd_spec_multi_generate: bad V / ld");
+    for (int w = 0; w < width; ++w) {
+        const sd_multi_replica &r = reps[w];
+        SD_REQUIRE(r.draft && r.target && r.seq && r.q_hist && r.p_hist, "sd_spec_multi_generate: replica %d: null pointer", w);
+        SD_REQUIRE(r.draft->m == reps[0].draft->m && r.target->m == reps[0].target->m && r.draft->max_seq == reps[0].draft->max_seq &&
+                   r.target->max_seq == reps[0].target->max_seq && r.draft->kv_fp8 == reps[0].draft->kv_fp8 &&
+                   r.target->kv_fp8 == reps[0].target->kv_fp8, "sd_spec_multi_generate: replica %d: sessions differ from replica 0's", w);
+    }
+    const int g = gamma, W = width, n_err = 3 * g + 1;
+    const int pass_rows = std::min(max_rows_per_forward, reps[0].target->max_pass_rows);
+    SD_REQUIRE(2 * W <= pass_rows && 2 * W <= std::min(reps[0].draft->max_rows, SD_MAX_ROWS),
+               "sd_spec_multi_generate: width %d: a draft step may carry 2 rows per replica, a pass holds %d", W, pass_rows);
+    SD_REQUIRE(g + 1 <= pass_rows, "sd_spec_multi_generate: gamma %d + 1 verify rows exceed one pass (%d rows)", g, pass_rows);
+    SD_REQUIRE(*len_io >= 1 && T + g + 1 <= seq_cap, "sd_spec_multi_generate: token buffers of %d hold T %d + gamma + 1", seq_cap, T);
+    hipStream_t st = (hipStream_t)stream;
+    sd_multi_result *res_dev = (sd_multi_result *)dev_block;
+    int *err_dev = (int *)((char *)dev_block + sizeof(sd_multi_result));
+    const sd_multi_result *res_host = (const sd_multi_result *)host_block;
+    const int *err_host = (const int *)((const char *)host_block + sizeof(sd_multi_result));
+    const size_t block_bytes = sd_spec_multi_block_bytes(W, g);
+    const bool timed = draft_ms_out || target_ms_out;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int i = 0; i < 4; ++i) {
+        const bool ok = i < 3 ? (!timed || hipEventCreate(&ev[i]) == hipSuccess)
+                              : hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) == hipSuccess;
+        if (!ok) {
+            for (int j = 0; j < i; ++j) if (ev[j]) (void)hipEventDestroy(ev[j]);
+            sd_set_error("sd_spec_multi_generate: hipEventCreate failed");
+            return SD_ERR_HIP;
+        }
+    }
+    hipEvent_t ev_done = ev[3];
+    std::vector<sd_batch_item> items;
+    std::vector<sd_norm_row> rows;
+    sd_multi_item mitems[16];
+    sd_multi_adopt_item aitems[16];
+    for (int w = 0; w < W; ++w) {
+        mitems[w].p_hist = reps[w].p_hist; mitems[w].q_hist = reps[w].q_hist; mitems[w].seq = reps[w].seq;
+        aitems[w].draft_kv = reps[w].draft->kv; aitems[w].target_kv = reps[w].target->kv; aitems[w].seq = reps[w].seq;
+    }
+    const int res_mode = target_norm_mode == draft_norm_mode ? target_norm_mode : 0;
+    int len = *len_io, draft_len = *draft_len_io, target_len = *target_len_io, iters = 0, eos_total = ori_eos_cnt;
+    uint64_t seed = *seed_io, draw = *draw_io;
+    *err_out = 0;
+    int rc = SD_OK;
+    while (len < T && iters < max_iters) {
+        const int L = len, d_lo = draft_len, t_lo = target_len;
+        if (!(draft_len >= 0 && draft_len < L && target_len >= 0 && target_len < L + g)) {
+            sd_set_error("sd_spec_multi_generate: cache lengths %d / %d do not fit a sequence of %d tokens", draft_len, target_len, L);
+            rc = SD_ERR_INVALID;
+            break;
+        }
+        // ---- gamma draft steps, all replicas per pass over the draft weights
+        if (timed) SD_LOOP_HIP(hipEventRecord(ev[0], st));
+        for (int i = 0; i < g && rc == SD_OK; ++i) {
+            const int n_new = L + i - draft_len;
+            const uint64_t draw0 = draw;
+            draw += (uint64_t)W;
+            items.assign(W, sd_batch_item{});
+            rows.assign(W, sd_norm_row{});
+            for (int w = 0; w < W; ++w) {
+                items[w].session = reps[w].draft; items[w].seq = reps[w].seq; items[w].pos0 = draft_len;
+                items[w].n_new = n_new; items[w].n_logits = 1;
+                rows[w].probs_out = reps[w].q_hist + (size_t)(L + i - 1) * ld;
+                rows[w].err = err_dev + w * n_err + i;
+                rows[w].exp_noise = nullptr;
+                rows[w].philox_seed = seed;
+                rows[w].draw_index = draw0 + (uint64_t)w;
+                rows[w].tok_out = reps[w].seq + (L + i);
+                rows[w].sample_err = err_dev + w * n_err + g + i;
+            }
+            if ((rc = sd_batch_forward(items.data(), W, draft_logits, ld_draft_logits, stream)) != SD_OK) break;
+            rc = sd_norm_batch(draft_logits, W, V, ld_draft_logits, temperature, top_k, top_p, draft_norm_mode, rows.data(), 1,
+                               norm_workspace, stream);
+            draft_len = L + i;
+        }
+        if (rc != SD_OK) break;
+        if (timed) SD_LOOP_HIP(hipEventRecord(ev[1], st));
+        // ---- the target over every replica's uncached rows, whole replicas per pass
+        const int n_new = L + g - target_len;
+        const int per_pass = std::max(1, pass_rows / n_new);
+        for (int a = 0; a < W && rc == SD_OK; a += per_pass) {
+            const int m = std::min(per_pass, W - a);
+            items.assign(m, sd_batch_item{});
+            rows.clear();
+            for (int j = 0; j < m; ++j) {
+                const sd_multi_replica &r = reps[a + j];
+                items[j].session = r.target; items[j].seq = r.seq; items[j].pos0 = target_len;
+                items[j].n_new = n_new; items[j].n_logits = n_new;
+                for (int k = 0; k < n_new; ++k) {
+                    sd_norm_row row = {};
+                    row.probs_out = r.p_hist + (size_t)(L + g - n_new + k) * ld;
+                    row.err = err_dev + (a + j) * n_err + 2 * g + std::min(k, g);
+                    rows.push_back(row);
+                }
+            }
+            if ((rc = sd_batch_forward(items.data(), m, target_logits, ld_target_logits, stream)) != SD_OK) break;
+            rc = sd_norm_batch(target_logits, (int)rows.size(), V, ld_target_logits, temperature, top_k, top_p, target_norm_mode,
+                               rows.data(), 0, norm_workspace, stream);
+        }
+        if (rc != SD_OK) break;
+        if (timed) SD_LOOP_HIP(hipEventRecord(ev[2], st));
+        draw += (uint64_t)W;                                      // the target's own sample, drawn and thrown away
+        // ---- replica scan + residual / bonus sample (one launch), winner broadcast (one launch), one copy, one wait
+        if (random_seed) { seed = random_seed; draw = 0; }        // the reseed quirk: the stream restarts before the uniforms
+        const uint64_t d_scan = draw;
+        draw += (uint64_t)W * g;
+        const uint64_t d_res = draw++;
+        if ((rc = sd_multi_accept_resample(mitems, W, ld, V, L, g, r_const, seed, d_scan, d_res, res_dev, res_mode, stream)) != SD_OK)
+            break;
+        if ((rc = sd_multi_adopt(aitems, W, res_dev, L, g, d_lo, t_lo, kv_planes(reps[0].draft), reps[0].draft->max_seq,
+                                 kv_row_bytes(reps[0].draft), kv_planes(reps[0].target), reps[0].target->max_seq,
+                                 kv_row_bytes(reps[0].target), seq_cap, stream)) != SD_OK)
+            break;
+        SD_LOOP_HIP(hipMemcpyAsync(host_block, dev_block, block_bytes, hipMemcpyDeviceToHost, st));
+        SD_LOOP_HIP(hipEventRecord(ev_done, st));
+        if ((rc = poll_event(ev_done, "sd_spec_multi_generate")) != SD_OK) break;
+        // error words first, a draft sample word before a norm word (multi.py: the scan's result is not looked at then,
+        // and the resample draw is not taken)
+        bool any = false, samp = false;
+        for (int w = 0; w < W; ++w)
+            for (int i = 0; i < n_err; ++i)
+                if (err_host[w * n_err + i]) { any = true; samp = samp || (i >= g && i < 2 * g); }
+        if (any) {
+            *err_out = samp ? 1 : 2;
+            --draw;
+            if (acc_len_out) acc_len_out[iters] = -1;             // the iteration ran (it counts as a call) but was not scanned
+            ++iters;
+            break;
+        }
+        const sd_accept_result r = res_host->chosen;
+        const int l = r.n_accepted, n = r.n;
+        if (!(res_host->choice >= 0 && res_host->choice < W && l >= 0 && l <= g && n == L + l - 1)) {
+            sd_set_error("sd_spec_multi_generate: inconsistent result block (choice %d, n %d, L %d, accepted %d)", res_host->choice,
+                         n, L, l);
+            rc = SD_ERR_INVALID;
+            break;
+        }
+        if (timed) {
+            float dms = 0.f, tms = 0.f;
+            SD_LOOP_HIP(hipEventElapsedTime(&dms, ev[0], ev[1]));
+            SD_LOOP_HIP(hipEventElapsedTime(&tms, ev[1], ev[2]));
+            if (draft_ms_out) draft_ms_out[iters] = dms;
+            if (target_ms_out) target_ms_out[iters] = tms;
+        }
+        if (acc_len_out) acc_len_out[iters] = l;
+        for (int w = 0; w < W; ++w)
+            for (int i = 0; i < g; ++i) {
+                if (p_at_out) p_at_out[((size_t)iters * W + w) * g + i] = res_host->p_at[w * 16 + i];
+                if (q_at_out) q_at_out[((size_t)iters * W + w) * g + i] = res_host->q_at[w * 16 + i];
+            }
+        ++iters;
+        for (int i = 0; i < l; ++i) host_seq[len++] = r.drafted[i];
+        if (r.flags & 2) { *err_out = 1; break; }                 // the resample raised: the output was already cut to the accepted drafts
+        host_seq[len++] = r.next_token;
+        draft_len = std::min(L + g - 1, n + 1);
+        target_len = (r.flags & 4) ? L + g : n + 1;
+        for (int i = L; i < len; ++i) eos_total += host_seq[i] == eos_token_id;
+        if (eos_total > ori_eos_cnt) break;                       // the caller cuts after the first new EOS
+    }
+    for (int i = 0; i < 4; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]);
+    *len_io = len; *draft_len_io = draft_len; *target_len_io = target_len;
+    *seed_io = seed; *draw_io = draw; *n_iters_out = iters;
     return rc;
 }

@@ -1075,22 +1075,25 @@ struct MultiTab {
     const int32_t *seq[16];
 };
 
-__global__ __launch_bounds__(256) void accept_multi_kernel(MultiTab t, int width, long ld, int L, int gamma,
-                                                          const float *__restrict__ r, uint64_t seed, uint64_t draw,
-                                                          sd_multi_result *__restrict__ out) {
-    __shared__ float sp[256], sq[256];
-    __shared__ int sj[256];
+// The replica scan of accept_multi_kernel, shared with the fused launch below: thread `tid` < 256 gathers entry
+// (w, i) = (tid / 16, tid % 16) into sp / sq / sj, thread 0 runs the data-dependent scan and writes the block.
+__device__ __forceinline__ void accept_multi_body(const MultiTab &t, int width, long ld, int L, int gamma,
+                                                  const float *__restrict__ r, uint64_t seed, uint64_t draw,
+                                                  sd_multi_result *__restrict__ out, float *sp, float *sq, int *sj,
+                                                  int *choice_out) {
     const int tid = threadIdx.x, w = tid >> 4, i = tid & 15;
-    float p = 0.f, q = 0.f;
-    int j = -1;
-    if (w < width && i < gamma) {
-        j = t.seq[w][L + i];
-        p = t.p_hist[w][(size_t)(L + i - 1) * ld + j];
-        q = t.q_hist[w][(size_t)(L + i - 1) * ld + j];
+    if (tid < 256) {
+        float p = 0.f, q = 0.f;
+        int j = -1;
+        if (w < width && i < gamma) {
+            j = t.seq[w][L + i];
+            p = t.p_hist[w][(size_t)(L + i - 1) * ld + j];
+            q = t.q_hist[w][(size_t)(L + i - 1) * ld + j];
+        }
+        sp[tid] = p; sq[tid] = q; sj[tid] = j;
+        out->p_at[tid] = p;
+        out->q_at[tid] = q;
     }
-    sp[tid] = p; sq[tid] = q; sj[tid] = j;
-    out->p_at[tid] = p;
-    out->q_at[tid] = q;
     __syncthreads();
     if (tid != 0) return;
     int k = 0, max_l = 0, choice = 0, all = 0;
@@ -1123,6 +1126,34 @@ __global__ __launch_bounds__(256) void accept_multi_kernel(MultiTab t, int width
         c->q_at[ii] = sq[choice * 16 + ii];
         c->drafted[ii] = sj[choice * 16 + ii];
     }
+    if (choice_out) *choice_out = choice;
+}
+
+__global__ __launch_bounds__(256) void accept_multi_kernel(MultiTab t, int width, long ld, int L, int gamma,
+                                                          const float *__restrict__ r, uint64_t seed, uint64_t draw,
+                                                          sd_multi_result *__restrict__ out) {
+    __shared__ float sp[256], sq[256];
+    __shared__ int sj[256];
+    accept_multi_body(t, width, ld, L, gamma, r, seed, draw, out, sp, sq, sj, nullptr);
+}
+
+// accept_multi_kernel + multi_resample_kernel of one width-w iteration in ONE launch (the native loop of
+// multi_speculative_sampling): the scan above, then resample_body's dense passes on the WINNER's rows, which the
+// workgroup picks itself - the host never learns `choice` between the two.  Same device functions, same order of
+// operations, so the result block and the token at seq_w[n + 1] are bit-equal to the two-launch pair.  Device Philox only.
+__global__ __launch_bounds__(NT) void multi_accept_resample_kernel(MultiTab t, int width, long ld, int V, int L, int gamma,
+                                                                  const float *__restrict__ r, uint64_t seed,
+                                                                  uint64_t draw_scan, uint64_t draw_res,
+                                                                  sd_multi_result *__restrict__ out, int dt) {
+    __shared__ float sp[256], sq[256];
+    __shared__ int sj[256];
+    __shared__ int s_choice;
+    accept_multi_body(t, width, ld, L, gamma, r, seed, draw_scan, out, sp, sq, sj, &s_choice);
+    __threadfence_block();
+    __syncthreads();                                              // publishes the block (resample_body reads chosen.n back)
+    const int choice = s_choice;
+    resample_body<true>(t.p_hist[choice], t.q_hist[choice], ld, V, const_cast<int32_t *>(t.seq[choice]), gamma,
+                        (const float *)nullptr, seed, draw_res, &out->chosen, (int32_t *)nullptr, (const int *)nullptr, 0, dt);
 }
 
 __global__ __launch_bounds__(NT) void resample_batch_kernel(AcceptTab t, long ld, int V, int gamma, int dt) {
@@ -1551,6 +1582,23 @@ extern "C" int sd_multi_resample(const float *p_hist, const float *q_hist, long 
     SD_REQUIRE(p_hist && q_hist && seq && res && V > 0, "sd_multi_resample: bad arguments");
     hipLaunchKernelGGL(multi_resample_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, p_hist, q_hist, ld, V, seq,
                        gamma, exp_noise, philox_seed, draw_index, res, mode_dt(dtype_mode));
+    SD_LAUNCH_CHECK();
+    return SD_OK;
+}
+
+// sd_accept_multi + sd_multi_resample in ONE launch (the native width-w loop; exported so that tests hold it to the pair).
+extern "C" int sd_multi_accept_resample(const sd_multi_item *items, int width, long ld, int V, int L, int gamma,
+                                        const float *r, uint64_t philox_seed, uint64_t draw_scan, uint64_t draw_resample,
+                                        sd_multi_result *out, int dtype_mode, void *stream) {
+    SD_REQUIRE(items && out && width >= 1 && width <= 16, "sd_multi_accept_resample: 1..16 replicas");
+    SD_REQUIRE(gamma >= 1 && gamma <= 16 && L >= 1 && V > 0, "sd_multi_accept_resample: bad gamma / L / V");
+    MultiTab t = {};
+    for (int w = 0; w < width; ++w) {
+        SD_REQUIRE(items[w].p_hist && items[w].q_hist && items[w].seq, "sd_multi_accept_resample: replica %d: bad arguments", w);
+        t.p_hist[w] = items[w].p_hist; t.q_hist[w] = items[w].q_hist; t.seq[w] = items[w].seq;
+    }
+    hipLaunchKernelGGL(multi_accept_resample_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, t, width, ld, V, L, gamma, r,
+                       philox_seed, draw_scan, draw_resample, out, mode_dt(dtype_mode));
     SD_LAUNCH_CHECK();
     return SD_OK;
 }

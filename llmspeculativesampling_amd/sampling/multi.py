@@ -9,18 +9,26 @@ sample ``sd_multi_resample``, and where the reference re-materialises the cache 
 (kvcache_model.py:180-192) and slices it with ``rollback(end, choice)`` (:390-396, 433-436) only the few positions
 written in this iteration are copied from the winner's arenas to the others.
 
+Under device RNG (``DeviceNoise``, not ``verbose``) the whole loop runs inside libspecdec (``sd_spec_multi_generate``): the
+scan and the residual / bonus sample are one launch, the winner broadcast is one launch that reads ``choice`` from the
+device result block, and the host waits once per iteration.  ``SD_MULTI_NATIVE=0`` (read per call) keeps the Python loop
+below under device RNG too; the host-RNG modes always take it.
+
 Same signature, return value, ``details`` keys, RNG draw order and EOS rule.  ``strategy="beam"`` (the reference's
 default) and ``"acc_beam"`` rest on ``beam_sample_with_kv_cache`` (out of scope).
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
+from dataclasses import dataclass
 from time import process_time_ns
 
 import numpy as np
 import torch
 
-from .._lib import lib, check, SdMultiItem, SdMultiResult, SdNormRow, SpecDecError
+from .. import _lib
+from .._lib import lib, check, SdMultiItem, SdMultiReplica, SdMultiResult, SdNormRow, SpecDecError
 from ..engine import as_specdec_model, batch_forward, _stream, MAX_ROWS_PER_FORWARD, check_token_ids, same_device
 from .kvcache_model import KVCacheModel
 from .speculative_sampling import _make_noise
@@ -30,6 +38,94 @@ def _copy_positions(dst_ses, src_ses, lo: int, hi: int) -> None:
     """KV rows [lo, hi) of every layer / head from one replica's arena to another's."""
     if hi > lo:
         dst_ses.kv[:, :, :, lo:hi].copy_(src_ses.kv[:, :, :, lo:hi])
+
+
+def _takes_native_loop(noise, verbose) -> bool:
+    """The rule of speculative_sampling.py:84 plus the switch: device RNG, not verbose, SD_MULTI_NATIVE != 0 (read per call)."""
+    return bool(getattr(noise, "on_device", False)) and not verbose and os.environ.get("SD_MULTI_NATIVE", "1") != "0"
+
+
+def _check_native(rc: int) -> None:
+    """check(), except that a refused argument (width / gamma / row limits) is an engine failure here, never swallowed."""
+    if rc == _lib.SD_ERR_INVALID:
+        raise SpecDecError("sd_spec_multi_generate: " + lib.sd_last_error().decode(errors="replace"))
+    check(rc, "sd_spec_multi_generate")
+
+
+@dataclass
+class _MultiRun:
+    """What both loops of one multi_speculative_sampling call share: the replicas and the call's parameters."""
+    drafts: list
+    targets: list
+    seqs: list
+    T: int
+    gamma: int
+    eos_token_id: int
+    ori_eos: int
+    random_seed: int
+    sampling: tuple          # (temperature, top_k, top_p)
+    norm_ws: torch.Tensor
+    r_const: torch.Tensor
+
+
+def _native_multi_loop(run: _MultiRun, host, cache_len, noise, timed):
+    """Device-RNG mode: ONE call into libspecdec (sd_spec_multi_generate) runs every iteration - draft steps, verify passes,
+    the fused scan + resample launch, the winner broadcast launch, one copy and one stream wait each - and the interpreter
+    sees the finished sequence and the per-iteration statistics.  ``cache_len``: positions both models hold of ``host``."""
+    drafts, targets, seqs, T, gamma = run.drafts, run.targets, run.seqs, run.T, run.gamma
+    draft_m, target_m, W = drafts[0]._model, targets[0]._model, len(drafts)
+    V, ld = target_m.cfg.vocab_size, drafts[0]._probs.stride(0)
+    Tk, Kk, Pk = run.sampling
+    eos_token_id, ori_eos, random_seed, norm_ws, r_const = run.eos_token_id, run.ori_eos, run.random_seed, run.norm_ws, run.r_const
+    draft_len = target_len = cache_len
+    dev = target_m.device
+    d_ses, t_ses = [m._session for m in drafts], [m._session for m in targets]
+    reps = (SdMultiReplica * W)()
+    for w in range(W):
+        reps[w].draft, reps[w].target = d_ses[w].handle, t_ses[w].handle
+        reps[w].seq, reps[w].q_hist, reps[w].p_hist = seqs[w].data_ptr(), drafts[w]._probs.data_ptr(), targets[w]._probs.data_ptr()
+    nbytes = lib.sd_spec_multi_block_bytes(W, gamma)
+    dev_block = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+    host_block = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+    seq_host = np.zeros(T + gamma + 2, dtype=np.int32)
+    seq_host[:len(host)] = host
+    max_iters = max(1, T - len(host))
+    acc_arr = np.zeros(max_iters, dtype=np.int32)
+    p_arr = np.zeros(max_iters * W * gamma, dtype=np.float32)
+    q_arr = np.zeros(max_iters * W * gamma, dtype=np.float32)
+    dms_arr = np.zeros(max_iters, dtype=np.float32)
+    tms_arr = np.zeros(max_iters, dtype=np.float32)
+    c_len, c_dl, c_tl = C.c_int(len(host)), C.c_int(draft_len), C.c_int(target_len)
+    c_seed, c_draw = C.c_uint64(noise.seed), C.c_uint64(noise.draw)
+    c_iters, c_err = C.c_int(0), C.c_int(0)
+    tick = process_time_ns()
+    rc = lib.sd_spec_multi_generate(
+        reps, W, gamma, Tk, Kk, Pk, V, ld, seqs[0].numel(), draft_m.norm_mode, target_m.norm_mode,
+        d_ses[0].logits.data_ptr(), d_ses[0].logits.stride(0), t_ses[0].logits.data_ptr(), t_ses[0].logits.stride(0),
+        norm_ws.data_ptr(), t_ses[0].max_pass_rows, dev_block.data_ptr(), host_block.data_ptr(), seq_host.ctypes.data,
+        C.byref(c_len), T, int(eos_token_id) if eos_token_id is not None else -1, int(ori_eos), C.byref(c_seed),
+        C.byref(c_draw), int(random_seed or 0), r_const.data_ptr() if r_const is not None else None, C.byref(c_dl),
+        C.byref(c_tl), max_iters, acc_arr.ctypes.data, p_arr.ctypes.data, q_arr.ctypes.data,
+        dms_arr.ctypes.data if timed else None, tms_arr.ctypes.data if timed else None, C.byref(c_iters), C.byref(c_err),
+        _stream())
+    other_time = process_time_ns() - tick                             # host CPU time of the call (enqueue + waits + bookkeeping)
+    noise.seed, noise.draw = c_seed.value, c_draw.value
+    for ses in d_ses:
+        ses.cache_len = c_dl.value
+    for ses in t_ses:
+        ses.cache_len = c_tl.value
+    calls = c_iters.value
+    n_acc = calls - 1 if calls and acc_arr[calls - 1] < 0 else calls  # an iteration ended by an error word was not scanned
+    acc_len = acc_arr[:n_acc].tolist()
+    pa = p_arr[:n_acc * W * gamma]
+    qa = q_arr[:n_acc * W * gamma]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = pa / qa                                               # fp32 division, as p[...] / q[...] (:1597)
+    acc_rate = [0 if q == 0 else (1 if a > 1 else a) for a, q in zip(ratio.tolist(), qa.tolist())]
+    approx_time = int(sum(int(v * 1e6) for v in dms_arr[:calls])) if timed else 0
+    target_time = int(sum(int(v * 1e6) for v in tms_arr[:calls])) if timed else 0
+    out = seq_host[:c_len.value].tolist()
+    return rc, c_err.value, out, acc_len, acc_rate, calls, approx_time, target_time, other_time
 
 
 @torch.no_grad()
@@ -80,28 +176,30 @@ def multi_speculative_sampling(prefix: torch.Tensor, approx_model, target_model,
             _copy_positions(t_ses[w], t_ses[0], 0, L0 - 1)
     draft_len = target_len = L0 - 1
 
-    n_err = 2 * gamma + (gamma + 1)                  # draft norm / draft sample / target norm words per replica
-    err = torch.zeros((W, n_err), dtype=torch.int32, device=dev)
-    res_dev = torch.zeros(C.sizeof(SdMultiResult), dtype=torch.uint8, device=dev)
-    res_host = torch.zeros(C.sizeof(SdMultiResult), dtype=torch.uint8).pin_memory()
-    err_host = torch.zeros((W, n_err), dtype=torch.int32).pin_memory()
     norm_ws = torch.empty(lib.sd_norm_workspace_bytes(MAX_ROWS_PER_FORWARD), dtype=torch.uint8, device=dev)
-    q_ptr = [m._probs.data_ptr() for m in drafts]
-    p_ptr = [m._probs.data_ptr() for m in targets]
-    seq_ptr = [s.data_ptr() for s in seqs]
     ld = drafts[0]._probs.stride(0)
-    ld_bytes = ld * 4
-    err_ptr = err.data_ptr()
-    cu = _stream()
     r_const = None
     if random_seed and on_dev:
         g = torch.Generator().manual_seed(int(random_seed))
         r_const = torch.rand(1, generator=g).repeat(W * gamma).to(dev)
-    items = (SdMultiItem * W)()
-    for w in range(W):
-        items[w].p_hist, items[w].q_hist, items[w].seq = p_ptr[w], q_ptr[w], seq_ptr[w]
     Tk, Kk, Pk = float(temperature), int(top_k or 0), float(top_p or 0.0)
-    res_mode = target_m.norm_mode if target_m.norm_mode == draft_m.norm_mode else 0
+    native = _takes_native_loop(noise, verbose)
+    if not native:                                   # the Python loop's own buffers and tables
+        n_err = 2 * gamma + (gamma + 1)              # draft norm / draft sample / target norm words per replica
+        err = torch.zeros((W, n_err), dtype=torch.int32, device=dev)
+        res_dev = torch.zeros(C.sizeof(SdMultiResult), dtype=torch.uint8, device=dev)
+        res_host = torch.zeros(C.sizeof(SdMultiResult), dtype=torch.uint8).pin_memory()
+        err_host = torch.zeros((W, n_err), dtype=torch.int32).pin_memory()
+        q_ptr = [m._probs.data_ptr() for m in drafts]
+        p_ptr = [m._probs.data_ptr() for m in targets]
+        seq_ptr = [s.data_ptr() for s in seqs]
+        ld_bytes = ld * 4
+        err_ptr = err.data_ptr()
+        cu = _stream()
+        items = (SdMultiItem * W)()
+        for w in range(W):
+            items[w].p_hist, items[w].q_hist, items[w].seq = p_ptr[w], q_ptr[w], seq_ptr[w]
+        res_mode = target_m.norm_mode if target_m.norm_mode == draft_m.norm_mode else 0
 
     acc_len, acc_rate = [], []
     approx_time = target_time = other_time = 0
@@ -110,7 +208,26 @@ def multi_speculative_sampling(prefix: torch.Tensor, approx_model, target_model,
     try:
         if len(host) < T:
             check_token_ids(host, V)                                   # nn.Embedding's IndexError, swallowed below
-        while len(host) < T:
+        if native and len(host) < T:
+            run = _MultiRun(drafts, targets, seqs, T, gamma, eos_token_id, ori_eos, random_seed, (Tk, Kk, Pk), norm_ws, r_const)
+            rc, err_code, out, acc_len, acc_rate, approx_calls, approx_time, target_time, other_time = _native_multi_loop(
+                run, host, draft_len, noise, details)
+            target_calls = approx_calls
+            host = out
+            _check_native(rc)
+            if err_code == 1:
+                raise RuntimeError("prob error")                       # reference utils.py:224
+            if err_code == 2:
+                raise RuntimeError("norm logits error")                # reference utils.py:207
+            if sum(1 for x in host if x == eos_token_id) > ori_eos:    # EOS rule (:1688-1695)
+                seen = 0
+                for idx, x in enumerate(host):
+                    if x == eos_token_id:
+                        seen += 1
+                        if seen == ori_eos + 1:
+                            out = host[:idx + 1]
+                            break
+        while not native and len(host) < T:
             L = len(host)
             tt = process_time_ns()
             d_lo, t_lo = draft_len, target_len
