@@ -65,21 +65,6 @@ struct sd_session {
     float *attn_part;   // [groups*splits <= 64][Hq][TQ][D+2] partial attention sums of the split-key path
     float *part;
     size_t part_floats;
-    // native iteration (sd_spec_*): with want_raw_logits a forward whose lm_head ran unsplit leaves the logits in the
-    // GEMM's own output slab (no copy launch) and says where they are and whether they still have to be rounded to bf16
-    int want_raw_logits;
-    const float *last_logits;
-    long last_logits_ld;
-    int last_logits_round;
-    // ... and with head_zero_rows set the head also leaves its tile maxima (last_tile_max, NULL when it could not) and
-    // clears the probability rows head_zero_rows + i * head_zero_ld of its logit rows (see EPI_HEAD)
-    float *head_zero_rows;
-    long head_zero_ld;
-    // (stream-batched pass: the logit rows' probability rows lie in the streams' own arenas - one pointer per logit row,
-    //  head_zero_n of them, instead of head_zero_rows + i * head_zero_ld)
-    float *head_zero_ptr[16];
-    int head_zero_n;
-    const float *last_tile_max;
     // profiling
     int prof_on;
     std::vector<hipEvent_t> ev_pool;
@@ -566,10 +551,6 @@ extern "C" int sd_session_create(sd_model *m, int max_seq, int max_rows, void *k
     s->kv_scale = nullptr;
     s->tp_in = (float *)(s->scratch + p.tp_in);
     s->tp_out = (float *)(s->scratch + p.tp_out);
-    s->head_zero_rows = nullptr;
-    s->head_zero_ld = 0;
-    s->head_zero_n = 0;
-    s->last_tile_max = nullptr;
     s->h = s->scratch + p.h;
     s->h2 = s->scratch + p.h2;
     s->ao_ctr = (unsigned *)(s->scratch + p.aoctr);
@@ -590,8 +571,6 @@ extern "C" int sd_session_create(sd_model *m, int max_seq, int max_rows, void *k
     s->attn_part = (float *)(s->scratch + p.apart);
     s->part = (float *)(s->scratch + p.part);
     s->part_floats = p.part_floats;
-    s->want_raw_logits = 0;
-    s->last_logits = nullptr;
     s->prof_on = 0;
     s->ev_used = 0;
     s->prof_stream = nullptr;
@@ -691,6 +670,22 @@ extern "C" int sd_profile_read(sd_session *s, float *ms_out, int *count_out) {
 struct GemmOut {
     int S;
     size_t stride_s;   // floats between k-slices
+};
+
+// What the caller of ONE forward asks of its lm_head, and what the head answers (the native loops, spec_loops.h).  No
+// request (NULL): logits_kernel writes logits_out.
+struct HeadReq {
+    bool raw;              // a head that ran unsplit leaves the logits in the GEMM's own output slab (no copy launch)
+    float *zero_rows;      // ... and with zero_rows set it also leaves its tile maxima and clears the probability rows
+    long zero_ld;          //     zero_rows + i * zero_ld of its logit rows (see EPI_HEAD)
+    float *zero_ptr[16];   // (stream-batched pass: the logit rows' probability rows lie in the streams' own arenas - one
+    int zero_n;            //  pointer per logit row, zero_n of them, instead of zero_rows + i * zero_ld)
+};
+struct HeadOut {
+    const float *logits;   // where the logit rows are (NULL after a forward without logit rows), their row stride ...
+    long ld;
+    int round;             // ... and whether they still have to be rounded to the weights' 16-bit type (SD_NORM_ROUND_*)
+    const float *tile_max; // the head's tile maxima, NULL when it could not leave them
 };
 
 struct TpLoop {
@@ -1213,47 +1208,55 @@ static int launch_gemm_fin(sd_session *s, const void *W, const void *X, int M, i
     return SD_OK;
 }
 
+// The tail of every head whose accumulators lie in s->part as S slabs: a caller that takes the raw slab gets it as it is
+// when the head ran unsplit, everybody else gets the slabs folded and rounded into logits_out (logits_kernel).
+template <typename T>
+static int head_finish(sd_session *s, const HeadReq *rq, HeadOut *ho, int S, size_t stride_s, int n_logits, float *logits_out,
+                       long ld_logits, hipStream_t st) {
+    const sd_model_config &c = s->m->cfg;
+    const int V = c.vocab, round_t = (c.logits_bf16_round || c.arch != SD_ARCH_LLAMA) ? round_code(c.dtype) : 0;
+    if (rq && rq->raw && ho && S == 1) {                         // (no result struct: nowhere to hand the slab, so fold it)
+        ho->logits = s->part; ho->ld = V; ho->round = round_t;
+        return SD_OK;
+    }
+    ProfScope ps(s, PC_LOGITS, st);
+    hipLaunchKernelGGL((logits_kernel<T>), dim3((V + 255) / 256, n_logits), dim3(256), 0, st, s->part, S, stride_s, V, round_t,
+                       logits_out, ld_logits);
+    SD_LAUNCH_CHECK();
+    if (ho) { ho->logits = logits_out; ho->ld = ld_logits; ho->round = 0; }
+    return SD_OK;
+}
+
 // The lm_head over the (normalised, operand-layout) rows `hl`; xt (or NULL) maps logit row i to its row of hl.  Native
 // iteration: the head also leaves the maximum of every 16-column tile and clears the probability rows, so the
 // normalisation that follows needs no candidate pass over V (EPI_HEAD; whole k-range per workgroup).
 template <typename T>
-static int head_logits(sd_session *s, const T *hl, const RowTab *xt, int n_logits, float *logits_out, long ld_logits, hipStream_t st) {
+static int head_logits(sd_session *s, const T *hl, const RowTab *xt, int n_logits, float *logits_out, long ld_logits,
+                       const HeadReq *rq, HeadOut *ho, hipStream_t st) {
     using H16 = typename std::conditional<std::is_same<T, float>::value, bf16_t, T>::type;
     sd_model *m = s->m;
     const sd_model_config &c = m->cfg;
     const int ED = embed_dim(c);
-    const bool llama = c.arch == SD_ARCH_LLAMA;
-    GemmOut go;
+    GemmOut go = {1, 0};                                         // (what the EPI_HEAD launch leaves: one slab)
     int rc;
-    const int round_t = (c.logits_bf16_round || !llama) ? round_code(c.dtype) : 0;
-    const bool zero_tab = !s->head_zero_rows && s->head_zero_n > 0 && s->head_zero_n == n_logits;
+    const bool zero_tab = rq && !rq->zero_rows && rq->zero_n > 0 && rq->zero_n == n_logits;
     const GemmRoute hr = route_gemm(c.vocab, ED, n_logits, GN_GATHER);
-    if (is16(c.dtype) && s->want_raw_logits && (s->head_zero_rows || zero_tab) && n_logits <= 16 && c.vocab % 16 == 0 &&
+    if (is16(c.dtype) && rq && rq->raw && (rq->zero_rows || zero_tab) && n_logits <= 16 && c.vocab % 16 == 0 &&
         hr.kind == GK_STREAM && hr.S == 1) {
         GemmEpiT<H16> e = {};
         if (xt) { e.use_xmap = 1; e.tab = *xt; }
-        e.tile_max = s->tile_max; e.zero_rows = s->head_zero_rows; e.zero_ld = s->head_zero_ld;
+        e.tile_max = s->tile_max; e.zero_rows = rq->zero_rows; e.zero_ld = rq->zero_ld;
         if (zero_tab)
-            for (int i = 0; i < n_logits; ++i) e.zero_ptr[i] = s->head_zero_ptr[i];
+            for (int i = 0; i < n_logits; ++i) e.zero_ptr[i] = rq->zero_ptr[i];
         {
             ProfScope ps(s, PC_GEMM, st);
             if ((rc = launch_gemm<EPI_HEAD, H16>(hr, m->w.lm_head, hl, s->part, n_logits, c.vocab, ED, e, st)) != SD_OK) return rc;
         }
-        s->last_logits = s->part; s->last_logits_ld = c.vocab; s->last_logits_round = round_t;
-        s->last_tile_max = s->tile_max;
-        return SD_OK;
+        if (ho) ho->tile_max = s->tile_max;
+    } else if ((rc = run_gemm<H16>(s, m->w.lm_head, hl, n_logits, c.vocab, ED, &go, st, xt)) != SD_OK) {
+        return rc;
     }
-    if ((rc = run_gemm<H16>(s, m->w.lm_head, hl, n_logits, c.vocab, ED, &go, st, xt)) != SD_OK) return rc;
-    if (s->want_raw_logits && go.S == 1) {
-        s->last_logits = s->part; s->last_logits_ld = c.vocab; s->last_logits_round = round_t;
-    } else {
-        ProfScope ps(s, PC_LOGITS, st);
-        hipLaunchKernelGGL((logits_kernel<T>), dim3((c.vocab + 255) / 256, n_logits), dim3(256), 0, st, s->part, go.S,
-                           go.stride_s, c.vocab, round_t, logits_out, ld_logits);
-        SD_LAUNCH_CHECK();
-        s->last_logits = logits_out; s->last_logits_ld = ld_logits; s->last_logits_round = 0;
-    }
-    return SD_OK;
+    return head_finish<T>(s, rq, ho, go.S, go.stride_s, n_logits, logits_out, ld_logits, st);
 }
 
 // ---- small-model decode path (small_kernels.h): 5 launches per layer + the head --------------------------------
@@ -1297,7 +1300,8 @@ static int launch_small(sd_session *s, const void *W, const void *X, float *part
 static int launch_attn_bf16(sd_session *s, const bf16_t *q, const RowTab &tab, int layer, bf16_t *out, int s_max,
                             hipStream_t st);
 
-static int forward_small(sd_session *s, const RowTab &tab, int s_max, float *logits_out, long ld_logits, hipStream_t st) {
+static int forward_small(sd_session *s, const RowTab &tab, int s_max, float *logits_out, long ld_logits, const HeadReq *rq,
+                         HeadOut *ho, hipStream_t st) {
     sd_model *m = s->m;
     const sd_model_config &c = m->cfg;
     const int H = c.hidden, D = c.head_dim, I = c.inter, L = c.n_layers, M = tab.n_rows, n_logits = tab.n_logit_rows;
@@ -1384,7 +1388,6 @@ static int forward_small(sd_session *s, const RowTab &tab, int s_max, float *log
             if (rc != SD_OK) return rc;
         }
     }
-    s->last_tile_max = nullptr;
     if (n_logits > 0 && !all_pro) {
         // ---- head: the final residual + norm keeps its launch.  As a prologue of the lm_head every one of its 2000-3142
         // workgroups folds the slabs and normalises the rows for itself: 18.5 us against 4.4 + 9.6 on llama-68m, 31.4 against
@@ -1396,48 +1399,39 @@ static int forward_small(sd_session *s, const RowTab &tab, int s_max, float *log
                                (const bf16_t *)m->w.final_norm_b, c.norm_eps, norm_kind, (int)RES_PRE, (bf16_t *)s->h);
             SD_LAUNCH_CHECK();
         }
-        return head_logits<bf16_t>(s, (const bf16_t *)s->h, &tab, n_logits, logits_out, ld_logits, st);
+        return head_logits<bf16_t>(s, (const bf16_t *)s->h, &tab, n_logits, logits_out, ld_logits, rq, ho, st);
     }
     if (n_logits > 0) {
         // ---- head (SD_SMALL_PATH=2): prologue = last down slabs + residual + final norm on the rows that need logits
         GemmEpi e = {};
         e.use_xmap = 1; e.tab = tab;
         SmallPro p = resid_pro(S_d, (const bf16_t *)m->bfc2[L - 1], m->w.final_norm_w, m->w.final_norm_b, false);
-        const int round_t = (c.logits_bf16_round || !llama) ? round_code(c.dtype) : 0;
         SD_REQUIRE((size_t)16 * c.vocab <= s->part_floats, "forward_small: logits slab too small");
-        if (s->want_raw_logits && s->head_zero_rows && c.vocab % 16 == 0) {
-            e.tile_max = s->tile_max; e.zero_rows = s->head_zero_rows; e.zero_ld = s->head_zero_ld;
+        // (tile maxima only for the loop that names ONE block of probability rows: the per-stream table is head_logits' own)
+        if (rq && rq->raw && rq->zero_rows && c.vocab % 16 == 0) {
+            e.tile_max = s->tile_max; e.zero_rows = rq->zero_rows; e.zero_ld = rq->zero_ld;
             if ((rc = launch_small<PRO_RESID, EPI_HEAD>(s, m->w.lm_head, nullptr, s->part, n_logits, c.vocab, H, 1, H / 32, e, p, st)) != SD_OK) return rc;
-            s->last_tile_max = s->tile_max;
+            if (ho) ho->tile_max = s->tile_max;
         } else {
             if ((rc = launch_small<PRO_RESID, EPI_PART>(s, m->w.lm_head, nullptr, s->part, n_logits, c.vocab, H, 1, H / 32, e, p, st)) != SD_OK) return rc;
         }
-        if (s->want_raw_logits) {
-            s->last_logits = s->part; s->last_logits_ld = c.vocab; s->last_logits_round = round_t;
-        } else {
-            ProfScope ps(s, PC_LOGITS, st);
-            hipLaunchKernelGGL((logits_kernel<bf16_t>), dim3((c.vocab + 255) / 256, n_logits), dim3(256), 0, st, s->part, 1,
-                               (size_t)16 * c.vocab, c.vocab, round_t, logits_out, ld_logits);
-            SD_LAUNCH_CHECK();
-            s->last_logits = logits_out; s->last_logits_ld = ld_logits; s->last_logits_round = 0;
-        }
+        return head_finish<bf16_t>(s, rq, ho, 1, (size_t)16 * c.vocab, n_logits, logits_out, ld_logits, st);
     }
     return SD_OK;
 }
 
 
 template <typename T>
-static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logits_out, long ld_logits,
-                        hipStream_t st) {
+static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logits_out, long ld_logits, const HeadReq *rq,
+                        HeadOut *ho, hipStream_t st) {
     // 16-bit storage type of the MFMA GEMMs (the fp32 instantiation never launches them; it only has to compile)
     using H16 = typename std::conditional<std::is_same<T, float>::value, bf16_t, T>::type;
     const int n_new = tab.n_rows, n_logits = tab.n_logit_rows;
     sd_model *m = s->m;
     const sd_model_config &c = m->cfg;
     if constexpr (std::is_same<T, bf16_t>::value) {
-        if (small_path_ok(s, tab)) return forward_small(s, tab, s_max, logits_out, ld_logits, st);
+        if (small_path_ok(s, tab)) return forward_small(s, tab, s_max, logits_out, ld_logits, rq, ho, st);
     }
-    s->last_tile_max = nullptr;
     const int H = c.hidden, D = c.head_dim, I = c.inter, L = c.n_layers, ED = embed_dim(c);
     const bool llama = c.arch == SD_ARCH_LLAMA;
     const int norm_kind = llama ? NORM_RMS : NORM_LN;
@@ -1655,7 +1649,7 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
             SD_LAUNCH_CHECK();
             hl = eb;
         }
-        return head_logits<T>(s, hl, xt, n_logits, logits_out, ld_logits, st);
+        return head_logits<T>(s, hl, xt, n_logits, logits_out, ld_logits, rq, ho, st);
     }
     return SD_OK;
 }
@@ -1709,8 +1703,10 @@ static int launch_attn_bf16(sd_session *s, const bf16_t *q, const RowTab &tab, i
     }
 }
 
-static int run_forward(sd_session *s, const RowTab &tab, int s_max, float *logits_out, long ld_logits, void *stream) {
+static int run_forward(sd_session *s, const RowTab &tab, int s_max, float *logits_out, long ld_logits, const HeadReq *rq,
+                       HeadOut *ho, void *stream) {
     int rc;
+    if (ho) *ho = HeadOut{};                                     // (a forward without logit rows leaves it empty)
     if (s->resync) {
         // the previous forward of this session failed part-way (or ran with a test skew): its fused launches' arrival counters
         // and the host's epochs may disagree, and every later wait would then run into its 20 ms limit.  Stream-ordered
@@ -1723,18 +1719,18 @@ static int run_forward(sd_session *s, const RowTab &tab, int s_max, float *logit
     s->skew_now = s->test_skew;
     s->test_skew = 0;
     if (s->m->cfg.dtype == SD_BF16)
-        rc = forward_impl<bf16_t>(s, tab, s_max, logits_out, ld_logits, (hipStream_t)stream);
+        rc = forward_impl<bf16_t>(s, tab, s_max, logits_out, ld_logits, rq, ho, (hipStream_t)stream);
     else if (s->m->cfg.dtype == SD_F16)
-        rc = forward_impl<f16_t>(s, tab, s_max, logits_out, ld_logits, (hipStream_t)stream);
+        rc = forward_impl<f16_t>(s, tab, s_max, logits_out, ld_logits, rq, ho, (hipStream_t)stream);
     else
-        rc = forward_impl<float>(s, tab, s_max, logits_out, ld_logits, (hipStream_t)stream);
+        rc = forward_impl<float>(s, tab, s_max, logits_out, ld_logits, rq, ho, (hipStream_t)stream);
     if (rc != SD_OK || s->skew_now) s->resync = 1;
     s->skew_now = 0;
     return rc;
 }
 
-extern "C" int sd_session_forward(sd_session *s, const int32_t *tokens, int n_new, int pos0, int n_logits,
-                                  float *logits_out, long ld_logits, void *stream) {
+static int session_forward(sd_session *s, const int32_t *tokens, int n_new, int pos0, int n_logits, float *logits_out,
+                           long ld_logits, const HeadReq *rq, HeadOut *ho, void *stream) {
     SD_REQUIRE(s && tokens, "sd_session_forward: null argument");
     SD_REQUIRE(n_new >= 1 && pos0 >= 0, "sd_session_forward: n_new=%d pos0=%d", n_new, pos0);
     SD_REQUIRE(n_logits >= 0 && n_logits <= n_new, "sd_session_forward: n_logits=%d of n_new=%d", n_logits, n_new);
@@ -1763,7 +1759,12 @@ extern "C" int sd_session_forward(sd_session *s, const int32_t *tokens, int n_ne
     }
     for (int i = 0; i < n_logits; ++i) tab.xmap[i] = (unsigned char)(n_new - n_logits + i);   // n_new <= 256
     finish_table(tab);
-    return run_forward(s, tab, pos0 + n_new, logits_out, ld_logits, stream);
+    return run_forward(s, tab, pos0 + n_new, logits_out, ld_logits, rq, ho, stream);
+}
+
+extern "C" int sd_session_forward(sd_session *s, const int32_t *tokens, int n_new, int pos0, int n_logits,
+                                  float *logits_out, long ld_logits, void *stream) {
+    return session_forward(s, tokens, n_new, pos0, n_logits, logits_out, ld_logits, nullptr, nullptr, stream);
 }
 
 // Tree verify (reference kvcache_model.py:38-136 forward_tree_attention + modeling_llama.py:684-689): the n rows are
@@ -1800,7 +1801,7 @@ extern "C" int sd_session_forward_tree(sd_session *s, const int32_t *tokens, con
         tab.xmap[i] = (unsigned char)i;
     }
     finish_table(tab);
-    return run_forward(s, tab, base_len + n, logits_out, ld_logits, stream);
+    return run_forward(s, tab, base_len + n, logits_out, ld_logits, nullptr, nullptr, stream);
 }
 
 // Gather-compaction of the KV arena after a tree verify (reference kvcache_model.py:326-353 rollback_tree_attention,
@@ -1869,8 +1870,8 @@ extern "C" int sd_session_compact_kv(sd_session *s, int base_len, const int32_t 
 // over the weights.  Every item names its own session (KV arena), token buffer (device int32, indexed by absolute
 // position), cache length pos0, number of new rows and how many of its last rows need logits.  Activations use
 // items[0].session's scratch; all sessions must belong to the same model.  Logit rows come out packed in item order.
-extern "C" int sd_batch_forward(const sd_batch_item *items, int n_items, float *logits_out, long ld_logits,
-                                void *stream) {
+static int batch_forward(const sd_batch_item *items, int n_items, float *logits_out, long ld_logits, const HeadReq *rq,
+                         HeadOut *ho, void *stream) {
     SD_REQUIRE(items && n_items >= 1 && n_items <= SD_MAX_STREAMS, "sd_batch_forward: 1..%d items", SD_MAX_STREAMS);
     sd_session *s0 = items[0].session;
     SD_REQUIRE(s0, "sd_batch_forward: null session");
@@ -1910,7 +1911,12 @@ extern "C" int sd_batch_forward(const sd_batch_item *items, int n_items, float *
     tab.n_streams = n_items;
     tab.n_logit_rows = nlog;
     finish_table(tab);
-    return run_forward(s0, tab, s_max, logits_out, ld_logits, stream);
+    return run_forward(s0, tab, s_max, logits_out, ld_logits, rq, ho, stream);
+}
+
+extern "C" int sd_batch_forward(const sd_batch_item *items, int n_items, float *logits_out, long ld_logits,
+                                void *stream) {
+    return batch_forward(items, n_items, logits_out, ld_logits, nullptr, nullptr, stream);
 }
 
 // Batched prefill (throughput mode): the prompts of several streams through ONE pass over the weights - up to
@@ -1952,7 +1958,7 @@ extern "C" int sd_batch_prefill(const sd_batch_item *items, int n_items, void *s
     tab.n_streams = n_items;
     tab.n_logit_rows = 0;
     finish_table(tab);
-    return run_forward(s0, tab, s_max, nullptr, 0, stream);
+    return run_forward(s0, tab, s_max, nullptr, 0, nullptr, nullptr, stream);
 }
 
 // ---- standalone weight-streaming GEMM (unit tests + kernel-level roofline runs) --------------
@@ -1994,703 +2000,5 @@ extern "C" int sd_gemm_bf16(const void *w_packed, const void *x, int x_tiled, in
     return SD_OK;
 }
 
-// ---- one whole speculative iteration, enqueued natively ---------------------------------------
-// reference sampling/speculative_sampling.py:1934-2031 for the device-RNG mode: gamma x (draft forward +
-// norm_sample), one target forward over the uncached rows + norm_probs, accept scan, residual / bonus sample,
-// then the 144-byte result block and the gamma+2 candidate tokens are copied to pinned host memory.  Nothing
-// here synchronises; the caller waits on the stream once per iteration.
-int sd_resample_with_errors(const float *p_hist, const float *q_hist, long ld, int V, int32_t *seq, int gamma,
-                            uint64_t philox_seed, uint64_t draw_index, sd_accept_result *res, const int *err_flags,
-                            int n_err, int dtype_mode, hipStream_t st);
-
-// SD_NORM_DT_* of a model's probability rows: OPT keeps logits and probabilities in the weight dtype
-// (modeling_opt.py:974), Llama casts its logits to fp32 (modeling_llama.py:870)
-static int storage_mode(const sd_model *m) {
-    if (m->cfg.arch != SD_ARCH_OPT) return 0;
-    return m->cfg.dtype == SD_BF16 ? SD_NORM_DT_BF16 : (m->cfg.dtype == SD_F16 ? SD_NORM_DT_F16 : 0);
-}
-
-struct sd_spec {
-    sd_session *draft, *target;
-    int gamma, top_k, V;
-    float temperature, top_p;
-    int32_t *seq;
-    float *q_hist, *p_hist;
-    long ld;
-    float *draft_logits, *target_logits;
-    long ld_dl, ld_tl;
-    int *err;                    // device ints: [0..gamma) norm err of draft rows, [gamma..2gamma) sample err, [2gamma..3gamma+1) target rows
-    sd_accept_result *res_dev;
-    void *norm_ws;               // sd_norm_workspace_bytes(gamma+1) bytes, may be NULL
-    hipEvent_t ev[4];
-    hipEvent_t ev_done;          // end of an iteration's device -> host copy (sd_spec_generate polls it)
-    int timing;
-};
-
-extern "C" int sd_spec_create(sd_session *draft, sd_session *target, int gamma, float temperature, int top_k,
-                              float top_p, int32_t *seq, float *q_hist, float *p_hist, long ld, float *draft_logits,
-                              long ld_draft_logits, float *target_logits, long ld_target_logits, int *err_words,
-                              sd_accept_result *res_dev, void *norm_workspace, sd_spec **out) {
-    SD_REQUIRE(draft && target && seq && q_hist && p_hist && draft_logits && target_logits && err_words && res_dev && out,
-               "sd_spec_create: null argument");
-    SD_REQUIRE(gamma >= 1 && gamma <= 16, "sd_spec_create: gamma must be in 1..16");
-    SD_REQUIRE(draft->m->cfg.vocab == target->m->cfg.vocab, "sd_spec_create: draft and target vocabularies differ");
-    SD_REQUIRE(temperature != 0.0f, "sd_spec_create: temperature must be non-zero");
-    refresh_env();
-    sd_spec *sp = new sd_spec();
-    sp->draft = draft; sp->target = target; sp->gamma = gamma; sp->temperature = temperature; sp->top_k = top_k;
-    sp->top_p = top_p; sp->V = draft->m->cfg.vocab; sp->seq = seq; sp->q_hist = q_hist; sp->p_hist = p_hist; sp->ld = ld;
-    sp->draft_logits = draft_logits; sp->ld_dl = ld_draft_logits; sp->target_logits = target_logits; sp->ld_tl = ld_target_logits;
-    sp->err = err_words; sp->res_dev = res_dev; sp->norm_ws = norm_workspace; sp->timing = 0;
-    for (int i = 0; i < 4; ++i) SD_HIP_CHECK(hipEventCreate(&sp->ev[i]));
-    SD_HIP_CHECK(hipEventCreateWithFlags(&sp->ev_done, hipEventDisableTiming));
-    *out = sp;
-    return SD_OK;
-}
-
-extern "C" int sd_spec_destroy(sd_spec *sp) {
-    if (!sp) return SD_OK;
-    for (int i = 0; i < 4; ++i) (void)hipEventDestroy(sp->ev[i]);
-    (void)hipEventDestroy(sp->ev_done);
-    delete sp;
-    return SD_OK;
-}
-
-extern "C" int sd_spec_timing(sd_spec *sp, int on) {
-    SD_REQUIRE(sp, "sd_spec_timing: null handle");
-    sp->timing = on;
-    return SD_OK;
-}
-
-// milliseconds of the last iteration's draft phase and target (verify) phase; call after the stream is synchronised
-extern "C" int sd_spec_last_times(sd_spec *sp, float *draft_ms, float *target_ms) {
-    SD_REQUIRE(sp && draft_ms && target_ms && sp->timing, "sd_spec_last_times: timing is off");
-    SD_HIP_CHECK(hipEventElapsedTime(draft_ms, sp->ev[0], sp->ev[1]));
-    SD_HIP_CHECK(hipEventElapsedTime(target_ms, sp->ev[2], sp->ev[3]));
-    return SD_OK;
-}
-
-extern "C" int sd_norm_sample(const float *logits, int V, float temperature, int top_k, float top_p,
-                              int bf16_round_logits, float *probs_out, int *err_flag, const float *exp_noise,
-                              uint64_t philox_seed, uint64_t draw_index, int *tok_out, int *sample_err, void *workspace,
-                              void *stream);
-extern "C" int sd_norm_probs(const float *logits, int rows, int V, long ld_in, float temperature, int top_k,
-                             float top_p, int bf16_round_logits, float *probs_out, long ld_out, int *err_flag,
-                             void *workspace, void *stream);
-extern "C" int sd_accept_scan(const float *p_hist, const float *q_hist, long ld, const int32_t *seq, int L, int gamma,
-                              const float *r, uint64_t philox_seed, uint64_t draw_index, sd_accept_result *out,
-                              void *stream);
-
-int sd_norm_rows_with_tiles(const float *logits, int rows, int V, long ld_in, float temperature, int top_k, float top_p,
-                            int bf16_round_logits, float *probs_out, long ld_out, int *err_flag, uint64_t seed,
-                            uint64_t draw, int *tok_out, int *samp_err, void *workspace, const float *tile_max,
-                            void *stream, void *cand_lists);
-size_t sd_norm_candrow_bytes(int rows);
-int sd_norm_batch_tiles(const float *logits, int n_rows, int V, long ld_in, float temperature, int top_k, float top_p,
-                        int bf16_round_logits, const sd_norm_row *rows, int sample, void *workspace, const float *tile_max,
-                        void *cand_lists, void *stream);
-
-// feed seq[from, upto) in chunks of at most max_rows; logits come out for the last n_logits rows, all of them from the
-// final call (a chunk never ends inside the logits rows), so that call's output slab can be handed to the norm as is
-static int feed_rows(sd_session *ses, const int32_t *seq, int from, int upto, int n_logits, float *logits, long ld,
-                     void *stream) {
-    const int first_logit = upto - n_logits;
-    int done = from;
-    while (done < upto) {
-        int m = std::min(ses->max_rows, upto - done);
-        if (done < first_logit && done + m > first_logit && done + m < upto) m = first_logit - done;
-        const int lo = std::max(first_logit, done);
-        const int nl = std::max(0, done + m - lo);
-        const int rc = sd_session_forward(ses, seq + done, m, done, nl, nl ? logits + (size_t)(lo - first_logit) * ld : nullptr,
-                                          ld, stream);
-        if (rc != SD_OK) return rc;
-        done += m;
-    }
-    return SD_OK;
-}
-
-extern "C" int sd_spec_iteration(sd_spec *sp, int L, int draft_len, int target_len, uint64_t seed_draft,
-                                 uint64_t draw_draft0, uint64_t seed_accept, uint64_t draw_scan0,
-                                 uint64_t draw_resample, const float *r_const, sd_accept_result *res_host,
-                                 int32_t *tok_host, void *stream) {
-    SD_REQUIRE(sp && res_host, "sd_spec_iteration: null argument");
-    SD_REQUIRE(L >= 1 && draft_len >= 0 && draft_len < L && target_len >= 0 && target_len < L + sp->gamma,
-               "sd_spec_iteration: L=%d draft_len=%d target_len=%d", L, draft_len, target_len);
-    hipStream_t st = (hipStream_t)stream;
-    const int g = sp->gamma, V = sp->V;
-    int rc;
-    // EPI_HEAD's tile maxima serve the top-k candidate search only (1 <= k <= 64, positive temperature, 16 | V >= 4096)
-    const bool tiles_ok = sp->top_k >= 1 && sp->top_k <= 64 && sp->temperature > 0.0f && V % 16 == 0 && V >= 4096 &&
-                          V <= 65536 && sp->ld % 4 == 0 && g_env.head_tiles;
-    if (sp->timing) SD_HIP_CHECK(hipEventRecord(sp->ev[0], st));
-    // ---- draft: gamma steps; the sampled token goes straight into seq[] where the next step's embed reads it
-    for (int i = 0; i < g; ++i) {
-        const int upto = L + i;
-        float *q_row = sp->q_hist + (size_t)(upto - 1) * sp->ld;
-        sp->draft->want_raw_logits = 1;
-        sp->draft->head_zero_rows = tiles_ok ? q_row : nullptr;      // the head clears the row and leaves tile maxima
-        sp->draft->head_zero_ld = sp->ld;
-        rc = feed_rows(sp->draft, sp->seq, draft_len, upto, 1, sp->draft_logits, sp->ld_dl, stream);
-        sp->draft->want_raw_logits = 0;
-        sp->draft->head_zero_rows = nullptr;
-        if (rc != SD_OK) return rc;
-        draft_len = upto;
-        if ((rc = sd_norm_rows_with_tiles(sp->draft->last_logits, 1, V, sp->draft->last_logits_ld, sp->temperature, sp->top_k,
-                                          sp->top_p, sp->draft->last_logits_round | storage_mode(sp->draft->m), q_row, sp->ld, sp->err + i, seed_draft,
-                                          draw_draft0 + (uint64_t)i, sp->seq + upto, sp->err + g + i, sp->norm_ws,
-                                          sp->draft->last_tile_max, stream, nullptr)) != SD_OK)
-            return rc;
-    }
-    if (sp->timing) { SD_HIP_CHECK(hipEventRecord(sp->ev[1], st)); SD_HIP_CHECK(hipEventRecord(sp->ev[2], st)); }
-    // the target rows' candidate lists (behind the CandRows of the workspace) let the residual / bonus sample skip its
-    // passes over V; they exist when all gamma + 1 rows of this iteration are normalised here
-    static const int sparse_on = getenv("SD_SPARSE_RESAMPLE") ? atoi(getenv("SD_SPARSE_RESAMPLE")) : 1;
-    void *lists = nullptr;
-    // ---- target: every uncached row in one pass (the whole prompt on the first call), logits for the last gamma+1
-    {
-        const int upto = L + g;
-        const int rows = std::min(upto - target_len, g + 1);
-        if (sparse_on && sp->norm_ws && rows == g + 1) lists = (char *)sp->norm_ws + sd_norm_candrow_bytes(g + 1);
-        float *p_rows = sp->p_hist + (size_t)(upto - rows) * sp->ld;
-        sp->target->want_raw_logits = 1;
-        sp->target->head_zero_rows = tiles_ok ? p_rows : nullptr;
-        sp->target->head_zero_ld = sp->ld;
-        rc = feed_rows(sp->target, sp->seq, target_len, upto, rows, sp->target_logits, sp->ld_tl, stream);
-        sp->target->want_raw_logits = 0;
-        sp->target->head_zero_rows = nullptr;
-        if (rc != SD_OK) return rc;
-        if ((rc = sd_norm_rows_with_tiles(sp->target->last_logits, rows, V, sp->target->last_logits_ld, sp->temperature,
-                                          sp->top_k, sp->top_p, sp->target->last_logits_round | storage_mode(sp->target->m), p_rows,
-                                          sp->ld, sp->err + 2 * g,
-                                          0, 0, nullptr, nullptr, sp->norm_ws, sp->target->last_tile_max, stream, lists)) != SD_OK)
-            return rc;
-    }
-    if (sp->timing) SD_HIP_CHECK(hipEventRecord(sp->ev[3], st));
-    // ---- accept scan + residual / bonus sample
-    // p - q, max_fn and the draw are in the rows' dtype when both models keep 16-bit rows
-    const int res_mode = storage_mode(sp->target->m) == storage_mode(sp->draft->m) ? storage_mode(sp->target->m) : 0;
-    if (lists) {
-        if ((rc = sd_accept_resample(sp->p_hist, sp->q_hist, sp->ld, V, sp->seq, L, g, r_const, seed_accept, draw_scan0,
-                                     draw_resample, sp->res_dev, sp->err, 3 * g + 1, res_mode, lists, st)) != SD_OK)
-            return rc;
-    } else {
-        if ((rc = sd_accept_scan(sp->p_hist, sp->q_hist, sp->ld, sp->seq, L, g, r_const, seed_accept, draw_scan0, sp->res_dev, stream)) != SD_OK)
-            return rc;
-        if ((rc = sd_resample_with_errors(sp->p_hist, sp->q_hist, sp->ld, V, sp->seq, g, seed_accept, draw_resample, sp->res_dev,
-                                          sp->err, 3 * g + 1, res_mode, st)) != SD_OK)
-            return rc;
-    }
-    SD_HIP_CHECK(hipMemcpyAsync(res_host, sp->res_dev, sizeof(sd_accept_result), hipMemcpyDeviceToHost, st));
-    if (tok_host)       // optional second copy; the result block already carries the drafted tokens and the next one
-        SD_HIP_CHECK(hipMemcpyAsync(tok_host, sp->seq + L, sizeof(int32_t) * (size_t)(g + 2), hipMemcpyDeviceToHost, st));
-    return SD_OK;
-}
-
-// In-loop failure handling of the two native loops: every failure sets `rc` and leaves the loop, so the common epilogue
-// (event destruction, write-back of the in/out cursor state) always runs.
-#define SD_LOOP_HIP(expr)                                                                                   \
-    if (hipError_t _e = (expr); _e != hipSuccess) {                                                         \
-        sd_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);          \
-        rc = SD_ERR_HIP;                                                                                    \
-        break;                                                                                              \
-    }
-// Waits for `ev` by polling (a blocking wait parks the thread, and the launches of the next iteration's draft steps - which
-// the GPU consumes as fast as they arrive - then start from a cold core); bounded in wall-clock time.
-static int poll_event(hipEvent_t ev, const char *who) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 0;; ++spins) {
-        const hipError_t q = hipEventQuery(ev);
-        if (q == hipSuccess) return SD_OK;
-        if (q != hipErrorNotReady) { sd_set_error("%s: %s", who, hipGetErrorString(q)); return SD_ERR_HIP; }
-        if ((spins & 0xfff) == 0xfff &&
-            std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 60.0) {
-            sd_set_error("%s: the iteration's result did not arrive within 60 s", who);
-            return SD_ERR_HIP;
-        }
-    }
-}
-
-// The device-RNG loop without the interpreter between iterations (reference speculative_sampling.py:1934-2046).
-extern "C" int sd_spec_generate(sd_spec *sp, int32_t *host_seq, int *len_io, int T, int eos_token_id, int ori_eos_cnt,
-                                uint64_t *seed_io, uint64_t *draw_io, uint64_t random_seed, const float *r_const,
-                                int *draft_len_io, int *target_len_io, sd_accept_result *res_host, int max_iters,
-                                int32_t *acc_len_out, float *p_at_out, float *q_at_out, float *draft_ms_out,
-                                float *target_ms_out, int *n_iters_out, int *err_out, void *stream) {
-    SD_REQUIRE(sp && host_seq && len_io && seed_io && draw_io && draft_len_io && target_len_io && res_host && n_iters_out && err_out,
-               "sd_spec_generate: null argument");
-    SD_REQUIRE(!random_seed || r_const, "sd_spec_generate: random_seed needs its uniform (r_const)");
-    const int g = sp->gamma;
-    int len = *len_io, draft_len = *draft_len_io, target_len = *target_len_io, iters = 0, eos_total = ori_eos_cnt;
-    uint64_t seed = *seed_io, draw = *draw_io;
-    *err_out = 0;
-    int rc = SD_OK;
-    while (len < T && iters < max_iters) {
-        const int L = len;
-        const uint64_t d_draft = draw;                            // gamma draft samples, then the discarded target sample
-        draw += (uint64_t)g + 1;
-        const uint64_t seed_draft = seed;
-        uint64_t d_scan = 0;
-        if (random_seed) { seed = random_seed; draw = 0; }        // :1976-1977: the stream restarts before every uniform
-        else { d_scan = draw; draw += (uint64_t)g; }
-        const uint64_t d_res = draw++;
-        if ((rc = sd_spec_iteration(sp, L, draft_len, target_len, seed_draft, d_draft, seed, d_scan, d_res, r_const, res_host,
-                                    nullptr, stream)) != SD_OK)
-            break;
-        SD_LOOP_HIP(hipEventRecord(sp->ev_done, (hipStream_t)stream));
-        if ((rc = poll_event(sp->ev_done, "sd_spec_generate")) != SD_OK) break;
-        const sd_accept_result r = *res_host;
-        if (r.flags & 2) { *err_out = 1; break; }
-        if (r.flags & 8) {                                        // which word: a draft sample error, or a norm error
-            std::vector<int> ew(3 * g + 1);
-            SD_LOOP_HIP(hipMemcpy(ew.data(), sp->err, sizeof(int) * ew.size(), hipMemcpyDeviceToHost));
-            bool samp = false;
-            for (int i = g; i < 2 * g; ++i) samp = samp || ew[i] != 0;
-            *err_out = samp ? 1 : 2;
-            // a NaN row may be the poison of a timed-out in-launch wait (fused_kernels.h / normload_kernels.h): say so
-            unsigned wd = 0, wt = 0;
-            if (hipMemcpy(&wd, sp->draft->wait_status, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess &&
-                hipMemcpy(&wt, sp->target->wait_status, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess && (wd | wt))
-                sd_set_error("sd_spec_generate: a fused launch's in-launch wait timed out (status draft %#x, target %#x; "
-                             "sd_session_fused_status): its rows were poisoned with NaN", wd, wt);
-            break;
-        }
-        if (sp->timing && (draft_ms_out || target_ms_out)) {
-            float dms = 0.f, tms = 0.f;
-            SD_LOOP_HIP(hipEventElapsedTime(&dms, sp->ev[0], sp->ev[1]));
-            SD_LOOP_HIP(hipEventElapsedTime(&tms, sp->ev[2], sp->ev[3]));
-            if (draft_ms_out) draft_ms_out[iters] = dms;
-            if (target_ms_out) target_ms_out[iters] = tms;
-        }
-        const int l = r.n_accepted, n = r.n;
-        if (acc_len_out) acc_len_out[iters] = l;
-        for (int i = 0; i < g; ++i) {
-            if (p_at_out) p_at_out[(size_t)iters * g + i] = r.p_at[i];
-            if (q_at_out) q_at_out[(size_t)iters * g + i] = r.q_at[i];
-        }
-        ++iters;
-        if (!(n >= L - 1 && l >= 0 && l <= g)) {
-            sd_set_error("sd_spec_generate: inconsistent result block (n %d, L %d, accepted %d)", n, L, l);
-            rc = SD_ERR_INVALID;
-            break;
-        }
-        for (int i = 0; i < l; ++i) host_seq[len++] = r.drafted[i];
-        host_seq[len++] = r.next_token;
-        draft_len = std::min(L + g - 1, n + 1);                   // rollback(n + 1) of both caches (:2000, :2015 / 2023)
-        target_len = n + 1;
-        for (int i = L; i < len; ++i) eos_total += host_seq[i] == eos_token_id;
-        if (eos_total > ori_eos_cnt) break;                       // the caller cuts after the first new EOS (:2033-2041)
-    }
-    *len_io = len; *draft_len_io = draft_len; *target_len_io = target_len;
-    *seed_io = seed; *draw_io = draw; *n_iters_out = iters;
-    return rc;
-}
-
-// The stream-batched loop of sampling/batch.py in native code (reference algorithm per stream: speculative_sampling.py:1934-2046).
-extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, float temperature, int top_k,
-                                      float top_p, int V, long ld, int eos_token_id, uint64_t random_seed,
-                                      const float *r_const, int draft_norm_mode, int target_norm_mode, float *draft_logits,
-                                      long ld_draft_logits, float *target_logits, long ld_target_logits,
-                                      void *norm_workspace, int max_rows_per_forward, float *verify_ms_out,
-                                      int32_t *verify_streams_out, float *verify_ctx_out, int max_iters_log,
-                                      int *n_iters_out, int *err_out, void *stream) {
-    SD_REQUIRE(streams && n_streams >= 1 && n_streams <= 16 && gamma >= 1 && gamma <= 16 && draft_logits && target_logits &&
-               n_iters_out && err_out, "sd_spec_batch_generate: bad arguments");
-    SD_REQUIRE(!random_seed || r_const, "sd_spec_batch_generate: random_seed needs its uniform (r_const)");
-    for (int i = 1; i < n_streams; ++i)
-        SD_REQUIRE(streams[i].res_dev == streams[0].res_dev + i && streams[i].res_host == streams[0].res_host + i,
-                   "sd_spec_batch_generate: the streams' result blocks must be consecutive");
-    hipStream_t st = (hipStream_t)stream;
-    const int g = gamma, n_err = 3 * g + 1;
-    // streams per target pass (every verify row is a logit row: sd_model_max_pass_rows, 64 for a model whose lm_head or
-    // per-layer GEMMs stop at the streaming kernel)
-    const int pass_rows = std::min(max_rows_per_forward, streams[0].target ? streams[0].target->max_pass_rows : SD_MAX_ROWS);
-    const int max_verify = std::max(1, pass_rows / (g + 1));
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_done = nullptr;
-    if (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess ||
-        hipEventCreateWithFlags(&ev_done, hipEventDisableTiming) != hipSuccess) {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        sd_set_error("sd_spec_batch_generate: hipEventCreate failed");
-        return SD_ERR_HIP;
-    }
-    *err_out = 0;
-    int iters = 0, rc = SD_OK;
-    std::vector<sd_batch_stream *> act;
-    std::vector<int> Ls;
-    std::vector<uint64_t> base_draw;
-    std::vector<sd_batch_item> items;
-    std::vector<sd_norm_row> rows;
-    std::vector<sd_accept_item> aitems;
-    std::vector<const void *> list_of;
-    // SD_BATCH_FUSED_TAIL=0: the round-1 sampling tail (logits copy, candidate pass + norm per draft step; dense accept scan +
-    // resample) - kept for A/B runs and as the reference the fused tail is tested against; read per call
-    const bool fused_tail = !(getenv("SD_BATCH_FUSED_TAIL") && atoi(getenv("SD_BATCH_FUSED_TAIL")) == 0);
-    // EPI_HEAD's tile maxima serve the top-k candidate search only (as in sd_spec_iteration)
-    const bool tiles_ok = top_k >= 1 && top_k <= 64 && temperature > 0.0f && V % 16 == 0 && V >= 4096 && V <= 65536 &&
-                          ld % 4 == 0 && g_env.head_tiles;
-    for (int i = 0; i < n_streams; ++i) { streams[i].done = 0; streams[i].calls = 0; }
-    for (;;) {
-        act.clear();
-        for (int i = 0; i < n_streams; ++i) {
-            sd_batch_stream &s = streams[i];
-            if (!s.done && s.len >= s.T) s.done = 1;
-            if (!s.done) act.push_back(&s);
-        }
-        if (act.empty()) break;
-        const int n = (int)act.size();
-        Ls.assign(n, 0);
-        base_draw.assign(n, 0);
-        double ctx = 0.0;
-        for (int j = 0; j < n; ++j) {
-            Ls[j] = act[j]->len;
-            base_draw[j] = act[j]->draw;
-            act[j]->draw += (uint64_t)g;
-            ctx += Ls[j];
-        }
-        // the residual / bonus sample works on the target rows' candidate lists when ONE verify pass holds all streams (the
-        // workspace keeps the lists of one pass)
-        const bool lists_on = fused_tail && norm_workspace && n <= max_verify;
-        char *const list_base = norm_workspace ? (char *)norm_workspace + sd_norm_candrow_bytes(max_rows_per_forward) : nullptr;
-        const size_t list_stride = sd_cand_list_bytes(1);
-        list_of.assign(n, nullptr);
-        // ---- draft: gamma steps over all active streams
-        for (int i = 0; i < g && rc == SD_OK; ++i) {
-            items.assign(n, sd_batch_item{});
-            rows.assign(n, sd_norm_row{});
-            for (int j = 0; j < n; ++j) {
-                sd_batch_stream &s = *act[j];
-                items[j].session = s.draft; items[j].seq = s.seq; items[j].pos0 = s.draft_len;
-                items[j].n_new = Ls[j] + i - s.draft_len; items[j].n_logits = 1;
-                rows[j].probs_out = s.q_hist + (size_t)(Ls[j] + i - 1) * ld;
-                rows[j].err = s.err_words + i;
-                rows[j].exp_noise = nullptr;
-                rows[j].philox_seed = s.seed;
-                rows[j].draw_index = base_draw[j] + (uint64_t)i;
-                rows[j].tok_out = s.seq + (Ls[j] + i);
-                rows[j].sample_err = s.err_words + g + i;
-                s.draft_len = Ls[j] + i;
-            }
-            // the single-stream loop's sampler feed (sd_spec_iteration): the head leaves the logits in its own slab, the
-            // maximum of every 16-column tile, and clears the streams' probability rows - no logits copy, no candidate pass
-            sd_session *d0 = act[0]->draft;
-            if (fused_tail) {
-                d0->want_raw_logits = 1;
-                d0->head_zero_n = tiles_ok && n <= 16 ? n : 0;
-                for (int j = 0; j < d0->head_zero_n; ++j) d0->head_zero_ptr[j] = rows[j].probs_out;
-            }
-            rc = sd_batch_forward(items.data(), n, draft_logits, ld_draft_logits, stream);
-            d0->want_raw_logits = 0;
-            d0->head_zero_n = 0;
-            if (rc != SD_OK) break;
-            if (fused_tail)
-                rc = sd_norm_batch_tiles(d0->last_logits, n, V, d0->last_logits_ld, temperature, top_k, top_p,
-                                         d0->last_logits_round | draft_norm_mode, rows.data(), 1, norm_workspace, d0->last_tile_max,
-                                         nullptr, stream);
-            else
-                rc = sd_norm_batch(draft_logits, n, V, ld_draft_logits, temperature, top_k, top_p, draft_norm_mode, rows.data(), 1,
-                                   norm_workspace, stream);
-        }
-        if (rc != SD_OK) break;
-        // ---- verify: the uncached rows of every stream, max_verify streams per pass over the target weights
-        SD_LOOP_HIP(hipEventRecord(ev0, st));
-        for (int a0 = 0; a0 < n && rc == SD_OK; a0 += max_verify) {
-            const int m = std::min(max_verify, n - a0);
-            items.assign(m, sd_batch_item{});
-            rows.clear();
-            for (int j = 0; j < m; ++j) {
-                sd_batch_stream &s = *act[a0 + j];
-                const int L = Ls[a0 + j], nn = L + g - s.target_len;
-                items[j].session = s.target; items[j].seq = s.seq; items[j].pos0 = s.target_len;
-                items[j].n_new = nn; items[j].n_logits = nn;
-                for (int r = 0; r < nn; ++r) {
-                    sd_norm_row row = {};
-                    row.probs_out = s.p_hist + (size_t)(L + g - nn + r) * ld;
-                    row.err = s.err_words + 2 * g + std::min(r, g);
-                    rows.push_back(row);
-                }
-            }
-            if ((rc = sd_batch_forward(items.data(), m, target_logits, ld_target_logits, stream)) != SD_OK) break;
-            // one pass holds every stream: the rows' candidate lists (behind the CandRows of the workspace) serve the
-            // residual / bonus sample below
-            rc = sd_norm_batch_tiles(target_logits, (int)rows.size(), V, ld_target_logits, temperature, top_k, top_p, target_norm_mode,
-                                     rows.data(), 0, norm_workspace, nullptr, lists_on ? list_base : nullptr, stream);
-            if (lists_on) {
-                int r0 = 0;
-                for (int j = 0; j < m; ++j) {                       // stream j's lists are valid when all its gamma + 1 rows are here
-                    list_of[a0 + j] = items[j].n_new == g + 1 ? list_base + (size_t)r0 * list_stride : nullptr;
-                    r0 += items[j].n_new;
-                }
-            }
-        }
-        if (rc != SD_OK) break;
-        SD_LOOP_HIP(hipEventRecord(ev1, st));
-        // ---- accept scan + residual / bonus sample, all streams in two launches
-        aitems.assign(n, sd_accept_item{});
-        for (int j = 0; j < n; ++j) {
-            sd_batch_stream &s = *act[j];
-            s.draw += 1;                                          // the discarded target sample
-            uint64_t d_scan = 0;
-            if (random_seed) { s.seed = random_seed; s.draw = 0; }
-            else { d_scan = s.draw; s.draw += (uint64_t)g; }
-            sd_accept_item &it = aitems[j];
-            it.p_hist = s.p_hist; it.q_hist = s.q_hist; it.seq = s.seq; it.L = Ls[j];
-            it.r = r_const; it.exp_noise = nullptr;
-            it.philox_seed = s.seed; it.draw_scan = d_scan; it.draw_resample = s.draw++;
-            it.res = s.res_dev; it.err_flags = s.err_words; it.n_err = n_err;
-        }
-        const int res_mode = target_norm_mode == draft_norm_mode ? target_norm_mode : 0;
-        if (lists_on) rc = sd_accept_resample_batch(aitems.data(), n, ld, V, g, res_mode, list_of.data(), stream);
-        else rc = sd_accept_batch(aitems.data(), n, ld, V, g, res_mode, stream);
-        if (rc != SD_OK) break;
-        SD_LOOP_HIP(hipMemcpyAsync(streams[0].res_host, streams[0].res_dev, sizeof(sd_accept_result) * (size_t)n_streams,
-                                   hipMemcpyDeviceToHost, st));
-        SD_LOOP_HIP(hipEventRecord(ev_done, st));
-        if ((rc = poll_event(ev_done, "sd_spec_batch_generate")) != SD_OK) break;
-        if (iters < max_iters_log) {
-            float ms = 0.f;
-            if (verify_ms_out && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) verify_ms_out[iters] = ms;
-            if (verify_streams_out) verify_streams_out[iters] = n;
-            if (verify_ctx_out) verify_ctx_out[iters] = (float)(ctx / n + g);
-        }
-        ++iters;
-        bool failed = false;
-        for (int j = 0; j < n; ++j) {
-            sd_batch_stream &s = *act[j];
-            const sd_accept_result r = *s.res_host;
-            if (r.flags & (2 | 8)) { failed = true; break; }
-            const int L = Ls[j], l = r.n_accepted, nn = r.n;
-            if (s.acc_len_out) s.acc_len_out[s.calls] = l;
-            for (int i = 0; i < g; ++i) {
-                if (s.p_at_out) s.p_at_out[(size_t)s.calls * g + i] = r.p_at[i];
-                if (s.q_at_out) s.q_at_out[(size_t)s.calls * g + i] = r.q_at[i];
-            }
-            ++s.calls;
-            for (int i = 0; i < l; ++i) s.host_seq[s.len++] = r.drafted[i];
-            s.host_seq[s.len++] = r.next_token;
-            s.draft_len = std::min(L + g - 1, nn + 1);
-            s.target_len = nn + 1;
-            int eos_total = 0;
-            for (int i = 0; i < s.len; ++i) eos_total += s.host_seq[i] == eos_token_id;
-            if (eos_total > s.ori_eos_cnt) s.done = 1;            // the caller cuts after the first new EOS
-        }
-        if (failed) { *err_out = 1; break; }
-    }
-    (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1); (void)hipEventDestroy(ev_done);
-    *n_iters_out = iters;
-    return rc;
-}
-
-// ---- the width-w loop of sampling/multi.py in native code (reference speculative_sampling.py:1379-1716, strategy "iid")
-extern "C" int sd_multi_adopt(const sd_multi_adopt_item *items, int width, const sd_multi_result *res, int L, int gamma,
-                              int draft_lo, int target_lo, int draft_planes, int draft_max_seq, int draft_row_bytes,
-                              int target_planes, int target_max_seq, int target_row_bytes, int seq_cap, void *stream) {
-    SD_REQUIRE(items && res && width >= 1 && width <= 16, "sd_multi_adopt: 1..16 replicas");
-    SD_REQUIRE(gamma >= 1 && gamma <= 16 && L >= 1, "sd_multi_adopt: bad gamma / L");
-    SD_REQUIRE(draft_planes >= 0 && target_planes >= 0 && draft_row_bytes > 0 && target_row_bytes > 0 && draft_lo >= 0 &&
-               target_lo >= 0, "sd_multi_adopt: bad arena shape");
-    // the widest ranges the device may derive: draft [lo, L+gamma-1), target [lo, L+gamma), tokens [L, L+gamma+1)
-    SD_REQUIRE((draft_planes == 0 || L + gamma - 1 <= draft_max_seq) && (target_planes == 0 || L + gamma <= target_max_seq) &&
-               L + gamma + 1 <= seq_cap, "sd_multi_adopt: L %d + gamma %d overruns an arena (max_seq %d / %d) or a token buffer (%d)",
-               L, gamma, draft_max_seq, target_max_seq, seq_cap);
-    AdoptTab t = {};
-    for (int w = 0; w < width; ++w) {
-        SD_REQUIRE(items[w].seq && (draft_planes == 0 || items[w].draft_kv) && (target_planes == 0 || items[w].target_kv),
-                   "sd_multi_adopt: replica %d: null pointer", w);
-        t.d_kv[w] = (char *)items[w].draft_kv; t.t_kv[w] = (char *)items[w].target_kv; t.seq[w] = items[w].seq;
-    }
-    if (width == 1) return SD_OK;                                 // nobody to copy to
-    const AdoptArena d = {draft_planes, draft_max_seq, draft_row_bytes, draft_lo};
-    const AdoptArena tg = {target_planes, target_max_seq, target_row_bytes, target_lo};
-    hipLaunchKernelGGL(multi_adopt_kernel, dim3(draft_planes + target_planes + 1, width), dim3(128), 0, (hipStream_t)stream, t, width,
-                       res, L, gamma, d, tg, seq_cap);
-    SD_LAUNCH_CHECK();
-    return SD_OK;
-}
-
-static inline int kv_planes(const sd_session *s) { return s->m->cfg.n_layers * 2 * s->m->cfg.n_kv_heads; }
-static inline int kv_row_bytes(const sd_session *s) { return s->m->cfg.head_dim * (s->kv_fp8 ? 1 : (int)esize(s->m->cfg.dtype)); }
-
-extern "C" size_t sd_spec_multi_block_bytes(int width, int gamma) {
-    if (width < 1 || gamma < 1) return 0;
-    return sizeof(sd_multi_result) + sizeof(int32_t) * (size_t)width * (3 * gamma + 1);
-}
-
-extern "C" int sd_spec_multi_generate(const sd_multi_replica *reps, int width, int gamma, float temperature, int top_k,
-                                      float top_p, int V, long ld, int seq_cap, int draft_norm_mode, int target_norm_mode,
-                                      float *draft_logits, long ld_draft_logits, float *target_logits, long ld_target_logits,
-                                      void *norm_workspace, int max_rows_per_forward, void *dev_block, void *host_block,
-                                      int32_t *host_seq, int *len_io, int T, int eos_token_id, int ori_eos_cnt,
-                                      uint64_t *seed_io, uint64_t *draw_io, uint64_t random_seed, const float *r_const,
-                                      int *draft_len_io, int *target_len_io, int max_iters, int32_t *acc_len_out,
-                                      float *p_at_out, float *q_at_out, float *draft_ms_out, float *target_ms_out,
-                                      int *n_iters_out, int *err_out, void *stream) {
-    SD_REQUIRE(width >= 1 && width <= 16, "sd_spec_multi_generate: width %d outside 1..16", width);
-    SD_REQUIRE(gamma >= 1 && gamma <= 16, "sd_spec_multi_generate: gamma %d outside 1..16", gamma);
-    SD_REQUIRE(reps && draft_logits && target_logits && dev_block && host_block && host_seq && len_io && seed_io && draw_io &&
-               draft_len_io && target_len_io && n_iters_out && err_out, "sd_spec_multi_generate: null argument");
-    SD_REQUIRE(!random_seed || r_const, "sd_spec_multi_generate: random_seed needs its uniforms (r_const)");
-    SD_REQUIRE(V > 0 && ld >= V, "sd_spec_multi_generate: bad V / ld");
-    for (int w = 0; w < width; ++w) {
-        const sd_multi_replica &r = reps[w];
-        SD_REQUIRE(r.draft && r.target && r.seq && r.q_hist && r.p_hist, "sd_spec_multi_generate: replica %d: null pointer", w);
-        SD_REQUIRE(r.draft->m == reps[0].draft->m && r.target->m == reps[0].target->m && r.draft->max_seq == reps[0].draft->max_seq &&
-                   r.target->max_seq == reps[0].target->max_seq && r.draft->kv_fp8 == reps[0].draft->kv_fp8 &&
-                   r.target->kv_fp8 == reps[0].target->kv_fp8, "sd_spec_multi_generate: replica %d: sessions differ from replica 0's", w);
-    }
-    const int g = gamma, W = width, n_err = 3 * g + 1;
-    const int pass_rows = std::min(max_rows_per_forward, reps[0].target->max_pass_rows);
-    SD_REQUIRE(2 * W <= pass_rows && 2 * W <= std::min(reps[0].draft->max_rows, SD_MAX_ROWS),
-               "sd_spec_multi_generate: width %d: a draft step may carry 2 rows per replica, a pass holds %d", W, pass_rows);
-    SD_REQUIRE(g + 1 <= pass_rows, "sd_spec_multi_generate: gamma %d + 1 verify rows exceed one pass (%d rows)", g, pass_rows);
-    SD_REQUIRE(*len_io >= 1 && T + g + 1 <= seq_cap, "sd_spec_multi_generate: token buffers of %d hold T %d + gamma + 1", seq_cap, T);
-    hipStream_t st = (hipStream_t)stream;
-    sd_multi_result *res_dev = (sd_multi_result *)dev_block;
-    int *err_dev = (int *)((char *)dev_block + sizeof(sd_multi_result));
-    const sd_multi_result *res_host = (const sd_multi_result *)host_block;
-    const int *err_host = (const int *)((const char *)host_block + sizeof(sd_multi_result));
-    const size_t block_bytes = sd_spec_multi_block_bytes(W, g);
-    const bool timed = draft_ms_out || target_ms_out;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int i = 0; i < 4; ++i) {
-        const bool ok = i < 3 ? (!timed || hipEventCreate(&ev[i]) == hipSuccess)
-                              : hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) == hipSuccess;
-        if (!ok) {
-            for (int j = 0; j < i; ++j) if (ev[j]) (void)hipEventDestroy(ev[j]);
-            sd_set_error("sd_spec_multi_generate: hipEventCreate failed");
-            return SD_ERR_HIP;
-        }
-    }
-    hipEvent_t ev_done = ev[3];
-    std::vector<sd_batch_item> items;
-    std::vector<sd_norm_row> rows;
-    sd_multi_item mitems[16];
-    sd_multi_adopt_item aitems[16];
-    for (int w = 0; w < W; ++w) {
-        mitems[w].p_hist = reps[w].p_hist; mitems[w].q_hist = reps[w].q_hist; mitems[w].seq = reps[w].seq;
-        aitems[w].draft_kv = reps[w].draft->kv; aitems[w].target_kv = reps[w].target->kv; aitems[w].seq = reps[w].seq;
-    }
-    const int res_mode = target_norm_mode == draft_norm_mode ? target_norm_mode : 0;
-    int len = *len_io, draft_len = *draft_len_io, target_len = *target_len_io, iters = 0, eos_total = ori_eos_cnt;
-    uint64_t seed = *seed_io, draw = *draw_io;
-    *err_out = 0;
-    int rc = SD_OK;
-    while (len < T && iters < max_iters) {
-        const int L = len, d_lo = draft_len, t_lo = target_len;
-        if (!(draft_len >= 0 && draft_len < L && target_len >= 0 && target_len < L + g)) {
-            sd_set_error("sd_spec_multi_generate: cache lengths %d / %d do not fit a sequence of %d tokens", draft_len, target_len, L);
-            rc = SD_ERR_INVALID;
-            break;
-        }
-        // ---- gamma draft steps, all replicas per pass over the draft weights
-        if (timed) SD_LOOP_HIP(hipEventRecord(ev[0], st));
-        for (int i = 0; i < g && rc == SD_OK; ++i) {
-            const int n_new = L + i - draft_len;
-            const uint64_t draw0 = draw;
-            draw += (uint64_t)W;
-            items.assign(W, sd_batch_item{});
-            rows.assign(W, sd_norm_row{});
-            for (int w = 0; w < W; ++w) {
-                items[w].session = reps[w].draft; items[w].seq = reps[w].seq; items[w].pos0 = draft_len;
-                items[w].n_new = n_new; items[w].n_logits = 1;
-                rows[w].probs_out = reps[w].q_hist + (size_t)(L + i - 1) * ld;
-                rows[w].err = err_dev + w * n_err + i;
-                rows[w].exp_noise = nullptr;
-                rows[w].philox_seed = seed;
-                rows[w].draw_index = draw0 + (uint64_t)w;
-                rows[w].tok_out = reps[w].seq + (L + i);
-                rows[w].sample_err = err_dev + w * n_err + g + i;
-            }
-            if ((rc = sd_batch_forward(items.data(), W, draft_logits, ld_draft_logits, stream)) != SD_OK) break;
-            rc = sd_norm_batch(draft_logits, W, V, ld_draft_logits, temperature, top_k, top_p, draft_norm_mode, rows.data(), 1,
-                               norm_workspace, stream);
-            draft_len = L + i;
-        }
-        if (rc != SD_OK) break;
-        if (timed) SD_LOOP_HIP(hipEventRecord(ev[1], st));
-        // ---- the target over every replica's uncached rows, whole replicas per pass
-        const int n_new = L + g - target_len;
-        const int per_pass = std::max(1, pass_rows / n_new);
-        for (int a = 0; a < W && rc == SD_OK; a += per_pass) {
-            const int m = std::min(per_pass, W - a);
-            items.assign(m, sd_batch_item{});
-            rows.clear();
-            for (int j = 0; j < m; ++j) {
-                const sd_multi_replica &r = reps[a + j];
-                items[j].session = r.target; items[j].seq = r.seq; items[j].pos0 = target_len;
-                items[j].n_new = n_new; items[j].n_logits = n_new;
-                for (int k = 0; k < n_new; ++k) {
-                    sd_norm_row row = {};
-                    row.probs_out = r.p_hist + (size_t)(L + g - n_new + k) * ld;
-                    row.err = err_dev + (a + j) * n_err + 2 * g + std::min(k, g);
-                    rows.push_back(row);
-                }
-            }
-            if ((rc = sd_batch_forward(items.data(), m, target_logits, ld_target_logits, stream)) != SD_OK) break;
-            rc = sd_norm_batch(target_logits, (int)rows.size(), V, ld_target_logits, temperature, top_k, top_p, target_norm_mode,
-                               rows.data(), 0, norm_workspace, stream);
-        }
-        if (rc != SD_OK) break;
-        if (timed) SD_LOOP_HIP(hipEventRecord(ev[2], st));
-        draw += (uint64_t)W;                                      // the target's own sample, drawn and thrown away
-        // ---- replica scan + residual / bonus sample (one launch), winner broadcast (one launch), one copy, one wait
-        if (random_seed) { seed = random_seed; draw = 0; }        // the reseed quirk: the stream restarts before the uniforms
-        const uint64_t d_scan = draw;
-        draw += (uint64_t)W * g;
-        const uint64_t d_res = draw++;
-        if ((rc = sd_multi_accept_resample(mitems, W, ld, V, L, g, r_const, seed, d_scan, d_res, res_dev, res_mode, stream)) != SD_OK)
-            break;
-        if ((rc = sd_multi_adopt(aitems, W, res_dev, L, g, d_lo, t_lo, kv_planes(reps[0].draft), reps[0].draft->max_seq,
-                                 kv_row_bytes(reps[0].draft), kv_planes(reps[0].target), reps[0].target->max_seq,
-                                 kv_row_bytes(reps[0].target), seq_cap, stream)) != SD_OK)
-            break;
-        SD_LOOP_HIP(hipMemcpyAsync(host_block, dev_block, block_bytes, hipMemcpyDeviceToHost, st));
-        SD_LOOP_HIP(hipEventRecord(ev_done, st));
-        if ((rc = poll_event(ev_done, "sd_spec_multi_generate")) != SD_OK) break;
-        // error words first, a draft sample word before a norm word (multi.py: the scan's result is not looked at then,
-        // and the resample draw is not taken)
-        bool any = false, samp = false;
-        for (int w = 0; w < W; ++w)
-            for (int i = 0; i < n_err; ++i)
-                if (err_host[w * n_err + i]) { any = true; samp = samp || (i >= g && i < 2 * g); }
-        if (any) {
-            *err_out = samp ? 1 : 2;
-            --draw;
-            if (acc_len_out) acc_len_out[iters] = -1;             // the iteration ran (it counts as a call) but was not scanned
-            ++iters;
-            break;
-        }
-        const sd_accept_result r = res_host->chosen;
-        const int l = r.n_accepted, n = r.n;
-        if (!(res_host->choice >= 0 && res_host->choice < W && l >= 0 && l <= g && n == L + l - 1)) {
-            sd_set_error("sd_spec_multi_generate: inconsistent result block (choice %d, n %d, L %d, accepted %d)", res_host->choice,
-                         n, L, l);
-            rc = SD_ERR_INVALID;
-            break;
-        }
-        if (timed) {
-            float dms = 0.f, tms = 0.f;
-            SD_LOOP_HIP(hipEventElapsedTime(&dms, ev[0], ev[1]));
-            SD_LOOP_HIP(hipEventElapsedTime(&tms, ev[1], ev[2]));
-            if (draft_ms_out) draft_ms_out[iters] = dms;
-            if (target_ms_out) target_ms_out[iters] = tms;
-        }
-        if (acc_len_out) acc_len_out[iters] = l;
-        for (int w = 0; w < W; ++w)
-            for (int i = 0; i < g; ++i) {
-                if (p_at_out) p_at_out[((size_t)iters * W + w) * g + i] = res_host->p_at[w * 16 + i];
-                if (q_at_out) q_at_out[((size_t)iters * W + w) * g + i] = res_host->q_at[w * 16 + i];
-            }
-        ++iters;
-        for (int i = 0; i < l; ++i) host_seq[len++] = r.drafted[i];
-        if (r.flags & 2) { *err_out = 1; break; }                 // the resample raised: the output was already cut to the accepted drafts
-        host_seq[len++] = r.next_token;
-        draft_len = std::min(L + g - 1, n + 1);
-        target_len = (r.flags & 4) ? L + g : n + 1;
-        for (int i = L; i < len; ++i) eos_total += host_seq[i] == eos_token_id;
-        if (eos_total > ori_eos_cnt) break;                       // the caller cuts after the first new EOS
-    }
-    for (int i = 0; i < 4; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]);
-    *len_io = len; *draft_len_io = draft_len; *target_len_io = target_len;
-    *seed_io = seed; *draw_io = draw; *n_iters_out = iters;
-    return rc;
-}
+// ---- the native decode loops (sd_spec_*, sd_multi_adopt): same translation unit, they use sd_session and the forwards above
+#include "spec_loops.h"

@@ -1252,7 +1252,7 @@ static int launch_norm(const float *logits, int rows, int V, long ld_in, float t
     return SD_OK;
 }
 
-// internal (engine.hip, sd_spec_iteration): norm_logits of `rows` logit rows whose head left tile maxima (or NULL) and
+// internal (spec_loops.h, sd_spec_iteration): norm_logits of `rows` logit rows whose head left tile maxima (or NULL) and
 // cleared probs_out; with tok_out != NULL also the sample that follows a draft step (rows == 1)
 int sd_norm_rows_with_tiles(const float *logits, int rows, int V, long ld_in, float temperature, int top_k, float top_p,
                             int bf16_round_logits, float *probs_out, long ld_out, int *err_flag, uint64_t seed,

@@ -1,0 +1,686 @@
+// spec_loops.h - the native decode loops (single stream, lock-step streams, width-w iid) and the steps they share.  Host code,
+// included at the end of engine.hip, whose sd_session, HeadReq / HeadOut and session_forward / batch_forward it uses.
+#pragma once
+
+// SD_NORM_DT_* of a model's probability rows: OPT keeps logits and probabilities in the weight dtype
+// (modeling_opt.py:974), Llama casts its logits to fp32 (modeling_llama.py:870)
+static int storage_mode(const sd_model *m) {
+    if (m->cfg.arch != SD_ARCH_OPT) return 0;
+    return m->cfg.dtype == SD_BF16 ? SD_NORM_DT_BF16 : (m->cfg.dtype == SD_F16 ? SD_NORM_DT_F16 : 0);
+}
+
+struct sd_spec {
+    sd_session *draft, *target;
+    int gamma, top_k, V;
+    float temperature, top_p;
+    int32_t *seq;
+    float *q_hist, *p_hist;
+    long ld;
+    float *draft_logits, *target_logits;
+    long ld_dl, ld_tl;
+    int *err;                    // device ints: [0..gamma) norm err of draft rows, [gamma..2gamma) sample err, [2gamma..3gamma+1) target rows
+    sd_accept_result *res_dev;
+    void *norm_ws;               // sd_norm_workspace_bytes(gamma+1) bytes, may be NULL
+    hipEvent_t ev[4];
+    hipEvent_t ev_done;          // end of an iteration's device -> host copy (sd_spec_generate polls it)
+    int timing;
+};
+
+extern "C" int sd_spec_create(sd_session *draft, sd_session *target, int gamma, float temperature, int top_k,
+                              float top_p, int32_t *seq, float *q_hist, float *p_hist, long ld, float *draft_logits,
+                              long ld_draft_logits, float *target_logits, long ld_target_logits, int *err_words,
+                              sd_accept_result *res_dev, void *norm_workspace, sd_spec **out) {
+    SD_REQUIRE(draft && target && seq && q_hist && p_hist && draft_logits && target_logits && err_words && res_dev && out,
+               "sd_spec_create: null argument");
+    SD_REQUIRE(gamma >= 1 && gamma <= 16, "sd_spec_create: gamma must be in 1..16");
+    SD_REQUIRE(draft->m->cfg.vocab == target->m->cfg.vocab, "sd_spec_create: draft and target vocabularies differ");
+    SD_REQUIRE(temperature != 0.0f, "sd_spec_create: temperature must be non-zero");
+    refresh_env();
+    sd_spec *sp = new sd_spec();
+    sp->draft = draft; sp->target = target; sp->gamma = gamma; sp->temperature = temperature; sp->top_k = top_k;
+    sp->top_p = top_p; sp->V = draft->m->cfg.vocab; sp->seq = seq; sp->q_hist = q_hist; sp->p_hist = p_hist; sp->ld = ld;
+    sp->draft_logits = draft_logits; sp->ld_dl = ld_draft_logits; sp->target_logits = target_logits; sp->ld_tl = ld_target_logits;
+    sp->err = err_words; sp->res_dev = res_dev; sp->norm_ws = norm_workspace; sp->timing = 0;
+    for (int i = 0; i < 4; ++i) SD_HIP_CHECK(hipEventCreate(&sp->ev[i]));
+    SD_HIP_CHECK(hipEventCreateWithFlags(&sp->ev_done, hipEventDisableTiming));
+    *out = sp;
+    return SD_OK;
+}
+
+extern "C" int sd_spec_destroy(sd_spec *sp) {
+    if (!sp) return SD_OK;
+    for (int i = 0; i < 4; ++i) (void)hipEventDestroy(sp->ev[i]);
+    (void)hipEventDestroy(sp->ev_done);
+    delete sp;
+    return SD_OK;
+}
+
+extern "C" int sd_spec_timing(sd_spec *sp, int on) {
+    SD_REQUIRE(sp, "sd_spec_timing: null handle");
+    sp->timing = on;
+    return SD_OK;
+}
+
+// milliseconds of the last iteration's draft phase and target (verify) phase; call after the stream is synchronised
+extern "C" int sd_spec_last_times(sd_spec *sp, float *draft_ms, float *target_ms) {
+    SD_REQUIRE(sp && draft_ms && target_ms && sp->timing, "sd_spec_last_times: timing is off");
+    SD_HIP_CHECK(hipEventElapsedTime(draft_ms, sp->ev[0], sp->ev[1]));
+    SD_HIP_CHECK(hipEventElapsedTime(target_ms, sp->ev[2], sp->ev[3]));
+    return SD_OK;
+}
+
+// entries of sampling.hip that are not in the public header
+int sd_resample_with_errors(const float *p_hist, const float *q_hist, long ld, int V, int32_t *seq, int gamma,
+                            uint64_t philox_seed, uint64_t draw_index, sd_accept_result *res, const int *err_flags,
+                            int n_err, int dtype_mode, hipStream_t st);
+int sd_norm_rows_with_tiles(const float *logits, int rows, int V, long ld_in, float temperature, int top_k, float top_p,
+                            int bf16_round_logits, float *probs_out, long ld_out, int *err_flag, uint64_t seed,
+                            uint64_t draw, int *tok_out, int *samp_err, void *workspace, const float *tile_max,
+                            void *stream, void *cand_lists);
+size_t sd_norm_candrow_bytes(int rows);
+int sd_norm_batch_tiles(const float *logits, int n_rows, int V, long ld_in, float temperature, int top_k, float top_p,
+                        int bf16_round_logits, const sd_norm_row *rows, int sample, void *workspace, const float *tile_max,
+                        void *cand_lists, void *stream);
+
+// feed seq[from, upto) in chunks of at most max_rows; logits come out for the last n_logits rows, all of them from the
+// final call (a chunk never ends inside the logits rows), so that call's output slab can be handed to the norm as is
+static int feed_rows(sd_session *ses, const int32_t *seq, int from, int upto, int n_logits, float *logits, long ld,
+                     const HeadReq *rq, HeadOut *ho, void *stream) {
+    const int first_logit = upto - n_logits;
+    int done = from;
+    while (done < upto) {
+        int m = std::min(ses->max_rows, upto - done);
+        if (done < first_logit && done + m > first_logit && done + m < upto) m = first_logit - done;
+        const int lo = std::max(first_logit, done);
+        const int nl = std::max(0, done + m - lo);
+        const int rc = session_forward(ses, seq + done, m, done, nl, nl ? logits + (size_t)(lo - first_logit) * ld : nullptr, ld,
+                                       rq, ho, stream);
+        if (rc != SD_OK) return rc;
+        done += m;
+    }
+    return SD_OK;
+}
+
+// EPI_HEAD's tile maxima serve the top-k candidate search only (1 <= k <= 64, positive temperature, 16 | V >= 4096)
+static bool head_tiles_ok(int top_k, float temperature, int V, long ld) {
+    return top_k >= 1 && top_k <= 64 && temperature > 0.0f && V % 16 == 0 && V >= 4096 && V <= 65536 && ld % 4 == 0 &&
+           g_env.head_tiles;
+}
+
+// ---- one whole speculative iteration, enqueued natively ---------------------------------------
+// reference sampling/speculative_sampling.py:1934-2031 for the device-RNG mode: gamma x (draft forward +
+// norm_sample), one target forward over the uncached rows + norm_probs, accept scan, residual / bonus sample,
+// then the 144-byte result block and the gamma+2 candidate tokens are copied to pinned host memory.  Nothing
+// here synchronises; the caller waits on the stream once per iteration.
+extern "C" int sd_spec_iteration(sd_spec *sp, int L, int draft_len, int target_len, uint64_t seed_draft,
+                                 uint64_t draw_draft0, uint64_t seed_accept, uint64_t draw_scan0,
+                                 uint64_t draw_resample, const float *r_const, sd_accept_result *res_host,
+                                 int32_t *tok_host, void *stream) {
+    SD_REQUIRE(sp && res_host, "sd_spec_iteration: null argument");
+    SD_REQUIRE(L >= 1 && draft_len >= 0 && draft_len < L && target_len >= 0 && target_len < L + sp->gamma,
+               "sd_spec_iteration: L=%d draft_len=%d target_len=%d", L, draft_len, target_len);
+    hipStream_t st = (hipStream_t)stream;
+    const int g = sp->gamma, V = sp->V;
+    int rc;
+    const bool tiles_ok = head_tiles_ok(sp->top_k, sp->temperature, V, sp->ld);
+    HeadReq rq = {};
+    HeadOut ho = {};
+    rq.raw = true; rq.zero_ld = sp->ld;                          // (zero_rows: per forward, below)
+    if (sp->timing) SD_HIP_CHECK(hipEventRecord(sp->ev[0], st));
+    // ---- draft: gamma steps; the sampled token goes straight into seq[] where the next step's embed reads it
+    for (int i = 0; i < g; ++i) {
+        const int upto = L + i;
+        float *q_row = sp->q_hist + (size_t)(upto - 1) * sp->ld;
+        rq.zero_rows = tiles_ok ? q_row : nullptr;                   // the head clears the row and leaves tile maxima
+        if ((rc = feed_rows(sp->draft, sp->seq, draft_len, upto, 1, sp->draft_logits, sp->ld_dl, &rq, &ho, stream)) != SD_OK) return rc;
+        draft_len = upto;
+        if ((rc = sd_norm_rows_with_tiles(ho.logits, 1, V, ho.ld, sp->temperature, sp->top_k, sp->top_p,
+                                          ho.round | storage_mode(sp->draft->m), q_row, sp->ld, sp->err + i, seed_draft,
+                                          draw_draft0 + (uint64_t)i, sp->seq + upto, sp->err + g + i, sp->norm_ws, ho.tile_max,
+                                          stream, nullptr)) != SD_OK)
+            return rc;
+    }
+    if (sp->timing) { SD_HIP_CHECK(hipEventRecord(sp->ev[1], st)); SD_HIP_CHECK(hipEventRecord(sp->ev[2], st)); }
+    // the target rows' candidate lists (behind the CandRows of the workspace) let the residual / bonus sample skip its
+    // passes over V; they exist when all gamma + 1 rows of this iteration are normalised here
+    static const int sparse_on = getenv("SD_SPARSE_RESAMPLE") ? atoi(getenv("SD_SPARSE_RESAMPLE")) : 1;
+    void *lists = nullptr;
+    // ---- target: every uncached row in one pass (the whole prompt on the first call), logits for the last gamma+1
+    {
+        const int upto = L + g;
+        const int rows = std::min(upto - target_len, g + 1);
+        if (sparse_on && sp->norm_ws && rows == g + 1) lists = (char *)sp->norm_ws + sd_norm_candrow_bytes(g + 1);
+        float *p_rows = sp->p_hist + (size_t)(upto - rows) * sp->ld;
+        rq.zero_rows = tiles_ok ? p_rows : nullptr;
+        if ((rc = feed_rows(sp->target, sp->seq, target_len, upto, rows, sp->target_logits, sp->ld_tl, &rq, &ho, stream)) != SD_OK)
+            return rc;
+        if ((rc = sd_norm_rows_with_tiles(ho.logits, rows, V, ho.ld, sp->temperature, sp->top_k, sp->top_p,
+                                          ho.round | storage_mode(sp->target->m), p_rows, sp->ld, sp->err + 2 * g, 0, 0, nullptr,
+                                          nullptr, sp->norm_ws, ho.tile_max, stream, lists)) != SD_OK)
+            return rc;
+    }
+    if (sp->timing) SD_HIP_CHECK(hipEventRecord(sp->ev[3], st));
+    // ---- accept scan + residual / bonus sample
+    // p - q, max_fn and the draw are in the rows' dtype when both models keep 16-bit rows
+    const int res_mode = storage_mode(sp->target->m) == storage_mode(sp->draft->m) ? storage_mode(sp->target->m) : 0;
+    if (lists) {
+        if ((rc = sd_accept_resample(sp->p_hist, sp->q_hist, sp->ld, V, sp->seq, L, g, r_const, seed_accept, draw_scan0,
+                                     draw_resample, sp->res_dev, sp->err, 3 * g + 1, res_mode, lists, st)) != SD_OK)
+            return rc;
+    } else {
+        if ((rc = sd_accept_scan(sp->p_hist, sp->q_hist, sp->ld, sp->seq, L, g, r_const, seed_accept, draw_scan0, sp->res_dev, stream)) != SD_OK)
+            return rc;
+        if ((rc = sd_resample_with_errors(sp->p_hist, sp->q_hist, sp->ld, V, sp->seq, g, seed_accept, draw_resample, sp->res_dev,
+                                          sp->err, 3 * g + 1, res_mode, st)) != SD_OK)
+            return rc;
+    }
+    SD_HIP_CHECK(hipMemcpyAsync(res_host, sp->res_dev, sizeof(sd_accept_result), hipMemcpyDeviceToHost, st));
+    if (tok_host)       // optional second copy; the result block already carries the drafted tokens and the next one
+        SD_HIP_CHECK(hipMemcpyAsync(tok_host, sp->seq + L, sizeof(int32_t) * (size_t)(g + 2), hipMemcpyDeviceToHost, st));
+    return SD_OK;
+}
+
+// ---- steps the loops share ------------------------------------------------------------------------------------
+// In-loop failure handling of the three native loops: every failure sets `rc` and leaves the loop, so the common epilogue
+// (write-back of the in/out cursor state) always runs.
+#define SD_LOOP_HIP(expr)                                                                                   \
+    if (hipError_t _e = (expr); _e != hipSuccess) {                                                         \
+        sd_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);          \
+        rc = SD_ERR_HIP;                                                                                    \
+        break;                                                                                              \
+    }
+// Waits for `ev` by polling (a blocking wait parks the thread, and the launches of the next iteration's draft steps - which
+// the GPU consumes as fast as they arrive - then start from a cold core); bounded in wall-clock time.
+static int poll_event(hipEvent_t ev, const char *who) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned spins = 0;; ++spins) {
+        const hipError_t q = hipEventQuery(ev);
+        if (q == hipSuccess) return SD_OK;
+        if (q != hipErrorNotReady) { sd_set_error("%s: %s", who, hipGetErrorString(q)); return SD_ERR_HIP; }
+        if ((spins & 0xfff) == 0xfff &&
+            std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 60.0) {
+            sd_set_error("%s: the iteration's result did not arrive within 60 s", who);
+            return SD_ERR_HIP;
+        }
+    }
+}
+
+// The events of one call of a loop: `timing` events for hipEventElapsedTime and the one whose completion ends an
+// iteration; destroyed on every way out.  (sd_spec keeps its own: their lifetime is the handle's.)
+struct LoopEvents {
+    hipEvent_t t[3] = {nullptr, nullptr, nullptr}, done = nullptr;
+    bool ok = true;                                               // false: a creation failed (the error text is set)
+    LoopEvents(int timing, const char *who) {
+        for (int i = 0; i < timing && ok; ++i) ok = hipEventCreate(&t[i]) == hipSuccess;
+        ok = ok && hipEventCreateWithFlags(&done, hipEventDisableTiming) == hipSuccess;
+        if (!ok) sd_set_error("%s: hipEventCreate failed", who);
+    }
+    ~LoopEvents() {
+        for (hipEvent_t e : t) if (e) (void)hipEventDestroy(e);
+        if (done) (void)hipEventDestroy(done);
+    }
+    LoopEvents(const LoopEvents &) = delete;                     // (owns its events)
+};
+
+// The Philox draws of one iteration of one stream (single-stream and lock-step loops; the width-w loop counts W per step)
+struct Draws {
+    uint64_t seed_draft, draft0;         // draft step i samples with (seed_draft, draft0 + i)
+    uint64_t seed, scan0, resample;      // accept scan and residual / bonus sample
+    uint64_t draw;                       // the stream's next draw after this iteration (its seed is `seed`)
+};
+static Draws next_draws(uint64_t seed, uint64_t draw, int g, uint64_t random_seed) {
+    Draws d = {seed, draw};                                       // gamma draft samples, then the discarded target sample
+    draw += (uint64_t)g + 1;
+    if (random_seed) { seed = random_seed; draw = 0; }            // :1976-1977: the stream restarts before every uniform
+    else { d.scan0 = draw; draw += (uint64_t)g; }                 // (under random_seed the scan takes r_const)
+    d.seed = seed; d.resample = draw++; d.draw = draw;
+    return d;
+}
+
+// Draft step i of one stream / replica whose sequence has L tokens and whose draft cache holds draft_len: the uncached
+// rows, logits for the last, sampled with (seed, draw) into seq[L + i].  `err` are the stream's 3 * gamma + 1 error words.
+static void draft_step_rows(sd_batch_item &it, sd_norm_row &row, sd_session *draft, int32_t *seq, float *q_hist, long ld, int *err,
+                            int g, int L, int i, int draft_len, uint64_t seed, uint64_t draw) {
+    it.session = draft; it.seq = seq; it.pos0 = draft_len;
+    it.n_new = L + i - draft_len; it.n_logits = 1;
+    row.probs_out = q_hist + (size_t)(L + i - 1) * ld; row.tok_out = seq + (L + i);
+    row.err = err + i; row.sample_err = err + g + i;
+    row.exp_noise = nullptr; row.philox_seed = seed; row.draw_index = draw;
+}
+
+// The verify rows of one stream / replica: every uncached row of its L + gamma tokens is a logit row; their norm rows are
+// appended to `rows` (rows past the gamma-th share the last target error word).
+static void verify_pass_rows(sd_batch_item &it, std::vector<sd_norm_row> &rows, sd_session *target, const int32_t *seq, float *p_hist,
+                             long ld, int *err, int g, int L, int target_len) {
+    const int nn = L + g - target_len;
+    it.session = target; it.seq = seq; it.pos0 = target_len;
+    it.n_new = nn; it.n_logits = nn;
+    for (int r = 0; r < nn; ++r) {
+        sd_norm_row row = {};
+        row.probs_out = p_hist + (size_t)(L + g - nn + r) * ld;
+        row.err = err + 2 * g + std::min(r, g);
+        rows.push_back(row);
+    }
+}
+
+// Log entry `slot` of the acceptance statistics: the gamma target / draft probabilities of the drafted tokens
+static void log_ratios(float *p_at_out, float *q_at_out, size_t slot, int g, const float *p_at, const float *q_at) {
+    for (int i = 0; i < g; ++i) {
+        if (p_at_out) p_at_out[slot * g + i] = p_at[i];
+        if (q_at_out) q_at_out[slot * g + i] = q_at[i];
+    }
+}
+
+// Commits a result block to a sequence of L tokens: the accepted drafts and the next token are appended, both caches
+// roll back to n + 1 (speculative_sampling.py:2000, :2015 / 2023; the draft never holds the last drafted token).  A block
+// whose resample raised (flags & 2; only the width-w loop commits one) keeps the accepted drafts and nothing else: false.
+static bool commit_result(const sd_accept_result &r, int L, int g, int32_t *host_seq, int *len, int *draft_len, int *target_len) {
+    for (int i = 0; i < r.n_accepted; ++i) host_seq[(*len)++] = r.drafted[i];
+    if (r.flags & 2) return false;
+    host_seq[(*len)++] = r.next_token;
+    *draft_len = std::min(L + g - 1, r.n + 1);
+    *target_len = r.n + 1;
+    return true;
+}
+
+// The device-RNG loop without the interpreter between iterations (reference speculative_sampling.py:1934-2046).
+extern "C" int sd_spec_generate(sd_spec *sp, int32_t *host_seq, int *len_io, int T, int eos_token_id, int ori_eos_cnt,
+                                uint64_t *seed_io, uint64_t *draw_io, uint64_t random_seed, const float *r_const,
+                                int *draft_len_io, int *target_len_io, sd_accept_result *res_host, int max_iters,
+                                int32_t *acc_len_out, float *p_at_out, float *q_at_out, float *draft_ms_out,
+                                float *target_ms_out, int *n_iters_out, int *err_out, void *stream) {
+    SD_REQUIRE(sp && host_seq && len_io && seed_io && draw_io && draft_len_io && target_len_io && res_host && n_iters_out && err_out,
+               "sd_spec_generate: null argument");
+    SD_REQUIRE(!random_seed || r_const, "sd_spec_generate: random_seed needs its uniform (r_const)");
+    const int g = sp->gamma;
+    int len = *len_io, draft_len = *draft_len_io, target_len = *target_len_io, iters = 0, eos_total = ori_eos_cnt;
+    uint64_t seed = *seed_io, draw = *draw_io;
+    *err_out = 0;
+    int rc = SD_OK;
+    while (len < T && iters < max_iters) {
+        const int L = len;
+        const Draws d = next_draws(seed, draw, g, random_seed);
+        seed = d.seed; draw = d.draw;
+        if ((rc = sd_spec_iteration(sp, L, draft_len, target_len, d.seed_draft, d.draft0, d.seed, d.scan0, d.resample, r_const,
+                                    res_host, nullptr, stream)) != SD_OK)
+            break;
+        SD_LOOP_HIP(hipEventRecord(sp->ev_done, (hipStream_t)stream));
+        if ((rc = poll_event(sp->ev_done, "sd_spec_generate")) != SD_OK) break;
+        const sd_accept_result r = *res_host;
+        if (r.flags & 2) { *err_out = 1; break; }
+        if (r.flags & 8) {                                        // which word: a draft sample error, or a norm error
+            std::vector<int> ew(3 * g + 1);
+            SD_LOOP_HIP(hipMemcpy(ew.data(), sp->err, sizeof(int) * ew.size(), hipMemcpyDeviceToHost));
+            bool samp = false;
+            for (int i = g; i < 2 * g; ++i) samp = samp || ew[i] != 0;
+            *err_out = samp ? 1 : 2;
+            // a NaN row may be the poison of a timed-out in-launch wait (fused_kernels.h / normload_kernels.h): say so
+            unsigned wd = 0, wt = 0;
+            if (hipMemcpy(&wd, sp->draft->wait_status, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess &&
+                hipMemcpy(&wt, sp->target->wait_status, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess && (wd | wt))
+                sd_set_error("sd_spec_generate: a fused launch's in-launch wait timed out (status draft %#x, target %#x; "
+                             "sd_session_fused_status): its rows were poisoned with NaN", wd, wt);
+            break;
+        }
+        if (sp->timing && (draft_ms_out || target_ms_out)) {
+            float dms = 0.f, tms = 0.f;
+            SD_LOOP_HIP(hipEventElapsedTime(&dms, sp->ev[0], sp->ev[1]));
+            SD_LOOP_HIP(hipEventElapsedTime(&tms, sp->ev[2], sp->ev[3]));
+            if (draft_ms_out) draft_ms_out[iters] = dms;
+            if (target_ms_out) target_ms_out[iters] = tms;
+        }
+        const int l = r.n_accepted, n = r.n;
+        if (acc_len_out) acc_len_out[iters] = l;
+        log_ratios(p_at_out, q_at_out, (size_t)iters, g, r.p_at, r.q_at);
+        ++iters;
+        if (!(n >= L - 1 && l >= 0 && l <= g)) {
+            sd_set_error("sd_spec_generate: inconsistent result block (n %d, L %d, accepted %d)", n, L, l);
+            rc = SD_ERR_INVALID;
+            break;
+        }
+        commit_result(r, L, g, host_seq, &len, &draft_len, &target_len);      // (flags & 2 left the loop above)
+        for (int i = L; i < len; ++i) eos_total += host_seq[i] == eos_token_id;
+        if (eos_total > ori_eos_cnt) break;                       // the caller cuts after the first new EOS (:2033-2041)
+    }
+    *len_io = len; *draft_len_io = draft_len; *target_len_io = target_len;
+    *seed_io = seed; *draw_io = draw; *n_iters_out = iters;
+    return rc;
+}
+
+// The stream-batched loop of sampling/batch.py in native code (reference algorithm per stream: speculative_sampling.py:1934-2046).
+extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, float temperature, int top_k,
+                                      float top_p, int V, long ld, int eos_token_id, uint64_t random_seed,
+                                      const float *r_const, int draft_norm_mode, int target_norm_mode, float *draft_logits,
+                                      long ld_draft_logits, float *target_logits, long ld_target_logits,
+                                      void *norm_workspace, int max_rows_per_forward, float *verify_ms_out,
+                                      int32_t *verify_streams_out, float *verify_ctx_out, int max_iters_log,
+                                      int *n_iters_out, int *err_out, void *stream) {
+    SD_REQUIRE(streams && n_streams >= 1 && n_streams <= 16 && gamma >= 1 && gamma <= 16 && draft_logits && target_logits &&
+               n_iters_out && err_out, "sd_spec_batch_generate: bad arguments");
+    SD_REQUIRE(!random_seed || r_const, "sd_spec_batch_generate: random_seed needs its uniform (r_const)");
+    for (int i = 1; i < n_streams; ++i)
+        SD_REQUIRE(streams[i].res_dev == streams[0].res_dev + i && streams[i].res_host == streams[0].res_host + i,
+                   "sd_spec_batch_generate: the streams' result blocks must be consecutive");
+    hipStream_t st = (hipStream_t)stream;
+    const int g = gamma, n_err = 3 * g + 1;
+    // streams per target pass (every verify row is a logit row: sd_model_max_pass_rows, 64 for a model whose lm_head or
+    // per-layer GEMMs stop at the streaming kernel)
+    const int pass_rows = std::min(max_rows_per_forward, streams[0].target ? streams[0].target->max_pass_rows : SD_MAX_ROWS);
+    const int max_verify = std::max(1, pass_rows / (g + 1));
+    LoopEvents ev(2, "sd_spec_batch_generate");
+    if (!ev.ok) return SD_ERR_HIP;
+    *err_out = 0;
+    int iters = 0, rc = SD_OK;
+    std::vector<sd_batch_stream *> act;
+    std::vector<int> Ls;
+    std::vector<Draws> draws;
+    std::vector<sd_batch_item> items;
+    std::vector<sd_norm_row> rows;
+    std::vector<sd_accept_item> aitems;
+    std::vector<const void *> list_of;
+    // SD_BATCH_FUSED_TAIL=0: the round-1 sampling tail (logits copy, candidate pass + norm per draft step; dense accept scan +
+    // resample) - kept for A/B runs and as the reference the fused tail is tested against; read per call
+    const bool fused_tail = !(getenv("SD_BATCH_FUSED_TAIL") && atoi(getenv("SD_BATCH_FUSED_TAIL")) == 0);
+    const bool tiles_ok = head_tiles_ok(top_k, temperature, V, ld);
+    for (int i = 0; i < n_streams; ++i) { streams[i].done = 0; streams[i].calls = 0; }
+    for (;;) {
+        act.clear();
+        for (int i = 0; i < n_streams; ++i) {
+            sd_batch_stream &s = streams[i];
+            if (!s.done && s.len >= s.T) s.done = 1;
+            if (!s.done) act.push_back(&s);
+        }
+        if (act.empty()) break;
+        const int n = (int)act.size();
+        Ls.resize(n); draws.resize(n);
+        double ctx = 0.0;
+        for (int j = 0; j < n; ++j) {
+            Ls[j] = act[j]->len;
+            draws[j] = next_draws(act[j]->seed, act[j]->draw, g, random_seed);
+            act[j]->draw += (uint64_t)g;                          // (a failed forward leaves the stream here, seed untouched)
+            ctx += Ls[j];
+        }
+        // the residual / bonus sample works on the target rows' candidate lists when ONE verify pass holds all streams (the
+        // workspace keeps the lists of one pass)
+        const bool lists_on = fused_tail && norm_workspace && n <= max_verify;
+        char *const list_base = norm_workspace ? (char *)norm_workspace + sd_norm_candrow_bytes(max_rows_per_forward) : nullptr;
+        const size_t list_stride = sd_cand_list_bytes(1);
+        list_of.assign(n, nullptr);
+        // ---- draft: gamma steps over all active streams
+        for (int i = 0; i < g && rc == SD_OK; ++i) {
+            items.assign(n, sd_batch_item{});
+            rows.assign(n, sd_norm_row{});
+            for (int j = 0; j < n; ++j) {
+                sd_batch_stream &s = *act[j];
+                draft_step_rows(items[j], rows[j], s.draft, s.seq, s.q_hist, ld, s.err_words, g, Ls[j], i, s.draft_len,
+                                draws[j].seed_draft, draws[j].draft0 + (uint64_t)i);
+                s.draft_len = Ls[j] + i;
+            }
+            // the single-stream loop's sampler feed (sd_spec_iteration): the head leaves the logits in its own slab, the
+            // maximum of every 16-column tile, and clears the streams' probability rows - no logits copy, no candidate pass
+            HeadReq rq = {};
+            HeadOut ho = {};
+            rq.raw = fused_tail;
+            rq.zero_n = fused_tail && tiles_ok && n <= 16 ? n : 0;
+            for (int j = 0; j < rq.zero_n; ++j) rq.zero_ptr[j] = rows[j].probs_out;
+            if ((rc = batch_forward(items.data(), n, draft_logits, ld_draft_logits, &rq, &ho, stream)) != SD_OK) break;
+            if (fused_tail)
+                rc = sd_norm_batch_tiles(ho.logits, n, V, ho.ld, temperature, top_k, top_p, ho.round | draft_norm_mode, rows.data(), 1,
+                                         norm_workspace, ho.tile_max, nullptr, stream);
+            else
+                rc = sd_norm_batch(draft_logits, n, V, ld_draft_logits, temperature, top_k, top_p, draft_norm_mode, rows.data(), 1,
+                                   norm_workspace, stream);
+        }
+        if (rc != SD_OK) break;
+        // ---- verify: the uncached rows of every stream, max_verify streams per pass over the target weights
+        SD_LOOP_HIP(hipEventRecord(ev.t[0], st));
+        for (int a0 = 0; a0 < n && rc == SD_OK; a0 += max_verify) {
+            const int m = std::min(max_verify, n - a0);
+            items.assign(m, sd_batch_item{});
+            rows.clear();
+            for (int j = 0; j < m; ++j) {
+                sd_batch_stream &s = *act[a0 + j];
+                verify_pass_rows(items[j], rows, s.target, s.seq, s.p_hist, ld, s.err_words, g, Ls[a0 + j], s.target_len);
+            }
+            if ((rc = batch_forward(items.data(), m, target_logits, ld_target_logits, nullptr, nullptr, stream)) != SD_OK) break;
+            // one pass holds every stream: the rows' candidate lists (behind the CandRows of the workspace) serve the
+            // residual / bonus sample below
+            rc = sd_norm_batch_tiles(target_logits, (int)rows.size(), V, ld_target_logits, temperature, top_k, top_p, target_norm_mode,
+                                     rows.data(), 0, norm_workspace, nullptr, lists_on ? list_base : nullptr, stream);
+            if (lists_on) {
+                int r0 = 0;
+                for (int j = 0; j < m; ++j) {                       // stream j's lists are valid when all its gamma + 1 rows are here
+                    list_of[a0 + j] = items[j].n_new == g + 1 ? list_base + (size_t)r0 * list_stride : nullptr;
+                    r0 += items[j].n_new;
+                }
+            }
+        }
+        if (rc != SD_OK) break;
+        SD_LOOP_HIP(hipEventRecord(ev.t[1], st));
+        // ---- accept scan + residual / bonus sample, all streams in two launches
+        aitems.assign(n, sd_accept_item{});
+        for (int j = 0; j < n; ++j) {
+            sd_batch_stream &s = *act[j];
+            s.seed = draws[j].seed; s.draw = draws[j].draw;       // both forwards are enqueued: the rest of the iteration's draws
+            sd_accept_item &it = aitems[j];
+            it.p_hist = s.p_hist; it.q_hist = s.q_hist; it.seq = s.seq; it.L = Ls[j];
+            it.r = r_const; it.exp_noise = nullptr;
+            it.philox_seed = draws[j].seed; it.draw_scan = draws[j].scan0; it.draw_resample = draws[j].resample;
+            it.res = s.res_dev; it.err_flags = s.err_words; it.n_err = n_err;
+        }
+        const int res_mode = target_norm_mode == draft_norm_mode ? target_norm_mode : 0;
+        if (lists_on) rc = sd_accept_resample_batch(aitems.data(), n, ld, V, g, res_mode, list_of.data(), stream);
+        else rc = sd_accept_batch(aitems.data(), n, ld, V, g, res_mode, stream);
+        if (rc != SD_OK) break;
+        SD_LOOP_HIP(hipMemcpyAsync(streams[0].res_host, streams[0].res_dev, sizeof(sd_accept_result) * (size_t)n_streams,
+                                   hipMemcpyDeviceToHost, st));
+        SD_LOOP_HIP(hipEventRecord(ev.done, st));
+        if ((rc = poll_event(ev.done, "sd_spec_batch_generate")) != SD_OK) break;
+        if (iters < max_iters_log) {
+            float ms = 0.f;
+            if (verify_ms_out && hipEventElapsedTime(&ms, ev.t[0], ev.t[1]) == hipSuccess) verify_ms_out[iters] = ms;
+            if (verify_streams_out) verify_streams_out[iters] = n;
+            if (verify_ctx_out) verify_ctx_out[iters] = (float)(ctx / n + g);
+        }
+        ++iters;
+        bool failed = false;
+        for (int j = 0; j < n; ++j) {
+            sd_batch_stream &s = *act[j];
+            const sd_accept_result r = *s.res_host;
+            if (r.flags & (2 | 8)) { failed = true; break; }
+            if (s.acc_len_out) s.acc_len_out[s.calls] = r.n_accepted;
+            log_ratios(s.p_at_out, s.q_at_out, (size_t)s.calls, g, r.p_at, r.q_at);
+            ++s.calls;
+            commit_result(r, Ls[j], g, s.host_seq, &s.len, &s.draft_len, &s.target_len);
+            int eos_total = 0;
+            for (int i = 0; i < s.len; ++i) eos_total += s.host_seq[i] == eos_token_id;
+            if (eos_total > s.ori_eos_cnt) s.done = 1;            // the caller cuts after the first new EOS
+        }
+        if (failed) { *err_out = 1; break; }
+    }
+    *n_iters_out = iters;
+    return rc;
+}
+
+// ---- the width-w loop of sampling/multi.py in native code (reference speculative_sampling.py:1379-1716, strategy "iid")
+extern "C" int sd_multi_adopt(const sd_multi_adopt_item *items, int width, const sd_multi_result *res, int L, int gamma,
+                              int draft_lo, int target_lo, int draft_planes, int draft_max_seq, int draft_row_bytes,
+                              int target_planes, int target_max_seq, int target_row_bytes, int seq_cap, void *stream) {
+    SD_REQUIRE(items && res && width >= 1 && width <= 16, "sd_multi_adopt: 1..16 replicas");
+    SD_REQUIRE(gamma >= 1 && gamma <= 16 && L >= 1, "sd_multi_adopt: bad gamma / L");
+    SD_REQUIRE(draft_planes >= 0 && target_planes >= 0 && draft_row_bytes > 0 && target_row_bytes > 0 && draft_lo >= 0 &&
+               target_lo >= 0, "sd_multi_adopt: bad arena shape");
+    // the widest ranges the device may derive: draft [lo, L+gamma-1), target [lo, L+gamma), tokens [L, L+gamma+1)
+    SD_REQUIRE((draft_planes == 0 || L + gamma - 1 <= draft_max_seq) && (target_planes == 0 || L + gamma <= target_max_seq) &&
+               L + gamma + 1 <= seq_cap, "sd_multi_adopt: L %d + gamma %d overruns an arena (max_seq %d / %d) or a token buffer (%d)",
+               L, gamma, draft_max_seq, target_max_seq, seq_cap);
+    AdoptTab t = {};
+    for (int w = 0; w < width; ++w) {
+        SD_REQUIRE(items[w].seq && (draft_planes == 0 || items[w].draft_kv) && (target_planes == 0 || items[w].target_kv),
+                   "sd_multi_adopt: replica %d: null pointer", w);
+        t.d_kv[w] = (char *)items[w].draft_kv; t.t_kv[w] = (char *)items[w].target_kv; t.seq[w] = items[w].seq;
+    }
+    if (width == 1) return SD_OK;                                 // nobody to copy to
+    const AdoptArena d = {draft_planes, draft_max_seq, draft_row_bytes, draft_lo};
+    const AdoptArena tg = {target_planes, target_max_seq, target_row_bytes, target_lo};
+    hipLaunchKernelGGL(multi_adopt_kernel, dim3(draft_planes + target_planes + 1, width), dim3(128), 0, (hipStream_t)stream, t, width,
+                       res, L, gamma, d, tg, seq_cap);
+    SD_LAUNCH_CHECK();
+    return SD_OK;
+}
+
+static inline int kv_planes(const sd_session *s) { return s->m->cfg.n_layers * 2 * s->m->cfg.n_kv_heads; }
+static inline int kv_row_bytes(const sd_session *s) { return s->m->cfg.head_dim * (s->kv_fp8 ? 1 : (int)esize(s->m->cfg.dtype)); }
+
+extern "C" size_t sd_spec_multi_block_bytes(int width, int gamma) {
+    if (width < 1 || gamma < 1) return 0;
+    return sizeof(sd_multi_result) + sizeof(int32_t) * (size_t)width * (3 * gamma + 1);
+}
+
+extern "C" int sd_spec_multi_generate(const sd_multi_replica *reps, int width, int gamma, float temperature, int top_k,
+                                      float top_p, int V, long ld, int seq_cap, int draft_norm_mode, int target_norm_mode,
+                                      float *draft_logits, long ld_draft_logits, float *target_logits, long ld_target_logits,
+                                      void *norm_workspace, int max_rows_per_forward, void *dev_block, void *host_block,
+                                      int32_t *host_seq, int *len_io, int T, int eos_token_id, int ori_eos_cnt,
+                                      uint64_t *seed_io, uint64_t *draw_io, uint64_t random_seed, const float *r_const,
+                                      int *draft_len_io, int *target_len_io, int max_iters, int32_t *acc_len_out,
+                                      float *p_at_out, float *q_at_out, float *draft_ms_out, float *target_ms_out,
+                                      int *n_iters_out, int *err_out, void *stream) {
+    SD_REQUIRE(width >= 1 && width <= 16, "sd_spec_multi_generate: width %d outside 1..16", width);
+    SD_REQUIRE(gamma >= 1 && gamma <= 16, "sd_spec_multi_generate: gamma %d outside 1..16", gamma);
+    SD_REQUIRE(reps && draft_logits && target_logits && dev_block && host_block && host_seq && len_io && seed_io && draw_io &&
+               draft_len_io && target_len_io && n_iters_out && err_out, "sd_spec_multi_generate: null argument");
+    SD_REQUIRE(!random_seed || r_const, "sd_spec_multi_generate: random_seed needs its uniforms (r_const)");
+    SD_REQUIRE(V > 0 && ld >= V, "sd_spec_multi_generate: bad V / ld");
+    for (int w = 0; w < width; ++w) {
+        const sd_multi_replica &r = reps[w];
+        SD_REQUIRE(r.draft && r.target && r.seq && r.q_hist && r.p_hist, "sd_spec_multi_generate: replica %d: null pointer", w);
+        SD_REQUIRE(r.draft->m == reps[0].draft->m && r.target->m == reps[0].target->m && r.draft->max_seq == reps[0].draft->max_seq &&
+                   r.target->max_seq == reps[0].target->max_seq && r.draft->kv_fp8 == reps[0].draft->kv_fp8 &&
+                   r.target->kv_fp8 == reps[0].target->kv_fp8, "sd_spec_multi_generate: replica %d: sessions differ from replica 0's", w);
+    }
+    const int g = gamma, W = width, n_err = 3 * g + 1;
+    const int pass_rows = std::min(max_rows_per_forward, reps[0].target->max_pass_rows);
+    SD_REQUIRE(2 * W <= pass_rows && 2 * W <= std::min(reps[0].draft->max_rows, SD_MAX_ROWS),
+               "sd_spec_multi_generate: width %d: a draft step may carry 2 rows per replica, a pass holds %d", W, pass_rows);
+    SD_REQUIRE(g + 1 <= pass_rows, "sd_spec_multi_generate: gamma %d + 1 verify rows exceed one pass (%d rows)", g, pass_rows);
+    SD_REQUIRE(*len_io >= 1 && T + g + 1 <= seq_cap, "sd_spec_multi_generate: token buffers of %d hold T %d + gamma + 1", seq_cap, T);
+    hipStream_t st = (hipStream_t)stream;
+    sd_multi_result *res_dev = (sd_multi_result *)dev_block;
+    int *err_dev = (int *)((char *)dev_block + sizeof(sd_multi_result));
+    const sd_multi_result *res_host = (const sd_multi_result *)host_block;
+    const int *err_host = (const int *)((const char *)host_block + sizeof(sd_multi_result));
+    const size_t block_bytes = sd_spec_multi_block_bytes(W, g);
+    const bool timed = draft_ms_out || target_ms_out;
+    LoopEvents ev(timed ? 3 : 0, "sd_spec_multi_generate");
+    if (!ev.ok) return SD_ERR_HIP;
+    std::vector<sd_batch_item> items;
+    std::vector<sd_norm_row> rows;
+    sd_multi_item mitems[16];
+    sd_multi_adopt_item aitems[16];
+    for (int w = 0; w < W; ++w) {
+        mitems[w].p_hist = reps[w].p_hist; mitems[w].q_hist = reps[w].q_hist; mitems[w].seq = reps[w].seq;
+        aitems[w].draft_kv = reps[w].draft->kv; aitems[w].target_kv = reps[w].target->kv; aitems[w].seq = reps[w].seq;
+    }
+    const int res_mode = target_norm_mode == draft_norm_mode ? target_norm_mode : 0;
+    int len = *len_io, draft_len = *draft_len_io, target_len = *target_len_io, iters = 0, eos_total = ori_eos_cnt;
+    uint64_t seed = *seed_io, draw = *draw_io;
+    *err_out = 0;
+    int rc = SD_OK;
+    while (len < T && iters < max_iters) {
+        const int L = len, d_lo = draft_len, t_lo = target_len;
+        if (!(draft_len >= 0 && draft_len < L && target_len >= 0 && target_len < L + g)) {
+            sd_set_error("sd_spec_multi_generate: cache lengths %d / %d do not fit a sequence of %d tokens", draft_len, target_len, L);
+            rc = SD_ERR_INVALID;
+            break;
+        }
+        // ---- gamma draft steps, all replicas per pass over the draft weights
+        if (timed) SD_LOOP_HIP(hipEventRecord(ev.t[0], st));
+        for (int i = 0; i < g && rc == SD_OK; ++i) {
+            const uint64_t draw0 = draw;
+            draw += (uint64_t)W;
+            items.assign(W, sd_batch_item{});
+            rows.assign(W, sd_norm_row{});
+            for (int w = 0; w < W; ++w)                            // one shared stream: replica w takes draw0 + w
+                draft_step_rows(items[w], rows[w], reps[w].draft, reps[w].seq, reps[w].q_hist, ld, err_dev + w * n_err, g, L, i,
+                                draft_len, seed, draw0 + (uint64_t)w);
+            if ((rc = batch_forward(items.data(), W, draft_logits, ld_draft_logits, nullptr, nullptr, stream)) != SD_OK) break;
+            rc = sd_norm_batch(draft_logits, W, V, ld_draft_logits, temperature, top_k, top_p, draft_norm_mode, rows.data(), 1,
+                               norm_workspace, stream);
+            draft_len = L + i;
+        }
+        if (rc != SD_OK) break;
+        if (timed) SD_LOOP_HIP(hipEventRecord(ev.t[1], st));
+        // ---- the target over every replica's uncached rows, whole replicas per pass
+        const int n_new = L + g - target_len;
+        const int per_pass = std::max(1, pass_rows / n_new);
+        for (int a = 0; a < W && rc == SD_OK; a += per_pass) {
+            const int m = std::min(per_pass, W - a);
+            items.assign(m, sd_batch_item{});
+            rows.clear();
+            for (int j = 0; j < m; ++j) {
+                const sd_multi_replica &r = reps[a + j];
+                verify_pass_rows(items[j], rows, r.target, r.seq, r.p_hist, ld, err_dev + (a + j) * n_err, g, L, target_len);
+            }
+            if ((rc = batch_forward(items.data(), m, target_logits, ld_target_logits, nullptr, nullptr, stream)) != SD_OK) break;
+            rc = sd_norm_batch(target_logits, (int)rows.size(), V, ld_target_logits, temperature, top_k, top_p, target_norm_mode,
+                               rows.data(), 0, norm_workspace, stream);
+        }
+        if (rc != SD_OK) break;
+        if (timed) SD_LOOP_HIP(hipEventRecord(ev.t[2], st));
+        draw += (uint64_t)W;                                      // the target's own sample, drawn and thrown away
+        // ---- replica scan + residual / bonus sample (one launch), winner broadcast (one launch), one copy, one wait
+        if (random_seed) { seed = random_seed; draw = 0; }        // the reseed quirk: the stream restarts before the uniforms
+        const uint64_t d_scan = draw;
+        draw += (uint64_t)W * g;
+        const uint64_t d_res = draw++;
+        if ((rc = sd_multi_accept_resample(mitems, W, ld, V, L, g, r_const, seed, d_scan, d_res, res_dev, res_mode, stream)) != SD_OK)
+            break;
+        if ((rc = sd_multi_adopt(aitems, W, res_dev, L, g, d_lo, t_lo, kv_planes(reps[0].draft), reps[0].draft->max_seq,
+                                 kv_row_bytes(reps[0].draft), kv_planes(reps[0].target), reps[0].target->max_seq,
+                                 kv_row_bytes(reps[0].target), seq_cap, stream)) != SD_OK)
+            break;
+        SD_LOOP_HIP(hipMemcpyAsync(host_block, dev_block, block_bytes, hipMemcpyDeviceToHost, st));
+        SD_LOOP_HIP(hipEventRecord(ev.done, st));
+        if ((rc = poll_event(ev.done, "sd_spec_multi_generate")) != SD_OK) break;
+        // error words first, a draft sample word before a norm word (multi.py: the scan's result is not looked at then,
+        // and the resample draw is not taken)
+        bool any = false, samp = false;
+        for (int w = 0; w < W; ++w)
+            for (int i = 0; i < n_err; ++i)
+                if (err_host[w * n_err + i]) { any = true; samp = samp || (i >= g && i < 2 * g); }
+        if (any) {
+            *err_out = samp ? 1 : 2;
+            --draw;
+            if (acc_len_out) acc_len_out[iters] = -1;             // the iteration ran (it counts as a call) but was not scanned
+            ++iters;
+            break;
+        }
+        const sd_accept_result r = res_host->chosen;
+        const int l = r.n_accepted, n = r.n;
+        if (!(res_host->choice >= 0 && res_host->choice < W && l >= 0 && l <= g && n == L + l - 1)) {
+            sd_set_error("sd_spec_multi_generate: inconsistent result block (choice %d, n %d, L %d, accepted %d)", res_host->choice,
+                         n, L, l);
+            rc = SD_ERR_INVALID;
+            break;
+        }
+        if (timed) {
+            float dms = 0.f, tms = 0.f;
+            SD_LOOP_HIP(hipEventElapsedTime(&dms, ev.t[0], ev.t[1]));
+            SD_LOOP_HIP(hipEventElapsedTime(&tms, ev.t[1], ev.t[2]));
+            if (draft_ms_out) draft_ms_out[iters] = dms;
+            if (target_ms_out) target_ms_out[iters] = tms;
+        }
+        if (acc_len_out) acc_len_out[iters] = l;
+        for (int w = 0; w < W; ++w)                               // (the block keeps 16 ratios per replica)
+            log_ratios(p_at_out, q_at_out, (size_t)iters * W + w, g, res_host->p_at + w * 16, res_host->q_at + w * 16);
+        ++iters;
+        if (!commit_result(r, L, g, host_seq, &len, &draft_len, &target_len)) { *err_out = 1; break; }   // the resample raised
+        if (r.flags & 4) target_len = L + g;
+        for (int i = L; i < len; ++i) eos_total += host_seq[i] == eos_token_id;
+        if (eos_total > ori_eos_cnt) break;                       // the caller cuts after the first new EOS
+    }
+    *len_io = len; *draft_len_io = draft_len; *target_len_io = target_len;
+    *seed_io = seed; *draw_io = draw; *n_iters_out = iters;
+    return rc;
+}

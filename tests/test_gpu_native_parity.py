@@ -193,6 +193,32 @@ def test_native_bf16_iteration_bit_equals_python_loop(hip, case, capsys):
         assert 0 < sum(da["acc_len"]) < 4 * len(da["acc_len"])   # partial accepts really occur
 
 
+def test_native_bf16_iteration_small_path_2_head_bit_equals_python_loop(hip, capsys):
+    """The native loop's head request arriving at the small-model chain's own head (SD_SMALL_PATH=2: the lm_head with the
+    residual + final norm as its prologue): it leaves the raw slab and the tile maxima for the norm (EPI_HEAD), where the
+    Python-orchestrated loop (verbose=True) takes the same launch's slab through logits_kernel.  Same pair, prompt and
+    Philox seed as the `perturbed` case above: tokens, acc_len and acc_rate must be bit-equal."""
+    os.environ["SD_SMALL_PATH"] = "2"                            # read when a session is made, so before the models
+    try:
+        cfg = ModelConfig(**BF16_CFG)
+        dsd = make_state_dict(cfg, 5, dtype=torch.bfloat16)
+        tsd = {k: v.to(torch.bfloat16) for k, v in perturb_state_dict({a: b.float() for a, b in dsd.items()}, 6, 0.05).items()}
+        prompt = torch.from_numpy(np.random.default_rng(3).integers(3, cfg.vocab_size, size=(1, 24))).cuda()
+        dm = hip.engine.SpecDecModel.from_state_dict(cfg, dsd, dtype=torch.bfloat16)
+        tm = hip.engine.SpecDecModel.from_state_dict(cfg, tsd, dtype=torch.bfloat16)
+        kw = dict(gamma=4, top_k=20, top_p=0.9)
+        a, da = hip.S.speculative_sampling(prompt, dm, tm, -1, None, 40, details=True, rng=hip.noise.DeviceNoise(123), **kw)
+        b, db = hip.S.speculative_sampling(prompt, dm, tm, -1, None, 40, details=True, rng=hip.noise.DeviceNoise(123),
+                                           verbose=True, **kw)
+    finally:
+        os.environ.pop("SD_SMALL_PATH", None)
+    capsys.readouterr()
+    assert torch.equal(a, b)
+    assert da["acc_len"] == db["acc_len"] and da["target_call_times"] == db["target_call_times"]
+    assert float(da["acc_rate"]) == float(db["acc_rate"])
+    assert 0 < sum(da["acc_len"]) < 4 * len(da["acc_len"])       # partial accepts really occur
+
+
 # an OPT pair whose vocab (50272 = 3142 column tiles) has no many-row lm_head kernel: 8 streams x 9 rows verify as 7 + 1 streams
 OPT_BF16_CFG = dict(arch="opt", vocab_size=50272, hidden_size=512, ffn_dim=2048, num_hidden_layers=2, num_attention_heads=8,
                     num_key_value_heads=8, max_position_embeddings=512, do_layer_norm_before=True)
