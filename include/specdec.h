@@ -524,6 +524,43 @@ int sd_spec_multi_generate(const sd_multi_replica *reps, int width, int gamma, f
                            uint64_t random_seed, const float *r_const, int *draft_len_io, int *target_len_io,
                            int max_iters, int32_t *acc_len_out, float *p_at_out, float *q_at_out, float *draft_ms_out,
                            float *target_ms_out, int *n_iters_out, int *err_out, void *stream);
+/* Autoregressive sampling (reference autoregressive_sampling.py:9-61) of up to 16 independent streams in lock-step, no
+ * interpreter between steps.  Per step: the uncached rows seq[cache_len .. len) of every stream that is not done go through
+ * ONE sd_batch_forward; one sd_norm_batch with sample = 1 (on the head's tile maxima where the lock-step draft steps use
+ * them) writes stream b's probability row probs_b[len_b - 1] and samples its token with Philox (seed_b, draw_b) straight
+ * into seq_b[len_b]; one 64-lane launch gathers {int32 token, int32 flags} per stream into dev_block (flags: bit 0 sample
+ * error, bit 1 norm error, bit 2 token == eos_token_id) and clears the error words; ONE async copy of 8 * n_streams bytes to
+ * host_block and ONE stream wait end the step.
+ * Per stream: its session, device token buffer (int32, indexed by absolute position, capacity > T), probability arena
+ * (row stride ld), two device error words (norm error, sample error; zero on entry), host token buffer (capacity >= T,
+ * holding the `len` tokens so far) and the in/out state: len, the length T to reach, cache_len, the Philox position.
+ * A stream is done when it holds T tokens or its new token is eos_token_id (the EOS is kept); done streams drop out of the
+ * later passes.  `draw` advances by one per generated token, cache_len ends at len - 1, `steps` counts the stream's tokens.
+ * One stream may arrive with any cache_len < len (the first step then feeds the whole prompt in chunks, as
+ * sd_session_forward callers do); with more streams every one arrives with cache_len == len - 1 (sd_batch_prefill).
+ * dev_block (device) / host_block (pinned host): sd_ar_block_bytes(n_streams) bytes each = 8 * n_streams rounded up to a
+ * multiple of 16 (0 outside 1..16 streams).  norm_workspace: sd_norm_workspace_bytes(n_streams) bytes, or NULL.
+ * step_ms_out / step_streams_out (host, max_steps_log entries, may be NULL): HIP-event time of each step and the streams in it.
+ * An error word ends the loop after that step, whose tokens are not committed: *err_out 2 = 'norm logits error' (a norm
+ * word, looked at first: the reference normalises before it samples, and the fused sampler sets both words on a row it
+ * cannot normalise), 1 = 'prob error' (a sample word alone); *n_steps_out counts that step.
+ * Limits: n_streams in 1..16 and <= sd_model_max_pass_rows, one model behind all sessions; a violation returns
+ * SD_ERR_INVALID before anything is launched. */
+typedef struct {
+    sd_session *session;
+    int32_t *seq;
+    float *probs;
+    int *err_words;
+    int32_t *host_seq;
+    int32_t len, T, cache_len;
+    uint64_t seed, draw;
+    int32_t done, steps;
+} sd_ar_stream;
+size_t sd_ar_block_bytes(int n_streams);
+int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, float temperature, int top_k, float top_p, int V, long ld,
+                         int eos_token_id, int norm_mode, float *logits, long ld_logits, void *norm_workspace,
+                         void *dev_block, void *host_block, float *step_ms_out, int32_t *step_streams_out,
+                         int max_steps_log, int *n_steps_out, int *err_out, void *stream);
 /* HIP-event timing of the draft phase and the target (verify) phase of the last iteration, on the launch stream. */
 int sd_spec_timing(sd_spec *sp, int on);
 int sd_spec_last_times(sd_spec *sp, float *draft_ms, float *target_ms);

@@ -63,6 +63,12 @@ class SdBatchStream(C.Structure):
                 ("q_at_out", C.c_void_p)]
 
 
+class SdArStream(C.Structure):
+    _fields_ = [("session", C.c_void_p), ("seq", C.c_void_p), ("probs", C.c_void_p), ("err_words", C.c_void_p),
+                ("host_seq", C.c_void_p), ("len", C.c_int32), ("T", C.c_int32), ("cache_len", C.c_int32),
+                ("seed", C.c_uint64), ("draw", C.c_uint64), ("done", C.c_int32), ("steps", C.c_int32)]
+
+
 class SdBatchItem(C.Structure):
     _fields_ = [("session", C.c_void_p), ("seq", C.c_void_p), ("pos0", C.c_int32), ("n_new", C.c_int32),
                 ("n_logits", C.c_int32)]
@@ -141,6 +147,9 @@ SYMBOLS = [
                                     C.c_long, _VP, C.c_long, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
     ("sd_spec_generate", _I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP,
                               _VP, _VP, _VP]),
+    ("sd_ar_block_bytes", C.c_size_t, [_I]),
+    ("sd_ar_batch_generate", _I, [C.POINTER(SdArStream), _I, _F, _I, _F, _I, _L, _I, _I, _VP, _L, _VP, _VP, _VP, _VP, _VP, _I,
+                                  _VP, _VP, _VP]),
     ("sd_batch_forward", _I, [C.POINTER(SdBatchItem), _I, _VP, _L, _VP]),
     ("sd_batch_prefill", _I, [C.POINTER(SdBatchItem), _I, _VP]),
     ("sd_spec_create", _I, [_VP, _VP, _I, _F, _I, _F, _VP, _VP, _VP, _L, _VP, _L, _VP, _L, _VP, _VP, _VP, C.POINTER(_VP)]),

@@ -1,5 +1,6 @@
-// spec_loops.h - the native decode loops (single stream, lock-step streams, width-w iid) and the steps they share.  Host code,
-// included at the end of engine.hip, whose sd_session, HeadReq / HeadOut and session_forward / batch_forward it uses.
+// spec_loops.h - the native decode loops (single stream, lock-step streams, width-w iid, autoregressive streams) and the steps
+// they share.  Host code - and the one small kernel of the autoregressive loop's hand-off - included at the end of
+// engine.hip, whose sd_session, HeadReq / HeadOut and session_forward / batch_forward it uses.
 #pragma once
 
 // SD_NORM_DT_* of a model's probability rows: OPT keeps logits and probabilities in the weight dtype
@@ -682,5 +683,132 @@ extern "C" int sd_spec_multi_generate(const sd_multi_replica *reps, int width, i
     }
     *len_io = len; *draft_len_io = draft_len; *target_len_io = target_len;
     *seed_io = seed; *draw_io = draw; *n_iters_out = iters;
+    return rc;
+}
+
+// ---- autoregressive sampling of up to 16 lock-step streams (reference autoregressive_sampling.py:9-61 per stream)
+// What one step hands to the host: per stream its fresh token and flag bits (1 sample error, 2 norm error, 4 token == eos)
+struct ArSlot { int32_t token, flags; };
+// The streams of one step by value, indexed by stream; a stream that sits the step out has seq == NULL
+struct ArTab {
+    const int32_t *seq[16];
+    int *err[16];                 // {norm error, sample error}
+    int len[16];                  // the step sampled seq[len]
+};
+
+// One 64-lane workgroup, lane b for stream b: the 8-byte slot of every stream in one vector store each, and the two error
+// words cleared for the next step.  Ordered behind the sampler by the stream alone.
+__global__ __launch_bounds__(64) void ar_collect_kernel(ArTab t, int n_streams, int eos, ArSlot *__restrict__ out) {
+    const int b = threadIdx.x;
+    if (b >= n_streams || b >= 16) return;
+    ArSlot s = {0, 0};
+    if (t.seq[b]) {
+        int *e = t.err[b];
+        s.token = t.seq[b][t.len[b]];
+        s.flags = (e[1] != 0 ? 1 : 0) | (e[0] != 0 ? 2 : 0) | (s.token == eos ? 4 : 0);
+        e[0] = 0; e[1] = 0;
+    }
+    *reinterpret_cast<int2 *>(out + b) = make_int2(s.token, s.flags);
+}
+
+extern "C" size_t sd_ar_block_bytes(int n_streams) {
+    if (n_streams < 1 || n_streams > 16) return 0;
+    return ((size_t)n_streams * sizeof(ArSlot) + 15) & ~(size_t)15;
+}
+
+extern "C" int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, float temperature, int top_k, float top_p, int V,
+                                    long ld, int eos_token_id, int norm_mode, float *logits, long ld_logits,
+                                    void *norm_workspace, void *dev_block, void *host_block, float *step_ms_out,
+                                    int32_t *step_streams_out, int max_steps_log, int *n_steps_out, int *err_out,
+                                    void *stream) {
+    SD_REQUIRE(n_streams >= 1 && n_streams <= 16, "sd_ar_batch_generate: n_streams %d outside 1..16", n_streams);
+    SD_REQUIRE(streams && logits && dev_block && host_block && n_steps_out && err_out, "sd_ar_batch_generate: null argument");
+    SD_REQUIRE(V > 0 && ld >= V && temperature != 0.0f, "sd_ar_batch_generate: bad V / ld / temperature");
+    for (int b = 0; b < n_streams; ++b) {
+        const sd_ar_stream &s = streams[b];
+        SD_REQUIRE(s.session && s.seq && s.probs && s.err_words && s.host_seq, "sd_ar_batch_generate: stream %d: null pointer", b);
+        SD_REQUIRE(s.len >= 1 && s.cache_len >= 0 && s.cache_len < s.len, "sd_ar_batch_generate: stream %d: cache_len %d of %d tokens",
+                   b, s.cache_len, s.len);
+        SD_REQUIRE(n_streams == 1 || s.cache_len == s.len - 1,
+                   "sd_ar_batch_generate: stream %d: with more than one stream every stream arrives prefilled (cache_len %d, len %d - 1)",
+                   b, s.cache_len, s.len);
+    }
+    for (int b = 0; b < n_streams; ++b)
+        SD_REQUIRE(streams[b].session->m == streams[0].session->m, "sd_ar_batch_generate: stream %d: session of another model", b);
+    SD_REQUIRE(n_streams <= streams[0].session->max_pass_rows, "sd_ar_batch_generate: %d streams exceed one pass (%d rows)", n_streams,
+               streams[0].session->max_pass_rows);
+    hipStream_t st = (hipStream_t)stream;
+    const bool timed = step_ms_out != nullptr;
+    LoopEvents ev(timed ? 2 : 0, "sd_ar_batch_generate");
+    if (!ev.ok) return SD_ERR_HIP;
+    const bool tiles_ok = head_tiles_ok(top_k, temperature, V, ld);
+    const ArSlot *slots = (const ArSlot *)host_block;
+    std::vector<sd_batch_item> items;
+    std::vector<sd_norm_row> rows;
+    int act[16];
+    for (int b = 0; b < n_streams; ++b) { streams[b].done = 0; streams[b].steps = 0; }
+    *err_out = 0;
+    int steps = 0, rc = SD_OK;
+    for (;;) {
+        int n = 0;
+        for (int b = 0; b < n_streams; ++b) {
+            sd_ar_stream &s = streams[b];
+            if (!s.done && s.len >= s.T) s.done = 1;
+            if (!s.done) act[n++] = b;
+        }
+        if (n == 0) break;
+        // ---- an autoregressive step is draft step 0 of a gamma = 1 iteration run on the stream's own model: the uncached
+        // rows, logits for the last, sampled with (seed, draw) into seq[len]; error words {norm, sample}
+        items.assign(n, sd_batch_item{});
+        rows.assign(n, sd_norm_row{});
+        ArTab tab = {};
+        HeadReq rq = {};
+        HeadOut ho = {};
+        rq.raw = true;                                            // the lock-step draft step's sampler feed (see there)
+        rq.zero_n = tiles_ok ? n : 0;
+        for (int j = 0; j < n; ++j) {
+            sd_ar_stream &s = streams[act[j]];
+            draft_step_rows(items[j], rows[j], s.session, s.seq, s.probs, ld, s.err_words, 1, s.len, 0, s.cache_len, s.seed, s.draw);
+            rq.zero_ptr[j] = rows[j].probs_out;
+            tab.seq[act[j]] = s.seq; tab.err[act[j]] = s.err_words; tab.len[act[j]] = s.len;
+        }
+        if (timed) SD_LOOP_HIP(hipEventRecord(ev.t[0], st));
+        if (n_streams == 1 && items[0].n_new > 1)                 // the prompt: chunked like the interpreter loop's first forward
+            rc = feed_rows(items[0].session, items[0].seq, items[0].pos0, items[0].pos0 + items[0].n_new, 1, logits, ld_logits, &rq,
+                           &ho, stream);
+        else
+            rc = batch_forward(items.data(), n, logits, ld_logits, &rq, &ho, stream);
+        if (rc != SD_OK) break;
+        if ((rc = sd_norm_batch_tiles(ho.logits, n, V, ho.ld, temperature, top_k, top_p, ho.round | norm_mode, rows.data(), 1,
+                                      norm_workspace, ho.tile_max, nullptr, stream)) != SD_OK)
+            break;
+        // ---- the hand-off: 8 bytes per stream, one copy, one wait
+        hipLaunchKernelGGL(ar_collect_kernel, dim3(1), dim3(64), 0, st, tab, n_streams, eos_token_id, (ArSlot *)dev_block);
+        SD_LOOP_HIP(hipGetLastError());
+        SD_LOOP_HIP(hipMemcpyAsync(host_block, dev_block, sizeof(ArSlot) * (size_t)n_streams, hipMemcpyDeviceToHost, st));
+        if (timed) SD_LOOP_HIP(hipEventRecord(ev.t[1], st));
+        SD_LOOP_HIP(hipEventRecord(ev.done, st));
+        if ((rc = poll_event(ev.done, "sd_ar_batch_generate")) != SD_OK) break;
+        if (steps < max_steps_log) {
+            float ms = 0.f;
+            if (timed && hipEventElapsedTime(&ms, ev.t[0], ev.t[1]) == hipSuccess) step_ms_out[steps] = ms;
+            if (step_streams_out) step_streams_out[steps] = n;
+        }
+        ++steps;
+        int flags = 0;
+        for (int j = 0; j < n; ++j) flags |= slots[act[j]].flags;
+        // the norm word first: the reference normalises before it samples (autoregressive_sampling.py:48-50), and the fused
+        // sampler sets both words on a row it cannot normalise
+        if (flags & 3) { *err_out = (flags & 2) ? 2 : 1; break; }
+        for (int j = 0; j < n; ++j) {
+            sd_ar_stream &s = streams[act[j]];
+            const ArSlot r = slots[act[j]];
+            s.host_seq[s.len] = r.token;
+            s.cache_len = s.len;                                  // every token but the new one is cached
+            ++s.len; ++s.draw; ++s.steps;
+            if (r.flags & 4) s.done = 1;                          // the EOS is kept (:55)
+        }
+    }
+    *n_steps_out = steps;
     return rc;
 }

@@ -1,9 +1,12 @@
 """Drop-in for reference sampling/autoregressive_sampling.py:8-61 (``autoregressive_sampling``)."""
 from __future__ import annotations
 
+import ctypes as C
+
+import numpy as np
 import torch
 
-from .._lib import lib, check
+from .._lib import lib, check, SdArStream
 from ..engine import as_specdec_model, _stream, check_token_ids
 from ..noise import DeviceNoise, HostTorchNoise
 from .kvcache_model import KVCacheModel
@@ -11,9 +14,11 @@ from .kvcache_model import KVCacheModel
 
 @torch.no_grad()
 def autoregressive_sampling(x: torch.Tensor, model, N: int, eos_token_id: int, temperature: float = 1,
-                            top_k: int = 0, top_p: float = 0, pad_token_id=None, *, rng=None):
+                            top_k: int = 0, top_p: float = 0, pad_token_id=None, *, rng=None, _native: bool = True):
     """reference autoregressive_sampling.py:9-61: exactly N tokens unless EOS is drawn (the EOS is kept).
-    RNG contract: one ``sample`` per token."""
+    RNG contract: one ``sample`` per token.  With the device RNG the whole loop is one native call
+    (sd_ar_batch_generate with one stream); ``_native=False`` keeps the interpreter loop below, which the host RNG
+    and ReplayNoise always take (same tokens, same exceptions)."""
     assert x.shape[0] == 1
     m = as_specdec_model(model)
     dev = m.device
@@ -31,7 +36,11 @@ def autoregressive_sampling(x: torch.Tensor, model, N: int, eos_token_id: int, t
     seq32 = torch.zeros(L0 + N + 1, dtype=torch.int32, device=dev)
     seq32[:L0] = x[0].to(device=dev, dtype=torch.int32)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    st = _stream()
+    if _native and getattr(noise, "on_device", False):
+        run = ArRun(m, temperature, top_k, top_p, eos_token_id)
+        run.add(kv, seq32, x[0].to(device="cpu", dtype=torch.int32).numpy(), L0 + N, noise)
+        run.generate()
+        return torch.from_numpy(run.tokens(0)).to(torch.int64).unsqueeze(0).to(x.device)
     n_out = 0
     # the EOS test needs each token on the host (autoregressive_sampling.py:55): one 4-byte read per step
     for i in range(N):
@@ -39,9 +48,67 @@ def autoregressive_sampling(x: torch.Tensor, model, N: int, eos_token_id: int, t
         kv.forward_sample(seq32, S, noise, err)
         n_out += 1
         tok = int(seq32[S])
+        kv.check_errors(S - 1, S)         # first, as the reference normalises before it samples (a NaN row sets both words)
         if int(err) != 0:
             raise RuntimeError("prob error")
-        kv.check_errors(S - 1, S)
         if tok == eos_token_id:
             break
     return seq32[:L0 + n_out].to(torch.int64).unsqueeze(0).to(x.device)
+
+
+class ArRun:
+    """One call of sd_ar_batch_generate: the streams' table, the host token buffers and the 8-byte-per-stream hand-off
+    blocks; shared by autoregressive_sampling (one stream) and sampling.batch.autoregressive_sampling_batch."""
+
+    def __init__(self, model, temperature, top_k, top_p, eos_token_id):
+        self.m = model
+        self.args = (float(temperature), int(top_k or 0), float(top_p or 0.0))
+        self.eos = -1 if eos_token_id is None else int(eos_token_id)
+        self.streams = []                                         # (kv, seq32, host tokens, err words, noise)
+        self.steps = []                                           # (ms, n_streams) per step, filled by generate(timing=True)
+
+    def add(self, kv: KVCacheModel, seq32: torch.Tensor, prompt: np.ndarray, T: int, noise) -> None:
+        """A stream whose session holds ``kv.cache_len`` of the ``len(prompt)`` tokens in seq32 and is to reach T tokens."""
+        host = np.zeros(T + 1, dtype=np.int32)
+        host[:len(prompt)] = prompt
+        err = torch.zeros(2, dtype=torch.int32, device=self.m.device)
+        self.streams.append((kv, seq32, host, err, noise, len(prompt), int(T)))
+
+    def generate(self, timing: bool = False) -> None:
+        B = len(self.streams)
+        if not 1 <= B <= 16:
+            raise ValueError(f"autoregressive sampling takes 1..16 streams per call, not {B}")
+        dev = self.m.device
+        arr = (SdArStream * B)()
+        for it, (kv, seq32, host, err, noise, L, T) in zip(arr, self.streams):
+            it.session, it.seq, it.probs = kv._session.handle, seq32.data_ptr(), kv._probs.data_ptr()
+            it.err_words, it.host_seq = err.data_ptr(), host.ctypes.data
+            it.len, it.T, it.cache_len = L, T, kv._session.cache_len
+            it.seed, it.draw = noise.seed, noise.draw
+        nb = lib.sd_ar_block_bytes(B)
+        dev_block = torch.zeros(nb, dtype=torch.uint8, device=dev)
+        host_block = torch.zeros(nb, dtype=torch.uint8).pin_memory()
+        kv0 = self.streams[0][0]
+        norm_ws = kv0._norm_ws if B <= kv0._session.max_rows else None
+        n_log = max(T - L for (_, _, _, _, _, L, T) in self.streams) if timing else 0
+        ms = np.zeros(max(n_log, 1), dtype=np.float32)
+        cnt = np.zeros(max(n_log, 1), dtype=np.int32)
+        n_steps, c_err = C.c_int(0), C.c_int(0)
+        ses0 = kv0._session
+        rc = lib.sd_ar_batch_generate(arr, B, *self.args, self.m.cfg.vocab_size, kv0._probs.stride(0), self.eos, self.m.norm_mode,
+                                      ses0.logits.data_ptr(), ses0.logits.stride(0),
+                                      norm_ws.data_ptr() if norm_ws is not None else None, dev_block.data_ptr(),
+                                      host_block.data_ptr(), ms.ctypes.data if timing else None,
+                                      cnt.ctypes.data if timing else None, n_log, C.byref(n_steps), C.byref(c_err), _stream())
+        self.lens = []
+        for it, (kv, _, _, _, noise, _, _) in zip(arr, self.streams):   # the state the loop left, also after a failure
+            kv._session.cache_len = it.cache_len
+            noise.draw = it.draw
+            self.lens.append(it.len)
+        check(rc, "sd_ar_batch_generate")
+        if c_err.value:
+            raise RuntimeError("norm logits error" if c_err.value == 2 else "prob error")
+        self.steps = [(float(ms[i]), int(cnt[i])) for i in range(min(n_steps.value, n_log))]
+
+    def tokens(self, i: int) -> np.ndarray:
+        return self.streams[i][2][:self.lens[i]]

@@ -18,6 +18,7 @@ import torch
 from .._lib import lib, check, SdAcceptResult, SdBatchStream
 from ..engine import as_specdec_model, _stream, check_token_ids, same_device, batch_prefill
 from ..noise import DeviceNoise
+from .autoregressive_sampling import ArRun
 from .kvcache_model import KVCacheModel
 
 
@@ -166,3 +167,44 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
                "target_post_prob_time": 0} for s in streams]
         return outs, ds
     return outs
+
+
+@torch.no_grad()
+def autoregressive_sampling_batch(xs: Sequence[torch.Tensor], model, N: int, eos_token_id, temperature: float = 1,
+                                  top_k: int = 0, top_p: float = 0, pad_token_id=None, *,
+                                  seeds: Optional[Sequence[int]] = None, _timing: Optional[dict] = None):
+    """``autoregressive_sampling`` for B streams at once: ``xs[i]`` is (1, L_i) int64, the result a list of (1, len_i)
+    tensors.  The streams decode in lock-step and share every pass over the weights (sd_ar_batch_generate): each runs the
+    algorithm of reference autoregressive_sampling.py:9-61 on its own Philox stream ``seeds[i]`` (default
+    ``torch.initial_seed() + i``), so the outputs equal those of B ``autoregressive_sampling(..., rng=DeviceNoise(seed))``
+    calls.  ``_timing["step"]`` receives (milliseconds, streams in the step) per step."""
+    B = len(xs)
+    if not 1 <= B <= 16:
+        raise ValueError(f"autoregressive_sampling_batch takes 1..16 streams per call, not {B}")
+    m = as_specdec_model(model)
+    dev = m.device
+    V = m.cfg.vocab_size
+    for x in xs:
+        assert x.dim() == 2 and x.shape[0] == 1 and x.shape[1] >= 1, "every stream is one (1, L) prompt"
+        check_token_ids(x, V)
+    seeds = list(seeds) if seeds is not None else [int(torch.initial_seed()) + i for i in range(B)]
+    run = ArRun(m, temperature, top_k, top_p, eos_token_id)
+    kvs, seqs = [], []
+    for x, seed in zip(xs, seeds):
+        L = x.shape[1]
+        cap = L + int(N) + 1
+        kv = KVCacheModel(m, temperature, top_k, top_p, max_seq=cap, full_history=False)
+        kv._ensure(cap)
+        seq32 = torch.zeros(cap, dtype=torch.int32, device=dev)
+        seq32[:L] = x[0].to(device=dev, dtype=torch.int32)
+        kvs.append(kv)
+        seqs.append(seq32)
+    # everything but the last prompt token, the prompts packed into shared passes; every step of the loop then feeds one
+    # row per stream
+    batch_prefill([kv._session for kv in kvs], seqs, [x.shape[1] - 1 for x in xs])
+    for x, seed, kv, seq32 in zip(xs, seeds, kvs, seqs):
+        run.add(kv, seq32, x[0].to(device="cpu", dtype=torch.int32).numpy(), x.shape[1] + int(N), DeviceNoise(seed))
+    run.generate(timing=_timing is not None)
+    if _timing is not None:
+        _timing.setdefault("step", []).extend(run.steps)
+    return [torch.from_numpy(run.tokens(i)).to(torch.int64).unsqueeze(0).to(x.device) for i, x in enumerate(xs)]

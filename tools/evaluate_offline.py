@@ -28,8 +28,8 @@ from llmspeculativesampling_amd import harness  # noqa: E402
 from llmspeculativesampling_amd.config import load_config  # noqa: E402
 from llmspeculativesampling_amd.engine import SpecDecModel  # noqa: E402
 from llmspeculativesampling_amd.quality import get_score  # noqa: E402
-from llmspeculativesampling_amd.sampling import (autoregressive_sampling, multi_speculative_sampling,  # noqa: E402
-                                                 speculative_sampling)
+from llmspeculativesampling_amd.sampling import (autoregressive_sampling, autoregressive_sampling_batch,  # noqa: E402
+                                                 multi_speculative_sampling, speculative_sampling)
 
 
 def parse_arguments():
@@ -50,6 +50,9 @@ def parse_arguments():
     p.add_argument("--dtype", default="bfloat16", choices=["bfloat16", "float32"])
     p.add_argument("--rng", default="host", choices=["host", "device"])
     p.add_argument("--skip", default="", help="comma list of loops to skip: ar,ss,iid")
+    p.add_argument("--ar-streams", type=int, default=0, metavar="B",
+                   help="also run the autoregressive arm B (1..16) prompts at a time in lock-step (device RNG) and print "
+                        "its tokens/s; 0 = off")
     return p.parse_args()
 
 
@@ -114,6 +117,24 @@ def main():
                         emit([f"terminated at {n_done}"])
                         break
             emit(harness.large_model_log_lines(total_ns, tokens, scores, pm.total()))
+
+        # ---- the same arm as a throughput run: B prompts per call share every pass over the target's weights
+        if "ar" not in skip and args.ar_streams > 0:
+            tokens, wall = 0, 0.0
+            for g0 in range(0, len(ds), args.ar_streams):
+                group = [ids.cuda() for ids in ds[g0:g0 + args.ar_streams]]
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                outs = autoregressive_sampling_batch(group, large, args.max_tokens, eos_token_id=tok.eos_token_id,
+                                                     top_k=top_k, top_p=top_p, pad_token_id=tok.pad_token_id)
+                torch.cuda.synchronize()
+                wall += time.perf_counter() - t
+                tokens += sum(o.size(1) - ids.size(1) for o, ids in zip(outs, group))
+                if wall > args.max_seconds:
+                    emit([f"terminated at {g0 + len(group)}"])
+                    break
+            emit([f"autoregressive, {args.ar_streams} lock-step streams (device RNG): total time {wall} s, total tokens "
+                  f"{tokens}, {tokens / max(wall, 1e-9)} tokens/s"])
 
         # ---- speculative sampling (evaluation.py:515-583) and the iid variant
         loops = []
