@@ -1,0 +1,112 @@
+"""Host-side steps the decode-loop wrappers share (speculative_sampling, batch, multi, autoregressive_sampling): each
+piece of reference semantics - the EOS rule, the reseed quirk, how the acceptance ratio is rounded - is written once."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from ..noise import DeviceNoise, HostTorchNoise
+from .kvcache_model import KVCacheModel
+
+
+def make_noise(rng, device):
+    if rng is None or rng == "host":
+        return HostTorchNoise(device)
+    if rng == "device":
+        return DeviceNoise(seed=int(torch.initial_seed()))
+    return rng
+
+
+def cut_after_new_eos(tokens: list, eos_token_id, ori_eos_cnt: int) -> list:
+    """EOS rule over the whole sequence (reference speculative_sampling.py:2033-2041): the prefix up to and including EOS
+    number ``ori_eos_cnt + 1``; ``tokens`` itself (the same object) when no new EOS was produced."""
+    seen = 0
+    for idx, x in enumerate(tokens):
+        if x == eos_token_id:
+            seen += 1
+            if seen == ori_eos_cnt + 1:
+                return tokens[:idx + 1]
+    return tokens
+
+
+def reseed_uniforms(random_seed, n: int, device):
+    """reseed-before-every-r quirk (:1976-1977): all r of a call are one and the same draw, whatever was accepted."""
+    if not random_seed:
+        return None
+    g = torch.Generator().manual_seed(int(random_seed))
+    return torch.rand(1, generator=g).repeat(n).to(device)
+
+
+def accept_rates_f64(p_at, q_at) -> list:
+    """min(1, p / q) as the python double ratio of two float32 values, like the reference's .item() division (:1966-1971)."""
+    return np.minimum(1.0, np.asarray(p_at).astype(np.float64) / np.asarray(q_at).astype(np.float64)).tolist()
+
+
+def accept_rates_f32_zero_q(p_at, q_at) -> list:
+    """The width-w loop's form (:1597): fp32 division as p[...] / q[...], clamped to 1, and 0 where q is 0."""
+    qa = np.asarray(q_at, dtype=np.float32).ravel()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.asarray(p_at, dtype=np.float32).ravel() / qa
+    return [0 if q == 0 else (1 if a > 1 else a) for a, q in zip(ratio.tolist(), qa.tolist())]
+
+
+def open_stream(model, prompt_row, cap: int, seq_len: int, temperature, top_k, top_p, noise=None):
+    """One decode stream's device state: a KVCacheModel with arenas for ``cap`` positions and, when ``seq_len`` is not 0,
+    an int32 token buffer of that length that starts with the prompt (else None)."""
+    kv = KVCacheModel(model, temperature, top_k, top_p, max_seq=cap, noise=noise, full_history=False)
+    kv._ensure(cap)
+    if not seq_len:
+        return kv, None
+    dev = kv._model.device
+    seq32 = torch.zeros(seq_len, dtype=torch.int32, device=dev)
+    seq32[:len(prompt_row)] = prompt_row.to(device=dev, dtype=torch.int32)
+    return kv, seq32
+
+
+class LoopLog:
+    """The host arrays one native loop call (or one stream of it) writes: the token buffer, the accepted length per
+    iteration, ``per_iter`` logged p / q values per iteration and, when ``timed``, the two phases' milliseconds."""
+
+    def __init__(self, tokens, seq_cap: int, max_iters: int, per_iter: int, q_fill: float, timed: bool = False):
+        self.host_seq = np.zeros(seq_cap, dtype=np.int32)
+        self.host_seq[:len(tokens)] = tokens
+        self.per_iter = per_iter
+        self.acc = np.zeros(max_iters, dtype=np.int32)
+        self.p_at = np.zeros(max_iters * per_iter, dtype=np.float32)
+        self.q_at = np.full(max_iters * per_iter, q_fill, dtype=np.float32)   # what a slot no iteration wrote divides by
+        self.draft_ms = np.zeros(max_iters, dtype=np.float32) if timed else None
+        self.target_ms = np.zeros(max_iters, dtype=np.float32) if timed else None
+
+    def ptrs(self) -> tuple:
+        """(acc_len, p_at, q_at, draft_ms, target_ms) as the native calls take them; the last two None when not timed."""
+        ms = (self.draft_ms, self.target_ms)
+        return tuple(a.ctypes.data if a is not None else None for a in (self.acc, self.p_at, self.q_at) + ms)
+
+    def tokens(self, n: int) -> list:
+        return self.host_seq[:n].tolist()
+
+    def acc_len(self, calls: int) -> list:
+        return self.acc[:calls].tolist()
+
+    def ratios(self, calls: int) -> tuple:
+        return self.p_at[:calls * self.per_iter], self.q_at[:calls * self.per_iter]
+
+    def phase_ns(self, calls: int) -> tuple:
+        """(draft, target) device time: every entry truncated to whole nanoseconds, then summed; zeros when not timed."""
+        if self.draft_ms is None:
+            return 0, 0
+        return tuple(int(sum(int(v * 1e6) for v in ms[:calls])) for ms in (self.draft_ms, self.target_ms))
+
+
+def raise_loop_error(code: int) -> None:
+    """The native loops' err_out as the reference's exceptions (utils.py:224, :207)."""
+    if code == 1:
+        raise RuntimeError("prob error")
+    if code == 2:
+        raise RuntimeError("norm logits error")
+
+
+def details_dict(approx_time, target_time, other_time, acc_len, acc_rate, target_calls, approx_calls, **more) -> dict:
+    """The reference's ``details`` keys in its order; ``more``: the three target_* times of speculative_sampling."""
+    return {"approx_time": approx_time, "target_time": target_time, "other_time": other_time, "acc_len": acc_len,
+            "acc_rate": acc_rate, "target_call_times": target_calls, "approx_call_times": approx_calls, **more}

@@ -2,13 +2,14 @@
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 import torch
 
 from .._lib import lib, check, SdArStream
 from ..engine import as_specdec_model, _stream, check_token_ids
-from ..noise import DeviceNoise, HostTorchNoise
+from ._loop_common import make_noise, open_stream, raise_loop_error
 from .kvcache_model import KVCacheModel
 
 
@@ -25,16 +26,8 @@ def autoregressive_sampling(x: torch.Tensor, model, N: int, eos_token_id: int, t
     V = m.cfg.vocab_size
     L0 = x.shape[1]
     check_token_ids(x, V)
-    if rng is None or rng == "host":
-        noise = HostTorchNoise(dev)
-    elif rng == "device":
-        noise = DeviceNoise(seed=int(torch.initial_seed()))
-    else:
-        noise = rng
-    kv = KVCacheModel(m, temperature, top_k, top_p, max_seq=L0 + N + 1, noise=noise, full_history=False)
-    kv._ensure(L0 + N + 1)
-    seq32 = torch.zeros(L0 + N + 1, dtype=torch.int32, device=dev)
-    seq32[:L0] = x[0].to(device=dev, dtype=torch.int32)
+    noise = make_noise(rng, dev)
+    kv, seq32 = open_stream(m, x[0], L0 + N + 1, L0 + N + 1, temperature, top_k, top_p, noise)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     if _native and getattr(noise, "on_device", False):
         run = ArRun(m, temperature, top_k, top_p, eos_token_id)
@@ -56,6 +49,17 @@ def autoregressive_sampling(x: torch.Tensor, model, N: int, eos_token_id: int, t
     return seq32[:L0 + n_out].to(torch.int64).unsqueeze(0).to(x.device)
 
 
+@dataclass
+class _ArStream:
+    kv: KVCacheModel
+    seq32: torch.Tensor
+    host: np.ndarray             # the host token buffer, T + 1 long
+    err: torch.Tensor
+    noise: object
+    L: int
+    T: int
+
+
 class ArRun:
     """One call of sd_ar_batch_generate: the streams' table, the host token buffers and the 8-byte-per-stream hand-off
     blocks; shared by autoregressive_sampling (one stream) and sampling.batch.autoregressive_sampling_batch."""
@@ -64,7 +68,7 @@ class ArRun:
         self.m = model
         self.args = (float(temperature), int(top_k or 0), float(top_p or 0.0))
         self.eos = -1 if eos_token_id is None else int(eos_token_id)
-        self.streams = []                                         # (kv, seq32, host tokens, err words, noise)
+        self.streams = []                                         # _ArStream per add()
         self.steps = []                                           # (ms, n_streams) per step, filled by generate(timing=True)
 
     def add(self, kv: KVCacheModel, seq32: torch.Tensor, prompt: np.ndarray, T: int, noise) -> None:
@@ -72,7 +76,7 @@ class ArRun:
         host = np.zeros(T + 1, dtype=np.int32)
         host[:len(prompt)] = prompt
         err = torch.zeros(2, dtype=torch.int32, device=self.m.device)
-        self.streams.append((kv, seq32, host, err, noise, len(prompt), int(T)))
+        self.streams.append(_ArStream(kv, seq32, host, err, noise, len(prompt), int(T)))
 
     def generate(self, timing: bool = False) -> None:
         B = len(self.streams)
@@ -80,17 +84,17 @@ class ArRun:
             raise ValueError(f"autoregressive sampling takes 1..16 streams per call, not {B}")
         dev = self.m.device
         arr = (SdArStream * B)()
-        for it, (kv, seq32, host, err, noise, L, T) in zip(arr, self.streams):
-            it.session, it.seq, it.probs = kv._session.handle, seq32.data_ptr(), kv._probs.data_ptr()
-            it.err_words, it.host_seq = err.data_ptr(), host.ctypes.data
-            it.len, it.T, it.cache_len = L, T, kv._session.cache_len
-            it.seed, it.draw = noise.seed, noise.draw
+        for it, s in zip(arr, self.streams):
+            it.session, it.seq, it.probs = s.kv._session.handle, s.seq32.data_ptr(), s.kv._probs.data_ptr()
+            it.err_words, it.host_seq = s.err.data_ptr(), s.host.ctypes.data
+            it.len, it.T, it.cache_len = s.L, s.T, s.kv._session.cache_len
+            it.seed, it.draw = s.noise.seed, s.noise.draw
         nb = lib.sd_ar_block_bytes(B)
         dev_block = torch.zeros(nb, dtype=torch.uint8, device=dev)
         host_block = torch.zeros(nb, dtype=torch.uint8).pin_memory()
-        kv0 = self.streams[0][0]
+        kv0 = self.streams[0].kv
         norm_ws = kv0._norm_ws if B <= kv0._session.max_rows else None
-        n_log = max(T - L for (_, _, _, _, _, L, T) in self.streams) if timing else 0
+        n_log = max(s.T - s.L for s in self.streams) if timing else 0
         ms = np.zeros(max(n_log, 1), dtype=np.float32)
         cnt = np.zeros(max(n_log, 1), dtype=np.int32)
         n_steps, c_err = C.c_int(0), C.c_int(0)
@@ -101,14 +105,13 @@ class ArRun:
                                       host_block.data_ptr(), ms.ctypes.data if timing else None,
                                       cnt.ctypes.data if timing else None, n_log, C.byref(n_steps), C.byref(c_err), _stream())
         self.lens = []
-        for it, (kv, _, _, _, noise, _, _) in zip(arr, self.streams):   # the state the loop left, also after a failure
-            kv._session.cache_len = it.cache_len
-            noise.draw = it.draw
+        for it, s in zip(arr, self.streams):                      # the state the loop left, also after a failure
+            s.kv._session.cache_len = it.cache_len
+            s.noise.draw = it.draw
             self.lens.append(it.len)
         check(rc, "sd_ar_batch_generate")
-        if c_err.value:
-            raise RuntimeError("norm logits error" if c_err.value == 2 else "prob error")
+        raise_loop_error(c_err.value)
         self.steps = [(float(ms[i]), int(cnt[i])) for i in range(min(n_steps.value, n_log))]
 
     def tokens(self, i: int) -> np.ndarray:
-        return self.streams[i][2][:self.lens[i]]
+        return self.streams[i].host[:self.lens[i]]

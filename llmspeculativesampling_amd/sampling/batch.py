@@ -10,6 +10,7 @@ same seeds the outputs equal those of B separate ``speculative_sampling(..., rng
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -18,14 +19,30 @@ import torch
 from .._lib import lib, check, SdAcceptResult, SdBatchStream
 from ..engine import as_specdec_model, _stream, check_token_ids, same_device, batch_prefill
 from ..noise import DeviceNoise
+from ._loop_common import LoopLog, accept_rates_f64, cut_after_new_eos, details_dict, open_stream, reseed_uniforms
 from .autoregressive_sampling import ArRun
 from .kvcache_model import KVCacheModel
 
 
+@dataclass
 class _Stream:
-    __slots__ = ("idx", "draft", "target", "seq32", "host", "noise", "ori_eos", "T", "done", "out", "acc_len",
-                 "acc_rate", "calls", "draft_len", "target_len", "err", "prompt_len", "q_ptr", "p_ptr", "seq_ptr",
-                 "err_ptr")
+    draft: KVCacheModel
+    target: KVCacheModel
+    seq32: torch.Tensor
+    err: torch.Tensor
+    noise: DeviceNoise
+    log: LoopLog
+    prompt_len: int
+    T: int
+    ori_eos: int
+
+
+class _Ms:                                                        # (bench.py reads e0.elapsed_time(e1))
+    def __init__(self, ms):
+        self.ms = ms
+
+    def elapsed_time(self, _other):
+        return self.ms
 
 
 @torch.no_grad()
@@ -48,38 +65,21 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
     res_sz = C.sizeof(SdAcceptResult)
     res_dev = torch.zeros((B, res_sz), dtype=torch.uint8, device=dev)
     res_host = torch.zeros((B, res_sz), dtype=torch.uint8).pin_memory()
-    n_err = 3 * gamma + 1
-    r_const = None
-    if random_seed:
-        g = torch.Generator().manual_seed(int(random_seed))
-        r_const = torch.rand(1, generator=g).repeat(gamma).to(dev)
+    r_const = reseed_uniforms(random_seed, gamma, dev)
+    max_iters = max(1, int(max_len)) + 1
 
     streams: List[_Stream] = []
     for i, pf in enumerate(prefixes):
         assert pf.shape[0] == 1, "input batch size must be 1"
-        st = _Stream()
-        st.idx = i
         L = pf.shape[1]
-        st.prompt_len = L
-        st.T = L + max_len
-        cap = st.T + gamma + 2
-        st.draft = KVCacheModel(draft_m, temperature, top_k, top_p, max_seq=cap, full_history=False)
-        st.target = KVCacheModel(target_m, temperature, top_k, top_p, max_seq=cap, full_history=False)
-        st.draft._ensure(cap)
-        st.target._ensure(cap)
-        st.seq32 = torch.zeros(cap + 1, dtype=torch.int32, device=dev)
-        st.seq32[:L] = pf[0].to(device=dev, dtype=torch.int32)
-        st.host = [int(t) for t in pf[0].tolist()]
-        st.ori_eos = sum(1 for t in st.host if t == eos_token_id)
-        st.noise = DeviceNoise(seeds[i])
-        st.done = False
-        st.out = st.host
-        st.acc_len, st.acc_rate, st.calls = [], [], 0
-        st.err = torch.zeros(n_err, dtype=torch.int32, device=dev)
-        st.draft_len = st.target_len = L - 1
-        st.q_ptr, st.p_ptr = st.draft._probs.data_ptr(), st.target._probs.data_ptr()
-        st.seq_ptr, st.err_ptr = st.seq32.data_ptr(), st.err.data_ptr()
-        streams.append(st)
+        T = L + max_len
+        cap = T + gamma + 2
+        draft, _ = open_stream(draft_m, None, cap, 0, temperature, top_k, top_p)
+        target, seq32 = open_stream(target_m, pf[0], cap, cap + 1, temperature, top_k, top_p)
+        host = [int(t) for t in pf[0].tolist()]
+        err = torch.zeros(3 * gamma + 1, dtype=torch.int32, device=dev)
+        streams.append(_Stream(draft, target, seq32, err, DeviceNoise(seeds[i]),
+                               LoopLog(host, cap, max_iters, gamma, q_fill=1.0), L, T, host.count(eos_token_id)))
 
     # prefill everything but the last prompt token, the B prompts packed into passes of up to 256 rows (engine.batch_prefill:
     # one pass over the weights serves several streams); the decode loop then starts with 1 new draft row and gamma+1 new
@@ -95,26 +95,17 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
     norm_ws = torch.empty(lib.sd_norm_workspace_bytes(per_pass), dtype=torch.uint8, device=dev)
     cu = _stream()
     arr = (SdBatchStream * B)()
-    keep = []                                                     # host arrays the native loop writes into
-    max_iters = max(1, int(max_len)) + 1
-    for s in streams:
-        cap = s.T + gamma + 2
-        hs = np.zeros(cap, dtype=np.int32)
-        hs[:len(s.host)] = s.host
-        acc = np.zeros(max_iters, dtype=np.int32)
-        pa = np.zeros(max_iters * gamma, dtype=np.float32)
-        qa = np.ones(max_iters * gamma, dtype=np.float32)
-        keep.append((hs, acc, pa, qa))
-        it = arr[s.idx]
+    for i, (it, s) in enumerate(zip(arr, streams)):
         it.draft, it.target = s.draft._session.handle, s.target._session.handle
-        it.seq, it.q_hist, it.p_hist, it.err_words = s.seq_ptr, s.q_ptr, s.p_ptr, s.err_ptr
-        it.res_dev = res_dev.data_ptr() + s.idx * res_sz
-        it.res_host = res_host.data_ptr() + s.idx * res_sz
-        it.host_seq = hs.ctypes.data
-        it.len, it.T, it.ori_eos_cnt = len(s.host), s.T, s.ori_eos
-        it.draft_len, it.target_len = s.draft_len, s.target_len
+        it.seq, it.q_hist, it.p_hist = s.seq32.data_ptr(), s.draft._probs.data_ptr(), s.target._probs.data_ptr()
+        it.err_words = s.err.data_ptr()
+        it.res_dev = res_dev.data_ptr() + i * res_sz
+        it.res_host = res_host.data_ptr() + i * res_sz
+        it.host_seq = s.log.host_seq.ctypes.data
+        it.len, it.T, it.ori_eos_cnt = s.prompt_len, s.T, s.ori_eos
+        it.draft_len = it.target_len = s.prompt_len - 1
         it.seed, it.draw = s.noise.seed, s.noise.draw
-        it.acc_len_out, it.p_at_out, it.q_at_out = acc.ctypes.data, pa.ctypes.data, qa.ctypes.data
+        it.acc_len_out, it.p_at_out, it.q_at_out = s.log.ptrs()[:3]
     n_log = max_iters * 2
     v_ms = np.zeros(n_log, dtype=np.float32)
     v_n = np.zeros(n_log, dtype=np.int32)
@@ -131,42 +122,18 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
     if c_err.value:
         raise RuntimeError("s")
     if _timing is not None:
-        class _Ms:                                                # (bench.py reads e0.elapsed_time(e1))
-            def __init__(self, ms):
-                self.ms = ms
-
-            def elapsed_time(self, _other):
-                return self.ms
         for i in range(min(c_iters.value, n_log)):
             _timing.setdefault("verify", []).append((_Ms(float(v_ms[i])), None, int(v_n[i]), float(v_ctx[i])))
-    for s, (hs, acc, pa, qa) in zip(streams, keep):
-        it = arr[s.idx]
-        s.host = hs[:it.len].tolist()
-        s.calls = it.calls
-        s.acc_len = acc[:it.calls].tolist()
-        s.acc_rate = np.minimum(1.0, pa[:it.calls * gamma].astype(np.float64) / qa[:it.calls * gamma].astype(np.float64)).tolist()
-        s.draft_len, s.target_len = it.draft_len, it.target_len
+    outs, ds = [], []
+    for it, s, pf in zip(arr, streams, prefixes):
         s.noise.seed, s.noise.draw = it.seed, it.draw
-        s.draft._session.cache_len, s.target._session.cache_len = s.draft_len, s.target_len
-        s.out = s.host
-        if sum(1 for x in s.host if x == eos_token_id) > s.ori_eos:
-            seen, cut = 0, len(s.host)
-            for idx, x in enumerate(s.host):
-                if x == eos_token_id:
-                    seen += 1
-                    if seen == s.ori_eos + 1:
-                        cut = idx + 1
-                        break
-            s.out = s.host[:cut]
-
-    outs = [torch.tensor([s.out], dtype=torch.int64, device=prefixes[i].device) for i, s in enumerate(streams)]
-    if details:
-        ds = [{"approx_time": 0, "target_time": 0, "other_time": 0, "acc_len": s.acc_len,
-               "acc_rate": float(np.mean(s.acc_rate)) if s.acc_rate else 0.0, "target_call_times": s.calls,
-               "approx_call_times": s.calls, "target_model_time": 0, "target_pre_cache_time": 0,
-               "target_post_prob_time": 0} for s in streams]
-        return outs, ds
-    return outs
+        s.draft._session.cache_len, s.target._session.cache_len = it.draft_len, it.target_len
+        out = cut_after_new_eos(s.log.tokens(it.len), eos_token_id, s.ori_eos)
+        outs.append(torch.tensor([out], dtype=torch.int64, device=pf.device))
+        rate = accept_rates_f64(*s.log.ratios(it.calls))
+        ds.append(details_dict(0, 0, 0, s.log.acc_len(it.calls), float(np.mean(rate)) if rate else 0.0, it.calls, it.calls,
+                               target_model_time=0, target_pre_cache_time=0, target_post_prob_time=0))
+    return (outs, ds) if details else outs
 
 
 @torch.no_grad()
@@ -182,23 +149,14 @@ def autoregressive_sampling_batch(xs: Sequence[torch.Tensor], model, N: int, eos
     if not 1 <= B <= 16:
         raise ValueError(f"autoregressive_sampling_batch takes 1..16 streams per call, not {B}")
     m = as_specdec_model(model)
-    dev = m.device
     V = m.cfg.vocab_size
     for x in xs:
         assert x.dim() == 2 and x.shape[0] == 1 and x.shape[1] >= 1, "every stream is one (1, L) prompt"
         check_token_ids(x, V)
     seeds = list(seeds) if seeds is not None else [int(torch.initial_seed()) + i for i in range(B)]
     run = ArRun(m, temperature, top_k, top_p, eos_token_id)
-    kvs, seqs = [], []
-    for x, seed in zip(xs, seeds):
-        L = x.shape[1]
-        cap = L + int(N) + 1
-        kv = KVCacheModel(m, temperature, top_k, top_p, max_seq=cap, full_history=False)
-        kv._ensure(cap)
-        seq32 = torch.zeros(cap, dtype=torch.int32, device=dev)
-        seq32[:L] = x[0].to(device=dev, dtype=torch.int32)
-        kvs.append(kv)
-        seqs.append(seq32)
+    caps = [x.shape[1] + int(N) + 1 for x in xs]
+    kvs, seqs = map(list, zip(*[open_stream(m, x[0], cap, cap, temperature, top_k, top_p) for x, cap in zip(xs, caps)]))
     # everything but the last prompt token, the prompts packed into shared passes; every step of the loop then feeds one
     # row per stream
     batch_prefill([kv._session for kv in kvs], seqs, [x.shape[1] - 1 for x in xs])

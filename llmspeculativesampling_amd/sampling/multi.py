@@ -30,8 +30,8 @@ import torch
 from .. import _lib
 from .._lib import lib, check, SdMultiItem, SdMultiReplica, SdMultiResult, SdNormRow, SpecDecError
 from ..engine import as_specdec_model, batch_forward, _stream, MAX_ROWS_PER_FORWARD, check_token_ids, same_device
-from .kvcache_model import KVCacheModel
-from .speculative_sampling import _make_noise
+from ._loop_common import (LoopLog, accept_rates_f32_zero_q, cut_after_new_eos, details_dict, make_noise, open_stream,
+                           raise_loop_error, reseed_uniforms)
 
 
 def _copy_positions(dst_ses, src_ses, lo: int, hi: int) -> None:
@@ -68,6 +68,20 @@ class _MultiRun:
     r_const: torch.Tensor
 
 
+@dataclass
+class _MultiResult:
+    """What one sd_spec_multi_generate call left; ``rc`` and ``err`` are for the caller to raise on."""
+    rc: int
+    err: int
+    tokens: list
+    acc_len: list
+    acc_rate: list
+    calls: int
+    approx_time: int
+    target_time: int
+    other_time: int
+
+
 def _native_multi_loop(run: _MultiRun, host, cache_len, noise, timed):
     """Device-RNG mode: ONE call into libspecdec (sd_spec_multi_generate) runs every iteration - draft steps, verify passes,
     the fused scan + resample launch, the winner broadcast launch, one copy and one stream wait each - and the interpreter
@@ -76,8 +90,6 @@ def _native_multi_loop(run: _MultiRun, host, cache_len, noise, timed):
     draft_m, target_m, W = drafts[0]._model, targets[0]._model, len(drafts)
     V, ld = target_m.cfg.vocab_size, drafts[0]._probs.stride(0)
     Tk, Kk, Pk = run.sampling
-    eos_token_id, ori_eos, random_seed, norm_ws, r_const = run.eos_token_id, run.ori_eos, run.random_seed, run.norm_ws, run.r_const
-    draft_len = target_len = cache_len
     dev = target_m.device
     d_ses, t_ses = [m._session for m in drafts], [m._session for m in targets]
     reps = (SdMultiReplica * W)()
@@ -87,27 +99,19 @@ def _native_multi_loop(run: _MultiRun, host, cache_len, noise, timed):
     nbytes = lib.sd_spec_multi_block_bytes(W, gamma)
     dev_block = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
     host_block = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
-    seq_host = np.zeros(T + gamma + 2, dtype=np.int32)
-    seq_host[:len(host)] = host
     max_iters = max(1, T - len(host))
-    acc_arr = np.zeros(max_iters, dtype=np.int32)
-    p_arr = np.zeros(max_iters * W * gamma, dtype=np.float32)
-    q_arr = np.zeros(max_iters * W * gamma, dtype=np.float32)
-    dms_arr = np.zeros(max_iters, dtype=np.float32)
-    tms_arr = np.zeros(max_iters, dtype=np.float32)
-    c_len, c_dl, c_tl = C.c_int(len(host)), C.c_int(draft_len), C.c_int(target_len)
+    log = LoopLog(host, T + gamma + 2, max_iters, W * gamma, q_fill=0.0, timed=timed)
+    c_len, c_dl, c_tl = C.c_int(len(host)), C.c_int(cache_len), C.c_int(cache_len)
     c_seed, c_draw = C.c_uint64(noise.seed), C.c_uint64(noise.draw)
     c_iters, c_err = C.c_int(0), C.c_int(0)
     tick = process_time_ns()
     rc = lib.sd_spec_multi_generate(
         reps, W, gamma, Tk, Kk, Pk, V, ld, seqs[0].numel(), draft_m.norm_mode, target_m.norm_mode,
         d_ses[0].logits.data_ptr(), d_ses[0].logits.stride(0), t_ses[0].logits.data_ptr(), t_ses[0].logits.stride(0),
-        norm_ws.data_ptr(), t_ses[0].max_pass_rows, dev_block.data_ptr(), host_block.data_ptr(), seq_host.ctypes.data,
-        C.byref(c_len), T, int(eos_token_id) if eos_token_id is not None else -1, int(ori_eos), C.byref(c_seed),
-        C.byref(c_draw), int(random_seed or 0), r_const.data_ptr() if r_const is not None else None, C.byref(c_dl),
-        C.byref(c_tl), max_iters, acc_arr.ctypes.data, p_arr.ctypes.data, q_arr.ctypes.data,
-        dms_arr.ctypes.data if timed else None, tms_arr.ctypes.data if timed else None, C.byref(c_iters), C.byref(c_err),
-        _stream())
+        run.norm_ws.data_ptr(), t_ses[0].max_pass_rows, dev_block.data_ptr(), host_block.data_ptr(), log.host_seq.ctypes.data,
+        C.byref(c_len), T, int(run.eos_token_id) if run.eos_token_id is not None else -1, int(run.ori_eos), C.byref(c_seed),
+        C.byref(c_draw), int(run.random_seed or 0), run.r_const.data_ptr() if run.r_const is not None else None,
+        C.byref(c_dl), C.byref(c_tl), max_iters, *log.ptrs(), C.byref(c_iters), C.byref(c_err), _stream())
     other_time = process_time_ns() - tick                             # host CPU time of the call (enqueue + waits + bookkeeping)
     noise.seed, noise.draw = c_seed.value, c_draw.value
     for ses in d_ses:
@@ -115,17 +119,9 @@ def _native_multi_loop(run: _MultiRun, host, cache_len, noise, timed):
     for ses in t_ses:
         ses.cache_len = c_tl.value
     calls = c_iters.value
-    n_acc = calls - 1 if calls and acc_arr[calls - 1] < 0 else calls  # an iteration ended by an error word was not scanned
-    acc_len = acc_arr[:n_acc].tolist()
-    pa = p_arr[:n_acc * W * gamma]
-    qa = q_arr[:n_acc * W * gamma]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        ratio = pa / qa                                               # fp32 division, as p[...] / q[...] (:1597)
-    acc_rate = [0 if q == 0 else (1 if a > 1 else a) for a, q in zip(ratio.tolist(), qa.tolist())]
-    approx_time = int(sum(int(v * 1e6) for v in dms_arr[:calls])) if timed else 0
-    target_time = int(sum(int(v * 1e6) for v in tms_arr[:calls])) if timed else 0
-    out = seq_host[:c_len.value].tolist()
-    return rc, c_err.value, out, acc_len, acc_rate, calls, approx_time, target_time, other_time
+    n_acc = calls - 1 if calls and log.acc[calls - 1] < 0 else calls  # an iteration ended by an error word was not scanned
+    return _MultiResult(rc, c_err.value, log.tokens(c_len.value), log.acc_len(n_acc),
+                        accept_rates_f32_zero_q(*log.ratios(n_acc)), calls, *log.phase_ns(calls), other_time)
 
 
 @torch.no_grad()
@@ -154,18 +150,14 @@ def multi_speculative_sampling(prefix: torch.Tensor, approx_model, target_model,
     T = L0 + max_len
     cap = T + gamma + 2
     host = [int(t) for t in prefix[0].tolist()]
-    ori_eos = sum(1 for t in host if t == eos_token_id)
-    noise = _make_noise(rng, dev)
+    ori_eos = host.count(eos_token_id)
+    noise = make_noise(rng, dev)
     on_dev = getattr(noise, "on_device", False)
 
-    drafts = [KVCacheModel(draft_m, temperature, top_k, top_p, max_seq=cap, full_history=False) for _ in range(W)]
-    targets = [KVCacheModel(target_m, temperature, top_k, top_p, max_seq=cap, full_history=False) for _ in range(W)]
-    for m in drafts + targets:
-        m._ensure(cap)
+    drafts = [open_stream(draft_m, None, cap, 0, temperature, top_k, top_p)[0] for _ in range(W)]
+    targets, seqs = map(list, zip(*[open_stream(target_m, prefix[0], cap, cap + 1, temperature, top_k, top_p)
+                                    for _ in range(W)]))
     d_ses, t_ses = [m._session for m in drafts], [m._session for m in targets]
-    seqs = [torch.zeros(cap + 1, dtype=torch.int32, device=dev) for _ in range(W)]
-    for s in seqs:
-        s[:L0] = prefix[0].to(device=dev, dtype=torch.int32)
     # the prompt but its last token goes through each model once; the other replicas get copies of those KV rows
     # (the reference runs the same rows width times, kvcache_model.py:156 with a (width, L) batch)
     if L0 > 1:
@@ -178,10 +170,7 @@ def multi_speculative_sampling(prefix: torch.Tensor, approx_model, target_model,
 
     norm_ws = torch.empty(lib.sd_norm_workspace_bytes(MAX_ROWS_PER_FORWARD), dtype=torch.uint8, device=dev)
     ld = drafts[0]._probs.stride(0)
-    r_const = None
-    if random_seed and on_dev:
-        g = torch.Generator().manual_seed(int(random_seed))
-        r_const = torch.rand(1, generator=g).repeat(W * gamma).to(dev)
+    r_const = reseed_uniforms(random_seed, W * gamma, dev) if on_dev else None
     Tk, Kk, Pk = float(temperature), int(top_k or 0), float(top_p or 0.0)
     native = _takes_native_loop(noise, verbose)
     if not native:                                   # the Python loop's own buffers and tables
@@ -210,23 +199,12 @@ def multi_speculative_sampling(prefix: torch.Tensor, approx_model, target_model,
             check_token_ids(host, V)                                   # nn.Embedding's IndexError, swallowed below
         if native and len(host) < T:
             run = _MultiRun(drafts, targets, seqs, T, gamma, eos_token_id, ori_eos, random_seed, (Tk, Kk, Pk), norm_ws, r_const)
-            rc, err_code, out, acc_len, acc_rate, approx_calls, approx_time, target_time, other_time = _native_multi_loop(
-                run, host, draft_len, noise, details)
-            target_calls = approx_calls
-            host = out
-            _check_native(rc)
-            if err_code == 1:
-                raise RuntimeError("prob error")                       # reference utils.py:224
-            if err_code == 2:
-                raise RuntimeError("norm logits error")                # reference utils.py:207
-            if sum(1 for x in host if x == eos_token_id) > ori_eos:    # EOS rule (:1688-1695)
-                seen = 0
-                for idx, x in enumerate(host):
-                    if x == eos_token_id:
-                        seen += 1
-                        if seen == ori_eos + 1:
-                            out = host[:idx + 1]
-                            break
+            res = _native_multi_loop(run, host, draft_len, noise, details)
+            out, acc_len, acc_rate, approx_calls, target_calls = res.tokens, res.acc_len, res.acc_rate, res.calls, res.calls
+            approx_time, target_time, other_time = res.approx_time, res.target_time, res.other_time
+            _check_native(res.rc)
+            raise_loop_error(res.err)
+            out = cut_after_new_eos(out, eos_token_id, ori_eos)        # EOS rule (:1688-1695)
         while not native and len(host) < T:
             L = len(host)
             tt = process_time_ns()
@@ -311,16 +289,7 @@ def multi_speculative_sampling(prefix: torch.Tensor, approx_model, target_model,
             all_accept = bool(res.chosen.flags & 4)
             pa = np.ctypeslib.as_array(res.p_at).reshape(16, 16)[:W, :gamma].astype(np.float32)
             qa = np.ctypeslib.as_array(res.q_at).reshape(16, 16)[:W, :gamma].astype(np.float32)
-            with np.errstate(divide="ignore", invalid="ignore"):
-                ratio = pa / qa                                        # fp32 division, as p[...] / q[...] (:1597)
-            for w in range(W):
-                for i in range(gamma):
-                    a = float(ratio[w, i])
-                    if a > 1:
-                        a = 1
-                    if qa[w, i] == 0:
-                        a = 0
-                    acc_rate.append(a)
+            acc_rate.extend(accept_rates_f32_zero_q(pa, qa))           # replica by replica
             acc_len.append(l)
             # ---- residual / bonus sample on the winner's rows (:1645-1679)
             if on_dev:
@@ -348,16 +317,8 @@ def multi_speculative_sampling(prefix: torch.Tensor, approx_model, target_model,
                     _copy_positions(t_ses[w], t_ses[choice], t_lo, new_target)
             draft_len, target_len = new_draft, new_target
             other_time += process_time_ns() - tt
-            out = host
-            if sum(1 for x in host if x == eos_token_id) > ori_eos:    # EOS rule (:1688-1695)
-                seen, cut = 0, len(host)
-                for idx, x in enumerate(host):
-                    if x == eos_token_id:
-                        seen += 1
-                        if seen == ori_eos + 1:
-                            cut = idx + 1
-                            break
-                out = host[:cut]
+            out = cut_after_new_eos(host, eos_token_id, ori_eos)       # EOS rule (:1688-1695)
+            if out is not host:                                        # a new EOS was produced
                 break
     except SpecDecError:                                               # an engine failure is never swallowed
         raise
@@ -371,7 +332,6 @@ def multi_speculative_sampling(prefix: torch.Tensor, approx_model, target_model,
         print("other time", other_time / 1e9)
         print("acc len", np.mean(acc_len) if acc_len else 0.0, len(acc_len), acc_len)
     if details:
-        return result, {"approx_time": approx_time, "target_time": target_time, "other_time": other_time,
-                        "acc_len": acc_len, "acc_rate": np.mean(acc_rate) if acc_rate else 0.0,
-                        "target_call_times": target_calls, "approx_call_times": approx_calls}
+        return result, details_dict(approx_time, target_time, other_time, acc_len, np.mean(acc_rate) if acc_rate else 0.0,
+                                    target_calls, approx_calls)
     return result

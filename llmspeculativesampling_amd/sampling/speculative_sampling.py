@@ -16,16 +16,10 @@ import torch
 
 from .._lib import lib, check, SdAcceptResult
 from ..engine import as_specdec_model, _stream, check_token_ids, same_device
-from ..noise import DeviceNoise, HostTorchNoise
-from .kvcache_model import KVCacheModel
+from ._loop_common import (LoopLog, accept_rates_f64, cut_after_new_eos, details_dict, make_noise, open_stream,
+                           raise_loop_error, reseed_uniforms)
 
-
-def _make_noise(rng, device):
-    if rng is None or rng == "host":
-        return HostTorchNoise(device)
-    if rng == "device":
-        return DeviceNoise(seed=int(torch.initial_seed()))
-    return rng
+_make_noise = make_noise                              # beam.py, multi.py and tests import it from here
 
 
 @torch.no_grad()
@@ -59,17 +53,16 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
         except IndexError as e:
             print(e)
             raise RuntimeError("s") from e
-    ori_eos_cnt = sum(1 for t in host_seq if t == eos_token_id)
-    noise = _make_noise(rng, dev)
+    noise = make_noise(rng, dev)
+    draft, _ = open_stream(draft_m, None, cap, 0, temperature, top_k, top_p, noise)
+    target, seq32 = open_stream(target_m, prefix[0], cap, cap + 1, temperature, top_k, top_p, noise)
+    if getattr(noise, "on_device", False) and not verbose:
+        return _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T, gamma, random_seed, details,
+                                   noise, _event_logs)
 
-    draft = KVCacheModel(draft_m, temperature, top_k, top_p, max_seq=cap, noise=noise, full_history=False)
-    target = KVCacheModel(target_m, temperature, top_k, top_p, max_seq=cap, noise=noise, full_history=False)
-    draft._ensure(cap)
-    target._ensure(cap)
+    ori_eos_cnt = host_seq.count(eos_token_id)
     if _event_logs is not None:                       # bench.py: HIP-event brackets around every forward
         draft.event_log, target.event_log = _event_logs
-    seq32 = torch.zeros(cap + 1, dtype=torch.int32, device=dev)
-    seq32[:seq_len0] = prefix[0].to(device=dev, dtype=torch.int32)
     res_dev = torch.zeros(C.sizeof(SdAcceptResult), dtype=torch.uint8, device=dev)
     res_host = torch.zeros(C.sizeof(SdAcceptResult), dtype=torch.uint8).pin_memory()
     tok_host = torch.zeros(gamma + 2, dtype=torch.int32).pin_memory()
@@ -80,11 +73,6 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
     # p - q, max_fn and the residual draw run in the rows' dtype when both models keep 16-bit rows (OPT)
     res_mode = target_m.norm_mode if target_m.norm_mode == draft_m.norm_mode else 0
     res_dtype = target_m.probs_dtype if res_mode else torch.float32
-
-    if getattr(noise, "on_device", False) and not verbose:
-        return _native_device_loop(prefix, draft, target, seq32, host_seq, ori_eos_cnt, eos_token_id, T, gamma,
-                                   temperature, top_k, top_p, random_seed, details, noise, res_dev, res_host, tok_host,
-                                   _event_logs)
 
     approx_time = target_time = other_time = 0
     approx_calls = target_calls = 0
@@ -120,8 +108,7 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
                     # stream restarts after it, whatever was accepted
                     noise.reseed(random_seed)
                     if r_const is None:
-                        g = torch.Generator().manual_seed(int(random_seed))
-                        r_const = torch.rand(1, generator=g).repeat(gamma).to(dev)
+                        r_const = reseed_uniforms(random_seed, gamma, dev)
                     check(lib.sd_accept_scan(p_hist.data_ptr(), q_hist.data_ptr(), ld, seq32.data_ptr(), L, gamma,
                                              r_const.data_ptr(), 0, 0, res_dev.data_ptr(), st), "sd_accept_scan")
                 else:
@@ -160,20 +147,11 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
             host_seq = host_seq + drafted + [t]
             draft.rollback(n + 1)
             target.rollback(n + 1 if l < gamma else n + 2)
-            out_tokens = host_seq
             if verbose:
                 print(f"accepted {l} of {gamma}: {drafted} + {t}")
             # ---- EOS rule over the whole sequence (:2033-2041)
-            eos_total = sum(1 for x in host_seq if x == eos_token_id)
-            if eos_total > ori_eos_cnt:
-                seen, cut = 0, len(host_seq)
-                for idx, x in enumerate(host_seq):
-                    if x == eos_token_id:
-                        seen += 1
-                        if seen == ori_eos_cnt + 1:
-                            cut = idx + 1
-                            break
-                out_tokens = host_seq[:cut]
+            out_tokens = cut_after_new_eos(host_seq, eos_token_id, ori_eos_cnt)
+            if out_tokens is not host_seq:            # a new EOS was produced
                 break
             other_time += process_time_ns() - tick
     except Exception as e:                            # (:2044-2046); the cause stays attached to the traceback
@@ -184,115 +162,74 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
     if verbose:
         print(f"generated tokens numbers {len(host_seq) - seq_len0}, acc len {acc_len}")
     if details:
-        return out, {
-            "approx_time": approx_time, "target_time": target_time, "other_time": other_time,
-            "acc_len": acc_len, "acc_rate": np.mean(acc_rate),
-            "target_call_times": target_calls, "approx_call_times": approx_calls,
-            "target_model_time": target.forward_time_dict["_model_time"],
-            "target_pre_cache_time": target.forward_time_dict["prepare_cache_time"],
-            "target_post_prob_time": target.forward_time_dict["norm_prob_time"],
-        }
+        return out, details_dict(approx_time, target_time, other_time, acc_len, np.mean(acc_rate), target_calls, approx_calls,
+                                 target_model_time=target.forward_time_dict["_model_time"],
+                                 target_pre_cache_time=target.forward_time_dict["prepare_cache_time"],
+                                 target_post_prob_time=target.forward_time_dict["norm_prob_time"])
     return out
 
 
-def _native_device_loop(prefix, draft, target, seq32, host_seq, ori_eos_cnt, eos_token_id, T, gamma, temperature,
-                        top_k, top_p, random_seed, details, noise, res_dev, res_host, tok_host, timing_log):
-    """Device-RNG mode: every iteration is ONE call into libspecdec (sd_spec_iteration) that enqueues the gamma draft
-    steps, the target forward, the accept scan and the resample; the host waits on the stream once per iteration and
-    reads 208 + 4*(gamma+2) bytes from pinned memory.  Same loop semantics as the Python-orchestrated path above
-    (reference speculative_sampling.py:1934-2046)."""
+def _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T, gamma, random_seed, details, noise,
+                        timing_log):
+    """Device-RNG mode: the loop itself runs inside libspecdec (sd_spec_generate): per iteration the gamma draft steps,
+    the target forward, the accept scan and the resample are enqueued and the stream is waited on once, in native code;
+    the interpreter only sees the finished sequence and the per-iteration statistics.  Same loop semantics as the
+    Python-orchestrated path above (reference speculative_sampling.py:1934-2046)."""
     dev = target._model.device
-    V = target._model.cfg.vocab_size
-    seq_len0 = prefix.shape[1]
+    seq_len0 = len(host_seq)
+    ori_eos_cnt = host_seq.count(eos_token_id)
+    res_dev = torch.zeros(C.sizeof(SdAcceptResult), dtype=torch.uint8, device=dev)
+    res_host = torch.zeros(C.sizeof(SdAcceptResult), dtype=torch.uint8).pin_memory()
     err_words = torch.zeros(3 * gamma + 1, dtype=torch.int32, device=dev)
     sp = C.c_void_p()
-    check(lib.sd_spec_create(draft._session.handle, target._session.handle, gamma, float(temperature), int(top_k or 0),
-                             float(top_p or 0.0), seq32.data_ptr(), draft._probs.data_ptr(), target._probs.data_ptr(),
-                             draft._probs.stride(0), draft._session.logits.data_ptr(), draft._session.logits.stride(0),
-                             target._session.logits.data_ptr(), target._session.logits.stride(0), err_words.data_ptr(),
-                             res_dev.data_ptr(), target._norm_ws.data_ptr(), C.byref(sp)), "sd_spec_create")
+    check(lib.sd_spec_create(draft._session.handle, target._session.handle, gamma, float(target._temperature),
+                             int(target._top_k or 0), float(target._top_p or 0.0), seq32.data_ptr(), draft._probs.data_ptr(),
+                             target._probs.data_ptr(), draft._probs.stride(0), draft._session.logits.data_ptr(),
+                             draft._session.logits.stride(0), target._session.logits.data_ptr(),
+                             target._session.logits.stride(0), err_words.data_ptr(), res_dev.data_ptr(),
+                             target._norm_ws.data_ptr(), C.byref(sp)), "sd_spec_create")
     timed = timing_log is not None or details          # HIP-event brackets around the draft and the verify phase
     if timed:
         check(lib.sd_spec_timing(sp, 1), "sd_spec_timing")
-    r_const = None
-    if random_seed:
-        g = torch.Generator().manual_seed(int(random_seed))
-        r_const = torch.rand(1, generator=g).repeat(gamma).to(dev)
-    st = _stream()
-    approx_time = target_time = other_time = 0
-    calls = 0
-    acc_rate, acc_len = [], []
-    draft_len = target_len = 0
-    # the loop itself runs inside libspecdec (sd_spec_generate): one call, one stream wait per iteration in native code,
-    # the interpreter only sees the finished sequence and the per-iteration statistics
-    cap = T + gamma + 2
-    seq_host = np.zeros(cap, dtype=np.int32)
-    seq_host[:len(host_seq)] = host_seq
-    max_iters = max(1, T - len(host_seq))
-    acc_arr = np.zeros(max_iters, dtype=np.int32)
-    p_arr = np.zeros(max_iters * gamma, dtype=np.float32)
-    q_arr = np.ones(max_iters * gamma, dtype=np.float32)
-    dms_arr = np.zeros(max_iters, dtype=np.float32)
-    tms_arr = np.zeros(max_iters, dtype=np.float32)
-    c_len, c_dl, c_tl = C.c_int(len(host_seq)), C.c_int(0), C.c_int(0)
+    r_const = reseed_uniforms(random_seed, gamma, dev)
+    max_iters = max(1, T - seq_len0)
+    log = LoopLog(host_seq, T + gamma + 2, max_iters, gamma, q_fill=1.0, timed=timed)
+    c_len, c_dl, c_tl = C.c_int(seq_len0), C.c_int(0), C.c_int(0)
     c_seed, c_draw = C.c_uint64(noise.seed), C.c_uint64(noise.draw)
     c_iters, c_err = C.c_int(0), C.c_int(0)
-    out_tokens = host_seq
     try:
         tick = process_time_ns()
-        check(lib.sd_spec_generate(sp, seq_host.ctypes.data, C.byref(c_len), T, int(eos_token_id), int(ori_eos_cnt),
+        check(lib.sd_spec_generate(sp, log.host_seq.ctypes.data, C.byref(c_len), T, int(eos_token_id), ori_eos_cnt,
                                    C.byref(c_seed), C.byref(c_draw), int(random_seed or 0),
                                    r_const.data_ptr() if r_const is not None else None, C.byref(c_dl), C.byref(c_tl),
-                                   res_host.data_ptr(), max_iters, acc_arr.ctypes.data, p_arr.ctypes.data, q_arr.ctypes.data,
-                                   dms_arr.ctypes.data if timed else None, tms_arr.ctypes.data if timed else None,
-                                   C.byref(c_iters), C.byref(c_err), st), "sd_spec_generate")
-        other_time += process_time_ns() - tick           # host CPU time of the loop (enqueue + waits + bookkeeping)
+                                   res_host.data_ptr(), max_iters, *log.ptrs(), C.byref(c_iters), C.byref(c_err), _stream()),
+              "sd_spec_generate")
+        other_time = process_time_ns() - tick            # host CPU time of the loop (enqueue + waits + bookkeeping)
         noise.seed, noise.draw = c_seed.value, c_draw.value
-        if c_err.value == 1:
-            raise RuntimeError("prob error")
-        if c_err.value == 2:
-            raise RuntimeError("norm logits error")
+        raise_loop_error(c_err.value)
         calls = c_iters.value
-        draft_len, target_len = c_dl.value, c_tl.value
-        host_seq = seq_host[:c_len.value].tolist()
-        acc_len = acc_arr[:calls].tolist()
-        # python double ratio of the two float32 values, as the reference's .item() division (:1966-1971)
-        acc_rate = np.minimum(1.0, p_arr[:calls * gamma].astype(np.float64) / q_arr[:calls * gamma].astype(np.float64)).tolist()
-        if timed:
-            # the reference's approx_time / target_time are host process_time deltas around generate() (:1937-1962);
-            # here the host only enqueues, so the device time of the two phases (HIP events) is what is reported
-            approx_time = int(sum(int(v * 1e6) for v in dms_arr[:calls]))
-            target_time = int(sum(int(v * 1e6) for v in tms_arr[:calls]))
-            if timing_log is not None:
-                Lc, tl = seq_len0, 0
-                for i in range(calls):
-                    timing_log["draft_ms"].append(float(dms_arr[i]))
-                    timing_log["target"].append((float(tms_arr[i]), Lc + gamma - tl, Lc + gamma))
-                    tl = Lc + int(acc_arr[i])                    # n + 1 with n = L + l - 1
-                    Lc += int(acc_arr[i]) + 1
-        out_tokens = host_seq
-        if sum(1 for x in host_seq if x == eos_token_id) > ori_eos_cnt:
-            seen, cut = 0, len(host_seq)
-            for idx, x in enumerate(host_seq):
-                if x == eos_token_id:
-                    seen += 1
-                    if seen == ori_eos_cnt + 1:
-                        cut = idx + 1
-                        break
-            out_tokens = host_seq[:cut]
+        acc_len = log.acc_len(calls)
+        acc_rate = accept_rates_f64(*log.ratios(calls))
+        # the reference's approx_time / target_time are host process_time deltas around generate() (:1937-1962);
+        # here the host only enqueues, so the device time of the two phases (HIP events) is what is reported
+        approx_time, target_time = log.phase_ns(calls)
+        if timing_log is not None:
+            Lc, tl = seq_len0, 0
+            for i in range(calls):
+                timing_log["draft_ms"].append(float(log.draft_ms[i]))
+                timing_log["target"].append((float(log.target_ms[i]), Lc + gamma - tl, Lc + gamma))
+                tl = Lc + acc_len[i]                             # n + 1 with n = L + l - 1
+                Lc += acc_len[i] + 1
+        out_tokens = cut_after_new_eos(log.tokens(c_len.value), eos_token_id, ori_eos_cnt)
     except Exception as e:
         print(e)
-        lib.sd_spec_destroy(sp)
         raise RuntimeError("s") from e
-    lib.sd_spec_destroy(sp)
-    draft._session.cache_len, target._session.cache_len = draft_len, target_len
+    finally:
+        lib.sd_spec_destroy(sp)
+    draft._session.cache_len, target._session.cache_len = c_dl.value, c_tl.value
     out = torch.tensor([out_tokens], dtype=torch.int64, device=prefix.device)
     if details:
-        return out, {
-            "approx_time": approx_time, "target_time": target_time, "other_time": other_time,
-            "acc_len": acc_len, "acc_rate": np.mean(acc_rate),
-            "target_call_times": calls, "approx_call_times": calls,
-            # the verify phase is one fused launch chain (forward + norm_probs, no cache preparation): all of it is model time
-            "target_model_time": target_time, "target_pre_cache_time": 0, "target_post_prob_time": 0,
-        }
+        # the verify phase is one fused launch chain (forward + norm_probs, no cache preparation): all of it is model time
+        return out, details_dict(approx_time, target_time, other_time, acc_len, np.mean(acc_rate), calls, calls,
+                                 target_model_time=target_time, target_pre_cache_time=0, target_post_prob_time=0)
     return out

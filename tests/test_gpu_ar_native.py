@@ -96,10 +96,7 @@ class _Direct:
         self.arr = (hip.L.SdArStream * self.B)()
         for it, p, seed in zip(self.arr, prompts, seeds):
             L, cap = p.shape[1], p.shape[1] + 40
-            kv = hip.S.KVCacheModel(m, 1.0, 20, 0.9, max_seq=cap, full_history=False)
-            kv._ensure(cap)
-            seq = torch.zeros(cap, dtype=torch.int32, device="cuda")
-            seq[:L] = p[0].to(device="cuda", dtype=torch.int32)
+            kv, seq = hip.S._loop_common.open_stream(m, p[0], cap, cap, 1.0, 20, 0.9)
             host = np.zeros(cap, dtype=np.int32)
             host[:L] = p[0].numpy()
             err = torch.zeros(2, dtype=torch.int32, device="cuda")

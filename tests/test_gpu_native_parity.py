@@ -141,6 +141,30 @@ def test_stream_batched_loop_equals_oracle_per_stream(hip, gamma, n_streams):
     assert 0 < sum(sum(wd["acc_len"]) for _, wd in wants) < gamma * sum(len(wd["acc_len"]) for _, wd in wants)
 
 
+DETAILS_KEYS = {"approx_time", "target_time", "other_time", "acc_len", "acc_rate", "target_call_times", "approx_call_times",
+                "target_model_time", "target_pre_cache_time", "target_post_prob_time"}
+
+
+def test_stream_batched_and_single_stream_details_agree(hip):
+    """speculative_sampling_batch against one speculative_sampling(rng=DeviceNoise(seed)) call per stream, both with
+    details: the same tokens, accepted lengths and call counts, and exactly the reference's ten keys from both.  acc_rate is
+    held to [0, 1] within each call only: the two loops log p / q through different sampler entries."""
+    dc, dsd, tc, tsd = _pair("corr")
+    prompts = [torch.from_numpy(np.random.default_rng(60 + n).integers(3, dc.vocab_size, size=(1, n))).cuda() for n in (3, 5)]
+    seeds = [5, 6]
+    dm = hip.engine.SpecDecModel.from_state_dict(dc, dsd, dtype=torch.float32)
+    tm = hip.engine.SpecDecModel.from_state_dict(tc, tsd, dtype=torch.float32)
+    kw = dict(gamma=2, top_k=20, top_p=0.9, details=True)
+    outs, ds = hip.S.speculative_sampling_batch(prompts, dm, tm, 2, None, 8, seeds=seeds, **kw)
+    for p, seed, out, d in zip(prompts, seeds, outs, ds):
+        one, d1 = hip.S.speculative_sampling(p, dm, tm, 2, None, 8, rng=hip.noise.DeviceNoise(seed), **kw)
+        assert torch.equal(out, one)
+        assert set(d) == set(d1) == DETAILS_KEYS
+        assert d["acc_len"] == d1["acc_len"] and len(d["acc_len"]) >= 1
+        assert d["target_call_times"] == d["approx_call_times"] == d1["target_call_times"] == d1["approx_call_times"]
+        assert 0 <= d["acc_rate"] <= 1 and 0 <= d1["acc_rate"] <= 1
+
+
 def test_autoregressive_device_rng_equals_oracle(hip):
     cfg = load_config("tiny-llama-target")
     sd = make_state_dict(cfg, 31)
