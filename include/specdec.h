@@ -367,6 +367,12 @@ int sd_session_destroy(sd_session *s);
  * fp8(x / scale).  K / V rows are quantised where they are appended (the QKV epilogue, after RoPE), the attention kernel
  * widens them back in registers.  16-bit models with head_dim >= 32; call before the first forward. */
 int sd_session_set_kv_fp8(sd_session *s, const float *scales);
+/* How many times this session has launched the matrix-core prefill attention kernel (attn_prefill_kernel) so far: once
+ * per layer of every pass that qualifies (16-bit model, head_dim 64 or 128, 16-bit or fp8 arena; a call of more than 80
+ * rows or a batched prefill of >= 32 rows; no tree; SD_PREFILL_ATTN != 0); every other pass runs attn_kernel and leaves
+ * the count alone.  A batched pass counts on its first session.  A host integer: no device work, no
+ * synchronisation. */
+int sd_session_prefill_attn_launches(const sd_session *s);
 
 /* One model forward over n_new tokens at absolute positions pos0 .. pos0+n_new-1, appending their
  * K/V rows into the arena in-kernel (replaces the per-layer torch.cat of modeling_llama.py:337-338 /

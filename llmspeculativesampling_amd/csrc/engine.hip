@@ -59,6 +59,7 @@ struct sd_session {
     size_t spart_floats;
     float *tile_max;    // [SD_MAX_ROWS][vocab / 16] maxima of the head's 16-column tiles (EPI_HEAD)
     int kv_fp8;         // the arena holds fp8 e4m3 (sd_session_set_kv_fp8)
+    int prefill_attn_launches;   // attn_prefill_kernel launches so far (sd_session_prefill_attn_launches: the route, for tests)
     const float *kv_scale;   // device [L][2][Hkv]
     struct sd_tp *tp;   // tensor-parallel group of this shard (NULL: the model is whole)
     float *tp_in, *tp_out;   // [max_rows][hidden] fp32: this rank's partial O / down output, and the all-reduced sum
@@ -549,6 +550,7 @@ extern "C" int sd_session_create(sd_model *m, int max_seq, int max_rows, void *k
     s->tp = nullptr;
     s->kv_fp8 = 0;
     s->kv_scale = nullptr;
+    s->prefill_attn_launches = 0;
     s->tp_in = (float *)(s->scratch + p.tp_in);
     s->tp_out = (float *)(s->scratch + p.tp_out);
     s->h = s->scratch + p.h;
@@ -590,6 +592,10 @@ extern "C" int sd_session_set_kv_fp8(sd_session *s, const float *scales) {
     s->kv_scale = scales;
     return SD_OK;
 }
+
+// attn_prefill_kernel launches of this session so far (a host counter: the session profile counts one attention-class launch
+// whichever kernel ran).  A batched pass counts on its first session.
+extern "C" int sd_session_prefill_attn_launches(const sd_session *s) { return s ? s->prefill_attn_launches : 0; }
 
 extern "C" int sd_session_destroy(sd_session *s) {
     if (!s) return SD_OK;
@@ -1016,18 +1022,31 @@ static int run_gemm_fused(sd_session *s, const void *W, const void *X, int M, in
     return launch_gemm<EPI, H>(r, W, X, nullptr, M, N, K, e, st);
 }
 
-// Prefill passes (rows = consecutive positions of a stream) of a 16-bit model with head_dim 128: 16-row groups, both products
-// on the matrix cores (prefill_attn.h).  Returns false when the pass does not qualify (the caller takes attn_kernel).
+// Prefill passes (rows = consecutive positions of a stream) of a 16-bit model with head_dim 64 or 128, the arena in the model
+// type or in fp8: 16-row groups, both products on the matrix cores (prefill_attn.h).  Returns false when the pass does not
+// qualify (the caller takes attn_kernel).
 #define PA_LDS_MAX (150 * 1024)
-static size_t prefill_attn_lds(int s_max) {
-    return (size_t)PA_ROWS * ((size_t)align_up(s_max, 64) + PA_SPAD) * sizeof(float) + (size_t)PA_VCH * PA_VST;
+static size_t prefill_attn_lds(int s_max, int D) {
+    return (size_t)PA_ROWS * ((size_t)align_up(s_max, 64) + PA_SPAD) * sizeof(float) + (size_t)PA_VCH * PA_VST(D);
 }
 template <typename T>
 static bool prefill_attn_ok(const sd_session *s, const RowTab &tab, int s_max) {
     if constexpr (sizeof(T) != 2) return false;
     const sd_model_config &c = s->m->cfg;
-    return g_env.prefill_attn && tab.contig && !tab.tree && !tab.kv_fp8 && c.head_dim == 128 && tab.n_rows >= 32 &&
-           c.n_heads % c.n_kv_heads == 0 && prefill_attn_lds(s_max) <= PA_LDS_MAX;
+    return g_env.prefill_attn && tab.contig && !tab.tree && (c.head_dim == 64 || c.head_dim == 128) && tab.n_rows >= 32 &&
+           c.n_heads % c.n_kv_heads == 0 && prefill_attn_lds(s_max, c.head_dim) <= PA_LDS_MAX;
+}
+template <typename T, int D, bool KV8>
+static void launch_attn_prefill_inst(const sd_model_config &c, const T *q, const PaGroups &pg, int layer, T *out, int s_max,
+                                     hipStream_t st) {
+    static bool attr = false;                                     // (one flag per instance)
+    if (!attr) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(attn_prefill_kernel<T, D, KV8>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, PA_LDS_MAX);
+        attr = true;
+    }
+    hipLaunchKernelGGL((attn_prefill_kernel<T, D, KV8>), dim3(c.n_heads, pg.n), dim3(256), prefill_attn_lds(s_max, D), st, q, pg, layer,
+                       out, c.n_heads, c.n_kv_heads, c.arch, 1.0f / sqrtf((float)D), (int)align_up(s_max, 64));
 }
 template <typename T>
 static int launch_attn_prefill(sd_session *s, const T *q, const RowTab &tab, int layer, T *out, int s_max, hipStream_t st) {
@@ -1041,18 +1060,18 @@ static int launch_attn_prefill(sd_session *s, const T *q, const RowTab &tab, int
         if (join) { pg.nrows[i - 1] += tab.grp_n[g]; continue; }
         pg.row0[i] = tab.grp_row0[g]; pg.nrows[i] = tab.grp_n[g]; pg.pos[i] = tab.grp_pos[g];
         pg.max_seq[i] = tab.max_seq[tab.grp_stream[g]]; pg.kv[i] = tab.kv_base[tab.grp_stream[g]];
+        pg.kv_scale[i] = tab.kv_fp8 ? tab.kv_scale[tab.grp_stream[g]] : nullptr;
         ++pg.n;
     }
-    const int s_cap = (int)align_up(s_max, 64);
-    const size_t lds = prefill_attn_lds(s_max);
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(attn_prefill_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  PA_LDS_MAX);
-        attr = true;
+    const bool d64 = c.head_dim == 64;
+    if (tab.kv_fp8) {
+        if (d64) launch_attn_prefill_inst<T, 64, true>(c, q, pg, layer, out, s_max, st);
+        else launch_attn_prefill_inst<T, 128, true>(c, q, pg, layer, out, s_max, st);
+    } else {
+        if (d64) launch_attn_prefill_inst<T, 64, false>(c, q, pg, layer, out, s_max, st);
+        else launch_attn_prefill_inst<T, 128, false>(c, q, pg, layer, out, s_max, st);
     }
-    hipLaunchKernelGGL((attn_prefill_kernel<T>), dim3(c.n_heads, pg.n), dim3(256), lds, st, q, pg, layer, out, c.n_heads, c.n_kv_heads,
-                       c.arch, 1.0f / sqrtf((float)c.head_dim), s_cap);
+    ++s->prefill_attn_launches;
     return SD_OK;
 }
 

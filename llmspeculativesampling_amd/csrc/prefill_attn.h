@@ -16,12 +16,32 @@
 //     which makes the two groups of a 32-lane half read 8 consecutive key rows (288-byte row pitch: conflict-free).
 // fp32 accumulation inside the MFMA, one rounding of the output - the reference's bf16 matmul; the order of the sum differs
 // from attn_kernel's (and from torch's), as any two correct evaluations do.
+//
+// Instances: head_dim D in {64, 128}, the arena in the model type T or in fp8 e4m3 (KV8).
+//   * KV8: a lane's score operand is 8 consecutive BYTES of the key row, widened to T by fp8x8_to_16 (exact), and the scores
+//     are rounded as attn_body rounds them - rnd(acc * k_scale), then Llama's rnd(. / sqrt(D)) - so a row's probabilities
+//     still do not depend on which kernel ran.  Values are widened to T while their chunk is staged, so the LDS holds the
+//     same [key][pitch] image of T as on the 16-bit path (the global reads halve, the transposed-read / MFMA loop is the
+//     same code), P stays in T, and the fp32 accumulators are multiplied by v_scale in front of the single rounding of the
+//     store (attn_body: `a * v_scale` in the same place).  The scales travel per group in PaGroups.
+//   * D = 64: D / 32 = 2 score MFMAs per key tile; four 16-dim output tiles, so wave w owns dims 16 w .. 16 w + 15 (ONE
+//     accumulator where D = 128 has two); a V chunk is 64 keys x 128 B of T.
+//   * Row pitch of the V image, 2 D + 32 bytes.  ds_read_b64_tr_b16 is served in two groups of 32 lanes, a lane's bank is
+//     (addr / 4) mod 64, i.e. its offset inside a 256-byte bank row.  A 32-lane half is the lane groups g4 = 2 a, 2 a + 1:
+//     their lanes 4 q4 + p4 address key rows 8 a + 4 (g4 & 1) + q4 = 8 consecutive rows r = 0..7 of the image, 32
+//     contiguous bytes (4 p4 x 8 B: 8 banks) at the same column offset in each.  8 rows x 8 banks fill the 64 banks exactly
+//     once iff the row starts r * pitch mod 256 are the 8 distinct multiples of 32, i.e. iff pitch = 32 x (an odd number)
+//     mod 256.  D = 128 (256-byte rows): 288 = 32 x 9, r * 288 mod 256 = 0, 32, 64, .., 224.  D = 64 (128-byte rows): the
+//     bare 128 = 32 x 4 would put rows r and r + 2 on the same banks (4-way); 160 = 32 x 5 gives r * 160 mod 256 = 0, 160,
+//     64, 224, 128, 32, 192, 96 - conflict-free, and a multiple of 16 for the staging writes.  The second read of a step
+//     (+ 16 rows = 16 x pitch, a multiple of 256) is an instruction of its own on the same banks.
+//   * The transposed read needs EXEC all ones: no divergent flow surrounds it (chunk and step counts are per workgroup).
 #pragma once
 #include "model_kernels.h"
 
 #define PA_ROWS 16
 #define PA_VCH 64                                   // keys per staged V chunk
-#define PA_VST 288                                  // bytes per key row of the LDS V image (256 + 32)
+#define PA_VST(D) (2 * (D) + 32)                    // bytes per key row of the LDS V image (derivation above): 288 / 160
 #define PA_SPAD 4                                   // floats of padding per score row (16 rows x ds_read_b128: no bank shared)
 
 // row groups of a prefill pass: <= 16 consecutive rows of one stream each (built on the host from the table's 8-row groups)
@@ -29,26 +49,37 @@ struct PaGroups {
     int n;
     int row0[SD_MAX_GROUPS], nrows[SD_MAX_GROUPS], pos[SD_MAX_GROUPS], max_seq[SD_MAX_GROUPS];
     const void *kv[SD_MAX_GROUPS];
+    const float *kv_scale[SD_MAX_GROUPS];           // fp8 arena: the group's stream's scales [L][2][Hkv] (NULL otherwise)
 };
+static_assert(sizeof(PaGroups) <= 1536, "PaGroups travels by value in the kernel arguments (4 KiB in all)");
 
 typedef short pa_v4s __attribute__((ext_vector_type(4)));
 
-template <typename T>
+template <typename T, int D, bool KV8>
 __global__ __launch_bounds__(256) void attn_prefill_kernel(const T *__restrict__ qbuf, PaGroups pg, int layer, T *__restrict__ out,
                                                           int Hq, int Hkv, int arch, float inv_sqrt_d, int s_cap) {
-    constexpr int D = 128;
+    static_assert(D == 64 || D == 128, "four waves x (D / 64) output tiles of 16 dims");
     static_assert(sizeof(T) == 2, "16-bit models");
+    using E = typename std::conditional<KV8, unsigned char, T>::type;      // arena element
+    using E8 = typename std::conditional<KV8, uint2, u32x4>::type;         // 8 consecutive arena elements
+    constexpr int VST = PA_VST(D);
     extern __shared__ __attribute__((aligned(16))) char pa_smem[];
     const int ss = s_cap + PA_SPAD;                               // score row pitch (floats)
     float *sc = reinterpret_cast<float *>(pa_smem);               // [16][ss]
-    char *vb = pa_smem + (size_t)PA_ROWS * ss * sizeof(float);    // [PA_VCH][PA_VST]
+    char *vb = pa_smem + (size_t)PA_ROWS * ss * sizeof(float);    // [PA_VCH][VST]
     const int head = blockIdx.x, g = blockIdx.y;
     const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = tid & 63;
     const int r0 = pg.row0[g], nr = pg.nrows[g], p0 = pg.pos[g], max_seq = pg.max_seq[g];
     const int kvh = head / (Hq / Hkv);
-    const T *karena = (const T *)pg.kv[g] + (size_t)layer * 2 * Hkv * max_seq * D;
-    const T *K = karena + (size_t)kvh * max_seq * D;
-    const T *V = karena + (size_t)(Hkv + kvh) * max_seq * D;
+    const E *karena = (const E *)pg.kv[g] + (size_t)layer * 2 * Hkv * max_seq * D;
+    const E *K = karena + (size_t)kvh * max_seq * D;
+    const E *V = karena + (size_t)(Hkv + kvh) * max_seq * D;
+    float k_scale = 1.f, v_scale = 1.f;
+    if constexpr (KV8) {
+        const float *scl = pg.kv_scale[g] + (size_t)layer * 2 * Hkv;
+        k_scale = scl[kvh];
+        v_scale = scl[Hkv + kvh];
+    }
     const int s_hi = p0 + nr, s_last = s_hi - 1;                  // row t of the group sees keys 0 .. p0 + t
     const int s_pad = (s_hi + 31) & ~31;
 
@@ -62,12 +93,12 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const T *__restrict__
             for (int i = 0; i < 4; ++i) qf[dk][i] = mrow < nr ? qf[dk][i] : 0u;       // rows >= nr of the q operand are zero
         }
         for (int kt0 = w; kt0 * 16 < s_hi; kt0 += 16) {           // four key tiles per wave and round, all K loads up front
-            u32x4 kf[4][D / 32];
+            E8 kf[4][D / 32];                                     // (fp8: 8 bytes per operand, widened at the MFMA)
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const T *kr = K + (size_t)min((kt0 + 4 * u) * 16 + mrow, s_last) * D + kq;
+                const E *kr = K + (size_t)min((kt0 + 4 * u) * 16 + mrow, s_last) * D + kq;
 #pragma unroll
-                for (int dk = 0; dk < D / 32; ++dk) kf[u][dk] = *reinterpret_cast<const u32x4 *>(kr + dk * 32);
+                for (int dk = 0; dk < D / 32; ++dk) kf[u][dk] = *reinterpret_cast<const E8 *>(kr + dk * 32);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -75,12 +106,15 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const T *__restrict__
                 if (kt * 16 >= s_hi) continue;
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int dk = 0; dk < D / 32; ++dk) acc = mfma16<T>(kf[u][dk], qf[dk], acc);
+                for (int dk = 0; dk < D / 32; ++dk) {
+                    if constexpr (KV8) acc = mfma16<T>(fp8x8_to_16<T>(kf[u][dk]), qf[dk], acc);
+                    else acc = mfma16<T>(kf[u][dk], qf[dk], acc);
+                }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int s = kt * 16 + (lane >> 4) * 4 + j;
                     if (s < s_hi) {
-                        float v = rnd<T>(acc[j]);
+                        float v = rnd<T>(KV8 ? acc[j] * k_scale : acc[j]);
                         if (arch == SD_ARCH_LLAMA) v = rnd<T>(v * inv_sqrt_d);
                         sc[(size_t)mrow * ss + s] = s <= p0 + mrow ? v : -INFINITY;
                     }
@@ -123,27 +157,34 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const T *__restrict__
         }
     }
 
-    {   // ---- P.V on the matrix cores; wave w owns head dims 32 w .. 32 w + 31 (two 16-dim tiles)
+    {   // ---- P.V on the matrix cores; wave w owns head dims (D / 4) w .. + D / 4 - 1 (NT = D / 64 tiles of 16 dims)
+        constexpr int NT = D / 64, PPR = D / 8, NP = PA_VCH * PPR / 256;
         const int g4 = lane >> 4, i16 = lane & 15, q4 = i16 >> 2, p4 = i16 & 3;
-        f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        f32x4 acc[NT];
+#pragma unroll
+        for (int d2 = 0; d2 < NT; ++d2) acc[d2] = f32x4{0.f, 0.f, 0.f, 0.f};
         const int nch = (s_hi + PA_VCH - 1) / PA_VCH;
-        // a chunk = 64 keys x 256 B = 1024 pieces of 16 B; thread tid moves pieces tid, tid + 256, ...: key piece >> 4, 16-byte
-        // column piece & 15 (a key past the range re-reads the last one: its probabilities are zero)
-        u32x4 vr[4];
+        // a chunk = 64 keys x D elements = 64 PPR pieces of 8 elements (16 B of T in the image; 8 B in an fp8 arena); thread
+        // tid moves pieces tid, tid + 256, ...: key piece / PPR, 16-byte column piece % PPR (a key past the range re-reads the
+        // last one: its probabilities are zero)
+        E8 vr[NP];
         auto vload = [&](int c) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int piece = tid + 256 * i, key = min(c * PA_VCH + (piece >> 4), s_last);
-                vr[i] = *reinterpret_cast<const u32x4 *>(V + (size_t)key * D + (piece & 15) * 8);
+            for (int i = 0; i < NP; ++i) {
+                const int piece = tid + 256 * i, key = min(c * PA_VCH + piece / PPR, s_last);
+                vr[i] = *reinterpret_cast<const E8 *>(V + (size_t)key * D + (piece % PPR) * 8);
             }
         };
         vload(0);
         for (int c = 0; c < nch; ++c) {
             __syncthreads();                                      // the previous chunk is no longer read (c = 0: P is complete)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
+            for (int i = 0; i < NP; ++i) {
                 const int piece = tid + 256 * i;
-                *reinterpret_cast<u32x4 *>(vb + (piece >> 4) * PA_VST + (piece & 15) * 16) = vr[i];
+                u32x4 vw;
+                if constexpr (KV8) vw = fp8x8_to_16<T>(vr[i]);    // exact; from here on the 16-bit path's image
+                else vw = vr[i];
+                *reinterpret_cast<u32x4 *>(vb + (piece / PPR) * VST + (piece % PPR) * 16) = vw;
             }
             __syncthreads();
             if (c + 1 < nch) vload(c + 1);
@@ -155,12 +196,12 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const T *__restrict__
                 const T ph[8] = {(T)pa[0], (T)pa[1], (T)pa[2], (T)pa[3], (T)pb[0], (T)pb[1], (T)pb[2], (T)pb[3]};
                 const u32x4 pf = *reinterpret_cast<const u32x4 *>(ph);
 #pragma unroll
-                for (int d2 = 0; d2 < 2; ++d2) {
+                for (int d2 = 0; d2 < NT; ++d2) {
                     // A: lane 4 q4 + p4 of its 16-lane group supplies the address of key row 16 h + 4 g4 + q4 of the step,
                     // dims 16 dt + 4 p4 .. + 3; lane i16 receives dim 16 dt + i16 of the group's four keys
-                    const char *va = vb + (size_t)(st * 32 + 4 * g4 + q4) * PA_VST + ((2 * w + d2) * 16 + 4 * p4) * 2;
+                    const char *va = vb + (size_t)(st * 32 + 4 * g4 + q4) * VST + ((NT * w + d2) * 16 + 4 * p4) * 2;
                     const pa_v4s a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pa_v4s __attribute__((address_space(3))) *)(va));
-                    const pa_v4s a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pa_v4s __attribute__((address_space(3))) *)(va + 16 * PA_VST));
+                    const pa_v4s a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pa_v4s __attribute__((address_space(3))) *)(va + 16 * VST));
                     u32x4 af;
                     af[0] = ((const unsigned *)&a0)[0]; af[1] = ((const unsigned *)&a0)[1];
                     af[2] = ((const unsigned *)&a1)[0]; af[3] = ((const unsigned *)&a1)[1];
@@ -171,9 +212,11 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const T *__restrict__
         // lane l holds out[row l & 15][dims 16 dt + 4 (l >> 4) .. + 3]: one 8-byte store inside an 8-element operand group
         if (i16 < nr) {
 #pragma unroll
-            for (int d2 = 0; d2 < 2; ++d2)
-                store4_maybe_wt<false>(out + xoff<T>(r0 + i16, head * D + (2 * w + d2) * 16 + 4 * g4, Hq * D), acc[d2][0], acc[d2][1],
+            for (int d2 = 0; d2 < NT; ++d2) {
+                if constexpr (KV8) acc[d2] *= v_scale;
+                store4_maybe_wt<false>(out + xoff<T>(r0 + i16, head * D + (NT * w + d2) * 16 + 4 * g4, Hq * D), acc[d2][0], acc[d2][1],
                                        acc[d2][2], acc[d2][3]);
+            }
         }
     }
 }

@@ -397,6 +397,12 @@ class Session:
     def rollback(self, end_pos: int) -> None:
         self.cache_len = min(self.cache_len, int(end_pos))
 
+    def prefill_attn_launches(self) -> int:
+        """attn_prefill_kernel launches of this session so far (one per layer of a pass that takes the matrix-core prefill
+        attention; a batched pass counts on its first session).  A host counter: the profile's attention class counts one
+        launch whichever kernel ran."""
+        return int(lib.sd_session_prefill_attn_launches(self.handle))
+
     def past_key_values(self):
         """The reference's tuple layout: one (k, v) pair of (1, H_kv, S, D) views per layer."""
         S = self.cache_len
