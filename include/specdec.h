@@ -367,12 +367,30 @@ int sd_session_destroy(sd_session *s);
  * fp8(x / scale).  K / V rows are quantised where they are appended (the QKV epilogue, after RoPE), the attention kernel
  * widens them back in registers.  16-bit models with head_dim >= 32; call before the first forward. */
 int sd_session_set_kv_fp8(sd_session *s, const float *scales);
-/* How many times this session has launched the matrix-core prefill attention kernel (attn_prefill_kernel) so far: once
+/* How many times this session has launched a matrix-core prefill attention kernel (attn_prefill_kernel or, past its context
+ * limit, attn_prefill_blocked_kernel) so far: once
  * per layer of every pass that qualifies (16-bit model, head_dim 64 or 128, 16-bit or fp8 arena; a call of more than 80
  * rows or a batched prefill of >= 32 rows; no tree; SD_PREFILL_ATTN != 0); every other pass runs attn_kernel and leaves
  * the count alone.  A batched pass counts on its first session.  A host integer: no device work, no
  * synchronisation. */
 int sd_session_prefill_attn_launches(const sd_session *s);
+/* The matrix-core prefill attention has two kernels: attn_prefill_kernel keeps a row group's whole score tile in LDS and
+ * runs while that fits (2048 keys at head_dim 128, 2176 at 64); past it - by default where sd_prefill_attn_route says so, and
+ * at any context when SD_PREFILL_ATTN_BLOCK=K (K > 0, rounded up to a multiple of 64) is set - attn_prefill_blocked_kernel
+ * sweeps the keys in blocks and computes the same bits at any context length.  sd_session_prefill_attn_launches counts both, this one the blocked kernel's launches
+ * alone. */
+int sd_session_prefill_attn_blocked_launches(const sd_session *s);
+/* The plan such a pass gets (host only: no device, no session): for a model of `head_dim`, a pass whose last row sees s_max
+ * keys and block_keys = the value of SD_PREFILL_ATTN_BLOCK (0: the default policy), *kernel = 0 (no matrix-core kernel for
+ * this head_dim), 1 (single tile) or 2 (blocked), *block = keys per score tile, *lds_bytes = the launch's dynamic LDS.
+ * The launch path calls the same function.  Any out pointer may be NULL. */
+int sd_prefill_attn_plan(int head_dim, int s_max, int block_keys, int *kernel, int *block, long *lds_bytes);
+/* The route of a contiguous pass of n_rows rows (one stream) on a model of n_heads heads whose last row sees s_max keys (host
+ * only; the function the launch path calls): *kernel = 0 (attn_kernel), 1 (single tile) or 2 (blocked).  Past the tile limit
+ * the blocked kernel is the default where the launch has at least 2 workgroups (heads x 16-row groups) per CU - below that its
+ * three sweeps are slower than attn_kernel's split keys - and where attn_kernel's splits cannot hold the pass at all; a forced
+ * block always takes it.  cus = 0: the device's CU count (256 without a device). */
+int sd_prefill_attn_route(int head_dim, int n_heads, int n_rows, int s_max, int block_keys, int cus, int *kernel);
 
 /* One model forward over n_new tokens at absolute positions pos0 .. pos0+n_new-1, appending their
  * K/V rows into the arena in-kernel (replaces the per-layer torch.cat of modeling_llama.py:337-338 /

@@ -132,6 +132,9 @@ SYMBOLS = [
     ("sd_session_destroy", _I, [_VP]),
     ("sd_session_set_kv_fp8", _I, [_VP, _VP]),
     ("sd_session_prefill_attn_launches", _I, [_VP]),
+    ("sd_session_prefill_attn_blocked_launches", _I, [_VP]),
+    ("sd_prefill_attn_plan", _I, [_I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long)]),
+    ("sd_prefill_attn_route", _I, [_I, _I, _I, _I, _I, _I, C.POINTER(C.c_int)]),
     ("sd_session_forward", _I, [_VP, _VP, _I, _I, _I, _VP, _L, _VP]),
     ("sd_session_forward_tree", _I, [_VP, _VP, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), _I, _I, _VP, _L, _VP]),
     ("sd_session_compact_kv", _I, [_VP, _I, _VP, _I, _VP]),

@@ -59,7 +59,8 @@ struct sd_session {
     size_t spart_floats;
     float *tile_max;    // [SD_MAX_ROWS][vocab / 16] maxima of the head's 16-column tiles (EPI_HEAD)
     int kv_fp8;         // the arena holds fp8 e4m3 (sd_session_set_kv_fp8)
-    int prefill_attn_launches;   // attn_prefill_kernel launches so far (sd_session_prefill_attn_launches: the route, for tests)
+    int prefill_attn_launches;   // attn_prefill_kernel + attn_prefill_blocked_kernel launches so far (sd_session_prefill_attn_launches: the route, for tests)
+    int prefill_attn_blocked_launches;   // ... of which attn_prefill_blocked_kernel
     const float *kv_scale;   // device [L][2][Hkv]
     struct sd_tp *tp;   // tensor-parallel group of this shard (NULL: the model is whole)
     float *tp_in, *tp_out;   // [max_rows][hidden] fp32: this rank's partial O / down output, and the all-reduced sum
@@ -145,7 +146,7 @@ extern "C" int sd_pack_weight_bf16(const void *src, void *dst, int N, int K, voi
 struct EnvTun {
     int gemm_ntw = 4, gemm_units = -1, small_path = 1, small_split_bytes = 0, tiny_split_bytes = 24576, fuse_embed_qkv = 1, head_tiles = 1;
     int attn_split_keys = 384, attn_keys_per_split = 256;
-    int mm_mtw = 0, mm_s = 0, prefill_attn = 1, mm_slabs_min = 24;
+    int mm_mtw = 0, mm_s = 0, prefill_attn = 1, prefill_attn_block = 0, mm_slabs_min = 24;
     int wide_qkv = 1, tp_one_slab = 1, gemm_rows = 1, cus = 0, fuse_attn_o = 1, ao_stamps = 0, ao_delay = 300, ao_gap = 100, norm_on_load = 2, rows_max = SD_ROWS_MAX;
 };
 static EnvTun g_env;
@@ -169,6 +170,7 @@ static void refresh_env() {
     g_env.fuse_attn_o = geti("SD_FUSE_ATTN_O", 1);    // 0: attention and the O projection as two launches (A/B runs, bit-compare tests)
     g_env.norm_on_load = geti("SD_NORM_ON_LOAD", 2);  // 0: residual+norm launches stay; 1: attention -> MLP seam only; 2: both seams (A/B runs, compare tests)
     g_env.prefill_attn = geti("SD_PREFILL_ATTN", 1);  // 0: prefill passes keep attn_kernel's 8-row groups (A/B runs, compare tests)
+    g_env.prefill_attn_block = std::max(0, geti("SD_PREFILL_ATTN_BLOCK", 0));   // K > 0: every matrix-core prefill pass takes attn_prefill_blocked_kernel with blocks of K keys (rounded up to 64; tests, sweeps); 0: only past the single tile's LDS limit
     g_env.mm_slabs_min = geti("SD_MM_SLABS_MIN", 24); // rows from which the k-slab GEMMs (O / down) of a pass take gemm_bf16_mm instead of the balanced kernel
     g_env.mm_mtw = geti("SD_MM_MTW", 0);              // (sweeps) m-tiles per wave of gemm_bf16_mm: 2 = 128-row blocks, 4 = 256-row blocks; 0 = by row count
     g_env.mm_s = geti("SD_MM_S", 0);                  // (sweeps) k-slabs of gemm_bf16_mm; 0 = planned
@@ -551,6 +553,7 @@ extern "C" int sd_session_create(sd_model *m, int max_seq, int max_rows, void *k
     s->kv_fp8 = 0;
     s->kv_scale = nullptr;
     s->prefill_attn_launches = 0;
+    s->prefill_attn_blocked_launches = 0;
     s->tp_in = (float *)(s->scratch + p.tp_in);
     s->tp_out = (float *)(s->scratch + p.tp_out);
     s->h = s->scratch + p.h;
@@ -593,9 +596,11 @@ extern "C" int sd_session_set_kv_fp8(sd_session *s, const float *scales) {
     return SD_OK;
 }
 
-// attn_prefill_kernel launches of this session so far (a host counter: the session profile counts one attention-class launch
+// attn_prefill_kernel + attn_prefill_blocked_kernel launches of this session so far (a host counter: the session profile counts one attention-class launch
 // whichever kernel ran).  A batched pass counts on its first session.
 extern "C" int sd_session_prefill_attn_launches(const sd_session *s) { return s ? s->prefill_attn_launches : 0; }
+// ... of which attn_prefill_blocked_kernel's (a context past the single score tile, or SD_PREFILL_ATTN_BLOCK set)
+extern "C" int sd_session_prefill_attn_blocked_launches(const sd_session *s) { return s ? s->prefill_attn_blocked_launches : 0; }
 
 extern "C" int sd_session_destroy(sd_session *s) {
     if (!s) return SD_OK;
@@ -1022,35 +1027,125 @@ static int run_gemm_fused(sd_session *s, const void *W, const void *X, int M, in
     return launch_gemm<EPI, H>(r, W, X, nullptr, M, N, K, e, st);
 }
 
+// keys per workgroup above which a group's keys are cut over several workgroups (and merged by attn_combine_kernel)
+#define ATT_SPLIT_KEYS 384
+#define ATT_MAX_PARTS 64          // groups * splits the partial buffer is sized for
+// 160 KiB per workgroup less the kernel's static LDS (the split path's per-row max / denominator)
+#define ATT_LDS_MAX ((size_t)160 * 1024 - 512)
+// attn_kernel's key splits for a pass of n_groups row groups whose last row sees s_max keys: the dynamic LDS of a workgroup
+// (> ATT_LDS_MAX: the pass does not fit - launch_attn's capacity error)
+static size_t attn_split_plan(int D, int s_max, int n_groups, int *nsplit_out, int *s_cap_out) {
+    auto lds_for = [&](int nsplit, int *s_cap) {
+        const int keys = nsplit > 1 ? (((s_max + nsplit - 1) / nsplit + 15) & ~15) : s_max;
+        *s_cap = (int)align_up(keys, 64);
+        return sizeof(float) * ((size_t)ATT_TQ * D + (size_t)(256 / (D / 8)) * ATT_TQ * D + (size_t)ATT_TQ * *s_cap);
+    };
+    const int split_keys = g_env.attn_split_keys, keys_per = g_env.attn_keys_per_split;
+    int nsplit = 1, s_cap;
+    if (s_max > split_keys) {
+        nsplit = std::min(8, (s_max + keys_per - 1) / keys_per);
+        while (nsplit > 1 && nsplit * n_groups > ATT_MAX_PARTS) --nsplit;
+    }
+    // very long contexts: more, smaller chunks until one chunk's score rows fit the LDS
+    while (lds_for(nsplit, &s_cap) > ATT_LDS_MAX && (nsplit + 1) * n_groups <= ATT_MAX_PARTS) ++nsplit;
+    const size_t lds = lds_for(nsplit, &s_cap);
+    *nsplit_out = nsplit;
+    *s_cap_out = s_cap;
+    return lds;
+}
+
 // Prefill passes (rows = consecutive positions of a stream) of a 16-bit model with head_dim 64 or 128, the arena in the model
 // type or in fp8: 16-row groups, both products on the matrix cores (prefill_attn.h).  Returns false when the pass does not
-// qualify (the caller takes attn_kernel).
+// qualify (the caller takes attn_kernel).  While the whole score tile of a row group fits PA_LDS_MAX (2048 keys at head_dim
+// 128, 2176 at 64) attn_prefill_kernel runs; past that attn_prefill_blocked_kernel with blocks of PA_BLOCK_KEYS keys
+// (plan_prefill_attn) - by default where route_prefill_attn finds that it pays or that attn_kernel cannot hold the pass.
 #define PA_LDS_MAX (150 * 1024)
-static size_t prefill_attn_lds(int s_max, int D) {
-    return (size_t)PA_ROWS * ((size_t)align_up(s_max, 64) + PA_SPAD) * sizeof(float) + (size_t)PA_VCH * PA_VST(D);
+#define PA_BLOCK_KEYS 256         // 16 x 260 floats + the V chunk = 34.3 KiB (26.3 at head_dim 64): four workgroups per CU; the sweep's best
+struct PaPlan { int kernel, block; size_t lds; };                 // kernel: 0 none, 1 single tile, 2 blocked; block: keys per score tile
+static size_t prefill_attn_lds(int keys, int D) {
+    return (size_t)PA_ROWS * ((size_t)align_up(keys, 64) + PA_SPAD) * sizeof(float) + (size_t)PA_VCH * PA_VST(D);
+}
+// block_keys > 0 (SD_PREFILL_ATTN_BLOCK) forces the blocked kernel with blocks of that many keys, rounded up to a multiple
+// of 64 and held to what the LDS takes
+static PaPlan plan_prefill_attn(int D, int s_max, int block_keys) {
+    if ((D != 64 && D != 128) || s_max < 1) return {0, 0, 0};
+    if (block_keys > 0) {
+        int kb = (int)align_up(block_keys, 64);
+        while (prefill_attn_lds(kb, D) > PA_LDS_MAX) kb -= 64;
+        return {2, kb, prefill_attn_lds(kb, D)};
+    }
+    if (prefill_attn_lds(s_max, D) <= PA_LDS_MAX) return {1, (int)align_up(s_max, 64), prefill_attn_lds(s_max, D)};
+    return {2, PA_BLOCK_KEYS, prefill_attn_lds(PA_BLOCK_KEYS, D)};
+}
+extern "C" int sd_prefill_attn_plan(int head_dim, int s_max, int block_keys, int *kernel, int *block, long *lds_bytes) {
+    SD_REQUIRE(s_max >= 1 && block_keys >= 0, "sd_prefill_attn_plan: s_max %d, block_keys %d", s_max, block_keys);
+    const PaPlan p = plan_prefill_attn(head_dim, s_max, block_keys);
+    if (kernel) *kernel = p.kernel;
+    if (block) *block = p.block;
+    if (lds_bytes) *lds_bytes = (long)p.lds;
+    return SD_OK;
+}
+// Which attention kernel a pass that meets the gate takes: 0 attn_kernel, 1 the single tile, 2 the blocked kernel.  Past the
+// tile limit the blocked kernel is the default only where it pays or where nothing else runs.  Measured (DESIGN.md section 6,
+// 256-row passes at 2560 and 4096 keys, seven shapes): its three score sweeps are latency-bound while a CU holds one 4-wave
+// workgroup, so against attn_kernel's split keys it is 0.47-0.53x at 128 workgroups (heads x 16-row groups), 0.62-0.69x at
+// 192, 0.84-0.93x at 256, 1.3-1.45x at 512 and 1.9-2.2x at 1024 - whatever the head dim.  So: at least PA_BLOCKED_WG_PER_CU
+// workgroups per CU -> blocked; fewer -> attn_kernel, as before this kernel existed, while its key splits hold the pass
+// (attn_split_plan), and the blocked kernel past that, where launch_attn would return SD_ERR_CAPACITY.  A forced block
+// (SD_PREFILL_ATTN_BLOCK) takes the blocked kernel always.
+#define PA_BLOCKED_WG_PER_CU 2
+static int route_prefill_attn(int D, int n_heads, int n_rows, int n_groups, int s_max, int block_keys, int cus) {
+    const PaPlan pl = plan_prefill_attn(D, s_max, block_keys);
+    if (pl.kernel != 2 || block_keys > 0) return pl.kernel;
+    if (n_heads * ((n_rows + PA_ROWS - 1) / PA_ROWS) >= PA_BLOCKED_WG_PER_CU * cus) return 2;
+    int nsplit, s_cap;
+    return attn_split_plan(D, s_max, n_groups, &nsplit, &s_cap) > ATT_LDS_MAX ? 2 : 0;
+}
+extern "C" int sd_prefill_attn_route(int head_dim, int n_heads, int n_rows, int s_max, int block_keys, int cus, int *kernel) {
+    SD_REQUIRE(kernel && n_heads >= 1 && n_rows >= 1 && s_max >= 1 && block_keys >= 0 && cus >= 0,
+               "sd_prefill_attn_route: heads %d, rows %d, s_max %d, block_keys %d, cus %d", n_heads, n_rows, s_max, block_keys, cus);
+    if (!cus) {                                                   // (no tunable is resampled here: sessions keep theirs)
+        int dev = 0, n = 0;
+        if (g_env.cus > 0) cus = g_env.cus;
+        else if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cus = n;
+        else { (void)hipGetLastError(); cus = 256; }
+    }
+    *kernel = route_prefill_attn(head_dim, n_heads, n_rows, (n_rows + ATT_TQ - 1) / ATT_TQ, s_max, block_keys, cus);
+    return SD_OK;
 }
 template <typename T>
 static bool prefill_attn_ok(const sd_session *s, const RowTab &tab, int s_max) {
     if constexpr (sizeof(T) != 2) return false;
     const sd_model_config &c = s->m->cfg;
-    return g_env.prefill_attn && tab.contig && !tab.tree && (c.head_dim == 64 || c.head_dim == 128) && tab.n_rows >= 32 &&
-           c.n_heads % c.n_kv_heads == 0 && prefill_attn_lds(s_max, c.head_dim) <= PA_LDS_MAX;
+    if (!(g_env.prefill_attn && tab.contig && !tab.tree && (c.head_dim == 64 || c.head_dim == 128) && tab.n_rows >= 32 &&
+          c.n_heads % c.n_kv_heads == 0))
+        return false;
+    return route_prefill_attn(c.head_dim, c.n_heads, tab.n_rows, tab.n_groups, s_max, g_env.prefill_attn_block,
+                              g_env.cus > 0 ? g_env.cus : 256) != 0;
 }
 template <typename T, int D, bool KV8>
-static void launch_attn_prefill_inst(const sd_model_config &c, const T *q, const PaGroups &pg, int layer, T *out, int s_max,
+static void launch_attn_prefill_inst(const sd_model_config &c, const T *q, const PaGroups &pg, int layer, T *out, const PaPlan &pl,
                                      hipStream_t st) {
     static bool attr = false;                                     // (one flag per instance)
     if (!attr) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(attn_prefill_kernel<T, D, KV8>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, PA_LDS_MAX);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(attn_prefill_blocked_kernel<T, D, KV8>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, PA_LDS_MAX);
         attr = true;
     }
-    hipLaunchKernelGGL((attn_prefill_kernel<T, D, KV8>), dim3(c.n_heads, pg.n), dim3(256), prefill_attn_lds(s_max, D), st, q, pg, layer,
-                       out, c.n_heads, c.n_kv_heads, c.arch, 1.0f / sqrtf((float)D), (int)align_up(s_max, 64));
+    if (pl.kernel == 2)
+        hipLaunchKernelGGL((attn_prefill_blocked_kernel<T, D, KV8>), dim3(c.n_heads, pg.n), dim3(256), pl.lds, st, q, pg, layer, out,
+                           c.n_heads, c.n_kv_heads, c.arch, 1.0f / sqrtf((float)D), pl.block);
+    else
+        hipLaunchKernelGGL((attn_prefill_kernel<T, D, KV8>), dim3(c.n_heads, pg.n), dim3(256), pl.lds, st, q, pg, layer, out,
+                           c.n_heads, c.n_kv_heads, c.arch, 1.0f / sqrtf((float)D), pl.block);
 }
 template <typename T>
 static int launch_attn_prefill(sd_session *s, const T *q, const RowTab &tab, int layer, T *out, int s_max, hipStream_t st) {
     const sd_model_config &c = s->m->cfg;
+    const PaPlan pl = plan_prefill_attn(c.head_dim, s_max, g_env.prefill_attn_block);
+    SD_REQUIRE(pl.kernel != 0, "internal: no prefill attention kernel for head_dim %d", c.head_dim);
     // the table's groups are <= ATT_TQ consecutive rows of a stream: two neighbours of one stream make a 16-row group
     PaGroups pg = {};
     for (int g = 0; g < tab.n_groups; ++g) {
@@ -1065,39 +1160,23 @@ static int launch_attn_prefill(sd_session *s, const T *q, const RowTab &tab, int
     }
     const bool d64 = c.head_dim == 64;
     if (tab.kv_fp8) {
-        if (d64) launch_attn_prefill_inst<T, 64, true>(c, q, pg, layer, out, s_max, st);
-        else launch_attn_prefill_inst<T, 128, true>(c, q, pg, layer, out, s_max, st);
+        if (d64) launch_attn_prefill_inst<T, 64, true>(c, q, pg, layer, out, pl, st);
+        else launch_attn_prefill_inst<T, 128, true>(c, q, pg, layer, out, pl, st);
     } else {
-        if (d64) launch_attn_prefill_inst<T, 64, false>(c, q, pg, layer, out, s_max, st);
-        else launch_attn_prefill_inst<T, 128, false>(c, q, pg, layer, out, s_max, st);
+        if (d64) launch_attn_prefill_inst<T, 64, false>(c, q, pg, layer, out, pl, st);
+        else launch_attn_prefill_inst<T, 128, false>(c, q, pg, layer, out, pl, st);
     }
+    if (pl.kernel == 2) ++s->prefill_attn_blocked_launches;
     ++s->prefill_attn_launches;
     return SD_OK;
 }
 
-// keys per workgroup above which a group's keys are cut over several workgroups (and merged by attn_combine_kernel)
-#define ATT_SPLIT_KEYS 384
-#define ATT_MAX_PARTS 64          // groups * splits the partial buffer is sized for
-
 template <typename T, int D>
 static int launch_attn(sd_session *s, const T *q, const RowTab &tab, int layer, T *out, int s_max, hipStream_t st) {
     const sd_model_config &c = s->m->cfg;
-    // 160 KiB per workgroup less the kernel's static LDS (the split path's per-row max / denominator)
-    const size_t lds_max = 160 * 1024 - 512;
-    auto lds_for = [&](int nsplit, int *s_cap) {
-        const int keys = nsplit > 1 ? (((s_max + nsplit - 1) / nsplit + 15) & ~15) : s_max;
-        *s_cap = (int)align_up(keys, 64);
-        return sizeof(float) * ((size_t)ATT_TQ * D + (size_t)(256 / (D / 8)) * ATT_TQ * D + (size_t)ATT_TQ * *s_cap);
-    };
-    const int split_keys = g_env.attn_split_keys, keys_per = g_env.attn_keys_per_split;
-    int nsplit = 1, s_cap;
-    if (s_max > split_keys) {
-        nsplit = std::min(8, (s_max + keys_per - 1) / keys_per);
-        while (nsplit > 1 && nsplit * tab.n_groups > ATT_MAX_PARTS) --nsplit;
-    }
-    // very long contexts: more, smaller chunks until one chunk's score rows fit the LDS
-    while (lds_for(nsplit, &s_cap) > lds_max && (nsplit + 1) * tab.n_groups <= ATT_MAX_PARTS) ++nsplit;
-    const size_t lds = lds_for(nsplit, &s_cap);
+    const size_t lds_max = ATT_LDS_MAX;
+    int nsplit, s_cap;
+    const size_t lds = attn_split_plan(D, s_max, tab.n_groups, &nsplit, &s_cap);
     if (lds > lds_max) {
         sd_set_error("attention: %d keys x %d row groups exceed the LDS score tile", s_max, tab.n_groups);
         return SD_ERR_CAPACITY;

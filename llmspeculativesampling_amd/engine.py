@@ -398,10 +398,15 @@ class Session:
         self.cache_len = min(self.cache_len, int(end_pos))
 
     def prefill_attn_launches(self) -> int:
-        """attn_prefill_kernel launches of this session so far (one per layer of a pass that takes the matrix-core prefill
-        attention; a batched pass counts on its first session).  A host counter: the profile's attention class counts one
+        """attn_prefill_kernel / attn_prefill_blocked_kernel launches of this session so far (one per layer of a pass that takes
+        the matrix-core prefill attention; a batched pass counts on its first session).  A host counter: the profile's attention class counts one
         launch whichever kernel ran."""
         return int(lib.sd_session_prefill_attn_launches(self.handle))
+
+    def prefill_attn_blocked_launches(self) -> int:
+        """Of those, the launches of attn_prefill_blocked_kernel (a context past the single score tile's LDS limit, or
+        SD_PREFILL_ATTN_BLOCK=K set when the session was created)."""
+        return int(lib.sd_session_prefill_attn_blocked_launches(self.handle))
 
     def past_key_values(self):
         """The reference's tuple layout: one (k, v) pair of (1, H_kv, S, D) views per layer."""
