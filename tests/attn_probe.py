@@ -310,11 +310,24 @@ def layout_tokens(lay: Layout) -> np.ndarray:
 
 
 # ----------------------------------------------------------------------------- the oracle on a layout
+def kv_rows(lm, ids, lo, hi, chunk=512):
+    """K / V rows lo .. hi - 1 of a ONE-layer model: they depend on token and position alone, so they are computed in
+    chunks at their own positions (the attention inside a chunk is discarded) instead of by one hi-row causal forward."""
+    assert lm.cfg.num_hidden_layers == 1
+    ks, vs = [], []
+    for a in range(lo, hi, chunk):
+        b = min(hi, a + chunk)
+        k, v = lm(ids[:, a:b], position_ids=torch.arange(a, b)[None]).past_key_values[0]
+        ks.append(k)
+        vs.append(v)
+    return torch.cat(ks, 2), torch.cat(vs, 2)
+
+
 class ProbeOracle:
     """oracle.RefCausalLM of a probe model in one dtype, with the K / V rows of F and M at every position tabulated once
     (layer 0's rows are a function of token and position alone), so a layout costs one n-row forward."""
 
-    def __init__(self, name: str, dtype=torch.float32, kv_quant: Optional[str] = None, sd=None):
+    def __init__(self, name: str, dtype=torch.float32, kv_quant: Optional[str] = None, sd=None, max_seq: int = MAX_SEQ):
         self.name, self.dtype = name, dtype
         self.cfg = probe_config(name)
         sd = sd if sd is not None else probe_state_dict(name)
@@ -324,8 +337,9 @@ class ProbeOracle:
         self.lm = oracle.RefCausalLM(self.cfg, self.sd, kv_quant=kv_quant)
         self.tab = {}
         for tok in (F_TOK, M_TOK):
-            ids = torch.full((1, MAX_SEQ), tok, dtype=torch.long)
-            self.tab[tok] = self.lm(ids).past_key_values[0]
+            ids = torch.full((1, max_seq), tok, dtype=torch.long)
+            # (a table past MAX_SEQ positions is tabulated in chunks; up to it by the one forward the bars were measured with)
+            self.tab[tok] = self.lm(ids).past_key_values[0] if max_seq <= MAX_SEQ else kv_rows(self.lm, ids, 0, max_seq)
 
     def past(self, tokens: np.ndarray, upto: int):
         if upto == 0:

@@ -82,20 +82,21 @@ class _Env:
 class Runner:
     """One model + one arena.  `slots` mirrors which token's K / V row every arena slot holds; a layout re-plants only the
     slots that differ (runs of consecutive positions, n_logits = 0).  with_marker = False feeds F wherever the layout has
-    M - the same calls otherwise."""
+    M - the same calls otherwise.  max_seq: arena slots (attn_probe.MAX_SEQ unless given)."""
 
-    def __init__(self, hip, name, dt, kv_dtype=None, with_marker=True, model=None):
+    def __init__(self, hip, name, dt, kv_dtype=None, with_marker=True, model=None, max_seq=None):
         self.hip, self.cfg = hip, P.probe_config(name)
+        self.max_seq = P.MAX_SEQ if max_seq is None else max_seq
         dtype = P.DTYPES[dt]
         self.m = model or hip.engine.SpecDecModel.from_state_dict(self.cfg, P.cast_sd(_sd(name), dtype), dtype=dtype)
-        self.ses = self.m.new_session(P.MAX_SEQ, kv_dtype=kv_dtype)
+        self.ses = self.m.new_session(self.max_seq, kv_dtype=kv_dtype)
         if kv_dtype == "fp8":                                      # before any row is stored: the store divides by the scale
             sc = P.fp8_scales(name).to(self.ses.kv_scale.device)
             assert sc.shape == self.ses.kv_scale.shape
             self.ses.kv_scale.copy_(sc)
             torch.cuda.synchronize()
         self.with_marker = with_marker
-        self.slots = np.full(P.MAX_SEQ, -1, dtype=np.int64)
+        self.slots = np.full(self.max_seq, -1, dtype=np.int64)
 
     def _dev(self, toks):
         t = np.array(toks, dtype=np.int64)
@@ -116,7 +117,7 @@ class Runner:
         t = P.layout_tokens(lay)
         pos0 = lay.S - lay.n
         self.plant(t, 0, pos0)
-        if lay.S < P.MAX_SEQ:
+        if lay.S < self.max_seq:
             self.plant(t, lay.S, lay.S + 1)                        # the stale slot behind the last key
         nl = lay.n if n_logits is None else n_logits
         out = self.ses.forward(self._dev(t[pos0:lay.S]), nl, pos0=pos0).float().cpu().clone()

@@ -12,8 +12,8 @@ D = 64) and, under SD_PREFILL_ATTN_BLOCK=K, at any context.
   5. the public loop (speculative_sampling) and sd_batch_prefill under a forced block of 64 keys against the default route.
 
 Oracle, runner, bars and scale folding are those of tests/attn_probe.py, test_gpu_attention_edges.py and
-prefill_probe_layouts.py; their MAX_SEQ is 1040, so the long-context tests bring a runner and an oracle of their own that take
-the arena length from the model (registered for the length of a test, as the wide_models fixture does).  No bar is measured on
+prefill_probe_layouts.py; their MAX_SEQ is 1040, so the long-context tests give the runner and the oracle the arena length of
+the model (registered for the length of a test, as the wide_models fixture does).  No bar is measured on
 the code under test: bit equality, _assert_within_reference_error (HIP's error against the fp32 truth at most 1.5x the
 same-dtype oracle's own) and attn_probe.tol16 of the reference's error between the two kernels."""
 import functools
@@ -111,63 +111,9 @@ def long_models(monkeypatch):
         monkeypatch.setitem(P.MODELS, name, kw)
 
 
-class _LongRunner(Runner):
-    """Runner with the arena as long as the model's position table (Runner's is attn_probe.MAX_SEQ)."""
-
-    def __init__(self, hip, name, dt, kv_dtype=None):
-        self.hip, self.cfg = hip, P.probe_config(name)
-        self.max_seq = self.cfg.max_position_embeddings
-        dtype = P.DTYPES[dt]
-        self.m = hip.engine.SpecDecModel.from_state_dict(self.cfg, P.cast_sd(_sd(name), dtype), dtype=dtype)
-        self.ses = self.m.new_session(self.max_seq, kv_dtype=kv_dtype)
-        if kv_dtype == "fp8":
-            self.ses.kv_scale.copy_(P.fp8_scales(name).to(self.ses.kv_scale.device))
-            torch.cuda.synchronize()
-        self.with_marker = True
-        self.slots = np.full(self.max_seq, -1, dtype=np.int64)
-
-    def run(self, lay, n_logits):
-        t = P.layout_tokens(lay)
-        pos0 = lay.S - lay.n
-        self.plant(t, 0, pos0)
-        assert lay.S < self.max_seq
-        self.plant(t, lay.S, lay.S + 1)
-        out = self.ses.forward(self._dev(t[pos0:lay.S]), n_logits, pos0=pos0).float().cpu().clone()
-        self.slots[pos0:lay.S] = t[pos0:lay.S]
-        return out
-
-
-def _kv_rows(lm, ids, lo, hi, chunk=512):
-    """K / V rows lo .. hi - 1 of a ONE-layer model: they depend on token and position alone, so they are computed in
-    chunks at their own positions (the attention inside a chunk is discarded) instead of by one hi-row causal forward."""
-    assert lm.cfg.num_hidden_layers == 1
-    ks, vs = [], []
-    for a in range(lo, hi, chunk):
-        b = min(hi, a + chunk)
-        k, v = lm(ids[:, a:b], position_ids=torch.arange(a, b)[None]).past_key_values[0]
-        ks.append(k)
-        vs.append(v)
-    return torch.cat(ks, 2), torch.cat(vs, 2)
-
-
-class _LongOracle(P.ProbeOracle):
-    """ProbeOracle with the K / V rows of F and M tabulated at every position of the model (ProbeOracle: MAX_SEQ)."""
-
-    def __init__(self, name, dtype=torch.float32, kv_quant=None):
-        self.name, self.dtype = name, dtype
-        self.cfg = P.probe_config(name)
-        sd = _sd(name)
-        if kv_quant == "fp8":
-            sd = P.fp8_scaled_sd(name, sd)
-        self.sd = P.cast_sd(sd, dtype)
-        self.lm = oracle.RefCausalLM(self.cfg, self.sd, kv_quant=kv_quant)
-        n = self.cfg.max_position_embeddings
-        self.tab = {tok: _kv_rows(self.lm, torch.full((1, n), tok, dtype=torch.long), 0, n) for tok in (P.F_TOK, P.M_TOK)}
-
-
 @functools.lru_cache(maxsize=None)
 def _long_oracle(name, dt, kvq=None):
-    return _LongOracle(name, P.DTYPES[dt], kvq)
+    return P.ProbeOracle(name, P.DTYPES[dt], kvq, sd=_sd(name), max_seq=P.probe_config(name).max_position_embeddings)
 
 
 # --------------------------------------------------------------------------- 3. past the tile limit, default settings
@@ -203,7 +149,7 @@ def test_past_the_tile_limit_the_blocked_kernel_and_the_default_route(hip, long_
     for tag, flag, block in (("default", 1, 0), ("blocked", 1, 256), ("attn_kernel", 0, 0)):
         st = _Stats(f"S = 2304, {tag} {name} {dt} {kvq}")
         with _Env(SD_PREFILL_ATTN=flag, SD_PREFILL_ATTN_BLOCK=block):
-            r = _LongRunner(hip, name, dt, kv_dtype=kvq)
+            r = Runner(hip, name, dt, kv_dtype=kvq, max_seq=P.probe_config(name).max_position_embeddings)
             assert r.ses.max_rows >= n
             kernel = _route(hip, r.cfg, n, S, block) if flag else 0
             assert kernel == (2 if block else 0 if r.cfg.num_attention_heads * 16 < 2 * torch.cuda.get_device_properties(0).multi_processor_count else 2)
@@ -213,6 +159,7 @@ def test_past_the_tile_limit_the_blocked_kernel_and_the_default_route(hip, long_
                 r.plant(t, 0, S - n)
                 r.plant(t, S, S + 1)
                 before = _counts(r.ses)
+                assert lay.S < r.max_seq                           # (Runner.run plants the stale slot behind the call)
                 got[tag, lay] = r.run(lay, B.TAIL)
                 after = _counts(r.ses)
                 assert (after[0] - before[0], after[1] - before[1]) == want, (tag, lay, before, after)
@@ -236,9 +183,9 @@ def _errors(got, ref16, truth, label):
 
 
 def _ref_tail_and_verify(lm, ids, n_prompt, n_tail):
-    """Logits of the prompt's last n_tail rows and of the rows fed behind the prompt (a one-layer model: _kv_rows)."""
+    """Logits of the prompt's last n_tail rows and of the rows fed behind the prompt (a one-layer model: attn_probe.kv_rows)."""
     cut = n_prompt - n_tail
-    a = lm(ids[:, cut:n_prompt], past_key_values=[_kv_rows(lm, ids, 0, cut)])
+    a = lm(ids[:, cut:n_prompt], past_key_values=[P.kv_rows(lm, ids, 0, cut)])
     b = lm(ids[:, n_prompt:], past_key_values=a.past_key_values)
     return a.logits.float()[0], b.logits.float()[0]
 
