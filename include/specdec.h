@@ -515,6 +515,60 @@ int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, f
                            float *target_logits, long ld_target_logits, void *norm_workspace, int max_rows_per_forward,
                            float *verify_ms_out, int32_t *verify_streams_out, float *verify_ctx_out, int max_iters_log,
                            int *n_iters_out, int *err_out, void *stream);
+/* Continuous batching for the lock-step loop: any number of prompts share `n_slots` (1..16) slots.  A slot is an
+ * sd_batch_stream of which the caller fills the device side only - the two sessions, the token buffer (slot_cap ints), the
+ * probability arenas, the error words and the consecutive result blocks; the arenas and sessions hold slot_cap positions,
+ * slot_cap >= max over the prompts of max(L, T) + gamma + 2.  The loop owns the other fields.  Prompts are admitted in array
+ * order: whenever a slot's stream is done (it holds T tokens or produced a new EOS - sd_spec_batch_generate's rule) the next
+ * waiting prompt takes the slot at the next iteration boundary as a JOINER: its tokens are copied to the slot's token buffer
+ * (asynchronously, on `stream`), both cache lengths start at 0, the error words and the result block are cleared.  Its rows
+ * [0, L-1) then ride the passes the loop runs anyway - the draft rows the gamma draft steps, the target rows the verify
+ * passes - as extra items with n_logits = 0 behind the active streams' items, as many per pass as sd_spec_queue_plan gives;
+ * it decodes from the first boundary at which both models hold L-1 positions (L = 1: at once), on Philox stream (seed, 0).
+ * A prompt with L >= T is finished at admission.  While no stream is active (the start of the call, or every stream ending
+ * at once) the joiners of all slots are prefilled by sd_batch_prefill passes instead.  Each prompt runs exactly the algorithm
+ * of sd_spec_generate; everything else - arguments, statistics, *err_out, the sampling tail - is sd_spec_batch_generate's.
+ * Per prompt: its tokens (pinned host, L ints), L, the length T to reach, the EOS count of the prompt, the seed, the host
+ * token buffer (>= T + gamma + 1 ints, holding the prompt) and the per-iteration logs; out: len, calls, admit_iter (the
+ * first iteration it decodes in) and finish_iter (its last; both the boundary's iteration number for a prompt that never
+ * decodes).  passes_out (4 ints, may be NULL): passes over the target weights, passes over the draft weights, target passes
+ * that carried prompt rows only, and how many of those were sd_batch_prefill passes. */
+typedef struct {
+    const int32_t *tokens;
+    int32_t L, T, ori_eos_cnt;
+    uint64_t seed;
+    int32_t *host_seq;
+    int32_t *acc_len_out;
+    float *p_at_out, *q_at_out;
+    int32_t len, calls, admit_iter, finish_iter;
+} sd_queue_prompt;
+int sd_spec_queue_generate(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
+                           int prefill_chunk, int gamma, float temperature, int top_k, float top_p, int V, long ld,
+                           int eos_token_id, uint64_t random_seed, const float *r_const, int draft_norm_mode,
+                           int target_norm_mode, float *draft_logits, long ld_draft_logits, float *target_logits,
+                           long ld_target_logits, void *norm_workspace, int max_rows_per_forward, float *verify_ms_out,
+                           int32_t *verify_streams_out, float *verify_ctx_out, int max_iters_log, int *n_iters_out,
+                           int *passes_out, int *err_out, void *stream);
+/* The passes of one step of that loop (host only; the function the loop calls, once per draft step and once per verify).
+ * Inputs: the rows one pass may hold; the logit rows a pass may hold once not every row is one (sd_batch_forward: 64); the
+ * active streams' row counts, in order (n_act <= 16), and whether those rows are all logit rows (a verify) or one per
+ * stream (a draft step); the joiners' remaining rows in queue order (n_join <= 16); prefill_chunk, the most joiner rows a
+ * pass may carry (0: whatever room it has); force_progress.  The active streams are cut into passes of whole streams, in
+ * order, as many per pass as the rows allow (at least one, at most 16) - with no joiner that is sd_spec_batch_generate's
+ * split.  Each pass then takes joiner rows, first joiner first, one chunk per joiner: up to row_budget minus the pass's
+ * rows, up to prefill_chunk, up to 16 items in all, and none when its logit rows exceed mixed_logit_limit.  With
+ * force_progress, when a joiner has rows left and no pass took one, a last pass without active streams carries joiner rows
+ * only.  passes[p] = active streams [act0, act0 + n_act) and chunks[chunk0 .. chunk0 + n_chunks); a chunk = (joiner, its
+ * first row counted from the joiner's next row, rows); a joiner's chunks are consecutive over the passes. */
+typedef struct {
+    int32_t act0, n_act, chunk0, n_chunks;
+} sd_queue_pass;
+typedef struct {
+    int32_t joiner, row0, rows;
+} sd_queue_chunk;
+int sd_spec_queue_plan(int row_budget, int mixed_logit_limit, const int32_t *act_rows, int n_act, int logit_rows,
+                       const int32_t *join_rows, int n_join, int prefill_chunk, int force_progress, sd_queue_pass *passes,
+                       int max_passes, sd_queue_chunk *chunks, int max_chunks, int *n_passes_out, int *n_chunks_out);
 /* The whole loop of multi_speculative_sampling(strategy="iid") (speculative_sampling.py:1379-1716) for the device-RNG mode,
  * no interpreter between iterations.  `width` replicas, each with its own sessions, token buffer and probability arenas;
  * per iteration: gamma draft steps (one pass over the draft weights for all replicas each, sampled straight into

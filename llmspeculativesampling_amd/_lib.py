@@ -63,6 +63,20 @@ class SdBatchStream(C.Structure):
                 ("q_at_out", C.c_void_p)]
 
 
+class SdQueuePrompt(C.Structure):
+    _fields_ = [("tokens", C.c_void_p), ("L", C.c_int32), ("T", C.c_int32), ("ori_eos_cnt", C.c_int32), ("seed", C.c_uint64),
+                ("host_seq", C.c_void_p), ("acc_len_out", C.c_void_p), ("p_at_out", C.c_void_p), ("q_at_out", C.c_void_p),
+                ("len", C.c_int32), ("calls", C.c_int32), ("admit_iter", C.c_int32), ("finish_iter", C.c_int32)]
+
+
+class SdQueuePass(C.Structure):
+    _fields_ = [("act0", C.c_int32), ("n_act", C.c_int32), ("chunk0", C.c_int32), ("n_chunks", C.c_int32)]
+
+
+class SdQueueChunk(C.Structure):
+    _fields_ = [("joiner", C.c_int32), ("row0", C.c_int32), ("rows", C.c_int32)]
+
+
 class SdArStream(C.Structure):
     _fields_ = [("session", C.c_void_p), ("seq", C.c_void_p), ("probs", C.c_void_p), ("err_words", C.c_void_p),
                 ("host_seq", C.c_void_p), ("len", C.c_int32), ("T", C.c_int32), ("cache_len", C.c_int32),
@@ -149,6 +163,10 @@ SYMBOLS = [
     ("sd_accept_resample_batch", _I, [C.POINTER(SdAcceptItem), _I, _L, _I, _I, _I, _VPP, _VP]),   # internal
     ("sd_spec_batch_generate", _I, [_VP, _I, _I, C.c_float, _I, C.c_float, _I, C.c_long, _I, C.c_uint64, _VP, _I, _I, _VP,
                                     C.c_long, _VP, C.c_long, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
+    ("sd_spec_queue_generate", _I, [C.POINTER(SdBatchStream), _I, _I, C.POINTER(SdQueuePrompt), _I, _I, _I, _F, _I, _F, _I, _L, _I,
+                                    _U64, _VP, _I, _I, _VP, _L, _VP, _L, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
+    ("sd_spec_queue_plan", _I, [_I, _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(C.c_int32), _I, _I, _I, C.POINTER(SdQueuePass), _I,
+                                C.POINTER(SdQueueChunk), _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("sd_spec_generate", _I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP,
                               _VP, _VP, _VP]),
     ("sd_ar_block_bytes", C.c_size_t, [_I]),

@@ -1,4 +1,5 @@
-// spec_loops.h - the native decode loops (single stream, lock-step streams, width-w iid, autoregressive streams) and the steps
+// spec_loops.h - the native decode loops (single stream, lock-step streams with or without a prompt queue, width-w iid,
+// autoregressive streams) and the steps
 // they share.  Host code - and the one small kernel of the autoregressive loop's hand-off - included at the end of
 // engine.hip, whose sd_session, HeadReq / HeadOut and session_forward / batch_forward it uses.
 #pragma once
@@ -348,50 +349,215 @@ extern "C" int sd_spec_generate(sd_spec *sp, int32_t *host_seq, int *len_io, int
     return rc;
 }
 
-// The stream-batched loop of sampling/batch.py in native code (reference algorithm per stream: speculative_sampling.py:1934-2046).
-extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, float temperature, int top_k,
-                                      float top_p, int V, long ld, int eos_token_id, uint64_t random_seed,
-                                      const float *r_const, int draft_norm_mode, int target_norm_mode, float *draft_logits,
-                                      long ld_draft_logits, float *target_logits, long ld_target_logits,
-                                      void *norm_workspace, int max_rows_per_forward, float *verify_ms_out,
-                                      int32_t *verify_streams_out, float *verify_ctx_out, int max_iters_log,
-                                      int *n_iters_out, int *err_out, void *stream) {
-    SD_REQUIRE(streams && n_streams >= 1 && n_streams <= 16 && gamma >= 1 && gamma <= 16 && draft_logits && target_logits &&
-               n_iters_out && err_out, "sd_spec_batch_generate: bad arguments");
-    SD_REQUIRE(!random_seed || r_const, "sd_spec_batch_generate: random_seed needs its uniform (r_const)");
-    for (int i = 1; i < n_streams; ++i)
-        SD_REQUIRE(streams[i].res_dev == streams[0].res_dev + i && streams[i].res_host == streams[0].res_host + i,
-                   "sd_spec_batch_generate: the streams' result blocks must be consecutive");
+// ---- the prompt queue of the lock-step loop ---------------------------------------------------------------------
+// The passes of one draft step or one verify (include/specdec.h has the contract): whole active streams per pass, then the
+// joiners' rows where a pass has room.  Host only; lockstep_loop calls it for every step it enqueues.
+extern "C" int sd_spec_queue_plan(int row_budget, int mixed_logit_limit, const int32_t *act_rows, int n_act, int logit_rows,
+                                  const int32_t *join_rows, int n_join, int prefill_chunk, int force_progress,
+                                  sd_queue_pass *passes, int max_passes, sd_queue_chunk *chunks, int max_chunks,
+                                  int *n_passes_out, int *n_chunks_out) {
+    SD_REQUIRE(passes && chunks && n_passes_out && n_chunks_out, "sd_spec_queue_plan: null argument");
+    SD_REQUIRE(row_budget >= 1 && mixed_logit_limit >= 0 && prefill_chunk >= 0, "sd_spec_queue_plan: row_budget %d, logit limit %d, "
+               "prefill_chunk %d", row_budget, mixed_logit_limit, prefill_chunk);
+    SD_REQUIRE(n_act >= 0 && n_act <= SD_MAX_STREAMS && n_join >= 0 && n_join <= SD_MAX_STREAMS && (n_act == 0 || act_rows) &&
+               (n_join == 0 || join_rows), "sd_spec_queue_plan: 0..%d active streams and joiners", SD_MAX_STREAMS);
+    for (int j = 0; j < n_act; ++j) SD_REQUIRE(act_rows[j] >= 1, "sd_spec_queue_plan: active stream %d has %d rows", j, act_rows[j]);
+    int left[SD_MAX_STREAMS], off[SD_MAX_STREAMS];
+    bool waiting = false;
+    for (int j = 0; j < n_join; ++j) {
+        SD_REQUIRE(join_rows[j] >= 0, "sd_spec_queue_plan: joiner %d has %d rows left", j, join_rows[j]);
+        left[j] = join_rows[j]; off[j] = 0;
+        waiting = waiting || left[j] > 0;
+    }
+    int np = 0, nc = 0;
+    // the joiner rows pass `p` carries next to `rows` rows of `items` active streams, `logits` of them logit rows
+    auto ride = [&](sd_queue_pass &p, int rows, int items, int logits) -> bool {
+        int room = logits > mixed_logit_limit ? 0 : row_budget - rows;
+        if (prefill_chunk > 0) room = std::min(room, prefill_chunk);
+        p.chunk0 = nc; p.n_chunks = 0;
+        for (int j = 0; j < n_join && room > 0 && items < SD_MAX_STREAMS; ++j) {
+            const int c = std::min(left[j], room);
+            if (c <= 0) continue;
+            if (nc >= max_chunks) return false;
+            chunks[nc++] = sd_queue_chunk{j, off[j], c};
+            ++p.n_chunks; ++items;
+            left[j] -= c; off[j] += c; room -= c;
+        }
+        return true;
+    };
+    bool fits = true;
+    for (int a = 0; a < n_act && fits;) {
+        int rows = 0, m = 0;
+        while (a + m < n_act && m < SD_MAX_STREAMS && (m == 0 || rows + act_rows[a + m] <= row_budget)) rows += act_rows[a + m++];
+        if (np >= max_passes) { fits = false; break; }
+        sd_queue_pass &p = passes[np++];
+        p.act0 = a; p.n_act = m;
+        fits = ride(p, rows, m, logit_rows ? rows : m);
+        a += m;
+    }
+    if (fits && force_progress && waiting && nc == 0) {           // the progress guarantee: a pass of joiner rows only
+        if (np >= max_passes) fits = false;
+        else {
+            sd_queue_pass &p = passes[np++];
+            p.act0 = n_act; p.n_act = 0;
+            fits = ride(p, 0, 0, 0);
+        }
+    }
+    if (!fits) {
+        sd_set_error("sd_spec_queue_plan: the plan exceeds %d passes / %d chunks", max_passes, max_chunks);
+        return SD_ERR_CAPACITY;
+    }
+    *n_passes_out = np; *n_chunks_out = nc;
+    return SD_OK;
+}
+
+// What the queue adds to the lock-step loop (NULL there: every stream arrives loaded and prefilled)
+struct PromptQueue {
+    sd_queue_prompt *prompts;
+    int n_prompts, prefill_chunk;
+    int next = 0;                                                 // the first prompt that still waits
+    int occ[SD_MAX_STREAMS];                                      // the prompt in slot i, -1: free
+    bool joining[SD_MAX_STREAMS];                                 // ... whose rows [0, L-1) are not all cached yet
+    int target_passes = 0, draft_passes = 0, extra_passes = 0, prefill_passes = 0;
+};
+
+// An iteration boundary of the queue: done streams hand their results to their prompts and free their slots, waiting
+// prompts take free slots as joiners, joiners whose two caches hold L-1 positions become active.
+static int queue_boundary(PromptQueue &q, sd_batch_stream *slots, int n_slots, int iters, int g, hipStream_t st) {
+    for (int i = 0; i < n_slots; ++i) {
+        sd_batch_stream &s = slots[i];
+        if (q.occ[i] >= 0 && s.done) {
+            sd_queue_prompt &p = q.prompts[q.occ[i]];
+            p.len = s.len; p.calls = s.calls; p.finish_iter = iters - 1;
+            q.occ[i] = -1;
+        }
+        while (q.occ[i] < 0 && q.next < q.n_prompts) {
+            sd_queue_prompt &p = q.prompts[q.next];
+            p.len = p.L; p.calls = 0; p.admit_iter = p.finish_iter = iters;
+            if (p.L >= p.T) { ++q.next; continue; }               // nothing to generate: the prompt is the result
+            SD_HIP_CHECK(hipMemcpyAsync(s.seq, p.tokens, sizeof(int32_t) * (size_t)p.L, hipMemcpyHostToDevice, st));
+            SD_HIP_CHECK(hipMemsetAsync(s.err_words, 0, sizeof(int) * (size_t)(3 * g + 1), st));
+            SD_HIP_CHECK(hipMemsetAsync(s.res_dev, 0, sizeof(sd_accept_result), st));
+            s.host_seq = p.host_seq; s.len = p.L; s.T = p.T; s.ori_eos_cnt = p.ori_eos_cnt;
+            s.draft_len = s.target_len = 0;
+            s.seed = p.seed; s.draw = 0; s.done = 0; s.calls = 0;
+            s.acc_len_out = p.acc_len_out; s.p_at_out = p.p_at_out; s.q_at_out = p.q_at_out;
+            q.occ[i] = q.next++;
+            q.joining[i] = true;
+        }
+        if (q.occ[i] >= 0 && q.joining[i] && s.draft_len == s.len - 1 && s.target_len == s.len - 1) {
+            q.joining[i] = false;
+            q.prompts[q.occ[i]].admit_iter = iters;
+        }
+    }
+    return SD_OK;
+}
+
+// No stream is active: what the joiners still miss of their rows [0, L-1) goes through sd_batch_prefill passes, packed in
+// queue order - up to the sessions' row budget, 32 attention groups of 8 rows and 16 items per pass, a long prompt in chunks.
+static int queue_idle_prefill(PromptQueue &q, sd_batch_stream *slots, const std::vector<int> &join, void *stream) {
+    std::vector<sd_batch_item> items;
+    for (int side = 0; side < 2; ++side) {
+        int cap = SD_MAX_FWD_ROWS, rows = 0, groups = 0, rc;
+        for (int i : join) cap = std::min(cap, (side ? slots[i].target : slots[i].draft)->max_rows);
+        items.clear();
+        auto flush = [&]() -> int {
+            if (items.empty()) return SD_OK;
+            const int r = sd_batch_prefill(items.data(), (int)items.size(), stream);
+            if (side) { ++q.target_passes; ++q.extra_passes; ++q.prefill_passes; } else ++q.draft_passes;
+            items.clear(); rows = groups = 0;
+            return r;
+        };
+        for (int i : join) {
+            sd_batch_stream &s = slots[i];
+            int &have = side ? s.target_len : s.draft_len;
+            while (have < s.len - 1) {
+                const int c = std::min({s.len - 1 - have, cap - rows, (SD_MAX_GROUPS - groups) * ATT_TQ});
+                if (c <= 0 || (int)items.size() >= SD_MAX_STREAMS) { if ((rc = flush()) != SD_OK) return rc; continue; }
+                items.push_back(sd_batch_item{side ? s.target : s.draft, s.seq, have, c, 0});
+                have += c; rows += c; groups += (c + ATT_TQ - 1) / ATT_TQ;
+            }
+        }
+        if ((rc = flush()) != SD_OK) return rc;
+    }
+    return SD_OK;
+}
+
+// The lock-step loop of sampling/batch.py in native code (reference algorithm per stream: speculative_sampling.py:1934-2046),
+// with or without a prompt queue behind the streams' slots.
+static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_streams, PromptQueue *q, int gamma, float temperature,
+                         int top_k, float top_p, int V, long ld, int eos_token_id, uint64_t random_seed, const float *r_const,
+                         int draft_norm_mode, int target_norm_mode, float *draft_logits, long ld_draft_logits,
+                         float *target_logits, long ld_target_logits, void *norm_workspace, int max_rows_per_forward,
+                         float *verify_ms_out, int32_t *verify_streams_out, float *verify_ctx_out, int max_iters_log,
+                         int *n_iters_out, int *err_out, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     const int g = gamma, n_err = 3 * g + 1;
-    // streams per target pass (every verify row is a logit row: sd_model_max_pass_rows, 64 for a model whose lm_head or
-    // per-layer GEMMs stop at the streaming kernel)
+    // rows per target pass (every verify row is a logit row: sd_model_max_pass_rows, 64 for a model whose lm_head or
+    // per-layer GEMMs stop at the streaming kernel) and per draft pass (sd_batch_forward's own limit)
     const int pass_rows = std::min(max_rows_per_forward, streams[0].target ? streams[0].target->max_pass_rows : SD_MAX_ROWS);
-    const int max_verify = std::max(1, pass_rows / (g + 1));
-    LoopEvents ev(2, "sd_spec_batch_generate");
+    const int draft_rows = std::min(streams[0].draft ? streams[0].draft->max_rows : SD_MAX_ROWS, SD_MAX_ROWS);
+    LoopEvents ev(2, who);
     if (!ev.ok) return SD_ERR_HIP;
     *err_out = 0;
     int iters = 0, rc = SD_OK;
     std::vector<sd_batch_stream *> act;
-    std::vector<int> Ls;
+    std::vector<int> Ls, join;
     std::vector<Draws> draws;
     std::vector<sd_batch_item> items;
     std::vector<sd_norm_row> rows;
     std::vector<sd_accept_item> aitems;
     std::vector<const void *> list_of;
+    int32_t act_rows[SD_MAX_STREAMS], join_rows[SD_MAX_STREAMS];
+    sd_queue_pass passes[SD_MAX_STREAMS + 1];
+    sd_queue_chunk chunks[(SD_MAX_STREAMS + 1) * SD_MAX_STREAMS];
+    int n_passes = 0, n_chunks = 0;
+    // the passes of a draft step (side 0) or of the verify (side 1) over act_rows[], joiners riding where there is room
+    auto plan = [&](int side, bool force) -> int {
+        for (size_t k = 0; k < join.size(); ++k) {
+            const sd_batch_stream &s = streams[join[k]];
+            join_rows[k] = s.len - 1 - (side ? s.target_len : s.draft_len);
+        }
+        return sd_spec_queue_plan(side ? pass_rows : draft_rows, SD_STREAM_MAX_ROWS, act_rows, (int)act.size(), side, join_rows,
+                                  (int)join.size(), q ? q->prefill_chunk : 0, force, passes, SD_MAX_STREAMS + 1, chunks,
+                                  (SD_MAX_STREAMS + 1) * SD_MAX_STREAMS, &n_passes, &n_chunks);
+    };
+    // the joiner items of pass `p`, behind its active streams' items (no logit rows: the logit rows stay packed in stream order)
+    auto add_joiners = [&](const sd_queue_pass &p, int side) {
+        for (int k = p.chunk0; k < p.chunk0 + p.n_chunks; ++k) {
+            sd_batch_stream &s = streams[join[chunks[k].joiner]];
+            int &have = side ? s.target_len : s.draft_len;
+            items.push_back(sd_batch_item{side ? s.target : s.draft, s.seq, have, chunks[k].rows, 0});
+            have += chunks[k].rows;
+        }
+        if (!q) return;
+        ++(side ? q->target_passes : q->draft_passes);
+        if (side && p.n_act == 0) ++q->extra_passes;
+    };
     // SD_BATCH_FUSED_TAIL=0: the round-1 sampling tail (logits copy, candidate pass + norm per draft step; dense accept scan +
     // resample) - kept for A/B runs and as the reference the fused tail is tested against; read per call
     const bool fused_tail = !(getenv("SD_BATCH_FUSED_TAIL") && atoi(getenv("SD_BATCH_FUSED_TAIL")) == 0);
     const bool tiles_ok = head_tiles_ok(top_k, temperature, V, ld);
-    for (int i = 0; i < n_streams; ++i) { streams[i].done = 0; streams[i].calls = 0; }
+    for (int i = 0; i < n_streams; ++i) {
+        streams[i].done = q ? 1 : 0; streams[i].calls = 0;
+        if (q) { q->occ[i] = -1; q->joining[i] = false; }
+    }
     for (;;) {
-        act.clear();
+        for (int i = 0; i < n_streams; ++i)
+            if (!streams[i].done && streams[i].len >= streams[i].T) streams[i].done = 1;
+        if (q && (rc = queue_boundary(*q, streams, n_streams, iters, g, st)) != SD_OK) break;
+        act.clear(); join.clear();
         for (int i = 0; i < n_streams; ++i) {
-            sd_batch_stream &s = streams[i];
-            if (!s.done && s.len >= s.T) s.done = 1;
-            if (!s.done) act.push_back(&s);
+            if (streams[i].done) continue;
+            if (q && q->joining[i]) join.push_back(i);
+            else act.push_back(&streams[i]);
         }
-        if (act.empty()) break;
+        if (q) std::sort(join.begin(), join.end(), [&](int a, int b) { return q->occ[a] < q->occ[b]; });
+        if (act.empty()) {
+            if (join.empty()) break;
+            if ((rc = queue_idle_prefill(*q, streams, join, stream)) != SD_OK) break;
+            continue;                                             // (the boundary makes them active)
+        }
         const int n = (int)act.size();
         Ls.resize(n); draws.resize(n);
         double ctx = 0.0;
@@ -401,49 +567,63 @@ extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, i
             act[j]->draw += (uint64_t)g;                          // (a failed forward leaves the stream here, seed untouched)
             ctx += Ls[j];
         }
+        // ---- draft: gamma steps over all active streams
+        bool rode = false;                                        // a joiner's draft rows rode a pass of this iteration
+        for (int i = 0; i < g && rc == SD_OK; ++i) {
+            for (int j = 0; j < n; ++j) act_rows[j] = Ls[j] + i - act[j]->draft_len;
+            if ((rc = plan(0, i == g - 1 && !rode)) != SD_OK) break;
+            rode = rode || n_chunks > 0;
+            for (int p = 0; p < n_passes && rc == SD_OK; ++p) {
+                const int a0 = passes[p].act0, m = passes[p].n_act;
+                items.assign(m, sd_batch_item{});
+                rows.assign(m, sd_norm_row{});
+                for (int j = 0; j < m; ++j) {
+                    sd_batch_stream &s = *act[a0 + j];
+                    draft_step_rows(items[j], rows[j], s.draft, s.seq, s.q_hist, ld, s.err_words, g, Ls[a0 + j], i, s.draft_len,
+                                    draws[a0 + j].seed_draft, draws[a0 + j].draft0 + (uint64_t)i);
+                    s.draft_len = Ls[a0 + j] + i;
+                }
+                add_joiners(passes[p], 0);
+                // the single-stream loop's sampler feed (sd_spec_iteration): the head leaves the logits in its own slab, the
+                // maximum of every 16-column tile, and clears the streams' probability rows - no logits copy, no candidate pass
+                HeadReq rq = {};
+                HeadOut ho = {};
+                rq.raw = fused_tail;
+                rq.zero_n = fused_tail && tiles_ok && m <= 16 ? m : 0;
+                for (int j = 0; j < rq.zero_n; ++j) rq.zero_ptr[j] = rows[j].probs_out;
+                if ((rc = batch_forward(items.data(), (int)items.size(), draft_logits, ld_draft_logits, &rq, &ho, stream)) != SD_OK) break;
+                if (m == 0) continue;                             // (joiner rows only)
+                if (fused_tail)
+                    rc = sd_norm_batch_tiles(ho.logits, m, V, ho.ld, temperature, top_k, top_p, ho.round | draft_norm_mode, rows.data(),
+                                             1, norm_workspace, ho.tile_max, nullptr, stream);
+                else
+                    rc = sd_norm_batch(draft_logits, m, V, ld_draft_logits, temperature, top_k, top_p, draft_norm_mode, rows.data(), 1,
+                                       norm_workspace, stream);
+            }
+        }
+        if (rc != SD_OK) break;
+        // ---- verify: the uncached rows of every stream, as many whole streams per pass over the target weights as it holds
+        for (int j = 0; j < n; ++j) act_rows[j] = Ls[j] + g - act[j]->target_len;
+        if ((rc = plan(1, true)) != SD_OK) break;
         // the residual / bonus sample works on the target rows' candidate lists when ONE verify pass holds all streams (the
         // workspace keeps the lists of one pass)
-        const bool lists_on = fused_tail && norm_workspace && n <= max_verify;
+        const bool lists_on = fused_tail && norm_workspace && passes[0].n_act == n;
         char *const list_base = norm_workspace ? (char *)norm_workspace + sd_norm_candrow_bytes(max_rows_per_forward) : nullptr;
         const size_t list_stride = sd_cand_list_bytes(1);
         list_of.assign(n, nullptr);
-        // ---- draft: gamma steps over all active streams
-        for (int i = 0; i < g && rc == SD_OK; ++i) {
-            items.assign(n, sd_batch_item{});
-            rows.assign(n, sd_norm_row{});
-            for (int j = 0; j < n; ++j) {
-                sd_batch_stream &s = *act[j];
-                draft_step_rows(items[j], rows[j], s.draft, s.seq, s.q_hist, ld, s.err_words, g, Ls[j], i, s.draft_len,
-                                draws[j].seed_draft, draws[j].draft0 + (uint64_t)i);
-                s.draft_len = Ls[j] + i;
-            }
-            // the single-stream loop's sampler feed (sd_spec_iteration): the head leaves the logits in its own slab, the
-            // maximum of every 16-column tile, and clears the streams' probability rows - no logits copy, no candidate pass
-            HeadReq rq = {};
-            HeadOut ho = {};
-            rq.raw = fused_tail;
-            rq.zero_n = fused_tail && tiles_ok && n <= 16 ? n : 0;
-            for (int j = 0; j < rq.zero_n; ++j) rq.zero_ptr[j] = rows[j].probs_out;
-            if ((rc = batch_forward(items.data(), n, draft_logits, ld_draft_logits, &rq, &ho, stream)) != SD_OK) break;
-            if (fused_tail)
-                rc = sd_norm_batch_tiles(ho.logits, n, V, ho.ld, temperature, top_k, top_p, ho.round | draft_norm_mode, rows.data(), 1,
-                                         norm_workspace, ho.tile_max, nullptr, stream);
-            else
-                rc = sd_norm_batch(draft_logits, n, V, ld_draft_logits, temperature, top_k, top_p, draft_norm_mode, rows.data(), 1,
-                                   norm_workspace, stream);
-        }
-        if (rc != SD_OK) break;
-        // ---- verify: the uncached rows of every stream, max_verify streams per pass over the target weights
         SD_LOOP_HIP(hipEventRecord(ev.t[0], st));
-        for (int a0 = 0; a0 < n && rc == SD_OK; a0 += max_verify) {
-            const int m = std::min(max_verify, n - a0);
+        for (int p = 0; p < n_passes && rc == SD_OK; ++p) {
+            const int a0 = passes[p].act0, m = passes[p].n_act;
             items.assign(m, sd_batch_item{});
             rows.clear();
             for (int j = 0; j < m; ++j) {
                 sd_batch_stream &s = *act[a0 + j];
                 verify_pass_rows(items[j], rows, s.target, s.seq, s.p_hist, ld, s.err_words, g, Ls[a0 + j], s.target_len);
             }
-            if ((rc = batch_forward(items.data(), m, target_logits, ld_target_logits, nullptr, nullptr, stream)) != SD_OK) break;
+            add_joiners(passes[p], 1);
+            if ((rc = batch_forward(items.data(), (int)items.size(), target_logits, ld_target_logits, nullptr, nullptr, stream)) != SD_OK)
+                break;
+            if (m == 0) continue;                                 // (joiner rows only)
             // one pass holds every stream: the rows' candidate lists (behind the CandRows of the workspace) serve the
             // residual / bonus sample below
             rc = sd_norm_batch_tiles(target_logits, (int)rows.size(), V, ld_target_logits, temperature, top_k, top_p, target_norm_mode,
@@ -458,7 +638,9 @@ extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, i
         }
         if (rc != SD_OK) break;
         SD_LOOP_HIP(hipEventRecord(ev.t[1], st));
-        // ---- accept scan + residual / bonus sample, all streams in two launches
+        // ---- accept scan + residual / bonus sample, all streams in two launches.  The scan reads probability rows L-1 ..
+        // L+gamma-1 only, and this iteration wrote every one of them: the q rows in its draft steps, the p rows in the verify's
+        // sd_norm_batch_tiles above, which writes whole rows.  So a slot's p_hist / q_hist never show a previous occupant.
         aitems.assign(n, sd_accept_item{});
         for (int j = 0; j < n; ++j) {
             sd_batch_stream &s = *act[j];
@@ -476,7 +658,7 @@ extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, i
         SD_LOOP_HIP(hipMemcpyAsync(streams[0].res_host, streams[0].res_dev, sizeof(sd_accept_result) * (size_t)n_streams,
                                    hipMemcpyDeviceToHost, st));
         SD_LOOP_HIP(hipEventRecord(ev.done, st));
-        if ((rc = poll_event(ev.done, "sd_spec_batch_generate")) != SD_OK) break;
+        if ((rc = poll_event(ev.done, who)) != SD_OK) break;
         if (iters < max_iters_log) {
             float ms = 0.f;
             if (verify_ms_out && hipEventElapsedTime(&ms, ev.t[0], ev.t[1]) == hipSuccess) verify_ms_out[iters] = ms;
@@ -500,6 +682,73 @@ extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, i
         if (failed) { *err_out = 1; break; }
     }
     *n_iters_out = iters;
+    return rc;
+}
+
+static int check_result_blocks(const char *who, const sd_batch_stream *streams, int n_streams) {
+    for (int i = 1; i < n_streams; ++i)
+        SD_REQUIRE(streams[i].res_dev == streams[0].res_dev + i && streams[i].res_host == streams[0].res_host + i,
+                   "%s: the streams' result blocks must be consecutive", who);
+    return SD_OK;
+}
+
+extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, float temperature, int top_k,
+                                      float top_p, int V, long ld, int eos_token_id, uint64_t random_seed,
+                                      const float *r_const, int draft_norm_mode, int target_norm_mode, float *draft_logits,
+                                      long ld_draft_logits, float *target_logits, long ld_target_logits,
+                                      void *norm_workspace, int max_rows_per_forward, float *verify_ms_out,
+                                      int32_t *verify_streams_out, float *verify_ctx_out, int max_iters_log,
+                                      int *n_iters_out, int *err_out, void *stream) {
+    SD_REQUIRE(streams && n_streams >= 1 && n_streams <= 16 && gamma >= 1 && gamma <= 16 && draft_logits && target_logits &&
+               n_iters_out && err_out, "sd_spec_batch_generate: bad arguments");
+    SD_REQUIRE(!random_seed || r_const, "sd_spec_batch_generate: random_seed needs its uniform (r_const)");
+    if (int rc = check_result_blocks("sd_spec_batch_generate", streams, n_streams); rc != SD_OK) return rc;
+    return lockstep_loop("sd_spec_batch_generate", streams, n_streams, nullptr, gamma, temperature, top_k, top_p, V, ld, eos_token_id,
+                         random_seed, r_const, draft_norm_mode, target_norm_mode, draft_logits, ld_draft_logits, target_logits,
+                         ld_target_logits, norm_workspace, max_rows_per_forward, verify_ms_out, verify_streams_out, verify_ctx_out,
+                         max_iters_log, n_iters_out, err_out, stream);
+}
+
+extern "C" int sd_spec_queue_generate(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
+                                      int prefill_chunk, int gamma, float temperature, int top_k, float top_p, int V, long ld,
+                                      int eos_token_id, uint64_t random_seed, const float *r_const, int draft_norm_mode,
+                                      int target_norm_mode, float *draft_logits, long ld_draft_logits, float *target_logits,
+                                      long ld_target_logits, void *norm_workspace, int max_rows_per_forward,
+                                      float *verify_ms_out, int32_t *verify_streams_out, float *verify_ctx_out,
+                                      int max_iters_log, int *n_iters_out, int *passes_out, int *err_out, void *stream) {
+    SD_REQUIRE(n_slots >= 1 && n_slots <= 16, "sd_spec_queue_generate: n_slots %d outside 1..16", n_slots);
+    SD_REQUIRE(gamma >= 1 && gamma <= 16, "sd_spec_queue_generate: gamma %d outside 1..16", gamma);
+    SD_REQUIRE(n_prompts >= 1 && prefill_chunk >= 0, "sd_spec_queue_generate: n_prompts %d, prefill_chunk %d", n_prompts, prefill_chunk);
+    SD_REQUIRE(slots && prompts && draft_logits && target_logits && n_iters_out && err_out, "sd_spec_queue_generate: null argument");
+    SD_REQUIRE(!random_seed || r_const, "sd_spec_queue_generate: random_seed needs its uniform (r_const)");
+    for (int i = 0; i < n_slots; ++i) {
+        const sd_batch_stream &s = slots[i];
+        SD_REQUIRE(s.draft && s.target && s.seq && s.q_hist && s.p_hist && s.err_words && s.res_dev && s.res_host,
+                   "sd_spec_queue_generate: slot %d: null pointer", i);
+        SD_REQUIRE(s.draft->m == slots[0].draft->m && s.target->m == slots[0].target->m,
+                   "sd_spec_queue_generate: slot %d: sessions of another model than slot 0's", i);
+    }
+    if (int rc = check_result_blocks("sd_spec_queue_generate", slots, n_slots); rc != SD_OK) return rc;
+    for (int k = 0; k < n_prompts; ++k) {
+        const sd_queue_prompt &p = prompts[k];
+        SD_REQUIRE(p.tokens && p.host_seq && p.L >= 1, "sd_spec_queue_generate: prompt %d: null pointer or L %d < 1", k, p.L);
+        const int need = std::max(p.L, p.T) + gamma + 2;
+        SD_REQUIRE(need <= slot_cap, "sd_spec_queue_generate: prompt %d needs %d positions per slot, slot_cap is %d", k, need, slot_cap);
+    }
+    for (int i = 0; i < n_slots; ++i)
+        SD_REQUIRE(slots[i].draft->max_seq >= slot_cap - 2 && slots[i].target->max_seq >= slot_cap - 2,
+                   "sd_spec_queue_generate: slot %d: KV arenas of %d / %d positions, slot_cap %d needs %d", i, slots[i].draft->max_seq,
+                   slots[i].target->max_seq, slot_cap, slot_cap - 2);
+    PromptQueue q;
+    q.prompts = prompts; q.n_prompts = n_prompts; q.prefill_chunk = prefill_chunk;
+    const int rc = lockstep_loop("sd_spec_queue_generate", slots, n_slots, &q, gamma, temperature, top_k, top_p, V, ld, eos_token_id,
+                                 random_seed, r_const, draft_norm_mode, target_norm_mode, draft_logits, ld_draft_logits,
+                                 target_logits, ld_target_logits, norm_workspace, max_rows_per_forward, verify_ms_out,
+                                 verify_streams_out, verify_ctx_out, max_iters_log, n_iters_out, err_out, stream);
+    if (passes_out) {
+        passes_out[0] = q.target_passes; passes_out[1] = q.draft_passes;
+        passes_out[2] = q.extra_passes; passes_out[3] = q.prefill_passes;
+    }
     return rc;
 }
 

@@ -63,6 +63,34 @@ def open_stream(model, prompt_row, cap: int, seq_len: int, temperature, top_k, t
     return kv, seq32
 
 
+def open_spec_slot(draft_m, target_m, prompt_row, cap: int, gamma: int, temperature, top_k, top_p):
+    """The device state of one lock-step speculative stream (or of one slot of the prompt queue): the two KVCacheModels with
+    arenas for ``cap`` positions, the int32 token buffer (``cap + 1`` entries, starting with ``prompt_row``) and the
+    3 * gamma + 1 error words."""
+    draft, _ = open_stream(draft_m, None, cap, 0, temperature, top_k, top_p)
+    target, seq32 = open_stream(target_m, prompt_row, cap, cap + 1, temperature, top_k, top_p)
+    err = torch.zeros(3 * gamma + 1, dtype=torch.int32, device=target_m.device)
+    return draft, target, seq32, err
+
+
+def bind_spec_slot(item, draft, target, seq32, err, res_dev: int, res_host: int) -> None:
+    """The device side of an SdBatchStream: sessions, token buffer, probability arenas, error words, result blocks."""
+    item.draft, item.target = draft._session.handle, target._session.handle
+    item.seq, item.q_hist, item.p_hist = seq32.data_ptr(), draft._probs.data_ptr(), target._probs.data_ptr()
+    item.err_words = err.data_ptr()
+    item.res_dev, item.res_host = res_dev, res_host
+
+
+def lockstep_result(log: "LoopLog", n_tokens: int, calls: int, eos_token_id, ori_eos: int, device):
+    """What a lock-step loop returns for one stream: the (1, len) int64 tokens, cut after the first new EOS, and the
+    reference's ``details`` dict (no phase times: the streams share their passes)."""
+    out = cut_after_new_eos(log.tokens(n_tokens), eos_token_id, ori_eos)
+    rate = accept_rates_f64(*log.ratios(calls))
+    det = details_dict(0, 0, 0, log.acc_len(calls), float(np.mean(rate)) if rate else 0.0, calls, calls,
+                       target_model_time=0, target_pre_cache_time=0, target_post_prob_time=0)
+    return torch.tensor([out], dtype=torch.int64, device=device), det
+
+
 class LoopLog:
     """The host arrays one native loop call (or one stream of it) writes: the token buffer, the accepted length per
     iteration, ``per_iter`` logged p / q values per iteration and, when ``timed``, the two phases' milliseconds."""

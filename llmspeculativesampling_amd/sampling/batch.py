@@ -6,6 +6,9 @@ ONE stream, the tokens produced are B times as many.
 Every stream keeps its own KV arenas, probability arenas, token buffer and Philox stream, and runs exactly the
 per-stream algorithm of reference sampling/speculative_sampling.py:1876-2076 (batch size 1 there, :1905): with the
 same seeds the outputs equal those of B separate ``speculative_sampling(..., rng=DeviceNoise(seed))`` calls.
+
+``speculative_sampling_queue`` puts a prompt queue behind the same loop (continuous batching): any number of prompts share
+up to 16 slots, and a stream that ends hands its slot to the next waiting prompt.
 """
 from __future__ import annotations
 
@@ -16,10 +19,10 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from .._lib import lib, check, SdAcceptResult, SdBatchStream
+from .._lib import lib, check, SdAcceptResult, SdBatchStream, SdQueuePrompt
 from ..engine import as_specdec_model, _stream, check_token_ids, same_device, batch_prefill
 from ..noise import DeviceNoise
-from ._loop_common import LoopLog, accept_rates_f64, cut_after_new_eos, details_dict, open_stream, reseed_uniforms
+from ._loop_common import LoopLog, bind_spec_slot, lockstep_result, open_spec_slot, open_stream, reseed_uniforms
 from .autoregressive_sampling import ArRun
 from .kvcache_model import KVCacheModel
 
@@ -74,10 +77,8 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
         L = pf.shape[1]
         T = L + max_len
         cap = T + gamma + 2
-        draft, _ = open_stream(draft_m, None, cap, 0, temperature, top_k, top_p)
-        target, seq32 = open_stream(target_m, pf[0], cap, cap + 1, temperature, top_k, top_p)
+        draft, target, seq32, err = open_spec_slot(draft_m, target_m, pf[0], cap, gamma, temperature, top_k, top_p)
         host = [int(t) for t in pf[0].tolist()]
-        err = torch.zeros(3 * gamma + 1, dtype=torch.int32, device=dev)
         streams.append(_Stream(draft, target, seq32, err, DeviceNoise(seeds[i]),
                                LoopLog(host, cap, max_iters, gamma, q_fill=1.0), L, T, host.count(eos_token_id)))
 
@@ -96,11 +97,7 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
     cu = _stream()
     arr = (SdBatchStream * B)()
     for i, (it, s) in enumerate(zip(arr, streams)):
-        it.draft, it.target = s.draft._session.handle, s.target._session.handle
-        it.seq, it.q_hist, it.p_hist = s.seq32.data_ptr(), s.draft._probs.data_ptr(), s.target._probs.data_ptr()
-        it.err_words = s.err.data_ptr()
-        it.res_dev = res_dev.data_ptr() + i * res_sz
-        it.res_host = res_host.data_ptr() + i * res_sz
+        bind_spec_slot(it, s.draft, s.target, s.seq32, s.err, res_dev.data_ptr() + i * res_sz, res_host.data_ptr() + i * res_sz)
         it.host_seq = s.log.host_seq.ctypes.data
         it.len, it.T, it.ori_eos_cnt = s.prompt_len, s.T, s.ori_eos
         it.draft_len = it.target_len = s.prompt_len - 1
@@ -128,11 +125,115 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
     for it, s, pf in zip(arr, streams, prefixes):
         s.noise.seed, s.noise.draw = it.seed, it.draw
         s.draft._session.cache_len, s.target._session.cache_len = it.draft_len, it.target_len
-        out = cut_after_new_eos(s.log.tokens(it.len), eos_token_id, s.ori_eos)
-        outs.append(torch.tensor([out], dtype=torch.int64, device=pf.device))
-        rate = accept_rates_f64(*s.log.ratios(it.calls))
-        ds.append(details_dict(0, 0, 0, s.log.acc_len(it.calls), float(np.mean(rate)) if rate else 0.0, it.calls, it.calls,
-                               target_model_time=0, target_pre_cache_time=0, target_post_prob_time=0))
+        out, det = lockstep_result(s.log, it.len, it.calls, eos_token_id, s.ori_eos, pf.device)
+        outs.append(out)
+        ds.append(det)
+    return (outs, ds) if details else outs
+
+
+def _queue_arguments(prefixes, max_len, seeds, slots):
+    """speculative_sampling_queue's argument checks (before a model or the GPU is touched); returns the per-prompt budgets."""
+    if isinstance(slots, bool) or not isinstance(slots, int) or not 1 <= slots <= 16:
+        raise ValueError(f"slots: 1..16 streams decode at once, not {slots!r}")
+    try:
+        N = len(prefixes)
+    except TypeError:
+        raise ValueError("prefixes: a sequence of (1, L) int64 prompts is required") from None
+    if N < 1:
+        raise ValueError("prefixes: at least one prompt is required")
+    for i, pf in enumerate(prefixes):
+        if not isinstance(pf, torch.Tensor) or pf.dim() != 2 or pf.shape[0] != 1 or pf.shape[1] < 1:
+            raise ValueError(f"prefixes[{i}]: every prompt is one (1, L >= 1) tensor, got "
+                             f"{tuple(pf.shape) if isinstance(pf, torch.Tensor) else type(pf).__name__}")
+    if seeds is not None and len(seeds) != N:
+        raise ValueError(f"seeds: {len(seeds)} seeds for {N} prompts")
+    if isinstance(max_len, (int, np.integer)):
+        return [int(max_len)] * N
+    if len(max_len) != N:
+        raise ValueError(f"max_len: {len(max_len)} budgets for {N} prompts")
+    return [int(m) for m in max_len]
+
+
+@torch.no_grad()
+def speculative_sampling_queue(prefixes: Sequence[torch.Tensor], approx_model, target_model, eos_token_id, pad_token_id,
+                               max_len, gamma: int = 4, temperature: float = 1, top_k: int = 0, top_p: float = 0,
+                               random_seed: int = None, details: bool = False, seeds: Optional[Sequence[int]] = None,
+                               slots: int = 8, prefill_chunk: int = 0, _timing: Optional[dict] = None):
+    """Continuous batching: any number of prompts share ``slots`` lock-step streams (sd_spec_queue_generate).  Prompts are
+    admitted in list order; a stream that ends at a new EOS or at its length (``max_len``: one int, or one per prompt) hands
+    its slot to the next waiting prompt, whose prefill rides the passes the other streams run anyway - at most
+    ``prefill_chunk`` prompt rows per pass (0: whatever room a pass has).  Prompt i runs on Philox stream ``seeds[i]``
+    (default ``torch.initial_seed() + i``) from draw 0 wherever and whenever it is admitted: its tokens, ``acc_len`` and call
+    counts equal those of ``speculative_sampling(prefixes[i], ..., max_len_i, rng=DeviceNoise(seeds[i]))``.  Returns the
+    outputs in prompt order (and the ``details`` dicts of speculative_sampling_batch when ``details``).
+    ``_timing`` receives "verify" entries as speculative_sampling_batch writes them, "iterations", "target_passes",
+    "draft_passes", "extra_passes" (target passes that carried prompt rows only; "prefill_passes" of them ran while no
+    stream was active) and per prompt "admit_iter" / "finish_iter" (its first / last iteration)."""
+    budgets = _queue_arguments(prefixes, max_len, seeds, slots)
+    if isinstance(prefill_chunk, bool) or not isinstance(prefill_chunk, int) or prefill_chunk < 0:
+        raise ValueError(f"prefill_chunk: a row count >= 0 is required, not {prefill_chunk!r}")
+    if not 1 <= gamma <= 16:
+        raise ValueError(f"gamma: 1..16, not {gamma}")
+    draft_m, target_m = as_specdec_model(approx_model), as_specdec_model(target_model)
+    same_device(draft_m, target_m)
+    dev = target_m.device
+    V = target_m.cfg.vocab_size
+    assert draft_m.cfg.vocab_size == V
+    for pf in prefixes:
+        check_token_ids(pf, V)
+    N = len(prefixes)
+    S = min(slots, N)
+    seeds = list(seeds) if seeds is not None else [int(torch.initial_seed()) + i for i in range(N)]
+    lens = [pf.shape[1] for pf in prefixes]
+    cap = max(L + max(m, 0) for L, m in zip(lens, budgets)) + gamma + 2   # every slot holds the largest prompt of the call
+    res_sz = C.sizeof(SdAcceptResult)
+    res_dev = torch.zeros((S, res_sz), dtype=torch.uint8, device=dev)
+    res_host = torch.zeros((S, res_sz), dtype=torch.uint8).pin_memory()
+    r_const = reseed_uniforms(random_seed, gamma, dev)
+    empty = torch.zeros(0, dtype=torch.int64)
+    held = [open_spec_slot(draft_m, target_m, empty, cap, gamma, temperature, top_k, top_p) for _ in range(S)]
+    slot_arr = (SdBatchStream * S)()
+    for i, (it, (draft, target, seq32, err)) in enumerate(zip(slot_arr, held)):
+        bind_spec_slot(it, draft, target, seq32, err, res_dev.data_ptr() + i * res_sz, res_host.data_ptr() + i * res_sz)
+    # the prompts wait in pinned host memory: the loop copies one into its slot when it is admitted
+    tokens = torch.cat([pf[0].to(device="cpu", dtype=torch.int32) for pf in prefixes]).pin_memory()
+    offs = np.concatenate([[0], np.cumsum(lens)])
+    logs, arr = [], (SdQueuePrompt * N)()
+    for i, (it, pf, L, m) in enumerate(zip(arr, prefixes, lens, budgets)):
+        host = tokens[offs[i]:offs[i + 1]].tolist()
+        T = L + m
+        log = LoopLog(host, max(L, T) + gamma + 2, max(1, m) + 1, gamma, q_fill=1.0)
+        logs.append(log)
+        it.tokens = tokens.data_ptr() + int(offs[i]) * 4
+        it.L, it.T, it.ori_eos_cnt, it.seed = L, T, host.count(eos_token_id), int(seeds[i]) & 0xFFFFFFFFFFFFFFFF
+        it.host_seq = log.host_seq.ctypes.data
+        it.acc_len_out, it.p_at_out, it.q_at_out = log.ptrs()[:3]
+    d0, t0 = held[0][0]._session, held[0][1]._session
+    per_pass = t0.max_pass_rows
+    norm_ws = torch.empty(lib.sd_norm_workspace_bytes(per_pass), dtype=torch.uint8, device=dev)
+    n_log = sum(max(1, m) + 1 for m in budgets)                   # (an iteration has at least one stream in it)
+    v_ms = np.zeros(n_log, dtype=np.float32)
+    v_n = np.zeros(n_log, dtype=np.int32)
+    v_ctx = np.zeros(n_log, dtype=np.float32)
+    c_iters, c_err, passes = C.c_int(0), C.c_int(0), (C.c_int * 4)()
+    check(lib.sd_spec_queue_generate(slot_arr, S, cap, arr, N, prefill_chunk, gamma, float(temperature), int(top_k or 0),
+                                     float(top_p or 0.0), V, held[0][0]._probs.stride(0), int(eos_token_id),
+                                     int(random_seed or 0), r_const.data_ptr() if r_const is not None else None,
+                                     draft_m.norm_mode, target_m.norm_mode, d0.logits.data_ptr(), d0.logits.stride(0),
+                                     t0.logits.data_ptr(), t0.logits.stride(0), norm_ws.data_ptr(), per_pass,
+                                     v_ms.ctypes.data, v_n.ctypes.data, v_ctx.ctypes.data, n_log, C.byref(c_iters), passes,
+                                     C.byref(c_err), _stream()), "sd_spec_queue_generate")
+    if c_err.value:
+        raise RuntimeError("s")
+    if _timing is not None:
+        for i in range(min(c_iters.value, n_log)):
+            _timing.setdefault("verify", []).append((_Ms(float(v_ms[i])), None, int(v_n[i]), float(v_ctx[i])))
+        _timing.update(iterations=c_iters.value, target_passes=passes[0], draft_passes=passes[1], extra_passes=passes[2],
+                       prefill_passes=passes[3], admit_iter=[it.admit_iter for it in arr],
+                       finish_iter=[it.finish_iter for it in arr])
+    res = [lockstep_result(log, it.len, it.calls, eos_token_id, it.ori_eos_cnt, pf.device)
+           for it, log, pf in zip(arr, logs, prefixes)]
+    outs, ds = [r[0] for r in res], [r[1] for r in res]
     return (outs, ds) if details else outs
 
 

@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""Times continuous batching (speculative_sampling_queue) against the calls of speculative_sampling_batch it replaces, on the
+pair bench.py uses (llama-68m -> llama-2-13b, random-init weights through synth.py, bf16, device RNG, top_k 20 / top_p 0.9,
+gamma 4, 8 slots).
+
+    python tools/queue_bench.py [--workloads ragged,uniform --reps 5 --json-out profiles/queue_bench.json]
+
+Two workloads, EOS off (every prompt generates its max_len):
+  ragged   32 prompts with the lengths of harness.synthetic_prompts (bench.py --prompt-lens synthetic-c3), cut to what a
+           slot's arenas hold, max_len alternating 32 / 128.  queue: one call, 8 slots.  batch: four calls of
+           speculative_sampling_batch with 8 prompts each, in list order - each call runs until its slowest stream is done.
+  uniform  8 prompts of 128 tokens, max_len 128: one queue call against one batch call.  The queue has nothing to admit
+           after the start and must cost nothing: its median has to lie within the min-max spread of the batch reps.
+Both arms run in this process, alternated rep by rep after one warm-up rep of each (which also loads every kernel); a rep is
+the whole call or calls, prefill included, between two device synchronisations on the host clock.  Per arm: tokens/s per rep
+and their median, iterations, passes over the target weights (verify passes plus prompt-only passes; for the batch arm the
+prefill passes engine.batch_prefill packs plus one verify pass per iteration - 8 streams x 5 rows fit one) and the mean number
+of streams per iteration.  The pass counts depend on the tokens alone (on how often a draft is accepted), not on the clock.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from llmspeculativesampling_amd.config import load_config  # noqa: E402
+from llmspeculativesampling_amd.engine import SpecDecModel, MAX_PREFILL_ROWS  # noqa: E402
+from llmspeculativesampling_amd.harness import synthetic_prompts  # noqa: E402
+from llmspeculativesampling_amd.sampling import speculative_sampling_batch, speculative_sampling_queue  # noqa: E402
+
+SLOTS, GAMMA = 8, 4
+
+
+def prefill_passes(lens):
+    """Passes engine.batch_prefill needs for prompts of these lengths (its greedy packing: 256 rows, 32 groups of 8 rows)."""
+    passes = rows = groups = 0
+    for n in (L - 1 for L in lens):
+        if n <= 0:
+            continue
+        g = (n + 7) // 8
+        if n > MAX_PREFILL_ROWS or g > 32:
+            passes += (rows > 0) + (n + MAX_PREFILL_ROWS - 1) // MAX_PREFILL_ROWS
+            rows = groups = 0
+            continue
+        if rows + n > MAX_PREFILL_ROWS or groups + g > 32:
+            passes, rows, groups = passes + 1, 0, 0
+        rows, groups = rows + n, groups + g
+    return passes + (rows > 0)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--draft", default="llama-68m")
+    ap.add_argument("--target", default="llama-2-13b")
+    ap.add_argument("--workloads", default="ragged,uniform")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--max-prompt", type=int, default=512, help="prompts are cut to this many tokens")
+    ap.add_argument("--json-out", default=None)
+    a = ap.parse_args()
+    dcfg, tcfg = load_config(a.draft), load_config(a.target)
+    max_pos = min(dcfg.max_position_embeddings, tcfg.max_position_embeddings, a.max_prompt + 128 + GAMMA + 8)
+    cut = max_pos - 128 - GAMMA - 8                               # a prompt and its slot fit
+    dm = SpecDecModel.synthetic(dcfg, seed=1, dtype=torch.bfloat16, max_pos=max_pos)
+    tm = SpecDecModel.synthetic(tcfg, seed=2, dtype=torch.bfloat16, max_pos=max_pos)
+    kw = dict(gamma=GAMMA, top_k=20, top_p=0.9)
+    work = {}
+    if "ragged" in a.workloads:
+        ps = [p[:, :cut].cuda() for p in synthetic_prompts(100, tcfg.vocab_size, seed=5)[:32]]
+        work["ragged"] = (ps, [32 if i % 2 == 0 else 128 for i in range(32)])
+    if "uniform" in a.workloads:
+        ps = [torch.from_numpy(np.random.default_rng(100 + i).integers(3, tcfg.vocab_size, size=(1, 128))).cuda() for i in range(8)]
+        work["uniform"] = (ps, [128] * 8)
+    out = {"config": {k: v for k, v in vars(a).items() if k != "json_out"}, "dtype": "bfloat16", "slots": SLOTS, "gamma": GAMMA,
+           "workloads": {}}
+    for name, (prompts, budgets) in work.items():
+        lens = [int(p.shape[1]) for p in prompts]
+
+        def queue(seed0):
+            t = {}
+            outs = speculative_sampling_queue(prompts, dm, tm, -1, None, budgets, seeds=[seed0 + i for i in range(len(prompts))],
+                                              slots=SLOTS, _timing=t, **kw)
+            return outs, dict(iterations=t["iterations"], target_passes=t["target_passes"], extra_passes=t["extra_passes"],
+                              mean_streams=float(np.mean([v[2] for v in t["verify"]])))
+
+        def batch(seed0):
+            outs, iters, passes, streams = [], 0, 0, []
+            for c in range(0, len(prompts), SLOTS):
+                t = {}
+                # a call takes one max_len: the longest budget of its prompts, every output cut to its own budget afterwards
+                got = speculative_sampling_batch(prompts[c:c + SLOTS], dm, tm, -1, None, max(budgets[c:c + SLOTS]),
+                                                 seeds=[seed0 + c + i for i in range(len(prompts[c:c + SLOTS]))], _timing=t, **kw)
+                outs += [o[:, :L + m] for o, L, m in zip(got, lens[c:], budgets[c:])]
+                iters += len(t["verify"])
+                passes += len(t["verify"]) + prefill_passes(lens[c:c + SLOTS])
+                streams += [v[2] for v in t["verify"]]
+            return outs, dict(iterations=iters, target_passes=passes, extra_passes=None, mean_streams=float(np.mean(streams)))
+
+        arms = {"queue": queue, "batch": batch}
+        stats = {}
+        for arm, fn in arms.items():                               # warm-up of every shape
+            stats[arm] = fn(1000)[1]
+        torch.cuda.synchronize()
+        rates = {arm: [] for arm in arms}
+        for r in range(a.reps):
+            for arm, fn in arms.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                outs, st = fn(2000 + 100 * r)
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                # the useful tokens: what each prompt asked for (an iteration may overshoot max_len by up to gamma)
+                rates[arm].append(sum(min(o.shape[1] - L, m) for o, L, m in zip(outs, lens, budgets)) / dt)
+                stats[arm] = st
+        res = {arm: dict(stats[arm], tokens_per_s_reps=v, tokens_per_s_median=float(np.median(v))) for arm, v in rates.items()}
+        res["queue_over_batch_tokens_per_s"] = res["queue"]["tokens_per_s_median"] / res["batch"]["tokens_per_s_median"]
+        res["queue_median_within_batch_spread"] = bool(min(rates["batch"]) <= res["queue"]["tokens_per_s_median"] <= max(rates["batch"]))
+        res["prompt_lens"], res["max_len"] = lens, budgets
+        out["workloads"][name] = res
+        print(json.dumps({name: res}), flush=True)
+    if a.json_out:
+        with open(a.json_out, "w") as f:
+            json.dump(out, f, indent=1, sort_keys=True)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
