@@ -569,6 +569,34 @@ typedef struct {
 int sd_spec_queue_plan(int row_budget, int mixed_logit_limit, const int32_t *act_rows, int n_act, int logit_rows,
                        const int32_t *join_rows, int n_join, int prefill_chunk, int force_progress, sd_queue_pass *passes,
                        int max_passes, sd_queue_chunk *chunks, int max_chunks, int *n_passes_out, int *n_chunks_out);
+/* Session-to-session KV copy.  KV positions [lo, hi) of every layer, K and V, and KV head go from src's arena to each dst's
+ * arena, as bytes; one launch on `stream` serves all items, 1..16 of them.  The arenas may hold different numbers of
+ * positions.  Refused with SD_ERR_INVALID before any launch: a null argument, n_items outside 1..16, a dst of another model
+ * than src's, dst == src, one arena fp8 and the other not, lo < 0, hi < lo, hi past either arena.  An item with hi == lo is
+ * skipped, and a call whose items are all empty launches nothing.  fp8 arenas: the stored bytes mean the same in both sessions
+ * only under equal scale tables - the caller answers for that.  No cache length is read or written: lengths live with the
+ * callers. */
+typedef struct {
+    sd_session *dst;
+    int32_t lo, hi;
+} sd_kv_copy_item;
+int sd_session_copy_kv(const sd_session *src, const sd_kv_copy_item *items, int n_items, void *stream);
+/* sd_spec_queue_generate for prompts that start with the same tokens.  The donors are sessions of the draft and the target
+ * model that hold positions [0, shared_rows) of those tokens - prefilled by the caller on `stream` - and stay untouched.  A
+ * prompt that takes a slot starts with both cache lengths at c = min(shared_rows, L - 1), not at 0: those rows reach the
+ * slot's arenas through one sd_session_copy_kv launch per model for all prompts admitted at that iteration boundary, on
+ * `stream`, ahead of the iteration's forwards; its rows [c, L-1) then ride the passes as sd_spec_queue_generate describes
+ * (c == L-1: it decodes from that boundary on).  Null donors with shared_rows 0 give sd_spec_queue_generate itself.
+ * passes_out (6 ints, may be NULL): the 4 of sd_spec_queue_generate, then the target rows forwarded for prompts inside the
+ * call, then the KV rows copied per model, summed over the prompts. */
+int sd_spec_queue_generate_shared(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
+                                  int prefill_chunk, int gamma, float temperature, int top_k, float top_p, int V, long ld,
+                                  int eos_token_id, uint64_t random_seed, const float *r_const, int draft_norm_mode,
+                                  int target_norm_mode, float *draft_logits, long ld_draft_logits, float *target_logits,
+                                  long ld_target_logits, void *norm_workspace, int max_rows_per_forward, float *verify_ms_out,
+                                  int32_t *verify_streams_out, float *verify_ctx_out, int max_iters_log, int *n_iters_out,
+                                  int *passes_out, int *err_out, void *stream, sd_session *donor_draft,
+                                  sd_session *donor_target, int shared_rows);
 /* The whole loop of multi_speculative_sampling(strategy="iid") (speculative_sampling.py:1379-1716) for the device-RNG mode,
  * no interpreter between iterations.  `width` replicas, each with its own sessions, token buffer and probability arenas;
  * per iteration: gamma draft steps (one pass over the draft weights for all replicas each, sampled straight into

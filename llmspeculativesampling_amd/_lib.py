@@ -77,6 +77,10 @@ class SdQueueChunk(C.Structure):
     _fields_ = [("joiner", C.c_int32), ("row0", C.c_int32), ("rows", C.c_int32)]
 
 
+class SdKvCopyItem(C.Structure):
+    _fields_ = [("dst", C.c_void_p), ("lo", C.c_int32), ("hi", C.c_int32)]
+
+
 class SdArStream(C.Structure):
     _fields_ = [("session", C.c_void_p), ("seq", C.c_void_p), ("probs", C.c_void_p), ("err_words", C.c_void_p),
                 ("host_seq", C.c_void_p), ("len", C.c_int32), ("T", C.c_int32), ("cache_len", C.c_int32),
@@ -165,6 +169,10 @@ SYMBOLS = [
                                     C.c_long, _VP, C.c_long, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
     ("sd_spec_queue_generate", _I, [C.POINTER(SdBatchStream), _I, _I, C.POINTER(SdQueuePrompt), _I, _I, _I, _F, _I, _F, _I, _L, _I,
                                     _U64, _VP, _I, _I, _VP, _L, _VP, _L, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
+    ("sd_spec_queue_generate_shared", _I, [C.POINTER(SdBatchStream), _I, _I, C.POINTER(SdQueuePrompt), _I, _I, _I, _F, _I, _F, _I, _L,
+                                           _I, _U64, _VP, _I, _I, _VP, _L, _VP, _L, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP,
+                                           _VP, _VP, _I]),
+    ("sd_session_copy_kv", _I, [_VP, C.POINTER(SdKvCopyItem), _I, _VP]),
     ("sd_spec_queue_plan", _I, [_I, _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(C.c_int32), _I, _I, _I, C.POINTER(SdQueuePass), _I,
                                 C.POINTER(SdQueueChunk), _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("sd_spec_generate", _I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP,

@@ -17,6 +17,7 @@
 #include "fused_kernels.h"
 #include "normload_kernels.h"
 #include "multi_kernels.h"
+#include "kv_copy_kernels.h"
 
 static thread_local char g_err[512] = "";
 void sd_set_error(const char *fmt, ...) {

@@ -419,11 +419,17 @@ struct PromptQueue {
     int occ[SD_MAX_STREAMS];                                      // the prompt in slot i, -1: free
     bool joining[SD_MAX_STREAMS];                                 // ... whose rows [0, L-1) are not all cached yet
     int target_passes = 0, draft_passes = 0, extra_passes = 0, prefill_passes = 0;
+    // a shared prompt prefix (sd_spec_queue_generate_shared): the donors hold positions [0, shared_rows) of the two models
+    sd_session *donor_draft = nullptr, *donor_target = nullptr;
+    int shared_rows = 0;
+    int prompt_rows = 0, copied_rows = 0;                         // target rows forwarded for prompts; KV rows copied per model
 };
 
 // An iteration boundary of the queue: done streams hand their results to their prompts and free their slots, waiting
 // prompts take free slots as joiners, joiners whose two caches hold L-1 positions become active.
 static int queue_boundary(PromptQueue &q, sd_batch_stream *slots, int n_slots, int iters, int g, hipStream_t st) {
+    sd_kv_copy_item d_copy[SD_MAX_STREAMS], t_copy[SD_MAX_STREAMS];   // the shared prefix rows of the prompts admitted here
+    int n_copy = 0;
     for (int i = 0; i < n_slots; ++i) {
         sd_batch_stream &s = slots[i];
         if (q.occ[i] >= 0 && s.done) {
@@ -439,7 +445,14 @@ static int queue_boundary(PromptQueue &q, sd_batch_stream *slots, int n_slots, i
             SD_HIP_CHECK(hipMemsetAsync(s.err_words, 0, sizeof(int) * (size_t)(3 * g + 1), st));
             SD_HIP_CHECK(hipMemsetAsync(s.res_dev, 0, sizeof(sd_accept_result), st));
             s.host_seq = p.host_seq; s.len = p.L; s.T = p.T; s.ori_eos_cnt = p.ori_eos_cnt;
-            s.draft_len = s.target_len = 0;
+            // the shared prefix comes from the donors; the last prompt token is always fed as the first decode row
+            const int c = std::min(q.shared_rows, p.L - 1);
+            s.draft_len = s.target_len = c;
+            if (c > 0) {
+                d_copy[n_copy] = sd_kv_copy_item{s.draft, 0, c};
+                t_copy[n_copy++] = sd_kv_copy_item{s.target, 0, c};
+                q.copied_rows += c;
+            }
             s.seed = p.seed; s.draw = 0; s.done = 0; s.calls = 0;
             s.acc_len_out = p.acc_len_out; s.p_at_out = p.p_at_out; s.q_at_out = p.q_at_out;
             q.occ[i] = q.next++;
@@ -449,6 +462,10 @@ static int queue_boundary(PromptQueue &q, sd_batch_stream *slots, int n_slots, i
             q.joining[i] = false;
             q.prompts[q.occ[i]].admit_iter = iters;
         }
+    }
+    if (n_copy) {                                                 // one launch per model, ahead of every forward of the iteration
+        if (int rc = sd_session_copy_kv(q.donor_draft, d_copy, n_copy, st); rc != SD_OK) return rc;
+        if (int rc = sd_session_copy_kv(q.donor_target, t_copy, n_copy, st); rc != SD_OK) return rc;
     }
     return SD_OK;
 }
@@ -476,6 +493,7 @@ static int queue_idle_prefill(PromptQueue &q, sd_batch_stream *slots, const std:
                 if (c <= 0 || (int)items.size() >= SD_MAX_STREAMS) { if ((rc = flush()) != SD_OK) return rc; continue; }
                 items.push_back(sd_batch_item{side ? s.target : s.draft, s.seq, have, c, 0});
                 have += c; rows += c; groups += (c + ATT_TQ - 1) / ATT_TQ;
+                if (side) q.prompt_rows += c;
             }
         }
         if ((rc = flush()) != SD_OK) return rc;
@@ -529,6 +547,7 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
             int &have = side ? s.target_len : s.draft_len;
             items.push_back(sd_batch_item{side ? s.target : s.draft, s.seq, have, chunks[k].rows, 0});
             have += chunks[k].rows;
+            if (side) q->prompt_rows += chunks[k].rows;
         }
         if (!q) return;
         ++(side ? q->target_passes : q->draft_passes);
@@ -709,6 +728,64 @@ extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, i
                          max_iters_log, n_iters_out, err_out, stream);
 }
 
+// The two entry points of the prompt queue: `who` names the one that was called; without donors (shared_rows 0) the loop is
+// sd_spec_queue_generate's, pass for pass.  n_passes_out: how many ints of passes_out the entry point documents.
+static int queue_generate(const char *who, int n_passes_out, sd_session *donor_draft, sd_session *donor_target, int shared_rows,
+                          sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
+                          int prefill_chunk, int gamma, float temperature, int top_k, float top_p, int V, long ld,
+                          int eos_token_id, uint64_t random_seed, const float *r_const, int draft_norm_mode,
+                          int target_norm_mode, float *draft_logits, long ld_draft_logits, float *target_logits,
+                          long ld_target_logits, void *norm_workspace, int max_rows_per_forward,
+                          float *verify_ms_out, int32_t *verify_streams_out, float *verify_ctx_out,
+                          int max_iters_log, int *n_iters_out, int *passes_out, int *err_out, void *stream) {
+    SD_REQUIRE(n_slots >= 1 && n_slots <= 16, "%s: n_slots %d outside 1..16", who, n_slots);
+    SD_REQUIRE(gamma >= 1 && gamma <= 16, "%s: gamma %d outside 1..16", who, gamma);
+    SD_REQUIRE(n_prompts >= 1 && prefill_chunk >= 0, "%s: n_prompts %d, prefill_chunk %d", who, n_prompts, prefill_chunk);
+    SD_REQUIRE(slots && prompts && draft_logits && target_logits && n_iters_out && err_out, "%s: null argument", who);
+    SD_REQUIRE(!random_seed || r_const, "%s: random_seed needs its uniform (r_const)", who);
+    SD_REQUIRE(shared_rows >= 0 && (shared_rows > 0) == (donor_draft != nullptr) && (shared_rows > 0) == (donor_target != nullptr),
+               "%s: shared_rows %d needs both donor sessions, and 0 rows none", who, shared_rows);
+    for (int i = 0; i < n_slots; ++i) {
+        const sd_batch_stream &s = slots[i];
+        SD_REQUIRE(s.draft && s.target && s.seq && s.q_hist && s.p_hist && s.err_words && s.res_dev && s.res_host,
+                   "%s: slot %d: null pointer", who, i);
+        SD_REQUIRE(s.draft->m == slots[0].draft->m && s.target->m == slots[0].target->m,
+                   "%s: slot %d: sessions of another model than slot 0's", who, i);
+    }
+    if (shared_rows > 0) {
+        SD_REQUIRE(donor_draft->m == slots[0].draft->m && donor_target->m == slots[0].target->m,
+                   "%s: the donors are sessions of other models than the slots'", who);
+        SD_REQUIRE(shared_rows <= donor_draft->max_seq && shared_rows <= donor_target->max_seq,
+                   "%s: shared_rows %d, the donors hold %d / %d positions", who, shared_rows, donor_draft->max_seq,
+                   donor_target->max_seq);
+        SD_REQUIRE(donor_draft->kv_fp8 == slots[0].draft->kv_fp8 && donor_target->kv_fp8 == slots[0].target->kv_fp8,
+                   "%s: the donors' KV arenas have another dtype than the slots'", who);
+    }
+    if (int rc = check_result_blocks(who, slots, n_slots); rc != SD_OK) return rc;
+    for (int k = 0; k < n_prompts; ++k) {
+        const sd_queue_prompt &p = prompts[k];
+        SD_REQUIRE(p.tokens && p.host_seq && p.L >= 1, "%s: prompt %d: null pointer or L %d < 1", who, k, p.L);
+        const int need = std::max(p.L, p.T) + gamma + 2;
+        SD_REQUIRE(need <= slot_cap, "%s: prompt %d needs %d positions per slot, slot_cap is %d", who, k, need, slot_cap);
+    }
+    for (int i = 0; i < n_slots; ++i)
+        SD_REQUIRE(slots[i].draft->max_seq >= slot_cap - 2 && slots[i].target->max_seq >= slot_cap - 2,
+                   "%s: slot %d: KV arenas of %d / %d positions, slot_cap %d needs %d", who, i, slots[i].draft->max_seq,
+                   slots[i].target->max_seq, slot_cap, slot_cap - 2);
+    PromptQueue q;
+    q.prompts = prompts; q.n_prompts = n_prompts; q.prefill_chunk = prefill_chunk;
+    q.donor_draft = donor_draft; q.donor_target = donor_target; q.shared_rows = shared_rows;
+    const int rc = lockstep_loop(who, slots, n_slots, &q, gamma, temperature, top_k, top_p, V, ld, eos_token_id,
+                                 random_seed, r_const, draft_norm_mode, target_norm_mode, draft_logits, ld_draft_logits,
+                                 target_logits, ld_target_logits, norm_workspace, max_rows_per_forward, verify_ms_out,
+                                 verify_streams_out, verify_ctx_out, max_iters_log, n_iters_out, err_out, stream);
+    if (passes_out) {
+        const int v[6] = {q.target_passes, q.draft_passes, q.extra_passes, q.prefill_passes, q.prompt_rows, q.copied_rows};
+        for (int i = 0; i < n_passes_out; ++i) passes_out[i] = v[i];
+    }
+    return rc;
+}
+
 extern "C" int sd_spec_queue_generate(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
                                       int prefill_chunk, int gamma, float temperature, int top_k, float top_p, int V, long ld,
                                       int eos_token_id, uint64_t random_seed, const float *r_const, int draft_norm_mode,
@@ -716,40 +793,26 @@ extern "C" int sd_spec_queue_generate(sd_batch_stream *slots, int n_slots, int s
                                       long ld_target_logits, void *norm_workspace, int max_rows_per_forward,
                                       float *verify_ms_out, int32_t *verify_streams_out, float *verify_ctx_out,
                                       int max_iters_log, int *n_iters_out, int *passes_out, int *err_out, void *stream) {
-    SD_REQUIRE(n_slots >= 1 && n_slots <= 16, "sd_spec_queue_generate: n_slots %d outside 1..16", n_slots);
-    SD_REQUIRE(gamma >= 1 && gamma <= 16, "sd_spec_queue_generate: gamma %d outside 1..16", gamma);
-    SD_REQUIRE(n_prompts >= 1 && prefill_chunk >= 0, "sd_spec_queue_generate: n_prompts %d, prefill_chunk %d", n_prompts, prefill_chunk);
-    SD_REQUIRE(slots && prompts && draft_logits && target_logits && n_iters_out && err_out, "sd_spec_queue_generate: null argument");
-    SD_REQUIRE(!random_seed || r_const, "sd_spec_queue_generate: random_seed needs its uniform (r_const)");
-    for (int i = 0; i < n_slots; ++i) {
-        const sd_batch_stream &s = slots[i];
-        SD_REQUIRE(s.draft && s.target && s.seq && s.q_hist && s.p_hist && s.err_words && s.res_dev && s.res_host,
-                   "sd_spec_queue_generate: slot %d: null pointer", i);
-        SD_REQUIRE(s.draft->m == slots[0].draft->m && s.target->m == slots[0].target->m,
-                   "sd_spec_queue_generate: slot %d: sessions of another model than slot 0's", i);
-    }
-    if (int rc = check_result_blocks("sd_spec_queue_generate", slots, n_slots); rc != SD_OK) return rc;
-    for (int k = 0; k < n_prompts; ++k) {
-        const sd_queue_prompt &p = prompts[k];
-        SD_REQUIRE(p.tokens && p.host_seq && p.L >= 1, "sd_spec_queue_generate: prompt %d: null pointer or L %d < 1", k, p.L);
-        const int need = std::max(p.L, p.T) + gamma + 2;
-        SD_REQUIRE(need <= slot_cap, "sd_spec_queue_generate: prompt %d needs %d positions per slot, slot_cap is %d", k, need, slot_cap);
-    }
-    for (int i = 0; i < n_slots; ++i)
-        SD_REQUIRE(slots[i].draft->max_seq >= slot_cap - 2 && slots[i].target->max_seq >= slot_cap - 2,
-                   "sd_spec_queue_generate: slot %d: KV arenas of %d / %d positions, slot_cap %d needs %d", i, slots[i].draft->max_seq,
-                   slots[i].target->max_seq, slot_cap, slot_cap - 2);
-    PromptQueue q;
-    q.prompts = prompts; q.n_prompts = n_prompts; q.prefill_chunk = prefill_chunk;
-    const int rc = lockstep_loop("sd_spec_queue_generate", slots, n_slots, &q, gamma, temperature, top_k, top_p, V, ld, eos_token_id,
-                                 random_seed, r_const, draft_norm_mode, target_norm_mode, draft_logits, ld_draft_logits,
-                                 target_logits, ld_target_logits, norm_workspace, max_rows_per_forward, verify_ms_out,
-                                 verify_streams_out, verify_ctx_out, max_iters_log, n_iters_out, err_out, stream);
-    if (passes_out) {
-        passes_out[0] = q.target_passes; passes_out[1] = q.draft_passes;
-        passes_out[2] = q.extra_passes; passes_out[3] = q.prefill_passes;
-    }
-    return rc;
+    return queue_generate("sd_spec_queue_generate", 4, nullptr, nullptr, 0, slots, n_slots, slot_cap, prompts, n_prompts,
+                          prefill_chunk, gamma, temperature, top_k, top_p, V, ld,
+                          eos_token_id, random_seed, r_const, draft_norm_mode, target_norm_mode, draft_logits, ld_draft_logits,
+                          target_logits, ld_target_logits, norm_workspace, max_rows_per_forward, verify_ms_out, verify_streams_out,
+                          verify_ctx_out, max_iters_log, n_iters_out, passes_out, err_out, stream);
+}
+
+extern "C" int sd_spec_queue_generate_shared(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
+                                             int prefill_chunk, int gamma, float temperature, int top_k, float top_p, int V, long ld,
+                                             int eos_token_id, uint64_t random_seed, const float *r_const, int draft_norm_mode,
+                                             int target_norm_mode, float *draft_logits, long ld_draft_logits, float *target_logits,
+                                             long ld_target_logits, void *norm_workspace, int max_rows_per_forward,
+                                             float *verify_ms_out, int32_t *verify_streams_out, float *verify_ctx_out,
+                                             int max_iters_log, int *n_iters_out, int *passes_out, int *err_out, void *stream,
+                                             sd_session *donor_draft, sd_session *donor_target, int shared_rows) {
+    return queue_generate("sd_spec_queue_generate_shared", 6, donor_draft, donor_target, shared_rows, slots, n_slots, slot_cap,
+                          prompts, n_prompts, prefill_chunk, gamma, temperature, top_k, top_p, V, ld,
+                          eos_token_id, random_seed, r_const, draft_norm_mode, target_norm_mode, draft_logits, ld_draft_logits,
+                          target_logits, ld_target_logits, norm_workspace, max_rows_per_forward, verify_ms_out, verify_streams_out,
+                          verify_ctx_out, max_iters_log, n_iters_out, passes_out, err_out, stream);
 }
 
 // ---- the width-w loop of sampling/multi.py in native code (reference speculative_sampling.py:1379-1716, strategy "iid")
@@ -781,6 +844,39 @@ extern "C" int sd_multi_adopt(const sd_multi_adopt_item *items, int width, const
 
 static inline int kv_planes(const sd_session *s) { return s->m->cfg.n_layers * 2 * s->m->cfg.n_kv_heads; }
 static inline int kv_row_bytes(const sd_session *s) { return s->m->cfg.head_dim * (s->kv_fp8 ? 1 : (int)esize(s->m->cfg.dtype)); }
+
+extern "C" int sd_session_copy_kv(const sd_session *src, const sd_kv_copy_item *items, int n_items, void *stream) {
+    SD_REQUIRE(src && items, "sd_session_copy_kv: null argument");
+    SD_REQUIRE(n_items >= 1 && n_items <= 16, "sd_session_copy_kv: n_items %d outside 1..16", n_items);
+    KvCopyTab t = {};
+    int n = 0, longest = 0;
+    for (int i = 0; i < n_items; ++i) {
+        const sd_kv_copy_item &it = items[i];
+        SD_REQUIRE(it.dst, "sd_session_copy_kv: item %d: null argument", i);
+        SD_REQUIRE(it.dst->m == src->m, "sd_session_copy_kv: item %d: a session of another model than the source's", i);
+        SD_REQUIRE(it.dst != src, "sd_session_copy_kv: item %d: source and destination are one session", i);
+        SD_REQUIRE(!it.dst->kv_fp8 == !src->kv_fp8, "sd_session_copy_kv: item %d: one arena is fp8 and the other is not", i);
+        SD_REQUIRE(it.lo >= 0 && it.hi >= it.lo && it.hi <= src->max_seq && it.hi <= it.dst->max_seq,
+                   "sd_session_copy_kv: item %d: positions [%d, %d) of arenas of %d (source) and %d positions", i, it.lo, it.hi,
+                   src->max_seq, it.dst->max_seq);
+        if (it.hi == it.lo) continue;
+        t.dst[n] = it.dst->kv; t.dst_max_seq[n] = it.dst->max_seq; t.lo[n] = it.lo; t.hi[n] = it.hi;
+        longest = std::max(longest, it.hi - it.lo);
+        ++n;
+    }
+    if (n == 0) return SD_OK;                                     // nothing to copy
+    const int planes = kv_planes(src), row_bytes = kv_row_bytes(src);
+    SD_REQUIRE(planes >= 1 && planes <= 65535, "sd_session_copy_kv: %d KV planes exceed a grid dimension", planes);
+    // a workgroup moves up to 16 KiB (four 16-byte accesses per lane); a shorter run is one chunk, rounded to whole vectors
+    const size_t run = (size_t)longest * row_bytes;
+    const int chunk = (int)std::min<size_t>(KV_COPY_CHUNK_MAX, (run + 15) / 16 * 16);
+    const size_t chunks = (run + chunk - 1) / chunk;
+    SD_REQUIRE(chunks <= 0x7fffffffu, "sd_session_copy_kv: a run of %zu bytes per plane is too long", run);
+    hipLaunchKernelGGL(session_copy_kv_kernel, dim3((unsigned)chunks, planes, n), dim3(KV_COPY_THREADS), 0, (hipStream_t)stream,
+                       src->kv, src->max_seq, row_bytes, chunk, t);
+    SD_LAUNCH_CHECK();
+    return SD_OK;
+}
 
 extern "C" size_t sd_spec_multi_block_bytes(int width, int gamma) {
     if (width < 1 || gamma < 1) return 0;

@@ -397,6 +397,15 @@ class Session:
     def rollback(self, end_pos: int) -> None:
         self.cache_len = min(self.cache_len, int(end_pos))
 
+    def copy_kv_from(self, src: "Session", lo: int, hi: int) -> None:
+        """KV positions [lo, hi) of every layer, K and V, and KV head from ``src``'s arena into this one (sd_session_copy_kv:
+        one launch, bytes as they are).  ``src`` is another session of the same model; the two arenas may hold different
+        numbers of positions.  fp8 arenas need equal scale tables.  No ``cache_len`` is read or set - the caller owns both."""
+        if self.kv_fp8 and src.kv_fp8 and not torch.equal(self.kv_scale, src.kv_scale):
+            raise ValueError("copy_kv_from: the two fp8 arenas have different scale tables")
+        item = _lib.SdKvCopyItem(self.handle, int(lo), int(hi))
+        check(lib.sd_session_copy_kv(src.handle, C.byref(item), 1, _stream()), "sd_session_copy_kv")
+
     def prefill_attn_launches(self) -> int:
         """attn_prefill_kernel / attn_prefill_blocked_kernel launches of this session so far (one per layer of a pass that takes
         the matrix-core prefill attention; a batched pass counts on its first session).  A host counter: the profile's attention class counts one

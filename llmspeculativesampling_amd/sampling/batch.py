@@ -154,6 +154,24 @@ def _queue_arguments(prefixes, max_len, seeds, slots):
     return [int(m) for m in max_len]
 
 
+def _shared_prefix_argument(prefixes, shared_prefix) -> int:
+    """speculative_sampling_queue_shared's check of ``shared_prefix`` (after _queue_arguments, before a model or the GPU is touched)."""
+    if isinstance(shared_prefix, bool) or not isinstance(shared_prefix, (int, np.integer)) or shared_prefix < 0:
+        raise ValueError(f"shared_prefix: a token count >= 0 is required, not {shared_prefix!r}")
+    P = int(shared_prefix)
+    shortest = min(pf.shape[1] for pf in prefixes)
+    if P > shortest:
+        raise ValueError(f"shared_prefix: {P} tokens, but the shortest prompt has {shortest}")
+    if P:
+        head = prefixes[0][0, :P].cpu()
+        for i, pf in enumerate(prefixes[1:], 1):
+            differ = (pf[0, :P].cpu() != head).nonzero()
+            if differ.numel():
+                raise ValueError(f"shared_prefix: prompt {i} differs from prompt 0 at position {int(differ[0])}: the first {P} tokens "
+                                 "of every prompt must be the same")
+    return P
+
+
 @torch.no_grad()
 def speculative_sampling_queue(prefixes: Sequence[torch.Tensor], approx_model, target_model, eos_token_id, pad_token_id,
                                max_len, gamma: int = 4, temperature: float = 1, top_k: int = 0, top_p: float = 0,
@@ -168,8 +186,39 @@ def speculative_sampling_queue(prefixes: Sequence[torch.Tensor], approx_model, t
     outputs in prompt order (and the ``details`` dicts of speculative_sampling_batch when ``details``).
     ``_timing`` receives "verify" entries as speculative_sampling_batch writes them, "iterations", "target_passes",
     "draft_passes", "extra_passes" (target passes that carried prompt rows only; "prefill_passes" of them ran while no
-    stream was active) and per prompt "admit_iter" / "finish_iter" (its first / last iteration)."""
+    stream was active), "prompt_rows" (target rows forwarded for prompts), "copied_rows" (0 here) and per prompt
+    "admit_iter" / "finish_iter" (its first / last iteration).  speculative_sampling_queue_shared is this call for prompts
+    that start with the same tokens."""
+    return _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max_len, gamma, temperature, top_k, top_p,
+                  random_seed, details, seeds, slots, prefill_chunk, _timing, 0)
+
+
+@torch.no_grad()
+def speculative_sampling_queue_shared(prefixes: Sequence[torch.Tensor], approx_model, target_model, eos_token_id, pad_token_id,
+                                      max_len, gamma: int = 4, temperature: float = 1, top_k: int = 0, top_p: float = 0,
+                                      random_seed: int = None, details: bool = False, seeds: Optional[Sequence[int]] = None,
+                                      slots: int = 8, prefill_chunk: int = 0, _timing: Optional[dict] = None,
+                                      shared_prefix: int = 0):
+    """speculative_sampling_queue with ``shared_prefix=P``: the first P tokens of every prompt are the same (a system prompt, a
+    few-shot header; P <= the shortest prompt, checked token by token before a model is touched).  Their K / V rows depend on
+    those tokens alone, so they go through each model once, into a donor pair of sessions, and an admitted prompt receives its
+    first min(P, L_i - 1) rows as a copy of the donors' (sd_session_copy_kv) and forwards only the rest; the last prompt token is
+    always fed as the first decode row.  The queue's contract holds unchanged - prompt i equals its speculative_sampling run -
+    for 16-bit models up to the rounding a different pass shape for the prefix rows gives, which is the caveat the queue has
+    anyway.  ``_timing``: "prompt_rows" includes the donor's rows, "copied_rows" is the number of KV rows copied per model
+    summed over the prompts, and the donor's prefill passes count in "target_passes", "draft_passes", "extra_passes" and
+    "prefill_passes", so a call compares with its ``shared_prefix=0`` twin.  With 0 (the default) there is no donor and the
+    call is speculative_sampling_queue's, bit for bit and pass for pass.  (A function of its own: the queue's parameter list
+    is pinned by its tests.)"""
+    return _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max_len, gamma, temperature, top_k, top_p,
+                  random_seed, details, seeds, slots, prefill_chunk, _timing, shared_prefix)
+
+
+def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max_len, gamma, temperature, top_k, top_p,
+           random_seed, details, seeds, slots, prefill_chunk, _timing, shared_prefix):
+    """The prompt queue behind both public entry points (their docstrings have the contract)."""
     budgets = _queue_arguments(prefixes, max_len, seeds, slots)
+    shared = _shared_prefix_argument(prefixes, shared_prefix)
     if isinstance(prefill_chunk, bool) or not isinstance(prefill_chunk, int) or prefill_chunk < 0:
         raise ValueError(f"prefill_chunk: a row count >= 0 is required, not {prefill_chunk!r}")
     if not 1 <= gamma <= 16:
@@ -215,21 +264,35 @@ def speculative_sampling_queue(prefixes: Sequence[torch.Tensor], approx_model, t
     v_ms = np.zeros(n_log, dtype=np.float32)
     v_n = np.zeros(n_log, dtype=np.int32)
     v_ctx = np.zeros(n_log, dtype=np.float32)
-    c_iters, c_err, passes = C.c_int(0), C.c_int(0), (C.c_int * 4)()
-    check(lib.sd_spec_queue_generate(slot_arr, S, cap, arr, N, prefill_chunk, gamma, float(temperature), int(top_k or 0),
-                                     float(top_p or 0.0), V, held[0][0]._probs.stride(0), int(eos_token_id),
-                                     int(random_seed or 0), r_const.data_ptr() if r_const is not None else None,
-                                     draft_m.norm_mode, target_m.norm_mode, d0.logits.data_ptr(), d0.logits.stride(0),
-                                     t0.logits.data_ptr(), t0.logits.stride(0), norm_ws.data_ptr(), per_pass,
-                                     v_ms.ctypes.data, v_n.ctypes.data, v_ctx.ctypes.data, n_log, C.byref(c_iters), passes,
-                                     C.byref(c_err), _stream()), "sd_spec_queue_generate")
+    c_iters, c_err, passes = C.c_int(0), C.c_int(0), (C.c_int * 6)()
+    args = (slot_arr, S, cap, arr, N, prefill_chunk, gamma, float(temperature), int(top_k or 0), float(top_p or 0.0), V,
+            held[0][0]._probs.stride(0), int(eos_token_id), int(random_seed or 0), r_const.data_ptr() if r_const is not None else None,
+            draft_m.norm_mode, target_m.norm_mode, d0.logits.data_ptr(), d0.logits.stride(0), t0.logits.data_ptr(),
+            t0.logits.stride(0), norm_ws.data_ptr(), per_pass, v_ms.ctypes.data, v_n.ctypes.data, v_ctx.ctypes.data, n_log,
+            C.byref(c_iters), passes, C.byref(c_err), _stream())
+    # the donors hold the shared rows a prompt can use: the longest prompt's last token is fed as a decode row like everyone's
+    rows = min(shared, max(lens) - 1)
+    donors, donor_passes = [None, None], [0, 0]                   # (draft, target) sessions and the passes of their prefill
+    if rows > 0:
+        head = tokens[:rows].to(dev)
+        donors = [draft_m.new_session(rows), target_m.new_session(rows)]
+        for side, ses in enumerate(donors):
+            if ses.kv_fp8 and not torch.equal(ses.kv_scale, held[0][side]._session.kv_scale):
+                raise ValueError("shared_prefix: the fp8 KV arenas of the donors and the slots have different scale tables")
+            batch_prefill([ses], [head], [rows])
+            donor_passes[side] = -(-rows // ses.max_rows)
+    # (without donors sd_spec_queue_generate_shared is sd_spec_queue_generate, which has no room for the two row counts)
+    check(lib.sd_spec_queue_generate_shared(*args, *[ses.handle if ses else None for ses in donors], rows),
+          "sd_spec_queue_generate_shared")
+    passes[4] += rows                                             # the donor's target rows are prompt rows too
     if c_err.value:
         raise RuntimeError("s")
     if _timing is not None:
         for i in range(min(c_iters.value, n_log)):
             _timing.setdefault("verify", []).append((_Ms(float(v_ms[i])), None, int(v_n[i]), float(v_ctx[i])))
-        _timing.update(iterations=c_iters.value, target_passes=passes[0], draft_passes=passes[1], extra_passes=passes[2],
-                       prefill_passes=passes[3], admit_iter=[it.admit_iter for it in arr],
+        _timing.update(iterations=c_iters.value, target_passes=passes[0] + donor_passes[1], draft_passes=passes[1] + donor_passes[0],
+                       extra_passes=passes[2] + donor_passes[1], prefill_passes=passes[3] + donor_passes[1],
+                       prompt_rows=passes[4], copied_rows=passes[5], admit_iter=[it.admit_iter for it in arr],
                        finish_iter=[it.finish_iter for it in arr])
     res = [lockstep_result(log, it.len, it.calls, eos_token_id, it.ori_eos_cnt, pf.device)
            for it, log, pf in zip(arr, logs, prefixes)]

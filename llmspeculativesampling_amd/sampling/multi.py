@@ -35,9 +35,9 @@ from ._loop_common import (LoopLog, accept_rates_f32_zero_q, cut_after_new_eos, 
 
 
 def _copy_positions(dst_ses, src_ses, lo: int, hi: int) -> None:
-    """KV rows [lo, hi) of every layer / head from one replica's arena to another's."""
+    """KV rows [lo, hi) of every layer / head from one replica's arena to another's (sd_session_copy_kv)."""
     if hi > lo:
-        dst_ses.kv[:, :, :, lo:hi].copy_(src_ses.kv[:, :, :, lo:hi])
+        dst_ses.copy_kv_from(src_ses, lo, hi)
 
 
 def _takes_native_loop(noise, verbose) -> bool:

@@ -4,13 +4,21 @@ pair bench.py uses (llama-68m -> llama-2-13b, random-init weights through synth.
 gamma 4, 8 slots).
 
     python tools/queue_bench.py [--workloads ragged,uniform --reps 5 --json-out profiles/queue_bench.json]
+    python tools/queue_bench.py --workloads shared --json-out profiles/queue_bench_shared_prefix.json
 
-Two workloads, EOS off (every prompt generates its max_len):
+Three decoding workloads, EOS off (every prompt generates its max_len):
   ragged   32 prompts with the lengths of harness.synthetic_prompts (bench.py --prompt-lens synthetic-c3), cut to what a
            slot's arenas hold, max_len alternating 32 / 128.  queue: one call, 8 slots.  batch: four calls of
            speculative_sampling_batch with 8 prompts each, in list order - each call runs until its slowest stream is done.
   uniform  8 prompts of 128 tokens, max_len 128: one queue call against one batch call.  The queue has nothing to admit
            after the start and must cost nothing: its median has to lie within the min-max spread of the batch reps.
+  shared   (--workloads shared) 32 prompts, each one fixed 256-token prefix followed by the first <= 256 tokens of a ragged
+           prompt, max_len alternating 32 / 128, 8 slots.  Both arms are speculative_sampling_queue_shared: shared_prefix=0 (every prompt forwards all
+           its rows) against shared_prefix=256 (the prefix goes through the models once, the prompts copy its K / V rows).
+           Per arm also the target rows forwarded for prompts.
+  copy     (--workloads copy) no decoding: sd_session_copy_kv alone at the target's KV shape, 256 and 512 rows to 1 and 8
+           destinations - device-event time per launch over 20 launches after 3 warm-up launches, and the bytes read plus
+           the bytes written over that time.
 Both arms run in this process, alternated rep by rep after one warm-up rep of each (which also loads every kernel); a rep is
 the whole call or calls, prefill included, between two device synchronisations on the host clock.  Per arm: tokens/s per rep
 and their median, iterations, passes over the target weights (verify passes plus prompt-only passes; for the batch arm the
@@ -30,9 +38,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from llmspeculativesampling_amd.config import load_config  # noqa: E402
 from llmspeculativesampling_amd.engine import SpecDecModel, MAX_PREFILL_ROWS  # noqa: E402
 from llmspeculativesampling_amd.harness import synthetic_prompts  # noqa: E402
-from llmspeculativesampling_amd.sampling import speculative_sampling_batch, speculative_sampling_queue  # noqa: E402
+from llmspeculativesampling_amd.sampling import speculative_sampling_batch, speculative_sampling_queue, speculative_sampling_queue_shared  # noqa: E402
 
 SLOTS, GAMMA = 8, 4
+SHARED = 256                                                      # tokens of the `shared` workload's common prefix
 
 
 def prefill_passes(lens):
@@ -50,6 +59,35 @@ def prefill_passes(lens):
             passes, rows, groups = passes + 1, 0, 0
         rows, groups = rows + n, groups + g
     return passes + (rows > 0)
+
+
+def copy_bench(model, rows_list=(256, 512), dst_counts=(1, 8), warmup=3, launches=20):
+    """sd_session_copy_kv alone: [{rows, destinations, us, bytes_moved, read_plus_write_GB_per_s}]."""
+    import ctypes as C
+    from llmspeculativesampling_amd._lib import lib, check, SdKvCopyItem
+    from llmspeculativesampling_amd.engine import _stream
+    cap = max(rows_list)
+    src = model.new_session(cap)
+    src.kv.normal_()
+    dsts = [model.new_session(cap) for _ in range(max(dst_counts))]
+    out = []
+    for rows in rows_list:
+        for n in dst_counts:
+            items = (SdKvCopyItem * n)()
+            for it, d in zip(items, dsts):
+                it.dst, it.lo, it.hi = d.handle, 0, rows
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            for i in range(warmup + launches):
+                if i == warmup:
+                    e0.record()
+                check(lib.sd_session_copy_kv(src.handle, items, n, _stream()), "sd_session_copy_kv")
+            e1.record()
+            torch.cuda.synchronize()
+            assert all(torch.equal(d.kv[:, :, :, :rows], src.kv[:, :, :, :rows]) for d in dsts[:n])
+            us = e0.elapsed_time(e1) * 1e3 / launches
+            moved = 2 * n * src.kv[:, :, :, :rows].numel() * src.kv.element_size()
+            out.append(dict(rows=rows, destinations=n, us=us, bytes_moved=moved, read_plus_write_GB_per_s=moved / us * 1e-3))
+    return out
 
 
 def main():
@@ -74,17 +112,25 @@ def main():
     if "uniform" in a.workloads:
         ps = [torch.from_numpy(np.random.default_rng(100 + i).integers(3, tcfg.vocab_size, size=(1, 128))).cuda() for i in range(8)]
         work["uniform"] = (ps, [128] * 8)
+    if "shared" in a.workloads:
+        head = torch.from_numpy(np.random.default_rng(77).integers(3, tcfg.vocab_size, size=(1, SHARED)))
+        ps = [torch.cat([head, p[:, :min(256, cut - SHARED)]], 1).cuda() for p in synthetic_prompts(100, tcfg.vocab_size, seed=5)[:32]]
+        work["shared"] = (ps, [32 if i % 2 == 0 else 128 for i in range(32)])
     out = {"config": {k: v for k, v in vars(a).items() if k != "json_out"}, "dtype": "bfloat16", "slots": SLOTS, "gamma": GAMMA,
            "workloads": {}}
+    if "copy" in a.workloads:
+        out["copy_kv"] = copy_bench(tm)
+        print(json.dumps({"copy_kv": out["copy_kv"]}), flush=True)
     for name, (prompts, budgets) in work.items():
         lens = [int(p.shape[1]) for p in prompts]
 
-        def queue(seed0):
+        def queue(seed0, **more):
             t = {}
-            outs = speculative_sampling_queue(prompts, dm, tm, -1, None, budgets, seeds=[seed0 + i for i in range(len(prompts))],
-                                              slots=SLOTS, _timing=t, **kw)
+            fn = speculative_sampling_queue_shared if more else speculative_sampling_queue
+            outs = fn(prompts, dm, tm, -1, None, budgets, seeds=[seed0 + i for i in range(len(prompts))], slots=SLOTS, _timing=t,
+                      **more, **kw)
             return outs, dict(iterations=t["iterations"], target_passes=t["target_passes"], extra_passes=t["extra_passes"],
-                              mean_streams=float(np.mean([v[2] for v in t["verify"]])))
+                              mean_streams=float(np.mean([v[2] for v in t["verify"]])), prompt_rows=t["prompt_rows"])
 
         def batch(seed0):
             outs, iters, passes, streams = [], 0, 0, []
@@ -100,6 +146,9 @@ def main():
             return outs, dict(iterations=iters, target_passes=passes, extra_passes=None, mean_streams=float(np.mean(streams)))
 
         arms = {"queue": queue, "batch": batch}
+        if name == "shared":
+            arms = {"shared_prefix_0": lambda seed0: queue(seed0, shared_prefix=0),
+                    f"shared_prefix_{SHARED}": lambda seed0: queue(seed0, shared_prefix=SHARED)}
         stats = {}
         for arm, fn in arms.items():                               # warm-up of every shape
             stats[arm] = fn(1000)[1]
@@ -116,8 +165,12 @@ def main():
                 rates[arm].append(sum(min(o.shape[1] - L, m) for o, L, m in zip(outs, lens, budgets)) / dt)
                 stats[arm] = st
         res = {arm: dict(stats[arm], tokens_per_s_reps=v, tokens_per_s_median=float(np.median(v))) for arm, v in rates.items()}
-        res["queue_over_batch_tokens_per_s"] = res["queue"]["tokens_per_s_median"] / res["batch"]["tokens_per_s_median"]
-        res["queue_median_within_batch_spread"] = bool(min(rates["batch"]) <= res["queue"]["tokens_per_s_median"] <= max(rates["batch"]))
+        if name == "shared":
+            res["shared_over_plain_tokens_per_s"] = res[f"shared_prefix_{SHARED}"]["tokens_per_s_median"] / \
+                res["shared_prefix_0"]["tokens_per_s_median"]
+        else:
+            res["queue_over_batch_tokens_per_s"] = res["queue"]["tokens_per_s_median"] / res["batch"]["tokens_per_s_median"]
+            res["queue_median_within_batch_spread"] = bool(min(rates["batch"]) <= res["queue"]["tokens_per_s_median"] <= max(rates["batch"]))
         res["prompt_lens"], res["max_len"] = lens, budgets
         out["workloads"][name] = res
         print(json.dumps({name: res}), flush=True)
