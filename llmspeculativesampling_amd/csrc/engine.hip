@@ -145,10 +145,10 @@ extern "C" int sd_pack_weight_bf16(const void *src, void *dst, int N, int K, voi
 #define SD_STREAM_MAX_ROWS 64                        // rows the streaming kernel's m-tile variants cover
 #define SD_ROWS_MAX 144                              // rows the balanced one-workgroup-per-CU kernel covers (9 m-tiles: a 128-token prompt + gamma rows)
 struct EnvTun {
-    int gemm_ntw = 4, gemm_units = -1, small_path = 1, small_split_bytes = 0, tiny_split_bytes = 24576, fuse_embed_qkv = 1, head_tiles = 1;
+    int gemm_ntw = 4, gemm_units = -1, small_path = 1, fuse_embed_qkv = 1;
     int attn_split_keys = 384, attn_keys_per_split = 256;
     int mm_mtw = 0, mm_s = 0, prefill_attn = 1, prefill_attn_block = 0, mm_slabs_min = 24;
-    int wide_qkv = 1, tp_one_slab = 1, gemm_rows = 1, cus = 0, fuse_attn_o = 1, ao_stamps = 0, ao_delay = 300, ao_gap = 100, norm_on_load = 2, rows_max = SD_ROWS_MAX;
+    int gemm_rows = 1, cus = 0, fuse_attn_o = 1, ao_stamps = 0, norm_on_load = 2, rows_max = SD_ROWS_MAX;
 };
 static EnvTun g_env;
 static void refresh_env() {
@@ -159,15 +159,10 @@ static void refresh_env() {
     // (llama-68m 94.9 -> 92.3 us, opt-125m 426-440 -> 417 us per draft step); 2: every seam a prologue incl. the head (slower);
     // 0: the per-op chain.  Rounds 2-4 measured the prologue route 75 % slower: that was a 254-VGPR compile of gemm_small
     g_env.small_path = geti("SD_SMALL_PATH", 1);
-    g_env.small_split_bytes = geti("SD_SMALL_SPLIT_BYTES", 0);
-    g_env.tiny_split_bytes = geti("SD_TINY_SPLIT_BYTES", 24576);   // k-slab size of <= 16-row GEMMs on matrices of <= 8 MB (0: the big-matrix policy)
     g_env.fuse_embed_qkv = geti("SD_FUSE_EMBED_QKV", 1);
-    g_env.head_tiles = geti("SD_HEAD_TILES", 1);
     g_env.attn_split_keys = geti("SD_ATTN_SPLIT_KEYS", 384);          // keys per workgroup above which a group's keys are split
     g_env.attn_keys_per_split = std::max(16, geti("SD_ATTN_KEYS_PER_SPLIT", 256));
     g_env.ao_stamps = geti("SD_AO_STAMPS", 0);
-    g_env.ao_delay = geti("SD_AO_DELAY", 300);        // 10 ns ticks the O workgroups hold their weight requests back (fused_kernels.h)
-    g_env.ao_gap = geti("SD_AO_GAP", 100);            // ... and pause after every 8 requests
     g_env.fuse_attn_o = geti("SD_FUSE_ATTN_O", 1);    // 0: attention and the O projection as two launches (A/B runs, bit-compare tests)
     g_env.norm_on_load = geti("SD_NORM_ON_LOAD", 2);  // 0: residual+norm launches stay; 1: attention -> MLP seam only; 2: both seams (A/B runs, compare tests)
     g_env.prefill_attn = geti("SD_PREFILL_ATTN", 1);  // 0: prefill passes keep attn_kernel's 8-row groups (A/B runs, compare tests)
@@ -177,8 +172,6 @@ static void refresh_env() {
     g_env.mm_s = geti("SD_MM_S", 0);                  // (sweeps) k-slabs of gemm_bf16_mm; 0 = planned
 
     g_env.gemm_rows = geti("SD_GEMM_ROWS", 1);        // 0: 17..64-row GEMMs stay on the streaming kernel (A/B runs, bit-compare tests)
-    g_env.wide_qkv = geti("SD_WIDE_QKV", 1);          // 0: a QKV projection with <= 128 n-tiles keeps one 4-wave workgroup per tile (A/B, compare tests)
-    g_env.tp_one_slab = geti("SD_TP_ONE_SLAB", 1);    // 0: a shard's O / down projection keeps its k-slabs + the fold launch in front of the all-reduce (A/B)
     g_env.rows_max = std::min(SD_ROWS_MAX, std::max(SD_STREAM_MAX_ROWS, geti("SD_GEMM_ROWS_MAX", SD_ROWS_MAX)));   // 65..this many rows take the balanced kernel, more gemm_bf16_mm
     if (!g_env.cus) {
         int dev = 0, n = 0;
@@ -202,6 +195,7 @@ static int gemm_ntw(int N, int M) {
     return 1;
 }
 
+#define TINY_SPLIT_BYTES 24576                       // weights a workgroup streams in a <= 16-row GEMM on a matrix of <= 8 MB
 static void gemm_split(int N, int K, int M, int *S_out, int *ks_per_out) {
     const int NTL = N / 16 / gemm_ntw(N, M), KS = K / 32;
     int max_s = KS / 8;
@@ -221,13 +215,13 @@ static void gemm_split(int N, int K, int M, int *S_out, int *ks_per_out) {
             const double cost = (wbytes + slab * c) / eff * (blocks < 768 ? 1.25 : 1.0);   // too few workgroups under-fill the load path
             if (cost < best) { best = cost; S = c; }
         }
-    } else if ((size_t)N * K * 2 <= ((size_t)8 << 20) && g_env.tiny_split_bytes > 0) {
+    } else if ((size_t)N * K * 2 <= ((size_t)8 << 20)) {
         // a matrix of a small model (the draft's O / down projection: 1.2 / 4.7 MB): its launch is latency, not bytes, and
         // every slab is another 16-byte load per column group in the consumer's fold - so few slabs, each workgroup streaming
-        // about tiny_split_bytes (24 KiB: down 12 -> 4 slabs, O 3 -> 1; on one box llama-68m / opt-125m steps of 91.5 / 415.4 us
+        // about TINY_SPLIT_BYTES (24 KiB: down 12 -> 4 slabs, O 3 -> 1; on one box llama-68m / opt-125m steps of 91.5 / 415.4 us
         // with the big-matrix policy, 87.3 / 387.6 at 24 KiB, 89.4 / 397.0 at 32, 90.2 / 402.5 at 48, 93.7 / 420.7 at 96 -
-        // tools/draft_step_bench.py SD_TINY_SPLIT_BYTES=...)
-        S = (int)((K * 32 + g_env.tiny_split_bytes / 2) / g_env.tiny_split_bytes);
+        // profiles/r04_draft_step_ab.txt)
+        S = (int)((K * 32 + TINY_SPLIT_BYTES / 2) / TINY_SPLIT_BYTES);
     } else if (NTL < 1024) {
         // fewest slabs that give >= 1024 workgroups, preferring a workgroup count that fills all 256 CUs evenly
         // (measured on MI355X: 7.5 workgroups per CU runs 10 % slower than 15 per CU, tools/gemm_bench.py)
@@ -279,7 +273,7 @@ static GemmRoute route_gemm(int N, int K, int M, int need) {
     GemmRoute r = {};
     const bool fused = need & GN_FUSED, x_tiled = !(need & (GN_GATHER | GN_ROWMAJOR));
     const int KS = K / 32, Mpad = (int)align_up(M, 16);
-    if ((need & GN_QKV) && g_env.wide_qkv && M <= 16 && x_tiled && N / 16 <= 128 && KS >= 128) {
+    if ((need & GN_QKV) && M <= 16 && x_tiled && N / 16 <= 128 && KS >= 128) {
         r.kind = GK_STREAM_W16;
         r.S = 1;
         r.ksp = KS;
@@ -984,11 +978,11 @@ static int launch_gemm(const GemmRoute &r, const void *W, const void *X, float *
     return SD_OK;
 }
 
-// X: [M][K] activations, W: [N][K] weights -> split-K slabs in s->part.  xtab: the lm_head's row gather (NULL: every row in
-// place); one_slab: GN_ONE_SLAB
+// X: [M][K] activations, W: [N][K] weights -> split-K slabs in s->part, cut the way `r` says (16-bit models; an fp32 model
+// has one kernel and no route).  xtab: the lm_head's row gather (NULL: every row in place - a route made without GN_GATHER)
 template <typename H = bf16_t>
-static int run_gemm(sd_session *s, const void *W, const void *X, int M, int N, int K, GemmOut *go, hipStream_t st,
-                    const RowTab *xtab = nullptr, bool one_slab = false) {
+static int run_gemm(sd_session *s, const GemmRoute &r, const void *W, const void *X, int M, int N, int K, GemmOut *go,
+                    hipStream_t st, const RowTab *xtab = nullptr) {
     const sd_model_config &c = s->m->cfg;
     ProfScope ps(s, PC_GEMM, st);
     if (!is16(c.dtype)) {
@@ -1000,11 +994,6 @@ static int run_gemm(sd_session *s, const void *W, const void *X, int M, int N, i
         go->stride_s = (size_t)M * N;
         return SD_OK;
     }
-    bool xmap_identity = true;
-    if (xtab)
-        for (int i = 0; i < M && xmap_identity; ++i) xmap_identity = xtab->xmap[i] == i;
-    if (xmap_identity) xtab = nullptr;                            // every row in place (a verify pass): no gather
-    const GemmRoute r = route_gemm(N, K, M, (xtab ? GN_GATHER : 0) | (one_slab ? GN_ONE_SLAB : 0));
     const int Mpad = (int)align_up(M, 16);
     SD_REQUIRE(r.kind != GK_NONE, "internal: no GEMM kernel for %d rows of %d x %d (past the session's row limits)", M, N, K);
     SD_REQUIRE((size_t)r.S * Mpad * N <= s->part_floats, "run_gemm: partial buffer too small");
@@ -1017,19 +1006,16 @@ static int run_gemm(sd_session *s, const void *W, const void *X, int M, int N, i
     return SD_OK;
 }
 
-// bf16 GEMM whose workgroups keep the whole k-range (SB = 1) and finish with a fused epilogue
+// bf16 GEMM whose workgroups keep the whole k-range (SB = 1) and finish with a fused epilogue: r is a GN_FUSED route
 // (eight waves per tile for a shard's gate/up - 448 n-tiles - measured slower: 5.94 against 5.86 ms per verify)
 template <int EPI, typename H = bf16_t>
-static int run_gemm_fused(sd_session *s, const void *W, const void *X, int M, int N, int K, const GemmEpiT<H> &e,
-                          hipStream_t st) {
+static int run_gemm_fused(sd_session *s, const GemmRoute &r, const void *W, const void *X, int M, int N, int K,
+                          const GemmEpiT<H> &e, hipStream_t st) {
     ProfScope ps(s, PC_GEMM, st);
-    const GemmRoute r = route_gemm(N, K, M, GN_FUSED | (EPI == EPI_QKV_ROPE || EPI == EPI_QKV_PLAIN ? GN_QKV : 0));
     SD_REQUIRE(r.kind != GK_NONE, "internal: no fused GEMM kernel for %d rows of %d x %d (past the session's row limits)", M, N, K);
     return launch_gemm<EPI, H>(r, W, X, nullptr, M, N, K, e, st);
 }
 
-// keys per workgroup above which a group's keys are cut over several workgroups (and merged by attn_combine_kernel)
-#define ATT_SPLIT_KEYS 384
 #define ATT_MAX_PARTS 64          // groups * splits the partial buffer is sized for
 // 160 KiB per workgroup less the kernel's static LDS (the split path's per-row max / denominator)
 #define ATT_LDS_MAX ((size_t)160 * 1024 - 512)
@@ -1114,6 +1100,24 @@ extern "C" int sd_prefill_attn_route(int head_dim, int n_heads, int n_rows, int 
     *kernel = route_prefill_attn(head_dim, n_heads, n_rows, (n_rows + ATT_TQ - 1) / ATT_TQ, s_max, block_keys, cus);
     return SD_OK;
 }
+// The route of one forward pass: which launches it makes and how each of them is cut.  All of it follows from (session, row
+// table, s_max, tunables), so plan_forward fills it once, before the layer loop, and the launch helpers read it - they
+// decide nothing themselves.  What does differ between layers (a layer's biases, l + 1 < L) stays in the loop.
+enum AttnKind { AK_KERNEL = 0, AK_OPROJ, AK_PREFILL };           // attn_kernel (+ combine) | fused attention + O | matrix cores
+struct FwdPlan {
+    bool small;                       // the small-model decode path (forward_small)
+    bool embed_qkv;                   // the embedding and the first pre-norm ride the layer-0 QKV launch
+    int attn;                         // AttnKind
+    PaPlan pa;                        // AK_PREFILL: kernel, keys per score tile, LDS ...
+    PaGroups pg;                      // ... and its 16-row groups
+    int s_max, nsplit, s_cap;         // AK_KERNEL: key splits and the keys one holds; AK_OPROJ: one split
+    size_t attn_lds;                  // ... and a workgroup's dynamic LDS (AK_KERNEL past ATT_LDS_MAX: launch_attn's capacity error)
+    bool seam_o, seam_d;              // norm on load may open at the attention -> MLP seam / the down -> next QKV seam
+    GemmRoute qkv, o, gu, down;       // the per-layer GEMMs of a 16-bit model (not of the small path, which cuts its own)
+    GemmRoute head;                   // the lm_head with its row gather (16-bit model, logit rows)
+    int rn_threads;                   // blockDim of residual_norm_kernel
+};
+
 template <typename T>
 static bool prefill_attn_ok(const sd_session *s, const RowTab &tab, int s_max) {
     if constexpr (sizeof(T) != 2) return false;
@@ -1142,13 +1146,9 @@ static void launch_attn_prefill_inst(const sd_model_config &c, const T *q, const
         hipLaunchKernelGGL((attn_prefill_kernel<T, D, KV8>), dim3(c.n_heads, pg.n), dim3(256), pl.lds, st, q, pg, layer, out,
                            c.n_heads, c.n_kv_heads, c.arch, 1.0f / sqrtf((float)D), pl.block);
 }
-template <typename T>
-static int launch_attn_prefill(sd_session *s, const T *q, const RowTab &tab, int layer, T *out, int s_max, hipStream_t st) {
-    const sd_model_config &c = s->m->cfg;
-    const PaPlan pl = plan_prefill_attn(c.head_dim, s_max, g_env.prefill_attn_block);
-    SD_REQUIRE(pl.kernel != 0, "internal: no prefill attention kernel for head_dim %d", c.head_dim);
-    // the table's groups are <= ATT_TQ consecutive rows of a stream: two neighbours of one stream make a 16-row group
-    PaGroups pg = {};
+// the table's groups are <= ATT_TQ consecutive rows of a stream: two neighbours of one stream make a 16-row group
+static void prefill_groups(const RowTab &tab, PaGroups &pg) {
+    pg = PaGroups{};
     for (int g = 0; g < tab.n_groups; ++g) {
         const int i = pg.n;
         const bool join = i > 0 && pg.nrows[i - 1] == ATT_TQ && tab.grp_stream[g] == tab.grp_stream[g - 1] &&
@@ -1159,13 +1159,19 @@ static int launch_attn_prefill(sd_session *s, const T *q, const RowTab &tab, int
         pg.kv_scale[i] = tab.kv_fp8 ? tab.kv_scale[tab.grp_stream[g]] : nullptr;
         ++pg.n;
     }
+}
+template <typename T>
+static int launch_attn_prefill(sd_session *s, const T *q, const RowTab &tab, const FwdPlan &fp, int layer, T *out, hipStream_t st) {
+    const sd_model_config &c = s->m->cfg;
+    const PaPlan &pl = fp.pa;
+    SD_REQUIRE(pl.kernel != 0, "internal: no prefill attention kernel for head_dim %d", c.head_dim);
     const bool d64 = c.head_dim == 64;
     if (tab.kv_fp8) {
-        if (d64) launch_attn_prefill_inst<T, 64, true>(c, q, pg, layer, out, pl, st);
-        else launch_attn_prefill_inst<T, 128, true>(c, q, pg, layer, out, pl, st);
+        if (d64) launch_attn_prefill_inst<T, 64, true>(c, q, fp.pg, layer, out, pl, st);
+        else launch_attn_prefill_inst<T, 128, true>(c, q, fp.pg, layer, out, pl, st);
     } else {
-        if (d64) launch_attn_prefill_inst<T, 64, false>(c, q, pg, layer, out, pl, st);
-        else launch_attn_prefill_inst<T, 128, false>(c, q, pg, layer, out, pl, st);
+        if (d64) launch_attn_prefill_inst<T, 64, false>(c, q, fp.pg, layer, out, pl, st);
+        else launch_attn_prefill_inst<T, 128, false>(c, q, fp.pg, layer, out, pl, st);
     }
     if (pl.kernel == 2) ++s->prefill_attn_blocked_launches;
     ++s->prefill_attn_launches;
@@ -1173,13 +1179,12 @@ static int launch_attn_prefill(sd_session *s, const T *q, const RowTab &tab, int
 }
 
 template <typename T, int D>
-static int launch_attn(sd_session *s, const T *q, const RowTab &tab, int layer, T *out, int s_max, hipStream_t st) {
+static int launch_attn(sd_session *s, const T *q, const RowTab &tab, const FwdPlan &fp, int layer, T *out, hipStream_t st) {
     const sd_model_config &c = s->m->cfg;
-    const size_t lds_max = ATT_LDS_MAX;
-    int nsplit, s_cap;
-    const size_t lds = attn_split_plan(D, s_max, tab.n_groups, &nsplit, &s_cap);
+    const size_t lds_max = ATT_LDS_MAX, lds = fp.attn_lds;
+    const int nsplit = fp.nsplit, s_cap = fp.s_cap;
     if (lds > lds_max) {
-        sd_set_error("attention: %d keys x %d row groups exceed the LDS score tile", s_max, tab.n_groups);
+        sd_set_error("attention: %d keys x %d row groups exceed the LDS score tile", fp.s_max, tab.n_groups);
         return SD_ERR_CAPACITY;
     }
     auto launch = [&](auto kv8, auto tree) -> int {
@@ -1208,12 +1213,22 @@ static int launch_attn(sd_session *s, const T *q, const RowTab &tab, int layer, 
                            (const float *)s->attn_part, tab, out, c.n_heads, nsplit);
     return SD_OK;
 }
-
+template <typename T>
+static int launch_attn_d(sd_session *s, const T *q, const RowTab &tab, const FwdPlan &fp, int layer, T *out, hipStream_t st) {
+    switch (s->m->cfg.head_dim) {
+        case 16: return launch_attn<T, 16>(s, q, tab, fp, layer, out, st);
+        case 32: return launch_attn<T, 32>(s, q, tab, fp, layer, out, st);
+        case 64: return launch_attn<T, 64>(s, q, tab, fp, layer, out, st);
+        default: return launch_attn<T, 128>(s, q, tab, fp, layer, out, st);
+    }
+}
 
 // Attention + O projection in one launch (fused_kernels.h) for <= 8 rows of one stream on a 16-bit model with
 // head_dim 128 and K = n_heads * 128 <= 5120: returns false when the shape does not qualify (the caller then takes the two
 // launches).  On success the O projection's single slab is in s->part.
 #define AO_LDS_MAX (80 * 1024)
+#define AO_DELAY_TICKS 300        // 10 ns ticks the O workgroups hold their weight requests back (fused_kernels.h) ...
+#define AO_GAP_TICKS 100          // ... and pause after every 8 requests
 static size_t attn_oproj_lds(int s_max) {
     constexpr int D = 128;
     const int s_cap = (int)align_up(s_max, 64);
@@ -1236,25 +1251,25 @@ static bool attn_oproj_ok(const sd_session *s, const RowTab &tab, int s_max) {
     return true;
 }
 template <typename T>
-static int launch_attn_oproj(sd_session *s, const T *q, const RowTab &tab, int layer, T *out, int s_max, const void *wo,
+static int launch_attn_oproj(sd_session *s, const T *q, const RowTab &tab, const FwdPlan &fp, int layer, T *out, const void *wo,
                              bool resid, hipStream_t st) {
     const sd_model_config &c = s->m->cfg;
-    const int s_cap = (int)align_up(s_max, 64);
-    const size_t lds = attn_oproj_lds(s_max);
+    const int s_cap = fp.s_cap;
+    const size_t lds = fp.attn_lds;
     static bool attr = false;
     if (!attr) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(attn_oproj_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   AO_LDS_MAX);
         attr = true;
     }
-    SD_REQUIRE(lds <= AO_LDS_MAX, "attn_oproj: %d keys exceed the launch's LDS budget", s_max);      // (attn_oproj_ok checked)
+    SD_REQUIRE(lds <= AO_LDS_MAX, "attn_oproj: %d keys exceed the launch's LDS budget", fp.s_max);      // (attn_oproj_ok checked)
     // arrivals counted so far, this launch's included; the epoch advances only once the launch is known to be enqueued (a
     // failed launch must not leave every later wait of the session one arrival short)
     const unsigned n_arrive = (unsigned)(c.n_heads * tab.n_groups);
     const unsigned want = s->ao_epoch + n_arrive + (unsigned)s->skew_now;
     hipLaunchKernelGGL((attn_oproj_kernel<T>), dim3(c.n_heads * tab.n_groups + (c.hidden / 16 + 1) / 2), dim3(512), lds, st, q, tab, layer, out, c.n_heads,
                        c.n_kv_heads, c.arch, 1.0f / sqrtf((float)c.head_dim), s_cap, (const u32x4 *)wo, s->part, tab.n_rows, c.hidden,
-                       q_dim(c), s->ao_ctr, want, g_env.ao_delay, g_env.ao_gap,
+                       q_dim(c), s->ao_ctr, want, AO_DELAY_TICKS, AO_GAP_TICKS,
                        g_env.ao_stamps ? s->ao_stamps : (long long *)nullptr,
                        (T *)s->x, (T *)s->h, resid ? s->ssq : (float *)nullptr, s->wait_status);
     SD_LAUNCH_CHECK();
@@ -1293,9 +1308,9 @@ static int launch_gemm_xn(sd_session *s, const void *W, const void *X, int M, in
 
 // The k-split GEMM (streaming kernel's split) finishing with the residual epilogue: rows -> s->x, s->h (un-normalised), s->ssq
 template <typename H>
-static int launch_gemm_fin(sd_session *s, const void *W, const void *X, int M, int N, int K, const void *bias, hipStream_t st) {
+static int launch_gemm_fin(sd_session *s, const GemmRoute &pl, const void *W, const void *X, int M, int N, int K, const void *bias,
+                           hipStream_t st) {
     ProfScope ps(s, PC_GEMM, st);
-    const GemmRoute pl = route_gemm(N, K, M, 0);
     SD_REQUIRE(pl.kind == GK_STREAM && M <= 16 && (size_t)pl.S * 16 * N <= s->part_floats, "k-split GEMM with residual epilogue: M=%d N=%d K=%d", M, N, K);
     GemmEpiT<H> e = {};
     e.bias = (const H *)bias; e.res_x = (H *)s->x; e.res_h = (H *)s->h; e.res_ssq = s->ssq;
@@ -1326,12 +1341,25 @@ static int head_finish(sd_session *s, const HeadReq *rq, HeadOut *ho, int S, siz
     return SD_OK;
 }
 
-// The lm_head over the (normalised, operand-layout) rows `hl`; xt (or NULL) maps logit row i to its row of hl.  Native
+// the route of a GEMM a pass runs once (an fp32 model has one kernel and no routes)
+static GemmRoute route_of(const sd_model_config &c, int N, int K, int M, int need) {
+    return is16(c.dtype) ? route_gemm(N, K, M, need) : GemmRoute{};
+}
+
+// A gather table whose first M rows are all in place (a verify pass: every row a logit row) is no gather for the 16-bit GEMMs
+static const RowTab *gather_tab(const sd_model_config &c, const RowTab *xt, int M) {
+    for (int i = 0; xt && i < M; ++i)
+        if (xt->xmap[i] != i || !is16(c.dtype)) return xt;
+    return nullptr;
+}
+
+// The lm_head over the (normalised, operand-layout) rows `hl`; xt (or NULL) maps logit row i to its row of hl; hr is its
+// route as a gathering GEMM (16-bit models).  Native
 // iteration: the head also leaves the maximum of every 16-column tile and clears the probability rows, so the
 // normalisation that follows needs no candidate pass over V (EPI_HEAD; whole k-range per workgroup).
 template <typename T>
-static int head_logits(sd_session *s, const T *hl, const RowTab *xt, int n_logits, float *logits_out, long ld_logits,
-                       const HeadReq *rq, HeadOut *ho, hipStream_t st) {
+static int head_logits(sd_session *s, const GemmRoute &hr, const T *hl, const RowTab *xt, int n_logits, float *logits_out,
+                       long ld_logits, const HeadReq *rq, HeadOut *ho, hipStream_t st) {
     using H16 = typename std::conditional<std::is_same<T, float>::value, bf16_t, T>::type;
     sd_model *m = s->m;
     const sd_model_config &c = m->cfg;
@@ -1339,7 +1367,6 @@ static int head_logits(sd_session *s, const T *hl, const RowTab *xt, int n_logit
     GemmOut go = {1, 0};                                         // (what the EPI_HEAD launch leaves: one slab)
     int rc;
     const bool zero_tab = rq && !rq->zero_rows && rq->zero_n > 0 && rq->zero_n == n_logits;
-    const GemmRoute hr = route_gemm(c.vocab, ED, n_logits, GN_GATHER);
     if (is16(c.dtype) && rq && rq->raw && (rq->zero_rows || zero_tab) && n_logits <= 16 && c.vocab % 16 == 0 &&
         hr.kind == GK_STREAM && hr.S == 1) {
         GemmEpiT<H16> e = {};
@@ -1352,17 +1379,18 @@ static int head_logits(sd_session *s, const T *hl, const RowTab *xt, int n_logit
             if ((rc = launch_gemm<EPI_HEAD, H16>(hr, m->w.lm_head, hl, s->part, n_logits, c.vocab, ED, e, st)) != SD_OK) return rc;
         }
         if (ho) ho->tile_max = s->tile_max;
-    } else if ((rc = run_gemm<H16>(s, m->w.lm_head, hl, n_logits, c.vocab, ED, &go, st, xt)) != SD_OK) {
-        return rc;
+    } else {
+        xt = gather_tab(c, xt, n_logits);
+        const GemmRoute r = xt ? hr : route_of(c, c.vocab, ED, n_logits, 0);
+        if ((rc = run_gemm<H16>(s, r, m->w.lm_head, hl, n_logits, c.vocab, ED, &go, st, xt)) != SD_OK) return rc;
     }
     return head_finish<T>(s, rq, ho, go.S, go.stride_s, n_logits, logits_out, ld_logits, st);
 }
 
-// ---- small-model decode path (small_kernels.h): 5 launches per layer + the head --------------------------------
+// whether a pass takes the small-model decode path (forward_small)
 static bool small_path_ok(const sd_session *s, const RowTab &tab) {
     const sd_model_config &c = s->m->cfg;
-    const int enabled = g_env.small_path;
-    if (!enabled || c.dtype != SD_BF16 || !c.fused_layout || tab.contig || s->tp) return false;
+    if (!g_env.small_path || c.dtype != SD_BF16 || !c.fused_layout || tab.contig || s->tp) return false;
     if (tab.n_rows > SMALL_MAX_ROWS || tab.n_logit_rows > SMALL_MAX_ROWS) return false;
     if (c.hidden > 2048 || c.hidden % 32 != 0 || embed_dim(c) != c.hidden) return false;
     if (c.arch == SD_ARCH_OPT && !c.opt_pre_ln) return false;          // post-LN keeps the stand-alone norm launches
@@ -1370,18 +1398,11 @@ static bool small_path_ok(const sd_session *s, const RowTab &tab) {
     return true;
 }
 
-// k-slabs of the small path's O / down GEMMs.  Default: the streaming GEMM's own policy (bit-identical slabs, what the
-// parity tests compare against); SD_SMALL_SPLIT_BYTES = b cuts them so that a workgroup streams about b bytes.
+// k-slabs of the small path's O / down GEMMs: the streaming GEMM's own policy (bit-identical slabs, what the parity tests
+// compare against), at most the 16 slabs s->spart holds
 static void small_split(int N, int K, int *S_out, int *ksp_out) {
-    const int bytes = g_env.small_split_bytes;
     const int KS = K / 32;
-    if (bytes <= 0) { gemm_split(N, K, 1, S_out, ksp_out); }
-    else {
-        int S = std::max(1, std::min(16, (int)((K * 32 + bytes / 2) / bytes)));
-        int ksp = (KS + S - 1) / S;
-        *S_out = (KS + ksp - 1) / ksp;
-        *ksp_out = ksp;
-    }
+    gemm_split(N, K, 1, S_out, ksp_out);
     if (*S_out > 16) { *ksp_out = (KS + 15) / 16; *S_out = (KS + *ksp_out - 1) / *ksp_out; }
 }
 
@@ -1396,17 +1417,114 @@ static int launch_small(sd_session *s, const void *W, const void *X, float *part
     return SD_OK;
 }
 
-static int launch_attn_bf16(sd_session *s, const bf16_t *q, const RowTab &tab, int layer, bf16_t *out, int s_max,
-                            hipStream_t st);
+// the QKV epilogue of layer l: rope / scale -> q buffer, K / V appended in place
+template <typename H>
+static GemmEpiT<H> qkv_epi(const sd_session *s, const RowTab &tab, int l) {
+    const sd_model *m = s->m;
+    const sd_model_config &c = m->cfg;
+    GemmEpiT<H> e = {};
+    e.out = (H *)s->qbuf; e.bias = (const H *)m->bqkv[l];
+    e.cos_t = (const H *)m->w.rope_cos; e.sin_t = (const H *)m->w.rope_sin;
+    e.Hq = c.n_heads; e.Hkv = c.n_kv_heads; e.D = c.head_dim; e.layer = l; e.tab = tab;
+    e.q_scale = 1.0f / sqrtf((float)c.head_dim);
+    return e;
+}
+// the gate/up (fc1) epilogue of layer l: SiLU * up / ReLU -> activation buffer
+template <typename H>
+static GemmEpiT<H> act_epi(const sd_session *s, int l) {
+    GemmEpiT<H> e = {};
+    e.out = (H *)s->act; e.bias = (const H *)s->m->bfc1[l]; e.n_out = s->m->cfg.inter;
+    return e;
+}
+// the embedding prologue of a layer-0 QKV launch: rows -> s->x, operand = their first pre-norm.  For the 1..4 new rows of a
+// small model (the draft's decode step) every workgroup normalises the rows itself while its weight tiles are in flight:
+// one launch instead of two, 6.7 us against 5.0 + 5.0 on llama-68m (tools/draft_step_bench.py)
+static SmallPro embed_pro(const sd_session *s, const FwdPlan &fp) {
+    const sd_model *m = s->m;
+    const sd_model_config &c = m->cfg;
+    const bool llama = c.arch == SD_ARCH_LLAMA;
+    SmallPro p = {};
+    p.embed = (const bf16_t *)m->w.embed; p.pos_embed = llama ? nullptr : (const bf16_t *)m->w.pos_embed;
+    p.pos_off = 2; p.vocab = c.vocab; p.r_out = (bf16_t *)s->x;       // OPT offset (modeling_opt.py:104)
+    p.nw = (const bf16_t *)m->n1w[0]; p.nb = (const bf16_t *)m->n1b[0]; p.eps = c.norm_eps; p.kind = llama ? NORM_RMS : NORM_LN;
+    p.H = c.hidden; p.rn_threads = fp.rn_threads;
+    return p;
+}
+// the QKV launch of the small-model kernel for layer e.layer, behind prologue p (rope on Llama)
+template <int PRO>
+static int launch_small_qkv(sd_session *s, const GemmEpi &e, const SmallPro &p, hipStream_t st) {
+    const sd_model_config &c = s->m->cfg;
+    const void *W = s->m->wqkv[e.layer];
+    const int M = e.tab.n_rows, N = qkv_cols(c), H = c.hidden;
+    return c.arch == SD_ARCH_LLAMA ? launch_small<PRO, EPI_QKV_ROPE>(s, W, nullptr, nullptr, M, N, H, 1, H / 32, e, p, st)
+                                   : launch_small<PRO, EPI_QKV_PLAIN>(s, W, nullptr, nullptr, M, N, H, 1, H / 32, e, p, st);
+}
 
-static int forward_small(sd_session *s, const RowTab &tab, int s_max, float *logits_out, long ld_logits, const HeadReq *rq,
+// residual rows x += fold(S slabs of src) + bias, and their norm (mode RES_*) -> operand rows s->h
+template <typename T>
+static int resid_norm(sd_session *s, const FwdPlan &fp, int M, T *x, const float *src, int S, size_t stride_s, const void *bias,
+                      const void *nw, const void *nb, int mode, hipStream_t st) {
+    const sd_model_config &c = s->m->cfg;
+    ProfScope ps(s, PC_NORM, st);
+    hipLaunchKernelGGL((residual_norm_kernel<T>), dim3(M), dim3(fp.rn_threads), 0, st, x, src, S, stride_s, c.hidden, (const T *)bias,
+                       (const T *)nw, (const T *)nb, c.norm_eps, c.arch == SD_ARCH_LLAMA ? NORM_RMS : NORM_LN, mode, (T *)s->h);
+    SD_LAUNCH_CHECK();
+    return SD_OK;
+}
+
+// Decide the route of a pass (FwdPlan)
+template <typename T>
+static void plan_forward(const sd_session *s, const RowTab &tab, int s_max, FwdPlan &fp) {
+    const sd_model_config &c = s->m->cfg;
+    const int H = c.hidden, M = tab.n_rows, ED = embed_dim(c);
+    const bool llama = c.arch == SD_ARCH_LLAMA, pre = llama || c.opt_pre_ln, fused = is16(c.dtype) && c.fused_layout != 0;
+    // residual+norm keeps the row in registers: 2 groups of 4 columns per thread (H <= 8192)
+    fp.rn_threads = (int)std::min<size_t>(1024, std::max<size_t>(64, align_up((H / 4 + RN_RG - 1) / RN_RG, 64)));
+    fp.s_max = s_max; fp.nsplit = fp.s_cap = 0; fp.attn_lds = 0; fp.pa = PaPlan{};         // (everything but pg, which only
+    fp.qkv = fp.o = fp.gu = fp.down = fp.head = GemmRoute{};                                // AK_PREFILL fills and reads)
+    fp.small = small_path_ok(s, tab);
+    fp.embed_qkv = fp.small || (c.dtype == SD_BF16 && g_env.fuse_embed_qkv && fused && pre && (llama || ED == H) && !tab.contig &&
+                                M <= SMALL_MAX_ROWS && H <= 2048 && H % 32 == 0);
+    if (!fp.small && attn_oproj_ok<T>(s, tab, s_max)) {
+        fp.attn = AK_OPROJ;
+        fp.nsplit = 1; fp.s_cap = (int)align_up(s_max, 64); fp.attn_lds = attn_oproj_lds(s_max);
+    } else if (!fp.small && prefill_attn_ok<T>(s, tab, s_max)) {
+        fp.attn = AK_PREFILL;
+        fp.pa = plan_prefill_attn(c.head_dim, s_max, g_env.prefill_attn_block);
+        prefill_groups(tab, fp.pg);
+    } else {
+        fp.attn = AK_KERNEL;
+        fp.attn_lds = attn_split_plan(c.head_dim, s_max, tab.n_groups, &fp.nsplit, &fp.s_cap);
+    }
+    // the residual add in the producer's epilogue, the norm in the consumer's operand load (no launch between)
+    const bool seams = pre && fused && norm_on_load_ok<T>(s, tab);
+    fp.seam_o = seams && fp.attn == AK_OPROJ;
+    fp.seam_d = seams && g_env.norm_on_load > 1;
+    if (!is16(c.dtype)) return;
+    if (!fp.small) {
+        // (a shard's O / down projection: one slab, which the all-reduce takes as it is)
+        const int row_par = s->tp ? GN_ONE_SLAB : 0;
+        fp.qkv = route_gemm(qkv_cols(c), H, M, fused ? GN_FUSED | GN_QKV : 0);
+        fp.o = route_gemm(H, q_dim(c), M, row_par);
+        fp.gu = route_gemm(gu_cols(c), H, M, fused ? GN_FUSED : 0);
+        fp.down = route_gemm(H, c.inter, M, row_par);
+    }
+    if (tab.n_logit_rows > 0) fp.head = route_gemm(c.vocab, ED, tab.n_logit_rows, GN_GATHER);
+}
+
+// launch_attn_d<bf16_t>, defined behind forward_impl: the kernels of the code object lie in the order in which this file
+// first instantiates them, and moving attn_kernel's bf16 instances in front of the small path's GEMMs made launches of
+// unchanged kernels 0.2-0.4 us slower (profiles/forward_refactor_ab.json)
+static int launch_attn_bf16(sd_session *s, const bf16_t *q, const RowTab &tab, const FwdPlan &fp, int layer, bf16_t *out, hipStream_t st);
+
+// ---- small-model decode path (small_kernels.h): 5 launches per layer + the head --------------------------------
+static int forward_small(sd_session *s, const RowTab &tab, const FwdPlan &fp, float *logits_out, long ld_logits, const HeadReq *rq,
                          HeadOut *ho, hipStream_t st) {
     sd_model *m = s->m;
     const sd_model_config &c = m->cfg;
-    const int H = c.hidden, D = c.head_dim, I = c.inter, L = c.n_layers, M = tab.n_rows, n_logits = tab.n_logit_rows;
+    const int H = c.hidden, I = c.inter, L = c.n_layers, M = tab.n_rows, n_logits = tab.n_logit_rows;
     const bool llama = c.arch == SD_ARCH_LLAMA;
     const int norm_kind = llama ? NORM_RMS : NORM_LN;
-    const int rn_threads = (int)std::min<size_t>(1024, std::max<size_t>(64, align_up((H / 4 + RN_RG - 1) / RN_RG, 64)));
     bf16_t *R[2] = {(bf16_t *)s->x, (bf16_t *)s->x2};
     bf16_t *qb = (bf16_t *)s->qbuf, *at = (bf16_t *)s->attn, *ac = (bf16_t *)s->act;
     int cur = 0;                                                   // R[cur] holds the residual stream
@@ -1414,6 +1532,10 @@ static int forward_small(sd_session *s, const RowTab &tab, int s_max, float *log
     // SD_SMALL_PATH=1: the two norm launches of a layer become prologues of QKV / gate-up; O, down and the head keep the
     // per-op chain's kernels.  =2: every seam a prologue and gemm_small for O / down (the round-2 route, kept for A/B)
     const bool all_pro = g_env.small_path >= 2;
+    // the epilogue descriptors are built once per pass (3 KB each, and this is the draft step's host thread): a layer changes
+    // its bias and its number
+    GemmEpi qe = qkv_epi<bf16_t>(s, tab, 0), ae = act_epi<bf16_t>(s, 0);
+    const GemmEpi no_epi = {};
     int S_o, ksp_o, S_d, ksp_d;
     small_split(H, q_dim(c), &S_o, &ksp_o);
     small_split(H, I, &S_d, &ksp_d);
@@ -1424,81 +1546,54 @@ static int forward_small(sd_session *s, const RowTab &tab, int s_max, float *log
         p.slab = s->spart; p.S = S; p.stride_s = (size_t)16 * H; p.bias = bias;
         p.r_in = R[cur]; p.r_out = write_r ? R[cur ^ 1] : nullptr;
         p.nw = (const bf16_t *)nw; p.nb = (const bf16_t *)nb; p.eps = c.norm_eps; p.kind = norm_kind; p.H = H;
-        p.rn_threads = rn_threads;
+        p.rn_threads = fp.rn_threads;
         return p;
     };
-
     for (int l = 0; l < L; ++l) {
         // ---- QKV: prologue = embedding (layer 0) or previous layer's down slabs + residual, then input norm
-        {
-            GemmEpi e = {};
-            e.out = qb; e.bias = (const bf16_t *)m->bqkv[l];
-            e.cos_t = (const bf16_t *)m->w.rope_cos; e.sin_t = (const bf16_t *)m->w.rope_sin;
-            e.Hq = c.n_heads; e.Hkv = c.n_kv_heads; e.D = D; e.layer = l; e.tab = tab;
-            e.q_scale = 1.0f / sqrtf((float)D);
-            if (l == 0) {
-                SmallPro p = {};
-                p.embed = (const bf16_t *)m->w.embed; p.pos_embed = llama ? nullptr : (const bf16_t *)m->w.pos_embed;
-                p.pos_off = 2; p.vocab = c.vocab; p.r_out = R[cur];
-                p.nw = (const bf16_t *)m->n1w[0]; p.nb = (const bf16_t *)m->n1b[0]; p.eps = c.norm_eps; p.kind = norm_kind;
-                p.H = H; p.rn_threads = rn_threads;
-                rc = llama ? launch_small<PRO_EMBED, EPI_QKV_ROPE>(s, m->wqkv[l], nullptr, nullptr, M, qkv_cols(c), H, 1, H / 32, e, p, st)
-                           : launch_small<PRO_EMBED, EPI_QKV_PLAIN>(s, m->wqkv[l], nullptr, nullptr, M, qkv_cols(c), H, 1, H / 32, e, p, st);
-            } else {
-                const SmallPro p = resid_pro(S_d, (const bf16_t *)m->bfc2[l - 1], m->n1w[l], m->n1b[l], true);
-                rc = llama ? launch_small<PRO_RESID, EPI_QKV_ROPE>(s, m->wqkv[l], nullptr, nullptr, M, qkv_cols(c), H, 1, H / 32, e, p, st)
-                           : launch_small<PRO_RESID, EPI_QKV_PLAIN>(s, m->wqkv[l], nullptr, nullptr, M, qkv_cols(c), H, 1, H / 32, e, p, st);
-                cur ^= 1;
-            }
-            if (rc != SD_OK) return rc;
+        qe.bias = (const bf16_t *)m->bqkv[l]; qe.layer = l;
+        if (l == 0) {
+            rc = launch_small_qkv<PRO_EMBED>(s, qe, embed_pro(s, fp), st);
+        } else {
+            rc = launch_small_qkv<PRO_RESID>(s, qe, resid_pro(S_d, (const bf16_t *)m->bfc2[l - 1], m->n1w[l], m->n1b[l], true), st);
+            cur ^= 1;
         }
+        if (rc != SD_OK) return rc;
         // ---- attention over the arena
         {
             ProfScope ps(s, PC_ATTN, st);
-            if ((rc = launch_attn_bf16(s, qb, tab, l, at, s_max, st)) != SD_OK) return rc;
+            if ((rc = launch_attn_bf16(s, qb, tab, fp, l, at, st)) != SD_OK) return rc;
             SD_LAUNCH_CHECK();
         }
+        // the slabs of O / down: gemm_small (SD_SMALL_PATH=2) or the streaming kernel, which leaves the same slabs - [S][16][H],
+        // the same k-split, the same sums - and runs 0.1-0.9 us faster than gemm_small<PRO_TILED> on these shapes
+        auto slab_gemm = [&](const void *W, const bf16_t *X, int K, int S, int ksp) -> int {
+            if (all_pro) return launch_small<PRO_TILED, EPI_PART>(s, W, X, s->spart, M, H, K, S, ksp, no_epi, SmallPro{}, st);
+            ProfScope ps(s, PC_GEMM, st);
+            const int rc2 = dispatch_gemm_bf16<EPI_PART, bf16_t>(W, X, s->spart, M, 16, H, K, S, ksp, no_epi, st);
+            SD_LAUNCH_CHECK();
+            return rc2;
+        };
         // ---- O projection -> slabs
-        {
-            GemmEpi e = {};
-            SmallPro p = {};
-            // (the streaming kernel leaves the same slabs: [S][16][H], the same k-split, the same sums - and runs 0.1-0.9 us
-            //  faster than gemm_small<PRO_TILED> on these shapes)
-            if (all_pro) rc = launch_small<PRO_TILED, EPI_PART>(s, m->wo[l], at, s->spart, M, H, q_dim(c), S_o, ksp_o, e, p, st);
-            else { ProfScope ps(s, PC_GEMM, st); rc = dispatch_gemm_bf16<EPI_PART, bf16_t>(m->wo[l], at, s->spart, M, 16, H, q_dim(c), S_o, ksp_o, e, st); SD_LAUNCH_CHECK(); }
-            if (rc != SD_OK) return rc;
-        }
+        if ((rc = slab_gemm(m->wo[l], at, q_dim(c), S_o, ksp_o)) != SD_OK) return rc;
         // ---- gate/up (fc1): prologue = O slabs + residual + post-attention norm; epilogue = SiLU * up / ReLU
-        {
-            GemmEpi e = {};
-            e.out = ac; e.bias = (const bf16_t *)m->bfc1[l]; e.n_out = I;
-            const SmallPro p = resid_pro(S_o, (const bf16_t *)m->bo[l], m->n2w[l], m->n2b[l], true);
-            rc = llama ? launch_small<PRO_RESID, EPI_ACT_SILU>(s, m->wgu[l], nullptr, nullptr, M, gu_cols(c), H, 1, H / 32, e, p, st)
-                       : launch_small<PRO_RESID, EPI_ACT_RELU>(s, m->wgu[l], nullptr, nullptr, M, gu_cols(c), H, 1, H / 32, e, p, st);
-            if (rc != SD_OK) return rc;
-            cur ^= 1;
-        }
+        ae.bias = (const bf16_t *)m->bfc1[l];
+        const SmallPro p = resid_pro(S_o, (const bf16_t *)m->bo[l], m->n2w[l], m->n2b[l], true);
+        rc = llama ? launch_small<PRO_RESID, EPI_ACT_SILU>(s, m->wgu[l], nullptr, nullptr, M, gu_cols(c), H, 1, H / 32, ae, p, st)
+                   : launch_small<PRO_RESID, EPI_ACT_RELU>(s, m->wgu[l], nullptr, nullptr, M, gu_cols(c), H, 1, H / 32, ae, p, st);
+        if (rc != SD_OK) return rc;
+        cur ^= 1;
         // ---- down projection (fc2) -> slabs
-        {
-            GemmEpi e = {};
-            SmallPro p = {};
-            if (all_pro) rc = launch_small<PRO_TILED, EPI_PART>(s, m->wdown[l], ac, s->spart, M, H, I, S_d, ksp_d, e, p, st);
-            else { ProfScope ps(s, PC_GEMM, st); rc = dispatch_gemm_bf16<EPI_PART, bf16_t>(m->wdown[l], ac, s->spart, M, 16, H, I, S_d, ksp_d, e, st); SD_LAUNCH_CHECK(); }
-            if (rc != SD_OK) return rc;
-        }
+        if ((rc = slab_gemm(m->wdown[l], ac, I, S_d, ksp_d)) != SD_OK) return rc;
     }
     if (n_logits > 0 && !all_pro) {
         // ---- head: the final residual + norm keeps its launch.  As a prologue of the lm_head every one of its 2000-3142
         // workgroups folds the slabs and normalises the rows for itself: 18.5 us against 4.4 + 9.6 on llama-68m, 31.4 against
         // 4.3 + 14.2 on opt-125m (rocprofv3, profiles/r04_small_path_*.txt)
-        {
-            ProfScope ps(s, PC_NORM, st);
-            hipLaunchKernelGGL((residual_norm_kernel<bf16_t>), dim3(M), dim3(rn_threads), 0, st, R[cur], (const float *)s->spart, S_d,
-                               (size_t)16 * H, H, (const bf16_t *)m->bfc2[L - 1], (const bf16_t *)m->w.final_norm_w,
-                               (const bf16_t *)m->w.final_norm_b, c.norm_eps, norm_kind, (int)RES_PRE, (bf16_t *)s->h);
-            SD_LAUNCH_CHECK();
-        }
-        return head_logits<bf16_t>(s, (const bf16_t *)s->h, &tab, n_logits, logits_out, ld_logits, rq, ho, st);
+        if ((rc = resid_norm<bf16_t>(s, fp, M, R[cur], s->spart, S_d, (size_t)16 * H, m->bfc2[L - 1], m->w.final_norm_w, m->w.final_norm_b,
+                                     RES_PRE, st)) != SD_OK)
+            return rc;
+        return head_logits<bf16_t>(s, fp.head, (const bf16_t *)s->h, &tab, n_logits, logits_out, ld_logits, rq, ho, st);
     }
     if (n_logits > 0) {
         // ---- head (SD_SMALL_PATH=2): prologue = last down slabs + residual + final norm on the rows that need logits
@@ -1519,7 +1614,6 @@ static int forward_small(sd_session *s, const RowTab &tab, int s_max, float *log
     return SD_OK;
 }
 
-
 template <typename T>
 static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logits_out, long ld_logits, const HeadReq *rq,
                         HeadOut *ho, hipStream_t st) {
@@ -1528,229 +1622,147 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
     const int n_new = tab.n_rows, n_logits = tab.n_logit_rows;
     sd_model *m = s->m;
     const sd_model_config &c = m->cfg;
-    if constexpr (std::is_same<T, bf16_t>::value) {
-        if (small_path_ok(s, tab)) return forward_small(s, tab, s_max, logits_out, ld_logits, rq, ho, st);
-    }
+    FwdPlan fp;
+    plan_forward<T>(s, tab, s_max, fp);
+    if (fp.small) return forward_small(s, tab, fp, logits_out, ld_logits, rq, ho, st);
     const int H = c.hidden, D = c.head_dim, I = c.inter, L = c.n_layers, ED = embed_dim(c);
-    const bool llama = c.arch == SD_ARCH_LLAMA;
-    const int norm_kind = llama ? NORM_RMS : NORM_LN;
-    const bool pre = llama || c.opt_pre_ln;
-    const bool fused = is16(c.dtype) && c.fused_layout != 0;
+    const bool llama = c.arch == SD_ARCH_LLAMA, pre = llama || c.opt_pre_ln, fused = is16(c.dtype) && c.fused_layout != 0;
+    const bool plain_embed = llama || ED == H;                             // no input projection
+    const int norm_kind = llama ? NORM_RMS : NORM_LN, pos_off = 2;           // OPT offset (modeling_opt.py:104)
+    const T *pos_embed = llama ? (const T *)nullptr : (const T *)m->w.pos_embed;
     T *x = (T *)s->x, *h = (T *)s->h, *qb = (T *)s->qbuf, *at = (T *)s->attn, *ac = (T *)s->act, *eb = (T *)s->ebuf;
     const size_t norm_lds = (size_t)(H + 32) * sizeof(float);
-    const int pos_off = 2;                                                   // OPT offset (modeling_opt.py:104)
-    // residual+norm keeps the row in registers: 2 groups of 4 columns per thread (H <= 8192)
-    const int rn_threads = (int)std::min<size_t>(1024, std::max<size_t>(64, align_up((H / 4 + RN_RG - 1) / RN_RG, 64)));
     GemmOut go;
     int rc;
 
-    // ---- 1..4 new rows of a small model (the draft's decode step): embedding + first pre-norm are the PROLOGUE of the
-    // layer-0 QKV GEMM (every workgroup normalises the <= 4 rows itself while its weight tiles are in flight): one
-    // launch instead of two, 6.7 us against 5.0 + 5.0 on llama-68m (tools/draft_step_bench.py)
-    bool qkv0_done = false;
-    if constexpr (std::is_same<T, bf16_t>::value) {
-        if (g_env.fuse_embed_qkv && fused && pre && (llama || ED == H) && !tab.contig && n_new <= SMALL_MAX_ROWS && H <= 2048 &&
-            H % 32 == 0) {
-            GemmEpi e = {};
-            e.out = (bf16_t *)qb; e.bias = (const bf16_t *)m->bqkv[0];
-            e.cos_t = (const bf16_t *)m->w.rope_cos; e.sin_t = (const bf16_t *)m->w.rope_sin;
-            e.Hq = c.n_heads; e.Hkv = c.n_kv_heads; e.D = D; e.layer = 0; e.tab = tab;
-            e.q_scale = 1.0f / sqrtf((float)D);
-            SmallPro p = {};
-            p.embed = (const bf16_t *)m->w.embed; p.pos_embed = llama ? nullptr : (const bf16_t *)m->w.pos_embed;
-            p.pos_off = pos_off; p.vocab = c.vocab; p.r_out = (bf16_t *)x;
-            p.nw = (const bf16_t *)m->n1w[0]; p.nb = (const bf16_t *)m->n1b[0]; p.eps = c.norm_eps; p.kind = norm_kind; p.H = H;
-            rc = llama ? launch_small<PRO_EMBED, EPI_QKV_ROPE>(s, m->wqkv[0], nullptr, nullptr, n_new, qkv_cols(c), H, 1, H / 32, e, p, st)
-                       : launch_small<PRO_EMBED, EPI_QKV_PLAIN>(s, m->wqkv[0], nullptr, nullptr, n_new, qkv_cols(c), H, 1, H / 32, e, p, st);
-            if (rc != SD_OK) return rc;
-            qkv0_done = true;
-        }
-    }
-    // ---- embeddings (+ the first pre-norm in the same launch when there is no input projection)
-    if (qkv0_done) {
-    } else if ((llama || ED == H) && pre) {
+    // ---- embeddings -> residual rows x, first pre-norm -> operand rows h (one launch when there is no input projection),
+    // unless both are the prologue of the layer-0 QKV launch below
+    if (!fp.embed_qkv && plain_embed && pre) {
         ProfScope ps(s, PC_EMBED, st);
-        hipLaunchKernelGGL((embed_norm_kernel<T>), dim3(n_new), dim3(256), norm_lds, st, tab, (const T *)m->w.embed, H,
-                           llama ? (const T *)nullptr : (const T *)m->w.pos_embed, pos_off, x, (const T *)m->n1w[0],
-                           (const T *)m->n1b[0], c.norm_eps, norm_kind, h, c.vocab);
+        hipLaunchKernelGGL((embed_norm_kernel<T>), dim3(n_new), dim3(256), norm_lds, st, tab, (const T *)m->w.embed, H, pos_embed,
+                           pos_off, x, (const T *)m->n1w[0], (const T *)m->n1b[0], c.norm_eps, norm_kind, h, c.vocab);
         SD_LAUNCH_CHECK();
-    } else {
-        if (llama || ED == H) {
+    } else if (!fp.embed_qkv) {
+        if (plain_embed) {
             ProfScope ps(s, PC_EMBED, st);
-            hipLaunchKernelGGL((embed_kernel<T>), dim3(n_new), dim3(256), 0, st, tab, (const T *)m->w.embed, H,
-                               llama ? (const T *)nullptr : (const T *)m->w.pos_embed, pos_off, x, 0, c.vocab);
+            hipLaunchKernelGGL((embed_kernel<T>), dim3(n_new), dim3(256), 0, st, tab, (const T *)m->w.embed, H, pos_embed, pos_off,
+                               x, 0, c.vocab);
             SD_LAUNCH_CHECK();
-        } else {
+        } else {                                                  // OPT project_in
             {
                 ProfScope ps(s, PC_EMBED, st);
                 hipLaunchKernelGGL((embed_kernel<T>), dim3(n_new), dim3(256), 0, st, tab, (const T *)m->w.embed, ED,
                                    (const T *)nullptr, 0, eb, 1, c.vocab);
                 SD_LAUNCH_CHECK();
             }
-            if ((rc = run_gemm<H16>(s, m->w.project_in, eb, n_new, H, ED, &go, st)) != SD_OK) return rc;
+            if ((rc = run_gemm<H16>(s, route_of(c, H, ED, n_new, 0), m->w.project_in, eb, n_new, H, ED, &go, st)) != SD_OK) return rc;
             ProfScope ps(s, PC_EMBED, st);
             hipLaunchKernelGGL((reduce_addpos_kernel<T>), dim3(n_new), dim3(256), 0, st, s->part, go.S, go.stride_s, H,
                                (const T *)m->w.pos_embed, tab, pos_off, x);
             SD_LAUNCH_CHECK();
         }
-        // ---- first pre-norm
-        if (pre) {
-            ProfScope ps(s, PC_NORM, st);
+        ProfScope ps(s, PC_NORM, st);                             // ---- first pre-norm
+        if (pre)
             hipLaunchKernelGGL((norm_kernel<T>), dim3(n_new), dim3(256), norm_lds, st, x, H, (const T *)m->n1w[0],
                                (const T *)m->n1b[0], c.norm_eps, norm_kind, h);
-            SD_LAUNCH_CHECK();
-        } else {
-            ProfScope ps(s, PC_NORM, st);
+        else
             hipLaunchKernelGGL((to_operand_kernel<T>), dim3(n_new), dim3(256), 0, st, (const T *)x, H, h);
-            SD_LAUNCH_CHECK();
-        }
+        SD_LAUNCH_CHECK();
     }
-
-    bool xn_d = false;                                                // layer l - 1's down projection left un-normalised rows + partials
     for (int l = 0; l < L; ++l) {
-        // qkv projection -> rope / scale -> q buffer + in-place KV append (fused into the GEMM's epilogue with the fused
+        // a seam opens where the producer has no bias; the last layer keeps its residual+norm launch (the final norm feeds the head)
+        const bool xn_q = fp.seam_d && l > 0 && !m->bfc2[l - 1];        // layer l - 1's down projection left un-normalised rows
+        const bool xn_o = fp.seam_o && !m->bo[l];
+        const bool xn_d = fp.seam_d && l + 1 < L && !m->bfc2[l];
+        // ---- QKV projection -> rope / scale -> q buffer + in-place KV append (fused into the GEMM's epilogue with the fused
         // weight layout, else slabs for the stand-alone epilogue)
-        if (l == 0 && qkv0_done) {
-        } else if (xn_d) {
-            if constexpr (!std::is_same<T, float>::value) {
-                GemmEpiT<H16> e = {};
-                e.out = (H16 *)qb; e.bias = (const H16 *)m->bqkv[l];
-                e.cos_t = (const H16 *)m->w.rope_cos; e.sin_t = (const H16 *)m->w.rope_sin;
-                e.Hq = c.n_heads; e.Hkv = c.n_kv_heads; e.D = D; e.layer = l; e.tab = tab;
-                e.q_scale = 1.0f / sqrtf((float)D);
-                if ((rc = launch_gemm_xn<EPI_QKV_ROPE, H16>(s, m->wqkv[l], h, n_new, qkv_cols(c), H, m->n1w[l], c.norm_eps, e, st)) != SD_OK)
-                    return rc;
-            }
+        if (l == 0 && fp.embed_qkv) {
+            if ((rc = launch_small_qkv<PRO_EMBED>(s, qkv_epi<bf16_t>(s, tab, 0), embed_pro(s, fp), st)) != SD_OK) return rc;
+        } else if (xn_q) {
+            rc = launch_gemm_xn<EPI_QKV_ROPE, H16>(s, m->wqkv[l], h, n_new, qkv_cols(c), H, m->n1w[l], c.norm_eps, qkv_epi<H16>(s, tab, l), st);
+            if (rc != SD_OK) return rc;
         } else if (fused) {
-            GemmEpiT<H16> e = {};
-            e.out = (H16 *)qb; e.bias = (const H16 *)m->bqkv[l];
-            e.cos_t = (const H16 *)m->w.rope_cos; e.sin_t = (const H16 *)m->w.rope_sin;
-            e.Hq = c.n_heads; e.Hkv = c.n_kv_heads; e.D = D; e.layer = l; e.tab = tab;
-            e.q_scale = 1.0f / sqrtf((float)D);
-            rc = llama ? run_gemm_fused<EPI_QKV_ROPE, H16>(s, m->wqkv[l], h, n_new, qkv_cols(c), H, e, st)
-                       : run_gemm_fused<EPI_QKV_PLAIN, H16>(s, m->wqkv[l], h, n_new, qkv_cols(c), H, e, st);
+            const GemmEpiT<H16> e = qkv_epi<H16>(s, tab, l);
+            rc = llama ? run_gemm_fused<EPI_QKV_ROPE, H16>(s, fp.qkv, m->wqkv[l], h, n_new, qkv_cols(c), H, e, st)
+                       : run_gemm_fused<EPI_QKV_PLAIN, H16>(s, fp.qkv, m->wqkv[l], h, n_new, qkv_cols(c), H, e, st);
             if (rc != SD_OK) return rc;
         } else {
-            if ((rc = run_gemm<H16>(s, m->wqkv[l], h, n_new, qkv_cols(c), H, &go, st)) != SD_OK) return rc;
+            if ((rc = run_gemm<H16>(s, fp.qkv, m->wqkv[l], h, n_new, qkv_cols(c), H, &go, st)) != SD_OK) return rc;
             ProfScope ps(s, PC_QKV, st);
             hipLaunchKernelGGL((qkv_epilogue_kernel<T>), dim3(n_new, c.n_heads + 2 * c.n_kv_heads),
                                dim3(std::max(D / 2, 64)), 0, st, s->part, go.S, go.stride_s, qkv_cols(c),
                                (const T *)m->bqkv[l], (const T *)m->w.rope_cos, (const T *)m->w.rope_sin, c.arch,
-                               1.0f / sqrtf((float)D), c.n_heads, c.n_kv_heads, D, tab, l, qb, fused ? 1 : 0);
+                               1.0f / sqrtf((float)D), c.n_heads, c.n_kv_heads, D, tab, l, qb, 0);
             SD_LAUNCH_CHECK();
         }
-        bool o_done = false, xn_o = false, attn_done = false;
-        if constexpr (!std::is_same<T, float>::value) {
-            if (attn_oproj_ok<T>(s, tab, s_max)) {
-                // the residual add in the O projection's epilogue, the norm in gate/up's operand load (no launch between)
-                xn_o = pre && fused && norm_on_load_ok<T>(s, tab) && !m->bo[l];
-                ProfScope ps(s, PC_ATTN, st);
-                if ((rc = launch_attn_oproj<T>(s, qb, tab, l, at, s_max, m->wo[l], xn_o, st)) != SD_OK) return rc;
-                SD_LAUNCH_CHECK();
-                go.S = 1;
-                go.stride_s = (size_t)16 * H;
-                o_done = true;
-            }
-        }
-        if constexpr (!std::is_same<T, float>::value) {
-            if (!o_done && prefill_attn_ok<T>(s, tab, s_max)) {
-                ProfScope ps(s, PC_ATTN, st);
-                if ((rc = launch_attn_prefill<T>(s, qb, tab, l, at, s_max, st)) != SD_OK) return rc;
-                SD_LAUNCH_CHECK();
-                attn_done = true;
-            }
-        }
-        if (!o_done && !attn_done) {
+        // ---- attention over the arena (AK_OPROJ: and the O projection, its single slab left in s->part)
+        {
             ProfScope ps(s, PC_ATTN, st);
-            switch (D) {
-                case 16: rc = launch_attn<T, 16>(s, qb, tab, l, at, s_max, st); break;
-                case 32: rc = launch_attn<T, 32>(s, qb, tab, l, at, s_max, st); break;
-                case 64: rc = launch_attn<T, 64>(s, qb, tab, l, at, s_max, st); break;
-                default: rc = launch_attn<T, 128>(s, qb, tab, l, at, s_max, st); break;
+            if constexpr (!std::is_same<T, float>::value) {            // (the fp32 instantiation has neither kernel)
+                if (fp.attn == AK_OPROJ) rc = launch_attn_oproj<T>(s, qb, tab, fp, l, at, m->wo[l], xn_o, st);
+                else if (fp.attn == AK_PREFILL) rc = launch_attn_prefill<T>(s, qb, tab, fp, l, at, st);
             }
+            if (fp.attn == AK_KERNEL) rc = launch_attn_d<T>(s, qb, tab, fp, l, at, st);
             if (rc != SD_OK) return rc;
             SD_LAUNCH_CHECK();
         }
-        // output projection + residual (+ norm feeding the MLP)
-        if (!o_done && (rc = run_gemm<H16>(s, m->wo[l], at, n_new, H, q_dim(c), &go, st, nullptr, s->tp && g_env.tp_one_slab)) != SD_OK) return rc;
+        // ---- output projection + residual (+ norm feeding the MLP)
+        if (fp.attn == AK_OPROJ) go = GemmOut{1, (size_t)16 * H};
+        else if ((rc = run_gemm<H16>(s, fp.o, m->wo[l], at, n_new, H, q_dim(c), &go, st)) != SD_OK) return rc;
         const float *osrc = s->part;
         if ((rc = tp_reduce(s, &go, &osrc, n_new, H, st)) != SD_OK) return rc;
-        if (!xn_o) {
-            ProfScope ps(s, PC_NORM, st);
-            const int mode = pre ? RES_PRE : RES_POST;
-            const T *nw = pre ? (const T *)m->n2w[l] : (const T *)m->n1w[l];
-            const T *nb = pre ? (const T *)m->n2b[l] : (const T *)m->n1b[l];
-            hipLaunchKernelGGL((residual_norm_kernel<T>), dim3(n_new), dim3(rn_threads), 0, st, x, osrc, go.S,
-                               go.stride_s, H, (const T *)m->bo[l], nw, nb, c.norm_eps, norm_kind, mode, h);
-            SD_LAUNCH_CHECK();
-        }
-        // MLP
-        if constexpr (!std::is_same<T, float>::value) {
-            if (xn_o) {
-                GemmEpiT<H16> e = {};
-                e.out = (H16 *)ac; e.n_out = I;
-                if ((rc = launch_gemm_xn<EPI_ACT_SILU, H16>(s, m->wgu[l], h, n_new, gu_cols(c), H, m->n2w[l], c.norm_eps, e, st)) != SD_OK)
-                    return rc;
-            }
-        }
+        if (!xn_o && (rc = resid_norm<T>(s, fp, n_new, x, osrc, go.S, go.stride_s, m->bo[l], pre ? m->n2w[l] : m->n1w[l],
+                                         pre ? m->n2b[l] : m->n1b[l], pre ? RES_PRE : RES_POST, st)) != SD_OK)
+            return rc;
+        // ---- gate/up (fc1) -> SiLU * up / ReLU -> activation buffer
         if (xn_o) {
+            rc = launch_gemm_xn<EPI_ACT_SILU, H16>(s, m->wgu[l], h, n_new, gu_cols(c), H, m->n2w[l], c.norm_eps, act_epi<H16>(s, l), st);
+            if (rc != SD_OK) return rc;
         } else if (fused) {
-            GemmEpiT<H16> e = {};
-            e.out = (H16 *)ac; e.bias = (const H16 *)m->bfc1[l]; e.n_out = I;
-            rc = llama ? run_gemm_fused<EPI_ACT_SILU, H16>(s, m->wgu[l], h, n_new, gu_cols(c), H, e, st)
-                       : run_gemm_fused<EPI_ACT_RELU, H16>(s, m->wgu[l], h, n_new, gu_cols(c), H, e, st);
+            const GemmEpiT<H16> e = act_epi<H16>(s, l);
+            rc = llama ? run_gemm_fused<EPI_ACT_SILU, H16>(s, fp.gu, m->wgu[l], h, n_new, gu_cols(c), H, e, st)
+                       : run_gemm_fused<EPI_ACT_RELU, H16>(s, fp.gu, m->wgu[l], h, n_new, gu_cols(c), H, e, st);
             if (rc != SD_OK) return rc;
         } else {
-            if ((rc = run_gemm<H16>(s, m->wgu[l], h, n_new, gu_cols(c), H, &go, st)) != SD_OK) return rc;
+            if ((rc = run_gemm<H16>(s, fp.gu, m->wgu[l], h, n_new, gu_cols(c), H, &go, st)) != SD_OK) return rc;
             ProfScope ps(s, PC_ACT, st);
             hipLaunchKernelGGL((act_kernel<T>), dim3((I + 255) / 256, n_new), dim3(256), 0, st, s->part, go.S,
-                               go.stride_s, I, gu_cols(c), c.arch, (const T *)m->bfc1[l], ac, fused ? 1 : 0);
+                               go.stride_s, I, gu_cols(c), c.arch, (const T *)m->bfc1[l], ac, 0);
             SD_LAUNCH_CHECK();
         }
-        // down projection: with the norm-on-load seam its last k-slab's workgroups add the residual and the next layer's QKV
-        // normalises on load (no residual+norm launch); the last layer keeps the launch (the final norm feeds the head)
-        xn_d = false;
-        if constexpr (!std::is_same<T, float>::value) {
-            xn_d = g_env.norm_on_load > 1 && pre && fused && l + 1 < L && norm_on_load_ok<T>(s, tab) && !m->bfc2[l];
-            if (xn_d && (rc = launch_gemm_fin<H16>(s, m->wdown[l], ac, n_new, H, I, nullptr, st)) != SD_OK) return rc;
-        }
-        if (xn_d) continue;
-        if ((rc = run_gemm<H16>(s, m->wdown[l], ac, n_new, H, I, &go, st, nullptr, s->tp && g_env.tp_one_slab)) != SD_OK) return rc;
-        const float *dsrc = s->part;
-        if ((rc = tp_reduce(s, &go, &dsrc, n_new, H, st)) != SD_OK) return rc;
-        {
-            ProfScope ps(s, PC_NORM, st);
-            int mode;
-            const T *nw = nullptr, *nb = nullptr;
-            if (pre) {
-                if (l + 1 < L) { mode = RES_PRE; nw = (const T *)m->n1w[l + 1]; nb = (const T *)m->n1b[l + 1]; }
-                else if (m->w.final_norm_w) { mode = RES_PRE; nw = (const T *)m->w.final_norm_w; nb = (const T *)m->w.final_norm_b; }
-                else mode = RES_NONE;
-            } else {
-                mode = RES_POST; nw = (const T *)m->n2w[l]; nb = (const T *)m->n2b[l];
-            }
-            hipLaunchKernelGGL((residual_norm_kernel<T>), dim3(n_new), dim3(rn_threads), 0, st, x, dsrc, go.S,
-                               go.stride_s, H, (const T *)m->bfc2[l], nw, nb, c.norm_eps, norm_kind, mode, h);
-            SD_LAUNCH_CHECK();
+        // ---- down projection (fc2) + residual (+ the next norm).  With the norm-on-load seam its last k-slab's workgroups add
+        // the residual and the next layer's QKV normalises on load (no residual+norm launch)
+        if (xn_d) {
+            if ((rc = launch_gemm_fin<H16>(s, fp.down, m->wdown[l], ac, n_new, H, I, nullptr, st)) != SD_OK) return rc;
+        } else {
+            if ((rc = run_gemm<H16>(s, fp.down, m->wdown[l], ac, n_new, H, I, &go, st)) != SD_OK) return rc;
+            const float *dsrc = s->part;
+            if ((rc = tp_reduce(s, &go, &dsrc, n_new, H, st)) != SD_OK) return rc;
+            int mode = RES_NONE;
+            const void *nw = nullptr, *nb = nullptr;
+            if (!pre) { mode = RES_POST; nw = m->n2w[l]; nb = m->n2b[l]; }
+            else if (l + 1 < L) { mode = RES_PRE; nw = m->n1w[l + 1]; nb = m->n1b[l + 1]; }
+            else if (m->w.final_norm_w) { mode = RES_PRE; nw = m->w.final_norm_w; nb = m->w.final_norm_b; }
+            if ((rc = resid_norm<T>(s, fp, n_new, x, dsrc, go.S, go.stride_s, m->bfc2[l], nw, nb, mode, st)) != SD_OK) return rc;
         }
     }
 
-    if (n_logits > 0) {
-        // only the rows tab.xmap lists feed the head (the last rows of each stream)
-        const T *hl = h;
-        const RowTab *xt = &tab;
-        if (ED != H) {                                          // OPT project_out (modeling_opt.py:744-745)
-            if ((rc = run_gemm<H16>(s, m->w.project_out, hl, n_logits, ED, H, &go, st, xt)) != SD_OK) return rc;
-            xt = nullptr;
-            ProfScope ps(s, PC_LOGITS, st);
-            hipLaunchKernelGGL((reduce_rows_kernel<T>), dim3((ED + 255) / 256, n_logits), dim3(256), 0, st, s->part,
-                               go.S, go.stride_s, ED, eb);
-            SD_LAUNCH_CHECK();
-            hl = eb;
-        }
-        return head_logits<T>(s, hl, xt, n_logits, logits_out, ld_logits, rq, ho, st);
+    if (n_logits == 0) return SD_OK;
+    // only the rows tab.xmap lists feed the head (the last rows of each stream)
+    const T *hl = h;
+    const RowTab *xt = &tab;
+    if (ED != H) {                                              // OPT project_out (modeling_opt.py:744-745)
+        xt = gather_tab(c, xt, n_logits);
+        const GemmRoute r = route_of(c, ED, H, n_logits, xt ? GN_GATHER : 0);
+        if ((rc = run_gemm<H16>(s, r, m->w.project_out, hl, n_logits, ED, H, &go, st, xt)) != SD_OK) return rc;
+        ProfScope ps(s, PC_LOGITS, st);
+        hipLaunchKernelGGL((reduce_rows_kernel<T>), dim3((ED + 255) / 256, n_logits), dim3(256), 0, st, s->part, go.S, go.stride_s,
+                           ED, eb);
+        SD_LAUNCH_CHECK();
+        hl = eb;
+        xt = nullptr;
     }
-    return SD_OK;
+    return head_logits<T>(s, fp.head, hl, xt, n_logits, logits_out, ld_logits, rq, ho, st);
 }
 
 // fill the attention groups and the lm_head row map of a table whose rows are already laid out stream by stream
@@ -1792,14 +1804,17 @@ static void finish_table(RowTab &tab) {
     }
 }
 
-static int launch_attn_bf16(sd_session *s, const bf16_t *q, const RowTab &tab, int layer, bf16_t *out, int s_max,
-                            hipStream_t st) {
-    switch (s->m->cfg.head_dim) {
-        case 16: return launch_attn<bf16_t, 16>(s, q, tab, layer, out, s_max, st);
-        case 32: return launch_attn<bf16_t, 32>(s, q, tab, layer, out, s_max, st);
-        case 64: return launch_attn<bf16_t, 64>(s, q, tab, layer, out, s_max, st);
-        default: return launch_attn<bf16_t, 128>(s, q, tab, layer, out, s_max, st);
-    }
+static int launch_attn_bf16(sd_session *s, const bf16_t *q, const RowTab &tab, const FwdPlan &fp, int layer, bf16_t *out, hipStream_t st) {
+    return launch_attn_d<bf16_t>(s, q, tab, fp, layer, out, st);
+}
+
+// stream i of a table: the session's arena and the stream's token buffer
+static void bind_stream(RowTab &tab, int i, const sd_session *s, const int32_t *tokens) {
+    tab.tok_base[i] = tokens;
+    tab.kv_base[i] = s->kv;
+    tab.max_seq[i] = s->max_seq;
+    tab.kv_fp8 = s->kv_fp8;
+    tab.kv_scale[i] = s->kv_scale;
 }
 
 static int run_forward(sd_session *s, const RowTab &tab, int s_max, float *logits_out, long ld_logits, const HeadReq *rq,
@@ -1845,11 +1860,7 @@ static int session_forward(sd_session *s, const int32_t *tokens, int n_new, int 
     tab.n_rows = n_new;
     tab.n_streams = 1;
     tab.n_logit_rows = n_logits;
-    tab.tok_base[0] = tokens - pos0;            // indexed by absolute position, only ever read at pos0 .. pos0+n_new-1
-    tab.kv_base[0] = s->kv;
-    tab.max_seq[0] = s->max_seq;
-    tab.kv_fp8 = s->kv_fp8;
-    tab.kv_scale[0] = s->kv_scale;
+    bind_stream(tab, 0, s, tokens - pos0);      // indexed by absolute position, only ever read at pos0 .. pos0+n_new-1
     if (n_new > SD_MAX_ROWS) {                      // prefill chunk: positions are implicit
         tab.contig = 1;
         tab.pos0 = pos0;
@@ -1885,11 +1896,7 @@ extern "C" int sd_session_forward_tree(sd_session *s, const int32_t *tokens, con
     tab.n_logit_rows = n;
     tab.tree = 1;
     tab.tree_base = base_len;
-    tab.kv_base[0] = s->kv;
-    tab.max_seq[0] = s->max_seq;
-    tab.kv_fp8 = s->kv_fp8;
-    tab.kv_scale[0] = s->kv_scale;
-    tab.tok_base[0] = tokens;                    // tree rows: the token of node i is tokens[i] (tab_tok)
+    bind_stream(tab, 0, s, tokens);              // tree rows: the token of node i is tokens[i] (tab_tok)
     for (int i = 0; i < n; ++i) {
         SD_REQUIRE(positions[i] >= 0 && positions[i] < s->m->cfg.max_pos, "sd_session_forward_tree: position %d out of range", positions[i]);
         SD_REQUIRE((masks[i] >> i) & 1ull, "sd_session_forward_tree: node %d must see itself", i);
@@ -1987,11 +1994,7 @@ static int batch_forward(const sd_batch_item *items, int n_items, float *logits_
             return SD_ERR_CAPACITY;
         }
         SD_REQUIRE(it.session->kv_fp8 == s0->kv_fp8, "sd_batch_forward: item %d: KV arenas of different dtypes", i);
-        tab.tok_base[i] = it.seq;
-        tab.kv_base[i] = it.session->kv;
-        tab.max_seq[i] = it.session->max_seq;
-        tab.kv_fp8 = it.session->kv_fp8;
-        tab.kv_scale[i] = it.session->kv_scale;
+        bind_stream(tab, i, it.session, it.seq);
         for (int r = 0; r < it.n_new; ++r) {
             tab.row_pos[rows + r] = it.pos0 + r;
             tab.row_stream[rows + r] = (unsigned char)i;
@@ -2041,11 +2044,7 @@ extern "C" int sd_batch_prefill(const sd_batch_item *items, int n_items, void *s
                          it.session->max_seq);
             return SD_ERR_CAPACITY;
         }
-        tab.tok_base[i] = it.seq;
-        tab.kv_base[i] = it.session->kv;
-        tab.max_seq[i] = it.session->max_seq;
-        tab.kv_fp8 = it.session->kv_fp8;
-        tab.kv_scale[i] = it.session->kv_scale;
+        bind_stream(tab, i, it.session, it.seq);
         tab.seg_row0[i] = rows;
         tab.seg_pos0[i] = it.pos0;
         rows += it.n_new;

@@ -98,7 +98,7 @@ __global__ __launch_bounds__(512, 2) void attn_oproj_kernel(const T *__restrict_
     const int ks0 = min(KS, wv * per), ks1 = min(KS, ks0 + per), nk = ks1 - ks0, dlast = max(nk - 1, 0);
     const u32x4 *wp = Wo + ((size_t)ntg * KS + min(ks0, KS - 1)) * 64 + lane;
     // Pacing of the weight requests (10 ns ticks): a hold-back before the first request and a pause after every 8 (defaults
-    // 3 us / 1 us, SD_AO_DELAY / SD_AO_GAP).  Measured with the stamps (tools/ao_stamps.py, 13b layer, 5 rows x 195 keys,
+    // 3 us / 1 us: AO_DELAY_TICKS / AO_GAP_TICKS in engine.hip).  Measured with the stamps (tools/ao_stamps.py, 13b layer, 5 rows x 195 keys,
     // cold caches, profiles/r03_attn_oproj_stamps.txt): requested at once the 52 MB land in 6.5-7.5 us and every
     // attention workgroup arrives at 10.6-15 us instead of ~8 - its K / V loads queue behind the stream; held back 3.5 us,
     // half of the attention workgroups arrive at 9.4-10 us (undisturbed) and the other half at 13-14.7 us, the weights at

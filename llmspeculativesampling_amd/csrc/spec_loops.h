@@ -105,8 +105,7 @@ static int feed_rows(sd_session *ses, const int32_t *seq, int from, int upto, in
 
 // EPI_HEAD's tile maxima serve the top-k candidate search only (1 <= k <= 64, positive temperature, 16 | V >= 4096)
 static bool head_tiles_ok(int top_k, float temperature, int V, long ld) {
-    return top_k >= 1 && top_k <= 64 && temperature > 0.0f && V % 16 == 0 && V >= 4096 && V <= 65536 && ld % 4 == 0 &&
-           g_env.head_tiles;
+    return top_k >= 1 && top_k <= 64 && temperature > 0.0f && V % 16 == 0 && V >= 4096 && V <= 65536 && ld % 4 == 0;
 }
 
 // ---- one whole speculative iteration, enqueued natively ---------------------------------------
@@ -145,13 +144,12 @@ extern "C" int sd_spec_iteration(sd_spec *sp, int L, int draft_len, int target_l
     if (sp->timing) { SD_HIP_CHECK(hipEventRecord(sp->ev[1], st)); SD_HIP_CHECK(hipEventRecord(sp->ev[2], st)); }
     // the target rows' candidate lists (behind the CandRows of the workspace) let the residual / bonus sample skip its
     // passes over V; they exist when all gamma + 1 rows of this iteration are normalised here
-    static const int sparse_on = getenv("SD_SPARSE_RESAMPLE") ? atoi(getenv("SD_SPARSE_RESAMPLE")) : 1;
     void *lists = nullptr;
     // ---- target: every uncached row in one pass (the whole prompt on the first call), logits for the last gamma+1
     {
         const int upto = L + g;
         const int rows = std::min(upto - target_len, g + 1);
-        if (sparse_on && sp->norm_ws && rows == g + 1) lists = (char *)sp->norm_ws + sd_norm_candrow_bytes(g + 1);
+        if (sp->norm_ws && rows == g + 1) lists = (char *)sp->norm_ws + sd_norm_candrow_bytes(g + 1);
         float *p_rows = sp->p_hist + (size_t)(upto - rows) * sp->ld;
         rq.zero_rows = tiles_ok ? p_rows : nullptr;
         if ((rc = feed_rows(sp->target, sp->seq, target_len, upto, rows, sp->target_logits, sp->ld_tl, &rq, &ho, stream)) != SD_OK)
