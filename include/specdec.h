@@ -339,6 +339,24 @@ int sd_model_max_pass_rows(const sd_model *m);
  * GEMM kernels read: 1 KiB tiles [N/16][K/32][lane 0..63][8 bf16], lane = 16*(k/8 % 4) + n % 16. */
 int sd_pack_weight_bf16(const void *w_rowmajor, void *w_packed, int N, int K, void *stream);
 
+/* Lossless 12-bit records of a bf16 matrix that is already in sd_pack_weight_bf16's layout: per
+ * 1 KiB tile 768 bytes of codes (sign, mantissa, a 4-bit exponent code relative to the tile's window of 15 binades) and a
+ * 16-byte side record (the window's base and up to six "escapes", elements below the window, with their true exponents).
+ * The single-stream decode / verify passes of a bf16 Llama model (<= 8 rows, the norm-on-load route) stream them instead
+ * of the bf16 tiles, 23.4 % fewer bytes, and decode them in registers to the same bits.
+ * sd_w12_bytes: sizes of the two arrays.  codes must be 128-byte aligned, meta 16-byte aligned.
+ * sd_pack_weight_w12: packs; *status_dev (a DEVICE int, cleared and written on `stream`) becomes 1 when some tile has more
+ *   than six escapes - the matrix is then not packable, the two arrays mean nothing and the caller keeps bf16 - else 0.
+ * sd_unpack_weight_w12: records -> the tiled bf16 layout (the format's executable definition; tests).
+ * sd_model_set_w12: registers the records of layer `layer`'s matrix `which` with a bf16 model (NULL, NULL: unregisters).
+ *   The bf16 copy stays in use for every other pass; the caller keeps both alive.  Not while a forward is in flight.
+ * sd_session_w12_launches: GEMM launches of this session so far that streamed records (a host integer, for tests). */
+enum { SD_W12_QKV = 0, SD_W12_GATE_UP = 1, SD_W12_DOWN = 2 };
+int sd_w12_bytes(int N, int K, size_t *codes_bytes, size_t *meta_bytes);
+int sd_pack_weight_w12(const void *w_tiled, void *codes, void *meta, int N, int K, int *status_dev, void *stream);
+int sd_unpack_weight_w12(const void *codes, const void *meta, void *w_tiled, int N, int K, void *stream);
+int sd_model_set_w12(sd_model *m, int which, int layer, const void *codes, const void *meta);
+
 /* Row-major bf16 activations [M][K] (K % 32 == 0) -> the GEMM operand layout the engine keeps them in between
  * kernels: 16-row tiles [ceil(M/16)][K/32][lane 0..63][8 bf16], lane = 16*(k/8 % 4) + m % 16, so that a wave's MFMA
  * fragment is one contiguous 1 KiB read.  x_tiled must hold roundup(M,16) * K elements. */
@@ -374,6 +392,7 @@ int sd_session_set_kv_fp8(sd_session *s, const float *scales);
  * the count alone.  A batched pass counts on its first session.  A host integer: no device work, no
  * synchronisation. */
 int sd_session_prefill_attn_launches(const sd_session *s);
+int sd_session_w12_launches(const sd_session *s);
 /* The matrix-core prefill attention has two kernels: attn_prefill_kernel keeps a row group's whole score tile in LDS and
  * runs while that fits (2048 keys at head_dim 128, 2176 at 64); past it - by default where sd_prefill_attn_route says so, and
  * at any context when SD_PREFILL_ATTN_BLOCK=K (K > 0, rounded up to a multiple of 64) is set - attn_prefill_blocked_kernel

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("SD_LIBSPECDEC") or os.path.join(_HERE, "libspecdec.so
 
 SD_OK, SD_ERR_INVALID, SD_ERR_NORM_LOGITS, SD_ERR_PROB, SD_ERR_HIP, SD_ERR_CAPACITY = 0, -1, -2, -3, -4, -5
 SD_F32, SD_BF16, SD_F16 = 0, 1, 2
+SD_W12_QKV, SD_W12_GATE_UP, SD_W12_DOWN = 0, 1, 2          # matrices sd_model_set_w12 takes 12-bit records for
 SD_NORM_ROUND_BF16, SD_NORM_ROUND_F16, SD_NORM_DT_BF16, SD_NORM_DT_F16 = 1, 2, 16, 32
 N_PROFILE_CLASSES = 8
 PROFILE_CLASS_NAMES = ["gemm", "attention", "norm_residual", "qkv_rope_append", "activation", "embed",
@@ -142,6 +143,11 @@ SYMBOLS = [
     ("sd_model_max_rows", _I, [_VP]),
     ("sd_model_max_pass_rows", _I, [_VP]),
     ("sd_pack_weight_bf16", _I, [_VP, _VP, _I, _I, _VP]),
+    ("sd_w12_bytes", _I, [_I, _I, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    ("sd_pack_weight_w12", _I, [_VP, _VP, _VP, _I, _I, _VP, _VP]),
+    ("sd_unpack_weight_w12", _I, [_VP, _VP, _VP, _I, _I, _VP]),
+    ("sd_model_set_w12", _I, [_VP, _I, _I, _VP, _VP]),
+    ("sd_session_w12_launches", _I, [_VP]),
     ("sd_pack_activation_bf16", _I, [_VP, _VP, _I, _I, _VP]),
     ("sd_gemm_bf16", _I, [_VP, _VP, _I, _I, _I, _I, _VP, C.c_size_t, _VP, C.POINTER(C.c_int), _VP]),
     ("sd_session_kv_bytes", C.c_size_t, [_VP, _I]),

@@ -33,6 +33,7 @@ struct sd_model {
     sd_model_config cfg;
     sd_model_weights w;
     std::vector<const void *> wqkv, bqkv, wo, bo, wgu, bfc1, wdown, bfc2, n1w, n1b, n2w, n2b;
+    std::vector<W12Arg> w12[3];   // [SD_W12_*][layer]: 12-bit records of that matrix (sd_model_set_w12; codes == NULL: none)
 };
 
 enum { PC_GEMM = 0, PC_ATTN, PC_NORM, PC_QKV, PC_ACT, PC_EMBED, PC_LOGITS, PC_OTHER };
@@ -62,6 +63,7 @@ struct sd_session {
     int kv_fp8;         // the arena holds fp8 e4m3 (sd_session_set_kv_fp8)
     int prefill_attn_launches;   // attn_prefill_kernel + attn_prefill_blocked_kernel launches so far (sd_session_prefill_attn_launches: the route, for tests)
     int prefill_attn_blocked_launches;   // ... of which attn_prefill_blocked_kernel
+    int w12_launches;            // GEMM launches that streamed 12-bit weight records so far (sd_session_w12_launches)
     const float *kv_scale;   // device [L][2][Hkv]
     struct sd_tp *tp;   // tensor-parallel group of this shard (NULL: the model is whole)
     float *tp_in, *tp_out;   // [max_rows][hidden] fp32: this rank's partial O / down output, and the all-reduced sum
@@ -117,6 +119,7 @@ extern "C" int sd_model_create(const sd_model_config *cfg, const sd_model_weight
     copy_ptrs(m->wdown, w->w_down, L); copy_ptrs(m->bfc2, w->b_fc2, L);
     copy_ptrs(m->n1w, w->norm1_w, L); copy_ptrs(m->n1b, w->norm1_b, L);
     copy_ptrs(m->n2w, w->norm2_w, L); copy_ptrs(m->n2b, w->norm2_b, L);
+    for (auto &v : m->w12) v.assign(L, W12Arg{nullptr, nullptr});
     *out = m;
     return SD_OK;
 }
@@ -134,6 +137,24 @@ extern "C" int sd_pack_weight_bf16(const void *src, void *dst, int N, int K, voi
     hipLaunchKernelGGL(pack_weight_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)src,
                        (uint16_t *)dst, N, K);
     SD_LAUNCH_CHECK();
+    return SD_OK;
+}
+
+// ---- 12-bit weight records (w12.h)
+extern "C" int sd_w12_bytes(int N, int K, size_t *codes_bytes, size_t *meta_bytes) {
+    SD_REQUIRE(N > 0 && K > 0 && N % 16 == 0 && K % 32 == 0, "sd_w12_bytes: need N %% 16 == 0 and K %% 32 == 0 (got %d x %d)", N, K);
+    const size_t tiles = (size_t)(N / 16) * (K / 32);
+    if (codes_bytes) *codes_bytes = tiles * W12_TILE_DWORDS * sizeof(unsigned);
+    if (meta_bytes) *meta_bytes = tiles * sizeof(u32x4);
+    return SD_OK;
+}
+// (sd_pack_weight_w12 / sd_unpack_weight_w12: at the end of the file, with the other kernels that read the records)
+extern "C" int sd_model_set_w12(sd_model *m, int which, int layer, const void *codes, const void *meta) {
+    SD_REQUIRE(m && which >= 0 && which < 3 && layer >= 0 && layer < m->cfg.n_layers, "sd_model_set_w12: bad matrix %d of layer %d", which, layer);
+    SD_REQUIRE(m->cfg.dtype == SD_BF16, "sd_model_set_w12: the 12-bit records hold bf16 weights");
+    SD_REQUIRE((codes != nullptr) == (meta != nullptr), "sd_model_set_w12: codes and meta come together");
+    SD_REQUIRE(((uintptr_t)codes & 127) == 0 && ((uintptr_t)meta & 15) == 0, "sd_model_set_w12: codes must be 128-byte, meta 16-byte aligned");
+    m->w12[which][layer] = W12Arg{(const unsigned *)codes, (const u32x4 *)meta};
     return SD_OK;
 }
 
@@ -548,6 +569,7 @@ extern "C" int sd_session_create(sd_model *m, int max_seq, int max_rows, void *k
     s->kv_fp8 = 0;
     s->kv_scale = nullptr;
     s->prefill_attn_launches = 0;
+    s->w12_launches = 0;
     s->prefill_attn_blocked_launches = 0;
     s->tp_in = (float *)(s->scratch + p.tp_in);
     s->tp_out = (float *)(s->scratch + p.tp_out);
@@ -594,6 +616,7 @@ extern "C" int sd_session_set_kv_fp8(sd_session *s, const float *scales) {
 // attn_prefill_kernel + attn_prefill_blocked_kernel launches of this session so far (a host counter: the session profile counts one attention-class launch
 // whichever kernel ran).  A batched pass counts on its first session.
 extern "C" int sd_session_prefill_attn_launches(const sd_session *s) { return s ? s->prefill_attn_launches : 0; }
+extern "C" int sd_session_w12_launches(const sd_session *s) { return s ? s->w12_launches : 0; }
 // ... of which attn_prefill_blocked_kernel's (a context past the single score tile, or SD_PREFILL_ATTN_BLOCK set)
 extern "C" int sd_session_prefill_attn_blocked_launches(const sd_session *s) { return s ? s->prefill_attn_blocked_launches : 0; }
 
@@ -1322,6 +1345,18 @@ static int launch_gemm_fin(sd_session *s, const GemmRoute &pl, const void *W, co
     return SD_OK;
 }
 
+// The same two launches reading 12-bit weight records (w12.h) - defined at the end of this file, so that their kernels
+// follow every other kernel of the code object (see launch_attn_bf16 below for what a kernel in the middle costs)
+static int launch_gemm_xn_w12(sd_session *s, bool qkv, W12Arg W, const void *X, int M, int N, int K, const void *norm_w, float eps,
+                              GemmEpiT<bf16_t> e, hipStream_t st);
+static int launch_gemm_fin_w12(sd_session *s, const GemmRoute &pl, W12Arg W, const void *X, int M, int N, int K, hipStream_t st);
+// the 12-bit records of layer l's matrix `which`, if this pass may read them (bf16 model, a copy registered)
+template <typename T>
+static W12Arg w12_of(const sd_model *m, int which, int l) {
+    if constexpr (std::is_same<T, bf16_t>::value) return m->w12[which][l];
+    return W12Arg{nullptr, nullptr};
+}
+
 // The tail of every head whose accumulators lie in s->part as S slabs: a caller that takes the raw slab gets it as it is
 // when the head ran unsplit, everybody else gets the slabs folded and rounded into logits_out (logits_kernel).
 template <typename T>
@@ -1678,6 +1713,9 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
         // weight layout, else slabs for the stand-alone epilogue)
         if (l == 0 && fp.embed_qkv) {
             if ((rc = launch_small_qkv<PRO_EMBED>(s, qkv_epi<bf16_t>(s, tab, 0), embed_pro(s, fp), st)) != SD_OK) return rc;
+        } else if (xn_q && w12_of<T>(m, SD_W12_QKV, l).codes) {
+            rc = launch_gemm_xn_w12(s, true, w12_of<T>(m, SD_W12_QKV, l), h, n_new, qkv_cols(c), H, m->n1w[l], c.norm_eps, qkv_epi<bf16_t>(s, tab, l), st);
+            if (rc != SD_OK) return rc;
         } else if (xn_q) {
             rc = launch_gemm_xn<EPI_QKV_ROPE, H16>(s, m->wqkv[l], h, n_new, qkv_cols(c), H, m->n1w[l], c.norm_eps, qkv_epi<H16>(s, tab, l), st);
             if (rc != SD_OK) return rc;
@@ -1715,7 +1753,10 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
                                          pre ? m->n2b[l] : m->n1b[l], pre ? RES_PRE : RES_POST, st)) != SD_OK)
             return rc;
         // ---- gate/up (fc1) -> SiLU * up / ReLU -> activation buffer
-        if (xn_o) {
+        if (xn_o && w12_of<T>(m, SD_W12_GATE_UP, l).codes) {
+            rc = launch_gemm_xn_w12(s, false, w12_of<T>(m, SD_W12_GATE_UP, l), h, n_new, gu_cols(c), H, m->n2w[l], c.norm_eps, act_epi<bf16_t>(s, l), st);
+            if (rc != SD_OK) return rc;
+        } else if (xn_o) {
             rc = launch_gemm_xn<EPI_ACT_SILU, H16>(s, m->wgu[l], h, n_new, gu_cols(c), H, m->n2w[l], c.norm_eps, act_epi<H16>(s, l), st);
             if (rc != SD_OK) return rc;
         } else if (fused) {
@@ -1732,7 +1773,9 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
         }
         // ---- down projection (fc2) + residual (+ the next norm).  With the norm-on-load seam its last k-slab's workgroups add
         // the residual and the next layer's QKV normalises on load (no residual+norm launch)
-        if (xn_d) {
+        if (xn_d && w12_of<T>(m, SD_W12_DOWN, l).codes) {
+            if ((rc = launch_gemm_fin_w12(s, fp.down, w12_of<T>(m, SD_W12_DOWN, l), ac, n_new, H, I, st)) != SD_OK) return rc;
+        } else if (xn_d) {
             if ((rc = launch_gemm_fin<H16>(s, fp.down, m->wdown[l], ac, n_new, H, I, nullptr, st)) != SD_OK) return rc;
         } else {
             if ((rc = run_gemm<H16>(s, fp.down, m->wdown[l], ac, n_new, H, I, &go, st)) != SD_OK) return rc;
@@ -2100,3 +2143,58 @@ extern "C" int sd_gemm_bf16(const void *w_packed, const void *x, int x_tiled, in
 
 // ---- the native decode loops (sd_spec_*, sd_multi_adopt): same translation unit, they use sd_session and the forwards above
 #include "spec_loops.h"
+
+// ---- the norm-on-load and the finishing GEMM on 12-bit weight records (forward declarations above launch_gemm_xn's users).
+// Last in the file: their kernels are the last of the code object.
+static int launch_gemm_xn_w12(sd_session *s, bool qkv, W12Arg W, const void *X, int M, int N, int K, const void *norm_w, float eps,
+                              GemmEpiT<bf16_t> e, hipStream_t st) {
+    ProfScope ps(s, PC_GEMM, st);
+    SD_REQUIRE(M <= 8 && N % 16 == 0 && K % 1024 == 0 && K <= 8192, "norm-on-load GEMM: M=%d N=%d K=%d", M, N, K);
+    e.nrm_ssq = s->ssq; e.nrm_w = (const bf16_t *)norm_w; e.nrm_nt = K / 16; e.nrm_eps = eps;
+    auto go = [&](auto epi, auto c) {
+        hipLaunchKernelGGL((gemm_bf16_stream_xn<decltype(epi)::value, decltype(c)::value, bf16_t, WFetchW12>), dim3(N / 16), dim3(256),
+                           (size_t)K * sizeof(bf16_t), st, W, (const bf16_t *)X, (float *)nullptr, M, N, K, 1, K / 32, e);
+    };
+    auto by_rows = [&](auto epi) {
+        using std::integral_constant;
+        if (M <= 4) go(epi, integral_constant<int, 4>{});
+        else if (M == 5) go(epi, integral_constant<int, 3>{});
+        else go(epi, integral_constant<int, 2>{});
+    };
+    if (qkv) by_rows(std::integral_constant<int, EPI_QKV_ROPE>{});
+    else by_rows(std::integral_constant<int, EPI_ACT_SILU>{});
+    SD_LAUNCH_CHECK();
+    ++s->w12_launches;
+    return SD_OK;
+}
+static int launch_gemm_fin_w12(sd_session *s, const GemmRoute &pl, W12Arg W, const void *X, int M, int N, int K, hipStream_t st) {
+    ProfScope ps(s, PC_GEMM, st);
+    SD_REQUIRE(pl.kind == GK_STREAM && M <= 16 && (size_t)pl.S * 16 * N <= s->part_floats, "k-split GEMM with residual epilogue: M=%d N=%d K=%d", M, N, K);
+    GemmEpiT<bf16_t> e = {};
+    e.res_x = (bf16_t *)s->x; e.res_h = (bf16_t *)s->h; e.res_ssq = s->ssq;
+    const unsigned want = s->fin_epoch + (unsigned)(pl.S - 1) + (unsigned)s->skew_now;
+    hipLaunchKernelGGL((gemm_bf16_stream_fin<bf16_t, WFetchW12>), dim3((N / 16) * pl.S), dim3(256), 0, st, W, (const bf16_t *)X, s->part,
+                       M, N, K, pl.S, pl.ksp, e, s->fin_ctr, want, s->wait_status);
+    SD_LAUNCH_CHECK();
+    s->fin_epoch += (unsigned)(pl.S - 1);
+    ++s->w12_launches;
+    return SD_OK;
+}
+extern "C" int sd_pack_weight_w12(const void *w_tiled, void *codes, void *meta, int N, int K, int *status_dev, void *stream) {
+    SD_REQUIRE(w_tiled && codes && meta && status_dev && N > 0 && K > 0 && N % 16 == 0 && K % 32 == 0,
+               "sd_pack_weight_w12: need N %% 16 == 0 and K %% 32 == 0 (got %d x %d) and no null pointer", N, K);
+    SD_REQUIRE(((uintptr_t)codes & 127) == 0 && ((uintptr_t)meta & 15) == 0, "sd_pack_weight_w12: codes must be 128-byte, meta 16-byte aligned");
+    SD_HIP_CHECK(hipMemsetAsync(status_dev, 0, sizeof(int), (hipStream_t)stream));
+    hipLaunchKernelGGL(w12_pack_kernel<0>, dim3((unsigned)((size_t)(N / 16) * (K / 32))), dim3(64), 0, (hipStream_t)stream,
+                       (const u32x4 *)w_tiled, (unsigned *)codes, (u32x4 *)meta, status_dev);
+    SD_LAUNCH_CHECK();
+    return SD_OK;
+}
+extern "C" int sd_unpack_weight_w12(const void *codes, const void *meta, void *w_tiled, int N, int K, void *stream) {
+    SD_REQUIRE(w_tiled && codes && meta && N > 0 && K > 0 && N % 16 == 0 && K % 32 == 0,
+               "sd_unpack_weight_w12: need N %% 16 == 0 and K %% 32 == 0 (got %d x %d) and no null pointer", N, K);
+    hipLaunchKernelGGL(w12_unpack_kernel<0>, dim3((unsigned)((size_t)(N / 16) * (K / 32))), dim3(64), 0, (hipStream_t)stream,
+                       W12Arg{(const unsigned *)codes, (const u32x4 *)meta}, (u32x4 *)w_tiled);
+    SD_LAUNCH_CHECK();
+    return SD_OK;
+}

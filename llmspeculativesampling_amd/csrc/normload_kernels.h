@@ -9,6 +9,7 @@
 #pragma once
 #include "model_kernels.h"
 #include "rows_kernels.h"
+#include "w12.h"
 
 // ---- the streaming GEMM for <= 8 UN-normalised rows: RMSNorm applied while the operand is loaded -----------------------
 // (modeling_llama.py:84-89: x.float() * rsqrt(mean(x^2) + eps), back to the weight dtype, times the weight.)
@@ -40,8 +41,10 @@ __device__ __forceinline__ u32x4 norm_frag(u32x4 x, u32x4 g, float r) {
 // C: k-steps whose M valid rows fit one conversion register (C * 4 * M <= 64 lanes).  Weight requests stay in groups of
 // four k-steps (the streaming kernel's measured optimum; groups of three ran 4 % slower whatever the conversion cost), so
 // a group takes NCV = ceil(4 / C) conversions, the last one covering what is left of the four.
-template <int EPI, int C, typename H = bf16_t>
-__global__ __launch_bounds__(256, 8) void gemm_bf16_stream_xn(const u32x4 *__restrict__ Wp, const H *__restrict__ X,
+// WF is the weight fetch (w12.h): bf16 tiles, 16 bytes per lane and k-step, or their 12-bit records, 12 bytes per lane
+// plus the tile's side record through the scalar cache, decoded to the same u32x4 right before its MFMA.
+template <int EPI, int C, typename H = bf16_t, typename WF = WFetchBf16>
+__global__ __launch_bounds__(256, 8) void gemm_bf16_stream_xn(typename WF::Arg Wp, const H *__restrict__ X,
                                                              float *__restrict__ part, int M, int N, int K, int SB,
                                                              int ks_per_blk, GemmEpiT<H> e) {
     constexpr int G = 4, NCV = (G + C - 1) / C;
@@ -54,7 +57,7 @@ __global__ __launch_bounds__(256, 8) void gemm_bf16_stream_xn(const u32x4 *__res
     const int kb0 = sb * ks_per_blk, kb1 = min(KS, kb0 + ks_per_blk);
     const int per = (kb1 - kb0 + 3) >> 2;
     const int ks0 = min(kb1, kb0 + wv * per), ks1 = min(kb1, ks0 + per), ksa = min(ks0, KS - 1), nk = ks1 - ks0;
-    const u32x4 *wp = Wp + ((size_t)ntg * KS + ksa) * 64 + lane;
+    const WF wf(Wp, (size_t)ntg * KS + ksa, lane);
     // ---- prologue requests: norm weight -> LDS by DMA (no registers), the row's partials, then the first group's weights
     const unsigned gs_base = (unsigned)(uintptr_t)xn_smem;
     const u32x4 *gsrc = reinterpret_cast<const u32x4 *>(e.nrm_w);
@@ -66,10 +69,11 @@ __global__ __launch_bounds__(256, 8) void gemm_bf16_stream_xn(const u32x4 *__res
 #pragma unroll
     for (int j = 0; j < XN_MAX4; ++j) sv[j] = sp[min(j, n4 - 1)];
     asm volatile("" ::: "memory");
-    u32x4 w[G], xc[NCV];
+    typename WF::Frag w[G];
+    u32x4 xc[NCV];
     const bool g0 = nk >= G;
 #pragma unroll
-    for (int u = 0; u < G; ++u) w[u] = __builtin_nontemporal_load(wp + (g0 ? (size_t)u * 64 : 0));
+    for (int u = 0; u < G; ++u) w[u] = wf.fetch(g0 ? (size_t)u : 0);
     asm volatile("" ::: "memory");
     // ---- row totals
     float sum = 0.f;
@@ -118,7 +122,7 @@ __global__ __launch_bounds__(256, 8) void gemm_bf16_stream_xn(const u32x4 *__res
         }
 #pragma unroll
         for (int u = 0; u < G; ++u) {
-            u32x4 x, wz = w[u];
+            u32x4 x, wz = WF::frag(w[u], lane);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 x[i] = (unsigned)__builtin_amdgcn_ds_bpermute(bsrc + (u % C) * 16 * M, (int)xc[u / C][i]);
@@ -137,14 +141,14 @@ __global__ __launch_bounds__(256, 8) void gemm_bf16_stream_xn(const u32x4 *__res
         issue_x(ks, G);
         asm volatile("" ::: "memory");
 #pragma unroll
-        for (int u = 0; u < G; ++u) w[u] = __builtin_nontemporal_load(wp + (size_t)(ks + u) * 64);
+        for (int u = 0; u < G; ++u) w[u] = wf.fetch((size_t)(ks + u));
         compute(ks, G);
     }
     if (ks < nk) {                                                // the last < 4 k-steps: past-the-range steps repeat the first
         const int left = nk - ks;
         issue_x(ks, left);
 #pragma unroll
-        for (int u = 0; u < G; ++u) w[u] = __builtin_nontemporal_load(wp + (size_t)(ks + (u < left ? u : 0)) * 64);
+        for (int u = 0; u < G; ++u) w[u] = wf.fetch((size_t)(ks + (u < left ? u : 0)));
         compute(ks, left);
     }
     red[wv][0][lane] = acc;
@@ -177,8 +181,8 @@ __device__ __forceinline__ f32x4 load_f32x4_sc1(const float *p) {
     return f32x4{__uint_as_float((unsigned)a), __uint_as_float((unsigned)(a >> 32)), __uint_as_float((unsigned)b),
                  __uint_as_float((unsigned)(b >> 32))};
 }
-template <typename H = bf16_t>
-__global__ __launch_bounds__(256) void gemm_bf16_stream_fin(const u32x4 *__restrict__ Wp, const H *__restrict__ X,
+template <typename H = bf16_t, typename WF = WFetchBf16>
+__global__ __launch_bounds__(256) void gemm_bf16_stream_fin(typename WF::Arg Wp, const H *__restrict__ X,
                                                            float *__restrict__ part, int M, int N, int K, int SB,
                                                            int ks_per_blk, GemmEpiT<H> e, unsigned *__restrict__ ctr,
                                                            unsigned want, unsigned *__restrict__ wait_status) {
@@ -192,30 +196,32 @@ __global__ __launch_bounds__(256) void gemm_bf16_stream_fin(const u32x4 *__restr
     const int per = (kb1 - kb0 + 3) >> 2;
     const int ks0 = min(kb1, kb0 + wv * per), ks1 = min(kb1, ks0 + per), ksa = min(ks0, KS - 1);
     const uint2 xpre = fin ? resid_prefetch<H>(e.res_x, M, N, ntg, (int)threadIdx.x) : uint2{0u, 0u};
-    const u32x4 *wp = Wp + ((size_t)ntg * KS + ksa) * 64 + lane;
+    WF wf(Wp, (size_t)ntg * KS + ksa, lane);
     const int mrow = (lane & 15) < M ? (lane & 15) : 0;           // rows >= M read row 0 (their output columns are dropped)
     const H *xp = X + (size_t)ksa * 512 + ((lane >> 4) * 16 + mrow) * 8;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     int ks = ks0;
     for (; ks + U <= ks1; ks += U) {
-        u32x4 w[U], x[U];
+        typename WF::Frag w[U];
+        u32x4 x[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) w[u] = __builtin_nontemporal_load(wp + (size_t)u * 64);
+        for (int u = 0; u < U; ++u) w[u] = wf.fetch((size_t)u);
 #pragma unroll
         for (int u = 0; u < U; ++u) x[u] = *reinterpret_cast<const u32x4 *>(xp + u * 512);
 #pragma unroll
-        for (int u = 0; u < U; ++u) acc = mfma16<H>(w[u], x[u], acc);
-        wp += (size_t)U * 64; xp += U * 512;
+        for (int u = 0; u < U; ++u) acc = mfma16<H>(WF::frag(w[u], lane), x[u], acc);
+        wf.advance(U); xp += U * 512;
     }
     if (ks < ks1) {                                               // the last < 4 k-steps as one burst too
         const int rem = ks1 - ks;
-        u32x4 w[U - 1], x[U - 1];
+        typename WF::Frag w[U - 1];
+        u32x4 x[U - 1];
 #pragma unroll
         for (int u = 0; u < U - 1; ++u)
-            if (u < rem) { w[u] = __builtin_nontemporal_load(wp + (size_t)u * 64); x[u] = *reinterpret_cast<const u32x4 *>(xp + u * 512); }
+            if (u < rem) { w[u] = wf.fetch((size_t)u); x[u] = *reinterpret_cast<const u32x4 *>(xp + u * 512); }
 #pragma unroll
         for (int u = 0; u < U - 1; ++u)
-            if (u < rem) acc = mfma16<H>(w[u], x[u], acc);
+            if (u < rem) acc = mfma16<H>(WF::frag(w[u], lane), x[u], acc);
     }
     red[wv][0][lane] = acc;
     __syncthreads();

@@ -12,6 +12,8 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
+import sys
 from typing import Callable, Dict, List, Optional
 
 import torch
@@ -62,7 +64,8 @@ class SpecDecModel:
     ``.config.is_encoder_decoder`` (speculative_sampling.py:1942) and ``.device`` (:1909)."""
 
     def __init__(self, cfg: ModelConfig, get_tensor: Callable[[str], torch.Tensor],
-                 dtype: torch.dtype = torch.bfloat16, device: str = "cuda", max_pos: Optional[int] = None):
+                 dtype: torch.dtype = torch.bfloat16, device: str = "cuda", max_pos: Optional[int] = None,
+                 w12: Optional[bool] = None):
         if not torch.cuda.is_available():
             raise RuntimeError("SpecDecModel needs a GPU: the HIP path has no CPU fallback")
         assert dtype in (torch.float32, torch.bfloat16, torch.float16)
@@ -75,7 +78,10 @@ class SpecDecModel:
         self.tp_group = None                         # tp.TPGroup when this model is one shard of a tensor-parallel target
         self._keep: List[torch.Tensor] = []          # owns every device tensor the handle points into
         self._arrays = []
-        self.weight_bytes = 0                        # bytes the forward streams (embedding tables excluded)
+        self.weight_bytes = 0                        # algorithmic bf16 bytes a forward streams (embedding tables excluded)
+        self.streamed_weight_bytes = 0               # bytes a <= 8-row decode / verify pass streams (12-bit records where packed)
+        self.w12 = w12                               # None: SD_W12 / the memory rule decide (_pack_w12)
+        self.w12_packed: Dict[str, List[int]] = {}   # matrix kind -> layers whose 12-bit records are registered
         self.fused = dtype != torch.float32 and cfg.intermediate_size % 8 == 0 and cfg.head_dim % 4 == 0
         # dtype of the probability rows the reference would keep for this model (kvcache_model.py:167-168 on the model's
         # logits): OPT's logits stay in the weight dtype (modeling_opt.py:974), Llama's are cast to fp32 (:870)
@@ -194,6 +200,67 @@ class SpecDecModel:
         check(lib.sd_model_create(C.byref(c), C.byref(w), C.byref(h)), "sd_model_create")
         self.handle = h
         self._w, self._c = w, c
+        self.streamed_weight_bytes = self.weight_bytes
+        self._pack_w12({"qkv": wqkv, "gate_up": wgu, "down": wdn})
+
+    # -- 12-bit weight records ------------------------------------------
+    W12_DEFAULT = True                           # what an unset SD_W12 means, memory permitting
+    W12_FREE_FRACTION = 0.20                     # of device memory that must stay free after packing
+
+    def _pack_w12(self, mats: Dict[str, List[torch.Tensor]]) -> None:
+        """Second, lossless 12-bit copy of the matrices the single-stream decode / verify passes stream (the norm-on-load
+        route of engine.hip: a whole bf16 Llama model in the fused layout, hidden % 1024 == 0).  Both copies stay: prefill
+        and every pass of more than 8 rows read bf16.  ``w12`` argument, then SD_W12 (1 force / 0 forbid), then the memory
+        rule: pack when the records fit and leave W12_FREE_FRACTION of the device free."""
+        cfg = self.cfg
+        H = cfg.hidden_size
+        ok = (self.dtype == torch.bfloat16 and cfg.arch == "llama" and self.fused and H % 1024 == 0 and H <= 8192
+              and cfg.num_attention_heads * cfg.head_dim == H)          # (a tensor-parallel shard never takes the route)
+        env = os.environ.get("SD_W12")
+        want = self.w12 if self.w12 is not None else (env != "0" if env in ("0", "1") else None)
+        if not ok or want is False:
+            return
+        L = cfg.num_hidden_layers
+        # the launches that can read records: QKV behind a down projection's seam (layers >= 1), gate/up behind the fused
+        # attention + O launch (head_dim 128), down in front of a next layer
+        todo = [("qkv", _lib.SD_W12_QKV, l) for l in range(1, L)]
+        todo += [("gate_up", _lib.SD_W12_GATE_UP, l) for l in range(L)] if cfg.head_dim == 128 else []
+        todo += [("down", _lib.SD_W12_DOWN, l) for l in range(L - 1)]
+        sizes = []
+        for kind, _, l in todo:
+            N, K = mats[kind][l].shape
+            cb, mb = C.c_size_t(), C.c_size_t()
+            check(lib.sd_w12_bytes(N, K, C.byref(cb), C.byref(mb)), "sd_w12_bytes")
+            sizes.append((cb.value, mb.value))
+        need = sum(a + b for a, b in sizes)
+        if want is None:
+            free, total = torch.cuda.mem_get_info(self.device)
+            fits = free - need >= self.W12_FREE_FRACTION * total
+            if not (self.W12_DEFAULT and fits):
+                if self.W12_DEFAULT:
+                    print(f"[specdec] 12-bit weight records not built: {need / 2**30:.1f} GiB more would leave "
+                          f"{(free - need) / 2**30:.1f} of {total / 2**30:.1f} GiB free (< {self.W12_FREE_FRACTION:.0%}); "
+                          "weights stay bf16 (SD_W12=1 forces packing)", file=sys.stderr)
+                return
+        status = torch.zeros(max(len(todo), 1), dtype=torch.int32, device=self.device)
+        bufs = []
+        for i, ((kind, which, l), (cb, mb)) in enumerate(zip(todo, sizes)):
+            t = mats[kind][l]
+            N, K = t.shape
+            codes = torch.empty(cb, dtype=torch.uint8, device=self.device)
+            meta = torch.empty(mb, dtype=torch.uint8, device=self.device)
+            check(lib.sd_pack_weight_w12(t.data_ptr(), codes.data_ptr(), meta.data_ptr(), N, K,
+                                         status.data_ptr() + 4 * i, _stream()), "sd_pack_weight_w12")
+            bufs.append((codes, meta))
+        bad = status.cpu().tolist()                  # (synchronises)
+        for (kind, which, l), (codes, meta), (cb, mb), st in zip(todo, bufs, sizes, bad):
+            if st:                                   # a tile with more than six escapes: this matrix stays bf16
+                continue
+            check(lib.sd_model_set_w12(self.handle, which, l, codes.data_ptr(), meta.data_ptr()), "sd_model_set_w12")
+            self._keep += [codes, meta]
+            self.w12_packed.setdefault(kind, []).append(l)
+            t = mats[kind][l]
+            self.streamed_weight_bytes += cb + mb - t.numel() * t.element_size()
 
     def __del__(self):
         h = getattr(self, "handle", None)
@@ -204,8 +271,8 @@ class SpecDecModel:
     # -- constructors -----------------------------------------------------------------------
     @classmethod
     def from_state_dict(cls, cfg: ModelConfig, sd: Dict[str, torch.Tensor], dtype=torch.bfloat16,
-                        device="cuda", max_pos=None) -> "SpecDecModel":
-        return cls(cfg, lambda n: sd[n], dtype=dtype, device=device, max_pos=max_pos)
+                        device="cuda", max_pos=None, w12: Optional[bool] = None) -> "SpecDecModel":
+        return cls(cfg, lambda n: sd[n], dtype=dtype, device=device, max_pos=max_pos, w12=w12)
 
     @classmethod
     def from_hf(cls, module, dtype: Optional[torch.dtype] = None, device="cuda", max_pos=None) -> "SpecDecModel":
@@ -222,7 +289,7 @@ class SpecDecModel:
     @classmethod
     def synthetic(cls, cfg: ModelConfig, seed: int, dtype=torch.bfloat16, device="cuda", max_pos=None,
                   method: str = "torch", gain: float = 1.0, head_gain: float = 4.0, transform=None,
-                  seed_of=None) -> "SpecDecModel":
+                  seed_of=None, w12: Optional[bool] = None) -> "SpecDecModel":
         """Random-init weights generated tensor by tensor (never the whole model at once on the host).
         ``transform(name, tensor) -> tensor`` post-processes each generated tensor (synth.acceptance_dial_pair)."""
         from .synth import param_shapes, _scale
@@ -244,7 +311,7 @@ class SpecDecModel:
         def get(name: str) -> torch.Tensor:
             t = raw(name)
             return transform(name, t) if transform is not None else t
-        m = cls(cfg, get, dtype=dtype, device=device, max_pos=max_pos)
+        m = cls(cfg, get, dtype=dtype, device=device, max_pos=max_pos, w12=w12)
         m._synth_get, m._synth_names = get, list(shapes)     # lets a host baseline regenerate the same tensors
         return m
 
@@ -411,6 +478,11 @@ class Session:
         the matrix-core prefill attention; a batched pass counts on its first session).  A host counter: the profile's attention class counts one
         launch whichever kernel ran."""
         return int(lib.sd_session_prefill_attn_launches(self.handle))
+
+    def w12_launches(self) -> int:
+        """GEMM launches of this session so far that streamed 12-bit weight records (a host counter: <= 8-row passes of a
+        model with packed copies; prefill and wider passes read bf16 and leave it alone)."""
+        return int(lib.sd_session_w12_launches(self.handle))
 
     def prefill_attn_blocked_launches(self) -> int:
         """Of those, the launches of attn_prefill_blocked_kernel (a context past the single score tile's LDS limit, or

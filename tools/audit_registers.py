@@ -26,8 +26,10 @@ def pretty(name):
     args = []
     if rest.startswith("I"):
         rest = rest[:rest.find("Ev") + 1] if "Ev" in rest else rest
-        for tok in re.finditer(r"L([ib])(\d+)E|DF16b|DF16_|f", rest[1:]):
-            args.append(tok.group(2) if tok.group(0).startswith("L") else {"DF16b": "bf16", "DF16_": "f16"}.get(tok.group(0), "float"))
+        for tok in re.finditer(r"L([ib])(\d+)E|DF16b|DF16_|9WFetchW12|10WFetchBf16|f", rest[1:]):
+            if tok.group(0) == "10WFetchBf16":                 # (the default weight fetch of the norm-on-load GEMMs: not shown)
+                continue
+            args.append(tok.group(2) if tok.group(0).startswith("L") else {"DF16b": "bf16", "DF16_": "f16", "9WFetchW12": "w12"}.get(tok.group(0), "float"))
     return f"{base}<{', '.join(args)}>" if args else base
 
 

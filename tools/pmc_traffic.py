@@ -33,13 +33,17 @@ def demangle(name, _cache={}):
     args = []
     if rest.startswith("I"):
         rest = rest[:rest.find("Ev") + 1] if "Ev" in rest else rest      # the template list ends before the void return type
-        for tok in re.finditer(r"L([ib])(\d+)E|DF16b|DF16_|f", rest[1:]):
+        for tok in re.finditer(r"L([ib])(\d+)E|DF16b|DF16_|9WFetchW12|10WFetchBf16|f", rest[1:]):
             if tok.group(0).startswith("L"):
                 args.append(tok.group(2))
             elif tok.group(0) == "DF16b":
                 args.append("bf16")
             elif tok.group(0) == "DF16_":
                 args.append("f16")
+            elif tok.group(0) == "9WFetchW12":                            # the weight fetch of the norm-on-load GEMMs (csrc/w12.h)
+                args.append("w12")
+            elif tok.group(0) == "10WFetchBf16":
+                continue
             else:
                 args.append("float")
             if len(args) >= 6:
@@ -79,6 +83,9 @@ def main():
     is_gu = lambda k, g: re.match(r"gemm_bf16_stream<1, \d+, 1,|gemm_bf16_stream_xn<1,", k) is not None and g == 1728 * 256
     gu = [v for (_, k, g, v) in frows if is_gu(k, g)]
     gu_bytes = 2 * inter * hidden * 2
+    w12 = any(is_gu(k, g) and "w12" in k for (_, k, g, v) in frows)
+    if w12:                                                  # 12-bit records: 784 bytes per 1 KiB tile (768 codes + 16 side record)
+        gu_bytes = gu_bytes * 784 // 1024
     calib = (sum(gu) / len(gu) * 1024 * 2) / gu_bytes if gu else None
     # one verify step = the target kernels between two draft phases; identify verify steps by the lm_head GEMM with
     # grid 2000 workgroups (N = 32000) and K = 5120 (target): dispatches with grid 2000*256 alternate draft / target;
@@ -91,7 +98,7 @@ def main():
     out = {
         "command": "rocprofv3 --pmc {FETCH_SIZE|WRITE_SIZE} -- python3 bench.py --steps 1 --warmup 0 --cpu-baseline 0 --profile-classes 0 --max-len 32",
         "units": "bytes; FETCH_SIZE KiB x 1024 x 2 (gfx950 half-count correction), WRITE_SIZE KiB x 1024",
-        "calibration_gate_up_gemm": {"dispatches": len(gu), "algorithmic_bytes": gu_bytes,
+        "calibration_gate_up_gemm": {"dispatches": len(gu), "algorithmic_bytes": gu_bytes, "weights": "12-bit records" if w12 else "bf16",
                                      "corrected_fetch_over_algorithmic": calib},
         "verify_steps_in_run": n_verify,
         "hbm_bytes_per_iteration_read": tgt_f / max(1, n_verify), "hbm_bytes_per_iteration_written": tgt_w / max(1, n_verify),

@@ -18,13 +18,17 @@ def demangle(name, _cache={}):
     args = []
     if rest.startswith("I"):
         rest = rest[:rest.find("Ev") + 1] if "Ev" in rest else rest      # the template list ends before the void return type
-        for tok in re.finditer(r"L([ib])(\d+)E|DF16b|DF16_|f", rest[1:]):
+        for tok in re.finditer(r"L([ib])(\d+)E|DF16b|DF16_|9WFetchW12|10WFetchBf16|f", rest[1:]):
             if tok.group(0).startswith("L"):
                 args.append(tok.group(2))
             elif tok.group(0) == "DF16b":
                 args.append("bf16")
             elif tok.group(0) == "DF16_":
                 args.append("f16")
+            elif tok.group(0) == "9WFetchW12":                            # the weight fetch of the norm-on-load GEMMs (csrc/w12.h)
+                args.append("w12")
+            elif tok.group(0) == "10WFetchBf16":
+                continue
             else:
                 args.append("float")
             if len(args) >= 6:
