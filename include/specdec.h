@@ -371,12 +371,48 @@ int sd_pack_activation_bf16(const void *x_rowmajor, void *x_tiled, int M, int K,
 int sd_gemm_bf16(const void *w_packed, const void *x, int x_tiled, int M, int N, int K, float *part,
                  size_t part_floats, float *out, int *splits_out, void *stream);
 
-/* A session = one KV arena + scratch for one sequence (one KVCacheModel of the reference).
+/* What the GEMM planner needs to know about a call besides (N, K, M): a set of these bits. */
+enum {
+    SD_GN_GATHER = 1,    /* X rows are gathered through a row table (the lm_head of some rows of a pass) */
+    SD_GN_ROWMAJOR = 2,  /* X is plain row-major (sd_gemm_bf16 with x_tiled == 0) */
+    SD_GN_FUSED = 4,     /* an epilogue runs in the launch: every workgroup keeps its whole k-range (one slab, X tiled) */
+    SD_GN_QKV = 8,       /* ... and it is the QKV epilogue */
+    SD_GN_ONE_SLAB = 16  /* one k-slab where the shape allows it (a tensor-parallel shard's O / down projection) */
+};
+/* The kernel a route names. */
+enum { SD_GEMM_NONE = 0, SD_GEMM_STREAM = 1, SD_GEMM_STREAM_W16 = 2, SD_GEMM_ROWS = 3, SD_GEMM_MM = 4 };
+/* The planner's answer for one 16-bit GEMM of M rows on an [N][K] weight, and the kernel instance its launch takes. */
+typedef struct sd_gemm_route_info {
+    int32_t kind;                       /* SD_GEMM_*; SD_GEMM_NONE: no kernel (the row limits keep such calls out) */
+    int32_t S, ksp;                     /* k-slabs and k-steps (of 32) per slab: (S-1)*ksp < K/32 <= S*ksp */
+    int32_t mtw;                        /* gemm_bf16_mm: m-tiles per wave (2: 128-row blocks, 4: 256-row blocks) */
+    int32_t NG, grid, nwn, nwk, nld;    /* gemm_bf16_rows: n-groups, workgroups (NG * S) and the wave grid of a workgroup:
+                                           nwn compute waves per k-group x nwk k-groups + nld loader waves */
+    int32_t inst_mt;                    /* the instance's m-tiles (mm: of a row block); 0: the launch has no instance */
+    int32_t inst_ntw, inst_unroll;      /* gemm_bf16_stream: n-tiles per wave, k-steps per burst (8: the one-burst form) */
+    int32_t inst_ch, inst_wbm;          /* gemm_bf16_rows: k-steps per chunk, chunks per weight burst */
+    int32_t inst_nt;                    /* gemm_bf16_mm: non-temporal weight loads */
+    int32_t lds_bytes;                  /* dynamic LDS of the launch (rows, mm) */
+    uint64_t part_floats;               /* S * roundup(M,16) * N: the floats an unfused launch leaves in `part` */
+} sd_gemm_route_info;
+/* The route of such a GEMM (host only: no device, no session; the launch helpers take their kernel instance by the
+ * functions this query calls).  Reads the SD_GEMM_* / SD_MM_* tunables of the environment at the call.  SD_ERR_INVALID for
+ * M outside 1..256, N % 16, K % 32 or need outside the SD_GN_* bits; a shape without a kernel is SD_OK with SD_GEMM_NONE. */
+int sd_gemm_route(int N, int K, int M, int need, sd_gemm_route_info *out);
+/* sd_gemm_bf16 on the route `need` selects: need = 0 is x_tiled, SD_GN_ROWMAJOR plain rows; SD_GN_FUSED and SD_GN_ONE_SLAB
+ * (X tiled) run the one-slab plans the forward pass uses with its fused epilogues / on a shard as plain slab GEMMs.
+ * SD_GN_GATHER and SD_GN_QKV need a row table / the QKV epilogue: SD_ERR_INVALID here. */
+int sd_gemm_bf16_need(const void *w_packed, const void *x, int M, int N, int K, int need, float *part, size_t part_floats,
+                      float *out, int *splits_out, void *stream);
+
+/* A session =one KV arena + scratch for one sequence (one KVCacheModel of the reference).
  * kv_arena: [n_layers][2][n_kv_heads][max_seq][head_dim] in `dtype`, caller-allocated.
  * scratch: sd_session_scratch_bytes() bytes, caller-allocated. */
 typedef struct sd_session sd_session;
 size_t sd_session_kv_bytes(const sd_model *m, int max_seq);
 size_t sd_session_scratch_bytes(const sd_model *m, int max_rows);
+/* Floats of the scratch that hold the GEMMs' k-slabs (host only): no route of a pass of <= max_rows rows may leave more. */
+size_t sd_session_part_floats(const sd_model *m, int max_rows);
 int sd_session_create(sd_model *m, int max_seq, int max_rows, void *kv_arena, void *scratch,
                       sd_session **out);
 int sd_session_destroy(sd_session *s);

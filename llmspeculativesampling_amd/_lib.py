@@ -101,6 +101,15 @@ class SdModelConfig(C.Structure):
                 ("fused_layout", C.c_int32)]
 
 
+SD_GN_GATHER, SD_GN_ROWMAJOR, SD_GN_FUSED, SD_GN_QKV, SD_GN_ONE_SLAB = 1, 2, 4, 8, 16      # what a GEMM call needs of its route
+SD_GEMM_NONE, SD_GEMM_STREAM, SD_GEMM_STREAM_W16, SD_GEMM_ROWS, SD_GEMM_MM = 0, 1, 2, 3, 4
+
+
+class SdGemmRouteInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("kind", "S", "ksp", "mtw", "NG", "grid", "nwn", "nwk", "nld", "inst_mt", "inst_ntw",
+                                         "inst_unroll", "inst_ch", "inst_wbm", "inst_nt", "lds_bytes")] + [("part_floats", C.c_uint64)]
+
+
 _VP = C.c_void_p
 _VPP = C.POINTER(C.c_void_p)
 
@@ -150,8 +159,11 @@ SYMBOLS = [
     ("sd_session_w12_launches", _I, [_VP]),
     ("sd_pack_activation_bf16", _I, [_VP, _VP, _I, _I, _VP]),
     ("sd_gemm_bf16", _I, [_VP, _VP, _I, _I, _I, _I, _VP, C.c_size_t, _VP, C.POINTER(C.c_int), _VP]),
+    ("sd_gemm_route", _I, [_I, _I, _I, _I, C.POINTER(SdGemmRouteInfo)]),
+    ("sd_gemm_bf16_need", _I, [_VP, _VP, _I, _I, _I, _I, _VP, C.c_size_t, _VP, C.POINTER(C.c_int), _VP]),
     ("sd_session_kv_bytes", C.c_size_t, [_VP, _I]),
     ("sd_session_scratch_bytes", C.c_size_t, [_VP, _I]),
+    ("sd_session_part_floats", C.c_size_t, [_VP, _I]),
     ("sd_session_create", _I, [_VP, _I, _I, _VP, _VP, C.POINTER(_VP)]),
     ("sd_session_destroy", _I, [_VP]),
     ("sd_session_set_kv_fp8", _I, [_VP, _VP]),

@@ -216,6 +216,26 @@ static int gemm_ntw(int N, int M) {
     return 1;
 }
 
+// The gemm_bf16_stream instance a GEMM of M rows runs on - what dispatch_gemm_bf16 / launch_gemm_bf16 launch and what
+// sd_gemm_route reports: MT m-tiles, NTW n-tiles per wave, UNROLL k-steps requested together.  MT == 0: no instance.
+struct StreamInst { int MT, NTW, UNROLL; };
+constexpr int stream_unroll(int MT, int NTW) { return NTW >= 8 ? 1 : (MT > 2 ? 2 : 4); }   // 4 measured best for decode rows (tools/gemm_bench.py)
+// a wave's whole k-range in ONE burst when it is 5..8 k-steps (the draft model's K = 768 GEMMs: 6 per wave), instead of a
+// group of four and a second round trip for the rest: the <1, 8> instance, one m-tile and one n-tile per wave only
+static bool stream_burst8(int MT, int NTW, int K, int ks_per) {
+    const int per_wave = (std::min(ks_per, K / 32) + 3) / 4;
+    return MT == 1 && NTW == 1 && per_wave > 4 && per_wave <= 8;
+}
+static StreamInst stream_instance(int N, int K, int M, int Mpad, int ks_per) {
+    const int MT = Mpad / 16;
+    if (MT < 1 || MT > 4) return StreamInst{0, 0, 0};
+    // rows beyond one m-tile (prefill, stream-batched verify): every activation fragment a wave loads is reused for
+    // NTW weight tiles, because activations and weights share the CU's load path (X:W bytes = 16*MT : 16*NTW)
+    int ntw = MT == 1 ? 1 : gemm_ntw(N, M);
+    if (MT == 2 && ntw > 4) ntw = 4;                              // (no 8-tile instance at 2 m-tiles)
+    return StreamInst{MT, ntw, stream_burst8(MT, ntw, K, ks_per) ? 8 : stream_unroll(MT, ntw)};
+}
+
 #define TINY_SPLIT_BYTES 24576                       // weights a workgroup streams in a <= 16-row GEMM on a matrix of <= 8 MB
 static void gemm_split(int N, int K, int M, int *S_out, int *ks_per_out) {
     const int NTL = N / 16 / gemm_ntw(N, M), KS = K / 32;
@@ -339,13 +359,23 @@ static GemmRoute route_gemm(int N, int K, int M, int need) {
     return r;
 }
 
+// The gemm_bf16_mm instance of a route's mtw (launch_gemm_mm launches it, sd_gemm_route reports it): 128-row blocks
+// (mtw 2), or 256-row blocks (any other mtw: 4), which hold every row of a pass (<= 256 rows) - their weight tiles are read
+// once chip-wide -> non-temporal.  lds: NBUF = 3 stages x KT = 2 k-tiles x (8 W + BMT X) KiB.
+struct MmInst { int mtw, nt; size_t lds; };
+static MmInst mm_instance(int mtw) {
+    const int m = mtw == 2 ? 2 : 4;
+    return MmInst{m, m == 4, (size_t)3 * (8 + 4 * m) * 2 * 1024};
+}
+
 // gemm_bf16_mm (mm_kernels.h): EPI != EPI_PART needs r.S == 1 (the block holds the whole k-range)
 template <int EPI, typename H = bf16_t>
 static void launch_gemm_mm(const void *W, const void *X, float *part, int M, int Mpad, int N, int K, const GemmRoute &r,
                            const GemmEpiT<H> &e, hipStream_t st) {
-    const int BMT = 4 * r.mtw, MB = (Mpad / 16 + BMT - 1) / BMT, NB = N / 16 / 8;
+    const MmInst in = mm_instance(r.mtw);
+    const int BMT = 4 * in.mtw, MB = (Mpad / 16 + BMT - 1) / BMT, NB = N / 16 / 8;
     const dim3 grid(MB * NB * r.S);
-    const size_t lds = (size_t)3 * (8 + BMT) * 2 * 1024;          // NBUF = 3 stages x KT = 2 k-tiles x (8 W + BMT X) KiB
+    const size_t lds = in.lds;
     auto go = [&](auto kern) {
         static bool attr = false;                                 // (one flag per instantiation of this lambda = per kernel)
         if (!attr) {
@@ -355,8 +385,7 @@ static void launch_gemm_mm(const void *W, const void *X, float *part, int M, int
         hipLaunchKernelGGL(kern, grid, dim3(MM_THREADS), lds, st, (const u32x4 *)W, (const u32x4 *)X, part, M, Mpad, N, K, r.S,
                            r.ksp, e);
     };
-    // 256-row blocks hold every row of a pass (<= 256 rows): their weight tiles are read once chip-wide -> non-temporal
-    if (r.mtw == 2) go(gemm_bf16_mm<2, EPI, H, false>);
+    if (in.mtw == 2) go(gemm_bf16_mm<2, EPI, H, false>);
     else go(gemm_bf16_mm<4, EPI, H, true>);
 }
 
@@ -394,22 +423,34 @@ static RowsPlan rows_plan(int N, int K, int M, bool fused) {
     return p;
 }
 
-template <int EPI, typename H>
-static int launch_gemm_rows(const void *W, const void *X, float *part, int M, int Mpad, int N, int K, const RowsPlan &pl,
-                            const GemmEpiT<H> &e, hipStream_t st) {
+// The gemm_bf16_rows instance of a plan at Mpad rows (launch_gemm_rows launches it, sd_gemm_route reports it): MT m-tiles,
+// chunks of CH k-steps, weight bursts of WBM chunks, and the launch's dynamic LDS.  ok: one of the compiled instances.
+#define GR_LDS_CAP ((size_t)158 * 1024)
+struct RowsInst { int MT, CH, WBM; size_t lds; bool ok; };
+static RowsInst rows_instance(int Mpad, const RowsPlan &pl) {
     // m-tiles of the kernel instance: 2..5 as they are, 6..8 all take the 8-tile instance (the loader re-reads the last
     // real tile for the missing ones, the epilogue drops rows >= M)
     const int MT = Mpad / 16 <= 5 ? Mpad / 16 : (Mpad / 16 <= 8 ? 8 : 9);
     // activation panel (2 buffers x nwk k-groups x CH k-steps x MT tiles), reused as the fold buffer (nwn tiles x nwk x
     // MT); chunks of 8 k-steps where the panel fits the CU's LDS (one workgroup per CU owns all of it), else 6 or 4 -
     // with chunks of 4 a compute wave's weight burst spans two chunks (8 KiB requested together: WBM = 2)
-    constexpr size_t lds_cap = 158 * 1024;
     int ch = 4;
     for (int c2 : {8, 6})
-        if ((size_t)1024 * MT * 2 * pl.nwk * c2 <= lds_cap) { ch = c2; break; }
+        if ((size_t)1024 * MT * 2 * pl.nwk * c2 <= GR_LDS_CAP) { ch = c2; break; }
     if (MT == 2) ch = 8;                                          // (2 x 4 x 8 x 2 KiB always fits)
     if (MT == 3 && ch == 4) ch = 6;                               // (2 x 4 x 6 x 3 KiB = 144 KiB: the widest 3-tile panel)
-    const size_t lds = (size_t)1024 * MT * std::max(2 * pl.nwk * ch, pl.nwk * pl.nwn);
+    RowsInst in = {MT, ch, ch == 4 ? 2 : 1, (size_t)1024 * MT * std::max(2 * pl.nwk * ch, pl.nwk * pl.nwn), false};
+    in.ok = MT >= 2 && (MT == 2 ? ch == 8 : MT == 3 ? ch >= 6 : MT == 4 ? true : MT == 5 ? ch <= 6 : ch == 4);
+    return in;
+}
+
+template <int EPI, typename H>
+static int launch_gemm_rows(const void *W, const void *X, float *part, int M, int Mpad, int N, int K, const RowsPlan &pl,
+                            const GemmEpiT<H> &e, hipStream_t st) {
+    constexpr size_t lds_cap = GR_LDS_CAP;
+    const RowsInst in = rows_instance(Mpad, pl);
+    const int MT = in.MT, ch = in.CH;
+    const size_t lds = in.lds;
     SD_REQUIRE(lds <= lds_cap && Mpad / 16 <= MT, "gemm_rows: %d rows, %zu bytes of LDS", M, lds);
     auto go = [&](auto mt_c, auto ch_c, auto wbm_c) {
         constexpr int MTc = decltype(mt_c)::value, CHc = decltype(ch_c)::value, WBMc = decltype(wbm_c)::value;
@@ -425,6 +466,7 @@ static int launch_gemm_rows(const void *W, const void *X, float *part, int M, in
     using std::integral_constant;
     using I1 = integral_constant<int, 1>;
     using I2 = integral_constant<int, 2>;
+    if (!in.ok) { sd_set_error("gemm_rows: %d rows (chunk %d)", M, ch); return SD_ERR_INVALID; }
     if (MT == 2) go(integral_constant<int, 2>{}, integral_constant<int, 8>{}, I1{});
     else if (MT == 3) { if (ch == 8) go(integral_constant<int, 3>{}, integral_constant<int, 8>{}, I1{});
                         else go(integral_constant<int, 3>{}, integral_constant<int, 6>{}, I1{}); }
@@ -433,9 +475,8 @@ static int launch_gemm_rows(const void *W, const void *X, float *part, int M, in
                         else go(integral_constant<int, 4>{}, integral_constant<int, 4>{}, I2{}); }
     else if (MT == 5) { if (ch == 6) go(integral_constant<int, 5>{}, integral_constant<int, 6>{}, I1{});       // (8 never fits at 5 m-tiles)
                         else go(integral_constant<int, 5>{}, integral_constant<int, 4>{}, I2{}); }
-    else if (MT == 8 && ch == 4) go(integral_constant<int, 8>{}, integral_constant<int, 4>{}, I2{});
-    else if (MT == 9 && ch == 4) go(integral_constant<int, 9>{}, integral_constant<int, 4>{}, I2{});
-    else { sd_set_error("gemm_rows: %d rows (chunk %d)", M, ch); return SD_ERR_INVALID; }
+    else if (MT == 8) go(integral_constant<int, 8>{}, integral_constant<int, 4>{}, I2{});
+    else go(integral_constant<int, 9>{}, integral_constant<int, 4>{}, I2{});
     return SD_OK;
 }
 
@@ -933,12 +974,9 @@ template <int MT, int EPI, int NTW, typename H = bf16_t>
 static void launch_gemm_bf16(const void *W, const void *X, float *part, int M, int Mpad, int N, int K, int S,
                              int ks_per, const GemmEpiT<H> &e, hipStream_t st) {
     const int blocks = (N / 16 / NTW) * S;
-    constexpr int UNROLL = NTW >= 8 ? 1 : (MT > 2 ? 2 : 4);        // 4 measured best for decode rows (tools/gemm_bench.py)
+    constexpr int UNROLL = stream_unroll(MT, NTW);
     if constexpr (MT == 1 && NTW == 1) {
-        // a wave's whole k-range in ONE burst when it is 5..8 k-steps (the draft model's K = 768 GEMMs: 6 per wave), instead
-        // of a group of four and a second round trip for the rest
-        const int per_wave = (std::min(ks_per, K / 32) + 3) / 4;
-        if (per_wave > 4 && per_wave <= 8) {
+        if (stream_burst8(MT, NTW, K, ks_per)) {
             hipLaunchKernelGGL((gemm_bf16_stream<1, 8, EPI, 1, true, H>), dim3(blocks), dim3(256), 0, st,
                                (const u32x4 *)W, (const H *)X, part, M, Mpad, N, K, S, ks_per, e);
             return;
@@ -951,12 +989,10 @@ static void launch_gemm_bf16(const void *W, const void *X, float *part, int M, i
 template <int EPI, typename H = bf16_t>
 static int dispatch_gemm_bf16(const void *W, const void *X, float *part, int M, int Mpad, int N, int K, int S,
                               int ksp, const GemmEpiT<H> &e, hipStream_t st) {
-    const int MT = Mpad / 16;
-    // rows beyond one m-tile (prefill, stream-batched verify): every activation fragment a wave loads is reused for
-    // NTW weight tiles, because activations and weights share the CU's load path (X:W bytes = 16*MT : 16*NTW)
-    const int ntw = gemm_ntw(N, M);
+    const StreamInst in = stream_instance(N, K, M, Mpad, ksp);    // (launch_gemm_bf16 takes the UNROLL by the same functions)
+    const int MT = in.MT, ntw = in.NTW;
     if (MT == 1) launch_gemm_bf16<1, EPI, 1, H>(W, X, part, M, Mpad, N, K, S, ksp, e, st);
-    else if (MT == 2) { if (ntw >= 4) launch_gemm_bf16<2, EPI, 4, H>(W, X, part, M, Mpad, N, K, S, ksp, e, st);
+    else if (MT == 2) { if (ntw == 4) launch_gemm_bf16<2, EPI, 4, H>(W, X, part, M, Mpad, N, K, S, ksp, e, st);
                         else if (ntw == 2) launch_gemm_bf16<2, EPI, 2, H>(W, X, part, M, Mpad, N, K, S, ksp, e, st);
                         else launch_gemm_bf16<2, EPI, 1, H>(W, X, part, M, Mpad, N, K, S, ksp, e, st); }
     else if (MT == 3) { if (ntw == 8) launch_gemm_bf16<3, EPI, 8, H>(W, X, part, M, Mpad, N, K, S, ksp, e, st);
@@ -2118,13 +2154,57 @@ extern "C" int sd_pack_activation_bf16(const void *x_rowmajor, void *x_tiled, in
     return SD_OK;
 }
 
-extern "C" int sd_gemm_bf16(const void *w_packed, const void *x, int x_tiled, int M, int N, int K, float *part,
-                            size_t part_floats, float *out, int *splits_out, void *stream) {
+static_assert(SD_GEMM_NONE == GK_NONE && SD_GEMM_STREAM == GK_STREAM && SD_GEMM_STREAM_W16 == GK_STREAM_W16 &&
+              SD_GEMM_ROWS == GK_ROWS && SD_GEMM_MM == GK_MM, "specdec.h publishes GemmKind");
+static_assert(SD_GN_GATHER == GN_GATHER && SD_GN_ROWMAJOR == GN_ROWMAJOR && SD_GN_FUSED == GN_FUSED && SD_GN_QKV == GN_QKV &&
+              SD_GN_ONE_SLAB == GN_ONE_SLAB, "specdec.h publishes GemmNeed");
+
+// The planner's decision for one GEMM, with the kernel instance the launch helpers take for it - by the functions they call
+extern "C" int sd_gemm_route(int N, int K, int M, int need, sd_gemm_route_info *out) {
+    SD_REQUIRE(out, "sd_gemm_route: null argument");
+    SD_REQUIRE(M >= 1 && M <= SD_MAX_FWD_ROWS && N >= 16 && K >= 32 && N % 16 == 0 && K % 32 == 0,
+               "sd_gemm_route: need 1<=M<=%d, N%%16==0, K%%32==0", SD_MAX_FWD_ROWS);
+    SD_REQUIRE(need >= 0 && need < 32, "sd_gemm_route: need is a set of SD_GN_* bits");
+    refresh_env();
+    const GemmRoute r = route_gemm(N, K, M, need);
+    const int Mpad = (int)align_up(M, 16);
+    sd_gemm_route_info o = {};
+    o.kind = r.kind; o.S = r.S; o.ksp = r.ksp; o.mtw = r.mtw;
+    if (r.kind == GK_STREAM) {
+        const StreamInst in = stream_instance(N, K, M, Mpad, r.ksp);
+        o.inst_mt = in.MT; o.inst_ntw = in.NTW; o.inst_unroll = in.UNROLL;
+    } else if (r.kind == GK_STREAM_W16) {
+        o.inst_mt = 1; o.inst_ntw = 1;
+    } else if (r.kind == GK_ROWS) {
+        const RowsInst in = rows_instance(Mpad, r.rp);
+        o.NG = r.rp.NG; o.grid = r.rp.grid; o.nwn = r.rp.nwn; o.nwk = r.rp.nwk; o.nld = r.rp.nld;
+        if (in.ok && Mpad / 16 <= in.MT) { o.inst_mt = in.MT; o.inst_ch = in.CH; o.inst_wbm = in.WBM; }
+        o.lds_bytes = (int32_t)in.lds;
+    } else if (r.kind == GK_MM) {
+        const MmInst in = mm_instance(r.mtw);
+        o.inst_mt = 4 * in.mtw; o.inst_nt = in.nt; o.lds_bytes = (int32_t)in.lds;
+    }
+    o.part_floats = r.kind == GK_NONE ? 0 : (uint64_t)r.S * Mpad * N;
+    *out = o;
+    return SD_OK;
+}
+
+extern "C" size_t sd_session_part_floats(const sd_model *m, int max_rows) {
+    if (!m) return 0;
+    refresh_env();
+    return plan_scratch(m->cfg, std::min(max_rows, sd_model_max_rows(m))).part_floats;
+}
+
+extern "C" int sd_gemm_bf16_need(const void *w_packed, const void *x, int M, int N, int K, int need, float *part,
+                                 size_t part_floats, float *out, int *splits_out, void *stream) {
     SD_REQUIRE(w_packed && x && part, "sd_gemm_bf16: null argument");
     refresh_env();
     SD_REQUIRE(M >= 1 && M <= SD_MAX_FWD_ROWS && N % 16 == 0 && K % 32 == 0,
                "sd_gemm_bf16: need 1<=M<=%d, N%%16==0, K%%32==0", SD_MAX_FWD_ROWS);
-    const GemmRoute r = route_gemm(N, K, M, x_tiled ? 0 : GN_ROWMAJOR);
+    SD_REQUIRE(need >= 0 && need < 32 && !(need & (GN_GATHER | GN_QKV)),
+               "sd_gemm_bf16_need: need %d (a row gather needs a row table, the QKV route its epilogue)", need);
+    const bool x_tiled = !(need & GN_ROWMAJOR);
+    const GemmRoute r = route_gemm(N, K, M, need);
     SD_REQUIRE(r.kind != GK_NONE, "sd_gemm_bf16: more than 64 rows need the tile layout (x_tiled) and N %% 128 == 0");
     const int Mpad = (int)align_up(M, 16);
     SD_REQUIRE((size_t)r.S * Mpad * N <= part_floats, "sd_gemm_bf16: part buffer needs %zu floats", (size_t)r.S * Mpad * N);
@@ -2139,6 +2219,11 @@ extern "C" int sd_gemm_bf16(const void *w_packed, const void *x, int x_tiled, in
     }
     if (splits_out) *splits_out = r.S;
     return SD_OK;
+}
+
+extern "C" int sd_gemm_bf16(const void *w_packed, const void *x, int x_tiled, int M, int N, int K, float *part,
+                            size_t part_floats, float *out, int *splits_out, void *stream) {
+    return sd_gemm_bf16_need(w_packed, x, M, N, K, x_tiled ? 0 : GN_ROWMAJOR, part, part_floats, out, splits_out, stream);
 }
 
 // ---- the native decode loops (sd_spec_*, sd_multi_adopt): same translation unit, they use sd_session and the forwards above

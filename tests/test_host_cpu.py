@@ -36,6 +36,15 @@ def test_struct_layouts_match_header():
     assert C.sizeof(_lib.SdModelConfig) == 15 * 4
     assert C.sizeof(_lib.SdBatchStream) == 9 * 8 + 5 * 4 + 4 + 2 * 8 + 2 * 4 + 3 * 8      # (4 bytes of padding before `seed`)
     assert C.sizeof(_lib.SdModelWeights) == 21 * 8
+    assert C.sizeof(_lib.SdGemmRouteInfo) == 16 * 4 + 8 and _lib.SdGemmRouteInfo.part_floats.offset == 64
+    # the query fills every field of the struct as the header lays it out (a streaming route, a rows route, an mm route)
+    info = _lib.SdGemmRouteInfo()
+    assert _lib.lib.sd_gemm_route(5120, 5120, 5, _lib.SD_GN_ROWMAJOR, C.byref(info)) == _lib.SD_OK
+    assert (info.kind, info.inst_mt, info.inst_ntw, info.part_floats) == (_lib.SD_GEMM_STREAM, 1, 1, info.S * 16 * 5120)
+    assert _lib.lib.sd_gemm_route(15360, 5120, 40, _lib.SD_GN_FUSED, C.byref(info)) == _lib.SD_OK
+    assert (info.kind, info.S, info.ksp, info.NG, info.grid, info.nwn, info.inst_mt) == (_lib.SD_GEMM_ROWS, 1, 160, 256, 256, 4, 3)
+    assert _lib.lib.sd_gemm_route(5120, 13824, 256, 0, C.byref(info)) == _lib.SD_OK
+    assert (info.kind, info.mtw, info.inst_mt, info.inst_nt, info.lds_bytes) == (_lib.SD_GEMM_MM, 4, 16, 1, 3 * 24 * 2 * 1024)
 
 
 def test_argument_errors_do_not_need_a_gpu():
