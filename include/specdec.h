@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define SD_ABI_VERSION 4
+#define SD_ABI_VERSION 5
 
 typedef enum {
     SD_OK = 0,
@@ -522,20 +522,38 @@ int sd_spec_iteration(sd_spec *sp, int L, int draft_len, int target_len, uint64_
                       uint64_t seed_accept, uint64_t draw_scan0, uint64_t draw_resample, const float *r_const,
                       sd_accept_result *res_host, int32_t *tok_host /* gamma+2 ids from seq[L], may be NULL */,
                       void *stream);
+/* ---- Argument blocks of the native loops below: caller-owned host structs, used during the call only.  An entry refuses a
+ * NULL block with SD_ERR_INVALID before anything is written or launched.
+ * sd_sampling: what every loop samples with and stops on; ld = row stride of the probability arenas.
+ * sd_head_scratch: one model's logit rows (scratch for its head) and the SD_NORM_* mode its rows are normalised in.
+ * sd_spec_scratch: both heads; norm_workspace (device, may be NULL): sd_norm_workspace_bytes(max_rows_per_forward) bytes, the
+ *   candidate rows of a pass and, behind them, one candidate list per row; the most rows a target pass may carry.
+ * sd_lockstep_log: host arrays of max_iters_log entries (each may be NULL): time of an iteration's verify passes, streams in
+ *   it, their mean context.  Out: n_iters, and err = 1 when a stream hit a sampling / normalisation error (the reference raises).
+ * sd_seq_state: in/out state and logs of ONE sequence.  host_seq (host int32, capacity >= T + gamma + 1) holds the `len` tokens
+ *   so far and receives the new ones; draft_len / target_len are the cache lengths, (seed, draw) the Philox position; the loop
+ *   ends at T tokens, at a new EOS (more than ori_eos_cnt in all) or after max_iters iterations.  All written back on every way
+ *   out, also after an error.  Per iteration i < n_iters: acc_len_out[i], p_at_out / q_at_out (the accept ratios' operands),
+ *   draft_ms_out / target_ms_out[i]; any of the five may be NULL.  err: 0, 1 = 'prob error', 2 = 'norm logits error'.
+ * sd_ar_log: host arrays of max_steps_log entries (may be NULL): HIP-event time of each step, streams in it.  Out: n_steps, err. */
+typedef struct { float temperature; int32_t top_k; float top_p; int32_t V; long ld; int32_t eos_token_id; } sd_sampling;
+typedef struct { float *logits; long ld_logits; int32_t norm_mode; } sd_head_scratch;
+typedef struct { sd_head_scratch draft, target; void *norm_workspace; int32_t max_rows_per_forward; } sd_spec_scratch;
+typedef struct { float *verify_ms_out; int32_t *verify_streams_out; float *verify_ctx_out; int32_t max_iters_log, n_iters, err; } sd_lockstep_log;
+typedef struct {
+    int32_t *host_seq; int32_t len, T, ori_eos_cnt, draft_len, target_len; uint64_t seed, draw; int32_t max_iters;
+    int32_t *acc_len_out; float *p_at_out, *q_at_out, *draft_ms_out, *target_ms_out;
+    int32_t n_iters, err;
+} sd_seq_state;
+typedef struct { float *step_ms_out; int32_t *step_streams_out; int32_t max_steps_log; int32_t n_steps, err; } sd_ar_log;
 /* The whole loop of speculative_sampling.py:1934-2046 for the device-RNG mode: iterations (sd_spec_iteration + one stream
  * wait each) until the sequence holds T tokens, a new EOS appears (more than ori_eos_cnt of them in total) or an error
- * word is set - no Python between iterations.  host_seq (host int32, capacity >= T + gamma + 1) holds the *len_io tokens so
- * far and receives the new ones; *seed_io / *draw_io are the Philox stream position (advanced exactly as the iteration's
- * draw order prescribes: gamma draft draws, the discarded target sample, gamma uniforms - or, with random_seed != 0, the
- * stream restarted at (random_seed, 0) - and the resample); *draft_len_io / *target_len_io the cache lengths.  Per
- * iteration i < *n_iters_out: acc_len_out[i]; p_at_out / q_at_out[i * gamma ..] (the accept ratios' operands);
- * draft_ms_out / target_ms_out[i] when timing is on (else untouched; any of the five may be NULL).  *err_out: 0, or
- * 1 = 'prob error' (sample / resample), 2 = 'norm logits error'.  res_host: pinned host memory for the result block. */
-int sd_spec_generate(sd_spec *sp, int32_t *host_seq, int *len_io, int T, int eos_token_id, int ori_eos_cnt,
-                     uint64_t *seed_io, uint64_t *draw_io, uint64_t random_seed, const float *r_const, int *draft_len_io,
-                     int *target_len_io, sd_accept_result *res_host, int max_iters, int32_t *acc_len_out, float *p_at_out,
-                     float *q_at_out, float *draft_ms_out, float *target_ms_out, int *n_iters_out, int *err_out,
-                     void *stream);
+ * word is set - no Python between iterations.  `seq`: the sd_seq_state; its Philox position is advanced exactly as the
+ * iteration's draw order prescribes: gamma draft draws, the discarded target sample, gamma uniforms - or, with random_seed
+ * != 0, the stream restarted at (random_seed, 0) - and the resample.  gamma p_at / q_at values per iteration; the two times
+ * when timing is on (else untouched).  Sampling parameters: sd_spec_create's.  res_host: pinned, for the result block. */
+int sd_spec_generate(sd_spec *sp, sd_seq_state *seq, int eos_token_id, uint64_t random_seed, const float *r_const,
+                     sd_accept_result *res_host, void *stream);
 /* The stream-batched loop (throughput mode) without the interpreter between iterations: up to 16
  * independent streams decode in lock-step - every draft step one sd_batch_forward + sd_norm_batch over the active
  * streams, every verify one target pass per max_rows_per_forward / (gamma + 1) streams, then sd_accept_batch, one copy of
@@ -543,11 +561,8 @@ int sd_spec_generate(sd_spec *sp, int32_t *host_seq, int *len_io, int T, int eos
  * sessions, the device token buffer / probability arenas / error words, its device and pinned-host result block (the
  * streams' blocks must be consecutive: one copy moves them all), the host token buffer and the in/out loop state
  * (lengths, cache lengths, Philox position); per-iteration statistics as in sd_spec_generate.  Each stream runs exactly
- * the algorithm of sd_spec_generate with its own Philox stream.  verify_ms_out / verify_streams_out / verify_ctx_out
- * (host, max_iters_log entries, may be NULL): time of each iteration's verify passes, streams in it, their mean context.
- * *err_out: 1 when a stream hit a sampling / normalisation error (the reference raises).
- * norm_workspace (device, may be NULL): sd_norm_workspace_bytes(max_rows_per_forward) bytes - the candidate rows of a pass and,
- * behind them, one candidate list per row.  With it the loop runs the single-stream loop's sampling tail (since round 4):
+ * the algorithm of sd_spec_generate with its own Philox stream.  Sampling parameters, scratch and log: the blocks above.
+ * With a norm_workspace the loop runs the single-stream loop's sampling tail (since round 4):
  * the draft head leaves tile maxima and clears the streams' probability rows, the target rows come back with candidate
  * lists, accept scan + residual / bonus sample are one launch on them - bit-equal to the dense kernels named above, which
  * remain the path without a workspace, with more streams than one verify pass holds, and under SD_BATCH_FUSED_TAIL=0. */
@@ -564,12 +579,9 @@ typedef struct {
     int32_t *acc_len_out;
     float *p_at_out, *q_at_out;
 } sd_batch_stream;
-int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, float temperature, int top_k, float top_p,
-                           int V, long ld, int eos_token_id, uint64_t random_seed, const float *r_const,
-                           int draft_norm_mode, int target_norm_mode, float *draft_logits, long ld_draft_logits,
-                           float *target_logits, long ld_target_logits, void *norm_workspace, int max_rows_per_forward,
-                           float *verify_ms_out, int32_t *verify_streams_out, float *verify_ctx_out, int max_iters_log,
-                           int *n_iters_out, int *err_out, void *stream);
+int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
+                           uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log,
+                           void *stream);
 /* Continuous batching for the lock-step loop: any number of prompts share `n_slots` (1..16) slots.  A slot is an
  * sd_batch_stream of which the caller fills the device side only - the two sessions, the token buffer (slot_cap ints), the
  * probability arenas, the error words and the consecutive result blocks; the arenas and sessions hold slot_cap positions,
@@ -582,7 +594,7 @@ int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, f
  * it decodes from the first boundary at which both models hold L-1 positions (L = 1: at once), on Philox stream (seed, 0).
  * A prompt with L >= T is finished at admission.  While no stream is active (the start of the call, or every stream ending
  * at once) the joiners of all slots are prefilled by sd_batch_prefill passes instead.  Each prompt runs exactly the algorithm
- * of sd_spec_generate; everything else - arguments, statistics, *err_out, the sampling tail - is sd_spec_batch_generate's.
+ * of sd_spec_generate; everything else - the blocks, statistics, log->err, the sampling tail - is sd_spec_batch_generate's.
  * Per prompt: its tokens (pinned host, L ints), L, the length T to reach, the EOS count of the prompt, the seed, the host
  * token buffer (>= T + gamma + 1 ints, holding the prompt) and the per-iteration logs; out: len, calls, admit_iter (the
  * first iteration it decodes in) and finish_iter (its last; both the boundary's iteration number for a prompt that never
@@ -598,12 +610,9 @@ typedef struct {
     int32_t len, calls, admit_iter, finish_iter;
 } sd_queue_prompt;
 int sd_spec_queue_generate(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
-                           int prefill_chunk, int gamma, float temperature, int top_k, float top_p, int V, long ld,
-                           int eos_token_id, uint64_t random_seed, const float *r_const, int draft_norm_mode,
-                           int target_norm_mode, float *draft_logits, long ld_draft_logits, float *target_logits,
-                           long ld_target_logits, void *norm_workspace, int max_rows_per_forward, float *verify_ms_out,
-                           int32_t *verify_streams_out, float *verify_ctx_out, int max_iters_log, int *n_iters_out,
-                           int *passes_out, int *err_out, void *stream);
+                           int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
+                           const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log, int *passes_out,
+                           void *stream);
 /* The passes of one step of that loop (host only; the function the loop calls, once per draft step and once per verify).
  * Inputs: the rows one pass may hold; the logit rows a pass may hold once not every row is one (sd_batch_forward: 64); the
  * active streams' row counts, in order (n_act <= 16), and whether those rows are all logit rows (a verify) or one per
@@ -645,13 +654,9 @@ int sd_session_copy_kv(const sd_session *src, const sd_kv_copy_item *items, int 
  * passes_out (6 ints, may be NULL): the 4 of sd_spec_queue_generate, then the target rows forwarded for prompts inside the
  * call, then the KV rows copied per model, summed over the prompts. */
 int sd_spec_queue_generate_shared(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
-                                  int prefill_chunk, int gamma, float temperature, int top_k, float top_p, int V, long ld,
-                                  int eos_token_id, uint64_t random_seed, const float *r_const, int draft_norm_mode,
-                                  int target_norm_mode, float *draft_logits, long ld_draft_logits, float *target_logits,
-                                  long ld_target_logits, void *norm_workspace, int max_rows_per_forward, float *verify_ms_out,
-                                  int32_t *verify_streams_out, float *verify_ctx_out, int max_iters_log, int *n_iters_out,
-                                  int *passes_out, int *err_out, void *stream, sd_session *donor_draft,
-                                  sd_session *donor_target, int shared_rows);
+                                  int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
+                                  const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log, int *passes_out,
+                                  void *stream, sd_session *donor_draft, sd_session *donor_target, int shared_rows);
 /* The whole loop of multi_speculative_sampling(strategy="iid") (speculative_sampling.py:1379-1716) for the device-RNG mode,
  * no interpreter between iterations.  `width` replicas, each with its own sessions, token buffer and probability arenas;
  * per iteration: gamma draft steps (one pass over the draft weights for all replicas each, sampled straight into
@@ -660,31 +665,25 @@ int sd_spec_queue_generate_shared(sd_batch_stream *slots, int n_slots, int slot_
  * dev_block (device) / host_block (pinned host), sd_spec_multi_block_bytes(width, gamma) bytes each: the sd_multi_result
  * followed by the iteration's error words, int32 [width][3*gamma+1] (per replica: gamma draft norm words, gamma draft
  * sample words, gamma+1 target norm words); the caller zeroes dev_block once.
- * Philox position (*seed_io, *draw_io), advanced per iteration exactly as the Python loop advances it: width draws per
- * draft step (replica w of step i: draw + i*width + w), width draws skipped for the target's discarded sample, then -
- * after a restart at (random_seed, 0) when random_seed != 0, in which case the scan reads r_const (width*gamma device
- * floats) instead - width*gamma uniforms, then one resample draw.
- * host_seq (host int32, capacity >= T + gamma + 1) holds the *len_io tokens so far and receives the new ones; the loop
- * ends when it holds T tokens, when more than ori_eos_cnt EOS are in it (the caller cuts), after max_iters iterations, or
- * on an error: *err_out 1 = 'prob error' (a draft sample word, or the resample: then the accepted drafts ARE appended, as
- * the reference has already cut its output there), 2 = 'norm logits error'.  Per iteration i < *n_iters_out:
- * acc_len_out[i] (-1 for an iteration that ended on an error word: it counts as a call, its scan was not read), p_at_out / q_at_out[i*width*gamma ..] ([w][j], gamma columns), draft_ms_out / target_ms_out[i] (HIP
- * events; any of the five may be NULL).  Limits: width <= 16, gamma <= 16, 2*width <= max_rows_per_forward (a draft
- * step may carry two rows per replica); a violation returns SD_ERR_INVALID before anything is launched. */
+ * `seq` is the sequence's sd_seq_state, sampling / scratch the blocks above.  Its Philox position is advanced per iteration
+ * exactly as the Python loop advances it: width draws per draft step (replica w of step i: draw + i*width + w), width draws
+ * skipped for the target's discarded sample, then - after a restart at (random_seed, 0) when random_seed != 0, in which case
+ * the scan reads r_const (width*gamma device floats) instead - width*gamma uniforms, then one resample draw.
+ * The loop ends as sd_seq_state says (on a new EOS the caller cuts), or on an error: seq->err 1 = 'prob error' (a draft
+ * sample word, or the resample: then the accepted drafts ARE appended, as the reference has already cut its output there),
+ * 2 = 'norm logits error'.  acc_len_out[i] is -1 for an iteration that ended on an error word (it counts as a call, its scan
+ * was not read); p_at_out / q_at_out[i*width*gamma ..] are [w][j], gamma columns; the two times are HIP events.
+ * Limits: width <= 16, gamma <= 16, 2*width <= max_rows_per_forward (a draft step may carry two rows per replica); a
+ * violation returns SD_ERR_INVALID before anything is launched. */
 typedef struct {
     sd_session *draft, *target;
     int32_t *seq;                 /* device int32, seq_cap entries */
     float *q_hist, *p_hist;       /* probability arenas by absolute position, row stride ld */
 } sd_multi_replica;
 size_t sd_spec_multi_block_bytes(int width, int gamma);
-int sd_spec_multi_generate(const sd_multi_replica *reps, int width, int gamma, float temperature, int top_k, float top_p,
-                           int V, long ld, int seq_cap, int draft_norm_mode, int target_norm_mode, float *draft_logits,
-                           long ld_draft_logits, float *target_logits, long ld_target_logits, void *norm_workspace,
-                           int max_rows_per_forward, void *dev_block, void *host_block, int32_t *host_seq, int *len_io,
-                           int T, int eos_token_id, int ori_eos_cnt, uint64_t *seed_io, uint64_t *draw_io,
-                           uint64_t random_seed, const float *r_const, int *draft_len_io, int *target_len_io,
-                           int max_iters, int32_t *acc_len_out, float *p_at_out, float *q_at_out, float *draft_ms_out,
-                           float *target_ms_out, int *n_iters_out, int *err_out, void *stream);
+int sd_spec_multi_generate(const sd_multi_replica *reps, int width, int gamma, int seq_cap, const sd_sampling *sampling,
+                           uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch, void *dev_block,
+                           void *host_block, sd_seq_state *seq, void *stream);
 /* Autoregressive sampling (reference autoregressive_sampling.py:9-61) of up to 16 independent streams in lock-step, no
  * interpreter between steps.  Per step: the uncached rows seq[cache_len .. len) of every stream that is not done go through
  * ONE sd_batch_forward; one sd_norm_batch with sample = 1 (on the head's tile maxima where the lock-step draft steps use
@@ -701,10 +700,10 @@ int sd_spec_multi_generate(const sd_multi_replica *reps, int width, int gamma, f
  * sd_session_forward callers do); with more streams every one arrives with cache_len == len - 1 (sd_batch_prefill).
  * dev_block (device) / host_block (pinned host): sd_ar_block_bytes(n_streams) bytes each = 8 * n_streams rounded up to a
  * multiple of 16 (0 outside 1..16 streams).  norm_workspace: sd_norm_workspace_bytes(n_streams) bytes, or NULL.
- * step_ms_out / step_streams_out (host, max_steps_log entries, may be NULL): HIP-event time of each step and the streams in it.
- * An error word ends the loop after that step, whose tokens are not committed: *err_out 2 = 'norm logits error' (a norm
+ * sampling, head (the model's logit rows and norm mode) and log: the blocks above.
+ * An error word ends the loop after that step, whose tokens are not committed: log->err 2 = 'norm logits error' (a norm
  * word, looked at first: the reference normalises before it samples, and the fused sampler sets both words on a row it
- * cannot normalise), 1 = 'prob error' (a sample word alone); *n_steps_out counts that step.
+ * cannot normalise), 1 = 'prob error' (a sample word alone); log->n_steps counts that step.
  * Limits: n_streams in 1..16 and <= sd_model_max_pass_rows, one model behind all sessions; a violation returns
  * SD_ERR_INVALID before anything is launched. */
 typedef struct {
@@ -718,10 +717,8 @@ typedef struct {
     int32_t done, steps;
 } sd_ar_stream;
 size_t sd_ar_block_bytes(int n_streams);
-int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, float temperature, int top_k, float top_p, int V, long ld,
-                         int eos_token_id, int norm_mode, float *logits, long ld_logits, void *norm_workspace,
-                         void *dev_block, void *host_block, float *step_ms_out, int32_t *step_streams_out,
-                         int max_steps_log, int *n_steps_out, int *err_out, void *stream);
+int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
+                         void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream);
 /* HIP-event timing of the draft phase and the target (verify) phase of the last iteration, on the launch stream. */
 int sd_spec_timing(sd_spec *sp, int on);
 int sd_spec_last_times(sd_spec *sp, float *draft_ms, float *target_ms);

@@ -88,6 +88,37 @@ class SdArStream(C.Structure):
                 ("seed", C.c_uint64), ("draw", C.c_uint64), ("done", C.c_int32), ("steps", C.c_int32)]
 
 
+class SdSampling(C.Structure):
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("V", C.c_int32), ("ld", C.c_long),
+                ("eos_token_id", C.c_int32)]
+
+
+class SdHeadScratch(C.Structure):
+    _fields_ = [("logits", C.c_void_p), ("ld_logits", C.c_long), ("norm_mode", C.c_int32)]
+
+
+class SdSpecScratch(C.Structure):
+    _fields_ = [("draft", SdHeadScratch), ("target", SdHeadScratch), ("norm_workspace", C.c_void_p),
+                ("max_rows_per_forward", C.c_int32)]
+
+
+class SdLockstepLog(C.Structure):
+    _fields_ = [("verify_ms_out", C.c_void_p), ("verify_streams_out", C.c_void_p), ("verify_ctx_out", C.c_void_p),
+                ("max_iters_log", C.c_int32), ("n_iters", C.c_int32), ("err", C.c_int32)]
+
+
+class SdSeqState(C.Structure):
+    _fields_ = [("host_seq", C.c_void_p), ("len", C.c_int32), ("T", C.c_int32), ("ori_eos_cnt", C.c_int32),
+                ("draft_len", C.c_int32), ("target_len", C.c_int32), ("seed", C.c_uint64), ("draw", C.c_uint64),
+                ("max_iters", C.c_int32), ("acc_len_out", C.c_void_p), ("p_at_out", C.c_void_p), ("q_at_out", C.c_void_p),
+                ("draft_ms_out", C.c_void_p), ("target_ms_out", C.c_void_p), ("n_iters", C.c_int32), ("err", C.c_int32)]
+
+
+class SdArLog(C.Structure):
+    _fields_ = [("step_ms_out", C.c_void_p), ("step_streams_out", C.c_void_p), ("max_steps_log", C.c_int32),
+                ("n_steps", C.c_int32), ("err", C.c_int32)]
+
+
 class SdBatchItem(C.Structure):
     _fields_ = [("session", C.c_void_p), ("seq", C.c_void_p), ("pos0", C.c_int32), ("n_new", C.c_int32),
                 ("n_logits", C.c_int32)]
@@ -122,8 +153,19 @@ class SdModelWeights(C.Structure):
                 ("norm2_b", _VPP)]
 
 
+# every struct include/specdec.h declares, by its C name
+C_STRUCTS = {"sd_accept_result": SdAcceptResult, "sd_norm_row": SdNormRow, "sd_accept_item": SdAcceptItem,
+             "sd_multi_result": SdMultiResult, "sd_multi_item": SdMultiItem, "sd_multi_adopt_item": SdMultiAdoptItem,
+             "sd_multi_replica": SdMultiReplica, "sd_batch_stream": SdBatchStream, "sd_queue_prompt": SdQueuePrompt,
+             "sd_queue_pass": SdQueuePass, "sd_queue_chunk": SdQueueChunk, "sd_kv_copy_item": SdKvCopyItem,
+             "sd_ar_stream": SdArStream, "sd_sampling": SdSampling, "sd_head_scratch": SdHeadScratch,
+             "sd_spec_scratch": SdSpecScratch, "sd_lockstep_log": SdLockstepLog, "sd_seq_state": SdSeqState,
+             "sd_ar_log": SdArLog, "sd_batch_item": SdBatchItem, "sd_model_config": SdModelConfig,
+             "sd_gemm_route_info": SdGemmRouteInfo, "sd_model_weights": SdModelWeights}
+
 # every symbol include/specdec.h declares: (name, restype, argtypes)
 _F, _I, _L, _U64 = C.c_float, C.c_int, C.c_long, C.c_uint64
+_P = C.POINTER
 SYMBOLS = [
     ("sd_version", _I, []),
     ("sd_last_error", C.c_char_p, []),
@@ -138,9 +180,8 @@ SYMBOLS = [
     ("sd_multi_accept_resample", _I, [C.POINTER(SdMultiItem), _I, _L, _I, _I, _I, _VP, _U64, _U64, _U64, _VP, _I, _VP]),   # internal
     ("sd_multi_adopt", _I, [C.POINTER(SdMultiAdoptItem), _I, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP]),
     ("sd_spec_multi_block_bytes", C.c_size_t, [_I, _I]),
-    ("sd_spec_multi_generate", _I, [C.POINTER(SdMultiReplica), _I, _I, _F, _I, _F, _I, _L, _I, _I, _I, _VP, _L, _VP, _L, _VP, _I,
-                                    _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _U64, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP,
-                                    _VP, _VP, _VP]),
+    ("sd_spec_multi_generate", _I, [_P(SdMultiReplica), _I, _I, _I, _P(SdSampling), _U64, _VP, _P(SdSpecScratch), _VP, _VP,
+                                    _P(SdSeqState), _VP]),
     ("sd_sample", _I, [_VP, _I, _VP, _U64, _U64, _VP, _VP, _I, _VP]),
     ("sd_philox_exp", _I, [_U64, _U64, _I, _VP, _VP]),
     ("sd_philox_uniform", _I, [_U64, _U64, _I, _VP, _VP]),
@@ -183,21 +224,17 @@ SYMBOLS = [
     ("sd_norm_probs_debug", _I, [_VP, _I, _I, _L, _F, _I, _F, _I, _VP, _L, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _U64, _U64,
                                  _VP, _VP, _VP]),                                     # test hook
     ("sd_accept_resample_batch", _I, [C.POINTER(SdAcceptItem), _I, _L, _I, _I, _I, _VPP, _VP]),   # internal
-    ("sd_spec_batch_generate", _I, [_VP, _I, _I, C.c_float, _I, C.c_float, _I, C.c_long, _I, C.c_uint64, _VP, _I, _I, _VP,
-                                    C.c_long, _VP, C.c_long, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
-    ("sd_spec_queue_generate", _I, [C.POINTER(SdBatchStream), _I, _I, C.POINTER(SdQueuePrompt), _I, _I, _I, _F, _I, _F, _I, _L, _I,
-                                    _U64, _VP, _I, _I, _VP, _L, _VP, _L, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
-    ("sd_spec_queue_generate_shared", _I, [C.POINTER(SdBatchStream), _I, _I, C.POINTER(SdQueuePrompt), _I, _I, _I, _F, _I, _F, _I, _L,
-                                           _I, _U64, _VP, _I, _I, _VP, _L, _VP, _L, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP,
-                                           _VP, _VP, _I]),
+    ("sd_spec_batch_generate", _I, [_P(SdBatchStream), _I, _I, _P(SdSampling), _U64, _VP, _P(SdSpecScratch), _P(SdLockstepLog), _VP]),
+    ("sd_spec_queue_generate", _I, [_P(SdBatchStream), _I, _I, _P(SdQueuePrompt), _I, _I, _I, _P(SdSampling), _U64, _VP,
+                                    _P(SdSpecScratch), _P(SdLockstepLog), _VP, _VP]),
+    ("sd_spec_queue_generate_shared", _I, [_P(SdBatchStream), _I, _I, _P(SdQueuePrompt), _I, _I, _I, _P(SdSampling), _U64, _VP,
+                                           _P(SdSpecScratch), _P(SdLockstepLog), _VP, _VP, _VP, _VP, _I]),
     ("sd_session_copy_kv", _I, [_VP, C.POINTER(SdKvCopyItem), _I, _VP]),
     ("sd_spec_queue_plan", _I, [_I, _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(C.c_int32), _I, _I, _I, C.POINTER(SdQueuePass), _I,
                                 C.POINTER(SdQueueChunk), _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    ("sd_spec_generate", _I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP,
-                              _VP, _VP, _VP]),
+    ("sd_spec_generate", _I, [_VP, _P(SdSeqState), _I, _U64, _VP, _VP, _VP]),
     ("sd_ar_block_bytes", C.c_size_t, [_I]),
-    ("sd_ar_batch_generate", _I, [C.POINTER(SdArStream), _I, _F, _I, _F, _I, _L, _I, _I, _VP, _L, _VP, _VP, _VP, _VP, _VP, _I,
-                                  _VP, _VP, _VP]),
+    ("sd_ar_batch_generate", _I, [_P(SdArStream), _I, _P(SdSampling), _P(SdHeadScratch), _VP, _VP, _VP, _P(SdArLog), _VP]),
     ("sd_batch_forward", _I, [C.POINTER(SdBatchItem), _I, _VP, _L, _VP]),
     ("sd_batch_prefill", _I, [C.POINTER(SdBatchItem), _I, _VP]),
     ("sd_spec_create", _I, [_VP, _VP, _I, _F, _I, _F, _VP, _VP, _VP, _L, _VP, _L, _VP, _L, _VP, _VP, _VP, C.POINTER(_VP)]),

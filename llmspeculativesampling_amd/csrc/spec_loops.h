@@ -284,36 +284,31 @@ static bool commit_result(const sd_accept_result &r, int L, int g, int32_t *host
 }
 
 // The device-RNG loop without the interpreter between iterations (reference speculative_sampling.py:1934-2046).
-extern "C" int sd_spec_generate(sd_spec *sp, int32_t *host_seq, int *len_io, int T, int eos_token_id, int ori_eos_cnt,
-                                uint64_t *seed_io, uint64_t *draw_io, uint64_t random_seed, const float *r_const,
-                                int *draft_len_io, int *target_len_io, sd_accept_result *res_host, int max_iters,
-                                int32_t *acc_len_out, float *p_at_out, float *q_at_out, float *draft_ms_out,
-                                float *target_ms_out, int *n_iters_out, int *err_out, void *stream) {
-    SD_REQUIRE(sp && host_seq && len_io && seed_io && draw_io && draft_len_io && target_len_io && res_host && n_iters_out && err_out,
-               "sd_spec_generate: null argument");
+extern "C" int sd_spec_generate(sd_spec *sp, sd_seq_state *s, int eos_token_id, uint64_t random_seed, const float *r_const,
+                                sd_accept_result *res_host, void *stream) {
+    SD_REQUIRE(sp && s && s->host_seq && res_host, "sd_spec_generate: null argument");
     SD_REQUIRE(!random_seed || r_const, "sd_spec_generate: random_seed needs its uniform (r_const)");
     const int g = sp->gamma;
-    int len = *len_io, draft_len = *draft_len_io, target_len = *target_len_io, iters = 0, eos_total = ori_eos_cnt;
-    uint64_t seed = *seed_io, draw = *draw_io;
-    *err_out = 0;
+    int eos_total = s->ori_eos_cnt;
+    s->n_iters = s->err = 0;
     int rc = SD_OK;
-    while (len < T && iters < max_iters) {
-        const int L = len;
-        const Draws d = next_draws(seed, draw, g, random_seed);
-        seed = d.seed; draw = d.draw;
-        if ((rc = sd_spec_iteration(sp, L, draft_len, target_len, d.seed_draft, d.draft0, d.seed, d.scan0, d.resample, r_const,
+    while (s->len < s->T && s->n_iters < s->max_iters) {
+        const int L = s->len, iters = s->n_iters;
+        const Draws d = next_draws(s->seed, s->draw, g, random_seed);
+        s->seed = d.seed; s->draw = d.draw;
+        if ((rc = sd_spec_iteration(sp, L, s->draft_len, s->target_len, d.seed_draft, d.draft0, d.seed, d.scan0, d.resample, r_const,
                                     res_host, nullptr, stream)) != SD_OK)
             break;
         SD_LOOP_HIP(hipEventRecord(sp->ev_done, (hipStream_t)stream));
         if ((rc = poll_event(sp->ev_done, "sd_spec_generate")) != SD_OK) break;
         const sd_accept_result r = *res_host;
-        if (r.flags & 2) { *err_out = 1; break; }
+        if (r.flags & 2) { s->err = 1; break; }
         if (r.flags & 8) {                                        // which word: a draft sample error, or a norm error
             std::vector<int> ew(3 * g + 1);
             SD_LOOP_HIP(hipMemcpy(ew.data(), sp->err, sizeof(int) * ew.size(), hipMemcpyDeviceToHost));
             bool samp = false;
             for (int i = g; i < 2 * g; ++i) samp = samp || ew[i] != 0;
-            *err_out = samp ? 1 : 2;
+            s->err = samp ? 1 : 2;
             // a NaN row may be the poison of a timed-out in-launch wait (fused_kernels.h / normload_kernels.h): say so
             unsigned wd = 0, wt = 0;
             if (hipMemcpy(&wd, sp->draft->wait_status, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess &&
@@ -322,28 +317,26 @@ extern "C" int sd_spec_generate(sd_spec *sp, int32_t *host_seq, int *len_io, int
                              "sd_session_fused_status): its rows were poisoned with NaN", wd, wt);
             break;
         }
-        if (sp->timing && (draft_ms_out || target_ms_out)) {
+        if (sp->timing && (s->draft_ms_out || s->target_ms_out)) {
             float dms = 0.f, tms = 0.f;
             SD_LOOP_HIP(hipEventElapsedTime(&dms, sp->ev[0], sp->ev[1]));
             SD_LOOP_HIP(hipEventElapsedTime(&tms, sp->ev[2], sp->ev[3]));
-            if (draft_ms_out) draft_ms_out[iters] = dms;
-            if (target_ms_out) target_ms_out[iters] = tms;
+            if (s->draft_ms_out) s->draft_ms_out[iters] = dms;
+            if (s->target_ms_out) s->target_ms_out[iters] = tms;
         }
         const int l = r.n_accepted, n = r.n;
-        if (acc_len_out) acc_len_out[iters] = l;
-        log_ratios(p_at_out, q_at_out, (size_t)iters, g, r.p_at, r.q_at);
-        ++iters;
+        if (s->acc_len_out) s->acc_len_out[iters] = l;
+        log_ratios(s->p_at_out, s->q_at_out, (size_t)iters, g, r.p_at, r.q_at);
+        ++s->n_iters;
         if (!(n >= L - 1 && l >= 0 && l <= g)) {
             sd_set_error("sd_spec_generate: inconsistent result block (n %d, L %d, accepted %d)", n, L, l);
             rc = SD_ERR_INVALID;
             break;
         }
-        commit_result(r, L, g, host_seq, &len, &draft_len, &target_len);      // (flags & 2 left the loop above)
-        for (int i = L; i < len; ++i) eos_total += host_seq[i] == eos_token_id;
-        if (eos_total > ori_eos_cnt) break;                       // the caller cuts after the first new EOS (:2033-2041)
+        commit_result(r, L, g, s->host_seq, &s->len, &s->draft_len, &s->target_len);      // (flags & 2 left the loop above)
+        for (int i = L; i < s->len; ++i) eos_total += s->host_seq[i] == eos_token_id;
+        if (eos_total > s->ori_eos_cnt) break;                    // the caller cuts after the first new EOS (:2033-2041)
     }
-    *len_io = len; *draft_len_io = draft_len; *target_len_io = target_len;
-    *seed_io = seed; *draw_io = draw; *n_iters_out = iters;
     return rc;
 }
 
@@ -501,22 +494,19 @@ static int queue_idle_prefill(PromptQueue &q, sd_batch_stream *slots, const std:
 
 // The lock-step loop of sampling/batch.py in native code (reference algorithm per stream: speculative_sampling.py:1934-2046),
 // with or without a prompt queue behind the streams' slots.
-static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_streams, PromptQueue *q, int gamma, float temperature,
-                         int top_k, float top_p, int V, long ld, int eos_token_id, uint64_t random_seed, const float *r_const,
-                         int draft_norm_mode, int target_norm_mode, float *draft_logits, long ld_draft_logits,
-                         float *target_logits, long ld_target_logits, void *norm_workspace, int max_rows_per_forward,
-                         float *verify_ms_out, int32_t *verify_streams_out, float *verify_ctx_out, int max_iters_log,
-                         int *n_iters_out, int *err_out, void *stream) {
+static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_streams, PromptQueue *q, int gamma, const sd_sampling &sm,
+                         uint64_t random_seed, const float *r_const, const sd_spec_scratch &sc, sd_lockstep_log *log, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     const int g = gamma, n_err = 3 * g + 1;
     // rows per target pass (every verify row is a logit row: sd_model_max_pass_rows, 64 for a model whose lm_head or
     // per-layer GEMMs stop at the streaming kernel) and per draft pass (sd_batch_forward's own limit)
-    const int pass_rows = std::min(max_rows_per_forward, streams[0].target ? streams[0].target->max_pass_rows : SD_MAX_ROWS);
+    const int pass_rows = std::min(sc.max_rows_per_forward, streams[0].target ? streams[0].target->max_pass_rows : SD_MAX_ROWS);
     const int draft_rows = std::min(streams[0].draft ? streams[0].draft->max_rows : SD_MAX_ROWS, SD_MAX_ROWS);
     LoopEvents ev(2, who);
     if (!ev.ok) return SD_ERR_HIP;
-    *err_out = 0;
-    int iters = 0, rc = SD_OK;
+    log->n_iters = log->err = 0;
+    int rc = SD_OK;
+    int &iters = log->n_iters;
     std::vector<sd_batch_stream *> act;
     std::vector<int> Ls, join;
     std::vector<Draws> draws;
@@ -554,7 +544,7 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
     // SD_BATCH_FUSED_TAIL=0: the round-1 sampling tail (logits copy, candidate pass + norm per draft step; dense accept scan +
     // resample) - kept for A/B runs and as the reference the fused tail is tested against; read per call
     const bool fused_tail = !(getenv("SD_BATCH_FUSED_TAIL") && atoi(getenv("SD_BATCH_FUSED_TAIL")) == 0);
-    const bool tiles_ok = head_tiles_ok(top_k, temperature, V, ld);
+    const bool tiles_ok = head_tiles_ok(sm.top_k, sm.temperature, sm.V, sm.ld);
     for (int i = 0; i < n_streams; ++i) {
         streams[i].done = q ? 1 : 0; streams[i].calls = 0;
         if (q) { q->occ[i] = -1; q->joining[i] = false; }
@@ -596,7 +586,7 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
                 rows.assign(m, sd_norm_row{});
                 for (int j = 0; j < m; ++j) {
                     sd_batch_stream &s = *act[a0 + j];
-                    draft_step_rows(items[j], rows[j], s.draft, s.seq, s.q_hist, ld, s.err_words, g, Ls[a0 + j], i, s.draft_len,
+                    draft_step_rows(items[j], rows[j], s.draft, s.seq, s.q_hist, sm.ld, s.err_words, g, Ls[a0 + j], i, s.draft_len,
                                     draws[a0 + j].seed_draft, draws[a0 + j].draft0 + (uint64_t)i);
                     s.draft_len = Ls[a0 + j] + i;
                 }
@@ -608,14 +598,14 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
                 rq.raw = fused_tail;
                 rq.zero_n = fused_tail && tiles_ok && m <= 16 ? m : 0;
                 for (int j = 0; j < rq.zero_n; ++j) rq.zero_ptr[j] = rows[j].probs_out;
-                if ((rc = batch_forward(items.data(), (int)items.size(), draft_logits, ld_draft_logits, &rq, &ho, stream)) != SD_OK) break;
+                if ((rc = batch_forward(items.data(), (int)items.size(), sc.draft.logits, sc.draft.ld_logits, &rq, &ho, stream)) != SD_OK) break;
                 if (m == 0) continue;                             // (joiner rows only)
                 if (fused_tail)
-                    rc = sd_norm_batch_tiles(ho.logits, m, V, ho.ld, temperature, top_k, top_p, ho.round | draft_norm_mode, rows.data(),
-                                             1, norm_workspace, ho.tile_max, nullptr, stream);
+                    rc = sd_norm_batch_tiles(ho.logits, m, sm.V, ho.ld, sm.temperature, sm.top_k, sm.top_p, ho.round | sc.draft.norm_mode,
+                                             rows.data(), 1, sc.norm_workspace, ho.tile_max, nullptr, stream);
                 else
-                    rc = sd_norm_batch(draft_logits, m, V, ld_draft_logits, temperature, top_k, top_p, draft_norm_mode, rows.data(), 1,
-                                       norm_workspace, stream);
+                    rc = sd_norm_batch(sc.draft.logits, m, sm.V, sc.draft.ld_logits, sm.temperature, sm.top_k, sm.top_p, sc.draft.norm_mode,
+                                       rows.data(), 1, sc.norm_workspace, stream);
             }
         }
         if (rc != SD_OK) break;
@@ -624,8 +614,8 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
         if ((rc = plan(1, true)) != SD_OK) break;
         // the residual / bonus sample works on the target rows' candidate lists when ONE verify pass holds all streams (the
         // workspace keeps the lists of one pass)
-        const bool lists_on = fused_tail && norm_workspace && passes[0].n_act == n;
-        char *const list_base = norm_workspace ? (char *)norm_workspace + sd_norm_candrow_bytes(max_rows_per_forward) : nullptr;
+        const bool lists_on = fused_tail && sc.norm_workspace && passes[0].n_act == n;
+        char *const list_base = sc.norm_workspace ? (char *)sc.norm_workspace + sd_norm_candrow_bytes(sc.max_rows_per_forward) : nullptr;
         const size_t list_stride = sd_cand_list_bytes(1);
         list_of.assign(n, nullptr);
         SD_LOOP_HIP(hipEventRecord(ev.t[0], st));
@@ -635,16 +625,16 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
             rows.clear();
             for (int j = 0; j < m; ++j) {
                 sd_batch_stream &s = *act[a0 + j];
-                verify_pass_rows(items[j], rows, s.target, s.seq, s.p_hist, ld, s.err_words, g, Ls[a0 + j], s.target_len);
+                verify_pass_rows(items[j], rows, s.target, s.seq, s.p_hist, sm.ld, s.err_words, g, Ls[a0 + j], s.target_len);
             }
             add_joiners(passes[p], 1);
-            if ((rc = batch_forward(items.data(), (int)items.size(), target_logits, ld_target_logits, nullptr, nullptr, stream)) != SD_OK)
+            if ((rc = batch_forward(items.data(), (int)items.size(), sc.target.logits, sc.target.ld_logits, nullptr, nullptr, stream)) != SD_OK)
                 break;
             if (m == 0) continue;                                 // (joiner rows only)
             // one pass holds every stream: the rows' candidate lists (behind the CandRows of the workspace) serve the
             // residual / bonus sample below
-            rc = sd_norm_batch_tiles(target_logits, (int)rows.size(), V, ld_target_logits, temperature, top_k, top_p, target_norm_mode,
-                                     rows.data(), 0, norm_workspace, nullptr, lists_on ? list_base : nullptr, stream);
+            rc = sd_norm_batch_tiles(sc.target.logits, (int)rows.size(), sm.V, sc.target.ld_logits, sm.temperature, sm.top_k, sm.top_p,
+                                     sc.target.norm_mode, rows.data(), 0, sc.norm_workspace, nullptr, lists_on ? list_base : nullptr, stream);
             if (lists_on) {
                 int r0 = 0;
                 for (int j = 0; j < m; ++j) {                       // stream j's lists are valid when all its gamma + 1 rows are here
@@ -668,19 +658,19 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
             it.philox_seed = draws[j].seed; it.draw_scan = draws[j].scan0; it.draw_resample = draws[j].resample;
             it.res = s.res_dev; it.err_flags = s.err_words; it.n_err = n_err;
         }
-        const int res_mode = target_norm_mode == draft_norm_mode ? target_norm_mode : 0;
-        if (lists_on) rc = sd_accept_resample_batch(aitems.data(), n, ld, V, g, res_mode, list_of.data(), stream);
-        else rc = sd_accept_batch(aitems.data(), n, ld, V, g, res_mode, stream);
+        const int res_mode = sc.target.norm_mode == sc.draft.norm_mode ? sc.target.norm_mode : 0;
+        if (lists_on) rc = sd_accept_resample_batch(aitems.data(), n, sm.ld, sm.V, g, res_mode, list_of.data(), stream);
+        else rc = sd_accept_batch(aitems.data(), n, sm.ld, sm.V, g, res_mode, stream);
         if (rc != SD_OK) break;
         SD_LOOP_HIP(hipMemcpyAsync(streams[0].res_host, streams[0].res_dev, sizeof(sd_accept_result) * (size_t)n_streams,
                                    hipMemcpyDeviceToHost, st));
         SD_LOOP_HIP(hipEventRecord(ev.done, st));
         if ((rc = poll_event(ev.done, who)) != SD_OK) break;
-        if (iters < max_iters_log) {
+        if (iters < log->max_iters_log) {
             float ms = 0.f;
-            if (verify_ms_out && hipEventElapsedTime(&ms, ev.t[0], ev.t[1]) == hipSuccess) verify_ms_out[iters] = ms;
-            if (verify_streams_out) verify_streams_out[iters] = n;
-            if (verify_ctx_out) verify_ctx_out[iters] = (float)(ctx / n + g);
+            if (log->verify_ms_out && hipEventElapsedTime(&ms, ev.t[0], ev.t[1]) == hipSuccess) log->verify_ms_out[iters] = ms;
+            if (log->verify_streams_out) log->verify_streams_out[iters] = n;
+            if (log->verify_ctx_out) log->verify_ctx_out[iters] = (float)(ctx / n + g);
         }
         ++iters;
         bool failed = false;
@@ -693,12 +683,11 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
             ++s.calls;
             commit_result(r, Ls[j], g, s.host_seq, &s.len, &s.draft_len, &s.target_len);
             int eos_total = 0;
-            for (int i = 0; i < s.len; ++i) eos_total += s.host_seq[i] == eos_token_id;
+            for (int i = 0; i < s.len; ++i) eos_total += s.host_seq[i] == sm.eos_token_id;
             if (eos_total > s.ori_eos_cnt) s.done = 1;            // the caller cuts after the first new EOS
         }
-        if (failed) { *err_out = 1; break; }
+        if (failed) { log->err = 1; break; }
     }
-    *n_iters_out = iters;
     return rc;
 }
 
@@ -709,37 +698,28 @@ static int check_result_blocks(const char *who, const sd_batch_stream *streams, 
     return SD_OK;
 }
 
-extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, float temperature, int top_k,
-                                      float top_p, int V, long ld, int eos_token_id, uint64_t random_seed,
-                                      const float *r_const, int draft_norm_mode, int target_norm_mode, float *draft_logits,
-                                      long ld_draft_logits, float *target_logits, long ld_target_logits,
-                                      void *norm_workspace, int max_rows_per_forward, float *verify_ms_out,
-                                      int32_t *verify_streams_out, float *verify_ctx_out, int max_iters_log,
-                                      int *n_iters_out, int *err_out, void *stream) {
-    SD_REQUIRE(streams && n_streams >= 1 && n_streams <= 16 && gamma >= 1 && gamma <= 16 && draft_logits && target_logits &&
-               n_iters_out && err_out, "sd_spec_batch_generate: bad arguments");
+extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
+                                      uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
+                                      sd_lockstep_log *log, void *stream) {
+    SD_REQUIRE(streams && n_streams >= 1 && n_streams <= 16 && gamma >= 1 && gamma <= 16 && sampling && scratch && log &&
+               scratch->draft.logits && scratch->target.logits, "sd_spec_batch_generate: bad arguments");
     SD_REQUIRE(!random_seed || r_const, "sd_spec_batch_generate: random_seed needs its uniform (r_const)");
     if (int rc = check_result_blocks("sd_spec_batch_generate", streams, n_streams); rc != SD_OK) return rc;
-    return lockstep_loop("sd_spec_batch_generate", streams, n_streams, nullptr, gamma, temperature, top_k, top_p, V, ld, eos_token_id,
-                         random_seed, r_const, draft_norm_mode, target_norm_mode, draft_logits, ld_draft_logits, target_logits,
-                         ld_target_logits, norm_workspace, max_rows_per_forward, verify_ms_out, verify_streams_out, verify_ctx_out,
-                         max_iters_log, n_iters_out, err_out, stream);
+    return lockstep_loop("sd_spec_batch_generate", streams, n_streams, nullptr, gamma, *sampling, random_seed, r_const, *scratch, log,
+                         stream);
 }
 
 // The two entry points of the prompt queue: `who` names the one that was called; without donors (shared_rows 0) the loop is
 // sd_spec_queue_generate's, pass for pass.  n_passes_out: how many ints of passes_out the entry point documents.
 static int queue_generate(const char *who, int n_passes_out, sd_session *donor_draft, sd_session *donor_target, int shared_rows,
                           sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
-                          int prefill_chunk, int gamma, float temperature, int top_k, float top_p, int V, long ld,
-                          int eos_token_id, uint64_t random_seed, const float *r_const, int draft_norm_mode,
-                          int target_norm_mode, float *draft_logits, long ld_draft_logits, float *target_logits,
-                          long ld_target_logits, void *norm_workspace, int max_rows_per_forward,
-                          float *verify_ms_out, int32_t *verify_streams_out, float *verify_ctx_out,
-                          int max_iters_log, int *n_iters_out, int *passes_out, int *err_out, void *stream) {
+                          int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed, const float *r_const,
+                          const sd_spec_scratch *scratch, sd_lockstep_log *log, int *passes_out, void *stream) {
     SD_REQUIRE(n_slots >= 1 && n_slots <= 16, "%s: n_slots %d outside 1..16", who, n_slots);
     SD_REQUIRE(gamma >= 1 && gamma <= 16, "%s: gamma %d outside 1..16", who, gamma);
     SD_REQUIRE(n_prompts >= 1 && prefill_chunk >= 0, "%s: n_prompts %d, prefill_chunk %d", who, n_prompts, prefill_chunk);
-    SD_REQUIRE(slots && prompts && draft_logits && target_logits && n_iters_out && err_out, "%s: null argument", who);
+    SD_REQUIRE(slots && prompts && sampling && scratch && log && scratch->draft.logits && scratch->target.logits,
+               "%s: null argument", who);
     SD_REQUIRE(!random_seed || r_const, "%s: random_seed needs its uniform (r_const)", who);
     SD_REQUIRE(shared_rows >= 0 && (shared_rows > 0) == (donor_draft != nullptr) && (shared_rows > 0) == (donor_target != nullptr),
                "%s: shared_rows %d needs both donor sessions, and 0 rows none", who, shared_rows);
@@ -773,10 +753,7 @@ static int queue_generate(const char *who, int n_passes_out, sd_session *donor_d
     PromptQueue q;
     q.prompts = prompts; q.n_prompts = n_prompts; q.prefill_chunk = prefill_chunk;
     q.donor_draft = donor_draft; q.donor_target = donor_target; q.shared_rows = shared_rows;
-    const int rc = lockstep_loop(who, slots, n_slots, &q, gamma, temperature, top_k, top_p, V, ld, eos_token_id,
-                                 random_seed, r_const, draft_norm_mode, target_norm_mode, draft_logits, ld_draft_logits,
-                                 target_logits, ld_target_logits, norm_workspace, max_rows_per_forward, verify_ms_out,
-                                 verify_streams_out, verify_ctx_out, max_iters_log, n_iters_out, err_out, stream);
+    const int rc = lockstep_loop(who, slots, n_slots, &q, gamma, *sampling, random_seed, r_const, *scratch, log, stream);
     if (passes_out) {
         const int v[6] = {q.target_passes, q.draft_passes, q.extra_passes, q.prefill_passes, q.prompt_rows, q.copied_rows};
         for (int i = 0; i < n_passes_out; ++i) passes_out[i] = v[i];
@@ -785,32 +762,20 @@ static int queue_generate(const char *who, int n_passes_out, sd_session *donor_d
 }
 
 extern "C" int sd_spec_queue_generate(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
-                                      int prefill_chunk, int gamma, float temperature, int top_k, float top_p, int V, long ld,
-                                      int eos_token_id, uint64_t random_seed, const float *r_const, int draft_norm_mode,
-                                      int target_norm_mode, float *draft_logits, long ld_draft_logits, float *target_logits,
-                                      long ld_target_logits, void *norm_workspace, int max_rows_per_forward,
-                                      float *verify_ms_out, int32_t *verify_streams_out, float *verify_ctx_out,
-                                      int max_iters_log, int *n_iters_out, int *passes_out, int *err_out, void *stream) {
+                                      int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
+                                      const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log, int *passes_out,
+                                      void *stream) {
     return queue_generate("sd_spec_queue_generate", 4, nullptr, nullptr, 0, slots, n_slots, slot_cap, prompts, n_prompts,
-                          prefill_chunk, gamma, temperature, top_k, top_p, V, ld,
-                          eos_token_id, random_seed, r_const, draft_norm_mode, target_norm_mode, draft_logits, ld_draft_logits,
-                          target_logits, ld_target_logits, norm_workspace, max_rows_per_forward, verify_ms_out, verify_streams_out,
-                          verify_ctx_out, max_iters_log, n_iters_out, passes_out, err_out, stream);
+                          prefill_chunk, gamma, sampling, random_seed, r_const, scratch, log, passes_out, stream);
 }
 
 extern "C" int sd_spec_queue_generate_shared(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
-                                             int prefill_chunk, int gamma, float temperature, int top_k, float top_p, int V, long ld,
-                                             int eos_token_id, uint64_t random_seed, const float *r_const, int draft_norm_mode,
-                                             int target_norm_mode, float *draft_logits, long ld_draft_logits, float *target_logits,
-                                             long ld_target_logits, void *norm_workspace, int max_rows_per_forward,
-                                             float *verify_ms_out, int32_t *verify_streams_out, float *verify_ctx_out,
-                                             int max_iters_log, int *n_iters_out, int *passes_out, int *err_out, void *stream,
-                                             sd_session *donor_draft, sd_session *donor_target, int shared_rows) {
+                                             int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
+                                             const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log,
+                                             int *passes_out, void *stream, sd_session *donor_draft, sd_session *donor_target,
+                                             int shared_rows) {
     return queue_generate("sd_spec_queue_generate_shared", 6, donor_draft, donor_target, shared_rows, slots, n_slots, slot_cap,
-                          prompts, n_prompts, prefill_chunk, gamma, temperature, top_k, top_p, V, ld,
-                          eos_token_id, random_seed, r_const, draft_norm_mode, target_norm_mode, draft_logits, ld_draft_logits,
-                          target_logits, ld_target_logits, norm_workspace, max_rows_per_forward, verify_ms_out, verify_streams_out,
-                          verify_ctx_out, max_iters_log, n_iters_out, passes_out, err_out, stream);
+                          prompts, n_prompts, prefill_chunk, gamma, sampling, random_seed, r_const, scratch, log, passes_out, stream);
 }
 
 // ---- the width-w loop of sampling/multi.py in native code (reference speculative_sampling.py:1379-1716, strategy "iid")
@@ -881,21 +846,17 @@ extern "C" size_t sd_spec_multi_block_bytes(int width, int gamma) {
     return sizeof(sd_multi_result) + sizeof(int32_t) * (size_t)width * (3 * gamma + 1);
 }
 
-extern "C" int sd_spec_multi_generate(const sd_multi_replica *reps, int width, int gamma, float temperature, int top_k,
-                                      float top_p, int V, long ld, int seq_cap, int draft_norm_mode, int target_norm_mode,
-                                      float *draft_logits, long ld_draft_logits, float *target_logits, long ld_target_logits,
-                                      void *norm_workspace, int max_rows_per_forward, void *dev_block, void *host_block,
-                                      int32_t *host_seq, int *len_io, int T, int eos_token_id, int ori_eos_cnt,
-                                      uint64_t *seed_io, uint64_t *draw_io, uint64_t random_seed, const float *r_const,
-                                      int *draft_len_io, int *target_len_io, int max_iters, int32_t *acc_len_out,
-                                      float *p_at_out, float *q_at_out, float *draft_ms_out, float *target_ms_out,
-                                      int *n_iters_out, int *err_out, void *stream) {
+extern "C" int sd_spec_multi_generate(const sd_multi_replica *reps, int width, int gamma, int seq_cap, const sd_sampling *sampling,
+                                      uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch, void *dev_block,
+                                      void *host_block, sd_seq_state *s, void *stream) {
     SD_REQUIRE(width >= 1 && width <= 16, "sd_spec_multi_generate: width %d outside 1..16", width);
     SD_REQUIRE(gamma >= 1 && gamma <= 16, "sd_spec_multi_generate: gamma %d outside 1..16", gamma);
-    SD_REQUIRE(reps && draft_logits && target_logits && dev_block && host_block && host_seq && len_io && seed_io && draw_io &&
-               draft_len_io && target_len_io && n_iters_out && err_out, "sd_spec_multi_generate: null argument");
+    SD_REQUIRE(reps && sampling && scratch && s && scratch->draft.logits && scratch->target.logits && dev_block && host_block &&
+               s->host_seq, "sd_spec_multi_generate: null argument");
+    const sd_sampling &sm = *sampling;
+    const sd_spec_scratch &sc = *scratch;
     SD_REQUIRE(!random_seed || r_const, "sd_spec_multi_generate: random_seed needs its uniforms (r_const)");
-    SD_REQUIRE(V > 0 && ld >= V, "sd_spec_multi_generate: bad V / ld");
+    SD_REQUIRE(sm.V > 0 && sm.ld >= sm.V, "sd_spec_multi_generate: bad V / ld");
     for (int w = 0; w < width; ++w) {
         const sd_multi_replica &r = reps[w];
         SD_REQUIRE(r.draft && r.target && r.seq && r.q_hist && r.p_hist, "sd_spec_multi_generate: replica %d: null pointer", w);
@@ -904,18 +865,18 @@ extern "C" int sd_spec_multi_generate(const sd_multi_replica *reps, int width, i
                    r.target->kv_fp8 == reps[0].target->kv_fp8, "sd_spec_multi_generate: replica %d: sessions differ from replica 0's", w);
     }
     const int g = gamma, W = width, n_err = 3 * g + 1;
-    const int pass_rows = std::min(max_rows_per_forward, reps[0].target->max_pass_rows);
+    const int pass_rows = std::min(sc.max_rows_per_forward, reps[0].target->max_pass_rows);
     SD_REQUIRE(2 * W <= pass_rows && 2 * W <= std::min(reps[0].draft->max_rows, SD_MAX_ROWS),
                "sd_spec_multi_generate: width %d: a draft step may carry 2 rows per replica, a pass holds %d", W, pass_rows);
     SD_REQUIRE(g + 1 <= pass_rows, "sd_spec_multi_generate: gamma %d + 1 verify rows exceed one pass (%d rows)", g, pass_rows);
-    SD_REQUIRE(*len_io >= 1 && T + g + 1 <= seq_cap, "sd_spec_multi_generate: token buffers of %d hold T %d + gamma + 1", seq_cap, T);
+    SD_REQUIRE(s->len >= 1 && s->T + g + 1 <= seq_cap, "sd_spec_multi_generate: token buffers of %d hold T %d + gamma + 1", seq_cap, s->T);
     hipStream_t st = (hipStream_t)stream;
     sd_multi_result *res_dev = (sd_multi_result *)dev_block;
     int *err_dev = (int *)((char *)dev_block + sizeof(sd_multi_result));
     const sd_multi_result *res_host = (const sd_multi_result *)host_block;
     const int *err_host = (const int *)((const char *)host_block + sizeof(sd_multi_result));
     const size_t block_bytes = sd_spec_multi_block_bytes(W, g);
-    const bool timed = draft_ms_out || target_ms_out;
+    const bool timed = s->draft_ms_out || s->target_ms_out;
     LoopEvents ev(timed ? 3 : 0, "sd_spec_multi_generate");
     if (!ev.ok) return SD_ERR_HIP;
     std::vector<sd_batch_item> items;
@@ -926,37 +887,36 @@ extern "C" int sd_spec_multi_generate(const sd_multi_replica *reps, int width, i
         mitems[w].p_hist = reps[w].p_hist; mitems[w].q_hist = reps[w].q_hist; mitems[w].seq = reps[w].seq;
         aitems[w].draft_kv = reps[w].draft->kv; aitems[w].target_kv = reps[w].target->kv; aitems[w].seq = reps[w].seq;
     }
-    const int res_mode = target_norm_mode == draft_norm_mode ? target_norm_mode : 0;
-    int len = *len_io, draft_len = *draft_len_io, target_len = *target_len_io, iters = 0, eos_total = ori_eos_cnt;
-    uint64_t seed = *seed_io, draw = *draw_io;
-    *err_out = 0;
+    const int res_mode = sc.target.norm_mode == sc.draft.norm_mode ? sc.target.norm_mode : 0;
+    int eos_total = s->ori_eos_cnt;
+    s->n_iters = s->err = 0;
     int rc = SD_OK;
-    while (len < T && iters < max_iters) {
-        const int L = len, d_lo = draft_len, t_lo = target_len;
-        if (!(draft_len >= 0 && draft_len < L && target_len >= 0 && target_len < L + g)) {
-            sd_set_error("sd_spec_multi_generate: cache lengths %d / %d do not fit a sequence of %d tokens", draft_len, target_len, L);
+    while (s->len < s->T && s->n_iters < s->max_iters) {
+        const int L = s->len, d_lo = s->draft_len, t_lo = s->target_len, iters = s->n_iters;
+        if (!(d_lo >= 0 && d_lo < L && t_lo >= 0 && t_lo < L + g)) {
+            sd_set_error("sd_spec_multi_generate: cache lengths %d / %d do not fit a sequence of %d tokens", d_lo, t_lo, L);
             rc = SD_ERR_INVALID;
             break;
         }
         // ---- gamma draft steps, all replicas per pass over the draft weights
         if (timed) SD_LOOP_HIP(hipEventRecord(ev.t[0], st));
         for (int i = 0; i < g && rc == SD_OK; ++i) {
-            const uint64_t draw0 = draw;
-            draw += (uint64_t)W;
+            const uint64_t draw0 = s->draw;
+            s->draw += (uint64_t)W;
             items.assign(W, sd_batch_item{});
             rows.assign(W, sd_norm_row{});
             for (int w = 0; w < W; ++w)                            // one shared stream: replica w takes draw0 + w
-                draft_step_rows(items[w], rows[w], reps[w].draft, reps[w].seq, reps[w].q_hist, ld, err_dev + w * n_err, g, L, i,
-                                draft_len, seed, draw0 + (uint64_t)w);
-            if ((rc = batch_forward(items.data(), W, draft_logits, ld_draft_logits, nullptr, nullptr, stream)) != SD_OK) break;
-            rc = sd_norm_batch(draft_logits, W, V, ld_draft_logits, temperature, top_k, top_p, draft_norm_mode, rows.data(), 1,
-                               norm_workspace, stream);
-            draft_len = L + i;
+                draft_step_rows(items[w], rows[w], reps[w].draft, reps[w].seq, reps[w].q_hist, sm.ld, err_dev + w * n_err, g, L, i,
+                                s->draft_len, s->seed, draw0 + (uint64_t)w);
+            if ((rc = batch_forward(items.data(), W, sc.draft.logits, sc.draft.ld_logits, nullptr, nullptr, stream)) != SD_OK) break;
+            rc = sd_norm_batch(sc.draft.logits, W, sm.V, sc.draft.ld_logits, sm.temperature, sm.top_k, sm.top_p, sc.draft.norm_mode,
+                               rows.data(), 1, sc.norm_workspace, stream);
+            s->draft_len = L + i;
         }
         if (rc != SD_OK) break;
         if (timed) SD_LOOP_HIP(hipEventRecord(ev.t[1], st));
         // ---- the target over every replica's uncached rows, whole replicas per pass
-        const int n_new = L + g - target_len;
+        const int n_new = L + g - t_lo;
         const int per_pass = std::max(1, pass_rows / n_new);
         for (int a = 0; a < W && rc == SD_OK; a += per_pass) {
             const int m = std::min(per_pass, W - a);
@@ -964,21 +924,21 @@ extern "C" int sd_spec_multi_generate(const sd_multi_replica *reps, int width, i
             rows.clear();
             for (int j = 0; j < m; ++j) {
                 const sd_multi_replica &r = reps[a + j];
-                verify_pass_rows(items[j], rows, r.target, r.seq, r.p_hist, ld, err_dev + (a + j) * n_err, g, L, target_len);
+                verify_pass_rows(items[j], rows, r.target, r.seq, r.p_hist, sm.ld, err_dev + (a + j) * n_err, g, L, t_lo);
             }
-            if ((rc = batch_forward(items.data(), m, target_logits, ld_target_logits, nullptr, nullptr, stream)) != SD_OK) break;
-            rc = sd_norm_batch(target_logits, (int)rows.size(), V, ld_target_logits, temperature, top_k, top_p, target_norm_mode,
-                               rows.data(), 0, norm_workspace, stream);
+            if ((rc = batch_forward(items.data(), m, sc.target.logits, sc.target.ld_logits, nullptr, nullptr, stream)) != SD_OK) break;
+            rc = sd_norm_batch(sc.target.logits, (int)rows.size(), sm.V, sc.target.ld_logits, sm.temperature, sm.top_k, sm.top_p,
+                               sc.target.norm_mode, rows.data(), 0, sc.norm_workspace, stream);
         }
         if (rc != SD_OK) break;
         if (timed) SD_LOOP_HIP(hipEventRecord(ev.t[2], st));
-        draw += (uint64_t)W;                                      // the target's own sample, drawn and thrown away
+        s->draw += (uint64_t)W;                                   // the target's own sample, drawn and thrown away
         // ---- replica scan + residual / bonus sample (one launch), winner broadcast (one launch), one copy, one wait
-        if (random_seed) { seed = random_seed; draw = 0; }        // the reseed quirk: the stream restarts before the uniforms
-        const uint64_t d_scan = draw;
-        draw += (uint64_t)W * g;
-        const uint64_t d_res = draw++;
-        if ((rc = sd_multi_accept_resample(mitems, W, ld, V, L, g, r_const, seed, d_scan, d_res, res_dev, res_mode, stream)) != SD_OK)
+        if (random_seed) { s->seed = random_seed; s->draw = 0; }   // the reseed quirk: the stream restarts before the uniforms
+        const uint64_t d_scan = s->draw;
+        s->draw += (uint64_t)W * g;
+        const uint64_t d_res = s->draw++;
+        if ((rc = sd_multi_accept_resample(mitems, W, sm.ld, sm.V, L, g, r_const, s->seed, d_scan, d_res, res_dev, res_mode, stream)) != SD_OK)
             break;
         if ((rc = sd_multi_adopt(aitems, W, res_dev, L, g, d_lo, t_lo, kv_planes(reps[0].draft), reps[0].draft->max_seq,
                                  kv_row_bytes(reps[0].draft), kv_planes(reps[0].target), reps[0].target->max_seq,
@@ -994,10 +954,10 @@ extern "C" int sd_spec_multi_generate(const sd_multi_replica *reps, int width, i
             for (int i = 0; i < n_err; ++i)
                 if (err_host[w * n_err + i]) { any = true; samp = samp || (i >= g && i < 2 * g); }
         if (any) {
-            *err_out = samp ? 1 : 2;
-            --draw;
-            if (acc_len_out) acc_len_out[iters] = -1;             // the iteration ran (it counts as a call) but was not scanned
-            ++iters;
+            s->err = samp ? 1 : 2;
+            --s->draw;
+            if (s->acc_len_out) s->acc_len_out[iters] = -1;       // the iteration ran (it counts as a call) but was not scanned
+            ++s->n_iters;
             break;
         }
         const sd_accept_result r = res_host->chosen;
@@ -1012,20 +972,18 @@ extern "C" int sd_spec_multi_generate(const sd_multi_replica *reps, int width, i
             float dms = 0.f, tms = 0.f;
             SD_LOOP_HIP(hipEventElapsedTime(&dms, ev.t[0], ev.t[1]));
             SD_LOOP_HIP(hipEventElapsedTime(&tms, ev.t[1], ev.t[2]));
-            if (draft_ms_out) draft_ms_out[iters] = dms;
-            if (target_ms_out) target_ms_out[iters] = tms;
+            if (s->draft_ms_out) s->draft_ms_out[iters] = dms;
+            if (s->target_ms_out) s->target_ms_out[iters] = tms;
         }
-        if (acc_len_out) acc_len_out[iters] = l;
+        if (s->acc_len_out) s->acc_len_out[iters] = l;
         for (int w = 0; w < W; ++w)                               // (the block keeps 16 ratios per replica)
-            log_ratios(p_at_out, q_at_out, (size_t)iters * W + w, g, res_host->p_at + w * 16, res_host->q_at + w * 16);
-        ++iters;
-        if (!commit_result(r, L, g, host_seq, &len, &draft_len, &target_len)) { *err_out = 1; break; }   // the resample raised
-        if (r.flags & 4) target_len = L + g;
-        for (int i = L; i < len; ++i) eos_total += host_seq[i] == eos_token_id;
-        if (eos_total > ori_eos_cnt) break;                       // the caller cuts after the first new EOS
+            log_ratios(s->p_at_out, s->q_at_out, (size_t)iters * W + w, g, res_host->p_at + w * 16, res_host->q_at + w * 16);
+        ++s->n_iters;
+        if (!commit_result(r, L, g, s->host_seq, &s->len, &s->draft_len, &s->target_len)) { s->err = 1; break; }   // the resample raised
+        if (r.flags & 4) s->target_len = L + g;
+        for (int i = L; i < s->len; ++i) eos_total += s->host_seq[i] == sm.eos_token_id;
+        if (eos_total > s->ori_eos_cnt) break;                    // the caller cuts after the first new EOS
     }
-    *len_io = len; *draft_len_io = draft_len; *target_len_io = target_len;
-    *seed_io = seed; *draw_io = draw; *n_iters_out = iters;
     return rc;
 }
 
@@ -1059,14 +1017,12 @@ extern "C" size_t sd_ar_block_bytes(int n_streams) {
     return ((size_t)n_streams * sizeof(ArSlot) + 15) & ~(size_t)15;
 }
 
-extern "C" int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, float temperature, int top_k, float top_p, int V,
-                                    long ld, int eos_token_id, int norm_mode, float *logits, long ld_logits,
-                                    void *norm_workspace, void *dev_block, void *host_block, float *step_ms_out,
-                                    int32_t *step_streams_out, int max_steps_log, int *n_steps_out, int *err_out,
-                                    void *stream) {
+extern "C" int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
+                                    void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream) {
     SD_REQUIRE(n_streams >= 1 && n_streams <= 16, "sd_ar_batch_generate: n_streams %d outside 1..16", n_streams);
-    SD_REQUIRE(streams && logits && dev_block && host_block && n_steps_out && err_out, "sd_ar_batch_generate: null argument");
-    SD_REQUIRE(V > 0 && ld >= V && temperature != 0.0f, "sd_ar_batch_generate: bad V / ld / temperature");
+    SD_REQUIRE(streams && sampling && head && log && head->logits && dev_block && host_block, "sd_ar_batch_generate: null argument");
+    const sd_sampling &sm = *sampling;
+    SD_REQUIRE(sm.V > 0 && sm.ld >= sm.V && sm.temperature != 0.0f, "sd_ar_batch_generate: bad V / ld / temperature");
     for (int b = 0; b < n_streams; ++b) {
         const sd_ar_stream &s = streams[b];
         SD_REQUIRE(s.session && s.seq && s.probs && s.err_words && s.host_seq, "sd_ar_batch_generate: stream %d: null pointer", b);
@@ -1081,17 +1037,17 @@ extern "C" int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, float 
     SD_REQUIRE(n_streams <= streams[0].session->max_pass_rows, "sd_ar_batch_generate: %d streams exceed one pass (%d rows)", n_streams,
                streams[0].session->max_pass_rows);
     hipStream_t st = (hipStream_t)stream;
-    const bool timed = step_ms_out != nullptr;
+    const bool timed = log->step_ms_out != nullptr;
     LoopEvents ev(timed ? 2 : 0, "sd_ar_batch_generate");
     if (!ev.ok) return SD_ERR_HIP;
-    const bool tiles_ok = head_tiles_ok(top_k, temperature, V, ld);
+    const bool tiles_ok = head_tiles_ok(sm.top_k, sm.temperature, sm.V, sm.ld);
     const ArSlot *slots = (const ArSlot *)host_block;
     std::vector<sd_batch_item> items;
     std::vector<sd_norm_row> rows;
     int act[16];
     for (int b = 0; b < n_streams; ++b) { streams[b].done = 0; streams[b].steps = 0; }
-    *err_out = 0;
-    int steps = 0, rc = SD_OK;
+    log->n_steps = log->err = 0;
+    int rc = SD_OK;
     for (;;) {
         int n = 0;
         for (int b = 0; b < n_streams; ++b) {
@@ -1111,38 +1067,38 @@ extern "C" int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, float 
         rq.zero_n = tiles_ok ? n : 0;
         for (int j = 0; j < n; ++j) {
             sd_ar_stream &s = streams[act[j]];
-            draft_step_rows(items[j], rows[j], s.session, s.seq, s.probs, ld, s.err_words, 1, s.len, 0, s.cache_len, s.seed, s.draw);
+            draft_step_rows(items[j], rows[j], s.session, s.seq, s.probs, sm.ld, s.err_words, 1, s.len, 0, s.cache_len, s.seed, s.draw);
             rq.zero_ptr[j] = rows[j].probs_out;
             tab.seq[act[j]] = s.seq; tab.err[act[j]] = s.err_words; tab.len[act[j]] = s.len;
         }
         if (timed) SD_LOOP_HIP(hipEventRecord(ev.t[0], st));
         if (n_streams == 1 && items[0].n_new > 1)                 // the prompt: chunked like the interpreter loop's first forward
-            rc = feed_rows(items[0].session, items[0].seq, items[0].pos0, items[0].pos0 + items[0].n_new, 1, logits, ld_logits, &rq,
-                           &ho, stream);
+            rc = feed_rows(items[0].session, items[0].seq, items[0].pos0, items[0].pos0 + items[0].n_new, 1, head->logits, head->ld_logits,
+                           &rq, &ho, stream);
         else
-            rc = batch_forward(items.data(), n, logits, ld_logits, &rq, &ho, stream);
+            rc = batch_forward(items.data(), n, head->logits, head->ld_logits, &rq, &ho, stream);
         if (rc != SD_OK) break;
-        if ((rc = sd_norm_batch_tiles(ho.logits, n, V, ho.ld, temperature, top_k, top_p, ho.round | norm_mode, rows.data(), 1,
-                                      norm_workspace, ho.tile_max, nullptr, stream)) != SD_OK)
+        if ((rc = sd_norm_batch_tiles(ho.logits, n, sm.V, ho.ld, sm.temperature, sm.top_k, sm.top_p, ho.round | head->norm_mode,
+                                      rows.data(), 1, norm_workspace, ho.tile_max, nullptr, stream)) != SD_OK)
             break;
         // ---- the hand-off: 8 bytes per stream, one copy, one wait
-        hipLaunchKernelGGL(ar_collect_kernel, dim3(1), dim3(64), 0, st, tab, n_streams, eos_token_id, (ArSlot *)dev_block);
+        hipLaunchKernelGGL(ar_collect_kernel, dim3(1), dim3(64), 0, st, tab, n_streams, sm.eos_token_id, (ArSlot *)dev_block);
         SD_LOOP_HIP(hipGetLastError());
         SD_LOOP_HIP(hipMemcpyAsync(host_block, dev_block, sizeof(ArSlot) * (size_t)n_streams, hipMemcpyDeviceToHost, st));
         if (timed) SD_LOOP_HIP(hipEventRecord(ev.t[1], st));
         SD_LOOP_HIP(hipEventRecord(ev.done, st));
         if ((rc = poll_event(ev.done, "sd_ar_batch_generate")) != SD_OK) break;
-        if (steps < max_steps_log) {
+        if (log->n_steps < log->max_steps_log) {
             float ms = 0.f;
-            if (timed && hipEventElapsedTime(&ms, ev.t[0], ev.t[1]) == hipSuccess) step_ms_out[steps] = ms;
-            if (step_streams_out) step_streams_out[steps] = n;
+            if (timed && hipEventElapsedTime(&ms, ev.t[0], ev.t[1]) == hipSuccess) log->step_ms_out[log->n_steps] = ms;
+            if (log->step_streams_out) log->step_streams_out[log->n_steps] = n;
         }
-        ++steps;
+        ++log->n_steps;
         int flags = 0;
         for (int j = 0; j < n; ++j) flags |= slots[act[j]].flags;
         // the norm word first: the reference normalises before it samples (autoregressive_sampling.py:48-50), and the fused
         // sampler sets both words on a row it cannot normalise
-        if (flags & 3) { *err_out = (flags & 2) ? 2 : 1; break; }
+        if (flags & 3) { log->err = (flags & 2) ? 2 : 1; break; }
         for (int j = 0; j < n; ++j) {
             sd_ar_stream &s = streams[act[j]];
             const ArSlot r = slots[act[j]];
@@ -1152,6 +1108,5 @@ extern "C" int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, float 
             if (r.flags & 4) s.done = 1;                          // the EOS is kept (:55)
         }
     }
-    *n_steps_out = steps;
     return rc;
 }

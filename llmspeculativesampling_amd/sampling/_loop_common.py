@@ -5,6 +5,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from .._lib import SdHeadScratch, SdLockstepLog, SdSampling, SdSeqState, SdSpecScratch
 from ..noise import DeviceNoise, HostTorchNoise
 from .kvcache_model import KVCacheModel
 
@@ -81,6 +82,37 @@ def bind_spec_slot(item, draft, target, seq32, err, res_dev: int, res_host: int)
     item.res_dev, item.res_host = res_dev, res_host
 
 
+def sampling_block(temperature, top_k, top_p, V: int, ld: int, eos_token_id) -> SdSampling:
+    """What a native loop samples with and stops on; ``None`` / 0 switch a filter off, no EOS is -1."""
+    return SdSampling(float(temperature), int(top_k or 0), float(top_p or 0.0), int(V), int(ld),
+                      -1 if eos_token_id is None else int(eos_token_id))
+
+
+def head_scratch(session) -> SdHeadScratch:
+    """One model's logit rows (its session's) and the mode its rows are normalised in."""
+    return SdHeadScratch(session.logits.data_ptr(), session.logits.stride(0), session.model.norm_mode)
+
+
+def spec_scratch(draft_ses, target_ses, norm_ws, per_pass: int) -> SdSpecScratch:
+    """The two heads' scratch, the norm workspace (a tensor or None) and the rows a target pass may carry."""
+    return SdSpecScratch(head_scratch(draft_ses), head_scratch(target_ses), norm_ws.data_ptr() if norm_ws is not None else None,
+                         int(per_pass))
+
+
+class LockstepLog:
+    """The per-iteration verify log of a lock-step loop: the host arrays and the SdLockstepLog that points at them."""
+
+    def __init__(self, n_log: int):
+        self.ms = np.zeros(n_log, dtype=np.float32)
+        self.n = np.zeros(n_log, dtype=np.int32)
+        self.ctx = np.zeros(n_log, dtype=np.float32)
+        self.block = SdLockstepLog(self.ms.ctypes.data, self.n.ctypes.data, self.ctx.ctypes.data, n_log)
+
+    def entries(self) -> list:
+        """(milliseconds, streams, mean context) of every logged iteration."""
+        return [(float(self.ms[i]), int(self.n[i]), float(self.ctx[i])) for i in range(min(self.block.n_iters, len(self.ms)))]
+
+
 def lockstep_result(log: "LoopLog", n_tokens: int, calls: int, eos_token_id, ori_eos: int, device):
     """What a lock-step loop returns for one stream: the (1, len) int64 tokens, cut after the first new EOS, and the
     reference's ``details`` dict (no phase times: the streams share their passes)."""
@@ -110,6 +142,14 @@ class LoopLog:
         ms = (self.draft_ms, self.target_ms)
         return tuple(a.ctypes.data if a is not None else None for a in (self.acc, self.p_at, self.q_at) + ms)
 
+    def seq_state(self, n_tokens: int, T: int, ori_eos_cnt: int, cache_len: tuple, noise, max_iters: int) -> SdSeqState:
+        """The in/out state of the one sequence this log belongs to: ``n_tokens`` of ``T`` so far, the (draft, target) cache
+        lengths, the Philox position of ``noise``; the log pointers are this object's arrays."""
+        st = SdSeqState(host_seq=self.host_seq.ctypes.data, len=n_tokens, T=T, ori_eos_cnt=ori_eos_cnt, draft_len=cache_len[0],
+                        target_len=cache_len[1], seed=noise.seed, draw=noise.draw, max_iters=max_iters)
+        st.acc_len_out, st.p_at_out, st.q_at_out, st.draft_ms_out, st.target_ms_out = self.ptrs()
+        return st
+
     def tokens(self, n: int) -> list:
         return self.host_seq[:n].tolist()
 
@@ -127,7 +167,7 @@ class LoopLog:
 
 
 def raise_loop_error(code: int) -> None:
-    """The native loops' err_out as the reference's exceptions (utils.py:224, :207)."""
+    """The ``err`` a native loop leaves in its log / state block as the reference's exceptions (utils.py:224, :207)."""
     if code == 1:
         raise RuntimeError("prob error")
     if code == 2:

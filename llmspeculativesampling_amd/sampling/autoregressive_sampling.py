@@ -1,15 +1,14 @@
 """Drop-in for reference sampling/autoregressive_sampling.py:8-61 (``autoregressive_sampling``)."""
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 import torch
 
-from .._lib import lib, check, SdArStream
+from .._lib import lib, check, SdArLog, SdArStream
 from ..engine import as_specdec_model, _stream, check_token_ids
-from ._loop_common import make_noise, open_stream, raise_loop_error
+from ._loop_common import head_scratch, make_noise, open_stream, raise_loop_error, sampling_block
 from .kvcache_model import KVCacheModel
 
 
@@ -97,21 +96,18 @@ class ArRun:
         n_log = max(s.T - s.L for s in self.streams) if timing else 0
         ms = np.zeros(max(n_log, 1), dtype=np.float32)
         cnt = np.zeros(max(n_log, 1), dtype=np.int32)
-        n_steps, c_err = C.c_int(0), C.c_int(0)
-        ses0 = kv0._session
-        rc = lib.sd_ar_batch_generate(arr, B, *self.args, self.m.cfg.vocab_size, kv0._probs.stride(0), self.eos, self.m.norm_mode,
-                                      ses0.logits.data_ptr(), ses0.logits.stride(0),
-                                      norm_ws.data_ptr() if norm_ws is not None else None, dev_block.data_ptr(),
-                                      host_block.data_ptr(), ms.ctypes.data if timing else None,
-                                      cnt.ctypes.data if timing else None, n_log, C.byref(n_steps), C.byref(c_err), _stream())
+        log = SdArLog(ms.ctypes.data if timing else None, cnt.ctypes.data if timing else None, n_log)
+        rc = lib.sd_ar_batch_generate(arr, B, sampling_block(*self.args, self.m.cfg.vocab_size, kv0._probs.stride(0), self.eos),
+                                      head_scratch(kv0._session), norm_ws.data_ptr() if norm_ws is not None else None,
+                                      dev_block.data_ptr(), host_block.data_ptr(), log, _stream())
         self.lens = []
         for it, s in zip(arr, self.streams):                      # the state the loop left, also after a failure
             s.kv._session.cache_len = it.cache_len
             s.noise.draw = it.draw
             self.lens.append(it.len)
         check(rc, "sd_ar_batch_generate")
-        raise_loop_error(c_err.value)
-        self.steps = [(float(ms[i]), int(cnt[i])) for i in range(min(n_steps.value, n_log))]
+        raise_loop_error(log.err)
+        self.steps = [(float(ms[i]), int(cnt[i])) for i in range(min(log.n_steps, n_log))]
 
     def tokens(self, i: int) -> np.ndarray:
         return self.streams[i].host[:self.lens[i]]

@@ -22,7 +22,8 @@ import torch
 from .._lib import lib, check, SdAcceptResult, SdBatchStream, SdQueuePrompt
 from ..engine import as_specdec_model, _stream, check_token_ids, same_device, batch_prefill
 from ..noise import DeviceNoise
-from ._loop_common import LoopLog, bind_spec_slot, lockstep_result, open_spec_slot, open_stream, reseed_uniforms
+from ._loop_common import (LockstepLog, LoopLog, bind_spec_slot, lockstep_result, open_spec_slot, open_stream, reseed_uniforms,
+                           sampling_block, spec_scratch)
 from .autoregressive_sampling import ArRun
 from .kvcache_model import KVCacheModel
 
@@ -103,24 +104,16 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
         it.draft_len = it.target_len = s.prompt_len - 1
         it.seed, it.draw = s.noise.seed, s.noise.draw
         it.acc_len_out, it.p_at_out, it.q_at_out = s.log.ptrs()[:3]
-    n_log = max_iters * 2
-    v_ms = np.zeros(n_log, dtype=np.float32)
-    v_n = np.zeros(n_log, dtype=np.int32)
-    v_ctx = np.zeros(n_log, dtype=np.float32)
-    c_iters, c_err = C.c_int(0), C.c_int(0)
+    vlog = LockstepLog(max_iters * 2)
     d0, t0 = streams[0].draft._session, streams[0].target._session
-    check(lib.sd_spec_batch_generate(arr, B, gamma, float(temperature), int(top_k or 0), float(top_p or 0.0), V,
-                                     streams[0].draft._probs.stride(0), int(eos_token_id), int(random_seed or 0),
-                                     r_const.data_ptr() if r_const is not None else None, draft_m.norm_mode,
-                                     target_m.norm_mode, d0.logits.data_ptr(), d0.logits.stride(0), t0.logits.data_ptr(),
-                                     t0.logits.stride(0), norm_ws.data_ptr(), per_pass,
-                                     v_ms.ctypes.data, v_n.ctypes.data, v_ctx.ctypes.data, n_log, C.byref(c_iters),
-                                     C.byref(c_err), cu), "sd_spec_batch_generate")
-    if c_err.value:
+    check(lib.sd_spec_batch_generate(arr, B, gamma, sampling_block(temperature, top_k, top_p, V, streams[0].draft._probs.stride(0),
+                                                                   eos_token_id),
+                                     int(random_seed or 0), r_const.data_ptr() if r_const is not None else None,
+                                     spec_scratch(d0, t0, norm_ws, per_pass), vlog.block, cu), "sd_spec_batch_generate")
+    if vlog.block.err:
         raise RuntimeError("s")
     if _timing is not None:
-        for i in range(min(c_iters.value, n_log)):
-            _timing.setdefault("verify", []).append((_Ms(float(v_ms[i])), None, int(v_n[i]), float(v_ctx[i])))
+        _timing.setdefault("verify", []).extend((_Ms(ms), None, n, ctx) for ms, n, ctx in vlog.entries())
     outs, ds = [], []
     for it, s, pf in zip(arr, streams, prefixes):
         s.noise.seed, s.noise.draw = it.seed, it.draw
@@ -260,16 +253,11 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
     d0, t0 = held[0][0]._session, held[0][1]._session
     per_pass = t0.max_pass_rows
     norm_ws = torch.empty(lib.sd_norm_workspace_bytes(per_pass), dtype=torch.uint8, device=dev)
-    n_log = sum(max(1, m) + 1 for m in budgets)                   # (an iteration has at least one stream in it)
-    v_ms = np.zeros(n_log, dtype=np.float32)
-    v_n = np.zeros(n_log, dtype=np.int32)
-    v_ctx = np.zeros(n_log, dtype=np.float32)
-    c_iters, c_err, passes = C.c_int(0), C.c_int(0), (C.c_int * 6)()
-    args = (slot_arr, S, cap, arr, N, prefill_chunk, gamma, float(temperature), int(top_k or 0), float(top_p or 0.0), V,
-            held[0][0]._probs.stride(0), int(eos_token_id), int(random_seed or 0), r_const.data_ptr() if r_const is not None else None,
-            draft_m.norm_mode, target_m.norm_mode, d0.logits.data_ptr(), d0.logits.stride(0), t0.logits.data_ptr(),
-            t0.logits.stride(0), norm_ws.data_ptr(), per_pass, v_ms.ctypes.data, v_n.ctypes.data, v_ctx.ctypes.data, n_log,
-            C.byref(c_iters), passes, C.byref(c_err), _stream())
+    vlog = LockstepLog(sum(max(1, m) + 1 for m in budgets))       # (an iteration has at least one stream in it)
+    passes = (C.c_int * 6)()
+    args = (slot_arr, S, cap, arr, N, prefill_chunk, gamma,
+            sampling_block(temperature, top_k, top_p, V, held[0][0]._probs.stride(0), eos_token_id), int(random_seed or 0),
+            r_const.data_ptr() if r_const is not None else None, spec_scratch(d0, t0, norm_ws, per_pass), vlog.block, passes, _stream())
     # the donors hold the shared rows a prompt can use: the longest prompt's last token is fed as a decode row like everyone's
     rows = min(shared, max(lens) - 1)
     donors, donor_passes = [None, None], [0, 0]                   # (draft, target) sessions and the passes of their prefill
@@ -285,12 +273,11 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
     check(lib.sd_spec_queue_generate_shared(*args, *[ses.handle if ses else None for ses in donors], rows),
           "sd_spec_queue_generate_shared")
     passes[4] += rows                                             # the donor's target rows are prompt rows too
-    if c_err.value:
+    if vlog.block.err:
         raise RuntimeError("s")
     if _timing is not None:
-        for i in range(min(c_iters.value, n_log)):
-            _timing.setdefault("verify", []).append((_Ms(float(v_ms[i])), None, int(v_n[i]), float(v_ctx[i])))
-        _timing.update(iterations=c_iters.value, target_passes=passes[0] + donor_passes[1], draft_passes=passes[1] + donor_passes[0],
+        _timing.setdefault("verify", []).extend((_Ms(ms), None, n, ctx) for ms, n, ctx in vlog.entries())
+        _timing.update(iterations=vlog.block.n_iters, target_passes=passes[0] + donor_passes[1], draft_passes=passes[1] + donor_passes[0],
                        extra_passes=passes[2] + donor_passes[1], prefill_passes=passes[3] + donor_passes[1],
                        prompt_rows=passes[4], copied_rows=passes[5], admit_iter=[it.admit_iter for it in arr],
                        finish_iter=[it.finish_iter for it in arr])

@@ -31,7 +31,7 @@ from .. import _lib
 from .._lib import lib, check, SdMultiItem, SdMultiReplica, SdMultiResult, SdNormRow, SpecDecError
 from ..engine import as_specdec_model, batch_forward, _stream, MAX_ROWS_PER_FORWARD, check_token_ids, same_device
 from ._loop_common import (LoopLog, accept_rates_f32_zero_q, cut_after_new_eos, details_dict, make_noise, open_stream,
-                           raise_loop_error, reseed_uniforms)
+                           raise_loop_error, reseed_uniforms, sampling_block, spec_scratch)
 
 
 def _copy_positions(dst_ses, src_ses, lo: int, hi: int) -> None:
@@ -87,9 +87,8 @@ def _native_multi_loop(run: _MultiRun, host, cache_len, noise, timed):
     the fused scan + resample launch, the winner broadcast launch, one copy and one stream wait each - and the interpreter
     sees the finished sequence and the per-iteration statistics.  ``cache_len``: positions both models hold of ``host``."""
     drafts, targets, seqs, T, gamma = run.drafts, run.targets, run.seqs, run.T, run.gamma
-    draft_m, target_m, W = drafts[0]._model, targets[0]._model, len(drafts)
+    target_m, W = targets[0]._model, len(drafts)
     V, ld = target_m.cfg.vocab_size, drafts[0]._probs.stride(0)
-    Tk, Kk, Pk = run.sampling
     dev = target_m.device
     d_ses, t_ses = [m._session for m in drafts], [m._session for m in targets]
     reps = (SdMultiReplica * W)()
@@ -101,26 +100,21 @@ def _native_multi_loop(run: _MultiRun, host, cache_len, noise, timed):
     host_block = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
     max_iters = max(1, T - len(host))
     log = LoopLog(host, T + gamma + 2, max_iters, W * gamma, q_fill=0.0, timed=timed)
-    c_len, c_dl, c_tl = C.c_int(len(host)), C.c_int(cache_len), C.c_int(cache_len)
-    c_seed, c_draw = C.c_uint64(noise.seed), C.c_uint64(noise.draw)
-    c_iters, c_err = C.c_int(0), C.c_int(0)
+    st = log.seq_state(len(host), T, int(run.ori_eos), (cache_len, cache_len), noise, max_iters)
     tick = process_time_ns()
-    rc = lib.sd_spec_multi_generate(
-        reps, W, gamma, Tk, Kk, Pk, V, ld, seqs[0].numel(), draft_m.norm_mode, target_m.norm_mode,
-        d_ses[0].logits.data_ptr(), d_ses[0].logits.stride(0), t_ses[0].logits.data_ptr(), t_ses[0].logits.stride(0),
-        run.norm_ws.data_ptr(), t_ses[0].max_pass_rows, dev_block.data_ptr(), host_block.data_ptr(), log.host_seq.ctypes.data,
-        C.byref(c_len), T, int(run.eos_token_id) if run.eos_token_id is not None else -1, int(run.ori_eos), C.byref(c_seed),
-        C.byref(c_draw), int(run.random_seed or 0), run.r_const.data_ptr() if run.r_const is not None else None,
-        C.byref(c_dl), C.byref(c_tl), max_iters, *log.ptrs(), C.byref(c_iters), C.byref(c_err), _stream())
+    rc = lib.sd_spec_multi_generate(reps, W, gamma, seqs[0].numel(), sampling_block(*run.sampling, V, ld, run.eos_token_id),
+                                    int(run.random_seed or 0), run.r_const.data_ptr() if run.r_const is not None else None,
+                                    spec_scratch(d_ses[0], t_ses[0], run.norm_ws, t_ses[0].max_pass_rows), dev_block.data_ptr(),
+                                    host_block.data_ptr(), st, _stream())
     other_time = process_time_ns() - tick                             # host CPU time of the call (enqueue + waits + bookkeeping)
-    noise.seed, noise.draw = c_seed.value, c_draw.value
+    noise.seed, noise.draw = st.seed, st.draw
     for ses in d_ses:
-        ses.cache_len = c_dl.value
+        ses.cache_len = st.draft_len
     for ses in t_ses:
-        ses.cache_len = c_tl.value
-    calls = c_iters.value
+        ses.cache_len = st.target_len
+    calls = st.n_iters
     n_acc = calls - 1 if calls and log.acc[calls - 1] < 0 else calls  # an iteration ended by an error word was not scanned
-    return _MultiResult(rc, c_err.value, log.tokens(c_len.value), log.acc_len(n_acc),
+    return _MultiResult(rc, st.err, log.tokens(st.len), log.acc_len(n_acc),
                         accept_rates_f32_zero_q(*log.ratios(n_acc)), calls, *log.phase_ns(calls), other_time)
 
 

@@ -194,20 +194,16 @@ def _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T,
     r_const = reseed_uniforms(random_seed, gamma, dev)
     max_iters = max(1, T - seq_len0)
     log = LoopLog(host_seq, T + gamma + 2, max_iters, gamma, q_fill=1.0, timed=timed)
-    c_len, c_dl, c_tl = C.c_int(seq_len0), C.c_int(0), C.c_int(0)
-    c_seed, c_draw = C.c_uint64(noise.seed), C.c_uint64(noise.draw)
-    c_iters, c_err = C.c_int(0), C.c_int(0)
+    st = log.seq_state(seq_len0, T, ori_eos_cnt, (0, 0), noise, max_iters)
     try:
         tick = process_time_ns()
-        check(lib.sd_spec_generate(sp, log.host_seq.ctypes.data, C.byref(c_len), T, int(eos_token_id), ori_eos_cnt,
-                                   C.byref(c_seed), C.byref(c_draw), int(random_seed or 0),
-                                   r_const.data_ptr() if r_const is not None else None, C.byref(c_dl), C.byref(c_tl),
-                                   res_host.data_ptr(), max_iters, *log.ptrs(), C.byref(c_iters), C.byref(c_err), _stream()),
+        check(lib.sd_spec_generate(sp, C.byref(st), int(eos_token_id), int(random_seed or 0),
+                                   r_const.data_ptr() if r_const is not None else None, res_host.data_ptr(), _stream()),
               "sd_spec_generate")
         other_time = process_time_ns() - tick            # host CPU time of the loop (enqueue + waits + bookkeeping)
-        noise.seed, noise.draw = c_seed.value, c_draw.value
-        raise_loop_error(c_err.value)
-        calls = c_iters.value
+        noise.seed, noise.draw = st.seed, st.draw
+        raise_loop_error(st.err)
+        calls = st.n_iters
         acc_len = log.acc_len(calls)
         acc_rate = accept_rates_f64(*log.ratios(calls))
         # the reference's approx_time / target_time are host process_time deltas around generate() (:1937-1962);
@@ -220,13 +216,13 @@ def _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T,
                 timing_log["target"].append((float(log.target_ms[i]), Lc + gamma - tl, Lc + gamma))
                 tl = Lc + acc_len[i]                             # n + 1 with n = L + l - 1
                 Lc += acc_len[i] + 1
-        out_tokens = cut_after_new_eos(log.tokens(c_len.value), eos_token_id, ori_eos_cnt)
+        out_tokens = cut_after_new_eos(log.tokens(st.len), eos_token_id, ori_eos_cnt)
     except Exception as e:
         print(e)
         raise RuntimeError("s") from e
     finally:
         lib.sd_spec_destroy(sp)
-    draft._session.cache_len, target._session.cache_len = c_dl.value, c_tl.value
+    draft._session.cache_len, target._session.cache_len = st.draft_len, st.target_len
     out = torch.tensor([out_tokens], dtype=torch.int64, device=prefix.device)
     if details:
         # the verify phase is one fused launch chain (forward + norm_probs, no cache preparation): all of it is model time

@@ -3,64 +3,24 @@ sd_ar_stream, the size of the hand-off block, argument refusal before any launch
 takes.  No GPU needed."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ["sd_ar_block_bytes", "sd_ar_batch_generate"]
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "specdec.h")).read()
-
-
-def _declared_arg_count(name):
-    m = re.search(r"\b(?:int|size_t)\s+" + name + r"\s*\(([^;]*?)\)\s*;", _header(), re.S)
-    assert m, name
-    return len([a for a in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(",") if a.strip()])
-
 
 def test_ar_symbols_are_exported_and_declared():
+    """(Argument counts and classes against the header: test_abi_cpu.py.)"""
     from llmspeculativesampling_amd import _lib
-    bound = {n: (res, args) for n, res, args in _lib.SYMBOLS}
-    raw = C.CDLL(_lib.LIB_PATH)
-    for name in NEW:
-        assert hasattr(raw, name), name
-        fn = getattr(_lib.lib, name)
-        res, args = bound[name]
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-        assert len(args) == _declared_arg_count(name), name
-    assert bound["sd_ar_block_bytes"][0] is C.c_size_t and bound["sd_ar_batch_generate"][0] is C.c_int
+    bound, raw = {n: res for n, res, _ in _lib.SYMBOLS}, C.CDLL(_lib.LIB_PATH)
+    assert hasattr(raw, "sd_ar_block_bytes") and hasattr(raw, "sd_ar_batch_generate")
+    assert bound["sd_ar_block_bytes"] is C.c_size_t and bound["sd_ar_batch_generate"] is C.c_int
 
 
 def test_ar_stream_layout_matches_the_header():
-    """Field order and C types are read from the header's struct; offsets follow from the x86-64 rules (natural alignment)."""
     from llmspeculativesampling_amd import _lib
-    body = re.search(r"typedef struct \{([^}]*)\}\s*sd_ar_stream;", _header(), re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []                                                   # (name, size)
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        ctype, names = re.match(r"((?:const\s+)?[A-Za-z_0-9]+)\s+(.*)", decl, re.S).groups()
-        for nm in names.split(","):
-            nm = nm.strip()
-            ptr = nm.startswith("*")
-            size = 8 if ptr else {"int32_t": 4, "int": 4, "uint64_t": 8, "float": 4}[ctype]
-            fields.append((nm.lstrip("*").strip(), size))
-    assert [f for f, _ in fields] == ["session", "seq", "probs", "err_words", "host_seq", "len", "T", "cache_len", "seed",
-                                      "draw", "done", "steps"]
-    assert [f for f, _ in _lib.SdArStream._fields_] == [f for f, _ in fields]
-    off = 0
-    for name, size in fields:
-        off = (off + size - 1) // size * size
-        d = getattr(_lib.SdArStream, name)
-        assert (d.offset, d.size) == (off, size), name
-        off += size
-    assert C.sizeof(_lib.SdArStream) == (off + 7) // 8 * 8 == 80
+    assert [f for f, _ in _lib.SdArStream._fields_] == ["session", "seq", "probs", "err_words", "host_seq", "len", "T", "cache_len",
+                                                       "seed", "draw", "done", "steps"]
+    assert C.sizeof(_lib.SdArStream) == 80
 
 
 def test_ar_block_bytes():
@@ -71,36 +31,41 @@ def test_ar_block_bytes():
     assert [_lib.lib.sd_ar_block_bytes(n) for n in (-1, 0, 17)] == [0, 0, 0]
 
 
-def _call(lib, table, n, z):
-    buf = (C.c_char * 256)()
-    p = C.addressof(buf)
-    return lib.sd_ar_batch_generate(table, n, 1.0, 20, 0.9, 128, 128, 2, 0, p, 128, None, p, p, None, None, 0, C.byref(z),
-                                    C.byref(z), None)
+def _call(lib, table, n, log, without=""):
+    """sd_ar_batch_generate on placeholder buffers; ``without`` names a block to hand over as NULL."""
+    from llmspeculativesampling_amd import _lib
+    p = C.addressof((C.c_char * 256)())
+    sampling = _lib.SdSampling(temperature=1.0, top_k=20, top_p=0.9, V=128, ld=128, eos_token_id=2)
+    head = _lib.SdHeadScratch(logits=None if without == "logits" else p, ld_logits=128, norm_mode=0)
+    block = None if without == "block" else p
+    return lib.sd_ar_batch_generate(table, n, None if without == "sampling" else sampling, None if without == "head" else head,
+                                    None, block, block, None if without == "log" else log, None)
 
 
 def test_ar_generate_refuses_bad_arguments_before_any_launch():
     from llmspeculativesampling_amd import _lib
     lib = _lib.lib
-    z = C.c_int(-7)
+    log = _lib.SdArLog(n_steps=-7, err=-7)
     table = (_lib.SdArStream * 16)()
     for n in (0, 17, -1):
-        assert _call(lib, table, n, z) == _lib.SD_ERR_INVALID
+        assert _call(lib, table, n, log) == _lib.SD_ERR_INVALID
         assert re.search(r"n_streams -?\d+ outside 1\.\.16", lib.sd_last_error().decode())
-    assert _call(lib, None, 2, z) == _lib.SD_ERR_INVALID and b"sd_ar_batch_generate: null" in lib.sd_last_error()
-    assert lib.sd_ar_batch_generate(table, 2, 1.0, 20, 0.9, 128, 128, 2, 0, None, 128, None, None, None, None, None, 0, None,
-                                    None, None) == _lib.SD_ERR_INVALID
+    assert _call(lib, None, 2, log) == _lib.SD_ERR_INVALID and b"sd_ar_batch_generate: null" in lib.sd_last_error()
+    for block in ("sampling", "head", "logits", "block", "log"):
+        assert _call(lib, table, 2, log, without=block) == _lib.SD_ERR_INVALID
+        assert b"sd_ar_batch_generate: null" in lib.sd_last_error()
     # a table entry without its pointers
-    assert _call(lib, table, 1, z) == _lib.SD_ERR_INVALID and b"stream 0: null pointer" in lib.sd_last_error()
+    assert _call(lib, table, 1, log) == _lib.SD_ERR_INVALID and b"stream 0: null pointer" in lib.sd_last_error()
     # two streams, the second not prefilled up to its last token (placeholder pointers: the refusal comes before any use)
     for it in table[:2]:
         it.session = it.seq = it.probs = it.err_words = it.host_seq = 0x1000
         it.len, it.T, it.cache_len = 9, 12, 8
     table[1].cache_len = 5
-    assert _call(lib, table, 2, z) == _lib.SD_ERR_INVALID
+    assert _call(lib, table, 2, log) == _lib.SD_ERR_INVALID
     assert b"stream 1" in lib.sd_last_error() and b"prefilled" in lib.sd_last_error()
     table[1].cache_len = 9                                        # a cache longer than the sequence
-    assert _call(lib, table, 2, z) == _lib.SD_ERR_INVALID and b"stream 1: cache_len 9 of 9" in lib.sd_last_error()
-    assert z.value == -7                                          # nothing was written, nothing ran
+    assert _call(lib, table, 2, log) == _lib.SD_ERR_INVALID and b"stream 1: cache_len 9 of 9" in lib.sd_last_error()
+    assert (log.n_steps, log.err) == (-7, -7)                     # nothing was written, nothing ran
     with pytest.raises(ValueError, match="sd_ar_batch_generate"):
         _lib.check(_lib.SD_ERR_INVALID, "sd_ar_batch_generate")
 

@@ -1,7 +1,6 @@
 """The native autoregressive loop (sd_ar_batch_generate) on the GPU (`pytest -m gpu`): stream-batched runs against the CPU
 oracle per stream (the device's Philox variates replayed into it, tests/philox_replay.py), the loop's in/out state through a
 direct ctypes call, the single-stream route against the interpreter loop bit for bit in bf16, and the error path."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -113,12 +112,13 @@ class _Direct:
         for it, T in zip(self.arr, Ts):
             it.T = T
         ses, kv = self.kvs[0]._session, self.kvs[0]
-        n_steps, err = C.c_int(-1), C.c_int(-1)
-        rc = self.hip.lib.sd_ar_batch_generate(self.arr, self.B, 1.0, 20, 0.9, self.m.cfg.vocab_size, kv._probs.stride(0), eos,
-                                               self.m.norm_mode, ses.logits.data_ptr(), ses.logits.stride(0),
-                                               kv._norm_ws.data_ptr(), self.dev_block.data_ptr(), self.host_block.data_ptr(),
-                                               None, None, 0, C.byref(n_steps), C.byref(err), _st())
-        return rc, n_steps.value, err.value
+        L = self.hip.L
+        sampling = L.SdSampling(temperature=1.0, top_k=20, top_p=0.9, V=self.m.cfg.vocab_size, ld=kv._probs.stride(0), eos_token_id=eos)
+        head = L.SdHeadScratch(logits=ses.logits.data_ptr(), ld_logits=ses.logits.stride(0), norm_mode=self.m.norm_mode)
+        log = L.SdArLog(n_steps=-1, err=-1)
+        rc = self.hip.lib.sd_ar_batch_generate(self.arr, self.B, sampling, head, kv._norm_ws.data_ptr(), self.dev_block.data_ptr(),
+                                               self.host_block.data_ptr(), log, _st())
+        return rc, log.n_steps, log.err
 
 
 def test_direct_call_state_and_continuation(hip):

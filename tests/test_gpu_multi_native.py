@@ -14,6 +14,7 @@ import torch
 import oracle
 from llmspeculativesampling_amd.config import ModelConfig, load_config
 from llmspeculativesampling_amd.synth import make_state_dict, perturb_state_dict
+from test_multi_native_cpu import multi_blocks
 
 pytestmark = pytest.mark.gpu
 
@@ -495,10 +496,9 @@ def test_native_multi_loop_errors_are_printed_and_swallowed_like_the_python_loop
 def test_native_multi_loop_refuses_bad_width_and_gamma_before_any_launch(hip):
     """width / gamma outside 1..16 and 2 * width beyond a pass: SD_ERR_INVALID, surfaced as SpecDecError; nothing is
     dereferenced or launched (every pointer handed over is null)."""
+    sampling, scratch, state = multi_blocks(hip.L)
     for width, gamma in ((17, 4), (0, 4), (4, 17), (4, 0)):
-        rc = hip.lib.sd_spec_multi_generate(None, width, gamma, 1.0, 0, 0.0, 128, 128, 64, 0, 0, None, 0, None, 0, None, 80,
-                                            None, None, None, None, 10, 2, 0, None, None, 0, None, None, None, 1, None, None,
-                                            None, None, None, None, None, None)
+        rc = hip.lib.sd_spec_multi_generate(None, width, gamma, 64, sampling, 0, None, scratch, None, None, state, None)
         assert rc == hip.L.SD_ERR_INVALID
         with pytest.raises(hip.L.SpecDecError, match="width|gamma"):
             hip.multi._check_native(rc)

@@ -1,7 +1,6 @@
 """CPU-side checks that need no GPU: the C ABI loads and exports every symbol of include/specdec.h, the host
 logic (noise providers, configs, synthetic weights, stream sharding + gather over gloo with world_size 2)."""
 import os
-import re
 import sys
 
 import numpy as np
@@ -12,20 +11,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_library_exports_every_declared_symbol():
-    import ctypes as C
-    hdr = open(os.path.join(ROOT, "include", "specdec.h")).read()
-    declared = set(re.findall(r"\b(sd_[a-z0-9_]+)\s*\(", hdr))
-    types = {"sd_status", "sd_dtype", "sd_arch", "sd_accept_result", "sd_model_config", "sd_model_weights",
-             "sd_model", "sd_session"}
-    declared -= types
-    assert len(declared) >= 18
+    from test_abi_cpu import test_every_declared_symbol_is_bound_and_exported as whole_header_check
+    whole_header_check()
     from llmspeculativesampling_amd import _lib
-    bound = {n for n, _, _ in _lib.SYMBOLS}
-    assert declared == bound, (declared ^ bound)
-    raw = C.CDLL(_lib.LIB_PATH)
-    for name in declared:
-        assert hasattr(raw, name), name
-    assert _lib.lib.sd_version() == 4           # a host-only call: no GPU needed
+    assert _lib.lib.sd_version() == 5           # a host-only call: no GPU needed
 
 
 def test_struct_layouts_match_header():
@@ -483,12 +472,19 @@ def test_new_entry_points_reject_null_arguments_without_a_gpu():
     from llmspeculativesampling_amd import _lib
     lib = _lib.lib
     z = C.c_int(0)
-    assert lib.sd_spec_generate(None, None, None, 8, 2, 0, None, None, 0, None, None, None, None, 1, None, None, None, None,
-                                None, C.byref(z), C.byref(z), None) == _lib.SD_ERR_INVALID
-    assert b"sd_spec_generate" in lib.sd_last_error()
-    assert lib.sd_spec_batch_generate(None, 0, 4, 1.0, 20, 0.9, 32000, 32000, 2, 0, None, 0, 0, None, 0, None, 0, None, 64,
-                                      None, None, None, 0, C.byref(z), C.byref(z), None) == _lib.SD_ERR_INVALID
-    assert b"sd_spec_batch_generate" in lib.sd_last_error()
+    sampling, scratch = _lib.SdSampling(temperature=1.0, top_k=20, top_p=0.9, V=32000, ld=32000, eos_token_id=2), _lib.SdSpecScratch()
+    state, log = _lib.SdSeqState(T=8, max_iters=1, n_iters=-7, err=-7), _lib.SdLockstepLog(n_iters=-7, err=-7)
+    P = 0x1000                                  # a placeholder pointer: the refusal comes before any use
+    for sp, st in ((None, state), (P, None)):   # a null handle, a null state block
+        assert lib.sd_spec_generate(sp, st, 2, 0, None, P, None) == _lib.SD_ERR_INVALID
+        assert b"sd_spec_generate" in lib.sd_last_error()
+    scratch.draft.logits = scratch.target.logits = P
+    streams = (_lib.SdBatchStream * 1)()
+    for args in ((None, 0, sampling, scratch, log), (streams, 1, None, scratch, log), (streams, 1, sampling, None, log),
+                 (streams, 1, sampling, scratch, None)):
+        assert lib.sd_spec_batch_generate(*args[:2], 4, args[2], 0, None, *args[3:], None) == _lib.SD_ERR_INVALID
+        assert b"sd_spec_batch_generate" in lib.sd_last_error()
+    assert (state.n_iters, state.err, log.n_iters, log.err) == (-7, -7, -7, -7)         # nothing was written
     assert lib.sd_accept_resample(None, None, 32000, 32000, None, 4, 4, None, 1, 0, 0, None, None, 0, 0, None, None) \
         == _lib.SD_ERR_INVALID
     assert lib.sd_norm_probs_lists(None, 1, 32000, 32000, 1.0, 20, 0.9, 0, None, 32000, None, None, None, None) \

@@ -124,6 +124,10 @@ def test_loop_log_arrays_and_slices(q_fill, timed):
     else:
         assert log.draft_ms is None and log.target_ms is None and ptrs[3:] == (None, None)
         assert log.phase_ns(3) == (0, 0)
+    st = log.seq_state(3, 9, 1, (2, 1), noise.DeviceNoise(7), 4)   # the sequence's sd_seq_state: state in, this log's arrays out
+    assert (st.host_seq, st.len, st.T, st.ori_eos_cnt, st.draft_len, st.target_len, st.seed, st.draw, st.max_iters, st.n_iters, st.err) \
+        == (log.host_seq.ctypes.data, 3, 9, 1, 2, 1, 7, 0, 4, 0, 0)
+    assert (st.acc_len_out, st.p_at_out, st.q_at_out, st.draft_ms_out, st.target_ms_out) == ptrs
     # what a native loop would leave after two iterations
     log.host_seq[3:8] = [8, 9, 10, 11, 12]
     log.acc[:2] = [3, 1]
@@ -143,6 +147,12 @@ def test_loop_log_phase_ns_truncates_every_entry_before_summing():
     log.target_ms[:] = [1.5, 0.25, 7.0]
     assert log.phase_ns(2) == (2, 1_750_000) and log.phase_ns(3) == (5_000_002, 8_750_000)
     assert log.phase_ns(0) == (0, 0) and all(type(v) is int for v in log.phase_ns(3))
+
+
+def test_sampling_block_writes_the_conventions_once():
+    for args, want in (((1, None, None, 128, 160, None), (1.0, 0, 0.0, 128, 160, -1)), ((0.5, 20, 0.5, 8, 8, 0), (0.5, 20, 0.5, 8, 8, 0))):
+        s = LC.sampling_block(*args)                               # None: that filter is off / there is no EOS; token 0 is an EOS
+        assert (s.temperature, s.top_k, s.top_p, s.V, s.ld, s.eos_token_id) == want
 
 
 def test_raise_loop_error_texts():

@@ -1,30 +1,20 @@
 """Host-side checks of the native width-w loop: ABI of the new entry points, argument refusal, and the rule that decides
 which loop multi_speculative_sampling takes.  No GPU needed."""
 import ctypes as C
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ["sd_multi_accept_resample", "sd_multi_adopt", "sd_spec_multi_block_bytes", "sd_spec_multi_generate"]
 
-
-def _declared_arg_count(name):
-    hdr = open(os.path.join(ROOT, "include", "specdec.h")).read()
-    m = re.search(r"\b(?:int|size_t)\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr, re.S)
-    assert m, name
-    return len([a for a in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(",") if a.strip()])
+def multi_blocks(lib):
+    # the argument blocks of a direct sd_spec_multi_generate call that hands over no buffer at all
+    return (lib.SdSampling(temperature=1.0, top_k=0, top_p=0.0, V=128, ld=128, eos_token_id=2),
+            lib.SdSpecScratch(max_rows_per_forward=80), lib.SdSeqState(T=10, max_iters=1))
 
 
 def test_new_symbols_resolve_with_the_declared_argument_types():
+    """(Argument counts and classes against the header: test_abi_cpu.py.)"""
     from llmspeculativesampling_amd import _lib
-    bound = {n: (res, args) for n, res, args in _lib.SYMBOLS}
-    for name in NEW:
-        fn = getattr(_lib.lib, name)
-        res, args = bound[name]
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-        assert len(args) == _declared_arg_count(name), name
     assert C.sizeof(_lib.SdMultiAdoptItem) == 24 and C.sizeof(_lib.SdMultiReplica) == 40
     assert _lib.lib.sd_spec_multi_block_bytes(4, 4) == C.sizeof(_lib.SdMultiResult) + 4 * 4 * 13
     assert _lib.lib.sd_spec_multi_block_bytes(0, 4) == 0
@@ -33,10 +23,9 @@ def test_new_symbols_resolve_with_the_declared_argument_types():
 def test_native_multi_entry_points_refuse_bad_limits_on_the_host():
     from llmspeculativesampling_amd import _lib
     from llmspeculativesampling_amd.sampling import multi
+    sampling, scratch, state = multi_blocks(_lib)
     for width, gamma in ((17, 4), (0, 4), (4, 17), (4, 0)):
-        rc = _lib.lib.sd_spec_multi_generate(None, width, gamma, 1.0, 0, 0.0, 128, 128, 64, 0, 0, None, 0, None, 0, None, 80,
-                                             None, None, None, None, 10, 2, 0, None, None, 0, None, None, None, 1, None, None,
-                                             None, None, None, None, None, None)
+        rc = _lib.lib.sd_spec_multi_generate(None, width, gamma, 64, sampling, 0, None, scratch, None, None, state, None)
         assert rc == _lib.SD_ERR_INVALID
         assert re.search("width|gamma", _lib.lib.sd_last_error().decode())
         with pytest.raises(_lib.SpecDecError):
@@ -48,6 +37,11 @@ def test_native_multi_entry_points_refuse_bad_limits_on_the_host():
     res = (C.c_char * C.sizeof(_lib.SdMultiResult))()
     assert _lib.lib.sd_multi_adopt(items, 2, C.addressof(res), 6, 4, 5, 5, 1, 8, 16, 1, 16, 16, 32, None) == _lib.SD_ERR_INVALID
     assert "overruns" in _lib.lib.sd_last_error().decode()
+    reps = (_lib.SdMultiReplica * 2)()
+    for blocks in ((None, scratch, state), (sampling, None, state), (sampling, scratch, None)):   # a null block, limits in range
+        assert _lib.lib.sd_spec_multi_generate(reps, 2, 4, 64, blocks[0], 0, None, blocks[1], None, None, blocks[2], None) \
+            == _lib.SD_ERR_INVALID
+        assert b"sd_spec_multi_generate: null argument" in _lib.lib.sd_last_error()
     multi._check_native(0)
 
 

@@ -5,8 +5,6 @@ restatement of the kernel's three sweeps for one row, which must reproduce the s
 import ctypes as C
 import functools
 import math
-import os
-import re
 
 import numpy as np
 import pytest
@@ -16,7 +14,6 @@ import prefill_block_layouts as B
 from prefill_probe_layouts import wide_models  # noqa: F401  (fixture)
 from test_attn_probe_cpu import _check
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["sd_session_prefill_attn_blocked_launches", "sd_prefill_attn_plan", "sd_prefill_attn_route"]
 LDS_MAX = 150 * 1024                                               # PA_LDS_MAX (engine.hip)
 
@@ -122,26 +119,16 @@ def test_route_refuses_bad_arguments():
 
 
 # ----------------------------------------------------------------------------- ABI
-def _declared_arg_count(name):
-    header = open(os.path.join(ROOT, "include", "specdec.h")).read()
-    m = re.search(r"\b(?:int|size_t)\s+" + name + r"\s*\(([^;]*?)\)\s*;", header, re.S)
-    assert m, name
-    return len([a for a in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(",") if a.strip()])
-
-
 def test_blocked_symbols_are_exported_declared_and_bound():
+    """(Argument counts and classes against the header: test_abi_cpu.py.)"""
     from llmspeculativesampling_amd import _lib, engine
-    bound = {n: (res, args) for n, res, args in _lib.SYMBOLS}
+    bound = {n: res for n, res, _ in _lib.SYMBOLS}
     raw = C.CDLL(_lib.LIB_PATH)
     for name in NEW:
-        assert hasattr(raw, name), name
-        fn = getattr(_lib.lib, name)
-        res, args = bound[name]
-        assert res is C.c_int and fn.restype is res and list(fn.argtypes) == list(args)
-        assert len(args) == _declared_arg_count(name), name
+        assert hasattr(raw, name) and bound[name] is C.c_int, name
     assert _lib.lib.sd_session_prefill_attn_blocked_launches(None) == 0        # (a host integer: no session, no count)
     assert callable(engine.Session.prefill_attn_blocked_launches)
-    assert _lib.lib.sd_version() == 4                                          # additions only
+    assert _lib.lib.sd_version() == 5
 
 
 # ----------------------------------------------------------------------------- layouts

@@ -3,20 +3,14 @@ sd_spec_queue_generate, sd_spec_queue_plan): argument refusal before a model is 
 structs, and the invariants of the pass plan - the function the native loop itself calls.  No GPU needed."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["sd_spec_queue_generate", "sd_spec_queue_plan"]
 MIXED = 64                                                        # logit rows of a pass once not every row is one
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "specdec.h")).read()
 
 
 # ----------------------------------------------------------------------------- the Python entry point
@@ -68,71 +62,47 @@ def test_existing_batch_function_still_refuses_a_17th_stream():
 
 
 # ----------------------------------------------------------------------------- ABI
-def _declared_arg_count(name):
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*?)\)\s*;", _header(), re.S)
-    assert m, name
-    return len([a for a in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(",") if a.strip()])
-
-
 def test_queue_symbols_are_exported_and_declared():
+    """(Argument counts and classes of every symbol against the header: test_abi_cpu.py.)"""
     from llmspeculativesampling_amd import _lib
     bound = {n: (res, args) for n, res, args in _lib.SYMBOLS}
     raw = C.CDLL(_lib.LIB_PATH)
     for name in NEW:
-        assert hasattr(raw, name), name
-        fn = getattr(_lib.lib, name)
-        res, args = bound[name]
-        assert res is C.c_int and fn.restype is res and list(fn.argtypes) == list(args)
-        assert len(args) == _declared_arg_count(name), name
-    # the queue's loop takes the batch loop's arguments plus slot_cap, the prompts, their count, prefill_chunk and passes_out
-    assert len(bound["sd_spec_queue_generate"][1]) == len(bound["sd_spec_batch_generate"][1]) + 5
-
-
-def _struct_fields(name):
-    body = re.search(r"typedef struct \{([^}]*)\}\s*" + name + ";", _header(), re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        ctype, names = re.match(r"((?:const\s+)?[A-Za-z_0-9]+)\s+(.*)", decl, re.S).groups()
-        for nm in names.split(","):
-            nm = nm.strip()
-            size = 8 if nm.startswith("*") else {"int32_t": 4, "int": 4, "uint64_t": 8, "float": 4}[ctype]
-            fields.append((nm.lstrip("*").strip(), size))
-    return fields
+        assert hasattr(raw, name) and bound[name][0] is C.c_int, name
+    # the batch loop's arguments - the same three blocks among them - plus slot_cap, prompts, n_prompts, prefill_chunk, passes_out
+    streams, n, *rest, stream = bound["sd_spec_batch_generate"][1]
+    blocks = [C.POINTER(_lib.SdSampling), C.POINTER(_lib.SdSpecScratch), C.POINTER(_lib.SdLockstepLog)]
+    assert [a for a in rest if a in blocks] == blocks
+    assert list(bound["sd_spec_queue_generate"][1]) == [streams, n, C.c_int, C.POINTER(_lib.SdQueuePrompt), C.c_int, C.c_int, *rest,
+                                                        C.c_void_p, stream]
 
 
 @pytest.mark.parametrize("cname,pyname,size", [("sd_queue_prompt", "SdQueuePrompt", 80), ("sd_queue_pass", "SdQueuePass", 16),
                                                ("sd_queue_chunk", "SdQueueChunk", 12)])
 def test_queue_struct_layouts_match_the_header(cname, pyname, size):
-    """Field order and C types are read from the header's struct; offsets follow from the x86-64 rules (natural alignment)."""
     from llmspeculativesampling_amd import _lib
-    cls, fields = getattr(_lib, pyname), _struct_fields(cname)
-    assert [f for f, _ in cls._fields_] == [f for f, _ in fields]
-    off, align = 0, 1
-    for name, sz in fields:
-        off = (off + sz - 1) // sz * sz
-        d = getattr(cls, name)
-        assert (d.offset, d.size) == (off, sz), name
-        off += sz
-        align = max(align, sz)
-    assert C.sizeof(cls) == (off + align - 1) // align * align == size
+    assert _lib.C_STRUCTS[cname] is getattr(_lib, pyname) and C.sizeof(getattr(_lib, pyname)) == size
+
+
+def queue_blocks(p):
+    """The three argument blocks of a queue call on the placeholder buffer ``p``; the log's outputs are preset to -7."""
+    from llmspeculativesampling_amd import _lib
+    head = _lib.SdHeadScratch(logits=p, ld_logits=128, norm_mode=0)
+    return (_lib.SdSampling(temperature=1.0, top_k=20, top_p=0.9, V=128, ld=128, eos_token_id=2),
+            _lib.SdSpecScratch(draft=head, target=head, norm_workspace=None, max_rows_per_forward=64),
+            _lib.SdLockstepLog(max_iters_log=0, n_iters=-7, err=-7))
 
 
 def test_queue_generate_refuses_bad_arguments_before_any_launch():
     from llmspeculativesampling_amd import _lib
     lib = _lib.lib
-    z = C.c_int(-7)
     buf = (C.c_char * 256)()
-    p = C.addressof(buf)
+    sampling, scratch, log = queue_blocks(C.addressof(buf))
     slots = (_lib.SdBatchStream * 16)()
     prompts = (_lib.SdQueuePrompt * 2)()
 
-    def call(n_slots=2, slot_cap=64, n_prompts=2, chunk=0, gamma=4, sl=slots, pr=prompts):
-        return lib.sd_spec_queue_generate(sl, n_slots, slot_cap, pr, n_prompts, chunk, gamma, 1.0, 20, 0.9, 128, 128, 2, 0, None, 0,
-                                          0, p, 128, p, 128, None, 64, None, None, None, 0, C.byref(z), None, C.byref(z), None)
+    def call(n_slots=2, slot_cap=64, n_prompts=2, chunk=0, gamma=4, sl=slots, pr=prompts, sm=sampling, sc=scratch, lg=log):
+        return lib.sd_spec_queue_generate(sl, n_slots, slot_cap, pr, n_prompts, chunk, gamma, sm, 0, None, sc, lg, None, None)
 
     for n in (0, 17, -1):
         assert call(n_slots=n) == _lib.SD_ERR_INVALID and re.search(r"n_slots -?\d+ outside 1\.\.16", lib.sd_last_error().decode())
@@ -142,8 +112,10 @@ def test_queue_generate_refuses_bad_arguments_before_any_launch():
     assert call(chunk=-1) == _lib.SD_ERR_INVALID and b"prefill_chunk -1" in lib.sd_last_error()
     assert call(sl=None) == _lib.SD_ERR_INVALID and b"null argument" in lib.sd_last_error()
     assert call(pr=None) == _lib.SD_ERR_INVALID and b"null argument" in lib.sd_last_error()
+    for block in ("sm", "sc", "lg"):
+        assert call(**{block: None}) == _lib.SD_ERR_INVALID and b"sd_spec_queue_generate: null argument" in lib.sd_last_error()
     assert call() == _lib.SD_ERR_INVALID and b"slot 0: null pointer" in lib.sd_last_error()
-    assert z.value == -7                                          # nothing was written, nothing ran
+    assert (log.n_iters, log.err) == (-7, -7)                     # nothing was written, nothing ran
     with pytest.raises(ValueError, match="sd_spec_queue_generate"):
         _lib.check(_lib.SD_ERR_INVALID, "sd_spec_queue_generate")
 
