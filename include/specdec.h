@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define SD_ABI_VERSION 5
+#define SD_ABI_VERSION 6
 
 typedef enum {
     SD_OK = 0,
@@ -503,29 +503,14 @@ int sd_batch_forward(const sd_batch_item *items, int n_items, float *logits_out,
  * K / V rows are appended to every stream's own arena; nothing else comes back.  All sessions share one model. */
 int sd_batch_prefill(const sd_batch_item *items, int n_items, void *stream);
 
-/* One whole speculative iteration enqueued natively (device-RNG mode), reference speculative_sampling.py:1934-2031:
- * gamma x (draft forward over the uncached rows + sd_norm_sample straight into seq[]), one target forward over its
- * uncached rows + sd_norm_probs of the last gamma+1, sd_accept_scan, residual / bonus sample, then async copies of
- * the result block and of seq[L .. L+gamma+2) into pinned host memory.  Nothing synchronises: the caller waits on
- * the stream once per iteration.  seq: device int32 sequence buffer; q_hist / p_hist: probability arenas indexed by
- * position (row stride ld); *_logits: scratch rows for the heads; err_words: 3*gamma+1 device ints (folded into
- * res.flags bit3 = 'norm logits error' / sample error).  Philox draws: draft step i uses (seed_draft,
- * draw_draft0+i); the accept uniforms (seed_accept, draw_scan0+i) unless r_const (gamma device floats: the
- * random_seed quirk) is given; the resample (seed_accept, draw_resample). */
-typedef struct sd_spec sd_spec;
-int sd_spec_create(sd_session *draft, sd_session *target, int gamma, float temperature, int top_k, float top_p,
-                   int32_t *seq, float *q_hist, float *p_hist, long ld, float *draft_logits, long ld_draft_logits,
-                   float *target_logits, long ld_target_logits, int *err_words, sd_accept_result *res_dev,
-                   void *norm_workspace /* sd_norm_workspace_bytes(gamma+1) bytes or NULL */, sd_spec **out);
-int sd_spec_destroy(sd_spec *sp);
-int sd_spec_iteration(sd_spec *sp, int L, int draft_len, int target_len, uint64_t seed_draft, uint64_t draw_draft0,
-                      uint64_t seed_accept, uint64_t draw_scan0, uint64_t draw_resample, const float *r_const,
-                      sd_accept_result *res_host, int32_t *tok_host /* gamma+2 ids from seq[L], may be NULL */,
-                      void *stream);
 /* ---- Argument blocks of the native loops below: caller-owned host structs, used during the call only.  An entry refuses a
  * NULL block with SD_ERR_INVALID before anything is written or launched.
  * sd_sampling: what every loop samples with and stops on; ld = row stride of the probability arenas.
  * sd_head_scratch: one model's logit rows (scratch for its head) and the SD_NORM_* mode its rows are normalised in.
+ * sd_spec_stream: the device side of ONE stream (the eight leading fields of sd_batch_stream): the two sessions, the device
+ *   int32 token buffer, the probability arenas indexed by position (row stride sd_sampling.ld), 3*gamma+1 device error words
+ *   (gamma draft norm words, gamma draft sample words, gamma+1 target norm words; folded into res.flags bit 3), the device
+ *   result block and its pinned-host copy.
  * sd_spec_scratch: both heads; norm_workspace (device, may be NULL): sd_norm_workspace_bytes(max_rows_per_forward) bytes, the
  *   candidate rows of a pass and, behind them, one candidate list per row; the most rows a target pass may carry.
  * sd_lockstep_log: host arrays of max_iters_log entries (each may be NULL): time of an iteration's verify passes, streams in
@@ -538,6 +523,9 @@ int sd_spec_iteration(sd_spec *sp, int L, int draft_len, int target_len, uint64_
  * sd_ar_log: host arrays of max_steps_log entries (may be NULL): HIP-event time of each step, streams in it.  Out: n_steps, err. */
 typedef struct { float temperature; int32_t top_k; float top_p; int32_t V; long ld; int32_t eos_token_id; } sd_sampling;
 typedef struct { float *logits; long ld_logits; int32_t norm_mode; } sd_head_scratch;
+typedef struct {
+    sd_session *draft, *target; int32_t *seq; float *q_hist, *p_hist; int *err_words; sd_accept_result *res_dev, *res_host;
+} sd_spec_stream;
 typedef struct { sd_head_scratch draft, target; void *norm_workspace; int32_t max_rows_per_forward; } sd_spec_scratch;
 typedef struct { float *verify_ms_out; int32_t *verify_streams_out; float *verify_ctx_out; int32_t max_iters_log, n_iters, err; } sd_lockstep_log;
 typedef struct {
@@ -546,14 +534,21 @@ typedef struct {
     int32_t n_iters, err;
 } sd_seq_state;
 typedef struct { float *step_ms_out; int32_t *step_streams_out; int32_t max_steps_log; int32_t n_steps, err; } sd_ar_log;
-/* The whole loop of speculative_sampling.py:1934-2046 for the device-RNG mode: iterations (sd_spec_iteration + one stream
- * wait each) until the sequence holds T tokens, a new EOS appears (more than ori_eos_cnt of them in total) or an error
- * word is set - no Python between iterations.  `seq`: the sd_seq_state; its Philox position is advanced exactly as the
+/* The whole loop of speculative_sampling.py:1934-2046 for the device-RNG mode, no Python between iterations.  An iteration
+ * (:1934-2031) is gamma x (draft forward over the uncached rows + sd_norm_sample straight into seq[]), one target forward over
+ * its uncached rows + sd_norm_probs of the last gamma+1, sd_accept_scan and the residual / bonus sample (one launch on the
+ * target rows' candidate lists when the workspace holds them), one async copy of the result block to dev->res_host and one
+ * stream wait; iterations run until the sequence holds T tokens, a new EOS appears (more than ori_eos_cnt of
+ * sampling->eos_token_id in total) or an error word is set.  The Philox position of `seq` is advanced exactly as the
  * iteration's draw order prescribes: gamma draft draws, the discarded target sample, gamma uniforms - or, with random_seed
- * != 0, the stream restarted at (random_seed, 0) - and the resample.  gamma p_at / q_at values per iteration; the two times
- * when timing is on (else untouched).  Sampling parameters: sd_spec_create's.  res_host: pinned, for the result block. */
-int sd_spec_generate(sd_spec *sp, sd_seq_state *seq, int eos_token_id, uint64_t random_seed, const float *r_const,
-                     sd_accept_result *res_host, void *stream);
+ * != 0, the stream restarted at (random_seed, 0), the scan then reading r_const (gamma device floats) - and the resample.
+ * gamma p_at / q_at values per iteration; the two phases are timed with HIP events exactly when seq->draft_ms_out or
+ * seq->target_ms_out is set.  Norm modes: scratch->draft / target.norm_mode; the residual runs in the target's mode when both
+ * are equal, else in fp32.  Refused with SD_ERR_INVALID before anything is written or launched, in this order: a NULL block or
+ * a NULL pointer in dev, seq->host_seq or either scratch->*.logits; gamma outside 1..16; random_seed without r_const;
+ * temperature 0; a norm_workspace with max_rows_per_forward < gamma + 1; then sampling->V differing from a model's vocabulary. */
+int sd_spec_generate(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling, const sd_spec_scratch *scratch,
+                     sd_seq_state *seq, uint64_t random_seed, const float *r_const, void *stream);
 /* The stream-batched loop (throughput mode) without the interpreter between iterations: up to 16
  * independent streams decode in lock-step - every draft step one sd_batch_forward + sd_norm_batch over the active
  * streams, every verify one target pass per max_rows_per_forward / (gamma + 1) streams, then sd_accept_batch, one copy of
@@ -719,9 +714,6 @@ typedef struct {
 size_t sd_ar_block_bytes(int n_streams);
 int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
                          void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream);
-/* HIP-event timing of the draft phase and the target (verify) phase of the last iteration, on the launch stream. */
-int sd_spec_timing(sd_spec *sp, int on);
-int sd_spec_last_times(sd_spec *sp, float *draft_ms, float *target_ms);
 
 /* ------------------------------------------------------------------------------------------
  * Tensor parallelism of one decoder over the GPUs of a node (BASELINE config 5: Llama-2-70b, TP = 8 over xGMI).

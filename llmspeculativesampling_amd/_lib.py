@@ -97,6 +97,10 @@ class SdHeadScratch(C.Structure):
     _fields_ = [("logits", C.c_void_p), ("ld_logits", C.c_long), ("norm_mode", C.c_int32)]
 
 
+class SdSpecStream(C.Structure):
+    _fields_ = SdBatchStream._fields_[:8]                  # the device side of one stream, as sd_batch_stream starts
+
+
 class SdSpecScratch(C.Structure):
     _fields_ = [("draft", SdHeadScratch), ("target", SdHeadScratch), ("norm_workspace", C.c_void_p),
                 ("max_rows_per_forward", C.c_int32)]
@@ -159,7 +163,7 @@ C_STRUCTS = {"sd_accept_result": SdAcceptResult, "sd_norm_row": SdNormRow, "sd_a
              "sd_multi_replica": SdMultiReplica, "sd_batch_stream": SdBatchStream, "sd_queue_prompt": SdQueuePrompt,
              "sd_queue_pass": SdQueuePass, "sd_queue_chunk": SdQueueChunk, "sd_kv_copy_item": SdKvCopyItem,
              "sd_ar_stream": SdArStream, "sd_sampling": SdSampling, "sd_head_scratch": SdHeadScratch,
-             "sd_spec_scratch": SdSpecScratch, "sd_lockstep_log": SdLockstepLog, "sd_seq_state": SdSeqState,
+             "sd_spec_stream": SdSpecStream, "sd_spec_scratch": SdSpecScratch, "sd_lockstep_log": SdLockstepLog, "sd_seq_state": SdSeqState,
              "sd_ar_log": SdArLog, "sd_batch_item": SdBatchItem, "sd_model_config": SdModelConfig,
              "sd_gemm_route_info": SdGemmRouteInfo, "sd_model_weights": SdModelWeights}
 
@@ -232,16 +236,11 @@ SYMBOLS = [
     ("sd_session_copy_kv", _I, [_VP, C.POINTER(SdKvCopyItem), _I, _VP]),
     ("sd_spec_queue_plan", _I, [_I, _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(C.c_int32), _I, _I, _I, C.POINTER(SdQueuePass), _I,
                                 C.POINTER(SdQueueChunk), _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    ("sd_spec_generate", _I, [_VP, _P(SdSeqState), _I, _U64, _VP, _VP, _VP]),
+    ("sd_spec_generate", _I, [_P(SdSpecStream), _I, _P(SdSampling), _P(SdSpecScratch), _P(SdSeqState), _U64, _VP, _VP]),
     ("sd_ar_block_bytes", C.c_size_t, [_I]),
     ("sd_ar_batch_generate", _I, [_P(SdArStream), _I, _P(SdSampling), _P(SdHeadScratch), _VP, _VP, _VP, _P(SdArLog), _VP]),
     ("sd_batch_forward", _I, [C.POINTER(SdBatchItem), _I, _VP, _L, _VP]),
     ("sd_batch_prefill", _I, [C.POINTER(SdBatchItem), _I, _VP]),
-    ("sd_spec_create", _I, [_VP, _VP, _I, _F, _I, _F, _VP, _VP, _VP, _L, _VP, _L, _VP, _L, _VP, _VP, _VP, C.POINTER(_VP)]),
-    ("sd_spec_destroy", _I, [_VP]),
-    ("sd_spec_iteration", _I, [_VP, _I, _I, _I, _U64, _U64, _U64, _U64, _U64, _VP, _VP, _VP, _VP]),
-    ("sd_spec_timing", _I, [_VP, _I]),
-    ("sd_spec_last_times", _I, [_VP, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("sd_tp_unique_id", _I, [_VP]),
     ("sd_tp_create_rccl", _I, [_I, _I, _VP, C.POINTER(_VP)]),
     ("sd_tp_create_loopback", _I, [_I, C.POINTER(_VP)]),

@@ -7,6 +7,7 @@
 // One workgroup of 1024 threads (16 waves) owns one vocabulary row: the row is staged once in
 // LDS (V*4 B <= 128 KiB for Llama's V = 32000) and every later pass reads LDS, not HBM.
 #include "common.h"
+#include "sampler_host.h"
 #include <stdlib.h>
 
 #ifdef SD_STAMPS
@@ -1191,11 +1192,10 @@ extern "C" int sd_philox_uniform(uint64_t seed, uint64_t draw_index, int n, floa
 }
 
 int g_norm_tile_threads = 0;                 // (tools/norm_stamps.cpp sweeps it; 0 = 256)
-static int launch_norm(const float *logits, int rows, int V, long ld_in, float temperature, int top_k, float top_p,
-                       int bf16_round_logits, float *probs_out, long ld_out, int *err_flag, bool do_sample,
-                       const float *noise, uint64_t seed, uint64_t draw, int *tok_out, int *samp_err, void *workspace,
-                       void *stream, const NormTab *tabp = nullptr, int filter_only = 0,
-                       const float *tile_max = nullptr, CandList *cl_out = nullptr, int *route = nullptr) {
+// tab (or NULL): the row table of a batched launch.  Its rows sample when the caller said so, a single row when it has a tok_out.
+static int launch_norm(const NormRequest &rq, const NormTab *tabp, void *stream) {
+    const bool do_sample = tabp ? rq.table_sample != 0 : rq.tok_out != nullptr;
+    const int V = rq.V, top_k = rq.top_k;
     NormTab tab = {};
     const int use_tab = tabp != nullptr;
     if (tabp) tab = *tabp;
@@ -1215,33 +1215,34 @@ static int launch_norm(const float *logits, int rows, int V, long ld_in, float t
         attr_set = true;
     }
     // the head already left tile maxima and a cleared output row (EPI_HEAD): no candidate pass over V at all
-    if (tile_max && !(top_k >= 1 && top_k <= 64 && temperature > 0.0f && (V & 15) == 0 && V >= 4096 && V <= 65536 &&
-                      (ld_in & 3) == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0 && !filter_only))
+    const float *tile_max = rq.tile_max;
+    if (tile_max && !(top_k >= 1 && top_k <= 64 && rq.temperature > 0.0f && (V & 15) == 0 && V >= 4096 && V <= 65536 &&
+                      (rq.ld_in & 3) == 0 && (reinterpret_cast<uintptr_t>(rq.logits) & 15) == 0 && !rq.filter_only))
         tile_max = nullptr;
     // two-kernel fast path: the row is cut over NB_SPLIT workgroups first (see norm_cand_kernel)
     CandRow *ws = nullptr;
-    if (!tile_max && workspace && top_k >= 1 && top_k <= 64 && V >= 4096 && (V & 3) == 0 && (ld_in & 3) == 0 && (ld_out & 3) == 0 &&
-        ((V >> 2) + NB_SPLIT - 1) / NB_SPLIT <= 256 * CAND_MAXIT && (reinterpret_cast<uintptr_t>(logits) & 15) == 0 &&
-        (use_tab || (reinterpret_cast<uintptr_t>(probs_out) & 15) == 0)) {
-        ws = static_cast<CandRow *>(workspace);
-        hipLaunchKernelGGL(norm_cand_kernel, dim3(NB_SPLIT, rows), dim3(256), 0, (hipStream_t)stream, logits, ld_in, V,
-                           temperature, top_k, bf16_round_logits, probs_out, ld_out, ws, tab, use_tab);
+    if (!tile_max && rq.workspace && top_k >= 1 && top_k <= 64 && V >= 4096 && (V & 3) == 0 && (rq.ld_in & 3) == 0 &&
+        (rq.ld_out & 3) == 0 && ((V >> 2) + NB_SPLIT - 1) / NB_SPLIT <= 256 * CAND_MAXIT &&
+        (reinterpret_cast<uintptr_t>(rq.logits) & 15) == 0 && (use_tab || (reinterpret_cast<uintptr_t>(rq.probs_out) & 15) == 0)) {
+        ws = static_cast<CandRow *>(rq.workspace);
+        hipLaunchKernelGGL(norm_cand_kernel, dim3(NB_SPLIT, rq.rows), dim3(256), 0, (hipStream_t)stream, rq.logits, rq.ld_in, V,
+                           rq.temperature, top_k, rq.mode, rq.probs_out, rq.ld_out, ws, tab, use_tab);
         SD_LAUNCH_CHECK();
     }
     // with tile maxima the work is a few dozen candidates: 4 waves (cheap barriers), no row staging
     const int nthr = tile_max ? (g_norm_tile_threads > 0 ? g_norm_tile_threads : 256) : NT;
     const int staged_k = tile_max ? 0 : staged;
     const size_t lds_k = tile_max ? base : lds;
-    const float *noise_k = do_sample ? noise : nullptr;
-    int *tok_k = do_sample ? tok_out : nullptr, *serr_k = do_sample ? samp_err : nullptr;
-    const uint64_t seed_k = do_sample ? seed : 0, draw_k = do_sample ? draw : 0;
-    const int filter_k = do_sample ? 0 : filter_only;
+    const float *noise_k = do_sample ? rq.noise : nullptr;
+    int *tok_k = do_sample ? rq.tok_out : nullptr, *serr_k = do_sample ? rq.samp_err : nullptr;
+    const uint64_t seed_k = do_sample ? rq.seed : 0, draw_k = do_sample ? rq.draw : 0;
+    const int filter_k = do_sample ? 0 : rq.filter_only;
 #define NORM_LAUNCH(SAMPLE, ROUTED)                                                                                        \
-    hipLaunchKernelGGL((norm_probs_kernel<SAMPLE, ROUTED>), dim3(rows), dim3(nthr), lds_k, (hipStream_t)stream, logits,     \
-                       ld_in, V, temperature, top_k, top_p, bf16_round_logits, staged_k, probs_out, ld_out, err_flag,      \
+    hipLaunchKernelGGL((norm_probs_kernel<SAMPLE, ROUTED>), dim3(rq.rows), dim3(nthr), lds_k, (hipStream_t)stream, rq.logits, \
+                       rq.ld_in, V, rq.temperature, top_k, rq.top_p, rq.mode, staged_k, rq.probs_out, rq.ld_out, rq.err,     \
                        noise_k, seed_k, draw_k, tok_k, serr_k, (const CandRow *)ws, tab, use_tab, filter_k, tile_max,      \
-                       cl_out, route)
-    if (route) {                                                  // test hook: the instantiations that record the route
+                       static_cast<CandList *>(rq.lists), rq.route)
+    if (rq.route) {                                               // test hook: the instantiations that record the route
         if (do_sample) NORM_LAUNCH(true, true); else NORM_LAUNCH(false, true);
     } else {
         if (do_sample) NORM_LAUNCH(true, false); else NORM_LAUNCH(false, false);
@@ -1251,16 +1252,14 @@ static int launch_norm(const float *logits, int rows, int V, long ld_in, float t
     return SD_OK;
 }
 
-// internal (spec_loops.h, sd_spec_iteration): norm_logits of `rows` logit rows whose head left tile maxima (or NULL) and
-// cleared probs_out; with tok_out != NULL also the sample that follows a draft step (rows == 1)
-int sd_norm_rows_with_tiles(const float *logits, int rows, int V, long ld_in, float temperature, int top_k, float top_p,
-                            int bf16_round_logits, float *probs_out, long ld_out, int *err_flag, uint64_t seed,
-                            uint64_t draw, int *tok_out, int *samp_err, void *workspace, const float *tile_max,
-                            void *stream, void *cand_lists) {
-    return launch_norm(logits, rows, V, ld_in, temperature, top_k, top_p, bf16_round_logits, probs_out, ld_out, err_flag,
-                       tok_out != nullptr, nullptr, seed, draw, tok_out, samp_err, workspace, stream, nullptr, 0, tile_max,
-                       static_cast<CandList *>(cand_lists));
+// The input rows and the parameters of a request, as the public entries take them; the caller names its outputs and options
+static NormRequest norm_input(const float *logits, int rows, int V, long ld_in, float temperature, int top_k, float top_p, int mode) {
+    NormRequest rq = {};
+    rq.logits = logits; rq.rows = rows; rq.V = V; rq.ld_in = ld_in;
+    rq.temperature = temperature; rq.top_k = top_k; rq.top_p = top_p; rq.mode = mode;
+    return rq;
 }
+int sd_norm_rows_with_tiles(const NormRequest &rq, void *stream) { return launch_norm(rq, nullptr, stream); }
 extern "C" size_t sd_cand_list_bytes(int rows) { return (size_t)(rows > 0 ? rows : 0) * sizeof(CandList); }
 extern "C" int sd_norm_probs_lists(const float *logits, int rows, int V, long ld_in, float temperature, int top_k,
                                    float top_p, int bf16_round_logits, float *probs_out, long ld_out, int *err_flag,
@@ -1268,9 +1267,9 @@ extern "C" int sd_norm_probs_lists(const float *logits, int rows, int V, long ld
     SD_REQUIRE(logits && probs_out && cand_lists && rows >= 0 && V > 0, "sd_norm_probs_lists: bad arguments");
     SD_REQUIRE(temperature != 0.0f, "sd_norm_probs_lists: temperature must be non-zero");
     if (rows == 0) return SD_OK;
-    return launch_norm(logits, rows, V, ld_in, temperature, top_k, top_p, bf16_round_logits, probs_out, ld_out, err_flag,
-                       false, nullptr, 0, 0, nullptr, nullptr, workspace, stream, nullptr, 0, nullptr,
-                       static_cast<CandList *>(cand_lists));
+    NormRequest rq = norm_input(logits, rows, V, ld_in, temperature, top_k, top_p, bf16_round_logits);
+    rq.probs_out = probs_out; rq.ld_out = ld_out; rq.err = err_flag; rq.workspace = workspace; rq.lists = cand_lists;
+    return launch_norm(rq, nullptr, stream);
 }
 
 // Test hook: launch_norm with everything passed through and the rows' route words read back (specdec.h).
@@ -1285,9 +1284,11 @@ extern "C" int sd_norm_probs_debug(const float *logits, int rows, int V, long ld
     SD_REQUIRE(route_out, "sd_norm_probs_debug: route_out is required");
     SD_REQUIRE(!filter_only || (!workspace && !tile_max), "sd_norm_probs_debug: filter_only takes no workspace / tile maxima");
     if (rows == 0) return SD_OK;
-    return launch_norm(logits, rows, V, ld_in, temperature, top_k, top_p, bf16_round_logits, probs_out, ld_out, err_flag,
-                       do_sample != 0, exp_noise, philox_seed, draw_index, tok_out, sample_err, workspace, stream, nullptr,
-                       filter_only, tile_max, static_cast<CandList *>(cand_lists), route_out);
+    NormRequest rq = norm_input(logits, rows, V, ld_in, temperature, top_k, top_p, bf16_round_logits);
+    rq.probs_out = probs_out; rq.ld_out = ld_out; rq.err = err_flag;
+    if (do_sample) { rq.noise = exp_noise; rq.seed = philox_seed; rq.draw = draw_index; rq.tok_out = tok_out; rq.samp_err = sample_err; }
+    rq.workspace = workspace; rq.tile_max = tile_max; rq.lists = cand_lists; rq.filter_only = filter_only; rq.route = route_out;
+    return launch_norm(rq, nullptr, stream);
 }
 
 // top_k_top_p_filter on its own (utils.py:152-179): out = logit where kept, -inf where dropped (out != logits).
@@ -1297,8 +1298,9 @@ extern "C" int sd_topk_topp_filter(const float *logits, int rows, int V, long ld
     SD_REQUIRE(dtype_mode == 0 || dtype_mode == SD_NORM_DT_BF16 || dtype_mode == SD_NORM_DT_F16,
                "sd_topk_topp_filter: dtype_mode %d", dtype_mode);
     if (rows == 0) return SD_OK;
-    return launch_norm(logits, rows, V, ld_in, 1.0f, top_k, top_p, dtype_mode, out, ld_out, nullptr, false, nullptr, 0, 0, nullptr,
-                       nullptr, nullptr, stream, nullptr, 1);
+    NormRequest rq = norm_input(logits, rows, V, ld_in, 1.0f, top_k, top_p, dtype_mode);
+    rq.probs_out = out; rq.ld_out = ld_out; rq.filter_only = 1;
+    return launch_norm(rq, nullptr, stream);
 }
 
 // (+ one CandList per row behind the CandRows: the native iteration keeps the target rows' candidate lists there)
@@ -1311,8 +1313,9 @@ extern "C" int sd_norm_probs(const float *logits, int rows, int V, long ld_in, f
     SD_REQUIRE(logits && probs_out && rows >= 0 && V > 0, "sd_norm_probs: bad arguments");
     SD_REQUIRE(temperature != 0.0f, "sd_norm_probs: temperature must be non-zero");
     if (rows == 0) return SD_OK;
-    return launch_norm(logits, rows, V, ld_in, temperature, top_k, top_p, bf16_round_logits, probs_out, ld_out,
-                       err_flag, false, nullptr, 0, 0, nullptr, nullptr, workspace, stream);
+    NormRequest rq = norm_input(logits, rows, V, ld_in, temperature, top_k, top_p, bf16_round_logits);
+    rq.probs_out = probs_out; rq.ld_out = ld_out; rq.err = err_flag; rq.workspace = workspace;
+    return launch_norm(rq, nullptr, stream);
 }
 
 extern "C" int sd_norm_sample(const float *logits, int V, float temperature, int top_k, float top_p,
@@ -1321,21 +1324,21 @@ extern "C" int sd_norm_sample(const float *logits, int V, float temperature, int
                               void *workspace, void *stream) {
     SD_REQUIRE(logits && probs_out && tok_out && V > 0, "sd_norm_sample: bad arguments");
     SD_REQUIRE(temperature != 0.0f, "sd_norm_sample: temperature must be non-zero");
-    return launch_norm(logits, 1, V, V, temperature, top_k, top_p, bf16_round_logits, probs_out, V, err_flag, true,
-                       exp_noise, philox_seed, draw_index, tok_out, sample_err, workspace, stream);
+    NormRequest rq = norm_input(logits, 1, V, V, temperature, top_k, top_p, bf16_round_logits);
+    rq.probs_out = probs_out; rq.ld_out = V; rq.err = err_flag; rq.workspace = workspace;
+    rq.noise = exp_noise; rq.seed = philox_seed; rq.draw = draw_index; rq.tok_out = tok_out; rq.samp_err = sample_err;
+    return launch_norm(rq, nullptr, stream);
 }
 
-// Batched rows: row r of `logits` (stride ld_in) is normalised into rows[r].probs_out; with `sample` each row also
+// Batched rows: row r of rq.logits (stride ld_in) is normalised into rows[r].probs_out; with `sample` each row also
 // draws its token (rows[r].tok_out) from its own noise / Philox stream.  Launches of at most SD_NORM_BATCH rows.
-// tile_max (or NULL): the head left the rows' tile maxima [n_rows][V / 16] and cleared the output rows (EPI_HEAD);
-// cand_lists (or NULL): one CandList per row comes back (the native lock-step loop's residual / bonus sample reads them).
-int sd_norm_batch_tiles(const float *logits, int n_rows, int V, long ld_in, float temperature, int top_k, float top_p,
-                        int bf16_round_logits, const sd_norm_row *rows, int sample, void *workspace, const float *tile_max,
-                        void *cand_lists, void *stream) {
-    SD_REQUIRE(logits && rows && n_rows >= 0 && V > 0, "sd_norm_batch: bad arguments");
-    SD_REQUIRE(temperature != 0.0f, "sd_norm_batch: temperature must be non-zero");
-    for (int r0 = 0; r0 < n_rows; r0 += SD_NORM_BATCH) {
-        const int n = n_rows - r0 < SD_NORM_BATCH ? n_rows - r0 : SD_NORM_BATCH;
+// rq.tile_max (or NULL): the head left the rows' tile maxima [rq.rows][V / 16] and cleared the output rows (EPI_HEAD);
+// rq.lists (or NULL): one CandList per row comes back (the native lock-step loop's residual / bonus sample reads them).
+int sd_norm_batch_tiles(const NormRequest &rq, const sd_norm_row *rows, int sample, void *stream) {
+    SD_REQUIRE(rq.logits && rows && rq.rows >= 0 && rq.V > 0, "sd_norm_batch: bad arguments");
+    SD_REQUIRE(rq.temperature != 0.0f, "sd_norm_batch: temperature must be non-zero");
+    for (int r0 = 0; r0 < rq.rows; r0 += SD_NORM_BATCH) {
+        const int n = rq.rows - r0 < SD_NORM_BATCH ? rq.rows - r0 : SD_NORM_BATCH;
         NormTab tab = {};
         bool aligned = true;
         for (int i = 0; i < n; ++i) {
@@ -1345,21 +1348,21 @@ int sd_norm_batch_tiles(const float *logits, int n_rows, int V, long ld_in, floa
             tab.noise[i] = d.exp_noise; tab.seed[i] = d.philox_seed; tab.draw[i] = d.draw_index;
             aligned = aligned && (reinterpret_cast<uintptr_t>(d.probs_out) & 15) == 0;
         }
-        char *ws = workspace ? static_cast<char *>(workspace) + (size_t)r0 * sizeof(CandRow) : nullptr;
-        const int rc = launch_norm(logits + (size_t)r0 * ld_in, n, V, ld_in, temperature, top_k, top_p, bf16_round_logits,
-                                   tab.out[0], 4, nullptr, sample != 0, nullptr, 0, 0, nullptr, nullptr,
-                                   aligned ? ws : nullptr, stream, &tab, 0,
-                                   tile_max ? tile_max + (size_t)r0 * (size_t)(V >> 4) : nullptr,
-                                   cand_lists ? static_cast<CandList *>(cand_lists) + r0 : nullptr);
-        if (rc != SD_OK) return rc;
+        NormRequest part = norm_input(rq.logits + (size_t)r0 * rq.ld_in, n, rq.V, rq.ld_in, rq.temperature, rq.top_k, rq.top_p, rq.mode);
+        part.probs_out = tab.out[0]; part.ld_out = 4; part.table_sample = sample != 0;
+        if (rq.workspace && aligned) part.workspace = static_cast<char *>(rq.workspace) + (size_t)r0 * sizeof(CandRow);
+        if (rq.tile_max) part.tile_max = rq.tile_max + (size_t)r0 * (size_t)(rq.V >> 4);
+        if (rq.lists) part.lists = static_cast<CandList *>(rq.lists) + r0;
+        if (const int rc = launch_norm(part, &tab, stream); rc != SD_OK) return rc;
     }
     return SD_OK;
 }
 extern "C" int sd_norm_batch(const float *logits, int n_rows, int V, long ld_in, float temperature, int top_k,
                              float top_p, int bf16_round_logits, const sd_norm_row *rows, int sample, void *workspace,
                              void *stream) {
-    return sd_norm_batch_tiles(logits, n_rows, V, ld_in, temperature, top_k, top_p, bf16_round_logits, rows, sample, workspace,
-                               nullptr, nullptr, stream);
+    NormRequest rq = norm_input(logits, n_rows, V, ld_in, temperature, top_k, top_p, bf16_round_logits);
+    rq.workspace = workspace;
+    return sd_norm_batch_tiles(rq, rows, sample, stream);
 }
 
 static inline int mode_dt(int dtype_mode) { return (dtype_mode >> 4) & 3; }
@@ -1391,26 +1394,28 @@ extern "C" int sd_accept_scan(const float *p_hist, const float *q_hist, long ld,
     return SD_OK;
 }
 
+// sd_resample and, with the error words of a native iteration (folded into res->flags bit 3), sd_resample_with_errors
+static int launch_resample(const float *p_hist, const float *q_hist, long ld, int V, int32_t *seq, int gamma, const float *exp_noise,
+                           uint64_t philox_seed, uint64_t draw_index, sd_accept_result *res, int32_t *seq_len,
+                           const int *err_flags, int n_err, int dtype_mode, void *stream) {
+    hipLaunchKernelGGL(resample_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, p_hist, q_hist, ld, V, seq, gamma,
+                       exp_noise, philox_seed, draw_index, res, seq_len, err_flags, n_err, mode_dt(dtype_mode));
+    SD_LAUNCH_CHECK();
+    return SD_OK;
+}
+
 extern "C" int sd_resample(const float *p_hist, const float *q_hist, long ld, int V, int32_t *seq, int L, int gamma,
                            const float *exp_noise, uint64_t philox_seed, uint64_t draw_index,
                            sd_accept_result *res, int32_t *seq_len, int dtype_mode, void *stream) {
     SD_REQUIRE(p_hist && q_hist && seq && res && V > 0, "sd_resample: bad arguments");
     (void)L;
-    hipLaunchKernelGGL(resample_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, p_hist, q_hist, ld, V, seq, gamma,
-                       exp_noise, philox_seed, draw_index, res, seq_len, (const int *)nullptr, 0, mode_dt(dtype_mode));
-    SD_LAUNCH_CHECK();
-    return SD_OK;
+    return launch_resample(p_hist, q_hist, ld, V, seq, gamma, exp_noise, philox_seed, draw_index, res, seq_len, nullptr, 0, dtype_mode, stream);
 }
 
-// internal: the same with the iteration's error words folded into res->flags bit3 (used by sd_spec_iteration)
 int sd_resample_with_errors(const float *p_hist, const float *q_hist, long ld, int V, int32_t *seq, int gamma,
                             uint64_t philox_seed, uint64_t draw_index, sd_accept_result *res, const int *err_flags,
-                            int n_err, int dtype_mode, hipStream_t st) {
-    hipLaunchKernelGGL(resample_kernel, dim3(1), dim3(NT), 0, st, p_hist, q_hist, ld, V, seq, gamma,
-                       (const float *)nullptr, philox_seed, draw_index, res, (int32_t *)nullptr, err_flags, n_err,
-                       mode_dt(dtype_mode));
-    SD_LAUNCH_CHECK();
-    return SD_OK;
+                            int n_err, int dtype_mode, void *stream) {
+    return launch_resample(p_hist, q_hist, ld, V, seq, gamma, nullptr, philox_seed, draw_index, res, nullptr, err_flags, n_err, dtype_mode, stream);
 }
 
 // accept scan + residual / bonus sample of one native iteration in ONE launch, the sample working on the candidate list of

@@ -1,88 +1,9 @@
 // spec_loops.h - the native decode loops (single stream, lock-step streams with or without a prompt queue, width-w iid,
 // autoregressive streams) and the steps
 // they share.  Host code - and the one small kernel of the autoregressive loop's hand-off - included at the end of
-// engine.hip, whose sd_session, HeadReq / HeadOut and session_forward / batch_forward it uses.
+// engine.hip, whose sd_session, HeadReq / HeadOut and session_forward / batch_forward it uses; the sampler entries that are
+// not public come from sampler_host.h.
 #pragma once
-
-// SD_NORM_DT_* of a model's probability rows: OPT keeps logits and probabilities in the weight dtype
-// (modeling_opt.py:974), Llama casts its logits to fp32 (modeling_llama.py:870)
-static int storage_mode(const sd_model *m) {
-    if (m->cfg.arch != SD_ARCH_OPT) return 0;
-    return m->cfg.dtype == SD_BF16 ? SD_NORM_DT_BF16 : (m->cfg.dtype == SD_F16 ? SD_NORM_DT_F16 : 0);
-}
-
-struct sd_spec {
-    sd_session *draft, *target;
-    int gamma, top_k, V;
-    float temperature, top_p;
-    int32_t *seq;
-    float *q_hist, *p_hist;
-    long ld;
-    float *draft_logits, *target_logits;
-    long ld_dl, ld_tl;
-    int *err;                    // device ints: [0..gamma) norm err of draft rows, [gamma..2gamma) sample err, [2gamma..3gamma+1) target rows
-    sd_accept_result *res_dev;
-    void *norm_ws;               // sd_norm_workspace_bytes(gamma+1) bytes, may be NULL
-    hipEvent_t ev[4];
-    hipEvent_t ev_done;          // end of an iteration's device -> host copy (sd_spec_generate polls it)
-    int timing;
-};
-
-extern "C" int sd_spec_create(sd_session *draft, sd_session *target, int gamma, float temperature, int top_k,
-                              float top_p, int32_t *seq, float *q_hist, float *p_hist, long ld, float *draft_logits,
-                              long ld_draft_logits, float *target_logits, long ld_target_logits, int *err_words,
-                              sd_accept_result *res_dev, void *norm_workspace, sd_spec **out) {
-    SD_REQUIRE(draft && target && seq && q_hist && p_hist && draft_logits && target_logits && err_words && res_dev && out,
-               "sd_spec_create: null argument");
-    SD_REQUIRE(gamma >= 1 && gamma <= 16, "sd_spec_create: gamma must be in 1..16");
-    SD_REQUIRE(draft->m->cfg.vocab == target->m->cfg.vocab, "sd_spec_create: draft and target vocabularies differ");
-    SD_REQUIRE(temperature != 0.0f, "sd_spec_create: temperature must be non-zero");
-    refresh_env();
-    sd_spec *sp = new sd_spec();
-    sp->draft = draft; sp->target = target; sp->gamma = gamma; sp->temperature = temperature; sp->top_k = top_k;
-    sp->top_p = top_p; sp->V = draft->m->cfg.vocab; sp->seq = seq; sp->q_hist = q_hist; sp->p_hist = p_hist; sp->ld = ld;
-    sp->draft_logits = draft_logits; sp->ld_dl = ld_draft_logits; sp->target_logits = target_logits; sp->ld_tl = ld_target_logits;
-    sp->err = err_words; sp->res_dev = res_dev; sp->norm_ws = norm_workspace; sp->timing = 0;
-    for (int i = 0; i < 4; ++i) SD_HIP_CHECK(hipEventCreate(&sp->ev[i]));
-    SD_HIP_CHECK(hipEventCreateWithFlags(&sp->ev_done, hipEventDisableTiming));
-    *out = sp;
-    return SD_OK;
-}
-
-extern "C" int sd_spec_destroy(sd_spec *sp) {
-    if (!sp) return SD_OK;
-    for (int i = 0; i < 4; ++i) (void)hipEventDestroy(sp->ev[i]);
-    (void)hipEventDestroy(sp->ev_done);
-    delete sp;
-    return SD_OK;
-}
-
-extern "C" int sd_spec_timing(sd_spec *sp, int on) {
-    SD_REQUIRE(sp, "sd_spec_timing: null handle");
-    sp->timing = on;
-    return SD_OK;
-}
-
-// milliseconds of the last iteration's draft phase and target (verify) phase; call after the stream is synchronised
-extern "C" int sd_spec_last_times(sd_spec *sp, float *draft_ms, float *target_ms) {
-    SD_REQUIRE(sp && draft_ms && target_ms && sp->timing, "sd_spec_last_times: timing is off");
-    SD_HIP_CHECK(hipEventElapsedTime(draft_ms, sp->ev[0], sp->ev[1]));
-    SD_HIP_CHECK(hipEventElapsedTime(target_ms, sp->ev[2], sp->ev[3]));
-    return SD_OK;
-}
-
-// entries of sampling.hip that are not in the public header
-int sd_resample_with_errors(const float *p_hist, const float *q_hist, long ld, int V, int32_t *seq, int gamma,
-                            uint64_t philox_seed, uint64_t draw_index, sd_accept_result *res, const int *err_flags,
-                            int n_err, int dtype_mode, hipStream_t st);
-int sd_norm_rows_with_tiles(const float *logits, int rows, int V, long ld_in, float temperature, int top_k, float top_p,
-                            int bf16_round_logits, float *probs_out, long ld_out, int *err_flag, uint64_t seed,
-                            uint64_t draw, int *tok_out, int *samp_err, void *workspace, const float *tile_max,
-                            void *stream, void *cand_lists);
-size_t sd_norm_candrow_bytes(int rows);
-int sd_norm_batch_tiles(const float *logits, int n_rows, int V, long ld_in, float temperature, int top_k, float top_p,
-                        int bf16_round_logits, const sd_norm_row *rows, int sample, void *workspace, const float *tile_max,
-                        void *cand_lists, void *stream);
 
 // feed seq[from, upto) in chunks of at most max_rows; logits come out for the last n_logits rows, all of them from the
 // final call (a chunk never ends inside the logits rows), so that call's output slab can be handed to the norm as is
@@ -108,77 +29,18 @@ static bool head_tiles_ok(int top_k, float temperature, int V, long ld) {
     return top_k >= 1 && top_k <= 64 && temperature > 0.0f && V % 16 == 0 && V >= 4096 && V <= 65536 && ld % 4 == 0;
 }
 
-// ---- one whole speculative iteration, enqueued natively ---------------------------------------
-// reference sampling/speculative_sampling.py:1934-2031 for the device-RNG mode: gamma x (draft forward +
-// norm_sample), one target forward over the uncached rows + norm_probs, accept scan, residual / bonus sample,
-// then the 144-byte result block and the gamma+2 candidate tokens are copied to pinned host memory.  Nothing
-// here synchronises; the caller waits on the stream once per iteration.
-extern "C" int sd_spec_iteration(sd_spec *sp, int L, int draft_len, int target_len, uint64_t seed_draft,
-                                 uint64_t draw_draft0, uint64_t seed_accept, uint64_t draw_scan0,
-                                 uint64_t draw_resample, const float *r_const, sd_accept_result *res_host,
-                                 int32_t *tok_host, void *stream) {
-    SD_REQUIRE(sp && res_host, "sd_spec_iteration: null argument");
-    SD_REQUIRE(L >= 1 && draft_len >= 0 && draft_len < L && target_len >= 0 && target_len < L + sp->gamma,
-               "sd_spec_iteration: L=%d draft_len=%d target_len=%d", L, draft_len, target_len);
-    hipStream_t st = (hipStream_t)stream;
-    const int g = sp->gamma, V = sp->V;
-    int rc;
-    const bool tiles_ok = head_tiles_ok(sp->top_k, sp->temperature, V, sp->ld);
-    HeadReq rq = {};
-    HeadOut ho = {};
-    rq.raw = true; rq.zero_ld = sp->ld;                          // (zero_rows: per forward, below)
-    if (sp->timing) SD_HIP_CHECK(hipEventRecord(sp->ev[0], st));
-    // ---- draft: gamma steps; the sampled token goes straight into seq[] where the next step's embed reads it
-    for (int i = 0; i < g; ++i) {
-        const int upto = L + i;
-        float *q_row = sp->q_hist + (size_t)(upto - 1) * sp->ld;
-        rq.zero_rows = tiles_ok ? q_row : nullptr;                   // the head clears the row and leaves tile maxima
-        if ((rc = feed_rows(sp->draft, sp->seq, draft_len, upto, 1, sp->draft_logits, sp->ld_dl, &rq, &ho, stream)) != SD_OK) return rc;
-        draft_len = upto;
-        if ((rc = sd_norm_rows_with_tiles(ho.logits, 1, V, ho.ld, sp->temperature, sp->top_k, sp->top_p,
-                                          ho.round | storage_mode(sp->draft->m), q_row, sp->ld, sp->err + i, seed_draft,
-                                          draw_draft0 + (uint64_t)i, sp->seq + upto, sp->err + g + i, sp->norm_ws, ho.tile_max,
-                                          stream, nullptr)) != SD_OK)
-            return rc;
-    }
-    if (sp->timing) { SD_HIP_CHECK(hipEventRecord(sp->ev[1], st)); SD_HIP_CHECK(hipEventRecord(sp->ev[2], st)); }
-    // the target rows' candidate lists (behind the CandRows of the workspace) let the residual / bonus sample skip its
-    // passes over V; they exist when all gamma + 1 rows of this iteration are normalised here
-    void *lists = nullptr;
-    // ---- target: every uncached row in one pass (the whole prompt on the first call), logits for the last gamma+1
-    {
-        const int upto = L + g;
-        const int rows = std::min(upto - target_len, g + 1);
-        if (sp->norm_ws && rows == g + 1) lists = (char *)sp->norm_ws + sd_norm_candrow_bytes(g + 1);
-        float *p_rows = sp->p_hist + (size_t)(upto - rows) * sp->ld;
-        rq.zero_rows = tiles_ok ? p_rows : nullptr;
-        if ((rc = feed_rows(sp->target, sp->seq, target_len, upto, rows, sp->target_logits, sp->ld_tl, &rq, &ho, stream)) != SD_OK)
-            return rc;
-        if ((rc = sd_norm_rows_with_tiles(ho.logits, rows, V, ho.ld, sp->temperature, sp->top_k, sp->top_p,
-                                          ho.round | storage_mode(sp->target->m), p_rows, sp->ld, sp->err + 2 * g, 0, 0, nullptr,
-                                          nullptr, sp->norm_ws, ho.tile_max, stream, lists)) != SD_OK)
-            return rc;
-    }
-    if (sp->timing) SD_HIP_CHECK(hipEventRecord(sp->ev[3], st));
-    // ---- accept scan + residual / bonus sample
-    // p - q, max_fn and the draw are in the rows' dtype when both models keep 16-bit rows
-    const int res_mode = storage_mode(sp->target->m) == storage_mode(sp->draft->m) ? storage_mode(sp->target->m) : 0;
-    if (lists) {
-        if ((rc = sd_accept_resample(sp->p_hist, sp->q_hist, sp->ld, V, sp->seq, L, g, r_const, seed_accept, draw_scan0,
-                                     draw_resample, sp->res_dev, sp->err, 3 * g + 1, res_mode, lists, st)) != SD_OK)
-            return rc;
-    } else {
-        if ((rc = sd_accept_scan(sp->p_hist, sp->q_hist, sp->ld, sp->seq, L, g, r_const, seed_accept, draw_scan0, sp->res_dev, stream)) != SD_OK)
-            return rc;
-        if ((rc = sd_resample_with_errors(sp->p_hist, sp->q_hist, sp->ld, V, sp->seq, g, seed_accept, draw_resample, sp->res_dev,
-                                          sp->err, 3 * g + 1, res_mode, st)) != SD_OK)
-            return rc;
-    }
-    SD_HIP_CHECK(hipMemcpyAsync(res_host, sp->res_dev, sizeof(sd_accept_result), hipMemcpyDeviceToHost, st));
-    if (tok_host)       // optional second copy; the result block already carries the drafted tokens and the next one
-        SD_HIP_CHECK(hipMemcpyAsync(tok_host, sp->seq + L, sizeof(int32_t) * (size_t)(g + 2), hipMemcpyDeviceToHost, st));
-    return SD_OK;
+// The norm launch of a loop's logit rows: the loop's sampling parameters, the rows where the forward left them (their pending
+// rounding joins the model's mode) and the head's tile maxima.  The caller adds what differs: the row count, the outputs, the
+// draws, the workspace, the lists.
+static NormRequest norm_request(const sd_sampling &sm, int mode, const HeadOut &ho) {
+    NormRequest rq = {};
+    rq.logits = ho.logits; rq.V = sm.V; rq.ld_in = ho.ld;
+    rq.temperature = sm.temperature; rq.top_k = sm.top_k; rq.top_p = sm.top_p; rq.mode = ho.round | mode;
+    rq.tile_max = ho.tile_max;
+    return rq;
 }
+// ... of a forward that was asked for nothing but its logit rows in the model's scratch
+static HeadOut scratch_rows(const sd_head_scratch &h) { return HeadOut{h.logits, h.ld_logits, 0, nullptr}; }
 
 // ---- steps the loops share ------------------------------------------------------------------------------------
 // In-loop failure handling of the three native loops: every failure sets `rc` and leaves the loop, so the common epilogue
@@ -206,9 +68,9 @@ static int poll_event(hipEvent_t ev, const char *who) {
 }
 
 // The events of one call of a loop: `timing` events for hipEventElapsedTime and the one whose completion ends an
-// iteration; destroyed on every way out.  (sd_spec keeps its own: their lifetime is the handle's.)
+// iteration; destroyed on every way out.
 struct LoopEvents {
-    hipEvent_t t[3] = {nullptr, nullptr, nullptr}, done = nullptr;
+    hipEvent_t t[4] = {nullptr, nullptr, nullptr, nullptr}, done = nullptr;
     bool ok = true;                                               // false: a creation failed (the error text is set)
     LoopEvents(int timing, const char *who) {
         for (int i = 0; i < timing && ok; ++i) ok = hipEventCreate(&t[i]) == hipSuccess;
@@ -283,12 +145,95 @@ static bool commit_result(const sd_accept_result &r, int L, int g, int32_t *host
     return true;
 }
 
+// ---- one whole speculative iteration, enqueued natively ---------------------------------------
+// reference sampling/speculative_sampling.py:1934-2031 for the device-RNG mode: gamma x (draft forward +
+// norm_sample), one target forward over the uncached rows + norm_probs, accept scan, residual / bonus sample,
+// then the 208-byte result block is copied to pinned host memory.  Nothing here synchronises; the caller waits on
+// the stream once per iteration.  `timed`: the draft phase is ev.t[0] .. t[1], the verify phase ev.t[2] .. t[3].
+static int spec_iteration(const sd_spec_stream &dv, int g, const sd_sampling &sm, const sd_spec_scratch &sc, const Draws &d, int L,
+                          int draft_len, int target_len, const float *r_const, const LoopEvents &ev, bool timed, void *stream) {
+    SD_REQUIRE(L >= 1 && draft_len >= 0 && draft_len < L && target_len >= 0 && target_len < L + g,
+               "sd_spec_generate: L=%d draft_len=%d target_len=%d", L, draft_len, target_len);
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    const bool tiles_ok = head_tiles_ok(sm.top_k, sm.temperature, sm.V, sm.ld);
+    int *const err = dv.err_words;     // [0..gamma) norm err of draft rows, [gamma..2gamma) sample err, [2gamma..3gamma+1) target rows
+    HeadReq rq = {};
+    HeadOut ho = {};
+    rq.raw = true; rq.zero_ld = sm.ld;                           // (zero_rows: per forward, below)
+    if (timed) SD_HIP_CHECK(hipEventRecord(ev.t[0], st));
+    // ---- draft: gamma steps; the sampled token goes straight into seq[] where the next step's embed reads it
+    for (int i = 0; i < g; ++i) {
+        const int upto = L + i;
+        float *q_row = dv.q_hist + (size_t)(upto - 1) * sm.ld;
+        rq.zero_rows = tiles_ok ? q_row : nullptr;                   // the head clears the row and leaves tile maxima
+        if ((rc = feed_rows(dv.draft, dv.seq, draft_len, upto, 1, sc.draft.logits, sc.draft.ld_logits, &rq, &ho, stream)) != SD_OK)
+            return rc;
+        draft_len = upto;
+        NormRequest nr = norm_request(sm, sc.draft.norm_mode, ho);
+        nr.rows = 1; nr.probs_out = q_row; nr.ld_out = sm.ld; nr.err = err + i;
+        nr.seed = d.seed_draft; nr.draw = d.draft0 + (uint64_t)i; nr.tok_out = dv.seq + upto; nr.samp_err = err + g + i;
+        nr.workspace = sc.norm_workspace;
+        if ((rc = sd_norm_rows_with_tiles(nr, stream)) != SD_OK) return rc;
+    }
+    if (timed) { SD_HIP_CHECK(hipEventRecord(ev.t[1], st)); SD_HIP_CHECK(hipEventRecord(ev.t[2], st)); }
+    // the target rows' candidate lists (behind the CandRows of the workspace) let the residual / bonus sample skip its
+    // passes over V; they exist when all gamma + 1 rows of this iteration are normalised here
+    void *lists = nullptr;
+    // ---- target: every uncached row in one pass (the whole prompt on the first call), logits for the last gamma+1
+    {
+        const int upto = L + g;
+        const int rows = std::min(upto - target_len, g + 1);
+        if (sc.norm_workspace && rows == g + 1) lists = (char *)sc.norm_workspace + sd_norm_candrow_bytes(g + 1);
+        float *p_rows = dv.p_hist + (size_t)(upto - rows) * sm.ld;
+        rq.zero_rows = tiles_ok ? p_rows : nullptr;
+        if ((rc = feed_rows(dv.target, dv.seq, target_len, upto, rows, sc.target.logits, sc.target.ld_logits, &rq, &ho, stream)) != SD_OK)
+            return rc;
+        NormRequest nr = norm_request(sm, sc.target.norm_mode, ho);
+        nr.rows = rows; nr.probs_out = p_rows; nr.ld_out = sm.ld; nr.err = err + 2 * g;
+        nr.workspace = sc.norm_workspace; nr.lists = lists;
+        if ((rc = sd_norm_rows_with_tiles(nr, stream)) != SD_OK) return rc;
+    }
+    if (timed) SD_HIP_CHECK(hipEventRecord(ev.t[3], st));
+    // ---- accept scan + residual / bonus sample
+    // p - q, max_fn and the draw are in the rows' dtype when both models keep 16-bit rows
+    const int res_mode = sc.target.norm_mode == sc.draft.norm_mode ? sc.target.norm_mode : 0;
+    if (lists) {
+        if ((rc = sd_accept_resample(dv.p_hist, dv.q_hist, sm.ld, sm.V, dv.seq, L, g, r_const, d.seed, d.scan0, d.resample, dv.res_dev,
+                                     err, 3 * g + 1, res_mode, lists, st)) != SD_OK)
+            return rc;
+    } else {
+        if ((rc = sd_accept_scan(dv.p_hist, dv.q_hist, sm.ld, dv.seq, L, g, r_const, d.seed, d.scan0, dv.res_dev, stream)) != SD_OK)
+            return rc;
+        if ((rc = sd_resample_with_errors(dv.p_hist, dv.q_hist, sm.ld, sm.V, dv.seq, g, d.seed, d.resample, dv.res_dev, err, 3 * g + 1,
+                                          res_mode, stream)) != SD_OK)
+            return rc;
+    }
+    SD_HIP_CHECK(hipMemcpyAsync(dv.res_host, dv.res_dev, sizeof(sd_accept_result), hipMemcpyDeviceToHost, st));
+    return SD_OK;
+}
+
 // The device-RNG loop without the interpreter between iterations (reference speculative_sampling.py:1934-2046).
-extern "C" int sd_spec_generate(sd_spec *sp, sd_seq_state *s, int eos_token_id, uint64_t random_seed, const float *r_const,
-                                sd_accept_result *res_host, void *stream) {
-    SD_REQUIRE(sp && s && s->host_seq && res_host, "sd_spec_generate: null argument");
+extern "C" int sd_spec_generate(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling, const sd_spec_scratch *scratch,
+                                sd_seq_state *s, uint64_t random_seed, const float *r_const, void *stream) {
+    SD_REQUIRE(dev && sampling && scratch && s && dev->draft && dev->target && dev->seq && dev->q_hist && dev->p_hist &&
+               dev->err_words && dev->res_dev && dev->res_host && s->host_seq && scratch->draft.logits && scratch->target.logits,
+               "sd_spec_generate: null argument");
+    SD_REQUIRE(gamma >= 1 && gamma <= 16, "sd_spec_generate: gamma %d outside 1..16", gamma);
     SD_REQUIRE(!random_seed || r_const, "sd_spec_generate: random_seed needs its uniform (r_const)");
-    const int g = sp->gamma;
+    const sd_sampling &sm = *sampling;
+    SD_REQUIRE(sm.temperature != 0.0f, "sd_spec_generate: temperature must be non-zero");
+    SD_REQUIRE(!scratch->norm_workspace || scratch->max_rows_per_forward >= gamma + 1,
+               "sd_spec_generate: a norm workspace of %d rows, the target's gamma %d + 1 rows keep their lists there",
+               scratch->max_rows_per_forward, gamma);
+    SD_REQUIRE(sm.V == dev->draft->m->cfg.vocab && sm.V == dev->target->m->cfg.vocab && sm.ld >= sm.V,
+               "sd_spec_generate: V %d (ld %ld), the models' vocabularies are %d / %d", sm.V, sm.ld, dev->draft->m->cfg.vocab,
+               dev->target->m->cfg.vocab);
+    refresh_env();
+    const int g = gamma;
+    const bool timed = s->draft_ms_out || s->target_ms_out;
+    LoopEvents ev(timed ? 4 : 0, "sd_spec_generate");
+    if (!ev.ok) return SD_ERR_HIP;
     int eos_total = s->ori_eos_cnt;
     s->n_iters = s->err = 0;
     int rc = SD_OK;
@@ -296,31 +241,29 @@ extern "C" int sd_spec_generate(sd_spec *sp, sd_seq_state *s, int eos_token_id, 
         const int L = s->len, iters = s->n_iters;
         const Draws d = next_draws(s->seed, s->draw, g, random_seed);
         s->seed = d.seed; s->draw = d.draw;
-        if ((rc = sd_spec_iteration(sp, L, s->draft_len, s->target_len, d.seed_draft, d.draft0, d.seed, d.scan0, d.resample, r_const,
-                                    res_host, nullptr, stream)) != SD_OK)
-            break;
-        SD_LOOP_HIP(hipEventRecord(sp->ev_done, (hipStream_t)stream));
-        if ((rc = poll_event(sp->ev_done, "sd_spec_generate")) != SD_OK) break;
-        const sd_accept_result r = *res_host;
+        if ((rc = spec_iteration(*dev, g, sm, *scratch, d, L, s->draft_len, s->target_len, r_const, ev, timed, stream)) != SD_OK) break;
+        SD_LOOP_HIP(hipEventRecord(ev.done, (hipStream_t)stream));
+        if ((rc = poll_event(ev.done, "sd_spec_generate")) != SD_OK) break;
+        const sd_accept_result r = *dev->res_host;
         if (r.flags & 2) { s->err = 1; break; }
         if (r.flags & 8) {                                        // which word: a draft sample error, or a norm error
             std::vector<int> ew(3 * g + 1);
-            SD_LOOP_HIP(hipMemcpy(ew.data(), sp->err, sizeof(int) * ew.size(), hipMemcpyDeviceToHost));
+            SD_LOOP_HIP(hipMemcpy(ew.data(), dev->err_words, sizeof(int) * ew.size(), hipMemcpyDeviceToHost));
             bool samp = false;
             for (int i = g; i < 2 * g; ++i) samp = samp || ew[i] != 0;
             s->err = samp ? 1 : 2;
             // a NaN row may be the poison of a timed-out in-launch wait (fused_kernels.h / normload_kernels.h): say so
             unsigned wd = 0, wt = 0;
-            if (hipMemcpy(&wd, sp->draft->wait_status, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess &&
-                hipMemcpy(&wt, sp->target->wait_status, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess && (wd | wt))
+            if (hipMemcpy(&wd, dev->draft->wait_status, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess &&
+                hipMemcpy(&wt, dev->target->wait_status, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess && (wd | wt))
                 sd_set_error("sd_spec_generate: a fused launch's in-launch wait timed out (status draft %#x, target %#x; "
                              "sd_session_fused_status): its rows were poisoned with NaN", wd, wt);
             break;
         }
-        if (sp->timing && (s->draft_ms_out || s->target_ms_out)) {
+        if (timed) {
             float dms = 0.f, tms = 0.f;
-            SD_LOOP_HIP(hipEventElapsedTime(&dms, sp->ev[0], sp->ev[1]));
-            SD_LOOP_HIP(hipEventElapsedTime(&tms, sp->ev[2], sp->ev[3]));
+            SD_LOOP_HIP(hipEventElapsedTime(&dms, ev.t[0], ev.t[1]));
+            SD_LOOP_HIP(hipEventElapsedTime(&tms, ev.t[2], ev.t[3]));
             if (s->draft_ms_out) s->draft_ms_out[iters] = dms;
             if (s->target_ms_out) s->target_ms_out[iters] = tms;
         }
@@ -334,7 +277,7 @@ extern "C" int sd_spec_generate(sd_spec *sp, sd_seq_state *s, int eos_token_id, 
             break;
         }
         commit_result(r, L, g, s->host_seq, &s->len, &s->draft_len, &s->target_len);      // (flags & 2 left the loop above)
-        for (int i = L; i < s->len; ++i) eos_total += s->host_seq[i] == eos_token_id;
+        for (int i = L; i < s->len; ++i) eos_total += s->host_seq[i] == sm.eos_token_id;
         if (eos_total > s->ori_eos_cnt) break;                    // the caller cuts after the first new EOS (:2033-2041)
     }
     return rc;
@@ -591,7 +534,7 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
                     s.draft_len = Ls[a0 + j] + i;
                 }
                 add_joiners(passes[p], 0);
-                // the single-stream loop's sampler feed (sd_spec_iteration): the head leaves the logits in its own slab, the
+                // the single-stream loop's sampler feed (spec_iteration): the head leaves the logits in its own slab, the
                 // maximum of every 16-column tile, and clears the streams' probability rows - no logits copy, no candidate pass
                 HeadReq rq = {};
                 HeadOut ho = {};
@@ -600,12 +543,9 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
                 for (int j = 0; j < rq.zero_n; ++j) rq.zero_ptr[j] = rows[j].probs_out;
                 if ((rc = batch_forward(items.data(), (int)items.size(), sc.draft.logits, sc.draft.ld_logits, &rq, &ho, stream)) != SD_OK) break;
                 if (m == 0) continue;                             // (joiner rows only)
-                if (fused_tail)
-                    rc = sd_norm_batch_tiles(ho.logits, m, sm.V, ho.ld, sm.temperature, sm.top_k, sm.top_p, ho.round | sc.draft.norm_mode,
-                                             rows.data(), 1, sc.norm_workspace, ho.tile_max, nullptr, stream);
-                else
-                    rc = sd_norm_batch(sc.draft.logits, m, sm.V, sc.draft.ld_logits, sm.temperature, sm.top_k, sm.top_p, sc.draft.norm_mode,
-                                       rows.data(), 1, sc.norm_workspace, stream);
+                NormRequest nr = norm_request(sm, sc.draft.norm_mode, fused_tail ? ho : scratch_rows(sc.draft));
+                nr.rows = m; nr.workspace = sc.norm_workspace;
+                rc = sd_norm_batch_tiles(nr, rows.data(), 1, stream);
             }
         }
         if (rc != SD_OK) break;
@@ -633,8 +573,9 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
             if (m == 0) continue;                                 // (joiner rows only)
             // one pass holds every stream: the rows' candidate lists (behind the CandRows of the workspace) serve the
             // residual / bonus sample below
-            rc = sd_norm_batch_tiles(sc.target.logits, (int)rows.size(), sm.V, sc.target.ld_logits, sm.temperature, sm.top_k, sm.top_p,
-                                     sc.target.norm_mode, rows.data(), 0, sc.norm_workspace, nullptr, lists_on ? list_base : nullptr, stream);
+            NormRequest nr = norm_request(sm, sc.target.norm_mode, scratch_rows(sc.target));
+            nr.rows = (int)rows.size(); nr.workspace = sc.norm_workspace; nr.lists = lists_on ? list_base : nullptr;
+            rc = sd_norm_batch_tiles(nr, rows.data(), 0, stream);
             if (lists_on) {
                 int r0 = 0;
                 for (int j = 0; j < m; ++j) {                       // stream j's lists are valid when all its gamma + 1 rows are here
@@ -909,8 +850,9 @@ extern "C" int sd_spec_multi_generate(const sd_multi_replica *reps, int width, i
                 draft_step_rows(items[w], rows[w], reps[w].draft, reps[w].seq, reps[w].q_hist, sm.ld, err_dev + w * n_err, g, L, i,
                                 s->draft_len, s->seed, draw0 + (uint64_t)w);
             if ((rc = batch_forward(items.data(), W, sc.draft.logits, sc.draft.ld_logits, nullptr, nullptr, stream)) != SD_OK) break;
-            rc = sd_norm_batch(sc.draft.logits, W, sm.V, sc.draft.ld_logits, sm.temperature, sm.top_k, sm.top_p, sc.draft.norm_mode,
-                               rows.data(), 1, sc.norm_workspace, stream);
+            NormRequest nr = norm_request(sm, sc.draft.norm_mode, scratch_rows(sc.draft));
+            nr.rows = W; nr.workspace = sc.norm_workspace;
+            rc = sd_norm_batch_tiles(nr, rows.data(), 1, stream);
             s->draft_len = L + i;
         }
         if (rc != SD_OK) break;
@@ -927,8 +869,9 @@ extern "C" int sd_spec_multi_generate(const sd_multi_replica *reps, int width, i
                 verify_pass_rows(items[j], rows, r.target, r.seq, r.p_hist, sm.ld, err_dev + (a + j) * n_err, g, L, t_lo);
             }
             if ((rc = batch_forward(items.data(), m, sc.target.logits, sc.target.ld_logits, nullptr, nullptr, stream)) != SD_OK) break;
-            rc = sd_norm_batch(sc.target.logits, (int)rows.size(), sm.V, sc.target.ld_logits, sm.temperature, sm.top_k, sm.top_p,
-                               sc.target.norm_mode, rows.data(), 0, sc.norm_workspace, stream);
+            NormRequest nr = norm_request(sm, sc.target.norm_mode, scratch_rows(sc.target));
+            nr.rows = (int)rows.size(); nr.workspace = sc.norm_workspace;
+            rc = sd_norm_batch_tiles(nr, rows.data(), 0, stream);
         }
         if (rc != SD_OK) break;
         if (timed) SD_LOOP_HIP(hipEventRecord(ev.t[2], st));
@@ -1078,9 +1021,9 @@ extern "C" int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, const 
         else
             rc = batch_forward(items.data(), n, head->logits, head->ld_logits, &rq, &ho, stream);
         if (rc != SD_OK) break;
-        if ((rc = sd_norm_batch_tiles(ho.logits, n, sm.V, ho.ld, sm.temperature, sm.top_k, sm.top_p, ho.round | head->norm_mode,
-                                      rows.data(), 1, norm_workspace, ho.tile_max, nullptr, stream)) != SD_OK)
-            break;
+        NormRequest nr = norm_request(sm, head->norm_mode, ho);
+        nr.rows = n; nr.workspace = norm_workspace;
+        if ((rc = sd_norm_batch_tiles(nr, rows.data(), 1, stream)) != SD_OK) break;
         // ---- the hand-off: 8 bytes per stream, one copy, one wait
         hipLaunchKernelGGL(ar_collect_kernel, dim3(1), dim3(64), 0, st, tab, n_streams, sm.eos_token_id, (ArSlot *)dev_block);
         SD_LOOP_HIP(hipGetLastError());

@@ -5,7 +5,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .._lib import SdHeadScratch, SdLockstepLog, SdSampling, SdSeqState, SdSpecScratch
+from .._lib import SdHeadScratch, SdLockstepLog, SdSampling, SdSeqState, SdSpecScratch, SdSpecStream
 from ..noise import DeviceNoise, HostTorchNoise
 from .kvcache_model import KVCacheModel
 
@@ -74,12 +74,17 @@ def open_spec_slot(draft_m, target_m, prompt_row, cap: int, gamma: int, temperat
     return draft, target, seq32, err
 
 
+def spec_stream(draft, target, seq32, err, res_dev: int, res_host: int) -> SdSpecStream:
+    """The device side of one speculative stream: sessions, token buffer, probability arenas, error words, result blocks."""
+    return SdSpecStream(draft._session.handle, target._session.handle, seq32.data_ptr(), draft._probs.data_ptr(),
+                        target._probs.data_ptr(), err.data_ptr(), res_dev, res_host)
+
+
 def bind_spec_slot(item, draft, target, seq32, err, res_dev: int, res_host: int) -> None:
-    """The device side of an SdBatchStream: sessions, token buffer, probability arenas, error words, result blocks."""
-    item.draft, item.target = draft._session.handle, target._session.handle
-    item.seq, item.q_hist, item.p_hist = seq32.data_ptr(), draft._probs.data_ptr(), target._probs.data_ptr()
-    item.err_words = err.data_ptr()
-    item.res_dev, item.res_host = res_dev, res_host
+    """The device side of an SdBatchStream: its leading fields are an SdSpecStream's."""
+    dev = spec_stream(draft, target, seq32, err, res_dev, res_host)
+    for name, _ in SdSpecStream._fields_:
+        setattr(item, name, getattr(dev, name))
 
 
 def sampling_block(temperature, top_k, top_p, V: int, ld: int, eos_token_id) -> SdSampling:

@@ -83,6 +83,10 @@ class KVCacheModel:
     def cache_len(self) -> int:
         return 0 if self._session is None else self._session.cache_len
 
+    def _norm_args(self) -> tuple:
+        """(temperature, top_k, top_p, norm mode) as the sampler entries take them; ``None`` / 0 switch a filter off."""
+        return float(self._temperature), int(self._top_k or 0), float(self._top_p or 0.0), self._model.norm_mode
+
     # -- device-resident core used by the decode loops --------------------------------------
     def forward_rows(self, seq32: torch.Tensor, upto: int, n_rows_out: int) -> None:
         """Feed tokens seq32[cache_len:upto] and write normalised probabilities for the last
@@ -105,8 +109,7 @@ class KVCacheModel:
             end = first + done + blk
             logits = ses.forward(seq32[ses.cache_len:end], blk)
             t1 = process_time_ns()
-            check(lib.sd_norm_probs(logits.data_ptr(), blk, V, logits.stride(0), float(self._temperature),
-                                    int(self._top_k or 0), float(self._top_p or 0.0), self._model.norm_mode,
+            check(lib.sd_norm_probs(logits.data_ptr(), blk, V, logits.stride(0), *self._norm_args(),
                                     self._probs[end - blk].data_ptr(), self._probs.stride(0),
                                     self._err[end - blk].data_ptr(), self._norm_ws.data_ptr(), st), "sd_norm_probs")
             self.forward_time_dict["norm_prob_time"] += process_time_ns() - t1
@@ -140,9 +143,7 @@ class KVCacheModel:
         else:
             e = noise.exponential(V, self._model.probs_dtype)
             e_ptr, seed, draw = e.data_ptr(), 0, 0
-        check(lib.sd_norm_sample(logits.data_ptr(), V, float(self._temperature), int(self._top_k or 0),
-                                 float(self._top_p or 0.0), self._model.norm_mode, self._probs[row].data_ptr(),
-                                 self._err[row].data_ptr(),
+        check(lib.sd_norm_sample(logits.data_ptr(), V, *self._norm_args(), self._probs[row].data_ptr(), self._err[row].data_ptr(),
                                  e_ptr, seed, draw, seq32[upto].data_ptr(), samp_err.data_ptr(), self._norm_ws.data_ptr(),
                                  _stream()),
               "sd_norm_sample")
@@ -275,13 +276,11 @@ class KVCacheModel:
                         rows[k].sample_err = serr.data_ptr() + 4 * w if last else None
                         k += 1
                 if n_out == 1:
-                    check(lib.sd_norm_batch(logits.data_ptr(), k, V, logits.stride(0), float(self._temperature),
-                                            int(self._top_k or 0), float(self._top_p or 0.0), m.norm_mode, rows, 1,
+                    check(lib.sd_norm_batch(logits.data_ptr(), k, V, logits.stride(0), *self._norm_args(), rows, 1,
                                             self._norm_ws.data_ptr(), st), "sd_norm_batch")
                 else:
                     # several history rows per replica: normalise all of them, then sample each replica's last row
-                    check(lib.sd_norm_batch(logits.data_ptr(), k, V, logits.stride(0), float(self._temperature),
-                                            int(self._top_k or 0), float(self._top_p or 0.0), m.norm_mode, rows, 0,
+                    check(lib.sd_norm_batch(logits.data_ptr(), k, V, logits.stride(0), *self._norm_args(), rows, 0,
                                             self._norm_ws.data_ptr(), st), "sd_norm_batch")
                     for w in ws:
                         check(lib.sd_sample(probs[w][upto - 1].data_ptr(), V, (e_base + w * V * 4) if e_base else None,
@@ -354,8 +353,8 @@ class KVCacheModel:
         check(lib.sd_session_forward_tree(ses.handle, tree_tok.data_ptr(), pos_host, masks, N, P, logits.data_ptr(),
                                           logits.stride(0), _stream()), "sd_session_forward_tree")
         t1 = process_time_ns()
-        check(lib.sd_norm_probs(logits.data_ptr(), N, V, logits.stride(0), float(self._temperature), int(self._top_k or 0),
-                                float(self._top_p or 0.0), m.norm_mode, self._probs[P].data_ptr(), self._probs.stride(0),
+        check(lib.sd_norm_probs(logits.data_ptr(), N, V, logits.stride(0), *self._norm_args(), self._probs[P].data_ptr(),
+                                self._probs.stride(0),
                                 self._err[P].data_ptr(), self._norm_ws.data_ptr() if N <= ses.max_rows else None, _stream()),
               "sd_norm_probs")
         self.forward_time_dict["_model_time"] += t1 - t0

@@ -17,7 +17,7 @@ import torch
 from .._lib import lib, check, SdAcceptResult
 from ..engine import as_specdec_model, _stream, check_token_ids, same_device
 from ._loop_common import (LoopLog, accept_rates_f64, cut_after_new_eos, details_dict, make_noise, open_stream,
-                           raise_loop_error, reseed_uniforms)
+                           raise_loop_error, reseed_uniforms, sampling_block, spec_scratch, spec_stream)
 
 _make_noise = make_noise                              # beam.py, multi.py and tests import it from here
 
@@ -181,25 +181,19 @@ def _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T,
     res_dev = torch.zeros(C.sizeof(SdAcceptResult), dtype=torch.uint8, device=dev)
     res_host = torch.zeros(C.sizeof(SdAcceptResult), dtype=torch.uint8).pin_memory()
     err_words = torch.zeros(3 * gamma + 1, dtype=torch.int32, device=dev)
-    sp = C.c_void_p()
-    check(lib.sd_spec_create(draft._session.handle, target._session.handle, gamma, float(target._temperature),
-                             int(target._top_k or 0), float(target._top_p or 0.0), seq32.data_ptr(), draft._probs.data_ptr(),
-                             target._probs.data_ptr(), draft._probs.stride(0), draft._session.logits.data_ptr(),
-                             draft._session.logits.stride(0), target._session.logits.data_ptr(),
-                             target._session.logits.stride(0), err_words.data_ptr(), res_dev.data_ptr(),
-                             target._norm_ws.data_ptr(), C.byref(sp)), "sd_spec_create")
     timed = timing_log is not None or details          # HIP-event brackets around the draft and the verify phase
-    if timed:
-        check(lib.sd_spec_timing(sp, 1), "sd_spec_timing")
     r_const = reseed_uniforms(random_seed, gamma, dev)
     max_iters = max(1, T - seq_len0)
     log = LoopLog(host_seq, T + gamma + 2, max_iters, gamma, q_fill=1.0, timed=timed)
     st = log.seq_state(seq_len0, T, ori_eos_cnt, (0, 0), noise, max_iters)
+    stream = spec_stream(draft, target, seq32, err_words, res_dev.data_ptr(), res_host.data_ptr())
+    sampling = sampling_block(target._temperature, target._top_k, target._top_p, target._model.cfg.vocab_size,
+                              draft._probs.stride(0), eos_token_id)
+    scratch = spec_scratch(draft._session, target._session, target._norm_ws, target._session.max_rows)
     try:
         tick = process_time_ns()
-        check(lib.sd_spec_generate(sp, C.byref(st), int(eos_token_id), int(random_seed or 0),
-                                   r_const.data_ptr() if r_const is not None else None, res_host.data_ptr(), _stream()),
-              "sd_spec_generate")
+        check(lib.sd_spec_generate(stream, gamma, sampling, scratch, st, int(random_seed or 0),
+                                   r_const.data_ptr() if r_const is not None else None, _stream()), "sd_spec_generate")
         other_time = process_time_ns() - tick            # host CPU time of the loop (enqueue + waits + bookkeeping)
         noise.seed, noise.draw = st.seed, st.draw
         raise_loop_error(st.err)
@@ -220,8 +214,6 @@ def _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T,
     except Exception as e:
         print(e)
         raise RuntimeError("s") from e
-    finally:
-        lib.sd_spec_destroy(sp)
     draft._session.cache_len, target._session.cache_len = st.draft_len, st.target_len
     out = torch.tensor([out_tokens], dtype=torch.int64, device=prefix.device)
     if details:

@@ -10,7 +10,7 @@ PROTOS, STRUCTS = abi_header.parse()
 
 def test_every_declared_symbol_is_bound_and_exported():
     print(f"{len(PROTOS)} prototypes, {len(STRUCTS)} structs")
-    assert len(PROTOS) >= 83 and len(STRUCTS) >= 23
+    assert len(PROTOS) >= 78 and len(STRUCTS) >= 24
     bound = [n for n, _, _ in _lib.SYMBOLS]
     assert len(bound) == len(set(bound)) and set(bound) == set(PROTOS), set(bound) ^ set(PROTOS)
     raw = C.CDLL(_lib.LIB_PATH)
@@ -31,3 +31,18 @@ def test_every_struct_matches_its_ctypes_class():
     assert set(_lib.C_STRUCTS) == set(STRUCTS), set(_lib.C_STRUCTS) ^ set(STRUCTS)
     for name, cls in _lib.C_STRUCTS.items():
         assert ([(f, getattr(cls, f).offset, getattr(cls, f).size) for f, _ in cls._fields_], C.sizeof(cls)) == STRUCTS[name], name
+
+
+def test_spec_generate_takes_the_shared_blocks():
+    """The single-stream loop is one call on the blocks the other loops take, plus the device side of its one stream."""
+    assert not [n for n in PROTOS if n in ("sd_spec_create", "sd_spec_destroy", "sd_spec_timing", "sd_spec_last_times",
+                                           "sd_spec_iteration")]
+    assert PROTOS["sd_spec_generate"] == ("i32", ["ptr", "i32", "ptr", "ptr", "ptr", "u64", "ptr", "ptr"],
+                                          ["sd_spec_stream", "int", "sd_sampling", "sd_spec_scratch", "sd_seq_state", "uint64_t",
+                                           "float", "void"])
+    fields = ["draft", "target", "seq", "q_hist", "p_hist", "err_words", "res_dev", "res_host"]
+    assert STRUCTS["sd_spec_stream"] == ([(f, 8 * i, 8) for i, f in enumerate(fields)], 64)
+    assert C.sizeof(_lib.SdSpecStream) == 64 and [f for f, _ in _lib.SdSpecStream._fields_] == fields
+    # ... which are the eight leading fields of sd_batch_stream, at the same offsets
+    assert STRUCTS["sd_batch_stream"][0][:8] == STRUCTS["sd_spec_stream"][0]
+    assert [(f, getattr(_lib.SdBatchStream, f).offset) for f in fields] == [(f, getattr(_lib.SdSpecStream, f).offset) for f in fields]

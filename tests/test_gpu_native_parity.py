@@ -1,5 +1,5 @@
-"""Round-2 parity tests (`pytest -m gpu`): the paths bench.py actually times - the native device-RNG iteration
-(sd_spec_iteration), the stream-batched loop and the bf16 fused kernels at the headline shapes - held to the CPU oracle,
+"""Round-2 parity tests (`pytest -m gpu`): the paths bench.py actually times - the native device-RNG loop
+(sd_spec_generate), the stream-batched loop and the bf16 fused kernels at the headline shapes - held to the CPU oracle,
 plus the drop-in boundary (HF modules, KVCacheModel multi / choice, bad token ids, top_k_top_p_filter).
 
 The device RNG is replayed into the oracle through sd_philox_exp / sd_philox_uniform (tests/philox_replay.py), so the
@@ -81,7 +81,7 @@ NATIVE_CASES = [
 
 @pytest.mark.parametrize("name,kind,kw,eos,max_len", NATIVE_CASES, ids=[c[0] for c in NATIVE_CASES])
 def test_native_device_loop_equals_oracle_on_the_device_rng_stream(hip, name, kind, kw, eos, max_len):
-    """speculative_sampling(rng=DeviceNoise(seed)) -> _native_device_loop -> sd_spec_iteration (what bench.py times)
+    """speculative_sampling(rng=DeviceNoise(seed)) -> _native_device_loop -> sd_spec_generate (what bench.py times)
     against oracle.speculative_sampling fed the SAME Philox variates: ids, acc_len, call counts identical (fp32)."""
     dc, dsd, tc, tsd = _pair(kind)
     prompt = torch.from_numpy(np.random.default_rng(5).integers(3, dc.vocab_size, size=(1, 13)))
@@ -108,6 +108,33 @@ def test_native_device_loop_equals_oracle_on_the_device_rng_stream(hip, name, ki
         assert all(a == kw["gamma"] for a in gd["acc_len"])
     # native mode reports the device time of the two phases (HIP events) where the reference reports process_time
     assert gd["approx_time"] > 0 and gd["target_time"] > 0 and gd["target_model_time"] == gd["target_time"]
+
+
+def test_native_device_loop_is_the_same_run_timed_or_not(hip, monkeypatch):
+    """One sd_spec_generate call per run: without details and timing log (no timing events) and with details (the two
+    phases timed) the tokens are identical, both sessions end at the same cache lengths, and the timed run reports both times."""
+    import importlib
+    ss = importlib.import_module("llmspeculativesampling_amd.sampling.speculative_sampling")
+    opened = []
+
+    def recording_open_stream(*a, **k):
+        kv, seq32 = ss_open(*a, **k)
+        opened.append(kv)
+        return kv, seq32
+    ss_open = ss.open_stream
+    monkeypatch.setattr(ss, "open_stream", recording_open_stream)
+    dc, dsd, tc, tsd = _pair("corr")
+    prompt = torch.from_numpy(np.random.default_rng(5).integers(3, dc.vocab_size, size=(1, 13))).cuda()
+    dm = hip.engine.SpecDecModel.from_state_dict(dc, dsd, dtype=torch.float32)
+    tm = hip.engine.SpecDecModel.from_state_dict(tc, tsd, dtype=torch.float32)
+    kw = dict(gamma=4, top_k=20, top_p=0.9)
+    plain = hip.S.speculative_sampling(prompt, dm, tm, 2, None, 16, details=False, rng=hip.noise.DeviceNoise(77), **kw)
+    timed, d = hip.S.speculative_sampling(prompt, dm, tm, 2, None, 16, details=True, rng=hip.noise.DeviceNoise(77), **kw)
+    assert isinstance(plain, torch.Tensor) and torch.equal(plain, timed) and plain.shape[1] > 13
+    assert d["approx_time"] > 0 and d["target_time"] > 0
+    (d0, t0), (d1, t1) = opened[:2], opened[2:]                  # (draft, target) of the first and of the second run
+    assert d0._model is dm and t0._model is tm and len(opened) == 4
+    assert (d1.cache_len, t1.cache_len) == (d0.cache_len, t0.cache_len) and 0 < d0.cache_len <= t0.cache_len
 
 
 @pytest.mark.parametrize("gamma,n_streams", [(4, 4), (2, 4), (8, 8)], ids=["g4x4", "g2x4", "g8x8_two_passes"])
@@ -183,7 +210,7 @@ BF16_CFG = dict(arch="llama", vocab_size=8192, hidden_size=256, intermediate_siz
 
 @pytest.mark.parametrize("case", ["perturbed", "all_accept", "long_prompt", "split_lm_head"])
 def test_native_bf16_iteration_bit_equals_python_loop(hip, case, capsys):
-    """The benchmarked configuration (bf16 weights, sd_spec_iteration, device Philox, vocab wide enough for the
+    """The benchmarked configuration (bf16 weights, sd_spec_generate, device Philox, vocab wide enough for the
     16-workgroup norm fast path, lm_head output slab handed straight to the norm) against the Python-orchestrated HIP
     loop (verbose=True) under the same Philox seed: tokens, acc_len and acc_rate must be bit-equal.  Covers a pair with
     partial accepts, an all-accept pair (rollback(n+2), 2-row draft step, bonus sample), a prompt longer than one

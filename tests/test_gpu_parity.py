@@ -765,7 +765,7 @@ def test_speculative_bf16_statistics_vs_oracle(hip):
 
 
 def test_native_iteration_matches_python_loop(hip, capsys):
-    """sd_spec_iteration (one native call per iteration, device Philox) == the Python-orchestrated loop with the
+    """sd_spec_generate (the native loop, one stream wait per iteration, device Philox) == the Python-orchestrated loop with the
     same Philox seed (verbose=True keeps the Python path), incl. the random_seed quirk and an all-accept pair."""
     from llmspeculativesampling_amd.synth import perturb_state_dict
     cfg = load_config("tiny-llama-target")

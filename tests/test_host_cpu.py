@@ -14,7 +14,7 @@ def test_library_exports_every_declared_symbol():
     from test_abi_cpu import test_every_declared_symbol_is_bound_and_exported as whole_header_check
     whole_header_check()
     from llmspeculativesampling_amd import _lib
-    assert _lib.lib.sd_version() == 5           # a host-only call: no GPU needed
+    assert _lib.lib.sd_version() == 6           # a host-only call: no GPU needed
 
 
 def test_struct_layouts_match_header():
@@ -475,10 +475,11 @@ def test_new_entry_points_reject_null_arguments_without_a_gpu():
     sampling, scratch = _lib.SdSampling(temperature=1.0, top_k=20, top_p=0.9, V=32000, ld=32000, eos_token_id=2), _lib.SdSpecScratch()
     state, log = _lib.SdSeqState(T=8, max_iters=1, n_iters=-7, err=-7), _lib.SdLockstepLog(n_iters=-7, err=-7)
     P = 0x1000                                  # a placeholder pointer: the refusal comes before any use
-    for sp, st in ((None, state), (P, None)):   # a null handle, a null state block
-        assert lib.sd_spec_generate(sp, st, 2, 0, None, P, None) == _lib.SD_ERR_INVALID
-        assert b"sd_spec_generate" in lib.sd_last_error()
     scratch.draft.logits = scratch.target.logits = P
+    dev = _lib.SdSpecStream(P, P, P, P, P, P, P, P)
+    for dv, st in ((None, state), (dev, None)):   # a null stream block, a null state block (test_spec_native_cpu.py has the rest)
+        assert lib.sd_spec_generate(dv, 4, sampling, scratch, st, 0, None, None) == _lib.SD_ERR_INVALID
+        assert b"sd_spec_generate" in lib.sd_last_error()
     streams = (_lib.SdBatchStream * 1)()
     for args in ((None, 0, sampling, scratch, log), (streams, 1, None, scratch, log), (streams, 1, sampling, None, log),
                  (streams, 1, sampling, scratch, None)):

@@ -155,6 +155,22 @@ def test_sampling_block_writes_the_conventions_once():
         assert (s.temperature, s.top_k, s.top_p, s.V, s.ld, s.eos_token_id) == want
 
 
+def test_spec_stream_and_bind_spec_slot_fill_the_same_eight_fields():
+    """The device side of one speculative stream, from two stand-in KVCacheModels (a session handle and a probability arena each)."""
+    from types import SimpleNamespace as NS
+    from llmspeculativesampling_amd import _lib
+    draft = NS(_session=NS(handle=0x1100), _probs=torch.zeros(4, 8))
+    target = NS(_session=NS(handle=0x2200), _probs=torch.zeros(4, 8))
+    seq32, err = torch.zeros(6, dtype=torch.int32), torch.zeros(13, dtype=torch.int32)
+    want = (0x1100, 0x2200, seq32.data_ptr(), draft._probs.data_ptr(), target._probs.data_ptr(), err.data_ptr(), 0x3300, 0x4400)
+    fields = ["draft", "target", "seq", "q_hist", "p_hist", "err_words", "res_dev", "res_host"]
+    dev = LC.spec_stream(draft, target, seq32, err, 0x3300, 0x4400)
+    assert type(dev) is _lib.SdSpecStream and tuple(getattr(dev, f) for f in fields) == want
+    item = _lib.SdBatchStream(len=5, T=9)                            # the slot's own fields stay as they are
+    LC.bind_spec_slot(item, draft, target, seq32, err, 0x3300, 0x4400)
+    assert tuple(getattr(item, f) for f in fields) == want and (item.len, item.T, item.host_seq) == (5, 9, None)
+
+
 def test_raise_loop_error_texts():
     LC.raise_loop_error(0)
     with pytest.raises(RuntimeError, match="^prob error$"):

@@ -35,7 +35,11 @@ int main() {
         g_norm_tile_threads = atoi(thr);
         for (int it = 0; it < 3; ++it) {
             hipMemset(o, 0, V * 4);
-            sd_norm_rows_with_tiles(x, 1, V, V, 1.0f, 20, 0.9f, 0, o, V, err, 1, 2, tok, err + 1, nullptr, tm, nullptr, nullptr);
+            NormRequest rq = {};
+            rq.logits = x; rq.rows = 1; rq.V = V; rq.ld_in = V; rq.temperature = 1.0f; rq.top_k = 20; rq.top_p = 0.9f;
+            rq.probs_out = o; rq.ld_out = V; rq.err = err; rq.seed = 1; rq.draw = 2; rq.tok_out = tok; rq.samp_err = err + 1;
+            rq.tile_max = tm;
+            sd_norm_rows_with_tiles(rq, nullptr);
             hipDeviceSynchronize();
         }
         char tag[64]; int t2; hipMemcpy(&t2, tok, 4, hipMemcpyDeviceToHost);
