@@ -103,6 +103,14 @@ typedef struct {
 } sd_norm_row;
 int sd_norm_batch(const float *logits, int n_rows, int V, long ld_in, float temperature, int top_k, float top_p,
                   int bf16_round_logits, const sd_norm_row *rows, int sample, void *workspace, void *stream);
+/* sd_norm_batch with one (temperature, top_k, top_p) per row: row r is filtered with params[r] (a host array of n_rows
+ * entries), and its result is exactly what sd_norm_batch gives for that row alone with those three values, whatever the
+ * other rows of the call ask for.  The candidate workspace serves the rows with 1 <= top_k <= 64; the others take the path
+ * they take without one.  Refused with SD_ERR_INVALID before anything is written or launched, the message naming the row: a
+ * NULL params, a temperature of 0, a negative top_k. */
+typedef struct { float temperature; int32_t top_k; float top_p; } sd_row_sampling;
+int sd_norm_batch_rows(const float *logits, int n_rows, int V, long ld_in, const sd_row_sampling *params,
+                       int bf16_round_logits, const sd_norm_row *rows, int sample, void *workspace, void *stream);
 
 /* sample (utils.py:213-233) for num_samples == 1: argmax_i probs[i] / noise[i] (first index wins
  * ties), then the "< 1e-9 -> argmax(probs)" fix-up.  exp_noise is a device row of Exp(1) variates
@@ -201,6 +209,13 @@ int sd_norm_probs_debug(const float *logits, int rows, int V, long ld_in, float 
                         void *cand_lists, void *stream, const float *tile_max, int filter_only, int do_sample,
                         const float *exp_noise, uint64_t philox_seed, uint64_t draw_index, int *tok_out, int *sample_err,
                         int *route_out);
+/* TEST HOOK: sd_norm_batch_rows on the route-recording instantiations.  tile_max (or NULL): the rows' tile maxima as above
+ * (the output rows zero-filled by the caller); the launch uses them only when every row of it has 1 <= top_k <= 64 and
+ * temperature > 0, else it drops them and the eligible rows go through the workspace.  cand_lists (or NULL): n_rows lists.
+ * route_out (device, n_rows ints, required): row r's SD_ROUTE_* word. */
+int sd_norm_batch_rows_debug(const float *logits, int n_rows, int V, long ld_in, const sd_row_sampling *params,
+                             int bf16_round_logits, const sd_norm_row *rows, int sample, void *workspace, void *stream,
+                             const float *tile_max, void *cand_lists, int *route_out);
 
 /* sd_accept_scan + sd_resample for up to 16 independent streams in two launches (stream-batched decode).
  * Per item: its probability arenas, token buffer, prefix length L, the gamma uniforms r (or NULL: Philox
@@ -652,6 +667,22 @@ int sd_spec_queue_generate_shared(sd_batch_stream *slots, int n_slots, int slot_
                                   int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
                                   const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log, int *passes_out,
                                   void *stream, sd_session *donor_draft, sd_session *donor_target, int shared_rows);
+/* Per-request sampling parameters in the two lock-step loops.  stream_params[i] is what stream i of
+ * sd_spec_batch_generate samples with; prompt_params[k] is what prompt k of the queue samples with in whichever slot it
+ * decodes, so a slot changes parameters when it changes hands.  With an array, sampling->temperature / top_k / top_p are
+ * not read (V, ld and eos_token_id are); every draft and verify row is normalised with its stream's triple through
+ * sd_norm_batch_rows' launch, and the draft head leaves tile maxima in the passes whose sampled rows all have
+ * 1 <= top_k <= 64 and temperature > 0.  Each stream still runs exactly sd_spec_generate's algorithm with its own triple.
+ * With a NULL array the calls are sd_spec_batch_generate and sd_spec_queue_generate_shared themselves.  Refused with
+ * SD_ERR_INVALID before anything is written or launched, naming the index: a temperature of 0, a negative top_k. */
+int sd_spec_batch_generate_rows(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
+                                uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log,
+                                void *stream, const sd_row_sampling *stream_params);
+int sd_spec_queue_generate_rows(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
+                                int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
+                                const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log, int *passes_out,
+                                void *stream, sd_session *donor_draft, sd_session *donor_target, int shared_rows,
+                                const sd_row_sampling *prompt_params);
 /* The whole loop of multi_speculative_sampling(strategy="iid") (speculative_sampling.py:1379-1716) for the device-RNG mode,
  * no interpreter between iterations.  `width` replicas, each with its own sessions, token buffer and probability arenas;
  * per iteration: gamma draft steps (one pass over the draft weights for all replicas each, sampled straight into

@@ -31,6 +31,10 @@ class SdNormRow(C.Structure):
                 ("draw_index", C.c_uint64), ("tok_out", C.c_void_p), ("sample_err", C.c_void_p)]
 
 
+class SdRowSampling(C.Structure):
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float)]
+
+
 class SdAcceptItem(C.Structure):
     _fields_ = [("p_hist", C.c_void_p), ("q_hist", C.c_void_p), ("seq", C.c_void_p), ("L", C.c_int32),
                 ("r", C.c_void_p), ("exp_noise", C.c_void_p), ("philox_seed", C.c_uint64), ("draw_scan", C.c_uint64),
@@ -158,7 +162,8 @@ class SdModelWeights(C.Structure):
 
 
 # every struct include/specdec.h declares, by its C name
-C_STRUCTS = {"sd_accept_result": SdAcceptResult, "sd_norm_row": SdNormRow, "sd_accept_item": SdAcceptItem,
+C_STRUCTS = {"sd_accept_result": SdAcceptResult, "sd_norm_row": SdNormRow, "sd_row_sampling": SdRowSampling,
+             "sd_accept_item": SdAcceptItem,
              "sd_multi_result": SdMultiResult, "sd_multi_item": SdMultiItem, "sd_multi_adopt_item": SdMultiAdoptItem,
              "sd_multi_replica": SdMultiReplica, "sd_batch_stream": SdBatchStream, "sd_queue_prompt": SdQueuePrompt,
              "sd_queue_pass": SdQueuePass, "sd_queue_chunk": SdQueueChunk, "sd_kv_copy_item": SdKvCopyItem,
@@ -178,6 +183,9 @@ SYMBOLS = [
     ("sd_norm_workspace_bytes", C.c_size_t, [_I]),
     ("sd_norm_sample", _I, [_VP, _I, _F, _I, _F, _I, _VP, _VP, _VP, _U64, _U64, _VP, _VP, _VP, _VP]),
     ("sd_norm_batch", _I, [_VP, _I, _I, _L, _F, _I, _F, _I, C.POINTER(SdNormRow), _I, _VP, _VP]),
+    ("sd_norm_batch_rows", _I, [_VP, _I, _I, _L, C.POINTER(SdRowSampling), _I, C.POINTER(SdNormRow), _I, _VP, _VP]),
+    ("sd_norm_batch_rows_debug", _I, [_VP, _I, _I, _L, C.POINTER(SdRowSampling), _I, C.POINTER(SdNormRow), _I, _VP, _VP, _VP, _VP,
+                                      _VP]),                                 # test hook
     ("sd_accept_batch", _I, [C.POINTER(SdAcceptItem), _I, _L, _I, _I, _I, _VP]),
     ("sd_accept_multi", _I, [C.POINTER(SdMultiItem), _I, _L, _I, _I, _VP, _U64, _U64, _VP, _VP]),
     ("sd_multi_resample", _I, [_VP, _VP, _L, _I, _VP, _I, _VP, _U64, _U64, _VP, _I, _VP]),
@@ -233,6 +241,10 @@ SYMBOLS = [
                                     _P(SdSpecScratch), _P(SdLockstepLog), _VP, _VP]),
     ("sd_spec_queue_generate_shared", _I, [_P(SdBatchStream), _I, _I, _P(SdQueuePrompt), _I, _I, _I, _P(SdSampling), _U64, _VP,
                                            _P(SdSpecScratch), _P(SdLockstepLog), _VP, _VP, _VP, _VP, _I]),
+    ("sd_spec_batch_generate_rows", _I, [_P(SdBatchStream), _I, _I, _P(SdSampling), _U64, _VP, _P(SdSpecScratch), _P(SdLockstepLog),
+                                         _VP, _P(SdRowSampling)]),
+    ("sd_spec_queue_generate_rows", _I, [_P(SdBatchStream), _I, _I, _P(SdQueuePrompt), _I, _I, _I, _P(SdSampling), _U64, _VP,
+                                         _P(SdSpecScratch), _P(SdLockstepLog), _VP, _VP, _VP, _VP, _I, _P(SdRowSampling)]),
     ("sd_session_copy_kv", _I, [_VP, C.POINTER(SdKvCopyItem), _I, _VP]),
     ("sd_spec_queue_plan", _I, [_I, _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(C.c_int32), _I, _I, _I, C.POINTER(SdQueuePass), _I,
                                 C.POINTER(SdQueueChunk), _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

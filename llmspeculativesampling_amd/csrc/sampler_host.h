@@ -25,6 +25,8 @@ struct NormRequest {
     void *lists;              // one CandList per row comes back (sd_cand_list_bytes)
     int filter_only;          // top_k_top_p_filter's result instead of probabilities
     int *route;               // test hook: the rows' route words
+    const sd_row_sampling *row_params;   // sd_norm_batch_tiles only: row r is filtered with row_params[r], and temperature /
+                                         // top_k / top_p above are not read
 };
 
 // norm_logits of rows whose head left tile maxima (or NULL) and cleared probs_out; with tok_out also the sample that follows a

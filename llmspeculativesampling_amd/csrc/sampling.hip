@@ -207,7 +207,17 @@ struct NormTab {
     int *samp_err[SD_NORM_BATCH];
     const float *noise[SD_NORM_BATCH];
     uint64_t seed[SD_NORM_BATCH], draw[SD_NORM_BATCH];
+    // row_params != 0: row i is filtered with (temperature[i], top_k[i], top_p[i]) instead of the launch's scalar triple
+    // (sd_norm_batch_rows); indexed by the launch-local row like everything above, so workgroup-uniform
+    float temperature[SD_NORM_BATCH];
+    int top_k[SD_NORM_BATCH];
+    float top_p[SD_NORM_BATCH];
+    int row_params;
 };
+// passed by value: with the other arguments of norm_probs_kernel (about 150 bytes) the kernel-argument block stays under 4096
+static_assert(sizeof(NormTab) == 3272 && sizeof(NormTab) + 256 <= 4096, "NormTab outgrew the kernel-argument block");
+// entry A (norm_cand_kernel's workspace) serves a row of a launch with per-row parameters when the row itself is eligible
+__host__ __device__ __forceinline__ bool cand_k_ok(int top_k) { return top_k >= 1 && top_k <= 64; }
 
 #define NB_SPLIT 16
 #define CAND_CAP 192
@@ -248,6 +258,11 @@ __global__ __launch_bounds__(256) void norm_cand_kernel(const float *__restrict_
     __shared__ float redf[16];
     __shared__ int redi[16];
     const int row = blockIdx.y, b = blockIdx.x, tid = threadIdx.x;
+    if (use_tab && tab.row_params) {                              // per-row parameters: a row that entry A does not serve is
+        top_k = tab.top_k[blockIdx.y];                            // left alone (norm_probs_kernel takes its general path and
+        if (!cand_k_ok(top_k)) return;                            // writes the whole row): out before the first store
+        temperature = tab.temperature[blockIdx.y];
+    }
     const float4 *x4 = reinterpret_cast<const float4 *>(logits + (size_t)row * ld_in);
     float4 *o4 = reinterpret_cast<float4 *>(use_tab ? tab.out[blockIdx.y] : out + (size_t)row * ld_out);
     const int V4 = V >> 2, C4 = (V4 + NB_SPLIT - 1) / NB_SPLIT;
@@ -351,6 +366,13 @@ __global__ __launch_bounds__(NT) void norm_probs_kernel(const float *__restrict_
         draw = tab.draw[blockIdx.x];
         tok_out = tab.tok_out[blockIdx.x];
         samp_err = tab.samp_err[blockIdx.x];
+        if (tab.row_params) {                                     // ... and per-row filter parameters (workgroup-uniform)
+            temperature = tab.temperature[blockIdx.x];
+            top_k = tab.top_k[blockIdx.x];
+            top_p = tab.top_p[blockIdx.x];
+            // entry A is per row: norm_cand_kernel left this row alone unless 1 <= top_k <= 64 (entry B is per launch)
+            if (!cand_k_ok(top_k)) ws = nullptr;
+        }
     }
     const uint32_t neg_inf_key = 0x007fffffu;                     // fkey(-inf)
     CandList *cl = cl_out ? cl_out + row : nullptr;
@@ -1214,14 +1236,25 @@ static int launch_norm(const NormRequest &rq, const NormTab *tabp, void *stream)
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
     }
+    // which rows the two fast entries can serve.  Entry B's 256-thread, unstaged launch shape belongs to the launch, so with
+    // per-row parameters every row must be eligible; entry A is decided per row inside the kernels, and norm_cand_kernel
+    // launches when any row is
+    bool any_a = cand_k_ok(top_k), all_b = any_a && rq.temperature > 0.0f;
+    if (tab.row_params) {
+        any_a = false; all_b = true;
+        for (int i = 0; i < rq.rows; ++i) {
+            any_a = any_a || cand_k_ok(tab.top_k[i]);
+            all_b = all_b && cand_k_ok(tab.top_k[i]) && tab.temperature[i] > 0.0f;
+        }
+    }
     // the head already left tile maxima and a cleared output row (EPI_HEAD): no candidate pass over V at all
     const float *tile_max = rq.tile_max;
-    if (tile_max && !(top_k >= 1 && top_k <= 64 && rq.temperature > 0.0f && (V & 15) == 0 && V >= 4096 && V <= 65536 &&
+    if (tile_max && !(all_b && (V & 15) == 0 && V >= 4096 && V <= 65536 &&
                       (rq.ld_in & 3) == 0 && (reinterpret_cast<uintptr_t>(rq.logits) & 15) == 0 && !rq.filter_only))
         tile_max = nullptr;
     // two-kernel fast path: the row is cut over NB_SPLIT workgroups first (see norm_cand_kernel)
     CandRow *ws = nullptr;
-    if (!tile_max && rq.workspace && top_k >= 1 && top_k <= 64 && V >= 4096 && (V & 3) == 0 && (rq.ld_in & 3) == 0 &&
+    if (!tile_max && rq.workspace && any_a && V >= 4096 && (V & 3) == 0 && (rq.ld_in & 3) == 0 &&
         (rq.ld_out & 3) == 0 && ((V >> 2) + NB_SPLIT - 1) / NB_SPLIT <= 256 * CAND_MAXIT &&
         (reinterpret_cast<uintptr_t>(rq.logits) & 15) == 0 && (use_tab || (reinterpret_cast<uintptr_t>(rq.probs_out) & 15) == 0)) {
         ws = static_cast<CandRow *>(rq.workspace);
@@ -1336,7 +1369,12 @@ extern "C" int sd_norm_sample(const float *logits, int V, float temperature, int
 // rq.lists (or NULL): one CandList per row comes back (the native lock-step loop's residual / bonus sample reads them).
 int sd_norm_batch_tiles(const NormRequest &rq, const sd_norm_row *rows, int sample, void *stream) {
     SD_REQUIRE(rq.logits && rows && rq.rows >= 0 && rq.V > 0, "sd_norm_batch: bad arguments");
-    SD_REQUIRE(rq.temperature != 0.0f, "sd_norm_batch: temperature must be non-zero");
+    const sd_row_sampling *rp = rq.row_params;
+    SD_REQUIRE(rp || rq.temperature != 0.0f, "sd_norm_batch: temperature must be non-zero");
+    for (int r = 0; rp && r < rq.rows; ++r) {                     // (every row, ahead of the first launch)
+        SD_REQUIRE(rp[r].temperature != 0.0f, "sd_norm_batch_rows: row %d: temperature must be non-zero", r);
+        SD_REQUIRE(rp[r].top_k >= 0, "sd_norm_batch_rows: row %d: top_k %d is negative", r, rp[r].top_k);
+    }
     for (int r0 = 0; r0 < rq.rows; r0 += SD_NORM_BATCH) {
         const int n = rq.rows - r0 < SD_NORM_BATCH ? rq.rows - r0 : SD_NORM_BATCH;
         NormTab tab = {};
@@ -1346,13 +1384,16 @@ int sd_norm_batch_tiles(const NormRequest &rq, const sd_norm_row *rows, int samp
             SD_REQUIRE(d.probs_out && (!sample || d.tok_out), "sd_norm_batch: row %d: null output", r0 + i);
             tab.out[i] = d.probs_out; tab.err[i] = d.err; tab.tok_out[i] = d.tok_out; tab.samp_err[i] = d.sample_err;
             tab.noise[i] = d.exp_noise; tab.seed[i] = d.philox_seed; tab.draw[i] = d.draw_index;
+            if (rp) { tab.temperature[i] = rp[r0 + i].temperature; tab.top_k[i] = rp[r0 + i].top_k; tab.top_p[i] = rp[r0 + i].top_p; }
             aligned = aligned && (reinterpret_cast<uintptr_t>(d.probs_out) & 15) == 0;
         }
+        tab.row_params = rp != nullptr;
         NormRequest part = norm_input(rq.logits + (size_t)r0 * rq.ld_in, n, rq.V, rq.ld_in, rq.temperature, rq.top_k, rq.top_p, rq.mode);
         part.probs_out = tab.out[0]; part.ld_out = 4; part.table_sample = sample != 0;
         if (rq.workspace && aligned) part.workspace = static_cast<char *>(rq.workspace) + (size_t)r0 * sizeof(CandRow);
         if (rq.tile_max) part.tile_max = rq.tile_max + (size_t)r0 * (size_t)(rq.V >> 4);
         if (rq.lists) part.lists = static_cast<CandList *>(rq.lists) + r0;
+        if (rq.route) part.route = rq.route + r0;
         if (const int rc = launch_norm(part, &tab, stream); rc != SD_OK) return rc;
     }
     return SD_OK;
@@ -1362,6 +1403,26 @@ extern "C" int sd_norm_batch(const float *logits, int n_rows, int V, long ld_in,
                              void *stream) {
     NormRequest rq = norm_input(logits, n_rows, V, ld_in, temperature, top_k, top_p, bf16_round_logits);
     rq.workspace = workspace;
+    return sd_norm_batch_tiles(rq, rows, sample, stream);
+}
+
+// sd_norm_batch with one (temperature, top_k, top_p) per row
+extern "C" int sd_norm_batch_rows(const float *logits, int n_rows, int V, long ld_in, const sd_row_sampling *params,
+                                  int bf16_round_logits, const sd_norm_row *rows, int sample, void *workspace, void *stream) {
+    SD_REQUIRE(params, "sd_norm_batch_rows: params is NULL (sd_norm_batch takes one triple for all rows)");
+    NormRequest rq = norm_input(logits, n_rows, V, ld_in, 0.0f, 0, 0.0f, bf16_round_logits);
+    rq.workspace = workspace; rq.row_params = params;
+    return sd_norm_batch_tiles(rq, rows, sample, stream);
+}
+
+// Test hook: sd_norm_batch_rows on the instantiations that record the route, with tile maxima and lists passed through
+extern "C" int sd_norm_batch_rows_debug(const float *logits, int n_rows, int V, long ld_in, const sd_row_sampling *params,
+                                        int bf16_round_logits, const sd_norm_row *rows, int sample, void *workspace, void *stream,
+                                        const float *tile_max, void *cand_lists, int *route_out) {
+    SD_REQUIRE(params, "sd_norm_batch_rows_debug: params is NULL");
+    SD_REQUIRE(route_out, "sd_norm_batch_rows_debug: route_out is required");
+    NormRequest rq = norm_input(logits, n_rows, V, ld_in, 0.0f, 0, 0.0f, bf16_round_logits);
+    rq.workspace = workspace; rq.row_params = params; rq.tile_max = tile_max; rq.lists = cand_lists; rq.route = route_out;
     return sd_norm_batch_tiles(rq, rows, sample, stream);
 }
 

@@ -437,8 +437,9 @@ static int queue_idle_prefill(PromptQueue &q, sd_batch_stream *slots, const std:
 
 // The lock-step loop of sampling/batch.py in native code (reference algorithm per stream: speculative_sampling.py:1934-2046),
 // with or without a prompt queue behind the streams' slots.
+// params (or NULL: sm's triple for everyone): per-request sampling parameters, indexed by stream - with a queue, by prompt.
 static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_streams, PromptQueue *q, int gamma, const sd_sampling &sm,
-                         uint64_t random_seed, const float *r_const, const sd_spec_scratch &sc, sd_lockstep_log *log, void *stream) {
+                         const sd_row_sampling *params, uint64_t random_seed, const float *r_const, const sd_spec_scratch &sc, sd_lockstep_log *log, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     const int g = gamma, n_err = 3 * g + 1;
     // rows per target pass (every verify row is a logit row: sd_model_max_pass_rows, 64 for a model whose lm_head or
@@ -455,6 +456,7 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
     std::vector<Draws> draws;
     std::vector<sd_batch_item> items;
     std::vector<sd_norm_row> rows;
+    std::vector<sd_row_sampling> prows;                           // the parameters of rows[] (with `params` only)
     std::vector<sd_accept_item> aitems;
     std::vector<const void *> list_of;
     int32_t act_rows[SD_MAX_STREAMS], join_rows[SD_MAX_STREAMS];
@@ -488,6 +490,8 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
     // resample) - kept for A/B runs and as the reference the fused tail is tested against; read per call
     const bool fused_tail = !(getenv("SD_BATCH_FUSED_TAIL") && atoi(getenv("SD_BATCH_FUSED_TAIL")) == 0);
     const bool tiles_ok = head_tiles_ok(sm.top_k, sm.temperature, sm.V, sm.ld);
+    // the triple of the request a stream runs: a queue's slot changes parameters when it changes hands
+    auto params_of = [&](const sd_batch_stream &s) -> const sd_row_sampling & { return params[q ? q->occ[&s - streams] : &s - streams]; };
     for (int i = 0; i < n_streams; ++i) {
         streams[i].done = q ? 1 : 0; streams[i].calls = 0;
         if (q) { q->occ[i] = -1; q->joining[i] = false; }
@@ -527,6 +531,16 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
                 const int a0 = passes[p].act0, m = passes[p].n_act;
                 items.assign(m, sd_batch_item{});
                 rows.assign(m, sd_norm_row{});
+                // per-request parameters: the head is asked for tile maxima when every sampled row of THIS pass can use them
+                bool pass_tiles = tiles_ok;
+                if (params) {
+                    prows.resize(m);
+                    pass_tiles = true;
+                    for (int j = 0; j < m; ++j) {
+                        prows[j] = params_of(*act[a0 + j]);
+                        pass_tiles = pass_tiles && head_tiles_ok(prows[j].top_k, prows[j].temperature, sm.V, sm.ld);
+                    }
+                }
                 for (int j = 0; j < m; ++j) {
                     sd_batch_stream &s = *act[a0 + j];
                     draft_step_rows(items[j], rows[j], s.draft, s.seq, s.q_hist, sm.ld, s.err_words, g, Ls[a0 + j], i, s.draft_len,
@@ -539,12 +553,12 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
                 HeadReq rq = {};
                 HeadOut ho = {};
                 rq.raw = fused_tail;
-                rq.zero_n = fused_tail && tiles_ok && m <= 16 ? m : 0;
+                rq.zero_n = fused_tail && pass_tiles && m <= 16 ? m : 0;
                 for (int j = 0; j < rq.zero_n; ++j) rq.zero_ptr[j] = rows[j].probs_out;
                 if ((rc = batch_forward(items.data(), (int)items.size(), sc.draft.logits, sc.draft.ld_logits, &rq, &ho, stream)) != SD_OK) break;
                 if (m == 0) continue;                             // (joiner rows only)
                 NormRequest nr = norm_request(sm, sc.draft.norm_mode, fused_tail ? ho : scratch_rows(sc.draft));
-                nr.rows = m; nr.workspace = sc.norm_workspace;
+                nr.rows = m; nr.workspace = sc.norm_workspace; nr.row_params = params ? prows.data() : nullptr;
                 rc = sd_norm_batch_tiles(nr, rows.data(), 1, stream);
             }
         }
@@ -562,10 +576,11 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
         for (int p = 0; p < n_passes && rc == SD_OK; ++p) {
             const int a0 = passes[p].act0, m = passes[p].n_act;
             items.assign(m, sd_batch_item{});
-            rows.clear();
+            rows.clear(); prows.clear();
             for (int j = 0; j < m; ++j) {
                 sd_batch_stream &s = *act[a0 + j];
                 verify_pass_rows(items[j], rows, s.target, s.seq, s.p_hist, sm.ld, s.err_words, g, Ls[a0 + j], s.target_len);
+                if (params) prows.resize(rows.size(), params_of(s));   // (every row of the stream takes its triple)
             }
             add_joiners(passes[p], 1);
             if ((rc = batch_forward(items.data(), (int)items.size(), sc.target.logits, sc.target.ld_logits, nullptr, nullptr, stream)) != SD_OK)
@@ -575,6 +590,7 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
             // residual / bonus sample below
             NormRequest nr = norm_request(sm, sc.target.norm_mode, scratch_rows(sc.target));
             nr.rows = (int)rows.size(); nr.workspace = sc.norm_workspace; nr.lists = lists_on ? list_base : nullptr;
+            nr.row_params = params ? prows.data() : nullptr;
             rc = sd_norm_batch_tiles(nr, rows.data(), 0, stream);
             if (lists_on) {
                 int r0 = 0;
@@ -639,23 +655,49 @@ static int check_result_blocks(const char *who, const sd_batch_stream *streams, 
     return SD_OK;
 }
 
+// what the _rows entries refuse in a parameter array (`what` names its entries: "stream", "prompt")
+static int check_row_params(const char *who, const char *what, const sd_row_sampling *params, int n) {
+    for (int i = 0; i < n; ++i) {
+        SD_REQUIRE(params[i].temperature != 0.0f, "%s: %s %d: temperature must be non-zero", who, what, i);
+        SD_REQUIRE(params[i].top_k >= 0, "%s: %s %d: top_k %d is negative", who, what, i, params[i].top_k);
+    }
+    return SD_OK;
+}
+
+static int batch_generate(const char *who, sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
+                          const sd_row_sampling *params, uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
+                          sd_lockstep_log *log, void *stream) {
+    SD_REQUIRE(streams && n_streams >= 1 && n_streams <= 16 && gamma >= 1 && gamma <= 16 && sampling && scratch && log &&
+               scratch->draft.logits && scratch->target.logits, "%s: bad arguments", who);
+    SD_REQUIRE(!random_seed || r_const, "%s: random_seed needs its uniform (r_const)", who);
+    if (int rc = check_result_blocks(who, streams, n_streams); rc != SD_OK) return rc;
+    if (params)
+        if (int rc = check_row_params(who, "stream", params, n_streams); rc != SD_OK) return rc;
+    return lockstep_loop(who, streams, n_streams, nullptr, gamma, *sampling, params, random_seed, r_const, *scratch, log, stream);
+}
+
 extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
                                       uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
                                       sd_lockstep_log *log, void *stream) {
-    SD_REQUIRE(streams && n_streams >= 1 && n_streams <= 16 && gamma >= 1 && gamma <= 16 && sampling && scratch && log &&
-               scratch->draft.logits && scratch->target.logits, "sd_spec_batch_generate: bad arguments");
-    SD_REQUIRE(!random_seed || r_const, "sd_spec_batch_generate: random_seed needs its uniform (r_const)");
-    if (int rc = check_result_blocks("sd_spec_batch_generate", streams, n_streams); rc != SD_OK) return rc;
-    return lockstep_loop("sd_spec_batch_generate", streams, n_streams, nullptr, gamma, *sampling, random_seed, r_const, *scratch, log,
-                         stream);
+    return batch_generate("sd_spec_batch_generate", streams, n_streams, gamma, sampling, nullptr, random_seed, r_const, scratch, log,
+                          stream);
+}
+
+extern "C" int sd_spec_batch_generate_rows(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
+                                           uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
+                                           sd_lockstep_log *log, void *stream, const sd_row_sampling *stream_params) {
+    if (!stream_params) return sd_spec_batch_generate(streams, n_streams, gamma, sampling, random_seed, r_const, scratch, log, stream);
+    return batch_generate("sd_spec_batch_generate_rows", streams, n_streams, gamma, sampling, stream_params, random_seed, r_const,
+                          scratch, log, stream);
 }
 
 // The two entry points of the prompt queue: `who` names the one that was called; without donors (shared_rows 0) the loop is
 // sd_spec_queue_generate's, pass for pass.  n_passes_out: how many ints of passes_out the entry point documents.
 static int queue_generate(const char *who, int n_passes_out, sd_session *donor_draft, sd_session *donor_target, int shared_rows,
                           sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
-                          int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed, const float *r_const,
-                          const sd_spec_scratch *scratch, sd_lockstep_log *log, int *passes_out, void *stream) {
+                          int prefill_chunk, int gamma, const sd_sampling *sampling, const sd_row_sampling *params,
+                          uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log,
+                          int *passes_out, void *stream) {
     SD_REQUIRE(n_slots >= 1 && n_slots <= 16, "%s: n_slots %d outside 1..16", who, n_slots);
     SD_REQUIRE(gamma >= 1 && gamma <= 16, "%s: gamma %d outside 1..16", who, gamma);
     SD_REQUIRE(n_prompts >= 1 && prefill_chunk >= 0, "%s: n_prompts %d, prefill_chunk %d", who, n_prompts, prefill_chunk);
@@ -691,10 +733,12 @@ static int queue_generate(const char *who, int n_passes_out, sd_session *donor_d
         SD_REQUIRE(slots[i].draft->max_seq >= slot_cap - 2 && slots[i].target->max_seq >= slot_cap - 2,
                    "%s: slot %d: KV arenas of %d / %d positions, slot_cap %d needs %d", who, i, slots[i].draft->max_seq,
                    slots[i].target->max_seq, slot_cap, slot_cap - 2);
+    if (params)
+        if (int rc = check_row_params(who, "prompt", params, n_prompts); rc != SD_OK) return rc;
     PromptQueue q;
     q.prompts = prompts; q.n_prompts = n_prompts; q.prefill_chunk = prefill_chunk;
     q.donor_draft = donor_draft; q.donor_target = donor_target; q.shared_rows = shared_rows;
-    const int rc = lockstep_loop(who, slots, n_slots, &q, gamma, *sampling, random_seed, r_const, *scratch, log, stream);
+    const int rc = lockstep_loop(who, slots, n_slots, &q, gamma, *sampling, params, random_seed, r_const, *scratch, log, stream);
     if (passes_out) {
         const int v[6] = {q.target_passes, q.draft_passes, q.extra_passes, q.prefill_passes, q.prompt_rows, q.copied_rows};
         for (int i = 0; i < n_passes_out; ++i) passes_out[i] = v[i];
@@ -707,7 +751,7 @@ extern "C" int sd_spec_queue_generate(sd_batch_stream *slots, int n_slots, int s
                                       const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log, int *passes_out,
                                       void *stream) {
     return queue_generate("sd_spec_queue_generate", 4, nullptr, nullptr, 0, slots, n_slots, slot_cap, prompts, n_prompts,
-                          prefill_chunk, gamma, sampling, random_seed, r_const, scratch, log, passes_out, stream);
+                          prefill_chunk, gamma, sampling, nullptr, random_seed, r_const, scratch, log, passes_out, stream);
 }
 
 extern "C" int sd_spec_queue_generate_shared(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
@@ -716,7 +760,21 @@ extern "C" int sd_spec_queue_generate_shared(sd_batch_stream *slots, int n_slots
                                              int *passes_out, void *stream, sd_session *donor_draft, sd_session *donor_target,
                                              int shared_rows) {
     return queue_generate("sd_spec_queue_generate_shared", 6, donor_draft, donor_target, shared_rows, slots, n_slots, slot_cap,
-                          prompts, n_prompts, prefill_chunk, gamma, sampling, random_seed, r_const, scratch, log, passes_out, stream);
+                          prompts, n_prompts, prefill_chunk, gamma, sampling, nullptr, random_seed, r_const, scratch, log, passes_out,
+                          stream);
+}
+
+extern "C" int sd_spec_queue_generate_rows(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
+                                           int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
+                                           const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log,
+                                           int *passes_out, void *stream, sd_session *donor_draft, sd_session *donor_target,
+                                           int shared_rows, const sd_row_sampling *prompt_params) {
+    if (!prompt_params)
+        return sd_spec_queue_generate_shared(slots, n_slots, slot_cap, prompts, n_prompts, prefill_chunk, gamma, sampling, random_seed,
+                                             r_const, scratch, log, passes_out, stream, donor_draft, donor_target, shared_rows);
+    return queue_generate("sd_spec_queue_generate_rows", 6, donor_draft, donor_target, shared_rows, slots, n_slots, slot_cap, prompts,
+                          n_prompts, prefill_chunk, gamma, sampling, prompt_params, random_seed, r_const, scratch, log, passes_out,
+                          stream);
 }
 
 // ---- the width-w loop of sampling/multi.py in native code (reference speculative_sampling.py:1379-1716, strategy "iid")

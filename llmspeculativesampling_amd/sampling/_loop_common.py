@@ -5,7 +5,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .._lib import SdHeadScratch, SdLockstepLog, SdSampling, SdSeqState, SdSpecScratch, SdSpecStream
+from .._lib import SdHeadScratch, SdLockstepLog, SdRowSampling, SdSampling, SdSeqState, SdSpecScratch, SdSpecStream
 from ..noise import DeviceNoise, HostTorchNoise
 from .kvcache_model import KVCacheModel
 
@@ -91,6 +91,45 @@ def sampling_block(temperature, top_k, top_p, V: int, ld: int, eos_token_id) -> 
     """What a native loop samples with and stops on; ``None`` / 0 switch a filter off, no EOS is -1."""
     return SdSampling(float(temperature), int(top_k or 0), float(top_p or 0.0), int(V), int(ld),
                       -1 if eos_token_id is None else int(eos_token_id))
+
+
+def _per_request(x) -> bool:
+    return isinstance(x, (list, tuple)) or (isinstance(x, (np.ndarray, torch.Tensor)) and x.ndim > 0)
+
+
+def row_sampling(n: int, what: str, temperature, top_k, top_p):
+    """Per-request ``temperature`` / ``top_k`` / ``top_p`` of the lock-step loops: each a scalar (broadcast) or a sequence with
+    one entry per ``what`` ("prompt", "stream"), ``n`` of them.  Returns ``None`` when all three are scalars - the call then
+    takes the scalar entry point as before, unchecked as before - else the ``n`` (temperature, top_k, top_p) triples; raises
+    ValueError naming the parameter for a sequence of another length, a temperature of 0, a negative or non-integer top_k.
+    Touches no model and no GPU."""
+    given = {"temperature": temperature, "top_k": top_k, "top_p": top_p}
+    if not any(_per_request(v) for v in given.values()):
+        return None
+    cols = {}
+    for name, v in given.items():
+        if not _per_request(v):
+            cols[name] = [v] * n
+            continue
+        if len(v) != n:
+            raise ValueError(f"{name}: {len(v)} entries for {n} {what}s")
+        cols[name] = [x.item() if isinstance(x, (np.generic, torch.Tensor)) else x for x in v]
+    triples = []
+    for i, (t, k, p) in enumerate(zip(cols["temperature"], cols["top_k"], cols["top_p"])):
+        if isinstance(t, bool) or not isinstance(t, (int, float)) or float(t) == 0.0:
+            raise ValueError(f"temperature: {what} {i}: a non-zero number is required, not {t!r}")
+        k = 0 if k is None else k
+        if isinstance(k, bool) or not isinstance(k, (int, float)) or k != int(k) or k < 0:
+            raise ValueError(f"top_k: {what} {i}: an integer >= 0 is required, not {k!r}")
+        if p is not None and (isinstance(p, bool) or not isinstance(p, (int, float))):
+            raise ValueError(f"top_p: {what} {i}: a number is required, not {p!r}")
+        triples.append((float(t), int(k), float(p or 0.0)))
+    return triples
+
+
+def row_sampling_array(triples):
+    """The SdRowSampling array of row_sampling's triples (``None`` stays ``None``: the NULL array of the _rows entries)."""
+    return None if triples is None else (SdRowSampling * len(triples))(*[SdRowSampling(*t) for t in triples])
 
 
 def head_scratch(session) -> SdHeadScratch:

@@ -23,7 +23,7 @@ from .._lib import lib, check, SdAcceptResult, SdBatchStream, SdQueuePrompt
 from ..engine import as_specdec_model, _stream, check_token_ids, same_device, batch_prefill
 from ..noise import DeviceNoise
 from ._loop_common import (LockstepLog, LoopLog, bind_spec_slot, lockstep_result, open_spec_slot, open_stream, reseed_uniforms,
-                           sampling_block, spec_scratch)
+                           row_sampling, row_sampling_array, sampling_block, spec_scratch)
 from .autoregressive_sampling import ArRun
 from .kvcache_model import KVCacheModel
 
@@ -55,7 +55,16 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
                                top_p: float = 0, random_seed: int = None, details: bool = False,
                                seeds: Optional[Sequence[int]] = None, _timing: Optional[dict] = None):
     """B streams at once; ``prefixes[i]`` is (1, L_i) int64.  Returns a list of (1, len_i) tensors (and a list of
-    ``details`` dicts with the reference's keys when ``details``).  Device Philox RNG, stream i seeded ``seeds[i]``."""
+    ``details`` dicts with the reference's keys when ``details``).  Device Philox RNG, stream i seeded ``seeds[i]``.
+    ``temperature``, ``top_k`` and ``top_p`` each take one value for all streams or a sequence with one entry per stream
+    (``T_i``, ``k_i``, ``p_i``; a scalar beside a sequence is broadcast): stream i equals ``speculative_sampling(prefixes[i],
+    ..., temperature=T_i, top_k=k_i, top_p=p_i, rng=DeviceNoise(seeds[i]))``.  A sequence of another length, a temperature
+    entry of 0 or a negative / non-integer top_k entry raises ValueError before a model is touched.  With three scalars the
+    call is sd_spec_batch_generate's as before; with any sequence it goes to sd_spec_batch_generate_rows."""
+    try:
+        triples = row_sampling(len(prefixes), "stream", temperature, top_k, top_p)
+    except TypeError:
+        raise ValueError("prefixes: a sequence of (1, L) int64 prompts is required") from None
     draft_m, target_m = as_specdec_model(approx_model), as_specdec_model(target_model)
     same_device(draft_m, target_m)
     dev = target_m.device
@@ -78,7 +87,8 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
         L = pf.shape[1]
         T = L + max_len
         cap = T + gamma + 2
-        draft, target, seq32, err = open_spec_slot(draft_m, target_m, pf[0], cap, gamma, temperature, top_k, top_p)
+        draft, target, seq32, err = open_spec_slot(draft_m, target_m, pf[0], cap, gamma,
+                                                   *(triples[i] if triples else (temperature, top_k, top_p)))
         host = [int(t) for t in pf[0].tolist()]
         streams.append(_Stream(draft, target, seq32, err, DeviceNoise(seeds[i]),
                                LoopLog(host, cap, max_iters, gamma, q_fill=1.0), L, T, host.count(eos_token_id)))
@@ -106,10 +116,15 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
         it.acc_len_out, it.p_at_out, it.q_at_out = s.log.ptrs()[:3]
     vlog = LockstepLog(max_iters * 2)
     d0, t0 = streams[0].draft._session, streams[0].target._session
-    check(lib.sd_spec_batch_generate(arr, B, gamma, sampling_block(temperature, top_k, top_p, V, streams[0].draft._probs.stride(0),
-                                                                   eos_token_id),
-                                     int(random_seed or 0), r_const.data_ptr() if r_const is not None else None,
-                                     spec_scratch(d0, t0, norm_ws, per_pass), vlog.block, cu), "sd_spec_batch_generate")
+    # (with per-stream parameters the block's own triple is not read: stream 0's stands in)
+    args = (arr, B, gamma, sampling_block(*(triples[0] if triples else (temperature, top_k, top_p)), V,
+                                          streams[0].draft._probs.stride(0), eos_token_id),
+            int(random_seed or 0), r_const.data_ptr() if r_const is not None else None, spec_scratch(d0, t0, norm_ws, per_pass),
+            vlog.block, cu)
+    if triples is None:
+        check(lib.sd_spec_batch_generate(*args), "sd_spec_batch_generate")
+    else:
+        check(lib.sd_spec_batch_generate_rows(*args, row_sampling_array(triples)), "sd_spec_batch_generate_rows")
     if vlog.block.err:
         raise RuntimeError("s")
     if _timing is not None:
@@ -177,6 +192,12 @@ def speculative_sampling_queue(prefixes: Sequence[torch.Tensor], approx_model, t
     (default ``torch.initial_seed() + i``) from draw 0 wherever and whenever it is admitted: its tokens, ``acc_len`` and call
     counts equal those of ``speculative_sampling(prefixes[i], ..., max_len_i, rng=DeviceNoise(seeds[i]))``.  Returns the
     outputs in prompt order (and the ``details`` dicts of speculative_sampling_batch when ``details``).
+    ``temperature``, ``top_k`` and ``top_p`` each take one value for all prompts or a sequence with one entry per prompt
+    (``T_i``, ``k_i``, ``p_i``, the convention of ``max_len``; a scalar beside a sequence is broadcast): prompt i then equals
+    ``speculative_sampling(prefixes[i], ..., temperature=T_i, top_k=k_i, top_p=p_i, rng=DeviceNoise(seeds[i]))``, whichever
+    slot it decodes in and whatever its neighbours ask for.  A sequence of another length, a temperature entry of 0 or a
+    negative / non-integer top_k entry raises ValueError before a model is touched.  With three scalars the call takes the
+    scalar entry point as before; with any sequence it goes to sd_spec_queue_generate_rows.
     ``_timing`` receives "verify" entries as speculative_sampling_batch writes them, "iterations", "target_passes",
     "draft_passes", "extra_passes" (target passes that carried prompt rows only; "prefill_passes" of them ran while no
     stream was active), "prompt_rows" (target rows forwarded for prompts), "copied_rows" (0 here) and per prompt
@@ -201,7 +222,9 @@ def speculative_sampling_queue_shared(prefixes: Sequence[torch.Tensor], approx_m
     anyway.  ``_timing``: "prompt_rows" includes the donor's rows, "copied_rows" is the number of KV rows copied per model
     summed over the prompts, and the donor's prefill passes count in "target_passes", "draft_passes", "extra_passes" and
     "prefill_passes", so a call compares with its ``shared_prefix=0`` twin.  With 0 (the default) there is no donor and the
-    call is speculative_sampling_queue's, bit for bit and pass for pass.  (A function of its own: the queue's parameter list
+    call is speculative_sampling_queue's, bit for bit and pass for pass.  ``temperature``, ``top_k`` and ``top_p`` take
+    per-prompt sequences exactly as in speculative_sampling_queue: prompt i equals ``speculative_sampling(prefixes[i], ...,
+    temperature=T_i, top_k=k_i, top_p=p_i, rng=DeviceNoise(seeds[i]))`` up to that caveat.  (A function of its own: the queue's parameter list
     is pinned by its tests.)"""
     return _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max_len, gamma, temperature, top_k, top_p,
                   random_seed, details, seeds, slots, prefill_chunk, _timing, shared_prefix)
@@ -216,6 +239,9 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
         raise ValueError(f"prefill_chunk: a row count >= 0 is required, not {prefill_chunk!r}")
     if not 1 <= gamma <= 16:
         raise ValueError(f"gamma: 1..16, not {gamma}")
+    triples = row_sampling(len(prefixes), "prompt", temperature, top_k, top_p)
+    if triples is not None:                                       # (a slot's KVCacheModel and the block's own triple are not read)
+        temperature, top_k, top_p = triples[0]
     draft_m, target_m = as_specdec_model(approx_model), as_specdec_model(target_model)
     same_device(draft_m, target_m)
     dev = target_m.device
@@ -270,8 +296,11 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
             batch_prefill([ses], [head], [rows])
             donor_passes[side] = -(-rows // ses.max_rows)
     # (without donors sd_spec_queue_generate_shared is sd_spec_queue_generate, which has no room for the two row counts)
-    check(lib.sd_spec_queue_generate_shared(*args, *[ses.handle if ses else None for ses in donors], rows),
-          "sd_spec_queue_generate_shared")
+    args += (*[ses.handle if ses else None for ses in donors], rows)
+    if triples is None:
+        check(lib.sd_spec_queue_generate_shared(*args), "sd_spec_queue_generate_shared")
+    else:
+        check(lib.sd_spec_queue_generate_rows(*args, row_sampling_array(triples)), "sd_spec_queue_generate_rows")
     passes[4] += rows                                             # the donor's target rows are prompt rows too
     if vlog.block.err:
         raise RuntimeError("s")

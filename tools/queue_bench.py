@@ -5,8 +5,9 @@ gamma 4, 8 slots).
 
     python tools/queue_bench.py [--workloads ragged,uniform --reps 5 --json-out profiles/queue_bench.json]
     python tools/queue_bench.py --workloads shared --json-out profiles/queue_bench_shared_prefix.json
+    python tools/queue_bench.py --workloads mixed --json-out profiles/queue_bench_mixed_params.json
 
-Three decoding workloads, EOS off (every prompt generates its max_len):
+Decoding workloads, EOS off (every prompt generates its max_len):
   ragged   32 prompts with the lengths of harness.synthetic_prompts (bench.py --prompt-lens synthetic-c3), cut to what a
            slot's arenas hold, max_len alternating 32 / 128.  queue: one call, 8 slots.  batch: four calls of
            speculative_sampling_batch with 8 prompts each, in list order - each call runs until its slowest stream is done.
@@ -16,6 +17,12 @@ Three decoding workloads, EOS off (every prompt generates its max_len):
            prompt, max_len alternating 32 / 128, 8 slots.  Both arms are speculative_sampling_queue_shared: shared_prefix=0 (every prompt forwards all
            its rows) against shared_prefix=256 (the prefix goes through the models once, the prompts copy its K / V rows).
            Per arm also the target rows forwarded for prompts.
+  mixed    (--workloads mixed) the ragged prompts and budgets, but prompt i samples with class (i // 2) % 4 of MIXED_CLASSES - four
+           different (temperature, top_k, top_p), one of them with top_k == 0; the budgets alternate with i, so every class
+           holds four prompts of each budget (i % 4 would hand two classes the short budgets and two the long ones, and the
+           per-class arm calls without a straggler that no real load gives it).  mixed_queue: ONE speculative_sampling_queue call
+           with per-prompt parameter lists, 8 slots.  per_class_queues: what a caller had to do before the lists existed - four
+           queue calls, one per class, each with that class's 8 prompts and scalar parameters, 8 slots.
   copy     (--workloads copy) no decoding: sd_session_copy_kv alone at the target's KV shape, 256 and 512 rows to 1 and 8
            destinations - device-event time per launch over 20 launches after 3 warm-up launches, and the bytes read plus
            the bytes written over that time.
@@ -42,6 +49,7 @@ from llmspeculativesampling_amd.sampling import speculative_sampling_batch, spec
 
 SLOTS, GAMMA = 8, 4
 SHARED = 256                                                      # tokens of the `shared` workload's common prefix
+MIXED_CLASSES = [(1.0, 20, 0.9), (0.7, 50, 0.95), (1.0, 0, 0.9), (1.3, 5, 0.0)]   # (temperature, top_k, top_p) of `mixed`
 
 
 def prefill_passes(lens):
@@ -116,6 +124,9 @@ def main():
         head = torch.from_numpy(np.random.default_rng(77).integers(3, tcfg.vocab_size, size=(1, SHARED)))
         ps = [torch.cat([head, p[:, :min(256, cut - SHARED)]], 1).cuda() for p in synthetic_prompts(100, tcfg.vocab_size, seed=5)[:32]]
         work["shared"] = (ps, [32 if i % 2 == 0 else 128 for i in range(32)])
+    if "mixed" in a.workloads:
+        ps = [p[:, :cut].cuda() for p in synthetic_prompts(100, tcfg.vocab_size, seed=5)[:32]]
+        work["mixed"] = (ps, [32 if i % 2 == 0 else 128 for i in range(32)])
     out = {"config": {k: v for k, v in vars(a).items() if k != "json_out"}, "dtype": "bfloat16", "slots": SLOTS, "gamma": GAMMA,
            "workloads": {}}
     if "copy" in a.workloads:
@@ -145,7 +156,32 @@ def main():
                 streams += [v[2] for v in t["verify"]]
             return outs, dict(iterations=iters, target_passes=passes, extra_passes=None, mean_streams=float(np.mean(streams)))
 
+        def mixed_queue(seed0):
+            t = {}
+            cls = [MIXED_CLASSES[(i // 2) % 4] for i in range(len(prompts))]
+            outs = speculative_sampling_queue(prompts, dm, tm, -1, None, budgets, gamma=GAMMA, temperature=[c[0] for c in cls],
+                                              top_k=[c[1] for c in cls], top_p=[c[2] for c in cls],
+                                              seeds=[seed0 + i for i in range(len(prompts))], slots=SLOTS, _timing=t)
+            return outs, dict(iterations=t["iterations"], target_passes=t["target_passes"], extra_passes=t["extra_passes"],
+                              mean_streams=float(np.mean([v[2] for v in t["verify"]])), calls=1)
+
+        def per_class_queues(seed0):
+            outs, iters, passes, extra, streams = [None] * len(prompts), 0, 0, 0, []
+            for c, (T, k, pp) in enumerate(MIXED_CLASSES):
+                ids = [i for i in range(len(prompts)) if (i // 2) % 4 == c]
+                t = {}
+                got = speculative_sampling_queue([prompts[i] for i in ids], dm, tm, -1, None, [budgets[i] for i in ids], gamma=GAMMA,
+                                                 temperature=T, top_k=k, top_p=pp, seeds=[seed0 + i for i in ids], slots=SLOTS, _timing=t)
+                for i, o in zip(ids, got):
+                    outs[i] = o
+                iters, passes, extra = iters + t["iterations"], passes + t["target_passes"], extra + t["extra_passes"]
+                streams += [v[2] for v in t["verify"]]
+            return outs, dict(iterations=iters, target_passes=passes, extra_passes=extra, mean_streams=float(np.mean(streams)),
+                              calls=len(MIXED_CLASSES))
+
         arms = {"queue": queue, "batch": batch}
+        if name == "mixed":
+            arms = {"mixed_queue": mixed_queue, "per_class_queues": per_class_queues}
         if name == "shared":
             arms = {"shared_prefix_0": lambda seed0: queue(seed0, shared_prefix=0),
                     f"shared_prefix_{SHARED}": lambda seed0: queue(seed0, shared_prefix=SHARED)}
@@ -165,7 +201,11 @@ def main():
                 rates[arm].append(sum(min(o.shape[1] - L, m) for o, L, m in zip(outs, lens, budgets)) / dt)
                 stats[arm] = st
         res = {arm: dict(stats[arm], tokens_per_s_reps=v, tokens_per_s_median=float(np.median(v))) for arm, v in rates.items()}
-        if name == "shared":
+        if name == "mixed":
+            res["classes"] = [dict(temperature=T, top_k=k, top_p=pp) for T, k, pp in MIXED_CLASSES]
+            res["mixed_over_per_class_tokens_per_s"] = res["mixed_queue"]["tokens_per_s_median"] / \
+                res["per_class_queues"]["tokens_per_s_median"]
+        elif name == "shared":
             res["shared_over_plain_tokens_per_s"] = res[f"shared_prefix_{SHARED}"]["tokens_per_s_median"] / \
                 res["shared_prefix_0"]["tokens_per_s_median"]
         else:
