@@ -746,6 +746,58 @@ size_t sd_ar_block_bytes(int n_streams);
 int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
                          void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream);
 
+/* ---- Per-token target log-probabilities.  For a token t that a loop emits at position i, the score is
+ * x[t] - log sum_v exp(x[v]) in fp32, x = the target model's raw logit row for position i - 1: rounded to the weights'
+ * 16-bit type where the rows still have to be (SD_NORM_ROUND_*), taken BEFORE temperature, top_k and top_p - what the model
+ * says, not what the sampler drew from.  Its mean over a call's new tokens is the reference harness' get_score
+ * (evaluation.py:109-124) without a second target pass.
+ * sd_token_logprobs scores up to 16 items x 17 rows in one launch on `stream` (one workgroup per scored row).  An item is one
+ * stream's `rows` consecutive fp32 logit rows (row stride ld >= V; no alignment asked of ld or of the rows), the device
+ * tokens to score them at (row r at tokens[r]), `rows` device output floats and `res`, a device result block or NULL: with
+ * it only rows r <= res->n_accepted are scored and the other output floats stay untouched, so the launch goes behind the
+ * accept / resample launch that fills the block.  `items` is a host array; mode: SD_NORM_ROUND_BF16 / _F16 or 0 (bits 0-1,
+ * the other bits are not read).  A token outside [0, V) scores NaN and reads nothing; a NaN in a row gives NaN for that row;
+ * -inf entries weigh nothing and a row of nothing else gives NaN.  Refused with SD_ERR_INVALID before any launch: a NULL
+ * argument (res excepted), n_items outside 1..16, V < 1, both rounding bits, rows outside 1..17, ld < V. */
+typedef struct {
+    const float *logits;
+    long ld;
+    int32_t rows;
+    const int32_t *tokens;
+    const sd_accept_result *res;
+    float *out;
+} sd_logprob_item;
+int sd_token_logprobs(const sd_logprob_item *items, int n_items, int V, int mode, void *stream);
+/* sd_logprob_block: what a loop needs to return those scores with its tokens; caller-owned like the blocks above.  dev
+ * (device) and host (pinned host): 16 x 17 floats each, stream (slot) i's slice at i * 17.  logprob_out[k]: a host float array
+ * per stream - per prompt in the queue - with the capacity of that stream's host token buffer; entry j is the score of the
+ * j-th token the call emitted for it (position L + j, L = its length on entry).  The _logprobs entries take exactly what the
+ * widest entry of their loop takes, plus the block; a NULL block is that entry itself, launch for launch.  With a block, per
+ * iteration or step: ONE sd_token_logprobs launch over all active streams behind the accept / resample launch (behind the
+ * sampler in the autoregressive loop, one row per stream at seq[len]), ONE more async copy of the float slices beside the
+ * copy of the result blocks, ahead of the one wait; after it the stream's n_accepted + 1 floats are appended where its tokens
+ * are.  A failed iteration appends none.  Every verify pass of the lock-step loops writes the same logit slab, so in an
+ * iteration whose verify takes several passes the loop - with a block only - accepts (sd_accept_batch) and scores a pass's
+ * streams before it enqueues the next pass; still one copy and one wait.  The rows are read where the forward left them:
+ * scratch->target.logits in the lock-step loops, the head's own slab in the other two.  Refused with SD_ERR_INVALID behind
+ * the entry's own refusals, before anything is launched: a NULL dev, host or logprob_out, or a NULL array in it. */
+typedef struct { float *dev, *host; float **logprob_out; } sd_logprob_block;
+int sd_spec_generate_logprobs(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling, const sd_spec_scratch *scratch,
+                              sd_seq_state *seq, uint64_t random_seed, const float *r_const, void *stream,
+                              const sd_logprob_block *logprobs);
+int sd_spec_batch_generate_logprobs(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
+                                    uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
+                                    sd_lockstep_log *log, void *stream, const sd_row_sampling *stream_params,
+                                    const sd_logprob_block *logprobs);
+int sd_spec_queue_generate_logprobs(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
+                                    int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
+                                    const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log, int *passes_out,
+                                    void *stream, sd_session *donor_draft, sd_session *donor_target, int shared_rows,
+                                    const sd_row_sampling *prompt_params, const sd_logprob_block *logprobs);
+int sd_ar_batch_generate_logprobs(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
+                                  void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream,
+                                  const sd_logprob_block *logprobs);
+
 /* ------------------------------------------------------------------------------------------
  * Tensor parallelism of one decoder over the GPUs of a node (BASELINE config 5: Llama-2-70b, TP = 8 over xGMI).
  * The reference is single-process: this is new capability behind the same call signatures.

@@ -127,6 +127,18 @@ class SdArLog(C.Structure):
                 ("n_steps", C.c_int32), ("err", C.c_int32)]
 
 
+class SdLogprobItem(C.Structure):
+    _fields_ = [("logits", C.c_void_p), ("ld", C.c_long), ("rows", C.c_int32), ("tokens", C.c_void_p), ("res", C.c_void_p),
+                ("out", C.c_void_p)]
+
+
+class SdLogprobBlock(C.Structure):
+    _fields_ = [("dev", C.c_void_p), ("host", C.c_void_p), ("logprob_out", C.POINTER(C.c_void_p))]
+
+
+LOGPROB_SLICE, LOGPROB_STREAMS = 17, 16                  # sd_logprob_block: 16 streams x 17 floats, device and pinned host
+
+
 class SdBatchItem(C.Structure):
     _fields_ = [("session", C.c_void_p), ("seq", C.c_void_p), ("pos0", C.c_int32), ("n_new", C.c_int32),
                 ("n_logits", C.c_int32)]
@@ -169,7 +181,8 @@ C_STRUCTS = {"sd_accept_result": SdAcceptResult, "sd_norm_row": SdNormRow, "sd_r
              "sd_queue_pass": SdQueuePass, "sd_queue_chunk": SdQueueChunk, "sd_kv_copy_item": SdKvCopyItem,
              "sd_ar_stream": SdArStream, "sd_sampling": SdSampling, "sd_head_scratch": SdHeadScratch,
              "sd_spec_stream": SdSpecStream, "sd_spec_scratch": SdSpecScratch, "sd_lockstep_log": SdLockstepLog, "sd_seq_state": SdSeqState,
-             "sd_ar_log": SdArLog, "sd_batch_item": SdBatchItem, "sd_model_config": SdModelConfig,
+             "sd_ar_log": SdArLog, "sd_batch_item": SdBatchItem,
+             "sd_logprob_item": SdLogprobItem, "sd_logprob_block": SdLogprobBlock, "sd_model_config": SdModelConfig,
              "sd_gemm_route_info": SdGemmRouteInfo, "sd_model_weights": SdModelWeights}
 
 # every symbol include/specdec.h declares: (name, restype, argtypes)
@@ -251,6 +264,16 @@ SYMBOLS = [
     ("sd_spec_generate", _I, [_P(SdSpecStream), _I, _P(SdSampling), _P(SdSpecScratch), _P(SdSeqState), _U64, _VP, _VP]),
     ("sd_ar_block_bytes", C.c_size_t, [_I]),
     ("sd_ar_batch_generate", _I, [_P(SdArStream), _I, _P(SdSampling), _P(SdHeadScratch), _VP, _VP, _VP, _P(SdArLog), _VP]),
+    ("sd_token_logprobs", _I, [_P(SdLogprobItem), _I, _I, _I, _VP]),
+    ("sd_spec_generate_logprobs", _I, [_P(SdSpecStream), _I, _P(SdSampling), _P(SdSpecScratch), _P(SdSeqState), _U64, _VP, _VP,
+                                       _P(SdLogprobBlock)]),
+    ("sd_spec_batch_generate_logprobs", _I, [_P(SdBatchStream), _I, _I, _P(SdSampling), _U64, _VP, _P(SdSpecScratch),
+                                             _P(SdLockstepLog), _VP, _P(SdRowSampling), _P(SdLogprobBlock)]),
+    ("sd_spec_queue_generate_logprobs", _I, [_P(SdBatchStream), _I, _I, _P(SdQueuePrompt), _I, _I, _I, _P(SdSampling), _U64, _VP,
+                                             _P(SdSpecScratch), _P(SdLockstepLog), _VP, _VP, _VP, _VP, _I, _P(SdRowSampling),
+                                             _P(SdLogprobBlock)]),
+    ("sd_ar_batch_generate_logprobs", _I, [_P(SdArStream), _I, _P(SdSampling), _P(SdHeadScratch), _VP, _VP, _VP, _P(SdArLog), _VP,
+                                           _P(SdLogprobBlock)]),
     ("sd_batch_forward", _I, [C.POINTER(SdBatchItem), _I, _VP, _L, _VP]),
     ("sd_batch_prefill", _I, [C.POINTER(SdBatchItem), _I, _VP]),
     ("sd_tp_unique_id", _I, [_VP]),

@@ -41,6 +41,13 @@ template <> __device__ __forceinline__ float from_f<float>(float x) { return x; 
 template <> __device__ __forceinline__ bf16_t from_f<bf16_t>(float x) { return (bf16_t)x; }
 template <> __device__ __forceinline__ f16_t from_f<f16_t>(float x) { return (f16_t)x; }
 template <typename T> __device__ __forceinline__ float rnd(float x) { return to_f(from_f<T>(x)); }
+// ... and the same rounding by a run-time code, as the sampler kernels and the log-probability kernel take it:
+// dt 0 fp32 (no rounding), 1 bf16, 2 fp16
+__device__ __forceinline__ float rnd_dt(float x, int dt) {
+    return dt == 1 ? (float)(bf16_t)x : (dt == 2 ? (float)(_Float16)x : x);
+}
+// value of a logit as the model's head leaves it: mode bits 0-1 = rounding of the fp32 accumulator (1 bf16, 2 fp16)
+__device__ __forceinline__ float head_round(float x, int mode) { return rnd_dt(x, mode & 3); }
 
 // ---- wave / block reductions (wave = 64 lanes)
 // Data-parallel-primitive moves instead of __shfl_xor (which hipcc lowers to six dependent ds_bpermute_b32 through the

@@ -18,6 +18,7 @@
 #include "normload_kernels.h"
 #include "multi_kernels.h"
 #include "kv_copy_kernels.h"
+#include "logprob_kernels.h"
 #include "sampler_host.h"
 
 static thread_local char g_err[512] = "";

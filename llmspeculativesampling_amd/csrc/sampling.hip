@@ -119,12 +119,7 @@ __device__ __forceinline__ float philox_uniform(uint64_t seed, uint64_t draw) {
 // ---- storage-dtype arithmetic (SD_NORM_* in specdec.h).  The reference keeps OPT's logits and the whole norm_logits /
 // sample / max_fn chain in the weight dtype (modeling_opt.py:974, utils.py:182-245); torch's CPU kernels for bf16 / fp16
 // compute each op in fp32 and round its result to the tensor dtype, so "dtype-faithful" = fp32 math with a rounding
-// to the storage type wherever torch materialises a tensor.  dt: 0 fp32 (no rounding), 1 bf16, 2 fp16.
-__device__ __forceinline__ float rnd_dt(float x, int dt) {
-    return dt == 1 ? (float)(bf16_t)x : (dt == 2 ? (float)(_Float16)x : x);
-}
-// value of a logit as the model's head leaves it: mode bits 0-1 = rounding of the fp32 accumulator (1 bf16, 2 fp16)
-__device__ __forceinline__ float head_round(float x, int mode) { return rnd_dt(x, mode & 3); }
+// to the storage type wherever torch materialises a tensor.  rnd_dt and head_round (common.h) are that rounding.
 // z = logits / temperature (utils.py:197), rounded when the row lives in a 16-bit dtype (mode bits 4-5)
 __device__ __forceinline__ float scaled_logit(float x, float temperature, int mode) {
     return rnd_dt(head_round(x, mode) / temperature, (mode >> 4) & 3);

@@ -145,15 +145,56 @@ static bool commit_result(const sd_accept_result &r, int L, int g, int32_t *host
     return true;
 }
 
+// ---- per-token target log-probabilities (include/specdec.h has the definition and the loops' contract) -----------
+extern "C" int sd_token_logprobs(const sd_logprob_item *items, int n_items, int V, int mode, void *stream) {
+    SD_REQUIRE(items, "sd_token_logprobs: null argument");
+    SD_REQUIRE(n_items >= 1 && n_items <= LOGPROB_MAX_ITEMS, "sd_token_logprobs: n_items %d outside 1..%d", n_items, LOGPROB_MAX_ITEMS);
+    SD_REQUIRE(V >= 1 && (mode & 3) != 3, "sd_token_logprobs: V %d, mode %#x", V, mode);
+    LogprobTab t = {};
+    int max_rows = 0;
+    for (int i = 0; i < n_items; ++i) {
+        const sd_logprob_item &it = items[i];
+        SD_REQUIRE(it.logits && it.tokens && it.out, "sd_token_logprobs: item %d: null argument", i);
+        SD_REQUIRE(it.rows >= 1 && it.rows <= LOGPROB_MAX_ROWS, "sd_token_logprobs: item %d: rows %d outside 1..%d", i, it.rows,
+                   LOGPROB_MAX_ROWS);
+        SD_REQUIRE(it.ld >= V, "sd_token_logprobs: item %d: ld %ld < V %d", i, it.ld, V);
+        t.logits[i] = it.logits; t.tokens[i] = it.tokens; t.res[i] = it.res; t.out[i] = it.out; t.ld[i] = it.ld; t.rows[i] = it.rows;
+        max_rows = std::max(max_rows, (int)it.rows);
+    }
+    return launch_token_logprobs(t, n_items, max_rows, V, mode & 3, (hipStream_t)stream);
+}
+
+enum { LP_SLICE = LOGPROB_MAX_ROWS };                             // floats per stream in sd_logprob_block.dev / host
+// what the _logprobs entries refuse in their block (behind the entry's own refusals): n arrays, one per stream / prompt
+static int check_logprob_block(const char *who, const sd_logprob_block *lp, int n) {
+    SD_REQUIRE(lp->dev && lp->host && lp->logprob_out, "%s: logprobs: null pointer", who);
+    for (int i = 0; i < n; ++i) SD_REQUIRE(lp->logprob_out[i], "%s: logprobs: logprob_out[%d] is null", who, i);
+    return SD_OK;
+}
+// The gamma + 1 target rows of a stream whose sequence had L tokens: row r scores seq[L + r], the gamma drafted tokens and,
+// at seq[L + n_accepted], the token the resample appended.  `slot`: the stream's slice of the block.
+static sd_logprob_item verify_logprob_item(const sd_logprob_block &lp, int slot, const float *logits, long ld, int g,
+                                           const int32_t *seq, int L, const sd_accept_result *res_dev) {
+    return sd_logprob_item{logits, ld, g + 1, seq + L, res_dev, lp.dev + (size_t)slot * LP_SLICE};
+}
+// After the wait: the n_accepted + 1 scores of a committed result go where commit_result put its tokens (emitted-token numbers
+// first .. first + n_accepted)
+static void commit_logprobs(const sd_logprob_block &lp, int slot, float *out, int first, const sd_accept_result &r) {
+    for (int i = 0; i <= r.n_accepted; ++i) out[first + i] = lp.host[(size_t)slot * LP_SLICE + i];
+}
+
 // ---- one whole speculative iteration, enqueued natively ---------------------------------------
 // reference sampling/speculative_sampling.py:1934-2031 for the device-RNG mode: gamma x (draft forward +
 // norm_sample), one target forward over the uncached rows + norm_probs, accept scan, residual / bonus sample,
 // then the 208-byte result block is copied to pinned host memory.  Nothing here synchronises; the caller waits on
 // the stream once per iteration.  `timed`: the draft phase is ev.t[0] .. t[1], the verify phase ev.t[2] .. t[3].
 static int spec_iteration(const sd_spec_stream &dv, int g, const sd_sampling &sm, const sd_spec_scratch &sc, const Draws &d, int L,
-                          int draft_len, int target_len, const float *r_const, const LoopEvents &ev, bool timed, void *stream) {
+                          int draft_len, int target_len, const float *r_const, const LoopEvents &ev, bool timed, void *stream,
+                          const sd_logprob_block *lp) {
     SD_REQUIRE(L >= 1 && draft_len >= 0 && draft_len < L && target_len >= 0 && target_len < L + g,
                "sd_spec_generate: L=%d draft_len=%d target_len=%d", L, draft_len, target_len);
+    SD_REQUIRE(!lp || target_len <= L - 1, "sd_spec_generate_logprobs: target_len %d of %d tokens leaves fewer than gamma + 1 target rows",
+               target_len, L);
     hipStream_t st = (hipStream_t)stream;
     int rc;
     const bool tiles_ok = head_tiles_ok(sm.top_k, sm.temperature, sm.V, sm.ld);
@@ -209,13 +250,18 @@ static int spec_iteration(const sd_spec_stream &dv, int g, const sd_sampling &sm
                                           res_mode, stream)) != SD_OK)
             return rc;
     }
+    if (lp) {                                                     // `ho` is the target's: its gamma + 1 rows where the head left them
+        const sd_logprob_item it = verify_logprob_item(*lp, 0, ho.logits, ho.ld, g, dv.seq, L, dv.res_dev);
+        if ((rc = sd_token_logprobs(&it, 1, sm.V, ho.round | sc.target.norm_mode, stream)) != SD_OK) return rc;
+        SD_HIP_CHECK(hipMemcpyAsync(lp->host, lp->dev, sizeof(float) * (size_t)(g + 1), hipMemcpyDeviceToHost, st));
+    }
     SD_HIP_CHECK(hipMemcpyAsync(dv.res_host, dv.res_dev, sizeof(sd_accept_result), hipMemcpyDeviceToHost, st));
     return SD_OK;
 }
 
 // The device-RNG loop without the interpreter between iterations (reference speculative_sampling.py:1934-2046).
-extern "C" int sd_spec_generate(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling, const sd_spec_scratch *scratch,
-                                sd_seq_state *s, uint64_t random_seed, const float *r_const, void *stream) {
+static int spec_generate(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling, const sd_spec_scratch *scratch,
+                         sd_seq_state *s, uint64_t random_seed, const float *r_const, void *stream, const sd_logprob_block *lp) {
     SD_REQUIRE(dev && sampling && scratch && s && dev->draft && dev->target && dev->seq && dev->q_hist && dev->p_hist &&
                dev->err_words && dev->res_dev && dev->res_host && s->host_seq && scratch->draft.logits && scratch->target.logits,
                "sd_spec_generate: null argument");
@@ -229,8 +275,10 @@ extern "C" int sd_spec_generate(const sd_spec_stream *dev, int gamma, const sd_s
     SD_REQUIRE(sm.V == dev->draft->m->cfg.vocab && sm.V == dev->target->m->cfg.vocab && sm.ld >= sm.V,
                "sd_spec_generate: V %d (ld %ld), the models' vocabularies are %d / %d", sm.V, sm.ld, dev->draft->m->cfg.vocab,
                dev->target->m->cfg.vocab);
+    if (lp)
+        if (int rc = check_logprob_block("sd_spec_generate_logprobs", lp, 1); rc != SD_OK) return rc;
     refresh_env();
-    const int g = gamma;
+    const int g = gamma, L0 = s->len;
     const bool timed = s->draft_ms_out || s->target_ms_out;
     LoopEvents ev(timed ? 4 : 0, "sd_spec_generate");
     if (!ev.ok) return SD_ERR_HIP;
@@ -241,7 +289,7 @@ extern "C" int sd_spec_generate(const sd_spec_stream *dev, int gamma, const sd_s
         const int L = s->len, iters = s->n_iters;
         const Draws d = next_draws(s->seed, s->draw, g, random_seed);
         s->seed = d.seed; s->draw = d.draw;
-        if ((rc = spec_iteration(*dev, g, sm, *scratch, d, L, s->draft_len, s->target_len, r_const, ev, timed, stream)) != SD_OK) break;
+        if ((rc = spec_iteration(*dev, g, sm, *scratch, d, L, s->draft_len, s->target_len, r_const, ev, timed, stream, lp)) != SD_OK) break;
         SD_LOOP_HIP(hipEventRecord(ev.done, (hipStream_t)stream));
         if ((rc = poll_event(ev.done, "sd_spec_generate")) != SD_OK) break;
         const sd_accept_result r = *dev->res_host;
@@ -277,10 +325,21 @@ extern "C" int sd_spec_generate(const sd_spec_stream *dev, int gamma, const sd_s
             break;
         }
         commit_result(r, L, g, s->host_seq, &s->len, &s->draft_len, &s->target_len);      // (flags & 2 left the loop above)
+        if (lp) commit_logprobs(*lp, 0, lp->logprob_out[0], L - L0, r);
         for (int i = L; i < s->len; ++i) eos_total += s->host_seq[i] == sm.eos_token_id;
         if (eos_total > s->ori_eos_cnt) break;                    // the caller cuts after the first new EOS (:2033-2041)
     }
     return rc;
+}
+
+extern "C" int sd_spec_generate(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling, const sd_spec_scratch *scratch,
+                                sd_seq_state *s, uint64_t random_seed, const float *r_const, void *stream) {
+    return spec_generate(dev, gamma, sampling, scratch, s, random_seed, r_const, stream, nullptr);
+}
+extern "C" int sd_spec_generate_logprobs(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling,
+                                         const sd_spec_scratch *scratch, sd_seq_state *s, uint64_t random_seed, const float *r_const,
+                                         void *stream, const sd_logprob_block *logprobs) {
+    return spec_generate(dev, gamma, sampling, scratch, s, random_seed, r_const, stream, logprobs);
 }
 
 // ---- the prompt queue of the lock-step loop ---------------------------------------------------------------------
@@ -439,7 +498,8 @@ static int queue_idle_prefill(PromptQueue &q, sd_batch_stream *slots, const std:
 // with or without a prompt queue behind the streams' slots.
 // params (or NULL: sm's triple for everyone): per-request sampling parameters, indexed by stream - with a queue, by prompt.
 static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_streams, PromptQueue *q, int gamma, const sd_sampling &sm,
-                         const sd_row_sampling *params, uint64_t random_seed, const float *r_const, const sd_spec_scratch &sc, sd_lockstep_log *log, void *stream) {
+                         const sd_row_sampling *params, uint64_t random_seed, const float *r_const, const sd_spec_scratch &sc, sd_lockstep_log *log, void *stream,
+                         const sd_logprob_block *lp) {
     hipStream_t st = (hipStream_t)stream;
     const int g = gamma, n_err = 3 * g + 1;
     // rows per target pass (every verify row is a logit row: sd_model_max_pass_rows, 64 for a model whose lm_head or
@@ -492,7 +552,10 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
     const bool tiles_ok = head_tiles_ok(sm.top_k, sm.temperature, sm.V, sm.ld);
     // the triple of the request a stream runs: a queue's slot changes parameters when it changes hands
     auto params_of = [&](const sd_batch_stream &s) -> const sd_row_sampling & { return params[q ? q->occ[&s - streams] : &s - streams]; };
+    int L0[SD_MAX_STREAMS];                                       // (logprobs without a queue) the streams' lengths on entry
+    std::vector<sd_logprob_item> litems;
     for (int i = 0; i < n_streams; ++i) {
+        L0[i] = streams[i].len;
         streams[i].done = q ? 1 : 0; streams[i].calls = 0;
         if (q) { q->occ[i] = -1; q->joining[i] = false; }
     }
@@ -572,6 +635,21 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
         char *const list_base = sc.norm_workspace ? (char *)sc.norm_workspace + sd_norm_candrow_bytes(sc.max_rows_per_forward) : nullptr;
         const size_t list_stride = sd_cand_list_bytes(1);
         list_of.assign(n, nullptr);
+        const int res_mode = sc.target.norm_mode == sc.draft.norm_mode ? sc.target.norm_mode : 0;
+        // the accept item of active stream j
+        auto accept_item = [&](int j) {
+            const sd_batch_stream &s = *act[j];
+            sd_accept_item it = {};
+            it.p_hist = s.p_hist; it.q_hist = s.q_hist; it.seq = s.seq; it.L = Ls[j];
+            it.r = r_const; it.exp_noise = nullptr;
+            it.philox_seed = draws[j].seed; it.draw_scan = draws[j].scan0; it.draw_resample = draws[j].resample;
+            it.res = s.res_dev; it.err_flags = s.err_words; it.n_err = n_err;
+            return it;
+        };
+        // logprobs: every verify pass writes the same slab, sc.target.logits, so when the verify takes several passes each
+        // pass's streams are accepted and scored before the next pass is enqueued (no lists then: lists_on needs one pass)
+        const bool by_pass = lp && passes[0].n_act != n;
+        litems.clear();
         SD_LOOP_HIP(hipEventRecord(ev.t[0], st));
         for (int p = 0; p < n_passes && rc == SD_OK; ++p) {
             const int a0 = passes[p].act0, m = passes[p].n_act;
@@ -599,26 +677,44 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
                     r0 += items[j].n_new;
                 }
             }
+            if (!lp || rc != SD_OK) continue;
+            // the streams' last gamma + 1 logit rows, packed in stream order in the slab
+            const size_t l0 = litems.size();
+            for (int j = 0, r0 = 0; j < m; r0 += items[j++].n_new) {
+                const sd_batch_stream &s = *act[a0 + j];
+                if (items[j].n_new < g + 1) {
+                    sd_set_error("%s: logprobs: stream %d has %d verify rows, fewer than gamma + 1", who, (int)(&s - streams), items[j].n_new);
+                    rc = SD_ERR_INVALID;
+                    break;
+                }
+                litems.push_back(verify_logprob_item(*lp, (int)(&s - streams), sc.target.logits + (size_t)(r0 + items[j].n_new - (g + 1)) * sc.target.ld_logits,
+                                                     sc.target.ld_logits, g, s.seq, Ls[a0 + j], s.res_dev));
+            }
+            if (!by_pass || rc != SD_OK) continue;
+            aitems.clear();
+            for (int j = 0; j < m; ++j) aitems.push_back(accept_item(a0 + j));
+            if ((rc = sd_accept_batch(aitems.data(), m, sm.ld, sm.V, g, res_mode, stream)) != SD_OK) break;
+            rc = sd_token_logprobs(litems.data() + l0, m, sm.V, sc.target.norm_mode, stream);
         }
         if (rc != SD_OK) break;
         SD_LOOP_HIP(hipEventRecord(ev.t[1], st));
         // ---- accept scan + residual / bonus sample, all streams in two launches.  The scan reads probability rows L-1 ..
         // L+gamma-1 only, and this iteration wrote every one of them: the q rows in its draft steps, the p rows in the verify's
         // sd_norm_batch_tiles above, which writes whole rows.  So a slot's p_hist / q_hist never show a previous occupant.
-        aitems.assign(n, sd_accept_item{});
         for (int j = 0; j < n; ++j) {
             sd_batch_stream &s = *act[j];
             s.seed = draws[j].seed; s.draw = draws[j].draw;       // both forwards are enqueued: the rest of the iteration's draws
-            sd_accept_item &it = aitems[j];
-            it.p_hist = s.p_hist; it.q_hist = s.q_hist; it.seq = s.seq; it.L = Ls[j];
-            it.r = r_const; it.exp_noise = nullptr;
-            it.philox_seed = draws[j].seed; it.draw_scan = draws[j].scan0; it.draw_resample = draws[j].resample;
-            it.res = s.res_dev; it.err_flags = s.err_words; it.n_err = n_err;
         }
-        const int res_mode = sc.target.norm_mode == sc.draft.norm_mode ? sc.target.norm_mode : 0;
-        if (lists_on) rc = sd_accept_resample_batch(aitems.data(), n, sm.ld, sm.V, g, res_mode, list_of.data(), stream);
-        else rc = sd_accept_batch(aitems.data(), n, sm.ld, sm.V, g, res_mode, stream);
-        if (rc != SD_OK) break;
+        if (!by_pass) {
+            aitems.clear();
+            for (int j = 0; j < n; ++j) aitems.push_back(accept_item(j));
+            if (lists_on) rc = sd_accept_resample_batch(aitems.data(), n, sm.ld, sm.V, g, res_mode, list_of.data(), stream);
+            else rc = sd_accept_batch(aitems.data(), n, sm.ld, sm.V, g, res_mode, stream);
+            if (rc != SD_OK) break;
+            if (lp && (rc = sd_token_logprobs(litems.data(), n, sm.V, sc.target.norm_mode, stream)) != SD_OK) break;
+        }
+        if (lp)
+            SD_LOOP_HIP(hipMemcpyAsync(lp->host, lp->dev, sizeof(float) * (size_t)n_streams * LP_SLICE, hipMemcpyDeviceToHost, st));
         SD_LOOP_HIP(hipMemcpyAsync(streams[0].res_host, streams[0].res_dev, sizeof(sd_accept_result) * (size_t)n_streams,
                                    hipMemcpyDeviceToHost, st));
         SD_LOOP_HIP(hipEventRecord(ev.done, st));
@@ -639,6 +735,10 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
             log_ratios(s.p_at_out, s.q_at_out, (size_t)s.calls, g, r.p_at, r.q_at);
             ++s.calls;
             commit_result(r, Ls[j], g, s.host_seq, &s.len, &s.draft_len, &s.target_len);
+            if (lp) {                                             // a queue's slot writes to the array of the prompt it runs
+                const int slot = (int)(&s - streams), k = q ? q->occ[slot] : slot;
+                commit_logprobs(*lp, slot, lp->logprob_out[k], Ls[j] - (q ? q->prompts[k].L : L0[slot]), r);
+            }
             int eos_total = 0;
             for (int i = 0; i < s.len; ++i) eos_total += s.host_seq[i] == sm.eos_token_id;
             if (eos_total > s.ori_eos_cnt) s.done = 1;            // the caller cuts after the first new EOS
@@ -666,14 +766,16 @@ static int check_row_params(const char *who, const char *what, const sd_row_samp
 
 static int batch_generate(const char *who, sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
                           const sd_row_sampling *params, uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
-                          sd_lockstep_log *log, void *stream) {
+                          sd_lockstep_log *log, void *stream, const sd_logprob_block *lp = nullptr) {
     SD_REQUIRE(streams && n_streams >= 1 && n_streams <= 16 && gamma >= 1 && gamma <= 16 && sampling && scratch && log &&
                scratch->draft.logits && scratch->target.logits, "%s: bad arguments", who);
     SD_REQUIRE(!random_seed || r_const, "%s: random_seed needs its uniform (r_const)", who);
     if (int rc = check_result_blocks(who, streams, n_streams); rc != SD_OK) return rc;
     if (params)
         if (int rc = check_row_params(who, "stream", params, n_streams); rc != SD_OK) return rc;
-    return lockstep_loop(who, streams, n_streams, nullptr, gamma, *sampling, params, random_seed, r_const, *scratch, log, stream);
+    if (lp)
+        if (int rc = check_logprob_block(who, lp, n_streams); rc != SD_OK) return rc;
+    return lockstep_loop(who, streams, n_streams, nullptr, gamma, *sampling, params, random_seed, r_const, *scratch, log, stream, lp);
 }
 
 extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
@@ -697,7 +799,7 @@ static int queue_generate(const char *who, int n_passes_out, sd_session *donor_d
                           sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
                           int prefill_chunk, int gamma, const sd_sampling *sampling, const sd_row_sampling *params,
                           uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log,
-                          int *passes_out, void *stream) {
+                          int *passes_out, void *stream, const sd_logprob_block *lp = nullptr) {
     SD_REQUIRE(n_slots >= 1 && n_slots <= 16, "%s: n_slots %d outside 1..16", who, n_slots);
     SD_REQUIRE(gamma >= 1 && gamma <= 16, "%s: gamma %d outside 1..16", who, gamma);
     SD_REQUIRE(n_prompts >= 1 && prefill_chunk >= 0, "%s: n_prompts %d, prefill_chunk %d", who, n_prompts, prefill_chunk);
@@ -738,7 +840,9 @@ static int queue_generate(const char *who, int n_passes_out, sd_session *donor_d
     PromptQueue q;
     q.prompts = prompts; q.n_prompts = n_prompts; q.prefill_chunk = prefill_chunk;
     q.donor_draft = donor_draft; q.donor_target = donor_target; q.shared_rows = shared_rows;
-    const int rc = lockstep_loop(who, slots, n_slots, &q, gamma, *sampling, params, random_seed, r_const, *scratch, log, stream);
+    if (lp)
+        if (int rc = check_logprob_block(who, lp, n_prompts); rc != SD_OK) return rc;
+    const int rc = lockstep_loop(who, slots, n_slots, &q, gamma, *sampling, params, random_seed, r_const, *scratch, log, stream, lp);
     if (passes_out) {
         const int v[6] = {q.target_passes, q.draft_passes, q.extra_passes, q.prefill_passes, q.prompt_rows, q.copied_rows};
         for (int i = 0; i < n_passes_out; ++i) passes_out[i] = v[i];
@@ -775,6 +879,30 @@ extern "C" int sd_spec_queue_generate_rows(sd_batch_stream *slots, int n_slots, 
     return queue_generate("sd_spec_queue_generate_rows", 6, donor_draft, donor_target, shared_rows, slots, n_slots, slot_cap, prompts,
                           n_prompts, prefill_chunk, gamma, sampling, prompt_params, random_seed, r_const, scratch, log, passes_out,
                           stream);
+}
+
+// The lock-step loops with per-token target log-probabilities: the _rows entries' arguments plus the block (NULL: those entries)
+extern "C" int sd_spec_batch_generate_logprobs(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
+                                               uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
+                                               sd_lockstep_log *log, void *stream, const sd_row_sampling *stream_params,
+                                               const sd_logprob_block *logprobs) {
+    if (!logprobs)
+        return sd_spec_batch_generate_rows(streams, n_streams, gamma, sampling, random_seed, r_const, scratch, log, stream, stream_params);
+    return batch_generate("sd_spec_batch_generate_logprobs", streams, n_streams, gamma, sampling, stream_params, random_seed, r_const,
+                          scratch, log, stream, logprobs);
+}
+
+extern "C" int sd_spec_queue_generate_logprobs(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
+                                               int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
+                                               const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log,
+                                               int *passes_out, void *stream, sd_session *donor_draft, sd_session *donor_target,
+                                               int shared_rows, const sd_row_sampling *prompt_params, const sd_logprob_block *logprobs) {
+    if (!logprobs)
+        return sd_spec_queue_generate_rows(slots, n_slots, slot_cap, prompts, n_prompts, prefill_chunk, gamma, sampling, random_seed,
+                                           r_const, scratch, log, passes_out, stream, donor_draft, donor_target, shared_rows, prompt_params);
+    return queue_generate("sd_spec_queue_generate_logprobs", 6, donor_draft, donor_target, shared_rows, slots, n_slots, slot_cap, prompts,
+                          n_prompts, prefill_chunk, gamma, sampling, prompt_params, random_seed, r_const, scratch, log, passes_out,
+                          stream, logprobs);
 }
 
 // ---- the width-w loop of sampling/multi.py in native code (reference speculative_sampling.py:1379-1716, strategy "iid")
@@ -1018,8 +1146,9 @@ extern "C" size_t sd_ar_block_bytes(int n_streams) {
     return ((size_t)n_streams * sizeof(ArSlot) + 15) & ~(size_t)15;
 }
 
-extern "C" int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
-                                    void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream) {
+static int ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
+                             void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream,
+                             const sd_logprob_block *lp) {
     SD_REQUIRE(n_streams >= 1 && n_streams <= 16, "sd_ar_batch_generate: n_streams %d outside 1..16", n_streams);
     SD_REQUIRE(streams && sampling && head && log && head->logits && dev_block && host_block, "sd_ar_batch_generate: null argument");
     const sd_sampling &sm = *sampling;
@@ -1037,6 +1166,8 @@ extern "C" int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, const 
         SD_REQUIRE(streams[b].session->m == streams[0].session->m, "sd_ar_batch_generate: stream %d: session of another model", b);
     SD_REQUIRE(n_streams <= streams[0].session->max_pass_rows, "sd_ar_batch_generate: %d streams exceed one pass (%d rows)", n_streams,
                streams[0].session->max_pass_rows);
+    if (lp)
+        if (int rc = check_logprob_block("sd_ar_batch_generate_logprobs", lp, n_streams); rc != SD_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const bool timed = log->step_ms_out != nullptr;
     LoopEvents ev(timed ? 2 : 0, "sd_ar_batch_generate");
@@ -1045,8 +1176,8 @@ extern "C" int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, const 
     const ArSlot *slots = (const ArSlot *)host_block;
     std::vector<sd_batch_item> items;
     std::vector<sd_norm_row> rows;
-    int act[16];
-    for (int b = 0; b < n_streams; ++b) { streams[b].done = 0; streams[b].steps = 0; }
+    int act[16], L0[16];                                          // (L0, logprobs: the streams' lengths on entry)
+    for (int b = 0; b < n_streams; ++b) { streams[b].done = 0; streams[b].steps = 0; L0[b] = streams[b].len; }
     log->n_steps = log->err = 0;
     int rc = SD_OK;
     for (;;) {
@@ -1082,6 +1213,15 @@ extern "C" int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, const 
         NormRequest nr = norm_request(sm, head->norm_mode, ho);
         nr.rows = n; nr.workspace = norm_workspace;
         if ((rc = sd_norm_batch_tiles(nr, rows.data(), 1, stream)) != SD_OK) break;
+        if (lp) {                                                 // behind the sampler: stream b's one row, scored at seq[len]
+            sd_logprob_item li[16];
+            for (int j = 0; j < n; ++j) {
+                const sd_ar_stream &s = streams[act[j]];
+                li[j] = sd_logprob_item{ho.logits + (size_t)j * ho.ld, ho.ld, 1, s.seq + s.len, nullptr, lp->dev + (size_t)act[j] * LP_SLICE};
+            }
+            if ((rc = sd_token_logprobs(li, n, sm.V, ho.round | head->norm_mode, stream)) != SD_OK) break;
+            SD_LOOP_HIP(hipMemcpyAsync(lp->host, lp->dev, sizeof(float) * ((size_t)(n_streams - 1) * LP_SLICE + 1), hipMemcpyDeviceToHost, st));
+        }
         // ---- the hand-off: 8 bytes per stream, one copy, one wait
         hipLaunchKernelGGL(ar_collect_kernel, dim3(1), dim3(64), 0, st, tab, n_streams, sm.eos_token_id, (ArSlot *)dev_block);
         SD_LOOP_HIP(hipGetLastError());
@@ -1104,10 +1244,21 @@ extern "C" int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, const 
             sd_ar_stream &s = streams[act[j]];
             const ArSlot r = slots[act[j]];
             s.host_seq[s.len] = r.token;
+            if (lp) lp->logprob_out[act[j]][s.len - L0[act[j]]] = lp->host[(size_t)act[j] * LP_SLICE];
             s.cache_len = s.len;                                  // every token but the new one is cached
             ++s.len; ++s.draw; ++s.steps;
             if (r.flags & 4) s.done = 1;                          // the EOS is kept (:55)
         }
     }
     return rc;
+}
+
+extern "C" int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
+                                    void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream) {
+    return ar_batch_generate(streams, n_streams, sampling, head, norm_workspace, dev_block, host_block, log, stream, nullptr);
+}
+extern "C" int sd_ar_batch_generate_logprobs(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling,
+                                             const sd_head_scratch *head, void *norm_workspace, void *dev_block, void *host_block,
+                                             sd_ar_log *log, void *stream, const sd_logprob_block *logprobs) {
+    return ar_batch_generate(streams, n_streams, sampling, head, norm_workspace, dev_block, host_block, log, stream, logprobs);
 }

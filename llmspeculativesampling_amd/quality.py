@@ -27,3 +27,10 @@ def get_score(output: torch.Tensor, target_model, input_len: int) -> torch.Tenso
     logp = torch.log_softmax(logits[:-1], dim=-1)
     picked = torch.gather(logp, -1, output[0, 1:, None].to(m.device))
     return picked[input_len - 1:].mean()
+
+
+def score_from_logprobs(logprobs: torch.Tensor) -> torch.Tensor:
+    """get_score of an output whose decode call returned ``logprobs`` (``logprobs=True`` of the sampling functions,
+    speculative_sampling_queue_logprobs): those are the target log-probabilities get_score gathers - the model's own, before
+    temperature, top_k and top_p - so the score is their mean, and no second target pass runs."""
+    return logprobs.to(torch.float32).mean()

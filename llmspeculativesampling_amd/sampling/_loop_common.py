@@ -2,10 +2,13 @@
 piece of reference semantics - the EOS rule, the reseed quirk, how the acceptance ratio is rounded - is written once."""
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 import torch
 
-from .._lib import SdHeadScratch, SdLockstepLog, SdRowSampling, SdSampling, SdSeqState, SdSpecScratch, SdSpecStream
+from .._lib import (LOGPROB_SLICE, LOGPROB_STREAMS, SdHeadScratch, SdLockstepLog, SdLogprobBlock, SdRowSampling, SdSampling,
+                    SdSeqState, SdSpecScratch, SdSpecStream)
 from ..noise import DeviceNoise, HostTorchNoise
 from .kvcache_model import KVCacheModel
 
@@ -208,6 +211,35 @@ class LoopLog:
         if self.draft_ms is None:
             return 0, 0
         return tuple(int(sum(int(v * 1e6) for v in ms[:calls])) for ms in (self.draft_ms, self.target_ms))
+
+
+def device_rng(rng) -> bool:
+    """Whether ``rng`` selects the native device-RNG loops: "device", or a noise object that draws on the device."""
+    return rng == "device" if isinstance(rng, str) else bool(getattr(rng, "on_device", False))
+
+
+def logprobs_need_target_rows(target_m) -> None:
+    """``logprobs=True`` reads the target's logit rows where a single-GPU forward leaves them: a tensor-parallel shard is refused."""
+    if getattr(target_m, "tp_group", None) is not None:
+        raise ValueError("logprobs=True is not available with a tensor-parallel target model")
+
+
+class LogprobBlock:
+    """The SdLogprobBlock of one native loop call: the device and pinned-host float slices (16 streams x 17 floats) and one host
+    array per stream (per prompt in the queue) with the capacity of its token buffer, entry j = the target log-probability of
+    the j-th token the call emitted for it."""
+
+    def __init__(self, device, caps):
+        n = LOGPROB_SLICE * LOGPROB_STREAMS
+        self.dev = torch.zeros(n, dtype=torch.float32, device=device)
+        self.host = torch.zeros(n, dtype=torch.float32).pin_memory()
+        self.out = [np.zeros(max(1, int(c)), dtype=np.float32) for c in caps]
+        self._ptrs = (C.c_void_p * len(self.out))(*[a.ctypes.data for a in self.out])
+        self.block = SdLogprobBlock(self.dev.data_ptr(), self.host.data_ptr(), self._ptrs)
+
+    def tensor(self, i: int, n: int, device) -> torch.Tensor:
+        """The (1, n) float32 scores of stream i's first n new tokens (n: the output's length minus the prompt's)."""
+        return torch.from_numpy(self.out[i][:max(0, n)].copy()).unsqueeze(0).to(device)
 
 
 def raise_loop_error(code: int) -> None:

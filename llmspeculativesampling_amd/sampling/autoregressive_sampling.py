@@ -8,19 +8,28 @@ import torch
 
 from .._lib import lib, check, SdArLog, SdArStream
 from ..engine import as_specdec_model, _stream, check_token_ids
-from ._loop_common import head_scratch, make_noise, open_stream, raise_loop_error, sampling_block
+from ._loop_common import (LogprobBlock, device_rng, head_scratch, logprobs_need_target_rows, make_noise, open_stream,
+                           raise_loop_error, sampling_block)
 from .kvcache_model import KVCacheModel
 
 
 @torch.no_grad()
 def autoregressive_sampling(x: torch.Tensor, model, N: int, eos_token_id: int, temperature: float = 1,
-                            top_k: int = 0, top_p: float = 0, pad_token_id=None, *, rng=None, _native: bool = True):
+                            top_k: int = 0, top_p: float = 0, pad_token_id=None, *, rng=None, _native: bool = True,
+                            logprobs: bool = False):
     """reference autoregressive_sampling.py:9-61: exactly N tokens unless EOS is drawn (the EOS is kept).
     RNG contract: one ``sample`` per token.  With the device RNG the whole loop is one native call
     (sd_ar_batch_generate with one stream); ``_native=False`` keeps the interpreter loop below, which the host RNG
-    and ReplayNoise always take (same tokens, same exceptions)."""
+    and ReplayNoise always take (same tokens, same exceptions).
+    ``logprobs`` (native loop only): returns ``(tokens, logprobs)``, a float32 tensor (1, len(tokens) - len(x)) with the
+    model's log-probability of every new token - ``log_softmax`` in fp32 of the raw logit row it was sampled from, taken
+    before temperature, top_k and top_p: what the model says, not what the sampler drew from."""
+    if logprobs and not (_native and device_rng(rng)):
+        raise ValueError('logprobs=True needs the native loop: rng="device" (or a device noise object), not _native=False')
     assert x.shape[0] == 1
     m = as_specdec_model(model)
+    if logprobs:
+        logprobs_need_target_rows(m)
     dev = m.device
     V = m.cfg.vocab_size
     L0 = x.shape[1]
@@ -31,8 +40,9 @@ def autoregressive_sampling(x: torch.Tensor, model, N: int, eos_token_id: int, t
     if _native and getattr(noise, "on_device", False):
         run = ArRun(m, temperature, top_k, top_p, eos_token_id)
         run.add(kv, seq32, x[0].to(device="cpu", dtype=torch.int32).numpy(), L0 + N, noise)
-        run.generate()
-        return torch.from_numpy(run.tokens(0)).to(torch.int64).unsqueeze(0).to(x.device)
+        run.generate(logprobs=logprobs)
+        out = torch.from_numpy(run.tokens(0)).to(torch.int64).unsqueeze(0).to(x.device)
+        return (out, run.logprobs(0, x.device)) if logprobs else out
     n_out = 0
     # the EOS test needs each token on the host (autoregressive_sampling.py:55): one 4-byte read per step
     for i in range(N):
@@ -77,7 +87,7 @@ class ArRun:
         err = torch.zeros(2, dtype=torch.int32, device=self.m.device)
         self.streams.append(_ArStream(kv, seq32, host, err, noise, len(prompt), int(T)))
 
-    def generate(self, timing: bool = False) -> None:
+    def generate(self, timing: bool = False, logprobs: bool = False) -> None:
         B = len(self.streams)
         if not 1 <= B <= 16:
             raise ValueError(f"autoregressive sampling takes 1..16 streams per call, not {B}")
@@ -97,9 +107,14 @@ class ArRun:
         ms = np.zeros(max(n_log, 1), dtype=np.float32)
         cnt = np.zeros(max(n_log, 1), dtype=np.int32)
         log = SdArLog(ms.ctypes.data if timing else None, cnt.ctypes.data if timing else None, n_log)
-        rc = lib.sd_ar_batch_generate(arr, B, sampling_block(*self.args, self.m.cfg.vocab_size, kv0._probs.stride(0), self.eos),
-                                      head_scratch(kv0._session), norm_ws.data_ptr() if norm_ws is not None else None,
-                                      dev_block.data_ptr(), host_block.data_ptr(), log, _stream())
+        args = (arr, B, sampling_block(*self.args, self.m.cfg.vocab_size, kv0._probs.stride(0), self.eos),
+                head_scratch(kv0._session), norm_ws.data_ptr() if norm_ws is not None else None,
+                dev_block.data_ptr(), host_block.data_ptr(), log, _stream())
+        self.lp = LogprobBlock(dev, [s.T + 1 for s in self.streams]) if logprobs else None
+        if self.lp is None:
+            rc = lib.sd_ar_batch_generate(*args)
+        else:
+            rc = lib.sd_ar_batch_generate_logprobs(*args, self.lp.block)
         self.lens = []
         for it, s in zip(arr, self.streams):                      # the state the loop left, also after a failure
             s.kv._session.cache_len = it.cache_len
@@ -111,3 +126,7 @@ class ArRun:
 
     def tokens(self, i: int) -> np.ndarray:
         return self.streams[i].host[:self.lens[i]]
+
+    def logprobs(self, i: int, device) -> torch.Tensor:
+        """generate(logprobs=True): the (1, new tokens) float32 scores of stream i."""
+        return self.lp.tensor(i, self.lens[i] - self.streams[i].L, device)

@@ -22,8 +22,9 @@ import torch
 from .._lib import lib, check, SdAcceptResult, SdBatchStream, SdQueuePrompt
 from ..engine import as_specdec_model, _stream, check_token_ids, same_device, batch_prefill
 from ..noise import DeviceNoise
-from ._loop_common import (LockstepLog, LoopLog, bind_spec_slot, lockstep_result, open_spec_slot, open_stream, reseed_uniforms,
-                           row_sampling, row_sampling_array, sampling_block, spec_scratch)
+from ._loop_common import (LockstepLog, LogprobBlock, LoopLog, bind_spec_slot, lockstep_result, logprobs_need_target_rows,
+                           open_spec_slot, open_stream, reseed_uniforms, row_sampling, row_sampling_array, sampling_block,
+                           spec_scratch)
 from .autoregressive_sampling import ArRun
 from .kvcache_model import KVCacheModel
 
@@ -53,20 +54,27 @@ class _Ms:                                                        # (bench.py re
 def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, target_model, eos_token_id,
                                pad_token_id, max_len: int, gamma: int = 4, temperature: float = 1, top_k: int = 0,
                                top_p: float = 0, random_seed: int = None, details: bool = False,
-                               seeds: Optional[Sequence[int]] = None, _timing: Optional[dict] = None):
+                               seeds: Optional[Sequence[int]] = None, _timing: Optional[dict] = None, *,
+                               logprobs: bool = False):
     """B streams at once; ``prefixes[i]`` is (1, L_i) int64.  Returns a list of (1, len_i) tensors (and a list of
     ``details`` dicts with the reference's keys when ``details``).  Device Philox RNG, stream i seeded ``seeds[i]``.
     ``temperature``, ``top_k`` and ``top_p`` each take one value for all streams or a sequence with one entry per stream
     (``T_i``, ``k_i``, ``p_i``; a scalar beside a sequence is broadcast): stream i equals ``speculative_sampling(prefixes[i],
     ..., temperature=T_i, top_k=k_i, top_p=p_i, rng=DeviceNoise(seeds[i]))``.  A sequence of another length, a temperature
     entry of 0 or a negative / non-integer top_k entry raises ValueError before a model is touched.  With three scalars the
-    call is sd_spec_batch_generate's as before; with any sequence it goes to sd_spec_batch_generate_rows."""
+    call is sd_spec_batch_generate's as before; with any sequence it goes to sd_spec_batch_generate_rows.
+    ``logprobs``: the return value gains one last element, a list of float32 (1, len_i - L_i) tensors with the TARGET
+    model's log-probability of every new token of stream i, as ``speculative_sampling(logprobs=True)`` defines it: the
+    log-softmax of the raw target logits, before temperature, top_k and top_p - what the model says, not what the sampler
+    drew from - cut where the tokens are cut (sd_spec_batch_generate_logprobs)."""
     try:
         triples = row_sampling(len(prefixes), "stream", temperature, top_k, top_p)
     except TypeError:
         raise ValueError("prefixes: a sequence of (1, L) int64 prompts is required") from None
     draft_m, target_m = as_specdec_model(approx_model), as_specdec_model(target_model)
     same_device(draft_m, target_m)
+    if logprobs:
+        logprobs_need_target_rows(target_m)
     dev = target_m.device
     V = target_m.cfg.vocab_size
     assert draft_m.cfg.vocab_size == V
@@ -121,7 +129,10 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
                                           streams[0].draft._probs.stride(0), eos_token_id),
             int(random_seed or 0), r_const.data_ptr() if r_const is not None else None, spec_scratch(d0, t0, norm_ws, per_pass),
             vlog.block, cu)
-    if triples is None:
+    lp = LogprobBlock(dev, [len(s.log.host_seq) for s in streams]) if logprobs else None
+    if lp is not None:
+        check(lib.sd_spec_batch_generate_logprobs(*args, row_sampling_array(triples), lp.block), "sd_spec_batch_generate_logprobs")
+    elif triples is None:
         check(lib.sd_spec_batch_generate(*args), "sd_spec_batch_generate")
     else:
         check(lib.sd_spec_batch_generate_rows(*args, row_sampling_array(triples)), "sd_spec_batch_generate_rows")
@@ -136,7 +147,10 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
         out, det = lockstep_result(s.log, it.len, it.calls, eos_token_id, s.ori_eos, pf.device)
         outs.append(out)
         ds.append(det)
-    return (outs, ds) if details else outs
+    tail = ([lp.tensor(i, o.shape[1] - s.prompt_len, o.device) for i, (o, s) in enumerate(zip(outs, streams))],) if lp is not None else ()
+    if details:
+        return (outs, ds, *tail)
+    return (outs, *tail) if tail else outs
 
 
 def _queue_arguments(prefixes, max_len, seeds, slots):
@@ -230,8 +244,25 @@ def speculative_sampling_queue_shared(prefixes: Sequence[torch.Tensor], approx_m
                   random_seed, details, seeds, slots, prefill_chunk, _timing, shared_prefix)
 
 
+@torch.no_grad()
+def speculative_sampling_queue_logprobs(prefixes: Sequence[torch.Tensor], approx_model, target_model, eos_token_id, pad_token_id,
+                                        max_len, gamma: int = 4, temperature: float = 1, top_k: int = 0, top_p: float = 0,
+                                        random_seed: int = None, details: bool = False, seeds: Optional[Sequence[int]] = None,
+                                        slots: int = 8, prefill_chunk: int = 0, _timing: Optional[dict] = None,
+                                        shared_prefix: int = 0):
+    """speculative_sampling_queue_shared (``shared_prefix=0``: speculative_sampling_queue) that also returns, per prompt, the
+    TARGET model's log-probability of every new token: ``(outs, logprobs)`` or ``(outs, details, logprobs)``, ``logprobs[i]`` a
+    float32 (1, len_i - L_i) tensor on ``outs[i]``'s device, cut where the tokens are cut.  The score of a token is the
+    log-softmax in fp32 of the target's raw logit row for the position before it, taken before temperature, top_k and top_p -
+    what the model says, not what the sampler drew from - so ``logprobs[i].mean()`` is ``quality.get_score`` of output i
+    without a second target pass.  Tokens, details and Philox positions are those of the call without scores
+    (sd_spec_queue_generate_logprobs).  (A function of its own: the queues' parameter lists are pinned by their tests.)"""
+    return _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max_len, gamma, temperature, top_k, top_p,
+                  random_seed, details, seeds, slots, prefill_chunk, _timing, shared_prefix, logprobs=True)
+
+
 def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max_len, gamma, temperature, top_k, top_p,
-           random_seed, details, seeds, slots, prefill_chunk, _timing, shared_prefix):
+           random_seed, details, seeds, slots, prefill_chunk, _timing, shared_prefix, logprobs=False):
     """The prompt queue behind both public entry points (their docstrings have the contract)."""
     budgets = _queue_arguments(prefixes, max_len, seeds, slots)
     shared = _shared_prefix_argument(prefixes, shared_prefix)
@@ -244,6 +275,8 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
         temperature, top_k, top_p = triples[0]
     draft_m, target_m = as_specdec_model(approx_model), as_specdec_model(target_model)
     same_device(draft_m, target_m)
+    if logprobs:
+        logprobs_need_target_rows(target_m)
     dev = target_m.device
     V = target_m.cfg.vocab_size
     assert draft_m.cfg.vocab_size == V
@@ -297,7 +330,10 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
             donor_passes[side] = -(-rows // ses.max_rows)
     # (without donors sd_spec_queue_generate_shared is sd_spec_queue_generate, which has no room for the two row counts)
     args += (*[ses.handle if ses else None for ses in donors], rows)
-    if triples is None:
+    lp = LogprobBlock(dev, [len(log.host_seq) for log in logs]) if logprobs else None
+    if lp is not None:
+        check(lib.sd_spec_queue_generate_logprobs(*args, row_sampling_array(triples), lp.block), "sd_spec_queue_generate_logprobs")
+    elif triples is None:
         check(lib.sd_spec_queue_generate_shared(*args), "sd_spec_queue_generate_shared")
     else:
         check(lib.sd_spec_queue_generate_rows(*args, row_sampling_array(triples)), "sd_spec_queue_generate_rows")
@@ -313,22 +349,30 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
     res = [lockstep_result(log, it.len, it.calls, eos_token_id, it.ori_eos_cnt, pf.device)
            for it, log, pf in zip(arr, logs, prefixes)]
     outs, ds = [r[0] for r in res], [r[1] for r in res]
+    if lp is not None:
+        lps = [lp.tensor(i, o.shape[1] - L, o.device) for i, (o, L) in enumerate(zip(outs, lens))]
+        return (outs, ds, lps) if details else (outs, lps)
     return (outs, ds) if details else outs
 
 
 @torch.no_grad()
 def autoregressive_sampling_batch(xs: Sequence[torch.Tensor], model, N: int, eos_token_id, temperature: float = 1,
                                   top_k: int = 0, top_p: float = 0, pad_token_id=None, *,
-                                  seeds: Optional[Sequence[int]] = None, _timing: Optional[dict] = None):
+                                  seeds: Optional[Sequence[int]] = None, _timing: Optional[dict] = None,
+                                  logprobs: bool = False):
     """``autoregressive_sampling`` for B streams at once: ``xs[i]`` is (1, L_i) int64, the result a list of (1, len_i)
     tensors.  The streams decode in lock-step and share every pass over the weights (sd_ar_batch_generate): each runs the
     algorithm of reference autoregressive_sampling.py:9-61 on its own Philox stream ``seeds[i]`` (default
     ``torch.initial_seed() + i``), so the outputs equal those of B ``autoregressive_sampling(..., rng=DeviceNoise(seed))``
-    calls.  ``_timing["step"]`` receives (milliseconds, streams in the step) per step."""
+    calls.  ``_timing["step"]`` receives (milliseconds, streams in the step) per step.  ``logprobs``: returns ``(outs,
+    logprobs)``, a list of float32 (1, len_i - L_i) tensors with the model's log-probability of every new token: the
+    log-softmax of its raw logits, before temperature, top_k and top_p - what the model says, not what the sampler drew from."""
     B = len(xs)
     if not 1 <= B <= 16:
         raise ValueError(f"autoregressive_sampling_batch takes 1..16 streams per call, not {B}")
     m = as_specdec_model(model)
+    if logprobs:
+        logprobs_need_target_rows(m)
     V = m.cfg.vocab_size
     for x in xs:
         assert x.dim() == 2 and x.shape[0] == 1 and x.shape[1] >= 1, "every stream is one (1, L) prompt"
@@ -342,7 +386,8 @@ def autoregressive_sampling_batch(xs: Sequence[torch.Tensor], model, N: int, eos
     batch_prefill([kv._session for kv in kvs], seqs, [x.shape[1] - 1 for x in xs])
     for x, seed, kv, seq32 in zip(xs, seeds, kvs, seqs):
         run.add(kv, seq32, x[0].to(device="cpu", dtype=torch.int32).numpy(), x.shape[1] + int(N), DeviceNoise(seed))
-    run.generate(timing=_timing is not None)
+    run.generate(timing=_timing is not None, logprobs=logprobs)
     if _timing is not None:
         _timing.setdefault("step", []).extend(run.steps)
-    return [torch.from_numpy(run.tokens(i)).to(torch.int64).unsqueeze(0).to(x.device) for i, x in enumerate(xs)]
+    outs = [torch.from_numpy(run.tokens(i)).to(torch.int64).unsqueeze(0).to(x.device) for i, x in enumerate(xs)]
+    return (outs, [run.logprobs(i, x.device) for i, x in enumerate(xs)]) if logprobs else outs

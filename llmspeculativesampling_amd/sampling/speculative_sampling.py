@@ -16,8 +16,9 @@ import torch
 
 from .._lib import lib, check, SdAcceptResult
 from ..engine import as_specdec_model, _stream, check_token_ids, same_device
-from ._loop_common import (LoopLog, accept_rates_f64, cut_after_new_eos, details_dict, make_noise, open_stream,
-                           raise_loop_error, reseed_uniforms, sampling_block, spec_scratch, spec_stream)
+from ._loop_common import (LogprobBlock, LoopLog, accept_rates_f64, cut_after_new_eos, details_dict, device_rng,
+                           logprobs_need_target_rows, make_noise, open_stream, raise_loop_error, reseed_uniforms, sampling_block,
+                           spec_scratch, spec_stream)
 
 _make_noise = make_noise                              # beam.py, multi.py and tests import it from here
 
@@ -26,15 +27,25 @@ _make_noise = make_noise                              # beam.py, multi.py and te
 def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_token_id, pad_token_id,
                          max_len: int, gamma: int = 4, temperature: float = 1, top_k: int = 0, top_p: float = 0,
                          verbose: bool = False, random_seed: int = None, details: bool = False, *, rng=None,
-                         _event_logs=None):
+                         _event_logs=None, logprobs: bool = False):
     """reference speculative_sampling.py:1876-2076.
 
     ``rng`` (extension): "host" (default) draws every variate from torch's CPU generator in the
     reference's order, so token ids equal the reference's CPU path under the same seed; "device"
     uses on-device Philox (throughput mode); or a noise object from ``llmspeculativesampling_amd.noise``.
+
+    ``logprobs`` (extension, native device-RNG loop only): the return value gains one last element, a float32 tensor
+    (1, len(output) - len(prefix)) on the output's device with the TARGET model's log-probability of every new token:
+    ``log_softmax`` in fp32 of the target's raw logit row for the position before it, taken before temperature, top_k and
+    top_p - what the model says, not what the sampler drew from.  It is cut where the tokens are cut, and its mean is
+    ``quality.get_score`` of the output without a second target pass (``quality.score_from_logprobs``).
     """
+    if logprobs and (verbose or not device_rng(rng)):
+        raise ValueError('logprobs=True needs the native loop: rng="device" (or a device noise object) and verbose=False')
     assert prefix.shape[0] == 1, "input batch size must be 1"
     draft_m, target_m = as_specdec_model(approx_model), as_specdec_model(target_model)
+    if logprobs:
+        logprobs_need_target_rows(target_m)
     if draft_m.cfg.is_encoder_decoder or target_m.cfg.is_encoder_decoder:
         raise NotImplementedError("encoder-decoder models are out of scope")
     same_device(draft_m, target_m)
@@ -58,7 +69,7 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
     target, seq32 = open_stream(target_m, prefix[0], cap, cap + 1, temperature, top_k, top_p, noise)
     if getattr(noise, "on_device", False) and not verbose:
         return _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T, gamma, random_seed, details,
-                                   noise, _event_logs)
+                                   noise, _event_logs, logprobs)
 
     ori_eos_cnt = host_seq.count(eos_token_id)
     if _event_logs is not None:                       # bench.py: HIP-event brackets around every forward
@@ -170,7 +181,7 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
 
 
 def _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T, gamma, random_seed, details, noise,
-                        timing_log):
+                        timing_log, logprobs=False):
     """Device-RNG mode: the loop itself runs inside libspecdec (sd_spec_generate): per iteration the gamma draft steps,
     the target forward, the accept scan and the resample are enqueued and the stream is waited on once, in native code;
     the interpreter only sees the finished sequence and the per-iteration statistics.  Same loop semantics as the
@@ -190,10 +201,15 @@ def _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T,
     sampling = sampling_block(target._temperature, target._top_k, target._top_p, target._model.cfg.vocab_size,
                               draft._probs.stride(0), eos_token_id)
     scratch = spec_scratch(draft._session, target._session, target._norm_ws, target._session.max_rows)
+    lp = LogprobBlock(dev, [T + gamma + 2]) if logprobs else None
     try:
         tick = process_time_ns()
-        check(lib.sd_spec_generate(stream, gamma, sampling, scratch, st, int(random_seed or 0),
-                                   r_const.data_ptr() if r_const is not None else None, _stream()), "sd_spec_generate")
+        args = (stream, gamma, sampling, scratch, st, int(random_seed or 0), r_const.data_ptr() if r_const is not None else None,
+                _stream())
+        if lp is None:
+            check(lib.sd_spec_generate(*args), "sd_spec_generate")
+        else:
+            check(lib.sd_spec_generate_logprobs(*args, lp.block), "sd_spec_generate_logprobs")
         other_time = process_time_ns() - tick            # host CPU time of the loop (enqueue + waits + bookkeeping)
         noise.seed, noise.draw = st.seed, st.draw
         raise_loop_error(st.err)
@@ -216,8 +232,9 @@ def _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T,
         raise RuntimeError("s") from e
     draft._session.cache_len, target._session.cache_len = st.draft_len, st.target_len
     out = torch.tensor([out_tokens], dtype=torch.int64, device=prefix.device)
+    tail = (lp.tensor(0, len(out_tokens) - seq_len0, prefix.device),) if lp is not None else ()
     if details:
         # the verify phase is one fused launch chain (forward + norm_probs, no cache preparation): all of it is model time
-        return out, details_dict(approx_time, target_time, other_time, acc_len, np.mean(acc_rate), calls, calls,
-                                 target_model_time=target_time, target_pre_cache_time=0, target_post_prob_time=0)
-    return out
+        return (out, details_dict(approx_time, target_time, other_time, acc_len, np.mean(acc_rate), calls, calls,
+                                  target_model_time=target_time, target_pre_cache_time=0, target_post_prob_time=0), *tail)
+    return (out, *tail) if tail else out

@@ -27,7 +27,7 @@ sys.path.insert(0, ROOT)
 from llmspeculativesampling_amd import harness  # noqa: E402
 from llmspeculativesampling_amd.config import load_config  # noqa: E402
 from llmspeculativesampling_amd.engine import SpecDecModel  # noqa: E402
-from llmspeculativesampling_amd.quality import get_score  # noqa: E402
+from llmspeculativesampling_amd.quality import get_score, score_from_logprobs  # noqa: E402
 from llmspeculativesampling_amd.sampling import (autoregressive_sampling, autoregressive_sampling_batch,  # noqa: E402
                                                  multi_speculative_sampling, speculative_sampling)
 
@@ -53,7 +53,15 @@ def parse_arguments():
     p.add_argument("--ar-streams", type=int, default=0, metavar="B",
                    help="also run the autoregressive arm B (1..16) prompts at a time in lock-step (device RNG) and print "
                         "its tokens/s; 0 = off")
-    return p.parse_args()
+    p.add_argument("--scores-from-loop", action="store_true",
+                   help="with --rng device: the autoregressive and the speculative arm take each output's score from the "
+                        "decode call itself (logprobs=True) and no get_score pass runs; the iid arm has to be skipped")
+    args = p.parse_args()
+    if args.scores_from_loop and args.rng != "device":
+        p.error("--scores-from-loop needs --rng device")
+    if args.scores_from_loop and "iid" not in args.skip.split(","):
+        p.error("--scores-from-loop: the iid arm has no scores of its own, add --skip iid")
+    return args
 
 
 def build_model(name: str, dtype, seed: int) -> SpecDecModel:
@@ -109,10 +117,12 @@ def main():
                     t = process_time_ns()
                     out = autoregressive_sampling(ids, large, args.max_tokens, eos_token_id=tok.eos_token_id,
                                                   top_k=top_k, top_p=top_p, pad_token_id=tok.pad_token_id,
-                                                  rng=args.rng)
+                                                  rng=args.rng, logprobs=args.scores_from_loop)
                     total_ns += process_time_ns() - t
+                    if args.scores_from_loop:
+                        out, lp = out
                     tokens += len(out[0]) - ids.size(1)
-                    scores.append(get_score(out, large, ids.size(1)).item())
+                    scores.append((score_from_logprobs(lp) if args.scores_from_loop else get_score(out, large, ids.size(1))).item())
                     if total_ns / 1e9 > args.max_seconds:
                         emit([f"terminated at {n_done}"])
                         break
@@ -143,7 +153,8 @@ def main():
                           lambda ids: speculative_sampling(ids, small, large, eos_token_id=tok.eos_token_id,
                                                            pad_token_id=tok.pad_token_id, max_len=args.max_tokens,
                                                            gamma=args.gamma, top_k=top_k, top_p=top_p,
-                                                           random_seed=args.seed, details=True, rng=args.rng)))
+                                                           random_seed=args.seed, details=True, rng=args.rng,
+                                                           logprobs=args.scores_from_loop)))
         if "iid" not in skip:
             loops.append((f"iid multi-draft speculative decoding (gamma {args.gamma}, width {args.width})",
                           lambda ids: multi_speculative_sampling(ids, small, large, eos_token_id=tok.eos_token_id,
@@ -161,7 +172,7 @@ def main():
                 for n_done, ids in enumerate(ds, 1):
                     ids = ids.cuda()
                     t = process_time_ns()
-                    out, d = run(ids)
+                    out, d, *lp = run(ids)
                     total_ns += process_time_ns() - t
                     tokens += len(out[0]) - ids.size(1)
                     for k in ("approx_time", "target_time", "other_time", "target_call_times", "approx_call_times"):
@@ -170,7 +181,7 @@ def main():
                         agg[k] += d.get(k, 0)
                     agg["acc_len_sum"] += float(np.sum(d["acc_len"]))
                     agg["acc_rate"].append(float(d["acc_rate"]))
-                    scores.append(get_score(out, large, ids.size(1)).item())
+                    scores.append((score_from_logprobs(lp[0]) if lp else get_score(out, large, ids.size(1))).item())
                     if total_ns / 1e9 > args.max_seconds:
                         emit([f"terminated at {n_done}"])
                         break
