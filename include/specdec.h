@@ -798,6 +798,71 @@ int sd_ar_batch_generate_logprobs(sd_ar_stream *streams, int n_streams, const sd
                                   void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream,
                                   const sd_logprob_block *logprobs);
 
+/* ---- Per-request repetition, frequency and presence penalties.  A logit row at position pos predicts token pos + 1; its
+ * history is seq[0 .. pos], and the stream's prompt is the P tokens it held when the call started.  For a token id t, c_all(t)
+ * counts t in seq[0 .. pos] and c_out(t) in seq[P .. pos].  x is the logit as the sampler reads it, the pending SD_NORM_ROUND_*
+ * rounding applied.  With repetition r (finite, > 0, neutral 1), frequency f and presence p (finite, neutral 0):
+ *   1. c_all(t) > 0 and r != 1:  y = x > 0 ? x / r : x * r       (prompt + output, the usual repetition penalty)
+ *   2. c_out(t) > 0:             y = y - fl(f * float(c_out)), then y = y - p      (output tokens only)
+ * Each result is one IEEE fp32 operation (a correctly rounded division, no contraction of the product into the subtraction);
+ * in an SD_NORM_DT_* mode each of them, the product included, is also rounded to that 16-bit type, as torch's 16-bit CPU
+ * kernels do; the three parameters are not rounded.  A token that is not in the history keeps its (rounded) logit bit for bit;
+ * NaN and +-inf go through the same operations; a history entry outside [0, V) is ignored.
+ * (sampling.utils.apply_penalties is this text in torch.)
+ * sd_penalize_rows edits up to 16 items x 17 rows in one launch on `stream` (one workgroup per row and window of 4096 ids): an item is one stream's
+ * `rows` consecutive fp32 logit rows `in` (row stride ld_in >= V), where their edited copies go (`out`, row stride ld_out >= V;
+ * never `in`: the raw rows are not written, the log-probabilities above keep reading them), the stream's device tokens `seq`,
+ * of which row r sees the first hist0 + r, and its prompt length.  No alignment is asked of the rows or the strides.  `mode`
+ * is the word the norm launch would get: bits 0-1 the pending rounding, SD_NORM_DT_* the rows' dtype; the norm launch that
+ * reads `out` takes the same word with bits 0-1 cleared.  A neutral item (1, 0, 0) is rounded and copied.  The result is a
+ * pure function of the inputs (integer counts, every output element written once).  Refused with SD_ERR_INVALID before any
+ * launch, naming the item: a NULL argument, n_items outside 1..16, V outside 1..65536, both rounding bits, rows outside 1..17,
+ * a stride < V, hist0 < 1, prompt_len < 0, repetition <= 0 or a parameter that is not finite. */
+typedef struct { float repetition, frequency, presence; } sd_penalty;
+typedef struct {
+    const float *in;
+    float *out;
+    long ld_in, ld_out;
+    int32_t rows;
+    const int32_t *seq;
+    int32_t hist0, prompt_len;
+    sd_penalty pen;
+} sd_penalty_item;
+int sd_penalize_rows(const sd_penalty_item *items, int n_items, int V, int mode, void *stream);
+/* sd_penalty_block: what a loop needs to sample from penalised rows; caller-owned.  rows: a device slab of max_rows x ld
+ * floats (ld >= V) that holds the logit rows of the loop's largest pass: gamma + 1 in the single-stream loop, the streams in
+ * the autoregressive loop, min(rows per target pass, streams x (gamma + 1)) in the lock-step loops.  A 16-byte aligned slab
+ * with 4 | ld keeps the norm launch on its two-kernel path.  params[k] belongs to stream k - to prompt k in the queue, where a
+ * slot changes penalties when it changes hands.  The _penalties entries take exactly what the _logprobs entries take
+ * (logprobs may be NULL), plus the block; a NULL block, or one whose params are all neutral, is that entry itself, launch for
+ * launch.  Otherwise every pass - of a draft step, of the verify, of an autoregressive step - that holds at least one
+ * penalised active stream gets ONE sd_penalize_rows launch between the forward and the norm launch, over all its logit rows,
+ * one item per stream, hist0 = the position of the stream's first logit row + 1, prompt_len = its length on entry
+ * (sd_queue_prompt.L); the norm launch then reads `rows` with the pending rounding bits cleared.  Such a pass does not ask the
+ * head for tile maxima (the rule a top_k == 0 stream already imposes); its rows go through the norm workspace.  Passes
+ * without a penalised stream, joiner rows, the accept / resample launches, the candidate lists and the Philox draw order are
+ * untouched, and sd_token_logprobs keeps reading the raw rows: penalties act on what the sampler draws from, the scores stay
+ * what the model says.  The draft rows are penalised like the target rows, so that the acceptance rate holds.  Refused with
+ * SD_ERR_INVALID behind the entry's own refusals, before anything is launched, naming the index: a NULL rows or params,
+ * ld < V, max_rows too small, repetition <= 0 or a parameter that is not finite. */
+typedef struct { float *rows; long ld; int32_t max_rows; const sd_penalty *params; } sd_penalty_block;
+int sd_spec_generate_penalties(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling, const sd_spec_scratch *scratch,
+                               sd_seq_state *seq, uint64_t random_seed, const float *r_const, void *stream,
+                               const sd_logprob_block *logprobs, const sd_penalty_block *penalties);
+int sd_spec_batch_generate_penalties(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
+                                     uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
+                                     sd_lockstep_log *log, void *stream, const sd_row_sampling *stream_params,
+                                     const sd_logprob_block *logprobs, const sd_penalty_block *penalties);
+int sd_spec_queue_generate_penalties(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
+                                     int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
+                                     const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log, int *passes_out,
+                                     void *stream, sd_session *donor_draft, sd_session *donor_target, int shared_rows,
+                                     const sd_row_sampling *prompt_params, const sd_logprob_block *logprobs,
+                                     const sd_penalty_block *penalties);
+int sd_ar_batch_generate_penalties(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
+                                   void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream,
+                                   const sd_logprob_block *logprobs, const sd_penalty_block *penalties);
+
 /* ------------------------------------------------------------------------------------------
  * Tensor parallelism of one decoder over the GPUs of a node (BASELINE config 5: Llama-2-70b, TP = 8 over xGMI).
  * The reference is single-process: this is new capability behind the same call signatures.

@@ -136,6 +136,19 @@ class SdLogprobBlock(C.Structure):
     _fields_ = [("dev", C.c_void_p), ("host", C.c_void_p), ("logprob_out", C.POINTER(C.c_void_p))]
 
 
+class SdPenalty(C.Structure):
+    _fields_ = [("repetition", C.c_float), ("frequency", C.c_float), ("presence", C.c_float)]
+
+
+class SdPenaltyItem(C.Structure):
+    _fields_ = [("in", C.c_void_p), ("out", C.c_void_p), ("ld_in", C.c_long), ("ld_out", C.c_long), ("rows", C.c_int32),
+                ("seq", C.c_void_p), ("hist0", C.c_int32), ("prompt_len", C.c_int32), ("pen", SdPenalty)]
+
+
+class SdPenaltyBlock(C.Structure):
+    _fields_ = [("rows", C.c_void_p), ("ld", C.c_long), ("max_rows", C.c_int32), ("params", C.POINTER(SdPenalty))]
+
+
 LOGPROB_SLICE, LOGPROB_STREAMS = 17, 16                  # sd_logprob_block: 16 streams x 17 floats, device and pinned host
 
 
@@ -182,7 +195,8 @@ C_STRUCTS = {"sd_accept_result": SdAcceptResult, "sd_norm_row": SdNormRow, "sd_r
              "sd_ar_stream": SdArStream, "sd_sampling": SdSampling, "sd_head_scratch": SdHeadScratch,
              "sd_spec_stream": SdSpecStream, "sd_spec_scratch": SdSpecScratch, "sd_lockstep_log": SdLockstepLog, "sd_seq_state": SdSeqState,
              "sd_ar_log": SdArLog, "sd_batch_item": SdBatchItem,
-             "sd_logprob_item": SdLogprobItem, "sd_logprob_block": SdLogprobBlock, "sd_model_config": SdModelConfig,
+             "sd_logprob_item": SdLogprobItem, "sd_logprob_block": SdLogprobBlock, "sd_penalty": SdPenalty,
+             "sd_penalty_item": SdPenaltyItem, "sd_penalty_block": SdPenaltyBlock, "sd_model_config": SdModelConfig,
              "sd_gemm_route_info": SdGemmRouteInfo, "sd_model_weights": SdModelWeights}
 
 # every symbol include/specdec.h declares: (name, restype, argtypes)
@@ -274,6 +288,16 @@ SYMBOLS = [
                                              _P(SdLogprobBlock)]),
     ("sd_ar_batch_generate_logprobs", _I, [_P(SdArStream), _I, _P(SdSampling), _P(SdHeadScratch), _VP, _VP, _VP, _P(SdArLog), _VP,
                                            _P(SdLogprobBlock)]),
+    ("sd_penalize_rows", _I, [_P(SdPenaltyItem), _I, _I, _I, _VP]),
+    ("sd_spec_generate_penalties", _I, [_P(SdSpecStream), _I, _P(SdSampling), _P(SdSpecScratch), _P(SdSeqState), _U64, _VP, _VP,
+                                        _P(SdLogprobBlock), _P(SdPenaltyBlock)]),
+    ("sd_spec_batch_generate_penalties", _I, [_P(SdBatchStream), _I, _I, _P(SdSampling), _U64, _VP, _P(SdSpecScratch),
+                                              _P(SdLockstepLog), _VP, _P(SdRowSampling), _P(SdLogprobBlock), _P(SdPenaltyBlock)]),
+    ("sd_spec_queue_generate_penalties", _I, [_P(SdBatchStream), _I, _I, _P(SdQueuePrompt), _I, _I, _I, _P(SdSampling), _U64, _VP,
+                                              _P(SdSpecScratch), _P(SdLockstepLog), _VP, _VP, _VP, _VP, _I, _P(SdRowSampling),
+                                              _P(SdLogprobBlock), _P(SdPenaltyBlock)]),
+    ("sd_ar_batch_generate_penalties", _I, [_P(SdArStream), _I, _P(SdSampling), _P(SdHeadScratch), _VP, _VP, _VP, _P(SdArLog), _VP,
+                                            _P(SdLogprobBlock), _P(SdPenaltyBlock)]),
     ("sd_batch_forward", _I, [C.POINTER(SdBatchItem), _I, _VP, _L, _VP]),
     ("sd_batch_prefill", _I, [C.POINTER(SdBatchItem), _I, _VP]),
     ("sd_tp_unique_id", _I, [_VP]),

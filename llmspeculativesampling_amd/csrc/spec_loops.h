@@ -183,6 +183,64 @@ static void commit_logprobs(const sd_logprob_block &lp, int slot, float *out, in
     for (int i = 0; i <= r.n_accepted; ++i) out[first + i] = lp.host[(size_t)slot * LP_SLICE + i];
 }
 
+// ---- per-request penalties (include/specdec.h has the definition and the loops' contract) ------------------------
+static bool penalty_neutral(const sd_penalty &p) { return p.repetition == 1.0f && p.frequency == 0.0f && p.presence == 0.0f; }
+// what every entry refuses in a parameter triple (`what` names it: "item", "stream", "prompt")
+static int check_penalty(const char *who, const char *what, int i, const sd_penalty &p) {
+    SD_REQUIRE(std::isfinite(p.repetition) && std::isfinite(p.frequency) && std::isfinite(p.presence),
+               "%s: %s %d: penalties (%g, %g, %g) must be finite", who, what, i, p.repetition, p.frequency, p.presence);
+    SD_REQUIRE(p.repetition > 0.0f, "%s: %s %d: repetition penalty %g must be > 0", who, what, i, p.repetition);
+    return SD_OK;
+}
+
+extern "C" int sd_penalize_rows(const sd_penalty_item *items, int n_items, int V, int mode, void *stream) {
+    SD_REQUIRE(items, "sd_penalize_rows: null argument");
+    SD_REQUIRE(n_items >= 1 && n_items <= PEN_MAX_ITEMS, "sd_penalize_rows: n_items %d outside 1..%d", n_items, PEN_MAX_ITEMS);
+    SD_REQUIRE(V >= 1 && V <= 65536 && (mode & 3) != 3, "sd_penalize_rows: V %d outside 1..65536, or both rounding bits (mode %#x)", V, mode);
+    PenaltyTab t = {};
+    int max_rows = 0;
+    for (int i = 0; i < n_items; ++i) {
+        const sd_penalty_item &it = items[i];
+        SD_REQUIRE(it.in && it.out && it.seq, "sd_penalize_rows: item %d: null argument", i);
+        SD_REQUIRE(it.rows >= 1 && it.rows <= PEN_MAX_ROWS, "sd_penalize_rows: item %d: rows %d outside 1..%d", i, it.rows, PEN_MAX_ROWS);
+        SD_REQUIRE(it.ld_in >= V && it.ld_out >= V, "sd_penalize_rows: item %d: ld %ld / %ld < V %d", i, it.ld_in, it.ld_out, V);
+        SD_REQUIRE(it.hist0 >= 1 && it.prompt_len >= 0, "sd_penalize_rows: item %d: hist0 %d < 1 or prompt_len %d < 0", i, it.hist0,
+                   it.prompt_len);
+        if (int rc = check_penalty("sd_penalize_rows", "item", i, it.pen); rc != SD_OK) return rc;
+        t.in[i] = it.in; t.out[i] = it.out; t.seq[i] = it.seq; t.ld_in[i] = it.ld_in; t.ld_out[i] = it.ld_out;
+        t.rows[i] = it.rows; t.hist0[i] = it.hist0; t.prompt_len[i] = it.prompt_len;
+        t.repetition[i] = it.pen.repetition; t.frequency[i] = it.pen.frequency; t.presence[i] = it.pen.presence;
+        max_rows = std::max(max_rows, (int)it.rows);
+    }
+    return launch_penalize_rows(t, n_items, max_rows, V, mode, (hipStream_t)stream);
+}
+
+// what the _penalties entries refuse in their block (behind the entry's own refusals): n triples, one per `what`, and a slab
+// of at least need_rows rows.  *pb becomes NULL when every triple is neutral: the call is then the entry without a block.
+static int check_penalty_block(const char *who, const char *what, const sd_penalty_block **pb, int n, int V, int need_rows) {
+    const sd_penalty_block *b = *pb;
+    SD_REQUIRE(b->rows && b->params, "%s: penalties: null pointer", who);
+    SD_REQUIRE(b->ld >= V, "%s: penalties: ld %ld < V %d", who, b->ld, V);
+    SD_REQUIRE(b->max_rows >= need_rows, "%s: penalties: a slab of %d rows, the largest pass has %d", who, b->max_rows, need_rows);
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+        if (int rc = check_penalty(who, what, i, b->params[i]); rc != SD_OK) return rc;
+        any = any || !penalty_neutral(b->params[i]);
+    }
+    if (!any) *pb = nullptr;
+    return SD_OK;
+}
+// The item of one stream's `rows` logit rows, the first at position `pos`: packed from row `r0` of the pass's raw rows `src`
+// and of the block's slab
+static sd_penalty_item penalty_item(const sd_penalty_block &pb, const HeadOut &src, int r0, int rows, const int32_t *seq, int pos,
+                                    int prompt_len, const sd_penalty &pen) {
+    return sd_penalty_item{src.logits + (size_t)r0 * src.ld, pb.rows + (size_t)r0 * pb.ld, src.ld, pb.ld, rows, seq, pos + 1, prompt_len, pen};
+}
+// The norm request of a penalised pass reads the block's slab: already rounded, no tile maxima
+static void norm_from_penalised(NormRequest &nr, const sd_penalty_block &pb) {
+    nr.logits = pb.rows; nr.ld_in = pb.ld; nr.mode &= ~3; nr.tile_max = nullptr;
+}
+
 // ---- one whole speculative iteration, enqueued natively ---------------------------------------
 // reference sampling/speculative_sampling.py:1934-2031 for the device-RNG mode: gamma x (draft forward +
 // norm_sample), one target forward over the uncached rows + norm_probs, accept scan, residual / bonus sample,
@@ -190,14 +248,14 @@ static void commit_logprobs(const sd_logprob_block &lp, int slot, float *out, in
 // the stream once per iteration.  `timed`: the draft phase is ev.t[0] .. t[1], the verify phase ev.t[2] .. t[3].
 static int spec_iteration(const sd_spec_stream &dv, int g, const sd_sampling &sm, const sd_spec_scratch &sc, const Draws &d, int L,
                           int draft_len, int target_len, const float *r_const, const LoopEvents &ev, bool timed, void *stream,
-                          const sd_logprob_block *lp) {
+                          const sd_logprob_block *lp, const sd_penalty_block *pb, int prompt_len) {
     SD_REQUIRE(L >= 1 && draft_len >= 0 && draft_len < L && target_len >= 0 && target_len < L + g,
                "sd_spec_generate: L=%d draft_len=%d target_len=%d", L, draft_len, target_len);
     SD_REQUIRE(!lp || target_len <= L - 1, "sd_spec_generate_logprobs: target_len %d of %d tokens leaves fewer than gamma + 1 target rows",
                target_len, L);
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    const bool tiles_ok = head_tiles_ok(sm.top_k, sm.temperature, sm.V, sm.ld);
+    const bool tiles_ok = !pb && head_tiles_ok(sm.top_k, sm.temperature, sm.V, sm.ld);   // (a penalised pass takes no tile maxima)
     int *const err = dv.err_words;     // [0..gamma) norm err of draft rows, [gamma..2gamma) sample err, [2gamma..3gamma+1) target rows
     HeadReq rq = {};
     HeadOut ho = {};
@@ -212,6 +270,11 @@ static int spec_iteration(const sd_spec_stream &dv, int g, const sd_sampling &sm
             return rc;
         draft_len = upto;
         NormRequest nr = norm_request(sm, sc.draft.norm_mode, ho);
+        if (pb) {                                                 // the row at position upto - 1, edited out of place
+            const sd_penalty_item it = penalty_item(*pb, ho, 0, 1, dv.seq, upto - 1, prompt_len, pb->params[0]);
+            if ((rc = sd_penalize_rows(&it, 1, sm.V, nr.mode, stream)) != SD_OK) return rc;
+            norm_from_penalised(nr, *pb);
+        }
         nr.rows = 1; nr.probs_out = q_row; nr.ld_out = sm.ld; nr.err = err + i;
         nr.seed = d.seed_draft; nr.draw = d.draft0 + (uint64_t)i; nr.tok_out = dv.seq + upto; nr.samp_err = err + g + i;
         nr.workspace = sc.norm_workspace;
@@ -231,6 +294,11 @@ static int spec_iteration(const sd_spec_stream &dv, int g, const sd_sampling &sm
         if ((rc = feed_rows(dv.target, dv.seq, target_len, upto, rows, sc.target.logits, sc.target.ld_logits, &rq, &ho, stream)) != SD_OK)
             return rc;
         NormRequest nr = norm_request(sm, sc.target.norm_mode, ho);
+        if (pb) {
+            const sd_penalty_item it = penalty_item(*pb, ho, 0, rows, dv.seq, upto - rows, prompt_len, pb->params[0]);
+            if ((rc = sd_penalize_rows(&it, 1, sm.V, nr.mode, stream)) != SD_OK) return rc;
+            norm_from_penalised(nr, *pb);
+        }
         nr.rows = rows; nr.probs_out = p_rows; nr.ld_out = sm.ld; nr.err = err + 2 * g;
         nr.workspace = sc.norm_workspace; nr.lists = lists;
         if ((rc = sd_norm_rows_with_tiles(nr, stream)) != SD_OK) return rc;
@@ -261,7 +329,8 @@ static int spec_iteration(const sd_spec_stream &dv, int g, const sd_sampling &sm
 
 // The device-RNG loop without the interpreter between iterations (reference speculative_sampling.py:1934-2046).
 static int spec_generate(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling, const sd_spec_scratch *scratch,
-                         sd_seq_state *s, uint64_t random_seed, const float *r_const, void *stream, const sd_logprob_block *lp) {
+                         sd_seq_state *s, uint64_t random_seed, const float *r_const, void *stream, const sd_logprob_block *lp,
+                         const sd_penalty_block *pb = nullptr) {
     SD_REQUIRE(dev && sampling && scratch && s && dev->draft && dev->target && dev->seq && dev->q_hist && dev->p_hist &&
                dev->err_words && dev->res_dev && dev->res_host && s->host_seq && scratch->draft.logits && scratch->target.logits,
                "sd_spec_generate: null argument");
@@ -277,6 +346,8 @@ static int spec_generate(const sd_spec_stream *dev, int gamma, const sd_sampling
                dev->target->m->cfg.vocab);
     if (lp)
         if (int rc = check_logprob_block("sd_spec_generate_logprobs", lp, 1); rc != SD_OK) return rc;
+    if (pb)
+        if (int rc = check_penalty_block("sd_spec_generate_penalties", "stream", &pb, 1, sm.V, gamma + 1); rc != SD_OK) return rc;
     refresh_env();
     const int g = gamma, L0 = s->len;
     const bool timed = s->draft_ms_out || s->target_ms_out;
@@ -289,7 +360,7 @@ static int spec_generate(const sd_spec_stream *dev, int gamma, const sd_sampling
         const int L = s->len, iters = s->n_iters;
         const Draws d = next_draws(s->seed, s->draw, g, random_seed);
         s->seed = d.seed; s->draw = d.draw;
-        if ((rc = spec_iteration(*dev, g, sm, *scratch, d, L, s->draft_len, s->target_len, r_const, ev, timed, stream, lp)) != SD_OK) break;
+        if ((rc = spec_iteration(*dev, g, sm, *scratch, d, L, s->draft_len, s->target_len, r_const, ev, timed, stream, lp, pb, L0)) != SD_OK) break;
         SD_LOOP_HIP(hipEventRecord(ev.done, (hipStream_t)stream));
         if ((rc = poll_event(ev.done, "sd_spec_generate")) != SD_OK) break;
         const sd_accept_result r = *dev->res_host;
@@ -340,6 +411,11 @@ extern "C" int sd_spec_generate_logprobs(const sd_spec_stream *dev, int gamma, c
                                          const sd_spec_scratch *scratch, sd_seq_state *s, uint64_t random_seed, const float *r_const,
                                          void *stream, const sd_logprob_block *logprobs) {
     return spec_generate(dev, gamma, sampling, scratch, s, random_seed, r_const, stream, logprobs);
+}
+extern "C" int sd_spec_generate_penalties(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling,
+                                          const sd_spec_scratch *scratch, sd_seq_state *s, uint64_t random_seed, const float *r_const,
+                                          void *stream, const sd_logprob_block *logprobs, const sd_penalty_block *penalties) {
+    return spec_generate(dev, gamma, sampling, scratch, s, random_seed, r_const, stream, logprobs, penalties);
 }
 
 // ---- the prompt queue of the lock-step loop ---------------------------------------------------------------------
@@ -499,7 +575,7 @@ static int queue_idle_prefill(PromptQueue &q, sd_batch_stream *slots, const std:
 // params (or NULL: sm's triple for everyone): per-request sampling parameters, indexed by stream - with a queue, by prompt.
 static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_streams, PromptQueue *q, int gamma, const sd_sampling &sm,
                          const sd_row_sampling *params, uint64_t random_seed, const float *r_const, const sd_spec_scratch &sc, sd_lockstep_log *log, void *stream,
-                         const sd_logprob_block *lp) {
+                         const sd_logprob_block *lp, const sd_penalty_block *pb) {
     hipStream_t st = (hipStream_t)stream;
     const int g = gamma, n_err = 3 * g + 1;
     // rows per target pass (every verify row is a logit row: sd_model_max_pass_rows, 64 for a model whose lm_head or
@@ -552,8 +628,35 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
     const bool tiles_ok = head_tiles_ok(sm.top_k, sm.temperature, sm.V, sm.ld);
     // the triple of the request a stream runs: a queue's slot changes parameters when it changes hands
     auto params_of = [&](const sd_batch_stream &s) -> const sd_row_sampling & { return params[q ? q->occ[&s - streams] : &s - streams]; };
-    int L0[SD_MAX_STREAMS];                                       // (logprobs without a queue) the streams' lengths on entry
+    int L0[SD_MAX_STREAMS];                                       // (logprobs, penalties without a queue) the streams' lengths on entry
     std::vector<sd_logprob_item> litems;
+    // penalties: the triple and the prompt length of the request a stream runs, and the launch over a pass's logit rows - m
+    // streams from act[a0], stream j's n_rows(j) rows packed in stream order in `src`, the first at position pos0(j) -
+    // ahead of the norm launch `nr`, which then reads the block's slab.  A pass without a penalised stream is left alone.
+    auto pen_of = [&](const sd_batch_stream &s) -> const sd_penalty & { return pb->params[q ? q->occ[&s - streams] : &s - streams]; };
+    auto pass_penalised = [&](int a0, int m) {
+        bool any = false;
+        for (int j = 0; pb && j < m; ++j) any = any || !penalty_neutral(pen_of(*act[a0 + j]));
+        return any;
+    };
+    sd_penalty_item pitems[SD_MAX_STREAMS];
+    auto penalise_pass = [&](int a0, int m, const HeadOut &src, auto n_rows, auto pos0, NormRequest &nr) -> int {
+        int r0 = 0;
+        for (int j = 0; j < m; ++j) {
+            const sd_batch_stream &s = *act[a0 + j];
+            const int slot = (int)(&s - streams), nr_j = n_rows(j);
+            if (nr_j > PEN_MAX_ROWS || r0 + nr_j > pb->max_rows) {
+                sd_set_error("%s: penalties: stream %d has %d logit rows in a pass of more than %d (a launch takes %d per stream, the "
+                             "slab holds %d)", who, slot, nr_j, r0, PEN_MAX_ROWS, pb->max_rows);
+                return SD_ERR_INVALID;
+            }
+            pitems[j] = penalty_item(*pb, src, r0, nr_j, s.seq, pos0(j), q ? q->prompts[q->occ[slot]].L : L0[slot], pen_of(s));
+            r0 += nr_j;
+        }
+        if (int prc = sd_penalize_rows(pitems, m, sm.V, nr.mode, stream); prc != SD_OK) return prc;
+        norm_from_penalised(nr, *pb);
+        return SD_OK;
+    };
     for (int i = 0; i < n_streams; ++i) {
         L0[i] = streams[i].len;
         streams[i].done = q ? 1 : 0; streams[i].calls = 0;
@@ -604,6 +707,8 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
                         pass_tiles = pass_tiles && head_tiles_ok(prows[j].top_k, prows[j].temperature, sm.V, sm.ld);
                     }
                 }
+                const bool pen_pass = pass_penalised(a0, m);      // (its rows take no tile maxima)
+                pass_tiles = pass_tiles && !pen_pass;
                 for (int j = 0; j < m; ++j) {
                     sd_batch_stream &s = *act[a0 + j];
                     draft_step_rows(items[j], rows[j], s.draft, s.seq, s.q_hist, sm.ld, s.err_words, g, Ls[a0 + j], i, s.draft_len,
@@ -620,7 +725,10 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
                 for (int j = 0; j < rq.zero_n; ++j) rq.zero_ptr[j] = rows[j].probs_out;
                 if ((rc = batch_forward(items.data(), (int)items.size(), sc.draft.logits, sc.draft.ld_logits, &rq, &ho, stream)) != SD_OK) break;
                 if (m == 0) continue;                             // (joiner rows only)
-                NormRequest nr = norm_request(sm, sc.draft.norm_mode, fused_tail ? ho : scratch_rows(sc.draft));
+                const HeadOut src = fused_tail ? ho : scratch_rows(sc.draft);
+                NormRequest nr = norm_request(sm, sc.draft.norm_mode, src);
+                if (pen_pass && (rc = penalise_pass(a0, m, src, [](int) { return 1; }, [&](int j) { return Ls[a0 + j] + i - 1; }, nr)) != SD_OK)
+                    break;
                 nr.rows = m; nr.workspace = sc.norm_workspace; nr.row_params = params ? prows.data() : nullptr;
                 rc = sd_norm_batch_tiles(nr, rows.data(), 1, stream);
             }
@@ -667,6 +775,9 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
             // one pass holds every stream: the rows' candidate lists (behind the CandRows of the workspace) serve the
             // residual / bonus sample below
             NormRequest nr = norm_request(sm, sc.target.norm_mode, scratch_rows(sc.target));
+            if (pass_penalised(a0, m) && (rc = penalise_pass(a0, m, scratch_rows(sc.target), [&](int j) { return items[j].n_new; },
+                                                             [&](int j) { return items[j].pos0; }, nr)) != SD_OK)
+                break;
             nr.rows = (int)rows.size(); nr.workspace = sc.norm_workspace; nr.lists = lists_on ? list_base : nullptr;
             nr.row_params = params ? prows.data() : nullptr;
             rc = sd_norm_batch_tiles(nr, rows.data(), 0, stream);
@@ -764,9 +875,16 @@ static int check_row_params(const char *who, const char *what, const sd_row_samp
     return SD_OK;
 }
 
+// the logit rows of a lock-step loop's largest pass: whole streams of gamma + 1 verify rows, as many as a target pass holds
+static int lockstep_penalty_rows(const sd_batch_stream *streams, int n_streams, int gamma, const sd_spec_scratch &sc) {
+    const int pass_rows = std::min(sc.max_rows_per_forward, streams[0].target ? streams[0].target->max_pass_rows : SD_MAX_ROWS);
+    return std::min(std::max(pass_rows, gamma + 1), n_streams * (gamma + 1));
+}
+
 static int batch_generate(const char *who, sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
                           const sd_row_sampling *params, uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
-                          sd_lockstep_log *log, void *stream, const sd_logprob_block *lp = nullptr) {
+                          sd_lockstep_log *log, void *stream, const sd_logprob_block *lp = nullptr,
+                          const sd_penalty_block *pb = nullptr) {
     SD_REQUIRE(streams && n_streams >= 1 && n_streams <= 16 && gamma >= 1 && gamma <= 16 && sampling && scratch && log &&
                scratch->draft.logits && scratch->target.logits, "%s: bad arguments", who);
     SD_REQUIRE(!random_seed || r_const, "%s: random_seed needs its uniform (r_const)", who);
@@ -775,7 +893,11 @@ static int batch_generate(const char *who, sd_batch_stream *streams, int n_strea
         if (int rc = check_row_params(who, "stream", params, n_streams); rc != SD_OK) return rc;
     if (lp)
         if (int rc = check_logprob_block(who, lp, n_streams); rc != SD_OK) return rc;
-    return lockstep_loop(who, streams, n_streams, nullptr, gamma, *sampling, params, random_seed, r_const, *scratch, log, stream, lp);
+    if (pb)
+        if (int rc = check_penalty_block(who, "stream", &pb, n_streams, sampling->V, lockstep_penalty_rows(streams, n_streams, gamma, *scratch));
+            rc != SD_OK)
+            return rc;
+    return lockstep_loop(who, streams, n_streams, nullptr, gamma, *sampling, params, random_seed, r_const, *scratch, log, stream, lp, pb);
 }
 
 extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
@@ -799,7 +921,7 @@ static int queue_generate(const char *who, int n_passes_out, sd_session *donor_d
                           sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
                           int prefill_chunk, int gamma, const sd_sampling *sampling, const sd_row_sampling *params,
                           uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log,
-                          int *passes_out, void *stream, const sd_logprob_block *lp = nullptr) {
+                          int *passes_out, void *stream, const sd_logprob_block *lp = nullptr, const sd_penalty_block *pb = nullptr) {
     SD_REQUIRE(n_slots >= 1 && n_slots <= 16, "%s: n_slots %d outside 1..16", who, n_slots);
     SD_REQUIRE(gamma >= 1 && gamma <= 16, "%s: gamma %d outside 1..16", who, gamma);
     SD_REQUIRE(n_prompts >= 1 && prefill_chunk >= 0, "%s: n_prompts %d, prefill_chunk %d", who, n_prompts, prefill_chunk);
@@ -842,7 +964,11 @@ static int queue_generate(const char *who, int n_passes_out, sd_session *donor_d
     q.donor_draft = donor_draft; q.donor_target = donor_target; q.shared_rows = shared_rows;
     if (lp)
         if (int rc = check_logprob_block(who, lp, n_prompts); rc != SD_OK) return rc;
-    const int rc = lockstep_loop(who, slots, n_slots, &q, gamma, *sampling, params, random_seed, r_const, *scratch, log, stream, lp);
+    if (pb)
+        if (int rc = check_penalty_block(who, "prompt", &pb, n_prompts, sampling->V, lockstep_penalty_rows(slots, n_slots, gamma, *scratch));
+            rc != SD_OK)
+            return rc;
+    const int rc = lockstep_loop(who, slots, n_slots, &q, gamma, *sampling, params, random_seed, r_const, *scratch, log, stream, lp, pb);
     if (passes_out) {
         const int v[6] = {q.target_passes, q.draft_passes, q.extra_passes, q.prefill_passes, q.prompt_rows, q.copied_rows};
         for (int i = 0; i < n_passes_out; ++i) passes_out[i] = v[i];
@@ -903,6 +1029,34 @@ extern "C" int sd_spec_queue_generate_logprobs(sd_batch_stream *slots, int n_slo
     return queue_generate("sd_spec_queue_generate_logprobs", 6, donor_draft, donor_target, shared_rows, slots, n_slots, slot_cap, prompts,
                           n_prompts, prefill_chunk, gamma, sampling, prompt_params, random_seed, r_const, scratch, log, passes_out,
                           stream, logprobs);
+}
+
+// The lock-step loops with per-request penalties: the _logprobs entries' arguments (logprobs may be NULL) plus the block
+// (NULL: those entries)
+extern "C" int sd_spec_batch_generate_penalties(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
+                                                uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
+                                                sd_lockstep_log *log, void *stream, const sd_row_sampling *stream_params,
+                                                const sd_logprob_block *logprobs, const sd_penalty_block *penalties) {
+    if (!penalties)
+        return sd_spec_batch_generate_logprobs(streams, n_streams, gamma, sampling, random_seed, r_const, scratch, log, stream,
+                                               stream_params, logprobs);
+    return batch_generate("sd_spec_batch_generate_penalties", streams, n_streams, gamma, sampling, stream_params, random_seed, r_const,
+                          scratch, log, stream, logprobs, penalties);
+}
+
+extern "C" int sd_spec_queue_generate_penalties(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
+                                                int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
+                                                const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log,
+                                                int *passes_out, void *stream, sd_session *donor_draft, sd_session *donor_target,
+                                                int shared_rows, const sd_row_sampling *prompt_params, const sd_logprob_block *logprobs,
+                                                const sd_penalty_block *penalties) {
+    if (!penalties)
+        return sd_spec_queue_generate_logprobs(slots, n_slots, slot_cap, prompts, n_prompts, prefill_chunk, gamma, sampling, random_seed,
+                                               r_const, scratch, log, passes_out, stream, donor_draft, donor_target, shared_rows,
+                                               prompt_params, logprobs);
+    return queue_generate("sd_spec_queue_generate_penalties", 6, donor_draft, donor_target, shared_rows, slots, n_slots, slot_cap, prompts,
+                          n_prompts, prefill_chunk, gamma, sampling, prompt_params, random_seed, r_const, scratch, log, passes_out,
+                          stream, logprobs, penalties);
 }
 
 // ---- the width-w loop of sampling/multi.py in native code (reference speculative_sampling.py:1379-1716, strategy "iid")
@@ -1148,7 +1302,7 @@ extern "C" size_t sd_ar_block_bytes(int n_streams) {
 
 static int ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
                              void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream,
-                             const sd_logprob_block *lp) {
+                             const sd_logprob_block *lp, const sd_penalty_block *pb = nullptr) {
     SD_REQUIRE(n_streams >= 1 && n_streams <= 16, "sd_ar_batch_generate: n_streams %d outside 1..16", n_streams);
     SD_REQUIRE(streams && sampling && head && log && head->logits && dev_block && host_block, "sd_ar_batch_generate: null argument");
     const sd_sampling &sm = *sampling;
@@ -1168,6 +1322,8 @@ static int ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_samp
                streams[0].session->max_pass_rows);
     if (lp)
         if (int rc = check_logprob_block("sd_ar_batch_generate_logprobs", lp, n_streams); rc != SD_OK) return rc;
+    if (pb)
+        if (int rc = check_penalty_block("sd_ar_batch_generate_penalties", "stream", &pb, n_streams, sm.V, n_streams); rc != SD_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const bool timed = log->step_ms_out != nullptr;
     LoopEvents ev(timed ? 2 : 0, "sd_ar_batch_generate");
@@ -1196,7 +1352,9 @@ static int ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_samp
         HeadReq rq = {};
         HeadOut ho = {};
         rq.raw = true;                                            // the lock-step draft step's sampler feed (see there)
-        rq.zero_n = tiles_ok ? n : 0;
+        bool pen_step = false;                                    // a step with a penalised stream takes no tile maxima
+        for (int j = 0; pb && j < n; ++j) pen_step = pen_step || !penalty_neutral(pb->params[act[j]]);
+        rq.zero_n = tiles_ok && !pen_step ? n : 0;
         for (int j = 0; j < n; ++j) {
             sd_ar_stream &s = streams[act[j]];
             draft_step_rows(items[j], rows[j], s.session, s.seq, s.probs, sm.ld, s.err_words, 1, s.len, 0, s.cache_len, s.seed, s.draw);
@@ -1211,6 +1369,15 @@ static int ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_samp
             rc = batch_forward(items.data(), n, head->logits, head->ld_logits, &rq, &ho, stream);
         if (rc != SD_OK) break;
         NormRequest nr = norm_request(sm, head->norm_mode, ho);
+        if (pen_step) {                                           // stream act[j]'s one row, at position len - 1
+            sd_penalty_item pi[16];
+            for (int j = 0; j < n; ++j) {
+                const sd_ar_stream &s = streams[act[j]];
+                pi[j] = penalty_item(*pb, ho, j, 1, s.seq, s.len - 1, L0[act[j]], pb->params[act[j]]);
+            }
+            if ((rc = sd_penalize_rows(pi, n, sm.V, nr.mode, stream)) != SD_OK) break;
+            norm_from_penalised(nr, *pb);
+        }
         nr.rows = n; nr.workspace = norm_workspace;
         if ((rc = sd_norm_batch_tiles(nr, rows.data(), 1, stream)) != SD_OK) break;
         if (lp) {                                                 // behind the sampler: stream b's one row, scored at seq[len]
@@ -1261,4 +1428,10 @@ extern "C" int sd_ar_batch_generate_logprobs(sd_ar_stream *streams, int n_stream
                                              const sd_head_scratch *head, void *norm_workspace, void *dev_block, void *host_block,
                                              sd_ar_log *log, void *stream, const sd_logprob_block *logprobs) {
     return ar_batch_generate(streams, n_streams, sampling, head, norm_workspace, dev_block, host_block, log, stream, logprobs);
+}
+extern "C" int sd_ar_batch_generate_penalties(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling,
+                                              const sd_head_scratch *head, void *norm_workspace, void *dev_block, void *host_block,
+                                              sd_ar_log *log, void *stream, const sd_logprob_block *logprobs,
+                                              const sd_penalty_block *penalties) {
+    return ar_batch_generate(streams, n_streams, sampling, head, norm_workspace, dev_block, host_block, log, stream, logprobs, penalties);
 }

@@ -3,12 +3,13 @@ piece of reference semantics - the EOS rule, the reseed quirk, how the acceptanc
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 import torch
 
-from .._lib import (LOGPROB_SLICE, LOGPROB_STREAMS, SdHeadScratch, SdLockstepLog, SdLogprobBlock, SdRowSampling, SdSampling,
-                    SdSeqState, SdSpecScratch, SdSpecStream)
+from .._lib import (LOGPROB_SLICE, LOGPROB_STREAMS, SdHeadScratch, SdLockstepLog, SdLogprobBlock, SdPenalty, SdPenaltyBlock,
+                    SdRowSampling, SdSampling, SdSeqState, SdSpecScratch, SdSpecStream)
 from ..noise import DeviceNoise, HostTorchNoise
 from .kvcache_model import KVCacheModel
 
@@ -240,6 +241,49 @@ class LogprobBlock:
     def tensor(self, i: int, n: int, device) -> torch.Tensor:
         """The (1, n) float32 scores of stream i's first n new tokens (n: the output's length minus the prompt's)."""
         return torch.from_numpy(self.out[i][:max(0, n)].copy()).unsqueeze(0).to(device)
+
+
+def penalty_triples(n: int, what: str, repetition_penalty, frequency_penalty, presence_penalty):
+    """Per-request ``repetition_penalty`` / ``frequency_penalty`` / ``presence_penalty`` of the native loops: each one value
+    (broadcast) or a sequence with one entry per ``what`` ("prompt", "stream"), ``n`` of them.  Returns ``None`` for the three
+    neutral scalars (1, 0, 0) - the call then takes the entry point it took before - else the ``n`` (repetition, frequency,
+    presence) triples; raises ValueError naming the parameter for a sequence of another length, a value that is not a finite
+    number, a repetition penalty <= 0.  Touches no model and no GPU."""
+    given = {"repetition_penalty": repetition_penalty, "frequency_penalty": frequency_penalty, "presence_penalty": presence_penalty}
+    if not any(_per_request(v) for v in given.values()) and (repetition_penalty, frequency_penalty, presence_penalty) == (1.0, 0.0, 0.0) \
+            and not any(isinstance(v, bool) for v in given.values()):
+        return None
+    cols = {}
+    for name, v in given.items():
+        if not _per_request(v):
+            v = [v] * n
+        elif len(v) != n:
+            raise ValueError(f"{name}: {len(v)} entries for {n} {what}s")
+        cols[name] = [x.item() if isinstance(x, (np.generic, torch.Tensor)) else x for x in v]
+        for i, x in enumerate(cols[name]):
+            if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x):
+                raise ValueError(f"{name}: {what} {i}: a finite number is required, not {x!r}")
+            if name == "repetition_penalty" and x <= 0:
+                raise ValueError(f"repetition_penalty: {what} {i}: a value > 0 is required, not {x!r}")
+    return [(float(r), float(f), float(p)) for r, f, p in zip(*cols.values())]
+
+
+def penalties_need_target_rows(target_m) -> None:
+    """Penalties edit the logit rows where a single-GPU forward leaves them: a tensor-parallel shard is refused."""
+    if getattr(target_m, "tp_group", None) is not None:
+        raise ValueError("repetition / frequency / presence penalties are not available with a tensor-parallel target model")
+
+
+class PenaltyBlock:
+    """The SdPenaltyBlock of one native loop call: the triples (one per stream, per prompt in the queue) and the device slab
+    the edited logit rows of a pass go to - ``max_rows`` rows of V floats, 16-byte aligned with a stride that is a multiple
+    of 4, so the norm launch keeps its two-kernel path."""
+
+    def __init__(self, device, triples, V: int, max_rows: int):
+        ld = (int(V) + 3) // 4 * 4
+        self.rows = torch.empty((max(1, int(max_rows)), ld), dtype=torch.float32, device=device)
+        self._params = (SdPenalty * len(triples))(*[SdPenalty(*t) for t in triples])
+        self.block = SdPenaltyBlock(self.rows.data_ptr(), ld, self.rows.shape[0], self._params)
 
 
 def raise_loop_error(code: int) -> None:

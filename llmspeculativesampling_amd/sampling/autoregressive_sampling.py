@@ -8,22 +8,32 @@ import torch
 
 from .._lib import lib, check, SdArLog, SdArStream
 from ..engine import as_specdec_model, _stream, check_token_ids
-from ._loop_common import (LogprobBlock, device_rng, head_scratch, logprobs_need_target_rows, make_noise, open_stream,
-                           raise_loop_error, sampling_block)
+from ._loop_common import (LogprobBlock, PenaltyBlock, device_rng, head_scratch, logprobs_need_target_rows, make_noise, open_stream,
+                           penalties_need_target_rows, penalty_triples, raise_loop_error, sampling_block)
 from .kvcache_model import KVCacheModel
 
 
 @torch.no_grad()
 def autoregressive_sampling(x: torch.Tensor, model, N: int, eos_token_id: int, temperature: float = 1,
                             top_k: int = 0, top_p: float = 0, pad_token_id=None, *, rng=None, _native: bool = True,
-                            logprobs: bool = False):
+                            logprobs: bool = False, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
+                            presence_penalty: float = 0.0):
     """reference autoregressive_sampling.py:9-61: exactly N tokens unless EOS is drawn (the EOS is kept).
     RNG contract: one ``sample`` per token.  With the device RNG the whole loop is one native call
     (sd_ar_batch_generate with one stream); ``_native=False`` keeps the interpreter loop below, which the host RNG
     and ReplayNoise always take (same tokens, same exceptions).
     ``logprobs`` (native loop only): returns ``(tokens, logprobs)``, a float32 tensor (1, len(tokens) - len(x)) with the
     model's log-probability of every new token - ``log_softmax`` in fp32 of the raw logit row it was sampled from, taken
-    before temperature, top_k and top_p: what the model says, not what the sampler drew from."""
+    before temperature, top_k and top_p: what the model says, not what the sampler drew from.
+    ``repetition_penalty`` / ``frequency_penalty`` / ``presence_penalty`` (native loop only; neutral 1 / 0 / 0): every logit row
+    is edited on the device by its own history before it is normalised (``sampling.utils.apply_penalties``); ``logprobs`` stay
+    what the model says."""
+    pen = penalty_triples(1, "stream", repetition_penalty, frequency_penalty, presence_penalty)
+    if pen is not None and not (_native and device_rng(rng)):
+        raise ValueError('repetition / frequency / presence penalties need the native loop: rng="device" (or a device noise '
+                         'object), not _native=False')
+    if pen is not None:
+        penalties_need_target_rows(model)
     if logprobs and not (_native and device_rng(rng)):
         raise ValueError('logprobs=True needs the native loop: rng="device" (or a device noise object), not _native=False')
     assert x.shape[0] == 1
@@ -40,7 +50,7 @@ def autoregressive_sampling(x: torch.Tensor, model, N: int, eos_token_id: int, t
     if _native and getattr(noise, "on_device", False):
         run = ArRun(m, temperature, top_k, top_p, eos_token_id)
         run.add(kv, seq32, x[0].to(device="cpu", dtype=torch.int32).numpy(), L0 + N, noise)
-        run.generate(logprobs=logprobs)
+        run.generate(logprobs=logprobs, penalties=pen)
         out = torch.from_numpy(run.tokens(0)).to(torch.int64).unsqueeze(0).to(x.device)
         return (out, run.logprobs(0, x.device)) if logprobs else out
     n_out = 0
@@ -87,7 +97,8 @@ class ArRun:
         err = torch.zeros(2, dtype=torch.int32, device=self.m.device)
         self.streams.append(_ArStream(kv, seq32, host, err, noise, len(prompt), int(T)))
 
-    def generate(self, timing: bool = False, logprobs: bool = False) -> None:
+    def generate(self, timing: bool = False, logprobs: bool = False, penalties=None) -> None:
+        """``penalties``: None, or one (repetition, frequency, presence) triple per stream (_loop_common.penalty_triples)."""
         B = len(self.streams)
         if not 1 <= B <= 16:
             raise ValueError(f"autoregressive sampling takes 1..16 streams per call, not {B}")
@@ -111,7 +122,10 @@ class ArRun:
                 head_scratch(kv0._session), norm_ws.data_ptr() if norm_ws is not None else None,
                 dev_block.data_ptr(), host_block.data_ptr(), log, _stream())
         self.lp = LogprobBlock(dev, [s.T + 1 for s in self.streams]) if logprobs else None
-        if self.lp is None:
+        pb = PenaltyBlock(dev, penalties, self.m.cfg.vocab_size, B) if penalties is not None else None
+        if pb is not None:
+            rc = lib.sd_ar_batch_generate_penalties(*args, self.lp.block if self.lp is not None else None, pb.block)
+        elif self.lp is None:
             rc = lib.sd_ar_batch_generate(*args)
         else:
             rc = lib.sd_ar_batch_generate_logprobs(*args, self.lp.block)

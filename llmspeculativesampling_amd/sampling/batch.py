@@ -22,9 +22,9 @@ import torch
 from .._lib import lib, check, SdAcceptResult, SdBatchStream, SdQueuePrompt
 from ..engine import as_specdec_model, _stream, check_token_ids, same_device, batch_prefill
 from ..noise import DeviceNoise
-from ._loop_common import (LockstepLog, LogprobBlock, LoopLog, bind_spec_slot, lockstep_result, logprobs_need_target_rows,
-                           open_spec_slot, open_stream, reseed_uniforms, row_sampling, row_sampling_array, sampling_block,
-                           spec_scratch)
+from ._loop_common import (LockstepLog, LogprobBlock, LoopLog, PenaltyBlock, bind_spec_slot, lockstep_result,
+                           logprobs_need_target_rows, open_spec_slot, open_stream, penalties_need_target_rows, penalty_triples,
+                           reseed_uniforms, row_sampling, row_sampling_array, sampling_block, spec_scratch)
 from .autoregressive_sampling import ArRun
 from .kvcache_model import KVCacheModel
 
@@ -55,7 +55,7 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
                                pad_token_id, max_len: int, gamma: int = 4, temperature: float = 1, top_k: int = 0,
                                top_p: float = 0, random_seed: int = None, details: bool = False,
                                seeds: Optional[Sequence[int]] = None, _timing: Optional[dict] = None, *,
-                               logprobs: bool = False):
+                               logprobs: bool = False, repetition_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0):
     """B streams at once; ``prefixes[i]`` is (1, L_i) int64.  Returns a list of (1, len_i) tensors (and a list of
     ``details`` dicts with the reference's keys when ``details``).  Device Philox RNG, stream i seeded ``seeds[i]``.
     ``temperature``, ``top_k`` and ``top_p`` each take one value for all streams or a sequence with one entry per stream
@@ -66,11 +66,19 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
     ``logprobs``: the return value gains one last element, a list of float32 (1, len_i - L_i) tensors with the TARGET
     model's log-probability of every new token of stream i, as ``speculative_sampling(logprobs=True)`` defines it: the
     log-softmax of the raw target logits, before temperature, top_k and top_p - what the model says, not what the sampler
-    drew from - cut where the tokens are cut (sd_spec_batch_generate_logprobs)."""
+    drew from - cut where the tokens are cut (sd_spec_batch_generate_logprobs).
+    ``repetition_penalty`` / ``frequency_penalty`` / ``presence_penalty`` (neutral 1 / 0 / 0): each one value for all streams
+    or one per stream, broadcast like ``temperature``; stream i equals ``speculative_sampling(prefixes[i], ...,
+    repetition_penalty=r_i, frequency_penalty=f_i, presence_penalty=p_i, rng=DeviceNoise(seeds[i]))``
+    (sd_spec_batch_generate_penalties; ``sampling.utils.apply_penalties`` has the definition).  A sequence of another length, a
+    value that is not finite or a repetition penalty <= 0 raises ValueError before a model is touched."""
     try:
         triples = row_sampling(len(prefixes), "stream", temperature, top_k, top_p)
+        pen = penalty_triples(len(prefixes), "stream", repetition_penalty, frequency_penalty, presence_penalty)
     except TypeError:
         raise ValueError("prefixes: a sequence of (1, L) int64 prompts is required") from None
+    if pen is not None:
+        penalties_need_target_rows(target_model)
     draft_m, target_m = as_specdec_model(approx_model), as_specdec_model(target_model)
     same_device(draft_m, target_m)
     if logprobs:
@@ -130,7 +138,11 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
             int(random_seed or 0), r_const.data_ptr() if r_const is not None else None, spec_scratch(d0, t0, norm_ws, per_pass),
             vlog.block, cu)
     lp = LogprobBlock(dev, [len(s.log.host_seq) for s in streams]) if logprobs else None
-    if lp is not None:
+    pb = PenaltyBlock(dev, pen, V, min(max(per_pass, gamma + 1), B * (gamma + 1))) if pen is not None else None
+    if pb is not None:
+        check(lib.sd_spec_batch_generate_penalties(*args, row_sampling_array(triples), lp.block if lp is not None else None, pb.block),
+              "sd_spec_batch_generate_penalties")
+    elif lp is not None:
         check(lib.sd_spec_batch_generate_logprobs(*args, row_sampling_array(triples), lp.block), "sd_spec_batch_generate_logprobs")
     elif triples is None:
         check(lib.sd_spec_batch_generate(*args), "sd_spec_batch_generate")
@@ -261,9 +273,30 @@ def speculative_sampling_queue_logprobs(prefixes: Sequence[torch.Tensor], approx
                   random_seed, details, seeds, slots, prefill_chunk, _timing, shared_prefix, logprobs=True)
 
 
+@torch.no_grad()
+def speculative_sampling_queue_requests(prefixes: Sequence[torch.Tensor], approx_model, target_model, eos_token_id, pad_token_id,
+                                        max_len, gamma: int = 4, temperature: float = 1, top_k: int = 0, top_p: float = 0,
+                                        random_seed: int = None, details: bool = False, seeds: Optional[Sequence[int]] = None,
+                                        slots: int = 8, prefill_chunk: int = 0, _timing: Optional[dict] = None,
+                                        shared_prefix: int = 0, *, logprobs: bool = False, repetition_penalty=1.0,
+                                        frequency_penalty=0.0, presence_penalty=0.0):
+    """speculative_sampling_queue_shared with a request's whole sampling block: next to the per-prompt ``temperature`` /
+    ``top_k`` / ``top_p``, ``repetition_penalty`` / ``frequency_penalty`` / ``presence_penalty`` (neutral 1 / 0 / 0) each take
+    one value for all prompts or one per prompt.  Prompt i then equals ``speculative_sampling(prefixes[i], ...,
+    repetition_penalty=r_i, frequency_penalty=f_i, presence_penalty=p_i, rng=DeviceNoise(seeds[i]))``, whichever slot it decodes
+    in and whatever its neighbours ask for: a slot changes penalties when it changes hands, and the prompt that counts as a
+    request's prompt is its own (sd_spec_queue_generate_penalties; ``sampling.utils.apply_penalties`` has the definition).  A
+    sequence of another length, a value that is not finite or a repetition penalty <= 0 raises ValueError before a model is
+    touched.  ``logprobs=True`` returns what speculative_sampling_queue_logprobs returns: the scores stay what the model says,
+    penalties or not.  (A function of its own: the queues' parameter lists are pinned by their tests.)"""
+    return _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max_len, gamma, temperature, top_k, top_p,
+                  random_seed, details, seeds, slots, prefill_chunk, _timing, shared_prefix, logprobs=logprobs,
+                  penalties=(repetition_penalty, frequency_penalty, presence_penalty))
+
+
 def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max_len, gamma, temperature, top_k, top_p,
-           random_seed, details, seeds, slots, prefill_chunk, _timing, shared_prefix, logprobs=False):
-    """The prompt queue behind both public entry points (their docstrings have the contract)."""
+           random_seed, details, seeds, slots, prefill_chunk, _timing, shared_prefix, logprobs=False, penalties=(1.0, 0.0, 0.0)):
+    """The prompt queue behind the public entry points (their docstrings have the contract)."""
     budgets = _queue_arguments(prefixes, max_len, seeds, slots)
     shared = _shared_prefix_argument(prefixes, shared_prefix)
     if isinstance(prefill_chunk, bool) or not isinstance(prefill_chunk, int) or prefill_chunk < 0:
@@ -271,6 +304,9 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
     if not 1 <= gamma <= 16:
         raise ValueError(f"gamma: 1..16, not {gamma}")
     triples = row_sampling(len(prefixes), "prompt", temperature, top_k, top_p)
+    pen = penalty_triples(len(prefixes), "prompt", *penalties)
+    if pen is not None:
+        penalties_need_target_rows(target_model)
     if triples is not None:                                       # (a slot's KVCacheModel and the block's own triple are not read)
         temperature, top_k, top_p = triples[0]
     draft_m, target_m = as_specdec_model(approx_model), as_specdec_model(target_model)
@@ -331,7 +367,11 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
     # (without donors sd_spec_queue_generate_shared is sd_spec_queue_generate, which has no room for the two row counts)
     args += (*[ses.handle if ses else None for ses in donors], rows)
     lp = LogprobBlock(dev, [len(log.host_seq) for log in logs]) if logprobs else None
-    if lp is not None:
+    pb = PenaltyBlock(dev, pen, V, min(max(per_pass, gamma + 1), S * (gamma + 1))) if pen is not None else None
+    if pb is not None:
+        check(lib.sd_spec_queue_generate_penalties(*args, row_sampling_array(triples), lp.block if lp is not None else None, pb.block),
+              "sd_spec_queue_generate_penalties")
+    elif lp is not None:
         check(lib.sd_spec_queue_generate_logprobs(*args, row_sampling_array(triples), lp.block), "sd_spec_queue_generate_logprobs")
     elif triples is None:
         check(lib.sd_spec_queue_generate_shared(*args), "sd_spec_queue_generate_shared")
@@ -359,17 +399,23 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
 def autoregressive_sampling_batch(xs: Sequence[torch.Tensor], model, N: int, eos_token_id, temperature: float = 1,
                                   top_k: int = 0, top_p: float = 0, pad_token_id=None, *,
                                   seeds: Optional[Sequence[int]] = None, _timing: Optional[dict] = None,
-                                  logprobs: bool = False):
+                                  logprobs: bool = False, repetition_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0):
     """``autoregressive_sampling`` for B streams at once: ``xs[i]`` is (1, L_i) int64, the result a list of (1, len_i)
     tensors.  The streams decode in lock-step and share every pass over the weights (sd_ar_batch_generate): each runs the
     algorithm of reference autoregressive_sampling.py:9-61 on its own Philox stream ``seeds[i]`` (default
     ``torch.initial_seed() + i``), so the outputs equal those of B ``autoregressive_sampling(..., rng=DeviceNoise(seed))``
     calls.  ``_timing["step"]`` receives (milliseconds, streams in the step) per step.  ``logprobs``: returns ``(outs,
     logprobs)``, a list of float32 (1, len_i - L_i) tensors with the model's log-probability of every new token: the
-    log-softmax of its raw logits, before temperature, top_k and top_p - what the model says, not what the sampler drew from."""
+    log-softmax of its raw logits, before temperature, top_k and top_p - what the model says, not what the sampler drew from.
+    ``repetition_penalty`` / ``frequency_penalty`` / ``presence_penalty`` (neutral 1 / 0 / 0): each one value for all streams or
+    one per stream; stream i equals ``autoregressive_sampling(xs[i], ..., rng=DeviceNoise(seeds[i]))`` with its values
+    (sd_ar_batch_generate_penalties)."""
     B = len(xs)
     if not 1 <= B <= 16:
         raise ValueError(f"autoregressive_sampling_batch takes 1..16 streams per call, not {B}")
+    pen = penalty_triples(B, "stream", repetition_penalty, frequency_penalty, presence_penalty)
+    if pen is not None:
+        penalties_need_target_rows(model)
     m = as_specdec_model(model)
     if logprobs:
         logprobs_need_target_rows(m)
@@ -386,7 +432,7 @@ def autoregressive_sampling_batch(xs: Sequence[torch.Tensor], model, N: int, eos
     batch_prefill([kv._session for kv in kvs], seqs, [x.shape[1] - 1 for x in xs])
     for x, seed, kv, seq32 in zip(xs, seeds, kvs, seqs):
         run.add(kv, seq32, x[0].to(device="cpu", dtype=torch.int32).numpy(), x.shape[1] + int(N), DeviceNoise(seed))
-    run.generate(timing=_timing is not None, logprobs=logprobs)
+    run.generate(timing=_timing is not None, logprobs=logprobs, penalties=pen)
     if _timing is not None:
         _timing.setdefault("step", []).extend(run.steps)
     outs = [torch.from_numpy(run.tokens(i)).to(torch.int64).unsqueeze(0).to(x.device) for i, x in enumerate(xs)]

@@ -16,9 +16,9 @@ import torch
 
 from .._lib import lib, check, SdAcceptResult
 from ..engine import as_specdec_model, _stream, check_token_ids, same_device
-from ._loop_common import (LogprobBlock, LoopLog, accept_rates_f64, cut_after_new_eos, details_dict, device_rng,
-                           logprobs_need_target_rows, make_noise, open_stream, raise_loop_error, reseed_uniforms, sampling_block,
-                           spec_scratch, spec_stream)
+from ._loop_common import (LogprobBlock, LoopLog, PenaltyBlock, accept_rates_f64, cut_after_new_eos, details_dict, device_rng,
+                           logprobs_need_target_rows, make_noise, open_stream, penalties_need_target_rows, penalty_triples,
+                           raise_loop_error, reseed_uniforms, sampling_block, spec_scratch, spec_stream)
 
 _make_noise = make_noise                              # beam.py, multi.py and tests import it from here
 
@@ -27,7 +27,8 @@ _make_noise = make_noise                              # beam.py, multi.py and te
 def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_token_id, pad_token_id,
                          max_len: int, gamma: int = 4, temperature: float = 1, top_k: int = 0, top_p: float = 0,
                          verbose: bool = False, random_seed: int = None, details: bool = False, *, rng=None,
-                         _event_logs=None, logprobs: bool = False):
+                         _event_logs=None, logprobs: bool = False, repetition_penalty: float = 1.0,
+                         frequency_penalty: float = 0.0, presence_penalty: float = 0.0):
     """reference speculative_sampling.py:1876-2076.
 
     ``rng`` (extension): "host" (default) draws every variate from torch's CPU generator in the
@@ -39,7 +40,20 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
     ``log_softmax`` in fp32 of the target's raw logit row for the position before it, taken before temperature, top_k and
     top_p - what the model says, not what the sampler drew from.  It is cut where the tokens are cut, and its mean is
     ``quality.get_score`` of the output without a second target pass (``quality.score_from_logprobs``).
+
+    ``repetition_penalty`` / ``frequency_penalty`` / ``presence_penalty`` (extension, native device-RNG loop only; neutral
+    1 / 0 / 0): every draft and target logit row is edited on the device by the row's own history before it is normalised,
+    as ``sampling.utils.apply_penalties`` defines it - the repetition penalty over prompt and output tokens (x / r for a
+    positive logit, x * r otherwise), ``frequency * count`` and ``presence`` subtracted for tokens generated so far.  They
+    change what the sampler draws from; ``logprobs`` stay what the model says.  ValueError before a model is touched for a
+    value that is not finite, a repetition penalty <= 0, an interpreter path or a tensor-parallel target.
     """
+    pen = penalty_triples(1, "stream", repetition_penalty, frequency_penalty, presence_penalty)
+    if pen is not None and (verbose or not device_rng(rng)):
+        raise ValueError('repetition / frequency / presence penalties need the native loop: rng="device" (or a device noise '
+                         'object) and verbose=False')
+    if pen is not None:
+        penalties_need_target_rows(target_model)
     if logprobs and (verbose or not device_rng(rng)):
         raise ValueError('logprobs=True needs the native loop: rng="device" (or a device noise object) and verbose=False')
     assert prefix.shape[0] == 1, "input batch size must be 1"
@@ -69,7 +83,7 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
     target, seq32 = open_stream(target_m, prefix[0], cap, cap + 1, temperature, top_k, top_p, noise)
     if getattr(noise, "on_device", False) and not verbose:
         return _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T, gamma, random_seed, details,
-                                   noise, _event_logs, logprobs)
+                                   noise, _event_logs, logprobs, pen)
 
     ori_eos_cnt = host_seq.count(eos_token_id)
     if _event_logs is not None:                       # bench.py: HIP-event brackets around every forward
@@ -181,7 +195,7 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
 
 
 def _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T, gamma, random_seed, details, noise,
-                        timing_log, logprobs=False):
+                        timing_log, logprobs=False, pen=None):
     """Device-RNG mode: the loop itself runs inside libspecdec (sd_spec_generate): per iteration the gamma draft steps,
     the target forward, the accept scan and the resample are enqueued and the stream is waited on once, in native code;
     the interpreter only sees the finished sequence and the per-iteration statistics.  Same loop semantics as the
@@ -202,11 +216,14 @@ def _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T,
                               draft._probs.stride(0), eos_token_id)
     scratch = spec_scratch(draft._session, target._session, target._norm_ws, target._session.max_rows)
     lp = LogprobBlock(dev, [T + gamma + 2]) if logprobs else None
+    pb = PenaltyBlock(dev, pen, target._model.cfg.vocab_size, gamma + 1) if pen is not None else None
     try:
         tick = process_time_ns()
         args = (stream, gamma, sampling, scratch, st, int(random_seed or 0), r_const.data_ptr() if r_const is not None else None,
                 _stream())
-        if lp is None:
+        if pb is not None:
+            check(lib.sd_spec_generate_penalties(*args, lp.block if lp is not None else None, pb.block), "sd_spec_generate_penalties")
+        elif lp is None:
             check(lib.sd_spec_generate(*args), "sd_spec_generate")
         else:
             check(lib.sd_spec_generate_logprobs(*args, lp.block), "sd_spec_generate_logprobs")

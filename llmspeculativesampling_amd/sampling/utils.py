@@ -193,3 +193,31 @@ def get_expect_cnt_by_thres(p_width, expect_thres):
         n -= 1
         mass += p_width[n]
     return int(n)
+
+
+def apply_penalties(logits_row: torch.Tensor, history, prompt_len: int, repetition: float = 1.0, frequency: float = 0.0,
+                    presence: float = 0.0) -> torch.Tensor:
+    """The per-request penalties as the native loops apply them (sd_penalize_rows; include/specdec.h has the text), in pure
+    torch on any device: ``logits_row`` is one (V,) row that predicts the token behind ``history`` (the ids seen so far, of
+    which the first ``prompt_len`` are the prompt).  For a token id t with c_all occurrences in ``history`` and c_out in
+    ``history[prompt_len:]``: where c_all > 0 and repetition != 1, ``y = x / repetition if x > 0 else x * repetition``
+    (prompt and output); where c_out > 0, ``y = y - frequency * c_out``, then ``y = y - presence`` (output only).  Every
+    result is one fp32 operation, rounded to the row's dtype when that is bf16 / fp16, as torch's 16-bit CPU kernels do; the
+    three parameters are rounded to fp32 once and to nothing else.  A token outside the history keeps its logit bit for bit,
+    NaN and +-inf take the same operations, a history entry outside [0, V) is ignored.  Returns a new row of the same dtype."""
+    assert logits_row.dim() == 1
+    V, dtype, dev = logits_row.shape[0], logits_row.dtype, logits_row.device
+    low = dtype in (torch.bfloat16, torch.float16)
+    rnd = (lambda t: t.to(dtype).float()) if low else (lambda t: t)
+    hist = torch.as_tensor(history, dtype=torch.int64, device=dev).reshape(-1)
+
+    def counts(h):
+        h = h[(h >= 0) & (h < V)]
+        return torch.bincount(h, minlength=V)[:V]
+    c_all, c_out = counts(hist), counts(hist[int(prompt_len):])
+    theta, f, pi = (torch.tensor(float(v), dtype=torch.float32, device=dev) for v in (repetition, frequency, presence))
+    y = logits_row.float()
+    if float(theta) != 1.0:
+        y = torch.where(c_all > 0, rnd(torch.where(y > 0, y / theta, y * theta)), y)
+    y = torch.where(c_out > 0, rnd(rnd(y - rnd(f * c_out.float())) - pi), y)
+    return y.to(dtype)

@@ -26,6 +26,13 @@ Decoding workloads, EOS off (every prompt generates its max_len):
   copy     (--workloads copy) no decoding: sd_session_copy_kv alone at the target's KV shape, 256 and 512 rows to 1 and 8
            destinations - device-event time per launch over 20 launches after 3 warm-up launches, and the bytes read plus
            the bytes written over that time.
+  penalties (--workloads penalties --json-out profiles/penalties_ab.json) the uniform prompts through ONE
+           speculative_sampling_queue_requests call per arm, 8 slots: penalties off, on for every prompt (repetition 1.2,
+           frequency 0.5, presence 0.5) and on for every second prompt - in that arm every pass is a penalised pass (no tile
+           maxima for anyone) but only half the rows are edited, which separates what the lost tile maxima cost from what the
+           edit costs.  Also sd_penalize_rows alone at V = 32000 with 512-token histories, 8 items x 1 row (a draft step of 8
+           streams) and 8 items x 5 rows (their verify): device-event time per launch, and gamma x the first + the second as
+           the penalty launches' time per iteration.
 Both arms run in this process, alternated rep by rep after one warm-up rep of each (which also loads every kernel); a rep is
 the whole call or calls, prefill included, between two device synchronisations on the host clock.  Per arm: tokens/s per rep
 and their median, iterations, passes over the target weights (verify passes plus prompt-only passes; for the batch arm the
@@ -45,10 +52,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from llmspeculativesampling_amd.config import load_config  # noqa: E402
 from llmspeculativesampling_amd.engine import SpecDecModel, MAX_PREFILL_ROWS  # noqa: E402
 from llmspeculativesampling_amd.harness import synthetic_prompts  # noqa: E402
-from llmspeculativesampling_amd.sampling import speculative_sampling_batch, speculative_sampling_queue, speculative_sampling_queue_shared  # noqa: E402
+from llmspeculativesampling_amd.sampling import (speculative_sampling_batch, speculative_sampling_queue,  # noqa: E402
+                                                 speculative_sampling_queue_requests, speculative_sampling_queue_shared)
 
 SLOTS, GAMMA = 8, 4
 SHARED = 256                                                      # tokens of the `shared` workload's common prefix
+PENALTY = (1.2, 0.5, 0.5)                                         # (repetition, frequency, presence) of `penalties`
 MIXED_CLASSES = [(1.0, 20, 0.9), (0.7, 50, 0.95), (1.0, 0, 0.9), (1.3, 5, 0.0)]   # (temperature, top_k, top_p) of `mixed`
 
 
@@ -98,6 +107,33 @@ def copy_bench(model, rows_list=(256, 512), dst_counts=(1, 8), warmup=3, launche
     return out
 
 
+def penalty_bench(V=32000, hist=512, shapes=((8, 1), (8, 5)), warmup=3, launches=50):
+    """sd_penalize_rows alone: [{items, rows_per_item, rows, us}] (fp32 rows with the bf16 rounding pending, as a bf16 head
+    leaves them) and the launches of one iteration of 8 streams at gamma GAMMA."""
+    from llmspeculativesampling_amd._lib import lib, check, SdPenalty, SdPenaltyItem
+    from llmspeculativesampling_amd.engine import _stream
+    rows_max = max(n * r for n, r in shapes)
+    x = torch.randn(rows_max, V, device="cuda")
+    y = torch.empty_like(x)
+    seqs = [torch.randint(0, V, (hist + 32,), dtype=torch.int32, device="cuda") for _ in range(max(n for n, _ in shapes))]
+    out = []
+    for n, r in shapes:
+        items = (SdPenaltyItem * n)()
+        for i, it in enumerate(items):
+            setattr(it, "in", x[i * r].data_ptr())
+            it.out, it.ld_in, it.ld_out, it.rows = y[i * r].data_ptr(), V, V, r
+            it.seq, it.hist0, it.prompt_len, it.pen = seqs[i].data_ptr(), hist, hist // 2, SdPenalty(*PENALTY)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for i in range(warmup + launches):
+            if i == warmup:
+                e0.record()
+            check(lib.sd_penalize_rows(items, n, V, 1, _stream()), "sd_penalize_rows")
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(dict(items=n, rows_per_item=r, rows=n * r, us=e0.elapsed_time(e1) * 1e3 / launches))
+    return dict(V=V, history=hist, launches=out, us_per_iteration_8_streams=GAMMA * out[0]["us"] + out[1]["us"])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--draft", default="llama-68m")
@@ -129,11 +165,17 @@ def main():
         work["mixed"] = (ps, [32 if i % 2 == 0 else 128 for i in range(32)])
     out = {"config": {k: v for k, v in vars(a).items() if k != "json_out"}, "dtype": "bfloat16", "slots": SLOTS, "gamma": GAMMA,
            "workloads": {}}
+    if "penalties" in a.workloads:
+        ps = [torch.from_numpy(np.random.default_rng(100 + i).integers(3, tcfg.vocab_size, size=(1, 128))).cuda() for i in range(8)]
+        work["penalties"] = (ps, [128] * 8)
+        out["penalize_rows"] = penalty_bench()
+        print(json.dumps({"penalize_rows": out["penalize_rows"]}), flush=True)
     if "copy" in a.workloads:
         out["copy_kv"] = copy_bench(tm)
         print(json.dumps({"copy_kv": out["copy_kv"]}), flush=True)
     for name, (prompts, budgets) in work.items():
         lens = [int(p.shape[1]) for p in prompts]
+        lens_b = budgets                                          # (the tokens a rep generates: every prompt its budget)
 
         def queue(seed0, **more):
             t = {}
@@ -179,7 +221,19 @@ def main():
             return outs, dict(iterations=iters, target_passes=passes, extra_passes=extra, mean_streams=float(np.mean(streams)),
                               calls=len(MIXED_CLASSES))
 
+        def requests(seed0, on):
+            t = {}
+            cols = [[PENALTY[j] if i in on else (1.0, 0.0, 0.0)[j] for i in range(len(prompts))] for j in range(3)]
+            pen = dict(repetition_penalty=cols[0], frequency_penalty=cols[1], presence_penalty=cols[2]) if on else {}
+            outs = speculative_sampling_queue_requests(prompts, dm, tm, -1, None, budgets, seeds=[seed0 + i for i in range(len(prompts))],
+                                                       slots=SLOTS, _timing=t, **pen, **kw)
+            return outs, dict(iterations=t["iterations"], target_passes=t["target_passes"], extra_passes=t["extra_passes"],
+                              mean_streams=float(np.mean([v[2] for v in t["verify"]])), penalised_prompts=len(on))
+
         arms = {"queue": queue, "batch": batch}
+        if name == "penalties":
+            arms = {"off": lambda seed0: requests(seed0, ()), "all": lambda seed0: requests(seed0, range(len(prompts))),
+                    "half": lambda seed0: requests(seed0, range(0, len(prompts), 2))}
         if name == "mixed":
             arms = {"mixed_queue": mixed_queue, "per_class_queues": per_class_queues}
         if name == "shared":
@@ -205,6 +259,12 @@ def main():
             res["classes"] = [dict(temperature=T, top_k=k, top_p=pp) for T, k, pp in MIXED_CLASSES]
             res["mixed_over_per_class_tokens_per_s"] = res["mixed_queue"]["tokens_per_s_median"] / \
                 res["per_class_queues"]["tokens_per_s_median"]
+        elif name == "penalties":
+            res["penalty"] = dict(zip(("repetition", "frequency", "presence"), PENALTY))
+            for arm in ("all", "half"):
+                res[f"{arm}_over_off_tokens_per_s"] = res[arm]["tokens_per_s_median"] / res["off"]["tokens_per_s_median"]
+                res[f"{arm}_ms_per_iteration_over_off"] = 1e3 * sum(lens_b) * (
+                    1 / res[arm]["tokens_per_s_median"] / res[arm]["iterations"] - 1 / res["off"]["tokens_per_s_median"] / res["off"]["iterations"])
         elif name == "shared":
             res["shared_over_plain_tokens_per_s"] = res[f"shared_prefix_{SHARED}"]["tokens_per_s_median"] / \
                 res["shared_prefix_0"]["tokens_per_s_median"]
