@@ -863,6 +863,82 @@ int sd_ar_batch_generate_penalties(sd_ar_stream *streams, int n_streams, const s
                                    void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream,
                                    const sd_logprob_block *logprobs, const sd_penalty_block *penalties);
 
+/* ---- Per-request logit bias, allowed-token mask and min_tokens: the request fields that restrict what may be sampled.  A
+ * logit row at position pos predicts token pos + 1; with P the stream's prompt length on entry, that token is output number
+ * j = pos + 1 - P.  y is the logit as the sampler reads it after the penalties above (for a neutral triple: the logit with the
+ * pending SD_NORM_ROUND_* rounding applied).  For a request with bias list B, allowed set A (NULL = every id) and min_tokens m:
+ *   1. t in B:       y = y + b_t      (one IEEE fp32 addition, no contraction; in an SD_NORM_DT_* mode the result is rounded
+ *                                      to that 16-bit type, as the penalty operations are; b_t is not rounded)
+ *   2. t not in A:   y = -inf         (also where y is NaN or +inf)
+ *   3. t == eos_token_id, eos_token_id >= 0, m > 0 and j < m:   y = -inf
+ * in that order, behind the penalties: penalties -> bias -> masks, so that sd_penalize_rows' definition stays what it is and
+ * the masks win over everything.  An id that is in no list keeps its bits.  (sampling.utils.apply_logit_edits is this text in
+ * torch; it composes after apply_penalties.)
+ * sd_logit_edit: bias_ids / bias_vals are two parallel device arrays of n_bias entries, 0 <= n_bias <= SD_EDIT_MAX_BIAS, ids
+ * strictly ascending (an id outside [0, V) is ignored; of duplicate ids one value wins, nothing is read or written out of
+ * bounds); allowed is a device array of (V + 31) / 32 words, bit t & 31 of word t >> 5 set = token t allowed - a banned id is
+ * a cleared bit of the same mask.  Neutral is {NULL, NULL, 0, NULL, 0}.
+ * sd_edit_rows is sd_penalize_rows with the edits: the same items, grid (one workgroup per row and window of 4096 ids),
+ * alignment freedom and `mode`, out of place, up to 16 items x 17 rows in ONE launch that applies penalties, bias and masks in
+ * one pass over each window; row r of an item has j = hist0 + r - prompt_len.  Any part of an item may be neutral; an item that
+ * is neutral throughout is rounded and copied.  The result is a pure function of the inputs.  Refused with SD_ERR_INVALID before
+ * any launch, naming the item: what sd_penalize_rows refuses, n_bias outside 0..SD_EDIT_MAX_BIAS, n_bias > 0 with a NULL
+ * array, min_tokens < 0.  (sd_penalize_rows keeps its own kernel.) */
+#define SD_EDIT_MAX_BIAS 1024
+typedef struct {
+    const int32_t *bias_ids;
+    const float *bias_vals;
+    int32_t n_bias;
+    const uint32_t *allowed;
+    int32_t min_tokens;
+} sd_logit_edit;
+typedef struct {
+    const float *in;
+    float *out;
+    long ld_in, ld_out;
+    int32_t rows;
+    const int32_t *seq;
+    int32_t hist0, prompt_len;
+    sd_penalty pen;
+    sd_logit_edit edit;
+    int32_t eos_token_id;
+} sd_logit_edit_item;
+int sd_edit_rows(const sd_logit_edit_item *items, int n_items, int V, int mode, void *stream);
+/* sd_logit_edit_block: what a loop needs to sample from edited rows; caller-owned.  rows / ld / max_rows: a slab sized as
+ * sd_penalty_block's; params[k] belongs to stream k - to prompt k in the queue, where a slot changes its edits when it changes
+ * hands.  The _edits entries take exactly what the _penalties entries take (logprobs and penalties may be NULL), plus the
+ * block; the EOS id is sampling->eos_token_id.  A NULL block, or one whose params are all neutral, is the _penalties entry
+ * itself, launch for launch.  Otherwise every pass - of a draft step, of the verify, of an autoregressive step - that holds at
+ * least one active stream that is penalised or edited gets ONE sd_edit_rows launch between the forward and the norm launch (at
+ * most one, whether the pass holds penalised streams, edited streams or both), over all its logit rows, one item per stream;
+ * it writes the edit block's slab, the penalty block's slab is not touched, and the pass follows the rules of a penalised pass:
+ * no tile maxima, rows through the norm workspace, a norm request that reads the slab with the pending rounding bits cleared.
+ * Joiner rows, accept / resample, the candidate lists, the Philox order and the log-probability launch are untouched:
+ * sd_token_logprobs keeps reading the raw rows.  Draft rows are edited like target rows, so the acceptance rate holds and the
+ * draft never proposes a token the target gives zero mass.  A request whose mask and EOS floor leave no id allowed gives a
+ * row of -inf, which the norm launch reports as it reports any such row.  Refused with SD_ERR_INVALID behind the entry's own
+ * refusals, before anything is launched, naming the index: a NULL rows or params, ld < V, max_rows too small, n_bias outside
+ * 0..SD_EDIT_MAX_BIAS, n_bias > 0 with a NULL array, min_tokens < 0. */
+typedef struct { float *rows; long ld; int32_t max_rows; const sd_logit_edit *params; } sd_logit_edit_block;
+int sd_spec_generate_edits(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling, const sd_spec_scratch *scratch,
+                           sd_seq_state *seq, uint64_t random_seed, const float *r_const, void *stream,
+                           const sd_logprob_block *logprobs, const sd_penalty_block *penalties, const sd_logit_edit_block *edits);
+int sd_spec_batch_generate_edits(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
+                                 uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
+                                 sd_lockstep_log *log, void *stream, const sd_row_sampling *stream_params,
+                                 const sd_logprob_block *logprobs, const sd_penalty_block *penalties,
+                                 const sd_logit_edit_block *edits);
+int sd_spec_queue_generate_edits(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
+                                 int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
+                                 const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log, int *passes_out,
+                                 void *stream, sd_session *donor_draft, sd_session *donor_target, int shared_rows,
+                                 const sd_row_sampling *prompt_params, const sd_logprob_block *logprobs,
+                                 const sd_penalty_block *penalties, const sd_logit_edit_block *edits);
+int sd_ar_batch_generate_edits(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
+                               void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream,
+                               const sd_logprob_block *logprobs, const sd_penalty_block *penalties,
+                               const sd_logit_edit_block *edits);
+
 /* ------------------------------------------------------------------------------------------
  * Tensor parallelism of one decoder over the GPUs of a node (BASELINE config 5: Llama-2-70b, TP = 8 over xGMI).
  * The reference is single-process: this is new capability behind the same call signatures.

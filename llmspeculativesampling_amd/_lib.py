@@ -149,6 +149,20 @@ class SdPenaltyBlock(C.Structure):
     _fields_ = [("rows", C.c_void_p), ("ld", C.c_long), ("max_rows", C.c_int32), ("params", C.POINTER(SdPenalty))]
 
 
+class SdLogitEdit(C.Structure):
+    _fields_ = [("bias_ids", C.c_void_p), ("bias_vals", C.c_void_p), ("n_bias", C.c_int32), ("allowed", C.c_void_p),
+                ("min_tokens", C.c_int32)]
+
+
+class SdLogitEditItem(C.Structure):
+    _fields_ = SdPenaltyItem._fields_ + [("edit", SdLogitEdit), ("eos_token_id", C.c_int32)]
+
+
+class SdLogitEditBlock(C.Structure):
+    _fields_ = [("rows", C.c_void_p), ("ld", C.c_long), ("max_rows", C.c_int32), ("params", C.POINTER(SdLogitEdit))]
+
+
+SD_EDIT_MAX_BIAS = 1024                                  # bias entries per request
 LOGPROB_SLICE, LOGPROB_STREAMS = 17, 16                  # sd_logprob_block: 16 streams x 17 floats, device and pinned host
 
 
@@ -196,7 +210,8 @@ C_STRUCTS = {"sd_accept_result": SdAcceptResult, "sd_norm_row": SdNormRow, "sd_r
              "sd_spec_stream": SdSpecStream, "sd_spec_scratch": SdSpecScratch, "sd_lockstep_log": SdLockstepLog, "sd_seq_state": SdSeqState,
              "sd_ar_log": SdArLog, "sd_batch_item": SdBatchItem,
              "sd_logprob_item": SdLogprobItem, "sd_logprob_block": SdLogprobBlock, "sd_penalty": SdPenalty,
-             "sd_penalty_item": SdPenaltyItem, "sd_penalty_block": SdPenaltyBlock, "sd_model_config": SdModelConfig,
+             "sd_penalty_item": SdPenaltyItem, "sd_penalty_block": SdPenaltyBlock, "sd_logit_edit": SdLogitEdit,
+             "sd_logit_edit_item": SdLogitEditItem, "sd_logit_edit_block": SdLogitEditBlock, "sd_model_config": SdModelConfig,
              "sd_gemm_route_info": SdGemmRouteInfo, "sd_model_weights": SdModelWeights}
 
 # every symbol include/specdec.h declares: (name, restype, argtypes)
@@ -298,6 +313,17 @@ SYMBOLS = [
                                               _P(SdLogprobBlock), _P(SdPenaltyBlock)]),
     ("sd_ar_batch_generate_penalties", _I, [_P(SdArStream), _I, _P(SdSampling), _P(SdHeadScratch), _VP, _VP, _VP, _P(SdArLog), _VP,
                                             _P(SdLogprobBlock), _P(SdPenaltyBlock)]),
+    ("sd_edit_rows", _I, [_P(SdLogitEditItem), _I, _I, _I, _VP]),
+    ("sd_spec_generate_edits", _I, [_P(SdSpecStream), _I, _P(SdSampling), _P(SdSpecScratch), _P(SdSeqState), _U64, _VP, _VP,
+                                    _P(SdLogprobBlock), _P(SdPenaltyBlock), _P(SdLogitEditBlock)]),
+    ("sd_spec_batch_generate_edits", _I, [_P(SdBatchStream), _I, _I, _P(SdSampling), _U64, _VP, _P(SdSpecScratch),
+                                          _P(SdLockstepLog), _VP, _P(SdRowSampling), _P(SdLogprobBlock), _P(SdPenaltyBlock),
+                                          _P(SdLogitEditBlock)]),
+    ("sd_spec_queue_generate_edits", _I, [_P(SdBatchStream), _I, _I, _P(SdQueuePrompt), _I, _I, _I, _P(SdSampling), _U64, _VP,
+                                          _P(SdSpecScratch), _P(SdLockstepLog), _VP, _VP, _VP, _VP, _I, _P(SdRowSampling),
+                                          _P(SdLogprobBlock), _P(SdPenaltyBlock), _P(SdLogitEditBlock)]),
+    ("sd_ar_batch_generate_edits", _I, [_P(SdArStream), _I, _P(SdSampling), _P(SdHeadScratch), _VP, _VP, _VP, _P(SdArLog), _VP,
+                                        _P(SdLogprobBlock), _P(SdPenaltyBlock), _P(SdLogitEditBlock)]),
     ("sd_batch_forward", _I, [C.POINTER(SdBatchItem), _I, _VP, _L, _VP]),
     ("sd_batch_prefill", _I, [C.POINTER(SdBatchItem), _I, _VP]),
     ("sd_tp_unique_id", _I, [_VP]),

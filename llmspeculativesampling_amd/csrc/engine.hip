@@ -20,6 +20,7 @@
 #include "kv_copy_kernels.h"
 #include "logprob_kernels.h"
 #include "penalty_kernels.h"
+#include "logit_edit_kernels.h"
 #include "sampler_host.h"
 
 static thread_local char g_err[512] = "";

@@ -230,15 +230,103 @@ static int check_penalty_block(const char *who, const char *what, const sd_penal
     if (!any) *pb = nullptr;
     return SD_OK;
 }
-// The item of one stream's `rows` logit rows, the first at position `pos`: packed from row `r0` of the pass's raw rows `src`
-// and of the block's slab
-static sd_penalty_item penalty_item(const sd_penalty_block &pb, const HeadOut &src, int r0, int rows, const int32_t *seq, int pos,
-                                    int prompt_len, const sd_penalty &pen) {
-    return sd_penalty_item{src.logits + (size_t)r0 * src.ld, pb.rows + (size_t)r0 * pb.ld, src.ld, pb.ld, rows, seq, pos + 1, prompt_len, pen};
+
+// ---- per-request logit bias, allowed mask and min_tokens (include/specdec.h has the definition and the loops' contract) ----
+static bool edit_neutral(const sd_logit_edit &e) { return e.n_bias == 0 && !e.allowed && e.min_tokens == 0; }
+static int check_edit(const char *who, const char *what, int i, const sd_logit_edit &e) {
+    SD_REQUIRE(e.n_bias >= 0 && e.n_bias <= SD_EDIT_MAX_BIAS, "%s: %s %d: n_bias %d outside 0..%d", who, what, i, e.n_bias, SD_EDIT_MAX_BIAS);
+    SD_REQUIRE(e.n_bias == 0 || (e.bias_ids && e.bias_vals), "%s: %s %d: %d bias entries and a null array", who, what, i, e.n_bias);
+    SD_REQUIRE(e.min_tokens >= 0, "%s: %s %d: min_tokens %d < 0", who, what, i, e.min_tokens);
+    return SD_OK;
 }
-// The norm request of a penalised pass reads the block's slab: already rounded, no tile maxima
-static void norm_from_penalised(NormRequest &nr, const sd_penalty_block &pb) {
-    nr.logits = pb.rows; nr.ld_in = pb.ld; nr.mode &= ~3; nr.tile_max = nullptr;
+
+extern "C" int sd_edit_rows(const sd_logit_edit_item *items, int n_items, int V, int mode, void *stream) {
+    SD_REQUIRE(items, "sd_edit_rows: null argument");
+    SD_REQUIRE(n_items >= 1 && n_items <= PEN_MAX_ITEMS, "sd_edit_rows: n_items %d outside 1..%d", n_items, PEN_MAX_ITEMS);
+    SD_REQUIRE(V >= 1 && V <= 65536 && (mode & 3) != 3, "sd_edit_rows: V %d outside 1..65536, or both rounding bits (mode %#x)", V, mode);
+    EditTab e = {};
+    PenaltyTab &t = e.pen;
+    int max_rows = 0;
+    for (int i = 0; i < n_items; ++i) {
+        const sd_logit_edit_item &it = items[i];
+        SD_REQUIRE(it.in && it.out && it.seq, "sd_edit_rows: item %d: null argument", i);
+        SD_REQUIRE(it.rows >= 1 && it.rows <= PEN_MAX_ROWS, "sd_edit_rows: item %d: rows %d outside 1..%d", i, it.rows, PEN_MAX_ROWS);
+        SD_REQUIRE(it.ld_in >= V && it.ld_out >= V, "sd_edit_rows: item %d: ld %ld / %ld < V %d", i, it.ld_in, it.ld_out, V);
+        SD_REQUIRE(it.hist0 >= 1 && it.prompt_len >= 0, "sd_edit_rows: item %d: hist0 %d < 1 or prompt_len %d < 0", i, it.hist0,
+                   it.prompt_len);
+        if (int rc = check_penalty("sd_edit_rows", "item", i, it.pen); rc != SD_OK) return rc;
+        if (int rc = check_edit("sd_edit_rows", "item", i, it.edit); rc != SD_OK) return rc;
+        t.in[i] = it.in; t.out[i] = it.out; t.seq[i] = it.seq; t.ld_in[i] = it.ld_in; t.ld_out[i] = it.ld_out;
+        t.rows[i] = it.rows; t.hist0[i] = it.hist0; t.prompt_len[i] = it.prompt_len;
+        t.repetition[i] = it.pen.repetition; t.frequency[i] = it.pen.frequency; t.presence[i] = it.pen.presence;
+        e.bias_ids[i] = it.edit.bias_ids; e.bias_vals[i] = it.edit.bias_vals; e.n_bias[i] = it.edit.n_bias;
+        e.allowed[i] = it.edit.allowed; e.min_tokens[i] = it.edit.min_tokens; e.eos[i] = it.eos_token_id;
+        max_rows = std::max(max_rows, (int)it.rows);
+    }
+    return launch_edit_rows(e, n_items, max_rows, V, mode, (hipStream_t)stream);
+}
+
+// what the _edits entries refuse in their block, as check_penalty_block does; *eb becomes NULL when every record is neutral
+static int check_edit_block(const char *who, const char *what, const sd_logit_edit_block **eb, int n, int V, int need_rows) {
+    const sd_logit_edit_block *b = *eb;
+    SD_REQUIRE(b->rows && b->params, "%s: edits: null pointer", who);
+    SD_REQUIRE(b->ld >= V, "%s: edits: ld %ld < V %d", who, b->ld, V);
+    SD_REQUIRE(b->max_rows >= need_rows, "%s: edits: a slab of %d rows, the largest pass has %d", who, b->max_rows, need_rows);
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+        if (int rc = check_edit(who, what, i, b->params[i]); rc != SD_OK) return rc;
+        any = any || !edit_neutral(b->params[i]);
+    }
+    if (!any) *eb = nullptr;
+    return SD_OK;
+}
+
+// What a loop edits its logit rows by: the penalty block, the edit block or both, as ONE slab and two parameter tables, of
+// which either may be absent (NULL: neutral for everyone).  With an edit table the pass's launch is sd_edit_rows into the
+// edit block's slab, without one sd_penalize_rows into the penalty block's: the _penalties entries keep their launches.
+struct RowEdits {
+    float *rows; long ld; int max_rows;
+    const sd_penalty *pen;
+    const sd_logit_edit *edit;
+    int eos;
+    bool edited(int k) const { return (pen && !penalty_neutral(pen[k])) || (edit && !edit_neutral(edit[k])); }
+};
+// The entries' two blocks, checked (behind the entry's own refusals) and folded into *re: *out is NULL when nothing is left
+// to edit, and the call is then the entry without blocks.
+static int resolve_row_edits(const char *who, const char *what, const sd_penalty_block *pb, const sd_logit_edit_block *eb, int n,
+                             int V, int need_rows, int eos, RowEdits *re, const RowEdits **out) {
+    if (pb)
+        if (int rc = check_penalty_block(who, what, &pb, n, V, need_rows); rc != SD_OK) return rc;
+    if (eb)
+        if (int rc = check_edit_block(who, what, &eb, n, V, need_rows); rc != SD_OK) return rc;
+    *out = nullptr;
+    if (!pb && !eb) return SD_OK;
+    *re = eb ? RowEdits{eb->rows, eb->ld, eb->max_rows, pb ? pb->params : nullptr, eb->params, eos}
+             : RowEdits{pb->rows, pb->ld, pb->max_rows, pb->params, nullptr, eos};
+    *out = re;
+    return SD_OK;
+}
+// The item of stream / prompt `k`'s `rows` logit rows, the first at position `pos`: packed from row `r0` of the pass's raw
+// rows `src` and of the slab
+static sd_logit_edit_item edit_item(const RowEdits &re, int k, const HeadOut &src, int r0, int rows, const int32_t *seq, int pos,
+                                    int prompt_len) {
+    return sd_logit_edit_item{src.logits + (size_t)r0 * src.ld, re.rows + (size_t)r0 * re.ld, src.ld, re.ld, rows, seq, pos + 1, prompt_len,
+                              re.pen ? re.pen[k] : sd_penalty{1.0f, 0.0f, 0.0f},
+                              re.edit ? re.edit[k] : sd_logit_edit{nullptr, nullptr, 0, nullptr, 0}, re.eos};
+}
+// The one launch of an edited pass over its n items
+static int edit_rows(const RowEdits &re, const sd_logit_edit_item *items, int n, int V, int mode, void *stream) {
+    if (re.edit) return sd_edit_rows(items, n, V, mode, stream);
+    sd_penalty_item pi[PEN_MAX_ITEMS];
+    for (int j = 0; j < n && j < PEN_MAX_ITEMS; ++j) {
+        const sd_logit_edit_item &it = items[j];
+        pi[j] = sd_penalty_item{it.in, it.out, it.ld_in, it.ld_out, it.rows, it.seq, it.hist0, it.prompt_len, it.pen};
+    }
+    return sd_penalize_rows(pi, n, V, mode, stream);
+}
+// The norm request of an edited pass reads the slab: already rounded, no tile maxima
+static void norm_from_edited(NormRequest &nr, const RowEdits &re) {
+    nr.logits = re.rows; nr.ld_in = re.ld; nr.mode &= ~3; nr.tile_max = nullptr;
 }
 
 // ---- one whole speculative iteration, enqueued natively ---------------------------------------
@@ -248,14 +336,14 @@ static void norm_from_penalised(NormRequest &nr, const sd_penalty_block &pb) {
 // the stream once per iteration.  `timed`: the draft phase is ev.t[0] .. t[1], the verify phase ev.t[2] .. t[3].
 static int spec_iteration(const sd_spec_stream &dv, int g, const sd_sampling &sm, const sd_spec_scratch &sc, const Draws &d, int L,
                           int draft_len, int target_len, const float *r_const, const LoopEvents &ev, bool timed, void *stream,
-                          const sd_logprob_block *lp, const sd_penalty_block *pb, int prompt_len) {
+                          const sd_logprob_block *lp, const RowEdits *re, int prompt_len) {
     SD_REQUIRE(L >= 1 && draft_len >= 0 && draft_len < L && target_len >= 0 && target_len < L + g,
                "sd_spec_generate: L=%d draft_len=%d target_len=%d", L, draft_len, target_len);
     SD_REQUIRE(!lp || target_len <= L - 1, "sd_spec_generate_logprobs: target_len %d of %d tokens leaves fewer than gamma + 1 target rows",
                target_len, L);
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    const bool tiles_ok = !pb && head_tiles_ok(sm.top_k, sm.temperature, sm.V, sm.ld);   // (a penalised pass takes no tile maxima)
+    const bool tiles_ok = !re && head_tiles_ok(sm.top_k, sm.temperature, sm.V, sm.ld);   // (an edited pass takes no tile maxima)
     int *const err = dv.err_words;     // [0..gamma) norm err of draft rows, [gamma..2gamma) sample err, [2gamma..3gamma+1) target rows
     HeadReq rq = {};
     HeadOut ho = {};
@@ -270,10 +358,10 @@ static int spec_iteration(const sd_spec_stream &dv, int g, const sd_sampling &sm
             return rc;
         draft_len = upto;
         NormRequest nr = norm_request(sm, sc.draft.norm_mode, ho);
-        if (pb) {                                                 // the row at position upto - 1, edited out of place
-            const sd_penalty_item it = penalty_item(*pb, ho, 0, 1, dv.seq, upto - 1, prompt_len, pb->params[0]);
-            if ((rc = sd_penalize_rows(&it, 1, sm.V, nr.mode, stream)) != SD_OK) return rc;
-            norm_from_penalised(nr, *pb);
+        if (re) {                                                 // the row at position upto - 1, edited out of place
+            const sd_logit_edit_item it = edit_item(*re, 0, ho, 0, 1, dv.seq, upto - 1, prompt_len);
+            if ((rc = edit_rows(*re, &it, 1, sm.V, nr.mode, stream)) != SD_OK) return rc;
+            norm_from_edited(nr, *re);
         }
         nr.rows = 1; nr.probs_out = q_row; nr.ld_out = sm.ld; nr.err = err + i;
         nr.seed = d.seed_draft; nr.draw = d.draft0 + (uint64_t)i; nr.tok_out = dv.seq + upto; nr.samp_err = err + g + i;
@@ -294,10 +382,10 @@ static int spec_iteration(const sd_spec_stream &dv, int g, const sd_sampling &sm
         if ((rc = feed_rows(dv.target, dv.seq, target_len, upto, rows, sc.target.logits, sc.target.ld_logits, &rq, &ho, stream)) != SD_OK)
             return rc;
         NormRequest nr = norm_request(sm, sc.target.norm_mode, ho);
-        if (pb) {
-            const sd_penalty_item it = penalty_item(*pb, ho, 0, rows, dv.seq, upto - rows, prompt_len, pb->params[0]);
-            if ((rc = sd_penalize_rows(&it, 1, sm.V, nr.mode, stream)) != SD_OK) return rc;
-            norm_from_penalised(nr, *pb);
+        if (re) {
+            const sd_logit_edit_item it = edit_item(*re, 0, ho, 0, rows, dv.seq, upto - rows, prompt_len);
+            if ((rc = edit_rows(*re, &it, 1, sm.V, nr.mode, stream)) != SD_OK) return rc;
+            norm_from_edited(nr, *re);
         }
         nr.rows = rows; nr.probs_out = p_rows; nr.ld_out = sm.ld; nr.err = err + 2 * g;
         nr.workspace = sc.norm_workspace; nr.lists = lists;
@@ -330,7 +418,7 @@ static int spec_iteration(const sd_spec_stream &dv, int g, const sd_sampling &sm
 // The device-RNG loop without the interpreter between iterations (reference speculative_sampling.py:1934-2046).
 static int spec_generate(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling, const sd_spec_scratch *scratch,
                          sd_seq_state *s, uint64_t random_seed, const float *r_const, void *stream, const sd_logprob_block *lp,
-                         const sd_penalty_block *pb = nullptr) {
+                         const sd_penalty_block *pb = nullptr, const sd_logit_edit_block *eb = nullptr) {
     SD_REQUIRE(dev && sampling && scratch && s && dev->draft && dev->target && dev->seq && dev->q_hist && dev->p_hist &&
                dev->err_words && dev->res_dev && dev->res_host && s->host_seq && scratch->draft.logits && scratch->target.logits,
                "sd_spec_generate: null argument");
@@ -346,8 +434,11 @@ static int spec_generate(const sd_spec_stream *dev, int gamma, const sd_sampling
                dev->target->m->cfg.vocab);
     if (lp)
         if (int rc = check_logprob_block("sd_spec_generate_logprobs", lp, 1); rc != SD_OK) return rc;
-    if (pb)
-        if (int rc = check_penalty_block("sd_spec_generate_penalties", "stream", &pb, 1, sm.V, gamma + 1); rc != SD_OK) return rc;
+    RowEdits re_block;
+    const RowEdits *re = nullptr;
+    if (int rc = resolve_row_edits(eb ? "sd_spec_generate_edits" : "sd_spec_generate_penalties", "stream", pb, eb, 1, sm.V, gamma + 1,
+                                   sm.eos_token_id, &re_block, &re); rc != SD_OK)
+        return rc;
     refresh_env();
     const int g = gamma, L0 = s->len;
     const bool timed = s->draft_ms_out || s->target_ms_out;
@@ -360,7 +451,7 @@ static int spec_generate(const sd_spec_stream *dev, int gamma, const sd_sampling
         const int L = s->len, iters = s->n_iters;
         const Draws d = next_draws(s->seed, s->draw, g, random_seed);
         s->seed = d.seed; s->draw = d.draw;
-        if ((rc = spec_iteration(*dev, g, sm, *scratch, d, L, s->draft_len, s->target_len, r_const, ev, timed, stream, lp, pb, L0)) != SD_OK) break;
+        if ((rc = spec_iteration(*dev, g, sm, *scratch, d, L, s->draft_len, s->target_len, r_const, ev, timed, stream, lp, re, L0)) != SD_OK) break;
         SD_LOOP_HIP(hipEventRecord(ev.done, (hipStream_t)stream));
         if ((rc = poll_event(ev.done, "sd_spec_generate")) != SD_OK) break;
         const sd_accept_result r = *dev->res_host;
@@ -416,6 +507,12 @@ extern "C" int sd_spec_generate_penalties(const sd_spec_stream *dev, int gamma, 
                                           const sd_spec_scratch *scratch, sd_seq_state *s, uint64_t random_seed, const float *r_const,
                                           void *stream, const sd_logprob_block *logprobs, const sd_penalty_block *penalties) {
     return spec_generate(dev, gamma, sampling, scratch, s, random_seed, r_const, stream, logprobs, penalties);
+}
+extern "C" int sd_spec_generate_edits(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling, const sd_spec_scratch *scratch,
+                                      sd_seq_state *s, uint64_t random_seed, const float *r_const, void *stream,
+                                      const sd_logprob_block *logprobs, const sd_penalty_block *penalties,
+                                      const sd_logit_edit_block *edits) {
+    return spec_generate(dev, gamma, sampling, scratch, s, random_seed, r_const, stream, logprobs, penalties, edits);
 }
 
 // ---- the prompt queue of the lock-step loop ---------------------------------------------------------------------
@@ -575,7 +672,7 @@ static int queue_idle_prefill(PromptQueue &q, sd_batch_stream *slots, const std:
 // params (or NULL: sm's triple for everyone): per-request sampling parameters, indexed by stream - with a queue, by prompt.
 static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_streams, PromptQueue *q, int gamma, const sd_sampling &sm,
                          const sd_row_sampling *params, uint64_t random_seed, const float *r_const, const sd_spec_scratch &sc, sd_lockstep_log *log, void *stream,
-                         const sd_logprob_block *lp, const sd_penalty_block *pb) {
+                         const sd_logprob_block *lp, const RowEdits *re) {
     hipStream_t st = (hipStream_t)stream;
     const int g = gamma, n_err = 3 * g + 1;
     // rows per target pass (every verify row is a logit row: sd_model_max_pass_rows, 64 for a model whose lm_head or
@@ -630,31 +727,32 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
     auto params_of = [&](const sd_batch_stream &s) -> const sd_row_sampling & { return params[q ? q->occ[&s - streams] : &s - streams]; };
     int L0[SD_MAX_STREAMS];                                       // (logprobs, penalties without a queue) the streams' lengths on entry
     std::vector<sd_logprob_item> litems;
-    // penalties: the triple and the prompt length of the request a stream runs, and the launch over a pass's logit rows - m
-    // streams from act[a0], stream j's n_rows(j) rows packed in stream order in `src`, the first at position pos0(j) -
-    // ahead of the norm launch `nr`, which then reads the block's slab.  A pass without a penalised stream is left alone.
-    auto pen_of = [&](const sd_batch_stream &s) -> const sd_penalty & { return pb->params[q ? q->occ[&s - streams] : &s - streams]; };
-    auto pass_penalised = [&](int a0, int m) {
+    // penalties and edits: the request a stream runs (its index into the blocks' tables) and its prompt length, and the launch
+    // over a pass's logit rows - m streams from act[a0], stream j's n_rows(j) rows packed in stream order in `src`, the first
+    // at position pos0(j) - ahead of the norm launch `nr`, which then reads the slab.  A pass without a penalised or edited
+    // stream is left alone.
+    auto request_of = [&](const sd_batch_stream &s) { return q ? q->occ[&s - streams] : (int)(&s - streams); };
+    auto pass_edited = [&](int a0, int m) {
         bool any = false;
-        for (int j = 0; pb && j < m; ++j) any = any || !penalty_neutral(pen_of(*act[a0 + j]));
+        for (int j = 0; re && j < m; ++j) any = any || re->edited(request_of(*act[a0 + j]));
         return any;
     };
-    sd_penalty_item pitems[SD_MAX_STREAMS];
-    auto penalise_pass = [&](int a0, int m, const HeadOut &src, auto n_rows, auto pos0, NormRequest &nr) -> int {
+    sd_logit_edit_item pitems[SD_MAX_STREAMS];
+    auto edit_pass = [&](int a0, int m, const HeadOut &src, auto n_rows, auto pos0, NormRequest &nr) -> int {
         int r0 = 0;
         for (int j = 0; j < m; ++j) {
             const sd_batch_stream &s = *act[a0 + j];
             const int slot = (int)(&s - streams), nr_j = n_rows(j);
-            if (nr_j > PEN_MAX_ROWS || r0 + nr_j > pb->max_rows) {
-                sd_set_error("%s: penalties: stream %d has %d logit rows in a pass of more than %d (a launch takes %d per stream, the "
-                             "slab holds %d)", who, slot, nr_j, r0, PEN_MAX_ROWS, pb->max_rows);
+            if (nr_j > PEN_MAX_ROWS || r0 + nr_j > re->max_rows) {
+                sd_set_error("%s: %s: stream %d has %d logit rows in a pass of more than %d (a launch takes %d per stream, the "
+                             "slab holds %d)", who, re->edit ? "edits" : "penalties", slot, nr_j, r0, PEN_MAX_ROWS, re->max_rows);
                 return SD_ERR_INVALID;
             }
-            pitems[j] = penalty_item(*pb, src, r0, nr_j, s.seq, pos0(j), q ? q->prompts[q->occ[slot]].L : L0[slot], pen_of(s));
+            pitems[j] = edit_item(*re, request_of(s), src, r0, nr_j, s.seq, pos0(j), q ? q->prompts[q->occ[slot]].L : L0[slot]);
             r0 += nr_j;
         }
-        if (int prc = sd_penalize_rows(pitems, m, sm.V, nr.mode, stream); prc != SD_OK) return prc;
-        norm_from_penalised(nr, *pb);
+        if (int prc = edit_rows(*re, pitems, m, sm.V, nr.mode, stream); prc != SD_OK) return prc;
+        norm_from_edited(nr, *re);
         return SD_OK;
     };
     for (int i = 0; i < n_streams; ++i) {
@@ -707,7 +805,7 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
                         pass_tiles = pass_tiles && head_tiles_ok(prows[j].top_k, prows[j].temperature, sm.V, sm.ld);
                     }
                 }
-                const bool pen_pass = pass_penalised(a0, m);      // (its rows take no tile maxima)
+                const bool pen_pass = pass_edited(a0, m);         // (its rows take no tile maxima)
                 pass_tiles = pass_tiles && !pen_pass;
                 for (int j = 0; j < m; ++j) {
                     sd_batch_stream &s = *act[a0 + j];
@@ -727,7 +825,7 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
                 if (m == 0) continue;                             // (joiner rows only)
                 const HeadOut src = fused_tail ? ho : scratch_rows(sc.draft);
                 NormRequest nr = norm_request(sm, sc.draft.norm_mode, src);
-                if (pen_pass && (rc = penalise_pass(a0, m, src, [](int) { return 1; }, [&](int j) { return Ls[a0 + j] + i - 1; }, nr)) != SD_OK)
+                if (pen_pass && (rc = edit_pass(a0, m, src, [](int) { return 1; }, [&](int j) { return Ls[a0 + j] + i - 1; }, nr)) != SD_OK)
                     break;
                 nr.rows = m; nr.workspace = sc.norm_workspace; nr.row_params = params ? prows.data() : nullptr;
                 rc = sd_norm_batch_tiles(nr, rows.data(), 1, stream);
@@ -775,8 +873,8 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
             // one pass holds every stream: the rows' candidate lists (behind the CandRows of the workspace) serve the
             // residual / bonus sample below
             NormRequest nr = norm_request(sm, sc.target.norm_mode, scratch_rows(sc.target));
-            if (pass_penalised(a0, m) && (rc = penalise_pass(a0, m, scratch_rows(sc.target), [&](int j) { return items[j].n_new; },
-                                                             [&](int j) { return items[j].pos0; }, nr)) != SD_OK)
+            if (pass_edited(a0, m) && (rc = edit_pass(a0, m, scratch_rows(sc.target), [&](int j) { return items[j].n_new; },
+                                                      [&](int j) { return items[j].pos0; }, nr)) != SD_OK)
                 break;
             nr.rows = (int)rows.size(); nr.workspace = sc.norm_workspace; nr.lists = lists_on ? list_base : nullptr;
             nr.row_params = params ? prows.data() : nullptr;
@@ -884,7 +982,7 @@ static int lockstep_penalty_rows(const sd_batch_stream *streams, int n_streams, 
 static int batch_generate(const char *who, sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
                           const sd_row_sampling *params, uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
                           sd_lockstep_log *log, void *stream, const sd_logprob_block *lp = nullptr,
-                          const sd_penalty_block *pb = nullptr) {
+                          const sd_penalty_block *pb = nullptr, const sd_logit_edit_block *eb = nullptr) {
     SD_REQUIRE(streams && n_streams >= 1 && n_streams <= 16 && gamma >= 1 && gamma <= 16 && sampling && scratch && log &&
                scratch->draft.logits && scratch->target.logits, "%s: bad arguments", who);
     SD_REQUIRE(!random_seed || r_const, "%s: random_seed needs its uniform (r_const)", who);
@@ -893,11 +991,13 @@ static int batch_generate(const char *who, sd_batch_stream *streams, int n_strea
         if (int rc = check_row_params(who, "stream", params, n_streams); rc != SD_OK) return rc;
     if (lp)
         if (int rc = check_logprob_block(who, lp, n_streams); rc != SD_OK) return rc;
-    if (pb)
-        if (int rc = check_penalty_block(who, "stream", &pb, n_streams, sampling->V, lockstep_penalty_rows(streams, n_streams, gamma, *scratch));
-            rc != SD_OK)
+    RowEdits re_block;
+    const RowEdits *re = nullptr;
+    if (pb || eb)
+        if (int rc = resolve_row_edits(who, "stream", pb, eb, n_streams, sampling->V, lockstep_penalty_rows(streams, n_streams, gamma, *scratch),
+                                       sampling->eos_token_id, &re_block, &re); rc != SD_OK)
             return rc;
-    return lockstep_loop(who, streams, n_streams, nullptr, gamma, *sampling, params, random_seed, r_const, *scratch, log, stream, lp, pb);
+    return lockstep_loop(who, streams, n_streams, nullptr, gamma, *sampling, params, random_seed, r_const, *scratch, log, stream, lp, re);
 }
 
 extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
@@ -921,7 +1021,8 @@ static int queue_generate(const char *who, int n_passes_out, sd_session *donor_d
                           sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
                           int prefill_chunk, int gamma, const sd_sampling *sampling, const sd_row_sampling *params,
                           uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log,
-                          int *passes_out, void *stream, const sd_logprob_block *lp = nullptr, const sd_penalty_block *pb = nullptr) {
+                          int *passes_out, void *stream, const sd_logprob_block *lp = nullptr, const sd_penalty_block *pb = nullptr,
+                          const sd_logit_edit_block *eb = nullptr) {
     SD_REQUIRE(n_slots >= 1 && n_slots <= 16, "%s: n_slots %d outside 1..16", who, n_slots);
     SD_REQUIRE(gamma >= 1 && gamma <= 16, "%s: gamma %d outside 1..16", who, gamma);
     SD_REQUIRE(n_prompts >= 1 && prefill_chunk >= 0, "%s: n_prompts %d, prefill_chunk %d", who, n_prompts, prefill_chunk);
@@ -964,11 +1065,13 @@ static int queue_generate(const char *who, int n_passes_out, sd_session *donor_d
     q.donor_draft = donor_draft; q.donor_target = donor_target; q.shared_rows = shared_rows;
     if (lp)
         if (int rc = check_logprob_block(who, lp, n_prompts); rc != SD_OK) return rc;
-    if (pb)
-        if (int rc = check_penalty_block(who, "prompt", &pb, n_prompts, sampling->V, lockstep_penalty_rows(slots, n_slots, gamma, *scratch));
-            rc != SD_OK)
+    RowEdits re_block;
+    const RowEdits *re = nullptr;
+    if (pb || eb)
+        if (int rc = resolve_row_edits(who, "prompt", pb, eb, n_prompts, sampling->V, lockstep_penalty_rows(slots, n_slots, gamma, *scratch),
+                                       sampling->eos_token_id, &re_block, &re); rc != SD_OK)
             return rc;
-    const int rc = lockstep_loop(who, slots, n_slots, &q, gamma, *sampling, params, random_seed, r_const, *scratch, log, stream, lp, pb);
+    const int rc = lockstep_loop(who, slots, n_slots, &q, gamma, *sampling, params, random_seed, r_const, *scratch, log, stream, lp, re);
     if (passes_out) {
         const int v[6] = {q.target_passes, q.draft_passes, q.extra_passes, q.prefill_passes, q.prompt_rows, q.copied_rows};
         for (int i = 0; i < n_passes_out; ++i) passes_out[i] = v[i];
@@ -1057,6 +1160,35 @@ extern "C" int sd_spec_queue_generate_penalties(sd_batch_stream *slots, int n_sl
     return queue_generate("sd_spec_queue_generate_penalties", 6, donor_draft, donor_target, shared_rows, slots, n_slots, slot_cap, prompts,
                           n_prompts, prefill_chunk, gamma, sampling, prompt_params, random_seed, r_const, scratch, log, passes_out,
                           stream, logprobs, penalties);
+}
+
+// ... and with per-request logit edits: the _penalties entries' arguments (logprobs and penalties may be NULL) plus the block
+// (NULL: those entries)
+extern "C" int sd_spec_batch_generate_edits(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
+                                            uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
+                                            sd_lockstep_log *log, void *stream, const sd_row_sampling *stream_params,
+                                            const sd_logprob_block *logprobs, const sd_penalty_block *penalties,
+                                            const sd_logit_edit_block *edits) {
+    if (!edits)
+        return sd_spec_batch_generate_penalties(streams, n_streams, gamma, sampling, random_seed, r_const, scratch, log, stream,
+                                                stream_params, logprobs, penalties);
+    return batch_generate("sd_spec_batch_generate_edits", streams, n_streams, gamma, sampling, stream_params, random_seed, r_const,
+                          scratch, log, stream, logprobs, penalties, edits);
+}
+
+extern "C" int sd_spec_queue_generate_edits(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
+                                            int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
+                                            const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log,
+                                            int *passes_out, void *stream, sd_session *donor_draft, sd_session *donor_target,
+                                            int shared_rows, const sd_row_sampling *prompt_params, const sd_logprob_block *logprobs,
+                                            const sd_penalty_block *penalties, const sd_logit_edit_block *edits) {
+    if (!edits)
+        return sd_spec_queue_generate_penalties(slots, n_slots, slot_cap, prompts, n_prompts, prefill_chunk, gamma, sampling,
+                                                random_seed, r_const, scratch, log, passes_out, stream, donor_draft, donor_target,
+                                                shared_rows, prompt_params, logprobs, penalties);
+    return queue_generate("sd_spec_queue_generate_edits", 6, donor_draft, donor_target, shared_rows, slots, n_slots, slot_cap, prompts,
+                          n_prompts, prefill_chunk, gamma, sampling, prompt_params, random_seed, r_const, scratch, log, passes_out,
+                          stream, logprobs, penalties, edits);
 }
 
 // ---- the width-w loop of sampling/multi.py in native code (reference speculative_sampling.py:1379-1716, strategy "iid")
@@ -1302,7 +1434,8 @@ extern "C" size_t sd_ar_block_bytes(int n_streams) {
 
 static int ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
                              void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream,
-                             const sd_logprob_block *lp, const sd_penalty_block *pb = nullptr) {
+                             const sd_logprob_block *lp, const sd_penalty_block *pb = nullptr,
+                             const sd_logit_edit_block *eb = nullptr) {
     SD_REQUIRE(n_streams >= 1 && n_streams <= 16, "sd_ar_batch_generate: n_streams %d outside 1..16", n_streams);
     SD_REQUIRE(streams && sampling && head && log && head->logits && dev_block && host_block, "sd_ar_batch_generate: null argument");
     const sd_sampling &sm = *sampling;
@@ -1322,8 +1455,11 @@ static int ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_samp
                streams[0].session->max_pass_rows);
     if (lp)
         if (int rc = check_logprob_block("sd_ar_batch_generate_logprobs", lp, n_streams); rc != SD_OK) return rc;
-    if (pb)
-        if (int rc = check_penalty_block("sd_ar_batch_generate_penalties", "stream", &pb, n_streams, sm.V, n_streams); rc != SD_OK) return rc;
+    RowEdits re_block;
+    const RowEdits *re = nullptr;
+    if (int rc = resolve_row_edits(eb ? "sd_ar_batch_generate_edits" : "sd_ar_batch_generate_penalties", "stream", pb, eb, n_streams, sm.V,
+                                   n_streams, sm.eos_token_id, &re_block, &re); rc != SD_OK)
+        return rc;
     hipStream_t st = (hipStream_t)stream;
     const bool timed = log->step_ms_out != nullptr;
     LoopEvents ev(timed ? 2 : 0, "sd_ar_batch_generate");
@@ -1352,8 +1488,8 @@ static int ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_samp
         HeadReq rq = {};
         HeadOut ho = {};
         rq.raw = true;                                            // the lock-step draft step's sampler feed (see there)
-        bool pen_step = false;                                    // a step with a penalised stream takes no tile maxima
-        for (int j = 0; pb && j < n; ++j) pen_step = pen_step || !penalty_neutral(pb->params[act[j]]);
+        bool pen_step = false;                                    // a step with a penalised or edited stream takes no tile maxima
+        for (int j = 0; re && j < n; ++j) pen_step = pen_step || re->edited(act[j]);
         rq.zero_n = tiles_ok && !pen_step ? n : 0;
         for (int j = 0; j < n; ++j) {
             sd_ar_stream &s = streams[act[j]];
@@ -1370,13 +1506,13 @@ static int ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_samp
         if (rc != SD_OK) break;
         NormRequest nr = norm_request(sm, head->norm_mode, ho);
         if (pen_step) {                                           // stream act[j]'s one row, at position len - 1
-            sd_penalty_item pi[16];
+            sd_logit_edit_item pi[16];
             for (int j = 0; j < n; ++j) {
                 const sd_ar_stream &s = streams[act[j]];
-                pi[j] = penalty_item(*pb, ho, j, 1, s.seq, s.len - 1, L0[act[j]], pb->params[act[j]]);
+                pi[j] = edit_item(*re, act[j], ho, j, 1, s.seq, s.len - 1, L0[act[j]]);
             }
-            if ((rc = sd_penalize_rows(pi, n, sm.V, nr.mode, stream)) != SD_OK) break;
-            norm_from_penalised(nr, *pb);
+            if ((rc = edit_rows(*re, pi, n, sm.V, nr.mode, stream)) != SD_OK) break;
+            norm_from_edited(nr, *re);
         }
         nr.rows = n; nr.workspace = norm_workspace;
         if ((rc = sd_norm_batch_tiles(nr, rows.data(), 1, stream)) != SD_OK) break;
@@ -1434,4 +1570,11 @@ extern "C" int sd_ar_batch_generate_penalties(sd_ar_stream *streams, int n_strea
                                               sd_ar_log *log, void *stream, const sd_logprob_block *logprobs,
                                               const sd_penalty_block *penalties) {
     return ar_batch_generate(streams, n_streams, sampling, head, norm_workspace, dev_block, host_block, log, stream, logprobs, penalties);
+}
+extern "C" int sd_ar_batch_generate_edits(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
+                                          void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream,
+                                          const sd_logprob_block *logprobs, const sd_penalty_block *penalties,
+                                          const sd_logit_edit_block *edits) {
+    return ar_batch_generate(streams, n_streams, sampling, head, norm_workspace, dev_block, host_block, log, stream, logprobs, penalties,
+                             edits);
 }

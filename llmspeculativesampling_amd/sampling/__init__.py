@@ -7,7 +7,8 @@ when called.  ``beam_speculative_sampling_v2`` (section 8(f) rank 4) is built fo
 from .speculative_sampling import speculative_sampling
 from .autoregressive_sampling import autoregressive_sampling
 from .batch import (speculative_sampling_batch, speculative_sampling_queue, speculative_sampling_queue_shared,
-                    speculative_sampling_queue_logprobs, speculative_sampling_queue_requests, autoregressive_sampling_batch)
+                    speculative_sampling_queue_logprobs, speculative_sampling_queue_requests, speculative_sampling_queue_edits,
+                    autoregressive_sampling_batch)
 from .multi import multi_speculative_sampling
 from .beam import beam_speculative_sampling_v2
 from .kvcache_model import KVCacheModel
@@ -37,5 +38,5 @@ __all__ = ["speculative_sampling", "speculative_sampling_v2", "autoregressive_sa
            "beam_speculative_sampling", "BiLD_sampling", "mjsd_speculative_sampling", "random_width_beam_sampling",
            "beam_speculative_sampling_v2",
            "speculative_sampling_batch", "speculative_sampling_queue", "speculative_sampling_queue_shared",
-           "speculative_sampling_queue_logprobs", "speculative_sampling_queue_requests",
+           "speculative_sampling_queue_logprobs", "speculative_sampling_queue_requests", "speculative_sampling_queue_edits",
            "autoregressive_sampling_batch", "KVCacheModel", "norm_logits", "sample", "max_fn", "top_k_top_p_filter"]

@@ -8,8 +8,8 @@ import math
 import numpy as np
 import torch
 
-from .._lib import (LOGPROB_SLICE, LOGPROB_STREAMS, SdHeadScratch, SdLockstepLog, SdLogprobBlock, SdPenalty, SdPenaltyBlock,
-                    SdRowSampling, SdSampling, SdSeqState, SdSpecScratch, SdSpecStream)
+from .._lib import (LOGPROB_SLICE, LOGPROB_STREAMS, SD_EDIT_MAX_BIAS, SdHeadScratch, SdLockstepLog, SdLogitEdit, SdLogitEditBlock,
+                    SdLogprobBlock, SdPenalty, SdPenaltyBlock, SdRowSampling, SdSampling, SdSeqState, SdSpecScratch, SdSpecStream)
 from ..noise import DeviceNoise, HostTorchNoise
 from .kvcache_model import KVCacheModel
 
@@ -284,6 +284,216 @@ class PenaltyBlock:
         self.rows = torch.empty((max(1, int(max_rows)), ld), dtype=torch.float32, device=device)
         self._params = (SdPenalty * len(triples))(*[SdPenalty(*t) for t in triples])
         self.block = SdPenaltyBlock(self.rows.data_ptr(), ld, self.rows.shape[0], self._params)
+
+
+def _int_id(x):
+    """A token id as a python int, or None for anything that is not an integer (bool included)."""
+    if isinstance(x, torch.Tensor) and x.ndim == 0:
+        x = x.item()
+    if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+        return None
+    return int(x)
+
+
+def _id_lists(n: int, what: str, name: str, v):
+    """``allowed_token_ids`` / ``banned_token_ids``: None, a flat sequence of ids for every request, or a sequence with one
+    sequence-or-None per request -> n lists-or-None."""
+    if v is None:
+        return [None] * n
+    if isinstance(v, (np.ndarray, torch.Tensor)):
+        v = v.tolist()
+    if not isinstance(v, (list, tuple)):
+        raise ValueError(f"{name}: a sequence of token ids, or one sequence (or None) per {what}, is required, not {v!r}")
+    nested = lambda x: x is None or _per_request(x)
+    try:                                                          # (a long flat list is recognised as one array, not entry by entry)
+        arr = np.asarray(v)
+        flat = arr.ndim == 1 and arr.dtype != object
+    except ValueError:
+        flat = False
+    if flat and arr.dtype.kind in "iu":
+        return [arr] * n                                          # (parsed: ids_of takes it as it is)
+    if flat or not any(nested(x) for x in v):
+        return [list(v)] * n
+    if len(v) != n:
+        raise ValueError(f"{name}: {len(v)} entries for {n} {what}s")
+    out = []
+    for i, x in enumerate(v):
+        if not nested(x):
+            raise ValueError(f"{name}: {what} {i}: a sequence of token ids or None is required, not {x!r}")
+        out.append(None if x is None else list(x.tolist() if isinstance(x, (np.ndarray, torch.Tensor)) else x))
+    return out
+
+
+def allowed_mask_words(V: int, allowed=None, banned=()):
+    """The sd_logit_edit mask of one request: (V + 31) // 32 uint32 words, bit ``t & 31`` of word ``t >> 5`` set = token t
+    allowed.  ``allowed`` None means every id of [0, V); ``banned`` ids are cleared bits of the same mask; bits of ids >= V
+    in the last word are clear."""
+    bits = np.zeros(((V + 31) // 32) * 32, dtype=bool)
+    if allowed is None:
+        bits[:V] = True
+    else:
+        bits[np.asarray(allowed, dtype=np.int64)] = True
+    if len(banned):
+        bits[np.asarray(banned, dtype=np.int64)] = False
+    return np.packbits(bits.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1).astype(np.uint32)
+
+
+def logit_edits(n: int, what: str, V, eos_token_id, logit_bias=None, allowed_token_ids=None, banned_token_ids=None, min_tokens=0):
+    """Per-request ``logit_bias`` / ``allowed_token_ids`` / ``banned_token_ids`` / ``min_tokens`` of the native loops, ``n``
+    requests called ``what`` ("prompt", "stream").  ``logit_bias``: one ``{id: bias}`` mapping for every request or a sequence
+    with one mapping-or-None per request; the id lists: one flat sequence for every request or one sequence-or-None per
+    request; ``min_tokens``: an int or one per request.  Returns ``None`` when everything is neutral - the call then takes the
+    entry point it took before - else one record per request: ``dict(bias_ids=int32 array ascending, bias_vals=float32 array,
+    mask=uint32 words or None, min_tokens=int)``.  Raises ValueError naming the parameter and the request for a sequence of
+    another length, a bias that is not a finite number, more than 1024 bias entries, an id that is not an integer or lies
+    outside [0, V), min_tokens < 0, an allowed set that is empty once the banned ids are removed, or one that holds nothing but
+    EOS while min_tokens > 0.  ``V`` None: the vocabulary is not known yet - the upper bound of the ids is not checked and the
+    records carry no mask; the wrappers validate this way before they touch a model and finish the same records with
+    ``bind_logit_edits`` once V is known, so every list is parsed once.  Touches no GPU."""
+    if logit_bias is None or (hasattr(logit_bias, "items") and not isinstance(logit_bias, (list, tuple))):
+        biases = [logit_bias] * n
+    elif isinstance(logit_bias, (list, tuple)):
+        if len(logit_bias) != n:
+            raise ValueError(f"logit_bias: {len(logit_bias)} entries for {n} {what}s")
+        biases = list(logit_bias)
+    else:
+        raise ValueError(f"logit_bias: a mapping of token id to bias, or one mapping (or None) per {what}, is required, not {logit_bias!r}")
+    allowed, banned = _id_lists(n, what, "allowed_token_ids", allowed_token_ids), _id_lists(n, what, "banned_token_ids", banned_token_ids)
+    if _per_request(min_tokens):
+        if len(min_tokens) != n:
+            raise ValueError(f"min_tokens: {len(min_tokens)} entries for {n} {what}s")
+        mins = [x.item() if isinstance(x, (np.generic, torch.Tensor)) else x for x in min_tokens]
+    else:
+        mins = [min_tokens] * n
+
+    def ids_of(name, i, xs):
+        """-> the ids as a sorted array without repeats (a plain integer sequence is checked as one array)"""
+        try:
+            arr = np.asarray(xs) if len(xs) else np.zeros(0, dtype=np.int64)
+        except (OverflowError, ValueError):
+            arr = None
+        if arr is None or arr.ndim != 1 or arr.dtype.kind not in "iu":
+            for x in xs:
+                if _int_id(x) is None:
+                    raise ValueError(f"{name}: {what} {i}: token ids are integers, not {x!r}")
+            arr = np.asarray([_int_id(x) for x in xs], dtype=object)
+        bad = [int(t) for t in arr if t < 0 or t >= 2 ** 31] if arr.dtype == object else arr[(arr < 0) | (arr >= 2 ** 31)].tolist()
+        if bad:
+            raise ValueError(f"{name}: {what} {i}: token id {bad[0]} outside [0, {V if V is not None else 'V'})")
+        return np.unique(arr.astype(np.int64))
+    def bias_pairs(i, b):
+        """-> the mapping's (id, bias) pairs, ascending by id"""
+        keys, vals = (list(b.keys()), list(b.values())) if b else ([], [])
+        if len(keys) > SD_EDIT_MAX_BIAS:
+            raise ValueError(f"logit_bias: {what} {i}: {len(keys)} entries, at most {SD_EDIT_MAX_BIAS}")
+        for t in keys:                                            # (one by one: a float key must not pass as its integer value)
+            if _int_id(t) is None:
+                raise ValueError(f"logit_bias: {what} {i}: token ids are integers, not {t!r}")
+        if len(ids_of("logit_bias", i, keys)) != len(keys):
+            raise ValueError(f"logit_bias: {what} {i}: a token id is listed twice")
+        vals = [x.item() if isinstance(x, (np.generic, torch.Tensor)) else x for x in vals]
+        for t, x in zip(keys, vals):
+            if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x):
+                raise ValueError(f"logit_bias: {what} {i}: token {t}: a finite number is required, not {x!r}")
+        return sorted(zip((int(t) for t in keys), vals))
+    records, neutral, parsed = [], True, {}
+    masks = {}                                                    # one mask per pair of list objects: a list for all requests is built once
+    for i in range(n):
+        b = biases[i]
+        if b is not None and not hasattr(b, "items"):
+            raise ValueError(f"logit_bias: {what} {i}: a mapping of token id to bias or None is required, not {b!r}")
+        if b and id(b) in parsed:                                 # (one mapping for every request is parsed once)
+            pairs = parsed[id(b)]
+        else:
+            pairs = parsed[id(b)] = bias_pairs(i, b)
+        m = mins[i]
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or m < 0:
+            raise ValueError(f"min_tokens: {what} {i}: an integer >= 0 is required, not {m!r}")
+        key = (id(allowed[i]), id(banned[i]))
+        if key not in masks:
+            a = None if allowed[i] is None else ids_of("allowed_token_ids", i, allowed[i])
+            d = ids_of("banned_token_ids", i, banned[i]) if banned[i] is not None else np.zeros(0, dtype=np.int64)
+            left = np.setdiff1d(a, d) if a is not None else None   # (None: every id of [0, V) but d's)
+            masked = a is not None or len(d) > 0
+            masks[key] = (a, d, left, masked)
+        a, d, left, masked = masks[key]
+        neutral = neutral and not pairs and not masked and int(m) == 0
+        records.append(dict(bias_ids=np.asarray([t for t, _ in pairs], dtype=np.int32),
+                            bias_vals=np.asarray([float(x) for _, x in pairs], dtype=np.float32),
+                            allowed=a, banned=d, left=left, mask=None, masked=masked, min_tokens=int(m)))
+    if neutral:
+        return None
+    _check_left(records, what, None, eos_token_id)
+    return records if V is None else bind_logit_edits(records, what, V, eos_token_id)
+
+
+def _check_left(records, what: str, V, eos_token_id) -> None:
+    """What the masks leave: refuses a request with no id left, or with EOS alone while min_tokens > 0.  V None: only the
+    requests with an allowed list can be judged (banned ids alone empty nothing before the vocabulary is known)."""
+    for i, r in enumerate(records):
+        left, d, m = r["left"], r["banned"], r["min_tokens"]
+        n_left = len(left) if left is not None else (V - len(d) if V is not None else None)
+        if n_left == 0:
+            raise ValueError(f"allowed_token_ids: {what} {i}: no token id is left once the banned ids are removed")
+        if m > 0 and n_left == 1 and eos_token_id is not None and \
+                (int(left[0]) == eos_token_id if left is not None else (0 <= eos_token_id < V and eos_token_id not in d)):
+            raise ValueError(f"allowed_token_ids: {what} {i}: only EOS ({eos_token_id}) is allowed while min_tokens is {m}")
+
+
+def bind_logit_edits(records, what: str, V: int, eos_token_id):
+    """The second half of ``logit_edits``, once the vocabulary size is known: the upper bound of every id, what the banned ids
+    leave of [0, V), and the mask words - on the arrays the first half parsed (requests that share their lists share the
+    mask).  Completes and returns ``records``."""
+    masks = {}
+    for i, r in enumerate(records):
+        for name, ids in (("logit_bias", r["bias_ids"]), ("allowed_token_ids", r["allowed"]), ("banned_token_ids", r["banned"])):
+            if ids is not None and len(ids) and int(ids[-1]) >= V:     # (ascending)
+                raise ValueError(f"{name}: {what} {i}: token id {int(ids[ids >= V][0])} outside [0, {V})")
+    _check_left(records, what, V, eos_token_id)
+    for r in records:
+        key = (id(r["allowed"]), id(r["banned"]))
+        if r["masked"] and key not in masks:
+            masks[key] = allowed_mask_words(V, r["allowed"], r["banned"])
+        r["mask"] = masks.get(key) if r["masked"] else None
+    return records
+
+
+def edits_need_target_rows(target_m) -> None:
+    """Logit edits act on the logit rows where a single-GPU forward leaves them: a tensor-parallel shard is refused."""
+    if getattr(target_m, "tp_group", None) is not None:
+        raise ValueError("logit_bias / allowed_token_ids / banned_token_ids / min_tokens are not available with a tensor-parallel "
+                         "target model")
+
+
+EDITS_NEED_NATIVE = ('logit_bias / allowed_token_ids / banned_token_ids / min_tokens need the native loop: rng="device" (or a device '
+                     'noise object)')
+
+
+class LogitEditBlock:
+    """The SdLogitEditBlock of one native loop call: the records of ``logit_edits`` (one per stream, per prompt in the queue),
+    every request's bias ids, bias values and mask words uploaded as ONE concatenated tensor per kind, and the device slab the
+    edited logit rows of a pass go to, sized and aligned as PenaltyBlock's (``rows``: that block's slab, shared when a call has
+    both - the launch writes the edit block's)."""
+
+    def __init__(self, device, records, V: int, max_rows: int, rows=None):
+        ld = (int(V) + 3) // 4 * 4
+        self.rows = rows if rows is not None else torch.empty((max(1, int(max_rows)), ld), dtype=torch.float32, device=device)
+
+        def upload(arrays, dtype):
+            """-> the device address of every array (None for an absent / empty one) inside one tensor"""
+            sizes = [0 if a is None else len(a) for a in arrays]
+            if not sum(sizes):
+                return None, [None] * len(arrays)
+            host = np.concatenate([a for a in arrays if a is not None and len(a)]).astype(dtype)
+            dev = torch.from_numpy(host.view(np.int32) if dtype == np.uint32 else host).to(device)
+            offs = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+            return dev, [dev.data_ptr() + 4 * int(o) if k else None for o, k in zip(offs, sizes)]
+        self._ids, ids = upload([r["bias_ids"] for r in records], np.int32)
+        self._vals, vals = upload([r["bias_vals"] for r in records], np.float32)
+        self._masks, masks = upload([r["mask"] for r in records], np.uint32)
+        self._params = (SdLogitEdit * len(records))(*[SdLogitEdit(i, v, len(r["bias_ids"]), m, r["min_tokens"])
+                                                      for r, i, v, m in zip(records, ids, vals, masks)])
+        self.block = SdLogitEditBlock(self.rows.data_ptr(), self.rows.stride(0), self.rows.shape[0], self._params)
 
 
 def raise_loop_error(code: int) -> None:

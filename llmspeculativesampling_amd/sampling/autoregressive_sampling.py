@@ -8,7 +8,8 @@ import torch
 
 from .._lib import lib, check, SdArLog, SdArStream
 from ..engine import as_specdec_model, _stream, check_token_ids
-from ._loop_common import (LogprobBlock, PenaltyBlock, device_rng, head_scratch, logprobs_need_target_rows, make_noise, open_stream,
+from ._loop_common import (EDITS_NEED_NATIVE, LogitEditBlock, LogprobBlock, PenaltyBlock, device_rng, edits_need_target_rows,
+                           head_scratch, bind_logit_edits, logit_edits, logprobs_need_target_rows, make_noise, open_stream,
                            penalties_need_target_rows, penalty_triples, raise_loop_error, sampling_block)
 from .kvcache_model import KVCacheModel
 
@@ -17,7 +18,8 @@ from .kvcache_model import KVCacheModel
 def autoregressive_sampling(x: torch.Tensor, model, N: int, eos_token_id: int, temperature: float = 1,
                             top_k: int = 0, top_p: float = 0, pad_token_id=None, *, rng=None, _native: bool = True,
                             logprobs: bool = False, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
-                            presence_penalty: float = 0.0):
+                            presence_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
+                            min_tokens=0):
     """reference autoregressive_sampling.py:9-61: exactly N tokens unless EOS is drawn (the EOS is kept).
     RNG contract: one ``sample`` per token.  With the device RNG the whole loop is one native call
     (sd_ar_batch_generate with one stream); ``_native=False`` keeps the interpreter loop below, which the host RNG
@@ -27,7 +29,17 @@ def autoregressive_sampling(x: torch.Tensor, model, N: int, eos_token_id: int, t
     before temperature, top_k and top_p: what the model says, not what the sampler drew from.
     ``repetition_penalty`` / ``frequency_penalty`` / ``presence_penalty`` (native loop only; neutral 1 / 0 / 0): every logit row
     is edited on the device by its own history before it is normalised (``sampling.utils.apply_penalties``); ``logprobs`` stay
-    what the model says."""
+    what the model says.
+    ``logit_bias`` / ``allowed_token_ids`` / ``banned_token_ids`` / ``min_tokens`` (native loop only; neutral None / None / None
+    / 0): behind the penalties a ``{token id: bias}`` mapping is added, ids outside the allowed list or inside the banned list
+    become -inf, and so does ``eos_token_id`` until ``min_tokens`` tokens have been produced
+    (``sampling.utils.apply_logit_edits``)."""
+    edit_args = (logit_bias, allowed_token_ids, banned_token_ids, min_tokens)
+    ed = logit_edits(1, "stream", None, eos_token_id, *edit_args)
+    if ed is not None and not (_native and device_rng(rng)):
+        raise ValueError(EDITS_NEED_NATIVE + ", not _native=False")
+    if ed is not None:
+        edits_need_target_rows(model)
     pen = penalty_triples(1, "stream", repetition_penalty, frequency_penalty, presence_penalty)
     if pen is not None and not (_native and device_rng(rng)):
         raise ValueError('repetition / frequency / presence penalties need the native loop: rng="device" (or a device noise '
@@ -42,6 +54,8 @@ def autoregressive_sampling(x: torch.Tensor, model, N: int, eos_token_id: int, t
         logprobs_need_target_rows(m)
     dev = m.device
     V = m.cfg.vocab_size
+    if ed is not None:
+        ed = bind_logit_edits(ed, "stream", V, eos_token_id)
     L0 = x.shape[1]
     check_token_ids(x, V)
     noise = make_noise(rng, dev)
@@ -50,7 +64,7 @@ def autoregressive_sampling(x: torch.Tensor, model, N: int, eos_token_id: int, t
     if _native and getattr(noise, "on_device", False):
         run = ArRun(m, temperature, top_k, top_p, eos_token_id)
         run.add(kv, seq32, x[0].to(device="cpu", dtype=torch.int32).numpy(), L0 + N, noise)
-        run.generate(logprobs=logprobs, penalties=pen)
+        run.generate(logprobs=logprobs, penalties=pen, edits=ed)
         out = torch.from_numpy(run.tokens(0)).to(torch.int64).unsqueeze(0).to(x.device)
         return (out, run.logprobs(0, x.device)) if logprobs else out
     n_out = 0
@@ -97,8 +111,9 @@ class ArRun:
         err = torch.zeros(2, dtype=torch.int32, device=self.m.device)
         self.streams.append(_ArStream(kv, seq32, host, err, noise, len(prompt), int(T)))
 
-    def generate(self, timing: bool = False, logprobs: bool = False, penalties=None) -> None:
-        """``penalties``: None, or one (repetition, frequency, presence) triple per stream (_loop_common.penalty_triples)."""
+    def generate(self, timing: bool = False, logprobs: bool = False, penalties=None, edits=None) -> None:
+        """``penalties``: None, or one (repetition, frequency, presence) triple per stream (_loop_common.penalty_triples);
+        ``edits``: None, or one record per stream (_loop_common.logit_edits)."""
         B = len(self.streams)
         if not 1 <= B <= 16:
             raise ValueError(f"autoregressive sampling takes 1..16 streams per call, not {B}")
@@ -123,7 +138,11 @@ class ArRun:
                 dev_block.data_ptr(), host_block.data_ptr(), log, _stream())
         self.lp = LogprobBlock(dev, [s.T + 1 for s in self.streams]) if logprobs else None
         pb = PenaltyBlock(dev, penalties, self.m.cfg.vocab_size, B) if penalties is not None else None
-        if pb is not None:
+        eb = LogitEditBlock(dev, edits, self.m.cfg.vocab_size, B, pb.rows if pb is not None else None) if edits is not None else None
+        if eb is not None:
+            rc = lib.sd_ar_batch_generate_edits(*args, self.lp.block if self.lp is not None else None,
+                                                pb.block if pb is not None else None, eb.block)
+        elif pb is not None:
             rc = lib.sd_ar_batch_generate_penalties(*args, self.lp.block if self.lp is not None else None, pb.block)
         elif self.lp is None:
             rc = lib.sd_ar_batch_generate(*args)

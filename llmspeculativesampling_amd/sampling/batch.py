@@ -22,9 +22,10 @@ import torch
 from .._lib import lib, check, SdAcceptResult, SdBatchStream, SdQueuePrompt
 from ..engine import as_specdec_model, _stream, check_token_ids, same_device, batch_prefill
 from ..noise import DeviceNoise
-from ._loop_common import (LockstepLog, LogprobBlock, LoopLog, PenaltyBlock, bind_spec_slot, lockstep_result,
-                           logprobs_need_target_rows, open_spec_slot, open_stream, penalties_need_target_rows, penalty_triples,
-                           reseed_uniforms, row_sampling, row_sampling_array, sampling_block, spec_scratch)
+from ._loop_common import (LockstepLog, LogitEditBlock, LogprobBlock, LoopLog, PenaltyBlock, bind_spec_slot, edits_need_target_rows,
+                           lockstep_result, bind_logit_edits, logit_edits, logprobs_need_target_rows, open_spec_slot, open_stream,
+                           penalties_need_target_rows, penalty_triples, reseed_uniforms, row_sampling, row_sampling_array,
+                           sampling_block, spec_scratch)
 from .autoregressive_sampling import ArRun
 from .kvcache_model import KVCacheModel
 
@@ -55,7 +56,8 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
                                pad_token_id, max_len: int, gamma: int = 4, temperature: float = 1, top_k: int = 0,
                                top_p: float = 0, random_seed: int = None, details: bool = False,
                                seeds: Optional[Sequence[int]] = None, _timing: Optional[dict] = None, *,
-                               logprobs: bool = False, repetition_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0):
+                               logprobs: bool = False, repetition_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0,
+                               logit_bias=None, allowed_token_ids=None, banned_token_ids=None, min_tokens=0):
     """B streams at once; ``prefixes[i]`` is (1, L_i) int64.  Returns a list of (1, len_i) tensors (and a list of
     ``details`` dicts with the reference's keys when ``details``).  Device Philox RNG, stream i seeded ``seeds[i]``.
     ``temperature``, ``top_k`` and ``top_p`` each take one value for all streams or a sequence with one entry per stream
@@ -71,14 +73,23 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
     or one per stream, broadcast like ``temperature``; stream i equals ``speculative_sampling(prefixes[i], ...,
     repetition_penalty=r_i, frequency_penalty=f_i, presence_penalty=p_i, rng=DeviceNoise(seeds[i]))``
     (sd_spec_batch_generate_penalties; ``sampling.utils.apply_penalties`` has the definition).  A sequence of another length, a
-    value that is not finite or a repetition penalty <= 0 raises ValueError before a model is touched."""
+    value that is not finite or a repetition penalty <= 0 raises ValueError before a model is touched.
+    ``logit_bias`` (one ``{token id: bias}`` mapping for all streams, or a sequence with one mapping-or-None per stream),
+    ``allowed_token_ids`` / ``banned_token_ids`` (one flat sequence of ids for all streams, or one sequence-or-None per stream)
+    and ``min_tokens`` (an int, or one per stream): stream i equals ``speculative_sampling`` with its values
+    (sd_spec_batch_generate_edits; ``sampling.utils.apply_logit_edits`` has the definition, ``speculative_sampling`` the
+    refusals)."""
+    edit_args = (logit_bias, allowed_token_ids, banned_token_ids, min_tokens)
     try:
         triples = row_sampling(len(prefixes), "stream", temperature, top_k, top_p)
         pen = penalty_triples(len(prefixes), "stream", repetition_penalty, frequency_penalty, presence_penalty)
+        ed = logit_edits(len(prefixes), "stream", None, eos_token_id, *edit_args)
     except TypeError:
         raise ValueError("prefixes: a sequence of (1, L) int64 prompts is required") from None
     if pen is not None:
         penalties_need_target_rows(target_model)
+    if ed is not None:
+        edits_need_target_rows(target_model)
     draft_m, target_m = as_specdec_model(approx_model), as_specdec_model(target_model)
     same_device(draft_m, target_m)
     if logprobs:
@@ -86,6 +97,8 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
     dev = target_m.device
     V = target_m.cfg.vocab_size
     assert draft_m.cfg.vocab_size == V
+    if ed is not None:
+        ed = bind_logit_edits(ed, "stream", V, eos_token_id)
     for pf in prefixes:
         check_token_ids(pf, V)
     B = len(prefixes)
@@ -139,7 +152,12 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
             vlog.block, cu)
     lp = LogprobBlock(dev, [len(s.log.host_seq) for s in streams]) if logprobs else None
     pb = PenaltyBlock(dev, pen, V, min(max(per_pass, gamma + 1), B * (gamma + 1))) if pen is not None else None
-    if pb is not None:
+    eb = LogitEditBlock(dev, ed, V, min(max(per_pass, gamma + 1), B * (gamma + 1)), pb.rows if pb is not None else None) \
+        if ed is not None else None
+    if eb is not None:
+        check(lib.sd_spec_batch_generate_edits(*args, row_sampling_array(triples), lp.block if lp is not None else None,
+                                               pb.block if pb is not None else None, eb.block), "sd_spec_batch_generate_edits")
+    elif pb is not None:
         check(lib.sd_spec_batch_generate_penalties(*args, row_sampling_array(triples), lp.block if lp is not None else None, pb.block),
               "sd_spec_batch_generate_penalties")
     elif lp is not None:
@@ -294,8 +312,32 @@ def speculative_sampling_queue_requests(prefixes: Sequence[torch.Tensor], approx
                   penalties=(repetition_penalty, frequency_penalty, presence_penalty))
 
 
+@torch.no_grad()
+def speculative_sampling_queue_edits(prefixes: Sequence[torch.Tensor], approx_model, target_model, eos_token_id, pad_token_id,
+                                     max_len, gamma: int = 4, temperature: float = 1, top_k: int = 0, top_p: float = 0,
+                                     random_seed: int = None, details: bool = False, seeds: Optional[Sequence[int]] = None,
+                                     slots: int = 8, prefill_chunk: int = 0, _timing: Optional[dict] = None,
+                                     shared_prefix: int = 0, *, logprobs: bool = False, repetition_penalty=1.0,
+                                     frequency_penalty=0.0, presence_penalty=0.0, logit_bias=None, allowed_token_ids=None,
+                                     banned_token_ids=None, min_tokens=0):
+    """speculative_sampling_queue_requests with the request fields that restrict what may be sampled: ``logit_bias`` (one
+    ``{token id: bias}`` mapping for all prompts, or a sequence with one mapping-or-None per prompt), ``allowed_token_ids`` /
+    ``banned_token_ids`` (one flat sequence of ids for all prompts, or one sequence-or-None per prompt) and ``min_tokens`` (an
+    int, or one per prompt), as ``speculative_sampling`` describes them.  Prompt i equals ``speculative_sampling(prefixes[i],
+    ..., rng=DeviceNoise(seeds[i]))`` with its values, whichever slot it decodes in: a slot changes its edits when it changes
+    hands, and ``min_tokens`` counts the request's own output (sd_spec_queue_generate_edits; ``sampling.utils.apply_logit_edits``
+    has the definition).  ValueError before a model is touched, as ``speculative_sampling`` lists them, naming the parameter
+    and the prompt.  ``logprobs=True``: the scores stay what the model says.  (A function of its own:
+    speculative_sampling_queue_requests' parameter list is pinned by its test, as the other queues' are.)"""
+    return _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max_len, gamma, temperature, top_k, top_p,
+                  random_seed, details, seeds, slots, prefill_chunk, _timing, shared_prefix, logprobs=logprobs,
+                  penalties=(repetition_penalty, frequency_penalty, presence_penalty),
+                  edits=(logit_bias, allowed_token_ids, banned_token_ids, min_tokens))
+
+
 def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max_len, gamma, temperature, top_k, top_p,
-           random_seed, details, seeds, slots, prefill_chunk, _timing, shared_prefix, logprobs=False, penalties=(1.0, 0.0, 0.0)):
+           random_seed, details, seeds, slots, prefill_chunk, _timing, shared_prefix, logprobs=False, penalties=(1.0, 0.0, 0.0),
+           edits=(None, None, None, 0)):
     """The prompt queue behind the public entry points (their docstrings have the contract)."""
     budgets = _queue_arguments(prefixes, max_len, seeds, slots)
     shared = _shared_prefix_argument(prefixes, shared_prefix)
@@ -307,6 +349,9 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
     pen = penalty_triples(len(prefixes), "prompt", *penalties)
     if pen is not None:
         penalties_need_target_rows(target_model)
+    ed = logit_edits(len(prefixes), "prompt", None, eos_token_id, *edits)
+    if ed is not None:
+        edits_need_target_rows(target_model)
     if triples is not None:                                       # (a slot's KVCacheModel and the block's own triple are not read)
         temperature, top_k, top_p = triples[0]
     draft_m, target_m = as_specdec_model(approx_model), as_specdec_model(target_model)
@@ -316,6 +361,8 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
     dev = target_m.device
     V = target_m.cfg.vocab_size
     assert draft_m.cfg.vocab_size == V
+    if ed is not None:
+        ed = bind_logit_edits(ed, "prompt", V, eos_token_id)
     for pf in prefixes:
         check_token_ids(pf, V)
     N = len(prefixes)
@@ -368,7 +415,12 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
     args += (*[ses.handle if ses else None for ses in donors], rows)
     lp = LogprobBlock(dev, [len(log.host_seq) for log in logs]) if logprobs else None
     pb = PenaltyBlock(dev, pen, V, min(max(per_pass, gamma + 1), S * (gamma + 1))) if pen is not None else None
-    if pb is not None:
+    eb = LogitEditBlock(dev, ed, V, min(max(per_pass, gamma + 1), S * (gamma + 1)), pb.rows if pb is not None else None) \
+        if ed is not None else None
+    if eb is not None:
+        check(lib.sd_spec_queue_generate_edits(*args, row_sampling_array(triples), lp.block if lp is not None else None,
+                                               pb.block if pb is not None else None, eb.block), "sd_spec_queue_generate_edits")
+    elif pb is not None:
         check(lib.sd_spec_queue_generate_penalties(*args, row_sampling_array(triples), lp.block if lp is not None else None, pb.block),
               "sd_spec_queue_generate_penalties")
     elif lp is not None:
@@ -399,7 +451,8 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
 def autoregressive_sampling_batch(xs: Sequence[torch.Tensor], model, N: int, eos_token_id, temperature: float = 1,
                                   top_k: int = 0, top_p: float = 0, pad_token_id=None, *,
                                   seeds: Optional[Sequence[int]] = None, _timing: Optional[dict] = None,
-                                  logprobs: bool = False, repetition_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0):
+                                  logprobs: bool = False, repetition_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0,
+                                  logit_bias=None, allowed_token_ids=None, banned_token_ids=None, min_tokens=0):
     """``autoregressive_sampling`` for B streams at once: ``xs[i]`` is (1, L_i) int64, the result a list of (1, len_i)
     tensors.  The streams decode in lock-step and share every pass over the weights (sd_ar_batch_generate): each runs the
     algorithm of reference autoregressive_sampling.py:9-61 on its own Philox stream ``seeds[i]`` (default
@@ -409,17 +462,24 @@ def autoregressive_sampling_batch(xs: Sequence[torch.Tensor], model, N: int, eos
     log-softmax of its raw logits, before temperature, top_k and top_p - what the model says, not what the sampler drew from.
     ``repetition_penalty`` / ``frequency_penalty`` / ``presence_penalty`` (neutral 1 / 0 / 0): each one value for all streams or
     one per stream; stream i equals ``autoregressive_sampling(xs[i], ..., rng=DeviceNoise(seeds[i]))`` with its values
-    (sd_ar_batch_generate_penalties)."""
+    (sd_ar_batch_generate_penalties).  ``logit_bias`` / ``allowed_token_ids`` / ``banned_token_ids`` / ``min_tokens``: one
+    value for all streams or one per stream, as ``speculative_sampling_batch`` takes them (sd_ar_batch_generate_edits)."""
     B = len(xs)
     if not 1 <= B <= 16:
         raise ValueError(f"autoregressive_sampling_batch takes 1..16 streams per call, not {B}")
     pen = penalty_triples(B, "stream", repetition_penalty, frequency_penalty, presence_penalty)
     if pen is not None:
         penalties_need_target_rows(model)
+    edit_args = (logit_bias, allowed_token_ids, banned_token_ids, min_tokens)
+    ed = logit_edits(B, "stream", None, eos_token_id, *edit_args)
+    if ed is not None:
+        edits_need_target_rows(model)
     m = as_specdec_model(model)
     if logprobs:
         logprobs_need_target_rows(m)
     V = m.cfg.vocab_size
+    if ed is not None:
+        ed = bind_logit_edits(ed, "stream", V, eos_token_id)
     for x in xs:
         assert x.dim() == 2 and x.shape[0] == 1 and x.shape[1] >= 1, "every stream is one (1, L) prompt"
         check_token_ids(x, V)
@@ -432,7 +492,7 @@ def autoregressive_sampling_batch(xs: Sequence[torch.Tensor], model, N: int, eos
     batch_prefill([kv._session for kv in kvs], seqs, [x.shape[1] - 1 for x in xs])
     for x, seed, kv, seq32 in zip(xs, seeds, kvs, seqs):
         run.add(kv, seq32, x[0].to(device="cpu", dtype=torch.int32).numpy(), x.shape[1] + int(N), DeviceNoise(seed))
-    run.generate(timing=_timing is not None, logprobs=logprobs, penalties=pen)
+    run.generate(timing=_timing is not None, logprobs=logprobs, penalties=pen, edits=ed)
     if _timing is not None:
         _timing.setdefault("step", []).extend(run.steps)
     outs = [torch.from_numpy(run.tokens(i)).to(torch.int64).unsqueeze(0).to(x.device) for i, x in enumerate(xs)]

@@ -16,7 +16,8 @@ import torch
 
 from .._lib import lib, check, SdAcceptResult
 from ..engine import as_specdec_model, _stream, check_token_ids, same_device
-from ._loop_common import (LogprobBlock, LoopLog, PenaltyBlock, accept_rates_f64, cut_after_new_eos, details_dict, device_rng,
+from ._loop_common import (EDITS_NEED_NATIVE, LogitEditBlock, LogprobBlock, LoopLog, PenaltyBlock, accept_rates_f64,
+                           cut_after_new_eos, details_dict, device_rng, edits_need_target_rows, bind_logit_edits, logit_edits,
                            logprobs_need_target_rows, make_noise, open_stream, penalties_need_target_rows, penalty_triples,
                            raise_loop_error, reseed_uniforms, sampling_block, spec_scratch, spec_stream)
 
@@ -28,7 +29,8 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
                          max_len: int, gamma: int = 4, temperature: float = 1, top_k: int = 0, top_p: float = 0,
                          verbose: bool = False, random_seed: int = None, details: bool = False, *, rng=None,
                          _event_logs=None, logprobs: bool = False, repetition_penalty: float = 1.0,
-                         frequency_penalty: float = 0.0, presence_penalty: float = 0.0):
+                         frequency_penalty: float = 0.0, presence_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None,
+                         banned_token_ids=None, min_tokens=0):
     """reference speculative_sampling.py:1876-2076.
 
     ``rng`` (extension): "host" (default) draws every variate from torch's CPU generator in the
@@ -47,7 +49,22 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
     positive logit, x * r otherwise), ``frequency * count`` and ``presence`` subtracted for tokens generated so far.  They
     change what the sampler draws from; ``logprobs`` stay what the model says.  ValueError before a model is touched for a
     value that is not finite, a repetition penalty <= 0, an interpreter path or a tensor-parallel target.
+
+    ``logit_bias`` / ``allowed_token_ids`` / ``banned_token_ids`` / ``min_tokens`` (extension, native device-RNG loop only;
+    neutral None / None / None / 0): the request fields that restrict what may be sampled, applied on the device to every
+    draft and target logit row behind the penalties, as ``sampling.utils.apply_logit_edits`` defines it - a ``{token id:
+    bias}`` mapping of at most 1024 entries is added, every id outside ``allowed_token_ids`` (None: all) or inside
+    ``banned_token_ids`` becomes -inf, and so does ``eos_token_id`` until ``min_tokens`` tokens have been produced.
+    ``logprobs`` stay what the model says.  ValueError before a model is touched for a bias that is not a finite number, more
+    than 1024 entries, an id that is not an integer or lies outside the vocabulary, ``min_tokens < 0``, an allowed set that the
+    banned ids empty or that holds nothing but EOS while ``min_tokens > 0``, an interpreter path or a tensor-parallel target.
     """
+    edit_args = (logit_bias, allowed_token_ids, banned_token_ids, min_tokens)
+    ed = logit_edits(1, "stream", None, eos_token_id, *edit_args)
+    if ed is not None and (verbose or not device_rng(rng)):
+        raise ValueError(EDITS_NEED_NATIVE + " and verbose=False")
+    if ed is not None:
+        edits_need_target_rows(target_model)
     pen = penalty_triples(1, "stream", repetition_penalty, frequency_penalty, presence_penalty)
     if pen is not None and (verbose or not device_rng(rng)):
         raise ValueError('repetition / frequency / presence penalties need the native loop: rng="device" (or a device noise '
@@ -67,6 +84,8 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
     V = target_m.cfg.vocab_size
     assert draft_m.cfg.vocab_size == V, "draft and target must share a vocabulary"
     assert 1 <= gamma <= 16
+    if ed is not None:
+        ed = bind_logit_edits(ed, "stream", V, eos_token_id)
 
     seq_len0 = prefix.shape[1]
     T = seq_len0 + max_len
@@ -83,7 +102,7 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
     target, seq32 = open_stream(target_m, prefix[0], cap, cap + 1, temperature, top_k, top_p, noise)
     if getattr(noise, "on_device", False) and not verbose:
         return _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T, gamma, random_seed, details,
-                                   noise, _event_logs, logprobs, pen)
+                                   noise, _event_logs, logprobs, pen, ed)
 
     ori_eos_cnt = host_seq.count(eos_token_id)
     if _event_logs is not None:                       # bench.py: HIP-event brackets around every forward
@@ -195,7 +214,7 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
 
 
 def _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T, gamma, random_seed, details, noise,
-                        timing_log, logprobs=False, pen=None):
+                        timing_log, logprobs=False, pen=None, ed=None):
     """Device-RNG mode: the loop itself runs inside libspecdec (sd_spec_generate): per iteration the gamma draft steps,
     the target forward, the accept scan and the resample are enqueued and the stream is waited on once, in native code;
     the interpreter only sees the finished sequence and the per-iteration statistics.  Same loop semantics as the
@@ -217,11 +236,15 @@ def _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T,
     scratch = spec_scratch(draft._session, target._session, target._norm_ws, target._session.max_rows)
     lp = LogprobBlock(dev, [T + gamma + 2]) if logprobs else None
     pb = PenaltyBlock(dev, pen, target._model.cfg.vocab_size, gamma + 1) if pen is not None else None
+    eb = LogitEditBlock(dev, ed, target._model.cfg.vocab_size, gamma + 1, pb.rows if pb is not None else None) if ed is not None else None
     try:
         tick = process_time_ns()
         args = (stream, gamma, sampling, scratch, st, int(random_seed or 0), r_const.data_ptr() if r_const is not None else None,
                 _stream())
-        if pb is not None:
+        if eb is not None:
+            check(lib.sd_spec_generate_edits(*args, lp.block if lp is not None else None, pb.block if pb is not None else None, eb.block),
+                  "sd_spec_generate_edits")
+        elif pb is not None:
             check(lib.sd_spec_generate_penalties(*args, lp.block if lp is not None else None, pb.block), "sd_spec_generate_penalties")
         elif lp is None:
             check(lib.sd_spec_generate(*args), "sd_spec_generate")

@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from .. import _lib
@@ -220,4 +221,37 @@ def apply_penalties(logits_row: torch.Tensor, history, prompt_len: int, repetiti
     if float(theta) != 1.0:
         y = torch.where(c_all > 0, rnd(torch.where(y > 0, y / theta, y * theta)), y)
     y = torch.where(c_out > 0, rnd(rnd(y - rnd(f * c_out.float())) - pi), y)
+    return y.to(dtype)
+
+
+def apply_logit_edits(logits_row: torch.Tensor, out_index: int, eos_token_id, bias=None, allowed_mask=None, min_tokens: int = 0,
+                      dtype_mode=None) -> torch.Tensor:
+    """The per-request logit bias, allowed-token mask and min_tokens as the native loops apply them (sd_edit_rows;
+    include/specdec.h has the text), in pure torch on any device.  ``logits_row`` is one (V,) row as the sampler reads it
+    after the penalties - ``apply_penalties``' result; this function composes after it - that predicts the request's output
+    token number ``out_index`` (0 for the first token behind the prompt).  In this order:
+    1. for every ``{token id: b}`` of ``bias`` (a mapping, or None): ``y = y + b``, one fp32 addition, rounded to the row's
+       16-bit type where it lives in one (``dtype_mode``: None = the row's own dtype, else SD_NORM_DT_* - 0 fp32, 16 bf16,
+       32 fp16); ``b`` is rounded to fp32 once and to nothing else.  An id outside [0, V) is ignored; ids not in ``bias`` keep
+       their bits;
+    2. for every id whose bit is clear in ``allowed_mask`` (uint32 words, bit ``t & 31`` of word ``t >> 5``; None = every id
+       allowed): ``y = -inf``, also where y is NaN or +inf;
+    3. while ``out_index < min_tokens`` and ``eos_token_id >= 0``: ``y[eos_token_id] = -inf`` (``min_tokens`` 0 does nothing).
+    The masks win over everything.  Returns a new row of the same dtype."""
+    assert logits_row.dim() == 1
+    V, dtype, dev = logits_row.shape[0], logits_row.dtype, logits_row.device
+    low = {None: dtype if dtype in (torch.bfloat16, torch.float16) else None, 0: None, 16: torch.bfloat16, 32: torch.float16}[dtype_mode]
+    y = logits_row.float().clone()
+    pairs = [(int(t), float(b)) for t, b in (bias.items() if bias else ()) if 0 <= int(t) < V]
+    if pairs:
+        ids = torch.tensor([t for t, _ in pairs], dtype=torch.int64, device=dev)
+        vals = torch.tensor([b for _, b in pairs], dtype=torch.float32, device=dev)
+        s = y[ids] + vals
+        y[ids] = s.to(low).float() if low is not None else s
+    if allowed_mask is not None:
+        words = torch.as_tensor(np.asarray(allowed_mask).astype(np.int64) & 0xFFFFFFFF, device=dev)
+        t = torch.arange(V, device=dev)
+        y[((words[t >> 5] >> (t & 31)) & 1) == 0] = float("-inf")
+    if eos_token_id is not None and 0 <= int(eos_token_id) < V and int(min_tokens) > 0 and int(out_index) < int(min_tokens):
+        y[int(eos_token_id)] = float("-inf")
     return y.to(dtype)

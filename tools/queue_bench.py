@@ -33,6 +33,11 @@ Decoding workloads, EOS off (every prompt generates its max_len):
            edit costs.  Also sd_penalize_rows alone at V = 32000 with 512-token histories, 8 items x 1 row (a draft step of 8
            streams) and 8 items x 5 rows (their verify): device-event time per launch, and gamma x the first + the second as
            the penalty launches' time per iteration.
+  edits    (--workloads edits --json-out profiles/logit_edits_ab.json) the penalties workload's prompts and call, through
+           speculative_sampling_queue_edits: off; every prompt edited (300 bias entries, an allowed mask of half the vocabulary,
+           min_tokens 8); every prompt penalised (the `all` arm above); both at once - which is still ONE launch per pass.
+           Also sd_edit_rows alone at the shapes above, with the edits, and with the edits and the penalties, next to
+           sd_penalize_rows.
 Both arms run in this process, alternated rep by rep after one warm-up rep of each (which also loads every kernel); a rep is
 the whole call or calls, prefill included, between two device synchronisations on the host clock.  Per arm: tokens/s per rep
 and their median, iterations, passes over the target weights (verify passes plus prompt-only passes; for the batch arm the
@@ -53,11 +58,13 @@ from llmspeculativesampling_amd.config import load_config  # noqa: E402
 from llmspeculativesampling_amd.engine import SpecDecModel, MAX_PREFILL_ROWS  # noqa: E402
 from llmspeculativesampling_amd.harness import synthetic_prompts  # noqa: E402
 from llmspeculativesampling_amd.sampling import (speculative_sampling_batch, speculative_sampling_queue,  # noqa: E402
-                                                 speculative_sampling_queue_requests, speculative_sampling_queue_shared)
+                                                 speculative_sampling_queue_edits, speculative_sampling_queue_requests,
+                                                 speculative_sampling_queue_shared)
 
 SLOTS, GAMMA = 8, 4
 SHARED = 256                                                      # tokens of the `shared` workload's common prefix
 PENALTY = (1.2, 0.5, 0.5)                                         # (repetition, frequency, presence) of `penalties`
+EDIT_BIAS, EDIT_MIN_TOKENS = 300, 8                               # bias entries and min_tokens of `edits`; the mask allows every second id
 MIXED_CLASSES = [(1.0, 20, 0.9), (0.7, 50, 0.95), (1.0, 0, 0.9), (1.3, 5, 0.0)]   # (temperature, top_k, top_p) of `mixed`
 
 
@@ -134,6 +141,40 @@ def penalty_bench(V=32000, hist=512, shapes=((8, 1), (8, 5)), warmup=3, launches
     return dict(V=V, history=hist, launches=out, us_per_iteration_8_streams=GAMMA * out[0]["us"] + out[1]["us"])
 
 
+def edit_bench(V=32000, hist=512, shapes=((8, 1), (8, 5)), warmup=3, launches=50):
+    """sd_edit_rows alone at penalty_bench's shapes: {arm: [{items, rows_per_item, rows, us}]} for the `edits` workload's
+    edits alone and for edits and penalties together, and the launches of one iteration of 8 streams at gamma GAMMA."""
+    from llmspeculativesampling_amd._lib import lib, check, SdLogitEdit, SdLogitEditItem, SdPenalty
+    from llmspeculativesampling_amd.engine import _stream
+    rows_max = max(n * r for n, r in shapes)
+    x = torch.randn(rows_max, V, device="cuda")
+    y = torch.empty_like(x)
+    seqs = [torch.randint(0, V, (hist + 32,), dtype=torch.int32, device="cuda") for _ in range(max(n for n, _ in shapes))]
+    ids = torch.arange(0, V, V // EDIT_BIAS, dtype=torch.int32, device="cuda")[:EDIT_BIAS].contiguous()
+    vals = torch.randn(EDIT_BIAS, device="cuda")
+    mask = torch.full(((V + 31) // 32,), 0x55555555, dtype=torch.int32, device="cuda")
+    out = {}
+    for arm, pen in (("edits", (1.0, 0.0, 0.0)), ("both", PENALTY)):
+        res = []
+        for n, r in shapes:
+            items = (SdLogitEditItem * n)()
+            for i, it in enumerate(items):
+                setattr(it, "in", x[i * r].data_ptr())
+                it.out, it.ld_in, it.ld_out, it.rows = y[i * r].data_ptr(), V, V, r
+                it.seq, it.hist0, it.prompt_len, it.pen = seqs[i].data_ptr(), hist, hist // 2, SdPenalty(*pen)
+                it.edit, it.eos_token_id = SdLogitEdit(ids.data_ptr(), vals.data_ptr(), EDIT_BIAS, mask.data_ptr(), hist), 2
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            for i in range(warmup + launches):
+                if i == warmup:
+                    e0.record()
+                check(lib.sd_edit_rows(items, n, V, 1, _stream()), "sd_edit_rows")
+            e1.record()
+            torch.cuda.synchronize()
+            res.append(dict(items=n, rows_per_item=r, rows=n * r, us=e0.elapsed_time(e1) * 1e3 / launches))
+        out[arm] = dict(launches=res, us_per_iteration_8_streams=GAMMA * res[0]["us"] + res[1]["us"])
+    return dict(V=V, history=hist, bias_entries=EDIT_BIAS, **out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--draft", default="llama-68m")
@@ -170,6 +211,11 @@ def main():
         work["penalties"] = (ps, [128] * 8)
         out["penalize_rows"] = penalty_bench()
         print(json.dumps({"penalize_rows": out["penalize_rows"]}), flush=True)
+    if "edits" in a.workloads:
+        ps = [torch.from_numpy(np.random.default_rng(100 + i).integers(3, tcfg.vocab_size, size=(1, 128))).cuda() for i in range(8)]
+        work["edits"] = (ps, [128] * 8)
+        out["penalize_rows"], out["edit_rows"] = penalty_bench(), edit_bench()
+        print(json.dumps({"penalize_rows": out["penalize_rows"], "edit_rows": out["edit_rows"]}), flush=True)
     if "copy" in a.workloads:
         out["copy_kv"] = copy_bench(tm)
         print(json.dumps({"copy_kv": out["copy_kv"]}), flush=True)
@@ -230,7 +276,23 @@ def main():
             return outs, dict(iterations=t["iterations"], target_passes=t["target_passes"], extra_passes=t["extra_passes"],
                               mean_streams=float(np.mean([v[2] for v in t["verify"]])), penalised_prompts=len(on))
 
+        def edited(seed0, edits, pens):
+            t = {}
+            V = tcfg.vocab_size
+            more = dict(repetition_penalty=PENALTY[0], frequency_penalty=PENALTY[1], presence_penalty=PENALTY[2]) if pens else {}
+            if edits:
+                rng = np.random.default_rng(9)
+                more.update(logit_bias={int(i): float(b) for i, b in zip(rng.choice(V, size=EDIT_BIAS, replace=False), rng.standard_normal(EDIT_BIAS))},
+                            allowed_token_ids=list(range(0, V, 2)), min_tokens=EDIT_MIN_TOKENS)
+            outs = speculative_sampling_queue_edits(prompts, dm, tm, -1, None, budgets, seeds=[seed0 + i for i in range(len(prompts))],
+                                                    slots=SLOTS, _timing=t, **more, **kw)
+            return outs, dict(iterations=t["iterations"], target_passes=t["target_passes"], extra_passes=t["extra_passes"],
+                              mean_streams=float(np.mean([v[2] for v in t["verify"]])), edited=bool(edits), penalised=bool(pens))
+
         arms = {"queue": queue, "batch": batch}
+        if name == "edits":
+            arms = {"off": lambda seed0: edited(seed0, False, False), "edits": lambda seed0: edited(seed0, True, False),
+                    "penalties": lambda seed0: edited(seed0, False, True), "both": lambda seed0: edited(seed0, True, True)}
         if name == "penalties":
             arms = {"off": lambda seed0: requests(seed0, ()), "all": lambda seed0: requests(seed0, range(len(prompts))),
                     "half": lambda seed0: requests(seed0, range(0, len(prompts), 2))}
@@ -265,6 +327,13 @@ def main():
                 res[f"{arm}_over_off_tokens_per_s"] = res[arm]["tokens_per_s_median"] / res["off"]["tokens_per_s_median"]
                 res[f"{arm}_ms_per_iteration_over_off"] = 1e3 * sum(lens_b) * (
                     1 / res[arm]["tokens_per_s_median"] / res[arm]["iterations"] - 1 / res["off"]["tokens_per_s_median"] / res["off"]["iterations"])
+        elif name == "edits":
+            res["penalty"] = dict(zip(("repetition", "frequency", "presence"), PENALTY))
+            res["edit"] = dict(bias_entries=EDIT_BIAS, allowed="every second id", min_tokens=EDIT_MIN_TOKENS)
+            for arm in ("edits", "penalties", "both"):
+                res[f"{arm}_over_off_tokens_per_s"] = res[arm]["tokens_per_s_median"] / res["off"]["tokens_per_s_median"]
+                res[f"{arm}_ms_per_iteration"] = 1e3 * sum(lens_b) / res[arm]["tokens_per_s_median"] / res[arm]["iterations"]
+            res["off_ms_per_iteration"] = 1e3 * sum(lens_b) / res["off"]["tokens_per_s_median"] / res["off"]["iterations"]
         elif name == "shared":
             res["shared_over_plain_tokens_per_s"] = res[f"shared_prefix_{SHARED}"]["tokens_per_s_median"] / \
                 res["shared_prefix_0"]["tokens_per_s_median"]
