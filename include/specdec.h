@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define SD_ABI_VERSION 6
+#define SD_ABI_VERSION 7
 
 typedef enum {
     SD_OK = 0,
@@ -535,7 +535,14 @@ int sd_batch_prefill(const sd_batch_item *items, int n_items, void *stream);
  *   ends at T tokens, at a new EOS (more than ori_eos_cnt in all) or after max_iters iterations.  All written back on every way
  *   out, also after an error.  Per iteration i < n_iters: acc_len_out[i], p_at_out / q_at_out (the accept ratios' operands),
  *   draft_ms_out / target_ms_out[i]; any of the five may be NULL.  err: 0, 1 = 'prob error', 2 = 'norm logits error'.
- * sd_ar_log: host arrays of max_steps_log entries (may be NULL): HIP-event time of each step, streams in it.  Out: n_steps, err. */
+ * sd_ar_log: host arrays of max_steps_log entries (may be NULL): HIP-event time of each step, streams in it.  Out: n_steps, err.
+ * sd_loop_opts: what a call may carry per request, as the LAST argument of every loop entry: per-stream sampling parameters,
+ *   per-token log-probabilities, penalties and logit edits.  32 bytes, defined below behind its members' types, each of which
+ *   has its contract there.  Every member may be NULL, and a NULL `opts` is a block of four NULLs: the call is then, launch for
+ *   launch, the loop without the feature.  A member is checked behind the entry's own refusals, in the members' order
+ *   (row_params, logprobs, penalties, edits), with SD_ERR_INVALID before anything is written or launched; the text names the
+ *   entry that was called, then the member. */
+struct sd_loop_opts;
 typedef struct { float temperature; int32_t top_k; float top_p; int32_t V; long ld; int32_t eos_token_id; } sd_sampling;
 typedef struct { float *logits; long ld_logits; int32_t norm_mode; } sd_head_scratch;
 typedef struct {
@@ -561,9 +568,11 @@ typedef struct { float *step_ms_out; int32_t *step_streams_out; int32_t max_step
  * seq->target_ms_out is set.  Norm modes: scratch->draft / target.norm_mode; the residual runs in the target's mode when both
  * are equal, else in fp32.  Refused with SD_ERR_INVALID before anything is written or launched, in this order: a NULL block or
  * a NULL pointer in dev, seq->host_seq or either scratch->*.logits; gamma outside 1..16; random_seed without r_const;
- * temperature 0; a norm_workspace with max_rows_per_forward < gamma + 1; then sampling->V differing from a model's vocabulary. */
+ * temperature 0; a norm_workspace with max_rows_per_forward < gamma + 1; then sampling->V differing from a model's vocabulary;
+ * then opts: the loop samples with sampling's own triple, so a non-NULL opts->row_params is refused. */
 int sd_spec_generate(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling, const sd_spec_scratch *scratch,
-                     sd_seq_state *seq, uint64_t random_seed, const float *r_const, void *stream);
+                     sd_seq_state *seq, uint64_t random_seed, const float *r_const, void *stream,
+                     const struct sd_loop_opts *opts);
 /* The stream-batched loop (throughput mode) without the interpreter between iterations: up to 16
  * independent streams decode in lock-step - every draft step one sd_batch_forward + sd_norm_batch over the active
  * streams, every verify one target pass per max_rows_per_forward / (gamma + 1) streams, then sd_accept_batch, one copy of
@@ -591,7 +600,7 @@ typedef struct {
 } sd_batch_stream;
 int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
                            uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log,
-                           void *stream);
+                           void *stream, const struct sd_loop_opts *opts);
 /* Continuous batching for the lock-step loop: any number of prompts share `n_slots` (1..16) slots.  A slot is an
  * sd_batch_stream of which the caller fills the device side only - the two sessions, the token buffer (slot_cap ints), the
  * probability arenas, the error words and the consecutive result blocks; the arenas and sessions hold slot_cap positions,
@@ -608,8 +617,16 @@ int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, c
  * Per prompt: its tokens (pinned host, L ints), L, the length T to reach, the EOS count of the prompt, the seed, the host
  * token buffer (>= T + gamma + 1 ints, holding the prompt) and the per-iteration logs; out: len, calls, admit_iter (the
  * first iteration it decodes in) and finish_iter (its last; both the boundary's iteration number for a prompt that never
- * decodes).  passes_out (4 ints, may be NULL): passes over the target weights, passes over the draft weights, target passes
- * that carried prompt rows only, and how many of those were sd_batch_prefill passes. */
+ * decodes).
+ * Prompts that start with the same tokens: the donors are sessions of the draft and the target model that hold positions
+ * [0, shared_rows) of those tokens - prefilled by the caller on `stream` - and stay untouched.  A prompt that takes a slot then
+ * starts with both cache lengths at c = min(shared_rows, L - 1), not at 0: those rows reach the slot's arenas through one
+ * sd_session_copy_kv launch (below) per model for all prompts admitted at that iteration boundary, on `stream`, ahead of the
+ * iteration's forwards; its rows [c, L-1) then ride the passes as described (c == L-1: it decodes from that boundary on).
+ * Without a shared prefix the donors are NULL and shared_rows is 0.
+ * passes_out (6 ints, may be NULL): passes over the target weights, passes over the draft weights, target passes that carried
+ * prompt rows only, how many of those were sd_batch_prefill passes, the target rows forwarded for prompts inside the call, and
+ * the KV rows copied per model, summed over the prompts. */
 typedef struct {
     const int32_t *tokens;
     int32_t L, T, ori_eos_cnt;
@@ -622,7 +639,8 @@ typedef struct {
 int sd_spec_queue_generate(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
                            int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
                            const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log, int *passes_out,
-                           void *stream);
+                           void *stream, sd_session *donor_draft, sd_session *donor_target, int shared_rows,
+                           const struct sd_loop_opts *opts);
 /* The passes of one step of that loop (host only; the function the loop calls, once per draft step and once per verify).
  * Inputs: the rows one pass may hold; the logit rows a pass may hold once not every row is one (sd_batch_forward: 64); the
  * active streams' row counts, in order (n_act <= 16), and whether those rows are all logit rows (a verify) or one per
@@ -655,34 +673,6 @@ typedef struct {
     int32_t lo, hi;
 } sd_kv_copy_item;
 int sd_session_copy_kv(const sd_session *src, const sd_kv_copy_item *items, int n_items, void *stream);
-/* sd_spec_queue_generate for prompts that start with the same tokens.  The donors are sessions of the draft and the target
- * model that hold positions [0, shared_rows) of those tokens - prefilled by the caller on `stream` - and stay untouched.  A
- * prompt that takes a slot starts with both cache lengths at c = min(shared_rows, L - 1), not at 0: those rows reach the
- * slot's arenas through one sd_session_copy_kv launch per model for all prompts admitted at that iteration boundary, on
- * `stream`, ahead of the iteration's forwards; its rows [c, L-1) then ride the passes as sd_spec_queue_generate describes
- * (c == L-1: it decodes from that boundary on).  Null donors with shared_rows 0 give sd_spec_queue_generate itself.
- * passes_out (6 ints, may be NULL): the 4 of sd_spec_queue_generate, then the target rows forwarded for prompts inside the
- * call, then the KV rows copied per model, summed over the prompts. */
-int sd_spec_queue_generate_shared(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
-                                  int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
-                                  const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log, int *passes_out,
-                                  void *stream, sd_session *donor_draft, sd_session *donor_target, int shared_rows);
-/* Per-request sampling parameters in the two lock-step loops.  stream_params[i] is what stream i of
- * sd_spec_batch_generate samples with; prompt_params[k] is what prompt k of the queue samples with in whichever slot it
- * decodes, so a slot changes parameters when it changes hands.  With an array, sampling->temperature / top_k / top_p are
- * not read (V, ld and eos_token_id are); every draft and verify row is normalised with its stream's triple through
- * sd_norm_batch_rows' launch, and the draft head leaves tile maxima in the passes whose sampled rows all have
- * 1 <= top_k <= 64 and temperature > 0.  Each stream still runs exactly sd_spec_generate's algorithm with its own triple.
- * With a NULL array the calls are sd_spec_batch_generate and sd_spec_queue_generate_shared themselves.  Refused with
- * SD_ERR_INVALID before anything is written or launched, naming the index: a temperature of 0, a negative top_k. */
-int sd_spec_batch_generate_rows(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
-                                uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log,
-                                void *stream, const sd_row_sampling *stream_params);
-int sd_spec_queue_generate_rows(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
-                                int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
-                                const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log, int *passes_out,
-                                void *stream, sd_session *donor_draft, sd_session *donor_target, int shared_rows,
-                                const sd_row_sampling *prompt_params);
 /* The whole loop of multi_speculative_sampling(strategy="iid") (speculative_sampling.py:1379-1716) for the device-RNG mode,
  * no interpreter between iterations.  `width` replicas, each with its own sessions, token buffer and probability arenas;
  * per iteration: gamma draft steps (one pass over the draft weights for all replicas each, sampled straight into
@@ -731,7 +721,8 @@ int sd_spec_multi_generate(const sd_multi_replica *reps, int width, int gamma, i
  * word, looked at first: the reference normalises before it samples, and the fused sampler sets both words on a row it
  * cannot normalise), 1 = 'prob error' (a sample word alone); log->n_steps counts that step.
  * Limits: n_streams in 1..16 and <= sd_model_max_pass_rows, one model behind all sessions; a violation returns
- * SD_ERR_INVALID before anything is launched. */
+ * SD_ERR_INVALID before anything is launched.  Behind them opts: every stream samples with sampling's own triple, so a non-NULL
+ * opts->row_params is refused. */
 typedef struct {
     sd_session *session;
     int32_t *seq;
@@ -744,7 +735,8 @@ typedef struct {
 } sd_ar_stream;
 size_t sd_ar_block_bytes(int n_streams);
 int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
-                         void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream);
+                         void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream,
+                         const struct sd_loop_opts *opts);
 
 /* ---- Per-token target log-probabilities.  For a token t that a loop emits at position i, the score is
  * x[t] - log sum_v exp(x[v]) in fp32, x = the target model's raw logit row for position i - 1: rounded to the weights'
@@ -771,8 +763,8 @@ int sd_token_logprobs(const sd_logprob_item *items, int n_items, int V, int mode
 /* sd_logprob_block: what a loop needs to return those scores with its tokens; caller-owned like the blocks above.  dev
  * (device) and host (pinned host): 16 x 17 floats each, stream (slot) i's slice at i * 17.  logprob_out[k]: a host float array
  * per stream - per prompt in the queue - with the capacity of that stream's host token buffer; entry j is the score of the
- * j-th token the call emitted for it (position L + j, L = its length on entry).  The _logprobs entries take exactly what the
- * widest entry of their loop takes, plus the block; a NULL block is that entry itself, launch for launch.  With a block, per
+ * j-th token the call emitted for it (position L + j, L = its length on entry).  It is member `logprobs` of
+ * sd_loop_opts in all four loops; a NULL member is the loop without scores, launch for launch.  With a block, per
  * iteration or step: ONE sd_token_logprobs launch over all active streams behind the accept / resample launch (behind the
  * sampler in the autoregressive loop, one row per stream at seq[len]), ONE more async copy of the float slices beside the
  * copy of the result blocks, ahead of the one wait; after it the stream's n_accepted + 1 floats are appended where its tokens
@@ -782,21 +774,6 @@ int sd_token_logprobs(const sd_logprob_item *items, int n_items, int V, int mode
  * scratch->target.logits in the lock-step loops, the head's own slab in the other two.  Refused with SD_ERR_INVALID behind
  * the entry's own refusals, before anything is launched: a NULL dev, host or logprob_out, or a NULL array in it. */
 typedef struct { float *dev, *host; float **logprob_out; } sd_logprob_block;
-int sd_spec_generate_logprobs(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling, const sd_spec_scratch *scratch,
-                              sd_seq_state *seq, uint64_t random_seed, const float *r_const, void *stream,
-                              const sd_logprob_block *logprobs);
-int sd_spec_batch_generate_logprobs(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
-                                    uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
-                                    sd_lockstep_log *log, void *stream, const sd_row_sampling *stream_params,
-                                    const sd_logprob_block *logprobs);
-int sd_spec_queue_generate_logprobs(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
-                                    int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
-                                    const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log, int *passes_out,
-                                    void *stream, sd_session *donor_draft, sd_session *donor_target, int shared_rows,
-                                    const sd_row_sampling *prompt_params, const sd_logprob_block *logprobs);
-int sd_ar_batch_generate_logprobs(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
-                                  void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream,
-                                  const sd_logprob_block *logprobs);
 
 /* ---- Per-request repetition, frequency and presence penalties.  A logit row at position pos predicts token pos + 1; its
  * history is seq[0 .. pos], and the stream's prompt is the P tokens it held when the call started.  For a token id t, c_all(t)
@@ -833,8 +810,8 @@ int sd_penalize_rows(const sd_penalty_item *items, int n_items, int V, int mode,
  * floats (ld >= V) that holds the logit rows of the loop's largest pass: gamma + 1 in the single-stream loop, the streams in
  * the autoregressive loop, min(rows per target pass, streams x (gamma + 1)) in the lock-step loops.  A 16-byte aligned slab
  * with 4 | ld keeps the norm launch on its two-kernel path.  params[k] belongs to stream k - to prompt k in the queue, where a
- * slot changes penalties when it changes hands.  The _penalties entries take exactly what the _logprobs entries take
- * (logprobs may be NULL), plus the block; a NULL block, or one whose params are all neutral, is that entry itself, launch for
+ * slot changes penalties when it changes hands.  It is member `penalties` of sd_loop_opts in all four
+ * loops; a NULL member, or a block whose params are all neutral, is the loop without penalties, launch for
  * launch.  Otherwise every pass - of a draft step, of the verify, of an autoregressive step - that holds at least one
  * penalised active stream gets ONE sd_penalize_rows launch between the forward and the norm launch, over all its logit rows,
  * one item per stream, hist0 = the position of the stream's first logit row + 1, prompt_len = its length on entry
@@ -846,22 +823,6 @@ int sd_penalize_rows(const sd_penalty_item *items, int n_items, int V, int mode,
  * SD_ERR_INVALID behind the entry's own refusals, before anything is launched, naming the index: a NULL rows or params,
  * ld < V, max_rows too small, repetition <= 0 or a parameter that is not finite. */
 typedef struct { float *rows; long ld; int32_t max_rows; const sd_penalty *params; } sd_penalty_block;
-int sd_spec_generate_penalties(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling, const sd_spec_scratch *scratch,
-                               sd_seq_state *seq, uint64_t random_seed, const float *r_const, void *stream,
-                               const sd_logprob_block *logprobs, const sd_penalty_block *penalties);
-int sd_spec_batch_generate_penalties(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
-                                     uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
-                                     sd_lockstep_log *log, void *stream, const sd_row_sampling *stream_params,
-                                     const sd_logprob_block *logprobs, const sd_penalty_block *penalties);
-int sd_spec_queue_generate_penalties(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
-                                     int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
-                                     const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log, int *passes_out,
-                                     void *stream, sd_session *donor_draft, sd_session *donor_target, int shared_rows,
-                                     const sd_row_sampling *prompt_params, const sd_logprob_block *logprobs,
-                                     const sd_penalty_block *penalties);
-int sd_ar_batch_generate_penalties(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
-                                   void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream,
-                                   const sd_logprob_block *logprobs, const sd_penalty_block *penalties);
 
 /* ---- Per-request logit bias, allowed-token mask and min_tokens: the request fields that restrict what may be sampled.  A
  * logit row at position pos predicts token pos + 1; with P the stream's prompt length on entry, that token is output number
@@ -906,9 +867,10 @@ typedef struct {
 int sd_edit_rows(const sd_logit_edit_item *items, int n_items, int V, int mode, void *stream);
 /* sd_logit_edit_block: what a loop needs to sample from edited rows; caller-owned.  rows / ld / max_rows: a slab sized as
  * sd_penalty_block's; params[k] belongs to stream k - to prompt k in the queue, where a slot changes its edits when it changes
- * hands.  The _edits entries take exactly what the _penalties entries take (logprobs and penalties may be NULL), plus the
- * block; the EOS id is sampling->eos_token_id.  A NULL block, or one whose params are all neutral, is the _penalties entry
- * itself, launch for launch.  Otherwise every pass - of a draft step, of the verify, of an autoregressive step - that holds at
+ * hands.  It is member `edits` of sd_loop_opts in all four loops (logprobs and penalties may be NULL or set beside it);
+ * the EOS id is sampling->eos_token_id.  A NULL member, or a block whose params are all neutral, is the call with the other
+ * members alone, launch for launch.
+ * Otherwise every pass - of a draft step, of the verify, of an autoregressive step - that holds at
  * least one active stream that is penalised or edited gets ONE sd_edit_rows launch between the forward and the norm launch (at
  * most one, whether the pass holds penalised streams, edited streams or both), over all its logit rows, one item per stream;
  * it writes the edit block's slab, the penalty block's slab is not touched, and the pass follows the rules of a penalised pass:
@@ -920,24 +882,19 @@ int sd_edit_rows(const sd_logit_edit_item *items, int n_items, int V, int mode, 
  * refusals, before anything is launched, naming the index: a NULL rows or params, ld < V, max_rows too small, n_bias outside
  * 0..SD_EDIT_MAX_BIAS, n_bias > 0 with a NULL array, min_tokens < 0. */
 typedef struct { float *rows; long ld; int32_t max_rows; const sd_logit_edit *params; } sd_logit_edit_block;
-int sd_spec_generate_edits(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling, const sd_spec_scratch *scratch,
-                           sd_seq_state *seq, uint64_t random_seed, const float *r_const, void *stream,
-                           const sd_logprob_block *logprobs, const sd_penalty_block *penalties, const sd_logit_edit_block *edits);
-int sd_spec_batch_generate_edits(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
-                                 uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
-                                 sd_lockstep_log *log, void *stream, const sd_row_sampling *stream_params,
-                                 const sd_logprob_block *logprobs, const sd_penalty_block *penalties,
-                                 const sd_logit_edit_block *edits);
-int sd_spec_queue_generate_edits(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
-                                 int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
-                                 const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log, int *passes_out,
-                                 void *stream, sd_session *donor_draft, sd_session *donor_target, int shared_rows,
-                                 const sd_row_sampling *prompt_params, const sd_logprob_block *logprobs,
-                                 const sd_penalty_block *penalties, const sd_logit_edit_block *edits);
-int sd_ar_batch_generate_edits(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
-                               void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream,
-                               const sd_logprob_block *logprobs, const sd_penalty_block *penalties,
-                               const sd_logit_edit_block *edits);
+/* The loops' optional block (the argument blocks above say how it is read).  row_params: per-request sampling parameters in
+ * the two lock-step loops, NULL in the other two.  row_params[i] is what stream i of sd_spec_batch_generate samples with, and
+ * what prompt i of sd_spec_queue_generate samples with in whichever slot it decodes, so a slot changes parameters when it
+ * changes hands.  With an array, sampling->temperature / top_k / top_p are not read (V, ld and eos_token_id are); every draft
+ * and verify row is normalised with its stream's triple through sd_norm_batch_rows' launch, and the draft head leaves tile
+ * maxima in the passes whose sampled rows all have 1 <= top_k <= 64 and temperature > 0.  Each stream still runs exactly
+ * sd_spec_generate's algorithm with its own triple.  Refused, naming the index: a temperature of 0, a negative top_k. */
+typedef struct sd_loop_opts {
+    const sd_row_sampling *row_params;  /* lock-step loops only: per stream / per prompt */
+    const sd_logprob_block *logprobs;
+    const sd_penalty_block *penalties;
+    const sd_logit_edit_block *edits;
+} sd_loop_opts;
 
 /* ------------------------------------------------------------------------------------------
  * Tensor parallelism of one decoder over the GPUs of a node (BASELINE config 5: Llama-2-70b, TP = 8 over xGMI).

@@ -162,6 +162,11 @@ class SdLogitEditBlock(C.Structure):
     _fields_ = [("rows", C.c_void_p), ("ld", C.c_long), ("max_rows", C.c_int32), ("params", C.POINTER(SdLogitEdit))]
 
 
+class SdLoopOpts(C.Structure):                          # the loops' optional last argument; every member may be NULL
+    _fields_ = [("row_params", C.POINTER(SdRowSampling)), ("logprobs", C.POINTER(SdLogprobBlock)),
+                ("penalties", C.POINTER(SdPenaltyBlock)), ("edits", C.POINTER(SdLogitEditBlock))]
+
+
 SD_EDIT_MAX_BIAS = 1024                                  # bias entries per request
 LOGPROB_SLICE, LOGPROB_STREAMS = 17, 16                  # sd_logprob_block: 16 streams x 17 floats, device and pinned host
 
@@ -211,7 +216,8 @@ C_STRUCTS = {"sd_accept_result": SdAcceptResult, "sd_norm_row": SdNormRow, "sd_r
              "sd_ar_log": SdArLog, "sd_batch_item": SdBatchItem,
              "sd_logprob_item": SdLogprobItem, "sd_logprob_block": SdLogprobBlock, "sd_penalty": SdPenalty,
              "sd_penalty_item": SdPenaltyItem, "sd_penalty_block": SdPenaltyBlock, "sd_logit_edit": SdLogitEdit,
-             "sd_logit_edit_item": SdLogitEditItem, "sd_logit_edit_block": SdLogitEditBlock, "sd_model_config": SdModelConfig,
+             "sd_logit_edit_item": SdLogitEditItem, "sd_logit_edit_block": SdLogitEditBlock, "sd_loop_opts": SdLoopOpts,
+             "sd_model_config": SdModelConfig,
              "sd_gemm_route_info": SdGemmRouteInfo, "sd_model_weights": SdModelWeights}
 
 # every symbol include/specdec.h declares: (name, restype, argtypes)
@@ -278,52 +284,21 @@ SYMBOLS = [
     ("sd_norm_probs_debug", _I, [_VP, _I, _I, _L, _F, _I, _F, _I, _VP, _L, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _U64, _U64,
                                  _VP, _VP, _VP]),                                     # test hook
     ("sd_accept_resample_batch", _I, [C.POINTER(SdAcceptItem), _I, _L, _I, _I, _I, _VPP, _VP]),   # internal
-    ("sd_spec_batch_generate", _I, [_P(SdBatchStream), _I, _I, _P(SdSampling), _U64, _VP, _P(SdSpecScratch), _P(SdLockstepLog), _VP]),
+    ("sd_spec_batch_generate", _I, [_P(SdBatchStream), _I, _I, _P(SdSampling), _U64, _VP, _P(SdSpecScratch), _P(SdLockstepLog), _VP,
+                                    _P(SdLoopOpts)]),
     ("sd_spec_queue_generate", _I, [_P(SdBatchStream), _I, _I, _P(SdQueuePrompt), _I, _I, _I, _P(SdSampling), _U64, _VP,
-                                    _P(SdSpecScratch), _P(SdLockstepLog), _VP, _VP]),
-    ("sd_spec_queue_generate_shared", _I, [_P(SdBatchStream), _I, _I, _P(SdQueuePrompt), _I, _I, _I, _P(SdSampling), _U64, _VP,
-                                           _P(SdSpecScratch), _P(SdLockstepLog), _VP, _VP, _VP, _VP, _I]),
-    ("sd_spec_batch_generate_rows", _I, [_P(SdBatchStream), _I, _I, _P(SdSampling), _U64, _VP, _P(SdSpecScratch), _P(SdLockstepLog),
-                                         _VP, _P(SdRowSampling)]),
-    ("sd_spec_queue_generate_rows", _I, [_P(SdBatchStream), _I, _I, _P(SdQueuePrompt), _I, _I, _I, _P(SdSampling), _U64, _VP,
-                                         _P(SdSpecScratch), _P(SdLockstepLog), _VP, _VP, _VP, _VP, _I, _P(SdRowSampling)]),
+                                    _P(SdSpecScratch), _P(SdLockstepLog), _VP, _VP, _VP, _VP, _I, _P(SdLoopOpts)]),
     ("sd_session_copy_kv", _I, [_VP, C.POINTER(SdKvCopyItem), _I, _VP]),
     ("sd_spec_queue_plan", _I, [_I, _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(C.c_int32), _I, _I, _I, C.POINTER(SdQueuePass), _I,
                                 C.POINTER(SdQueueChunk), _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    ("sd_spec_generate", _I, [_P(SdSpecStream), _I, _P(SdSampling), _P(SdSpecScratch), _P(SdSeqState), _U64, _VP, _VP]),
+    ("sd_spec_generate", _I, [_P(SdSpecStream), _I, _P(SdSampling), _P(SdSpecScratch), _P(SdSeqState), _U64, _VP, _VP,
+                              _P(SdLoopOpts)]),
     ("sd_ar_block_bytes", C.c_size_t, [_I]),
-    ("sd_ar_batch_generate", _I, [_P(SdArStream), _I, _P(SdSampling), _P(SdHeadScratch), _VP, _VP, _VP, _P(SdArLog), _VP]),
+    ("sd_ar_batch_generate", _I, [_P(SdArStream), _I, _P(SdSampling), _P(SdHeadScratch), _VP, _VP, _VP, _P(SdArLog), _VP,
+                                  _P(SdLoopOpts)]),
     ("sd_token_logprobs", _I, [_P(SdLogprobItem), _I, _I, _I, _VP]),
-    ("sd_spec_generate_logprobs", _I, [_P(SdSpecStream), _I, _P(SdSampling), _P(SdSpecScratch), _P(SdSeqState), _U64, _VP, _VP,
-                                       _P(SdLogprobBlock)]),
-    ("sd_spec_batch_generate_logprobs", _I, [_P(SdBatchStream), _I, _I, _P(SdSampling), _U64, _VP, _P(SdSpecScratch),
-                                             _P(SdLockstepLog), _VP, _P(SdRowSampling), _P(SdLogprobBlock)]),
-    ("sd_spec_queue_generate_logprobs", _I, [_P(SdBatchStream), _I, _I, _P(SdQueuePrompt), _I, _I, _I, _P(SdSampling), _U64, _VP,
-                                             _P(SdSpecScratch), _P(SdLockstepLog), _VP, _VP, _VP, _VP, _I, _P(SdRowSampling),
-                                             _P(SdLogprobBlock)]),
-    ("sd_ar_batch_generate_logprobs", _I, [_P(SdArStream), _I, _P(SdSampling), _P(SdHeadScratch), _VP, _VP, _VP, _P(SdArLog), _VP,
-                                           _P(SdLogprobBlock)]),
     ("sd_penalize_rows", _I, [_P(SdPenaltyItem), _I, _I, _I, _VP]),
-    ("sd_spec_generate_penalties", _I, [_P(SdSpecStream), _I, _P(SdSampling), _P(SdSpecScratch), _P(SdSeqState), _U64, _VP, _VP,
-                                        _P(SdLogprobBlock), _P(SdPenaltyBlock)]),
-    ("sd_spec_batch_generate_penalties", _I, [_P(SdBatchStream), _I, _I, _P(SdSampling), _U64, _VP, _P(SdSpecScratch),
-                                              _P(SdLockstepLog), _VP, _P(SdRowSampling), _P(SdLogprobBlock), _P(SdPenaltyBlock)]),
-    ("sd_spec_queue_generate_penalties", _I, [_P(SdBatchStream), _I, _I, _P(SdQueuePrompt), _I, _I, _I, _P(SdSampling), _U64, _VP,
-                                              _P(SdSpecScratch), _P(SdLockstepLog), _VP, _VP, _VP, _VP, _I, _P(SdRowSampling),
-                                              _P(SdLogprobBlock), _P(SdPenaltyBlock)]),
-    ("sd_ar_batch_generate_penalties", _I, [_P(SdArStream), _I, _P(SdSampling), _P(SdHeadScratch), _VP, _VP, _VP, _P(SdArLog), _VP,
-                                            _P(SdLogprobBlock), _P(SdPenaltyBlock)]),
     ("sd_edit_rows", _I, [_P(SdLogitEditItem), _I, _I, _I, _VP]),
-    ("sd_spec_generate_edits", _I, [_P(SdSpecStream), _I, _P(SdSampling), _P(SdSpecScratch), _P(SdSeqState), _U64, _VP, _VP,
-                                    _P(SdLogprobBlock), _P(SdPenaltyBlock), _P(SdLogitEditBlock)]),
-    ("sd_spec_batch_generate_edits", _I, [_P(SdBatchStream), _I, _I, _P(SdSampling), _U64, _VP, _P(SdSpecScratch),
-                                          _P(SdLockstepLog), _VP, _P(SdRowSampling), _P(SdLogprobBlock), _P(SdPenaltyBlock),
-                                          _P(SdLogitEditBlock)]),
-    ("sd_spec_queue_generate_edits", _I, [_P(SdBatchStream), _I, _I, _P(SdQueuePrompt), _I, _I, _I, _P(SdSampling), _U64, _VP,
-                                          _P(SdSpecScratch), _P(SdLockstepLog), _VP, _VP, _VP, _VP, _I, _P(SdRowSampling),
-                                          _P(SdLogprobBlock), _P(SdPenaltyBlock), _P(SdLogitEditBlock)]),
-    ("sd_ar_batch_generate_edits", _I, [_P(SdArStream), _I, _P(SdSampling), _P(SdHeadScratch), _VP, _VP, _VP, _P(SdArLog), _VP,
-                                        _P(SdLogprobBlock), _P(SdPenaltyBlock), _P(SdLogitEditBlock)]),
     ("sd_batch_forward", _I, [C.POINTER(SdBatchItem), _I, _VP, _L, _VP]),
     ("sd_batch_prefill", _I, [C.POINTER(SdBatchItem), _I, _VP]),
     ("sd_tp_unique_id", _I, [_VP]),

@@ -165,7 +165,7 @@ extern "C" int sd_token_logprobs(const sd_logprob_item *items, int n_items, int 
 }
 
 enum { LP_SLICE = LOGPROB_MAX_ROWS };                             // floats per stream in sd_logprob_block.dev / host
-// what the _logprobs entries refuse in their block (behind the entry's own refusals): n arrays, one per stream / prompt
+// what the loops refuse in a logprob block (behind the entry's own refusals): n arrays, one per stream / prompt
 static int check_logprob_block(const char *who, const sd_logprob_block *lp, int n) {
     SD_REQUIRE(lp->dev && lp->host && lp->logprob_out, "%s: logprobs: null pointer", who);
     for (int i = 0; i < n; ++i) SD_REQUIRE(lp->logprob_out[i], "%s: logprobs: logprob_out[%d] is null", who, i);
@@ -193,30 +193,39 @@ static int check_penalty(const char *who, const char *what, int i, const sd_pena
     return SD_OK;
 }
 
+// What sd_penalize_rows and sd_edit_rows share: the call's own refusals ...
+static int check_row_edit_call(const char *who, const void *items, int n_items, int V, int mode) {
+    SD_REQUIRE(items, "%s: null argument", who);
+    SD_REQUIRE(n_items >= 1 && n_items <= PEN_MAX_ITEMS, "%s: n_items %d outside 1..%d", who, n_items, PEN_MAX_ITEMS);
+    SD_REQUIRE(V >= 1 && V <= 65536 && (mode & 3) != 3, "%s: V %d outside 1..65536, or both rounding bits (mode %#x)", who, V, mode);
+    return SD_OK;
+}
+// ... and item i, refused or put into its column of the table (sd_logit_edit_item starts with sd_penalty_item's fields)
+template <class Item>
+static int penalty_tab_item(const char *who, PenaltyTab &t, int i, const Item &it, int V, int *max_rows) {
+    SD_REQUIRE(it.in && it.out && it.seq, "%s: item %d: null argument", who, i);
+    SD_REQUIRE(it.rows >= 1 && it.rows <= PEN_MAX_ROWS, "%s: item %d: rows %d outside 1..%d", who, i, it.rows, PEN_MAX_ROWS);
+    SD_REQUIRE(it.ld_in >= V && it.ld_out >= V, "%s: item %d: ld %ld / %ld < V %d", who, i, it.ld_in, it.ld_out, V);
+    SD_REQUIRE(it.hist0 >= 1 && it.prompt_len >= 0, "%s: item %d: hist0 %d < 1 or prompt_len %d < 0", who, i, it.hist0, it.prompt_len);
+    if (int rc = check_penalty(who, "item", i, it.pen); rc != SD_OK) return rc;
+    t.in[i] = it.in; t.out[i] = it.out; t.seq[i] = it.seq; t.ld_in[i] = it.ld_in; t.ld_out[i] = it.ld_out;
+    t.rows[i] = it.rows; t.hist0[i] = it.hist0; t.prompt_len[i] = it.prompt_len;
+    t.repetition[i] = it.pen.repetition; t.frequency[i] = it.pen.frequency; t.presence[i] = it.pen.presence;
+    *max_rows = std::max(*max_rows, (int)it.rows);
+    return SD_OK;
+}
+
 extern "C" int sd_penalize_rows(const sd_penalty_item *items, int n_items, int V, int mode, void *stream) {
-    SD_REQUIRE(items, "sd_penalize_rows: null argument");
-    SD_REQUIRE(n_items >= 1 && n_items <= PEN_MAX_ITEMS, "sd_penalize_rows: n_items %d outside 1..%d", n_items, PEN_MAX_ITEMS);
-    SD_REQUIRE(V >= 1 && V <= 65536 && (mode & 3) != 3, "sd_penalize_rows: V %d outside 1..65536, or both rounding bits (mode %#x)", V, mode);
+    if (int rc = check_row_edit_call("sd_penalize_rows", items, n_items, V, mode); rc != SD_OK) return rc;
     PenaltyTab t = {};
     int max_rows = 0;
-    for (int i = 0; i < n_items; ++i) {
-        const sd_penalty_item &it = items[i];
-        SD_REQUIRE(it.in && it.out && it.seq, "sd_penalize_rows: item %d: null argument", i);
-        SD_REQUIRE(it.rows >= 1 && it.rows <= PEN_MAX_ROWS, "sd_penalize_rows: item %d: rows %d outside 1..%d", i, it.rows, PEN_MAX_ROWS);
-        SD_REQUIRE(it.ld_in >= V && it.ld_out >= V, "sd_penalize_rows: item %d: ld %ld / %ld < V %d", i, it.ld_in, it.ld_out, V);
-        SD_REQUIRE(it.hist0 >= 1 && it.prompt_len >= 0, "sd_penalize_rows: item %d: hist0 %d < 1 or prompt_len %d < 0", i, it.hist0,
-                   it.prompt_len);
-        if (int rc = check_penalty("sd_penalize_rows", "item", i, it.pen); rc != SD_OK) return rc;
-        t.in[i] = it.in; t.out[i] = it.out; t.seq[i] = it.seq; t.ld_in[i] = it.ld_in; t.ld_out[i] = it.ld_out;
-        t.rows[i] = it.rows; t.hist0[i] = it.hist0; t.prompt_len[i] = it.prompt_len;
-        t.repetition[i] = it.pen.repetition; t.frequency[i] = it.pen.frequency; t.presence[i] = it.pen.presence;
-        max_rows = std::max(max_rows, (int)it.rows);
-    }
+    for (int i = 0; i < n_items; ++i)
+        if (int rc = penalty_tab_item("sd_penalize_rows", t, i, items[i], V, &max_rows); rc != SD_OK) return rc;
     return launch_penalize_rows(t, n_items, max_rows, V, mode, (hipStream_t)stream);
 }
 
-// what the _penalties entries refuse in their block (behind the entry's own refusals): n triples, one per `what`, and a slab
-// of at least need_rows rows.  *pb becomes NULL when every triple is neutral: the call is then the entry without a block.
+// what the loops refuse in a penalty block (behind the entry's own refusals): n triples, one per `what`, and a slab of at
+// least need_rows rows.  *pb becomes NULL when every triple is neutral: the call is then the call without a block.
 static int check_penalty_block(const char *who, const char *what, const sd_penalty_block **pb, int n, int V, int need_rows) {
     const sd_penalty_block *b = *pb;
     SD_REQUIRE(b->rows && b->params, "%s: penalties: null pointer", who);
@@ -241,32 +250,20 @@ static int check_edit(const char *who, const char *what, int i, const sd_logit_e
 }
 
 extern "C" int sd_edit_rows(const sd_logit_edit_item *items, int n_items, int V, int mode, void *stream) {
-    SD_REQUIRE(items, "sd_edit_rows: null argument");
-    SD_REQUIRE(n_items >= 1 && n_items <= PEN_MAX_ITEMS, "sd_edit_rows: n_items %d outside 1..%d", n_items, PEN_MAX_ITEMS);
-    SD_REQUIRE(V >= 1 && V <= 65536 && (mode & 3) != 3, "sd_edit_rows: V %d outside 1..65536, or both rounding bits (mode %#x)", V, mode);
+    if (int rc = check_row_edit_call("sd_edit_rows", items, n_items, V, mode); rc != SD_OK) return rc;
     EditTab e = {};
-    PenaltyTab &t = e.pen;
     int max_rows = 0;
     for (int i = 0; i < n_items; ++i) {
         const sd_logit_edit_item &it = items[i];
-        SD_REQUIRE(it.in && it.out && it.seq, "sd_edit_rows: item %d: null argument", i);
-        SD_REQUIRE(it.rows >= 1 && it.rows <= PEN_MAX_ROWS, "sd_edit_rows: item %d: rows %d outside 1..%d", i, it.rows, PEN_MAX_ROWS);
-        SD_REQUIRE(it.ld_in >= V && it.ld_out >= V, "sd_edit_rows: item %d: ld %ld / %ld < V %d", i, it.ld_in, it.ld_out, V);
-        SD_REQUIRE(it.hist0 >= 1 && it.prompt_len >= 0, "sd_edit_rows: item %d: hist0 %d < 1 or prompt_len %d < 0", i, it.hist0,
-                   it.prompt_len);
-        if (int rc = check_penalty("sd_edit_rows", "item", i, it.pen); rc != SD_OK) return rc;
+        if (int rc = penalty_tab_item("sd_edit_rows", e.pen, i, it, V, &max_rows); rc != SD_OK) return rc;
         if (int rc = check_edit("sd_edit_rows", "item", i, it.edit); rc != SD_OK) return rc;
-        t.in[i] = it.in; t.out[i] = it.out; t.seq[i] = it.seq; t.ld_in[i] = it.ld_in; t.ld_out[i] = it.ld_out;
-        t.rows[i] = it.rows; t.hist0[i] = it.hist0; t.prompt_len[i] = it.prompt_len;
-        t.repetition[i] = it.pen.repetition; t.frequency[i] = it.pen.frequency; t.presence[i] = it.pen.presence;
         e.bias_ids[i] = it.edit.bias_ids; e.bias_vals[i] = it.edit.bias_vals; e.n_bias[i] = it.edit.n_bias;
         e.allowed[i] = it.edit.allowed; e.min_tokens[i] = it.edit.min_tokens; e.eos[i] = it.eos_token_id;
-        max_rows = std::max(max_rows, (int)it.rows);
     }
     return launch_edit_rows(e, n_items, max_rows, V, mode, (hipStream_t)stream);
 }
 
-// what the _edits entries refuse in their block, as check_penalty_block does; *eb becomes NULL when every record is neutral
+// what the loops refuse in an edit block, as check_penalty_block does; *eb becomes NULL when every record is neutral
 static int check_edit_block(const char *who, const char *what, const sd_logit_edit_block **eb, int n, int V, int need_rows) {
     const sd_logit_edit_block *b = *eb;
     SD_REQUIRE(b->rows && b->params, "%s: edits: null pointer", who);
@@ -283,7 +280,7 @@ static int check_edit_block(const char *who, const char *what, const sd_logit_ed
 
 // What a loop edits its logit rows by: the penalty block, the edit block or both, as ONE slab and two parameter tables, of
 // which either may be absent (NULL: neutral for everyone).  With an edit table the pass's launch is sd_edit_rows into the
-// edit block's slab, without one sd_penalize_rows into the penalty block's: the _penalties entries keep their launches.
+// edit block's slab, without one sd_penalize_rows into the penalty block's.
 struct RowEdits {
     float *rows; long ld; int max_rows;
     const sd_penalty *pen;
@@ -291,19 +288,45 @@ struct RowEdits {
     int eos;
     bool edited(int k) const { return (pen && !penalty_neutral(pen[k])) || (edit && !edit_neutral(edit[k])); }
 };
-// The entries' two blocks, checked (behind the entry's own refusals) and folded into *re: *out is NULL when nothing is left
-// to edit, and the call is then the entry without blocks.
-static int resolve_row_edits(const char *who, const char *what, const sd_penalty_block *pb, const sd_logit_edit_block *eb, int n,
-                             int V, int need_rows, int eos, RowEdits *re, const RowEdits **out) {
+
+// what the lock-step loops refuse in a parameter array (`what` names its entries: "stream", "prompt")
+static int check_row_params(const char *who, const char *what, const sd_row_sampling *params, int n) {
+    for (int i = 0; i < n; ++i) {
+        SD_REQUIRE(params[i].temperature != 0.0f, "%s: %s %d: temperature must be non-zero", who, what, i);
+        SD_REQUIRE(params[i].top_k >= 0, "%s: %s %d: top_k %d is negative", who, what, i, params[i].top_k);
+    }
+    return SD_OK;
+}
+
+// An entry's sd_loop_opts as its loop reads them: every member NULL when the call carries nothing of the kind.
+struct LoopOpts {
+    const sd_row_sampling *params = nullptr;                      // per stream - with a queue, per prompt (NULL: sm's triple for everyone)
+    const sd_logprob_block *lp = nullptr;
+    RowEdits re_block;
+    const RowEdits *re = nullptr;                                 // &re_block, or NULL when nothing is left to edit
+};
+// Checks `opts` (NULL: four NULL members) behind the entry's own refusals - row_params, logprobs, penalties, edits, in that
+// order - and resolves it into *o.  n: the streams / prompts (`what`) the members are indexed by; need_rows: the logit rows of
+// the loop's largest pass; the two loops that sample with sm's own triple pass row_params_allowed = false.
+static int resolve_loop_opts(const char *who, const char *what, const sd_loop_opts *opts, int n, int V, int need_rows, int eos,
+                             bool row_params_allowed, LoopOpts *o) {
+    if (!opts) return SD_OK;
+    if (opts->row_params) {
+        SD_REQUIRE(row_params_allowed, "%s: row_params: this loop samples with sampling's own triple", who);
+        if (int rc = check_row_params(who, what, opts->row_params, n); rc != SD_OK) return rc;
+    }
+    if (opts->logprobs)
+        if (int rc = check_logprob_block(who, opts->logprobs, n); rc != SD_OK) return rc;
+    const sd_penalty_block *pb = opts->penalties;
+    const sd_logit_edit_block *eb = opts->edits;
     if (pb)
         if (int rc = check_penalty_block(who, what, &pb, n, V, need_rows); rc != SD_OK) return rc;
     if (eb)
         if (int rc = check_edit_block(who, what, &eb, n, V, need_rows); rc != SD_OK) return rc;
-    *out = nullptr;
-    if (!pb && !eb) return SD_OK;
-    *re = eb ? RowEdits{eb->rows, eb->ld, eb->max_rows, pb ? pb->params : nullptr, eb->params, eos}
-             : RowEdits{pb->rows, pb->ld, pb->max_rows, pb->params, nullptr, eos};
-    *out = re;
+    o->params = opts->row_params; o->lp = opts->logprobs;
+    if (eb) o->re_block = RowEdits{eb->rows, eb->ld, eb->max_rows, pb ? pb->params : nullptr, eb->params, eos};
+    else if (pb) o->re_block = RowEdits{pb->rows, pb->ld, pb->max_rows, pb->params, nullptr, eos};
+    if (pb || eb) o->re = &o->re_block;
     return SD_OK;
 }
 // The item of stream / prompt `k`'s `rows` logit rows, the first at position `pos`: packed from row `r0` of the pass's raw
@@ -336,10 +359,12 @@ static void norm_from_edited(NormRequest &nr, const RowEdits &re) {
 // the stream once per iteration.  `timed`: the draft phase is ev.t[0] .. t[1], the verify phase ev.t[2] .. t[3].
 static int spec_iteration(const sd_spec_stream &dv, int g, const sd_sampling &sm, const sd_spec_scratch &sc, const Draws &d, int L,
                           int draft_len, int target_len, const float *r_const, const LoopEvents &ev, bool timed, void *stream,
-                          const sd_logprob_block *lp, const RowEdits *re, int prompt_len) {
+                          const LoopOpts &o, int prompt_len) {
+    const sd_logprob_block *const lp = o.lp;
+    const RowEdits *const re = o.re;
     SD_REQUIRE(L >= 1 && draft_len >= 0 && draft_len < L && target_len >= 0 && target_len < L + g,
                "sd_spec_generate: L=%d draft_len=%d target_len=%d", L, draft_len, target_len);
-    SD_REQUIRE(!lp || target_len <= L - 1, "sd_spec_generate_logprobs: target_len %d of %d tokens leaves fewer than gamma + 1 target rows",
+    SD_REQUIRE(!lp || target_len <= L - 1, "sd_spec_generate: logprobs: target_len %d of %d tokens leaves fewer than gamma + 1 target rows",
                target_len, L);
     hipStream_t st = (hipStream_t)stream;
     int rc;
@@ -416,9 +441,8 @@ static int spec_iteration(const sd_spec_stream &dv, int g, const sd_sampling &sm
 }
 
 // The device-RNG loop without the interpreter between iterations (reference speculative_sampling.py:1934-2046).
-static int spec_generate(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling, const sd_spec_scratch *scratch,
-                         sd_seq_state *s, uint64_t random_seed, const float *r_const, void *stream, const sd_logprob_block *lp,
-                         const sd_penalty_block *pb = nullptr, const sd_logit_edit_block *eb = nullptr) {
+extern "C" int sd_spec_generate(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling, const sd_spec_scratch *scratch,
+                                sd_seq_state *s, uint64_t random_seed, const float *r_const, void *stream, const sd_loop_opts *opts) {
     SD_REQUIRE(dev && sampling && scratch && s && dev->draft && dev->target && dev->seq && dev->q_hist && dev->p_hist &&
                dev->err_words && dev->res_dev && dev->res_host && s->host_seq && scratch->draft.logits && scratch->target.logits,
                "sd_spec_generate: null argument");
@@ -432,12 +456,8 @@ static int spec_generate(const sd_spec_stream *dev, int gamma, const sd_sampling
     SD_REQUIRE(sm.V == dev->draft->m->cfg.vocab && sm.V == dev->target->m->cfg.vocab && sm.ld >= sm.V,
                "sd_spec_generate: V %d (ld %ld), the models' vocabularies are %d / %d", sm.V, sm.ld, dev->draft->m->cfg.vocab,
                dev->target->m->cfg.vocab);
-    if (lp)
-        if (int rc = check_logprob_block("sd_spec_generate_logprobs", lp, 1); rc != SD_OK) return rc;
-    RowEdits re_block;
-    const RowEdits *re = nullptr;
-    if (int rc = resolve_row_edits(eb ? "sd_spec_generate_edits" : "sd_spec_generate_penalties", "stream", pb, eb, 1, sm.V, gamma + 1,
-                                   sm.eos_token_id, &re_block, &re); rc != SD_OK)
+    LoopOpts o;
+    if (int rc = resolve_loop_opts("sd_spec_generate", "stream", opts, 1, sm.V, gamma + 1, sm.eos_token_id, false, &o); rc != SD_OK)
         return rc;
     refresh_env();
     const int g = gamma, L0 = s->len;
@@ -451,7 +471,7 @@ static int spec_generate(const sd_spec_stream *dev, int gamma, const sd_sampling
         const int L = s->len, iters = s->n_iters;
         const Draws d = next_draws(s->seed, s->draw, g, random_seed);
         s->seed = d.seed; s->draw = d.draw;
-        if ((rc = spec_iteration(*dev, g, sm, *scratch, d, L, s->draft_len, s->target_len, r_const, ev, timed, stream, lp, re, L0)) != SD_OK) break;
+        if ((rc = spec_iteration(*dev, g, sm, *scratch, d, L, s->draft_len, s->target_len, r_const, ev, timed, stream, o, L0)) != SD_OK) break;
         SD_LOOP_HIP(hipEventRecord(ev.done, (hipStream_t)stream));
         if ((rc = poll_event(ev.done, "sd_spec_generate")) != SD_OK) break;
         const sd_accept_result r = *dev->res_host;
@@ -487,32 +507,11 @@ static int spec_generate(const sd_spec_stream *dev, int gamma, const sd_sampling
             break;
         }
         commit_result(r, L, g, s->host_seq, &s->len, &s->draft_len, &s->target_len);      // (flags & 2 left the loop above)
-        if (lp) commit_logprobs(*lp, 0, lp->logprob_out[0], L - L0, r);
+        if (o.lp) commit_logprobs(*o.lp, 0, o.lp->logprob_out[0], L - L0, r);
         for (int i = L; i < s->len; ++i) eos_total += s->host_seq[i] == sm.eos_token_id;
         if (eos_total > s->ori_eos_cnt) break;                    // the caller cuts after the first new EOS (:2033-2041)
     }
     return rc;
-}
-
-extern "C" int sd_spec_generate(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling, const sd_spec_scratch *scratch,
-                                sd_seq_state *s, uint64_t random_seed, const float *r_const, void *stream) {
-    return spec_generate(dev, gamma, sampling, scratch, s, random_seed, r_const, stream, nullptr);
-}
-extern "C" int sd_spec_generate_logprobs(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling,
-                                         const sd_spec_scratch *scratch, sd_seq_state *s, uint64_t random_seed, const float *r_const,
-                                         void *stream, const sd_logprob_block *logprobs) {
-    return spec_generate(dev, gamma, sampling, scratch, s, random_seed, r_const, stream, logprobs);
-}
-extern "C" int sd_spec_generate_penalties(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling,
-                                          const sd_spec_scratch *scratch, sd_seq_state *s, uint64_t random_seed, const float *r_const,
-                                          void *stream, const sd_logprob_block *logprobs, const sd_penalty_block *penalties) {
-    return spec_generate(dev, gamma, sampling, scratch, s, random_seed, r_const, stream, logprobs, penalties);
-}
-extern "C" int sd_spec_generate_edits(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling, const sd_spec_scratch *scratch,
-                                      sd_seq_state *s, uint64_t random_seed, const float *r_const, void *stream,
-                                      const sd_logprob_block *logprobs, const sd_penalty_block *penalties,
-                                      const sd_logit_edit_block *edits) {
-    return spec_generate(dev, gamma, sampling, scratch, s, random_seed, r_const, stream, logprobs, penalties, edits);
 }
 
 // ---- the prompt queue of the lock-step loop ---------------------------------------------------------------------
@@ -585,7 +584,7 @@ struct PromptQueue {
     int occ[SD_MAX_STREAMS];                                      // the prompt in slot i, -1: free
     bool joining[SD_MAX_STREAMS];                                 // ... whose rows [0, L-1) are not all cached yet
     int target_passes = 0, draft_passes = 0, extra_passes = 0, prefill_passes = 0;
-    // a shared prompt prefix (sd_spec_queue_generate_shared): the donors hold positions [0, shared_rows) of the two models
+    // a shared prompt prefix: the donors hold positions [0, shared_rows) of the two models
     sd_session *donor_draft = nullptr, *donor_target = nullptr;
     int shared_rows = 0;
     int prompt_rows = 0, copied_rows = 0;                         // target rows forwarded for prompts; KV rows copied per model
@@ -669,10 +668,13 @@ static int queue_idle_prefill(PromptQueue &q, sd_batch_stream *slots, const std:
 
 // The lock-step loop of sampling/batch.py in native code (reference algorithm per stream: speculative_sampling.py:1934-2046),
 // with or without a prompt queue behind the streams' slots.
-// params (or NULL: sm's triple for everyone): per-request sampling parameters, indexed by stream - with a queue, by prompt.
+// `who`: the entry that was called.  o's members are indexed by stream - with a queue, by prompt.
 static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_streams, PromptQueue *q, int gamma, const sd_sampling &sm,
-                         const sd_row_sampling *params, uint64_t random_seed, const float *r_const, const sd_spec_scratch &sc, sd_lockstep_log *log, void *stream,
-                         const sd_logprob_block *lp, const RowEdits *re) {
+                         uint64_t random_seed, const float *r_const, const sd_spec_scratch &sc, sd_lockstep_log *log, void *stream,
+                         const LoopOpts &o) {
+    const sd_row_sampling *const params = o.params;
+    const sd_logprob_block *const lp = o.lp;
+    const RowEdits *const re = o.re;
     hipStream_t st = (hipStream_t)stream;
     const int g = gamma, n_err = 3 * g + 1;
     // rows per target pass (every verify row is a logit row: sd_model_max_pass_rows, 64 for a model whose lm_head or
@@ -723,15 +725,15 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
     // resample) - kept for A/B runs and as the reference the fused tail is tested against; read per call
     const bool fused_tail = !(getenv("SD_BATCH_FUSED_TAIL") && atoi(getenv("SD_BATCH_FUSED_TAIL")) == 0);
     const bool tiles_ok = head_tiles_ok(sm.top_k, sm.temperature, sm.V, sm.ld);
-    // the triple of the request a stream runs: a queue's slot changes parameters when it changes hands
-    auto params_of = [&](const sd_batch_stream &s) -> const sd_row_sampling & { return params[q ? q->occ[&s - streams] : &s - streams]; };
     int L0[SD_MAX_STREAMS];                                       // (logprobs, penalties without a queue) the streams' lengths on entry
-    std::vector<sd_logprob_item> litems;
-    // penalties and edits: the request a stream runs (its index into the blocks' tables) and its prompt length, and the launch
-    // over a pass's logit rows - m streams from act[a0], stream j's n_rows(j) rows packed in stream order in `src`, the first
-    // at position pos0(j) - ahead of the norm launch `nr`, which then reads the slab.  A pass without a penalised or edited
-    // stream is left alone.
+    // the request a stream runs - its index into o's tables: a queue's slot changes parameters, penalties and edits when it
+    // changes hands - and that request's prompt length
     auto request_of = [&](const sd_batch_stream &s) { return q ? q->occ[&s - streams] : (int)(&s - streams); };
+    auto prompt_len_of = [&](const sd_batch_stream &s) { return q ? q->prompts[request_of(s)].L : L0[&s - streams]; };
+    std::vector<sd_logprob_item> litems;
+    // penalties and edits: the launch over a pass's logit rows - m streams from act[a0], stream j's n_rows(j) rows packed in
+    // stream order in `src`, the first at position pos0(j) - ahead of the norm launch `nr`, which then reads the slab.  A pass
+    // without a penalised or edited stream is left alone.
     auto pass_edited = [&](int a0, int m) {
         bool any = false;
         for (int j = 0; re && j < m; ++j) any = any || re->edited(request_of(*act[a0 + j]));
@@ -748,7 +750,7 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
                              "slab holds %d)", who, re->edit ? "edits" : "penalties", slot, nr_j, r0, PEN_MAX_ROWS, re->max_rows);
                 return SD_ERR_INVALID;
             }
-            pitems[j] = edit_item(*re, request_of(s), src, r0, nr_j, s.seq, pos0(j), q ? q->prompts[q->occ[slot]].L : L0[slot]);
+            pitems[j] = edit_item(*re, request_of(s), src, r0, nr_j, s.seq, pos0(j), prompt_len_of(s));
             r0 += nr_j;
         }
         if (int prc = edit_rows(*re, pitems, m, sm.V, nr.mode, stream); prc != SD_OK) return prc;
@@ -801,7 +803,7 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
                     prows.resize(m);
                     pass_tiles = true;
                     for (int j = 0; j < m; ++j) {
-                        prows[j] = params_of(*act[a0 + j]);
+                        prows[j] = params[request_of(*act[a0 + j])];
                         pass_tiles = pass_tiles && head_tiles_ok(prows[j].top_k, prows[j].temperature, sm.V, sm.ld);
                     }
                 }
@@ -864,7 +866,7 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
             for (int j = 0; j < m; ++j) {
                 sd_batch_stream &s = *act[a0 + j];
                 verify_pass_rows(items[j], rows, s.target, s.seq, s.p_hist, sm.ld, s.err_words, g, Ls[a0 + j], s.target_len);
-                if (params) prows.resize(rows.size(), params_of(s));   // (every row of the stream takes its triple)
+                if (params) prows.resize(rows.size(), params[request_of(s)]);   // (every row of the stream takes its triple)
             }
             add_joiners(passes[p], 1);
             if ((rc = batch_forward(items.data(), (int)items.size(), sc.target.logits, sc.target.ld_logits, nullptr, nullptr, stream)) != SD_OK)
@@ -944,10 +946,8 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
             log_ratios(s.p_at_out, s.q_at_out, (size_t)s.calls, g, r.p_at, r.q_at);
             ++s.calls;
             commit_result(r, Ls[j], g, s.host_seq, &s.len, &s.draft_len, &s.target_len);
-            if (lp) {                                             // a queue's slot writes to the array of the prompt it runs
-                const int slot = (int)(&s - streams), k = q ? q->occ[slot] : slot;
-                commit_logprobs(*lp, slot, lp->logprob_out[k], Ls[j] - (q ? q->prompts[k].L : L0[slot]), r);
-            }
+            if (lp)                                               // a queue's slot writes to the array of the prompt it runs
+                commit_logprobs(*lp, (int)(&s - streams), lp->logprob_out[request_of(s)], Ls[j] - prompt_len_of(s), r);
             int eos_total = 0;
             for (int i = 0; i < s.len; ++i) eos_total += s.host_seq[i] == sm.eos_token_id;
             if (eos_total > s.ori_eos_cnt) s.done = 1;            // the caller cuts after the first new EOS
@@ -964,65 +964,34 @@ static int check_result_blocks(const char *who, const sd_batch_stream *streams, 
     return SD_OK;
 }
 
-// what the _rows entries refuse in a parameter array (`what` names its entries: "stream", "prompt")
-static int check_row_params(const char *who, const char *what, const sd_row_sampling *params, int n) {
-    for (int i = 0; i < n; ++i) {
-        SD_REQUIRE(params[i].temperature != 0.0f, "%s: %s %d: temperature must be non-zero", who, what, i);
-        SD_REQUIRE(params[i].top_k >= 0, "%s: %s %d: top_k %d is negative", who, what, i, params[i].top_k);
-    }
-    return SD_OK;
-}
-
 // the logit rows of a lock-step loop's largest pass: whole streams of gamma + 1 verify rows, as many as a target pass holds
 static int lockstep_penalty_rows(const sd_batch_stream *streams, int n_streams, int gamma, const sd_spec_scratch &sc) {
     const int pass_rows = std::min(sc.max_rows_per_forward, streams[0].target ? streams[0].target->max_pass_rows : SD_MAX_ROWS);
     return std::min(std::max(pass_rows, gamma + 1), n_streams * (gamma + 1));
 }
 
-static int batch_generate(const char *who, sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
-                          const sd_row_sampling *params, uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
-                          sd_lockstep_log *log, void *stream, const sd_logprob_block *lp = nullptr,
-                          const sd_penalty_block *pb = nullptr, const sd_logit_edit_block *eb = nullptr) {
+extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
+                                      uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
+                                      sd_lockstep_log *log, void *stream, const sd_loop_opts *opts) {
+    const char *const who = "sd_spec_batch_generate";
     SD_REQUIRE(streams && n_streams >= 1 && n_streams <= 16 && gamma >= 1 && gamma <= 16 && sampling && scratch && log &&
                scratch->draft.logits && scratch->target.logits, "%s: bad arguments", who);
     SD_REQUIRE(!random_seed || r_const, "%s: random_seed needs its uniform (r_const)", who);
     if (int rc = check_result_blocks(who, streams, n_streams); rc != SD_OK) return rc;
-    if (params)
-        if (int rc = check_row_params(who, "stream", params, n_streams); rc != SD_OK) return rc;
-    if (lp)
-        if (int rc = check_logprob_block(who, lp, n_streams); rc != SD_OK) return rc;
-    RowEdits re_block;
-    const RowEdits *re = nullptr;
-    if (pb || eb)
-        if (int rc = resolve_row_edits(who, "stream", pb, eb, n_streams, sampling->V, lockstep_penalty_rows(streams, n_streams, gamma, *scratch),
-                                       sampling->eos_token_id, &re_block, &re); rc != SD_OK)
-            return rc;
-    return lockstep_loop(who, streams, n_streams, nullptr, gamma, *sampling, params, random_seed, r_const, *scratch, log, stream, lp, re);
+    LoopOpts o;
+    if (int rc = resolve_loop_opts(who, "stream", opts, n_streams, sampling->V, lockstep_penalty_rows(streams, n_streams, gamma, *scratch),
+                                   sampling->eos_token_id, true, &o); rc != SD_OK)
+        return rc;
+    return lockstep_loop(who, streams, n_streams, nullptr, gamma, *sampling, random_seed, r_const, *scratch, log, stream, o);
 }
 
-extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
-                                      uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
-                                      sd_lockstep_log *log, void *stream) {
-    return batch_generate("sd_spec_batch_generate", streams, n_streams, gamma, sampling, nullptr, random_seed, r_const, scratch, log,
-                          stream);
-}
-
-extern "C" int sd_spec_batch_generate_rows(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
-                                           uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
-                                           sd_lockstep_log *log, void *stream, const sd_row_sampling *stream_params) {
-    if (!stream_params) return sd_spec_batch_generate(streams, n_streams, gamma, sampling, random_seed, r_const, scratch, log, stream);
-    return batch_generate("sd_spec_batch_generate_rows", streams, n_streams, gamma, sampling, stream_params, random_seed, r_const,
-                          scratch, log, stream);
-}
-
-// The two entry points of the prompt queue: `who` names the one that was called; without donors (shared_rows 0) the loop is
-// sd_spec_queue_generate's, pass for pass.  n_passes_out: how many ints of passes_out the entry point documents.
-static int queue_generate(const char *who, int n_passes_out, sd_session *donor_draft, sd_session *donor_target, int shared_rows,
-                          sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
-                          int prefill_chunk, int gamma, const sd_sampling *sampling, const sd_row_sampling *params,
-                          uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log,
-                          int *passes_out, void *stream, const sd_logprob_block *lp = nullptr, const sd_penalty_block *pb = nullptr,
-                          const sd_logit_edit_block *eb = nullptr) {
+// The prompt queue: without donors (shared_rows 0) every prompt starts with empty caches.
+extern "C" int sd_spec_queue_generate(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
+                                      int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
+                                      const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log, int *passes_out,
+                                      void *stream, sd_session *donor_draft, sd_session *donor_target, int shared_rows,
+                                      const sd_loop_opts *opts) {
+    const char *const who = "sd_spec_queue_generate";
     SD_REQUIRE(n_slots >= 1 && n_slots <= 16, "%s: n_slots %d outside 1..16", who, n_slots);
     SD_REQUIRE(gamma >= 1 && gamma <= 16, "%s: gamma %d outside 1..16", who, gamma);
     SD_REQUIRE(n_prompts >= 1 && prefill_chunk >= 0, "%s: n_prompts %d, prefill_chunk %d", who, n_prompts, prefill_chunk);
@@ -1058,137 +1027,19 @@ static int queue_generate(const char *who, int n_passes_out, sd_session *donor_d
         SD_REQUIRE(slots[i].draft->max_seq >= slot_cap - 2 && slots[i].target->max_seq >= slot_cap - 2,
                    "%s: slot %d: KV arenas of %d / %d positions, slot_cap %d needs %d", who, i, slots[i].draft->max_seq,
                    slots[i].target->max_seq, slot_cap, slot_cap - 2);
-    if (params)
-        if (int rc = check_row_params(who, "prompt", params, n_prompts); rc != SD_OK) return rc;
+    LoopOpts o;
+    if (int rc = resolve_loop_opts(who, "prompt", opts, n_prompts, sampling->V, lockstep_penalty_rows(slots, n_slots, gamma, *scratch),
+                                   sampling->eos_token_id, true, &o); rc != SD_OK)
+        return rc;
     PromptQueue q;
     q.prompts = prompts; q.n_prompts = n_prompts; q.prefill_chunk = prefill_chunk;
     q.donor_draft = donor_draft; q.donor_target = donor_target; q.shared_rows = shared_rows;
-    if (lp)
-        if (int rc = check_logprob_block(who, lp, n_prompts); rc != SD_OK) return rc;
-    RowEdits re_block;
-    const RowEdits *re = nullptr;
-    if (pb || eb)
-        if (int rc = resolve_row_edits(who, "prompt", pb, eb, n_prompts, sampling->V, lockstep_penalty_rows(slots, n_slots, gamma, *scratch),
-                                       sampling->eos_token_id, &re_block, &re); rc != SD_OK)
-            return rc;
-    const int rc = lockstep_loop(who, slots, n_slots, &q, gamma, *sampling, params, random_seed, r_const, *scratch, log, stream, lp, re);
+    const int rc = lockstep_loop(who, slots, n_slots, &q, gamma, *sampling, random_seed, r_const, *scratch, log, stream, o);
     if (passes_out) {
         const int v[6] = {q.target_passes, q.draft_passes, q.extra_passes, q.prefill_passes, q.prompt_rows, q.copied_rows};
-        for (int i = 0; i < n_passes_out; ++i) passes_out[i] = v[i];
+        std::copy(v, v + 6, passes_out);
     }
     return rc;
-}
-
-extern "C" int sd_spec_queue_generate(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
-                                      int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
-                                      const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log, int *passes_out,
-                                      void *stream) {
-    return queue_generate("sd_spec_queue_generate", 4, nullptr, nullptr, 0, slots, n_slots, slot_cap, prompts, n_prompts,
-                          prefill_chunk, gamma, sampling, nullptr, random_seed, r_const, scratch, log, passes_out, stream);
-}
-
-extern "C" int sd_spec_queue_generate_shared(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
-                                             int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
-                                             const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log,
-                                             int *passes_out, void *stream, sd_session *donor_draft, sd_session *donor_target,
-                                             int shared_rows) {
-    return queue_generate("sd_spec_queue_generate_shared", 6, donor_draft, donor_target, shared_rows, slots, n_slots, slot_cap,
-                          prompts, n_prompts, prefill_chunk, gamma, sampling, nullptr, random_seed, r_const, scratch, log, passes_out,
-                          stream);
-}
-
-extern "C" int sd_spec_queue_generate_rows(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
-                                           int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
-                                           const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log,
-                                           int *passes_out, void *stream, sd_session *donor_draft, sd_session *donor_target,
-                                           int shared_rows, const sd_row_sampling *prompt_params) {
-    if (!prompt_params)
-        return sd_spec_queue_generate_shared(slots, n_slots, slot_cap, prompts, n_prompts, prefill_chunk, gamma, sampling, random_seed,
-                                             r_const, scratch, log, passes_out, stream, donor_draft, donor_target, shared_rows);
-    return queue_generate("sd_spec_queue_generate_rows", 6, donor_draft, donor_target, shared_rows, slots, n_slots, slot_cap, prompts,
-                          n_prompts, prefill_chunk, gamma, sampling, prompt_params, random_seed, r_const, scratch, log, passes_out,
-                          stream);
-}
-
-// The lock-step loops with per-token target log-probabilities: the _rows entries' arguments plus the block (NULL: those entries)
-extern "C" int sd_spec_batch_generate_logprobs(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
-                                               uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
-                                               sd_lockstep_log *log, void *stream, const sd_row_sampling *stream_params,
-                                               const sd_logprob_block *logprobs) {
-    if (!logprobs)
-        return sd_spec_batch_generate_rows(streams, n_streams, gamma, sampling, random_seed, r_const, scratch, log, stream, stream_params);
-    return batch_generate("sd_spec_batch_generate_logprobs", streams, n_streams, gamma, sampling, stream_params, random_seed, r_const,
-                          scratch, log, stream, logprobs);
-}
-
-extern "C" int sd_spec_queue_generate_logprobs(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
-                                               int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
-                                               const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log,
-                                               int *passes_out, void *stream, sd_session *donor_draft, sd_session *donor_target,
-                                               int shared_rows, const sd_row_sampling *prompt_params, const sd_logprob_block *logprobs) {
-    if (!logprobs)
-        return sd_spec_queue_generate_rows(slots, n_slots, slot_cap, prompts, n_prompts, prefill_chunk, gamma, sampling, random_seed,
-                                           r_const, scratch, log, passes_out, stream, donor_draft, donor_target, shared_rows, prompt_params);
-    return queue_generate("sd_spec_queue_generate_logprobs", 6, donor_draft, donor_target, shared_rows, slots, n_slots, slot_cap, prompts,
-                          n_prompts, prefill_chunk, gamma, sampling, prompt_params, random_seed, r_const, scratch, log, passes_out,
-                          stream, logprobs);
-}
-
-// The lock-step loops with per-request penalties: the _logprobs entries' arguments (logprobs may be NULL) plus the block
-// (NULL: those entries)
-extern "C" int sd_spec_batch_generate_penalties(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
-                                                uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
-                                                sd_lockstep_log *log, void *stream, const sd_row_sampling *stream_params,
-                                                const sd_logprob_block *logprobs, const sd_penalty_block *penalties) {
-    if (!penalties)
-        return sd_spec_batch_generate_logprobs(streams, n_streams, gamma, sampling, random_seed, r_const, scratch, log, stream,
-                                               stream_params, logprobs);
-    return batch_generate("sd_spec_batch_generate_penalties", streams, n_streams, gamma, sampling, stream_params, random_seed, r_const,
-                          scratch, log, stream, logprobs, penalties);
-}
-
-extern "C" int sd_spec_queue_generate_penalties(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
-                                                int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
-                                                const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log,
-                                                int *passes_out, void *stream, sd_session *donor_draft, sd_session *donor_target,
-                                                int shared_rows, const sd_row_sampling *prompt_params, const sd_logprob_block *logprobs,
-                                                const sd_penalty_block *penalties) {
-    if (!penalties)
-        return sd_spec_queue_generate_logprobs(slots, n_slots, slot_cap, prompts, n_prompts, prefill_chunk, gamma, sampling, random_seed,
-                                               r_const, scratch, log, passes_out, stream, donor_draft, donor_target, shared_rows,
-                                               prompt_params, logprobs);
-    return queue_generate("sd_spec_queue_generate_penalties", 6, donor_draft, donor_target, shared_rows, slots, n_slots, slot_cap, prompts,
-                          n_prompts, prefill_chunk, gamma, sampling, prompt_params, random_seed, r_const, scratch, log, passes_out,
-                          stream, logprobs, penalties);
-}
-
-// ... and with per-request logit edits: the _penalties entries' arguments (logprobs and penalties may be NULL) plus the block
-// (NULL: those entries)
-extern "C" int sd_spec_batch_generate_edits(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
-                                            uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch,
-                                            sd_lockstep_log *log, void *stream, const sd_row_sampling *stream_params,
-                                            const sd_logprob_block *logprobs, const sd_penalty_block *penalties,
-                                            const sd_logit_edit_block *edits) {
-    if (!edits)
-        return sd_spec_batch_generate_penalties(streams, n_streams, gamma, sampling, random_seed, r_const, scratch, log, stream,
-                                                stream_params, logprobs, penalties);
-    return batch_generate("sd_spec_batch_generate_edits", streams, n_streams, gamma, sampling, stream_params, random_seed, r_const,
-                          scratch, log, stream, logprobs, penalties, edits);
-}
-
-extern "C" int sd_spec_queue_generate_edits(sd_batch_stream *slots, int n_slots, int slot_cap, sd_queue_prompt *prompts, int n_prompts,
-                                            int prefill_chunk, int gamma, const sd_sampling *sampling, uint64_t random_seed,
-                                            const float *r_const, const sd_spec_scratch *scratch, sd_lockstep_log *log,
-                                            int *passes_out, void *stream, sd_session *donor_draft, sd_session *donor_target,
-                                            int shared_rows, const sd_row_sampling *prompt_params, const sd_logprob_block *logprobs,
-                                            const sd_penalty_block *penalties, const sd_logit_edit_block *edits) {
-    if (!edits)
-        return sd_spec_queue_generate_penalties(slots, n_slots, slot_cap, prompts, n_prompts, prefill_chunk, gamma, sampling,
-                                                random_seed, r_const, scratch, log, passes_out, stream, donor_draft, donor_target,
-                                                shared_rows, prompt_params, logprobs, penalties);
-    return queue_generate("sd_spec_queue_generate_edits", 6, donor_draft, donor_target, shared_rows, slots, n_slots, slot_cap, prompts,
-                          n_prompts, prefill_chunk, gamma, sampling, prompt_params, random_seed, r_const, scratch, log, passes_out,
-                          stream, logprobs, penalties, edits);
 }
 
 // ---- the width-w loop of sampling/multi.py in native code (reference speculative_sampling.py:1379-1716, strategy "iid")
@@ -1432,10 +1283,9 @@ extern "C" size_t sd_ar_block_bytes(int n_streams) {
     return ((size_t)n_streams * sizeof(ArSlot) + 15) & ~(size_t)15;
 }
 
-static int ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
-                             void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream,
-                             const sd_logprob_block *lp, const sd_penalty_block *pb = nullptr,
-                             const sd_logit_edit_block *eb = nullptr) {
+extern "C" int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
+                                    void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream,
+                                    const sd_loop_opts *opts) {
     SD_REQUIRE(n_streams >= 1 && n_streams <= 16, "sd_ar_batch_generate: n_streams %d outside 1..16", n_streams);
     SD_REQUIRE(streams && sampling && head && log && head->logits && dev_block && host_block, "sd_ar_batch_generate: null argument");
     const sd_sampling &sm = *sampling;
@@ -1453,13 +1303,12 @@ static int ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_samp
         SD_REQUIRE(streams[b].session->m == streams[0].session->m, "sd_ar_batch_generate: stream %d: session of another model", b);
     SD_REQUIRE(n_streams <= streams[0].session->max_pass_rows, "sd_ar_batch_generate: %d streams exceed one pass (%d rows)", n_streams,
                streams[0].session->max_pass_rows);
-    if (lp)
-        if (int rc = check_logprob_block("sd_ar_batch_generate_logprobs", lp, n_streams); rc != SD_OK) return rc;
-    RowEdits re_block;
-    const RowEdits *re = nullptr;
-    if (int rc = resolve_row_edits(eb ? "sd_ar_batch_generate_edits" : "sd_ar_batch_generate_penalties", "stream", pb, eb, n_streams, sm.V,
-                                   n_streams, sm.eos_token_id, &re_block, &re); rc != SD_OK)
+    LoopOpts o;
+    if (int rc = resolve_loop_opts("sd_ar_batch_generate", "stream", opts, n_streams, sm.V, n_streams, sm.eos_token_id, false, &o);
+        rc != SD_OK)
         return rc;
+    const sd_logprob_block *const lp = o.lp;
+    const RowEdits *const re = o.re;
     hipStream_t st = (hipStream_t)stream;
     const bool timed = log->step_ms_out != nullptr;
     LoopEvents ev(timed ? 2 : 0, "sd_ar_batch_generate");
@@ -1554,27 +1403,4 @@ static int ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_samp
         }
     }
     return rc;
-}
-
-extern "C" int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
-                                    void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream) {
-    return ar_batch_generate(streams, n_streams, sampling, head, norm_workspace, dev_block, host_block, log, stream, nullptr);
-}
-extern "C" int sd_ar_batch_generate_logprobs(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling,
-                                             const sd_head_scratch *head, void *norm_workspace, void *dev_block, void *host_block,
-                                             sd_ar_log *log, void *stream, const sd_logprob_block *logprobs) {
-    return ar_batch_generate(streams, n_streams, sampling, head, norm_workspace, dev_block, host_block, log, stream, logprobs);
-}
-extern "C" int sd_ar_batch_generate_penalties(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling,
-                                              const sd_head_scratch *head, void *norm_workspace, void *dev_block, void *host_block,
-                                              sd_ar_log *log, void *stream, const sd_logprob_block *logprobs,
-                                              const sd_penalty_block *penalties) {
-    return ar_batch_generate(streams, n_streams, sampling, head, norm_workspace, dev_block, host_block, log, stream, logprobs, penalties);
-}
-extern "C" int sd_ar_batch_generate_edits(sd_ar_stream *streams, int n_streams, const sd_sampling *sampling, const sd_head_scratch *head,
-                                          void *norm_workspace, void *dev_block, void *host_block, sd_ar_log *log, void *stream,
-                                          const sd_logprob_block *logprobs, const sd_penalty_block *penalties,
-                                          const sd_logit_edit_block *edits) {
-    return ar_batch_generate(streams, n_streams, sampling, head, norm_workspace, dev_block, host_block, log, stream, logprobs, penalties,
-                             edits);
 }

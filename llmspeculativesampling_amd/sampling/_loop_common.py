@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from .._lib import (LOGPROB_SLICE, LOGPROB_STREAMS, SD_EDIT_MAX_BIAS, SdHeadScratch, SdLockstepLog, SdLogitEdit, SdLogitEditBlock,
-                    SdLogprobBlock, SdPenalty, SdPenaltyBlock, SdRowSampling, SdSampling, SdSeqState, SdSpecScratch, SdSpecStream)
+                    SdLogprobBlock, SdLoopOpts, SdPenalty, SdPenaltyBlock, SdRowSampling, SdSampling, SdSeqState, SdSpecScratch, SdSpecStream)
 from ..noise import DeviceNoise, HostTorchNoise
 from .kvcache_model import KVCacheModel
 
@@ -104,7 +104,7 @@ def _per_request(x) -> bool:
 def row_sampling(n: int, what: str, temperature, top_k, top_p):
     """Per-request ``temperature`` / ``top_k`` / ``top_p`` of the lock-step loops: each a scalar (broadcast) or a sequence with
     one entry per ``what`` ("prompt", "stream"), ``n`` of them.  Returns ``None`` when all three are scalars - the call then
-    takes the scalar entry point as before, unchecked as before - else the ``n`` (temperature, top_k, top_p) triples; raises
+    is the scalar call as before, unchecked as before - else the ``n`` (temperature, top_k, top_p) triples; raises
     ValueError naming the parameter for a sequence of another length, a temperature of 0, a negative or non-integer top_k.
     Touches no model and no GPU."""
     given = {"temperature": temperature, "top_k": top_k, "top_p": top_p}
@@ -132,8 +132,19 @@ def row_sampling(n: int, what: str, temperature, top_k, top_p):
 
 
 def row_sampling_array(triples):
-    """The SdRowSampling array of row_sampling's triples (``None`` stays ``None``: the NULL array of the _rows entries)."""
+    """The SdRowSampling array of row_sampling's triples (``None`` stays ``None``: a NULL ``row_params``)."""
     return None if triples is None else (SdRowSampling * len(triples))(*[SdRowSampling(*t) for t in triples])
+
+
+def loop_opts(triples=None, lp=None, pb=None, eb=None):
+    """The SdLoopOpts of one native loop call, from row_sampling's triples, a LogprobBlock, a PenaltyBlock and a LogitEditBlock,
+    each of which may be ``None``: a NULL member.  All four ``None`` -> ``None``, the NULL block, so that a call with neutral
+    keywords is the call that was made before the keywords existed.  The struct keeps the row_sampling_array alive; the three
+    blocks stay with the caller."""
+    if triples is None and lp is None and pb is None and eb is None:
+        return None
+    ptr = lambda b: C.pointer(b.block) if b is not None else None
+    return SdLoopOpts(row_sampling_array(triples), ptr(lp), ptr(pb), ptr(eb))
 
 
 def head_scratch(session) -> SdHeadScratch:
@@ -246,7 +257,7 @@ class LogprobBlock:
 def penalty_triples(n: int, what: str, repetition_penalty, frequency_penalty, presence_penalty):
     """Per-request ``repetition_penalty`` / ``frequency_penalty`` / ``presence_penalty`` of the native loops: each one value
     (broadcast) or a sequence with one entry per ``what`` ("prompt", "stream"), ``n`` of them.  Returns ``None`` for the three
-    neutral scalars (1, 0, 0) - the call then takes the entry point it took before - else the ``n`` (repetition, frequency,
+    neutral scalars (1, 0, 0) - the call is then the call it was before - else the ``n`` (repetition, frequency,
     presence) triples; raises ValueError naming the parameter for a sequence of another length, a value that is not a finite
     number, a repetition penalty <= 0.  Touches no model and no GPU."""
     given = {"repetition_penalty": repetition_penalty, "frequency_penalty": frequency_penalty, "presence_penalty": presence_penalty}
@@ -342,8 +353,8 @@ def logit_edits(n: int, what: str, V, eos_token_id, logit_bias=None, allowed_tok
     """Per-request ``logit_bias`` / ``allowed_token_ids`` / ``banned_token_ids`` / ``min_tokens`` of the native loops, ``n``
     requests called ``what`` ("prompt", "stream").  ``logit_bias``: one ``{id: bias}`` mapping for every request or a sequence
     with one mapping-or-None per request; the id lists: one flat sequence for every request or one sequence-or-None per
-    request; ``min_tokens``: an int or one per request.  Returns ``None`` when everything is neutral - the call then takes the
-    entry point it took before - else one record per request: ``dict(bias_ids=int32 array ascending, bias_vals=float32 array,
+    request; ``min_tokens``: an int or one per request.  Returns ``None`` when everything is neutral - the call is then the
+    call it was before - else one record per request: ``dict(bias_ids=int32 array ascending, bias_vals=float32 array,
     mask=uint32 words or None, min_tokens=int)``.  Raises ValueError naming the parameter and the request for a sequence of
     another length, a bias that is not a finite number, more than 1024 bias entries, an id that is not an integer or lies
     outside [0, V), min_tokens < 0, an allowed set that is empty once the banned ids are removed, or one that holds nothing but

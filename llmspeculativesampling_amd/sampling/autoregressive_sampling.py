@@ -9,7 +9,7 @@ import torch
 from .._lib import lib, check, SdArLog, SdArStream
 from ..engine import as_specdec_model, _stream, check_token_ids
 from ._loop_common import (EDITS_NEED_NATIVE, LogitEditBlock, LogprobBlock, PenaltyBlock, device_rng, edits_need_target_rows,
-                           head_scratch, bind_logit_edits, logit_edits, logprobs_need_target_rows, make_noise, open_stream,
+                           head_scratch, bind_logit_edits, logit_edits, logprobs_need_target_rows, loop_opts, make_noise, open_stream,
                            penalties_need_target_rows, penalty_triples, raise_loop_error, sampling_block)
 from .kvcache_model import KVCacheModel
 
@@ -139,15 +139,7 @@ class ArRun:
         self.lp = LogprobBlock(dev, [s.T + 1 for s in self.streams]) if logprobs else None
         pb = PenaltyBlock(dev, penalties, self.m.cfg.vocab_size, B) if penalties is not None else None
         eb = LogitEditBlock(dev, edits, self.m.cfg.vocab_size, B, pb.rows if pb is not None else None) if edits is not None else None
-        if eb is not None:
-            rc = lib.sd_ar_batch_generate_edits(*args, self.lp.block if self.lp is not None else None,
-                                                pb.block if pb is not None else None, eb.block)
-        elif pb is not None:
-            rc = lib.sd_ar_batch_generate_penalties(*args, self.lp.block if self.lp is not None else None, pb.block)
-        elif self.lp is None:
-            rc = lib.sd_ar_batch_generate(*args)
-        else:
-            rc = lib.sd_ar_batch_generate_logprobs(*args, self.lp.block)
+        rc = lib.sd_ar_batch_generate(*args, loop_opts(None, self.lp, pb, eb))
         self.lens = []
         for it, s in zip(arr, self.streams):                      # the state the loop left, also after a failure
             s.kv._session.cache_len = it.cache_len

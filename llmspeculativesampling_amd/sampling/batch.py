@@ -23,8 +23,8 @@ from .._lib import lib, check, SdAcceptResult, SdBatchStream, SdQueuePrompt
 from ..engine import as_specdec_model, _stream, check_token_ids, same_device, batch_prefill
 from ..noise import DeviceNoise
 from ._loop_common import (LockstepLog, LogitEditBlock, LogprobBlock, LoopLog, PenaltyBlock, bind_spec_slot, edits_need_target_rows,
-                           lockstep_result, bind_logit_edits, logit_edits, logprobs_need_target_rows, open_spec_slot, open_stream,
-                           penalties_need_target_rows, penalty_triples, reseed_uniforms, row_sampling, row_sampling_array,
+                           lockstep_result, bind_logit_edits, logit_edits, logprobs_need_target_rows, loop_opts, open_spec_slot, open_stream,
+                           penalties_need_target_rows, penalty_triples, reseed_uniforms, row_sampling,
                            sampling_block, spec_scratch)
 from .autoregressive_sampling import ArRun
 from .kvcache_model import KVCacheModel
@@ -64,20 +64,20 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
     (``T_i``, ``k_i``, ``p_i``; a scalar beside a sequence is broadcast): stream i equals ``speculative_sampling(prefixes[i],
     ..., temperature=T_i, top_k=k_i, top_p=p_i, rng=DeviceNoise(seeds[i]))``.  A sequence of another length, a temperature
     entry of 0 or a negative / non-integer top_k entry raises ValueError before a model is touched.  With three scalars the
-    call is sd_spec_batch_generate's as before; with any sequence it goes to sd_spec_batch_generate_rows.
+    call is sd_spec_batch_generate's as before; any sequence is the ``row_params`` of its sd_loop_opts.
     ``logprobs``: the return value gains one last element, a list of float32 (1, len_i - L_i) tensors with the TARGET
     model's log-probability of every new token of stream i, as ``speculative_sampling(logprobs=True)`` defines it: the
     log-softmax of the raw target logits, before temperature, top_k and top_p - what the model says, not what the sampler
-    drew from - cut where the tokens are cut (sd_spec_batch_generate_logprobs).
+    drew from - cut where the tokens are cut (member ``logprobs`` of sd_loop_opts).
     ``repetition_penalty`` / ``frequency_penalty`` / ``presence_penalty`` (neutral 1 / 0 / 0): each one value for all streams
     or one per stream, broadcast like ``temperature``; stream i equals ``speculative_sampling(prefixes[i], ...,
     repetition_penalty=r_i, frequency_penalty=f_i, presence_penalty=p_i, rng=DeviceNoise(seeds[i]))``
-    (sd_spec_batch_generate_penalties; ``sampling.utils.apply_penalties`` has the definition).  A sequence of another length, a
+    (member ``penalties``; ``sampling.utils.apply_penalties`` has the definition).  A sequence of another length, a
     value that is not finite or a repetition penalty <= 0 raises ValueError before a model is touched.
     ``logit_bias`` (one ``{token id: bias}`` mapping for all streams, or a sequence with one mapping-or-None per stream),
     ``allowed_token_ids`` / ``banned_token_ids`` (one flat sequence of ids for all streams, or one sequence-or-None per stream)
     and ``min_tokens`` (an int, or one per stream): stream i equals ``speculative_sampling`` with its values
-    (sd_spec_batch_generate_edits; ``sampling.utils.apply_logit_edits`` has the definition, ``speculative_sampling`` the
+    (member ``edits``; ``sampling.utils.apply_logit_edits`` has the definition, ``speculative_sampling`` the
     refusals)."""
     edit_args = (logit_bias, allowed_token_ids, banned_token_ids, min_tokens)
     try:
@@ -154,18 +154,7 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
     pb = PenaltyBlock(dev, pen, V, min(max(per_pass, gamma + 1), B * (gamma + 1))) if pen is not None else None
     eb = LogitEditBlock(dev, ed, V, min(max(per_pass, gamma + 1), B * (gamma + 1)), pb.rows if pb is not None else None) \
         if ed is not None else None
-    if eb is not None:
-        check(lib.sd_spec_batch_generate_edits(*args, row_sampling_array(triples), lp.block if lp is not None else None,
-                                               pb.block if pb is not None else None, eb.block), "sd_spec_batch_generate_edits")
-    elif pb is not None:
-        check(lib.sd_spec_batch_generate_penalties(*args, row_sampling_array(triples), lp.block if lp is not None else None, pb.block),
-              "sd_spec_batch_generate_penalties")
-    elif lp is not None:
-        check(lib.sd_spec_batch_generate_logprobs(*args, row_sampling_array(triples), lp.block), "sd_spec_batch_generate_logprobs")
-    elif triples is None:
-        check(lib.sd_spec_batch_generate(*args), "sd_spec_batch_generate")
-    else:
-        check(lib.sd_spec_batch_generate_rows(*args, row_sampling_array(triples)), "sd_spec_batch_generate_rows")
+    check(lib.sd_spec_batch_generate(*args, loop_opts(triples, lp, pb, eb)), "sd_spec_batch_generate")
     if vlog.block.err:
         raise RuntimeError("s")
     if _timing is not None:
@@ -241,7 +230,7 @@ def speculative_sampling_queue(prefixes: Sequence[torch.Tensor], approx_model, t
     ``speculative_sampling(prefixes[i], ..., temperature=T_i, top_k=k_i, top_p=p_i, rng=DeviceNoise(seeds[i]))``, whichever
     slot it decodes in and whatever its neighbours ask for.  A sequence of another length, a temperature entry of 0 or a
     negative / non-integer top_k entry raises ValueError before a model is touched.  With three scalars the call takes the
-    scalar entry point as before; with any sequence it goes to sd_spec_queue_generate_rows.
+    scalar call as before; any sequence is the ``row_params`` of its sd_loop_opts.
     ``_timing`` receives "verify" entries as speculative_sampling_batch writes them, "iterations", "target_passes",
     "draft_passes", "extra_passes" (target passes that carried prompt rows only; "prefill_passes" of them ran while no
     stream was active), "prompt_rows" (target rows forwarded for prompts), "copied_rows" (0 here) and per prompt
@@ -286,7 +275,7 @@ def speculative_sampling_queue_logprobs(prefixes: Sequence[torch.Tensor], approx
     log-softmax in fp32 of the target's raw logit row for the position before it, taken before temperature, top_k and top_p -
     what the model says, not what the sampler drew from - so ``logprobs[i].mean()`` is ``quality.get_score`` of output i
     without a second target pass.  Tokens, details and Philox positions are those of the call without scores
-    (sd_spec_queue_generate_logprobs).  (A function of its own: the queues' parameter lists are pinned by their tests.)"""
+    (member ``logprobs`` of sd_loop_opts).  (A function of its own: the queues' parameter lists are pinned by their tests.)"""
     return _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max_len, gamma, temperature, top_k, top_p,
                   random_seed, details, seeds, slots, prefill_chunk, _timing, shared_prefix, logprobs=True)
 
@@ -303,7 +292,7 @@ def speculative_sampling_queue_requests(prefixes: Sequence[torch.Tensor], approx
     one value for all prompts or one per prompt.  Prompt i then equals ``speculative_sampling(prefixes[i], ...,
     repetition_penalty=r_i, frequency_penalty=f_i, presence_penalty=p_i, rng=DeviceNoise(seeds[i]))``, whichever slot it decodes
     in and whatever its neighbours ask for: a slot changes penalties when it changes hands, and the prompt that counts as a
-    request's prompt is its own (sd_spec_queue_generate_penalties; ``sampling.utils.apply_penalties`` has the definition).  A
+    request's prompt is its own (member ``penalties`` of sd_loop_opts; ``sampling.utils.apply_penalties`` has the definition).  A
     sequence of another length, a value that is not finite or a repetition penalty <= 0 raises ValueError before a model is
     touched.  ``logprobs=True`` returns what speculative_sampling_queue_logprobs returns: the scores stay what the model says,
     penalties or not.  (A function of its own: the queues' parameter lists are pinned by their tests.)"""
@@ -325,7 +314,7 @@ def speculative_sampling_queue_edits(prefixes: Sequence[torch.Tensor], approx_mo
     ``banned_token_ids`` (one flat sequence of ids for all prompts, or one sequence-or-None per prompt) and ``min_tokens`` (an
     int, or one per prompt), as ``speculative_sampling`` describes them.  Prompt i equals ``speculative_sampling(prefixes[i],
     ..., rng=DeviceNoise(seeds[i]))`` with its values, whichever slot it decodes in: a slot changes its edits when it changes
-    hands, and ``min_tokens`` counts the request's own output (sd_spec_queue_generate_edits; ``sampling.utils.apply_logit_edits``
+    hands, and ``min_tokens`` counts the request's own output (member ``edits`` of sd_loop_opts; ``sampling.utils.apply_logit_edits``
     has the definition).  ValueError before a model is touched, as ``speculative_sampling`` lists them, naming the parameter
     and the prompt.  ``logprobs=True``: the scores stay what the model says.  (A function of its own:
     speculative_sampling_queue_requests' parameter list is pinned by its test, as the other queues' are.)"""
@@ -411,24 +400,12 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
                 raise ValueError("shared_prefix: the fp8 KV arenas of the donors and the slots have different scale tables")
             batch_prefill([ses], [head], [rows])
             donor_passes[side] = -(-rows // ses.max_rows)
-    # (without donors sd_spec_queue_generate_shared is sd_spec_queue_generate, which has no room for the two row counts)
     args += (*[ses.handle if ses else None for ses in donors], rows)
     lp = LogprobBlock(dev, [len(log.host_seq) for log in logs]) if logprobs else None
     pb = PenaltyBlock(dev, pen, V, min(max(per_pass, gamma + 1), S * (gamma + 1))) if pen is not None else None
     eb = LogitEditBlock(dev, ed, V, min(max(per_pass, gamma + 1), S * (gamma + 1)), pb.rows if pb is not None else None) \
         if ed is not None else None
-    if eb is not None:
-        check(lib.sd_spec_queue_generate_edits(*args, row_sampling_array(triples), lp.block if lp is not None else None,
-                                               pb.block if pb is not None else None, eb.block), "sd_spec_queue_generate_edits")
-    elif pb is not None:
-        check(lib.sd_spec_queue_generate_penalties(*args, row_sampling_array(triples), lp.block if lp is not None else None, pb.block),
-              "sd_spec_queue_generate_penalties")
-    elif lp is not None:
-        check(lib.sd_spec_queue_generate_logprobs(*args, row_sampling_array(triples), lp.block), "sd_spec_queue_generate_logprobs")
-    elif triples is None:
-        check(lib.sd_spec_queue_generate_shared(*args), "sd_spec_queue_generate_shared")
-    else:
-        check(lib.sd_spec_queue_generate_rows(*args, row_sampling_array(triples)), "sd_spec_queue_generate_rows")
+    check(lib.sd_spec_queue_generate(*args, loop_opts(triples, lp, pb, eb)), "sd_spec_queue_generate")
     passes[4] += rows                                             # the donor's target rows are prompt rows too
     if vlog.block.err:
         raise RuntimeError("s")
@@ -462,8 +439,8 @@ def autoregressive_sampling_batch(xs: Sequence[torch.Tensor], model, N: int, eos
     log-softmax of its raw logits, before temperature, top_k and top_p - what the model says, not what the sampler drew from.
     ``repetition_penalty`` / ``frequency_penalty`` / ``presence_penalty`` (neutral 1 / 0 / 0): each one value for all streams or
     one per stream; stream i equals ``autoregressive_sampling(xs[i], ..., rng=DeviceNoise(seeds[i]))`` with its values
-    (sd_ar_batch_generate_penalties).  ``logit_bias`` / ``allowed_token_ids`` / ``banned_token_ids`` / ``min_tokens``: one
-    value for all streams or one per stream, as ``speculative_sampling_batch`` takes them (sd_ar_batch_generate_edits)."""
+    (member ``penalties`` of sd_loop_opts).  ``logit_bias`` / ``allowed_token_ids`` / ``banned_token_ids`` / ``min_tokens``: one
+    value for all streams or one per stream, as ``speculative_sampling_batch`` takes them (member ``edits``)."""
     B = len(xs)
     if not 1 <= B <= 16:
         raise ValueError(f"autoregressive_sampling_batch takes 1..16 streams per call, not {B}")

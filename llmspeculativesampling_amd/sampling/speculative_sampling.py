@@ -18,7 +18,7 @@ from .._lib import lib, check, SdAcceptResult
 from ..engine import as_specdec_model, _stream, check_token_ids, same_device
 from ._loop_common import (EDITS_NEED_NATIVE, LogitEditBlock, LogprobBlock, LoopLog, PenaltyBlock, accept_rates_f64,
                            cut_after_new_eos, details_dict, device_rng, edits_need_target_rows, bind_logit_edits, logit_edits,
-                           logprobs_need_target_rows, make_noise, open_stream, penalties_need_target_rows, penalty_triples,
+                           logprobs_need_target_rows, loop_opts, make_noise, open_stream, penalties_need_target_rows, penalty_triples,
                            raise_loop_error, reseed_uniforms, sampling_block, spec_scratch, spec_stream)
 
 _make_noise = make_noise                              # beam.py, multi.py and tests import it from here
@@ -241,15 +241,7 @@ def _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T,
         tick = process_time_ns()
         args = (stream, gamma, sampling, scratch, st, int(random_seed or 0), r_const.data_ptr() if r_const is not None else None,
                 _stream())
-        if eb is not None:
-            check(lib.sd_spec_generate_edits(*args, lp.block if lp is not None else None, pb.block if pb is not None else None, eb.block),
-                  "sd_spec_generate_edits")
-        elif pb is not None:
-            check(lib.sd_spec_generate_penalties(*args, lp.block if lp is not None else None, pb.block), "sd_spec_generate_penalties")
-        elif lp is None:
-            check(lib.sd_spec_generate(*args), "sd_spec_generate")
-        else:
-            check(lib.sd_spec_generate_logprobs(*args, lp.block), "sd_spec_generate_logprobs")
+        check(lib.sd_spec_generate(*args, loop_opts(None, lp, pb, eb)), "sd_spec_generate")
         other_time = process_time_ns() - tick            # host CPU time of the loop (enqueue + waits + bookkeeping)
         noise.seed, noise.draw = st.seed, st.draw
         raise_loop_error(st.err)

@@ -31,7 +31,7 @@ def test_ar_block_bytes():
     assert [_lib.lib.sd_ar_block_bytes(n) for n in (-1, 0, 17)] == [0, 0, 0]
 
 
-def _call(lib, table, n, log, without=""):
+def _call(lib, table, n, log, without="", opts=None):
     """sd_ar_batch_generate on placeholder buffers; ``without`` names a block to hand over as NULL."""
     from llmspeculativesampling_amd import _lib
     p = C.addressof((C.c_char * 256)())
@@ -39,7 +39,7 @@ def _call(lib, table, n, log, without=""):
     head = _lib.SdHeadScratch(logits=None if without == "logits" else p, ld_logits=128, norm_mode=0)
     block = None if without == "block" else p
     return lib.sd_ar_batch_generate(table, n, None if without == "sampling" else sampling, None if without == "head" else head,
-                                    None, block, block, None if without == "log" else log, None)
+                                    None, block, block, None if without == "log" else log, None, opts)
 
 
 def test_ar_generate_refuses_bad_arguments_before_any_launch():
@@ -65,6 +65,11 @@ def test_ar_generate_refuses_bad_arguments_before_any_launch():
     assert b"stream 1" in lib.sd_last_error() and b"prefilled" in lib.sd_last_error()
     table[1].cache_len = 9                                        # a cache longer than the sequence
     assert _call(lib, table, 2, log) == _lib.SD_ERR_INVALID and b"stream 1: cache_len 9 of 9" in lib.sd_last_error()
+    # the entry's own refusals come before anything in opts, and an empty block is a NULL one
+    bad = _lib.SdLoopOpts(row_params=(_lib.SdRowSampling * 2)(), penalties=C.pointer(_lib.SdPenaltyBlock()))
+    for opts in (bad, _lib.SdLoopOpts()):
+        assert _call(lib, table, 2, log, opts=opts) == _lib.SD_ERR_INVALID and b"stream 1: cache_len 9 of 9" in lib.sd_last_error()
+        assert _call(lib, table, 17, log, opts=opts) == _lib.SD_ERR_INVALID and b"n_streams 17 outside" in lib.sd_last_error()
     assert (log.n_steps, log.err) == (-7, -7)                     # nothing was written, nothing ran
     with pytest.raises(ValueError, match="sd_ar_batch_generate"):
         _lib.check(_lib.SD_ERR_INVALID, "sd_ar_batch_generate")

@@ -117,7 +117,7 @@ class _Direct:
         head = L.SdHeadScratch(logits=ses.logits.data_ptr(), ld_logits=ses.logits.stride(0), norm_mode=self.m.norm_mode)
         log = L.SdArLog(n_steps=-1, err=-1)
         rc = self.hip.lib.sd_ar_batch_generate(self.arr, self.B, sampling, head, kv._norm_ws.data_ptr(), self.dev_block.data_ptr(),
-                                               self.host_block.data_ptr(), log, _st())
+                                               self.host_block.data_ptr(), log, _st(), None)
         return rc, log.n_steps, log.err
 
 

@@ -474,7 +474,8 @@ def test_l5_bf16_fused_tail_equals_the_dense_tail_and_scores_stay_raw(hip):
 
 
 class _RecordingLib:
-    """The module's `lib` with every loop entry's name written down before the call goes through."""
+    """The module's `lib` with every loop entry's name and the set of non-NULL members of its last argument, the sd_loop_opts
+    (an empty set: opts was NULL), written down before the call goes through."""
 
     def __init__(self, lib, calls):
         self._lib, self._calls = lib, calls
@@ -485,15 +486,18 @@ class _RecordingLib:
             return fn
 
         def entry(*args):
-            self._calls.append(name)
+            opts = args[-1]
+            assert opts is None or isinstance(opts, _lib().SdLoopOpts), opts
+            self._calls.append((name, {f for f, _ in _lib().SdLoopOpts._fields_ if opts is not None and getattr(opts, f)}))
             return fn(*args)
         return entry
 
 
 def test_l6_which_entry_a_call_takes(hip, monkeypatch):
-    """Every wrapper's choice of entry, read off a recording `lib` in its module: neutral keywords (absent, or spelt out as
-    neutral values) take the entry the call took before the keywords existed, penalties alone the _penalties entry, edits -
-    with or without penalties and scores - the _edits entry."""
+    """Every wrapper's call, read off a recording `lib` in its module: neutral keywords (absent, or spelt out as neutral values)
+    produce the call that was made before the keywords existed - a NULL sd_loop_opts where nothing else asks for a member -
+    penalties alone set member penalties, edits member edits, with or without penalties and scores beside them.  The whole set
+    of non-NULL members is compared."""
     import importlib
     calls = []
     for mod in ("speculative_sampling", "batch", "autoregressive_sampling"):
@@ -513,26 +517,32 @@ def test_l6_which_entry_a_call_takes(hip, monkeypatch):
         fn(*args, **more)
         assert len(calls) == 1, calls
         return calls[0]
+    LP, PEN, ED = "logprobs", "penalties", "edits"
     single = lambda **more: took(hip.S.speculative_sampling, prompts[0], dm, tm, EOS, None, 6, rng=hip.noise.DeviceNoise(3), **kw, **more)
-    assert single() == single(**neutral1) == "sd_spec_generate"
-    assert single(logprobs=True) == single(logprobs=True, **neutral1) == "sd_spec_generate_logprobs"
-    assert single(**pen) == single(**pen, **neutral1) == "sd_spec_generate_penalties"
-    assert single(**edits1) == single(**edits1, **pen, logprobs=True) == single(min_tokens=1) == "sd_spec_generate_edits"
+    assert single() == single(**neutral1) == ("sd_spec_generate", set())
+    assert single(logprobs=True) == single(logprobs=True, **neutral1) == ("sd_spec_generate", {LP})
+    assert single(**pen) == single(**pen, **neutral1) == ("sd_spec_generate", {PEN})
+    assert single(**edits1) == single(min_tokens=1) == ("sd_spec_generate", {ED})
+    assert single(**edits1, **pen, logprobs=True) == ("sd_spec_generate", {LP, PEN, ED})
     batch = lambda **more: took(hip.S.speculative_sampling_batch, prompts, dm, tm, EOS, None, 6, seeds=SEEDS[:3], **kw, **more)
-    assert batch() == batch(**neutral3) == batch(**neutral1) == "sd_spec_batch_generate"
-    assert batch(logprobs=True, **neutral3) == "sd_spec_batch_generate_logprobs"
-    assert batch(**pen, **neutral3) == "sd_spec_batch_generate_penalties"
-    assert batch(**edits3) == batch(**edits1, **pen, logprobs=True) == "sd_spec_batch_generate_edits"
+    assert batch() == batch(**neutral3) == batch(**neutral1) == ("sd_spec_batch_generate", set())
+    assert batch(logprobs=True, **neutral3) == ("sd_spec_batch_generate", {LP})
+    assert batch(**pen, **neutral3) == ("sd_spec_batch_generate", {PEN})
+    assert batch(**edits3) == ("sd_spec_batch_generate", {ED})
+    assert batch(**edits1, **pen, logprobs=True) == ("sd_spec_batch_generate", {LP, PEN, ED})
+    assert batch(temperature=[1.0, 0.7, 1.0], **neutral3) == ("sd_spec_batch_generate", {"row_params"})
     queue = lambda **more: took(hip.S.speculative_sampling_queue_edits, prompts, dm, tm, EOS, None, 6, seeds=SEEDS[:3], slots=2, **kw, **more)
     plain = took(hip.S.speculative_sampling_queue_requests, prompts, dm, tm, EOS, None, 6, seeds=SEEDS[:3], slots=2, **kw)
-    assert plain == "sd_spec_queue_generate_shared" and queue() == queue(**neutral3) == queue(**neutral1) == plain
-    assert queue(logprobs=True, **neutral3) == "sd_spec_queue_generate_logprobs"
-    assert queue(**pen, **neutral3) == "sd_spec_queue_generate_penalties"
-    assert queue(**edits3) == queue(**edits1, **pen, logprobs=True) == "sd_spec_queue_generate_edits"
+    assert plain == ("sd_spec_queue_generate", set()) and queue() == queue(**neutral3) == queue(**neutral1) == plain
+    assert queue(logprobs=True, **neutral3) == ("sd_spec_queue_generate", {LP})
+    assert queue(**pen, **neutral3) == ("sd_spec_queue_generate", {PEN})
+    assert queue(**edits3) == ("sd_spec_queue_generate", {ED})
+    assert queue(**edits1, **pen, logprobs=True) == ("sd_spec_queue_generate", {LP, PEN, ED})
     ar = lambda **more: took(hip.S.autoregressive_sampling, prompts[0], tm, 6, EOS, rng=hip.noise.DeviceNoise(3), **kw, **more)
-    assert ar() == ar(**neutral1) == "sd_ar_batch_generate"
-    assert ar(**pen, **neutral1) == "sd_ar_batch_generate_penalties" and ar(**edits1) == ar(**edits1, **pen) == "sd_ar_batch_generate_edits"
+    assert ar() == ar(**neutral1) == ("sd_ar_batch_generate", set())
+    assert ar(**pen, **neutral1) == ("sd_ar_batch_generate", {PEN})
+    assert ar(**edits1) == ("sd_ar_batch_generate", {ED}) and ar(**edits1, **pen) == ("sd_ar_batch_generate", {PEN, ED})
     arb = lambda **more: took(hip.S.autoregressive_sampling_batch, prompts, tm, 6, EOS, seeds=SEEDS[:3], **kw, **more)
-    assert arb() == arb(**neutral3) == "sd_ar_batch_generate"
-    assert arb(logprobs=True, **neutral3) == "sd_ar_batch_generate_logprobs"
-    assert arb(**pen, **neutral3) == "sd_ar_batch_generate_penalties" and arb(**edits3) == "sd_ar_batch_generate_edits"
+    assert arb() == arb(**neutral3) == ("sd_ar_batch_generate", set())
+    assert arb(logprobs=True, **neutral3) == ("sd_ar_batch_generate", {LP})
+    assert arb(**pen, **neutral3) == ("sd_ar_batch_generate", {PEN}) and arb(**edits3) == ("sd_ar_batch_generate", {ED})

@@ -293,6 +293,34 @@ def test_batch_loop_with_per_stream_parameters_and_random_seed(hip):
     _assert_equal_runs(wants, outs, ds, "oracle")
 
 
+def test_the_loops_without_per_row_parameters_refuse_row_params(hip, monkeypatch):
+    """sd_spec_generate and sd_ar_batch_generate sample with sampling's own triple: a non-NULL row_params in their sd_loop_opts
+    is SD_ERR_INVALID behind the entry's own refusals (which read the sessions, hence a GPU test) and ahead of the other
+    members - the logprob block beside it is wrong too - and nothing runs: the same wrapper call without it gives the
+    tokens of an untouched Philox stream."""
+    import ctypes as C
+    import importlib
+    from llmspeculativesampling_amd import _lib
+    from llmspeculativesampling_amd.sampling import _loop_common as LC
+    dc, _, _, _, dm, tm = _pair_models("corr")
+    prompt = _prompts(dc.vocab_size, [9], 40)[0].cuda()
+    calls = {"sd_spec_generate": lambda rng: hip.S.speculative_sampling(prompt, dm, tm, -1, None, 6, gamma=4, rng=rng),
+             "sd_ar_batch_generate": lambda rng: hip.S.autoregressive_sampling(prompt, tm, 6, -1, rng=rng)}
+    keep = (_lib.SdRowSampling * 1)(_lib.SdRowSampling(1.0, 20, 0.9))
+    bad = lambda *a: _lib.SdLoopOpts(row_params=keep, logprobs=C.pointer(_lib.SdLogprobBlock()))
+    for mod, entry in (("speculative_sampling", "sd_spec_generate"), ("autoregressive_sampling", "sd_ar_batch_generate")):
+        m = importlib.import_module("llmspeculativesampling_amd.sampling." + mod)
+        want = calls[entry](hip.noise.DeviceNoise(77))
+        rng = hip.noise.DeviceNoise(77)
+        monkeypatch.setattr(m, "loop_opts", bad)
+        with pytest.raises((ValueError, RuntimeError)) as e:
+            calls[entry](rng)
+        err = e.value if isinstance(e.value, ValueError) else e.value.__cause__   # (speculative_sampling re-raises as the reference does)
+        assert isinstance(err, ValueError) and entry + ": row_params: " in str(err), err
+        monkeypatch.setattr(m, "loop_opts", LC.loop_opts)
+        assert torch.equal(calls[entry](rng), want)               # (the refused call drew nothing)
+
+
 COUNTS = ("iterations", "target_passes", "draft_passes", "extra_passes", "prefill_passes", "prompt_rows", "admit_iter", "finish_iter")
 
 

@@ -1,5 +1,5 @@
 """The prompt queue with a shared prompt prefix (`pytest -m gpu`): speculative_sampling_queue_shared(shared_prefix=P) /
-sd_spec_queue_generate_shared - the prefix goes through each model once, into a donor pair of sessions, and every admitted
+sd_spec_queue_generate with donor sessions - the prefix goes through each model once, into a donor pair of sessions, and every admitted
 prompt starts on a copy of its K / V rows.  Held per prompt to the CPU oracle on that prompt's own Philox stream and to the
 same call without sharing; the row and pass counts are derived from the prompt lengths, not measured."""
 import functools

@@ -14,7 +14,7 @@ def test_library_exports_every_declared_symbol():
     from test_abi_cpu import test_every_declared_symbol_is_bound_and_exported as whole_header_check
     whole_header_check()
     from llmspeculativesampling_amd import _lib
-    assert _lib.lib.sd_version() == 6           # a host-only call: no GPU needed
+    assert _lib.lib.sd_version() == 7           # a host-only call: no GPU needed
 
 
 def test_struct_layouts_match_header():
@@ -478,12 +478,12 @@ def test_new_entry_points_reject_null_arguments_without_a_gpu():
     scratch.draft.logits = scratch.target.logits = P
     dev = _lib.SdSpecStream(P, P, P, P, P, P, P, P)
     for dv, st in ((None, state), (dev, None)):   # a null stream block, a null state block (test_spec_native_cpu.py has the rest)
-        assert lib.sd_spec_generate(dv, 4, sampling, scratch, st, 0, None, None) == _lib.SD_ERR_INVALID
+        assert lib.sd_spec_generate(dv, 4, sampling, scratch, st, 0, None, None, None) == _lib.SD_ERR_INVALID
         assert b"sd_spec_generate" in lib.sd_last_error()
     streams = (_lib.SdBatchStream * 1)()
     for args in ((None, 0, sampling, scratch, log), (streams, 1, None, scratch, log), (streams, 1, sampling, None, log),
                  (streams, 1, sampling, scratch, None)):
-        assert lib.sd_spec_batch_generate(*args[:2], 4, args[2], 0, None, *args[3:], None) == _lib.SD_ERR_INVALID
+        assert lib.sd_spec_batch_generate(*args[:2], 4, args[2], 0, None, *args[3:], None, None) == _lib.SD_ERR_INVALID
         assert b"sd_spec_batch_generate" in lib.sd_last_error()
     assert (state.n_iters, state.err, log.n_iters, log.err) == (-7, -7, -7, -7)         # nothing was written
     assert lib.sd_accept_resample(None, None, 32000, 32000, None, 4, 4, None, 1, 0, 0, None, None, 0, 0, None, None) \

@@ -1,7 +1,8 @@
-"""Per-request logit_bias / allowed_token_ids / banned_token_ids / min_tokens: what needs no GPU - the additive ABI (five new
-symbols, three new structs, sd_version() still 6), sampling.utils.apply_logit_edits against a plain per-element loop in the
+"""Per-request logit_bias / allowed_token_ids / banned_token_ids / min_tokens: what needs no GPU - the ABI (one symbol, three
+structs; the loops take the block as member edits of sd_loop_opts; sd_version() 7), sampling.utils.apply_logit_edits against a
+plain per-element loop in the
 five rounding / dtype modes, the composition order with apply_penalties, the mask builder, every refusal that comes before a
-model is touched, the refusals of sd_edit_rows (all before a launch), and which entry a call takes."""
+model is touched, the refusals of sd_edit_rows (all before a launch), and which members of sd_loop_opts a call sets."""
 import ctypes as C
 import importlib
 import inspect
@@ -20,8 +21,9 @@ from llmspeculativesampling_amd.sampling import _loop_common as LC
 from llmspeculativesampling_amd.sampling.utils import apply_logit_edits, apply_penalties
 
 AR = importlib.import_module("llmspeculativesampling_amd.sampling.autoregressive_sampling")   # (the package exports the function)
-NEW = ("sd_edit_rows", "sd_spec_generate_edits", "sd_spec_batch_generate_edits", "sd_spec_queue_generate_edits",
-       "sd_ar_batch_generate_edits")
+NEW = ("sd_edit_rows",)
+REMOVED = ("sd_spec_generate_edits", "sd_spec_batch_generate_edits", "sd_spec_queue_generate_edits",
+           "sd_ar_batch_generate_edits")                                        # ABI 7: member edits of sd_loop_opts
 SYM = {name: (res, args) for name, res, args in _lib.SYMBOLS}
 PROTOS, STRUCTS = abi_header.parse()
 KEYWORDS = {"logit_bias": None, "allowed_token_ids": None, "banned_token_ids": None, "min_tokens": 0}
@@ -39,7 +41,9 @@ def test_new_symbols_are_declared_bound_and_exported():
         fn = getattr(_lib.lib, name)
         assert fn.restype is C.c_int and list(fn.argtypes) == list(SYM[name][1])
         assert PROTOS[name][1] == [abi_header.ctypes_class(t) for t in SYM[name][1]], name
-    assert _lib.lib.sd_version() == 6
+    for name in REMOVED:
+        assert name not in PROTOS and name not in SYM and not hasattr(raw, name), name
+    assert _lib.lib.sd_version() == 7
     assert "#define SD_EDIT_MAX_BIAS 1024" in open(abi_header.HEADER).read() and _lib.SD_EDIT_MAX_BIAS == 1024
 
 
@@ -57,12 +61,6 @@ def test_new_structs_match_the_header():
     n = len(_lib.SdPenaltyItem._fields_)
     assert STRUCTS["sd_logit_edit_item"][0][:n] == STRUCTS["sd_penalty_item"][0]
     assert C.sizeof(_lib.SdPenaltyItem) == 72 and C.sizeof(_lib.SdPenaltyBlock) == 32 and C.sizeof(_lib.SdPenalty) == 12
-
-
-def test_loop_entries_extend_the_penalties_argument_lists():
-    tail = [C.POINTER(_lib.SdLogitEditBlock)]
-    for loop in ("sd_spec_generate", "sd_spec_batch_generate", "sd_spec_queue_generate", "sd_ar_batch_generate"):
-        assert SYM[loop + "_edits"][1] == SYM[loop + "_penalties"][1] + tail, loop
 
 
 @pytest.mark.parametrize("name", FREE + ["speculative_sampling_queue_edits"])
@@ -342,20 +340,23 @@ def test_edit_rows_refusals_come_before_any_launch():
         assert _one(edit=edit) == _lib.SD_ERR_INVALID and "item 0" in err() and word in err(), (edit, err())
 
 
-# ----------------------------------------------------------------------------- which entry a call takes
+# ----------------------------------------------------------------------------- which members of sd_loop_opts a call sets
 class _Called(Exception):
     pass
 
 
 class _RecordingLib:
-    """Stands in for the module's `lib`: sd_ar_block_bytes answers, every loop entry says its name and stops the call."""
+    """Stands in for the module's `lib`: sd_ar_block_bytes answers, every loop entry says its name, its argument count and the
+    set of non-NULL members of its last argument, the sd_loop_opts (an empty set: opts was NULL), and stops the call."""
 
     def sd_ar_block_bytes(self, n):
         return 8 * n
 
     def __getattr__(self, name):
         def entry(*args):
-            raise _Called(name, len(args))
+            opts = args[-1]
+            assert opts is None or isinstance(opts, _lib.SdLoopOpts), opts
+            raise _Called(name, len(args), {f for f, _ in _lib.SdLoopOpts._fields_ if opts is not None and getattr(opts, f)})
         return entry
 
 
@@ -376,21 +377,22 @@ def _fake_run(monkeypatch):
 
 def test_neutral_calls_take_the_entry_they_took_before(monkeypatch):
     """generate() - behind autoregressive_sampling and autoregressive_sampling_batch - with the records logit_edits returns: None
-    (every neutral spelling) leaves the choice of entry to logprobs and penalties as before; records go to the _edits entry, with
-    and without a penalty block."""
+    (every neutral spelling) makes the call that was made before the keywords existed - a NULL sd_loop_opts, or the members
+    logprobs and penalties alone ask for; records set member edits, with and without a penalty block.  The whole set of non-NULL
+    members is compared, and a call that sets none passes NULL, not an empty block."""
     run = _fake_run(monkeypatch)
     neutral = LC.logit_edits(2, "stream", 64, 2, logit_bias=[None, {}], allowed_token_ids=None, banned_token_ids=[[], None], min_tokens=[0, 0])
     assert neutral is None
     pens = [(1.0, 0.0, 0.5), (1.0, 0.0, 0.0)]
     recs = LC.logit_edits(2, "stream", 64, 2, logit_bias=[{5: 1.0}, None], min_tokens=3, banned_token_ids=[7])
-    for kw, want in ((dict(edits=neutral), "sd_ar_batch_generate"), (dict(edits=neutral, logprobs=True), "sd_ar_batch_generate_logprobs"),
-                     (dict(edits=neutral, penalties=pens), "sd_ar_batch_generate_penalties"),
-                     (dict(edits=recs), "sd_ar_batch_generate_edits"), (dict(edits=recs, penalties=pens, logprobs=True), "sd_ar_batch_generate_edits")):
+    for kw, want in ((dict(edits=neutral), set()), (dict(edits=neutral, logprobs=True), {"logprobs"}),
+                     (dict(edits=neutral, penalties=pens), {"penalties"}),
+                     (dict(edits=neutral, penalties=pens, logprobs=True), {"logprobs", "penalties"}),
+                     (dict(edits=recs), {"edits"}), (dict(edits=recs, penalties=pens), {"penalties", "edits"}),
+                     (dict(edits=recs, penalties=pens, logprobs=True), {"logprobs", "penalties", "edits"})):
         with pytest.raises(_Called) as e:
             run.generate(**kw)
-        assert e.value.args[0] == want, (kw, e.value.args)
-        assert e.value.args[1] == 9 + {"sd_ar_batch_generate": 0, "sd_ar_batch_generate_logprobs": 1, "sd_ar_batch_generate_penalties": 2,
-                                       "sd_ar_batch_generate_edits": 3}[want]
+        assert e.value.args == ("sd_ar_batch_generate", 10, want), (kw, e.value.args)
 
 
 def test_edit_block_uploads_one_tensor_per_kind():

@@ -1,5 +1,5 @@
-"""Per-token target log-probabilities from the native decode loops: what needs no GPU - the additive ABI (five new symbols, two
-new structs), the keyword on the four free functions, the queue function's parameter list, the refusals that come before a
+"""Per-token target log-probabilities from the native decode loops: what needs no GPU - the ABI (one symbol, two structs; the loops
+take the block as member logprobs of sd_loop_opts), the keyword on the four free functions, the queue function's parameter list, the refusals that come before a
 model is touched, the refusals of sd_token_logprobs (all before a launch), the helper's float64 truth and the score."""
 import ctypes as C
 import inspect
@@ -14,8 +14,9 @@ import logprob_rows as LR
 import llmspeculativesampling_amd.sampling as S
 from llmspeculativesampling_amd import _lib, quality
 
-NEW = ("sd_token_logprobs", "sd_spec_generate_logprobs", "sd_spec_batch_generate_logprobs", "sd_spec_queue_generate_logprobs",
-       "sd_ar_batch_generate_logprobs")
+NEW = ("sd_token_logprobs",)
+REMOVED = ("sd_spec_generate_logprobs", "sd_spec_batch_generate_logprobs", "sd_spec_queue_generate_logprobs",
+           "sd_ar_batch_generate_logprobs")                                     # ABI 7: member logprobs of sd_loop_opts
 SYM = {name: (res, args) for name, res, args in _lib.SYMBOLS}
 PROTOS, STRUCTS = abi_header.parse()
 
@@ -27,6 +28,9 @@ def test_new_symbols_are_declared_bound_and_exported():
         assert hasattr(raw, name), name
         fn = getattr(_lib.lib, name)
         assert fn.restype is C.c_int and list(fn.argtypes) == list(SYM[name][1])
+    for name in REMOVED:
+        assert name not in PROTOS and name not in SYM and not hasattr(raw, name), name
+    assert _lib.lib.sd_version() == 7
 
 
 def test_new_structs_match_the_header():
@@ -37,14 +41,6 @@ def test_new_structs_match_the_header():
     # what the existing entries must keep
     assert C.sizeof(_lib.SdAcceptResult) == 208 == STRUCTS["sd_accept_result"][1]
     assert [_lib.lib.sd_ar_block_bytes(n) for n in (0, 1, 2, 3, 16, 17)] == [0, 16, 16, 32, 128, 0]
-
-
-def test_loop_entries_extend_the_widest_existing_argument_lists():
-    tail = [C.POINTER(_lib.SdLogprobBlock)]
-    assert SYM["sd_spec_generate_logprobs"][1] == SYM["sd_spec_generate"][1] + tail
-    assert SYM["sd_spec_batch_generate_logprobs"][1] == SYM["sd_spec_batch_generate_rows"][1] + tail
-    assert SYM["sd_spec_queue_generate_logprobs"][1] == SYM["sd_spec_queue_generate_rows"][1] + tail
-    assert SYM["sd_ar_batch_generate_logprobs"][1] == SYM["sd_ar_batch_generate"][1] + tail
 
 
 @pytest.mark.parametrize("name", ["speculative_sampling", "speculative_sampling_batch", "autoregressive_sampling",

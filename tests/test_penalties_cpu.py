@@ -1,5 +1,6 @@
-"""Per-request repetition / frequency / presence penalties: what needs no GPU - the additive ABI (five new symbols, three new
-structs, sd_version() still 6), the keywords on the four free functions and the new queue function, the refusals that come
+"""Per-request repetition / frequency / presence penalties: what needs no GPU - the ABI (one symbol, three structs; the
+loops take the block as member penalties of sd_loop_opts; sd_version() 7), the keywords on the four free functions and the new
+queue function, the refusals that come
 before a model is touched, the refusals of sd_penalize_rows (all before a launch), sampling.utils.apply_penalties against a
 hand-computed example (and HF's RepetitionPenaltyLogitsProcessor where transformers imports), and the wrapped oracle model
 (tests/penalised_model.py) against a forward without a cache."""
@@ -20,8 +21,9 @@ from llmspeculativesampling_amd.config import load_config
 from llmspeculativesampling_amd.sampling.utils import apply_penalties
 from llmspeculativesampling_amd.synth import make_state_dict
 
-NEW = ("sd_penalize_rows", "sd_spec_generate_penalties", "sd_spec_batch_generate_penalties", "sd_spec_queue_generate_penalties",
-       "sd_ar_batch_generate_penalties")
+NEW = ("sd_penalize_rows",)
+REMOVED = ("sd_spec_generate_penalties", "sd_spec_batch_generate_penalties", "sd_spec_queue_generate_penalties",
+           "sd_ar_batch_generate_penalties")                                    # ABI 7: member penalties of sd_loop_opts
 SYM = {name: (res, args) for name, res, args in _lib.SYMBOLS}
 PROTOS, STRUCTS = abi_header.parse()
 KEYWORDS = {"repetition_penalty": 1.0, "frequency_penalty": 0.0, "presence_penalty": 0.0}
@@ -35,7 +37,9 @@ def test_new_symbols_are_declared_bound_and_exported():
         assert hasattr(raw, name), name
         fn = getattr(_lib.lib, name)
         assert fn.restype is C.c_int and list(fn.argtypes) == list(SYM[name][1])
-    assert _lib.lib.sd_version() == 6
+    for name in REMOVED:
+        assert name not in PROTOS and name not in SYM and not hasattr(raw, name), name
+    assert _lib.lib.sd_version() == 7
 
 
 def test_new_structs_match_the_header():
@@ -49,12 +53,6 @@ def test_new_structs_match_the_header():
         assert [(f, getattr(cls, f).offset, getattr(cls, f).size) for f, _ in cls._fields_] == STRUCTS[name][0]
     # what the existing entries must keep
     assert C.sizeof(_lib.SdLogprobItem) == 48 and C.sizeof(_lib.SdLogprobBlock) == 24 and C.sizeof(_lib.SdAcceptResult) == 208
-
-
-def test_loop_entries_extend_the_logprobs_argument_lists():
-    tail = [C.POINTER(_lib.SdPenaltyBlock)]
-    for loop in ("sd_spec_generate", "sd_spec_batch_generate", "sd_spec_queue_generate", "sd_ar_batch_generate"):
-        assert SYM[loop + "_penalties"][1] == SYM[loop + "_logprobs"][1] + tail, loop
 
 
 @pytest.mark.parametrize("name", FREE + ["speculative_sampling_queue_requests"])

@@ -128,7 +128,7 @@ def test_blocked_symbols_are_exported_declared_and_bound():
         assert hasattr(raw, name) and bound[name] is C.c_int, name
     assert _lib.lib.sd_session_prefill_attn_blocked_launches(None) == 0        # (a host integer: no session, no count)
     assert callable(engine.Session.prefill_attn_blocked_launches)
-    assert _lib.lib.sd_version() == 6
+    assert _lib.lib.sd_version() == 7
 
 
 # ----------------------------------------------------------------------------- layouts

@@ -1,5 +1,5 @@
 """Host-side checks of the prompt queue's shared prompt prefix (speculative_sampling_queue_shared(shared_prefix=P),
-sd_spec_queue_generate_shared, sd_session_copy_kv): the argument is refused before a model is built, the new symbols and
+sd_spec_queue_generate's donors, sd_session_copy_kv): the argument is refused before a model is built, the new symbols and
 the copy item's layout match the header, and the native entry points refuse what needs no GPU to refuse.  No GPU needed."""
 import ctypes as C
 import re
@@ -83,11 +83,12 @@ def test_new_symbols_are_exported_and_declared():
     from llmspeculativesampling_amd import _lib
     bound = {n: (res, args) for n, res, args in _lib.SYMBOLS}
     raw = C.CDLL(_lib.LIB_PATH)
-    for name in ("sd_session_copy_kv", "sd_spec_queue_generate_shared"):
+    for name in ("sd_session_copy_kv", "sd_spec_queue_generate"):
         assert hasattr(raw, name) and bound[name][0] is C.c_int, name
-    # all of sd_spec_queue_generate's arguments, then the two donors and the row count
-    assert list(bound["sd_spec_queue_generate_shared"][1][:-3]) == list(bound["sd_spec_queue_generate"][1])
-    assert list(bound["sd_spec_queue_generate_shared"][1][-3:]) == [C.c_void_p, C.c_void_p, C.c_int]
+    # ABI 7: the queue has one entry, which takes the two donors and the row count ahead of its sd_loop_opts
+    # (test_abi_cpu.py has the whole list)
+    assert "sd_spec_queue_generate_shared" not in bound and not hasattr(raw, "sd_spec_queue_generate_shared")
+    assert list(bound["sd_spec_queue_generate"][1][-4:]) == [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_lib.SdLoopOpts)]
 
 
 def test_copy_item_layout_matches_the_header():
@@ -120,14 +121,14 @@ def test_shared_entry_point_refuses_bad_arguments_before_any_launch():
     prompts = (_lib.SdQueuePrompt * 2)()
 
     def call(donor_draft=None, donor_target=None, rows=0, n_slots=2, lg=log):
-        return lib.sd_spec_queue_generate_shared(slots, n_slots, 64, prompts, 2, 0, 4, sampling, 0, None, scratch, lg, None, None,
-                                                 donor_draft, donor_target, rows)
+        return lib.sd_spec_queue_generate(slots, n_slots, 64, prompts, 2, 0, 4, sampling, 0, None, scratch, lg, None, None,
+                                          donor_draft, donor_target, rows, None)
 
     for args in ((None, None, 3), (p, None, 3), (None, p, 3), (p, p, 0), (None, None, -1)):
         assert call(*args) == _lib.SD_ERR_INVALID
-        assert re.search(r"sd_spec_queue_generate_shared: shared_rows -?\d+ needs both donor sessions", lib.sd_last_error().decode())
-    assert call(n_slots=17) == _lib.SD_ERR_INVALID and b"sd_spec_queue_generate_shared: n_slots 17" in lib.sd_last_error()
-    # without donors the checks are sd_spec_queue_generate's, under the called entry point's name
-    assert call() == _lib.SD_ERR_INVALID and b"sd_spec_queue_generate_shared: slot 0: null pointer" in lib.sd_last_error()
-    assert call(lg=None) == _lib.SD_ERR_INVALID and b"sd_spec_queue_generate_shared: null argument" in lib.sd_last_error()
+        assert re.search(r"sd_spec_queue_generate: shared_rows -?\d+ needs both donor sessions", lib.sd_last_error().decode())
+    assert call(n_slots=17) == _lib.SD_ERR_INVALID and b"sd_spec_queue_generate: n_slots 17" in lib.sd_last_error()
+    # without donors the checks are the same, under the same name
+    assert call() == _lib.SD_ERR_INVALID and b"sd_spec_queue_generate: slot 0: null pointer" in lib.sd_last_error()
+    assert call(lg=None) == _lib.SD_ERR_INVALID and b"sd_spec_queue_generate: null argument" in lib.sd_last_error()
     assert (log.n_iters, log.err) == (-7, -7)                     # nothing was written, nothing ran

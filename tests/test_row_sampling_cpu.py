@@ -1,15 +1,17 @@
-"""Per-request temperature / top_k / top_p in the lock-step loops: what needs no GPU - the additive ABI (four new symbols, one
-new struct, version unchanged), the refusals of sd_norm_batch_rows and the argument checks of the three Python entries."""
+"""Per-request temperature / top_k / top_p in the lock-step loops: what needs no GPU - the ABI (two symbols, one struct; the
+loops take the array as member row_params of sd_loop_opts), the refusals of sd_norm_batch_rows and the argument checks of the three Python entries."""
 import ctypes as C
 
 import pytest
 import torch
 
+import abi_header
 from llmspeculativesampling_amd import _lib
 from llmspeculativesampling_amd.sampling import (speculative_sampling_batch, speculative_sampling_queue,
                                                  speculative_sampling_queue_shared)
 
-NEW = ("sd_norm_batch_rows", "sd_norm_batch_rows_debug", "sd_spec_batch_generate_rows", "sd_spec_queue_generate_rows")
+NEW = ("sd_norm_batch_rows", "sd_norm_batch_rows_debug")
+REMOVED = ("sd_spec_batch_generate_rows", "sd_spec_queue_generate_rows")      # ABI 7: member row_params of sd_loop_opts
 SYM = {name: (res, args) for name, res, args in _lib.SYMBOLS}
 
 
@@ -19,19 +21,16 @@ def test_new_symbols_are_exported_and_bound():
         assert SYM[name][0] is C.c_int
         fn = getattr(_lib.lib, name)
         assert fn.restype is C.c_int and list(fn.argtypes) == list(SYM[name][1])
+    protos, raw = abi_header.parse()[0], C.CDLL(_lib.LIB_PATH)
+    for name in REMOVED:
+        assert name not in protos and name not in SYM and not hasattr(raw, name), name
 
 
 def test_row_sampling_struct_and_version():
     assert _lib.C_STRUCTS["sd_row_sampling"] is _lib.SdRowSampling
     assert C.sizeof(_lib.SdRowSampling) == 12
     assert [n for n, _ in _lib.SdRowSampling._fields_] == ["temperature", "top_k", "top_p"]
-    assert _lib.lib.sd_version() == 6
-
-
-def test_rows_loop_entries_extend_the_existing_argument_lists():
-    tail = [C.POINTER(_lib.SdRowSampling)]
-    assert SYM["sd_spec_batch_generate_rows"][1] == SYM["sd_spec_batch_generate"][1] + tail
-    assert SYM["sd_spec_queue_generate_rows"][1] == SYM["sd_spec_queue_generate_shared"][1] + tail
+    assert _lib.lib.sd_version() == 7
 
 
 def _norm_rows(params, n):

@@ -20,9 +20,9 @@ def _blocks(gamma_rows=5):
     return dev, sampling, scratch, seq
 
 
-def _refused(text, dev, gamma, sampling, scratch, seq, random_seed=0, r_const=None):
+def _refused(text, dev, gamma, sampling, scratch, seq, random_seed=0, r_const=None, opts=None):
     lib = _lib.lib
-    assert lib.sd_spec_generate(dev, gamma, sampling, scratch, seq, random_seed, r_const, None) == _lib.SD_ERR_INVALID
+    assert lib.sd_spec_generate(dev, gamma, sampling, scratch, seq, random_seed, r_const, None, opts) == _lib.SD_ERR_INVALID
     msg = lib.sd_last_error().decode()
     assert msg.startswith("sd_spec_generate:") and text in msg, msg
 
@@ -62,6 +62,11 @@ def test_spec_generate_refusals_come_in_the_documented_order():
     sampling.temperature = 0.5
     _refused("workspace of 4 rows", dev, 4, sampling, scratch, seq)
     _refused("workspace of 4 rows", dev, 16, sampling, scratch, seq)
+    # the entry's own refusals come before anything in opts, and an empty block is a NULL one
+    bad = _lib.SdLoopOpts(row_params=(_lib.SdRowSampling * 1)(), logprobs=C.pointer(_lib.SdLogprobBlock()))
+    for opts in (bad, _lib.SdLoopOpts()):
+        _refused("gamma 17 outside 1..16", dev, 17, sampling, scratch, seq, opts=opts)
+        _refused("workspace of 4 rows", dev, 4, sampling, scratch, seq, opts=opts)
     assert (seq.n_iters, seq.err, seq.len) == (-7, -7, 9)         # nothing was written, nothing ran
     with pytest.raises(ValueError, match="sd_spec_generate"):
         _lib.check(_lib.SD_ERR_INVALID, "sd_spec_generate")

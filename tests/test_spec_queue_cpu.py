@@ -70,11 +70,12 @@ def test_queue_symbols_are_exported_and_declared():
     for name in NEW:
         assert hasattr(raw, name) and bound[name][0] is C.c_int, name
     # the batch loop's arguments - the same three blocks among them - plus slot_cap, prompts, n_prompts, prefill_chunk, passes_out
-    streams, n, *rest, stream = bound["sd_spec_batch_generate"][1]
+    # and, behind the stream, the two donors and their row count; both end in the sd_loop_opts
+    streams, n, *rest, stream, opts = bound["sd_spec_batch_generate"][1]
     blocks = [C.POINTER(_lib.SdSampling), C.POINTER(_lib.SdSpecScratch), C.POINTER(_lib.SdLockstepLog)]
-    assert [a for a in rest if a in blocks] == blocks
+    assert [a for a in rest if a in blocks] == blocks and opts == C.POINTER(_lib.SdLoopOpts)
     assert list(bound["sd_spec_queue_generate"][1]) == [streams, n, C.c_int, C.POINTER(_lib.SdQueuePrompt), C.c_int, C.c_int, *rest,
-                                                        C.c_void_p, stream]
+                                                        C.c_void_p, stream, C.c_void_p, C.c_void_p, C.c_int, opts]
 
 
 @pytest.mark.parametrize("cname,pyname,size", [("sd_queue_prompt", "SdQueuePrompt", 80), ("sd_queue_pass", "SdQueuePass", 16),
@@ -102,7 +103,8 @@ def test_queue_generate_refuses_bad_arguments_before_any_launch():
     prompts = (_lib.SdQueuePrompt * 2)()
 
     def call(n_slots=2, slot_cap=64, n_prompts=2, chunk=0, gamma=4, sl=slots, pr=prompts, sm=sampling, sc=scratch, lg=log):
-        return lib.sd_spec_queue_generate(sl, n_slots, slot_cap, pr, n_prompts, chunk, gamma, sm, 0, None, sc, lg, None, None)
+        return lib.sd_spec_queue_generate(sl, n_slots, slot_cap, pr, n_prompts, chunk, gamma, sm, 0, None, sc, lg, None, None,
+                                          None, None, 0, None)
 
     for n in (0, 17, -1):
         assert call(n_slots=n) == _lib.SD_ERR_INVALID and re.search(r"n_slots -?\d+ outside 1\.\.16", lib.sd_last_error().decode())
