@@ -181,6 +181,30 @@ __device__ __forceinline__ f32x4 load_f32x4_sc1(const float *p) {
     return f32x4{__uint_as_float((unsigned)a), __uint_as_float((unsigned)(a >> 32)), __uint_as_float((unsigned)b),
                  __uint_as_float((unsigned)(b >> 32))};
 }
+// One burst of the finishing GEMM on records: T tiles and their rows requested, every tile decoded straight-line as it
+// lands, ONE uniform branch (the OR of the T escape counts) to the repair of the decoded fragments, T MFMAs back to back.
+template <int T, typename H, typename WF>
+__device__ __forceinline__ f32x4 fin_records_burst(const WF &wf, const H *xp, int lane, f32x4 acc) {
+    typename WF::Frag w[T];
+    u32x4 x[T], wz[T];
+#pragma unroll
+    for (int u = 0; u < T; ++u) w[u] = wf.fetch((size_t)u);
+#pragma unroll
+    for (int u = 0; u < T; ++u) x[u] = *reinterpret_cast<const u32x4 *>(xp + u * 512);
+    unsigned esc = 0u;
+#pragma unroll
+    for (int u = 0; u < T; ++u) {
+        wz[u] = WF::decode(w[u]);
+        esc |= w[u].m[0];
+    }
+    if (w12_escapes(esc) != 0u) {
+#pragma unroll
+        for (int u = 0; u < T; ++u) WF::repair(wz[u], w[u], lane);
+    }
+#pragma unroll
+    for (int u = 0; u < T; ++u) acc = mfma16<H>(wz[u], x[u], acc);
+    return acc;
+}
 template <typename H = bf16_t, typename WF = WFetchBf16>
 __global__ __launch_bounds__(256) void gemm_bf16_stream_fin(typename WF::Arg Wp, const H *__restrict__ X,
                                                            float *__restrict__ part, int M, int N, int K, int SB,
@@ -188,8 +212,10 @@ __global__ __launch_bounds__(256) void gemm_bf16_stream_fin(typename WF::Arg Wp,
                                                            unsigned want, unsigned *__restrict__ wait_status) {
     constexpr int U = 4;
     __shared__ f32x4 red[4][1][64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int NTG = N >> 4, KS = K >> 5;
+    const int lane = threadIdx.x & 63;
+    int wv = threadIdx.x >> 6;
+    if constexpr (WF::kRecords) wv = __builtin_amdgcn_readfirstlane(wv);     // a wave's k-range and its loops in scalar registers:
+    const int NTG = N >> 4, KS = K >> 5;                                     // the side records of the tail are scalar loads too
     const int sb = blockIdx.x / NTG, ntg = blockIdx.x - sb * NTG;
     const bool fin = sb == SB - 1;
     const int kb0 = sb * ks_per_blk, kb1 = min(KS, kb0 + ks_per_blk);
@@ -201,27 +227,38 @@ __global__ __launch_bounds__(256) void gemm_bf16_stream_fin(typename WF::Arg Wp,
     const H *xp = X + (size_t)ksa * 512 + ((lane >> 4) * 16 + mrow) * 8;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     int ks = ks0;
-    for (; ks + U <= ks1; ks += U) {
-        typename WF::Frag w[U];
-        u32x4 x[U];
+    if constexpr (WF::kRecords) {
+        for (; ks + U <= ks1; ks += U) {
+            acc = fin_records_burst<U, H>(wf, xp, lane, acc);
+            wf.advance(U); xp += U * 512;
+        }
+        const int rem = ks1 - ks;                                 // the last < 4 k-steps as one burst too
+        if (rem == 3) acc = fin_records_burst<3, H>(wf, xp, lane, acc);
+        else if (rem == 2) acc = fin_records_burst<2, H>(wf, xp, lane, acc);
+        else if (rem == 1) acc = fin_records_burst<1, H>(wf, xp, lane, acc);
+    } else {
+        for (; ks + U <= ks1; ks += U) {
+            typename WF::Frag w[U];
+            u32x4 x[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) w[u] = wf.fetch((size_t)u);
+            for (int u = 0; u < U; ++u) w[u] = wf.fetch((size_t)u);
 #pragma unroll
-        for (int u = 0; u < U; ++u) x[u] = *reinterpret_cast<const u32x4 *>(xp + u * 512);
+            for (int u = 0; u < U; ++u) x[u] = *reinterpret_cast<const u32x4 *>(xp + u * 512);
 #pragma unroll
-        for (int u = 0; u < U; ++u) acc = mfma16<H>(WF::frag(w[u], lane), x[u], acc);
-        wf.advance(U); xp += U * 512;
-    }
-    if (ks < ks1) {                                               // the last < 4 k-steps as one burst too
-        const int rem = ks1 - ks;
-        typename WF::Frag w[U - 1];
-        u32x4 x[U - 1];
+            for (int u = 0; u < U; ++u) acc = mfma16<H>(WF::frag(w[u], lane), x[u], acc);
+            wf.advance(U); xp += U * 512;
+        }
+        if (ks < ks1) {                                           // the last < 4 k-steps as one burst too
+            const int rem = ks1 - ks;
+            typename WF::Frag w[U - 1];
+            u32x4 x[U - 1];
 #pragma unroll
-        for (int u = 0; u < U - 1; ++u)
-            if (u < rem) { w[u] = wf.fetch((size_t)u); x[u] = *reinterpret_cast<const u32x4 *>(xp + u * 512); }
+            for (int u = 0; u < U - 1; ++u)
+                if (u < rem) { w[u] = wf.fetch((size_t)u); x[u] = *reinterpret_cast<const u32x4 *>(xp + u * 512); }
 #pragma unroll
-        for (int u = 0; u < U - 1; ++u)
-            if (u < rem) acc = mfma16<H>(WF::frag(w[u], lane), x[u], acc);
+            for (int u = 0; u < U - 1; ++u)
+                if (u < rem) acc = mfma16<H>(WF::frag(w[u], lane), x[u], acc);
+        }
     }
     red[wv][0][lane] = acc;
     __syncthreads();

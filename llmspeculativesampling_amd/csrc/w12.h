@@ -31,14 +31,23 @@ typedef u32x3 u32x3_a4 __attribute__((aligned(4)));             // (a 12-byte re
 
 struct W12Arg { const unsigned *codes; const u32x4 *meta; };
 
-__device__ __forceinline__ u32x4 w12_decode(u32x3 p, u32x4 m, int lane) {
-    const unsigned base = m[0] & 0xffu, bb = base * 0x00800080u;
+// The decode comes in two parts, so that a kernel can decode a whole burst of tiles straight-line and settle the escapes of
+// the burst behind ONE uniform branch (gemm_bf16_stream_fin, normload_kernels.h): the codes under the tile's base, no
+// branch, and the repair of the decoded fragment from the side record.  w12_escapes is the burst's predicate: OR the m[0]
+// words of the burst's side records (scalar registers) and pass the result.
+__device__ __forceinline__ u32x4 w12_decode(u32x3 p, unsigned base) {
+    const unsigned bb = base * 0x00800080u;
     u32x4 o;
     o[0] = ((p[0] & W12_SM) | ((p[2] << 7) & W12_CM)) + bb;
     o[1] = ((__builtin_amdgcn_alignbit(p[0], p[0], 8) & W12_SM) | ((p[2] << 3) & W12_CM)) + bb;
     o[2] = ((p[1] & W12_SM) | ((p[2] >> 1) & W12_CM)) + bb;
     o[3] = ((__builtin_amdgcn_alignbit(p[1], p[1], 8) & W12_SM) | ((p[2] >> 5) & W12_CM)) + bb;
-    const int c = (int)((m[0] >> 8) & 7u);
+    return o;
+}
+__device__ __forceinline__ unsigned w12_escapes(unsigned m0) { return (m0 >> 8) & 7u; }
+__device__ __forceinline__ void w12_repair(u32x4 &o, u32x4 m, int lane) {
+    const unsigned base = m[0] & 0xffu;
+    const int c = (int)w12_escapes(m[0]);
     if (c != 0) {                                             // (uniform where m is: ~5 % of the tiles of N(0, 1/sqrt(K)) weights)
 #pragma unroll
         for (int j = 0; j < W12_MAX_ESC; ++j) {
@@ -52,7 +61,6 @@ __device__ __forceinline__ u32x4 w12_decode(u32x3 p, u32x4 m, int lane) {
             }
         }
     }
-    return o;
 }
 
 // ---- the two weight fetches of the norm-on-load / finishing GEMMs (normload_kernels.h): what a lane requests for one
@@ -66,6 +74,7 @@ struct WFetchBf16 {
     __device__ __forceinline__ Frag fetch(size_t k) const { return __builtin_nontemporal_load(p + k * 64); }
     __device__ __forceinline__ void advance(int n) { p += (size_t)n * 64; }
     static __device__ __forceinline__ u32x4 frag(const Frag &f, int) { return f; }
+    static constexpr bool kRecords = false;
 };
 struct WFetchW12 {
     typedef W12Arg Arg;
@@ -79,7 +88,14 @@ struct WFetchW12 {
         return Frag{__builtin_nontemporal_load(reinterpret_cast<const u32x3_a4 *>(p + k * W12_TILE_DWORDS)), mp[k]};
     }
     __device__ __forceinline__ void advance(int n) { p += (size_t)n * W12_TILE_DWORDS; mp += n; }
-    static __device__ __forceinline__ u32x4 frag(const Frag &f, int lane) { return w12_decode(f.v, f.m, lane); }
+    static __device__ __forceinline__ u32x4 decode(const Frag &f) { return w12_decode(f.v, f.m[0] & 0xffu); }
+    static __device__ __forceinline__ void repair(u32x4 &o, const Frag &f, int lane) { w12_repair(o, f.m, lane); }
+    static __device__ __forceinline__ u32x4 frag(const Frag &f, int lane) {
+        u32x4 o = decode(f);
+        repair(o, f, lane);
+        return o;
+    }
+    static constexpr bool kRecords = true;
 };
 
 // ---- packer: one wave per tile.  *status |= 1 when a tile has more than W12_MAX_ESC escapes (its records are still
