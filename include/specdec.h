@@ -775,6 +775,58 @@ int sd_token_logprobs(const sd_logprob_item *items, int n_items, int V, int mode
  * the entry's own refusals, before anything is launched: a NULL dev, host or logprob_out, or a NULL array in it. */
 typedef struct { float *dev, *host; float **logprob_out; } sd_logprob_block;
 
+/* ---- Token scoring: the log-probability and the rank of one token per logit row, and the row's top_n ids.  x is an fp32 logit
+ * row as sd_token_logprobs reads it (the pending SD_NORM_ROUND_* rounding applied to every entry), t the token it is scored at.
+ *   order         ids by value descending, compared as IEEE floats (-0.0 == +0.0), ties to the lower id first - torch.sort(x,
+ *                 descending=True, stable=True); -inf entries take part like any value and come last
+ *   logprob       x[t] - log sum_v exp(x[v]): sd_token_logprobs' float bit for bit (same accumulator, traversal and reduction)
+ *   rank          1 + #{v : x[v] > x[t]} + #{v < t : x[v] == x[t]}, t's 1-based place in the order
+ *   top_ids[j], top_logprobs[j]  (j < top_n) the j-th id of the order and its log-probability, from the same (max, sum) pair
+ *                 as logprob - bit-equal to it where top_ids[j] == t; entries j >= V are -1 and NaN
+ * A row whose log-sum is not finite - it holds a NaN or a +inf, or nothing but -inf - is void: logprob NaN, rank 0, every
+ * top_ids entry -1, every top_logprobs entry NaN.  A token outside [0, V) gives logprob NaN and rank 0 and reads nothing; the
+ * row's top list is still written.  (quality.score_rows_torch is this text in torch.)
+ * sd_score_rows scores up to 16 items x SD_SCORE_MAX_ROWS rows in one launch on `stream` (one workgroup per row; the row is read
+ * once from memory and once more from L2, and 65 more times only where over 12288 entries crowd the stripes of top_n lanes -
+ * no row of V <= 156672).  An item is `rows` consecutive fp32 logit rows (row stride ld >= V; no alignment asked of ld
+ * or of the rows), the device tokens to score them at, and where the results go: `rows` floats and ranks (rank may be NULL)
+ * and rows x top_n ids and floats, row-major (both unread when top_n == 0).  `items` is a host array; mode as for
+ * sd_token_logprobs.  Refused with SD_ERR_INVALID before any launch, naming the item: a NULL argument (rank excepted; the two
+ * top arrays only when top_n > 0), n_items outside 1..16, V < 1, both rounding bits, rows outside 1..SD_SCORE_MAX_ROWS, ld < V,
+ * top_n outside 0..SD_SCORE_MAX_TOP. */
+#define SD_SCORE_MAX_TOP 20
+#define SD_SCORE_MAX_ROWS 80
+typedef struct {
+    const float *logits;
+    long ld;
+    int32_t rows;
+    const int32_t *tokens;
+    float *logprob;
+    int32_t *rank;
+    int32_t *top_ids;
+    float *top_logprobs;
+} sd_score_item;
+int sd_score_rows(const sd_score_item *items, int n_items, int V, int top_n, int mode, void *stream);
+/* sd_score_sequence scores tokens first .. n - 1 of the n device ids `tokens` (each in [0, V), the caller's guarantee as for
+ * sd_session_forward; 1 <= first <= n - 1): output entry j is tokens[first + j] scored on the row of position first + j - 1.
+ * Positions [0, first - 1) are fed without logit rows, up to the session's max_rows per pass; positions [first - 1, n - 1) in
+ * passes whose rows are all logit rows, up to min(slab_rows, the session's rows per such pass) each, and every such pass is
+ * followed by ONE sd_score_rows launch on the rows where the forward left them - the head's own slab, its pending rounding as
+ * the mode, or `slab` (slab_rows x ld_slab floats, the only logit buffer) - writing straight into `out` at the pass's offset:
+ * n - first floats and ranks (rank may be NULL), (n - first) x top_n ids and floats.  Everything is enqueued on `stream` and
+ * nothing is waited for.  The session's cache is rewritten from position 0 and holds [0, n - 1) afterwards.  Refused with
+ * SD_ERR_INVALID before anything is launched: a NULL argument (out->rank excepted; the top arrays only when top_n > 0), n < 2,
+ * first outside 1..n - 1, top_n outside 0..SD_SCORE_MAX_TOP, slab_rows < 1, ld_slab < V, n - 1 > the session's max_seq, a
+ * session bound to a tensor-parallel group. */
+typedef struct {
+    float *logprob;
+    int32_t *rank;
+    int32_t *top_ids;
+    float *top_logprobs;
+} sd_score_out;
+int sd_score_sequence(sd_session *s, const int32_t *tokens, int n, int first, int top_n, float *slab, long ld_slab, int slab_rows,
+                      const sd_score_out *out, void *stream);
+
 /* ---- Per-request repetition, frequency and presence penalties.  A logit row at position pos predicts token pos + 1; its
  * history is seq[0 .. pos], and the stream's prompt is the P tokens it held when the call started.  For a token id t, c_all(t)
  * counts t in seq[0 .. pos] and c_out(t) in seq[P .. pos].  x is the logit as the sampler reads it, the pending SD_NORM_ROUND_*

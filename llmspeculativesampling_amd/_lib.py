@@ -136,6 +136,18 @@ class SdLogprobBlock(C.Structure):
     _fields_ = [("dev", C.c_void_p), ("host", C.c_void_p), ("logprob_out", C.POINTER(C.c_void_p))]
 
 
+class SdScoreItem(C.Structure):
+    _fields_ = [("logits", C.c_void_p), ("ld", C.c_long), ("rows", C.c_int32), ("tokens", C.c_void_p), ("logprob", C.c_void_p),
+                ("rank", C.c_void_p), ("top_ids", C.c_void_p), ("top_logprobs", C.c_void_p)]
+
+
+class SdScoreOut(C.Structure):
+    _fields_ = [("logprob", C.c_void_p), ("rank", C.c_void_p), ("top_ids", C.c_void_p), ("top_logprobs", C.c_void_p)]
+
+
+SD_SCORE_MAX_TOP, SD_SCORE_MAX_ROWS = 20, 80             # sd_score_rows: top_n and rows per item
+
+
 class SdPenalty(C.Structure):
     _fields_ = [("repetition", C.c_float), ("frequency", C.c_float), ("presence", C.c_float)]
 
@@ -214,7 +226,8 @@ C_STRUCTS = {"sd_accept_result": SdAcceptResult, "sd_norm_row": SdNormRow, "sd_r
              "sd_ar_stream": SdArStream, "sd_sampling": SdSampling, "sd_head_scratch": SdHeadScratch,
              "sd_spec_stream": SdSpecStream, "sd_spec_scratch": SdSpecScratch, "sd_lockstep_log": SdLockstepLog, "sd_seq_state": SdSeqState,
              "sd_ar_log": SdArLog, "sd_batch_item": SdBatchItem,
-             "sd_logprob_item": SdLogprobItem, "sd_logprob_block": SdLogprobBlock, "sd_penalty": SdPenalty,
+             "sd_logprob_item": SdLogprobItem, "sd_logprob_block": SdLogprobBlock, "sd_score_item": SdScoreItem,
+             "sd_score_out": SdScoreOut, "sd_penalty": SdPenalty,
              "sd_penalty_item": SdPenaltyItem, "sd_penalty_block": SdPenaltyBlock, "sd_logit_edit": SdLogitEdit,
              "sd_logit_edit_item": SdLogitEditItem, "sd_logit_edit_block": SdLogitEditBlock, "sd_loop_opts": SdLoopOpts,
              "sd_model_config": SdModelConfig,
@@ -297,6 +310,8 @@ SYMBOLS = [
     ("sd_ar_batch_generate", _I, [_P(SdArStream), _I, _P(SdSampling), _P(SdHeadScratch), _VP, _VP, _VP, _P(SdArLog), _VP,
                                   _P(SdLoopOpts)]),
     ("sd_token_logprobs", _I, [_P(SdLogprobItem), _I, _I, _I, _VP]),
+    ("sd_score_rows", _I, [_P(SdScoreItem), _I, _I, _I, _I, _VP]),
+    ("sd_score_sequence", _I, [_VP, _VP, _I, _I, _I, _VP, _L, _I, _P(SdScoreOut), _VP]),
     ("sd_penalize_rows", _I, [_P(SdPenaltyItem), _I, _I, _I, _VP]),
     ("sd_edit_rows", _I, [_P(SdLogitEditItem), _I, _I, _I, _VP]),
     ("sd_batch_forward", _I, [C.POINTER(SdBatchItem), _I, _VP, _L, _VP]),

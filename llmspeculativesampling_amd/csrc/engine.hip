@@ -19,6 +19,7 @@
 #include "multi_kernels.h"
 #include "kv_copy_kernels.h"
 #include "logprob_kernels.h"
+#include "score_kernels.h"
 #include "penalty_kernels.h"
 #include "logit_edit_kernels.h"
 #include "sampler_host.h"

@@ -35,9 +35,54 @@ struct LseAcc {
     }
 };
 
-// Grid (x, y) = (row, item), one workgroup of 256 threads per scored row, one pass over the row: a scalar head up to the
-// first 16-byte boundary (rows of an arena, or of a slab whose ld is no multiple of 4, start anywhere), 16 bytes per lane,
-// a scalar tail.  DT: the rows still have to be rounded to a 16-bit type (rnd_dt's codes) - every logit, the picked one too.
+// The row traversal sd_token_logprobs and sd_score_rows share (score_kernels.h), so that the two give the same (m, s) bit for
+// bit: one pass over the row by a 256-thread workgroup - a scalar head up to the first 16-byte boundary (rows of an arena, or
+// of a slab whose ld is no multiple of 4, start anywhere), 16 bytes per lane, a scalar tail - then the wave's pairs by
+// cross-lane moves; the four waves' pairs are left in sh_m / sh_s (behind a barrier) for lse_fold.  DT: the rows still have
+// to be rounded to a 16-bit type (rnd_dt's codes).  visit(x, id) sees every entry this thread reads, rounded, its ids ascending.
+struct LseNoVisit {
+    __device__ __forceinline__ void operator()(float, int) const {}
+};
+template <int DT, class Visit>
+__device__ __forceinline__ void lse_row(const float *x, int V, int tid, float *sh_m, float *sh_s, Visit &&visit) {
+    const int head = min(V, (int)(((16u - (unsigned)((uintptr_t)x & 15u)) & 15u) >> 2));
+    const int n4 = (V - head) >> 2, tail0 = head + 4 * n4;
+    LseAcc a = {-3.402823466e+38f, 0.f};
+    if (tid < head) {
+        const float v = rnd_dt(x[tid], DT);
+        a.add(v);
+        visit(v, tid);
+    }
+    const float4 *x4 = reinterpret_cast<const float4 *>(x + head);
+#pragma unroll 4
+    for (int i = tid; i < n4; i += LOGPROB_THREADS) {
+        const float4 v = x4[i];
+        const float v0 = rnd_dt(v.x, DT), v1 = rnd_dt(v.y, DT), v2 = rnd_dt(v.z, DT), v3 = rnd_dt(v.w, DT);
+        a.add4(v0, v1, v2, v3);
+        const int id = head + 4 * i;
+        visit(v0, id); visit(v1, id + 1); visit(v2, id + 2); visit(v3, id + 3);
+    }
+    if (tail0 + tid < V) {
+        const float v = rnd_dt(x[tail0 + tid], DT);
+        a.add(v);
+        visit(v, tail0 + tid);
+    }
+    // the wave's pairs by cross-lane moves, the four waves' through LDS
+    const float wm = wave_max(a.m);
+    const float ws = wave_sum(a.s * expf(a.m - wm));
+    if ((tid & 63) == 0) { sh_m[tid >> 6] = wm; sh_s[tid >> 6] = ws; }
+    __syncthreads();
+}
+// ... and the fold of the four waves' pairs into the row's (m, s): log sum_v exp(x[v]) = m + log s.  Any thread may call it
+// behind lse_row; every caller gets the same bits.
+__device__ __forceinline__ void lse_fold(const float *sh_m, const float *sh_s, float &m, float &s) {
+    m = sh_m[0]; s = 0.f;
+    for (int w = 1; w < LOGPROB_THREADS / 64; ++w) m = fmaxf(m, sh_m[w]);
+    for (int w = 0; w < LOGPROB_THREADS / 64; ++w) s += sh_s[w] * expf(sh_m[w] - m);
+}
+
+// Grid (x, y) = (row, item), one workgroup of 256 threads per scored row, one pass over the row (lse_row).  DT: the rows
+// still have to be rounded to a 16-bit type (rnd_dt's codes) - every logit, the picked one too.
 template <int DT>
 __global__ __launch_bounds__(LOGPROB_THREADS) void token_logprob_kernel(LogprobTab t, int V) {
     const int b = blockIdx.y, r = blockIdx.x, tid = threadIdx.x;
@@ -45,27 +90,11 @@ __global__ __launch_bounds__(LOGPROB_THREADS) void token_logprob_kernel(LogprobT
     const sd_accept_result *res = t.res[b];
     if (res && r > res->n_accepted) return;                       // not emitted: the output float stays as it is
     const float *x = t.logits[b] + (size_t)r * t.ld[b];
-    const int head = min(V, (int)(((16u - (unsigned)((uintptr_t)x & 15u)) & 15u) >> 2));
-    const int n4 = (V - head) >> 2, tail0 = head + 4 * n4;
-    LseAcc a = {-3.402823466e+38f, 0.f};
-    if (tid < head) a.add(rnd_dt(x[tid], DT));
-    const float4 *x4 = reinterpret_cast<const float4 *>(x + head);
-#pragma unroll 4
-    for (int i = tid; i < n4; i += LOGPROB_THREADS) {
-        const float4 v = x4[i];
-        a.add4(rnd_dt(v.x, DT), rnd_dt(v.y, DT), rnd_dt(v.z, DT), rnd_dt(v.w, DT));
-    }
-    if (tail0 + tid < V) a.add(rnd_dt(x[tail0 + tid], DT));
-    // the wave's pairs by cross-lane moves, the four waves' through LDS
     __shared__ float sh_m[LOGPROB_THREADS / 64], sh_s[LOGPROB_THREADS / 64];
-    const float wm = wave_max(a.m);
-    const float ws = wave_sum(a.s * expf(a.m - wm));
-    if ((tid & 63) == 0) { sh_m[tid >> 6] = wm; sh_s[tid >> 6] = ws; }
-    __syncthreads();
+    lse_row<DT>(x, V, tid, sh_m, sh_s, LseNoVisit());
     if (tid != 0) return;
-    float m = sh_m[0], s = 0.f;
-    for (int w = 1; w < LOGPROB_THREADS / 64; ++w) m = fmaxf(m, sh_m[w]);
-    for (int w = 0; w < LOGPROB_THREADS / 64; ++w) s += sh_s[w] * expf(sh_m[w] - m);
+    float m, s;
+    lse_fold(sh_m, sh_s, m, s);
     const int tok = t.tokens[b][r];
     const float xt = tok >= 0 && tok < V ? rnd_dt(x[tok], DT) : __builtin_nanf("");
     t.out[b][r] = (xt - m) - logf(s);

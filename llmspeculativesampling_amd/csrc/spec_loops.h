@@ -164,6 +164,8 @@ extern "C" int sd_token_logprobs(const sd_logprob_item *items, int n_items, int 
     return launch_token_logprobs(t, n_items, max_rows, V, mode & 3, (hipStream_t)stream);
 }
 
+#include "score_entries.h"                                       // sd_score_rows, sd_score_sequence
+
 enum { LP_SLICE = LOGPROB_MAX_ROWS };                             // floats per stream in sd_logprob_block.dev / host
 // what the loops refuse in a logprob block (behind the entry's own refusals): n arrays, one per stream / prompt
 static int check_logprob_block(const char *who, const sd_logprob_block *lp, int n) {
