@@ -949,6 +949,68 @@ typedef struct sd_loop_opts {
 } sd_loop_opts;
 
 /* ------------------------------------------------------------------------------------------
+ * Prompt-lookup drafting: speculative decoding without a draft model.  The proposer finds the most recent earlier occurrence
+ * of the sequence's last few tokens and proposes the tokens that followed it.  A lookup draft is a deterministic proposal, so
+ * its q row is one-hot; with one-hot rows in q_hist the accept / residual kernels above need no change: accept iff
+ * r <= p[j] / 1, the residual is max_fn(p - onehot_j).
+ *
+ * Definition, for one stream with tokens seq[0 .. L), gamma g, ngram_max N and ngram_min m (1 <= m <= N <= SD_LOOKUP_MAX_NGRAM = 8):
+ *  - For a continuation index c, 1 <= c <= L - 1, the match length is k(c) = the largest k <= min(N, c) with
+ *    seq[c-k .. c) == seq[L-k .. L).  The match may overlap the key itself.
+ *  - c counts when k(c) >= m.  Among those, choose the largest k(c), and among equal lengths the largest c (the most recent
+ *    occurrence).
+ *  - If none counts, use c = L - 1 with match length 0.  This always happens at L = 1.
+ *  - The drafted tokens are seq[L + i] = seq[c + (i mod (L - c))], i < g.  This is the sequential copy seq[L+i] = seq[c+i],
+ *    which runs into its own output when L - c < g.
+ *  - So the proposer always yields g tokens and the loops keep fixed shapes.  A hopeless proposal costs nothing in correctness.
+ *  - Per stream it writes the g tokens.  It also writes g one-hot rows: q_hist[(L-1+i)*ld + v] for every v < V becomes 0.0f, or
+ *    1.0f at v = seq[L+i].  Columns [V, ld) are untouched, and whatever the rows held before, NaN included, is gone.  It also
+ *    writes two device ints, info[0] = match length and info[1] = c.
+ *  - The result is a pure function of the inputs.  The kernel reads seq[0..L) and writes seq[L..L+g).
+ * A token outside [0, V) is copied like any other and its row is all zero (it is never used as an index).
+ *
+ * sd_lookup_propose: one launch serves 1..16 items; `items` is a host array; no alignment is asked of ld or the rows; the token
+ * buffer holds L + gamma ints and q_hist L + gamma - 1 rows.  Refused with SD_ERR_INVALID before any launch, naming the item:
+ * a NULL argument; n_items outside 1..16; gamma outside 1..16; ngram_max outside 1..8; ngram_min outside 1..ngram_max;
+ * V < 1 or ld < V; then per item a NULL pointer or L < 1. */
+#define SD_LOOKUP_MAX_NGRAM 8
+typedef struct { int32_t *seq; int32_t L; float *q_hist; int32_t *info; } sd_lookup_item;
+int sd_lookup_propose(const sd_lookup_item *items, int n_items, int V, long ld, int gamma, int ngram_max, int ngram_min,
+                      void *stream);
+/* sd_spec_generate with the gamma draft forwards replaced by ONE sd_lookup_propose launch; the rest of the iteration is
+ * sd_spec_generate's, launch for launch: one target forward over the uncached rows (the whole prompt on the first iteration),
+ * the norm launch of the last gamma + 1 rows (candidate lists when the workspace holds them, tile maxima where the head
+ * leaves them), sd_accept_resample - or the dense pair for a list-less row - one async copy and one wait.  The blocks are
+ * sd_spec_generate's: dev->draft must be NULL; scratch->draft is not read; seq->draft_len is neither read nor written;
+ * seq->draft_ms_out[i] receives the proposer's time when set; q_at is 1 for every drafted token.  dev->res_dev and
+ * dev->res_host hold sizeof(sd_accept_result) + 8 bytes: the proposer's two info ints follow the result block, and the one
+ * copy moves both.  match_len_out (host, one entry per iteration, may be NULL) receives info[0].  The residual runs in the
+ * target's norm mode (a one-hot row is exact in every dtype).  Philox position per iteration, d = seq->draw on entry of the
+ * iteration: d .. d+gamma reserved and unread (no draft samples, no discarded target sample), d+gamma+1 .. d+2*gamma the accept
+ * uniforms, d+2*gamma+1 the residual / bonus sample; the stream advances by 2*gamma + 2.  There is no random_seed / r_const.
+ * Refused with SD_ERR_INVALID before anything is written or launched, in this order: a NULL block, a NULL pointer in dev
+ * (target, seq, q_hist, p_hist, err_words, res_dev, res_host), seq->host_seq or scratch->target.logits; a non-NULL dev->draft;
+ * gamma outside 1..16; ngram_max outside 1..8; ngram_min outside 1..ngram_max; temperature 0; a norm_workspace with
+ * max_rows_per_forward < gamma + 1; then sampling->V differing from the target's vocabulary or ld < V. */
+int sd_lookup_generate(const sd_spec_stream *dev, int gamma, int ngram_max, int ngram_min, const sd_sampling *sampling,
+                       const sd_spec_scratch *scratch, sd_seq_state *seq, int32_t *match_len_out, void *stream);
+/* Up to 16 streams in lock-step, each running exactly the algorithm of sd_lookup_generate on its own Philox stream (seed,
+ * draw).  Per iteration: ONE sd_lookup_propose launch over the active streams; the verify passes of max_rows_per_forward /
+ * (gamma + 1) streams each (sd_batch_forward); the norm launch (sd_norm_batch) with lists when the workspace holds them and
+ * one pass holds every stream; sd_accept_resample_batch, or sd_accept_batch without lists; one copy and one wait.  Streams
+ * arrive prefilled to target_len == len - 1 with draft == NULL; draft_len is not used.  The streams' result blocks are
+ * consecutive as in sd_spec_batch_generate, and 2 * n_streams info ints follow the last block, on the device and on the host:
+ * stream i's pair at ints 2i, 2i + 1 behind res[n_streams], moved by the same one copy.  match_len_out (host, may be NULL):
+ * n_streams pointers, entry i one int per iteration of stream i (indexed like acc_len_out), or NULL.  A done stream drops out
+ * of later passes; the end-of-stream rule (T tokens or a new EOS) and log are sd_spec_batch_generate's.  Refused before
+ * anything is written or launched: NULL blocks, n_streams or gamma outside 1..16, n-gram bounds as above, temperature 0; then
+ * per stream a NULL pointer, a non-NULL draft, sessions of another model than stream 0's, target_len != len - 1; then result
+ * blocks that are not consecutive. */
+int sd_lookup_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, int ngram_max, int ngram_min,
+                             const sd_sampling *sampling, const sd_spec_scratch *scratch, sd_lockstep_log *log,
+                             int32_t **match_len_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Tensor parallelism of one decoder over the GPUs of a node (BASELINE config 5: Llama-2-70b, TP = 8 over xGMI).
  * The reference is single-process: this is new capability behind the same call signatures.
  * A shard is an ordinary sd_model whose config holds the LOCAL head / KV-head / MLP counts (n_heads * head_dim <= hidden)

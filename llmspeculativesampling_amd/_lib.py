@@ -179,7 +179,12 @@ class SdLoopOpts(C.Structure):                          # the loops' optional la
                 ("penalties", C.POINTER(SdPenaltyBlock)), ("edits", C.POINTER(SdLogitEditBlock))]
 
 
+class SdLookupItem(C.Structure):                         # one stream of sd_lookup_propose
+    _fields_ = [("seq", C.c_void_p), ("L", C.c_int32), ("q_hist", C.c_void_p), ("info", C.c_void_p)]
+
+
 SD_EDIT_MAX_BIAS = 1024                                  # bias entries per request
+SD_LOOKUP_MAX_NGRAM = 8                                  # the longest key the prompt-lookup proposer matches
 LOGPROB_SLICE, LOGPROB_STREAMS = 17, 16                  # sd_logprob_block: 16 streams x 17 floats, device and pinned host
 
 
@@ -230,6 +235,7 @@ C_STRUCTS = {"sd_accept_result": SdAcceptResult, "sd_norm_row": SdNormRow, "sd_r
              "sd_score_out": SdScoreOut, "sd_penalty": SdPenalty,
              "sd_penalty_item": SdPenaltyItem, "sd_penalty_block": SdPenaltyBlock, "sd_logit_edit": SdLogitEdit,
              "sd_logit_edit_item": SdLogitEditItem, "sd_logit_edit_block": SdLogitEditBlock, "sd_loop_opts": SdLoopOpts,
+             "sd_lookup_item": SdLookupItem,
              "sd_model_config": SdModelConfig,
              "sd_gemm_route_info": SdGemmRouteInfo, "sd_model_weights": SdModelWeights}
 
@@ -314,6 +320,10 @@ SYMBOLS = [
     ("sd_score_sequence", _I, [_VP, _VP, _I, _I, _I, _VP, _L, _I, _P(SdScoreOut), _VP]),
     ("sd_penalize_rows", _I, [_P(SdPenaltyItem), _I, _I, _I, _VP]),
     ("sd_edit_rows", _I, [_P(SdLogitEditItem), _I, _I, _I, _VP]),
+    ("sd_lookup_propose", _I, [_P(SdLookupItem), _I, _I, _L, _I, _I, _I, _VP]),
+    ("sd_lookup_generate", _I, [_P(SdSpecStream), _I, _I, _I, _P(SdSampling), _P(SdSpecScratch), _P(SdSeqState), _VP, _VP]),
+    ("sd_lookup_batch_generate", _I, [_P(SdBatchStream), _I, _I, _I, _I, _P(SdSampling), _P(SdSpecScratch), _P(SdLockstepLog), _VPP,
+                                      _VP]),
     ("sd_batch_forward", _I, [C.POINTER(SdBatchItem), _I, _VP, _L, _VP]),
     ("sd_batch_prefill", _I, [C.POINTER(SdBatchItem), _I, _VP]),
     ("sd_tp_unique_id", _I, [_VP]),

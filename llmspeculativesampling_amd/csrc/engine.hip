@@ -22,6 +22,7 @@
 #include "score_kernels.h"
 #include "penalty_kernels.h"
 #include "logit_edit_kernels.h"
+#include "lookup_kernels.h"
 #include "sampler_host.h"
 
 static thread_local char g_err[512] = "";

@@ -354,6 +354,11 @@ static void norm_from_edited(NormRequest &nr, const RowEdits &re) {
     nr.logits = re.rows; nr.ld_in = re.ld; nr.mode &= ~3; nr.tile_max = nullptr;
 }
 
+// (the verify half of an iteration: defined behind spec_iteration, shared with the prompt-lookup loop)
+static int verify_half(const sd_spec_stream &dv, int g, const sd_sampling &sm, const sd_spec_scratch &sc, const Draws &d,
+                       int L, int target_len, const float *r_const, int res_mode, size_t res_bytes, const LoopEvents &ev, bool timed,
+                       void *stream, const LoopOpts &o, int prompt_len);
+
 // ---- one whole speculative iteration, enqueued natively ---------------------------------------
 // reference sampling/speculative_sampling.py:1934-2031 for the device-RNG mode: gamma x (draft forward +
 // norm_sample), one target forward over the uncached rows + norm_probs, accept scan, residual / bonus sample,
@@ -362,11 +367,10 @@ static void norm_from_edited(NormRequest &nr, const RowEdits &re) {
 static int spec_iteration(const sd_spec_stream &dv, int g, const sd_sampling &sm, const sd_spec_scratch &sc, const Draws &d, int L,
                           int draft_len, int target_len, const float *r_const, const LoopEvents &ev, bool timed, void *stream,
                           const LoopOpts &o, int prompt_len) {
-    const sd_logprob_block *const lp = o.lp;
     const RowEdits *const re = o.re;
     SD_REQUIRE(L >= 1 && draft_len >= 0 && draft_len < L && target_len >= 0 && target_len < L + g,
                "sd_spec_generate: L=%d draft_len=%d target_len=%d", L, draft_len, target_len);
-    SD_REQUIRE(!lp || target_len <= L - 1, "sd_spec_generate: logprobs: target_len %d of %d tokens leaves fewer than gamma + 1 target rows",
+    SD_REQUIRE(!o.lp || target_len <= L - 1, "sd_spec_generate: logprobs: target_len %d of %d tokens leaves fewer than gamma + 1 target rows",
                target_len, L);
     hipStream_t st = (hipStream_t)stream;
     int rc;
@@ -395,7 +399,31 @@ static int spec_iteration(const sd_spec_stream &dv, int g, const sd_sampling &sm
         nr.workspace = sc.norm_workspace;
         if ((rc = sd_norm_rows_with_tiles(nr, stream)) != SD_OK) return rc;
     }
-    if (timed) { SD_HIP_CHECK(hipEventRecord(ev.t[1], st)); SD_HIP_CHECK(hipEventRecord(ev.t[2], st)); }
+    if (timed) SD_HIP_CHECK(hipEventRecord(ev.t[1], st));
+    // p - q, max_fn and the draw are in the rows' dtype when both models keep 16-bit rows
+    const int res_mode = sc.target.norm_mode == sc.draft.norm_mode ? sc.target.norm_mode : 0;
+    return verify_half(dv, g, sm, sc, d, L, target_len, r_const, res_mode, sizeof(sd_accept_result), ev, timed, stream,
+                       o, prompt_len);
+}
+
+// The verify half of an iteration, shared by the speculative and the prompt-lookup loop: seq[L .. L + gamma) and the q rows
+// L-1 .. L+gamma-2 are where the draft half (gamma draft steps, or one proposer launch) left them.  One target forward over
+// the uncached rows, the edits, the norm launch, accept scan + residual / bonus sample in `res_mode`, the log-prob launch,
+// and the copy of `res_bytes` from the result block (what follows the block rides along).  Timed: ev.t[2] .. t[3] around the
+// forward and the norm.
+static int verify_half(const sd_spec_stream &dv, int g, const sd_sampling &sm, const sd_spec_scratch &sc, const Draws &d,
+                       int L, int target_len, const float *r_const, int res_mode, size_t res_bytes, const LoopEvents &ev, bool timed,
+                       void *stream, const LoopOpts &o, int prompt_len) {
+    const sd_logprob_block *const lp = o.lp;
+    const RowEdits *const re = o.re;
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    const bool tiles_ok = !re && head_tiles_ok(sm.top_k, sm.temperature, sm.V, sm.ld);   // (an edited pass takes no tile maxima)
+    int *const err = dv.err_words;
+    HeadReq rq = {};
+    HeadOut ho = {};
+    rq.raw = true; rq.zero_ld = sm.ld;
+    if (timed) SD_HIP_CHECK(hipEventRecord(ev.t[2], st));
     // the target rows' candidate lists (behind the CandRows of the workspace) let the residual / bonus sample skip its
     // passes over V; they exist when all gamma + 1 rows of this iteration are normalised here
     void *lists = nullptr;
@@ -420,8 +448,6 @@ static int spec_iteration(const sd_spec_stream &dv, int g, const sd_sampling &sm
     }
     if (timed) SD_HIP_CHECK(hipEventRecord(ev.t[3], st));
     // ---- accept scan + residual / bonus sample
-    // p - q, max_fn and the draw are in the rows' dtype when both models keep 16-bit rows
-    const int res_mode = sc.target.norm_mode == sc.draft.norm_mode ? sc.target.norm_mode : 0;
     if (lists) {
         if ((rc = sd_accept_resample(dv.p_hist, dv.q_hist, sm.ld, sm.V, dv.seq, L, g, r_const, d.seed, d.scan0, d.resample, dv.res_dev,
                                      err, 3 * g + 1, res_mode, lists, st)) != SD_OK)
@@ -438,7 +464,7 @@ static int spec_iteration(const sd_spec_stream &dv, int g, const sd_sampling &sm
         if ((rc = sd_token_logprobs(&it, 1, sm.V, ho.round | sc.target.norm_mode, stream)) != SD_OK) return rc;
         SD_HIP_CHECK(hipMemcpyAsync(lp->host, lp->dev, sizeof(float) * (size_t)(g + 1), hipMemcpyDeviceToHost, st));
     }
-    SD_HIP_CHECK(hipMemcpyAsync(dv.res_host, dv.res_dev, sizeof(sd_accept_result), hipMemcpyDeviceToHost, st));
+    SD_HIP_CHECK(hipMemcpyAsync(dv.res_host, dv.res_dev, res_bytes, hipMemcpyDeviceToHost, st));
     return SD_OK;
 }
 
@@ -985,6 +1011,237 @@ extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, i
                                    sampling->eos_token_id, true, &o); rc != SD_OK)
         return rc;
     return lockstep_loop(who, streams, n_streams, nullptr, gamma, *sampling, random_seed, r_const, *scratch, log, stream, o);
+}
+
+// ---- prompt-lookup drafting (include/specdec.h has the definition and the loops' contract) ------------------------
+// what the three entries refuse in gamma and the n-gram bounds, in that order
+static int check_lookup_bounds(const char *who, int gamma, int ngram_max, int ngram_min) {
+    SD_REQUIRE(gamma >= 1 && gamma <= LOOKUP_MAX_GAMMA, "%s: gamma %d outside 1..%d", who, gamma, LOOKUP_MAX_GAMMA);
+    SD_REQUIRE(ngram_max >= 1 && ngram_max <= SD_LOOKUP_MAX_NGRAM, "%s: ngram_max %d outside 1..%d", who, ngram_max, SD_LOOKUP_MAX_NGRAM);
+    SD_REQUIRE(ngram_min >= 1 && ngram_min <= ngram_max, "%s: ngram_min %d outside 1..ngram_max %d", who, ngram_min, ngram_max);
+    return SD_OK;
+}
+
+extern "C" int sd_lookup_propose(const sd_lookup_item *items, int n_items, int V, long ld, int gamma, int ngram_max, int ngram_min,
+                                 void *stream) {
+    const char *const who = "sd_lookup_propose";
+    SD_REQUIRE(items, "%s: null argument", who);
+    SD_REQUIRE(n_items >= 1 && n_items <= LOOKUP_MAX_ITEMS, "%s: n_items %d outside 1..%d", who, n_items, LOOKUP_MAX_ITEMS);
+    if (int rc = check_lookup_bounds(who, gamma, ngram_max, ngram_min); rc != SD_OK) return rc;
+    SD_REQUIRE(V >= 1 && ld >= V, "%s: V %d < 1 or ld %ld < V", who, V, ld);
+    LookupTab t = {};
+    for (int i = 0; i < n_items; ++i) {
+        const sd_lookup_item &it = items[i];
+        SD_REQUIRE(it.seq && it.q_hist && it.info, "%s: item %d: null argument", who, i);
+        SD_REQUIRE(it.L >= 1, "%s: item %d: L %d < 1", who, i, it.L);
+        t.seq[i] = it.seq; t.q_hist[i] = it.q_hist; t.info[i] = it.info; t.L[i] = it.L;
+    }
+    return launch_lookup_propose(t, n_items, V, ld, gamma, ngram_max, ngram_min, (hipStream_t)stream);
+}
+
+// The prompt-lookup loop of one stream: sd_spec_generate's loop with one proposer launch where the gamma draft steps are.
+extern "C" int sd_lookup_generate(const sd_spec_stream *dev, int gamma, int ngram_max, int ngram_min, const sd_sampling *sampling,
+                                  const sd_spec_scratch *scratch, sd_seq_state *s, int32_t *match_len_out, void *stream) {
+    const char *const who = "sd_lookup_generate";
+    SD_REQUIRE(dev && sampling && scratch && s && dev->target && dev->seq && dev->q_hist && dev->p_hist && dev->err_words &&
+               dev->res_dev && dev->res_host && s->host_seq && scratch->target.logits, "%s: null argument", who);
+    SD_REQUIRE(!dev->draft, "%s: a draft session: prompt lookup drafts without a model (dev->draft must be NULL)", who);
+    if (int rc = check_lookup_bounds(who, gamma, ngram_max, ngram_min); rc != SD_OK) return rc;
+    const sd_sampling &sm = *sampling;
+    SD_REQUIRE(sm.temperature != 0.0f, "%s: temperature must be non-zero", who);
+    SD_REQUIRE(!scratch->norm_workspace || scratch->max_rows_per_forward >= gamma + 1,
+               "%s: a norm workspace of %d rows, the target's gamma %d + 1 rows keep their lists there", who,
+               scratch->max_rows_per_forward, gamma);
+    SD_REQUIRE(sm.V == dev->target->m->cfg.vocab && sm.ld >= sm.V, "%s: V %d (ld %ld), the target's vocabulary is %d", who, sm.V, sm.ld,
+               dev->target->m->cfg.vocab);
+    refresh_env();
+    const int g = gamma, L0 = s->len;
+    const bool timed = s->draft_ms_out || s->target_ms_out;
+    LoopEvents ev(timed ? 4 : 0, who);
+    if (!ev.ok) return SD_ERR_HIP;
+    hipStream_t st = (hipStream_t)stream;
+    int32_t *const info_dev = reinterpret_cast<int32_t *>(dev->res_dev + 1);          // the two ints behind the result block
+    const int32_t *const info_host = reinterpret_cast<const int32_t *>(dev->res_host + 1);
+    LoopOpts o;                                                   // (no options block in this entry: nothing to edit or score)
+    int eos_total = s->ori_eos_cnt, unused_draft_len = 0;
+    s->n_iters = s->err = 0;
+    int rc = SD_OK;
+    while (s->len < s->T && s->n_iters < s->max_iters) {
+        const int L = s->len, iters = s->n_iters;
+        if (!(L >= 1 && s->target_len >= 0 && s->target_len < L + g)) {
+            sd_set_error("%s: L=%d target_len=%d", who, L, s->target_len);
+            rc = SD_ERR_INVALID;
+            break;
+        }
+        // draws d .. d + gamma stay unread (no draft samples, no discarded target sample): the layout is sd_spec_generate's
+        const Draws d = next_draws(s->seed, s->draw, g, 0);
+        s->seed = d.seed; s->draw = d.draw;
+        if (timed) SD_LOOP_HIP(hipEventRecord(ev.t[0], st));
+        const sd_lookup_item item = {dev->seq, L, dev->q_hist, info_dev};
+        if ((rc = sd_lookup_propose(&item, 1, sm.V, sm.ld, g, ngram_max, ngram_min, stream)) != SD_OK) break;
+        if (timed) SD_LOOP_HIP(hipEventRecord(ev.t[1], st));
+        if ((rc = verify_half(*dev, g, sm, *scratch, d, L, s->target_len, nullptr, scratch->target.norm_mode,
+                              sizeof(sd_accept_result) + 2 * sizeof(int32_t), ev, timed, stream, o, L0)) != SD_OK)
+            break;
+        SD_LOOP_HIP(hipEventRecord(ev.done, st));
+        if ((rc = poll_event(ev.done, who)) != SD_OK) break;
+        const sd_accept_result r = *dev->res_host;
+        if (r.flags & 2) { s->err = 1; break; }
+        if (r.flags & 8) {                                        // only the target's norm words can be set: nothing was sampled to draft
+            s->err = 2;
+            unsigned wt = 0;
+            if (hipMemcpy(&wt, dev->target->wait_status, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess && wt)
+                sd_set_error("%s: a fused launch's in-launch wait timed out (status target %#x; sd_session_fused_status): its rows "
+                             "were poisoned with NaN", who, wt);
+            break;
+        }
+        if (timed) {
+            float dms = 0.f, tms = 0.f;
+            SD_LOOP_HIP(hipEventElapsedTime(&dms, ev.t[0], ev.t[1]));
+            SD_LOOP_HIP(hipEventElapsedTime(&tms, ev.t[2], ev.t[3]));
+            if (s->draft_ms_out) s->draft_ms_out[iters] = dms;
+            if (s->target_ms_out) s->target_ms_out[iters] = tms;
+        }
+        const int l = r.n_accepted, n = r.n;
+        if (s->acc_len_out) s->acc_len_out[iters] = l;
+        if (match_len_out) match_len_out[iters] = info_host[0];
+        log_ratios(s->p_at_out, s->q_at_out, (size_t)iters, g, r.p_at, r.q_at);
+        ++s->n_iters;
+        if (!(n >= L - 1 && l >= 0 && l <= g)) {
+            sd_set_error("%s: inconsistent result block (n %d, L %d, accepted %d)", who, n, L, l);
+            rc = SD_ERR_INVALID;
+            break;
+        }
+        commit_result(r, L, g, s->host_seq, &s->len, &unused_draft_len, &s->target_len);
+        for (int i = L; i < s->len; ++i) eos_total += s->host_seq[i] == sm.eos_token_id;
+        if (eos_total > s->ori_eos_cnt) break;                    // the caller cuts after the first new EOS
+    }
+    return rc;
+}
+
+// The lock-step prompt-lookup loop: per iteration one proposer launch over the active streams, the verify passes of whole
+// streams, accept + residual / bonus sample of all streams, one copy (result blocks and info ints) and one wait.
+extern "C" int sd_lookup_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, int ngram_max, int ngram_min,
+                                        const sd_sampling *sampling, const sd_spec_scratch *scratch, sd_lockstep_log *log,
+                                        int32_t **match_len_out, void *stream) {
+    const char *const who = "sd_lookup_batch_generate";
+    SD_REQUIRE(streams && sampling && scratch && log && scratch->target.logits, "%s: null argument", who);
+    SD_REQUIRE(n_streams >= 1 && n_streams <= SD_MAX_STREAMS, "%s: n_streams %d outside 1..%d", who, n_streams, SD_MAX_STREAMS);
+    if (int rc = check_lookup_bounds(who, gamma, ngram_max, ngram_min); rc != SD_OK) return rc;
+    const sd_sampling &sm = *sampling;
+    const sd_spec_scratch &sc = *scratch;
+    SD_REQUIRE(sm.temperature != 0.0f, "%s: temperature must be non-zero", who);
+    for (int i = 0; i < n_streams; ++i) {
+        const sd_batch_stream &s = streams[i];
+        SD_REQUIRE(s.target && s.seq && s.q_hist && s.p_hist && s.err_words && s.res_dev && s.res_host && s.host_seq,
+                   "%s: stream %d: null pointer", who, i);
+        SD_REQUIRE(!s.draft, "%s: stream %d: a draft session: prompt lookup drafts without a model (draft must be NULL)", who, i);
+        SD_REQUIRE(s.target->m == streams[0].target->m, "%s: stream %d: a session of another model than stream 0's", who, i);
+        SD_REQUIRE(s.len >= 1 && s.target_len == s.len - 1, "%s: stream %d: every stream arrives prefilled (target_len %d, len %d - 1)",
+                   who, i, s.target_len, s.len);
+    }
+    SD_REQUIRE(sm.V == streams[0].target->m->cfg.vocab && sm.ld >= sm.V, "%s: V %d (ld %ld), the target's vocabulary is %d", who, sm.V,
+               sm.ld, streams[0].target->m->cfg.vocab);
+    if (int rc = check_result_blocks(who, streams, n_streams); rc != SD_OK) return rc;
+    refresh_env();
+    hipStream_t st = (hipStream_t)stream;
+    const int g = gamma, n_err = 3 * g + 1;
+    const int per_pass = std::max(1, std::min(sc.max_rows_per_forward, streams[0].target->max_pass_rows) / (g + 1));
+    int32_t *const info_dev = reinterpret_cast<int32_t *>(streams[0].res_dev + n_streams);   // 2 ints per stream behind the blocks
+    const int32_t *const info_host = reinterpret_cast<const int32_t *>(streams[0].res_host + n_streams);
+    const size_t res_bytes = (size_t)n_streams * (sizeof(sd_accept_result) + 2 * sizeof(int32_t));
+    LoopEvents ev(2, who);
+    if (!ev.ok) return SD_ERR_HIP;
+    log->n_iters = log->err = 0;
+    int &iters = log->n_iters;
+    int rc = SD_OK;
+    sd_batch_stream *act[SD_MAX_STREAMS];
+    int Ls[SD_MAX_STREAMS];
+    Draws draws[SD_MAX_STREAMS];
+    sd_lookup_item litems[SD_MAX_STREAMS];
+    sd_accept_item aitems[SD_MAX_STREAMS];
+    const void *list_of[SD_MAX_STREAMS];
+    std::vector<sd_batch_item> items;
+    std::vector<sd_norm_row> rows;
+    char *const list_base = sc.norm_workspace ? (char *)sc.norm_workspace + sd_norm_candrow_bytes(sc.max_rows_per_forward) : nullptr;
+    const size_t list_stride = sd_cand_list_bytes(1);
+    for (int i = 0; i < n_streams; ++i) { streams[i].done = 0; streams[i].calls = 0; }
+    for (;;) {
+        int n = 0;
+        double ctx = 0.0;
+        for (int i = 0; i < n_streams; ++i) {
+            sd_batch_stream &s = streams[i];
+            if (!s.done && s.len >= s.T) s.done = 1;
+            if (s.done) continue;
+            Ls[n] = s.len;
+            draws[n] = next_draws(s.seed, s.draw, g, 0);          // d .. d + gamma stay unread
+            litems[n] = sd_lookup_item{s.seq, s.len, s.q_hist, info_dev + 2 * i};
+            ctx += s.len;
+            act[n++] = &s;
+        }
+        if (n == 0) break;
+        if ((rc = sd_lookup_propose(litems, n, sm.V, sm.ld, g, ngram_max, ngram_min, stream)) != SD_OK) break;
+        // ---- verify: gamma + 1 rows per stream, whole streams per pass; the candidate lists serve the residual / bonus sample
+        // when ONE pass holds every stream (the workspace keeps the lists of one pass)
+        const bool lists_on = sc.norm_workspace && n <= per_pass;
+        SD_LOOP_HIP(hipEventRecord(ev.t[0], st));
+        for (int a0 = 0; a0 < n && rc == SD_OK; a0 += per_pass) {
+            const int m = std::min(per_pass, n - a0);
+            items.assign(m, sd_batch_item{});
+            rows.clear();
+            for (int j = 0; j < m; ++j) {
+                sd_batch_stream &s = *act[a0 + j];
+                verify_pass_rows(items[j], rows, s.target, s.seq, s.p_hist, sm.ld, s.err_words, g, Ls[a0 + j], s.target_len);
+            }
+            if ((rc = batch_forward(items.data(), m, sc.target.logits, sc.target.ld_logits, nullptr, nullptr, stream)) != SD_OK) break;
+            NormRequest nr = norm_request(sm, sc.target.norm_mode, scratch_rows(sc.target));
+            nr.rows = (int)rows.size(); nr.workspace = sc.norm_workspace; nr.lists = lists_on ? list_base : nullptr;
+            rc = sd_norm_batch_tiles(nr, rows.data(), 0, stream);
+            for (int j = 0; j < m; ++j) list_of[a0 + j] = lists_on ? list_base + (size_t)j * (g + 1) * list_stride : nullptr;
+        }
+        if (rc != SD_OK) break;
+        SD_LOOP_HIP(hipEventRecord(ev.t[1], st));
+        for (int j = 0; j < n; ++j) {
+            sd_batch_stream &s = *act[j];
+            s.seed = draws[j].seed; s.draw = draws[j].draw;
+            sd_accept_item it = {};
+            it.p_hist = s.p_hist; it.q_hist = s.q_hist; it.seq = s.seq; it.L = Ls[j];
+            it.philox_seed = draws[j].seed; it.draw_scan = draws[j].scan0; it.draw_resample = draws[j].resample;
+            it.res = s.res_dev; it.err_flags = s.err_words; it.n_err = n_err;
+            aitems[j] = it;
+        }
+        if (lists_on) rc = sd_accept_resample_batch(aitems, n, sm.ld, sm.V, g, sc.target.norm_mode, list_of, stream);
+        else rc = sd_accept_batch(aitems, n, sm.ld, sm.V, g, sc.target.norm_mode, stream);
+        if (rc != SD_OK) break;
+        SD_LOOP_HIP(hipMemcpyAsync(streams[0].res_host, streams[0].res_dev, res_bytes, hipMemcpyDeviceToHost, st));
+        SD_LOOP_HIP(hipEventRecord(ev.done, st));
+        if ((rc = poll_event(ev.done, who)) != SD_OK) break;
+        if (iters < log->max_iters_log) {
+            float ms = 0.f;
+            if (log->verify_ms_out && hipEventElapsedTime(&ms, ev.t[0], ev.t[1]) == hipSuccess) log->verify_ms_out[iters] = ms;
+            if (log->verify_streams_out) log->verify_streams_out[iters] = n;
+            if (log->verify_ctx_out) log->verify_ctx_out[iters] = (float)(ctx / n + g);
+        }
+        ++iters;
+        bool failed = false;
+        for (int j = 0; j < n; ++j) {
+            sd_batch_stream &s = *act[j];
+            const int slot = (int)(&s - streams);
+            const sd_accept_result r = *s.res_host;
+            if (r.flags & (2 | 8)) { failed = true; break; }
+            if (s.acc_len_out) s.acc_len_out[s.calls] = r.n_accepted;
+            if (match_len_out && match_len_out[slot]) match_len_out[slot][s.calls] = info_host[2 * slot];
+            log_ratios(s.p_at_out, s.q_at_out, (size_t)s.calls, g, r.p_at, r.q_at);
+            ++s.calls;
+            int unused_draft_len = 0;
+            commit_result(r, Ls[j], g, s.host_seq, &s.len, &unused_draft_len, &s.target_len);
+            int eos_total = 0;
+            for (int i = 0; i < s.len; ++i) eos_total += s.host_seq[i] == sm.eos_token_id;
+            if (eos_total > s.ori_eos_cnt) s.done = 1;            // the caller cuts after the first new EOS
+        }
+        if (failed) { log->err = 1; break; }
+    }
+    return rc;
 }
 
 // The prompt queue: without donors (shared_rows 0) every prompt starts with empty caches.

@@ -9,6 +9,7 @@ from .autoregressive_sampling import autoregressive_sampling
 from .batch import (speculative_sampling_batch, speculative_sampling_queue, speculative_sampling_queue_shared,
                     speculative_sampling_queue_logprobs, speculative_sampling_queue_requests, speculative_sampling_queue_edits,
                     autoregressive_sampling_batch)
+from .lookup import prompt_lookup_sampling, prompt_lookup_sampling_batch
 from .multi import multi_speculative_sampling
 from .beam import beam_speculative_sampling_v2
 from .kvcache_model import KVCacheModel
@@ -39,4 +40,4 @@ __all__ = ["speculative_sampling", "speculative_sampling_v2", "autoregressive_sa
            "beam_speculative_sampling_v2",
            "speculative_sampling_batch", "speculative_sampling_queue", "speculative_sampling_queue_shared",
            "speculative_sampling_queue_logprobs", "speculative_sampling_queue_requests", "speculative_sampling_queue_edits",
-           "autoregressive_sampling_batch", "KVCacheModel", "norm_logits", "sample", "max_fn", "top_k_top_p_filter"]
+           "autoregressive_sampling_batch", "prompt_lookup_sampling", "prompt_lookup_sampling_batch", "KVCacheModel", "norm_logits", "sample", "max_fn", "top_k_top_p_filter"]

@@ -255,3 +255,24 @@ def apply_logit_edits(logits_row: torch.Tensor, out_index: int, eos_token_id, bi
     if eos_token_id is not None and 0 <= int(eos_token_id) < V and int(min_tokens) > 0 and int(out_index) < int(min_tokens):
         y[int(eos_token_id)] = float("-inf")
     return y.to(dtype)
+
+
+def lookup_propose(tokens, gamma: int, ngram_max: int = 3, ngram_min: int = 1):
+    """The prompt-lookup proposer (sd_lookup_propose; include/specdec.h has the definition) in plain Python: for the tokens
+    ``seq[0 .. L)`` a continuation index c, 1 <= c <= L - 1, has match length k(c) = the largest k <= min(ngram_max, c) with
+    ``seq[c-k .. c) == seq[L-k .. L)`` (the match may overlap the key); c counts when k(c) >= ngram_min; the longest match
+    wins, among equal lengths the largest c (the most recent occurrence); if none counts, c = L - 1 at length 0.  The drafted
+    tokens are ``seq[c + (i mod (L - c))]``, i < gamma: the sequential copy that runs into its own output.  Returns
+    ``(drafted, match_len, src)``: the gamma drafted ids as a list, k and c.  Touches no GPU."""
+    seq = [int(t) for t in (tokens.reshape(-1).tolist() if isinstance(tokens, (torch.Tensor, np.ndarray)) else tokens)]
+    L = len(seq)
+    if L < 1 or not 1 <= gamma <= 16 or not 1 <= ngram_min <= ngram_max <= _lib.SD_LOOKUP_MAX_NGRAM:
+        raise ValueError(f"lookup_propose: {L} tokens, gamma {gamma}, n-gram bounds {ngram_min}..{ngram_max}")
+    match_len, src = 0, L - 1
+    for c in range(1, L):
+        k = 0
+        while k < min(ngram_max, c) and seq[c - 1 - k] == seq[L - 1 - k]:
+            k += 1
+        if k >= ngram_min and k >= match_len:                    # (c ascends: an equal length further on replaces)
+            match_len, src = k, c
+    return [seq[src + i % (L - src)] for i in range(gamma)], match_len, src
