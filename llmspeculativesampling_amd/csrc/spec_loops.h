@@ -354,33 +354,40 @@ static void norm_from_edited(NormRequest &nr, const RowEdits &re) {
     nr.logits = re.rows; nr.ld_in = re.ld; nr.mode &= ~3; nr.tile_max = nullptr;
 }
 
-// (the verify half of an iteration: defined behind spec_iteration, shared with the prompt-lookup loop)
-static int verify_half(const sd_spec_stream &dv, int g, const sd_sampling &sm, const sd_spec_scratch &sc, const Draws &d,
-                       int L, int target_len, const float *r_const, int res_mode, size_t res_bytes, const LoopEvents &ev, bool timed,
-                       void *stream, const LoopOpts &o, int prompt_len);
+// What drafts an iteration's gamma tokens when no draft model does (NULL in a loop: the draft model's gamma steps): one
+// sd_lookup_propose launch over the active streams.  The proposer's two info ints of stream i are at info + 2 * i, behind
+// the streams' result blocks, and ride along in the iteration's one copy.
+struct LookupDraft {
+    int ngram_max, ngram_min;
+    int32_t *info_dev;
+    const int32_t *info_host;
+    int32_t *const *match_len_out;                                // one array per stream; NULL, or a NULL array: not logged
+    // after the wait: the match length of stream `slot`'s iteration number `call`
+    void log_match(int slot, int call) const {
+        if (match_len_out && match_len_out[slot]) match_len_out[slot][call] = info_host[2 * slot];
+    }
+};
+// p - q, max_fn and the draw of the accept / resample are in the rows' dtype when both models keep 16-bit rows; a lookup
+// draft's one-hot rows go with the target's
+static int accept_mode(const sd_spec_scratch &sc, const LookupDraft *lookup) {
+    return lookup || sc.target.norm_mode == sc.draft.norm_mode ? sc.target.norm_mode : 0;
+}
 
 // ---- one whole speculative iteration, enqueued natively ---------------------------------------
 // reference sampling/speculative_sampling.py:1934-2031 for the device-RNG mode: gamma x (draft forward +
-// norm_sample), one target forward over the uncached rows + norm_probs, accept scan, residual / bonus sample,
-// then the 208-byte result block is copied to pinned host memory.  Nothing here synchronises; the caller waits on
-// the stream once per iteration.  `timed`: the draft phase is ev.t[0] .. t[1], the verify phase ev.t[2] .. t[3].
-static int spec_iteration(const sd_spec_stream &dv, int g, const sd_sampling &sm, const sd_spec_scratch &sc, const Draws &d, int L,
-                          int draft_len, int target_len, const float *r_const, const LoopEvents &ev, bool timed, void *stream,
-                          const LoopOpts &o, int prompt_len) {
-    const RowEdits *const re = o.re;
-    SD_REQUIRE(L >= 1 && draft_len >= 0 && draft_len < L && target_len >= 0 && target_len < L + g,
-               "sd_spec_generate: L=%d draft_len=%d target_len=%d", L, draft_len, target_len);
-    SD_REQUIRE(!o.lp || target_len <= L - 1, "sd_spec_generate: logprobs: target_len %d of %d tokens leaves fewer than gamma + 1 target rows",
-               target_len, L);
-    hipStream_t st = (hipStream_t)stream;
+// norm_sample) - draft_steps, or one proposer launch -, then verify_half: one target forward over the uncached rows +
+// norm_probs, accept scan, residual / bonus sample, and the 208-byte result block is copied to pinned host memory.  Nothing
+// here synchronises; single_stream_loop waits on the stream once per iteration.
+//
+// The draft model's half: gamma steps; the sampled token goes straight into seq[] where the next step's embed reads it
+static int draft_steps(const sd_spec_stream &dv, int g, const sd_sampling &sm, const sd_spec_scratch &sc, const Draws &d, int L,
+                       int draft_len, void *stream, const RowEdits *re, int prompt_len) {
     int rc;
     const bool tiles_ok = !re && head_tiles_ok(sm.top_k, sm.temperature, sm.V, sm.ld);   // (an edited pass takes no tile maxima)
     int *const err = dv.err_words;     // [0..gamma) norm err of draft rows, [gamma..2gamma) sample err, [2gamma..3gamma+1) target rows
     HeadReq rq = {};
     HeadOut ho = {};
     rq.raw = true; rq.zero_ld = sm.ld;                           // (zero_rows: per forward, below)
-    if (timed) SD_HIP_CHECK(hipEventRecord(ev.t[0], st));
-    // ---- draft: gamma steps; the sampled token goes straight into seq[] where the next step's embed reads it
     for (int i = 0; i < g; ++i) {
         const int upto = L + i;
         float *q_row = dv.q_hist + (size_t)(upto - 1) * sm.ld;
@@ -399,14 +406,10 @@ static int spec_iteration(const sd_spec_stream &dv, int g, const sd_sampling &sm
         nr.workspace = sc.norm_workspace;
         if ((rc = sd_norm_rows_with_tiles(nr, stream)) != SD_OK) return rc;
     }
-    if (timed) SD_HIP_CHECK(hipEventRecord(ev.t[1], st));
-    // p - q, max_fn and the draw are in the rows' dtype when both models keep 16-bit rows
-    const int res_mode = sc.target.norm_mode == sc.draft.norm_mode ? sc.target.norm_mode : 0;
-    return verify_half(dv, g, sm, sc, d, L, target_len, r_const, res_mode, sizeof(sd_accept_result), ev, timed, stream,
-                       o, prompt_len);
+    return SD_OK;
 }
 
-// The verify half of an iteration, shared by the speculative and the prompt-lookup loop: seq[L .. L + gamma) and the q rows
+// The verify half of an iteration: seq[L .. L + gamma) and the q rows
 // L-1 .. L+gamma-2 are where the draft half (gamma draft steps, or one proposer launch) left them.  One target forward over
 // the uncached rows, the edits, the norm launch, accept scan + residual / bonus sample in `res_mode`, the log-prob launch,
 // and the copy of `res_bytes` from the result block (what follows the block rides along).  Timed: ev.t[2] .. t[3] around the
@@ -468,6 +471,95 @@ static int verify_half(const sd_spec_stream &dv, int g, const sd_sampling &sm, c
     return SD_OK;
 }
 
+// The loop of one stream: per iteration the draft half (the draft model's gamma steps, or `lookup`'s one launch), the verify
+// half, one wait, the commit.  `who`: the entry that was called.  Timed: the draft phase is ev.t[0] .. t[1], the verify
+// phase ev.t[2] .. t[3].  With `lookup` there is no draft session: s->draft_len is neither read nor written.
+static int single_stream_loop(const char *who, const sd_spec_stream &dv, int g, const sd_sampling &sm, const sd_spec_scratch &sc,
+                              sd_seq_state *s, uint64_t random_seed, const float *r_const, void *stream, const LoopOpts &o,
+                              const LookupDraft *lookup) {
+    hipStream_t st = (hipStream_t)stream;
+    const int L0 = s->len;
+    const bool timed = s->draft_ms_out || s->target_ms_out;
+    LoopEvents ev(timed ? 4 : 0, who);
+    if (!ev.ok) return SD_ERR_HIP;
+    const int res_mode = accept_mode(sc, lookup);
+    const size_t res_bytes = sizeof(sd_accept_result) + (lookup ? 2 * sizeof(int32_t) : 0);
+    int eos_total = s->ori_eos_cnt, no_draft_len = 0;
+    int *const draft_len = lookup ? &no_draft_len : &s->draft_len;
+    s->n_iters = s->err = 0;
+    int rc = SD_OK;
+    while (s->len < s->T && s->n_iters < s->max_iters) {
+        const int L = s->len, iters = s->n_iters;
+        if (lookup) SD_REQUIRE(L >= 1 && s->target_len >= 0 && s->target_len < L + g, "%s: L=%d target_len=%d", who, L, s->target_len);
+        // (a lookup iteration leaves draws d .. d + gamma unread - no draft samples, no discarded target sample: one layout)
+        const Draws d = next_draws(s->seed, s->draw, g, random_seed);
+        s->seed = d.seed; s->draw = d.draw;
+        if (!lookup) {                                            // (refused with the draws taken)
+            SD_REQUIRE(L >= 1 && *draft_len >= 0 && *draft_len < L && s->target_len >= 0 && s->target_len < L + g,
+                       "%s: L=%d draft_len=%d target_len=%d", who, L, *draft_len, s->target_len);
+            SD_REQUIRE(!o.lp || s->target_len <= L - 1, "%s: logprobs: target_len %d of %d tokens leaves fewer than gamma + 1 target rows",
+                       who, s->target_len, L);
+        }
+        if (timed) SD_LOOP_HIP(hipEventRecord(ev.t[0], st));
+        if (lookup) {
+            const sd_lookup_item item = {dv.seq, L, dv.q_hist, lookup->info_dev};
+            rc = sd_lookup_propose(&item, 1, sm.V, sm.ld, g, lookup->ngram_max, lookup->ngram_min, stream);
+        } else {
+            rc = draft_steps(dv, g, sm, sc, d, L, *draft_len, stream, o.re, L0);
+        }
+        if (rc != SD_OK) break;
+        if (timed) SD_LOOP_HIP(hipEventRecord(ev.t[1], st));
+        if ((rc = verify_half(dv, g, sm, sc, d, L, s->target_len, r_const, res_mode, res_bytes, ev, timed, stream, o, L0)) != SD_OK) break;
+        SD_LOOP_HIP(hipEventRecord(ev.done, st));
+        if ((rc = poll_event(ev.done, who)) != SD_OK) break;
+        const sd_accept_result r = *dv.res_host;
+        if (r.flags & 2) { s->err = 1; break; }
+        if (r.flags & 8) {                                        // which word: a draft sample error (a draft model's only), or a norm error
+            bool samp = false;
+            if (!lookup) {
+                std::vector<int> ew(3 * g + 1);
+                SD_LOOP_HIP(hipMemcpy(ew.data(), dv.err_words, sizeof(int) * ew.size(), hipMemcpyDeviceToHost));
+                for (int i = g; i < 2 * g; ++i) samp = samp || ew[i] != 0;
+            }
+            s->err = samp ? 1 : 2;
+            // a NaN row may be the poison of a timed-out in-launch wait (fused_kernels.h / normload_kernels.h): say so
+            unsigned wd = 0, wt = 0;
+            if ((lookup || hipMemcpy(&wd, dv.draft->wait_status, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess) &&
+                hipMemcpy(&wt, dv.target->wait_status, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess && (wd | wt)) {
+                if (lookup)
+                    sd_set_error("%s: a fused launch's in-launch wait timed out (status target %#x; sd_session_fused_status): its rows "
+                                 "were poisoned with NaN", who, wt);
+                else
+                    sd_set_error("%s: a fused launch's in-launch wait timed out (status draft %#x, target %#x; "
+                                 "sd_session_fused_status): its rows were poisoned with NaN", who, wd, wt);
+            }
+            break;
+        }
+        if (timed) {
+            float dms = 0.f, tms = 0.f;
+            SD_LOOP_HIP(hipEventElapsedTime(&dms, ev.t[0], ev.t[1]));
+            SD_LOOP_HIP(hipEventElapsedTime(&tms, ev.t[2], ev.t[3]));
+            if (s->draft_ms_out) s->draft_ms_out[iters] = dms;
+            if (s->target_ms_out) s->target_ms_out[iters] = tms;
+        }
+        const int l = r.n_accepted, n = r.n;
+        if (s->acc_len_out) s->acc_len_out[iters] = l;
+        if (lookup) lookup->log_match(0, iters);
+        log_ratios(s->p_at_out, s->q_at_out, (size_t)iters, g, r.p_at, r.q_at);
+        ++s->n_iters;
+        if (!(n >= L - 1 && l >= 0 && l <= g)) {
+            sd_set_error("%s: inconsistent result block (n %d, L %d, accepted %d)", who, n, L, l);
+            rc = SD_ERR_INVALID;
+            break;
+        }
+        commit_result(r, L, g, s->host_seq, &s->len, draft_len, &s->target_len);          // (flags & 2 left the loop above)
+        if (o.lp) commit_logprobs(*o.lp, 0, o.lp->logprob_out[0], L - L0, r);
+        for (int i = L; i < s->len; ++i) eos_total += s->host_seq[i] == sm.eos_token_id;
+        if (eos_total > s->ori_eos_cnt) break;                    // the caller cuts after the first new EOS (:2033-2041)
+    }
+    return rc;
+}
+
 // The device-RNG loop without the interpreter between iterations (reference speculative_sampling.py:1934-2046).
 extern "C" int sd_spec_generate(const sd_spec_stream *dev, int gamma, const sd_sampling *sampling, const sd_spec_scratch *scratch,
                                 sd_seq_state *s, uint64_t random_seed, const float *r_const, void *stream, const sd_loop_opts *opts) {
@@ -488,58 +580,7 @@ extern "C" int sd_spec_generate(const sd_spec_stream *dev, int gamma, const sd_s
     if (int rc = resolve_loop_opts("sd_spec_generate", "stream", opts, 1, sm.V, gamma + 1, sm.eos_token_id, false, &o); rc != SD_OK)
         return rc;
     refresh_env();
-    const int g = gamma, L0 = s->len;
-    const bool timed = s->draft_ms_out || s->target_ms_out;
-    LoopEvents ev(timed ? 4 : 0, "sd_spec_generate");
-    if (!ev.ok) return SD_ERR_HIP;
-    int eos_total = s->ori_eos_cnt;
-    s->n_iters = s->err = 0;
-    int rc = SD_OK;
-    while (s->len < s->T && s->n_iters < s->max_iters) {
-        const int L = s->len, iters = s->n_iters;
-        const Draws d = next_draws(s->seed, s->draw, g, random_seed);
-        s->seed = d.seed; s->draw = d.draw;
-        if ((rc = spec_iteration(*dev, g, sm, *scratch, d, L, s->draft_len, s->target_len, r_const, ev, timed, stream, o, L0)) != SD_OK) break;
-        SD_LOOP_HIP(hipEventRecord(ev.done, (hipStream_t)stream));
-        if ((rc = poll_event(ev.done, "sd_spec_generate")) != SD_OK) break;
-        const sd_accept_result r = *dev->res_host;
-        if (r.flags & 2) { s->err = 1; break; }
-        if (r.flags & 8) {                                        // which word: a draft sample error, or a norm error
-            std::vector<int> ew(3 * g + 1);
-            SD_LOOP_HIP(hipMemcpy(ew.data(), dev->err_words, sizeof(int) * ew.size(), hipMemcpyDeviceToHost));
-            bool samp = false;
-            for (int i = g; i < 2 * g; ++i) samp = samp || ew[i] != 0;
-            s->err = samp ? 1 : 2;
-            // a NaN row may be the poison of a timed-out in-launch wait (fused_kernels.h / normload_kernels.h): say so
-            unsigned wd = 0, wt = 0;
-            if (hipMemcpy(&wd, dev->draft->wait_status, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess &&
-                hipMemcpy(&wt, dev->target->wait_status, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess && (wd | wt))
-                sd_set_error("sd_spec_generate: a fused launch's in-launch wait timed out (status draft %#x, target %#x; "
-                             "sd_session_fused_status): its rows were poisoned with NaN", wd, wt);
-            break;
-        }
-        if (timed) {
-            float dms = 0.f, tms = 0.f;
-            SD_LOOP_HIP(hipEventElapsedTime(&dms, ev.t[0], ev.t[1]));
-            SD_LOOP_HIP(hipEventElapsedTime(&tms, ev.t[2], ev.t[3]));
-            if (s->draft_ms_out) s->draft_ms_out[iters] = dms;
-            if (s->target_ms_out) s->target_ms_out[iters] = tms;
-        }
-        const int l = r.n_accepted, n = r.n;
-        if (s->acc_len_out) s->acc_len_out[iters] = l;
-        log_ratios(s->p_at_out, s->q_at_out, (size_t)iters, g, r.p_at, r.q_at);
-        ++s->n_iters;
-        if (!(n >= L - 1 && l >= 0 && l <= g)) {
-            sd_set_error("sd_spec_generate: inconsistent result block (n %d, L %d, accepted %d)", n, L, l);
-            rc = SD_ERR_INVALID;
-            break;
-        }
-        commit_result(r, L, g, s->host_seq, &s->len, &s->draft_len, &s->target_len);      // (flags & 2 left the loop above)
-        if (o.lp) commit_logprobs(*o.lp, 0, o.lp->logprob_out[0], L - L0, r);
-        for (int i = L; i < s->len; ++i) eos_total += s->host_seq[i] == sm.eos_token_id;
-        if (eos_total > s->ori_eos_cnt) break;                    // the caller cuts after the first new EOS (:2033-2041)
-    }
-    return rc;
+    return single_stream_loop("sd_spec_generate", *dev, gamma, sm, *scratch, s, random_seed, r_const, stream, o, nullptr);
 }
 
 // ---- the prompt queue of the lock-step loop ---------------------------------------------------------------------
@@ -694,21 +735,30 @@ static int queue_idle_prefill(PromptQueue &q, sd_batch_stream *slots, const std:
     return SD_OK;
 }
 
+// rows per target pass of a lock-step loop: every verify row is a logit row (sd_model_max_pass_rows, 64 for a model whose
+// lm_head or per-layer GEMMs stop at the streaming kernel)
+static int target_pass_rows(const sd_batch_stream *streams, const sd_spec_scratch &sc) {
+    return std::min(sc.max_rows_per_forward, streams[0].target ? streams[0].target->max_pass_rows : SD_MAX_ROWS);
+}
+
 // The lock-step loop of sampling/batch.py in native code (reference algorithm per stream: speculative_sampling.py:1934-2046),
 // with or without a prompt queue behind the streams' slots.
-// `who`: the entry that was called.  o's members are indexed by stream - with a queue, by prompt.
-static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_streams, PromptQueue *q, int gamma, const sd_sampling &sm,
-                         uint64_t random_seed, const float *r_const, const sd_spec_scratch &sc, sd_lockstep_log *log, void *stream,
-                         const LoopOpts &o) {
+// `who`: the entry that was called.  o's members are indexed by stream - with a queue, by prompt.  `lookup` (never with a
+// queue): one proposer launch drafts for the active streams, which have no draft sessions; their draft_len stays as it is.
+static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_streams, PromptQueue *q, const LookupDraft *lookup, int gamma,
+                         const sd_sampling &sm, uint64_t random_seed, const float *r_const, const sd_spec_scratch &sc,
+                         sd_lockstep_log *log, void *stream, const LoopOpts &o) {
+    SD_REQUIRE(!(q && lookup), "%s: a prompt queue behind a lookup drafter", who);
     const sd_row_sampling *const params = o.params;
     const sd_logprob_block *const lp = o.lp;
     const RowEdits *const re = o.re;
     hipStream_t st = (hipStream_t)stream;
     const int g = gamma, n_err = 3 * g + 1;
-    // rows per target pass (every verify row is a logit row: sd_model_max_pass_rows, 64 for a model whose lm_head or
-    // per-layer GEMMs stop at the streaming kernel) and per draft pass (sd_batch_forward's own limit)
-    const int pass_rows = std::min(sc.max_rows_per_forward, streams[0].target ? streams[0].target->max_pass_rows : SD_MAX_ROWS);
+    // rows per target pass and per draft pass (sd_batch_forward's own limit)
+    const int pass_rows = target_pass_rows(streams, sc);
     const int draft_rows = std::min(streams[0].draft ? streams[0].draft->max_rows : SD_MAX_ROWS, SD_MAX_ROWS);
+    // the iteration's one copy: the streams' result blocks and, behind them, a lookup drafter's info ints
+    const size_t res_bytes = (size_t)n_streams * (sizeof(sd_accept_result) + (lookup ? 2 * sizeof(int32_t) : 0));
     LoopEvents ev(2, who);
     if (!ev.ok) return SD_ERR_HIP;
     log->n_iters = log->err = 0;
@@ -750,8 +800,9 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
         if (side && p.n_act == 0) ++q->extra_passes;
     };
     // SD_BATCH_FUSED_TAIL=0: the round-1 sampling tail (logits copy, candidate pass + norm per draft step; dense accept scan +
-    // resample) - kept for A/B runs and as the reference the fused tail is tested against; read per call
-    const bool fused_tail = !(getenv("SD_BATCH_FUSED_TAIL") && atoi(getenv("SD_BATCH_FUSED_TAIL")) == 0);
+    // resample) - kept for A/B runs and as the reference the fused tail is tested against; read per call, and not at all with a
+    // lookup drafter, whose loop has the fused tail only
+    const bool fused_tail = lookup || !(getenv("SD_BATCH_FUSED_TAIL") && atoi(getenv("SD_BATCH_FUSED_TAIL")) == 0);
     const bool tiles_ok = head_tiles_ok(sm.top_k, sm.temperature, sm.V, sm.ld);
     int L0[SD_MAX_STREAMS];                                       // (logprobs, penalties without a queue) the streams' lengths on entry
     // the request a stream runs - its index into o's tables: a queue's slot changes parameters, penalties and edits when it
@@ -768,6 +819,7 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
         return any;
     };
     sd_logit_edit_item pitems[SD_MAX_STREAMS];
+    sd_lookup_item lkitems[SD_MAX_STREAMS];
     auto edit_pass = [&](int a0, int m, const HeadOut &src, auto n_rows, auto pos0, NormRequest &nr) -> int {
         int r0 = 0;
         for (int j = 0; j < m; ++j) {
@@ -812,12 +864,21 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
         for (int j = 0; j < n; ++j) {
             Ls[j] = act[j]->len;
             draws[j] = next_draws(act[j]->seed, act[j]->draw, g, random_seed);
-            act[j]->draw += (uint64_t)g;                          // (a failed forward leaves the stream here, seed untouched)
+            // the draft model's samples are taken: a failed forward leaves the stream here, seed untouched.  (A lookup iteration
+            // leaves draws d .. d + gamma unread, and the stream where it was until both halves are enqueued.)
+            if (!lookup) act[j]->draw += (uint64_t)g;
             ctx += Ls[j];
         }
-        // ---- draft: gamma steps over all active streams
+        // ---- draft: one proposer launch, or gamma steps, over all active streams
+        if (lookup) {
+            for (int j = 0; j < n; ++j) {
+                sd_batch_stream &s = *act[j];
+                lkitems[j] = sd_lookup_item{s.seq, Ls[j], s.q_hist, lookup->info_dev + 2 * (&s - streams)};
+            }
+            rc = sd_lookup_propose(lkitems, n, sm.V, sm.ld, g, lookup->ngram_max, lookup->ngram_min, stream);
+        }
         bool rode = false;                                        // a joiner's draft rows rode a pass of this iteration
-        for (int i = 0; i < g && rc == SD_OK; ++i) {
+        for (int i = 0; i < (lookup ? 0 : g) && rc == SD_OK; ++i) {
             for (int j = 0; j < n; ++j) act_rows[j] = Ls[j] + i - act[j]->draft_len;
             if ((rc = plan(0, i == g - 1 && !rode)) != SD_OK) break;
             rode = rode || n_chunks > 0;
@@ -844,7 +905,7 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
                     s.draft_len = Ls[a0 + j] + i;
                 }
                 add_joiners(passes[p], 0);
-                // the single-stream loop's sampler feed (spec_iteration): the head leaves the logits in its own slab, the
+                // the single-stream loop's sampler feed (draft_steps): the head leaves the logits in its own slab, the
                 // maximum of every 16-column tile, and clears the streams' probability rows - no logits copy, no candidate pass
                 HeadReq rq = {};
                 HeadOut ho = {};
@@ -871,7 +932,7 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
         char *const list_base = sc.norm_workspace ? (char *)sc.norm_workspace + sd_norm_candrow_bytes(sc.max_rows_per_forward) : nullptr;
         const size_t list_stride = sd_cand_list_bytes(1);
         list_of.assign(n, nullptr);
-        const int res_mode = sc.target.norm_mode == sc.draft.norm_mode ? sc.target.norm_mode : 0;
+        const int res_mode = accept_mode(sc, lookup);
         // the accept item of active stream j
         auto accept_item = [&](int j) {
             const sd_batch_stream &s = *act[j];
@@ -954,8 +1015,7 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
         }
         if (lp)
             SD_LOOP_HIP(hipMemcpyAsync(lp->host, lp->dev, sizeof(float) * (size_t)n_streams * LP_SLICE, hipMemcpyDeviceToHost, st));
-        SD_LOOP_HIP(hipMemcpyAsync(streams[0].res_host, streams[0].res_dev, sizeof(sd_accept_result) * (size_t)n_streams,
-                                   hipMemcpyDeviceToHost, st));
+        SD_LOOP_HIP(hipMemcpyAsync(streams[0].res_host, streams[0].res_dev, res_bytes, hipMemcpyDeviceToHost, st));
         SD_LOOP_HIP(hipEventRecord(ev.done, st));
         if ((rc = poll_event(ev.done, who)) != SD_OK) break;
         if (iters < log->max_iters_log) {
@@ -971,10 +1031,12 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
             const sd_accept_result r = *s.res_host;
             if (r.flags & (2 | 8)) { failed = true; break; }
             if (s.acc_len_out) s.acc_len_out[s.calls] = r.n_accepted;
+            if (lookup) lookup->log_match((int)(&s - streams), s.calls);
             log_ratios(s.p_at_out, s.q_at_out, (size_t)s.calls, g, r.p_at, r.q_at);
             ++s.calls;
-            commit_result(r, Ls[j], g, s.host_seq, &s.len, &s.draft_len, &s.target_len);
-            if (lp)                                               // a queue's slot writes to the array of the prompt it runs
+            int no_draft_len = 0;
+            commit_result(r, Ls[j], g, s.host_seq, &s.len, lookup ? &no_draft_len : &s.draft_len, &s.target_len);
+            if (lp)                                              // a queue's slot writes to the array of the prompt it runs
                 commit_logprobs(*lp, (int)(&s - streams), lp->logprob_out[request_of(s)], Ls[j] - prompt_len_of(s), r);
             int eos_total = 0;
             for (int i = 0; i < s.len; ++i) eos_total += s.host_seq[i] == sm.eos_token_id;
@@ -994,8 +1056,7 @@ static int check_result_blocks(const char *who, const sd_batch_stream *streams, 
 
 // the logit rows of a lock-step loop's largest pass: whole streams of gamma + 1 verify rows, as many as a target pass holds
 static int lockstep_penalty_rows(const sd_batch_stream *streams, int n_streams, int gamma, const sd_spec_scratch &sc) {
-    const int pass_rows = std::min(sc.max_rows_per_forward, streams[0].target ? streams[0].target->max_pass_rows : SD_MAX_ROWS);
-    return std::min(std::max(pass_rows, gamma + 1), n_streams * (gamma + 1));
+    return std::min(std::max(target_pass_rows(streams, sc), gamma + 1), n_streams * (gamma + 1));
 }
 
 extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, const sd_sampling *sampling,
@@ -1010,7 +1071,7 @@ extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, i
     if (int rc = resolve_loop_opts(who, "stream", opts, n_streams, sampling->V, lockstep_penalty_rows(streams, n_streams, gamma, *scratch),
                                    sampling->eos_token_id, true, &o); rc != SD_OK)
         return rc;
-    return lockstep_loop(who, streams, n_streams, nullptr, gamma, *sampling, random_seed, r_const, *scratch, log, stream, o);
+    return lockstep_loop(who, streams, n_streams, nullptr, nullptr, gamma, *sampling, random_seed, r_const, *scratch, log, stream, o);
 }
 
 // ---- prompt-lookup drafting (include/specdec.h has the definition and the loops' contract) ------------------------
@@ -1055,72 +1116,14 @@ extern "C" int sd_lookup_generate(const sd_spec_stream *dev, int gamma, int ngra
     SD_REQUIRE(sm.V == dev->target->m->cfg.vocab && sm.ld >= sm.V, "%s: V %d (ld %ld), the target's vocabulary is %d", who, sm.V, sm.ld,
                dev->target->m->cfg.vocab);
     refresh_env();
-    const int g = gamma, L0 = s->len;
-    const bool timed = s->draft_ms_out || s->target_ms_out;
-    LoopEvents ev(timed ? 4 : 0, who);
-    if (!ev.ok) return SD_ERR_HIP;
-    hipStream_t st = (hipStream_t)stream;
-    int32_t *const info_dev = reinterpret_cast<int32_t *>(dev->res_dev + 1);          // the two ints behind the result block
-    const int32_t *const info_host = reinterpret_cast<const int32_t *>(dev->res_host + 1);
-    LoopOpts o;                                                   // (no options block in this entry: nothing to edit or score)
-    int eos_total = s->ori_eos_cnt, unused_draft_len = 0;
-    s->n_iters = s->err = 0;
-    int rc = SD_OK;
-    while (s->len < s->T && s->n_iters < s->max_iters) {
-        const int L = s->len, iters = s->n_iters;
-        if (!(L >= 1 && s->target_len >= 0 && s->target_len < L + g)) {
-            sd_set_error("%s: L=%d target_len=%d", who, L, s->target_len);
-            rc = SD_ERR_INVALID;
-            break;
-        }
-        // draws d .. d + gamma stay unread (no draft samples, no discarded target sample): the layout is sd_spec_generate's
-        const Draws d = next_draws(s->seed, s->draw, g, 0);
-        s->seed = d.seed; s->draw = d.draw;
-        if (timed) SD_LOOP_HIP(hipEventRecord(ev.t[0], st));
-        const sd_lookup_item item = {dev->seq, L, dev->q_hist, info_dev};
-        if ((rc = sd_lookup_propose(&item, 1, sm.V, sm.ld, g, ngram_max, ngram_min, stream)) != SD_OK) break;
-        if (timed) SD_LOOP_HIP(hipEventRecord(ev.t[1], st));
-        if ((rc = verify_half(*dev, g, sm, *scratch, d, L, s->target_len, nullptr, scratch->target.norm_mode,
-                              sizeof(sd_accept_result) + 2 * sizeof(int32_t), ev, timed, stream, o, L0)) != SD_OK)
-            break;
-        SD_LOOP_HIP(hipEventRecord(ev.done, st));
-        if ((rc = poll_event(ev.done, who)) != SD_OK) break;
-        const sd_accept_result r = *dev->res_host;
-        if (r.flags & 2) { s->err = 1; break; }
-        if (r.flags & 8) {                                        // only the target's norm words can be set: nothing was sampled to draft
-            s->err = 2;
-            unsigned wt = 0;
-            if (hipMemcpy(&wt, dev->target->wait_status, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess && wt)
-                sd_set_error("%s: a fused launch's in-launch wait timed out (status target %#x; sd_session_fused_status): its rows "
-                             "were poisoned with NaN", who, wt);
-            break;
-        }
-        if (timed) {
-            float dms = 0.f, tms = 0.f;
-            SD_LOOP_HIP(hipEventElapsedTime(&dms, ev.t[0], ev.t[1]));
-            SD_LOOP_HIP(hipEventElapsedTime(&tms, ev.t[2], ev.t[3]));
-            if (s->draft_ms_out) s->draft_ms_out[iters] = dms;
-            if (s->target_ms_out) s->target_ms_out[iters] = tms;
-        }
-        const int l = r.n_accepted, n = r.n;
-        if (s->acc_len_out) s->acc_len_out[iters] = l;
-        if (match_len_out) match_len_out[iters] = info_host[0];
-        log_ratios(s->p_at_out, s->q_at_out, (size_t)iters, g, r.p_at, r.q_at);
-        ++s->n_iters;
-        if (!(n >= L - 1 && l >= 0 && l <= g)) {
-            sd_set_error("%s: inconsistent result block (n %d, L %d, accepted %d)", who, n, L, l);
-            rc = SD_ERR_INVALID;
-            break;
-        }
-        commit_result(r, L, g, s->host_seq, &s->len, &unused_draft_len, &s->target_len);
-        for (int i = L; i < s->len; ++i) eos_total += s->host_seq[i] == sm.eos_token_id;
-        if (eos_total > s->ori_eos_cnt) break;                    // the caller cuts after the first new EOS
-    }
-    return rc;
+    // the two info ints are behind the result block; no options block in this entry: nothing to edit or score
+    const LookupDraft lookup = {ngram_max, ngram_min, reinterpret_cast<int32_t *>(dev->res_dev + 1),
+                                reinterpret_cast<const int32_t *>(dev->res_host + 1), &match_len_out};
+    return single_stream_loop(who, *dev, gamma, sm, *scratch, s, 0, nullptr, stream, LoopOpts(), &lookup);
 }
 
-// The lock-step prompt-lookup loop: per iteration one proposer launch over the active streams, the verify passes of whole
-// streams, accept + residual / bonus sample of all streams, one copy (result blocks and info ints) and one wait.
+// The lock-step prompt-lookup loop: lockstep_loop with one proposer launch over the active streams where the gamma draft
+// steps are; the info ints ride behind the streams' result blocks in the iteration's one copy.
 extern "C" int sd_lookup_batch_generate(sd_batch_stream *streams, int n_streams, int gamma, int ngram_max, int ngram_min,
                                         const sd_sampling *sampling, const sd_spec_scratch *scratch, sd_lockstep_log *log,
                                         int32_t **match_len_out, void *stream) {
@@ -1144,104 +1147,10 @@ extern "C" int sd_lookup_batch_generate(sd_batch_stream *streams, int n_streams,
                sm.ld, streams[0].target->m->cfg.vocab);
     if (int rc = check_result_blocks(who, streams, n_streams); rc != SD_OK) return rc;
     refresh_env();
-    hipStream_t st = (hipStream_t)stream;
-    const int g = gamma, n_err = 3 * g + 1;
-    const int per_pass = std::max(1, std::min(sc.max_rows_per_forward, streams[0].target->max_pass_rows) / (g + 1));
-    int32_t *const info_dev = reinterpret_cast<int32_t *>(streams[0].res_dev + n_streams);   // 2 ints per stream behind the blocks
-    const int32_t *const info_host = reinterpret_cast<const int32_t *>(streams[0].res_host + n_streams);
-    const size_t res_bytes = (size_t)n_streams * (sizeof(sd_accept_result) + 2 * sizeof(int32_t));
-    LoopEvents ev(2, who);
-    if (!ev.ok) return SD_ERR_HIP;
-    log->n_iters = log->err = 0;
-    int &iters = log->n_iters;
-    int rc = SD_OK;
-    sd_batch_stream *act[SD_MAX_STREAMS];
-    int Ls[SD_MAX_STREAMS];
-    Draws draws[SD_MAX_STREAMS];
-    sd_lookup_item litems[SD_MAX_STREAMS];
-    sd_accept_item aitems[SD_MAX_STREAMS];
-    const void *list_of[SD_MAX_STREAMS];
-    std::vector<sd_batch_item> items;
-    std::vector<sd_norm_row> rows;
-    char *const list_base = sc.norm_workspace ? (char *)sc.norm_workspace + sd_norm_candrow_bytes(sc.max_rows_per_forward) : nullptr;
-    const size_t list_stride = sd_cand_list_bytes(1);
-    for (int i = 0; i < n_streams; ++i) { streams[i].done = 0; streams[i].calls = 0; }
-    for (;;) {
-        int n = 0;
-        double ctx = 0.0;
-        for (int i = 0; i < n_streams; ++i) {
-            sd_batch_stream &s = streams[i];
-            if (!s.done && s.len >= s.T) s.done = 1;
-            if (s.done) continue;
-            Ls[n] = s.len;
-            draws[n] = next_draws(s.seed, s.draw, g, 0);          // d .. d + gamma stay unread
-            litems[n] = sd_lookup_item{s.seq, s.len, s.q_hist, info_dev + 2 * i};
-            ctx += s.len;
-            act[n++] = &s;
-        }
-        if (n == 0) break;
-        if ((rc = sd_lookup_propose(litems, n, sm.V, sm.ld, g, ngram_max, ngram_min, stream)) != SD_OK) break;
-        // ---- verify: gamma + 1 rows per stream, whole streams per pass; the candidate lists serve the residual / bonus sample
-        // when ONE pass holds every stream (the workspace keeps the lists of one pass)
-        const bool lists_on = sc.norm_workspace && n <= per_pass;
-        SD_LOOP_HIP(hipEventRecord(ev.t[0], st));
-        for (int a0 = 0; a0 < n && rc == SD_OK; a0 += per_pass) {
-            const int m = std::min(per_pass, n - a0);
-            items.assign(m, sd_batch_item{});
-            rows.clear();
-            for (int j = 0; j < m; ++j) {
-                sd_batch_stream &s = *act[a0 + j];
-                verify_pass_rows(items[j], rows, s.target, s.seq, s.p_hist, sm.ld, s.err_words, g, Ls[a0 + j], s.target_len);
-            }
-            if ((rc = batch_forward(items.data(), m, sc.target.logits, sc.target.ld_logits, nullptr, nullptr, stream)) != SD_OK) break;
-            NormRequest nr = norm_request(sm, sc.target.norm_mode, scratch_rows(sc.target));
-            nr.rows = (int)rows.size(); nr.workspace = sc.norm_workspace; nr.lists = lists_on ? list_base : nullptr;
-            rc = sd_norm_batch_tiles(nr, rows.data(), 0, stream);
-            for (int j = 0; j < m; ++j) list_of[a0 + j] = lists_on ? list_base + (size_t)j * (g + 1) * list_stride : nullptr;
-        }
-        if (rc != SD_OK) break;
-        SD_LOOP_HIP(hipEventRecord(ev.t[1], st));
-        for (int j = 0; j < n; ++j) {
-            sd_batch_stream &s = *act[j];
-            s.seed = draws[j].seed; s.draw = draws[j].draw;
-            sd_accept_item it = {};
-            it.p_hist = s.p_hist; it.q_hist = s.q_hist; it.seq = s.seq; it.L = Ls[j];
-            it.philox_seed = draws[j].seed; it.draw_scan = draws[j].scan0; it.draw_resample = draws[j].resample;
-            it.res = s.res_dev; it.err_flags = s.err_words; it.n_err = n_err;
-            aitems[j] = it;
-        }
-        if (lists_on) rc = sd_accept_resample_batch(aitems, n, sm.ld, sm.V, g, sc.target.norm_mode, list_of, stream);
-        else rc = sd_accept_batch(aitems, n, sm.ld, sm.V, g, sc.target.norm_mode, stream);
-        if (rc != SD_OK) break;
-        SD_LOOP_HIP(hipMemcpyAsync(streams[0].res_host, streams[0].res_dev, res_bytes, hipMemcpyDeviceToHost, st));
-        SD_LOOP_HIP(hipEventRecord(ev.done, st));
-        if ((rc = poll_event(ev.done, who)) != SD_OK) break;
-        if (iters < log->max_iters_log) {
-            float ms = 0.f;
-            if (log->verify_ms_out && hipEventElapsedTime(&ms, ev.t[0], ev.t[1]) == hipSuccess) log->verify_ms_out[iters] = ms;
-            if (log->verify_streams_out) log->verify_streams_out[iters] = n;
-            if (log->verify_ctx_out) log->verify_ctx_out[iters] = (float)(ctx / n + g);
-        }
-        ++iters;
-        bool failed = false;
-        for (int j = 0; j < n; ++j) {
-            sd_batch_stream &s = *act[j];
-            const int slot = (int)(&s - streams);
-            const sd_accept_result r = *s.res_host;
-            if (r.flags & (2 | 8)) { failed = true; break; }
-            if (s.acc_len_out) s.acc_len_out[s.calls] = r.n_accepted;
-            if (match_len_out && match_len_out[slot]) match_len_out[slot][s.calls] = info_host[2 * slot];
-            log_ratios(s.p_at_out, s.q_at_out, (size_t)s.calls, g, r.p_at, r.q_at);
-            ++s.calls;
-            int unused_draft_len = 0;
-            commit_result(r, Ls[j], g, s.host_seq, &s.len, &unused_draft_len, &s.target_len);
-            int eos_total = 0;
-            for (int i = 0; i < s.len; ++i) eos_total += s.host_seq[i] == sm.eos_token_id;
-            if (eos_total > s.ori_eos_cnt) s.done = 1;            // the caller cuts after the first new EOS
-        }
-        if (failed) { log->err = 1; break; }
-    }
-    return rc;
+    // 2 info ints per stream behind the blocks; no options block in this entry: nothing to edit or score
+    const LookupDraft lookup = {ngram_max, ngram_min, reinterpret_cast<int32_t *>(streams[0].res_dev + n_streams),
+                                reinterpret_cast<const int32_t *>(streams[0].res_host + n_streams), match_len_out};
+    return lockstep_loop(who, streams, n_streams, nullptr, &lookup, gamma, sm, 0, nullptr, sc, log, stream, LoopOpts());
 }
 
 // The prompt queue: without donors (shared_rows 0) every prompt starts with empty caches.
@@ -1293,7 +1202,7 @@ extern "C" int sd_spec_queue_generate(sd_batch_stream *slots, int n_slots, int s
     PromptQueue q;
     q.prompts = prompts; q.n_prompts = n_prompts; q.prefill_chunk = prefill_chunk;
     q.donor_draft = donor_draft; q.donor_target = donor_target; q.shared_rows = shared_rows;
-    const int rc = lockstep_loop(who, slots, n_slots, &q, gamma, *sampling, random_seed, r_const, *scratch, log, stream, o);
+    const int rc = lockstep_loop(who, slots, n_slots, &q, nullptr, gamma, *sampling, random_seed, r_const, *scratch, log, stream, o);
     if (passes_out) {
         const int v[6] = {q.target_passes, q.draft_passes, q.extra_passes, q.prefill_passes, q.prompt_rows, q.copied_rows};
         std::copy(v, v + 6, passes_out);

@@ -78,15 +78,17 @@ def open_spec_slot(draft_m, target_m, prompt_row, cap: int, gamma: int, temperat
     return draft, target, seq32, err
 
 
-def spec_stream(draft, target, seq32, err, res_dev: int, res_host: int) -> SdSpecStream:
-    """The device side of one speculative stream: sessions, token buffer, probability arenas, error words, result blocks."""
-    return SdSpecStream(draft._session.handle, target._session.handle, seq32.data_ptr(), draft._probs.data_ptr(),
-                        target._probs.data_ptr(), err.data_ptr(), res_dev, res_host)
+def spec_stream(draft, target, seq32, err, res_dev: int, res_host: int, q_hist=None) -> SdSpecStream:
+    """The device side of one speculative stream: sessions, token buffer, probability arenas, error words, result blocks.
+    ``draft`` None (prompt lookup): no draft session, and ``q_hist`` is the arena of the one-hot q rows."""
+    q_rows = draft._probs if draft is not None else q_hist
+    return SdSpecStream(draft._session.handle if draft is not None else None, target._session.handle, seq32.data_ptr(),
+                        q_rows.data_ptr(), target._probs.data_ptr(), err.data_ptr(), res_dev, res_host)
 
 
-def bind_spec_slot(item, draft, target, seq32, err, res_dev: int, res_host: int) -> None:
+def bind_spec_slot(item, draft, target, seq32, err, res_dev: int, res_host: int, q_hist=None) -> None:
     """The device side of an SdBatchStream: its leading fields are an SdSpecStream's."""
-    dev = spec_stream(draft, target, seq32, err, res_dev, res_host)
+    dev = spec_stream(draft, target, seq32, err, res_dev, res_host, q_hist)
     for name, _ in SdSpecStream._fields_:
         setattr(item, name, getattr(dev, name))
 

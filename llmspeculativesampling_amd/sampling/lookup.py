@@ -16,11 +16,11 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from .._lib import SD_LOOKUP_MAX_NGRAM, SdAcceptResult, SdBatchStream, SdSpecStream, check, lib
+from .._lib import SD_LOOKUP_MAX_NGRAM, SdAcceptResult, SdBatchStream, check, lib
 from ..engine import _stream, as_specdec_model, batch_prefill, check_token_ids
 from ..noise import DeviceNoise
-from ._loop_common import (LockstepLog, LoopLog, accept_rates_f64, cut_after_new_eos, details_dict, device_rng, lockstep_result,
-                           make_noise, open_stream, raise_loop_error, sampling_block, spec_scratch)
+from ._loop_common import (LockstepLog, LoopLog, accept_rates_f64, bind_spec_slot, cut_after_new_eos, details_dict, device_rng,
+                           lockstep_result, make_noise, open_stream, raise_loop_error, sampling_block, spec_scratch, spec_stream)
 
 INFO_BYTES = 8                                                    # the proposer's two ints behind a stream's result block
 
@@ -45,12 +45,6 @@ def _check_arguments(target_model, gamma, temperature, ngram_max, ngram_min, rng
     cfg = getattr(target_model, "cfg", None) or getattr(target_model, "config", None)
     if getattr(cfg, "is_encoder_decoder", False):
         raise ValueError("prompt lookup is not available with an encoder-decoder model")
-
-
-def _lookup_stream(target, seq32, q_hist, err, res_dev: int, res_host: int) -> SdSpecStream:
-    """The device side of a lookup stream: an sd_spec_stream with no draft session and an arena for the one-hot rows."""
-    return SdSpecStream(None, target._session.handle, seq32.data_ptr(), q_hist.data_ptr(), target._probs.data_ptr(), err.data_ptr(),
-                        res_dev, res_host)
 
 
 @torch.no_grad()
@@ -94,7 +88,7 @@ def prompt_lookup_sampling(prefix: torch.Tensor, target_model, eos_token_id, pad
     log = LoopLog(host_seq, cap, max_iters, gamma, q_fill=1.0, timed=details)
     match_len = np.zeros(max_iters, dtype=np.int32)
     st = log.seq_state(seq_len0, T, ori_eos_cnt, (0, 0), noise, max_iters)
-    stream = _lookup_stream(target, seq32, q_hist, err_words, res_dev.data_ptr(), res_host.data_ptr())
+    stream = spec_stream(None, target, seq32, err_words, res_dev.data_ptr(), res_host.data_ptr(), q_hist)
     sampling = sampling_block(target._temperature, target._top_k, target._top_p, V, ld, eos_token_id)
     scratch = spec_scratch(target._session, target._session, target._norm_ws, target._session.max_rows)
     try:
@@ -168,10 +162,8 @@ def prompt_lookup_sampling_batch(prefixes: Sequence[torch.Tensor], target_model,
     norm_ws = torch.empty(lib.sd_norm_workspace_bytes(per_pass), dtype=torch.uint8, device=dev)
     arr = (SdBatchStream * B)()
     for i, (it, s) in enumerate(zip(arr, streams)):
-        side = _lookup_stream(s["target"], s["seq32"], s["q_hist"], s["err"], res_dev.data_ptr() + i * res_sz,
-                              res_host.data_ptr() + i * res_sz)
-        for name, _ in SdSpecStream._fields_:                     # (an sd_batch_stream starts with an sd_spec_stream's fields)
-            setattr(it, name, getattr(side, name))
+        bind_spec_slot(it, None, s["target"], s["seq32"], s["err"], res_dev.data_ptr() + i * res_sz, res_host.data_ptr() + i * res_sz,
+                       s["q_hist"])
         it.host_seq = s["log"].host_seq.ctypes.data
         it.len, it.T, it.ori_eos_cnt = s["L"], s["T"], s["ori_eos"]
         it.draft_len, it.target_len = 0, s["L"] - 1

@@ -38,8 +38,14 @@ def _st():
     return torch.cuda.current_stream().cuda_stream
 
 
+_REFS = {}                                                        # one reference run per (prompt, seed, top_k, eos), shared by the tests
+
+
 def _reference(hip, om, prompt, seed, top_k, eos=-1):
-    return R.run(om, prompt, eos, MAX_LEN, G, 1, top_k, 0, NMAX, NMIN, PhiloxOracleNoise(hip.lib, seed, G, _st))
+    key = (tuple(prompt[0].tolist()), seed, top_k, eos)
+    if key not in _REFS:
+        _REFS[key] = R.run(om, prompt, eos, MAX_LEN, G, 1, top_k, 0, NMAX, NMIN, PhiloxOracleNoise(hip.lib, seed, G, _st))
+    return _REFS[key]
 
 
 @pytest.mark.parametrize("case", list(R.PARITY_CASES))
@@ -96,6 +102,36 @@ def test_lock_step_loop_equals_three_single_reference_runs(hip, tiny):
     for p, s, got in zip(prompts, seeds, outs):
         one = hip.S.prompt_lookup_sampling(p.cuda(), tm, eos, None, MAX_LEN, G, 1, 4, 0, NMAX, NMIN, rng=hip.noise.DeviceNoise(s))
         assert torch.equal(one, got)
+
+
+def test_lock_step_loop_with_one_stream_per_verify_pass(hip, tiny, monkeypatch):
+    """A target pass of gamma + 1 rows holds one stream: while several streams are active the verify takes one pass per stream,
+    with no candidate lists and the dense accept launch; the lists come back once a single stream is left.  The reference does
+    not depend on how the passes are cut, so the runs are those of the one-pass case above."""
+    cfg, om, tm = tiny
+    from llmspeculativesampling_amd.sampling import lookup
+    real = lookup.spec_scratch
+    monkeypatch.setattr(lookup, "spec_scratch", lambda draft_ses, target_ses, norm_ws, per_pass: real(draft_ses, target_ses, norm_ws, G + 1))
+    noises = []                                                   # the streams' Philox positions, as the wrapper leaves them
+    monkeypatch.setattr(lookup, "DeviceNoise", lambda seed: noises.append(hip.noise.DeviceNoise(seed)) or noises[-1])
+    prompts = [R.parity_prompt(cfg, ps, n) for ps, n, _ in R.PARITY_BATCH]
+    seeds = [s for _, _, s in R.PARITY_BATCH]
+    full, _ = _reference(hip, om, prompts[2], seeds[2], 4)
+    eos = int(full[0, prompts[2].shape[1] + 14])                  # stream 2 stops early, the others go on
+    wants = [_reference(hip, om, p, s, 4, eos) for p, s in zip(prompts, seeds)]
+    outs, ds = hip.S.prompt_lookup_sampling_batch([p.cuda() for p in prompts], tm, eos, None, MAX_LEN, G, 1, 4, 0, NMAX, NMIN,
+                                                  details=True, seeds=seeds)
+    lens = []
+    for (want, wd), got, gd in zip(wants, outs, ds):
+        print("acc_len", gd["acc_len"], "match_len", gd["match_len"])
+        np.testing.assert_array_equal(got.cpu().numpy(), want.numpy())
+        assert gd["acc_len"] == wd["acc_len"] and gd["match_len"] == wd["match_len"]
+        assert gd["target_call_times"] == len(wd["acc_len"])
+        lens.append(len(wd["acc_len"]))
+    assert [(nz.seed, nz.draw) for nz in noises] == [(s, wd["draws"]) for s, (_, wd) in zip(seeds, wants)]
+    # every stream runs iterations 0 .. len - 1: some iteration had several active streams (one pass each), a later one had one
+    lens.sort()
+    assert lens[-2] >= 1 and lens[-1] > lens[-2], lens
 
 
 BF16_CFG = dict(arch="llama", vocab_size=8192, hidden_size=256, intermediate_size=704, num_hidden_layers=2,
