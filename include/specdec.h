@@ -433,8 +433,9 @@ int sd_session_create(sd_model *m, int max_seq, int max_rows, void *kv_arena, vo
 int sd_session_destroy(sd_session *s);
 /* fp8 KV arena (BASELINE config 5): the arena then holds OCP e4m3 bytes, [n_layers][2][n_kv_heads][max_seq][head_dim],
  * half the bytes of a 16-bit arena; `scales` = device floats [n_layers][2][n_kv_heads], an element x is stored as
- * fp8(x / scale).  K / V rows are quantised where they are appended (the QKV epilogue, after RoPE), the attention kernel
- * widens them back in registers.  16-bit models with head_dim >= 32; call before the first forward. */
+ * fp8(x * (1 / scale)), reciprocal and product both in fp32, clamped to +-448, to nearest even; NaN stays NaN.  K / V rows
+ * are quantised where they are appended (the fused QKV epilogue, after RoPE), the attention kernel widens them back in
+ * registers.  16-bit models in the fused layout with head_dim >= 32; call before the first forward. */
 int sd_session_set_kv_fp8(sd_session *s, const float *scales);
 /* How many times this session has launched a matrix-core prefill attention kernel (attn_prefill_kernel or, past its context
  * limit, attn_prefill_blocked_kernel) so far: once

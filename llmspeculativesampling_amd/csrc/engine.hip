@@ -651,10 +651,12 @@ extern "C" int sd_session_create(sd_model *m, int max_seq, int max_rows, void *k
 
 // Switch the session's KV arena to OCP fp8 e4m3 (BASELINE config 5).  The arena then holds 1 byte per element
 // (half of sd_session_kv_bytes for a 16-bit model); `scales` is a device array [n_layers][2][n_kv_heads] (x is stored as
-// fp8(x / scale)); call before the first forward.
+// fp8(x * (1 / scale)), both in fp32 - model_kernels.h, to_fp8); call before the first forward.  The fused QKV epilogue is
+// the one store site, so the model must be in the fused layout (every 16-bit model the Python engine builds is).
 extern "C" int sd_session_set_kv_fp8(sd_session *s, const float *scales) {
     SD_REQUIRE(s && scales, "sd_session_set_kv_fp8: null argument");
     SD_REQUIRE(is16(s->m->cfg.dtype) && s->m->cfg.head_dim >= 32, "sd_session_set_kv_fp8: needs a 16-bit model with head_dim >= 32");
+    SD_REQUIRE(s->m->cfg.fused_layout != 0, "sd_session_set_kv_fp8: needs the fused weight layout (cfg.fused_layout)");
     s->kv_fp8 = 1;
     s->kv_scale = scales;
     return SD_OK;

@@ -49,7 +49,7 @@ struct RowTab {
     int tree, tree_base;
     unsigned long long tree_mask[SD_MAX_TREE];
     int kv_fp8;                                     // the arenas hold OCP fp8 e4m3 (1 byte per element) instead of T
-    const float *kv_scale[SD_MAX_STREAMS];          // fp8: per (layer, k|v, kv head) scales [L][2][Hkv], x = fp8 * scale
+    const float *kv_scale[SD_MAX_STREAMS];          // fp8: per (layer, k|v, kv head) scales [L][2][Hkv], stored fp8(x * (1 / scale)), read fp8 * scale
     // attention groups: <= ATT_TQ consecutive rows of one stream (first row, count, position of the first row, stream)
     int grp_row0[SD_MAX_GROUPS], grp_n[SD_MAX_GROUPS], grp_pos[SD_MAX_GROUPS], grp_stream[SD_MAX_GROUPS];
 };
@@ -98,17 +98,21 @@ enum { RES_PRE = 0, RES_POST = 1, RES_NONE = 2 };   // norm after the residual f
 enum { EPI_PART = 0, EPI_ACT_SILU = 1, EPI_ACT_RELU = 2, EPI_QKV_ROPE = 3, EPI_QKV_PLAIN = 4, EPI_HEAD = 5 };
 
 // Arguments of the fused epilogues (SB == 1: the workgroup holds the whole dot product after its LDS fold).
-// ---- fp8 (OCP e4m3, gfx950's native form) KV arena: x is stored as fp8(x / scale), read back as fp8 * scale.  The
-// attention kernel folds the K scale into the scores and the V scale into the output, so the fp8 -> 16-bit conversion of a
-// key / value element is exact (3 mantissa bits fit either 16-bit type).
+// ---- fp8 (OCP e4m3, gfx950's native form) KV arena: x (already rounded to the model's 16-bit type) is stored as
+// fp8(x * (1 / scale)), reciprocal and product both rounded to fp32 - NOT fp8(x / scale), which is another byte for a few
+// 16-bit values at scales such as 0.3 or 1.7 - clamped to +-448, to nearest even with denormals; read back as fp8 * scale.
+// The attention kernel folds the K scale into the scores and the V scale into the output, so the fp8 -> 16-bit conversion
+// of a key / value element is exact (3 mantissa bits fit either 16-bit type).  tests/fp8_store.py holds the definition in
+// integers; tests/test_gpu_fp8_store.py pins every stored byte to it.
+// NaN stays NaN (S.1111.111), as it would in a 16-bit arena: fminf / fmaxf return their other operand, so the bare clamp
+// would turn a poisoned row into the finite key -448.
+__device__ __forceinline__ float fp8_clamp(float p) { return p != p ? p : fminf(fmaxf(p, -448.f), 448.f); }
 __device__ __forceinline__ unsigned char to_fp8(float x, float inv_scale) {
-    const float v = fminf(fmaxf(x * inv_scale, -448.f), 448.f);
-    return (unsigned char)(__builtin_amdgcn_cvt_pk_fp8_f32(v, 0.f, 0, false) & 0xff);
+    return (unsigned char)(__builtin_amdgcn_cvt_pk_fp8_f32(fp8_clamp(x * inv_scale), 0.f, 0, false) & 0xff);
 }
 __device__ __forceinline__ void store4_fp8(unsigned char *dst, float a, float b, float c, float d, float inv_scale) {
-    const float lo = -448.f, hi = 448.f;
-    int w = __builtin_amdgcn_cvt_pk_fp8_f32(fminf(fmaxf(a * inv_scale, lo), hi), fminf(fmaxf(b * inv_scale, lo), hi), 0, false);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(fminf(fmaxf(c * inv_scale, lo), hi), fminf(fmaxf(d * inv_scale, lo), hi), w, true);
+    int w = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_clamp(a * inv_scale), fp8_clamp(b * inv_scale), 0, false);
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_clamp(c * inv_scale), fp8_clamp(d * inv_scale), w, true);
     *reinterpret_cast<int *>(dst) = w;
 }
 // 8 consecutive fp8 elements -> 8 elements of the 16-bit type T packed as the MFMA operand / the P.V unpack expects
@@ -938,15 +942,8 @@ __global__ void qkv_epilogue_kernel(const float *__restrict__ part, int S, size_
         q[d] = from_f<T>(o0);
         q[d + hd] = from_f<T>(o1);
     } else {
+        // (no fp8 store here: an fp8 arena needs the fused layout - sd_session_set_kv_fp8 - whose epilogue is the one store site)
         const int kvh = is_k ? head - Hq : head - Hq - Hkv;
-        if (tab.kv_fp8) {
-            unsigned char *dst8 = (unsigned char *)tab.kv_base[strm] + (size_t)layer * 2 * Hkv * max_seq * D +
-                                  ((size_t)(head - Hq) * max_seq + tab_slot(tab, row)) * D;
-            const float inv_sc = 1.0f / tab.kv_scale[strm][(size_t)layer * 2 * Hkv + (head - Hq)];
-            dst8[d] = to_fp8(o0, inv_sc);
-            dst8[d + hd] = to_fp8(o1, inv_sc);
-            return;
-        }
         T *dst = (is_k ? karena : varena) + ((size_t)kvh * max_seq + tab_slot(tab, row)) * D;
         dst[d] = from_f<T>(o0);
         dst[d + hd] = from_f<T>(o1);

@@ -408,7 +408,8 @@ class Session:
         self.kv_fp8 = kv_dtype == "fp8"
         assert kv_dtype in (None, "fp8"), kv_dtype
         shape = (cfg.num_hidden_layers, 2, cfg.num_key_value_heads, self.max_seq, cfg.head_dim)
-        if self.kv_fp8:                              # 1 byte per element; x is stored as fp8(x / scale[layer, k|v, head])
+        if self.kv_fp8:                              # 1 byte per element; x is stored as fp8(x * (1 / scale[layer, k|v, head])),
+                                                     # reciprocal and product both in fp32 (tests/fp8_store.py: e4m3_byte)
             self.kv = torch.zeros(shape, dtype=torch.uint8, device=dev)
             self.kv_scale = torch.ones((cfg.num_hidden_layers, 2, cfg.num_key_value_heads), dtype=torch.float32, device=dev)
         else:

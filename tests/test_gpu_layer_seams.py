@@ -324,7 +324,8 @@ def test_written_kv_rows_and_untouched_arena(hip, name, dt, pos0s, n):
 
 
 def test_fp8_arena_keeps_every_byte_outside_the_written_slots(hip):
-    """The same pass into an e4m3 arena: only the sentinel half is asserted (the stored bytes' exactness is not this test's)."""
+    """The same pass into an e4m3 arena: only the sentinel half is asserted here; every stored byte is held to exact e4m3
+    under its own scale by test_gpu_fp8_store.py."""
     name, dt, n = "llama_h256", "bf16", S.KV_ROWS
     st = _Stats(f"kv fp8 {name}")
     m = _model(hip, name, dt)
