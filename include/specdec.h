@@ -949,6 +949,73 @@ typedef struct sd_loop_opts {
     const sd_logit_edit_block *edits;
 } sd_loop_opts;
 
+/* ---- Grammar-constrained decoding: a per-request token automaton masks every logit row.  The allowed set of a row depends on
+ * the tokens the request has emitted so far, so the automaton advances on the device, along the drafted tokens, inside the one
+ * launch that already edits a pass's logit rows.
+ * sd_grammar: a deterministic automaton over token classes.  All pointers are device pointers and the arrays are caller-owned;
+ * the struct itself is copied where it is attached.
+ *   masks  n_states x W words, W = (V + 31) / 32: bit t & 31 of word s * W + (t >> 5) set = token t allowed in state s
+ *   next   n_states x n_classes: the state after a token of class c in state s, or -1
+ *   cls    V entries in [0, n_classes): a token's class; NULL = identity (n_classes == V)
+ * States.  A stream has prompt length P on entry of the call; the logit row at position pos predicts output token number
+ * j = pos + 1 - P and is masked by state s_j:
+ *   s_j = start for j <= 0;   s_{j+1} = step(s_j, seq[P + j]);
+ *   step(s, t) = next[s * n_classes + (cls ? cls[t] : t)] when 0 <= s < n_states, 0 <= t < V and that entry lies in
+ *   [0, n_states); step(s, t) = -1 (dead) in every other case.  Nothing is read out of bounds for any t or s.
+ * Edit order: penalties -> bias -> allowed mask -> grammar -> EOS floor.  With s_j >= 0 a token whose bit in masks[s_j] is
+ * clear becomes -inf, whatever the logit holds.  A dead row (s_j < 0) skips the grammar part, and so does a row with j < 0; their
+ * other edits still apply.  In valid use a dead row can only follow a drafted token that the target gives zero mass: that token
+ * is rejected at that row, so no later row is used - the rule exists so that nothing faults and no spurious row of -inf raises
+ * 'norm logits error' on a row nobody samples from.  An id that no part touches keeps its bits.
+ * (sampling.utils.apply_grammar is this text in torch; it composes after apply_logit_edits.)
+ * State cache.  A stream owns `states`, a device int32 array with states[j] = s_j.  A launch whose first row has j0 >= 1 reads
+ * states[j0 - 1] - the caller guarantees it is valid - and writes states[j0 .. j0 + rows); for j0 <= 0 it starts from `start`
+ * and writes only indices >= 0.  It never reads an index it writes, so the result is a pure function of its inputs, and no
+ * launch walks more than rows + 1 transitions.
+ * Why the loops keep states[j0 - 1] valid: an iteration's verify pass covers rows j0 .. j0 + gamma and writes
+ * states[j0 .. j0 + gamma] along the drafted tokens.  After n accepted tokens plus the resampled or bonus token the next first
+ * row is j0' = j0 + n + 1 <= j0 + gamma + 1.  states[j0' - 1] was written along accepted tokens only, and those did not
+ * change.  states[j0'] is re-derived from the new token seq[P + j0' - 1], which overwrites the stale value the rejected draft
+ * left.  Each draft step (one row) derives its state from the previous step's state the same way, and the verify rewrites the
+ * same values.  An autoregressive step is the one-row case.  A queue slot that changes hands starts again at j0 = 0. */
+typedef struct {
+    const uint32_t *masks;
+    const int32_t *next;
+    const int32_t *cls;
+    int32_t n_states, n_classes, start;
+} sd_grammar;
+/* Attaches a grammar to a stream's TARGET session (sd_ar_stream.session in the autoregressive loop), as sd_session_set_kv_fp8
+ * and sd_session_set_tp attach their state; g == NULL detaches.  The struct is copied; `states` (device, states_cap ints) is the
+ * stream's state cache.  Refused with SD_ERR_INVALID, naming what is wrong: a null session; n_states < 1; n_classes < 1; start
+ * outside [0, n_states); a NULL masks, next or states; states_cap < 1; cls == NULL with n_classes different from the model's
+ * vocabulary.
+ * The four loops that take sd_loop_opts look at their streams' target sessions: a pass of a draft step, of the verify or of an
+ * autoregressive step that holds at least one active stream with a grammar is an edited pass, also when penalties and edits are
+ * neutral.  Its one launch is sd_grammar_rows (below) into the edit block's slab; the norm request reads the slab and asks for
+ * no tile maxima; everything else - joiner rows, accept / resample, candidate lists, the Philox order, sd_token_logprobs on
+ * the raw rows - is untouched.  Draft and target rows get the same mask, so every loop's output is distributed as the target's
+ * own sampling under the grammar.  A pass without a grammar stream is the pass it was, launch for launch.  Refused behind the
+ * entry's own refusals and the members of opts, before anything is written or launched: a stream with a grammar while
+ * opts->edits is NULL (the masked rows need the edit block's slab; a block of neutral records is enough); states_cap smaller
+ * than the output positions the call can reach, T - P + gamma + 2 (gamma 0 in the autoregressive loop; in the queue the largest
+ * T and the smallest L); a stream that arrives with more cached target rows than len - 1.  In the queue the grammar of a slot's
+ * session serves every prompt that decodes in the slot, so the queue supports one grammar per call, attached to all slots, each
+ * slot with its own `states`; per-prompt grammars in the queue are out of scope.  sd_lookup_generate, sd_lookup_batch_generate
+ * and sd_spec_multi_generate have no edit pass and refuse a target session that carries a grammar. */
+int sd_session_set_grammar(sd_session *s, const sd_grammar *g, int32_t *states, int32_t states_cap);
+/* sd_edit_rows plus the grammar: the same grid, alignment freedom and `mode`, out of place, up to 16 items x 17 rows in ONE
+ * launch.  Row r of an item has j = row.hist0 + r - row.prompt_len; the workgroups of a row walk its at most r + 1 transitions
+ * from states[j0 - 1] (or from start) themselves, and the row's first workgroup writes states[j0 + r].  An item with a NULL
+ * grammar is edited exactly as sd_edit_rows edits it (its states is not read).  Refused with SD_ERR_INVALID before any launch,
+ * naming the item: what sd_edit_rows refuses, then per item the grammar refusals of sd_session_set_grammar (with V for the
+ * model's vocabulary; no states_cap here: the caller sizes states for j0 + rows). */
+typedef struct {
+    sd_logit_edit_item row;
+    const sd_grammar *grammar;
+    int32_t *states;
+} sd_grammar_item;
+int sd_grammar_rows(const sd_grammar_item *items, int n_items, int V, int mode, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Prompt-lookup drafting: speculative decoding without a draft model.  The proposer finds the most recent earlier occurrence
  * of the sequence's last few tokens and proposes the tokens that followed it.  A lookup draft is a deterministic proposal, so

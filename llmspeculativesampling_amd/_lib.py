@@ -179,6 +179,15 @@ class SdLoopOpts(C.Structure):                          # the loops' optional la
                 ("penalties", C.POINTER(SdPenaltyBlock)), ("edits", C.POINTER(SdLogitEditBlock))]
 
 
+class SdGrammar(C.Structure):                            # a token automaton; device tables, caller-owned
+    _fields_ = [("masks", C.c_void_p), ("next", C.c_void_p), ("cls", C.c_void_p), ("n_states", C.c_int32), ("n_classes", C.c_int32),
+                ("start", C.c_int32)]
+
+
+class SdGrammarItem(C.Structure):                        # one item of sd_grammar_rows: sd_edit_rows' item, the grammar, the state cache
+    _fields_ = [("row", SdLogitEditItem), ("grammar", C.POINTER(SdGrammar)), ("states", C.c_void_p)]
+
+
 class SdLookupItem(C.Structure):                         # one stream of sd_lookup_propose
     _fields_ = [("seq", C.c_void_p), ("L", C.c_int32), ("q_hist", C.c_void_p), ("info", C.c_void_p)]
 
@@ -235,7 +244,7 @@ C_STRUCTS = {"sd_accept_result": SdAcceptResult, "sd_norm_row": SdNormRow, "sd_r
              "sd_score_out": SdScoreOut, "sd_penalty": SdPenalty,
              "sd_penalty_item": SdPenaltyItem, "sd_penalty_block": SdPenaltyBlock, "sd_logit_edit": SdLogitEdit,
              "sd_logit_edit_item": SdLogitEditItem, "sd_logit_edit_block": SdLogitEditBlock, "sd_loop_opts": SdLoopOpts,
-             "sd_lookup_item": SdLookupItem,
+             "sd_lookup_item": SdLookupItem, "sd_grammar": SdGrammar, "sd_grammar_item": SdGrammarItem,
              "sd_model_config": SdModelConfig,
              "sd_gemm_route_info": SdGemmRouteInfo, "sd_model_weights": SdModelWeights}
 
@@ -320,6 +329,8 @@ SYMBOLS = [
     ("sd_score_sequence", _I, [_VP, _VP, _I, _I, _I, _VP, _L, _I, _P(SdScoreOut), _VP]),
     ("sd_penalize_rows", _I, [_P(SdPenaltyItem), _I, _I, _I, _VP]),
     ("sd_edit_rows", _I, [_P(SdLogitEditItem), _I, _I, _I, _VP]),
+    ("sd_session_set_grammar", _I, [_VP, _P(SdGrammar), _VP, C.c_int32]),
+    ("sd_grammar_rows", _I, [_P(SdGrammarItem), _I, _I, _I, _VP]),
     ("sd_lookup_propose", _I, [_P(SdLookupItem), _I, _I, _L, _I, _I, _I, _VP]),
     ("sd_lookup_generate", _I, [_P(SdSpecStream), _I, _I, _I, _P(SdSampling), _P(SdSpecScratch), _P(SdSeqState), _VP, _VP]),
     ("sd_lookup_batch_generate", _I, [_P(SdBatchStream), _I, _I, _I, _I, _P(SdSampling), _P(SdSpecScratch), _P(SdLockstepLog), _VPP,

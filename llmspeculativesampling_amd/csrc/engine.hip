@@ -22,6 +22,7 @@
 #include "score_kernels.h"
 #include "penalty_kernels.h"
 #include "logit_edit_kernels.h"
+#include "grammar_kernels.h"
 #include "lookup_kernels.h"
 #include "sampler_host.h"
 
@@ -72,6 +73,9 @@ struct sd_session {
     int w12_launches;            // GEMM launches that streamed 12-bit weight records so far (sd_session_w12_launches)
     const float *kv_scale;   // device [L][2][Hkv]
     struct sd_tp *tp;   // tensor-parallel group of this shard (NULL: the model is whole)
+    sd_grammar gram;        // the grammar of the stream this session is the target of (sd_session_set_grammar; masks NULL: none)
+    int32_t *gram_states;   // ... and the stream's state cache, gram_cap device ints
+    int gram_cap;
     float *tp_in, *tp_out;   // [max_rows][hidden] fp32: this rank's partial O / down output, and the all-reduced sum
     float *attn_part;   // [groups*splits <= 64][Hq][TQ][D+2] partial attention sums of the split-key path
     float *part;
@@ -615,6 +619,9 @@ extern "C" int sd_session_create(sd_model *m, int max_seq, int max_rows, void *k
     s->tp = nullptr;
     s->kv_fp8 = 0;
     s->kv_scale = nullptr;
+    s->gram = sd_grammar{};
+    s->gram_states = nullptr;
+    s->gram_cap = 0;
     s->prefill_attn_launches = 0;
     s->w12_launches = 0;
     s->prefill_attn_blocked_launches = 0;
@@ -659,6 +666,36 @@ extern "C" int sd_session_set_kv_fp8(sd_session *s, const float *scales) {
     SD_REQUIRE(s->m->cfg.fused_layout != 0, "sd_session_set_kv_fp8: needs the fused weight layout (cfg.fused_layout)");
     s->kv_fp8 = 1;
     s->kv_scale = scales;
+    return SD_OK;
+}
+
+// What every entry refuses in a grammar (`what` names where it sits: "grammar", "item 3: grammar"); V: the vocabulary.
+static int check_grammar(const char *who, const char *what, const sd_grammar &g, const int32_t *states, int V) {
+    SD_REQUIRE(g.n_states >= 1, "%s: %s: n_states %d < 1", who, what, g.n_states);
+    SD_REQUIRE(g.n_classes >= 1, "%s: %s: n_classes %d < 1", who, what, g.n_classes);
+    SD_REQUIRE(g.start >= 0 && g.start < g.n_states, "%s: %s: start %d outside [0, %d)", who, what, g.start, g.n_states);
+    SD_REQUIRE(g.masks && g.next && states, "%s: %s: null masks, next or states", who, what);
+    SD_REQUIRE(V < 0 || g.cls || g.n_classes == V, "%s: %s: no cls table and n_classes %d differs from the vocabulary %d", who, what,
+               g.n_classes, V);
+    return SD_OK;
+}
+
+// Attach a grammar to the session of a stream's target model (include/specdec.h has the definition and the loops' contract);
+// g == NULL detaches.  Host state only: nothing is launched, the device arrays stay the caller's.
+extern "C" int sd_session_set_grammar(sd_session *s, const sd_grammar *g, int32_t *states, int32_t states_cap) {
+    SD_REQUIRE(s, "sd_session_set_grammar: null session");
+    if (!g) {
+        s->gram = sd_grammar{};
+        s->gram_states = nullptr;
+        s->gram_cap = 0;
+        return SD_OK;
+    }
+    if (int rc = check_grammar("sd_session_set_grammar", "grammar", *g, states, -1); rc != SD_OK) return rc;   // (reads no session)
+    SD_REQUIRE(states_cap >= 1, "sd_session_set_grammar: grammar: states_cap %d < 1", states_cap);
+    if (int rc = check_grammar("sd_session_set_grammar", "grammar", *g, states, s->m->cfg.vocab); rc != SD_OK) return rc;
+    s->gram = *g;
+    s->gram_states = states;
+    s->gram_cap = states_cap;
     return SD_OK;
 }
 

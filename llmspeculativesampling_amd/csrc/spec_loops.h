@@ -251,6 +251,12 @@ static int check_edit(const char *who, const char *what, int i, const sd_logit_e
     return SD_OK;
 }
 
+// item i's edits in their columns of the table
+static void edit_tab_item(EditTab &e, int i, const sd_logit_edit_item &it) {
+    e.bias_ids[i] = it.edit.bias_ids; e.bias_vals[i] = it.edit.bias_vals; e.n_bias[i] = it.edit.n_bias;
+    e.allowed[i] = it.edit.allowed; e.min_tokens[i] = it.edit.min_tokens; e.eos[i] = it.eos_token_id;
+}
+
 extern "C" int sd_edit_rows(const sd_logit_edit_item *items, int n_items, int V, int mode, void *stream) {
     if (int rc = check_row_edit_call("sd_edit_rows", items, n_items, V, mode); rc != SD_OK) return rc;
     EditTab e = {};
@@ -259,10 +265,43 @@ extern "C" int sd_edit_rows(const sd_logit_edit_item *items, int n_items, int V,
         const sd_logit_edit_item &it = items[i];
         if (int rc = penalty_tab_item("sd_edit_rows", e.pen, i, it, V, &max_rows); rc != SD_OK) return rc;
         if (int rc = check_edit("sd_edit_rows", "item", i, it.edit); rc != SD_OK) return rc;
-        e.bias_ids[i] = it.edit.bias_ids; e.bias_vals[i] = it.edit.bias_vals; e.n_bias[i] = it.edit.n_bias;
-        e.allowed[i] = it.edit.allowed; e.min_tokens[i] = it.edit.min_tokens; e.eos[i] = it.eos_token_id;
+        edit_tab_item(e, i, it);
     }
     return launch_edit_rows(e, n_items, max_rows, V, mode, (hipStream_t)stream);
+}
+
+// ---- grammar-constrained decoding (include/specdec.h has the definition and the loops' contract) ------------------------
+extern "C" int sd_grammar_rows(const sd_grammar_item *items, int n_items, int V, int mode, void *stream) {
+    const char *const who = "sd_grammar_rows";
+    if (int rc = check_row_edit_call(who, items, n_items, V, mode); rc != SD_OK) return rc;
+    GrammarTab g = {};
+    int max_rows = 0;
+    for (int i = 0; i < n_items; ++i) {
+        const sd_logit_edit_item &it = items[i].row;
+        if (int rc = penalty_tab_item(who, g.edit.pen, i, it, V, &max_rows); rc != SD_OK) return rc;
+        if (int rc = check_edit(who, "item", i, it.edit); rc != SD_OK) return rc;
+        edit_tab_item(g.edit, i, it);
+    }
+    for (int i = 0; i < n_items; ++i) {
+        const sd_grammar *gr = items[i].grammar;
+        if (!gr) continue;                                        // edited exactly as sd_edit_rows edits it
+        char what[32];
+        snprintf(what, sizeof what, "item %d: grammar", i);
+        if (int rc = check_grammar(who, what, *gr, items[i].states, V); rc != SD_OK) return rc;
+        g.masks[i] = gr->masks; g.next[i] = gr->next; g.cls[i] = gr->cls; g.states[i] = items[i].states;
+        g.n_states[i] = gr->n_states; g.n_classes[i] = gr->n_classes; g.start[i] = gr->start;
+    }
+    return launch_grammar_rows(g, n_items, max_rows, V, mode, (hipStream_t)stream);
+}
+static bool has_grammar(const sd_session *t) { return t && t->gram.masks; }
+// what the loops refuse in the grammars of their n streams' target sessions (behind opts): a state cache that is smaller than
+// the output positions the call can reach, need[i] for `what` i
+static int check_grammar_states(const char *who, const char *what, const sd_session *const *ses, int n, const int *need) {
+    for (int i = 0; i < n; ++i)
+        SD_REQUIRE(!has_grammar(ses[i]) || ses[i]->gram_cap >= need[i],
+                   "%s: grammar: %s %d: states_cap %d is smaller than the %d output positions the call can reach (T - P + gamma + 2)",
+                   who, what, i, ses[i]->gram_cap, need[i]);
+    return SD_OK;
 }
 
 // what the loops refuse in an edit block, as check_penalty_block does; *eb becomes NULL when every record is neutral
@@ -288,7 +327,11 @@ struct RowEdits {
     const sd_penalty *pen;
     const sd_logit_edit *edit;
     int eos;
-    bool edited(int k) const { return (pen && !penalty_neutral(pen[k])) || (edit && !edit_neutral(edit[k])); }
+    bool grammar;                                                 // a stream of the call has a grammar: its passes are edited passes
+    // request k, decoding on target session t
+    bool edited(int k, const sd_session *t) const {
+        return (pen && !penalty_neutral(pen[k])) || (edit && !edit_neutral(edit[k])) || (grammar && has_grammar(t));
+    }
 };
 
 // what the lock-step loops refuse in a parameter array (`what` names its entries: "stream", "prompt")
@@ -310,9 +353,18 @@ struct LoopOpts {
 // Checks `opts` (NULL: four NULL members) behind the entry's own refusals - row_params, logprobs, penalties, edits, in that
 // order - and resolves it into *o.  n: the streams / prompts (`what`) the members are indexed by; need_rows: the logit rows of
 // the loop's largest pass; the two loops that sample with sm's own triple pass row_params_allowed = false.
+// ses: the n_ses target sessions of the call's streams (entries may be NULL); one of them with a grammar keeps the edit block
+// in use whatever its records hold, and is refused without one.
 static int resolve_loop_opts(const char *who, const char *what, const sd_loop_opts *opts, int n, int V, int need_rows, int eos,
-                             bool row_params_allowed, LoopOpts *o) {
-    if (!opts) return SD_OK;
+                             bool row_params_allowed, LoopOpts *o, const sd_session *const *ses, int n_ses) {
+    int gram = -1;
+    for (int i = n_ses - 1; i >= 0; --i)
+        if (has_grammar(ses[i])) gram = i;
+    if (!opts) {
+        SD_REQUIRE(gram < 0, "%s: grammar: the target session of stream %d has a grammar but opts->edits is NULL: the masked rows need "
+                   "the edit block's slab (a block of neutral records is enough)", who, gram);
+        return SD_OK;
+    }
     if (opts->row_params) {
         SD_REQUIRE(row_params_allowed, "%s: row_params: this loop samples with sampling's own triple", who);
         if (int rc = check_row_params(who, what, opts->row_params, n); rc != SD_OK) return rc;
@@ -325,9 +377,12 @@ static int resolve_loop_opts(const char *who, const char *what, const sd_loop_op
         if (int rc = check_penalty_block(who, what, &pb, n, V, need_rows); rc != SD_OK) return rc;
     if (eb)
         if (int rc = check_edit_block(who, what, &eb, n, V, need_rows); rc != SD_OK) return rc;
+    SD_REQUIRE(gram < 0 || opts->edits, "%s: grammar: the target session of stream %d has a grammar but opts->edits is NULL: the masked "
+               "rows need the edit block's slab (a block of neutral records is enough)", who, gram);
+    if (gram >= 0) eb = opts->edits;                              // (neutral records or not)
     o->params = opts->row_params; o->lp = opts->logprobs;
-    if (eb) o->re_block = RowEdits{eb->rows, eb->ld, eb->max_rows, pb ? pb->params : nullptr, eb->params, eos};
-    else if (pb) o->re_block = RowEdits{pb->rows, pb->ld, pb->max_rows, pb->params, nullptr, eos};
+    if (eb) o->re_block = RowEdits{eb->rows, eb->ld, eb->max_rows, pb ? pb->params : nullptr, eb->params, eos, gram >= 0};
+    else if (pb) o->re_block = RowEdits{pb->rows, pb->ld, pb->max_rows, pb->params, nullptr, eos, false};
     if (pb || eb) o->re = &o->re_block;
     return SD_OK;
 }
@@ -339,8 +394,18 @@ static sd_logit_edit_item edit_item(const RowEdits &re, int k, const HeadOut &sr
                               re.pen ? re.pen[k] : sd_penalty{1.0f, 0.0f, 0.0f},
                               re.edit ? re.edit[k] : sd_logit_edit{nullptr, nullptr, 0, nullptr, 0}, re.eos};
 }
-// The one launch of an edited pass over its n items
-static int edit_rows(const RowEdits &re, const sd_logit_edit_item *items, int n, int V, int mode, void *stream) {
+// The one launch of an edited pass over its n items; ses[j]: the target session of item j's stream.  A pass that holds a
+// stream with a grammar takes sd_grammar_rows, every other pass the launch it took before grammars existed.
+static int edit_rows(const RowEdits &re, const sd_logit_edit_item *items, int n, int V, int mode, void *stream,
+                     const sd_session *const *ses) {
+    bool gram = false;
+    for (int j = 0; re.grammar && j < n; ++j) gram = gram || has_grammar(ses[j]);
+    if (gram) {
+        sd_grammar_item gi[PEN_MAX_ITEMS];
+        for (int j = 0; j < n && j < PEN_MAX_ITEMS; ++j)
+            gi[j] = sd_grammar_item{items[j], has_grammar(ses[j]) ? &ses[j]->gram : nullptr, ses[j] ? ses[j]->gram_states : nullptr};
+        return sd_grammar_rows(gi, n, V, mode, stream);
+    }
     if (re.edit) return sd_edit_rows(items, n, V, mode, stream);
     sd_penalty_item pi[PEN_MAX_ITEMS];
     for (int j = 0; j < n && j < PEN_MAX_ITEMS; ++j) {
@@ -398,7 +463,8 @@ static int draft_steps(const sd_spec_stream &dv, int g, const sd_sampling &sm, c
         NormRequest nr = norm_request(sm, sc.draft.norm_mode, ho);
         if (re) {                                                 // the row at position upto - 1, edited out of place
             const sd_logit_edit_item it = edit_item(*re, 0, ho, 0, 1, dv.seq, upto - 1, prompt_len);
-            if ((rc = edit_rows(*re, &it, 1, sm.V, nr.mode, stream)) != SD_OK) return rc;
+            const sd_session *const ts = dv.target;
+            if ((rc = edit_rows(*re, &it, 1, sm.V, nr.mode, stream, &ts)) != SD_OK) return rc;
             norm_from_edited(nr, *re);
         }
         nr.rows = 1; nr.probs_out = q_row; nr.ld_out = sm.ld; nr.err = err + i;
@@ -442,7 +508,8 @@ static int verify_half(const sd_spec_stream &dv, int g, const sd_sampling &sm, c
         NormRequest nr = norm_request(sm, sc.target.norm_mode, ho);
         if (re) {
             const sd_logit_edit_item it = edit_item(*re, 0, ho, 0, rows, dv.seq, upto - rows, prompt_len);
-            if ((rc = edit_rows(*re, &it, 1, sm.V, nr.mode, stream)) != SD_OK) return rc;
+            const sd_session *const ts = dv.target;
+            if ((rc = edit_rows(*re, &it, 1, sm.V, nr.mode, stream, &ts)) != SD_OK) return rc;
             norm_from_edited(nr, *re);
         }
         nr.rows = rows; nr.probs_out = p_rows; nr.ld_out = sm.ld; nr.err = err + 2 * g;
@@ -577,8 +644,13 @@ extern "C" int sd_spec_generate(const sd_spec_stream *dev, int gamma, const sd_s
                "sd_spec_generate: V %d (ld %ld), the models' vocabularies are %d / %d", sm.V, sm.ld, dev->draft->m->cfg.vocab,
                dev->target->m->cfg.vocab);
     LoopOpts o;
-    if (int rc = resolve_loop_opts("sd_spec_generate", "stream", opts, 1, sm.V, gamma + 1, sm.eos_token_id, false, &o); rc != SD_OK)
+    const sd_session *const ts = dev->target;
+    if (int rc = resolve_loop_opts("sd_spec_generate", "stream", opts, 1, sm.V, gamma + 1, sm.eos_token_id, false, &o, &ts, 1); rc != SD_OK)
         return rc;
+    const int states_need = s->T - s->len + gamma + 2;
+    if (int rc = check_grammar_states("sd_spec_generate", "stream", &ts, 1, &states_need); rc != SD_OK) return rc;
+    SD_REQUIRE(!has_grammar(ts) || s->target_len <= s->len - 1, "sd_spec_generate: grammar: target_len %d of %d tokens: the first "
+               "verify pass must start at the prompt's last row", s->target_len, s->len);
     refresh_env();
     return single_stream_loop("sd_spec_generate", *dev, gamma, sm, *scratch, s, random_seed, r_const, stream, o, nullptr);
 }
@@ -815,10 +887,11 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
     // without a penalised or edited stream is left alone.
     auto pass_edited = [&](int a0, int m) {
         bool any = false;
-        for (int j = 0; re && j < m; ++j) any = any || re->edited(request_of(*act[a0 + j]));
+        for (int j = 0; re && j < m; ++j) any = any || re->edited(request_of(*act[a0 + j]), act[a0 + j]->target);
         return any;
     };
     sd_logit_edit_item pitems[SD_MAX_STREAMS];
+    const sd_session *pses[SD_MAX_STREAMS];
     sd_lookup_item lkitems[SD_MAX_STREAMS];
     auto edit_pass = [&](int a0, int m, const HeadOut &src, auto n_rows, auto pos0, NormRequest &nr) -> int {
         int r0 = 0;
@@ -831,9 +904,10 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
                 return SD_ERR_INVALID;
             }
             pitems[j] = edit_item(*re, request_of(s), src, r0, nr_j, s.seq, pos0(j), prompt_len_of(s));
+            pses[j] = s.target;
             r0 += nr_j;
         }
-        if (int prc = edit_rows(*re, pitems, m, sm.V, nr.mode, stream); prc != SD_OK) return prc;
+        if (int prc = edit_rows(*re, pitems, m, sm.V, nr.mode, stream, pses); prc != SD_OK) return prc;
         norm_from_edited(nr, *re);
         return SD_OK;
     };
@@ -1068,9 +1142,19 @@ extern "C" int sd_spec_batch_generate(sd_batch_stream *streams, int n_streams, i
     SD_REQUIRE(!random_seed || r_const, "%s: random_seed needs its uniform (r_const)", who);
     if (int rc = check_result_blocks(who, streams, n_streams); rc != SD_OK) return rc;
     LoopOpts o;
+    const sd_session *ts[SD_MAX_STREAMS];
+    int states_need[SD_MAX_STREAMS];
+    for (int i = 0; i < n_streams; ++i) {
+        ts[i] = streams[i].target;
+        states_need[i] = streams[i].T - streams[i].len + gamma + 2;
+    }
     if (int rc = resolve_loop_opts(who, "stream", opts, n_streams, sampling->V, lockstep_penalty_rows(streams, n_streams, gamma, *scratch),
-                                   sampling->eos_token_id, true, &o); rc != SD_OK)
+                                   sampling->eos_token_id, true, &o, ts, n_streams); rc != SD_OK)
         return rc;
+    if (int rc = check_grammar_states(who, "stream", ts, n_streams, states_need); rc != SD_OK) return rc;
+    for (int i = 0; i < n_streams; ++i)
+        SD_REQUIRE(!has_grammar(ts[i]) || streams[i].target_len <= streams[i].len - 1, "%s: grammar: stream %d: target_len %d of %d "
+                   "tokens: the first verify pass must start at the prompt's last row", who, i, streams[i].target_len, streams[i].len);
     return lockstep_loop(who, streams, n_streams, nullptr, nullptr, gamma, *sampling, random_seed, r_const, *scratch, log, stream, o);
 }
 
@@ -1115,6 +1199,8 @@ extern "C" int sd_lookup_generate(const sd_spec_stream *dev, int gamma, int ngra
                scratch->max_rows_per_forward, gamma);
     SD_REQUIRE(sm.V == dev->target->m->cfg.vocab && sm.ld >= sm.V, "%s: V %d (ld %ld), the target's vocabulary is %d", who, sm.V, sm.ld,
                dev->target->m->cfg.vocab);
+    SD_REQUIRE(!has_grammar(dev->target), "%s: the target session carries a grammar: this loop has no edit pass (detach it: "
+               "sd_session_set_grammar(s, NULL, NULL, 0))", who);
     refresh_env();
     // the two info ints are behind the result block; no options block in this entry: nothing to edit or score
     const LookupDraft lookup = {ngram_max, ngram_min, reinterpret_cast<int32_t *>(dev->res_dev + 1),
@@ -1140,6 +1226,8 @@ extern "C" int sd_lookup_batch_generate(sd_batch_stream *streams, int n_streams,
                    "%s: stream %d: null pointer", who, i);
         SD_REQUIRE(!s.draft, "%s: stream %d: a draft session: prompt lookup drafts without a model (draft must be NULL)", who, i);
         SD_REQUIRE(s.target->m == streams[0].target->m, "%s: stream %d: a session of another model than stream 0's", who, i);
+        SD_REQUIRE(!has_grammar(s.target), "%s: stream %d: the target session carries a grammar: this loop has no edit pass (detach it: "
+                   "sd_session_set_grammar(s, NULL, NULL, 0))", who, i);
         SD_REQUIRE(s.len >= 1 && s.target_len == s.len - 1, "%s: stream %d: every stream arrives prefilled (target_len %d, len %d - 1)",
                    who, i, s.target_len, s.len);
     }
@@ -1196,9 +1284,14 @@ extern "C" int sd_spec_queue_generate(sd_batch_stream *slots, int n_slots, int s
                    "%s: slot %d: KV arenas of %d / %d positions, slot_cap %d needs %d", who, i, slots[i].draft->max_seq,
                    slots[i].target->max_seq, slot_cap, slot_cap - 2);
     LoopOpts o;
+    const sd_session *ts[SD_MAX_STREAMS];
+    int states_need[SD_MAX_STREAMS], t_max = prompts[0].T, l_min = prompts[0].L;
+    for (int k = 1; k < n_prompts; ++k) { t_max = std::max(t_max, (int)prompts[k].T); l_min = std::min(l_min, (int)prompts[k].L); }
+    for (int i = 0; i < n_slots; ++i) { ts[i] = slots[i].target; states_need[i] = t_max - l_min + gamma + 2; }
     if (int rc = resolve_loop_opts(who, "prompt", opts, n_prompts, sampling->V, lockstep_penalty_rows(slots, n_slots, gamma, *scratch),
-                                   sampling->eos_token_id, true, &o); rc != SD_OK)
+                                   sampling->eos_token_id, true, &o, ts, n_slots); rc != SD_OK)
         return rc;
+    if (int rc = check_grammar_states(who, "slot", ts, n_slots, states_need); rc != SD_OK) return rc;
     PromptQueue q;
     q.prompts = prompts; q.n_prompts = n_prompts; q.prefill_chunk = prefill_chunk;
     q.donor_draft = donor_draft; q.donor_target = donor_target; q.shared_rows = shared_rows;
@@ -1295,6 +1388,8 @@ extern "C" int sd_spec_multi_generate(const sd_multi_replica *reps, int width, i
         SD_REQUIRE(r.draft->m == reps[0].draft->m && r.target->m == reps[0].target->m && r.draft->max_seq == reps[0].draft->max_seq &&
                    r.target->max_seq == reps[0].target->max_seq && r.draft->kv_fp8 == reps[0].draft->kv_fp8 &&
                    r.target->kv_fp8 == reps[0].target->kv_fp8, "sd_spec_multi_generate: replica %d: sessions differ from replica 0's", w);
+        SD_REQUIRE(!has_grammar(r.target), "sd_spec_multi_generate: replica %d: the target session carries a grammar: this loop has no "
+                   "edit pass (detach it: sd_session_set_grammar(s, NULL, NULL, 0))", w);
     }
     const int g = gamma, W = width, n_err = 3 * g + 1;
     const int pass_rows = std::min(sc.max_rows_per_forward, reps[0].target->max_pass_rows);
@@ -1472,9 +1567,14 @@ extern "C" int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, const 
     SD_REQUIRE(n_streams <= streams[0].session->max_pass_rows, "sd_ar_batch_generate: %d streams exceed one pass (%d rows)", n_streams,
                streams[0].session->max_pass_rows);
     LoopOpts o;
-    if (int rc = resolve_loop_opts("sd_ar_batch_generate", "stream", opts, n_streams, sm.V, n_streams, sm.eos_token_id, false, &o);
+    const sd_session *ts[16];
+    int states_need[16];
+    for (int b = 0; b < n_streams; ++b) { ts[b] = streams[b].session; states_need[b] = streams[b].T - streams[b].len + 2; }
+    if (int rc = resolve_loop_opts("sd_ar_batch_generate", "stream", opts, n_streams, sm.V, n_streams, sm.eos_token_id, false, &o, ts,
+                                   n_streams);
         rc != SD_OK)
         return rc;
+    if (int rc = check_grammar_states("sd_ar_batch_generate", "stream", ts, n_streams, states_need); rc != SD_OK) return rc;
     const sd_logprob_block *const lp = o.lp;
     const RowEdits *const re = o.re;
     hipStream_t st = (hipStream_t)stream;
@@ -1506,7 +1606,7 @@ extern "C" int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, const 
         HeadOut ho = {};
         rq.raw = true;                                            // the lock-step draft step's sampler feed (see there)
         bool pen_step = false;                                    // a step with a penalised or edited stream takes no tile maxima
-        for (int j = 0; re && j < n; ++j) pen_step = pen_step || re->edited(act[j]);
+        for (int j = 0; re && j < n; ++j) pen_step = pen_step || re->edited(act[j], streams[act[j]].session);
         rq.zero_n = tiles_ok && !pen_step ? n : 0;
         for (int j = 0; j < n; ++j) {
             sd_ar_stream &s = streams[act[j]];
@@ -1524,11 +1624,13 @@ extern "C" int sd_ar_batch_generate(sd_ar_stream *streams, int n_streams, const 
         NormRequest nr = norm_request(sm, head->norm_mode, ho);
         if (pen_step) {                                           // stream act[j]'s one row, at position len - 1
             sd_logit_edit_item pi[16];
+            const sd_session *ps[16];
             for (int j = 0; j < n; ++j) {
                 const sd_ar_stream &s = streams[act[j]];
                 pi[j] = edit_item(*re, act[j], ho, j, 1, s.seq, s.len - 1, L0[act[j]]);
+                ps[j] = s.session;
             }
-            if ((rc = edit_rows(*re, pi, n, sm.V, nr.mode, stream)) != SD_OK) break;
+            if ((rc = edit_rows(*re, pi, n, sm.V, nr.mode, stream, ps)) != SD_OK) break;
             norm_from_edited(nr, *re);
         }
         nr.rows = n; nr.workspace = norm_workspace;

@@ -8,7 +8,8 @@ from .speculative_sampling import speculative_sampling
 from .autoregressive_sampling import autoregressive_sampling
 from .batch import (speculative_sampling_batch, speculative_sampling_queue, speculative_sampling_queue_shared,
                     speculative_sampling_queue_logprobs, speculative_sampling_queue_requests, speculative_sampling_queue_edits,
-                    autoregressive_sampling_batch)
+                    speculative_sampling_queue_grammar, autoregressive_sampling_batch)
+from .grammar import TokenGrammar
 from .lookup import prompt_lookup_sampling, prompt_lookup_sampling_batch
 from .multi import multi_speculative_sampling
 from .beam import beam_speculative_sampling_v2
@@ -40,4 +41,4 @@ __all__ = ["speculative_sampling", "speculative_sampling_v2", "autoregressive_sa
            "beam_speculative_sampling_v2",
            "speculative_sampling_batch", "speculative_sampling_queue", "speculative_sampling_queue_shared",
            "speculative_sampling_queue_logprobs", "speculative_sampling_queue_requests", "speculative_sampling_queue_edits",
-           "autoregressive_sampling_batch", "prompt_lookup_sampling", "prompt_lookup_sampling_batch", "KVCacheModel", "norm_logits", "sample", "max_fn", "top_k_top_p_filter"]
+           "speculative_sampling_queue_grammar", "TokenGrammar", "autoregressive_sampling_batch", "prompt_lookup_sampling", "prompt_lookup_sampling_batch", "KVCacheModel", "norm_logits", "sample", "max_fn", "top_k_top_p_filter"]

@@ -471,6 +471,13 @@ def bind_logit_edits(records, what: str, V: int, eos_token_id):
     return records
 
 
+def neutral_logit_edits(n: int):
+    """``n`` records as ``logit_edits`` returns them, all neutral: what a call with a grammar and no edits of its own builds
+    its edit block from (the masked rows need the block's slab)."""
+    return [dict(bias_ids=np.zeros(0, dtype=np.int32), bias_vals=np.zeros(0, dtype=np.float32), allowed=None,
+                 banned=np.zeros(0, dtype=np.int64), left=None, mask=None, masked=False, min_tokens=0) for _ in range(n)]
+
+
 def edits_need_target_rows(target_m) -> None:
     """Logit edits act on the logit rows where a single-GPU forward leaves them: a tensor-parallel shard is refused."""
     if getattr(target_m, "tp_group", None) is not None:

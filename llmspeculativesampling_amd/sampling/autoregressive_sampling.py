@@ -9,8 +9,9 @@ import torch
 from .._lib import lib, check, SdArLog, SdArStream
 from ..engine import as_specdec_model, _stream, check_token_ids
 from ._loop_common import (EDITS_NEED_NATIVE, LogitEditBlock, LogprobBlock, PenaltyBlock, device_rng, edits_need_target_rows,
-                           head_scratch, bind_logit_edits, logit_edits, logprobs_need_target_rows, loop_opts, make_noise, open_stream,
-                           penalties_need_target_rows, penalty_triples, raise_loop_error, sampling_block)
+                           head_scratch, bind_logit_edits, logit_edits, logprobs_need_target_rows, loop_opts, make_noise,
+                           neutral_logit_edits, open_stream, penalties_need_target_rows, penalty_triples, raise_loop_error, sampling_block)
+from .grammar import GRAMMAR_NEEDS_NATIVE, GrammarBinding, check_grammar_vocab, grammar_list, grammar_needs_target_rows
 from .kvcache_model import KVCacheModel
 
 
@@ -19,7 +20,7 @@ def autoregressive_sampling(x: torch.Tensor, model, N: int, eos_token_id: int, t
                             top_k: int = 0, top_p: float = 0, pad_token_id=None, *, rng=None, _native: bool = True,
                             logprobs: bool = False, repetition_penalty: float = 1.0, frequency_penalty: float = 0.0,
                             presence_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None, banned_token_ids=None,
-                            min_tokens=0):
+                            min_tokens=0, grammar=None):
     """reference autoregressive_sampling.py:9-61: exactly N tokens unless EOS is drawn (the EOS is kept).
     RNG contract: one ``sample`` per token.  With the device RNG the whole loop is one native call
     (sd_ar_batch_generate with one stream); ``_native=False`` keeps the interpreter loop below, which the host RNG
@@ -33,7 +34,14 @@ def autoregressive_sampling(x: torch.Tensor, model, N: int, eos_token_id: int, t
     ``logit_bias`` / ``allowed_token_ids`` / ``banned_token_ids`` / ``min_tokens`` (native loop only; neutral None / None / None
     / 0): behind the penalties a ``{token id: bias}`` mapping is added, ids outside the allowed list or inside the banned list
     become -inf, and so does ``eos_token_id`` until ``min_tokens`` tokens have been produced
-    (``sampling.utils.apply_logit_edits``)."""
+    (``sampling.utils.apply_logit_edits``).
+    ``grammar`` (native loop only; a ``sampling.grammar.TokenGrammar`` or None): behind the edits every logit row is masked by
+    the automaton state its output prefix leads to (``sampling.utils.apply_grammar``); the state advances on the device."""
+    gr = grammar_list(1, "stream", grammar)
+    if gr is not None and not (_native and device_rng(rng)):
+        raise ValueError(GRAMMAR_NEEDS_NATIVE + ", not _native=False")
+    if gr is not None:
+        grammar_needs_target_rows(model)
     edit_args = (logit_bias, allowed_token_ids, banned_token_ids, min_tokens)
     ed = logit_edits(1, "stream", None, eos_token_id, *edit_args)
     if ed is not None and not (_native and device_rng(rng)):
@@ -56,6 +64,7 @@ def autoregressive_sampling(x: torch.Tensor, model, N: int, eos_token_id: int, t
     V = m.cfg.vocab_size
     if ed is not None:
         ed = bind_logit_edits(ed, "stream", V, eos_token_id)
+    check_grammar_vocab(gr, "stream", V)
     L0 = x.shape[1]
     check_token_ids(x, V)
     noise = make_noise(rng, dev)
@@ -64,7 +73,7 @@ def autoregressive_sampling(x: torch.Tensor, model, N: int, eos_token_id: int, t
     if _native and getattr(noise, "on_device", False):
         run = ArRun(m, temperature, top_k, top_p, eos_token_id)
         run.add(kv, seq32, x[0].to(device="cpu", dtype=torch.int32).numpy(), L0 + N, noise)
-        run.generate(logprobs=logprobs, penalties=pen, edits=ed)
+        run.generate(logprobs=logprobs, penalties=pen, edits=ed, grammars=gr)
         out = torch.from_numpy(run.tokens(0)).to(torch.int64).unsqueeze(0).to(x.device)
         return (out, run.logprobs(0, x.device)) if logprobs else out
     n_out = 0
@@ -111,9 +120,10 @@ class ArRun:
         err = torch.zeros(2, dtype=torch.int32, device=self.m.device)
         self.streams.append(_ArStream(kv, seq32, host, err, noise, len(prompt), int(T)))
 
-    def generate(self, timing: bool = False, logprobs: bool = False, penalties=None, edits=None) -> None:
+    def generate(self, timing: bool = False, logprobs: bool = False, penalties=None, edits=None, grammars=None) -> None:
         """``penalties``: None, or one (repetition, frequency, presence) triple per stream (_loop_common.penalty_triples);
-        ``edits``: None, or one record per stream (_loop_common.logit_edits)."""
+        ``edits``: None, or one record per stream (_loop_common.logit_edits); ``grammars``: None, or one TokenGrammar-or-None
+        per stream (grammar.grammar_list) - ``self.grammar_states`` then holds each such stream's device state cache."""
         B = len(self.streams)
         if not 1 <= B <= 16:
             raise ValueError(f"autoregressive sampling takes 1..16 streams per call, not {B}")
@@ -138,8 +148,17 @@ class ArRun:
                 dev_block.data_ptr(), host_block.data_ptr(), log, _stream())
         self.lp = LogprobBlock(dev, [s.T + 1 for s in self.streams]) if logprobs else None
         pb = PenaltyBlock(dev, penalties, self.m.cfg.vocab_size, B) if penalties is not None else None
+        if grammars is not None and edits is None:
+            edits = neutral_logit_edits(B)                         # the masked rows need the edit block's slab
         eb = LogitEditBlock(dev, edits, self.m.cfg.vocab_size, B, pb.rows if pb is not None else None) if edits is not None else None
-        rc = lib.sd_ar_batch_generate(*args, loop_opts(None, self.lp, pb, eb))
+        bound = GrammarBinding([s.kv._session for s in self.streams], grammars, [s.T - s.L + 2 for s in self.streams], dev) \
+            if grammars is not None else None
+        self.grammar_states = bound.states if bound is not None else None
+        try:
+            rc = lib.sd_ar_batch_generate(*args, loop_opts(None, self.lp, pb, eb))
+        finally:
+            if bound is not None:
+                bound.detach()
         self.lens = []
         for it, s in zip(arr, self.streams):                      # the state the loop left, also after a failure
             s.kv._session.cache_len = it.cache_len

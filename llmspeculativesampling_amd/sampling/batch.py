@@ -23,9 +23,10 @@ from .._lib import lib, check, SdAcceptResult, SdBatchStream, SdQueuePrompt
 from ..engine import as_specdec_model, _stream, check_token_ids, same_device, batch_prefill
 from ..noise import DeviceNoise
 from ._loop_common import (LockstepLog, LogitEditBlock, LogprobBlock, LoopLog, PenaltyBlock, bind_spec_slot, edits_need_target_rows,
-                           lockstep_result, bind_logit_edits, logit_edits, logprobs_need_target_rows, loop_opts, open_spec_slot, open_stream,
-                           penalties_need_target_rows, penalty_triples, reseed_uniforms, row_sampling,
+                           lockstep_result, bind_logit_edits, logit_edits, logprobs_need_target_rows, loop_opts, neutral_logit_edits,
+                           open_spec_slot, open_stream, penalties_need_target_rows, penalty_triples, reseed_uniforms, row_sampling,
                            sampling_block, spec_scratch)
+from .grammar import GrammarBinding, TokenGrammar, check_grammar_vocab, grammar_list, grammar_needs_target_rows
 from .autoregressive_sampling import ArRun
 from .kvcache_model import KVCacheModel
 
@@ -57,7 +58,7 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
                                top_p: float = 0, random_seed: int = None, details: bool = False,
                                seeds: Optional[Sequence[int]] = None, _timing: Optional[dict] = None, *,
                                logprobs: bool = False, repetition_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0,
-                               logit_bias=None, allowed_token_ids=None, banned_token_ids=None, min_tokens=0):
+                               logit_bias=None, allowed_token_ids=None, banned_token_ids=None, min_tokens=0, grammar=None):
     """B streams at once; ``prefixes[i]`` is (1, L_i) int64.  Returns a list of (1, len_i) tensors (and a list of
     ``details`` dicts with the reference's keys when ``details``).  Device Philox RNG, stream i seeded ``seeds[i]``.
     ``temperature``, ``top_k`` and ``top_p`` each take one value for all streams or a sequence with one entry per stream
@@ -78,14 +79,21 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
     ``allowed_token_ids`` / ``banned_token_ids`` (one flat sequence of ids for all streams, or one sequence-or-None per stream)
     and ``min_tokens`` (an int, or one per stream): stream i equals ``speculative_sampling`` with its values
     (member ``edits``; ``sampling.utils.apply_logit_edits`` has the definition, ``speculative_sampling`` the
-    refusals)."""
+    refusals).
+    ``grammar``: one ``sampling.grammar.TokenGrammar`` for all streams, or a sequence with one TokenGrammar-or-None per stream;
+    stream i equals ``speculative_sampling(prefixes[i], ..., grammar=g_i, rng=DeviceNoise(seeds[i]))``.  Streams that share a
+    grammar share its device tables; each has its own state cache (``_timing["grammar_states"]``: the device arrays, None for a
+    stream without a grammar)."""
     edit_args = (logit_bias, allowed_token_ids, banned_token_ids, min_tokens)
     try:
         triples = row_sampling(len(prefixes), "stream", temperature, top_k, top_p)
         pen = penalty_triples(len(prefixes), "stream", repetition_penalty, frequency_penalty, presence_penalty)
         ed = logit_edits(len(prefixes), "stream", None, eos_token_id, *edit_args)
+        gr = grammar_list(len(prefixes), "stream", grammar)
     except TypeError:
         raise ValueError("prefixes: a sequence of (1, L) int64 prompts is required") from None
+    if gr is not None:
+        grammar_needs_target_rows(target_model)
     if pen is not None:
         penalties_need_target_rows(target_model)
     if ed is not None:
@@ -99,6 +107,7 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
     assert draft_m.cfg.vocab_size == V
     if ed is not None:
         ed = bind_logit_edits(ed, "stream", V, eos_token_id)
+    check_grammar_vocab(gr, "stream", V)
     for pf in prefixes:
         check_token_ids(pf, V)
     B = len(prefixes)
@@ -152,9 +161,19 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
             vlog.block, cu)
     lp = LogprobBlock(dev, [len(s.log.host_seq) for s in streams]) if logprobs else None
     pb = PenaltyBlock(dev, pen, V, min(max(per_pass, gamma + 1), B * (gamma + 1))) if pen is not None else None
+    if gr is not None and ed is None:
+        ed = neutral_logit_edits(B)                               # the masked rows need the edit block's slab
     eb = LogitEditBlock(dev, ed, V, min(max(per_pass, gamma + 1), B * (gamma + 1)), pb.rows if pb is not None else None) \
         if ed is not None else None
-    check(lib.sd_spec_batch_generate(*args, loop_opts(triples, lp, pb, eb)), "sd_spec_batch_generate")
+    bound = GrammarBinding([s.target._session for s in streams], gr, [s.T - s.prompt_len + gamma + 2 for s in streams], dev) \
+        if gr is not None else None
+    try:
+        check(lib.sd_spec_batch_generate(*args, loop_opts(triples, lp, pb, eb)), "sd_spec_batch_generate")
+    finally:
+        if bound is not None:
+            bound.detach()
+    if _timing is not None and bound is not None:
+        _timing["grammar_states"] = bound.states
     if vlog.block.err:
         raise RuntimeError("s")
     if _timing is not None:
@@ -324,9 +343,31 @@ def speculative_sampling_queue_edits(prefixes: Sequence[torch.Tensor], approx_mo
                   edits=(logit_bias, allowed_token_ids, banned_token_ids, min_tokens))
 
 
+@torch.no_grad()
+def speculative_sampling_queue_grammar(prefixes: Sequence[torch.Tensor], approx_model, target_model, eos_token_id, pad_token_id,
+                                       max_len, gamma: int = 4, temperature: float = 1, top_k: int = 0, top_p: float = 0,
+                                       random_seed: int = None, details: bool = False, seeds: Optional[Sequence[int]] = None,
+                                       slots: int = 8, prefill_chunk: int = 0, _timing: Optional[dict] = None,
+                                       shared_prefix: int = 0, *, logprobs: bool = False, repetition_penalty=1.0,
+                                       frequency_penalty=0.0, presence_penalty=0.0, logit_bias=None, allowed_token_ids=None,
+                                       banned_token_ids=None, min_tokens=0, grammar=None):
+    """speculative_sampling_queue_edits with ``grammar``: ONE ``sampling.grammar.TokenGrammar`` (or None) that every prompt's
+    output must follow.  The grammar sits on the slots' target sessions, each slot with a state cache of its own, and a slot
+    that changes hands starts again at the start state; prompt i equals ``speculative_sampling(prefixes[i], ..., grammar=grammar,
+    rng=DeviceNoise(seeds[i]))`` with its other values, whichever slot it decodes in.  Per-prompt grammars in the queue are out
+    of scope (``speculative_sampling_batch`` takes one per stream).  ``_timing["grammar_states"]``: the slots' device state
+    caches.  (A function of its own: the queues' parameter lists are pinned by their tests.)"""
+    if grammar is not None and not isinstance(grammar, TokenGrammar):
+        raise ValueError(f"grammar: one TokenGrammar for all prompts (or None) is required, not {grammar!r}")
+    return _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max_len, gamma, temperature, top_k, top_p,
+                  random_seed, details, seeds, slots, prefill_chunk, _timing, shared_prefix, logprobs=logprobs,
+                  penalties=(repetition_penalty, frequency_penalty, presence_penalty),
+                  edits=(logit_bias, allowed_token_ids, banned_token_ids, min_tokens), grammar=grammar)
+
+
 def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max_len, gamma, temperature, top_k, top_p,
            random_seed, details, seeds, slots, prefill_chunk, _timing, shared_prefix, logprobs=False, penalties=(1.0, 0.0, 0.0),
-           edits=(None, None, None, 0)):
+           edits=(None, None, None, 0), grammar=None):
     """The prompt queue behind the public entry points (their docstrings have the contract)."""
     budgets = _queue_arguments(prefixes, max_len, seeds, slots)
     shared = _shared_prefix_argument(prefixes, shared_prefix)
@@ -341,6 +382,8 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
     ed = logit_edits(len(prefixes), "prompt", None, eos_token_id, *edits)
     if ed is not None:
         edits_need_target_rows(target_model)
+    if grammar is not None:
+        grammar_needs_target_rows(target_model)
     if triples is not None:                                       # (a slot's KVCacheModel and the block's own triple are not read)
         temperature, top_k, top_p = triples[0]
     draft_m, target_m = as_specdec_model(approx_model), as_specdec_model(target_model)
@@ -352,6 +395,7 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
     assert draft_m.cfg.vocab_size == V
     if ed is not None:
         ed = bind_logit_edits(ed, "prompt", V, eos_token_id)
+    check_grammar_vocab([grammar], "prompt", V)
     for pf in prefixes:
         check_token_ids(pf, V)
     N = len(prefixes)
@@ -403,9 +447,19 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
     args += (*[ses.handle if ses else None for ses in donors], rows)
     lp = LogprobBlock(dev, [len(log.host_seq) for log in logs]) if logprobs else None
     pb = PenaltyBlock(dev, pen, V, min(max(per_pass, gamma + 1), S * (gamma + 1))) if pen is not None else None
+    if grammar is not None and ed is None:
+        ed = neutral_logit_edits(N)                               # the masked rows need the edit block's slab
     eb = LogitEditBlock(dev, ed, V, min(max(per_pass, gamma + 1), S * (gamma + 1)), pb.rows if pb is not None else None) \
         if ed is not None else None
-    check(lib.sd_spec_queue_generate(*args, loop_opts(triples, lp, pb, eb)), "sd_spec_queue_generate")
+    states_cap = max(L + max(m, 0) for L, m in zip(lens, budgets)) - min(lens) + gamma + 2
+    bound = GrammarBinding([h[1]._session for h in held], [grammar] * S, [states_cap] * S, dev) if grammar is not None else None
+    try:
+        check(lib.sd_spec_queue_generate(*args, loop_opts(triples, lp, pb, eb)), "sd_spec_queue_generate")
+    finally:
+        if bound is not None:
+            bound.detach()
+    if _timing is not None and bound is not None:
+        _timing["grammar_states"] = bound.states
     passes[4] += rows                                             # the donor's target rows are prompt rows too
     if vlog.block.err:
         raise RuntimeError("s")
@@ -429,7 +483,7 @@ def autoregressive_sampling_batch(xs: Sequence[torch.Tensor], model, N: int, eos
                                   top_k: int = 0, top_p: float = 0, pad_token_id=None, *,
                                   seeds: Optional[Sequence[int]] = None, _timing: Optional[dict] = None,
                                   logprobs: bool = False, repetition_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0,
-                                  logit_bias=None, allowed_token_ids=None, banned_token_ids=None, min_tokens=0):
+                                  logit_bias=None, allowed_token_ids=None, banned_token_ids=None, min_tokens=0, grammar=None):
     """``autoregressive_sampling`` for B streams at once: ``xs[i]`` is (1, L_i) int64, the result a list of (1, len_i)
     tensors.  The streams decode in lock-step and share every pass over the weights (sd_ar_batch_generate): each runs the
     algorithm of reference autoregressive_sampling.py:9-61 on its own Philox stream ``seeds[i]`` (default
@@ -440,10 +494,15 @@ def autoregressive_sampling_batch(xs: Sequence[torch.Tensor], model, N: int, eos
     ``repetition_penalty`` / ``frequency_penalty`` / ``presence_penalty`` (neutral 1 / 0 / 0): each one value for all streams or
     one per stream; stream i equals ``autoregressive_sampling(xs[i], ..., rng=DeviceNoise(seeds[i]))`` with its values
     (member ``penalties`` of sd_loop_opts).  ``logit_bias`` / ``allowed_token_ids`` / ``banned_token_ids`` / ``min_tokens``: one
-    value for all streams or one per stream, as ``speculative_sampling_batch`` takes them (member ``edits``)."""
+    value for all streams or one per stream, as ``speculative_sampling_batch`` takes them (member ``edits``).  ``grammar``: one
+    ``sampling.grammar.TokenGrammar`` for all streams or one TokenGrammar-or-None per stream, as ``speculative_sampling_batch``
+    takes it (``_timing["grammar_states"]``: the streams' device state caches)."""
     B = len(xs)
     if not 1 <= B <= 16:
         raise ValueError(f"autoregressive_sampling_batch takes 1..16 streams per call, not {B}")
+    gr = grammar_list(B, "stream", grammar)
+    if gr is not None:
+        grammar_needs_target_rows(model)
     pen = penalty_triples(B, "stream", repetition_penalty, frequency_penalty, presence_penalty)
     if pen is not None:
         penalties_need_target_rows(model)
@@ -457,6 +516,7 @@ def autoregressive_sampling_batch(xs: Sequence[torch.Tensor], model, N: int, eos
     V = m.cfg.vocab_size
     if ed is not None:
         ed = bind_logit_edits(ed, "stream", V, eos_token_id)
+    check_grammar_vocab(gr, "stream", V)
     for x in xs:
         assert x.dim() == 2 and x.shape[0] == 1 and x.shape[1] >= 1, "every stream is one (1, L) prompt"
         check_token_ids(x, V)
@@ -469,8 +529,10 @@ def autoregressive_sampling_batch(xs: Sequence[torch.Tensor], model, N: int, eos
     batch_prefill([kv._session for kv in kvs], seqs, [x.shape[1] - 1 for x in xs])
     for x, seed, kv, seq32 in zip(xs, seeds, kvs, seqs):
         run.add(kv, seq32, x[0].to(device="cpu", dtype=torch.int32).numpy(), x.shape[1] + int(N), DeviceNoise(seed))
-    run.generate(timing=_timing is not None, logprobs=logprobs, penalties=pen, edits=ed)
+    run.generate(timing=_timing is not None, logprobs=logprobs, penalties=pen, edits=ed, grammars=gr)
     if _timing is not None:
         _timing.setdefault("step", []).extend(run.steps)
+        if run.grammar_states is not None:
+            _timing["grammar_states"] = run.grammar_states
     outs = [torch.from_numpy(run.tokens(i)).to(torch.int64).unsqueeze(0).to(x.device) for i, x in enumerate(xs)]
     return (outs, [run.logprobs(i, x.device) for i, x in enumerate(xs)]) if logprobs else outs

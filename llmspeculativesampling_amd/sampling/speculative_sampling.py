@@ -18,8 +18,9 @@ from .._lib import lib, check, SdAcceptResult
 from ..engine import as_specdec_model, _stream, check_token_ids, same_device
 from ._loop_common import (EDITS_NEED_NATIVE, LogitEditBlock, LogprobBlock, LoopLog, PenaltyBlock, accept_rates_f64,
                            cut_after_new_eos, details_dict, device_rng, edits_need_target_rows, bind_logit_edits, logit_edits,
-                           logprobs_need_target_rows, loop_opts, make_noise, open_stream, penalties_need_target_rows, penalty_triples,
-                           raise_loop_error, reseed_uniforms, sampling_block, spec_scratch, spec_stream)
+                           logprobs_need_target_rows, loop_opts, make_noise, neutral_logit_edits, open_stream, penalties_need_target_rows,
+                           penalty_triples, raise_loop_error, reseed_uniforms, sampling_block, spec_scratch, spec_stream)
+from .grammar import GRAMMAR_NEEDS_NATIVE, GrammarBinding, check_grammar_vocab, grammar_list, grammar_needs_target_rows
 
 _make_noise = make_noise                              # beam.py, multi.py and tests import it from here
 
@@ -30,7 +31,7 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
                          verbose: bool = False, random_seed: int = None, details: bool = False, *, rng=None,
                          _event_logs=None, logprobs: bool = False, repetition_penalty: float = 1.0,
                          frequency_penalty: float = 0.0, presence_penalty: float = 0.0, logit_bias=None, allowed_token_ids=None,
-                         banned_token_ids=None, min_tokens=0):
+                         banned_token_ids=None, min_tokens=0, grammar=None):
     """reference speculative_sampling.py:1876-2076.
 
     ``rng`` (extension): "host" (default) draws every variate from torch's CPU generator in the
@@ -58,7 +59,19 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
     ``logprobs`` stay what the model says.  ValueError before a model is touched for a bias that is not a finite number, more
     than 1024 entries, an id that is not an integer or lies outside the vocabulary, ``min_tokens < 0``, an allowed set that the
     banned ids empty or that holds nothing but EOS while ``min_tokens > 0``, an interpreter path or a tensor-parallel target.
+
+    ``grammar`` (extension, native device-RNG loop only; a ``sampling.grammar.TokenGrammar`` or None): the output must follow
+    the token automaton.  Every draft and target logit row is masked on the device, behind the logit edits, by the state the
+    row's own output prefix leads to (``sampling.utils.apply_grammar``); the automaton advances on the device along the drafted
+    tokens, so the output is distributed as the target's own sampling under the grammar.  ``logprobs`` stay what the model
+    says.  ValueError before a model is touched for an interpreter path or a tensor-parallel target, and for a grammar built
+    for another vocabulary once the model is known.
     """
+    gr = grammar_list(1, "stream", grammar)
+    if gr is not None and (verbose or not device_rng(rng)):
+        raise ValueError(GRAMMAR_NEEDS_NATIVE + " and verbose=False")
+    if gr is not None:
+        grammar_needs_target_rows(target_model)
     edit_args = (logit_bias, allowed_token_ids, banned_token_ids, min_tokens)
     ed = logit_edits(1, "stream", None, eos_token_id, *edit_args)
     if ed is not None and (verbose or not device_rng(rng)):
@@ -86,6 +99,7 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
     assert 1 <= gamma <= 16
     if ed is not None:
         ed = bind_logit_edits(ed, "stream", V, eos_token_id)
+    check_grammar_vocab(gr, "stream", V)
 
     seq_len0 = prefix.shape[1]
     T = seq_len0 + max_len
@@ -102,7 +116,7 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
     target, seq32 = open_stream(target_m, prefix[0], cap, cap + 1, temperature, top_k, top_p, noise)
     if getattr(noise, "on_device", False) and not verbose:
         return _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T, gamma, random_seed, details,
-                                   noise, _event_logs, logprobs, pen, ed)
+                                   noise, _event_logs, logprobs, pen, ed, gr)
 
     ori_eos_cnt = host_seq.count(eos_token_id)
     if _event_logs is not None:                       # bench.py: HIP-event brackets around every forward
@@ -214,7 +228,7 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
 
 
 def _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T, gamma, random_seed, details, noise,
-                        timing_log, logprobs=False, pen=None, ed=None):
+                        timing_log, logprobs=False, pen=None, ed=None, gr=None):
     """Device-RNG mode: the loop itself runs inside libspecdec (sd_spec_generate): per iteration the gamma draft steps,
     the target forward, the accept scan and the resample are enqueued and the stream is waited on once, in native code;
     the interpreter only sees the finished sequence and the per-iteration statistics.  Same loop semantics as the
@@ -236,7 +250,10 @@ def _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T,
     scratch = spec_scratch(draft._session, target._session, target._norm_ws, target._session.max_rows)
     lp = LogprobBlock(dev, [T + gamma + 2]) if logprobs else None
     pb = PenaltyBlock(dev, pen, target._model.cfg.vocab_size, gamma + 1) if pen is not None else None
+    if gr is not None and ed is None:
+        ed = neutral_logit_edits(1)                      # the masked rows need the edit block's slab
     eb = LogitEditBlock(dev, ed, target._model.cfg.vocab_size, gamma + 1, pb.rows if pb is not None else None) if ed is not None else None
+    bound = GrammarBinding([target._session], gr, [T - seq_len0 + gamma + 2], dev) if gr is not None else None
     try:
         tick = process_time_ns()
         args = (stream, gamma, sampling, scratch, st, int(random_seed or 0), r_const.data_ptr() if r_const is not None else None,
@@ -262,6 +279,9 @@ def _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T,
     except Exception as e:
         print(e)
         raise RuntimeError("s") from e
+    finally:
+        if bound is not None:
+            bound.detach()
     draft._session.cache_len, target._session.cache_len = st.draft_len, st.target_len
     out = torch.tensor([out_tokens], dtype=torch.int64, device=prefix.device)
     tail = (lp.tensor(0, len(out_tokens) - seq_len0, prefix.device),) if lp is not None else ()

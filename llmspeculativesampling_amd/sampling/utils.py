@@ -257,6 +257,24 @@ def apply_logit_edits(logits_row: torch.Tensor, out_index: int, eos_token_id, bi
     return y.to(dtype)
 
 
+def apply_grammar(logits_row: torch.Tensor, grammar, state: int) -> torch.Tensor:
+    """The grammar mask as the native loops apply it (sd_grammar_rows; include/specdec.h has the text), in pure torch on any
+    device.  ``logits_row`` is one (V,) row as the sampler reads it after the penalties and the logit edits -
+    ``apply_logit_edits``' result; this function composes after it - and ``state`` the automaton state the row's output prefix
+    leads to (``grammar.state_after(tokens[P:pos + 1])`` for the row at position pos of a stream whose prompt has P tokens).
+    With ``state >= 0`` every id whose bit is clear in ``grammar.masks[state]`` becomes -inf, whatever the logit holds; a dead
+    row (``state < 0``) is returned as it is, and so is a row inside the prompt, for which the caller passes ``state=-1``.
+    An allowed id keeps its bits.  Returns a new row of the same dtype."""
+    assert logits_row.dim() == 1 and logits_row.shape[0] == grammar.vocab_size
+    y = logits_row.clone()
+    if int(state) < 0 or int(state) >= grammar.n_states:
+        return y
+    words = torch.as_tensor(np.asarray(grammar.masks[int(state)]).astype(np.int64) & 0xFFFFFFFF, device=y.device)
+    t = torch.arange(y.shape[0], device=y.device)
+    y[((words[t >> 5] >> (t & 31)) & 1) == 0] = float("-inf")
+    return y
+
+
 def lookup_propose(tokens, gamma: int, ngram_max: int = 3, ngram_min: int = 1):
     """The prompt-lookup proposer (sd_lookup_propose; include/specdec.h has the definition) in plain Python: for the tokens
     ``seq[0 .. L)`` a continuation index c, 1 <= c <= L - 1, has match length k(c) = the largest k <= min(ngram_max, c) with
