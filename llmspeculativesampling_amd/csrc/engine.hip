@@ -975,15 +975,16 @@ static int tp_reduce(sd_session *s, GemmOut *go, const float **src, int M, int N
     sd_tp *t = s->tp;
     if (!t) return SD_OK;
     const int total = M * N;
+    // one slab (the row-parallel GEMM kept its whole k-range per workgroup): its [M][N] rows ARE this rank's partial - no fold
+    const float *mine = *src;
+    if (go->S != 1) {
+        ProfScope ps(s, PC_OTHER, st);                                  // (a scope of its own: the profile counts fold launches)
+        hipLaunchKernelGGL(tp_fold_kernel, dim3((total + 255) / 256), dim3(256), 0, st, *src, go->S, go->stride_s, total, s->tp_in);
+        SD_LAUNCH_CHECK();
+        mine = s->tp_in;
+    }
     {
         ProfScope ps(s, PC_OTHER, st);
-        // one slab (the row-parallel GEMM kept its whole k-range per workgroup): its [M][N] rows ARE this rank's partial - no fold
-        const float *mine = *src;
-        if (go->S != 1) {
-            hipLaunchKernelGGL(tp_fold_kernel, dim3((total + 255) / 256), dim3(256), 0, st, *src, go->S, go->stride_s, total, s->tp_in);
-            SD_LAUNCH_CHECK();
-            mine = s->tp_in;
-        }
         if (t->comm) {
             if (g_rccl.allreduce(mine, s->tp_out, (size_t)total, /* ncclFloat32 */ 7, /* ncclSum */ 0, t->comm, st) != 0) {
                 sd_set_error("ncclAllReduce failed");
