@@ -4,13 +4,19 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from contextlib import contextmanager
+from dataclasses import dataclass
+from time import process_time_ns
 
 import numpy as np
 import torch
 
-from .._lib import (LOGPROB_SLICE, LOGPROB_STREAMS, SD_EDIT_MAX_BIAS, SdHeadScratch, SdLockstepLog, SdLogitEdit, SdLogitEditBlock,
-                    SdLogprobBlock, SdLoopOpts, SdPenalty, SdPenaltyBlock, SdRowSampling, SdSampling, SdSeqState, SdSpecScratch, SdSpecStream)
+from .._lib import (LOGPROB_SLICE, LOGPROB_STREAMS, SD_EDIT_MAX_BIAS, SdAcceptResult, SdBatchStream, SdHeadScratch, SdLockstepLog,
+                    SdLogitEdit, SdLogitEditBlock, SdLogprobBlock, SdLoopOpts, SdPenalty, SdPenaltyBlock, SdRowSampling, SdSampling,
+                    SdSeqState, SdSpecScratch, SdSpecStream, lib)
+from ..engine import batch_prefill
 from ..noise import DeviceNoise, HostTorchNoise
+from .grammar import (GRAMMAR_NEEDS_NATIVE, GrammarBinding, check_grammar_vocab, grammar_list, grammar_needs_target_rows)
 from .kvcache_model import KVCacheModel
 
 
@@ -514,6 +520,212 @@ class LogitEditBlock:
         self._params = (SdLogitEdit * len(records))(*[SdLogitEdit(i, v, len(r["bias_ids"]), m, r["min_tokens"])
                                                       for r, i, v, m in zip(records, ids, vals, masks)])
         self.block = SdLogitEditBlock(self.rows.data_ptr(), self.rows.stride(0), self.rows.shape[0], self._params)
+
+
+PENALTIES_NEED_NATIVE = 'repetition / frequency / presence penalties need the native loop: rng="device" (or a device noise object)'
+LOGPROBS_NEED_NATIVE = 'logprobs=True needs the native loop: rng="device" (or a device noise object)'
+
+
+def slab_rows(gamma: int = 0, streams: int = 1, per_pass: int = 0, *, ar_streams: int = None) -> int:
+    """The rows of the slab a call's penalty and edit blocks write a pass's logit rows to: those of the loop's largest pass.  A
+    speculative pass holds whole streams of gamma + 1 rows, as many as fit into ``per_pass`` rows, at least one and at most all
+    ``streams`` (one stream: gamma + 1 whatever ``per_pass``); an autoregressive step holds one row of each of ``ar_streams``."""
+    if ar_streams is not None:
+        return int(ar_streams)
+    return min(max(per_pass, gamma + 1), streams * (gamma + 1))
+
+
+class AttachedOptions:
+    """What ``RequestOptions.attach`` holds during one native call: the blocks ``lp`` / ``pb`` / ``eb`` (each may be None),
+    ``members`` - loop_opts' four arguments; ``loop_opts`` is their SdLoopOpts, None when nothing is set - and
+    ``grammar_states``, the sessions' device state caches (None without a grammar)."""
+
+    def __init__(self, triples, lp, pb, eb, bound):
+        self.lp, self.pb, self.eb = lp, pb, eb
+        self.members = (triples, lp, pb, eb)
+        self.grammar_states = bound.states if bound is not None else None
+
+    @property
+    def loop_opts(self):
+        return loop_opts(*self.members)
+
+    def logprob_tensor(self, i: int, n: int, device) -> torch.Tensor:
+        return self.lp.tensor(i, n, device)
+
+
+class RequestOptions:
+    """The per-request options of one native loop call with ``n`` requests called ``what`` ("stream", "prompt"), from the
+    keywords to the blocks of its sd_loop_opts, in three stages every wrapper goes through in this order: ``parse`` (no model,
+    no GPU), the refusals ``require_native`` / ``require_target_rows`` / ``bind``, and ``attach`` around the native call.
+    The fields keep the leaf parsers' results, None for a neutral option: ``sampling`` (row_sampling's triples), ``logprobs``,
+    ``penalties`` (penalty_triples), ``edits`` (logit_edits' records), ``grammar`` (grammar_list)."""
+
+    def __init__(self, n: int, what: str, eos_token_id, sampling=None, logprobs=False, penalties=None, edits=None, grammar=None):
+        self.n, self.what, self.eos_token_id = n, what, eos_token_id
+        self.sampling, self.logprobs, self.penalties, self.edits, self.grammar = sampling, logprobs, penalties, edits, grammar
+
+    @classmethod
+    def parse(cls, n: int, what: str, eos_token_id, *, sampling=None, logprobs=False, penalties=(1.0, 0.0, 0.0),
+              edits=(None, None, None, 0), grammar=None) -> "RequestOptions":
+        """``sampling``: the (temperature, top_k, top_p) of an entry that takes per-request sequences, else None; ``penalties``:
+        (repetition, frequency, presence); ``edits``: (logit_bias, allowed_token_ids, banned_token_ids, min_tokens).  Parsed -
+        and refused with the leaf parsers' ValueErrors - in the order sampling, penalties, edits, grammar."""
+        return cls(n, what, eos_token_id, row_sampling(n, what, *sampling) if sampling is not None else None, logprobs,
+                   penalty_triples(n, what, *penalties), logit_edits(n, what, None, eos_token_id, *edits),
+                   grammar_list(n, what, grammar))
+
+    def require_native(self, ok: bool, suffix: str) -> None:
+        """The single-stream entries: an option that is set needs the native loop (``ok``); ``suffix`` names what else selects it."""
+        for given, text in ((self.grammar is not None, GRAMMAR_NEEDS_NATIVE), (self.edits is not None, EDITS_NEED_NATIVE),
+                            (self.penalties is not None, PENALTIES_NEED_NATIVE), (self.logprobs, LOGPROBS_NEED_NATIVE)):
+            if given and not ok:
+                raise ValueError(text + suffix)
+
+    def require_target_rows(self, target_model) -> None:
+        """Every option reads or edits the logit rows where a single-GPU forward leaves them: with one set, a tensor-parallel
+        target is refused (``target_model`` as the caller passed it: nothing is converted or touched)."""
+        for given, refuse in ((self.grammar is not None, grammar_needs_target_rows), (self.edits is not None, edits_need_target_rows),
+                              (self.penalties is not None, penalties_need_target_rows), (self.logprobs, logprobs_need_target_rows)):
+            if given:
+                refuse(target_model)
+
+    def bind(self, V: int) -> None:
+        """Once the vocabulary is known: the ids' upper bound and the masks of the edits, the grammars' vocabulary."""
+        if self.edits is not None:
+            self.edits = bind_logit_edits(self.edits, self.what, V, self.eos_token_id)
+        check_grammar_vocab(self.grammar, self.what, V)
+
+    @contextmanager
+    def attach(self, device, V: int, rows: int, logprob_caps, grammar_sessions, grammar_state_caps):
+        """Builds the blocks of the call - ``rows``: slab_rows(...), which the penalty and the edit block share;
+        ``logprob_caps``: the token capacity per request - and sets the grammars on ``grammar_sessions`` (the streams' target
+        sessions; in the queue the slots', fewer than requests, which all have the one grammar) with state caches of
+        ``grammar_state_caps`` ints.  Yields the AttachedOptions; the grammars come off again on exit, however the body ends."""
+        lp = LogprobBlock(device, logprob_caps) if self.logprobs else None
+        pb = PenaltyBlock(device, self.penalties, V, rows) if self.penalties is not None else None
+        edits = self.edits
+        if self.grammar is not None and edits is None:
+            edits = neutral_logit_edits(self.n)                   # the masked rows need the edit block's slab
+        eb = LogitEditBlock(device, edits, V, rows, pb.rows if pb is not None else None) if edits is not None else None
+        bound = GrammarBinding(grammar_sessions, self.grammar[:len(grammar_sessions)], grammar_state_caps, device) \
+            if self.grammar is not None else None
+        try:
+            yield AttachedOptions(self.sampling, lp, pb, eb, bound)
+        finally:
+            if bound is not None:
+                bound.detach()
+
+
+def stream_seeds(seeds, n: int) -> list:
+    """The Philox seeds of ``n`` streams: ``seeds``, or ``torch.initial_seed() + i`` for stream i."""
+    return list(seeds) if seeds is not None else [int(torch.initial_seed()) + i for i in range(n)]
+
+
+@dataclass
+class LockstepStream:
+    draft: KVCacheModel          # None without a draft model
+    target: KVCacheModel
+    seq32: torch.Tensor
+    err: torch.Tensor
+    q_hist: torch.Tensor         # without a draft model: the arena of the one-hot q rows; else None (the draft's _probs)
+    noise: DeviceNoise
+    log: LoopLog
+    prompt_len: int
+    T: int
+    ori_eos: int
+    device: object               # the prompt's: where the output goes
+
+
+class LockstepStreams:
+    """The stream table of one lock-step speculative call (sd_spec_batch_generate, sd_lookup_batch_generate): a stream per
+    prompt with its LoopLog, ``noises[i]`` and what the caller's ``open_slot(i, prompt_row, cap)`` opens for it - ``(draft,
+    target, seq32, err, q_hist)`` with arenas for ``cap`` positions and 3 * gamma + 1 error words; prompt lookup has no draft
+    model: ``draft`` None and an fp32 ``q_hist`` arena of the stream's own - everything but the last prompt token prefilled, and
+    the SdBatchStream array ``arr`` bound to it.  ``info_bytes``: bytes per stream behind the B result blocks (stream i's
+    block is at ``i * sizeof(SdAcceptResult)`` either way)."""
+
+    def __init__(self, prefixes, open_slot, device, eos_token_id, max_len, gamma: int, noises, info_bytes: int = 0):
+        B, res_sz = len(prefixes), C.sizeof(SdAcceptResult)
+        self.res_dev = torch.zeros(B * (res_sz + info_bytes), dtype=torch.uint8, device=device)
+        self.res_host = torch.zeros(B * (res_sz + info_bytes), dtype=torch.uint8).pin_memory()
+        self.max_iters = max(1, int(max_len)) + 1
+        self.streams = []
+        for i, (pf, noise) in enumerate(zip(prefixes, noises)):
+            assert pf.shape[0] == 1, "input batch size must be 1"
+            L = pf.shape[1]
+            T = L + max_len
+            cap = T + gamma + 2
+            host = [int(t) for t in pf[0].tolist()]
+            self.streams.append(LockstepStream(*open_slot(i, pf[0], cap), noise, LoopLog(host, cap, self.max_iters, gamma, q_fill=1.0),
+                                               L, T, host.count(eos_token_id), pf.device))
+        drafted = self.streams[0].draft is not None
+        # prefill everything but the last prompt token, the B prompts packed into passes of up to 256 rows (engine.batch_prefill:
+        # one pass over the weights serves several streams); the decode loop then starts with 1 new draft row and gamma+1 new
+        # target rows per stream like every later iteration
+        for side in ("draft", "target") if drafted else ("target",):
+            batch_prefill([getattr(s, side)._session for s in self.streams], [s.seq32 for s in self.streams],
+                          [s.prompt_len - 1 for s in self.streams])
+        self.arr = (SdBatchStream * B)()
+        for i, (it, s) in enumerate(zip(self.arr, self.streams)):
+            bind_spec_slot(it, s.draft, s.target, s.seq32, s.err, self.res_dev.data_ptr() + i * res_sz,
+                           self.res_host.data_ptr() + i * res_sz, s.q_hist)
+            it.host_seq = s.log.host_seq.ctypes.data
+            it.len, it.T, it.ori_eos_cnt = s.prompt_len, s.T, s.ori_eos
+            it.draft_len, it.target_len = s.prompt_len - 1 if drafted else 0, s.prompt_len - 1
+            it.seed, it.draw = s.noise.seed, s.noise.draw
+            it.acc_len_out, it.p_at_out, it.q_at_out = s.log.ptrs()[:3]
+        self.per_pass = self.streams[0].target._session.max_pass_rows
+        self.norm_ws = torch.empty(lib.sd_norm_workspace_bytes(self.per_pass), dtype=torch.uint8, device=device)
+        self.vlog = LockstepLog(self.max_iters * 2)
+
+    def results(self, eos_token_id) -> tuple:
+        """After the loop: RuntimeError("s") for a logged error; else every stream's Philox position and cache lengths go back
+        to its noise object and sessions, and the outputs and ``details`` dicts are returned (lockstep_result)."""
+        if self.vlog.block.err:
+            raise RuntimeError("s")
+        outs, ds = [], []
+        for it, s in zip(self.arr, self.streams):
+            s.noise.seed, s.noise.draw = it.seed, it.draw
+            if s.draft is not None:
+                s.draft._session.cache_len = it.draft_len
+            s.target._session.cache_len = it.target_len
+            out, det = lockstep_result(s.log, it.len, it.calls, eos_token_id, s.ori_eos, s.device)
+            outs.append(out)
+            ds.append(det)
+        return outs, ds
+
+
+def single_stream_native_call(call, host_seq: list, T: int, gamma: int, eos_token_id, noise, device, timed: bool, info_bytes: int = 0):
+    """One call of a single-stream native loop (sd_spec_generate, sd_lookup_generate): allocates the result pair (``info_bytes``
+    more behind the block) and the 3 * gamma + 1 error words, builds the LoopLog and its SdSeqState, and runs the caller's
+    ``call(res_dev, res_host, err_words, st)``, which makes the native call in its own module.  Returns ``(out_tokens, st, log,
+    acc_len, acc_rate, (approx_time, target_time, other_time))``: the tokens cut after the first new EOS, the statistics, the
+    two phases' device time (the reference's are host process_time deltas around generate() (:1937-1962); here the host only
+    enqueues, so HIP events are reported) and the host CPU time.  The noise position is written back; any exception leaves as
+    RuntimeError("s") (:2044-2046), the cause attached and printed."""
+    seq_len0 = len(host_seq)
+    ori_eos_cnt = host_seq.count(eos_token_id)
+    nb = C.sizeof(SdAcceptResult) + info_bytes
+    res_dev = torch.zeros(nb, dtype=torch.uint8, device=device)
+    res_host = torch.zeros(nb, dtype=torch.uint8).pin_memory()
+    err_words = torch.zeros(3 * gamma + 1, dtype=torch.int32, device=device)
+    max_iters = max(1, T - seq_len0)
+    log = LoopLog(host_seq, T + gamma + 2, max_iters, gamma, q_fill=1.0, timed=timed)
+    st = log.seq_state(seq_len0, T, ori_eos_cnt, (0, 0), noise, max_iters)
+    try:
+        tick = process_time_ns()
+        call(res_dev, res_host, err_words, st)
+        other_time = process_time_ns() - tick            # host CPU time of the loop (enqueue + waits + bookkeeping)
+        noise.seed, noise.draw = st.seed, st.draw
+        raise_loop_error(st.err)
+        acc_len = log.acc_len(st.n_iters)
+        acc_rate = accept_rates_f64(*log.ratios(st.n_iters))
+        times = (*log.phase_ns(st.n_iters), other_time)
+        out_tokens = cut_after_new_eos(log.tokens(st.len), eos_token_id, ori_eos_cnt)
+    except Exception as e:
+        print(e)
+        raise RuntimeError("s") from e
+    return out_tokens, st, log, acc_len, acc_rate, times
 
 
 def raise_loop_error(code: int) -> None:

@@ -8,10 +8,8 @@ import torch
 
 from .._lib import lib, check, SdArLog, SdArStream
 from ..engine import as_specdec_model, _stream, check_token_ids
-from ._loop_common import (EDITS_NEED_NATIVE, LogitEditBlock, LogprobBlock, PenaltyBlock, device_rng, edits_need_target_rows,
-                           head_scratch, bind_logit_edits, logit_edits, logprobs_need_target_rows, loop_opts, make_noise,
-                           neutral_logit_edits, open_stream, penalties_need_target_rows, penalty_triples, raise_loop_error, sampling_block)
-from .grammar import GRAMMAR_NEEDS_NATIVE, GrammarBinding, check_grammar_vocab, grammar_list, grammar_needs_target_rows
+from ._loop_common import (RequestOptions, device_rng, head_scratch, loop_opts, make_noise, open_stream, raise_loop_error,
+                           sampling_block, slab_rows)
 from .kvcache_model import KVCacheModel
 
 
@@ -37,34 +35,16 @@ def autoregressive_sampling(x: torch.Tensor, model, N: int, eos_token_id: int, t
     (``sampling.utils.apply_logit_edits``).
     ``grammar`` (native loop only; a ``sampling.grammar.TokenGrammar`` or None): behind the edits every logit row is masked by
     the automaton state its output prefix leads to (``sampling.utils.apply_grammar``); the state advances on the device."""
-    gr = grammar_list(1, "stream", grammar)
-    if gr is not None and not (_native and device_rng(rng)):
-        raise ValueError(GRAMMAR_NEEDS_NATIVE + ", not _native=False")
-    if gr is not None:
-        grammar_needs_target_rows(model)
-    edit_args = (logit_bias, allowed_token_ids, banned_token_ids, min_tokens)
-    ed = logit_edits(1, "stream", None, eos_token_id, *edit_args)
-    if ed is not None and not (_native and device_rng(rng)):
-        raise ValueError(EDITS_NEED_NATIVE + ", not _native=False")
-    if ed is not None:
-        edits_need_target_rows(model)
-    pen = penalty_triples(1, "stream", repetition_penalty, frequency_penalty, presence_penalty)
-    if pen is not None and not (_native and device_rng(rng)):
-        raise ValueError('repetition / frequency / presence penalties need the native loop: rng="device" (or a device noise '
-                         'object), not _native=False')
-    if pen is not None:
-        penalties_need_target_rows(model)
-    if logprobs and not (_native and device_rng(rng)):
-        raise ValueError('logprobs=True needs the native loop: rng="device" (or a device noise object), not _native=False')
+    opts = RequestOptions.parse(1, "stream", eos_token_id, logprobs=logprobs,
+                                penalties=(repetition_penalty, frequency_penalty, presence_penalty),
+                                edits=(logit_bias, allowed_token_ids, banned_token_ids, min_tokens), grammar=grammar)
+    opts.require_native(_native and device_rng(rng), ", not _native=False")
+    opts.require_target_rows(model)
     assert x.shape[0] == 1
     m = as_specdec_model(model)
-    if logprobs:
-        logprobs_need_target_rows(m)
     dev = m.device
     V = m.cfg.vocab_size
-    if ed is not None:
-        ed = bind_logit_edits(ed, "stream", V, eos_token_id)
-    check_grammar_vocab(gr, "stream", V)
+    opts.bind(V)
     L0 = x.shape[1]
     check_token_ids(x, V)
     noise = make_noise(rng, dev)
@@ -73,7 +53,7 @@ def autoregressive_sampling(x: torch.Tensor, model, N: int, eos_token_id: int, t
     if _native and getattr(noise, "on_device", False):
         run = ArRun(m, temperature, top_k, top_p, eos_token_id)
         run.add(kv, seq32, x[0].to(device="cpu", dtype=torch.int32).numpy(), L0 + N, noise)
-        run.generate(logprobs=logprobs, penalties=pen, edits=ed, grammars=gr)
+        run.generate(logprobs=logprobs, penalties=opts.penalties, edits=opts.edits, grammars=opts.grammar)
         out = torch.from_numpy(run.tokens(0)).to(torch.int64).unsqueeze(0).to(x.device)
         return (out, run.logprobs(0, x.device)) if logprobs else out
     n_out = 0
@@ -146,19 +126,11 @@ class ArRun:
         args = (arr, B, sampling_block(*self.args, self.m.cfg.vocab_size, kv0._probs.stride(0), self.eos),
                 head_scratch(kv0._session), norm_ws.data_ptr() if norm_ws is not None else None,
                 dev_block.data_ptr(), host_block.data_ptr(), log, _stream())
-        self.lp = LogprobBlock(dev, [s.T + 1 for s in self.streams]) if logprobs else None
-        pb = PenaltyBlock(dev, penalties, self.m.cfg.vocab_size, B) if penalties is not None else None
-        if grammars is not None and edits is None:
-            edits = neutral_logit_edits(B)                         # the masked rows need the edit block's slab
-        eb = LogitEditBlock(dev, edits, self.m.cfg.vocab_size, B, pb.rows if pb is not None else None) if edits is not None else None
-        bound = GrammarBinding([s.kv._session for s in self.streams], grammars, [s.T - s.L + 2 for s in self.streams], dev) \
-            if grammars is not None else None
-        self.grammar_states = bound.states if bound is not None else None
-        try:
-            rc = lib.sd_ar_batch_generate(*args, loop_opts(None, self.lp, pb, eb))
-        finally:
-            if bound is not None:
-                bound.detach()
+        opts = RequestOptions(B, "stream", self.eos, None, logprobs, penalties, edits, grammars)
+        with opts.attach(dev, self.m.cfg.vocab_size, slab_rows(ar_streams=B), [s.T + 1 for s in self.streams],
+                         [s.kv._session for s in self.streams], [s.T - s.L + 2 for s in self.streams]) as blocks:
+            self.blocks, self.grammar_states = blocks, blocks.grammar_states
+            rc = lib.sd_ar_batch_generate(*args, loop_opts(*blocks.members))
         self.lens = []
         for it, s in zip(arr, self.streams):                      # the state the loop left, also after a failure
             s.kv._session.cache_len = it.cache_len
@@ -173,4 +145,4 @@ class ArRun:
 
     def logprobs(self, i: int, device) -> torch.Tensor:
         """generate(logprobs=True): the (1, new tokens) float32 scores of stream i."""
-        return self.lp.tensor(i, self.lens[i] - self.streams[i].L, device)
+        return self.blocks.logprob_tensor(i, self.lens[i] - self.streams[i].L, device)

@@ -13,8 +13,7 @@ up to 16 slots, and a stream that ends hands its slot to the next waiting prompt
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import Optional, Sequence
 
 import numpy as np
 import torch
@@ -22,26 +21,10 @@ import torch
 from .._lib import lib, check, SdAcceptResult, SdBatchStream, SdQueuePrompt
 from ..engine import as_specdec_model, _stream, check_token_ids, same_device, batch_prefill
 from ..noise import DeviceNoise
-from ._loop_common import (LockstepLog, LogitEditBlock, LogprobBlock, LoopLog, PenaltyBlock, bind_spec_slot, edits_need_target_rows,
-                           lockstep_result, bind_logit_edits, logit_edits, logprobs_need_target_rows, loop_opts, neutral_logit_edits,
-                           open_spec_slot, open_stream, penalties_need_target_rows, penalty_triples, reseed_uniforms, row_sampling,
-                           sampling_block, spec_scratch)
-from .grammar import GrammarBinding, TokenGrammar, check_grammar_vocab, grammar_list, grammar_needs_target_rows
+from ._loop_common import (LockstepLog, LockstepStreams, LoopLog, RequestOptions, bind_spec_slot, lockstep_result, open_spec_slot,
+                           open_stream, reseed_uniforms, sampling_block, slab_rows, spec_scratch, stream_seeds)
+from .grammar import TokenGrammar
 from .autoregressive_sampling import ArRun
-from .kvcache_model import KVCacheModel
-
-
-@dataclass
-class _Stream:
-    draft: KVCacheModel
-    target: KVCacheModel
-    seq32: torch.Tensor
-    err: torch.Tensor
-    noise: DeviceNoise
-    log: LoopLog
-    prompt_len: int
-    T: int
-    ori_eos: int
 
 
 class _Ms:                                                        # (bench.py reads e0.elapsed_time(e1))
@@ -84,108 +67,47 @@ def speculative_sampling_batch(prefixes: Sequence[torch.Tensor], approx_model, t
     stream i equals ``speculative_sampling(prefixes[i], ..., grammar=g_i, rng=DeviceNoise(seeds[i]))``.  Streams that share a
     grammar share its device tables; each has its own state cache (``_timing["grammar_states"]``: the device arrays, None for a
     stream without a grammar)."""
-    edit_args = (logit_bias, allowed_token_ids, banned_token_ids, min_tokens)
     try:
-        triples = row_sampling(len(prefixes), "stream", temperature, top_k, top_p)
-        pen = penalty_triples(len(prefixes), "stream", repetition_penalty, frequency_penalty, presence_penalty)
-        ed = logit_edits(len(prefixes), "stream", None, eos_token_id, *edit_args)
-        gr = grammar_list(len(prefixes), "stream", grammar)
+        opts = RequestOptions.parse(len(prefixes), "stream", eos_token_id, sampling=(temperature, top_k, top_p), logprobs=logprobs,
+                                    penalties=(repetition_penalty, frequency_penalty, presence_penalty),
+                                    edits=(logit_bias, allowed_token_ids, banned_token_ids, min_tokens), grammar=grammar)
     except TypeError:
         raise ValueError("prefixes: a sequence of (1, L) int64 prompts is required") from None
-    if gr is not None:
-        grammar_needs_target_rows(target_model)
-    if pen is not None:
-        penalties_need_target_rows(target_model)
-    if ed is not None:
-        edits_need_target_rows(target_model)
+    opts.require_target_rows(target_model)
     draft_m, target_m = as_specdec_model(approx_model), as_specdec_model(target_model)
     same_device(draft_m, target_m)
-    if logprobs:
-        logprobs_need_target_rows(target_m)
     dev = target_m.device
     V = target_m.cfg.vocab_size
     assert draft_m.cfg.vocab_size == V
-    if ed is not None:
-        ed = bind_logit_edits(ed, "stream", V, eos_token_id)
-    check_grammar_vocab(gr, "stream", V)
+    opts.bind(V)
     for pf in prefixes:
         check_token_ids(pf, V)
     B = len(prefixes)
     assert 1 <= B <= 16 and 1 <= gamma <= 16
-    seeds = list(seeds) if seeds is not None else [int(torch.initial_seed()) + i for i in range(B)]
-    res_sz = C.sizeof(SdAcceptResult)
-    res_dev = torch.zeros((B, res_sz), dtype=torch.uint8, device=dev)
-    res_host = torch.zeros((B, res_sz), dtype=torch.uint8).pin_memory()
+    triples = opts.sampling or [(temperature, top_k, top_p)] * B
     r_const = reseed_uniforms(random_seed, gamma, dev)
-    max_iters = max(1, int(max_len)) + 1
-
-    streams: List[_Stream] = []
-    for i, pf in enumerate(prefixes):
-        assert pf.shape[0] == 1, "input batch size must be 1"
-        L = pf.shape[1]
-        T = L + max_len
-        cap = T + gamma + 2
-        draft, target, seq32, err = open_spec_slot(draft_m, target_m, pf[0], cap, gamma,
-                                                   *(triples[i] if triples else (temperature, top_k, top_p)))
-        host = [int(t) for t in pf[0].tolist()]
-        streams.append(_Stream(draft, target, seq32, err, DeviceNoise(seeds[i]),
-                               LoopLog(host, cap, max_iters, gamma, q_fill=1.0), L, T, host.count(eos_token_id)))
-
-    # prefill everything but the last prompt token, the B prompts packed into passes of up to 256 rows (engine.batch_prefill:
-    # one pass over the weights serves several streams); the decode loop then starts with 1 new draft row and gamma+1 new
-    # target rows per stream like every later iteration
-    for side in ("draft", "target"):
-        batch_prefill([getattr(s, side)._session for s in streams], [s.seq32 for s in streams],
-                      [s.prompt_len - 1 for s in streams])
+    table = LockstepStreams(prefixes, lambda i, row, cap: (*open_spec_slot(draft_m, target_m, row, cap, gamma, *triples[i]), None),
+                            dev, eos_token_id, max_len, gamma, [DeviceNoise(seed) for seed in stream_seeds(seeds, B)])
+    streams = table.streams
 
     # the lock-step loop itself runs inside libspecdec (sd_spec_batch_generate): per iteration gamma batched draft steps,
     # the verify passes, the batched accept + residual sample, one copy of the result blocks and one wait - the
     # interpreter sees the finished token buffers and the per-iteration statistics
-    per_pass = streams[0].target._session.max_pass_rows
-    norm_ws = torch.empty(lib.sd_norm_workspace_bytes(per_pass), dtype=torch.uint8, device=dev)
-    cu = _stream()
-    arr = (SdBatchStream * B)()
-    for i, (it, s) in enumerate(zip(arr, streams)):
-        bind_spec_slot(it, s.draft, s.target, s.seq32, s.err, res_dev.data_ptr() + i * res_sz, res_host.data_ptr() + i * res_sz)
-        it.host_seq = s.log.host_seq.ctypes.data
-        it.len, it.T, it.ori_eos_cnt = s.prompt_len, s.T, s.ori_eos
-        it.draft_len = it.target_len = s.prompt_len - 1
-        it.seed, it.draw = s.noise.seed, s.noise.draw
-        it.acc_len_out, it.p_at_out, it.q_at_out = s.log.ptrs()[:3]
-    vlog = LockstepLog(max_iters * 2)
     d0, t0 = streams[0].draft._session, streams[0].target._session
     # (with per-stream parameters the block's own triple is not read: stream 0's stands in)
-    args = (arr, B, gamma, sampling_block(*(triples[0] if triples else (temperature, top_k, top_p)), V,
-                                          streams[0].draft._probs.stride(0), eos_token_id),
-            int(random_seed or 0), r_const.data_ptr() if r_const is not None else None, spec_scratch(d0, t0, norm_ws, per_pass),
-            vlog.block, cu)
-    lp = LogprobBlock(dev, [len(s.log.host_seq) for s in streams]) if logprobs else None
-    pb = PenaltyBlock(dev, pen, V, min(max(per_pass, gamma + 1), B * (gamma + 1))) if pen is not None else None
-    if gr is not None and ed is None:
-        ed = neutral_logit_edits(B)                               # the masked rows need the edit block's slab
-    eb = LogitEditBlock(dev, ed, V, min(max(per_pass, gamma + 1), B * (gamma + 1)), pb.rows if pb is not None else None) \
-        if ed is not None else None
-    bound = GrammarBinding([s.target._session for s in streams], gr, [s.T - s.prompt_len + gamma + 2 for s in streams], dev) \
-        if gr is not None else None
-    try:
-        check(lib.sd_spec_batch_generate(*args, loop_opts(triples, lp, pb, eb)), "sd_spec_batch_generate")
-    finally:
-        if bound is not None:
-            bound.detach()
-    if _timing is not None and bound is not None:
-        _timing["grammar_states"] = bound.states
-    if vlog.block.err:
-        raise RuntimeError("s")
+    args = (table.arr, B, gamma, sampling_block(*triples[0], V, streams[0].draft._probs.stride(0), eos_token_id),
+            int(random_seed or 0), r_const.data_ptr() if r_const is not None else None,
+            spec_scratch(d0, t0, table.norm_ws, table.per_pass), table.vlog.block, _stream())
+    with opts.attach(dev, V, slab_rows(gamma, B, table.per_pass), [len(s.log.host_seq) for s in streams],
+                     [s.target._session for s in streams], [s.T - s.prompt_len + gamma + 2 for s in streams]) as blocks:
+        check(lib.sd_spec_batch_generate(*args, blocks.loop_opts), "sd_spec_batch_generate")
+    if _timing is not None and blocks.grammar_states is not None:
+        _timing["grammar_states"] = blocks.grammar_states
+    outs, ds = table.results(eos_token_id)
     if _timing is not None:
-        _timing.setdefault("verify", []).extend((_Ms(ms), None, n, ctx) for ms, n, ctx in vlog.entries())
-    outs, ds = [], []
-    for it, s, pf in zip(arr, streams, prefixes):
-        s.noise.seed, s.noise.draw = it.seed, it.draw
-        s.draft._session.cache_len, s.target._session.cache_len = it.draft_len, it.target_len
-        out, det = lockstep_result(s.log, it.len, it.calls, eos_token_id, s.ori_eos, pf.device)
-        outs.append(out)
-        ds.append(det)
-    tail = ([lp.tensor(i, o.shape[1] - s.prompt_len, o.device) for i, (o, s) in enumerate(zip(outs, streams))],) if lp is not None else ()
+        _timing.setdefault("verify", []).extend((_Ms(ms), None, n, ctx) for ms, n, ctx in table.vlog.entries())
+    tail = ([blocks.logprob_tensor(i, o.shape[1] - s.prompt_len, o.device) for i, (o, s) in enumerate(zip(outs, streams))],) \
+        if logprobs else ()
     if details:
         return (outs, ds, *tail)
     return (outs, *tail) if tail else outs
@@ -375,32 +297,23 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
         raise ValueError(f"prefill_chunk: a row count >= 0 is required, not {prefill_chunk!r}")
     if not 1 <= gamma <= 16:
         raise ValueError(f"gamma: 1..16, not {gamma}")
-    triples = row_sampling(len(prefixes), "prompt", temperature, top_k, top_p)
-    pen = penalty_triples(len(prefixes), "prompt", *penalties)
-    if pen is not None:
-        penalties_need_target_rows(target_model)
-    ed = logit_edits(len(prefixes), "prompt", None, eos_token_id, *edits)
-    if ed is not None:
-        edits_need_target_rows(target_model)
-    if grammar is not None:
-        grammar_needs_target_rows(target_model)
+    N = len(prefixes)
+    opts = RequestOptions.parse(N, "prompt", eos_token_id, sampling=(temperature, top_k, top_p), logprobs=logprobs, penalties=penalties,
+                                edits=edits, grammar=grammar)
+    opts.require_target_rows(target_model)
+    triples = opts.sampling
     if triples is not None:                                       # (a slot's KVCacheModel and the block's own triple are not read)
         temperature, top_k, top_p = triples[0]
     draft_m, target_m = as_specdec_model(approx_model), as_specdec_model(target_model)
     same_device(draft_m, target_m)
-    if logprobs:
-        logprobs_need_target_rows(target_m)
     dev = target_m.device
     V = target_m.cfg.vocab_size
     assert draft_m.cfg.vocab_size == V
-    if ed is not None:
-        ed = bind_logit_edits(ed, "prompt", V, eos_token_id)
-    check_grammar_vocab([grammar], "prompt", V)
+    opts.bind(V)
     for pf in prefixes:
         check_token_ids(pf, V)
-    N = len(prefixes)
     S = min(slots, N)
-    seeds = list(seeds) if seeds is not None else [int(torch.initial_seed()) + i for i in range(N)]
+    seeds = stream_seeds(seeds, N)
     lens = [pf.shape[1] for pf in prefixes]
     cap = max(L + max(m, 0) for L, m in zip(lens, budgets)) + gamma + 2   # every slot holds the largest prompt of the call
     res_sz = C.sizeof(SdAcceptResult)
@@ -445,21 +358,12 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
             batch_prefill([ses], [head], [rows])
             donor_passes[side] = -(-rows // ses.max_rows)
     args += (*[ses.handle if ses else None for ses in donors], rows)
-    lp = LogprobBlock(dev, [len(log.host_seq) for log in logs]) if logprobs else None
-    pb = PenaltyBlock(dev, pen, V, min(max(per_pass, gamma + 1), S * (gamma + 1))) if pen is not None else None
-    if grammar is not None and ed is None:
-        ed = neutral_logit_edits(N)                               # the masked rows need the edit block's slab
-    eb = LogitEditBlock(dev, ed, V, min(max(per_pass, gamma + 1), S * (gamma + 1)), pb.rows if pb is not None else None) \
-        if ed is not None else None
     states_cap = max(L + max(m, 0) for L, m in zip(lens, budgets)) - min(lens) + gamma + 2
-    bound = GrammarBinding([h[1]._session for h in held], [grammar] * S, [states_cap] * S, dev) if grammar is not None else None
-    try:
-        check(lib.sd_spec_queue_generate(*args, loop_opts(triples, lp, pb, eb)), "sd_spec_queue_generate")
-    finally:
-        if bound is not None:
-            bound.detach()
-    if _timing is not None and bound is not None:
-        _timing["grammar_states"] = bound.states
+    with opts.attach(dev, V, slab_rows(gamma, S, per_pass), [len(log.host_seq) for log in logs], [h[1]._session for h in held],
+                     [states_cap] * S) as blocks:
+        check(lib.sd_spec_queue_generate(*args, blocks.loop_opts), "sd_spec_queue_generate")
+    if _timing is not None and blocks.grammar_states is not None:
+        _timing["grammar_states"] = blocks.grammar_states
     passes[4] += rows                                             # the donor's target rows are prompt rows too
     if vlog.block.err:
         raise RuntimeError("s")
@@ -472,8 +376,8 @@ def _queue(prefixes, approx_model, target_model, eos_token_id, pad_token_id, max
     res = [lockstep_result(log, it.len, it.calls, eos_token_id, it.ori_eos_cnt, pf.device)
            for it, log, pf in zip(arr, logs, prefixes)]
     outs, ds = [r[0] for r in res], [r[1] for r in res]
-    if lp is not None:
-        lps = [lp.tensor(i, o.shape[1] - L, o.device) for i, (o, L) in enumerate(zip(outs, lens))]
+    if logprobs:
+        lps = [blocks.logprob_tensor(i, o.shape[1] - L, o.device) for i, (o, L) in enumerate(zip(outs, lens))]
         return (outs, ds, lps) if details else (outs, lps)
     return (outs, ds) if details else outs
 
@@ -500,27 +404,17 @@ def autoregressive_sampling_batch(xs: Sequence[torch.Tensor], model, N: int, eos
     B = len(xs)
     if not 1 <= B <= 16:
         raise ValueError(f"autoregressive_sampling_batch takes 1..16 streams per call, not {B}")
-    gr = grammar_list(B, "stream", grammar)
-    if gr is not None:
-        grammar_needs_target_rows(model)
-    pen = penalty_triples(B, "stream", repetition_penalty, frequency_penalty, presence_penalty)
-    if pen is not None:
-        penalties_need_target_rows(model)
-    edit_args = (logit_bias, allowed_token_ids, banned_token_ids, min_tokens)
-    ed = logit_edits(B, "stream", None, eos_token_id, *edit_args)
-    if ed is not None:
-        edits_need_target_rows(model)
+    opts = RequestOptions.parse(B, "stream", eos_token_id, logprobs=logprobs,
+                                penalties=(repetition_penalty, frequency_penalty, presence_penalty),
+                                edits=(logit_bias, allowed_token_ids, banned_token_ids, min_tokens), grammar=grammar)
+    opts.require_target_rows(model)
     m = as_specdec_model(model)
-    if logprobs:
-        logprobs_need_target_rows(m)
     V = m.cfg.vocab_size
-    if ed is not None:
-        ed = bind_logit_edits(ed, "stream", V, eos_token_id)
-    check_grammar_vocab(gr, "stream", V)
+    opts.bind(V)
     for x in xs:
         assert x.dim() == 2 and x.shape[0] == 1 and x.shape[1] >= 1, "every stream is one (1, L) prompt"
         check_token_ids(x, V)
-    seeds = list(seeds) if seeds is not None else [int(torch.initial_seed()) + i for i in range(B)]
+    seeds = stream_seeds(seeds, B)
     run = ArRun(m, temperature, top_k, top_p, eos_token_id)
     caps = [x.shape[1] + int(N) + 1 for x in xs]
     kvs, seqs = map(list, zip(*[open_stream(m, x[0], cap, cap, temperature, top_k, top_p) for x, cap in zip(xs, caps)]))
@@ -529,7 +423,7 @@ def autoregressive_sampling_batch(xs: Sequence[torch.Tensor], model, N: int, eos
     batch_prefill([kv._session for kv in kvs], seqs, [x.shape[1] - 1 for x in xs])
     for x, seed, kv, seq32 in zip(xs, seeds, kvs, seqs):
         run.add(kv, seq32, x[0].to(device="cpu", dtype=torch.int32).numpy(), x.shape[1] + int(N), DeviceNoise(seed))
-    run.generate(timing=_timing is not None, logprobs=logprobs, penalties=pen, edits=ed, grammars=gr)
+    run.generate(timing=_timing is not None, logprobs=logprobs, penalties=opts.penalties, edits=opts.edits, grammars=opts.grammar)
     if _timing is not None:
         _timing.setdefault("step", []).extend(run.steps)
         if run.grammar_states is not None:

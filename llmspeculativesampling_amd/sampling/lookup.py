@@ -10,17 +10,16 @@ takes.  Device Philox only; the loops run inside libspecdec (sd_lookup_generate,
 from __future__ import annotations
 
 import ctypes as C
-from time import process_time_ns
 from typing import Optional, Sequence
 
 import numpy as np
 import torch
 
-from .._lib import SD_LOOKUP_MAX_NGRAM, SdAcceptResult, SdBatchStream, check, lib
-from ..engine import _stream, as_specdec_model, batch_prefill, check_token_ids
+from .._lib import SD_LOOKUP_MAX_NGRAM, check, lib
+from ..engine import _stream, as_specdec_model, check_token_ids
 from ..noise import DeviceNoise
-from ._loop_common import (LockstepLog, LoopLog, accept_rates_f64, bind_spec_slot, cut_after_new_eos, details_dict, device_rng,
-                           lockstep_result, make_noise, open_stream, raise_loop_error, sampling_block, spec_scratch, spec_stream)
+from ._loop_common import (LockstepStreams, details_dict, device_rng, make_noise, open_stream, sampling_block,
+                           single_stream_native_call, spec_scratch, spec_stream, stream_seeds)
 
 INFO_BYTES = 8                                                    # the proposer's two ints behind a stream's result block
 
@@ -79,33 +78,17 @@ def prompt_lookup_sampling(prefix: torch.Tensor, target_model, eos_token_id, pad
     target, seq32 = open_stream(target_m, prefix[0], cap, cap + 1, temperature, top_k, top_p, noise)
     ld = target._probs.stride(0)
     q_hist = torch.empty((cap, ld), dtype=torch.float32, device=dev)
-    ori_eos_cnt = host_seq.count(eos_token_id)
-    res_sz = C.sizeof(SdAcceptResult)
-    res_dev = torch.zeros(res_sz + INFO_BYTES, dtype=torch.uint8, device=dev)
-    res_host = torch.zeros(res_sz + INFO_BYTES, dtype=torch.uint8).pin_memory()
-    err_words = torch.zeros(3 * gamma + 1, dtype=torch.int32, device=dev)
-    max_iters = max(1, T - seq_len0)
-    log = LoopLog(host_seq, cap, max_iters, gamma, q_fill=1.0, timed=details)
-    match_len = np.zeros(max_iters, dtype=np.int32)
-    st = log.seq_state(seq_len0, T, ori_eos_cnt, (0, 0), noise, max_iters)
-    stream = spec_stream(None, target, seq32, err_words, res_dev.data_ptr(), res_host.data_ptr(), q_hist)
+    match_len = np.zeros(max(1, T - seq_len0), dtype=np.int32)
     sampling = sampling_block(target._temperature, target._top_k, target._top_p, V, ld, eos_token_id)
     scratch = spec_scratch(target._session, target._session, target._norm_ws, target._session.max_rows)
-    try:
-        tick = process_time_ns()
+
+    def call(res_dev, res_host, err_words, st):
+        stream = spec_stream(None, target, seq32, err_words, res_dev.data_ptr(), res_host.data_ptr(), q_hist)
         check(lib.sd_lookup_generate(stream, gamma, ngram_max, ngram_min, sampling, scratch, st, match_len.ctypes.data, _stream()),
               "sd_lookup_generate")
-        other_time = process_time_ns() - tick
-        noise.seed, noise.draw = st.seed, st.draw
-        raise_loop_error(st.err)
-        calls = st.n_iters
-        acc_len = log.acc_len(calls)
-        acc_rate = accept_rates_f64(*log.ratios(calls))
-        approx_time, target_time = log.phase_ns(calls)
-        out_tokens = cut_after_new_eos(log.tokens(st.len), eos_token_id, ori_eos_cnt)
-    except Exception as e:
-        print(e)
-        raise RuntimeError("s") from e
+    out_tokens, st, _, acc_len, acc_rate, (approx_time, target_time, other_time) = \
+        single_stream_native_call(call, host_seq, T, gamma, eos_token_id, noise, dev, details, INFO_BYTES)
+    calls = st.n_iters
     target._session.cache_len = st.target_len
     out = torch.tensor([out_tokens], dtype=torch.int64, device=prefix.device)
     if details:
@@ -140,49 +123,23 @@ def prompt_lookup_sampling_batch(prefixes: Sequence[torch.Tensor], target_model,
     for pf in prefixes:
         assert pf.shape[0] == 1, "input batch size must be 1"
         check_token_ids(pf, V)
-    seeds = list(seeds) if seeds is not None else [int(torch.initial_seed()) + i for i in range(B)]
-    res_sz = C.sizeof(SdAcceptResult)
-    res_dev = torch.zeros(B * (res_sz + INFO_BYTES), dtype=torch.uint8, device=dev)     # B blocks, then B pairs of info ints
-    res_host = torch.zeros(B * (res_sz + INFO_BYTES), dtype=torch.uint8).pin_memory()
-    max_iters = max(1, int(max_len)) + 1
-    streams = []
-    for i, pf in enumerate(prefixes):
-        L = pf.shape[1]
-        T = L + max_len
-        cap = T + gamma + 2
-        target, seq32 = open_stream(target_m, pf[0], cap, cap + 1, temperature, top_k, top_p)
-        host = [int(t) for t in pf[0].tolist()]
-        streams.append(dict(target=target, seq32=seq32, err=torch.zeros(3 * gamma + 1, dtype=torch.int32, device=dev),
-                            q_hist=torch.empty((cap, target._probs.stride(0)), dtype=torch.float32, device=dev),
-                            noise=DeviceNoise(seeds[i]), log=LoopLog(host, cap, max_iters, gamma, q_fill=1.0), L=L, T=T,
-                            ori_eos=host.count(eos_token_id), match_len=np.zeros(max_iters, dtype=np.int32)))
-    batch_prefill([s["target"]._session for s in streams], [s["seq32"] for s in streams], [s["L"] - 1 for s in streams])
-    t0 = streams[0]["target"]
-    per_pass = t0._session.max_pass_rows
-    norm_ws = torch.empty(lib.sd_norm_workspace_bytes(per_pass), dtype=torch.uint8, device=dev)
-    arr = (SdBatchStream * B)()
-    for i, (it, s) in enumerate(zip(arr, streams)):
-        bind_spec_slot(it, None, s["target"], s["seq32"], s["err"], res_dev.data_ptr() + i * res_sz, res_host.data_ptr() + i * res_sz,
-                       s["q_hist"])
-        it.host_seq = s["log"].host_seq.ctypes.data
-        it.len, it.T, it.ori_eos_cnt = s["L"], s["T"], s["ori_eos"]
-        it.draft_len, it.target_len = 0, s["L"] - 1
-        it.seed, it.draw = s["noise"].seed, s["noise"].draw
-        it.acc_len_out, it.p_at_out, it.q_at_out = s["log"].ptrs()[:3]
-    vlog = LockstepLog(max_iters * 2)
-    ml = (C.c_void_p * B)(*[s["match_len"].ctypes.data for s in streams])
-    check(lib.sd_lookup_batch_generate(arr, B, gamma, ngram_max, ngram_min,
+    def open_slot(i, row, cap):
+        """no draft session: the stream's own error words and the arena of its one-hot q rows"""
+        target, seq32 = open_stream(target_m, row, cap, cap + 1, temperature, top_k, top_p)
+        return (None, target, seq32, torch.zeros(3 * gamma + 1, dtype=torch.int32, device=dev),
+                torch.empty((cap, target._probs.stride(0)), dtype=torch.float32, device=dev))
+    # the B result blocks, then the B pairs of info ints
+    table = LockstepStreams(prefixes, open_slot, dev, eos_token_id, max_len, gamma,
+                            [DeviceNoise(seed) for seed in stream_seeds(seeds, B)], INFO_BYTES)
+    t0 = table.streams[0].target
+    match_len = [np.zeros(table.max_iters, dtype=np.int32) for _ in range(B)]
+    ml = (C.c_void_p * B)(*[m.ctypes.data for m in match_len])
+    check(lib.sd_lookup_batch_generate(table.arr, B, gamma, ngram_max, ngram_min,
                                        sampling_block(temperature, top_k, top_p, V, t0._probs.stride(0), eos_token_id),
-                                       spec_scratch(t0._session, t0._session, norm_ws, per_pass), vlog.block, ml, _stream()),
+                                       spec_scratch(t0._session, t0._session, table.norm_ws, table.per_pass), table.vlog.block, ml,
+                                       _stream()),
           "sd_lookup_batch_generate")
-    if vlog.block.err:
-        raise RuntimeError("s")
-    outs, ds = [], []
-    for it, s, pf in zip(arr, streams, prefixes):
-        s["noise"].seed, s["noise"].draw = it.seed, it.draw
-        s["target"]._session.cache_len = it.target_len
-        out, det = lockstep_result(s["log"], it.len, it.calls, eos_token_id, s["ori_eos"], pf.device)
-        det["match_len"] = s["match_len"][:it.calls].tolist()
-        outs.append(out)
-        ds.append(det)
+    outs, ds = table.results(eos_token_id)
+    for it, det, m in zip(table.arr, ds, match_len):
+        det["match_len"] = m[:it.calls].tolist()
     return (outs, ds) if details else outs

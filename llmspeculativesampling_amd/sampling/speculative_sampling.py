@@ -16,11 +16,8 @@ import torch
 
 from .._lib import lib, check, SdAcceptResult
 from ..engine import as_specdec_model, _stream, check_token_ids, same_device
-from ._loop_common import (EDITS_NEED_NATIVE, LogitEditBlock, LogprobBlock, LoopLog, PenaltyBlock, accept_rates_f64,
-                           cut_after_new_eos, details_dict, device_rng, edits_need_target_rows, bind_logit_edits, logit_edits,
-                           logprobs_need_target_rows, loop_opts, make_noise, neutral_logit_edits, open_stream, penalties_need_target_rows,
-                           penalty_triples, raise_loop_error, reseed_uniforms, sampling_block, spec_scratch, spec_stream)
-from .grammar import GRAMMAR_NEEDS_NATIVE, GrammarBinding, check_grammar_vocab, grammar_list, grammar_needs_target_rows
+from ._loop_common import (RequestOptions, cut_after_new_eos, details_dict, device_rng, loop_opts, make_noise, open_stream,
+                           reseed_uniforms, sampling_block, single_stream_native_call, slab_rows, spec_scratch, spec_stream)
 
 _make_noise = make_noise                              # beam.py, multi.py and tests import it from here
 
@@ -67,29 +64,13 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
     says.  ValueError before a model is touched for an interpreter path or a tensor-parallel target, and for a grammar built
     for another vocabulary once the model is known.
     """
-    gr = grammar_list(1, "stream", grammar)
-    if gr is not None and (verbose or not device_rng(rng)):
-        raise ValueError(GRAMMAR_NEEDS_NATIVE + " and verbose=False")
-    if gr is not None:
-        grammar_needs_target_rows(target_model)
-    edit_args = (logit_bias, allowed_token_ids, banned_token_ids, min_tokens)
-    ed = logit_edits(1, "stream", None, eos_token_id, *edit_args)
-    if ed is not None and (verbose or not device_rng(rng)):
-        raise ValueError(EDITS_NEED_NATIVE + " and verbose=False")
-    if ed is not None:
-        edits_need_target_rows(target_model)
-    pen = penalty_triples(1, "stream", repetition_penalty, frequency_penalty, presence_penalty)
-    if pen is not None and (verbose or not device_rng(rng)):
-        raise ValueError('repetition / frequency / presence penalties need the native loop: rng="device" (or a device noise '
-                         'object) and verbose=False')
-    if pen is not None:
-        penalties_need_target_rows(target_model)
-    if logprobs and (verbose or not device_rng(rng)):
-        raise ValueError('logprobs=True needs the native loop: rng="device" (or a device noise object) and verbose=False')
+    opts = RequestOptions.parse(1, "stream", eos_token_id, logprobs=logprobs,
+                                penalties=(repetition_penalty, frequency_penalty, presence_penalty),
+                                edits=(logit_bias, allowed_token_ids, banned_token_ids, min_tokens), grammar=grammar)
+    opts.require_native(device_rng(rng) and not verbose, " and verbose=False")
+    opts.require_target_rows(target_model)
     assert prefix.shape[0] == 1, "input batch size must be 1"
     draft_m, target_m = as_specdec_model(approx_model), as_specdec_model(target_model)
-    if logprobs:
-        logprobs_need_target_rows(target_m)
     if draft_m.cfg.is_encoder_decoder or target_m.cfg.is_encoder_decoder:
         raise NotImplementedError("encoder-decoder models are out of scope")
     same_device(draft_m, target_m)
@@ -97,9 +78,7 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
     V = target_m.cfg.vocab_size
     assert draft_m.cfg.vocab_size == V, "draft and target must share a vocabulary"
     assert 1 <= gamma <= 16
-    if ed is not None:
-        ed = bind_logit_edits(ed, "stream", V, eos_token_id)
-    check_grammar_vocab(gr, "stream", V)
+    opts.bind(V)
 
     seq_len0 = prefix.shape[1]
     T = seq_len0 + max_len
@@ -116,7 +95,7 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
     target, seq32 = open_stream(target_m, prefix[0], cap, cap + 1, temperature, top_k, top_p, noise)
     if getattr(noise, "on_device", False) and not verbose:
         return _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T, gamma, random_seed, details,
-                                   noise, _event_logs, logprobs, pen, ed, gr)
+                                   noise, _event_logs, opts)
 
     ori_eos_cnt = host_seq.count(eos_token_id)
     if _event_logs is not None:                       # bench.py: HIP-event brackets around every forward
@@ -228,63 +207,37 @@ def speculative_sampling(prefix: torch.Tensor, approx_model, target_model, eos_t
 
 
 def _native_device_loop(prefix, draft, target, seq32, host_seq, eos_token_id, T, gamma, random_seed, details, noise,
-                        timing_log, logprobs=False, pen=None, ed=None, gr=None):
+                        timing_log, opts):
     """Device-RNG mode: the loop itself runs inside libspecdec (sd_spec_generate): per iteration the gamma draft steps,
     the target forward, the accept scan and the resample are enqueued and the stream is waited on once, in native code;
     the interpreter only sees the finished sequence and the per-iteration statistics.  Same loop semantics as the
     Python-orchestrated path above (reference speculative_sampling.py:1934-2046)."""
     dev = target._model.device
+    V = target._model.cfg.vocab_size
     seq_len0 = len(host_seq)
-    ori_eos_cnt = host_seq.count(eos_token_id)
-    res_dev = torch.zeros(C.sizeof(SdAcceptResult), dtype=torch.uint8, device=dev)
-    res_host = torch.zeros(C.sizeof(SdAcceptResult), dtype=torch.uint8).pin_memory()
-    err_words = torch.zeros(3 * gamma + 1, dtype=torch.int32, device=dev)
-    timed = timing_log is not None or details          # HIP-event brackets around the draft and the verify phase
     r_const = reseed_uniforms(random_seed, gamma, dev)
-    max_iters = max(1, T - seq_len0)
-    log = LoopLog(host_seq, T + gamma + 2, max_iters, gamma, q_fill=1.0, timed=timed)
-    st = log.seq_state(seq_len0, T, ori_eos_cnt, (0, 0), noise, max_iters)
-    stream = spec_stream(draft, target, seq32, err_words, res_dev.data_ptr(), res_host.data_ptr())
-    sampling = sampling_block(target._temperature, target._top_k, target._top_p, target._model.cfg.vocab_size,
-                              draft._probs.stride(0), eos_token_id)
+    sampling = sampling_block(target._temperature, target._top_k, target._top_p, V, draft._probs.stride(0), eos_token_id)
     scratch = spec_scratch(draft._session, target._session, target._norm_ws, target._session.max_rows)
-    lp = LogprobBlock(dev, [T + gamma + 2]) if logprobs else None
-    pb = PenaltyBlock(dev, pen, target._model.cfg.vocab_size, gamma + 1) if pen is not None else None
-    if gr is not None and ed is None:
-        ed = neutral_logit_edits(1)                      # the masked rows need the edit block's slab
-    eb = LogitEditBlock(dev, ed, target._model.cfg.vocab_size, gamma + 1, pb.rows if pb is not None else None) if ed is not None else None
-    bound = GrammarBinding([target._session], gr, [T - seq_len0 + gamma + 2], dev) if gr is not None else None
-    try:
-        tick = process_time_ns()
-        args = (stream, gamma, sampling, scratch, st, int(random_seed or 0), r_const.data_ptr() if r_const is not None else None,
-                _stream())
-        check(lib.sd_spec_generate(*args, loop_opts(None, lp, pb, eb)), "sd_spec_generate")
-        other_time = process_time_ns() - tick            # host CPU time of the loop (enqueue + waits + bookkeeping)
-        noise.seed, noise.draw = st.seed, st.draw
-        raise_loop_error(st.err)
-        calls = st.n_iters
-        acc_len = log.acc_len(calls)
-        acc_rate = accept_rates_f64(*log.ratios(calls))
-        # the reference's approx_time / target_time are host process_time deltas around generate() (:1937-1962);
-        # here the host only enqueues, so the device time of the two phases (HIP events) is what is reported
-        approx_time, target_time = log.phase_ns(calls)
-        if timing_log is not None:
-            Lc, tl = seq_len0, 0
-            for i in range(calls):
-                timing_log["draft_ms"].append(float(log.draft_ms[i]))
-                timing_log["target"].append((float(log.target_ms[i]), Lc + gamma - tl, Lc + gamma))
-                tl = Lc + acc_len[i]                             # n + 1 with n = L + l - 1
-                Lc += acc_len[i] + 1
-        out_tokens = cut_after_new_eos(log.tokens(st.len), eos_token_id, ori_eos_cnt)
-    except Exception as e:
-        print(e)
-        raise RuntimeError("s") from e
-    finally:
-        if bound is not None:
-            bound.detach()
+    with opts.attach(dev, V, slab_rows(gamma), [T + gamma + 2], [target._session], [T - seq_len0 + gamma + 2]) as blocks:
+        def call(res_dev, res_host, err_words, st):
+            stream = spec_stream(draft, target, seq32, err_words, res_dev.data_ptr(), res_host.data_ptr())
+            check(lib.sd_spec_generate(stream, gamma, sampling, scratch, st, int(random_seed or 0),
+                                       r_const.data_ptr() if r_const is not None else None, _stream(), loop_opts(*blocks.members)),
+                  "sd_spec_generate")
+        timed = timing_log is not None or details          # HIP-event brackets around the draft and the verify phase
+        out_tokens, st, log, acc_len, acc_rate, (approx_time, target_time, other_time) = \
+            single_stream_native_call(call, host_seq, T, gamma, eos_token_id, noise, dev, timed)
+    calls = st.n_iters
+    if timing_log is not None:
+        Lc, tl = seq_len0, 0
+        for i in range(calls):
+            timing_log["draft_ms"].append(float(log.draft_ms[i]))
+            timing_log["target"].append((float(log.target_ms[i]), Lc + gamma - tl, Lc + gamma))
+            tl = Lc + acc_len[i]                             # n + 1 with n = L + l - 1
+            Lc += acc_len[i] + 1
     draft._session.cache_len, target._session.cache_len = st.draft_len, st.target_len
     out = torch.tensor([out_tokens], dtype=torch.int64, device=prefix.device)
-    tail = (lp.tensor(0, len(out_tokens) - seq_len0, prefix.device),) if lp is not None else ()
+    tail = (blocks.logprob_tensor(0, len(out_tokens) - seq_len0, prefix.device),) if opts.logprobs else ()
     if details:
         # the verify phase is one fused launch chain (forward + norm_probs, no cache preparation): all of it is model time
         return (out, details_dict(approx_time, target_time, other_time, acc_len, np.mean(acc_rate), calls, calls,
