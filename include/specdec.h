@@ -425,9 +425,11 @@ int sd_gemm_bf16_need(const void *w_packed, const void *x, int M, int N, int K, 
  * scratch: sd_session_scratch_bytes() bytes, caller-allocated. */
 typedef struct sd_session sd_session;
 size_t sd_session_kv_bytes(const sd_model *m, int max_seq);
+/* Sized by the planner's SD_* tunables of the environment at the call: call it under the settings sd_session_create will see. */
 size_t sd_session_scratch_bytes(const sd_model *m, int max_rows);
 /* Floats of the scratch that hold the GEMMs' k-slabs (host only): no route of a pass of <= max_rows rows may leave more. */
 size_t sd_session_part_floats(const sd_model *m, int max_rows);
+/* Reads the planner's SD_* tunables once: the session plans every pass with them for life, whatever the environment says later. */
 int sd_session_create(sd_model *m, int max_seq, int max_rows, void *kv_arena, void *scratch,
                       sd_session **out);
 int sd_session_destroy(sd_session *s);

@@ -45,8 +45,15 @@ struct sd_model {
 
 enum { PC_GEMM = 0, PC_ATTN, PC_NORM, PC_QKV, PC_ACT, PC_EMBED, PC_LOGITS, PC_OTHER };
 
+// the planner's environment tunables (read_tunables below has the variable and the meaning of each)
+struct Tunables {
+    int gemm_ntw, gemm_units, small_path, fuse_embed_qkv, attn_split_keys, attn_keys_per_split, ao_stamps, fuse_attn_o;
+    int norm_on_load, prefill_attn, prefill_attn_block, mm_slabs_min, mm_mtw, mm_s, gemm_rows, rows_max;
+};
+
 struct sd_session {
     sd_model *m;
+    Tunables tun;    // the environment at sd_session_create, for life: what sized the scratch also routes every pass
     int max_seq, max_rows;
     int max_pass_rows;  // rows of a call whose rows are all logit rows (sd_model_max_pass_rows, <= max_rows)
     char *kv;        // [L][2][Hkv][max_seq][D]
@@ -171,55 +178,55 @@ extern "C" int sd_model_set_w12(sd_model *m, int which, int layer, const void *c
 // ---- split-K policy.  A workgroup (4 waves) owns one n-tile x one k-slab and folds its waves in LDS, so
 // SB slabs reach HBM.  SB is chosen so that about `target` workgroups exist (>= 4 per CU), with at least
 // 8 k-steps (8 KiB of weights) per workgroup.
-// Environment tunables, sampled when a session (or a spec handle) is created and by the public one-off GEMM entries - not
-// per launch: a draft step is ~40 getenv() scans otherwise, on the host thread that has to keep the GPU fed.
+// Environment tunables.  A session reads them once, when it is created, and keeps that block for life (s->tun); the
+// session-less entries (row limits, scratch sizes, sd_gemm_route, sd_gemm_bf16) read them at the call.  Never per launch:
+// a draft step is ~40 scans of the environment otherwise, on the host thread that has to keep the GPU fed.
 #define SD_STREAM_MAX_ROWS 64                        // rows the streaming kernel's m-tile variants cover
 #define SD_ROWS_MAX 144                              // rows the balanced one-workgroup-per-CU kernel covers (9 m-tiles: a 128-token prompt + gamma rows)
-struct EnvTun {
-    int gemm_ntw = 4, gemm_units = -1, small_path = 1, fuse_embed_qkv = 1;
-    int attn_split_keys = 384, attn_keys_per_split = 256;
-    int mm_mtw = 0, mm_s = 0, prefill_attn = 1, prefill_attn_block = 0, mm_slabs_min = 24;
-    int gemm_rows = 1, cus = 0, fuse_attn_o = 1, ao_stamps = 0, norm_on_load = 2, rows_max = SD_ROWS_MAX;
-};
-static EnvTun g_env;
-static void refresh_env() {
+static Tunables read_tunables() {
     auto geti = [](const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; };
-    g_env.gemm_ntw = geti("SD_GEMM_NTW", 4);
-    g_env.gemm_units = geti("SD_GEMM_UNITS", -1);
+    Tunables t;
+    t.gemm_ntw = geti("SD_GEMM_NTW", 4);
+    t.gemm_units = geti("SD_GEMM_UNITS", -1);
     // 1 (default since round 4): a small model's <= 4-row step runs the layers' two norm launches as prologues of QKV / gate-up
     // (llama-68m 94.9 -> 92.3 us, opt-125m 426-440 -> 417 us per draft step); 2: every seam a prologue incl. the head (slower);
     // 0: the per-op chain.  Rounds 2-4 measured the prologue route 75 % slower: that was a 254-VGPR compile of gemm_small
-    g_env.small_path = geti("SD_SMALL_PATH", 1);
-    g_env.fuse_embed_qkv = geti("SD_FUSE_EMBED_QKV", 1);
-    g_env.attn_split_keys = geti("SD_ATTN_SPLIT_KEYS", 384);          // keys per workgroup above which a group's keys are split
-    g_env.attn_keys_per_split = std::max(16, geti("SD_ATTN_KEYS_PER_SPLIT", 256));
-    g_env.ao_stamps = geti("SD_AO_STAMPS", 0);
-    g_env.fuse_attn_o = geti("SD_FUSE_ATTN_O", 1);    // 0: attention and the O projection as two launches (A/B runs, bit-compare tests)
-    g_env.norm_on_load = geti("SD_NORM_ON_LOAD", 2);  // 0: residual+norm launches stay; 1: attention -> MLP seam only; 2: both seams (A/B runs, compare tests)
-    g_env.prefill_attn = geti("SD_PREFILL_ATTN", 1);  // 0: prefill passes keep attn_kernel's 8-row groups (A/B runs, compare tests)
-    g_env.prefill_attn_block = std::max(0, geti("SD_PREFILL_ATTN_BLOCK", 0));   // K > 0: every matrix-core prefill pass takes attn_prefill_blocked_kernel with blocks of K keys (rounded up to 64; tests, sweeps); 0: only past the single tile's LDS limit
-    g_env.mm_slabs_min = geti("SD_MM_SLABS_MIN", 24); // rows from which the k-slab GEMMs (O / down) of a pass take gemm_bf16_mm instead of the balanced kernel
-    g_env.mm_mtw = geti("SD_MM_MTW", 0);              // (sweeps) m-tiles per wave of gemm_bf16_mm: 2 = 128-row blocks, 4 = 256-row blocks; 0 = by row count
-    g_env.mm_s = geti("SD_MM_S", 0);                  // (sweeps) k-slabs of gemm_bf16_mm; 0 = planned
-
-    g_env.gemm_rows = geti("SD_GEMM_ROWS", 1);        // 0: 17..64-row GEMMs stay on the streaming kernel (A/B runs, bit-compare tests)
-    g_env.rows_max = std::min(SD_ROWS_MAX, std::max(SD_STREAM_MAX_ROWS, geti("SD_GEMM_ROWS_MAX", SD_ROWS_MAX)));   // 65..this many rows take the balanced kernel, more gemm_bf16_mm
-    if (!g_env.cus) {
+    t.small_path = geti("SD_SMALL_PATH", 1);
+    t.fuse_embed_qkv = geti("SD_FUSE_EMBED_QKV", 1);
+    t.attn_split_keys = geti("SD_ATTN_SPLIT_KEYS", 384);          // keys per workgroup above which a group's keys are split
+    t.attn_keys_per_split = std::max(16, geti("SD_ATTN_KEYS_PER_SPLIT", 256));
+    t.ao_stamps = geti("SD_AO_STAMPS", 0);
+    t.fuse_attn_o = geti("SD_FUSE_ATTN_O", 1);    // 0: attention and the O projection as two launches (A/B runs, bit-compare tests)
+    t.norm_on_load = geti("SD_NORM_ON_LOAD", 2);  // 0: residual+norm launches stay; 1: attention -> MLP seam only; 2: both seams (A/B runs, compare tests)
+    t.prefill_attn = geti("SD_PREFILL_ATTN", 1);  // 0: prefill passes keep attn_kernel's 8-row groups (A/B runs, compare tests)
+    t.prefill_attn_block = std::max(0, geti("SD_PREFILL_ATTN_BLOCK", 0));   // K > 0: every matrix-core prefill pass takes attn_prefill_blocked_kernel with blocks of K keys (rounded up to 64; tests, sweeps); 0: only past the single tile's LDS limit
+    t.mm_slabs_min = geti("SD_MM_SLABS_MIN", 24); // rows from which the k-slab GEMMs (O / down) of a pass take gemm_bf16_mm instead of the balanced kernel
+    t.mm_mtw = geti("SD_MM_MTW", 0);              // (sweeps) m-tiles per wave of gemm_bf16_mm: 2 = 128-row blocks, 4 = 256-row blocks; 0 = by row count
+    t.mm_s = geti("SD_MM_S", 0);                  // (sweeps) k-slabs of gemm_bf16_mm; 0 = planned
+    t.gemm_rows = geti("SD_GEMM_ROWS", 1);        // 0: 17..64-row GEMMs stay on the streaming kernel (A/B runs, bit-compare tests)
+    t.rows_max = std::min(SD_ROWS_MAX, std::max(SD_STREAM_MAX_ROWS, geti("SD_GEMM_ROWS_MAX", SD_ROWS_MAX)));   // 65..this many rows take the balanced kernel, more gemm_bf16_mm
+    return t;
+}
+// CUs of the device, a property and no tunable: asked once per process.  No device (CPU container): plans are made for
+// the MI355X's 256 CUs
+static int device_cus() {
+    static const int cus = [] {
         int dev = 0, n = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-            g_env.cus = n;
-        else
-            (void)hipGetLastError();                  // no device (CPU container): plans are made for the MI355X's 256 CUs
-    }
+            return n;
+        (void)hipGetLastError();
+        return 256;
+    }();
+    return cus;
 }
 
-static int gemm_ntw(int N, int M) {
+static int gemm_ntw(const Tunables &t, int N, int M) {
     if (M <= 16) return 1;
     const int ntl = N / 16;
     // n-tiles per wave: more of them amortise the activation fragment loads, fewer give more workgroups.  Stream-batched
     // decode, 4 / 6 / 8 / 10 streams x 5 rows (bench.py --batch-streams): 529 / 727 / 861 / 990 tok/s with 4 tiles,
     // 504 / 753 / 808 / 908 with 2; 8 tiles: register pressure, slower everywhere.
-    const int want = g_env.gemm_ntw;
+    const int want = t.gemm_ntw;
     if (want >= 8 && ntl % 8 == 0) return 8;
     if (want >= 4 && ntl % 4 == 0) return 4;
     if (want >= 2 && ntl % 2 == 0) return 2;
@@ -236,24 +243,24 @@ static bool stream_burst8(int MT, int NTW, int K, int ks_per) {
     const int per_wave = (std::min(ks_per, K / 32) + 3) / 4;
     return MT == 1 && NTW == 1 && per_wave > 4 && per_wave <= 8;
 }
-static StreamInst stream_instance(int N, int K, int M, int Mpad, int ks_per) {
+static StreamInst stream_instance(const Tunables &t, int N, int K, int M, int Mpad, int ks_per) {
     const int MT = Mpad / 16;
     if (MT < 1 || MT > 4) return StreamInst{0, 0, 0};
     // rows beyond one m-tile (prefill, stream-batched verify): every activation fragment a wave loads is reused for
     // NTW weight tiles, because activations and weights share the CU's load path (X:W bytes = 16*MT : 16*NTW)
-    int ntw = MT == 1 ? 1 : gemm_ntw(N, M);
+    int ntw = MT == 1 ? 1 : gemm_ntw(t, N, M);
     if (MT == 2 && ntw > 4) ntw = 4;                              // (no 8-tile instance at 2 m-tiles)
     return StreamInst{MT, ntw, stream_burst8(MT, ntw, K, ks_per) ? 8 : stream_unroll(MT, ntw)};
 }
 
 #define TINY_SPLIT_BYTES 24576                       // weights a workgroup streams in a <= 16-row GEMM on a matrix of <= 8 MB
-static void gemm_split(int N, int K, int M, int *S_out, int *ks_per_out) {
-    const int NTL = N / 16 / gemm_ntw(N, M), KS = K / 32;
+static void gemm_split(const Tunables &t, int N, int K, int M, int *S_out, int *ks_per_out) {
+    const int NTL = N / 16 / gemm_ntw(t, N, M), KS = K / 32;
     int max_s = KS / 8;
     if (max_s < 1) max_s = 1;
     int S = 1;
-    if (g_env.gemm_units >= 0) {
-        S = (g_env.gemm_units + NTL / 2) / NTL;
+    if (t.gemm_units >= 0) {
+        S = (t.gemm_units + NTL / 2) / NTL;
     } else if (M > 16) {
         // many rows: every extra slab costs a write + a read of Mpad*N floats, which at 64 rows rivals the weight bytes
         // (256*S/K of them), so take the S that minimises (weights + slab traffic) / CU-fill efficiency
@@ -309,7 +316,7 @@ static void gemm_split(int N, int K, int M, int *S_out, int *ks_per_out) {
 // A route of kind GK_NONE has no kernel: the row limits (sd_model_max_rows, sd_model_max_pass_rows) keep such calls out.
 #define SD_MAX_FWD_ROWS 256
 struct RowsPlan { bool ok; int S, ksp, NG, grid, nwn, nwk, nld; };
-static RowsPlan rows_plan(int N, int K, int M, bool fused);
+static RowsPlan rows_plan(const Tunables &t, int N, int K, int M, bool fused);
 enum GemmKind { GK_NONE = 0, GK_STREAM, GK_STREAM_W16, GK_ROWS, GK_MM };
 enum GemmNeed {
     GN_GATHER = 1,     // X rows are gathered through the row table's xmap (the lm_head of some rows of a pass)
@@ -320,7 +327,7 @@ enum GemmNeed {
                        // partial then goes to the all-reduce as it is, without a fold launch in between)
 };
 struct GemmRoute { int kind, S, ksp, mtw; RowsPlan rp; };
-static GemmRoute route_gemm(int N, int K, int M, int need) {
+static GemmRoute route_gemm(const Tunables &t, int N, int K, int M, int need) {
     GemmRoute r = {};
     const bool fused = need & GN_FUSED, x_tiled = !(need & (GN_GATHER | GN_ROWMAJOR));
     const int KS = K / 32, Mpad = (int)align_up(M, 16);
@@ -330,22 +337,22 @@ static GemmRoute route_gemm(int N, int K, int M, int need) {
         r.ksp = KS;
         return r;
     }
-    const bool mm_slabs = !fused && M >= g_env.mm_slabs_min && (size_t)N * K >= ((size_t)16 << 20) && N / 16 / 8 < 64;
-    const RowsPlan rp = x_tiled ? rows_plan(N, K, M, fused) : RowsPlan{};
-    const bool rows_take = M > SD_STREAM_MAX_ROWS && M <= g_env.rows_max && !mm_slabs && rp.ok;
+    const bool mm_slabs = !fused && M >= t.mm_slabs_min && (size_t)N * K >= ((size_t)16 << 20) && N / 16 / 8 < 64;
+    const RowsPlan rp = x_tiled ? rows_plan(t, N, K, M, fused) : RowsPlan{};
+    const bool rows_take = M > SD_STREAM_MAX_ROWS && M <= t.rows_max && !mm_slabs && rp.ok;
     if (x_tiled && (M > SD_STREAM_MAX_ROWS || mm_slabs) && !rows_take && (N / 16) % 8 == 0 && KS % 2 == 0 && KS >= 16) {
         // 256-row blocks (mtw 4) or 128-row blocks (mtw 2) x 128 columns.  Fused: the block shape that fills the CUs better
         // (13b at 256 rows: gate/up 216 blocks of 256 rows, QKV 240 blocks of 128).  Otherwise 256-row blocks past 128
         // rows and k-slabs for about one block per CU (tools/mm_bench.py: O / down 6 slabs, QKV 2).
-        const int G = g_env.cus > 0 ? g_env.cus : 256, NB = N / 16 / 8;
+        const int G = device_cus(), NB = N / 16 / 8;
         auto blocks_of = [&](int mtw) { const int BMT = 4 * mtw; return ((Mpad / 16 + BMT - 1) / BMT) * NB; };
         auto fill = [&](int blocks) { return (double)blocks / (double)(((blocks + G - 1) / G) * G); };
         r.kind = GK_MM;
         r.mtw = Mpad <= 128 ? 2 : 4;
         if (fused && Mpad > 128 && fill(blocks_of(2)) > fill(blocks_of(4)) + 0.05) r.mtw = 2;
-        if (g_env.mm_mtw) r.mtw = g_env.mm_mtw;
+        if (t.mm_mtw) r.mtw = t.mm_mtw;
         const int blocks = blocks_of(r.mtw);
-        int S = fused ? 1 : (g_env.mm_s ? g_env.mm_s : std::max(1, (G - G / 16 + blocks / 2) / blocks));
+        int S = fused ? 1 : (t.mm_s ? t.mm_s : std::max(1, (G - G / 16 + blocks / 2) / blocks));
         S = std::min(std::min(S, 8), std::max(1, KS / 8));     // (every slab is a write + a read of Mpad x N floats)
         r.ksp = (int)align_up((KS + S - 1) / S, 2);
         r.S = (KS + r.ksp - 1) / r.ksp;
@@ -360,7 +367,7 @@ static GemmRoute route_gemm(int N, int K, int M, int need) {
     }
     if (M > SD_STREAM_MAX_ROWS) return r;
     r.kind = GK_STREAM;
-    gemm_split(N, K, M, &r.S, &r.ksp);
+    gemm_split(t, N, K, M, &r.S, &r.ksp);
     // (<= 16 rows of a shard: one workgroup per n-tile over the whole k-range still gives >= 256 workgroups at hidden >= 4096)
     if (fused || ((need & GN_ONE_SLAB) && M <= 16 && N / 16 >= 256)) {
         r.S = 1;
@@ -401,10 +408,10 @@ static void launch_gemm_mm(const void *W, const void *X, float *part, int M, int
 
 // ---- 17..SD_ROWS_MAX rows: the balanced one-workgroup-per-CU kernel (rows_kernels.h).  S k-slabs x NG n-groups = one workgroup per
 // CU; a fused epilogue needs S == 1.  The plan minimises (weight bytes + slab traffic) / how evenly the n-tiles divide.
-static RowsPlan rows_plan(int N, int K, int M, bool fused) {
+static RowsPlan rows_plan(const Tunables &t, int N, int K, int M, bool fused) {
     RowsPlan p = {};
-    if (!g_env.gemm_rows || M <= 16 || M > SD_ROWS_MAX || N % 16 || K % 32) return p;
-    const int G = g_env.cus > 0 ? g_env.cus : 256, NT = N / 16, KS = K / 32, Mpad = (int)align_up(M, 16);
+    if (!t.gemm_rows || M <= 16 || M > SD_ROWS_MAX || N % 16 || K % 32) return p;
+    const int G = device_cus(), NT = N / 16, KS = K / 32, Mpad = (int)align_up(M, 16);
     const double wbytes = (double)N * K * 2.0, slab = 2.0 * Mpad * (double)N * 4.0;
     double best = 1e300;
     for (int S = 1; S <= (fused ? 1 : 16); S *= 2) {
@@ -492,12 +499,12 @@ static int launch_gemm_rows(const void *W, const void *X, float *part, int M, in
 
 // floats of the k-slabs a GEMM of an N x K weight leaves at up to `rows` rows: the largest of its routes that can run (X in
 // the tile layout, or gathered for the lm_head / OPT's project_out; fused epilogues leave no slabs)
-static size_t gemm_part_floats(const sd_model_config &c, int N, int K, int rows, bool gathered = false) {
+static size_t gemm_part_floats(const Tunables &t, const sd_model_config &c, int N, int K, int rows, bool gathered = false) {
     if (!is16(c.dtype)) return (size_t)rows * N;
     size_t best = 0;
     for (int m = 1; m <= rows; ++m)
         for (int need : {0, gathered ? GN_GATHER : 0}) {
-            const GemmRoute r = route_gemm(N, K, m, need);
+            const GemmRoute r = route_gemm(t, N, K, m, need);
             if (r.kind != GK_NONE) best = std::max(best, (size_t)r.S * align_up(m, 16) * N);
         }
     return best;
@@ -516,7 +523,7 @@ extern "C" size_t sd_session_kv_bytes(const sd_model *m, int max_seq) {
 struct ScratchPlan {
     size_t x, x2, h, h2, aoctr, ssq, finctr, q, attn, act, e, apart, part, spart, tmax, tp_in, tp_out, total, part_floats, spart_floats;
 };
-static ScratchPlan plan_scratch(const sd_model_config &c, int rows) {
+static ScratchPlan plan_scratch(const Tunables &t, const sd_model_config &c, int rows) {
     ScratchPlan p;
     const size_t es = esize(c.dtype);
     const int ed = embed_dim(c);
@@ -537,14 +544,14 @@ static ScratchPlan plan_scratch(const sd_model_config &c, int rows) {
     p.e = take(trows * ed * es);
     p.apart = take((size_t)64 * c.n_heads * 8 * (c.head_dim + 2) * sizeof(float));
     size_t pf = 0;
-    pf = std::max(pf, gemm_part_floats(c, qkv_cols(c), c.hidden, rows));
-    pf = std::max(pf, gemm_part_floats(c, c.hidden, q_dim(c), rows));
-    pf = std::max(pf, gemm_part_floats(c, gu_cols(c), c.hidden, rows));
-    pf = std::max(pf, gemm_part_floats(c, c.hidden, c.inter, rows));
-    pf = std::max(pf, gemm_part_floats(c, c.vocab, ed, rows, true));
+    pf = std::max(pf, gemm_part_floats(t, c, qkv_cols(c), c.hidden, rows));
+    pf = std::max(pf, gemm_part_floats(t, c, c.hidden, q_dim(c), rows));
+    pf = std::max(pf, gemm_part_floats(t, c, gu_cols(c), c.hidden, rows));
+    pf = std::max(pf, gemm_part_floats(t, c, c.hidden, c.inter, rows));
+    pf = std::max(pf, gemm_part_floats(t, c, c.vocab, ed, rows, true));
     if (ed != c.hidden) {
-        pf = std::max(pf, gemm_part_floats(c, c.hidden, ed, rows));
-        pf = std::max(pf, gemm_part_floats(c, ed, c.hidden, rows, true));
+        pf = std::max(pf, gemm_part_floats(t, c, c.hidden, ed, rows));
+        pf = std::max(pf, gemm_part_floats(t, c, ed, c.hidden, rows, true));
     }
     p.part_floats = pf;
     p.part = take(pf * sizeof(float));
@@ -560,37 +567,36 @@ static ScratchPlan plan_scratch(const sd_model_config &c, int rows) {
 
 // The rows up to `cap` at which every GEMM of a pass has a route (X in the tile layout), at every smaller count too: the
 // per-layer shapes (+ OPT's project_in / project_out), and with `head` the lm_head of a pass whose rows are all logit rows
-static int routed_rows(const sd_model_config &c, bool head, int cap) {
+static int routed_rows(const Tunables &t, const sd_model_config &c, bool head, int cap) {
     const int ed = embed_dim(c);
     std::vector<std::pair<int, int>> shapes = {{qkv_cols(c), c.hidden}, {c.hidden, q_dim(c)}, {gu_cols(c), c.hidden}, {c.hidden, c.inter}};
     if (ed != c.hidden) shapes.insert(shapes.end(), {{c.hidden, ed}, {ed, c.hidden}});
     if (head) shapes.push_back({c.vocab, ed});
     for (int m = 1; m <= cap; ++m)
         for (const auto &sh : shapes)
-            if (route_gemm(sh.first, sh.second, m, 0).kind == GK_NONE) return m - 1;
+            if (route_gemm(t, sh.first, sh.second, m, 0).kind == GK_NONE) return m - 1;
     return cap;
 }
 
 // Rows one sd_session_forward call may carry: 256 when every per-layer GEMM of the model has a route at every row count
 // (or the model is fp32, whose simple GEMM has no row limit), else the streaming kernel's 64.
-extern "C" int sd_model_max_rows(const sd_model *m) {
-    if (!m) return 0;
-    refresh_env();
-    if (!is16(m->cfg.dtype)) return SD_MAX_FWD_ROWS;
-    return routed_rows(m->cfg, false, SD_MAX_FWD_ROWS) == SD_MAX_FWD_ROWS ? SD_MAX_FWD_ROWS : SD_STREAM_MAX_ROWS;
+static int model_max_rows(const Tunables &t, const sd_model_config &c) {
+    if (!is16(c.dtype)) return SD_MAX_FWD_ROWS;
+    return routed_rows(t, c, false, SD_MAX_FWD_ROWS) == SD_MAX_FWD_ROWS ? SD_MAX_FWD_ROWS : SD_STREAM_MAX_ROWS;
 }
+extern "C" int sd_model_max_rows(const sd_model *m) { return m ? model_max_rows(read_tunables(), m->cfg) : 0; }
 
 // Rows of one pass whose rows are all logit rows (a stream-batched verify): at most SD_MAX_ROWS, and only as many as the
 // lm_head has a kernel for (a vocab that is not a multiple of 128 columns - OPT's 50272 - stops at the streaming kernel's 64).
-extern "C" int sd_model_max_pass_rows(const sd_model *m) {
-    if (!m) return 0;
-    const int cap = std::min(SD_MAX_ROWS, sd_model_max_rows(m));
-    return is16(m->cfg.dtype) ? routed_rows(m->cfg, true, cap) : cap;
+static int model_max_pass_rows(const Tunables &t, const sd_model_config &c) {
+    const int cap = std::min(SD_MAX_ROWS, model_max_rows(t, c));
+    return is16(c.dtype) ? routed_rows(t, c, true, cap) : cap;
 }
+extern "C" int sd_model_max_pass_rows(const sd_model *m) { return m ? model_max_pass_rows(read_tunables(), m->cfg) : 0; }
 
 extern "C" size_t sd_session_scratch_bytes(const sd_model *m, int max_rows) {
-    refresh_env();
-    return plan_scratch(m->cfg, std::min(max_rows, sd_model_max_rows(m))).total;
+    const Tunables t = read_tunables();
+    return plan_scratch(t, m->cfg, std::min(max_rows, model_max_rows(t, m->cfg))).total;
 }
 
 extern "C" int sd_session_create(sd_model *m, int max_seq, int max_rows, void *kv_arena, void *scratch,
@@ -601,16 +607,15 @@ extern "C" int sd_session_create(sd_model *m, int max_seq, int max_rows, void *k
         SD_REQUIRE(max_seq <= m->cfg.max_pos, "sd_session_create: OPT is limited to %d positions", m->cfg.max_pos);
     else
         SD_REQUIRE(max_seq <= m->cfg.max_pos, "sd_session_create: rope table has %d rows, max_seq %d", m->cfg.max_pos, max_seq);
-    refresh_env();
     sd_session *s = new sd_session();
     s->m = m;
+    s->tun = read_tunables();                                     // rows, scratch plan and every later route: one block
     s->max_seq = max_seq;
-    max_rows = std::min(max_rows, sd_model_max_rows(m));
-    s->max_rows = max_rows;
-    s->max_pass_rows = std::min(max_rows, sd_model_max_pass_rows(m));
+    s->max_rows = std::min(max_rows, model_max_rows(s->tun, m->cfg));
+    s->max_pass_rows = std::min(s->max_rows, model_max_pass_rows(s->tun, m->cfg));
     s->kv = (char *)kv_arena;
     s->scratch = (char *)scratch;
-    const ScratchPlan p = plan_scratch(m->cfg, max_rows);
+    const ScratchPlan p = plan_scratch(s->tun, m->cfg, s->max_rows);
     s->x = s->scratch + p.x;
     s->x2 = s->scratch + p.x2;
     s->spart = (float *)(s->scratch + p.spart);
@@ -1033,9 +1038,9 @@ static void launch_gemm_bf16(const void *W, const void *X, float *part, int M, i
 }
 
 template <int EPI, typename H = bf16_t>
-static int dispatch_gemm_bf16(const void *W, const void *X, float *part, int M, int Mpad, int N, int K, int S,
+static int dispatch_gemm_bf16(const Tunables &t, const void *W, const void *X, float *part, int M, int Mpad, int N, int K, int S,
                               int ksp, const GemmEpiT<H> &e, hipStream_t st) {
-    const StreamInst in = stream_instance(N, K, M, Mpad, ksp);    // (launch_gemm_bf16 takes the UNROLL by the same functions)
+    const StreamInst in = stream_instance(t, N, K, M, Mpad, ksp);    // (launch_gemm_bf16 takes the UNROLL by the same functions)
     const int MT = in.MT, ntw = in.NTW;
     if (MT == 1) launch_gemm_bf16<1, EPI, 1, H>(W, X, part, M, Mpad, N, K, S, ksp, e, st);
     else if (MT == 2) { if (ntw == 4) launch_gemm_bf16<2, EPI, 4, H>(W, X, part, M, Mpad, N, K, S, ksp, e, st);
@@ -1056,8 +1061,8 @@ static int dispatch_gemm_bf16(const void *W, const void *X, float *part, int M, 
 // Launch a bf16 GEMM the way route_gemm routed it.  EPI_PART leaves r.S k-slabs of [Mpad][N] floats in `part`; any other
 // epilogue finishes in the launch (a route of one slab).
 template <int EPI, typename H = bf16_t>
-static int launch_gemm(const GemmRoute &r, const void *W, const void *X, float *part, int M, int N, int K, const GemmEpiT<H> &e,
-                       hipStream_t st) {
+static int launch_gemm(const Tunables &t, const GemmRoute &r, const void *W, const void *X, float *part, int M, int N, int K,
+                       const GemmEpiT<H> &e, hipStream_t st) {
     const int Mpad = (int)align_up(M, 16);
     auto bad = [&] {
         sd_set_error("internal: GEMM route %d cannot run epilogue %d (M=%d N=%d K=%d)", r.kind, EPI, M, N, K);
@@ -1068,7 +1073,7 @@ static int launch_gemm(const GemmRoute &r, const void *W, const void *X, float *
         if (r.kind != GK_STREAM || Mpad != 16) return bad();
         launch_gemm_bf16<1, EPI_HEAD, 1, H>(W, X, part, M, Mpad, N, K, r.S, r.ksp, e, st);
     } else if (r.kind == GK_STREAM)
-        rc = dispatch_gemm_bf16<EPI, H>(W, X, part, M, Mpad, N, K, r.S, r.ksp, e, st);
+        rc = dispatch_gemm_bf16<EPI, H>(t, W, X, part, M, Mpad, N, K, r.S, r.ksp, e, st);
     else if (r.kind == GK_ROWS)
         rc = launch_gemm_rows<EPI, H>(W, X, part, M, Mpad, N, K, r.rp, e, st);
     else if (r.kind == GK_MM)
@@ -1104,7 +1109,7 @@ static int run_gemm(sd_session *s, const GemmRoute &r, const void *W, const void
     SD_REQUIRE((size_t)r.S * Mpad * N <= s->part_floats, "run_gemm: partial buffer too small");
     GemmEpiT<H> e = {};
     if (xtab) { e.use_xmap = 1; e.tab = *xtab; }
-    const int rc = launch_gemm<EPI_PART, H>(r, W, X, s->part, M, N, K, e, st);
+    const int rc = launch_gemm<EPI_PART, H>(s->tun, r, W, X, s->part, M, N, K, e, st);
     if (rc != SD_OK) return rc;
     go->S = r.S;
     go->stride_s = (size_t)Mpad * N;
@@ -1118,7 +1123,7 @@ static int run_gemm_fused(sd_session *s, const GemmRoute &r, const void *W, cons
                           const GemmEpiT<H> &e, hipStream_t st) {
     ProfScope ps(s, PC_GEMM, st);
     SD_REQUIRE(r.kind != GK_NONE, "internal: no fused GEMM kernel for %d rows of %d x %d (past the session's row limits)", M, N, K);
-    return launch_gemm<EPI, H>(r, W, X, nullptr, M, N, K, e, st);
+    return launch_gemm<EPI, H>(s->tun, r, W, X, nullptr, M, N, K, e, st);
 }
 
 #define ATT_MAX_PARTS 64          // groups * splits the partial buffer is sized for
@@ -1126,13 +1131,13 @@ static int run_gemm_fused(sd_session *s, const GemmRoute &r, const void *W, cons
 #define ATT_LDS_MAX ((size_t)160 * 1024 - 512)
 // attn_kernel's key splits for a pass of n_groups row groups whose last row sees s_max keys: the dynamic LDS of a workgroup
 // (> ATT_LDS_MAX: the pass does not fit - launch_attn's capacity error)
-static size_t attn_split_plan(int D, int s_max, int n_groups, int *nsplit_out, int *s_cap_out) {
+static size_t attn_split_plan(const Tunables &t, int D, int s_max, int n_groups, int *nsplit_out, int *s_cap_out) {
     auto lds_for = [&](int nsplit, int *s_cap) {
         const int keys = nsplit > 1 ? (((s_max + nsplit - 1) / nsplit + 15) & ~15) : s_max;
         *s_cap = (int)align_up(keys, 64);
         return sizeof(float) * ((size_t)ATT_TQ * D + (size_t)(256 / (D / 8)) * ATT_TQ * D + (size_t)ATT_TQ * *s_cap);
     };
-    const int split_keys = g_env.attn_split_keys, keys_per = g_env.attn_keys_per_split;
+    const int split_keys = t.attn_split_keys, keys_per = t.attn_keys_per_split;
     int nsplit = 1, s_cap;
     if (s_max > split_keys) {
         nsplit = std::min(8, (s_max + keys_per - 1) / keys_per);
@@ -1186,23 +1191,18 @@ extern "C" int sd_prefill_attn_plan(int head_dim, int s_max, int block_keys, int
 // (attn_split_plan), and the blocked kernel past that, where launch_attn would return SD_ERR_CAPACITY.  A forced block
 // (SD_PREFILL_ATTN_BLOCK) takes the blocked kernel always.
 #define PA_BLOCKED_WG_PER_CU 2
-static int route_prefill_attn(int D, int n_heads, int n_rows, int n_groups, int s_max, int block_keys, int cus) {
+static int route_prefill_attn(const Tunables &t, int D, int n_heads, int n_rows, int n_groups, int s_max, int block_keys, int cus) {
     const PaPlan pl = plan_prefill_attn(D, s_max, block_keys);
     if (pl.kernel != 2 || block_keys > 0) return pl.kernel;
     if (n_heads * ((n_rows + PA_ROWS - 1) / PA_ROWS) >= PA_BLOCKED_WG_PER_CU * cus) return 2;
     int nsplit, s_cap;
-    return attn_split_plan(D, s_max, n_groups, &nsplit, &s_cap) > ATT_LDS_MAX ? 2 : 0;
+    return attn_split_plan(t, D, s_max, n_groups, &nsplit, &s_cap) > ATT_LDS_MAX ? 2 : 0;
 }
 extern "C" int sd_prefill_attn_route(int head_dim, int n_heads, int n_rows, int s_max, int block_keys, int cus, int *kernel) {
     SD_REQUIRE(kernel && n_heads >= 1 && n_rows >= 1 && s_max >= 1 && block_keys >= 0 && cus >= 0,
                "sd_prefill_attn_route: heads %d, rows %d, s_max %d, block_keys %d, cus %d", n_heads, n_rows, s_max, block_keys, cus);
-    if (!cus) {                                                   // (no tunable is resampled here: sessions keep theirs)
-        int dev = 0, n = 0;
-        if (g_env.cus > 0) cus = g_env.cus;
-        else if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cus = n;
-        else { (void)hipGetLastError(); cus = 256; }
-    }
-    *kernel = route_prefill_attn(head_dim, n_heads, n_rows, (n_rows + ATT_TQ - 1) / ATT_TQ, s_max, block_keys, cus);
+    if (!cus) cus = device_cus();
+    *kernel = route_prefill_attn(read_tunables(), head_dim, n_heads, n_rows, (n_rows + ATT_TQ - 1) / ATT_TQ, s_max, block_keys, cus);
     return SD_OK;
 }
 // The route of one forward pass: which launches it makes and how each of them is cut.  All of it follows from (session, row
@@ -1227,11 +1227,10 @@ template <typename T>
 static bool prefill_attn_ok(const sd_session *s, const RowTab &tab, int s_max) {
     if constexpr (sizeof(T) != 2) return false;
     const sd_model_config &c = s->m->cfg;
-    if (!(g_env.prefill_attn && tab.contig && !tab.tree && (c.head_dim == 64 || c.head_dim == 128) && tab.n_rows >= 32 &&
+    if (!(s->tun.prefill_attn && tab.contig && !tab.tree && (c.head_dim == 64 || c.head_dim == 128) && tab.n_rows >= 32 &&
           c.n_heads % c.n_kv_heads == 0))
         return false;
-    return route_prefill_attn(c.head_dim, c.n_heads, tab.n_rows, tab.n_groups, s_max, g_env.prefill_attn_block,
-                              g_env.cus > 0 ? g_env.cus : 256) != 0;
+    return route_prefill_attn(s->tun, c.head_dim, c.n_heads, tab.n_rows, tab.n_groups, s_max, s->tun.prefill_attn_block, device_cus()) != 0;
 }
 template <typename T, int D, bool KV8>
 static void launch_attn_prefill_inst(const sd_model_config &c, const T *q, const PaGroups &pg, int layer, T *out, const PaPlan &pl,
@@ -1343,12 +1342,11 @@ template <typename T>
 static bool attn_oproj_ok(const sd_session *s, const RowTab &tab, int s_max) {
     const sd_model_config &c = s->m->cfg;
     if constexpr (sizeof(T) != 2) return false;
-    if (!g_env.fuse_attn_o || s->tp || tab.tree || tab.kv_fp8 || tab.contig) return false;
+    if (!s->tun.fuse_attn_o || s->tp || tab.tree || tab.kv_fp8 || tab.contig) return false;
     if (c.head_dim != 128 || tab.n_groups > 2 || tab.n_streams != 1 || tab.n_rows > 16) return false;
     const int K = q_dim(c), N = c.hidden;
-    if (K % 128 || K / 128 > AO_NKW || N % 16 || s_max > g_env.attn_split_keys) return false;
-    const int cus = g_env.cus > 0 ? g_env.cus : 256;
-    if (c.n_heads * tab.n_groups + (N / 16 + 1) / 2 > cus) return false;      // every workgroup resident at once, one per CU
+    if (K % 128 || K / 128 > AO_NKW || N % 16 || s_max > s->tun.attn_split_keys) return false;
+    if (c.n_heads * tab.n_groups + (N / 16 + 1) / 2 > device_cus()) return false;      // every workgroup resident at once, one per CU
     if ((size_t)16 * N > s->part_floats) return false;
     // (a context whose score tile does not fit the launch's LDS budget takes the two launches - never an error: the key
     //  limit SD_ATTN_SPLIT_KEYS is a tuning knob)
@@ -1375,7 +1373,7 @@ static int launch_attn_oproj(sd_session *s, const T *q, const RowTab &tab, const
     hipLaunchKernelGGL((attn_oproj_kernel<T>), dim3(c.n_heads * tab.n_groups + (c.hidden / 16 + 1) / 2), dim3(512), lds, st, q, tab, layer, out, c.n_heads,
                        c.n_kv_heads, c.arch, 1.0f / sqrtf((float)c.head_dim), s_cap, (const u32x4 *)wo, s->part, tab.n_rows, c.hidden,
                        q_dim(c), s->ao_ctr, want, AO_DELAY_TICKS, AO_GAP_TICKS,
-                       g_env.ao_stamps ? s->ao_stamps : (long long *)nullptr,
+                       s->tun.ao_stamps ? s->ao_stamps : (long long *)nullptr,
                        (T *)s->x, (T *)s->h, resid ? s->ssq : (float *)nullptr, s->wait_status);
     SD_LAUNCH_CHECK();
     s->ao_epoch += n_arrive;
@@ -1388,7 +1386,7 @@ template <typename T>
 static bool norm_on_load_ok(const sd_session *s, const RowTab &tab) {
     const sd_model_config &c = s->m->cfg;
     if constexpr (sizeof(T) != 2) return false;
-    if (!g_env.norm_on_load || c.arch != SD_ARCH_LLAMA || !c.fused_layout || s->tp) return false;
+    if (!s->tun.norm_on_load || c.arch != SD_ARCH_LLAMA || !c.fused_layout || s->tp) return false;
     // (9..16 rows: the conversions cost more than the launch they replace - +5.7 us on gate/up at 12 rows, tools/gemm_bench.py)
     return tab.n_rows <= 8 && c.hidden % 1024 == 0 && c.hidden <= 8192;
 }
@@ -1459,8 +1457,8 @@ static int head_finish(sd_session *s, const HeadReq *rq, HeadOut *ho, int S, siz
 }
 
 // the route of a GEMM a pass runs once (an fp32 model has one kernel and no routes)
-static GemmRoute route_of(const sd_model_config &c, int N, int K, int M, int need) {
-    return is16(c.dtype) ? route_gemm(N, K, M, need) : GemmRoute{};
+static GemmRoute route_of(const sd_session *s, int N, int K, int M, int need) {
+    return is16(s->m->cfg.dtype) ? route_gemm(s->tun, N, K, M, need) : GemmRoute{};
 }
 
 // A gather table whose first M rows are all in place (a verify pass: every row a logit row) is no gather for the 16-bit GEMMs
@@ -1493,12 +1491,12 @@ static int head_logits(sd_session *s, const GemmRoute &hr, const T *hl, const Ro
             for (int i = 0; i < n_logits; ++i) e.zero_ptr[i] = rq->zero_ptr[i];
         {
             ProfScope ps(s, PC_GEMM, st);
-            if ((rc = launch_gemm<EPI_HEAD, H16>(hr, m->w.lm_head, hl, s->part, n_logits, c.vocab, ED, e, st)) != SD_OK) return rc;
+            if ((rc = launch_gemm<EPI_HEAD, H16>(s->tun, hr, m->w.lm_head, hl, s->part, n_logits, c.vocab, ED, e, st)) != SD_OK) return rc;
         }
         if (ho) ho->tile_max = s->tile_max;
     } else {
         xt = gather_tab(c, xt, n_logits);
-        const GemmRoute r = xt ? hr : route_of(c, c.vocab, ED, n_logits, 0);
+        const GemmRoute r = xt ? hr : route_of(s, c.vocab, ED, n_logits, 0);
         if ((rc = run_gemm<H16>(s, r, m->w.lm_head, hl, n_logits, c.vocab, ED, &go, st, xt)) != SD_OK) return rc;
     }
     return head_finish<T>(s, rq, ho, go.S, go.stride_s, n_logits, logits_out, ld_logits, st);
@@ -1507,7 +1505,7 @@ static int head_logits(sd_session *s, const GemmRoute &hr, const T *hl, const Ro
 // whether a pass takes the small-model decode path (forward_small)
 static bool small_path_ok(const sd_session *s, const RowTab &tab) {
     const sd_model_config &c = s->m->cfg;
-    if (!g_env.small_path || c.dtype != SD_BF16 || !c.fused_layout || tab.contig || s->tp) return false;
+    if (!s->tun.small_path || c.dtype != SD_BF16 || !c.fused_layout || tab.contig || s->tp) return false;
     if (tab.n_rows > SMALL_MAX_ROWS || tab.n_logit_rows > SMALL_MAX_ROWS) return false;
     if (c.hidden > 2048 || c.hidden % 32 != 0 || embed_dim(c) != c.hidden) return false;
     if (c.arch == SD_ARCH_OPT && !c.opt_pre_ln) return false;          // post-LN keeps the stand-alone norm launches
@@ -1517,9 +1515,9 @@ static bool small_path_ok(const sd_session *s, const RowTab &tab) {
 
 // k-slabs of the small path's O / down GEMMs: the streaming GEMM's own policy (bit-identical slabs, what the parity tests
 // compare against), at most the 16 slabs s->spart holds
-static void small_split(int N, int K, int *S_out, int *ksp_out) {
+static void small_split(const Tunables &t, int N, int K, int *S_out, int *ksp_out) {
     const int KS = K / 32;
-    gemm_split(N, K, 1, S_out, ksp_out);
+    gemm_split(t, N, K, 1, S_out, ksp_out);
     if (*S_out > 16) { *ksp_out = (KS + 15) / 16; *S_out = (KS + *ksp_out - 1) / *ksp_out; }
 }
 
@@ -1593,6 +1591,7 @@ static int resid_norm(sd_session *s, const FwdPlan &fp, int M, T *x, const float
 template <typename T>
 static void plan_forward(const sd_session *s, const RowTab &tab, int s_max, FwdPlan &fp) {
     const sd_model_config &c = s->m->cfg;
+    const Tunables &t = s->tun;
     const int H = c.hidden, M = tab.n_rows, ED = embed_dim(c);
     const bool llama = c.arch == SD_ARCH_LLAMA, pre = llama || c.opt_pre_ln, fused = is16(c.dtype) && c.fused_layout != 0;
     // residual+norm keeps the row in registers: 2 groups of 4 columns per thread (H <= 8192)
@@ -1600,33 +1599,33 @@ static void plan_forward(const sd_session *s, const RowTab &tab, int s_max, FwdP
     fp.s_max = s_max; fp.nsplit = fp.s_cap = 0; fp.attn_lds = 0; fp.pa = PaPlan{};         // (everything but pg, which only
     fp.qkv = fp.o = fp.gu = fp.down = fp.head = GemmRoute{};                                // AK_PREFILL fills and reads)
     fp.small = small_path_ok(s, tab);
-    fp.embed_qkv = fp.small || (c.dtype == SD_BF16 && g_env.fuse_embed_qkv && fused && pre && (llama || ED == H) && !tab.contig &&
+    fp.embed_qkv = fp.small || (c.dtype == SD_BF16 && t.fuse_embed_qkv && fused && pre && (llama || ED == H) && !tab.contig &&
                                 M <= SMALL_MAX_ROWS && H <= 2048 && H % 32 == 0);
     if (!fp.small && attn_oproj_ok<T>(s, tab, s_max)) {
         fp.attn = AK_OPROJ;
         fp.nsplit = 1; fp.s_cap = (int)align_up(s_max, 64); fp.attn_lds = attn_oproj_lds(s_max);
     } else if (!fp.small && prefill_attn_ok<T>(s, tab, s_max)) {
         fp.attn = AK_PREFILL;
-        fp.pa = plan_prefill_attn(c.head_dim, s_max, g_env.prefill_attn_block);
+        fp.pa = plan_prefill_attn(c.head_dim, s_max, t.prefill_attn_block);
         prefill_groups(tab, fp.pg);
     } else {
         fp.attn = AK_KERNEL;
-        fp.attn_lds = attn_split_plan(c.head_dim, s_max, tab.n_groups, &fp.nsplit, &fp.s_cap);
+        fp.attn_lds = attn_split_plan(t, c.head_dim, s_max, tab.n_groups, &fp.nsplit, &fp.s_cap);
     }
     // the residual add in the producer's epilogue, the norm in the consumer's operand load (no launch between)
     const bool seams = pre && fused && norm_on_load_ok<T>(s, tab);
     fp.seam_o = seams && fp.attn == AK_OPROJ;
-    fp.seam_d = seams && g_env.norm_on_load > 1;
+    fp.seam_d = seams && t.norm_on_load > 1;
     if (!is16(c.dtype)) return;
     if (!fp.small) {
         // (a shard's O / down projection: one slab, which the all-reduce takes as it is)
         const int row_par = s->tp ? GN_ONE_SLAB : 0;
-        fp.qkv = route_gemm(qkv_cols(c), H, M, fused ? GN_FUSED | GN_QKV : 0);
-        fp.o = route_gemm(H, q_dim(c), M, row_par);
-        fp.gu = route_gemm(gu_cols(c), H, M, fused ? GN_FUSED : 0);
-        fp.down = route_gemm(H, c.inter, M, row_par);
+        fp.qkv = route_gemm(t, qkv_cols(c), H, M, fused ? GN_FUSED | GN_QKV : 0);
+        fp.o = route_gemm(t, H, q_dim(c), M, row_par);
+        fp.gu = route_gemm(t, gu_cols(c), H, M, fused ? GN_FUSED : 0);
+        fp.down = route_gemm(t, H, c.inter, M, row_par);
     }
-    if (tab.n_logit_rows > 0) fp.head = route_gemm(c.vocab, ED, tab.n_logit_rows, GN_GATHER);
+    if (tab.n_logit_rows > 0) fp.head = route_gemm(t, c.vocab, ED, tab.n_logit_rows, GN_GATHER);
 }
 
 // launch_attn_d<bf16_t>, defined behind forward_impl: the kernels of the code object lie in the order in which this file
@@ -1648,14 +1647,14 @@ static int forward_small(sd_session *s, const RowTab &tab, const FwdPlan &fp, fl
     int rc;
     // SD_SMALL_PATH=1: the two norm launches of a layer become prologues of QKV / gate-up; O, down and the head keep the
     // per-op chain's kernels.  =2: every seam a prologue and gemm_small for O / down (the round-2 route, kept for A/B)
-    const bool all_pro = g_env.small_path >= 2;
+    const bool all_pro = s->tun.small_path >= 2;
     // the epilogue descriptors are built once per pass (3 KB each, and this is the draft step's host thread): a layer changes
     // its bias and its number
     GemmEpi qe = qkv_epi<bf16_t>(s, tab, 0), ae = act_epi<bf16_t>(s, 0);
     const GemmEpi no_epi = {};
     int S_o, ksp_o, S_d, ksp_d;
-    small_split(H, q_dim(c), &S_o, &ksp_o);
-    small_split(H, I, &S_d, &ksp_d);
+    small_split(s->tun, H, q_dim(c), &S_o, &ksp_o);
+    small_split(s->tun, H, I, &S_d, &ksp_d);
     SD_REQUIRE((size_t)std::max(S_o, S_d) * 16 * H <= s->spart_floats, "forward_small: slab buffer too small");
 
     auto resid_pro = [&](int S, const bf16_t *bias, const void *nw, const void *nb, bool write_r) {
@@ -1687,7 +1686,7 @@ static int forward_small(sd_session *s, const RowTab &tab, const FwdPlan &fp, fl
         auto slab_gemm = [&](const void *W, const bf16_t *X, int K, int S, int ksp) -> int {
             if (all_pro) return launch_small<PRO_TILED, EPI_PART>(s, W, X, s->spart, M, H, K, S, ksp, no_epi, SmallPro{}, st);
             ProfScope ps(s, PC_GEMM, st);
-            const int rc2 = dispatch_gemm_bf16<EPI_PART, bf16_t>(W, X, s->spart, M, 16, H, K, S, ksp, no_epi, st);
+            const int rc2 = dispatch_gemm_bf16<EPI_PART, bf16_t>(s->tun, W, X, s->spart, M, 16, H, K, S, ksp, no_epi, st);
             SD_LAUNCH_CHECK();
             return rc2;
         };
@@ -1772,7 +1771,7 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
                                    (const T *)nullptr, 0, eb, 1, c.vocab);
                 SD_LAUNCH_CHECK();
             }
-            if ((rc = run_gemm<H16>(s, route_of(c, H, ED, n_new, 0), m->w.project_in, eb, n_new, H, ED, &go, st)) != SD_OK) return rc;
+            if ((rc = run_gemm<H16>(s, route_of(s, H, ED, n_new, 0), m->w.project_in, eb, n_new, H, ED, &go, st)) != SD_OK) return rc;
             ProfScope ps(s, PC_EMBED, st);
             hipLaunchKernelGGL((reduce_addpos_kernel<T>), dim3(n_new), dim3(256), 0, st, s->part, go.S, go.stride_s, H,
                                (const T *)m->w.pos_embed, tab, pos_off, x);
@@ -1878,7 +1877,7 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
     const RowTab *xt = &tab;
     if (ED != H) {                                              // OPT project_out (modeling_opt.py:744-745)
         xt = gather_tab(c, xt, n_logits);
-        const GemmRoute r = route_of(c, ED, H, n_logits, xt ? GN_GATHER : 0);
+        const GemmRoute r = route_of(s, ED, H, n_logits, xt ? GN_GATHER : 0);
         if ((rc = run_gemm<H16>(s, r, m->w.project_out, hl, n_logits, ED, H, &go, st, xt)) != SD_OK) return rc;
         ProfScope ps(s, PC_LOGITS, st);
         hipLaunchKernelGGL((reduce_rows_kernel<T>), dim3((ED + 255) / 256, n_logits), dim3(256), 0, st, s->part, go.S, go.stride_s,
@@ -2211,13 +2210,13 @@ extern "C" int sd_gemm_route(int N, int K, int M, int need, sd_gemm_route_info *
     SD_REQUIRE(M >= 1 && M <= SD_MAX_FWD_ROWS && N >= 16 && K >= 32 && N % 16 == 0 && K % 32 == 0,
                "sd_gemm_route: need 1<=M<=%d, N%%16==0, K%%32==0", SD_MAX_FWD_ROWS);
     SD_REQUIRE(need >= 0 && need < 32, "sd_gemm_route: need is a set of SD_GN_* bits");
-    refresh_env();
-    const GemmRoute r = route_gemm(N, K, M, need);
+    const Tunables t = read_tunables();
+    const GemmRoute r = route_gemm(t, N, K, M, need);
     const int Mpad = (int)align_up(M, 16);
     sd_gemm_route_info o = {};
     o.kind = r.kind; o.S = r.S; o.ksp = r.ksp; o.mtw = r.mtw;
     if (r.kind == GK_STREAM) {
-        const StreamInst in = stream_instance(N, K, M, Mpad, r.ksp);
+        const StreamInst in = stream_instance(t, N, K, M, Mpad, r.ksp);
         o.inst_mt = in.MT; o.inst_ntw = in.NTW; o.inst_unroll = in.UNROLL;
     } else if (r.kind == GK_STREAM_W16) {
         o.inst_mt = 1; o.inst_ntw = 1;
@@ -2237,27 +2236,27 @@ extern "C" int sd_gemm_route(int N, int K, int M, int need, sd_gemm_route_info *
 
 extern "C" size_t sd_session_part_floats(const sd_model *m, int max_rows) {
     if (!m) return 0;
-    refresh_env();
-    return plan_scratch(m->cfg, std::min(max_rows, sd_model_max_rows(m))).part_floats;
+    const Tunables t = read_tunables();
+    return plan_scratch(t, m->cfg, std::min(max_rows, model_max_rows(t, m->cfg))).part_floats;
 }
 
 extern "C" int sd_gemm_bf16_need(const void *w_packed, const void *x, int M, int N, int K, int need, float *part,
                                  size_t part_floats, float *out, int *splits_out, void *stream) {
     SD_REQUIRE(w_packed && x && part, "sd_gemm_bf16: null argument");
-    refresh_env();
     SD_REQUIRE(M >= 1 && M <= SD_MAX_FWD_ROWS && N % 16 == 0 && K % 32 == 0,
                "sd_gemm_bf16: need 1<=M<=%d, N%%16==0, K%%32==0", SD_MAX_FWD_ROWS);
     SD_REQUIRE(need >= 0 && need < 32 && !(need & (GN_GATHER | GN_QKV)),
                "sd_gemm_bf16_need: need %d (a row gather needs a row table, the QKV route its epilogue)", need);
     const bool x_tiled = !(need & GN_ROWMAJOR);
-    const GemmRoute r = route_gemm(N, K, M, need);
+    const Tunables t = read_tunables();
+    const GemmRoute r = route_gemm(t, N, K, M, need);
     SD_REQUIRE(r.kind != GK_NONE, "sd_gemm_bf16: more than 64 rows need the tile layout (x_tiled) and N %% 128 == 0");
     const int Mpad = (int)align_up(M, 16);
     SD_REQUIRE((size_t)r.S * Mpad * N <= part_floats, "sd_gemm_bf16: part buffer needs %zu floats", (size_t)r.S * Mpad * N);
     hipStream_t st = (hipStream_t)stream;
     GemmEpi e = {};
     e.x_rowmajor = x_tiled ? 0 : 1;
-    if (launch_gemm<EPI_PART>(r, w_packed, x, part, M, N, K, e, st) != SD_OK) return SD_ERR_INVALID;
+    if (launch_gemm<EPI_PART>(t, r, w_packed, x, part, M, N, K, e, st) != SD_OK) return SD_ERR_INVALID;
     if (out) {
         hipLaunchKernelGGL(reduce_f32_kernel, dim3((M * N + 255) / 256), dim3(256), 0, st, part, r.S,
                            (size_t)Mpad * N, M * N, out);

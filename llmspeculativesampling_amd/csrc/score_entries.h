@@ -37,7 +37,6 @@ extern "C" int sd_score_sequence(sd_session *s, const int32_t *tokens, int n, in
     SD_REQUIRE(ld_slab >= V, "sd_score_sequence: ld_slab %ld < V %d", ld_slab, V);
     SD_REQUIRE(n - 1 <= s->max_seq, "sd_score_sequence: %d positions, max_seq %d", n - 1, s->max_seq);
     SD_REQUIRE(!s->tp, "sd_score_sequence: the session is bound to a tensor-parallel group");
-    refresh_env();
     int rc;
     // the prompt: positions [0, first - 1), no logit rows
     if (first > 1 && (rc = feed_rows(s, tokens, 0, first - 1, 0, nullptr, 0, nullptr, nullptr, stream)) != SD_OK) return rc;

@@ -651,7 +651,6 @@ extern "C" int sd_spec_generate(const sd_spec_stream *dev, int gamma, const sd_s
     if (int rc = check_grammar_states("sd_spec_generate", "stream", &ts, 1, &states_need); rc != SD_OK) return rc;
     SD_REQUIRE(!has_grammar(ts) || s->target_len <= s->len - 1, "sd_spec_generate: grammar: target_len %d of %d tokens: the first "
                "verify pass must start at the prompt's last row", s->target_len, s->len);
-    refresh_env();
     return single_stream_loop("sd_spec_generate", *dev, gamma, sm, *scratch, s, random_seed, r_const, stream, o, nullptr);
 }
 
@@ -1201,7 +1200,6 @@ extern "C" int sd_lookup_generate(const sd_spec_stream *dev, int gamma, int ngra
                dev->target->m->cfg.vocab);
     SD_REQUIRE(!has_grammar(dev->target), "%s: the target session carries a grammar: this loop has no edit pass (detach it: "
                "sd_session_set_grammar(s, NULL, NULL, 0))", who);
-    refresh_env();
     // the two info ints are behind the result block; no options block in this entry: nothing to edit or score
     const LookupDraft lookup = {ngram_max, ngram_min, reinterpret_cast<int32_t *>(dev->res_dev + 1),
                                 reinterpret_cast<const int32_t *>(dev->res_host + 1), &match_len_out};
@@ -1234,7 +1232,6 @@ extern "C" int sd_lookup_batch_generate(sd_batch_stream *streams, int n_streams,
     SD_REQUIRE(sm.V == streams[0].target->m->cfg.vocab && sm.ld >= sm.V, "%s: V %d (ld %ld), the target's vocabulary is %d", who, sm.V,
                sm.ld, streams[0].target->m->cfg.vocab);
     if (int rc = check_result_blocks(who, streams, n_streams); rc != SD_OK) return rc;
-    refresh_env();
     // 2 info ints per stream behind the blocks; no options block in this entry: nothing to edit or score
     const LookupDraft lookup = {ngram_max, ngram_min, reinterpret_cast<int32_t *>(streams[0].res_dev + n_streams),
                                 reinterpret_cast<const int32_t *>(streams[0].res_host + n_streams), match_len_out};

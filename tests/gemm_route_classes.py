@@ -3,13 +3,13 @@ kernel instance / wave grid / raggedness every (shape, rows, need) point falls i
 
 tests/test_gemm_routes_cpu.py checks the planner's invariants over the whole universe; tests/test_gpu_gemm_routes.py runs
 every witness as an integer-exact GEMM."""
-import contextlib
 import ctypes as C
 import functools
 import json
 import os
 
 from llmspeculativesampling_amd import _lib
+from sd_env import tunables  # noqa: F401  (the planner reads its tunables at every query / run; importers use G.tunables)
 
 GATHER, ROWMAJOR, FUSED, QKV, ONE_SLAB = (_lib.SD_GN_GATHER, _lib.SD_GN_ROWMAJOR, _lib.SD_GN_FUSED, _lib.SD_GN_QKV,
                                           _lib.SD_GN_ONE_SLAB)
@@ -117,21 +117,6 @@ def universe():
 
 
 # ---- the query ------------------------------------------------------------------------------------------------------------
-@contextlib.contextmanager
-def tunables(env):
-    """The planner reads its tunables at every query / run: set them around the call only."""
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-
-
 class Route(_lib.SdGemmRouteInfo):
     def __repr__(self):
         return "Route(" + ", ".join(f"{f}={getattr(self, f)}" for f, _ in _lib.SdGemmRouteInfo._fields_) + ")"

@@ -25,9 +25,11 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+for d in (os.path.join(ROOT, "tests"), ROOT):
+    if d not in sys.path:
+        sys.path.insert(0, d)
 
+from sd_env import tunables                                                       # noqa: E402
 from llmspeculativesampling_amd import _lib, tp                                   # noqa: E402
 from llmspeculativesampling_amd.config import ModelConfig                         # noqa: E402
 from llmspeculativesampling_amd.engine import SpecDecModel, batch_forward, batch_prefill   # noqa: E402
@@ -96,13 +98,8 @@ def measured(ses, fn):
 def decode(name, rows, dtype=BF16, ctx=12, kv_dtype=None, env=None):
     """A `ctx`-token context pass, then the measured pass: `rows` new rows, logits for all of them."""
     def run():
-        for k, v in (env or {}).items():
-            os.environ[k] = v
-        try:
-            ses = model(name, dtype).new_session(256, kv_dtype=kv_dtype)        # (tunables are sampled here)
-        finally:
-            for k in env or {}:
-                os.environ.pop(k, None)
+        with tunables(env):
+            ses = model(name, dtype).new_session(256, kv_dtype=kv_dtype)        # (the session keeps the tunables of its creation)
         ids = tokens(ctx + rows)
         if ctx:
             ses.forward(ids[:ctx], 0)

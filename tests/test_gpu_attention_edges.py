@@ -32,6 +32,7 @@ import pytest
 import torch
 
 import attn_probe as P
+from sd_env import tunables
 from test_gpu_production_parity import _assert_within_reference_error
 
 pytestmark = pytest.mark.gpu
@@ -59,24 +60,6 @@ def hip():
     from llmspeculativesampling_amd import _lib, engine
     torch.set_num_threads(min(16, os.cpu_count() or 1))
     return types.SimpleNamespace(lib=_lib.lib, L=_lib, engine=engine)
-
-
-class _Env:
-    """Tunables are sampled when a session is created: set them around the creation (and the runs), always restore."""
-
-    def __init__(self, **kw):
-        self.kw = {k: str(v) for k, v in kw.items()}
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kw}
-        os.environ.update(self.kw)
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 class Runner:
@@ -166,7 +149,7 @@ def _run_causal(hip, label, name, dt, layouts, kvq=None, env=None, tail=None, ch
     o32 = _oracle(name, "fp32")
     o16 = None if dt == "fp32" else _oracle(name, dt, kvq)
     st = _Stats(f"{label} {name} {dt}{' fp8-kv' if kvq else ''}")
-    with _Env(**(env or {})):
+    with tunables(**(env or {})):
         a = Runner(hip, name, dt, kv_dtype=kvq)
         b = Runner(hip, name, dt, kv_dtype=kvq, with_marker=False, model=a.m)
         if check is not None:                                      # (on both runners: they must see the same calls)
@@ -262,7 +245,7 @@ def test_tree_planted_key_at_ancestor_and_non_ancestor_nodes(hip, name, dt, kvq)
     o16 = None if dt == "fp32" else _oracle(name, dt, kvq)
     for env in ({}, dict(SD_ATTN_SPLIT_KEYS=64, SD_ATTN_KEYS_PER_SPLIT=32)):
         st = _Stats(f"tree {'split(64,32)' if env else 'default'} {name} {dt}{' fp8-kv' if kvq else ''}")
-        with _Env(**env):
+        with tunables(**env):
             a = Runner(hip, name, dt, kv_dtype=kvq)
             b = Runner(hip, name, dt, kv_dtype=kvq, with_marker=False, model=a.m)
             for lay in P.tree_layouts():

@@ -32,7 +32,7 @@ import torch
 
 import fp8_store as F
 import seam_probe as S
-from test_gpu_attention_edges import _Env
+from sd_env import tunables
 
 pytestmark = pytest.mark.gpu
 
@@ -164,7 +164,7 @@ def test_every_bf16_mantissa_through_the_plain_store(hip, label, env, calls):
     """store4_fp8 behind EPI_QKV_PLAIN: 2 signs x 128 mantissas x 4 exponents, 24 uniform power-of-two scales from 'all flush'
     to 'all saturate' - every (sign, mantissa, e4m3 binade) class, every tie, every denormal."""
     bits = F.planted_bf16()
-    with _Env(**env):
+    with tunables(**env):
         ses = _planted_model(hip, bits, "bf16").new_session(S.MAX_POS, kv_dtype="fp8")
         assert ses.max_rows == 64
         _planted_rows(ses, bits, "bf16", F.sweep_scales(), calls, label, routes=env)
@@ -226,11 +226,10 @@ TWIN_CASES = [
 
 
 def _twins(hip, name, dt, env, w12=False):
-    """(16-bit session, fp8 session) of one model.  The tunables are process-wide and sampled whenever a session is created,
-    so both are created under the route's tunables plus SD_FUSE_ATTN_O=0 (which an fp8 arena implies anyway), and a test
-    creates no other session while it runs them."""
+    """(16-bit session, fp8 session) of one model.  A session keeps the tunables of its creation, so both are created under
+    the route's tunables plus SD_FUSE_ATTN_O=0 (which an fp8 arena implies anyway)."""
     m = _model(hip, name, dt, w12)
-    with _Env(**dict(env, **TWIN_ENV)):
+    with tunables(**dict(env, **TWIN_ENV)):
         s16 = m.new_session(S.MAX_POS)
         s8 = m.new_session(S.MAX_POS, kv_dtype="fp8")
     return m, s16, s8
@@ -292,7 +291,7 @@ def _stream_pair(hip, name, dt):
     m = _model(hip, name, dt)
     out = []
     for kind in ("real", "tight"):
-        with _Env(**TWIN_ENV):
+        with tunables(**TWIN_ENV):
             s16 = m.new_session(S.MAX_POS)
             s8 = m.new_session(S.MAX_POS, kv_dtype="fp8")
         tab = F.scale_table(name, dt, kind)

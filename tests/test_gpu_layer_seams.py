@@ -27,7 +27,8 @@ import pytest
 import torch
 
 import seam_probe as S
-from test_gpu_attention_edges import _Env, _Stats
+from sd_env import tunables
+from test_gpu_attention_edges import _Stats
 from test_gpu_production_parity import _assert_within_reference_error
 
 pytestmark = pytest.mark.gpu
@@ -93,7 +94,7 @@ def _judge(st, got, name, dt, toks, pos0=0):
 
 def _run_route(hip, label, env, w12, name, dt, rows, contig=False):
     st = _Stats(f"{label} {name} {dt}")
-    with _Env(**env):
+    with tunables(**env):
         m = _model(hip, name, dt, w12)
         ses = m.new_session(S.MAX_POS)
         assert ses.max_rows == (256 if dt == "fp32" or name in S.CONTIG_MODELS else 64), ses.max_rows
@@ -163,7 +164,7 @@ def test_planted_slab_reaches_every_loop_of_the_fold(hip, case):
     Sn, ksp = S.c_slabs(case)
     toks, dtype = S.c_tokens(n), S.DTYPES[dt]
     st = _Stats(f"C {label} S={Sn} -> {consumer}")
-    with _Env(**env):
+    with tunables(**env):
         for s in S.slab_classes(Sn):
             sd = S.slab_state_dict(name, weight, ksp, s)
             m = hip.engine.SpecDecModel.from_state_dict(S.probe_config(name), S.cast_sd(sd, dtype), dtype=dtype,
@@ -193,7 +194,7 @@ def test_decisive_activation_column_at_every_layout_edge(hip, label, name, dt, w
     (H = 1024, 5 rows; norm on load 1 / 2), in the many-row kernels (17, 64, 65 rows), and in a model with 12-bit records."""
     st = _Stats(f"D {label} {name} {dt}")
     dtype = S.DTYPES[dt]
-    with _Env(**env):
+    with tunables(**env):
         for j in S.act_columns(name):
             sd = S.act_state_dict(name, j)
             m = hip.engine.SpecDecModel.from_state_dict(S.probe_config(name), S.cast_sd(sd, dtype), dtype=dtype, w12=w12)
@@ -221,7 +222,7 @@ def test_opt_fc1_bias_cancels_to_a_decisive_remainder(hip, label, name, dt, env,
     (fp32), EPI_ACT_RELU in gemm_small (bf16, 1 row; SD_SMALL_PATH=2) and in the streaming / many-row GEMMs."""
     st = _Stats(f"D relu {label} {name} {dt}")
     dtype = S.DTYPES[dt]
-    with _Env(**env):
+    with tunables(**env):
         for j in S.act_columns(name):
             sd = S.relu_state_dict(name, j, "cancel")
             m = hip.engine.SpecDecModel.from_state_dict(S.probe_config(name), S.cast_sd(sd, dtype), dtype=dtype, w12=False)

@@ -2,7 +2,6 @@
 against apply_logit_edits o apply_penalties on the CPU, and the native loops against the CPU oracle run on models whose logits
 carry the same penalties and edits (tests/edited_model.py), each prompt under its own Philox variates."""
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -11,6 +10,7 @@ import torch
 import oracle
 from edited_model import EditedModel
 from philox_replay import PhiloxOracleNoise
+from sd_env import tunables
 from test_gpu_logprobs import _bf16_pair, _check, _corr_oracles
 from test_gpu_native_parity import _st
 from test_gpu_penalties import (BUDGETS, ITEMS, LENS, MODES, PARAMS, ROWS, SEEDS, SENTINEL, SHARED, _as_read, _histories, _loop_prompts,
@@ -455,15 +455,9 @@ def test_l5_bf16_fused_tail_equals_the_dense_tail_and_scores_stay_raw(hip):
                  logit_bias=[{allowed[0]: 2.0}, None, None, {7: -1.0}], min_tokens=[0, 0, 0, 3],
                  repetition_penalty=[1.0, 1.0, 1.0, 0.3], presence_penalty=[0.0, 0.0, 0.0, -6.0])
     runs = {}
-    old = os.environ.get("SD_BATCH_FUSED_TAIL")
-    try:
-        for tail in ("1", "0"):
-            os.environ["SD_BATCH_FUSED_TAIL"] = tail
+    for tail in ("1", "0"):
+        with tunables(SD_BATCH_FUSED_TAIL=tail):
             runs[tail] = hip.S.speculative_sampling_batch(prompts, dm, tm, -1, None, 12, details=True, logprobs=True, **kw, **edits)
-    finally:
-        os.environ.pop("SD_BATCH_FUSED_TAIL", None)
-        if old is not None:
-            os.environ["SD_BATCH_FUSED_TAIL"] = old
     (o1, d1, l1), (o0, d0, l0) = runs["1"], runs["0"]
     for a, b, da, db, la, lb in zip(o1, o0, d1, d0, l1, l0):
         assert torch.equal(a, b) and torch.equal(la, lb) and da["acc_len"] == db["acc_len"]

@@ -5,7 +5,6 @@ import contextlib
 import ctypes as C
 import functools
 import math
-import os
 import sys
 
 import pytest
@@ -13,6 +12,7 @@ import torch
 
 import oracle
 import logprob_rows as LR
+from sd_env import tunables
 from test_gpu_native_parity import BF16_CFG, _st
 from test_gpu_spec_queue import BUDGETS, KW, LENS, SEEDS, _corr_case, _ends, _models, _oracle, _prompts
 from llmspeculativesampling_amd.config import ModelConfig
@@ -359,17 +359,9 @@ def test_l4_dense_tail_and_fused_tail_score_the_same_slab(hip):
     cfg, dm, tm, _ = _bf16_pair()
     prompts = [p.cuda() for p in _prompts(cfg.vocab_size, [12, 5, 20, 9], 1500)]
     runs = []
-    old = os.environ.get("SD_BATCH_FUSED_TAIL")
-    try:
-        for tail in (None, "0"):
-            os.environ.pop("SD_BATCH_FUSED_TAIL", None)
-            if tail is not None:
-                os.environ["SD_BATCH_FUSED_TAIL"] = tail
+    for tail in (None, "0"):                                      # (None: the variable unset)
+        with tunables(SD_BATCH_FUSED_TAIL=tail):
             runs.append(hip.S.speculative_sampling_batch(prompts, dm, tm, -1, None, 12, seeds=[61, 62, 63, 64], logprobs=True, **KW))
-    finally:
-        os.environ.pop("SD_BATCH_FUSED_TAIL", None)
-        if old is not None:
-            os.environ["SD_BATCH_FUSED_TAIL"] = old
     (o1, l1), (o2, l2) = runs
     assert all(torch.equal(a, b) for a, b in zip(o1, o2)) and all(torch.equal(a, b) for a, b in zip(l1, l2))
     assert all(lp.shape[1] >= 12 for lp in l1)

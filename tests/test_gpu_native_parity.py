@@ -15,6 +15,7 @@ import torch
 import oracle
 from golden_io import logits_row
 from philox_replay import PhiloxOracleNoise
+from sd_env import tunables
 from llmspeculativesampling_amd.config import ModelConfig, load_config
 from llmspeculativesampling_amd.synth import make_state_dict, perturb_state_dict
 
@@ -225,15 +226,12 @@ def test_native_bf16_iteration_bit_equals_python_loop(hip, case, capsys):
     prompt = torch.from_numpy(np.random.default_rng(3).integers(3, cfg.vocab_size, size=(1, L))).cuda()
     dm = hip.engine.SpecDecModel.from_state_dict(cfg, dsd, dtype=torch.bfloat16)
     tm = dm if case == "all_accept" else hip.engine.SpecDecModel.from_state_dict(cfg, tsd, dtype=torch.bfloat16)
-    if case == "split_lm_head":
-        os.environ["SD_GEMM_UNITS"] = "1536"                     # 512 n-tiles -> 3 k-slabs: the head leaves partial slabs
-    try:
+    # 512 n-tiles -> 3 k-slabs: the head leaves partial slabs
+    with tunables({"SD_GEMM_UNITS": "1536"} if case == "split_lm_head" else {}):
         kw = dict(gamma=4, top_k=20, top_p=0.9)
         a, da = hip.S.speculative_sampling(prompt, dm, tm, -1, None, 40, details=True, rng=hip.noise.DeviceNoise(123), **kw)
         b, db = hip.S.speculative_sampling(prompt, dm, tm, -1, None, 40, details=True, rng=hip.noise.DeviceNoise(123),
                                            verbose=True, **kw)
-    finally:
-        os.environ.pop("SD_GEMM_UNITS", None)
     capsys.readouterr()
     assert torch.equal(a, b)
     assert da["acc_len"] == db["acc_len"] and da["target_call_times"] == db["target_call_times"]
@@ -249,8 +247,7 @@ def test_native_bf16_iteration_small_path_2_head_bit_equals_python_loop(hip, cap
     residual + final norm as its prologue): it leaves the raw slab and the tile maxima for the norm (EPI_HEAD), where the
     Python-orchestrated loop (verbose=True) takes the same launch's slab through logits_kernel.  Same pair, prompt and
     Philox seed as the `perturbed` case above: tokens, acc_len and acc_rate must be bit-equal."""
-    os.environ["SD_SMALL_PATH"] = "2"                            # read when a session is made, so before the models
-    try:
+    with tunables(SD_SMALL_PATH="2"):                            # read when a session is made, so before the models
         cfg = ModelConfig(**BF16_CFG)
         dsd = make_state_dict(cfg, 5, dtype=torch.bfloat16)
         tsd = {k: v.to(torch.bfloat16) for k, v in perturb_state_dict({a: b.float() for a, b in dsd.items()}, 6, 0.05).items()}
@@ -261,8 +258,6 @@ def test_native_bf16_iteration_small_path_2_head_bit_equals_python_loop(hip, cap
         a, da = hip.S.speculative_sampling(prompt, dm, tm, -1, None, 40, details=True, rng=hip.noise.DeviceNoise(123), **kw)
         b, db = hip.S.speculative_sampling(prompt, dm, tm, -1, None, 40, details=True, rng=hip.noise.DeviceNoise(123),
                                            verbose=True, **kw)
-    finally:
-        os.environ.pop("SD_SMALL_PATH", None)
     capsys.readouterr()
     assert torch.equal(a, b)
     assert da["acc_len"] == db["acc_len"] and da["target_call_times"] == db["target_call_times"]
@@ -299,18 +294,13 @@ def test_stream_batched_bf16_fused_tail_bit_equals_the_dense_tail(hip, case):
     kw = dict(gamma=gamma, top_k=20, top_p=0.9)
     if case == "seeded_g2":
         kw["random_seed"] = 42
-    if case == "split_lm_head":
-        os.environ["SD_GEMM_UNITS"] = "1536"
-    try:
+    with tunables({"SD_GEMM_UNITS": "1536"} if case == "split_lm_head" else {}):
         probe = hip.S.speculative_sampling_batch(prompts[1:2], dm, tm, -1, None, 24, seeds=seeds[1:2], **kw)
         eos = int(probe[0][0, prompts[1].shape[1] + 5])
         runs = {}
         for mode in ("0", "1"):
-            os.environ["SD_BATCH_FUSED_TAIL"] = mode
-            runs[mode] = hip.S.speculative_sampling_batch(prompts, dm, tm, eos, None, 24, details=True, seeds=seeds, **kw)
-    finally:
-        os.environ.pop("SD_BATCH_FUSED_TAIL", None)
-        os.environ.pop("SD_GEMM_UNITS", None)
+            with tunables(SD_BATCH_FUSED_TAIL=mode):
+                runs[mode] = hip.S.speculative_sampling_batch(prompts, dm, tm, eos, None, 24, details=True, seeds=seeds, **kw)
     (o0, d0), (o1, d1) = runs["0"], runs["1"]
     stopped = 0
     for a, b, da, db, p in zip(o0, o1, d0, d1, prompts):
@@ -592,8 +582,7 @@ def test_small_model_path_is_bit_identical_to_the_launch_per_op_chain(hip, name)
              "hybrid": {}}                                                    # (the default) the layers' norms as QKV / gate-up prologues;
                                                                                # O, down and the head on the per-op kernels
     for flag, env in modes.items():
-        os.environ.update(env)
-        try:
+        with tunables(env):
             ses = m.new_session(64)
             ses.forward(ids[:30], 0)                              # prompt (many rows: the per-op chain either way)
             got, pos = [], 30
@@ -601,9 +590,6 @@ def test_small_model_path_is_bit_identical_to_the_launch_per_op_chain(hip, name)
                 got.append(ses.forward(ids[pos:pos + q], q).clone())
                 pos += q
             outs[flag] = (torch.cat(got), ses.kv[:, :, :, :pos].clone())
-        finally:
-            for k in env:
-                os.environ.pop(k, None)
     outs["0"] = outs["per_op"]
     # the DEFAULT route (per-op chain + embedding / first norm fused into the layer-0 QKV GEMM) is bit-identical at any V
     assert torch.equal(outs["default"][0], outs["0"][0]) and torch.equal(outs["default"][1], outs["0"][1])
@@ -625,6 +611,39 @@ def test_small_model_path_is_bit_identical_to_the_launch_per_op_chain(hip, name)
     want = om(ids[None].long().cpu()).logits.float()[0, 30:41]
     got = outs["1"][0].cpu()
     assert float((got - want[: got.shape[0]]).abs().max()) <= 0.04 * float(want.abs().max())
+
+
+def test_session_keeps_the_tunables_of_its_creation(hip):
+    """A session plans every pass with the tunables read when it was created, whatever the environment says later and
+    whatever sessions are created after it.  Session A is made under SD_SMALL_PATH=0 (a 2-row step takes the per-op chain),
+    then B under the defaults (the same step takes the prologue path: other launch counts, so the profile sees the route) and
+    a third under SD_GEMM_UNITS=1536 (a head of 3 slabs: another `part` size).  A's step repeated after that makes the same
+    launches class by class and leaves bit-identical logits and K / V rows."""
+    cfg = ModelConfig(**BF16_CFG)
+    m = hip.engine.SpecDecModel.from_state_dict(cfg, make_state_dict(cfg, 90, dtype=torch.bfloat16), dtype=torch.bfloat16)
+    ids = torch.from_numpy(np.random.default_rng(19).integers(3, cfg.vocab_size, size=(32,))).to(torch.int32).cuda()
+
+    def step(ses):
+        ses.rollback(30)
+        ses.profile(True)
+        logits = ses.forward(ids[30:32], 2).clone()
+        counts = {k: n for k, (_, n) in ses.profile_read().items()}
+        ses.profile(False)
+        return counts, logits, ses.kv[:, :, :, :32].clone()
+    with tunables(SD_SMALL_PATH="0"):
+        a = m.new_session(64)
+        a.forward(ids[:30], 0)
+        counts_a, logits_a, kv_a = step(a)
+    b = m.new_session(64)
+    with tunables(SD_GEMM_UNITS="1536"):
+        c = m.new_session(64)
+    b.forward(ids[:30], 0)
+    counts_b = step(b)[0]
+    assert counts_b != counts_a, (counts_a, counts_b)             # the two routes are told apart by their launches
+    counts_again, logits_again, kv_again = step(a)
+    assert counts_again == counts_a, (counts_a, counts_again)
+    assert torch.equal(logits_again, logits_a) and torch.equal(kv_again, kv_a)
+    assert c.handle and b.handle                                  # (all three sessions alive to the end)
 
 
 # --------------------------------------------------------------------------- bounded in-launch waits of the fused launches
@@ -928,13 +947,10 @@ def test_rccl_group_of_one_runs_the_all_reduce_path(hip):
     ids = torch.from_numpy(np.random.default_rng(4).integers(3, cfg.vocab_size, size=(1, 24))).to(torch.int32).cuda()[0]
     want = m.new_session(32).forward(ids, 5).clone()
     grp = tp.TPGroup.rccl(0, 1, lambda b: b)
-    os.environ["SD_TP_FORCE"] = "1"
-    try:
+    with tunables(SD_TP_FORCE="1"):
         ses = m.new_session(32)
         grp.bind(ses)
         got = ses.forward(ids, 5).clone()
-    finally:
-        os.environ.pop("SD_TP_FORCE", None)
     torch.cuda.synchronize()
     assert float((got - want).abs().max()) <= 0.04 * float(want.abs().max())
 
@@ -1044,14 +1060,9 @@ def test_tree_attention_split_keys_chunk_without_visible_key(hip):
     seq, mask, pos, pids = hip.S.get_seq_att_mask(1, ai, ab, at, P, 0)
     outs = []
     for split in (False, True):
-        if split:
-            os.environ["SD_ATTN_SPLIT_KEYS"], os.environ["SD_ATTN_KEYS_PER_SPLIT"] = "64", "32"
-        try:
+        with tunables({"SD_ATTN_SPLIT_KEYS": "64", "SD_ATTN_KEYS_PER_SPLIT": "32"} if split else {}):
             kv = hip.S.KVCacheModel(m, 1, 20, 0.9)               # (the tunables are sampled when the session is created)
             outs.append(kv.forward_tree_attention(seq.cuda(), prompt.cuda(), mask.cuda(), pids.cuda(), pos.clone().cuda()).float().cpu())
-        finally:
-            os.environ.pop("SD_ATTN_SPLIT_KEYS", None)
-            os.environ.pop("SD_ATTN_KEYS_PER_SPLIT", None)
     assert bool(torch.isfinite(outs[1]).all())
     # split attention keeps un-rounded exp() weights until the combine, the one-workgroup form rounds the probabilities to
     # bf16 first (as the reference does): both are held to the oracle's bf16 tree forward under the wide-tree test's bar
@@ -1136,11 +1147,8 @@ def test_fused_attention_oproj_launch_vs_two_launches(hip):
             got.append(ses.forward(ids[pos:pos + q], q).clone())
             pos += q
         return torch.cat(got), ses.kv[:, :, :, :pos].clone()
-    os.environ["SD_FUSE_ATTN_O"] = "0"
-    try:
+    with tunables(SD_FUSE_ATTN_O="0"):
         ref_logits, ref_kv = run()
-    finally:
-        os.environ.pop("SD_FUSE_ATTN_O", None)
     first = run()
     assert torch.equal(first[1][0], ref_kv[0])                    # layer 0's K / V rows: independent of any O projection
     assert not bool(torch.isnan(first[0]).any())
@@ -1182,13 +1190,9 @@ def test_norm_on_load_layer_path_vs_residual_norm_launches(hip, mode, shape, dty
             got.append(ses.forward(ids[pos:pos + q], q).clone())
             pos += q
         return torch.cat(got), ses.kv[:, :, :, :pos].clone()
-    os.environ["SD_NORM_ON_LOAD"] = "0"
-    try:
+    with tunables(SD_NORM_ON_LOAD="0"):
         ref_logits, ref_kv = run()
-    finally:
-        os.environ.pop("SD_NORM_ON_LOAD", None)
-    os.environ["SD_NORM_ON_LOAD"] = mode
-    try:
+    with tunables(SD_NORM_ON_LOAD=mode):
         # the path under test really is taken: a 5-row step launches residual_norm_kernel once per layer seam that keeps it
         ses = m.new_session(400)
         ses.forward(ids[:200], 0)
@@ -1206,8 +1210,6 @@ def test_norm_on_load_layer_path_vs_residual_norm_launches(hip, mode, shape, dty
         for _ in range(9):
             again = run()
             assert torch.equal(again[0], first[0]) and torch.equal(again[1], first[1])
-    finally:
-        os.environ.pop("SD_NORM_ON_LOAD", None)
 
 
 @pytest.mark.gpu

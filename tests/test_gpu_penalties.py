@@ -4,7 +4,6 @@ the same penalties (tests/penalised_model.py), each prompt under its own Philox 
 import ctypes as C
 import functools
 import itertools
-import os
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import torch
 import oracle
 from penalised_model import PenalisedModel
 from philox_replay import PhiloxOracleNoise
+from sd_env import tunables
 from test_gpu_logprobs import _bf16_pair, _check, _corr_oracles
 from test_gpu_native_parity import _st
 from test_gpu_spec_queue import _models, _prompts
@@ -284,16 +284,10 @@ def test_l3_bf16_fused_tail_equals_the_dense_tail_and_scores_stay_raw(hip):
     # repetition < 1, negative frequency / presence - which moves the output for certain)
     pens = dict(repetition_penalty=[0.3, 1.0, 1.0, 1.0], frequency_penalty=[0.0, 0.0, 0.0, -4.0], presence_penalty=[-6.0, 0.0, 0.0, -4.0])
     runs = {}
-    old = os.environ.get("SD_BATCH_FUSED_TAIL")
-    try:
-        for tail in ("1", "0"):
-            os.environ["SD_BATCH_FUSED_TAIL"] = tail
+    for tail in ("1", "0"):
+        with tunables(SD_BATCH_FUSED_TAIL=tail):
             runs[tail] = hip.S.speculative_sampling_batch(prompts, dm, tm, -1, None, 12, gamma=4, top_k=20, top_p=0.9, details=True,
                                                           seeds=[61, 62, 63, 64], logprobs=True, **pens)
-    finally:
-        os.environ.pop("SD_BATCH_FUSED_TAIL", None)
-        if old is not None:
-            os.environ["SD_BATCH_FUSED_TAIL"] = old
     (o1, d1, l1), (o0, d0, l0) = runs["1"], runs["0"]
     for a, b, da, db, la, lb in zip(o1, o0, d1, d0, l1, l0):
         assert torch.equal(a, b) and torch.equal(la, lb) and da["acc_len"] == db["acc_len"]

@@ -27,7 +27,8 @@ import attn_probe as P
 import prefill_block_layouts as B
 import prefill_probe_layouts as L
 from prefill_probe_layouts import wide_models  # noqa: F401  (fixture)
-from test_gpu_attention_edges import Runner, _run_causal, _Stats, _Env, _sd, hip  # noqa: F401  (hip: the module's fixture)
+from sd_env import tunables
+from test_gpu_attention_edges import Runner, _run_causal, _Stats, _sd, hip  # noqa: F401  (hip: the module's fixture)
 from test_gpu_production_parity import _assert_within_reference_error
 from llmspeculativesampling_amd.config import ModelConfig, load_config
 from llmspeculativesampling_amd.synth import make_state_dict, perturb_state_dict
@@ -58,7 +59,7 @@ def test_blocked_kernel_is_bit_identical_to_the_tile_kernel(hip, name, dt, kvq):
     call under the forced setting and stays 0 under =0; the prefill counter counts either kernel."""
     got = {}
     for block in (0, 64, 128):
-        with _Env(SD_PREFILL_ATTN=1, SD_PREFILL_ATTN_BLOCK=block):
+        with tunables(SD_PREFILL_ATTN=1, SD_PREFILL_ATTN_BLOCK=block):
             r = Runner(hip, name, dt, kv_dtype=kvq)
             assert r.cfg.num_hidden_layers == 1
             for n, pos0 in BIT_CALLS:
@@ -148,7 +149,7 @@ def test_past_the_tile_limit_the_blocked_kernel_and_the_default_route(hip, long_
     got = {}
     for tag, flag, block in (("default", 1, 0), ("blocked", 1, 256), ("attn_kernel", 0, 0)):
         st = _Stats(f"S = 2304, {tag} {name} {dt} {kvq}")
-        with _Env(SD_PREFILL_ATTN=flag, SD_PREFILL_ATTN_BLOCK=block):
+        with tunables(SD_PREFILL_ATTN=flag, SD_PREFILL_ATTN_BLOCK=block):
             r = Runner(hip, name, dt, kv_dtype=kvq, max_seq=P.probe_config(name).max_position_embeddings)
             assert r.ses.max_rows >= n
             kernel = _route(hip, r.cfg, n, S, block) if flag else 0
@@ -210,7 +211,7 @@ def test_prompt_past_the_old_capacity_wall_and_a_verify_on_top(hip, base, dt, kv
     sd = {k: v.to(torch.bfloat16).float() for k, v in make_state_dict(cfg, 37, head_gain=2.0).items()}
     ids = torch.from_numpy(np.random.default_rng(13).integers(3, cfg.vocab_size, size=(1, WALL_PROMPT + 5)))
     scales = L.stream_scales(0, cfg)
-    with _Env(**DEFAULT):
+    with tunables(**DEFAULT):
         m = hip.engine.SpecDecModel.from_state_dict(cfg, P.cast_sd(sd, dtype), dtype=dtype)
         ses = m.new_session(WALL_POS, kv_dtype=kvq)
         if kvq:
@@ -246,7 +247,7 @@ def test_speculative_sampling_is_byte_equal_under_a_forced_block(hip, monkeypatc
     prompt = torch.from_numpy(np.random.default_rng(6).integers(3, tc.vocab_size, size=(1, 150))).cuda()
     runs = {}
     for block in (64, 0):
-        with _Env(SD_PREFILL_ATTN=1, SD_PREFILL_ATTN_BLOCK=block):
+        with tunables(SD_PREFILL_ATTN=1, SD_PREFILL_ATTN_BLOCK=block):
             dm = hip.engine.SpecDecModel.from_state_dict(dc, P.cast_sd(dsd, torch.bfloat16), dtype=torch.bfloat16)
             tm = hip.engine.SpecDecModel.from_state_dict(tc, P.cast_sd(tsd, torch.bfloat16), dtype=torch.bfloat16)
             sessions, new_session = [], tm.new_session
@@ -268,7 +269,7 @@ def test_batched_prefill_is_bit_equal_under_a_forced_block(hip):
     cfg, sd, ids = L.batch_model()
     got = {}
     for block in (64, 0):
-        with _Env(SD_PREFILL_ATTN=1, SD_PREFILL_ATTN_BLOCK=block):
+        with tunables(SD_PREFILL_ATTN=1, SD_PREFILL_ATTN_BLOCK=block):
             m = hip.engine.SpecDecModel.from_state_dict(cfg, P.cast_sd(sd, torch.bfloat16), dtype=torch.bfloat16)
             sess = []
             for i in range(3):

@@ -11,7 +11,6 @@ The fp32 pairs of L1 / L2 reach entry A in the loop (V = 8192, a workspace) but 
 for 16-bit models only.  Entry B under per-request parameters is covered by K2 at kernel level and by L5 in the loop: a bf16
 pair whose fused tail (tile maxima in the passes that allow them) must equal SD_BATCH_FUSED_TAIL=0 bit for bit."""
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -21,6 +20,7 @@ import oracle
 import sampler_rows as R
 from golden_io import logits_row
 from philox_replay import PhiloxOracleNoise
+from sd_env import tunables
 from test_gpu_native_parity import BF16_CFG, DETAILS_KEYS, _st
 from test_gpu_sampler_routes import CL_INTS, check_probs, launch
 from test_gpu_spec_queue import _models, _prompts
@@ -389,9 +389,8 @@ def test_bf16_fused_tail_equals_the_dense_tail_under_per_request_parameters(hip,
     Under the same seeds the fused tail must equal SD_BATCH_FUSED_TAIL=0 - no tile maxima, the dense accept - bit for bit."""
     cfg, dm, tm = _bf16_pair()
     runs = {}
-    try:
-        for mode in ("0", "1"):
-            os.environ["SD_BATCH_FUSED_TAIL"] = mode
+    for mode in ("0", "1"):
+        with tunables(SD_BATCH_FUSED_TAIL=mode):
             if entry == "queue_mixed":
                 prompts = [pf.cuda() for pf in _prompts(cfg.vocab_size, Q_LENS, 1000)]
                 # (eligible rows first: the first passes run on tile maxima, later ones lose them to a k == 0 neighbour)
@@ -403,8 +402,6 @@ def test_bf16_fused_tail_equals_the_dense_tail_under_per_request_parameters(hip,
                 triples = P_ELIGIBLE[:4] if entry == "batch_eligible" else P[:4]
                 runs[mode] = hip.S.speculative_sampling_batch(prompts, dm, tm, -1, None, 16, gamma=4, details=True,
                                                               seeds=[77, 78, 79, 80], **_columns(triples))
-    finally:
-        os.environ.pop("SD_BATCH_FUSED_TAIL", None)
     (o0, d0), (o1, d1) = runs["0"], runs["1"]
     for a, b, da, db in zip(o0, o1, d0, d1):
         assert torch.equal(a, b), (a, b)

@@ -18,7 +18,6 @@ Against STABLE_TIES = False (the reference's unstable sort) the result must be e
 bits of every probability and the helper's exact multiset comparison cannot apply, through the oracle's own pair
 (stable vs unstable) on the CPU - tests/test_sampler_rows_cpu.py - plus the bars above against the stable result."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -26,6 +25,7 @@ import torch
 
 import oracle
 import sampler_rows as R
+from sd_env import tunables
 from test_gpu_parity import assert_rows_equal_up_to_tied_logits
 
 pytestmark = pytest.mark.gpu
@@ -590,12 +590,9 @@ def test_exact_ties_through_a_real_head(hip, arch, kp, capsys, monkeypatch):
     prompts[0] = prompt
     seeds = [4100 + i for i in range(6)]
     runs = {}
-    try:
-        for mode in ("0", "1"):
-            os.environ["SD_BATCH_FUSED_TAIL"] = mode
+    for mode in ("0", "1"):
+        with tunables(SD_BATCH_FUSED_TAIL=mode):
             runs[mode] = hip.S.speculative_sampling_batch(prompts, dm, tm, -1, None, 24, details=True, seeds=seeds, **kw)
-    finally:
-        os.environ.pop("SD_BATCH_FUSED_TAIL", None)
     (o0, d0), (o1, d1) = runs["0"], runs["1"]
     hit = 0
     for x0, x1, e0, e1, pr in zip(o0, o1, d0, d1, prompts):

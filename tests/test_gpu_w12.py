@@ -2,13 +2,13 @@
 (tests/w12_format.py), and the forward pass that streams records against the same model streaming bf16 - bit for bit, since
 the records are decoded to the bf16 tile before the MFMA and nothing else changes."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import w12_format as F
+from sd_env import tunables
 from llmspeculativesampling_amd.config import ModelConfig
 
 pytestmark = pytest.mark.gpu
@@ -106,15 +106,8 @@ def _run(hip, w12, transform):
     after each.  hidden 1024 is a width the small-model path (<= 4 rows, hidden <= 2048, bf16 weights only) would take:
     SD_SMALL_PATH=0, sampled when the session is created, keeps the 1..4-row passes on the route of the 13b target."""
     m = hip.engine.SpecDecModel.synthetic(CFG, seed=21, dtype=torch.bfloat16, max_pos=128, transform=transform, w12=w12)
-    old = os.environ.get("SD_SMALL_PATH")
-    os.environ["SD_SMALL_PATH"] = "0"
-    try:
+    with tunables(SD_SMALL_PATH="0"):
         ses = m.new_session(128)
-    finally:
-        if old is None:
-            del os.environ["SD_SMALL_PATH"]
-        else:
-            os.environ["SD_SMALL_PATH"] = old
     ids = torch.from_numpy(np.random.default_rng(8).integers(3, CFG.vocab_size, size=128)).to(torch.int32).cuda()
     outs, counts, pos = [], [], 0
     for n in (PREFILL,) + PASSES + (WIDE,):

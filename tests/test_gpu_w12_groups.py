@@ -4,13 +4,13 @@ repairs its escapes behind one branch, so what is planted (tests/w12_groups.py) 
 and 6, in the first and the last group of a wave's range, next to groups without, in the tails, at the first and the last
 element of a tile and twice in one lane - in gate/up of layer 0, QKV of layer 1 and down of layer 0.  The plan is checked on
 the host (no GPU); on the GPU the forward pass on records must equal the bf16 route on the same weights bit for bit."""
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import w12_groups as G
+from sd_env import tunables
 
 # intermediate 2816: the harness of test_gpu_w12.py (down: 4 slabs of 22 k-steps, waves of 6 = a group and a tail of two);
 # 2560: 3 slabs of 27 / 27 / 26 k-steps, waves of 7 | 6 | 5 = tails of three, two and one
@@ -54,15 +54,8 @@ def _run(hip, inter, w12):
     p = G.plan(inter)
     m = hip.engine.SpecDecModel.synthetic(p.cfg, seed=G.SEED, dtype=torch.bfloat16, max_pos=128, method="numpy",
                                           transform=p.transform, w12=w12)
-    old = os.environ.get("SD_SMALL_PATH")
-    os.environ["SD_SMALL_PATH"] = "0"
-    try:
+    with tunables(SD_SMALL_PATH="0"):
         ses = m.new_session(128)
-    finally:
-        if old is None:
-            del os.environ["SD_SMALL_PATH"]
-        else:
-            os.environ["SD_SMALL_PATH"] = old
     ids = torch.from_numpy(np.random.default_rng(8).integers(3, p.cfg.vocab_size, size=128)).to(torch.int32).cuda()
     outs, counts, pos = [], [], 0
     for n in (PREFILL,) + PASSES:

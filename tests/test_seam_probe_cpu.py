@@ -33,7 +33,7 @@ def test_route_mirrors_match_the_sources():
     assert "return tab.n_rows <= 8 && c.hidden % 1024 == 0 && c.hidden <= 8192;" in src
     assert "tab.n_rows > SMALL_MAX_ROWS || tab.n_logit_rows > SMALL_MAX_ROWS" in src
     # small_split, which seam_probe.gemm_slabs(small=True) restates: the one-row plan, at most 16 slabs
-    assert "gemm_split(N, K, 1, S_out, ksp_out);" in src
+    assert "gemm_split(t, N, K, 1, S_out, ksp_out);" in src
     assert "if (*S_out > 16) { *ksp_out = (KS + 15) / 16; *S_out = (KS + *ksp_out - 1) / *ksp_out; }" in src
     assert [S.rn_threads(h) for h in (96, 128, 256, 1024, 4096, 8192)] == [64, 64, 64, 128, 512, 1024]
     # the register-group edge is a column of the row only where the second group is used at all

@@ -21,9 +21,6 @@ def main():
     m = SpecDecModel.synthetic(cfg, seed=1, dtype=torch.bfloat16)
     ctx = 192
     toks = torch.from_numpy(np.random.default_rng(0).integers(3, cfg.vocab_size, size=ctx + 256)).to(torch.int32).cuda()
-    ses = m.new_session(ctx + 260)
-    for lo in range(0, ctx, 64):
-        ses.forward(toks[lo:lo + 64], 0)
     variants = [v for v in os.environ.get("VARIANTS", "auto").split(",")]     # tiles per wave; auto = the engine's policy
     for M in Ms:
         for v in variants:
@@ -31,6 +28,9 @@ def main():
                 os.environ.pop("SD_GEMM_NTW", None)
             else:
                 os.environ["SD_GEMM_NTW"] = v
+            ses = m.new_session(ctx + 260)                            # (a session keeps the tunables of its creation)
+            for lo in range(0, ctx, 64):
+                ses.forward(toks[lo:lo + 64], 0)
             for _ in range(2):
                 ses.rollback(ctx)
                 ses.forward(toks[ctx:ctx + M], min(M, 5))
