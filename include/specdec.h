@@ -485,6 +485,14 @@ int sd_session_forward(sd_session *s, const int32_t *tokens, int n_new, int pos0
 int sd_session_forward_tree(sd_session *s, const int32_t *tokens, const int32_t *positions, const uint64_t *masks, int n,
                             int base_len, float *logits_out, long ld_logits, void *stream);
 int sd_session_compact_kv(sd_session *s, int base_len, const int32_t *idx_dev, int k, void *stream);
+/* The tree forward level by level: tokens / positions / masks describe all n nodes as above, and the rows of THIS call are
+ * the nodes [first, n).  Their K / V rows land at arena slots base_len + first .. base_len + n - 1, their masks still index
+ * all nodes: through the mask bits a row attends to the earlier nodes j < first that previous calls of the same tree left
+ * at slot base_len + j (the caller's promise; nothing checks it).  Logits come out for the LAST n_logits rows of the call
+ * (0: no head; logits_out may then be NULL), <= 64.  first == 0 with n_logits == n is sd_session_forward_tree, launch for
+ * launch.  A draft grows its tree with one call per level and never forwards a node twice. */
+int sd_session_forward_tree_from(sd_session *s, const int32_t *tokens, const int32_t *positions, const uint64_t *masks,
+                                 int first, int n, int base_len, int n_logits, float *logits_out, long ld_logits, void *stream);
 
 /* Single-stream decode / verify forwards of a 16-bit model run two kinds of launches whose workgroups wait for each other
  * on device-side counters: attention + O projection (csrc/fused_kernels.h) and the k-split down projection with the
@@ -703,6 +711,91 @@ size_t sd_spec_multi_block_bytes(int width, int gamma);
 int sd_spec_multi_generate(const sd_multi_replica *reps, int width, int gamma, int seq_cap, const sd_sampling *sampling,
                            uint64_t random_seed, const float *r_const, const sd_spec_scratch *scratch, void *dev_block,
                            void *host_block, sd_seq_state *seq, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Token-tree speculative sampling (SpecInfer's multi-step verification with children drawn without replacement, as in
+ * recursive speculative decoding; no counterpart in the reference).  One target pass verifies a TREE of draft tokens and
+ * the output stays distributed exactly as the target's own sampling.  DESIGN.md, "Token-tree speculative sampling".
+ *
+ * Shape: branching = (b_1 .. b_D), 1 <= b_d <= 8.  Node 0 is the last emitted token (the root); every node of level d - 1
+ * has b_d child slots; nodes are numbered breadth first (level by level, a parent's children consecutive), so a parent's id
+ * is below its children's and the nodes with children are ids 0 .. P - 1.  n = 1 + b_1 + b_1 b_2 + ... <= 64 nodes.
+ * sd_tree_topology_fill computes all of it on the host (SD_ERR_INVALID for a depth outside 1..63, a factor outside 1..8,
+ * more than 64 nodes); it depends on `branching` alone, only the tokens vary.
+ *
+ * Draw (sd_tree_draw, one workgroup per parent row): the children of parent u are the b tokens with the largest keys
+ * q_u[t] / e[t] (fp32 division) among the tokens with q_u[t] > 0, e ~ Exp(1) one noise row per parent, listed in descending
+ * key order, the lower token id first among equal keys: sequential sampling without replacement from q_u.  A slot past the
+ * number of tokens with mass is absent: token -1, and so is every slot of a parent that is absent itself (parent_tok[row]
+ * < 0; parent_tok may be NULL).  q: `rows` normalised rows, stride ld; row r writes tok_out[r * out_stride .. + b).  Noise:
+ * row r of exp_noise (stride ld_noise), or NULL for Philox (seed, draw_index + r).
+ *
+ * Accept walk (sd_tree_accept, one workgroup, one launch for the whole tree).  p: the target's normalised rows of all n
+ * nodes, q: the draft's rows of the nodes with children, both by node id with stride ld; tokens: device int32[n].  Start at
+ * u = 0, p' = p_u, q' = q_u.  For the children x_1 .. x_b of u in order, absent ones skipped: draw r uniform in [0,1);
+ * accept x_i iff r < min(1, p'[x_i] / q'[x_i]) (fp32 division; a NaN ratio rejects).  On accept the walk descends: u becomes
+ * that child and p', q' restart from its rows.  On reject p' <- max(p' - q', 0) / sum, then q'[x_i] <- 0, q' <- q' / sum q'
+ * (fp32, in `workspace`, 2 * V device floats; a residual without mass leaves p' as it is and sets flags bit 0).  The walk
+ * ends when every child of u is rejected - the final token is drawn from the current p' - or at a leaf - the final token is
+ * the bonus draw from the target's row there.  Final draw: argmax p'[t] / e[t] over p'[t] > 0, lowest id on ties.
+ * Noise order: the k-th accept test of the walk (k = 0, 1, ...; at most n - 1) reads r[k], or Philox uniform (seed,
+ * draw_uniform + k) when r is NULL; the final draw reads exp_noise[t], or Philox Exp (seed, draw_final) when it is NULL.
+ * Result block (device): depth = accepted children a; path[0..a] = the kept node ids (path[0] = 0), tokens[j] = the token of
+ * path[j]; next_token (-1 on error); n_uniform = accept tests made; flags: bit 0 a residual had no mass, bit 1 'prob error'
+ * (the final row holds a negative / NaN / Inf entry or no mass), bit 2 the walk ended at a leaf (bonus) - else the final
+ * token is a residual draw -, bit 3 one of the n_err device words err_flags was set.  path_idx (device int32[64] or NULL)
+ * receives path[0..a] as the index list sd_session_compact_kv takes; next_root (device int32 or NULL; may be tokens itself)
+ * receives the final token, the root of the next tree.  Neither entry synchronises. */
+#define SD_TREE_MAX_NODES 64
+#define SD_TREE_MAX_BRANCH 8
+typedef struct {
+    int32_t n, depth;                       /* nodes, levels D */
+    int32_t branching[64], level_start[64]; /* b_d at [d - 1]; first node id of level d at [d] */
+    int32_t parent[64], level[64], child0[64], n_child[64];   /* per node; n_child 0 and child0 0 for a leaf */
+} sd_tree_topology;
+typedef struct {
+    int32_t depth, next_token, flags, n_uniform;
+    int32_t path[64], tokens[64];
+} sd_tree_result;
+int sd_tree_topology_fill(const int32_t *branching, int depth, sd_tree_topology *out);
+int sd_tree_draw(const float *q, int rows, int V, long ld, int b, const int32_t *parent_tok, const float *exp_noise,
+                 long ld_noise, uint64_t philox_seed, uint64_t draw_index, int32_t *tok_out, int out_stride, void *stream);
+int sd_tree_accept(const sd_tree_topology *topo, int32_t *tokens, const float *p, const float *q, long ld, int V,
+                   float *workspace, const float *r, const float *exp_noise, uint64_t philox_seed, uint64_t draw_uniform,
+                   uint64_t draw_final, sd_tree_result *res, int32_t *path_idx, int32_t *next_root, const int *err_flags,
+                   int n_err, void *stream);
+/* The whole loop, single stream, device Philox, no interpreter between iterations.  The caller has fed the prompt but its
+ * last token to both sessions (seq->draft_len == seq->target_len == seq->len - 1) and put that token into dev->tokens[0].
+ * Arena invariant: at the top of every iteration both arenas hold exactly the len - 1 positions in front of the root.
+ * An iteration is
+ *   D draft calls of sd_session_forward_tree_from, one per level d = 0 .. D - 1 (the level's nodes only), each followed by
+ *     sd_norm_probs of the level's logit rows into q_rows and sd_tree_draw of their children into dev->tokens;
+ *   one target sd_session_forward_tree over all n nodes and sd_norm_probs of its n rows into p_rows;
+ *   sd_tree_accept; one async copy of the result block to res_host and one stream wait;
+ *   sd_session_compact_kv of the kept path on both arenas (the draft's: without the leaf when the walk ended at one - the
+ *     draft never forwards the leaf level - whose K / V row a one-row draft forward without logits then appends);
+ *   the token append and speculative_sampling's EOS rule (the loop stops at a new EOS, the caller cuts).
+ * Philox order of an iteration that starts at draw index w (P = nodes with children): parent u's noise row w + u; accept
+ * test k w + P + k; the final draw w + P + n - 1; the next iteration starts at w + P + n whatever was accepted.
+ * dev: the two sessions; tokens device int32[64]; q_rows / p_rows device [64][sampling->ld] floats; workspace 2 * V floats;
+ * err_words 128 device ints, zeroed by the caller (node u's draft norm word at [u], its target norm word at [64 + u]);
+ * path_idx device int32[64]; the device result block and its pinned-host copy.  seq: sd_seq_state as in sd_spec_generate;
+ * acc_len_out[i] = accepted depth of iteration i, draft_ms_out / target_ms_out HIP-event times of the two phases, p_at_out
+ * / q_at_out are not written; err 1 = 'prob error', 2 = 'norm logits error'.  Refused with SD_ERR_INVALID before anything
+ * is written or launched: a NULL block or pointer, a bad shape (sd_tree_topology_fill's rules), temperature 0, V differing
+ * from a model's vocabulary, cache lengths other than len - 1, a session whose max_rows is below the tree's widest call,
+ * a tensor-parallel or grammar-carrying session. */
+typedef struct {
+    sd_session *draft, *target;
+    int32_t *tokens;
+    float *q_rows, *p_rows, *workspace;
+    int *err_words;
+    int32_t *path_idx;
+    sd_tree_result *res_dev, *res_host;
+} sd_tree_stream;
+int sd_tree_generate(const sd_tree_stream *dev, const int32_t *branching, int depth, const sd_sampling *sampling,
+                     const sd_spec_scratch *scratch, sd_seq_state *seq, void *stream);
+
 /* Autoregressive sampling (reference autoregressive_sampling.py:9-61) of up to 16 independent streams in lock-step, no
  * interpreter between steps.  Per step: the uncached rows seq[cache_len .. len) of every stream that is not done go through
  * ONE sd_batch_forward; one sd_norm_batch with sample = 1 (on the head's tile maxima where the lock-step draft steps use

@@ -197,6 +197,24 @@ SD_LOOKUP_MAX_NGRAM = 8                                  # the longest key the p
 LOGPROB_SLICE, LOGPROB_STREAMS = 17, 16                  # sd_logprob_block: 16 streams x 17 floats, device and pinned host
 
 
+class SdTreeTopology(C.Structure):                     # sd_tree_topology_fill's view of a branching tuple (<= 64 nodes)
+    _fields_ = [("n", C.c_int32), ("depth", C.c_int32)] + [(f, C.c_int32 * 64) for f in ("branching", "level_start", "parent", "level",
+                                                                                          "child0", "n_child")]
+
+
+class SdTreeResult(C.Structure):                        # what sd_tree_accept leaves
+    _fields_ = [("depth", C.c_int32), ("next_token", C.c_int32), ("flags", C.c_int32), ("n_uniform", C.c_int32),
+                ("path", C.c_int32 * 64), ("tokens", C.c_int32 * 64)]
+
+
+class SdTreeStream(C.Structure):                        # the device side of sd_tree_generate's one stream
+    _fields_ = [(f, C.c_void_p) for f in ("draft", "target", "tokens", "q_rows", "p_rows", "workspace", "err_words", "path_idx",
+                                          "res_dev", "res_host")]
+
+
+SD_TREE_MAX_NODES, SD_TREE_MAX_BRANCH = 64, 8
+
+
 class SdBatchItem(C.Structure):
     _fields_ = [("session", C.c_void_p), ("seq", C.c_void_p), ("pos0", C.c_int32), ("n_new", C.c_int32),
                 ("n_logits", C.c_int32)]
@@ -245,6 +263,7 @@ C_STRUCTS = {"sd_accept_result": SdAcceptResult, "sd_norm_row": SdNormRow, "sd_r
              "sd_penalty_item": SdPenaltyItem, "sd_penalty_block": SdPenaltyBlock, "sd_logit_edit": SdLogitEdit,
              "sd_logit_edit_item": SdLogitEditItem, "sd_logit_edit_block": SdLogitEditBlock, "sd_loop_opts": SdLoopOpts,
              "sd_lookup_item": SdLookupItem, "sd_grammar": SdGrammar, "sd_grammar_item": SdGrammarItem,
+             "sd_tree_topology": SdTreeTopology, "sd_tree_result": SdTreeResult, "sd_tree_stream": SdTreeStream,
              "sd_model_config": SdModelConfig,
              "sd_gemm_route_info": SdGemmRouteInfo, "sd_model_weights": SdModelWeights}
 
@@ -303,6 +322,11 @@ SYMBOLS = [
     ("sd_session_forward", _I, [_VP, _VP, _I, _I, _I, _VP, _L, _VP]),
     ("sd_session_forward_tree", _I, [_VP, _VP, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), _I, _I, _VP, _L, _VP]),
     ("sd_session_compact_kv", _I, [_VP, _I, _VP, _I, _VP]),
+    ("sd_session_forward_tree_from", _I, [_VP, _VP, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), _I, _I, _I, _I, _VP, _L, _VP]),
+    ("sd_tree_topology_fill", _I, [C.POINTER(C.c_int32), _I, _P(SdTreeTopology)]),
+    ("sd_tree_draw", _I, [_VP, _I, _I, _L, _I, _VP, _VP, _L, _U64, _U64, _VP, _I, _VP]),
+    ("sd_tree_accept", _I, [_P(SdTreeTopology), _VP, _VP, _VP, _L, _I, _VP, _VP, _VP, _U64, _U64, _U64, _VP, _VP, _VP, _VP, _I, _VP]),
+    ("sd_tree_generate", _I, [_P(SdTreeStream), C.POINTER(C.c_int32), _I, _P(SdSampling), _P(SdSpecScratch), _P(SdSeqState), _VP]),
     ("sd_session_fused_status", _I, [_VP, _VP]),
     ("sd_session_test_skew_wait", _I, [_VP, _I]),
     ("sd_session_ao_stamps", _I, [_VP, _VP, _I]),

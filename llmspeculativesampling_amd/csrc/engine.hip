@@ -2005,33 +2005,53 @@ extern "C" int sd_session_forward(sd_session *s, const int32_t *tokens, int n_ne
 // the nodes of a draft token tree.  Node i has token tokens[i], position positions[i] (its depth: RoPE / learned
 // position), sees all `base_len` cached positions and the nodes whose bit is set in masks[i] (ancestors + itself, bit j
 // = node j, j <= i), and its K / V rows are appended at arena slot base_len + i.  Logits come out for all n nodes.
-extern "C" int sd_session_forward_tree(sd_session *s, const int32_t *tokens, const int32_t *positions, const uint64_t *masks,
-                                       int n, int base_len, float *logits_out, long ld_logits, void *stream) {
-    SD_REQUIRE(s && tokens && positions && masks && logits_out, "sd_session_forward_tree: null argument");
-    SD_REQUIRE(n >= 1 && n <= SD_MAX_TREE && base_len >= 0, "sd_session_forward_tree: 1..%d nodes", SD_MAX_TREE);
-    if (n > s->max_rows || base_len + n > s->max_seq) {
-        sd_set_error("sd_session_forward_tree: %d nodes after %d positions exceed max_rows %d / max_seq %d", n, base_len,
-                     s->max_rows, s->max_seq);
+// ... and the same pass level by level (first > 0): the rows of the call are the nodes [first, n), row m is node first + m
+// (tab.tree_first); the masks index all nodes, and the earlier ones lie where previous calls left them.  `who` names the entry.
+static int forward_tree_rows(const char *who, sd_session *s, const int32_t *tokens, const int32_t *positions, const uint64_t *masks,
+                             int first, int n, int base_len, int n_logits, float *logits_out, long ld_logits, void *stream) {
+    SD_REQUIRE(s && tokens && positions && masks && (logits_out || n_logits == 0), "%s: null argument", who);
+    SD_REQUIRE(n >= 1 && n <= SD_MAX_TREE && base_len >= 0, "%s: 1..%d nodes", who, SD_MAX_TREE);
+    SD_REQUIRE(first >= 0 && first < n && n_logits >= 0 && n_logits <= n - first, "%s: rows %d..%d of %d nodes, %d logit rows", who,
+               first, n, n, n_logits);
+    const int rows = n - first;
+    if (rows > s->max_rows || base_len + n > s->max_seq) {
+        sd_set_error("%s: %d nodes after %d positions exceed max_rows %d / max_seq %d", who, rows, base_len, s->max_rows, s->max_seq);
         return SD_ERR_CAPACITY;
     }
     RowTab tab = {};
-    tab.n_rows = n;
+    tab.n_rows = rows;
     tab.n_streams = 1;
-    tab.n_logit_rows = n;
+    tab.n_logit_rows = n_logits;
     tab.tree = 1;
     tab.tree_base = base_len;
-    bind_stream(tab, 0, s, tokens);              // tree rows: the token of node i is tokens[i] (tab_tok)
+    tab.tree_first = first;
+    bind_stream(tab, 0, s, tokens + first);      // tree rows: the token of node first + m is tokens[first + m] (tab_tok)
     for (int i = 0; i < n; ++i) {
-        SD_REQUIRE(positions[i] >= 0 && positions[i] < s->m->cfg.max_pos, "sd_session_forward_tree: position %d out of range", positions[i]);
-        SD_REQUIRE((masks[i] >> i) & 1ull, "sd_session_forward_tree: node %d must see itself", i);
-        SD_REQUIRE(i == 63 || (masks[i] >> (i + 1)) == 0, "sd_session_forward_tree: node %d sees a later node", i);
-        tab.row_pos[i] = positions[i];
-        tab.row_stream[i] = 0;
+        SD_REQUIRE(positions[i] >= 0 && positions[i] < s->m->cfg.max_pos, "%s: position %d out of range", who, positions[i]);
+        SD_REQUIRE((masks[i] >> i) & 1ull, "%s: node %d must see itself", who, i);
+        SD_REQUIRE(i == 63 || (masks[i] >> (i + 1)) == 0, "%s: node %d sees a later node", who, i);
         tab.tree_mask[i] = masks[i];
-        tab.xmap[i] = (unsigned char)i;
     }
+    for (int m = 0; m < rows; ++m) {
+        tab.row_pos[m] = positions[first + m];
+        tab.row_stream[m] = 0;
+    }
+    for (int i = 0; i < n_logits; ++i) tab.xmap[i] = (unsigned char)(rows - n_logits + i);
     finish_table(tab);
     return run_forward(s, tab, base_len + n, logits_out, ld_logits, nullptr, nullptr, stream);
+}
+
+extern "C" int sd_session_forward_tree(sd_session *s, const int32_t *tokens, const int32_t *positions, const uint64_t *masks,
+                                       int n, int base_len, float *logits_out, long ld_logits, void *stream) {
+    SD_REQUIRE(logits_out, "sd_session_forward_tree: null argument");
+    return forward_tree_rows("sd_session_forward_tree", s, tokens, positions, masks, 0, n, base_len, n, logits_out, ld_logits, stream);
+}
+
+extern "C" int sd_session_forward_tree_from(sd_session *s, const int32_t *tokens, const int32_t *positions, const uint64_t *masks,
+                                            int first, int n, int base_len, int n_logits, float *logits_out, long ld_logits,
+                                            void *stream) {
+    return forward_tree_rows("sd_session_forward_tree_from", s, tokens, positions, masks, first, n, base_len, n_logits, logits_out,
+                             ld_logits, stream);
 }
 
 // Gather-compaction of the KV arena after a tree verify (reference kvcache_model.py:326-353 rollback_tree_attention,
@@ -2273,6 +2293,7 @@ extern "C" int sd_gemm_bf16(const void *w_packed, const void *x, int x_tiled, in
 
 // ---- the native decode loops (sd_spec_*, sd_multi_adopt): same translation unit, they use sd_session and the forwards above
 #include "spec_loops.h"
+#include "tree_loop.h"
 
 // ---- the norm-on-load and the finishing GEMM on 12-bit weight records (forward declarations above launch_gemm_xn's users).
 // Last in the file: their kernels are the last of the code object.

@@ -49,6 +49,10 @@ struct RowTab {
     int tree, tree_base;
     unsigned long long tree_mask[SD_MAX_TREE];
     int kv_fp8;                                     // the arenas hold OCP fp8 e4m3 (1 byte per element) instead of T
+    int tree_first;                                 // tree verify level by level (sd_session_forward_tree_from): the rows are the
+                                                    // nodes tree_first .. tree_first + n_rows - 1 - row m is node tree_first + m, at
+                                                    // slot tree_base + tree_first + m - and the earlier nodes already lie at their
+                                                    // slots; tree_mask[] is indexed by node.  0 for every whole-tree pass
     const float *kv_scale[SD_MAX_STREAMS];          // fp8: per (layer, k|v, kv head) scales [L][2][Hkv], stored fp8(x * (1 / scale)), read fp8 * scale
     // attention groups: <= ATT_TQ consecutive rows of one stream (first row, count, position of the first row, stream)
     int grp_row0[SD_MAX_GROUPS], grp_n[SD_MAX_GROUPS], grp_pos[SD_MAX_GROUPS], grp_stream[SD_MAX_GROUPS];
@@ -84,7 +88,7 @@ __device__ __forceinline__ int tab_tok(const RowTab &t, int m, int pos) {
     return t.tree ? t.tok_base[0][m] : t.tok_base[tab_stream(t, m)][pos];
 }
 // arena slot row m's K / V rows are written to: its position, or (tree verify) the next free slot
-__device__ __forceinline__ int tab_slot(const RowTab &t, int m) { return t.tree ? t.tree_base + m : tab_pos(t, m); }
+__device__ __forceinline__ int tab_slot(const RowTab &t, int m) { return t.tree ? t.tree_base + t.tree_first + m : tab_pos(t, m); }
 
 enum { NORM_RMS = 0, NORM_LN = 1 };
 enum { RES_PRE = 0, RES_POST = 1, RES_NONE = 2 };   // norm after the residual feeds the next GEMM / replaces x / no norm
@@ -649,7 +653,8 @@ __global__ void embed_kernel(RowTab tab, const T *__restrict__ table, int dim, c
     const int row = blockIdx.x;
     const int pos = tab_pos(tab, row);
     // ids are validated on the host (IndexError, as nn.Embedding raises); the clamp only keeps a caller that goes
-    // straight to the C ABI with a bad id from reading outside the table
+    // straight to the C ABI with a bad id from reading outside the table.  One regular path relies on it too: the tree loop
+    // (tree_loop.h) forwards the absent slots of a draft tree, token -1, as token 0 and ignores their rows
     const int tok = min(max(tab_tok(tab, row, pos), 0), vocab - 1);
     const T *src = table + (size_t)tok * dim;
     const T *ps = pos_table ? pos_table + (size_t)(pos + pos_off) * dim : nullptr;
@@ -1043,7 +1048,7 @@ __device__ __forceinline__ void attn_body(const T *__restrict__ qbuf, const RowT
     // tree verify: every row may see all tab.tree_base cached keys and, among the tree rows of this call, those in its
     // mask; the causal arithmetic below then only bounds the key range (all tree rows), visibility comes from `vis`
     constexpr bool tree = TREE;                                   // (a template flag: the causal path pays nothing for it)
-    const int s_all = tree ? tab.tree_base + tab.n_rows : pos0 + r0 + nr;   // keys visible to the last row of the group
+    const int s_all = tree ? tab.tree_base + tab.tree_first + tab.n_rows : pos0 + r0 + nr;   // keys visible to the last row of the group
     const int chunk = nsplit > 1 ? (((s_all + nsplit - 1) / nsplit + 15) & ~15) : s_all;
     const int kb = nsplit > 1 ? bz * chunk : 0;
     const int s_hi = max(0, min(s_all, kb + chunk) - kb);
@@ -1051,7 +1056,7 @@ __device__ __forceinline__ void attn_body(const T *__restrict__ qbuf, const RowT
     auto vis = [&](int t, int s) -> bool {                        // may row t of the group see local key s?
         if (!tree) return s <= vis0 + t;
         const int g = s + kb - tab.tree_base;                     // index among the tree rows (< 0: a cached key)
-        return g < 0 || ((tab.tree_mask[min(r0 + t, SD_MAX_TREE - 1)] >> g) & 1ull);
+        return g < 0 || ((tab.tree_mask[min(tab.tree_first + r0 + t, SD_MAX_TREE - 1)] >> g) & 1ull);
     };
     // (an empty chunk - split attention past the visible keys - reads from the head's first key: loads are never branched
     //  around, see below, so their addresses must be valid)

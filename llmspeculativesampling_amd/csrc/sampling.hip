@@ -1706,3 +1706,5 @@ extern "C" int sd_accept_batch(const sd_accept_item *items, int n_items, long ld
     SD_LAUNCH_CHECK();
     return SD_OK;
 }
+
+#include "tree_kernels.h"                                       // sd_tree_topology_fill, sd_tree_draw, sd_tree_accept

@@ -12,6 +12,7 @@ from .batch import (speculative_sampling_batch, speculative_sampling_queue, spec
 from .grammar import TokenGrammar
 from .lookup import prompt_lookup_sampling, prompt_lookup_sampling_batch
 from .multi import multi_speculative_sampling
+from .tree import tree_speculative_sampling
 from .beam import beam_speculative_sampling_v2
 from .kvcache_model import KVCacheModel
 from .utils import (norm_logits, sample, max_fn, top_k_top_p_filter, get_seq_att_mask, get_accept_prob, update_large_prob,
@@ -38,7 +39,7 @@ random_width_beam_sampling = _out_of_scope("random_width_beam_sampling", "autore
 
 __all__ = ["speculative_sampling", "speculative_sampling_v2", "autoregressive_sampling", "multi_speculative_sampling",
            "beam_speculative_sampling", "BiLD_sampling", "mjsd_speculative_sampling", "random_width_beam_sampling",
-           "beam_speculative_sampling_v2",
+           "beam_speculative_sampling_v2", "tree_speculative_sampling",
            "speculative_sampling_batch", "speculative_sampling_queue", "speculative_sampling_queue_shared",
            "speculative_sampling_queue_logprobs", "speculative_sampling_queue_requests", "speculative_sampling_queue_edits",
            "speculative_sampling_queue_grammar", "TokenGrammar", "autoregressive_sampling_batch", "prompt_lookup_sampling", "prompt_lookup_sampling_batch", "KVCacheModel", "norm_logits", "sample", "max_fn", "top_k_top_p_filter"]
