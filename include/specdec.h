@@ -464,6 +464,48 @@ int sd_prefill_attn_plan(int head_dim, int s_max, int block_keys, int *kernel, i
  * three sweeps are slower than attn_kernel's split keys - and where attn_kernel's splits cannot hold the pass at all; a forced
  * block always takes it.  cus = 0: the device's CU count (256 without a device). */
 int sd_prefill_attn_route(int head_dim, int n_heads, int n_rows, int s_max, int block_keys, int cus, int *kernel);
+/* attn_kernel's key splits (host only; the function the launch path calls): a pass of n_groups row groups (<= 8 rows each,
+ * at most 32) whose last row sees s_max keys runs *nsplit workgroups per (head, group), each over *chunk_keys keys of s_max
+ * (every group cuts its own visible keys the same way), with *s_cap score columns and *lds_bytes of dynamic LDS per
+ * workgroup; more than 160 KiB - 512: the pass does not fit (SD_ERR_CAPACITY at the launch).  Reads SD_ATTN_SPLIT_KEYS and
+ * SD_ATTN_KEYS_PER_SPLIT at the call.  Any out pointer may be NULL.  SD_ERR_INVALID for a head_dim outside {16,32,64,128},
+ * s_max < 1 or n_groups outside 1..32. */
+int sd_attn_split(int head_dim, int s_max, int n_groups, int *nsplit, int *chunk_keys, int *s_cap, long *lds_bytes);
+
+/* The route of one forward pass is a function of (model config, planner tunables, pass) and is decided once, before the
+ * first launch.  sd_forward_route answers it on the host - no device, no session - for ONE single-stream pass as
+ * sd_session_forward builds it, by the very functions the launch path calls, under the SD_* tunables of the environment at
+ * the call (a session plans with those of its creation). */
+typedef struct sd_pass_desc {
+    int32_t n_rows, pos0;           /* the pass: n_rows new rows at positions pos0 .. (its last row sees pos0 + n_rows keys) */
+    int32_t n_logit_rows;           /* ... the last n_logit_rows of them feed the lm_head */
+    int32_t kv_fp8;                 /* 1: the session's arena holds fp8 (sd_session_set_kv_fp8) */
+    int32_t tp;                     /* 1: the session is bound to a tensor-parallel group (sd_session_set_tp) */
+    int32_t max_rows;               /* what sd_session_create was given: clamped to sd_model_max_rows, it sizes the k-slab scratch */
+    int32_t cus;                    /* CUs to plan for; 0: the device's (256 without a device) */
+} sd_pass_desc;
+enum { SD_ATTN_KERNEL = 0, SD_ATTN_OPROJ = 1, SD_ATTN_PREFILL = 2 };   /* attn_kernel (+ combine) | fused attention + O | matrix cores */
+typedef struct sd_gemm_cut {
+    int32_t kind, S, ksp;           /* SD_GEMM_*, k-slabs, k-steps per slab (sd_gemm_route_info) */
+} sd_gemm_cut;
+typedef struct sd_forward_route_info {
+    int32_t small;                  /* the small-model decode path */
+    int32_t embed_qkv;              /* the embedding and the first pre-norm ride the layer-0 QKV launch */
+    int32_t attn;                   /* SD_ATTN_* */
+    int32_t seam_o, seam_d;         /* norm on load may open at the attention -> MLP seam / the down -> next QKV seam */
+    int32_t rn_threads;             /* blockDim of residual_norm_kernel */
+    int32_t nsplit, chunk_keys, s_cap;  /* SD_ATTN_KERNEL / SD_ATTN_OPROJ: as sd_attn_split reports them (else 0) */
+    int32_t prefill_kernel, prefill_block;  /* SD_ATTN_PREFILL: as sd_prefill_attn_plan reports them (else 0) */
+    sd_gemm_cut qkv, o, gu, down;   /* the per-layer GEMMs of a 16-bit model off the small path (else all 0) */
+    sd_gemm_cut head;               /* the lm_head with its row gather (16-bit model, n_logit_rows > 0) */
+    int32_t small_o_S, small_o_ksp, small_d_S, small_d_ksp;    /* small: the k-slabs of its O / down GEMMs */
+    long attn_lds;                  /* SD_ATTN_KERNEL / SD_ATTN_OPROJ: dynamic LDS of a workgroup */
+} sd_forward_route_info;
+/* A model that needs a final-norm weight (the small path does) is assumed to have one.  SD_ERR_INVALID, with a message, for a
+ * NULL argument, a config sd_model_create would refuse (or a non-positive size), n_rows outside 1..256 or past the clamped
+ * max_rows, pos0 < 0 or pos0 + n_rows > cfg->max_pos, n_logit_rows outside 0..n_rows, kv_fp8 / tp outside {0, 1}, cus < 0.
+ * Logit rows sd_session_forward would refuse for their number come back as head.kind == SD_GEMM_NONE. */
+int sd_forward_route(const sd_model_config *cfg, const sd_pass_desc *pass, sd_forward_route_info *out);
 
 /* One model forward over n_new tokens at absolute positions pos0 .. pos0+n_new-1, appending their
  * K/V rows into the arena in-kernel (replaces the per-layer torch.cat of modeling_llama.py:337-338 /

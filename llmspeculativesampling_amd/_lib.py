@@ -237,6 +237,24 @@ class SdGemmRouteInfo(C.Structure):
                                          "inst_unroll", "inst_ch", "inst_wbm", "inst_nt", "lds_bytes")] + [("part_floats", C.c_uint64)]
 
 
+SD_ATTN_KERNEL, SD_ATTN_OPROJ, SD_ATTN_PREFILL = 0, 1, 2      # sd_forward_route_info.attn
+
+
+class SdPassDesc(C.Structure):                           # one single-stream pass, as sd_forward_route takes it
+    _fields_ = [(n, C.c_int32) for n in ("n_rows", "pos0", "n_logit_rows", "kv_fp8", "tp", "max_rows", "cus")]
+
+
+class SdGemmCut(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("kind", "S", "ksp")]
+
+
+class SdForwardRouteInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("small", "embed_qkv", "attn", "seam_o", "seam_d", "rn_threads", "nsplit", "chunk_keys",
+                                         "s_cap", "prefill_kernel", "prefill_block")] + \
+               [(n, SdGemmCut) for n in ("qkv", "o", "gu", "down", "head")] + \
+               [(n, C.c_int32) for n in ("small_o_S", "small_o_ksp", "small_d_S", "small_d_ksp")] + [("attn_lds", C.c_long)]
+
+
 _VP = C.c_void_p
 _VPP = C.POINTER(C.c_void_p)
 
@@ -265,7 +283,8 @@ C_STRUCTS = {"sd_accept_result": SdAcceptResult, "sd_norm_row": SdNormRow, "sd_r
              "sd_lookup_item": SdLookupItem, "sd_grammar": SdGrammar, "sd_grammar_item": SdGrammarItem,
              "sd_tree_topology": SdTreeTopology, "sd_tree_result": SdTreeResult, "sd_tree_stream": SdTreeStream,
              "sd_model_config": SdModelConfig,
-             "sd_gemm_route_info": SdGemmRouteInfo, "sd_model_weights": SdModelWeights}
+             "sd_gemm_route_info": SdGemmRouteInfo, "sd_model_weights": SdModelWeights,
+             "sd_pass_desc": SdPassDesc, "sd_gemm_cut": SdGemmCut, "sd_forward_route_info": SdForwardRouteInfo}
 
 # every symbol include/specdec.h declares: (name, restype, argtypes)
 _F, _I, _L, _U64 = C.c_float, C.c_int, C.c_long, C.c_uint64
@@ -319,6 +338,8 @@ SYMBOLS = [
     ("sd_session_prefill_attn_blocked_launches", _I, [_VP]),
     ("sd_prefill_attn_plan", _I, [_I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long)]),
     ("sd_prefill_attn_route", _I, [_I, _I, _I, _I, _I, _I, C.POINTER(C.c_int)]),
+    ("sd_attn_split", _I, [_I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long)]),
+    ("sd_forward_route", _I, [_P(SdModelConfig), _P(SdPassDesc), _P(SdForwardRouteInfo)]),
     ("sd_session_forward", _I, [_VP, _VP, _I, _I, _I, _VP, _L, _VP]),
     ("sd_session_forward_tree", _I, [_VP, _VP, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), _I, _I, _VP, _L, _VP]),
     ("sd_session_compact_kv", _I, [_VP, _I, _VP, _I, _VP]),

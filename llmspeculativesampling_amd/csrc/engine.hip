@@ -109,21 +109,27 @@ static void copy_ptrs(std::vector<const void *> &dst, const void *const *src, in
         for (int i = 0; i < n; ++i) dst[i] = src[i];
 }
 
-extern "C" int sd_model_create(const sd_model_config *cfg, const sd_model_weights *w, sd_model **out) {
-    SD_REQUIRE(cfg && w && out, "sd_model_create: null argument");
-    SD_REQUIRE(cfg->arch == SD_ARCH_LLAMA || cfg->arch == SD_ARCH_OPT, "sd_model_create: unknown arch %d", cfg->arch);
-    SD_REQUIRE(cfg->dtype == SD_F32 || cfg->dtype == SD_BF16 || cfg->dtype == SD_F16, "sd_model_create: unknown dtype %d", cfg->dtype);
+// the geometries the engine has kernels for (sd_model_create; sd_forward_route plans no other)
+static int check_config(const char *who, const sd_model_config *cfg) {
+    SD_REQUIRE(cfg->arch == SD_ARCH_LLAMA || cfg->arch == SD_ARCH_OPT, "%s: unknown arch %d", who, cfg->arch);
+    SD_REQUIRE(cfg->dtype == SD_F32 || cfg->dtype == SD_BF16 || cfg->dtype == SD_F16, "%s: unknown dtype %d", who, cfg->dtype);
     SD_REQUIRE(cfg->head_dim == 16 || cfg->head_dim == 32 || cfg->head_dim == 64 || cfg->head_dim == 128,
-               "sd_model_create: head_dim %d not in {16,32,64,128}", cfg->head_dim);
+               "%s: head_dim %d not in {16,32,64,128}", who, cfg->head_dim);
     // a tensor-parallel shard holds n_heads / world query heads: its attention width is a fraction of hidden
     SD_REQUIRE(cfg->n_heads * cfg->head_dim <= cfg->hidden && (cfg->n_heads * cfg->head_dim) % 32 == 0,
-               "sd_model_create: n_heads*head_dim must be <= hidden and a multiple of 32");
-    SD_REQUIRE(cfg->hidden % 4 == 0 && cfg->hidden <= 8192, "sd_model_create: hidden must be a multiple of 4 and <= 8192");
-    SD_REQUIRE(cfg->n_kv_heads > 0 && cfg->n_heads % cfg->n_kv_heads == 0, "sd_model_create: bad n_kv_heads");
-    if (is16(cfg->dtype)) {
+               "%s: n_heads*head_dim must be <= hidden and a multiple of 32", who);
+    SD_REQUIRE(cfg->hidden % 4 == 0 && cfg->hidden <= 8192, "%s: hidden must be a multiple of 4 and <= 8192", who);
+    SD_REQUIRE(cfg->n_kv_heads > 0 && cfg->n_heads % cfg->n_kv_heads == 0, "%s: bad n_kv_heads", who);
+    if (cfg->dtype != SD_F32) {
         SD_REQUIRE(cfg->hidden % 32 == 0 && cfg->inter % 32 == 0 && cfg->vocab % 16 == 0 && cfg->opt_proj_dim % 32 == 0,
-                   "sd_model_create: the 16-bit paths need hidden/inter/proj %% 32 == 0 and vocab %% 16 == 0");
+                   "%s: the 16-bit paths need hidden/inter/proj %% 32 == 0 and vocab %% 16 == 0", who);
     }
+    return SD_OK;
+}
+
+extern "C" int sd_model_create(const sd_model_config *cfg, const sd_model_weights *w, sd_model **out) {
+    SD_REQUIRE(cfg && w && out, "sd_model_create: null argument");
+    if (check_config("sd_model_create", cfg) != SD_OK) return SD_ERR_INVALID;
     SD_REQUIRE(w->embed && w->lm_head && w->wqkv && w->wo && w->w_gate_up && w->w_down && w->norm1_w && w->norm2_w,
                "sd_model_create: missing weight pointers");
     sd_model *m = new sd_model();
@@ -1131,9 +1137,11 @@ static int run_gemm_fused(sd_session *s, const GemmRoute &r, const void *W, cons
 #define ATT_LDS_MAX ((size_t)160 * 1024 - 512)
 // attn_kernel's key splits for a pass of n_groups row groups whose last row sees s_max keys: the dynamic LDS of a workgroup
 // (> ATT_LDS_MAX: the pass does not fit - launch_attn's capacity error)
+// keys of one of the nsplit chunks a row group that sees s_all keys is cut into (attn_body cuts every group's own keys so)
+static int attn_chunk_keys(int s_all, int nsplit) { return nsplit > 1 ? (((s_all + nsplit - 1) / nsplit + 15) & ~15) : s_all; }
 static size_t attn_split_plan(const Tunables &t, int D, int s_max, int n_groups, int *nsplit_out, int *s_cap_out) {
     auto lds_for = [&](int nsplit, int *s_cap) {
-        const int keys = nsplit > 1 ? (((s_max + nsplit - 1) / nsplit + 15) & ~15) : s_max;
+        const int keys = attn_chunk_keys(s_max, nsplit);
         *s_cap = (int)align_up(keys, 64);
         return sizeof(float) * ((size_t)ATT_TQ * D + (size_t)(256 / (D / 8)) * ATT_TQ * D + (size_t)ATT_TQ * *s_cap);
     };
@@ -1205,8 +1213,17 @@ extern "C" int sd_prefill_attn_route(int head_dim, int n_heads, int n_rows, int 
     *kernel = route_prefill_attn(read_tunables(), head_dim, n_heads, n_rows, (n_rows + ATT_TQ - 1) / ATT_TQ, s_max, block_keys, cus);
     return SD_OK;
 }
-// The route of one forward pass: which launches it makes and how each of them is cut.  All of it follows from (session, row
-// table, s_max, tunables), so plan_forward fills it once, before the layer loop, and the launch helpers read it - they
+// What the planner reads of a session - plain values, so that sd_forward_route plans a pass without a session or a device
+struct PlanCtx {
+    sd_model_config cfg;
+    Tunables tun;
+    bool tp;                          // the pass runs on a shard of a tensor-parallel group
+    bool final_norm;                  // the model has a final-norm weight
+    size_t part_floats;               // floats of the k-slab scratch (plan_scratch)
+    int cus;                          // CUs of the device
+};
+// The route of one forward pass: which launches it makes and how each of them is cut.  All of it follows from (PlanCtx, row
+// table, s_max), so plan_forward fills it once, before the layer loop, and the launch helpers read it - they
 // decide nothing themselves.  What does differ between layers (a layer's biases, l + 1 < L) stays in the loop.
 enum AttnKind { AK_KERNEL = 0, AK_OPROJ, AK_PREFILL };           // attn_kernel (+ combine) | fused attention + O | matrix cores
 struct FwdPlan {
@@ -1220,17 +1237,16 @@ struct FwdPlan {
     bool seam_o, seam_d;              // norm on load may open at the attention -> MLP seam / the down -> next QKV seam
     GemmRoute qkv, o, gu, down;       // the per-layer GEMMs of a 16-bit model (not of the small path, which cuts its own)
     GemmRoute head;                   // the lm_head with its row gather (16-bit model, logit rows)
+    int S_o, ksp_o, S_d, ksp_d;       // small: the k-slabs of its O / down GEMMs (small_split)
     int rn_threads;                   // blockDim of residual_norm_kernel
 };
 
-template <typename T>
-static bool prefill_attn_ok(const sd_session *s, const RowTab &tab, int s_max) {
-    if constexpr (sizeof(T) != 2) return false;
-    const sd_model_config &c = s->m->cfg;
-    if (!(s->tun.prefill_attn && tab.contig && !tab.tree && (c.head_dim == 64 || c.head_dim == 128) && tab.n_rows >= 32 &&
-          c.n_heads % c.n_kv_heads == 0))
+static bool prefill_attn_ok(const PlanCtx &pc, const RowTab &tab, int s_max) {
+    const sd_model_config &c = pc.cfg;
+    if (!(is16(c.dtype) && pc.tun.prefill_attn && tab.contig && !tab.tree && (c.head_dim == 64 || c.head_dim == 128) &&
+          tab.n_rows >= 32 && c.n_heads % c.n_kv_heads == 0))
         return false;
-    return route_prefill_attn(s->tun, c.head_dim, c.n_heads, tab.n_rows, tab.n_groups, s_max, s->tun.prefill_attn_block, device_cus()) != 0;
+    return route_prefill_attn(pc.tun, c.head_dim, c.n_heads, tab.n_rows, tab.n_groups, s_max, pc.tun.prefill_attn_block, pc.cus) != 0;
 }
 template <typename T, int D, bool KV8>
 static void launch_attn_prefill_inst(const sd_model_config &c, const T *q, const PaGroups &pg, int layer, T *out, const PaPlan &pl,
@@ -1338,16 +1354,15 @@ static size_t attn_oproj_lds(int s_max) {
     const int s_cap = (int)align_up(s_max, 64);
     return sizeof(float) * ((size_t)ATT_TQ * D + (size_t)(256 / (D / 8)) * ATT_TQ * D + (size_t)ATT_TQ * s_cap);
 }
-template <typename T>
-static bool attn_oproj_ok(const sd_session *s, const RowTab &tab, int s_max) {
-    const sd_model_config &c = s->m->cfg;
-    if constexpr (sizeof(T) != 2) return false;
-    if (!s->tun.fuse_attn_o || s->tp || tab.tree || tab.kv_fp8 || tab.contig) return false;
+static bool attn_oproj_ok(const PlanCtx &pc, const RowTab &tab, int s_max) {
+    const sd_model_config &c = pc.cfg;
+    if (!is16(c.dtype)) return false;
+    if (!pc.tun.fuse_attn_o || pc.tp || tab.tree || tab.kv_fp8 || tab.contig) return false;
     if (c.head_dim != 128 || tab.n_groups > 2 || tab.n_streams != 1 || tab.n_rows > 16) return false;
     const int K = q_dim(c), N = c.hidden;
-    if (K % 128 || K / 128 > AO_NKW || N % 16 || s_max > s->tun.attn_split_keys) return false;
-    if (c.n_heads * tab.n_groups + (N / 16 + 1) / 2 > device_cus()) return false;      // every workgroup resident at once, one per CU
-    if ((size_t)16 * N > s->part_floats) return false;
+    if (K % 128 || K / 128 > AO_NKW || N % 16 || s_max > pc.tun.attn_split_keys) return false;
+    if (c.n_heads * tab.n_groups + (N / 16 + 1) / 2 > pc.cus) return false;      // every workgroup resident at once, one per CU
+    if ((size_t)16 * N > pc.part_floats) return false;
     // (a context whose score tile does not fit the launch's LDS budget takes the two launches - never an error: the key
     //  limit SD_ATTN_SPLIT_KEYS is a tuning knob)
     if (attn_oproj_lds(s_max) > AO_LDS_MAX) return false;
@@ -1382,11 +1397,10 @@ static int launch_attn_oproj(sd_session *s, const T *q, const RowTab &tab, const
 
 // Norm on load (normload_kernels.h): <= 8 rows of a 16-bit Llama model whose residual rows were left un-normalised (+
 // per-tile sums of squares in s->ssq) by a residual epilogue; the consumer GEMM keeps its whole k-range per workgroup.
-template <typename T>
-static bool norm_on_load_ok(const sd_session *s, const RowTab &tab) {
-    const sd_model_config &c = s->m->cfg;
-    if constexpr (sizeof(T) != 2) return false;
-    if (!s->tun.norm_on_load || c.arch != SD_ARCH_LLAMA || !c.fused_layout || s->tp) return false;
+static bool norm_on_load_ok(const PlanCtx &pc, const RowTab &tab) {
+    const sd_model_config &c = pc.cfg;
+    if (!is16(c.dtype)) return false;
+    if (!pc.tun.norm_on_load || c.arch != SD_ARCH_LLAMA || !c.fused_layout || pc.tp) return false;
     // (9..16 rows: the conversions cost more than the launch they replace - +5.7 us on gate/up at 12 rows, tools/gemm_bench.py)
     return tab.n_rows <= 8 && c.hidden % 1024 == 0 && c.hidden <= 8192;
 }
@@ -1503,13 +1517,13 @@ static int head_logits(sd_session *s, const GemmRoute &hr, const T *hl, const Ro
 }
 
 // whether a pass takes the small-model decode path (forward_small)
-static bool small_path_ok(const sd_session *s, const RowTab &tab) {
-    const sd_model_config &c = s->m->cfg;
-    if (!s->tun.small_path || c.dtype != SD_BF16 || !c.fused_layout || tab.contig || s->tp) return false;
+static bool small_path_ok(const PlanCtx &pc, const RowTab &tab) {
+    const sd_model_config &c = pc.cfg;
+    if (!pc.tun.small_path || c.dtype != SD_BF16 || !c.fused_layout || tab.contig || pc.tp) return false;
     if (tab.n_rows > SMALL_MAX_ROWS || tab.n_logit_rows > SMALL_MAX_ROWS) return false;
     if (c.hidden > 2048 || c.hidden % 32 != 0 || embed_dim(c) != c.hidden) return false;
     if (c.arch == SD_ARCH_OPT && !c.opt_pre_ln) return false;          // post-LN keeps the stand-alone norm launches
-    if (!s->m->w.final_norm_w) return false;
+    if (!pc.final_norm) return false;
     return true;
 }
 
@@ -1588,23 +1602,27 @@ static int resid_norm(sd_session *s, const FwdPlan &fp, int M, T *x, const float
 }
 
 // Decide the route of a pass (FwdPlan)
-template <typename T>
-static void plan_forward(const sd_session *s, const RowTab &tab, int s_max, FwdPlan &fp) {
-    const sd_model_config &c = s->m->cfg;
-    const Tunables &t = s->tun;
+static void plan_forward(const PlanCtx &pc, const RowTab &tab, int s_max, FwdPlan &fp) {
+    const sd_model_config &c = pc.cfg;
+    const Tunables &t = pc.tun;
     const int H = c.hidden, M = tab.n_rows, ED = embed_dim(c);
     const bool llama = c.arch == SD_ARCH_LLAMA, pre = llama || c.opt_pre_ln, fused = is16(c.dtype) && c.fused_layout != 0;
     // residual+norm keeps the row in registers: 2 groups of 4 columns per thread (H <= 8192)
     fp.rn_threads = (int)std::min<size_t>(1024, std::max<size_t>(64, align_up((H / 4 + RN_RG - 1) / RN_RG, 64)));
     fp.s_max = s_max; fp.nsplit = fp.s_cap = 0; fp.attn_lds = 0; fp.pa = PaPlan{};         // (everything but pg, which only
     fp.qkv = fp.o = fp.gu = fp.down = fp.head = GemmRoute{};                                // AK_PREFILL fills and reads)
-    fp.small = small_path_ok(s, tab);
+    fp.S_o = fp.ksp_o = fp.S_d = fp.ksp_d = 0;
+    fp.small = small_path_ok(pc, tab);
+    if (fp.small) {
+        small_split(t, H, q_dim(c), &fp.S_o, &fp.ksp_o);
+        small_split(t, H, c.inter, &fp.S_d, &fp.ksp_d);
+    }
     fp.embed_qkv = fp.small || (c.dtype == SD_BF16 && t.fuse_embed_qkv && fused && pre && (llama || ED == H) && !tab.contig &&
                                 M <= SMALL_MAX_ROWS && H <= 2048 && H % 32 == 0);
-    if (!fp.small && attn_oproj_ok<T>(s, tab, s_max)) {
+    if (!fp.small && attn_oproj_ok(pc, tab, s_max)) {
         fp.attn = AK_OPROJ;
         fp.nsplit = 1; fp.s_cap = (int)align_up(s_max, 64); fp.attn_lds = attn_oproj_lds(s_max);
-    } else if (!fp.small && prefill_attn_ok<T>(s, tab, s_max)) {
+    } else if (!fp.small && prefill_attn_ok(pc, tab, s_max)) {
         fp.attn = AK_PREFILL;
         fp.pa = plan_prefill_attn(c.head_dim, s_max, t.prefill_attn_block);
         prefill_groups(tab, fp.pg);
@@ -1613,13 +1631,13 @@ static void plan_forward(const sd_session *s, const RowTab &tab, int s_max, FwdP
         fp.attn_lds = attn_split_plan(t, c.head_dim, s_max, tab.n_groups, &fp.nsplit, &fp.s_cap);
     }
     // the residual add in the producer's epilogue, the norm in the consumer's operand load (no launch between)
-    const bool seams = pre && fused && norm_on_load_ok<T>(s, tab);
+    const bool seams = pre && fused && norm_on_load_ok(pc, tab);
     fp.seam_o = seams && fp.attn == AK_OPROJ;
     fp.seam_d = seams && t.norm_on_load > 1;
     if (!is16(c.dtype)) return;
     if (!fp.small) {
         // (a shard's O / down projection: one slab, which the all-reduce takes as it is)
-        const int row_par = s->tp ? GN_ONE_SLAB : 0;
+        const int row_par = pc.tp ? GN_ONE_SLAB : 0;
         fp.qkv = route_gemm(t, qkv_cols(c), H, M, fused ? GN_FUSED | GN_QKV : 0);
         fp.o = route_gemm(t, H, q_dim(c), M, row_par);
         fp.gu = route_gemm(t, gu_cols(c), H, M, fused ? GN_FUSED : 0);
@@ -1652,9 +1670,7 @@ static int forward_small(sd_session *s, const RowTab &tab, const FwdPlan &fp, fl
     // its bias and its number
     GemmEpi qe = qkv_epi<bf16_t>(s, tab, 0), ae = act_epi<bf16_t>(s, 0);
     const GemmEpi no_epi = {};
-    int S_o, ksp_o, S_d, ksp_d;
-    small_split(s->tun, H, q_dim(c), &S_o, &ksp_o);
-    small_split(s->tun, H, I, &S_d, &ksp_d);
+    const int S_o = fp.S_o, ksp_o = fp.ksp_o, S_d = fp.S_d, ksp_d = fp.ksp_d;
     SD_REQUIRE((size_t)std::max(S_o, S_d) * 16 * H <= s->spart_floats, "forward_small: slab buffer too small");
 
     auto resid_pro = [&](int S, const bf16_t *bias, const void *nw, const void *nb, bool write_r) {
@@ -1739,7 +1755,7 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
     sd_model *m = s->m;
     const sd_model_config &c = m->cfg;
     FwdPlan fp;
-    plan_forward<T>(s, tab, s_max, fp);
+    plan_forward(PlanCtx{c, s->tun, s->tp != nullptr, m->w.final_norm_w != nullptr, s->part_floats, device_cus()}, tab, s_max, fp);
     if (fp.small) return forward_small(s, tab, fp, logits_out, ld_logits, rq, ho, st);
     const int H = c.hidden, D = c.head_dim, I = c.inter, L = c.n_layers, ED = embed_dim(c);
     const bool llama = c.arch == SD_ARCH_LLAMA, pre = llama || c.opt_pre_ln, fused = is16(c.dtype) && c.fused_layout != 0;
@@ -1928,6 +1944,22 @@ static void finish_table(RowTab &tab) {
     }
 }
 
+// the rows of a single-stream pass (sd_session_forward, sd_forward_route): n_new rows at pos0 .., the last n_logits of them
+// logit rows; the streams themselves are bound by the caller (bind_stream)
+static void single_stream_rows(RowTab &tab, int n_new, int pos0, int n_logits) {
+    tab.n_rows = n_new;
+    tab.n_streams = 1;
+    tab.n_logit_rows = n_logits;
+    if (n_new > SD_MAX_ROWS) {                      // prefill chunk: positions are implicit
+        tab.contig = 1;
+        tab.pos0 = pos0;
+    } else {
+        for (int i = 0; i < n_new; ++i) { tab.row_pos[i] = pos0 + i; tab.row_stream[i] = 0; }
+    }
+    for (int i = 0; i < n_logits; ++i) tab.xmap[i] = (unsigned char)(n_new - n_logits + i);   // n_new <= 256
+    finish_table(tab);
+}
+
 static int launch_attn_bf16(sd_session *s, const bf16_t *q, const RowTab &tab, const FwdPlan &fp, int layer, bf16_t *out, hipStream_t st) {
     return launch_attn_d<bf16_t>(s, q, tab, fp, layer, out, st);
 }
@@ -1981,18 +2013,8 @@ static int session_forward(sd_session *s, const int32_t *tokens, int n_new, int 
         return SD_ERR_CAPACITY;
     }
     RowTab tab = {};
-    tab.n_rows = n_new;
-    tab.n_streams = 1;
-    tab.n_logit_rows = n_logits;
+    single_stream_rows(tab, n_new, pos0, n_logits);
     bind_stream(tab, 0, s, tokens - pos0);      // indexed by absolute position, only ever read at pos0 .. pos0+n_new-1
-    if (n_new > SD_MAX_ROWS) {                      // prefill chunk: positions are implicit
-        tab.contig = 1;
-        tab.pos0 = pos0;
-    } else {
-        for (int i = 0; i < n_new; ++i) { tab.row_pos[i] = pos0 + i; tab.row_stream[i] = 0; }
-    }
-    for (int i = 0; i < n_logits; ++i) tab.xmap[i] = (unsigned char)(n_new - n_logits + i);   // n_new <= 256
-    finish_table(tab);
     return run_forward(s, tab, pos0 + n_new, logits_out, ld_logits, rq, ho, stream);
 }
 
@@ -2250,6 +2272,56 @@ extern "C" int sd_gemm_route(int N, int K, int M, int need, sd_gemm_route_info *
         o.inst_mt = 4 * in.mtw; o.inst_nt = in.nt; o.lds_bytes = (int32_t)in.lds;
     }
     o.part_floats = r.kind == GK_NONE ? 0 : (uint64_t)r.S * Mpad * N;
+    *out = o;
+    return SD_OK;
+}
+
+static_assert(SD_ATTN_KERNEL == AK_KERNEL && SD_ATTN_OPROJ == AK_OPROJ && SD_ATTN_PREFILL == AK_PREFILL, "specdec.h publishes AttnKind");
+
+// attn_kernel's key splits for a pass - by the function launch_attn's plan comes from
+extern "C" int sd_attn_split(int head_dim, int s_max, int n_groups, int *nsplit, int *chunk_keys, int *s_cap, long *lds_bytes) {
+    SD_REQUIRE((head_dim == 16 || head_dim == 32 || head_dim == 64 || head_dim == 128) && s_max >= 1 && n_groups >= 1 &&
+                   n_groups <= SD_MAX_GROUPS,
+               "sd_attn_split: head_dim %d, s_max %d, %d row groups (1..%d)", head_dim, s_max, n_groups, SD_MAX_GROUPS);
+    int ns, cap;
+    const size_t lds = attn_split_plan(read_tunables(), head_dim, s_max, n_groups, &ns, &cap);
+    if (nsplit) *nsplit = ns;
+    if (chunk_keys) *chunk_keys = attn_chunk_keys(s_max, ns);
+    if (s_cap) *s_cap = cap;
+    if (lds_bytes) *lds_bytes = (long)lds;
+    return SD_OK;
+}
+
+// The route of one single-stream pass: session_forward's row table and forward_impl's plan_forward, without the session
+extern "C" int sd_forward_route(const sd_model_config *cfg, const sd_pass_desc *pass, sd_forward_route_info *out) {
+    SD_REQUIRE(cfg && pass && out, "sd_forward_route: null argument");
+    if (check_config("sd_forward_route", cfg) != SD_OK) return SD_ERR_INVALID;
+    SD_REQUIRE(cfg->vocab >= 1 && cfg->hidden >= 1 && cfg->inter >= 1 && cfg->n_layers >= 1 && cfg->n_heads >= 1 && embed_dim(*cfg) >= 1,
+               "sd_forward_route: vocab, hidden, inter, layers, heads and the embedding width must be positive");
+    const sd_pass_desc &p = *pass;
+    SD_REQUIRE(p.n_rows >= 1 && p.n_rows <= SD_MAX_FWD_ROWS && p.pos0 >= 0 && p.pos0 <= cfg->max_pos - p.n_rows,
+               "sd_forward_route: n_rows=%d (1..%d) pos0=%d (max_pos %d)", p.n_rows, SD_MAX_FWD_ROWS, p.pos0, cfg->max_pos);
+    SD_REQUIRE(p.n_logit_rows >= 0 && p.n_logit_rows <= p.n_rows, "sd_forward_route: n_logit_rows=%d of n_rows=%d", p.n_logit_rows, p.n_rows);
+    SD_REQUIRE(p.max_rows >= 1 && p.cus >= 0 && (p.kv_fp8 | 1) == 1 && (p.tp | 1) == 1,
+               "sd_forward_route: max_rows=%d cus=%d kv_fp8=%d tp=%d", p.max_rows, p.cus, p.kv_fp8, p.tp);
+    PlanCtx pc = {*cfg, read_tunables(), p.tp != 0, true, 0, p.cus ? p.cus : device_cus()};
+    const int max_rows = std::min(p.max_rows, model_max_rows(pc.tun, pc.cfg));      // (as sd_session_create clamps it)
+    SD_REQUIRE(p.n_rows <= max_rows, "sd_forward_route: n_rows=%d exceeds the session's max_rows %d", p.n_rows, max_rows);
+    pc.part_floats = plan_scratch(pc.tun, pc.cfg, max_rows).part_floats;
+    RowTab tab = {};
+    single_stream_rows(tab, p.n_rows, p.pos0, p.n_logit_rows);
+    tab.kv_fp8 = p.kv_fp8;
+    FwdPlan fp;
+    plan_forward(pc, tab, p.pos0 + p.n_rows, fp);
+    auto cut = [](const GemmRoute &r) { return sd_gemm_cut{r.kind, r.S, r.ksp}; };
+    sd_forward_route_info o = {};
+    o.small = fp.small; o.embed_qkv = fp.embed_qkv; o.attn = fp.attn; o.seam_o = fp.seam_o; o.seam_d = fp.seam_d;
+    o.rn_threads = fp.rn_threads;
+    o.nsplit = fp.nsplit; o.chunk_keys = fp.nsplit ? attn_chunk_keys(fp.s_max, fp.nsplit) : 0; o.s_cap = fp.s_cap;
+    o.prefill_kernel = fp.pa.kernel; o.prefill_block = fp.pa.block;
+    o.qkv = cut(fp.qkv); o.o = cut(fp.o); o.gu = cut(fp.gu); o.down = cut(fp.down); o.head = cut(fp.head);
+    o.small_o_S = fp.S_o; o.small_o_ksp = fp.ksp_o; o.small_d_S = fp.S_d; o.small_d_ksp = fp.ksp_d;
+    o.attn_lds = (long)fp.attn_lds;
     *out = o;
     return SD_OK;
 }

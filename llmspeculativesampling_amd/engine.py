@@ -59,6 +59,25 @@ def same_device(draft: "SpecDecModel", target: "SpecDecModel") -> None:
                                   "decoding is out of scope (place both models on one GPU)")
 
 
+def fused_layout(cfg: ModelConfig, dtype: torch.dtype) -> bool:
+    """Whether a model's QKV / gate-up rows go into the fused-epilogue order (specdec.h, cfg.fused_layout)."""
+    return dtype != torch.float32 and cfg.intermediate_size % 8 == 0 and cfg.head_dim % 4 == 0
+
+
+def c_model_config(cfg: ModelConfig, dtype: torch.dtype, max_pos: Optional[int] = None,
+                   fused: Optional[bool] = None) -> _lib.SdModelConfig:
+    """The sd_model_config of `cfg` in `dtype` (what SpecDecModel creates its handle with; host only).  fused: the weight
+    layout, where it is not fused_layout's."""
+    return _lib.SdModelConfig(
+        arch=cfg.arch_id, dtype={torch.bfloat16: _lib.SD_BF16, torch.float16: _lib.SD_F16}.get(dtype, _lib.SD_F32),
+        vocab=cfg.vocab_size, hidden=cfg.hidden_size, inter=cfg.intermediate_size, n_layers=cfg.num_hidden_layers,
+        n_heads=cfg.num_attention_heads, n_kv_heads=cfg.num_key_value_heads, head_dim=cfg.head_dim,
+        max_pos=int(max_pos or cfg.max_position_embeddings), opt_pre_ln=int(cfg.do_layer_norm_before),
+        opt_proj_dim=cfg.word_embed_proj_dim or cfg.hidden_size,
+        norm_eps=cfg.rms_norm_eps if cfg.arch == "llama" else cfg.layer_norm_eps,
+        logits_bf16_round=int(dtype != torch.float32), fused_layout=int(fused_layout(cfg, dtype) if fused is None else fused))
+
+
 class SpecDecModel:
     """Weights in HBM + sd_model handle.  Exposes what the reference reads off a model object:
     ``.config.is_encoder_decoder`` (speculative_sampling.py:1942) and ``.device`` (:1909)."""
@@ -82,7 +101,7 @@ class SpecDecModel:
         self.streamed_weight_bytes = 0               # bytes a <= 8-row decode / verify pass streams (12-bit records where packed)
         self.w12 = w12                               # None: SD_W12 / the memory rule decide (_pack_w12)
         self.w12_packed: Dict[str, List[int]] = {}   # matrix kind -> layers whose 12-bit records are registered
-        self.fused = dtype != torch.float32 and cfg.intermediate_size % 8 == 0 and cfg.head_dim % 4 == 0
+        self.fused = fused_layout(cfg, dtype)
         # dtype of the probability rows the reference would keep for this model (kvcache_model.py:167-168 on the model's
         # logits): OPT's logits stay in the weight dtype (modeling_opt.py:974), Llama's are cast to fp32 (:870)
         self.probs_dtype = dtype if cfg.arch == "opt" else torch.float32
@@ -189,13 +208,7 @@ class SpecDecModel:
         w.norm1_w, w.norm1_b = self._ptr_array(n1w), self._ptr_array(n1b)
         w.norm2_w, w.norm2_b = self._ptr_array(n2w), self._ptr_array(n2b)
 
-        c = _lib.SdModelConfig(
-            arch=cfg.arch_id, dtype={torch.bfloat16: _lib.SD_BF16, torch.float16: _lib.SD_F16}.get(self.dtype, _lib.SD_F32),
-            vocab=cfg.vocab_size, hidden=cfg.hidden_size, inter=cfg.intermediate_size, n_layers=L,
-            n_heads=cfg.num_attention_heads, n_kv_heads=cfg.num_key_value_heads, head_dim=cfg.head_dim,
-            max_pos=self.max_pos, opt_pre_ln=int(cfg.do_layer_norm_before), opt_proj_dim=cfg.word_embed_proj_dim or cfg.hidden_size,
-            norm_eps=cfg.rms_norm_eps if cfg.arch == "llama" else cfg.layer_norm_eps,
-            logits_bf16_round=int(self.dtype != torch.float32), fused_layout=int(self.fused))
+        c = c_model_config(cfg, self.dtype, self.max_pos, self.fused)
         h = C.c_void_p()
         check(lib.sd_model_create(C.byref(c), C.byref(w), C.byref(h)), "sd_model_create")
         self.handle = h

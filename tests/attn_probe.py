@@ -20,10 +20,14 @@ One planted marker therefore owns > 99 % of the softmax row of every query that 
 (16-bit).  `discrimination` measures exactly that on the oracle alone.
 
 A layout is a filler context with M planted at one key; `Layout.cls` names the class of position, `branches` the
-dispatch branches of launch_attn / attn_body the shape sits on (plain Python mirrors of the launch arithmetic below).
+dispatch branches of launch_attn / attn_body the shape sits on.  The host's decision - how many key chunks a launch runs
+and how long they are - is asked of the engine (`split_plan`: sd_attn_split); what attn_body computes inside the kernel
+(a group's own chunk edges, the in-register limit, the V prefetch window, the P.V width, half / full wave) is mirrored below.
 """
 from __future__ import annotations
 
+import ctypes as C
+import functools
 import math
 from collections import namedtuple
 from typing import Dict, List, Optional
@@ -32,8 +36,10 @@ import numpy as np
 import torch
 
 import oracle
+from llmspeculativesampling_amd import _lib
 from llmspeculativesampling_amd.config import ModelConfig
 from llmspeculativesampling_amd.synth import make_state_dict
+from sd_env import tunables
 
 Q_TOK, M_TOK, F_TOK = 5, 6, 7
 MARGIN = 12.0                     # score of the marker's key above a filler's: e^12 / (e^12 + 1039) > 0.993 of the row
@@ -147,7 +153,23 @@ def cast_sd(sd, dtype):
     return out
 
 
-# ----------------------------------------------------------------------------- launch_attn's arithmetic, mirrored
+# ----------------------------------------------------------------------------- the key split, asked of the engine
+@functools.lru_cache(maxsize=None)
+def split_plan(s_all: int, n_groups: int = 1, split_keys: int = 384, keys_per: int = 256, D: int = 128):
+    """(nsplit, chunk_keys) of a launch of n_groups row groups whose last row sees s_all keys, under the (split_keys,
+    keys_per) tunables: sd_attn_split, i.e. attn_split_plan itself (D moves the plan only where a chunk's score rows outgrow
+    the LDS, past 2900 keys)."""
+    ns, ck = C.c_int(), C.c_int()
+    with tunables(SD_ATTN_SPLIT_KEYS=split_keys, SD_ATTN_KEYS_PER_SPLIT=keys_per):
+        _lib.check(_lib.lib.sd_attn_split(D, s_all, n_groups, C.byref(ns), C.byref(ck), None, None), "sd_attn_split")
+    return ns.value, ck.value
+
+
+def nsplit_for(s_all: int, n_groups: int = 1, split_keys: int = 384, keys_per: int = 256) -> int:
+    return split_plan(s_all, n_groups, split_keys, keys_per)[0]
+
+
+# ----------------------------------------------------------------------------- attn_body's arithmetic, mirrored
 def in_register_limit(nr: int) -> int:
     """Keys up to which a group's score rows stay in registers (s_hi <= 8 * LW).  attn_body's `half = nr > 4`: groups of 5..8
     rows run the HALF-wave softmax (one half-wave per row, LW = 32): 256 keys; groups of 4 or fewer rows the FULL-wave
@@ -155,16 +177,9 @@ def in_register_limit(nr: int) -> int:
     return 256 if nr > 4 else 512
 
 
-def nsplit_for(s_all: int, n_groups: int = 1, split_keys: int = 384, keys_per: int = 256) -> int:
-    ns = 1
-    if s_all > split_keys:
-        ns = min(8, (s_all + max(16, keys_per) - 1) // max(16, keys_per))
-        while ns > 1 and ns * n_groups > 64:
-            ns -= 1
-    return ns
-
-
 def chunk_keys(s_all: int, nsplit: int) -> int:
+    """Keys per chunk of a GROUP that sees s_all keys in a launch of nsplit chunks: attn_body cuts every group's own keys by
+    the rule sd_attn_split reports for the launch's longest group (test_attn_probe_cpu.py holds the two together)."""
     return (((s_all + nsplit - 1) // nsplit + 15) & ~15) if nsplit > 1 else s_all
 
 
@@ -195,8 +210,7 @@ def pv_width(nr: int) -> int:
 
 def branches(D: int, S: int, n: int, split_keys: int = 384, keys_per: int = 256) -> List[str]:
     gs = groups_of(n)
-    ns = nsplit_for(S, len(gs), split_keys, keys_per)
-    ck = chunk_keys(S, ns)
+    ns, ck = split_plan(S, len(gs), split_keys, keys_per, D)
     out = []
     for nr in sorted(set(gs)):
         out.append(("register" if ck <= in_register_limit(nr) else "lds") + "-softmax")
@@ -242,7 +256,7 @@ def _place(cls: str, S: int, n: int, D: int, k: int, split_keys: int, keys_per: 
         return Layout(S, n, 255, last, cls) if pos0 > 255 else None
     if cls == "key256":
         return Layout(S, n, 256, last, cls) if pos0 > 256 else None
-    ns = nsplit_for(S, len(groups_of(n)), split_keys, keys_per)
+    ns, ck = split_plan(S, len(groups_of(n)), split_keys, keys_per, D)
     if cls == "chunk_edge":
         if ns == 1:
             return None
@@ -250,7 +264,6 @@ def _place(cls: str, S: int, n: int, D: int, k: int, split_keys: int, keys_per: 
         return Layout(S, n, edges[k % len(edges)], last, cls) if edges else None
     if cls == "past_prefetch":
         w = v_prefetch_keys(D)
-        ck = chunk_keys(S, ns)
         if ck <= w:
             return None
         key = (k % ns) * ck + w                                    # first key past the window of chunk k
@@ -445,15 +458,15 @@ def batch_layouts(n_new) -> List[Layout]:
     chunks: the 3-key stream (S <= 12) gets one 16-key chunk and an empty second one (s_hi == 0); the 17-key stream (S =
     18..26) gets 16 keys and a second chunk of 2..10 keys (see batch_second_chunk_keys)."""
     s_max = max(c + n for c, n in zip(BATCH_CACHE, n_new))
-    ns = nsplit_for(s_max, sum(len(groups_of(n)) for n in n_new))
-    assert ns == 2
+    ns, ck = split_plan(s_max, sum(len(groups_of(n)) for n in n_new))
+    assert ns == 2 and s_max == BATCH_CACHE[1] + n_new[1]          # (stream 1 is the longest: its chunks are the launch's)
     out = []
     for i, (c, n) in enumerate(zip(BATCH_CACHE, n_new)):
         S = c + n
         if i == 0:
             out.append(Layout(S, n, 0, n - 1, "key0"))
         elif i == 1:
-            out.append(Layout(S, n, chunk_keys(S, ns), n - 1, "chunk_edge"))
+            out.append(Layout(S, n, ck, n - 1, "chunk_edge"))
         elif i == 2:
             out.append(Layout(S, n, S, n - 1, "forbidden"))
         else:

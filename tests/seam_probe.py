@@ -43,11 +43,14 @@ A pass is (tokens of its rows, pos0); the rows in front of pos0 are ordinary tok
 one pass as its rows: `passes(family, model, n)` cuts the family's plants into passes of n rows (at most 8 plants per
 pass, the remaining rows ordinary tokens).
 
-Route mirrors (plain Python restatements of plan_forward, pinned by test_seam_probe_cpu.py): rn_threads,
-SMALL_MAX_ROWS, small_path_ok, norm_on_load_ok.
+The route of a pass - the small path, the embedding prologue, fused attention + O, the norm-on-load seams, rn_threads, the
+small path's slab cut - is asked of the engine (`forward_route`: sd_forward_route, plan_forward itself); what is restated
+here is only how forward_small / forward_impl turn a route into launches per profile class (`expected_launches`).
+test_seam_probe_cpu.py pins the route every GPU case claims as literal data.
 """
 from __future__ import annotations
 
+import ctypes as C
 import functools
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -56,8 +59,11 @@ import torch
 import oracle
 from oracle import models_ref
 from attn_probe import FP32_TOL, errors, tol16, tree_ancestors, TREE_W  # noqa: F401  (re-exported: the GPU test's bars)
+from llmspeculativesampling_amd import _lib
 from llmspeculativesampling_amd.config import ModelConfig
+from llmspeculativesampling_amd.engine import c_model_config
 from llmspeculativesampling_amd.synth import make_state_dict
+from sd_env import tunables
 
 DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
 MAX_POS = 160                      # positions (and arena slots) of the 2-layer probe models: 130 prefill rows + a prefix
@@ -117,33 +123,24 @@ def _bf16(t: torch.Tensor) -> torch.Tensor:
     return t.to(torch.bfloat16).float()
 
 
-# ----------------------------------------------------------------------------- plan_forward's arithmetic, mirrored
-RN_RG = 2                          # register groups of 4 columns per thread of residual_norm_kernel
-SMALL_MAX_ROWS = 4
-NORM_ON_LOAD_MAX_ROWS = 8
+# ----------------------------------------------------------------------------- the route of a pass, asked of the engine
+def forward_route(name: str, dt: str, n: int, env: Optional[dict] = None, n_logits: Optional[int] = None,
+                  max_rows: int = 256) -> _lib.SdForwardRouteInfo:
+    """sd_forward_route's answer for ONE single-stream pass of n rows at position 0 of a probe model, with n_logits logit rows
+    (default: all of them, at most 64), in a session asked for max_rows rows, under the tunables `env` - plan_forward itself."""
+    cfg = probe_config(name)
+    c = c_model_config(cfg, DTYPES[dt])
+    p = _lib.SdPassDesc(n_rows=n, pos0=0, n_logit_rows=min(n, MAX_LOGIT_ROWS) if n_logits is None else n_logits, kv_fp8=0,
+                        tp=0, max_rows=max_rows, cus=0)
+    out = _lib.SdForwardRouteInfo()
+    with tunables(env or {}):
+        _lib.check(_lib.lib.sd_forward_route(C.byref(c), C.byref(p), C.byref(out)), "sd_forward_route")
+    return out
 
 
-def rn_threads(H: int) -> int:
+def rn_threads(name: str) -> int:
     """blockDim of residual_norm_kernel: thread t owns columns 4t .. 4t + 3 and 4 (t + rn_threads) .. + 3."""
-    per = (H // 4 + RN_RG - 1) // RN_RG
-    return min(1024, max(64, (per + 63) // 64 * 64))
-
-
-def norm_on_load_ok(cfg: ModelConfig, dt: str, n_rows: int, env_norm_on_load: int = 2) -> bool:
-    fused = dt != "fp32" and cfg.intermediate_size % 8 == 0 and cfg.head_dim % 4 == 0
-    return (dt != "fp32" and env_norm_on_load != 0 and cfg.arch == "llama" and fused and n_rows <= NORM_ON_LOAD_MAX_ROWS
-            and cfg.hidden_size % 1024 == 0 and cfg.hidden_size <= 8192)
-
-
-def small_path_ok(cfg: ModelConfig, dt: str, n_rows: int, env_small_path: int = 1) -> bool:
-    """forward_small: bf16, the fused layout, a non-contiguous pass of <= 4 rows, hidden <= 2048, no input projection,
-    not post-LN (a pass of <= 80 rows is never contiguous)."""
-    fused = cfg.intermediate_size % 8 == 0 and cfg.head_dim % 4 == 0
-    if not env_small_path or dt != "bf16" or not fused or n_rows > SMALL_MAX_ROWS:
-        return False
-    if cfg.hidden_size > 2048 or cfg.hidden_size % 32 or cfg.word_embed_proj_dim not in (0, cfg.hidden_size):
-        return False
-    return cfg.arch == "llama" or cfg.do_layer_norm_before
+    return forward_route(name, "fp32", 1).rn_threads
 
 
 def stat_columns(name: str) -> List[int]:
@@ -151,7 +148,7 @@ def stat_columns(name: str) -> List[int]:
     sum-of-squares tile); 4 rn_threads - 1 | 4 rn_threads (first column of residual_norm_kernel's second register
     group, where the row has one); H - 1."""
     H = probe_config(name).hidden_size
-    rt = rn_threads(H)
+    rt = rn_threads(name)
     out = []
     for c in (0, 3, 4, 7, 8, 15, 16, 4 * rt - 1, 4 * rt, H - 1):
         if c < H and c not in out:
@@ -497,7 +494,7 @@ def kv_pass(name: str, dt: str, n: int) -> Tuple[str, Tuple[int, ...]]:
 KV_SENTINEL = 0x7B                 # finite in every arena format: bf16 / fp16 0x7b7b, fp32 0x7b7b7b7b, e4m3 0x7b
 
 
-# ----------------------------------------------------------------------------- the launches of a pass, mirrored
+# ----------------------------------------------------------------------------- the launches of a route
 def call_chunks(n: int, max_rows: int) -> List[Tuple[int, int]]:
     """(rows, logit rows) of the passes Session.forward cuts a call of n rows into when the logits of its last
     min(n, 64) rows are asked for and one pass carries at most max_rows rows (Session.max_rows)."""
@@ -513,76 +510,62 @@ def call_chunks(n: int, max_rows: int) -> List[Tuple[int, int]]:
 
 
 def expected_call(name: str, dt: str, n: int, env: Optional[dict], w12, max_rows: int) -> dict:
-    """expected_launches summed over the passes of one call (a pass of more than 80 rows is a contiguous one).  w12: False,
-    True (every matrix packed) or SpecDecModel.w12_packed (matrix kind -> layers whose records were registered)."""
+    """expected_launches summed over the passes of one call.  w12: False, True (every matrix packed) or
+    SpecDecModel.w12_packed (matrix kind -> layers whose records were registered)."""
     tot: Dict[str, int] = {}
     for m, nl in call_chunks(n, max_rows):
-        for k, v in expected_launches(name, dt, m, env, w12, contig=m > 80, n_logits=nl).items():
+        for k, v in expected_launches(name, dt, m, env, w12, n_logits=nl, max_rows=max_rows).items():
             tot[k] = tot.get(k, 0) + v
     return tot
 
 
-def expected_launches(name: str, dt: str, n: int, env: Optional[dict] = None, w12=False, contig: bool = False,
-                      n_logits: Optional[int] = None) -> dict:
+def expected_launches(name: str, dt: str, n: int, env: Optional[dict] = None, w12=False, n_logits: Optional[int] = None,
+                      max_rows: int = 256) -> dict:
     """{profile class: launches} and "w12" (GEMM launches on 12-bit records) of ONE single-stream pass of n rows with
-    n_logits logit rows (default: all of them, at most 64), no key split: forward_small / forward_impl of engine.hip restated.  This is what tells
-    the routes apart: the small path has 4 L + 1 GEMM-class launches and one (SD_SMALL_PATH=1) or no norm launch; the
-    embedding prologue removes the embed launch; fused attention + O removes the O GEMM; a norm-on-load seam removes a
-    residual+norm launch; the 16-bit fused epilogues remove the qkv / activation launches."""
-    env = env or {}
+    n_logits logit rows (default: all of them, at most 64), no key split.  The route is the engine's own (forward_route);
+    restated here is what forward_small / forward_impl launch on it: the small path has 4 L + 1 GEMM-class launches and one
+    (SD_SMALL_PATH=1) or no norm launch; the embedding prologue removes the embed launch; fused attention + O removes the
+    O GEMM; a norm-on-load seam removes a residual+norm launch; the 16-bit fused epilogues remove the qkv / activation
+    launches."""
     cfg = probe_config(name)
     L, H, D = cfg.num_hidden_layers, cfg.hidden_size, cfg.head_dim
-    llama = cfg.arch == "llama"
-    pre = llama or cfg.do_layer_norm_before
-    is16 = dt != "fp32"
-    fused = is16 and cfg.intermediate_size % 8 == 0 and D % 4 == 0
+    pre = cfg.arch == "llama" or cfg.do_layer_norm_before
+    fused = c_model_config(cfg, DTYPES[dt]).fused_layout
     proj = cfg.word_embed_proj_dim not in (0, H)
-    e_small, e_embed = int(env.get("SD_SMALL_PATH", 1)), int(env.get("SD_FUSE_EMBED_QKV", 1))
-    e_nol, e_ao = int(env.get("SD_NORM_ON_LOAD", 2)), int(env.get("SD_FUSE_ATTN_O", 1))
+    r = forward_route(name, dt, n, env, n_logits, max_rows)
     head = 1 if (n if n_logits is None else n_logits) > 0 else 0
     out = {"gemm": 0, "attention": L, "norm_residual": 0, "qkv_rope_append": 0, "activation": 0, "embed": 0, "logits": head, "w12": 0}
-    if not contig and small_path_ok(cfg, dt, n, e_small):
+    if r.small:
         out["gemm"] = 4 * L + head
-        out["norm_residual"] = head if e_small == 1 else 0
+        out["norm_residual"] = head if int((env or {}).get("SD_SMALL_PATH", 1)) == 1 else 0      # (2: the head's prologue)
         return out
-    embed_qkv = (dt == "bf16" and e_embed and fused and pre and not proj and not contig and n <= SMALL_MAX_ROWS and H <= 2048
-                 and H % 32 == 0)
-    qd = cfg.num_attention_heads * D
-    oproj = (is16 and e_ao and not contig and D == 128 and n <= 16 and qd // 128 <= 40
-             and cfg.num_attention_heads * ((n + 7) // 8) + (H // 16 + 1) // 2 <= 256)
-    seams = pre and norm_on_load_ok(cfg, dt, n, e_nol)
-    seam_o, seam_d = seams and oproj, seams and e_nol > 1
-    if not embed_qkv:
+    oproj = r.attn == _lib.SD_ATTN_OPROJ
+    if not r.embed_qkv:
         out["embed"] = 2 if proj else 1
         out["gemm"] += 1 if proj else 0
         out["norm_residual"] += 0 if (not proj and pre) else 1
     for l in range(L):
-        xn_q, xn_d = seam_d and l > 0, seam_d and l + 1 < L
+        xn_q, xn_d = r.seam_d and l > 0, r.seam_d and l + 1 < L
         out["gemm"] += 3 + (0 if oproj else 1)
-        out["norm_residual"] += (0 if seam_o else 1) + (0 if xn_d else 1)
+        out["norm_residual"] += (0 if r.seam_o else 1) + (0 if xn_d else 1)
         if not fused:
             out["qkv_rope_append"] += 1
             out["activation"] += 1
         if w12:
             has = (lambda kind: True) if w12 is True else (lambda kind: l in w12.get(kind, ()))
-            out["w12"] += int(xn_q and has("qkv")) + int(seam_o and D == 128 and has("gate_up")) + int(xn_d and has("down"))
+            out["w12"] += int(xn_q and has("qkv")) + int(r.seam_o and D == 128 and has("gate_up")) + int(xn_d and has("down"))
     out["gemm"] += head * (2 if proj else 1)
     out["logits"] += head if proj else 0
     return out
 
 
 # ----------------------------------------------------------------------------- C. planted slabs
-def gemm_slabs(N: int, K: int, M: int, env: Optional[dict] = None, small: bool = False) -> Tuple[int, int]:
-    """(S, ksp) of the streaming GEMM [N][K] at M rows as sd_gemm_route plans it under the tunables `env`; small: the
-    small path's O / down slabs (small_split: the plan at ONE row, at most 16 slabs)."""
+def gemm_slabs(N: int, K: int, M: int, env: Optional[dict] = None) -> Tuple[int, int]:
+    """(S, ksp) of the streaming GEMM [N][K] at M rows as sd_gemm_route plans it under the tunables `env`."""
     import gemm_route_classes as G
-    with G.tunables({k: str(v) for k, v in (env or {}).items() if k.startswith("SD_GEMM") or k.startswith("SD_MM")}):
-        r = G.route(N, K, 1 if small else M, 0)
-    S, ksp, KS = r.S, r.ksp, K // 32
-    if small and S > 16:
-        ksp = (KS + 15) // 16
-        S = (KS + ksp - 1) // ksp
-    return S, ksp
+    with tunables({k: v for k, v in (env or {}).items() if k.startswith("SD_GEMM") or k.startswith("SD_MM")}):
+        r = G.route(N, K, M, 0)
+    return r.S, r.ksp
 
 
 def fold_loops(S: int) -> Dict[str, int]:
@@ -645,13 +628,15 @@ def c_gain(weight: str) -> float:
 
 
 def c_slabs(case) -> Tuple[int, int]:
-    """(S, ksp) of the planted matrix's GEMM in the case's pass."""
+    """(S, ksp) of the planted matrix's GEMM in the case's pass: the O / down projection's as the pass's route cuts it (on
+    the small path: small_split's slabs), any other matrix's as sd_gemm_route plans it."""
     _, name, dt, env, n, weight, _ = case
-    cfg = probe_config(name)
     if weight.endswith(("down_proj.weight", "o_proj.weight")):
-        small = small_path_ok(cfg, dt, n, int(env.get("SD_SMALL_PATH", 1)))
-        N, K = probe_state_dict(name)[weight].shape
-        return gemm_slabs(N, K, n, env, small)
+        r, down = forward_route(name, dt, n, env), weight.endswith("down_proj.weight")
+        if r.small:
+            return (r.small_d_S, r.small_d_ksp) if down else (r.small_o_S, r.small_o_ksp)
+        cut = r.down if down else r.o
+        return cut.S, cut.ksp
     N, K = probe_state_dict(name)[weight].shape
     return gemm_slabs(N, K, n, env)
 

@@ -2,7 +2,8 @@
 test_gpu_attention_edges.py runs must (1) discriminate - the probed row's fp32 oracle logits move by at least 20x the GPU
 test's tolerance when the marker is lost (replaced by the filler) or, for a forbidden key, leaked into the row - and (2) be
 passed by the reference itself: the oracle in the GPU test's dtype is finite and inside the 16-bit bar of the fp32 oracle.
-The dispatch arithmetic the layouts rely on is pinned as plain Python mirrors of launch_attn / attn_body."""
+The dispatch arithmetic the layouts rely on is pinned by value: the key split as sd_attn_split (launch_attn's own plan)
+answers it, attn_body's kernel-internal rules as plain Python mirrors."""
 import functools
 
 import pytest
@@ -23,7 +24,11 @@ def test_tol16_is_the_rule_of_assert_within_reference_error():
 def test_dispatch_arithmetic_the_layouts_rely_on():
     # split at s_max > 384 keys, ceil(s / 256) chunks (at most 8), each rounded up to 16 keys
     assert [P.nsplit_for(s) for s in (384, 385, 512, 513, 1025)] == [1, 2, 2, 3, 5]
-    assert [P.chunk_keys(s, P.nsplit_for(s)) for s in (384, 385, 511, 512, 513, 1025)] == [384, 208, 256, 256, 176, 208]
+    assert [P.split_plan(s)[1] for s in (384, 385, 511, 512, 513, 1025)] == [384, 208, 256, 256, 176, 208]
+    # attn_body cuts every group's own keys by the rule the host sizes the launch's longest group with
+    for st in ((384, 256), (64, 32), (4096, 256)):
+        for g in (1, 2, 9):
+            assert all(P.chunk_keys(s, P.split_plan(s, g, *st)[0]) == P.split_plan(s, g, *st)[1] for s in range(1, 1100))
     assert P.chunk_edges(385, 2) == [0, 207, 208, 384]
     assert P.chunk_edges(1025, 5) == [0, 207, 208, 415, 416, 623, 624, 831, 832, 1024]
     # (64, 32): 8 chunks of 16 keys at 65..128 keys - with 8 new rows the last chunks lie past row 0's causal range

@@ -18,8 +18,9 @@ _assert_within_reference_error of test_gpu_production_parity (HIP's error agains
 same-dtype oracle's own), per pass over all the logit rows the call returns.  Written K / V rows are held to the same rule
 (fp32: the arena bar of test_gpu_parity), and every arena byte outside the slots a pass owns must be unchanged.
 
-Every test asserts the route it claims from the session's profile class counts and w12_launches(), against
-seam_probe.expected_launches - the launch sequence of forward_small / forward_impl restated per tunable."""
+Every test asserts the launches its route implies from the session's profile class counts and w12_launches(), against
+seam_probe.expected_launches - the route as sd_forward_route plans it, the launch sequence of forward_small / forward_impl
+on that route restated; that each case's route is the one it claims is pinned as data in test_seam_probe_cpu.py."""
 import ctypes as C
 import os
 
@@ -144,7 +145,7 @@ def test_hidden_8192_fills_both_register_groups(hip):
     m = _model(hip, name, dt)
     ses = m.new_session(16)
     toks = S.h8192_pass()
-    assert [S.plant_column(name, t) for t in toks] == [4, 7, 8, 15, 16, 4095, 4096, 8191] and S.rn_threads(8192) == 1024
+    assert [S.plant_column(name, t) for t in toks] == [4, 7, 8, 15, 16, 4095, 4096, 8191] and S.rn_threads(name) == 1024
     out, got = _launches(ses, toks)
     _judge(st, out, name, dt, toks)
     want = S.expected_launches(name, dt, 8)

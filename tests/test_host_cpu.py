@@ -49,6 +49,44 @@ def test_argument_errors_do_not_need_a_gpu():
         _lib.check(_lib.lib.sd_pack_weight_bf16(C.addressof(buf), C.addressof(buf), 8, 32, None), "sd_pack_weight_bf16")
 
 
+def test_forward_route_and_attn_split_refuse_bad_arguments():
+    """sd_forward_route / sd_attn_split: SD_ERR_INVALID with a message that names the entry, nothing written, no GPU."""
+    import ctypes as C
+    from llmspeculativesampling_amd import _lib
+    from llmspeculativesampling_amd.config import load_config
+    from llmspeculativesampling_amd.engine import c_model_config
+    lib = _lib.lib
+    assert C.sizeof(_lib.SdPassDesc) == 7 * 4 and C.sizeof(_lib.SdGemmCut) == 12
+    assert C.sizeof(_lib.SdForwardRouteInfo) == 30 * 4 + 8 and _lib.SdForwardRouteInfo.attn_lds.offset == 120
+    good = dict(n_rows=5, pos0=3, n_logit_rows=5, kv_fp8=0, tp=0, max_rows=256, cus=0)
+
+    def ask(cfg, **over):
+        out = _lib.SdForwardRouteInfo(rn_threads=-7)
+        rc = lib.sd_forward_route(C.byref(cfg), C.byref(_lib.SdPassDesc(**dict(good, **over))), C.byref(out))
+        return rc, out
+
+    cfg = c_model_config(load_config("llama-68m"), torch.bfloat16)
+    rc, out = ask(cfg)
+    assert rc == _lib.SD_OK and out.rn_threads == 128 and (out.nsplit, out.chunk_keys, out.s_cap) == (1, 8, 64)
+    for over in (dict(n_rows=0), dict(n_rows=257), dict(pos0=-1), dict(pos0=cfg.max_pos - 4), dict(n_logit_rows=6),
+                 dict(n_logit_rows=-1), dict(max_rows=0), dict(max_rows=4), dict(cus=-1), dict(kv_fp8=2), dict(tp=-1)):
+        rc, out = ask(cfg, **over)
+        assert rc == _lib.SD_ERR_INVALID and b"sd_forward_route" in lib.sd_last_error() and out.rn_threads == -7, over
+    for field, value in (("arch", 9), ("dtype", 3), ("head_dim", 48), ("hidden", 8200), ("n_kv_heads", 5), ("vocab", 32001),
+                         ("inter", 0), ("n_layers", 0)):
+        bad = c_model_config(load_config("llama-68m"), torch.bfloat16)
+        setattr(bad, field, value)
+        assert ask(bad)[0] == _lib.SD_ERR_INVALID and b"sd_forward_route" in lib.sd_last_error(), field
+    p = C.byref(_lib.SdPassDesc(**good))
+    assert lib.sd_forward_route(None, p, C.byref(out)) == lib.sd_forward_route(C.byref(cfg), None, C.byref(out)) == \
+        lib.sd_forward_route(C.byref(cfg), p, None) == _lib.SD_ERR_INVALID
+    ns = C.c_int(-7)
+    for D, s_max, groups in ((48, 100, 1), (0, 100, 1), (128, 0, 1), (128, 100, 0), (128, 100, 33)):
+        assert lib.sd_attn_split(D, s_max, groups, C.byref(ns), None, None, None) == _lib.SD_ERR_INVALID, (D, s_max, groups)
+        assert b"sd_attn_split" in lib.sd_last_error() and ns.value == -7
+    assert lib.sd_attn_split(128, 100, 32, None, None, None, None) == _lib.SD_OK     # any out pointer may be NULL
+
+
 def test_configs_and_param_counts():
     from llmspeculativesampling_amd.config import load_config
     c13 = load_config("llama-2-13b")

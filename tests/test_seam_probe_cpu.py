@@ -3,7 +3,8 @@ test_gpu_layer_seams.py feeds must (i) be passed by the reference itself - the o
 inside _assert_within_reference_error and inside the 16-bit bar of the fp32 oracle - and (ii) discriminate: the fp32
 oracle's logits of the planted rows move by at least 20x the GPU test's tolerance when ONE norm site leaves the planted
 column out of its statistics (family A), or when an ordinary token takes a degenerate row's place (family B).  The route
-arithmetic the row counts rely on is pinned as plain Python mirrors of plan_forward.  `pytest -s` prints the floors."""
+every GPU case claims is pinned as literal data against sd_forward_route - plan_forward itself.  `pytest -s` prints the floors."""
+import json
 import os
 import re
 
@@ -22,33 +23,77 @@ def _define(header, name):
         return int(re.search(rf"^#define {name} (\d+)", f.read(), re.M).group(1))
 
 
-def test_route_mirrors_match_the_sources():
-    """rn_threads, SMALL_MAX_ROWS and the norm-on-load condition, against the constants and the expressions of the host
-    code (engine.hip is read as text: the mirror must be edited when the expression is)."""
-    assert _define("model_kernels.h", "RN_RG") == S.RN_RG == 2
-    assert _define("small_kernels.h", "SMALL_MAX_ROWS") == S.SMALL_MAX_ROWS == 4
-    with open(os.path.join(_CSRC, "engine.hip")) as f:
-        src = f.read()
-    assert "std::min<size_t>(1024, std::max<size_t>(64, align_up((H / 4 + RN_RG - 1) / RN_RG, 64)))" in src
-    assert "return tab.n_rows <= 8 && c.hidden % 1024 == 0 && c.hidden <= 8192;" in src
-    assert "tab.n_rows > SMALL_MAX_ROWS || tab.n_logit_rows > SMALL_MAX_ROWS" in src
-    # small_split, which seam_probe.gemm_slabs(small=True) restates: the one-row plan, at most 16 slabs
-    assert "gemm_split(t, N, K, 1, S_out, ksp_out);" in src
-    assert "if (*S_out > 16) { *ksp_out = (KS + 15) / 16; *S_out = (KS + *ksp_out - 1) / *ksp_out; }" in src
-    assert [S.rn_threads(h) for h in (96, 128, 256, 1024, 4096, 8192)] == [64, 64, 64, 128, 512, 1024]
+def _route(name, dt, n, env=None, n_logits=None):
+    """(small, embed_qkv, attention kind, seam_o, seam_d) of sd_forward_route's answer; the seams of a small-path pass,
+    which forward_small does not read, as None."""
+    r = S.forward_route(name, dt, n, env, n_logits)
+    kind = {S._lib.SD_ATTN_KERNEL: "kernel", S._lib.SD_ATTN_OPROJ: "oproj", S._lib.SD_ATTN_PREFILL: "prefill"}[r.attn]
+    return [bool(r.small), bool(r.embed_qkv), kind] + ([None, None] if r.small else [bool(r.seam_o), bool(r.seam_d)])
+
+
+def test_the_planner_decides_what_the_row_counts_rely_on():
+    """rn_threads, the small path and the norm-on-load seams as sd_forward_route - plan_forward itself - decides them, by
+    literal value."""
+    assert _define("model_kernels.h", "RN_RG") == 2 and _define("small_kernels.h", "SMALL_MAX_ROWS") == 4
+    by_hidden = {S.probe_config(n).hidden_size: n for n in S.MODELS}
+    assert [S.rn_threads(by_hidden[h]) for h in (96, 128, 256, 1024, 4096, 8192)] == [64, 64, 64, 128, 512, 1024]
     # the register-group edge is a column of the row only where the second group is used at all
-    assert S.stat_columns("llama_h1024")[-3:] == [511, 512, 1023] and 4 * S.rn_threads(256) == 256
+    assert S.stat_columns("llama_h1024")[-3:] == [511, 512, 1023] and 4 * S.rn_threads("llama_h256") == 256
     assert S.stat_columns("llama_h256") == [0, 3, 4, 7, 8, 15, 16, 255]
     assert S.stat_columns("llama_h8192")[-3:] == [4095, 4096, 8191]
-    cfg = S.probe_config("llama_h1024")
-    assert [S.norm_on_load_ok(cfg, "bf16", n) for n in (1, 8, 9)] == [True, True, False]
-    assert not S.norm_on_load_ok(cfg, "fp32", 1) and not S.norm_on_load_ok(cfg, "bf16", 1, env_norm_on_load=0)
-    assert not S.norm_on_load_ok(S.probe_config("llama_h256"), "bf16", 1)
-    assert [S.small_path_ok(cfg, "bf16", n) for n in (1, 4, 5)] == [True, True, False]
-    assert not S.small_path_ok(cfg, "fp16", 1) and not S.small_path_ok(cfg, "bf16", 1, env_small_path=0)
-    assert S.small_path_ok(S.probe_config("opt_pre_h256"), "bf16", 4)
-    assert not S.small_path_ok(S.probe_config("opt_post_h128"), "bf16", 1)
-    assert not S.small_path_ok(S.probe_config("opt_proj_h128"), "bf16", 1)
+    # norm on load: <= 8 rows of a 16-bit Llama model with hidden % 1024 == 0; both seams by default (fused attention + O
+    # carries the attention -> MLP one), none in fp32 or switched off, the down -> QKV one alone without fused attention + O
+    name = "llama_h1024"
+    small_off = {"SD_SMALL_PATH": 0}
+    assert [_route(name, "bf16", n, small_off)[3:] for n in (1, 8, 9)] == [[True, True], [True, True], [False, False]]
+    assert [_route(name, "fp16", n)[3:] for n in (1, 8, 9)] == [[True, True], [True, True], [False, False]]
+    assert _route(name, "fp32", 1)[3:] == [False, False]
+    assert _route(name, "bf16", 1, dict(small_off, SD_NORM_ON_LOAD=0))[3:] == [False, False]
+    assert _route(name, "bf16", 5, {"SD_NORM_ON_LOAD": 1})[3:] == [True, False]
+    assert _route(name, "bf16", 5, {"SD_FUSE_ATTN_O": 0})[2:] == ["kernel", False, True]
+    assert _route("llama_h256", "bf16", 1, small_off)[3:] == [False, False]
+    # the small path: bf16, <= 4 rows (and <= 4 logit rows), pre-LN, no input projection
+    assert [_route(name, "bf16", n)[0] for n in (1, 4, 5)] == [True, True, False]
+    assert not _route(name, "fp16", 1)[0] and not _route(name, "bf16", 1, small_off)[0]
+    assert _route("opt_pre_h256", "bf16", 4)[0]
+    assert not _route("opt_post_h128", "bf16", 1)[0] and not _route("opt_proj_h128", "bf16", 1)[0]
+    # off the small path the embedding prologue still rides the layer-0 QKV launch of such a pass, unless switched off
+    assert _route(name, "bf16", 4, small_off)[:2] == [False, True]
+    assert _route(name, "bf16", 4, dict(small_off, SD_FUSE_EMBED_QKV=0))[:2] == [False, False]
+
+
+def _gpu_passes():
+    """{(model, dtype, tunables, rows, logit rows)}: every single-stream pass whose launches test_gpu_layer_seams.py counts
+    (families A / B through S.ROUTES and the prefill call, H = 8192, C, D, OPT's fc1 edges) and the head cases, cut as
+    Session.forward cuts a call (a session carries 256 rows where the model's GEMMs route them, else 64: asserted there)."""
+    calls = [(name, dt, env, n) for _, env, _, name, dts, rows in S.ROUTES for dt in dts for n in rows]
+    calls += [(name, dt, {}, n) for name, dt in S.PREFILL_MODELS for n in S.PREFILL_ROWS]
+    calls.append(("llama_h8192", "bf16", {}, 8))
+    calls += [(name, dt, env, n) for _, name, dt, env, n, _, _ in S.C_CASES]
+    calls += [(name, dt, env, n) for _, name, dt, _, env, rows in S.D_CASES for n in rows]
+    calls += [(name, dt, env, n) for _, name, dt, env, rows in S.RELU_CASES for n in rows]
+    calls += [(name, dt, {}, n) for name, dt in S.HEAD_MODELS for n in S.HEAD_ROWS]
+    out = {}
+    for name, dt, env, n in calls:
+        for m, nl in S.call_chunks(n, 256 if dt == "fp32" or name in S.CONTIG_MODELS else 64):
+            out["|".join((name, dt, ",".join(f"{k}={v}" for k, v in sorted(env.items())), str(m), str(nl)))] = (name, dt, env, m, nl)
+    return out
+
+
+def test_every_gpu_pass_takes_the_route_it_claims():
+    """tests/golden/seam_routes.json: (small path, embedding prologue, attention kind, seam_o, seam_d) of every pass the GPU
+    seam tests run, recorded from the Python restatement of plan_forward these helpers carried before the engine could be
+    asked.  The GPU tests compare the launches made with the launches the engine's own plan implies; that the plan of each
+    case IS the route the case is there for stands here, as data."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "seam_routes.json")) as f:
+        claimed = json.load(f)
+    passes = _gpu_passes()
+    assert sorted(passes) == sorted(claimed)
+    for key, (name, dt, env, m, nl) in passes.items():
+        assert _route(name, dt, m, env, nl) == claimed[key], key
+    kinds = {tuple(v[:3]) for v in claimed.values()}
+    assert {k[2] for k in kinds} == {"kernel", "oproj", "prefill"} and {k[0] for k in kinds} == {True, False}
+    assert {(v[3], v[4]) for v in claimed.values()} >= {(True, True), (True, False), (False, True), (False, False), (None, None)}
 
 
 def test_probe_weights_are_bf16_numbers_and_the_plants_are_in_place():
@@ -149,12 +194,14 @@ def test_planted_slabs_reach_every_fold_loop_and_discriminate():
     assert S.fold_loops(3) == {"tail": 0} and S.fold_loops(5) == {"burst4": 0, "tail": 4} and S.fold_loops(8) == {"burst8": 0}
     assert S.fold_loops(13) == {"burst8": 0, "burst4": 8, "tail": 12} and S.slab_classes(13) == [0, 8, 12]
     assert S.fold_loops(16) == {"burst8": 0} and S.fold_loops(7) == {"burst4": 0, "tail": 4}
-    for N, K in ((256, 4096), (1024, 1024)):                         # small_split == the planner's one-row split up to 16 slabs
-        for units in (None, 48, 128, 208, 256, 4096):
+    for name, (N, K) in (("llama_c", (256, 4096)), ("llama_h1024", (1024, 1024))):      # the down projection [N][K] of a 3-row
+        for units in (None, 48, 128, 208, 256, 4096):                # small-path pass: the planner's one-row split up to 16 slabs
             env = {} if units is None else {"SD_GEMM_UNITS": units}
             with G.tunables({k: str(v) for k, v in env.items()}):
                 r = G.route(N, K, 1, 0)
-            Ss, ksp = S.gemm_slabs(N, K, 3, env, small=True)
+            fr = S.forward_route(name, "bf16", 3, env)
+            Ss, ksp = fr.small_d_S, fr.small_d_ksp
+            assert fr.small and S.probe_state_dict(name)["model.layers.0.mlp.down_proj.weight"].shape == (N, K)
             assert Ss <= 16 and (Ss - 1) * ksp < K // 32 <= Ss * ksp and (r.S > 16 or (Ss, ksp) == (r.S, r.ksp)), (N, K, units)
     table, seen = {}, set()
     for case in S.C_CASES:
