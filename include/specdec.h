@@ -471,6 +471,24 @@ int sd_prefill_attn_route(int head_dim, int n_heads, int n_rows, int s_max, int 
  * SD_ATTN_KEYS_PER_SPLIT at the call.  Any out pointer may be NULL.  SD_ERR_INVALID for a head_dim outside {16,32,64,128},
  * s_max < 1 or n_groups outside 1..32. */
 int sd_attn_split(int head_dim, int s_max, int n_groups, int *nsplit, int *chunk_keys, int *s_cap, long *lds_bytes);
+/* Grouped-query decode attention (attn_grouped_kernel): the decode, verify and stream-batched passes of a GQA model - 16-bit,
+ * fused layout, head_dim 64 or 128, 2..8 query heads per KV head, no tree, not a pass the matrix-core prefill kernels take;
+ * 16-bit or fp8 arena, TP shards included - can run one workgroup per (KV head, row group, key split) that reads each K / V
+ * element once for all the query heads of its KV head, with both products on the matrix cores and an online softmax whose
+ * LDS does not grow with the context.  The planner tunable SD_ATTN_GROUPED chooses: 0 never; 1 (default) only a pass whose
+ * key splits attn_kernel cannot hold (sd_attn_split's lds_bytes past its limit: SD_ERR_CAPACITY otherwise), so every pass
+ * that ran before takes the launches it took; 2 every pass that meets the gate, ahead of the fused attention + O launch.
+ * sd_grouped_attn_plan is the plan such a pass gets (host only; the function the launch path calls): *nsplit workgroups per
+ * (KV head, group), each over *chunk_keys keys (a multiple of 64, the same for every group of the pass), chosen so that KV
+ * heads x groups x splits fill `cus` CUs (0: the device's, 256 without a device) with at least 256 keys per split and groups x
+ * splits <= 64; *lds_bytes = the launch's dynamic LDS, a function of head_dim alone.  Any out pointer may be NULL.
+ * SD_ERR_INVALID for a head_dim outside {64,128}, heads per KV head outside 2..8 (or not whole), s_max < 1, n_groups outside
+ * 1..32 or cus < 0. */
+int sd_grouped_attn_plan(int head_dim, int n_heads, int n_kv_heads, int s_max, int n_groups, int cus, int *nsplit, int *chunk_keys,
+                         long *lds_bytes);
+/* How many times this session has launched attn_grouped_kernel so far: once per layer of every pass on that route.  A batched
+ * pass counts on its first session.  A host integer: no device work, no synchronisation. */
+int sd_session_grouped_attn_launches(const sd_session *s);
 
 /* The route of one forward pass is a function of (model config, planner tunables, pass) and is decided once, before the
  * first launch.  sd_forward_route answers it on the host - no device, no session - for ONE single-stream pass as
@@ -484,7 +502,7 @@ typedef struct sd_pass_desc {
     int32_t max_rows;               /* what sd_session_create was given: clamped to sd_model_max_rows, it sizes the k-slab scratch */
     int32_t cus;                    /* CUs to plan for; 0: the device's (256 without a device) */
 } sd_pass_desc;
-enum { SD_ATTN_KERNEL = 0, SD_ATTN_OPROJ = 1, SD_ATTN_PREFILL = 2 };   /* attn_kernel (+ combine) | fused attention + O | matrix cores */
+enum { SD_ATTN_KERNEL = 0, SD_ATTN_OPROJ = 1, SD_ATTN_PREFILL = 2, SD_ATTN_GROUPED = 3 };   /* attn_kernel (+ combine) | fused attention + O | matrix cores | grouped-query */
 typedef struct sd_gemm_cut {
     int32_t kind, S, ksp;           /* SD_GEMM_*, k-slabs, k-steps per slab (sd_gemm_route_info) */
 } sd_gemm_cut;
@@ -494,12 +512,12 @@ typedef struct sd_forward_route_info {
     int32_t attn;                   /* SD_ATTN_* */
     int32_t seam_o, seam_d;         /* norm on load may open at the attention -> MLP seam / the down -> next QKV seam */
     int32_t rn_threads;             /* blockDim of residual_norm_kernel */
-    int32_t nsplit, chunk_keys, s_cap;  /* SD_ATTN_KERNEL / SD_ATTN_OPROJ: as sd_attn_split reports them (else 0) */
+    int32_t nsplit, chunk_keys, s_cap;  /* SD_ATTN_KERNEL / SD_ATTN_OPROJ: as sd_attn_split reports them; SD_ATTN_GROUPED: nsplit and chunk_keys as sd_grouped_attn_plan does, s_cap 0 (else 0) */
     int32_t prefill_kernel, prefill_block;  /* SD_ATTN_PREFILL: as sd_prefill_attn_plan reports them (else 0) */
     sd_gemm_cut qkv, o, gu, down;   /* the per-layer GEMMs of a 16-bit model off the small path (else all 0) */
     sd_gemm_cut head;               /* the lm_head with its row gather (16-bit model, n_logit_rows > 0) */
     int32_t small_o_S, small_o_ksp, small_d_S, small_d_ksp;    /* small: the k-slabs of its O / down GEMMs */
-    long attn_lds;                  /* SD_ATTN_KERNEL / SD_ATTN_OPROJ: dynamic LDS of a workgroup */
+    long attn_lds;                  /* SD_ATTN_KERNEL / SD_ATTN_OPROJ / SD_ATTN_GROUPED: dynamic LDS of a workgroup */
 } sd_forward_route_info;
 /* A model that needs a final-norm weight (the small path does) is assumed to have one.  SD_ERR_INVALID, with a message, for a
  * NULL argument, a config sd_model_create would refuse (or a non-positive size), n_rows outside 1..256 or past the clamped

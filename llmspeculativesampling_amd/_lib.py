@@ -237,7 +237,7 @@ class SdGemmRouteInfo(C.Structure):
                                          "inst_unroll", "inst_ch", "inst_wbm", "inst_nt", "lds_bytes")] + [("part_floats", C.c_uint64)]
 
 
-SD_ATTN_KERNEL, SD_ATTN_OPROJ, SD_ATTN_PREFILL = 0, 1, 2      # sd_forward_route_info.attn
+SD_ATTN_KERNEL, SD_ATTN_OPROJ, SD_ATTN_PREFILL, SD_ATTN_GROUPED = 0, 1, 2, 3      # sd_forward_route_info.attn
 
 
 class SdPassDesc(C.Structure):                           # one single-stream pass, as sd_forward_route takes it
@@ -339,6 +339,8 @@ SYMBOLS = [
     ("sd_prefill_attn_plan", _I, [_I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long)]),
     ("sd_prefill_attn_route", _I, [_I, _I, _I, _I, _I, _I, C.POINTER(C.c_int)]),
     ("sd_attn_split", _I, [_I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long)]),
+    ("sd_grouped_attn_plan", _I, [_I, _I, _I, _I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long)]),
+    ("sd_session_grouped_attn_launches", _I, [_VP]),
     ("sd_forward_route", _I, [_P(SdModelConfig), _P(SdPassDesc), _P(SdForwardRouteInfo)]),
     ("sd_session_forward", _I, [_VP, _VP, _I, _I, _I, _VP, _L, _VP]),
     ("sd_session_forward_tree", _I, [_VP, _VP, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), _I, _I, _VP, _L, _VP]),

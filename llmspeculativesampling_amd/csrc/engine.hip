@@ -49,6 +49,7 @@ enum { PC_GEMM = 0, PC_ATTN, PC_NORM, PC_QKV, PC_ACT, PC_EMBED, PC_LOGITS, PC_OT
 struct Tunables {
     int gemm_ntw, gemm_units, small_path, fuse_embed_qkv, attn_split_keys, attn_keys_per_split, ao_stamps, fuse_attn_o;
     int norm_on_load, prefill_attn, prefill_attn_block, mm_slabs_min, mm_mtw, mm_s, gemm_rows, rows_max;
+    int attn_grouped;
 };
 
 struct sd_session {
@@ -78,6 +79,7 @@ struct sd_session {
     int prefill_attn_launches;   // attn_prefill_kernel + attn_prefill_blocked_kernel launches so far (sd_session_prefill_attn_launches: the route, for tests)
     int prefill_attn_blocked_launches;   // ... of which attn_prefill_blocked_kernel
     int w12_launches;            // GEMM launches that streamed 12-bit weight records so far (sd_session_w12_launches)
+    int grouped_attn_launches;   // attn_grouped_kernel launches so far (sd_session_grouped_attn_launches: the route, for tests)
     const float *kv_scale;   // device [L][2][Hkv]
     struct sd_tp *tp;   // tensor-parallel group of this shard (NULL: the model is whole)
     sd_grammar gram;        // the grammar of the stream this session is the target of (sd_session_set_grammar; masks NULL: none)
@@ -211,6 +213,10 @@ static Tunables read_tunables() {
     t.mm_s = geti("SD_MM_S", 0);                  // (sweeps) k-slabs of gemm_bf16_mm; 0 = planned
     t.gemm_rows = geti("SD_GEMM_ROWS", 1);        // 0: 17..64-row GEMMs stay on the streaming kernel (A/B runs, bit-compare tests)
     t.rows_max = std::min(SD_ROWS_MAX, std::max(SD_STREAM_MAX_ROWS, geti("SD_GEMM_ROWS_MAX", SD_ROWS_MAX)));   // 65..this many rows take the balanced kernel, more gemm_bf16_mm
+    // the grouped-query decode attention (grouped_attn.h) for the non-prefill passes of a GQA model - 0: never; 1: only a pass
+    // whose key splits attn_kernel's LDS cannot hold (SD_ERR_CAPACITY otherwise); 2: every pass that meets the gate, ahead of
+    // the fused attention + O launch too (A/B runs, tests)
+    t.attn_grouped = geti("SD_ATTN_GROUPED", 1);
     return t;
 }
 // CUs of the device, a property and no tunable: asked once per process.  No device (CPU container): plans are made for
@@ -635,6 +641,7 @@ extern "C" int sd_session_create(sd_model *m, int max_seq, int max_rows, void *k
     s->gram_cap = 0;
     s->prefill_attn_launches = 0;
     s->w12_launches = 0;
+    s->grouped_attn_launches = 0;
     s->prefill_attn_blocked_launches = 0;
     s->tp_in = (float *)(s->scratch + p.tp_in);
     s->tp_out = (float *)(s->scratch + p.tp_out);
@@ -714,6 +721,8 @@ extern "C" int sd_session_set_grammar(sd_session *s, const sd_grammar *g, int32_
 // whichever kernel ran).  A batched pass counts on its first session.
 extern "C" int sd_session_prefill_attn_launches(const sd_session *s) { return s ? s->prefill_attn_launches : 0; }
 extern "C" int sd_session_w12_launches(const sd_session *s) { return s ? s->w12_launches : 0; }
+// attn_grouped_kernel launches of this session so far: one per layer of every pass on the grouped-query route
+extern "C" int sd_session_grouped_attn_launches(const sd_session *s) { return s ? s->grouped_attn_launches : 0; }
 // ... of which attn_prefill_blocked_kernel's (a context past the single score tile, or SD_PREFILL_ATTN_BLOCK set)
 extern "C" int sd_session_prefill_attn_blocked_launches(const sd_session *s) { return s ? s->prefill_attn_blocked_launches : 0; }
 
@@ -1159,6 +1168,34 @@ static size_t attn_split_plan(const Tunables &t, int D, int s_max, int n_groups,
     return lds;
 }
 
+// attn_grouped_kernel's key splits (grouped_attn.h): one workgroup per (KV head, row group, split) with a fixed LDS footprint,
+// so the splits serve the device's occupancy alone - enough of them that KV heads x groups x splits reach the CU count, each
+// at least GA_SPLIT_MIN_KEYS keys (one 64-key block per wave), groups x splits within the partial buffer.  The chunk is a
+// multiple of 64 keys and the same for every group of the pass; splits that would start past s_max are dropped.
+#define GA_SPLIT_MIN_KEYS 256
+struct GaPlan { int nsplit, chunk; size_t lds; };
+static constexpr size_t grouped_attn_lds(int D) { return (size_t)4 * 64 * (2 * D + 32) + 2 * 4 * 64 * sizeof(float) + (D == 128 ? (size_t)4 * 16 * D * 2 : 0); }
+static GaPlan plan_grouped_attn(int D, int n_kv_heads, int s_max, int n_groups, int cus) {
+    const int wg = std::max(1, n_kv_heads * n_groups);
+    int nsplit = std::min({(cus + wg - 1) / wg, s_max / GA_SPLIT_MIN_KEYS, ATT_MAX_PARTS / n_groups});
+    nsplit = std::max(1, nsplit);
+    const int chunk = (int)align_up((s_max + nsplit - 1) / nsplit, 64);
+    return {(s_max + chunk - 1) / chunk, chunk, grouped_attn_lds(D)};
+}
+extern "C" int sd_grouped_attn_plan(int head_dim, int n_heads, int n_kv_heads, int s_max, int n_groups, int cus, int *nsplit,
+                                    int *chunk_keys, long *lds_bytes) {
+    SD_REQUIRE((head_dim == 64 || head_dim == 128) && n_kv_heads >= 1 && n_heads >= 2 * n_kv_heads && n_heads <= 8 * n_kv_heads &&
+                   n_heads % n_kv_heads == 0,
+               "sd_grouped_attn_plan: head_dim %d (64 or 128), %d heads over %d KV heads (2..8 per KV head)", head_dim, n_heads, n_kv_heads);
+    SD_REQUIRE(s_max >= 1 && n_groups >= 1 && n_groups <= SD_MAX_GROUPS && cus >= 0,
+               "sd_grouped_attn_plan: s_max %d, %d row groups (1..%d), cus %d", s_max, n_groups, SD_MAX_GROUPS, cus);
+    const GaPlan p = plan_grouped_attn(head_dim, n_kv_heads, s_max, n_groups, cus ? cus : device_cus());
+    if (nsplit) *nsplit = p.nsplit;
+    if (chunk_keys) *chunk_keys = p.chunk;
+    if (lds_bytes) *lds_bytes = (long)p.lds;
+    return SD_OK;
+}
+
 // Prefill passes (rows = consecutive positions of a stream) of a 16-bit model with head_dim 64 or 128, the arena in the model
 // type or in fp8: 16-row groups, both products on the matrix cores (prefill_attn.h).  Returns false when the pass does not
 // qualify (the caller takes attn_kernel).  While the whole score tile of a row group fits PA_LDS_MAX (2048 keys at head_dim
@@ -1225,7 +1262,7 @@ struct PlanCtx {
 // The route of one forward pass: which launches it makes and how each of them is cut.  All of it follows from (PlanCtx, row
 // table, s_max), so plan_forward fills it once, before the layer loop, and the launch helpers read it - they
 // decide nothing themselves.  What does differ between layers (a layer's biases, l + 1 < L) stays in the loop.
-enum AttnKind { AK_KERNEL = 0, AK_OPROJ, AK_PREFILL };           // attn_kernel (+ combine) | fused attention + O | matrix cores
+enum AttnKind { AK_KERNEL = 0, AK_OPROJ, AK_PREFILL, AK_GROUPED };   // attn_kernel (+ combine) | fused attention + O | matrix cores | grouped-query
 struct FwdPlan {
     bool small;                       // the small-model decode path (forward_small)
     bool embed_qkv;                   // the embedding and the first pre-norm ride the layer-0 QKV launch
@@ -1233,6 +1270,7 @@ struct FwdPlan {
     PaPlan pa;                        // AK_PREFILL: kernel, keys per score tile, LDS ...
     PaGroups pg;                      // ... and its 16-row groups
     int s_max, nsplit, s_cap;         // AK_KERNEL: key splits and the keys one holds; AK_OPROJ: one split
+    int ga_chunk;                     // AK_GROUPED: keys per split (nsplit: its splits; attn_lds: its fixed LDS)
     size_t attn_lds;                  // ... and a workgroup's dynamic LDS (AK_KERNEL past ATT_LDS_MAX: launch_attn's capacity error)
     bool seam_o, seam_d;              // norm on load may open at the attention -> MLP seam / the down -> next QKV seam
     GemmRoute qkv, o, gu, down;       // the per-layer GEMMs of a 16-bit model (not of the small path, which cuts its own)
@@ -1241,6 +1279,14 @@ struct FwdPlan {
     int rn_threads;                   // blockDim of residual_norm_kernel
 };
 
+// The grouped-query decode attention's gate: a 16-bit GQA model in the fused layout with 2..8 query heads per KV head and
+// head_dim 64 or 128, no tree pass (any arena type, any row table, TP shards included)
+static bool grouped_attn_ok(const PlanCtx &pc, const RowTab &tab) {
+    const sd_model_config &c = pc.cfg;
+    if (!(pc.tun.attn_grouped > 0 && is16(c.dtype) && c.fused_layout != 0 && !tab.tree && (c.head_dim == 64 || c.head_dim == 128)))
+        return false;
+    return c.n_heads % c.n_kv_heads == 0 && c.n_heads / c.n_kv_heads >= 2 && c.n_heads / c.n_kv_heads <= 8;
+}
 static bool prefill_attn_ok(const PlanCtx &pc, const RowTab &tab, int s_max) {
     const sd_model_config &c = pc.cfg;
     if (!(is16(c.dtype) && pc.tun.prefill_attn && tab.contig && !tab.tree && (c.head_dim == 64 || c.head_dim == 128) &&
@@ -1609,7 +1655,7 @@ static void plan_forward(const PlanCtx &pc, const RowTab &tab, int s_max, FwdPla
     const bool llama = c.arch == SD_ARCH_LLAMA, pre = llama || c.opt_pre_ln, fused = is16(c.dtype) && c.fused_layout != 0;
     // residual+norm keeps the row in registers: 2 groups of 4 columns per thread (H <= 8192)
     fp.rn_threads = (int)std::min<size_t>(1024, std::max<size_t>(64, align_up((H / 4 + RN_RG - 1) / RN_RG, 64)));
-    fp.s_max = s_max; fp.nsplit = fp.s_cap = 0; fp.attn_lds = 0; fp.pa = PaPlan{};         // (everything but pg, which only
+    fp.s_max = s_max; fp.nsplit = fp.s_cap = fp.ga_chunk = 0; fp.attn_lds = 0; fp.pa = PaPlan{};         // (everything but pg, which only
     fp.qkv = fp.o = fp.gu = fp.down = fp.head = GemmRoute{};                                // AK_PREFILL fills and reads)
     fp.S_o = fp.ksp_o = fp.S_d = fp.ksp_d = 0;
     fp.small = small_path_ok(pc, tab);
@@ -1619,16 +1665,27 @@ static void plan_forward(const PlanCtx &pc, const RowTab &tab, int s_max, FwdPla
     }
     fp.embed_qkv = fp.small || (c.dtype == SD_BF16 && t.fuse_embed_qkv && fused && pre && (llama || ED == H) && !tab.contig &&
                                 M <= SMALL_MAX_ROWS && H <= 2048 && H % 32 == 0);
-    if (!fp.small && attn_oproj_ok(pc, tab, s_max)) {
+    // the grouped-query route: a GQA model's passes that the prefill kernels do not take (grouped_attn_ok); by default only
+    // where attn_kernel's splits cannot hold the pass, so every pass that ran before takes the launches it took
+    auto take_grouped = [&]() {
+        const GaPlan gp = plan_grouped_attn(c.head_dim, c.n_kv_heads, s_max, tab.n_groups, pc.cus);
+        fp.attn = AK_GROUPED;
+        fp.nsplit = gp.nsplit; fp.ga_chunk = gp.chunk; fp.s_cap = 0; fp.attn_lds = gp.lds;
+    };
+    const bool prefill = !fp.small && prefill_attn_ok(pc, tab, s_max), grouped = !prefill && grouped_attn_ok(pc, tab);
+    if (grouped && t.attn_grouped >= 2) {
+        take_grouped();
+    } else if (!fp.small && attn_oproj_ok(pc, tab, s_max)) {
         fp.attn = AK_OPROJ;
         fp.nsplit = 1; fp.s_cap = (int)align_up(s_max, 64); fp.attn_lds = attn_oproj_lds(s_max);
-    } else if (!fp.small && prefill_attn_ok(pc, tab, s_max)) {
+    } else if (prefill) {
         fp.attn = AK_PREFILL;
         fp.pa = plan_prefill_attn(c.head_dim, s_max, t.prefill_attn_block);
         prefill_groups(tab, fp.pg);
     } else {
         fp.attn = AK_KERNEL;
         fp.attn_lds = attn_split_plan(t, c.head_dim, s_max, tab.n_groups, &fp.nsplit, &fp.s_cap);
+        if (fp.attn_lds > ATT_LDS_MAX && grouped) take_grouped();
     }
     // the residual add in the producer's epilogue, the norm in the consumer's operand load (no launch between)
     const bool seams = pre && fused && norm_on_load_ok(pc, tab);
@@ -1650,6 +1707,9 @@ static void plan_forward(const PlanCtx &pc, const RowTab &tab, int s_max, FwdPla
 // first instantiates them, and moving attn_kernel's bf16 instances in front of the small path's GEMMs made launches of
 // unchanged kernels 0.2-0.4 us slower (profiles/forward_refactor_ab.json)
 static int launch_attn_bf16(sd_session *s, const bf16_t *q, const RowTab &tab, const FwdPlan &fp, int layer, bf16_t *out, hipStream_t st);
+// the grouped-query route (grouped_attn.h), defined last in the file for the same reason
+template <typename T>
+static int launch_attn_grouped(sd_session *s, const T *q, const RowTab &tab, const FwdPlan &fp, int layer, T *out, hipStream_t st);
 
 // ---- small-model decode path (small_kernels.h): 5 launches per layer + the head --------------------------------
 static int forward_small(sd_session *s, const RowTab &tab, const FwdPlan &fp, float *logits_out, long ld_logits, const HeadReq *rq,
@@ -1836,6 +1896,7 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
             if constexpr (!std::is_same<T, float>::value) {            // (the fp32 instantiation has neither kernel)
                 if (fp.attn == AK_OPROJ) rc = launch_attn_oproj<T>(s, qb, tab, fp, l, at, m->wo[l], xn_o, st);
                 else if (fp.attn == AK_PREFILL) rc = launch_attn_prefill<T>(s, qb, tab, fp, l, at, st);
+                else if (fp.attn == AK_GROUPED) rc = launch_attn_grouped<T>(s, qb, tab, fp, l, at, st);
             }
             if (fp.attn == AK_KERNEL) rc = launch_attn_d<T>(s, qb, tab, fp, l, at, st);
             if (rc != SD_OK) return rc;
@@ -1961,6 +2022,7 @@ static void single_stream_rows(RowTab &tab, int n_new, int pos0, int n_logits) {
 }
 
 static int launch_attn_bf16(sd_session *s, const bf16_t *q, const RowTab &tab, const FwdPlan &fp, int layer, bf16_t *out, hipStream_t st) {
+    if (fp.attn == AK_GROUPED) return launch_attn_grouped<bf16_t>(s, q, tab, fp, layer, out, st);
     return launch_attn_d<bf16_t>(s, q, tab, fp, layer, out, st);
 }
 
@@ -2276,7 +2338,8 @@ extern "C" int sd_gemm_route(int N, int K, int M, int need, sd_gemm_route_info *
     return SD_OK;
 }
 
-static_assert(SD_ATTN_KERNEL == AK_KERNEL && SD_ATTN_OPROJ == AK_OPROJ && SD_ATTN_PREFILL == AK_PREFILL, "specdec.h publishes AttnKind");
+static_assert(SD_ATTN_KERNEL == AK_KERNEL && SD_ATTN_OPROJ == AK_OPROJ && SD_ATTN_PREFILL == AK_PREFILL && SD_ATTN_GROUPED == AK_GROUPED,
+              "specdec.h publishes AttnKind");
 
 // attn_kernel's key splits for a pass - by the function launch_attn's plan comes from
 extern "C" int sd_attn_split(int head_dim, int s_max, int n_groups, int *nsplit, int *chunk_keys, int *s_cap, long *lds_bytes) {
@@ -2317,7 +2380,8 @@ extern "C" int sd_forward_route(const sd_model_config *cfg, const sd_pass_desc *
     sd_forward_route_info o = {};
     o.small = fp.small; o.embed_qkv = fp.embed_qkv; o.attn = fp.attn; o.seam_o = fp.seam_o; o.seam_d = fp.seam_d;
     o.rn_threads = fp.rn_threads;
-    o.nsplit = fp.nsplit; o.chunk_keys = fp.nsplit ? attn_chunk_keys(fp.s_max, fp.nsplit) : 0; o.s_cap = fp.s_cap;
+    o.nsplit = fp.nsplit; o.chunk_keys = fp.attn == AK_GROUPED ? fp.ga_chunk : fp.nsplit ? attn_chunk_keys(fp.s_max, fp.nsplit) : 0;
+    o.s_cap = fp.s_cap;
     o.prefill_kernel = fp.pa.kernel; o.prefill_block = fp.pa.block;
     o.qkv = cut(fp.qkv); o.o = cut(fp.o); o.gu = cut(fp.gu); o.down = cut(fp.down); o.head = cut(fp.head);
     o.small_o_S = fp.S_o; o.small_o_ksp = fp.ksp_o; o.small_d_S = fp.S_d; o.small_d_ksp = fp.ksp_d;
@@ -2419,5 +2483,42 @@ extern "C" int sd_unpack_weight_w12(const void *codes, const void *meta, void *w
     hipLaunchKernelGGL(w12_unpack_kernel<0>, dim3((unsigned)((size_t)(N / 16) * (K / 32))), dim3(64), 0, (hipStream_t)stream,
                        W12Arg{(const unsigned *)codes, (const u32x4 *)meta}, (u32x4 *)w_tiled);
     SD_LAUNCH_CHECK();
+    return SD_OK;
+}
+
+// ---- the grouped-query decode attention (forward declaration in front of forward_small): the last kernels of the code object
+#include "grouped_attn.h"
+static_assert(grouped_attn_lds(64) == ga_lds_bytes(64) && grouped_attn_lds(128) == ga_lds_bytes(128), "the plan reports the launch's LDS");
+template <typename T>
+static int launch_attn_grouped(sd_session *s, const T *q, const RowTab &tab, const FwdPlan &fp, int layer, T *out, hipStream_t st) {
+    const sd_model_config &c = s->m->cfg;
+    const int G = c.n_heads / c.n_kv_heads;
+    SD_REQUIRE((c.head_dim == 64 || c.head_dim == 128) && G >= 2 && G <= 8 && !tab.tree && fp.nsplit >= 1 &&
+                   fp.nsplit * tab.n_groups <= ATT_MAX_PARTS && fp.ga_chunk % 64 == 0 && (long)fp.nsplit * fp.ga_chunk >= fp.s_max,
+               "internal: grouped attention planned for head_dim %d, %d heads per KV head, %d splits of %d keys", c.head_dim, G,
+               fp.nsplit, fp.ga_chunk);
+    auto launch = [&](auto d, auto kv8) {
+        constexpr int D = decltype(d)::value;
+        constexpr bool KV8 = decltype(kv8)::value;
+        static bool attr = false;                                 // (one flag per instantiation of this lambda)
+        if (!attr) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(attn_grouped_kernel<T, D, KV8>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)ga_lds_bytes(D));
+            attr = true;
+        }
+        hipLaunchKernelGGL((attn_grouped_kernel<T, D, KV8>), dim3(c.n_kv_heads, tab.n_groups, fp.nsplit), dim3(256), ga_lds_bytes(D), st,
+                           q, tab, layer, out, c.n_heads, c.n_kv_heads, c.arch, 1.0f / sqrtf((float)D), fp.ga_chunk, fp.nsplit,
+                           s->attn_part);
+        if (fp.nsplit > 1)
+            hipLaunchKernelGGL((attn_combine_kernel<T, D>), dim3(c.n_heads, tab.n_groups), dim3(128), 0, st,
+                               (const float *)s->attn_part, tab, out, c.n_heads, fp.nsplit);
+    };
+    using std::integral_constant;
+    if (c.head_dim == 64) {
+        if (tab.kv_fp8) launch(integral_constant<int, 64>{}, std::true_type{}); else launch(integral_constant<int, 64>{}, std::false_type{});
+    } else {
+        if (tab.kv_fp8) launch(integral_constant<int, 128>{}, std::true_type{}); else launch(integral_constant<int, 128>{}, std::false_type{});
+    }
+    ++s->grouped_attn_launches;
     return SD_OK;
 }

@@ -503,6 +503,11 @@ class Session:
         SD_PREFILL_ATTN_BLOCK=K set when the session was created)."""
         return int(lib.sd_session_prefill_attn_blocked_launches(self.handle))
 
+    def grouped_attn_launches(self) -> int:
+        """attn_grouped_kernel launches of this session so far: one per layer of every pass on the grouped-query decode
+        attention route (SD_ATTN_GROUPED; a batched pass counts on its first session).  A host counter."""
+        return int(lib.sd_session_grouped_attn_launches(self.handle))
+
     def past_key_values(self):
         """The reference's tuple layout: one (k, v) pair of (1, H_kv, S, D) views per layer."""
         S = self.cache_len
