@@ -489,6 +489,26 @@ int sd_grouped_attn_plan(int head_dim, int n_heads, int n_kv_heads, int s_max, i
 /* How many times this session has launched attn_grouped_kernel so far: once per layer of every pass on that route.  A batched
  * pass counts on its first session.  A host integer: no device work, no synchronisation. */
 int sd_session_grouped_attn_launches(const sd_session *s);
+/* Shared-prefix attention (attn_shared_kernel): a pass of sd_batch_forward_shared - two or more streams whose arenas all hold
+ * copies of a donor's rows [0, shared_keys), every row of the pass at or past that position - of a 16-bit model in the fused
+ * layout with head_dim 64 or 128 and 1..8 query heads per KV head (MHA included; 16-bit or fp8 arena, TP shards included; no
+ * tree, not the small path, not a contiguous prefill pass) can run ONE launch per layer in which prefix workgroups (KV head,
+ * 64-row query tile over the rows of ALL streams, prefix split) read keys [0, shared_keys) from the donor arena - once per
+ * tile instead of once per stream - and suffix workgroups (KV head, row group, suffix split) read keys [shared_keys, pos +
+ * rows) from the stream's own arena; attn_combine_kernel merges the splits.  The planner tunable SD_ATTN_SHARED chooses: 0
+ * never; 1 (default) passes whose shared_keys >= SD_ATTN_SHARED_MIN_KEYS (default and floor 512, so every pass with a shorter
+ * prefix takes the launches it took); 2 every pass that meets the gate.  sd_shared_attn_plan is the plan such a pass gets (host only; the function the launch path calls): *tiles query tiles
+ * per KV head, *prefix_splits of *prefix_chunk keys over [0, shared_keys) and *suffix_splits of *suffix_chunk keys over
+ * [shared_keys, s_max) (chunks are multiples of 64), chosen so that the workgroups of each role fill `cus` CUs (0: the
+ * device's, 256 without a device) with at least 256 keys per split and n_groups x (prefix + suffix splits) <= 64, the partial
+ * buffer every session owns; *lds_bytes = the launch's dynamic LDS, a function of head_dim alone.  Any out pointer may be NULL.
+ * SD_ERR_INVALID for a head_dim outside {64,128}, heads per KV head outside 1..8 (or not whole), shared_keys < 1, s_max <=
+ * shared_keys, n_rows outside 1..80, n_groups outside 1..min(n_rows, 32) or cus < 0. */
+int sd_shared_attn_plan(int head_dim, int n_heads, int n_kv_heads, int shared_keys, int s_max, int n_rows, int n_groups, int cus,
+                        int *tiles, int *prefix_splits, int *prefix_chunk, int *suffix_splits, int *suffix_chunk, long *lds_bytes);
+/* How many times this session has launched attn_shared_kernel so far: once per layer of every pass on that route.  A batched
+ * pass counts on its first session.  A host integer: no device work, no synchronisation. */
+int sd_session_shared_attn_launches(const sd_session *s);
 
 /* The route of one forward pass is a function of (model config, planner tunables, pass) and is decided once, before the
  * first launch.  sd_forward_route answers it on the host - no device, no session - for ONE single-stream pass as
@@ -502,7 +522,7 @@ typedef struct sd_pass_desc {
     int32_t max_rows;               /* what sd_session_create was given: clamped to sd_model_max_rows, it sizes the k-slab scratch */
     int32_t cus;                    /* CUs to plan for; 0: the device's (256 without a device) */
 } sd_pass_desc;
-enum { SD_ATTN_KERNEL = 0, SD_ATTN_OPROJ = 1, SD_ATTN_PREFILL = 2, SD_ATTN_GROUPED = 3 };   /* attn_kernel (+ combine) | fused attention + O | matrix cores | grouped-query */
+enum { SD_ATTN_KERNEL = 0, SD_ATTN_OPROJ = 1, SD_ATTN_PREFILL = 2, SD_ATTN_GROUPED = 3, SD_ATTN_SHARED = 4 };   /* attn_kernel (+ combine) | fused attention + O | matrix cores | grouped-query | shared-prefix (batched passes only: sd_forward_route describes single-stream passes and never reports it) */
 typedef struct sd_gemm_cut {
     int32_t kind, S, ksp;           /* SD_GEMM_*, k-slabs, k-steps per slab (sd_gemm_route_info) */
 } sd_gemm_cut;
@@ -584,6 +604,14 @@ typedef struct {
     int32_t pos0, n_new, n_logits;
 } sd_batch_item;
 int sd_batch_forward(const sd_batch_item *items, int n_items, float *logits_out, long ld_logits, void *stream);
+/* sd_batch_forward with a promise: rows [0, shared_keys) of every item's arena are copies of the same rows of `donor`'s
+ * (sd_session_copy_kv) - nothing checks this, as with the tree promise, and with fp8 arenas it includes equal scale tables -
+ * so the pass may read them from the donor once for all streams (attn_shared_kernel, where the gate and SD_ATTN_SHARED allow;
+ * every other pass takes sd_batch_forward's launches and reads the items' own rows).  The donor is only read.  SD_ERR_INVALID,
+ * with a message, for shared_keys < 0, past an item's pos0 or past the donor's capacity, and for a donor of another model or
+ * arena type.  shared_keys == 0 or donor == NULL is sd_batch_forward, launch for launch. */
+int sd_batch_forward_shared(const sd_batch_item *items, int n_items, const sd_session *donor, int shared_keys, float *logits_out,
+                            long ld_logits, void *stream);
 /* Batched prefill: the items' rows (each stream's n_new rows at positions pos0.. , a contiguous run; n_logits must be 0) go
  * through ONE pass over the weights - up to 256 rows and 32 attention groups (8 consecutive rows of one stream) in all.
  * K / V rows are appended to every stream's own arena; nothing else comes back.  All sessions share one model. */

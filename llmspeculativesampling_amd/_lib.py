@@ -237,7 +237,7 @@ class SdGemmRouteInfo(C.Structure):
                                          "inst_unroll", "inst_ch", "inst_wbm", "inst_nt", "lds_bytes")] + [("part_floats", C.c_uint64)]
 
 
-SD_ATTN_KERNEL, SD_ATTN_OPROJ, SD_ATTN_PREFILL, SD_ATTN_GROUPED = 0, 1, 2, 3      # sd_forward_route_info.attn
+SD_ATTN_KERNEL, SD_ATTN_OPROJ, SD_ATTN_PREFILL, SD_ATTN_GROUPED, SD_ATTN_SHARED = 0, 1, 2, 3, 4      # sd_forward_route_info.attn
 
 
 class SdPassDesc(C.Structure):                           # one single-stream pass, as sd_forward_route takes it
@@ -341,6 +341,8 @@ SYMBOLS = [
     ("sd_attn_split", _I, [_I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long)]),
     ("sd_grouped_attn_plan", _I, [_I, _I, _I, _I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long)]),
     ("sd_session_grouped_attn_launches", _I, [_VP]),
+    ("sd_shared_attn_plan", _I, [_I] * 8 + [C.POINTER(C.c_int)] * 5 + [C.POINTER(C.c_long)]),
+    ("sd_session_shared_attn_launches", _I, [_VP]),
     ("sd_forward_route", _I, [_P(SdModelConfig), _P(SdPassDesc), _P(SdForwardRouteInfo)]),
     ("sd_session_forward", _I, [_VP, _VP, _I, _I, _I, _VP, _L, _VP]),
     ("sd_session_forward_tree", _I, [_VP, _VP, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), _I, _I, _VP, _L, _VP]),
@@ -383,6 +385,7 @@ SYMBOLS = [
     ("sd_lookup_batch_generate", _I, [_P(SdBatchStream), _I, _I, _I, _I, _P(SdSampling), _P(SdSpecScratch), _P(SdLockstepLog), _VPP,
                                       _VP]),
     ("sd_batch_forward", _I, [C.POINTER(SdBatchItem), _I, _VP, _L, _VP]),
+    ("sd_batch_forward_shared", _I, [C.POINTER(SdBatchItem), _I, _VP, _I, _VP, _L, _VP]),
     ("sd_batch_prefill", _I, [C.POINTER(SdBatchItem), _I, _VP]),
     ("sd_tp_unique_id", _I, [_VP]),
     ("sd_tp_create_rccl", _I, [_I, _I, _VP, C.POINTER(_VP)]),

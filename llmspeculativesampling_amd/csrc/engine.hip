@@ -46,10 +46,13 @@ struct sd_model {
 enum { PC_GEMM = 0, PC_ATTN, PC_NORM, PC_QKV, PC_ACT, PC_EMBED, PC_LOGITS, PC_OTHER };
 
 // the planner's environment tunables (read_tunables below has the variable and the meaning of each)
+// defaults of the shared-prefix attention route (DESIGN.md section 6 has the sweep that sets them)
+#define SA_DEFAULT 1
+#define SA_DEFAULT_MIN_KEYS 512
 struct Tunables {
     int gemm_ntw, gemm_units, small_path, fuse_embed_qkv, attn_split_keys, attn_keys_per_split, ao_stamps, fuse_attn_o;
     int norm_on_load, prefill_attn, prefill_attn_block, mm_slabs_min, mm_mtw, mm_s, gemm_rows, rows_max;
-    int attn_grouped;
+    int attn_grouped, attn_shared, attn_shared_min_keys;
 };
 
 struct sd_session {
@@ -80,6 +83,7 @@ struct sd_session {
     int prefill_attn_blocked_launches;   // ... of which attn_prefill_blocked_kernel
     int w12_launches;            // GEMM launches that streamed 12-bit weight records so far (sd_session_w12_launches)
     int grouped_attn_launches;   // attn_grouped_kernel launches so far (sd_session_grouped_attn_launches: the route, for tests)
+    int shared_attn_launches;    // attn_shared_kernel launches so far (sd_session_shared_attn_launches)
     const float *kv_scale;   // device [L][2][Hkv]
     struct sd_tp *tp;   // tensor-parallel group of this shard (NULL: the model is whole)
     sd_grammar gram;        // the grammar of the stream this session is the target of (sd_session_set_grammar; masks NULL: none)
@@ -217,6 +221,11 @@ static Tunables read_tunables() {
     // whose key splits attn_kernel's LDS cannot hold (SD_ERR_CAPACITY otherwise); 2: every pass that meets the gate, ahead of
     // the fused attention + O launch too (A/B runs, tests)
     t.attn_grouped = geti("SD_ATTN_GROUPED", 1);
+    // the shared-prefix attention (shared_attn.h) for the passes of sd_batch_forward_shared - 0: never; 1: passes whose shared
+    // prefix is at least SD_ATTN_SHARED_MIN_KEYS keys (never below 512: shorter prefixes keep the launches they took); 2: every
+    // pass that meets the gate with a prefix of at least one key (A/B runs, tests)
+    t.attn_shared = geti("SD_ATTN_SHARED", SA_DEFAULT);
+    t.attn_shared_min_keys = std::max(512, geti("SD_ATTN_SHARED_MIN_KEYS", SA_DEFAULT_MIN_KEYS));
     return t;
 }
 // CUs of the device, a property and no tunable: asked once per process.  No device (CPU container): plans are made for
@@ -642,6 +651,7 @@ extern "C" int sd_session_create(sd_model *m, int max_seq, int max_rows, void *k
     s->prefill_attn_launches = 0;
     s->w12_launches = 0;
     s->grouped_attn_launches = 0;
+    s->shared_attn_launches = 0;
     s->prefill_attn_blocked_launches = 0;
     s->tp_in = (float *)(s->scratch + p.tp_in);
     s->tp_out = (float *)(s->scratch + p.tp_out);
@@ -723,6 +733,8 @@ extern "C" int sd_session_prefill_attn_launches(const sd_session *s) { return s 
 extern "C" int sd_session_w12_launches(const sd_session *s) { return s ? s->w12_launches : 0; }
 // attn_grouped_kernel launches of this session so far: one per layer of every pass on the grouped-query route
 extern "C" int sd_session_grouped_attn_launches(const sd_session *s) { return s ? s->grouped_attn_launches : 0; }
+// attn_shared_kernel launches of this session so far: one per layer of every pass on the shared-prefix route
+extern "C" int sd_session_shared_attn_launches(const sd_session *s) { return s ? s->shared_attn_launches : 0; }
 // ... of which attn_prefill_blocked_kernel's (a context past the single score tile, or SD_PREFILL_ATTN_BLOCK set)
 extern "C" int sd_session_prefill_attn_blocked_launches(const sd_session *s) { return s ? s->prefill_attn_blocked_launches : 0; }
 
@@ -1196,6 +1208,47 @@ extern "C" int sd_grouped_attn_plan(int head_dim, int n_heads, int n_kv_heads, i
     return SD_OK;
 }
 
+// attn_shared_kernel's plan (shared_attn.h): 64-row query tiles over the G x n_rows rows of a KV head, prefix splits over keys
+// [0, P) of the donor arena and suffix splits over keys [P, s_max) of the streams' own.  As with the grouped kernel the LDS is
+// fixed, so the splits serve occupancy alone: KV heads x tiles x prefix splits reach the CU count, and so do KV heads x groups x
+// suffix splits, each split at least GA_SPLIT_MIN_KEYS keys, groups x (prefix + suffix splits) within the partial buffer - the
+// suffix is planned first and leaves the prefix at least one.  Chunks are multiples of 64 keys; splits that would start past
+// their range are dropped.
+struct SaPlan { int tiles, psplits, pchunk, ssplits, schunk; size_t lds; };
+static SaPlan plan_shared_attn(int D, int n_heads, int n_kv_heads, int P, int s_max, int n_rows, int n_groups, int cus) {
+    const int G = n_heads / n_kv_heads, tiles = (G * n_rows + 63) / 64, S = s_max - P, parts = ATT_MAX_PARTS / n_groups;
+    auto cut = [&](int wg, int keys, int most, int *chunk) {
+        const int n = std::max(1, std::min({(cus + wg - 1) / wg, keys / GA_SPLIT_MIN_KEYS, most}));
+        *chunk = (int)align_up((keys + n - 1) / n, 64);
+        return (keys + *chunk - 1) / *chunk;
+    };
+    SaPlan p = {};
+    p.tiles = tiles;
+    p.ssplits = cut(n_kv_heads * n_groups, S, parts - 1, &p.schunk);
+    p.psplits = cut(n_kv_heads * tiles, P, parts - p.ssplits, &p.pchunk);
+    p.lds = grouped_attn_lds(D);
+    return p;
+}
+extern "C" int sd_shared_attn_plan(int head_dim, int n_heads, int n_kv_heads, int shared_keys, int s_max, int n_rows, int n_groups,
+                                   int cus, int *tiles, int *prefix_splits, int *prefix_chunk, int *suffix_splits, int *suffix_chunk,
+                                   long *lds_bytes) {
+    SD_REQUIRE((head_dim == 64 || head_dim == 128) && n_kv_heads >= 1 && n_heads >= n_kv_heads && n_heads <= 8 * n_kv_heads &&
+                   n_heads % n_kv_heads == 0,
+               "sd_shared_attn_plan: head_dim %d (64 or 128), %d heads over %d KV heads (1..8 per KV head)", head_dim, n_heads, n_kv_heads);
+    SD_REQUIRE(shared_keys >= 1 && s_max > shared_keys && n_rows >= 1 && n_rows <= SD_MAX_ROWS && n_groups >= 1 &&
+                   n_groups <= std::min(n_rows, SD_MAX_GROUPS) && cus >= 0,
+               "sd_shared_attn_plan: %d shared keys (>= 1) of s_max %d (more), %d rows (1..%d) in %d groups (1..%d, <= rows), cus %d",
+               shared_keys, s_max, n_rows, SD_MAX_ROWS, n_groups, SD_MAX_GROUPS, cus);
+    const SaPlan p = plan_shared_attn(head_dim, n_heads, n_kv_heads, shared_keys, s_max, n_rows, n_groups, cus ? cus : device_cus());
+    if (tiles) *tiles = p.tiles;
+    if (prefix_splits) *prefix_splits = p.psplits;
+    if (prefix_chunk) *prefix_chunk = p.pchunk;
+    if (suffix_splits) *suffix_splits = p.ssplits;
+    if (suffix_chunk) *suffix_chunk = p.schunk;
+    if (lds_bytes) *lds_bytes = (long)p.lds;
+    return SD_OK;
+}
+
 // Prefill passes (rows = consecutive positions of a stream) of a 16-bit model with head_dim 64 or 128, the arena in the model
 // type or in fp8: 16-row groups, both products on the matrix cores (prefill_attn.h).  Returns false when the pass does not
 // qualify (the caller takes attn_kernel).  While the whole score tile of a row group fits PA_LDS_MAX (2048 keys at head_dim
@@ -1262,7 +1315,7 @@ struct PlanCtx {
 // The route of one forward pass: which launches it makes and how each of them is cut.  All of it follows from (PlanCtx, row
 // table, s_max), so plan_forward fills it once, before the layer loop, and the launch helpers read it - they
 // decide nothing themselves.  What does differ between layers (a layer's biases, l + 1 < L) stays in the loop.
-enum AttnKind { AK_KERNEL = 0, AK_OPROJ, AK_PREFILL, AK_GROUPED };   // attn_kernel (+ combine) | fused attention + O | matrix cores | grouped-query
+enum AttnKind { AK_KERNEL = 0, AK_OPROJ, AK_PREFILL, AK_GROUPED, AK_SHARED };   // attn_kernel (+ combine) | fused attention + O | matrix cores | grouped-query | shared-prefix
 struct FwdPlan {
     bool small;                       // the small-model decode path (forward_small)
     bool embed_qkv;                   // the embedding and the first pre-norm ride the layer-0 QKV launch
@@ -1271,6 +1324,7 @@ struct FwdPlan {
     PaGroups pg;                      // ... and its 16-row groups
     int s_max, nsplit, s_cap;         // AK_KERNEL: key splits and the keys one holds; AK_OPROJ: one split
     int ga_chunk;                     // AK_GROUPED: keys per split (nsplit: its splits; attn_lds: its fixed LDS)
+    SaPlan sa;                        // AK_SHARED: tiles, prefix and suffix splits (nsplit: their sum; attn_lds: its fixed LDS)
     size_t attn_lds;                  // ... and a workgroup's dynamic LDS (AK_KERNEL past ATT_LDS_MAX: launch_attn's capacity error)
     bool seam_o, seam_d;              // norm on load may open at the attention -> MLP seam / the down -> next QKV seam
     GemmRoute qkv, o, gu, down;       // the per-layer GEMMs of a 16-bit model (not of the small path, which cuts its own)
@@ -1286,6 +1340,20 @@ static bool grouped_attn_ok(const PlanCtx &pc, const RowTab &tab) {
     if (!(pc.tun.attn_grouped > 0 && is16(c.dtype) && c.fused_layout != 0 && !tab.tree && (c.head_dim == 64 || c.head_dim == 128)))
         return false;
     return c.n_heads % c.n_kv_heads == 0 && c.n_heads / c.n_kv_heads >= 2 && c.n_heads / c.n_kv_heads <= 8;
+}
+// The shared-prefix attention's gate: a pass of sd_batch_forward_shared (>= 2 streams behind a donor's prefix, no tree, no
+// contiguous prefill rows) of a 16-bit model in the fused layout with 1..8 query heads per KV head and head_dim 64 or 128,
+// every group at or past the prefix, the prefix as long as the tunables ask (any arena type, TP shards included)
+static bool shared_attn_ok(const PlanCtx &pc, const RowTab &tab) {
+    const sd_model_config &c = pc.cfg;
+    const int need = pc.tun.attn_shared >= 2 ? 1 : pc.tun.attn_shared_min_keys;
+    if (!(pc.tun.attn_shared > 0 && tab.shared_kv && tab.shared_keys >= need && tab.n_streams >= 2 && !tab.contig && !tab.tree &&
+          is16(c.dtype) && c.fused_layout != 0 && (c.head_dim == 64 || c.head_dim == 128) && c.n_heads % c.n_kv_heads == 0 &&
+          c.n_heads / c.n_kv_heads <= 8))
+        return false;
+    for (int g = 0; g < tab.n_groups; ++g)
+        if (tab.grp_pos[g] < tab.shared_keys) return false;
+    return true;
 }
 static bool prefill_attn_ok(const PlanCtx &pc, const RowTab &tab, int s_max) {
     const sd_model_config &c = pc.cfg;
@@ -1655,7 +1723,7 @@ static void plan_forward(const PlanCtx &pc, const RowTab &tab, int s_max, FwdPla
     const bool llama = c.arch == SD_ARCH_LLAMA, pre = llama || c.opt_pre_ln, fused = is16(c.dtype) && c.fused_layout != 0;
     // residual+norm keeps the row in registers: 2 groups of 4 columns per thread (H <= 8192)
     fp.rn_threads = (int)std::min<size_t>(1024, std::max<size_t>(64, align_up((H / 4 + RN_RG - 1) / RN_RG, 64)));
-    fp.s_max = s_max; fp.nsplit = fp.s_cap = fp.ga_chunk = 0; fp.attn_lds = 0; fp.pa = PaPlan{};         // (everything but pg, which only
+    fp.s_max = s_max; fp.nsplit = fp.s_cap = fp.ga_chunk = 0; fp.attn_lds = 0; fp.pa = PaPlan{}; fp.sa = SaPlan{};         // (everything but pg, which only
     fp.qkv = fp.o = fp.gu = fp.down = fp.head = GemmRoute{};                                // AK_PREFILL fills and reads)
     fp.S_o = fp.ksp_o = fp.S_d = fp.ksp_d = 0;
     fp.small = small_path_ok(pc, tab);
@@ -1673,7 +1741,11 @@ static void plan_forward(const PlanCtx &pc, const RowTab &tab, int s_max, FwdPla
         fp.nsplit = gp.nsplit; fp.ga_chunk = gp.chunk; fp.s_cap = 0; fp.attn_lds = gp.lds;
     };
     const bool prefill = !fp.small && prefill_attn_ok(pc, tab, s_max), grouped = !prefill && grouped_attn_ok(pc, tab);
-    if (grouped && t.attn_grouped >= 2) {
+    if (!fp.small && !prefill && shared_attn_ok(pc, tab)) {       // the cross-stream route, ahead of every per-stream one
+        fp.attn = AK_SHARED;
+        fp.sa = plan_shared_attn(c.head_dim, c.n_heads, c.n_kv_heads, tab.shared_keys, s_max, tab.n_rows, tab.n_groups, pc.cus);
+        fp.nsplit = fp.sa.psplits + fp.sa.ssplits; fp.attn_lds = fp.sa.lds;
+    } else if (grouped && t.attn_grouped >= 2) {
         take_grouped();
     } else if (!fp.small && attn_oproj_ok(pc, tab, s_max)) {
         fp.attn = AK_OPROJ;
@@ -1710,6 +1782,9 @@ static int launch_attn_bf16(sd_session *s, const bf16_t *q, const RowTab &tab, c
 // the grouped-query route (grouped_attn.h), defined last in the file for the same reason
 template <typename T>
 static int launch_attn_grouped(sd_session *s, const T *q, const RowTab &tab, const FwdPlan &fp, int layer, T *out, hipStream_t st);
+// the shared-prefix route (shared_attn.h), likewise
+template <typename T>
+static int launch_attn_shared(sd_session *s, const T *q, const RowTab &tab, const FwdPlan &fp, int layer, T *out, hipStream_t st);
 
 // ---- small-model decode path (small_kernels.h): 5 launches per layer + the head --------------------------------
 static int forward_small(sd_session *s, const RowTab &tab, const FwdPlan &fp, float *logits_out, long ld_logits, const HeadReq *rq,
@@ -1897,6 +1972,7 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
                 if (fp.attn == AK_OPROJ) rc = launch_attn_oproj<T>(s, qb, tab, fp, l, at, m->wo[l], xn_o, st);
                 else if (fp.attn == AK_PREFILL) rc = launch_attn_prefill<T>(s, qb, tab, fp, l, at, st);
                 else if (fp.attn == AK_GROUPED) rc = launch_attn_grouped<T>(s, qb, tab, fp, l, at, st);
+                else if (fp.attn == AK_SHARED) rc = launch_attn_shared<T>(s, qb, tab, fp, l, at, st);
             }
             if (fp.attn == AK_KERNEL) rc = launch_attn_d<T>(s, qb, tab, fp, l, at, st);
             if (rc != SD_OK) return rc;
@@ -2204,8 +2280,10 @@ extern "C" int sd_session_compact_kv(sd_session *s, int base_len, const int32_t 
 // over the weights.  Every item names its own session (KV arena), token buffer (device int32, indexed by absolute
 // position), cache length pos0, number of new rows and how many of its last rows need logits.  Activations use
 // items[0].session's scratch; all sessions must belong to the same model.  Logit rows come out packed in item order.
+// donor / shared_keys (sd_batch_forward_shared): rows [0, shared_keys) of every item's arena are copies of the donor's - the
+// caller's promise, which nothing checks - so the pass may read them there once (shared_attn_ok); NULL / 0: no such promise.
 static int batch_forward(const sd_batch_item *items, int n_items, float *logits_out, long ld_logits, const HeadReq *rq,
-                         HeadOut *ho, void *stream) {
+                         HeadOut *ho, void *stream, const sd_session *donor = nullptr, int shared_keys = 0) {
     SD_REQUIRE(items && n_items >= 1 && n_items <= SD_MAX_STREAMS, "sd_batch_forward: 1..%d items", SD_MAX_STREAMS);
     sd_session *s0 = items[0].session;
     SD_REQUIRE(s0, "sd_batch_forward: null session");
@@ -2222,6 +2300,7 @@ static int batch_forward(const sd_batch_item *items, int n_items, float *logits_
             return SD_ERR_CAPACITY;
         }
         SD_REQUIRE(it.session->kv_fp8 == s0->kv_fp8, "sd_batch_forward: item %d: KV arenas of different dtypes", i);
+        SD_REQUIRE(!donor || shared_keys <= it.pos0, "sd_batch_forward_shared: %d shared keys past item %d's pos0 %d", shared_keys, i, it.pos0);
         bind_stream(tab, i, it.session, it.seq);
         for (int r = 0; r < it.n_new; ++r) {
             tab.row_pos[rows + r] = it.pos0 + r;
@@ -2240,8 +2319,23 @@ static int batch_forward(const sd_batch_item *items, int n_items, float *logits_
     tab.n_rows = rows;
     tab.n_streams = n_items;
     tab.n_logit_rows = nlog;
+    if (donor && shared_keys) {
+        SD_REQUIRE(shared_keys > 0 && shared_keys <= donor->max_seq, "sd_batch_forward_shared: %d shared keys outside the donor's %d positions",
+                   shared_keys, donor->max_seq);
+        SD_REQUIRE(donor->m == s0->m && !donor->kv_fp8 == !s0->kv_fp8, "sd_batch_forward_shared: a donor of another model or arena type");
+        tab.shared_keys = shared_keys;
+        tab.shared_kv = donor->kv;
+        tab.shared_max_seq = donor->max_seq;
+        tab.shared_scale = donor->kv_scale;
+    }
     finish_table(tab);
     return run_forward(s0, tab, s_max, logits_out, ld_logits, rq, ho, stream);
+}
+
+extern "C" int sd_batch_forward_shared(const sd_batch_item *items, int n_items, const sd_session *donor, int shared_keys, float *logits_out,
+                                       long ld_logits, void *stream) {
+    SD_REQUIRE(shared_keys >= 0, "sd_batch_forward_shared: %d shared keys", shared_keys);
+    return batch_forward(items, n_items, logits_out, ld_logits, nullptr, nullptr, stream, donor, shared_keys);
 }
 
 extern "C" int sd_batch_forward(const sd_batch_item *items, int n_items, float *logits_out, long ld_logits,
@@ -2338,7 +2432,8 @@ extern "C" int sd_gemm_route(int N, int K, int M, int need, sd_gemm_route_info *
     return SD_OK;
 }
 
-static_assert(SD_ATTN_KERNEL == AK_KERNEL && SD_ATTN_OPROJ == AK_OPROJ && SD_ATTN_PREFILL == AK_PREFILL && SD_ATTN_GROUPED == AK_GROUPED,
+static_assert(SD_ATTN_KERNEL == AK_KERNEL && SD_ATTN_OPROJ == AK_OPROJ && SD_ATTN_PREFILL == AK_PREFILL && SD_ATTN_GROUPED == AK_GROUPED &&
+                  SD_ATTN_SHARED == AK_SHARED,
               "specdec.h publishes AttnKind");
 
 // attn_kernel's key splits for a pass - by the function launch_attn's plan comes from
@@ -2520,5 +2615,44 @@ static int launch_attn_grouped(sd_session *s, const T *q, const RowTab &tab, con
         if (tab.kv_fp8) launch(integral_constant<int, 128>{}, std::true_type{}); else launch(integral_constant<int, 128>{}, std::false_type{});
     }
     ++s->grouped_attn_launches;
+    return SD_OK;
+}
+
+// ---- the shared-prefix attention (forward declaration in front of forward_small), after the grouped kernels it builds on
+#include "shared_attn.h"
+template <typename T>
+static int launch_attn_shared(sd_session *s, const T *q, const RowTab &tab, const FwdPlan &fp, int layer, T *out, hipStream_t st) {
+    const sd_model_config &c = s->m->cfg;
+    const int G = c.n_heads / c.n_kv_heads;
+    const SaPlan &p = fp.sa;
+    SD_REQUIRE((c.head_dim == 64 || c.head_dim == 128) && G >= 1 && G <= 8 && !tab.tree && tab.shared_kv && tab.shared_keys >= 1 &&
+                   tab.shared_keys <= tab.shared_max_seq && p.psplits >= 1 && p.ssplits >= 1 &&
+                   (p.psplits + p.ssplits) * tab.n_groups <= ATT_MAX_PARTS && p.pchunk % 64 == 0 && p.schunk % 64 == 0 &&
+                   p.tiles * 64 >= G * tab.n_rows && (long)p.psplits * p.pchunk >= tab.shared_keys &&
+                   (long)p.ssplits * p.schunk >= fp.s_max - tab.shared_keys,
+               "internal: shared attention planned for head_dim %d, %d heads per KV head, %d tiles, %d x %d + %d x %d keys", c.head_dim,
+               G, p.tiles, p.psplits, p.pchunk, p.ssplits, p.schunk);
+    auto launch = [&](auto d, auto kv8) {
+        constexpr int D = decltype(d)::value;
+        constexpr bool KV8 = decltype(kv8)::value;
+        static bool attr = false;                                 // (one flag per instantiation of this lambda)
+        if (!attr) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(attn_shared_kernel<T, D, KV8>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)ga_lds_bytes(D));
+            attr = true;
+        }
+        const int wgs = c.n_kv_heads * (p.tiles * p.psplits + tab.n_groups * p.ssplits);
+        hipLaunchKernelGGL((attn_shared_kernel<T, D, KV8>), dim3(wgs), dim3(256), ga_lds_bytes(D), st, q, tab, layer, c.n_heads,
+                           c.n_kv_heads, c.arch, 1.0f / sqrtf((float)D), p.tiles, p.psplits, p.pchunk, p.ssplits, p.schunk, s->attn_part);
+        hipLaunchKernelGGL((attn_combine_kernel<T, D>), dim3(c.n_heads, tab.n_groups), dim3(128), 0, st, (const float *)s->attn_part,
+                           tab, out, c.n_heads, p.psplits + p.ssplits);
+    };
+    using std::integral_constant;
+    if (c.head_dim == 64) {
+        if (tab.kv_fp8) launch(integral_constant<int, 64>{}, std::true_type{}); else launch(integral_constant<int, 64>{}, std::false_type{});
+    } else {
+        if (tab.kv_fp8) launch(integral_constant<int, 128>{}, std::true_type{}); else launch(integral_constant<int, 128>{}, std::false_type{});
+    }
+    ++s->shared_attn_launches;
     return SD_OK;
 }

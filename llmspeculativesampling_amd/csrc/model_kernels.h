@@ -56,6 +56,12 @@ struct RowTab {
     const float *kv_scale[SD_MAX_STREAMS];          // fp8: per (layer, k|v, kv head) scales [L][2][Hkv], stored fp8(x * (1 / scale)), read fp8 * scale
     // attention groups: <= ATT_TQ consecutive rows of one stream (first row, count, position of the first row, stream)
     int grp_row0[SD_MAX_GROUPS], grp_n[SD_MAX_GROUPS], grp_pos[SD_MAX_GROUPS], grp_stream[SD_MAX_GROUPS];
+    // shared prefix (sd_batch_forward_shared; 0 / NULL on every other path): rows [0, shared_keys) of every stream's arena are
+    // copies of the same rows of the arena shared_kv (capacity shared_max_seq, fp8 scales shared_scale), which
+    // attn_shared_kernel reads in their place
+    int shared_keys, shared_max_seq;
+    const void *shared_kv;
+    const float *shared_scale;
 };
 
 // Activation operands of the bf16 GEMMs (normalised rows, attention output, MLP activation, OPT projections) are kept

@@ -727,6 +727,7 @@ struct PromptQueue {
     // a shared prompt prefix: the donors hold positions [0, shared_rows) of the two models
     sd_session *donor_draft = nullptr, *donor_target = nullptr;
     int shared_rows = 0;
+    int copied[SD_MAX_STREAMS] = {};                              // rows [0, copied[i]) of slot i's arenas are copies of the donors'
     int prompt_rows = 0, copied_rows = 0;                         // target rows forwarded for prompts; KV rows copied per model
 };
 
@@ -753,6 +754,7 @@ static int queue_boundary(PromptQueue &q, sd_batch_stream *slots, int n_slots, i
             // the shared prefix comes from the donors; the last prompt token is always fed as the first decode row
             const int c = std::min(q.shared_rows, p.L - 1);
             s.draft_len = s.target_len = c;
+            q.copied[i] = c;
             if (c > 0) {
                 d_copy[n_copy] = sd_kv_copy_item{s.draft, 0, c};
                 t_copy[n_copy++] = sd_kv_copy_item{s.target, 0, c};
@@ -1031,7 +1033,14 @@ static int lockstep_loop(const char *who, sd_batch_stream *streams, int n_stream
                 if (params) prows.resize(rows.size(), params[request_of(s)]);   // (every row of the stream takes its triple)
             }
             add_joiners(passes[p], 1);
-            if ((rc = batch_forward(items.data(), (int)items.size(), sc.target.logits, sc.target.ld_logits, nullptr, nullptr, stream)) != SD_OK)
+            // a queue with a shared prefix: what every stream of the pass (joiner chunks included) copied from the donor may be
+            // read there once (sd_batch_forward_shared's promise; the planner decides whether the pass does)
+            int shared = q && q->donor_target ? q->shared_rows : 0;
+            for (const sd_batch_item &it : items)
+                for (int i = 0; shared > 0 && i < n_streams; ++i)
+                    if (streams[i].target == it.session) shared = std::min({shared, q->copied[i], (int)it.pos0});
+            if ((rc = batch_forward(items.data(), (int)items.size(), sc.target.logits, sc.target.ld_logits, nullptr, nullptr, stream,
+                                    shared > 0 ? q->donor_target : nullptr, shared)) != SD_OK)
                 break;
             if (m == 0) continue;                                 // (joiner rows only)
             // one pass holds every stream: the rows' candidate lists (behind the CandRows of the workspace) serve the

@@ -14,7 +14,7 @@ import ctypes as C
 import math
 import os
 import sys
-from typing import Callable, Dict, List, Optional
+from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 
@@ -508,6 +508,11 @@ class Session:
         attention route (SD_ATTN_GROUPED; a batched pass counts on its first session).  A host counter."""
         return int(lib.sd_session_grouped_attn_launches(self.handle))
 
+    def shared_attn_launches(self) -> int:
+        """attn_shared_kernel launches of this session so far: one per layer of every pass on the shared-prefix attention
+        route (batch_forward(shared=...), SD_ATTN_SHARED; a batched pass counts on its first session).  A host counter."""
+        return int(lib.sd_session_shared_attn_launches(self.handle))
+
     def past_key_values(self):
         """The reference's tuple layout: one (k, v) pair of (1, H_kv, S, D) views per layer."""
         S = self.cache_len
@@ -550,10 +555,12 @@ def as_specdec_model(model, dtype: Optional[torch.dtype] = None) -> SpecDecModel
 
 
 def batch_forward(sessions: List[Session], seqs: List[torch.Tensor], n_new: List[int], n_logits: List[int],
-                  logits_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  logits_out: Optional[torch.Tensor] = None, shared: Optional[Tuple[Session, int]] = None) -> torch.Tensor:
     """Stream-batched forward (sd_batch_forward): stream i feeds seqs[i][cache_len : cache_len + n_new[i]] (seqs[i] is
     that stream's whole int32 token buffer on the device, indexed by absolute position).  Returns the packed fp32 logits
-    of the last n_logits[i] rows of every stream, in stream order.  All sessions share one model."""
+    of the last n_logits[i] rows of every stream, in stream order.  All sessions share one model.
+    ``shared=(donor, keys)`` promises that positions [0, keys) of every session's arena are copies of ``donor``'s
+    (copy_kv_from), so the pass may read them there once for all streams (sd_batch_forward_shared; SD_ATTN_SHARED)."""
     B = len(sessions)
     items = (_lib.SdBatchItem * B)()
     for i, (ses, sq) in enumerate(zip(sessions, seqs)):
@@ -567,8 +574,15 @@ def batch_forward(sessions: List[Session], seqs: List[torch.Tensor], n_new: List
     if logits_out is None:
         logits_out = sessions[0].logits
     assert tot <= logits_out.shape[0]
-    check(lib.sd_batch_forward(items, B, logits_out.data_ptr() if tot else None, logits_out.stride(0), _stream()),
-          "sd_batch_forward")
+    if shared is not None:
+        donor, keys = shared
+        if donor.kv_fp8 and any(s.kv_fp8 and not torch.equal(s.kv_scale, donor.kv_scale) for s in sessions):
+            raise ValueError("batch_forward: shared: an fp8 arena's scale table differs from the donor's")
+        check(lib.sd_batch_forward_shared(items, B, donor.handle, int(keys), logits_out.data_ptr() if tot else None,
+                                          logits_out.stride(0), _stream()), "sd_batch_forward_shared")
+    else:
+        check(lib.sd_batch_forward(items, B, logits_out.data_ptr() if tot else None, logits_out.stride(0), _stream()),
+              "sd_batch_forward")
     for ses, n in zip(sessions, n_new):
         ses.cache_len += int(n)
     return logits_out[:tot]
