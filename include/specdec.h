@@ -372,6 +372,26 @@ int sd_pack_weight_w12(const void *w_tiled, void *codes, void *meta, int N, int 
 int sd_unpack_weight_w12(const void *codes, const void *meta, void *w_tiled, int N, int K, void *stream);
 int sd_model_set_w12(sd_model *m, int which, int layer, const void *codes, const void *meta);
 
+/* 4-bit group-quantised records of a bf16 matrix.  Groups are 128 consecutive k of one output row with
+ * a bf16 scale s and a zero point z in 0..15; codes q are in 0..15 and the weight is DEFINED as
+ * w = bf16_rne(float(s) * float(q - z)).  A record is a 16-row tile times one group, 1088 bytes: 64 lanes x 16 bytes of codes
+ * (dword u of lane l: the eight codes of W[n = l % 16][k-step u, quad l / 16], code e in bits 4e..4e+3) and 16 dwords
+ * s | z << 16, one per row; record (n-tile, group) lies at index n-tile * K / 128 + group.  4.25 bits per weight.
+ * The model keeps the tiled bf16 matrix of exactly these w for every other route; the <= 8-row passes of the norm-on-load
+ * route stream the records and decode them in registers to the same bits.
+ * sd_q4_bytes: size of the records (N % 16 == 0, K % 128 == 0).
+ * sd_pack_weight_q4: from plain row-major q (uint8 [N][K]), scales (bf16 [N][K / 128]) and zeros (uint8 [N][K / 128]) writes
+ *   the records (128-byte aligned) AND the tiled bf16 matrix of w (sd_pack_weight_bf16's layout).
+ * sd_unpack_weight_q4: records -> the tiled bf16 layout (the format's executable definition; tests).
+ * sd_model_set_q4: registers the records of layer `layer`'s matrix `which` (an SD_W12_* id) with a bf16 model whose tiled
+ *   copy of that matrix holds the same w (NULL: unregisters).  A matrix has 12-bit records or 4-bit records, not both: each
+ *   of the two setters refuses a matrix the other one has records for.  Not while a forward is in flight. */
+int sd_q4_bytes(int N, int K, size_t *bytes);
+int sd_pack_weight_q4(const void *q, const void *scales, const void *zeros, void *records, void *w_tiled_out, int N, int K,
+                      void *stream);
+int sd_unpack_weight_q4(const void *records, void *w_tiled, int N, int K, void *stream);
+int sd_model_set_q4(sd_model *m, int which, int layer, const void *records);
+
 /* Row-major bf16 activations [M][K] (K % 32 == 0) -> the GEMM operand layout the engine keeps them in between
  * kernels: 16-row tiles [ceil(M/16)][K/32][lane 0..63][8 bf16], lane = 16*(k/8 % 4) + m % 16, so that a wave's MFMA
  * fragment is one contiguous 1 KiB read.  x_tiled must hold roundup(M,16) * K elements. */
@@ -447,6 +467,7 @@ int sd_session_set_kv_fp8(sd_session *s, const float *scales);
  * synchronisation. */
 int sd_session_prefill_attn_launches(const sd_session *s);
 int sd_session_w12_launches(const sd_session *s);
+int sd_session_q4_launches(const sd_session *s);   /* ... that streamed 4-bit records */
 /* The matrix-core prefill attention has two kernels: attn_prefill_kernel keeps a row group's whole score tile in LDS and
  * runs while that fits (2048 keys at head_dim 128, 2176 at 64); past it - by default where sd_prefill_attn_route says so, and
  * at any context when SD_PREFILL_ATTN_BLOCK=K (K > 0, rounded up to a multiple of 64) is set - attn_prefill_blocked_kernel

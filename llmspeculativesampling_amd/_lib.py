@@ -324,6 +324,11 @@ SYMBOLS = [
     ("sd_unpack_weight_w12", _I, [_VP, _VP, _VP, _I, _I, _VP]),
     ("sd_model_set_w12", _I, [_VP, _I, _I, _VP, _VP]),
     ("sd_session_w12_launches", _I, [_VP]),
+    ("sd_q4_bytes", _I, [_I, _I, C.POINTER(C.c_size_t)]),
+    ("sd_pack_weight_q4", _I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _VP]),
+    ("sd_unpack_weight_q4", _I, [_VP, _VP, _I, _I, _VP]),
+    ("sd_model_set_q4", _I, [_VP, _I, _I, _VP]),
+    ("sd_session_q4_launches", _I, [_VP]),
     ("sd_pack_activation_bf16", _I, [_VP, _VP, _I, _I, _VP]),
     ("sd_gemm_bf16", _I, [_VP, _VP, _I, _I, _I, _I, _VP, C.c_size_t, _VP, C.POINTER(C.c_int), _VP]),
     ("sd_gemm_route", _I, [_I, _I, _I, _I, C.POINTER(SdGemmRouteInfo)]),

@@ -40,6 +40,7 @@ struct sd_model {
     sd_model_config cfg;
     sd_model_weights w;
     std::vector<const void *> wqkv, bqkv, wo, bo, wgu, bfc1, wdown, bfc2, n1w, n1b, n2w, n2b;
+    std::vector<const unsigned *> q4[3];   // [SD_W12_*][layer]: 4-bit group-quantised records of that matrix (sd_model_set_q4; NULL: none)
     std::vector<W12Arg> w12[3];   // [SD_W12_*][layer]: 12-bit records of that matrix (sd_model_set_w12; codes == NULL: none)
 };
 
@@ -81,6 +82,7 @@ struct sd_session {
     int kv_fp8;         // the arena holds fp8 e4m3 (sd_session_set_kv_fp8)
     int prefill_attn_launches;   // attn_prefill_kernel + attn_prefill_blocked_kernel launches so far (sd_session_prefill_attn_launches: the route, for tests)
     int prefill_attn_blocked_launches;   // ... of which attn_prefill_blocked_kernel
+    int q4_launches;             // GEMM launches that streamed 4-bit weight records so far (sd_session_q4_launches)
     int w12_launches;            // GEMM launches that streamed 12-bit weight records so far (sd_session_w12_launches)
     int grouped_attn_launches;   // attn_grouped_kernel launches so far (sd_session_grouped_attn_launches: the route, for tests)
     int shared_attn_launches;    // attn_shared_kernel launches so far (sd_session_shared_attn_launches)
@@ -149,6 +151,7 @@ extern "C" int sd_model_create(const sd_model_config *cfg, const sd_model_weight
     copy_ptrs(m->n1w, w->norm1_w, L); copy_ptrs(m->n1b, w->norm1_b, L);
     copy_ptrs(m->n2w, w->norm2_w, L); copy_ptrs(m->n2b, w->norm2_b, L);
     for (auto &v : m->w12) v.assign(L, W12Arg{nullptr, nullptr});
+    for (auto &v : m->q4) v.assign(L, nullptr);
     *out = m;
     return SD_OK;
 }
@@ -183,7 +186,24 @@ extern "C" int sd_model_set_w12(sd_model *m, int which, int layer, const void *c
     SD_REQUIRE(m->cfg.dtype == SD_BF16, "sd_model_set_w12: the 12-bit records hold bf16 weights");
     SD_REQUIRE((codes != nullptr) == (meta != nullptr), "sd_model_set_w12: codes and meta come together");
     SD_REQUIRE(((uintptr_t)codes & 127) == 0 && ((uintptr_t)meta & 15) == 0, "sd_model_set_w12: codes must be 128-byte, meta 16-byte aligned");
+    SD_REQUIRE(!codes || !m->q4[which][layer], "sd_model_set_w12: matrix %d of layer %d has 4-bit records registered", which, layer);
     m->w12[which][layer] = W12Arg{(const unsigned *)codes, (const u32x4 *)meta};
+    return SD_OK;
+}
+
+// ---- 4-bit group-quantised weight records (q4.h)
+extern "C" int sd_q4_bytes(int N, int K, size_t *bytes) {
+    SD_REQUIRE(bytes && N > 0 && K > 0 && N % 16 == 0 && K % 128 == 0, "sd_q4_bytes: need N %% 16 == 0, K %% 128 == 0 (got %d x %d) and no null pointer", N, K);
+    *bytes = (size_t)(N / 16) * (K / 128) * 1088;
+    return SD_OK;
+}
+// (sd_pack_weight_q4 / sd_unpack_weight_q4: at the end of the file, with the other kernels that read the records)
+extern "C" int sd_model_set_q4(sd_model *m, int which, int layer, const void *records) {
+    SD_REQUIRE(m && which >= 0 && which < 3 && layer >= 0 && layer < m->cfg.n_layers, "sd_model_set_q4: bad matrix %d of layer %d", which, layer);
+    SD_REQUIRE(m->cfg.dtype == SD_BF16, "sd_model_set_q4: the 4-bit records hold bf16 weights");
+    SD_REQUIRE(((uintptr_t)records & 127) == 0, "sd_model_set_q4: records must be 128-byte aligned");
+    SD_REQUIRE(!records || !m->w12[which][layer].codes, "sd_model_set_q4: matrix %d of layer %d has 12-bit records registered", which, layer);
+    m->q4[which][layer] = (const unsigned *)records;
     return SD_OK;
 }
 
@@ -650,6 +670,7 @@ extern "C" int sd_session_create(sd_model *m, int max_seq, int max_rows, void *k
     s->gram_cap = 0;
     s->prefill_attn_launches = 0;
     s->w12_launches = 0;
+    s->q4_launches = 0;
     s->grouped_attn_launches = 0;
     s->shared_attn_launches = 0;
     s->prefill_attn_blocked_launches = 0;
@@ -731,6 +752,7 @@ extern "C" int sd_session_set_grammar(sd_session *s, const sd_grammar *g, int32_
 // whichever kernel ran).  A batched pass counts on its first session.
 extern "C" int sd_session_prefill_attn_launches(const sd_session *s) { return s ? s->prefill_attn_launches : 0; }
 extern "C" int sd_session_w12_launches(const sd_session *s) { return s ? s->w12_launches : 0; }
+extern "C" int sd_session_q4_launches(const sd_session *s) { return s ? s->q4_launches : 0; }
 // attn_grouped_kernel launches of this session so far: one per layer of every pass on the grouped-query route
 extern "C" int sd_session_grouped_attn_launches(const sd_session *s) { return s ? s->grouped_attn_launches : 0; }
 // attn_shared_kernel launches of this session so far: one per layer of every pass on the shared-prefix route
@@ -1558,6 +1580,15 @@ static int launch_gemm_fin(sd_session *s, const GemmRoute &pl, const void *W, co
 static int launch_gemm_xn_w12(sd_session *s, bool qkv, W12Arg W, const void *X, int M, int N, int K, const void *norm_w, float eps,
                               GemmEpiT<bf16_t> e, hipStream_t st);
 static int launch_gemm_fin_w12(sd_session *s, const GemmRoute &pl, W12Arg W, const void *X, int M, int N, int K, hipStream_t st);
+// ... and reading 4-bit group-quantised records (q4.h), likewise defined at the end
+static int launch_gemm_xn_q4(sd_session *s, bool qkv, const unsigned *W, const void *X, int M, int N, int K, const void *norm_w, float eps,
+                             GemmEpiT<bf16_t> e, hipStream_t st);
+static int launch_gemm_fin_q4(sd_session *s, const GemmRoute &pl, const unsigned *W, const void *X, int M, int N, int K, hipStream_t st);
+template <typename T>
+static const unsigned *q4_of(const sd_model *m, int which, int l) {
+    if constexpr (std::is_same<T, bf16_t>::value) return m->q4[which][l];
+    return nullptr;
+}
 // the 12-bit records of layer l's matrix `which`, if this pass may read them (bf16 model, a copy registered)
 template <typename T>
 static W12Arg w12_of(const sd_model *m, int which, int l) {
@@ -1945,6 +1976,9 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
         // weight layout, else slabs for the stand-alone epilogue)
         if (l == 0 && fp.embed_qkv) {
             if ((rc = launch_small_qkv<PRO_EMBED>(s, qkv_epi<bf16_t>(s, tab, 0), embed_pro(s, fp), st)) != SD_OK) return rc;
+        } else if (xn_q && q4_of<T>(m, SD_W12_QKV, l)) {
+            rc = launch_gemm_xn_q4(s, true, q4_of<T>(m, SD_W12_QKV, l), h, n_new, qkv_cols(c), H, m->n1w[l], c.norm_eps, qkv_epi<bf16_t>(s, tab, l), st);
+            if (rc != SD_OK) return rc;
         } else if (xn_q && w12_of<T>(m, SD_W12_QKV, l).codes) {
             rc = launch_gemm_xn_w12(s, true, w12_of<T>(m, SD_W12_QKV, l), h, n_new, qkv_cols(c), H, m->n1w[l], c.norm_eps, qkv_epi<bf16_t>(s, tab, l), st);
             if (rc != SD_OK) return rc;
@@ -1987,7 +2021,10 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
                                          pre ? m->n2b[l] : m->n1b[l], pre ? RES_PRE : RES_POST, st)) != SD_OK)
             return rc;
         // ---- gate/up (fc1) -> SiLU * up / ReLU -> activation buffer
-        if (xn_o && w12_of<T>(m, SD_W12_GATE_UP, l).codes) {
+        if (xn_o && q4_of<T>(m, SD_W12_GATE_UP, l)) {
+            rc = launch_gemm_xn_q4(s, false, q4_of<T>(m, SD_W12_GATE_UP, l), h, n_new, gu_cols(c), H, m->n2w[l], c.norm_eps, act_epi<bf16_t>(s, l), st);
+            if (rc != SD_OK) return rc;
+        } else if (xn_o && w12_of<T>(m, SD_W12_GATE_UP, l).codes) {
             rc = launch_gemm_xn_w12(s, false, w12_of<T>(m, SD_W12_GATE_UP, l), h, n_new, gu_cols(c), H, m->n2w[l], c.norm_eps, act_epi<bf16_t>(s, l), st);
             if (rc != SD_OK) return rc;
         } else if (xn_o) {
@@ -2007,7 +2044,9 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
         }
         // ---- down projection (fc2) + residual (+ the next norm).  With the norm-on-load seam its last k-slab's workgroups add
         // the residual and the next layer's QKV normalises on load (no residual+norm launch)
-        if (xn_d && w12_of<T>(m, SD_W12_DOWN, l).codes) {
+        if (xn_d && q4_of<T>(m, SD_W12_DOWN, l)) {
+            if ((rc = launch_gemm_fin_q4(s, fp.down, q4_of<T>(m, SD_W12_DOWN, l), ac, n_new, H, I, st)) != SD_OK) return rc;
+        } else if (xn_d && w12_of<T>(m, SD_W12_DOWN, l).codes) {
             if ((rc = launch_gemm_fin_w12(s, fp.down, w12_of<T>(m, SD_W12_DOWN, l), ac, n_new, H, I, st)) != SD_OK) return rc;
         } else if (xn_d) {
             if ((rc = launch_gemm_fin<H16>(s, fp.down, m->wdown[l], ac, n_new, H, I, nullptr, st)) != SD_OK) return rc;
@@ -2654,5 +2693,64 @@ static int launch_attn_shared(sd_session *s, const T *q, const RowTab &tab, cons
         if (tab.kv_fp8) launch(integral_constant<int, 128>{}, std::true_type{}); else launch(integral_constant<int, 128>{}, std::false_type{});
     }
     ++s->shared_attn_launches;
+    return SD_OK;
+}
+
+// ---- the norm-on-load and the finishing GEMM on 4-bit group-quantised records, their packer and expander (forward
+// declarations above launch_gemm_xn's users): new kernels go behind every other kernel of the code object
+#include "q4.h"
+static int launch_gemm_xn_q4(sd_session *s, bool qkv, const unsigned *W, const void *X, int M, int N, int K, const void *norm_w, float eps,
+                             GemmEpiT<bf16_t> e, hipStream_t st) {
+    ProfScope ps(s, PC_GEMM, st);
+    SD_REQUIRE(M >= 1 && M <= 8 && N % 16 == 0 && K % 1024 == 0 && K <= 8192, "norm-on-load GEMM on 4-bit records: M=%d N=%d K=%d", M, N, K);
+    e.nrm_ssq = s->ssq; e.nrm_w = (const bf16_t *)norm_w; e.nrm_nt = K / 16; e.nrm_eps = eps;
+    auto go = [&](auto epi, auto c) {
+        hipLaunchKernelGGL((gemm_q4_stream_xn<decltype(epi)::value, decltype(c)::value>), dim3(N / 16), dim3(256),
+                           (size_t)K * sizeof(bf16_t), st, W, (const bf16_t *)X, M, N, K, e);
+    };
+    auto by_rows = [&](auto epi) {
+        using std::integral_constant;
+        if (M <= 4) go(epi, integral_constant<int, 4>{});
+        else if (M == 5) go(epi, integral_constant<int, 3>{});
+        else go(epi, integral_constant<int, 2>{});
+    };
+    if (qkv) by_rows(std::integral_constant<int, EPI_QKV_ROPE>{});
+    else by_rows(std::integral_constant<int, EPI_ACT_SILU>{});
+    SD_LAUNCH_CHECK();
+    ++s->q4_launches;
+    return SD_OK;
+}
+static int launch_gemm_fin_q4(sd_session *s, const GemmRoute &pl, const unsigned *W, const void *X, int M, int N, int K, hipStream_t st) {
+    ProfScope ps(s, PC_GEMM, st);
+    SD_REQUIRE(pl.kind == GK_STREAM && M <= 16 && K % 128 == 0 && (size_t)pl.S * 16 * N <= s->part_floats,
+               "k-split GEMM with residual epilogue on 4-bit records: M=%d N=%d K=%d", M, N, K);
+    GemmEpiT<bf16_t> e = {};
+    e.res_x = (bf16_t *)s->x; e.res_h = (bf16_t *)s->h; e.res_ssq = s->ssq;
+    const unsigned want = s->fin_epoch + (unsigned)(pl.S - 1) + (unsigned)s->skew_now;
+    hipLaunchKernelGGL(gemm_q4_stream_fin<0>, dim3((N / 16) * pl.S), dim3(256), 0, st, W, (const bf16_t *)X, s->part,
+                       M, N, K, pl.S, pl.ksp, e, s->fin_ctr, want, s->wait_status);
+    SD_LAUNCH_CHECK();
+    s->fin_epoch += (unsigned)(pl.S - 1);
+    ++s->q4_launches;
+    return SD_OK;
+}
+extern "C" int sd_pack_weight_q4(const void *q, const void *scales, const void *zeros, void *records, void *w_tiled_out, int N, int K,
+                                 void *stream) {
+    SD_REQUIRE(q && scales && zeros && records && w_tiled_out && N > 0 && K > 0 && N % 16 == 0 && K % 128 == 0,
+               "sd_pack_weight_q4: need N %% 16 == 0 and K %% 128 == 0 (got %d x %d) and no null pointer", N, K);
+    SD_REQUIRE(((uintptr_t)records & 127) == 0 && ((uintptr_t)w_tiled_out & 15) == 0 && ((uintptr_t)q & 7) == 0 && ((uintptr_t)scales & 1) == 0,
+               "sd_pack_weight_q4: records must be 128-byte, the tiles 16-byte, q 8-byte aligned");
+    hipLaunchKernelGGL(q4_pack_kernel<0>, dim3((unsigned)((size_t)(N / 16) * (K / 128))), dim3(64), 0, (hipStream_t)stream,
+                       (const uint8_t *)q, (const uint16_t *)scales, (const uint8_t *)zeros, (unsigned *)records, (u32x4 *)w_tiled_out, K);
+    SD_LAUNCH_CHECK();
+    return SD_OK;
+}
+extern "C" int sd_unpack_weight_q4(const void *records, void *w_tiled, int N, int K, void *stream) {
+    SD_REQUIRE(records && w_tiled && N > 0 && K > 0 && N % 16 == 0 && K % 128 == 0,
+               "sd_unpack_weight_q4: need N %% 16 == 0 and K %% 128 == 0 (got %d x %d) and no null pointer", N, K);
+    SD_REQUIRE(((uintptr_t)records & 15) == 0 && ((uintptr_t)w_tiled & 15) == 0, "sd_unpack_weight_q4: records and tiles must be 16-byte aligned");
+    hipLaunchKernelGGL(q4_unpack_kernel<0>, dim3((unsigned)((size_t)(N / 16) * (K / 128))), dim3(64), 0, (hipStream_t)stream,
+                       (const unsigned *)records, (u32x4 *)w_tiled, K);
+    SD_LAUNCH_CHECK();
     return SD_OK;
 }

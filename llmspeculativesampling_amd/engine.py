@@ -78,13 +78,40 @@ def c_model_config(cfg: ModelConfig, dtype: torch.dtype, max_pos: Optional[int] 
         logits_bf16_round=int(dtype != torch.float32), fused_layout=int(fused_layout(cfg, dtype) if fused is None else fused))
 
 
+Q4_GROUP = 128                                   # k per quantisation group of a q4 model (csrc/q4.h)
+
+
+def q4_quantise(w: torch.Tensor):
+    """Round-to-nearest 4-bit quantisation of a float32 [N][K] matrix in groups of 128 k per row -> (q uint8 [N][K], s bf16
+    [N][K / 128], z uint8 [N][K / 128]): s = (max - min) / 15 rounded to bf16, z = round(-min / s) and q = round(w / s) + z,
+    both clamped to 0..15; a constant group gets s = 0 (and z = q = 0).  The model's weight is bf16(s * (q - z))."""
+    N, K = w.shape
+    g = w.reshape(N, K // Q4_GROUP, Q4_GROUP)
+    lo, hi = g.amin(-1), g.amax(-1)
+    s = ((hi - lo) / 15).to(torch.bfloat16)
+    sf = s.float()
+    on, div = sf != 0, torch.where(sf != 0, sf, torch.ones_like(sf))
+    z = torch.where(on, torch.round(-lo / div), torch.zeros_like(sf)).clamp_(0, 15)
+    q = torch.where(on[..., None], torch.round(g / div[..., None]) + z[..., None], torch.zeros_like(g)).clamp_(0, 15)
+    return q.reshape(N, K).to(torch.uint8), s, z.to(torch.uint8)
+
+
 class SpecDecModel:
     """Weights in HBM + sd_model handle.  Exposes what the reference reads off a model object:
     ``.config.is_encoder_decoder`` (speculative_sampling.py:1942) and ``.device`` (:1909)."""
 
     def __init__(self, cfg: ModelConfig, get_tensor: Callable[[str], torch.Tensor],
                  dtype: torch.dtype = torch.bfloat16, device: str = "cuda", max_pos: Optional[int] = None,
-                 w12: Optional[bool] = None):
+                 w12: Optional[bool] = None, q4=None):
+        if q4 is None:                               # SD_Q4=1: quantise and stream records; SD_Q4=dequantised: the same model on bf16
+            q4 = {"1": True, "dequantised": "dequantised"}.get(os.environ.get("SD_Q4", ""))
+        if q4 and dtype != torch.bfloat16:           # (refusals first: nothing is allocated for a model q4 cannot hold)
+            raise ValueError(f"q4: the 4-bit records hold bf16 weights, not {dtype}")
+        if q4 and (cfg.hidden_size % Q4_GROUP or cfg.intermediate_size % Q4_GROUP):
+            raise ValueError(f"q4: quantisation groups are {Q4_GROUP} k: hidden {cfg.hidden_size} / intermediate "
+                             f"{cfg.intermediate_size} is no multiple")
+        if q4 and not (q4 is True or q4 == "dequantised" or callable(q4)):
+            raise ValueError(f"q4: expected True, 'dequantised' or a callable name -> (q, scales, zeros), got {q4!r}")
         if not torch.cuda.is_available():
             raise RuntimeError("SpecDecModel needs a GPU: the HIP path has no CPU fallback")
         assert dtype in (torch.float32, torch.bfloat16, torch.float16)
@@ -98,9 +125,12 @@ class SpecDecModel:
         self._keep: List[torch.Tensor] = []          # owns every device tensor the handle points into
         self._arrays = []
         self.weight_bytes = 0                        # algorithmic bf16 bytes a forward streams (embedding tables excluded)
-        self.streamed_weight_bytes = 0               # bytes a <= 8-row decode / verify pass streams (12-bit records where packed)
+        self.streamed_weight_bytes = 0               # bytes a <= 8-row decode / verify pass streams (12-bit / 4-bit records where registered)
         self.w12 = w12                               # None: SD_W12 / the memory rule decide (_pack_w12)
         self.w12_packed: Dict[str, List[int]] = {}   # matrix kind -> layers whose 12-bit records are registered
+        self.q4 = q4 or None                         # True / "dequantised" / callable: QKV, gate/up and down are 4-bit group-quantised
+        self.q4_packed: Dict[str, List[int]] = {}    # matrix kind -> layers whose 4-bit records are registered
+        self._q4_recs: List[tuple] = []              # (kind, layer, records, bf16 bytes) waiting for the model handle
         self.fused = fused_layout(cfg, dtype)
         # dtype of the probability rows the reference would keep for this model (kvcache_model.py:167-168 on the model's
         # logits): OPT's logits stay in the weight dtype (modeling_opt.py:974), Llama's are cast to fp32 (:870)
@@ -142,24 +172,29 @@ class SpecDecModel:
                 w.embed = _ptr(self._dev(get("model.embed_tokens.weight")))
                 for i in range(L):
                     p = f"model.layers.{i}."
-                    q, k, v = (get(p + f"self_attn.{n}_proj.weight").to(self.device) for n in "qkv")
-                    if self.fused:
-                        # pair-interleave the rows of every q / k head: d0, d0+D/2, d1, d1+D/2, ... so that one
-                        # accumulator quad of the GEMM holds two complete RoPE pairs (specdec.h, fused_layout)
-                        D, K = cfg.head_dim, q.shape[1]
-                        q = q.view(-1, 2, D // 2, K).transpose(1, 2).reshape(-1, K)
-                        k = k.view(-1, 2, D // 2, K).transpose(1, 2).reshape(-1, K)
-                    wqkv.append(self._gemm_weight(torch.cat([q, k, v], 0)))
-                    del q, k, v
+
+                    # (row operations only, written over a getter: a q4 model assembles its codes, scales and zero points
+                    # - one column per group - by the same steps)
+                    def qkv_rows(get, p=p):
+                        q, k, v = (get(p + f"self_attn.{n}_proj.weight").to(self.device) for n in "qkv")
+                        if self.fused:
+                            # pair-interleave the rows of every q / k head: d0, d0+D/2, d1, d1+D/2, ... so that one
+                            # accumulator quad of the GEMM holds two complete RoPE pairs (specdec.h, fused_layout)
+                            D, K = cfg.head_dim, q.shape[1]
+                            q = q.view(-1, 2, D // 2, K).transpose(1, 2).reshape(-1, K)
+                            k = k.view(-1, 2, D // 2, K).transpose(1, 2).reshape(-1, K)
+                        return torch.cat([q, k, v], 0)
+
+                    def gu_rows(get, p=p):
+                        g, u = get(p + "mlp.gate_proj.weight").to(self.device), get(p + "mlp.up_proj.weight").to(self.device)
+                        if self.fused:
+                            K = g.shape[1]                    # 8 gate rows, the same 8 up rows, ...
+                            return torch.stack([g.view(-1, 8, K), u.view(-1, 8, K)], 1).reshape(-1, K)
+                        return torch.cat([g, u], 0)
+                    wqkv.append(self._layer_matrix("qkv", i, qkv_rows, get))
                     wo.append(self._gemm_weight(get(p + "self_attn.o_proj.weight")))
-                    g, u = get(p + "mlp.gate_proj.weight").to(self.device), get(p + "mlp.up_proj.weight").to(self.device)
-                    if self.fused:
-                        K = g.shape[1]                        # 8 gate rows, the same 8 up rows, ...
-                        wgu.append(self._gemm_weight(torch.stack([g.view(-1, 8, K), u.view(-1, 8, K)], 1).reshape(-1, K)))
-                    else:
-                        wgu.append(self._gemm_weight(torch.cat([g, u], 0)))
-                    del g, u
-                    wdn.append(self._gemm_weight(get(p + "mlp.down_proj.weight")))
+                    wgu.append(self._layer_matrix("gate_up", i, gu_rows, get))
+                    wdn.append(self._layer_matrix("down", i, lambda get, p=p: get(p + "mlp.down_proj.weight"), get))
                     n1w.append(self._dev(get(p + "input_layernorm.weight")))
                     n2w.append(self._dev(get(p + "post_attention_layernorm.weight")))
                     for lst in (bqkv, bo, bfc1, bfc2, n1b, n2b):
@@ -188,14 +223,14 @@ class SpecDecModel:
                     w.final_norm_b = _ptr(self._dev(get(d + "final_layer_norm.bias")))
                 for i in range(L):
                     p = d + f"layers.{i}."
-                    q, k, v = (get(p + f"self_attn.{n}_proj.weight") for n in "qkv")
-                    wqkv.append(self._gemm_weight(torch.cat([q.to(self.device), k.to(self.device), v.to(self.device)], 0)))
+                    wqkv.append(self._layer_matrix("qkv", i, lambda get, p=p: torch.cat(
+                        [get(p + f"self_attn.{n}_proj.weight").to(self.device) for n in "qkv"], 0), get))
                     bqkv.append(self._dev(torch.cat([get(p + f"self_attn.{n}_proj.bias").to(self.device) for n in "qkv"], 0)))
                     wo.append(self._gemm_weight(get(p + "self_attn.out_proj.weight")))
                     bo.append(self._dev(get(p + "self_attn.out_proj.bias")))
-                    wgu.append(self._gemm_weight(get(p + "fc1.weight")))
+                    wgu.append(self._layer_matrix("gate_up", i, lambda get, p=p: get(p + "fc1.weight"), get))
                     bfc1.append(self._dev(get(p + "fc1.bias")))
-                    wdn.append(self._gemm_weight(get(p + "fc2.weight")))
+                    wdn.append(self._layer_matrix("down", i, lambda get, p=p: get(p + "fc2.weight"), get))
                     bfc2.append(self._dev(get(p + "fc2.bias")))
                     n1w.append(self._dev(get(p + "self_attn_layer_norm.weight")))
                     n1b.append(self._dev(get(p + "self_attn_layer_norm.bias")))
@@ -214,7 +249,61 @@ class SpecDecModel:
         self.handle = h
         self._w, self._c = w, c
         self.streamed_weight_bytes = self.weight_bytes
+        self._register_q4()
         self._pack_w12({"qkv": wqkv, "gate_up": wgu, "down": wdn})
+
+    # -- 4-bit group-quantised weights -----------------------------------
+    def _layer_matrix(self, kind: str, layer: int, rows, get) -> torch.Tensor:
+        """QKV, gate/up or down of one layer, assembled by ``rows(getter)``, in the device layout.  A q4 model gets the matrix
+        of w = bf16(s * (q - z)) and, where a <= 8-row pass can stream them (_record_sites), its 4-bit records."""
+        if not self.q4:
+            return self._gemm_weight(rows(get))
+        if callable(self.q4):                        # imported codes: the three tensors of every name, assembled alike
+            parts: Dict[str, tuple] = {}
+            q, s, z = (rows(lambda n, j=j: parts.setdefault(n, self.q4(n))[j]) for j in range(3))
+        else:
+            q, s, z = q4_quantise(rows(get).to(device=self.device, dtype=torch.float32))
+        q, z = (t.to(device=self.device, dtype=torch.uint8).contiguous() for t in (q, z))
+        s = s.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        N, K = q.shape
+        if K % Q4_GROUP or s.shape != (N, K // Q4_GROUP) or z.shape != s.shape:
+            raise ValueError(f"q4: {kind} of layer {layer}: codes {tuple(q.shape)}, scales {tuple(s.shape)}, zeros {tuple(z.shape)}")
+        nb = C.c_size_t()
+        check(lib.sd_q4_bytes(N, K, C.byref(nb)), "sd_q4_bytes")
+        rec = torch.empty(nb.value, dtype=torch.uint8, device=self.device)
+        out = torch.empty((N, K), dtype=torch.bfloat16, device=self.device)
+        check(lib.sd_pack_weight_q4(q.data_ptr(), s.data_ptr(), z.data_ptr(), rec.data_ptr(), out.data_ptr(), N, K, _stream()),
+              "sd_pack_weight_q4")
+        torch.cuda.current_stream().synchronize()
+        self.weight_bytes += out.numel() * out.element_size()
+        self._keep.append(out)
+        if self.q4 != "dequantised" and (kind, layer) in {(k, l) for k, _, l in self._record_sites()}:
+            self._q4_recs.append((kind, layer, rec, out.numel() * out.element_size()))
+        return out
+
+    def _register_q4(self) -> None:
+        which = {k: w for k, w, _ in self._record_sites()}
+        for kind, l, rec, bf16_bytes in self._q4_recs:
+            check(lib.sd_model_set_q4(self.handle, which[kind], l, rec.data_ptr()), "sd_model_set_q4")
+            self._keep.append(rec)
+            self.q4_packed.setdefault(kind, []).append(l)
+            self.streamed_weight_bytes += rec.numel() - bf16_bytes
+        self._q4_recs = []
+
+    def _record_sites(self) -> List[tuple]:
+        """(kind, SD_W12_* id, layer) of the matrices whose records a <= 8-row pass can stream: the norm-on-load route of
+        engine.hip (a whole bf16 Llama model in the fused layout, hidden % 1024 == 0)."""
+        cfg = self.cfg
+        H, L = cfg.hidden_size, cfg.num_hidden_layers
+        if not (self.dtype == torch.bfloat16 and cfg.arch == "llama" and self.fused and H % 1024 == 0 and H <= 8192
+                and cfg.num_attention_heads * cfg.head_dim == H):       # (a tensor-parallel shard never takes the route)
+            return []
+        # the launches that can read records: QKV behind a down projection's seam (layers >= 1), gate/up behind the fused
+        # attention + O launch (head_dim 128), down in front of a next layer
+        todo = [("qkv", _lib.SD_W12_QKV, l) for l in range(1, L)]
+        todo += [("gate_up", _lib.SD_W12_GATE_UP, l) for l in range(L)] if cfg.head_dim == 128 else []
+        todo += [("down", _lib.SD_W12_DOWN, l) for l in range(L - 1)]
+        return todo
 
     # -- 12-bit weight records (DESIGN.md section 3) ------------------------------------------
     W12_DEFAULT = True                           # what an unset SD_W12 means, memory permitting
@@ -225,20 +314,11 @@ class SpecDecModel:
         route of engine.hip: a whole bf16 Llama model in the fused layout, hidden % 1024 == 0).  Both copies stay: prefill
         and every pass of more than 8 rows read bf16.  ``w12`` argument, then SD_W12 (1 force / 0 forbid), then the memory
         rule: pack when the records fit and leave W12_FREE_FRACTION of the device free."""
-        cfg = self.cfg
-        H = cfg.hidden_size
-        ok = (self.dtype == torch.bfloat16 and cfg.arch == "llama" and self.fused and H % 1024 == 0 and H <= 8192
-              and cfg.num_attention_heads * cfg.head_dim == H)          # (a tensor-parallel shard never takes the route)
         env = os.environ.get("SD_W12")
         want = self.w12 if self.w12 is not None else (env != "0" if env in ("0", "1") else None)
-        if not ok or want is False:
+        todo = [t for t in self._record_sites() if t[2] not in self.q4_packed.get(t[0], [])]   # (4-bit records take precedence)
+        if not todo or want is False:
             return
-        L = cfg.num_hidden_layers
-        # the launches that can read records: QKV behind a down projection's seam (layers >= 1), gate/up behind the fused
-        # attention + O launch (head_dim 128), down in front of a next layer
-        todo = [("qkv", _lib.SD_W12_QKV, l) for l in range(1, L)]
-        todo += [("gate_up", _lib.SD_W12_GATE_UP, l) for l in range(L)] if cfg.head_dim == 128 else []
-        todo += [("down", _lib.SD_W12_DOWN, l) for l in range(L - 1)]
         sizes = []
         for kind, _, l in todo:
             N, K = mats[kind][l].shape
@@ -284,8 +364,8 @@ class SpecDecModel:
     # -- constructors -----------------------------------------------------------------------
     @classmethod
     def from_state_dict(cls, cfg: ModelConfig, sd: Dict[str, torch.Tensor], dtype=torch.bfloat16,
-                        device="cuda", max_pos=None, w12: Optional[bool] = None) -> "SpecDecModel":
-        return cls(cfg, lambda n: sd[n], dtype=dtype, device=device, max_pos=max_pos, w12=w12)
+                        device="cuda", max_pos=None, w12: Optional[bool] = None, q4=None) -> "SpecDecModel":
+        return cls(cfg, lambda n: sd[n], dtype=dtype, device=device, max_pos=max_pos, w12=w12, q4=q4)
 
     @classmethod
     def from_hf(cls, module, dtype: Optional[torch.dtype] = None, device="cuda", max_pos=None) -> "SpecDecModel":
@@ -302,7 +382,7 @@ class SpecDecModel:
     @classmethod
     def synthetic(cls, cfg: ModelConfig, seed: int, dtype=torch.bfloat16, device="cuda", max_pos=None,
                   method: str = "torch", gain: float = 1.0, head_gain: float = 4.0, transform=None,
-                  seed_of=None, w12: Optional[bool] = None) -> "SpecDecModel":
+                  seed_of=None, w12: Optional[bool] = None, q4=None) -> "SpecDecModel":
         """Random-init weights generated tensor by tensor (never the whole model at once on the host).
         ``transform(name, tensor) -> tensor`` post-processes each generated tensor (synth.acceptance_dial_pair)."""
         from .synth import param_shapes, _scale
@@ -324,7 +404,7 @@ class SpecDecModel:
         def get(name: str) -> torch.Tensor:
             t = raw(name)
             return transform(name, t) if transform is not None else t
-        m = cls(cfg, get, dtype=dtype, device=device, max_pos=max_pos, w12=w12)
+        m = cls(cfg, get, dtype=dtype, device=device, max_pos=max_pos, w12=w12, q4=q4)
         m._synth_get, m._synth_names = get, list(shapes)     # lets a host baseline regenerate the same tensors
         return m
 
@@ -497,6 +577,10 @@ class Session:
         """GEMM launches of this session so far that streamed 12-bit weight records (a host counter: <= 8-row passes of a
         model with packed copies; prefill and wider passes read bf16 and leave it alone)."""
         return int(lib.sd_session_w12_launches(self.handle))
+
+    def q4_launches(self) -> int:
+        """GEMM launches of this session so far that streamed 4-bit weight records (the same passes, on a q4 model)."""
+        return int(lib.sd_session_q4_launches(self.handle))
 
     def prefill_attn_blocked_launches(self) -> int:
         """Of those, the launches of attn_prefill_blocked_kernel (a context past the single score tile's LDS limit, or
