@@ -385,12 +385,25 @@ int sd_model_set_w12(sd_model *m, int which, int layer, const void *codes, const
  * sd_unpack_weight_q4: records -> the tiled bf16 layout (the format's executable definition; tests).
  * sd_model_set_q4: registers the records of layer `layer`'s matrix `which` (an SD_W12_* id) with a bf16 model whose tiled
  *   copy of that matrix holds the same w (NULL: unregisters).  A matrix has 12-bit records or 4-bit records, not both: each
- *   of the two setters refuses a matrix the other one has records for.  Not while a forward is in flight. */
+ *   of the two setters refuses a matrix the other one has records for.  Not while a forward is in flight.
+ * sd_model_set_q4_rows: on != 0 marks a bf16 model (NULL and other dtypes: SD_ERR_INVALID) whose 9..80-row passes send QKV,
+ *   gate/up (fused epilogues) and down (k-slabs for the residual+norm launch) of every layer that has records registered to
+ *   the balanced record GEMM - three record launches per layer; Llama models in the fused layout, outside a tensor-parallel
+ *   session.  W_o, the lm_head, attention, passes of <= 8 rows and of more than 80 rows keep the launches they take
+ *   without the mark.  Not while a forward is in flight.
+ * sd_gemm_q4_rows: that GEMM on its own (unit tests, kernel-level runs), sd_gemm_bf16's form:
+ *   part[s][m][n] = sum over k-slab s of x[m][k] * w[n][k] for the records' w, then (if out != NULL) out[m][n] = sum_s in
+ *   fp32.  1 <= M <= 80, N % 16 == 0, K % 128 == 0; x_tiled in sd_pack_activation_bf16's layout; slabs == 0: the plan's own
+ *   choice, else a power of two <= min(16, K / 128) that the plan can cut (SD_ERR_INVALID otherwise); part must hold
+ *   slabs * roundup(M,16) * N floats; the slab count comes back in *splits_out. */
 int sd_q4_bytes(int N, int K, size_t *bytes);
 int sd_pack_weight_q4(const void *q, const void *scales, const void *zeros, void *records, void *w_tiled_out, int N, int K,
                       void *stream);
 int sd_unpack_weight_q4(const void *records, void *w_tiled, int N, int K, void *stream);
 int sd_model_set_q4(sd_model *m, int which, int layer, const void *records);
+int sd_model_set_q4_rows(sd_model *m, int on);
+int sd_gemm_q4_rows(const void *records, const void *x_tiled, int M, int N, int K, int slabs, float *part, size_t part_floats,
+                    float *out, int *splits_out, void *stream);
 
 /* Row-major bf16 activations [M][K] (K % 32 == 0) -> the GEMM operand layout the engine keeps them in between
  * kernels: 16-row tiles [ceil(M/16)][K/32][lane 0..63][8 bf16], lane = 16*(k/8 % 4) + m % 16, so that a wave's MFMA

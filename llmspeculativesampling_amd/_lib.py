@@ -328,6 +328,8 @@ SYMBOLS = [
     ("sd_pack_weight_q4", _I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _VP]),
     ("sd_unpack_weight_q4", _I, [_VP, _VP, _I, _I, _VP]),
     ("sd_model_set_q4", _I, [_VP, _I, _I, _VP]),
+    ("sd_model_set_q4_rows", _I, [_VP, _I]),
+    ("sd_gemm_q4_rows", _I, [_VP, _VP, _I, _I, _I, _I, _VP, C.c_size_t, _VP, C.POINTER(C.c_int), _VP]),
     ("sd_session_q4_launches", _I, [_VP]),
     ("sd_pack_activation_bf16", _I, [_VP, _VP, _I, _I, _VP]),
     ("sd_gemm_bf16", _I, [_VP, _VP, _I, _I, _I, _I, _VP, C.c_size_t, _VP, C.POINTER(C.c_int), _VP]),

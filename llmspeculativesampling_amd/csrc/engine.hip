@@ -42,6 +42,7 @@ struct sd_model {
     std::vector<const void *> wqkv, bqkv, wo, bo, wgu, bfc1, wdown, bfc2, n1w, n1b, n2w, n2b;
     std::vector<const unsigned *> q4[3];   // [SD_W12_*][layer]: 4-bit group-quantised records of that matrix (sd_model_set_q4; NULL: none)
     std::vector<W12Arg> w12[3];   // [SD_W12_*][layer]: 12-bit records of that matrix (sd_model_set_w12; codes == NULL: none)
+    bool q4_rows = false;         // 9..80-row passes send QKV, gate/up and down to gemm_q4_rows where records are registered (sd_model_set_q4_rows)
 };
 
 enum { PC_GEMM = 0, PC_ATTN, PC_NORM, PC_QKV, PC_ACT, PC_EMBED, PC_LOGITS, PC_OTHER };
@@ -204,6 +205,12 @@ extern "C" int sd_model_set_q4(sd_model *m, int which, int layer, const void *re
     SD_REQUIRE(((uintptr_t)records & 127) == 0, "sd_model_set_q4: records must be 128-byte aligned");
     SD_REQUIRE(!records || !m->w12[which][layer].codes, "sd_model_set_q4: matrix %d of layer %d has 12-bit records registered", which, layer);
     m->q4[which][layer] = (const unsigned *)records;
+    return SD_OK;
+}
+extern "C" int sd_model_set_q4_rows(sd_model *m, int on) {
+    SD_REQUIRE(m, "sd_model_set_q4_rows: null model");
+    SD_REQUIRE(m->cfg.dtype == SD_BF16, "sd_model_set_q4_rows: the 4-bit records hold bf16 weights");
+    m->q4_rows = on != 0;
     return SD_OK;
 }
 
@@ -1589,6 +1596,25 @@ static const unsigned *q4_of(const sd_model *m, int which, int l) {
     if constexpr (std::is_same<T, bf16_t>::value) return m->q4[which][l];
     return nullptr;
 }
+// ... and the balanced record GEMM of the 9..80-row passes (q4_rows.h), likewise defined at the end.  q4_rows_of: the
+// records of layer l's matrix `which` if this pass sends it there - a model marked by sd_model_set_q4_rows (bf16 Llama in
+// the fused layout), outside a tensor-parallel session, 9..80 rows in the tile layout, a record plan for the shape
+#define SD_Q4_ROWS_MIN 9
+#define SD_Q4_ROWS_MAX 80
+static bool q4_rows_plan_ok(int N, int K, int M, bool fused);
+template <int EPI>
+static int launch_gemm_q4_rows(sd_session *s, const unsigned *W, const void *X, float *part, int M, int N, int K, int slabs,
+                               const GemmEpiT<bf16_t> &e, int *S_out, hipStream_t st);
+template <typename T>
+static const unsigned *q4_rows_of(const sd_session *s, int which, int l, int M, int N, int K, bool fused) {
+    const sd_model *m = s->m;
+    if constexpr (std::is_same<T, bf16_t>::value) {
+        if (!m->q4_rows || s->tp || m->cfg.arch != SD_ARCH_LLAMA || !m->cfg.fused_layout) return nullptr;
+        if (M < SD_Q4_ROWS_MIN || M > SD_Q4_ROWS_MAX || !m->q4[which][l] || !q4_rows_plan_ok(N, K, M, fused)) return nullptr;
+        return m->q4[which][l];
+    }
+    return nullptr;
+}
 // the 12-bit records of layer l's matrix `which`, if this pass may read them (bf16 model, a copy registered)
 template <typename T>
 static W12Arg w12_of(const sd_model *m, int which, int l) {
@@ -1985,6 +2011,10 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
         } else if (xn_q) {
             rc = launch_gemm_xn<EPI_QKV_ROPE, H16>(s, m->wqkv[l], h, n_new, qkv_cols(c), H, m->n1w[l], c.norm_eps, qkv_epi<H16>(s, tab, l), st);
             if (rc != SD_OK) return rc;
+        } else if (const unsigned *rec = q4_rows_of<T>(s, SD_W12_QKV, l, n_new, qkv_cols(c), H, true)) {
+            ProfScope ps(s, PC_GEMM, st);
+            rc = launch_gemm_q4_rows<EPI_QKV_ROPE>(s, rec, h, nullptr, n_new, qkv_cols(c), H, 1, qkv_epi<bf16_t>(s, tab, l), nullptr, st);
+            if (rc != SD_OK) return rc;
         } else if (fused) {
             const GemmEpiT<H16> e = qkv_epi<H16>(s, tab, l);
             rc = llama ? run_gemm_fused<EPI_QKV_ROPE, H16>(s, fp.qkv, m->wqkv[l], h, n_new, qkv_cols(c), H, e, st)
@@ -2030,6 +2060,10 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
         } else if (xn_o) {
             rc = launch_gemm_xn<EPI_ACT_SILU, H16>(s, m->wgu[l], h, n_new, gu_cols(c), H, m->n2w[l], c.norm_eps, act_epi<H16>(s, l), st);
             if (rc != SD_OK) return rc;
+        } else if (const unsigned *rec = q4_rows_of<T>(s, SD_W12_GATE_UP, l, n_new, gu_cols(c), H, true)) {
+            ProfScope ps(s, PC_GEMM, st);
+            rc = launch_gemm_q4_rows<EPI_ACT_SILU>(s, rec, h, nullptr, n_new, gu_cols(c), H, 1, act_epi<bf16_t>(s, l), nullptr, st);
+            if (rc != SD_OK) return rc;
         } else if (fused) {
             const GemmEpiT<H16> e = act_epi<H16>(s, l);
             rc = llama ? run_gemm_fused<EPI_ACT_SILU, H16>(s, fp.gu, m->wgu[l], h, n_new, gu_cols(c), H, e, st)
@@ -2051,7 +2085,11 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
         } else if (xn_d) {
             if ((rc = launch_gemm_fin<H16>(s, fp.down, m->wdown[l], ac, n_new, H, I, nullptr, st)) != SD_OK) return rc;
         } else {
-            if ((rc = run_gemm<H16>(s, fp.down, m->wdown[l], ac, n_new, H, I, &go, st)) != SD_OK) return rc;
+            if (const unsigned *rec = q4_rows_of<T>(s, SD_W12_DOWN, l, n_new, H, I, false)) {
+                ProfScope ps(s, PC_GEMM, st);             // the EPI_PART instance: slabs for the residual+norm launch below
+                if ((rc = launch_gemm_q4_rows<EPI_PART>(s, rec, ac, s->part, n_new, H, I, 0, GemmEpiT<bf16_t>{}, &go.S, st)) != SD_OK) return rc;
+                go.stride_s = align_up(n_new, 16) * (size_t)H;
+            } else if ((rc = run_gemm<H16>(s, fp.down, m->wdown[l], ac, n_new, H, I, &go, st)) != SD_OK) return rc;
             const float *dsrc = s->part;
             if ((rc = tp_reduce(s, &go, &dsrc, n_new, H, st)) != SD_OK) return rc;
             int mode = RES_NONE;
@@ -2699,6 +2737,7 @@ static int launch_attn_shared(sd_session *s, const T *q, const RowTab &tab, cons
 // ---- the norm-on-load and the finishing GEMM on 4-bit group-quantised records, their packer and expander (forward
 // declarations above launch_gemm_xn's users): new kernels go behind every other kernel of the code object
 #include "q4.h"
+#include "q4_rows.h"
 static int launch_gemm_xn_q4(sd_session *s, bool qkv, const unsigned *W, const void *X, int M, int N, int K, const void *norm_w, float eps,
                              GemmEpiT<bf16_t> e, hipStream_t st) {
     ProfScope ps(s, PC_GEMM, st);
@@ -2752,5 +2791,113 @@ extern "C" int sd_unpack_weight_q4(const void *records, void *w_tiled, int N, in
     hipLaunchKernelGGL(q4_unpack_kernel<0>, dim3((unsigned)((size_t)(N / 16) * (K / 128))), dim3(64), 0, (hipStream_t)stream,
                        (const unsigned *)records, (u32x4 *)w_tiled, K);
     SD_LAUNCH_CHECK();
+    return SD_OK;
+}
+
+// ---- 1..80 rows on 4-bit records: the balanced one-workgroup-per-CU kernel (q4_rows.h).  The record plan is rows_plan's
+// logic in whole records: S k-slabs of ksp k-steps (a multiple of 4) x NG n-groups, at most one workgroup per CU; a fused
+// epilogue needs S == 1.  Unlike rows_plan it has no other kernel to leave a shape to, so it takes any row count from 1,
+// a matrix with fewer n-tiles than CUs (NG = the tiles: one each) and the best cut whatever its efficiency; the cost is
+// (record bytes + slab traffic) / (how evenly the n-tiles divide x the share of the CUs that get a workgroup).
+// slabs > 0: that many slabs or no plan (sd_gemm_q4_rows); part_cap > 0: the floats the slabs may take.
+static RowsPlan q4_rows_plan(int N, int K, int M, bool fused, int slabs, size_t part_cap) {
+    RowsPlan p = {};
+    if (M < 1 || M > SD_Q4_ROWS_MAX || N < 16 || N % 16 || K < 128 || K % 128) return p;
+    const int G = device_cus(), NT = N / 16, KS = K / 32, KR = K / 128, Mpad = (int)align_up(M, 16);
+    const double wbytes = (double)NT * KR * (Q4_REC_DWORDS * 4), slab = 2.0 * Mpad * (double)N * 4.0;
+    double best = 1e300;
+    for (int S = 1; S <= (fused ? 1 : 16); S *= 2) {
+        if (slabs > 0 && S != slabs) continue;
+        if (G % S || S > KR) break;
+        const int ksp = 4 * ((KR + S - 1) / S), Sa = (KS + ksp - 1) / ksp;          // whole records per slab; slabs that hold any
+        if (Sa != S && slabs > 0) continue;
+        const int NG = std::min(G / S, NT), tpg = (NT + NG - 1) / NG;
+        if (tpg > GR_MAX_TILES) continue;
+        if (!fused && part_cap && (size_t)Sa * Mpad * N > part_cap) continue;
+        const double eff = (double)NT / NG / tpg * ((double)NG * Sa / G);
+        const double cost = (wbytes + (fused ? 0.0 : slab * Sa)) / eff;
+        if (cost < best) {
+            best = cost;
+            p.ok = true;
+            p.S = Sa; p.NG = NG; p.ksp = ksp;
+        }
+    }
+    if (p.ok) {
+        p.grid = p.NG * p.S;
+        // wave grid of a workgroup: nwn compute waves per k-group (one n-tile each) x nwk k-groups + loader waves, <= 16;
+        // no more k-groups than a slab has records; 5 m-tiles: 2 x 4 k-groups x 4 k-steps x 5 KiB exceed the CU's LDS
+        p.nwn = (NT + p.NG - 1) / p.NG;
+        p.nwk = std::min({4, (16 - 1) / p.nwn, p.ksp / 4});
+        if (Mpad > 64) p.nwk = std::min(p.nwk, 3);
+        p.nld = std::min(p.nwk, 16 - p.nwn * p.nwk);
+    }
+    return p;
+}
+static bool q4_rows_plan_ok(int N, int K, int M, bool fused) { return q4_rows_plan(N, K, M, fused, 0, 0).ok; }
+
+// gemm_q4_rows' instance of Mpad rows: MT = Mpad / 16 m-tiles, chunks of 8 k-steps at 1-2 m-tiles and 4 past that (as the
+// kernel has it), the activation panel (2 buffers x nwk k-groups x CH k-steps x MT KiB) reused as the fold buffer
+template <int EPI>
+static int q4_rows_go(const RowsPlan &pl, const unsigned *W, const void *X, float *part, int M, int N, int K,
+                      const GemmEpiT<bf16_t> &e, hipStream_t st) {
+    const int Mpad = (int)align_up(M, 16), MT = Mpad / 16, ch = MT <= 2 ? 8 : 4;
+    const size_t lds = (size_t)1024 * MT * std::max(2 * pl.nwk * ch, pl.nwk * pl.nwn);
+    SD_REQUIRE(pl.ok && MT >= 1 && MT <= Q4R_MAX_MT && lds <= GR_LDS_CAP && (EPI == EPI_PART || pl.S == 1),
+               "gemm_q4_rows: no instance for M=%d N=%d K=%d (%d slabs, %zu bytes of LDS)", M, N, K, pl.S, lds);
+    auto go = [&](auto mt_c) {
+        constexpr int MTc = decltype(mt_c)::value;
+        static bool attr = false;                                 // (one flag per instantiation)
+        if (!attr) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_q4_rows<MTc, EPI>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)GR_LDS_CAP);
+            attr = true;
+        }
+        hipLaunchKernelGGL((gemm_q4_rows<MTc, EPI>), dim3(pl.grid), dim3(GR_THREADS), lds, st, W, (const u32x4 *)X, part, M, Mpad,
+                           N, K, pl.NG, pl.ksp, pl.nwn, pl.nwk, pl.nld, e);
+    };
+    using std::integral_constant;
+    if (MT == 1) go(integral_constant<int, 1>{});
+    else if (MT == 2) go(integral_constant<int, 2>{});
+    else if (MT == 3) go(integral_constant<int, 3>{});
+    else if (MT == 4) go(integral_constant<int, 4>{});
+    else go(integral_constant<int, 5>{});
+    SD_LAUNCH_CHECK();
+    return SD_OK;
+}
+// a forward's launch: slabs == 1 for the fused epilogues; EPI_PART leaves *S_out slabs of [Mpad][N] floats in `part`
+template <int EPI>
+static int launch_gemm_q4_rows(sd_session *s, const unsigned *W, const void *X, float *part, int M, int N, int K, int slabs,
+                               const GemmEpiT<bf16_t> &e, int *S_out, hipStream_t st) {
+    const RowsPlan pl = q4_rows_plan(N, K, M, EPI != EPI_PART, slabs, EPI == EPI_PART ? s->part_floats : 0);
+    SD_REQUIRE(pl.ok, "gemm_q4_rows: no record plan for M=%d N=%d K=%d", M, N, K);
+    const int rc = q4_rows_go<EPI>(pl, W, X, part, M, N, K, e, st);
+    if (rc != SD_OK) return rc;
+    if (S_out) *S_out = pl.S;
+    ++s->q4_launches;
+    return SD_OK;
+}
+extern "C" int sd_gemm_q4_rows(const void *records, const void *x_tiled, int M, int N, int K, int slabs, float *part,
+                               size_t part_floats, float *out, int *splits_out, void *stream) {
+    SD_REQUIRE(records && x_tiled && part, "sd_gemm_q4_rows: null argument");
+    SD_REQUIRE(N >= 16 && N % 16 == 0, "sd_gemm_q4_rows: N %% 16 != 0 (N=%d): a record is a 16-row n-tile", N);
+    SD_REQUIRE(K >= 128 && K % 128 == 0, "sd_gemm_q4_rows: K %% 128 != 0 (K=%d): a record is one group of 128 k", K);
+    SD_REQUIRE(M >= 1 && M <= SD_Q4_ROWS_MAX, "sd_gemm_q4_rows: M out of range (M=%d, need 1..%d)", M, SD_Q4_ROWS_MAX);
+    SD_REQUIRE(((uintptr_t)records & 127) == 0 && ((uintptr_t)x_tiled & 15) == 0,
+               "sd_gemm_q4_rows: records must be 128-byte aligned (x_tiled 16-byte)");
+    SD_REQUIRE(slabs >= 0, "sd_gemm_q4_rows: slabs=%d (0: the plan's choice)", slabs);
+    const RowsPlan pl = q4_rows_plan(N, K, M, false, slabs, 0);
+    SD_REQUIRE(pl.ok, "sd_gemm_q4_rows: no record plan of %d slabs for N=%d K=%d (a power of two <= 16 and <= K / 128 that divides "
+               "the CUs evenly, at most %d n-tiles per workgroup)", slabs, N, K, GR_MAX_TILES);
+    const size_t Mpad = align_up(M, 16);
+    SD_REQUIRE((size_t)pl.S * Mpad * N <= part_floats, "sd_gemm_q4_rows: part_floats too small: %d slabs need %zu floats", pl.S,
+               (size_t)pl.S * Mpad * N);
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = q4_rows_go<EPI_PART>(pl, (const unsigned *)records, x_tiled, part, M, N, K, GemmEpiT<bf16_t>{}, st);
+    if (rc != SD_OK) return rc;
+    if (out) {
+        hipLaunchKernelGGL(reduce_f32_kernel, dim3((M * N + 255) / 256), dim3(256), 0, st, part, pl.S, Mpad * N, M * N, out);
+        SD_LAUNCH_CHECK();
+    }
+    if (splits_out) *splits_out = pl.S;
     return SD_OK;
 }

@@ -104,14 +104,19 @@ class SpecDecModel:
                  dtype: torch.dtype = torch.bfloat16, device: str = "cuda", max_pos: Optional[int] = None,
                  w12: Optional[bool] = None, q4=None):
         if q4 is None:                               # SD_Q4=1: quantise and stream records; SD_Q4=dequantised: the same model on bf16
-            q4 = {"1": True, "dequantised": "dequantised"}.get(os.environ.get("SD_Q4", ""))
+            q4 = {"1": True, "dequantised": "dequantised", "rows": "rows"}.get(os.environ.get("SD_Q4", ""))
+        # "rows" / ("rows", fn): q4=True / q4=fn, and the 9..80-row passes stream records too (every layer's are registered)
+        q4_rows = q4 == "rows" or (isinstance(q4, tuple) and len(q4) == 2 and q4[0] == "rows" and callable(q4[1]))
+        if q4_rows:
+            q4 = True if q4 == "rows" else q4[1]
         if q4 and dtype != torch.bfloat16:           # (refusals first: nothing is allocated for a model q4 cannot hold)
             raise ValueError(f"q4: the 4-bit records hold bf16 weights, not {dtype}")
         if q4 and (cfg.hidden_size % Q4_GROUP or cfg.intermediate_size % Q4_GROUP):
             raise ValueError(f"q4: quantisation groups are {Q4_GROUP} k: hidden {cfg.hidden_size} / intermediate "
                              f"{cfg.intermediate_size} is no multiple")
         if q4 and not (q4 is True or q4 == "dequantised" or callable(q4)):
-            raise ValueError(f"q4: expected True, 'dequantised' or a callable name -> (q, scales, zeros), got {q4!r}")
+            raise ValueError(f"q4: expected True, 'dequantised', 'rows', a callable name -> (q, scales, zeros) or "
+                             f"('rows', callable), got {q4!r}")
         if not torch.cuda.is_available():
             raise RuntimeError("SpecDecModel needs a GPU: the HIP path has no CPU fallback")
         assert dtype in (torch.float32, torch.bfloat16, torch.float16)
@@ -129,6 +134,7 @@ class SpecDecModel:
         self.w12 = w12                               # None: SD_W12 / the memory rule decide (_pack_w12)
         self.w12_packed: Dict[str, List[int]] = {}   # matrix kind -> layers whose 12-bit records are registered
         self.q4 = q4 or None                         # True / "dequantised" / callable: QKV, gate/up and down are 4-bit group-quantised
+        self.q4_rows = bool(q4_rows)                 # passes of 9..80 rows stream the records as well (gemm_q4_rows)
         self.q4_packed: Dict[str, List[int]] = {}    # matrix kind -> layers whose 4-bit records are registered
         self._q4_recs: List[tuple] = []              # (kind, layer, records, bf16 bytes) waiting for the model handle
         self.fused = fused_layout(cfg, dtype)
@@ -277,18 +283,33 @@ class SpecDecModel:
         torch.cuda.current_stream().synchronize()
         self.weight_bytes += out.numel() * out.element_size()
         self._keep.append(out)
-        if self.q4 != "dequantised" and (kind, layer) in {(k, l) for k, _, l in self._record_sites()}:
+        if self.q4 != "dequantised" and (kind, layer) in {(k, l) for k, _, l in self._q4_sites()}:
             self._q4_recs.append((kind, layer, rec, out.numel() * out.element_size()))
         return out
 
     def _register_q4(self) -> None:
-        which = {k: w for k, w, _ in self._record_sites()}
+        which = {k: w for k, w, _ in self._q4_sites()}
+        small = {(k, l) for k, _, l in self._record_sites()}     # the sites a <= 8-row pass streams
         for kind, l, rec, bf16_bytes in self._q4_recs:
             check(lib.sd_model_set_q4(self.handle, which[kind], l, rec.data_ptr()), "sd_model_set_q4")
             self._keep.append(rec)
             self.q4_packed.setdefault(kind, []).append(l)
-            self.streamed_weight_bytes += rec.numel() - bf16_bytes
+            if (kind, l) in small:
+                self.streamed_weight_bytes += rec.numel() - bf16_bytes
+        if self.q4_rows and self._q4_recs:
+            check(lib.sd_model_set_q4_rows(self.handle, 1), "sd_model_set_q4_rows")
         self._q4_recs = []
+
+    def _q4_sites(self) -> List[tuple]:
+        """(kind, SD_W12_* id, layer) of the matrices whose 4-bit records are registered: _record_sites, or - a "rows" model,
+        whose 9..80-row passes send them to gemm_q4_rows - QKV, gate/up and down of every layer of a bf16 Llama model in
+        the fused layout."""
+        if not self.q4_rows:
+            return self._record_sites()
+        if not (self.dtype == torch.bfloat16 and self.cfg.arch == "llama" and self.fused):
+            return []
+        ids = (("qkv", _lib.SD_W12_QKV), ("gate_up", _lib.SD_W12_GATE_UP), ("down", _lib.SD_W12_DOWN))
+        return [(k, w, l) for k, w in ids for l in range(self.cfg.num_hidden_layers)]
 
     def _record_sites(self) -> List[tuple]:
         """(kind, SD_W12_* id, layer) of the matrices whose records a <= 8-row pass can stream: the norm-on-load route of
