@@ -36,12 +36,20 @@ void sd_set_error(const char *fmt, ...) {
 extern "C" const char *sd_last_error(void) { return g_err; }
 extern "C" int sd_version(void) { return SD_ABI_VERSION; }
 
+// The weight records of one matrix: none, or one format and that format's pointers - never two
+enum WFmt { WF_NONE = 0, WF_W12, WF_Q4 };
+struct WRec {
+    WFmt fmt;
+    union {
+        W12Arg w12;               // WF_W12: 12-bit records (sd_model_set_w12)
+        const unsigned *q4;       // WF_Q4: 4-bit group-quantised records (sd_model_set_q4)
+    };
+};
 struct sd_model {
     sd_model_config cfg;
     sd_model_weights w;
     std::vector<const void *> wqkv, bqkv, wo, bo, wgu, bfc1, wdown, bfc2, n1w, n1b, n2w, n2b;
-    std::vector<const unsigned *> q4[3];   // [SD_W12_*][layer]: 4-bit group-quantised records of that matrix (sd_model_set_q4; NULL: none)
-    std::vector<W12Arg> w12[3];   // [SD_W12_*][layer]: 12-bit records of that matrix (sd_model_set_w12; codes == NULL: none)
+    std::vector<WRec> rec[3];     // [SD_W12_*][layer]: the records of that matrix
     bool q4_rows = false;         // 9..80-row passes send QKV, gate/up and down to gemm_q4_rows where records are registered (sd_model_set_q4_rows)
 };
 
@@ -151,8 +159,7 @@ extern "C" int sd_model_create(const sd_model_config *cfg, const sd_model_weight
     copy_ptrs(m->wdown, w->w_down, L); copy_ptrs(m->bfc2, w->b_fc2, L);
     copy_ptrs(m->n1w, w->norm1_w, L); copy_ptrs(m->n1b, w->norm1_b, L);
     copy_ptrs(m->n2w, w->norm2_w, L); copy_ptrs(m->n2b, w->norm2_b, L);
-    for (auto &v : m->w12) v.assign(L, W12Arg{nullptr, nullptr});
-    for (auto &v : m->q4) v.assign(L, nullptr);
+    for (auto &v : m->rec) v.assign(L, WRec{});
     *out = m;
     return SD_OK;
 }
@@ -187,8 +194,10 @@ extern "C" int sd_model_set_w12(sd_model *m, int which, int layer, const void *c
     SD_REQUIRE(m->cfg.dtype == SD_BF16, "sd_model_set_w12: the 12-bit records hold bf16 weights");
     SD_REQUIRE((codes != nullptr) == (meta != nullptr), "sd_model_set_w12: codes and meta come together");
     SD_REQUIRE(((uintptr_t)codes & 127) == 0 && ((uintptr_t)meta & 15) == 0, "sd_model_set_w12: codes must be 128-byte, meta 16-byte aligned");
-    SD_REQUIRE(!codes || !m->q4[which][layer], "sd_model_set_w12: matrix %d of layer %d has 4-bit records registered", which, layer);
-    m->w12[which][layer] = W12Arg{(const unsigned *)codes, (const u32x4 *)meta};
+    WRec &r = m->rec[which][layer];
+    SD_REQUIRE(!codes || r.fmt != WF_Q4, "sd_model_set_w12: matrix %d of layer %d has 4-bit records registered", which, layer);
+    if (codes) { r = WRec{}; r.fmt = WF_W12; r.w12 = W12Arg{(const unsigned *)codes, (const u32x4 *)meta}; }
+    else if (r.fmt == WF_W12) r = WRec{};                    // (NULL unregisters 12-bit records, and only those)
     return SD_OK;
 }
 
@@ -203,8 +212,10 @@ extern "C" int sd_model_set_q4(sd_model *m, int which, int layer, const void *re
     SD_REQUIRE(m && which >= 0 && which < 3 && layer >= 0 && layer < m->cfg.n_layers, "sd_model_set_q4: bad matrix %d of layer %d", which, layer);
     SD_REQUIRE(m->cfg.dtype == SD_BF16, "sd_model_set_q4: the 4-bit records hold bf16 weights");
     SD_REQUIRE(((uintptr_t)records & 127) == 0, "sd_model_set_q4: records must be 128-byte aligned");
-    SD_REQUIRE(!records || !m->w12[which][layer].codes, "sd_model_set_q4: matrix %d of layer %d has 12-bit records registered", which, layer);
-    m->q4[which][layer] = (const unsigned *)records;
+    WRec &r = m->rec[which][layer];
+    SD_REQUIRE(!records || r.fmt != WF_W12, "sd_model_set_q4: matrix %d of layer %d has 12-bit records registered", which, layer);
+    if (records) { r = WRec{}; r.fmt = WF_Q4; r.q4 = (const unsigned *)records; }
+    else if (r.fmt == WF_Q4) r = WRec{};                     // (NULL unregisters 4-bit records, and only those)
     return SD_OK;
 }
 extern "C" int sd_model_set_q4_rows(sd_model *m, int on) {
@@ -1340,10 +1351,12 @@ struct PlanCtx {
     bool final_norm;                  // the model has a final-norm weight
     size_t part_floats;               // floats of the k-slab scratch (plan_scratch)
     int cus;                          // CUs of the device
+    bool q4_rows;                     // the model's mark (sd_model_set_q4_rows): 9..80-row passes take the record row GEMM
 };
 // The route of one forward pass: which launches it makes and how each of them is cut.  All of it follows from (PlanCtx, row
 // table, s_max), so plan_forward fills it once, before the layer loop, and the launch helpers read it - they
-// decide nothing themselves.  What does differ between layers (a layer's biases, l + 1 < L) stays in the loop.
+// decide nothing themselves.  What does differ between layers stays in the loop: a layer's biases, l + 1 < L, and the
+// weight records registered for a matrix of that layer (WRec), whose format picks the enqueue step of a launch.
 enum AttnKind { AK_KERNEL = 0, AK_OPROJ, AK_PREFILL, AK_GROUPED, AK_SHARED };   // attn_kernel (+ combine) | fused attention + O | matrix cores | grouped-query | shared-prefix
 struct FwdPlan {
     bool small;                       // the small-model decode path (forward_small)
@@ -1358,6 +1371,8 @@ struct FwdPlan {
     bool seam_o, seam_d;              // norm on load may open at the attention -> MLP seam / the down -> next QKV seam
     GemmRoute qkv, o, gu, down;       // the per-layer GEMMs of a 16-bit model (not of the small path, which cuts its own)
     GemmRoute head;                   // the lm_head with its row gather (16-bit model, logit rows)
+    RowsPlan rows_qkv, rows_gu, rows_down;   // the record row GEMM where a matrix has 4-bit records (q4_rows_plan; !ok: not this pass):
+                                      // QKV and gate/up with their fused epilogues, down as slabs in s->part
     int S_o, ksp_o, S_d, ksp_d;       // small: the k-slabs of its O / down GEMMs (small_split)
     int rn_threads;                   // blockDim of residual_norm_kernel
 };
@@ -1547,80 +1562,103 @@ static bool norm_on_load_ok(const PlanCtx &pc, const RowTab &tab) {
     // (9..16 rows: the conversions cost more than the launch they replace - +5.7 us on gate/up at 12 rows, tools/gemm_bench.py)
     return tab.n_rows <= 8 && c.hidden % 1024 == 0 && c.hidden <= 8192;
 }
-template <int EPI, typename H>
-static int launch_gemm_xn(sd_session *s, const void *W, const void *X, int M, int N, int K, const void *norm_w, float eps,
-                          GemmEpiT<H> e, hipStream_t st) {
-    ProfScope ps(s, PC_GEMM, st);
-    SD_REQUIRE(M <= 8 && N % 16 == 0 && K % 1024 == 0 && K <= 8192, "norm-on-load GEMM: M=%d N=%d K=%d", M, N, K);
-    e.nrm_ssq = s->ssq; e.nrm_w = (const H *)norm_w; e.nrm_nt = K / 16; e.nrm_eps = eps;
-    // k-steps whose M valid rows fit one conversion register (C * 4 * M <= 64 lanes)
-    auto go = [&](auto c) {
-        hipLaunchKernelGGL((gemm_bf16_stream_xn<EPI, decltype(c)::value, H>), dim3(N / 16), dim3(256), (size_t)K * sizeof(H), st,
-                           (const u32x4 *)W, (const H *)X, (float *)nullptr, M, N, K, 1, K / 32, e);
-    };
+// Weight records (WRec) on these two launches.  Each launch has one host body - precondition, epilogue fields, launch check,
+// counters - and per weight format one enqueue step: the bf16 kernel's inside the body, the record formats' as plain
+// functions defined at the end of this file, so that their kernels follow every other kernel of the code object (see
+// launch_attn_bf16 below for what a kernel in the middle costs).  An enqueue step holds its format's own precondition, if
+// it has one, and the one hipLaunchKernelGGL.
+static void xn_enqueue_w12(int epi, W12Arg W, const void *X, int M, int N, int K, const GemmEpiT<bf16_t> &e, hipStream_t st);
+static int xn_enqueue_q4(int epi, const unsigned *W, const void *X, int M, int N, int K, const GemmEpiT<bf16_t> &e, hipStream_t st);
+static void fin_enqueue_w12(sd_session *s, const GemmRoute &pl, W12Arg W, const void *X, int M, int N, int K, const GemmEpiT<bf16_t> &e,
+                            unsigned want, hipStream_t st);
+static int fin_enqueue_q4(sd_session *s, const GemmRoute &pl, const unsigned *W, const void *X, int M, int N, int K,
+                          const GemmEpiT<bf16_t> &e, unsigned want, hipStream_t st);
+static void count_record_launch(sd_session *s, WFmt fmt) {
+    if (fmt == WF_W12) ++s->w12_launches;
+    else if (fmt == WF_Q4) ++s->q4_launches;
+}
+// the records of layer l's matrix `which` (SD_W12_*) as a pass of a T model may read them: only a bf16 model has any
+template <typename T>
+static WRec rec_of(const sd_model *m, int which, int l) {
+    if constexpr (std::is_same<T, bf16_t>::value) return m->rec[which][l];
+    return WRec{};
+}
+
+// The norm-on-load kernels' instance for M rows, whatever they read their weights from: C = the k-steps whose M valid rows
+// fit one conversion register (C * 4 * M <= 64 lanes); go(integral_constant<int, C>)
+template <typename F>
+static void xn_by_rows(int M, F go) {
     using std::integral_constant;
     if (M <= 4) go(integral_constant<int, 4>{});
     else if (M == 5) go(integral_constant<int, 3>{});
     else go(integral_constant<int, 2>{});
+}
+// ... and for an epilogue known at run time (the record formats' enqueue steps): go(integral_constant<int, EPI>, <int, C>)
+template <typename F>
+static void xn_by_epi_rows(int epi, int M, F go) {
+    auto by_rows = [&](auto e) { xn_by_rows(M, [&](auto c) { go(e, c); }); };
+    if (epi == EPI_QKV_ROPE) by_rows(std::integral_constant<int, EPI_QKV_ROPE>{});
+    else by_rows(std::integral_constant<int, EPI_ACT_SILU>{});
+}
+// W: the bf16 tiles, read where `rec` holds no records
+template <int EPI, typename H>
+static int launch_gemm_xn(sd_session *s, const WRec &rec, const void *W, const void *X, int M, int N, int K, const void *norm_w,
+                          float eps, GemmEpiT<H> e, hipStream_t st) {
+    static_assert(EPI == EPI_QKV_ROPE || EPI == EPI_ACT_SILU, "the epilogues xn_by_epi_rows knows");
+    ProfScope ps(s, PC_GEMM, st);
+    SD_REQUIRE(M <= 8 && N % 16 == 0 && K % 1024 == 0 && K <= 8192, "norm-on-load GEMM: M=%d N=%d K=%d", M, N, K);
+    e.nrm_ssq = s->ssq; e.nrm_w = (const H *)norm_w; e.nrm_nt = K / 16; e.nrm_eps = eps;
+    int rc = SD_OK;
+    if constexpr (std::is_same<H, bf16_t>::value) {
+        if (rec.fmt == WF_W12) xn_enqueue_w12(EPI, rec.w12, X, M, N, K, e, st);
+        else if (rec.fmt == WF_Q4) rc = xn_enqueue_q4(EPI, rec.q4, X, M, N, K, e, st);
+    }
+    if (rec.fmt == WF_NONE)
+        xn_by_rows(M, [&](auto c) {
+            hipLaunchKernelGGL((gemm_bf16_stream_xn<EPI, decltype(c)::value, H>), dim3(N / 16), dim3(256), (size_t)K * sizeof(H), st,
+                               (const u32x4 *)W, (const H *)X, (float *)nullptr, M, N, K, 1, K / 32, e);
+        });
+    if (rc != SD_OK) return rc;
     SD_LAUNCH_CHECK();
+    count_record_launch(s, rec.fmt);
     return SD_OK;
 }
 
-// The k-split GEMM (streaming kernel's split) finishing with the residual epilogue: rows -> s->x, s->h (un-normalised), s->ssq
+// The k-split GEMM (streaming kernel's split) finishing with the residual epilogue: rows -> s->x, s->h (un-normalised), s->ssq.
+// No bias: the seam opens only behind a producer that has none.
 template <typename H>
-static int launch_gemm_fin(sd_session *s, const GemmRoute &pl, const void *W, const void *X, int M, int N, int K, const void *bias,
+static int launch_gemm_fin(sd_session *s, const GemmRoute &pl, const WRec &rec, const void *W, const void *X, int M, int N, int K,
                            hipStream_t st) {
     ProfScope ps(s, PC_GEMM, st);
     SD_REQUIRE(pl.kind == GK_STREAM && M <= 16 && (size_t)pl.S * 16 * N <= s->part_floats, "k-split GEMM with residual epilogue: M=%d N=%d K=%d", M, N, K);
     GemmEpiT<H> e = {};
-    e.bias = (const H *)bias; e.res_x = (H *)s->x; e.res_h = (H *)s->h; e.res_ssq = s->ssq;
+    e.res_x = (H *)s->x; e.res_h = (H *)s->h; e.res_ssq = s->ssq;
+    // arrivals counted so far, this launch's included; the epoch advances only once the launch is known to be enqueued (a
+    // failed launch must not leave every later wait of the session one arrival short)
     const unsigned want = s->fin_epoch + (unsigned)(pl.S - 1) + (unsigned)s->skew_now;
-    hipLaunchKernelGGL((gemm_bf16_stream_fin<H>), dim3((N / 16) * pl.S), dim3(256), 0, st, (const u32x4 *)W, (const H *)X, s->part,
-                       M, N, K, pl.S, pl.ksp, e, s->fin_ctr, want, s->wait_status);
+    int rc = SD_OK;
+    if constexpr (std::is_same<H, bf16_t>::value) {
+        if (rec.fmt == WF_W12) fin_enqueue_w12(s, pl, rec.w12, X, M, N, K, e, want, st);
+        else if (rec.fmt == WF_Q4) rc = fin_enqueue_q4(s, pl, rec.q4, X, M, N, K, e, want, st);
+    }
+    if (rec.fmt == WF_NONE)
+        hipLaunchKernelGGL((gemm_bf16_stream_fin<H>), dim3((N / 16) * pl.S), dim3(256), 0, st, (const u32x4 *)W, (const H *)X, s->part,
+                           M, N, K, pl.S, pl.ksp, e, s->fin_ctr, want, s->wait_status);
+    if (rc != SD_OK) return rc;
     SD_LAUNCH_CHECK();
-    s->fin_epoch += (unsigned)(pl.S - 1);                         // (advanced only for a launch that was enqueued)
+    s->fin_epoch += (unsigned)(pl.S - 1);
+    count_record_launch(s, rec.fmt);
     return SD_OK;
 }
 
-// The same two launches reading 12-bit weight records (w12.h) - defined at the end of this file, so that their kernels
-// follow every other kernel of the code object (see launch_attn_bf16 below for what a kernel in the middle costs)
-static int launch_gemm_xn_w12(sd_session *s, bool qkv, W12Arg W, const void *X, int M, int N, int K, const void *norm_w, float eps,
-                              GemmEpiT<bf16_t> e, hipStream_t st);
-static int launch_gemm_fin_w12(sd_session *s, const GemmRoute &pl, W12Arg W, const void *X, int M, int N, int K, hipStream_t st);
-// ... and reading 4-bit group-quantised records (q4.h), likewise defined at the end
-static int launch_gemm_xn_q4(sd_session *s, bool qkv, const unsigned *W, const void *X, int M, int N, int K, const void *norm_w, float eps,
-                             GemmEpiT<bf16_t> e, hipStream_t st);
-static int launch_gemm_fin_q4(sd_session *s, const GemmRoute &pl, const unsigned *W, const void *X, int M, int N, int K, hipStream_t st);
-template <typename T>
-static const unsigned *q4_of(const sd_model *m, int which, int l) {
-    if constexpr (std::is_same<T, bf16_t>::value) return m->q4[which][l];
-    return nullptr;
-}
-// ... and the balanced record GEMM of the 9..80-row passes (q4_rows.h), likewise defined at the end.  q4_rows_of: the
-// records of layer l's matrix `which` if this pass sends it there - a model marked by sd_model_set_q4_rows (bf16 Llama in
-// the fused layout), outside a tensor-parallel session, 9..80 rows in the tile layout, a record plan for the shape
+// The balanced record GEMM of the 9..80-row passes (q4_rows.h), likewise defined at the end.  plan_forward plans it for
+// the pass (FwdPlan::rows_*), sd_gemm_q4_rows for its call; the launch takes the plan.
 #define SD_Q4_ROWS_MIN 9
 #define SD_Q4_ROWS_MAX 80
-static bool q4_rows_plan_ok(int N, int K, int M, bool fused);
+static RowsPlan q4_rows_plan(int N, int K, int M, bool fused, int slabs, size_t part_cap, int cus);
 template <int EPI>
-static int launch_gemm_q4_rows(sd_session *s, const unsigned *W, const void *X, float *part, int M, int N, int K, int slabs,
-                               const GemmEpiT<bf16_t> &e, int *S_out, hipStream_t st);
-template <typename T>
-static const unsigned *q4_rows_of(const sd_session *s, int which, int l, int M, int N, int K, bool fused) {
-    const sd_model *m = s->m;
-    if constexpr (std::is_same<T, bf16_t>::value) {
-        if (!m->q4_rows || s->tp || m->cfg.arch != SD_ARCH_LLAMA || !m->cfg.fused_layout) return nullptr;
-        if (M < SD_Q4_ROWS_MIN || M > SD_Q4_ROWS_MAX || !m->q4[which][l] || !q4_rows_plan_ok(N, K, M, fused)) return nullptr;
-        return m->q4[which][l];
-    }
-    return nullptr;
-}
-// the 12-bit records of layer l's matrix `which`, if this pass may read them (bf16 model, a copy registered)
-template <typename T>
-static W12Arg w12_of(const sd_model *m, int which, int l) {
-    if constexpr (std::is_same<T, bf16_t>::value) return m->w12[which][l];
-    return W12Arg{nullptr, nullptr};
-}
+static int launch_gemm_q4_rows(sd_session *s, const RowsPlan &pl, const unsigned *W, const void *X, float *part, int M, int N, int K,
+                               const GemmEpiT<bf16_t> &e, hipStream_t st);
 
 // The tail of every head whose accumulators lie in s->part as S slabs: a caller that takes the raw slab gets it as it is
 // when the head ran unsplit, everybody else gets the slabs folded and rounded into logits_out (logits_kernel).
@@ -1783,6 +1821,7 @@ static void plan_forward(const PlanCtx &pc, const RowTab &tab, int s_max, FwdPla
     fp.s_max = s_max; fp.nsplit = fp.s_cap = fp.ga_chunk = 0; fp.attn_lds = 0; fp.pa = PaPlan{}; fp.sa = SaPlan{};         // (everything but pg, which only
     fp.qkv = fp.o = fp.gu = fp.down = fp.head = GemmRoute{};                                // AK_PREFILL fills and reads)
     fp.S_o = fp.ksp_o = fp.S_d = fp.ksp_d = 0;
+    fp.rows_qkv = fp.rows_gu = fp.rows_down = RowsPlan{};
     fp.small = small_path_ok(pc, tab);
     if (fp.small) {
         small_split(t, H, q_dim(c), &fp.S_o, &fp.ksp_o);
@@ -1828,6 +1867,13 @@ static void plan_forward(const PlanCtx &pc, const RowTab &tab, int s_max, FwdPla
         fp.o = route_gemm(t, H, q_dim(c), M, row_par);
         fp.gu = route_gemm(t, gu_cols(c), H, M, fused ? GN_FUSED : 0);
         fp.down = route_gemm(t, H, c.inter, M, row_par);
+    }
+    // the record row GEMM: a model marked for it (bf16 Llama in the fused layout), outside a tensor-parallel session, 9..80
+    // rows, a record plan for the shape - down's within the slab scratch.  Which matrices have records is the loop's to read.
+    if (pc.q4_rows && c.dtype == SD_BF16 && llama && c.fused_layout && !pc.tp && M >= SD_Q4_ROWS_MIN && M <= SD_Q4_ROWS_MAX) {
+        fp.rows_qkv = q4_rows_plan(qkv_cols(c), H, M, true, 0, 0, pc.cus);
+        fp.rows_gu = q4_rows_plan(gu_cols(c), H, M, true, 0, 0, pc.cus);
+        fp.rows_down = q4_rows_plan(H, c.inter, M, false, 0, pc.part_floats, pc.cus);
     }
     if (tab.n_logit_rows > 0) fp.head = route_gemm(t, c.vocab, ED, tab.n_logit_rows, GN_GATHER);
 }
@@ -1947,7 +1993,7 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
     sd_model *m = s->m;
     const sd_model_config &c = m->cfg;
     FwdPlan fp;
-    plan_forward(PlanCtx{c, s->tun, s->tp != nullptr, m->w.final_norm_w != nullptr, s->part_floats, device_cus()}, tab, s_max, fp);
+    plan_forward(PlanCtx{c, s->tun, s->tp != nullptr, m->w.final_norm_w != nullptr, s->part_floats, device_cus(), m->q4_rows}, tab, s_max, fp);
     if (fp.small) return forward_small(s, tab, fp, logits_out, ld_logits, rq, ho, st);
     const int H = c.hidden, D = c.head_dim, I = c.inter, L = c.n_layers, ED = embed_dim(c);
     const bool llama = c.arch == SD_ARCH_LLAMA, pre = llama || c.opt_pre_ln, fused = is16(c.dtype) && c.fused_layout != 0;
@@ -1998,22 +2044,16 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
         const bool xn_q = fp.seam_d && l > 0 && !m->bfc2[l - 1];        // layer l - 1's down projection left un-normalised rows
         const bool xn_o = fp.seam_o && !m->bo[l];
         const bool xn_d = fp.seam_d && l + 1 < L && !m->bfc2[l];
+        const WRec r_qkv = rec_of<T>(m, SD_W12_QKV, l), r_gu = rec_of<T>(m, SD_W12_GATE_UP, l), r_down = rec_of<T>(m, SD_W12_DOWN, l);
         // ---- QKV projection -> rope / scale -> q buffer + in-place KV append (fused into the GEMM's epilogue with the fused
         // weight layout, else slabs for the stand-alone epilogue)
         if (l == 0 && fp.embed_qkv) {
             if ((rc = launch_small_qkv<PRO_EMBED>(s, qkv_epi<bf16_t>(s, tab, 0), embed_pro(s, fp), st)) != SD_OK) return rc;
-        } else if (xn_q && q4_of<T>(m, SD_W12_QKV, l)) {
-            rc = launch_gemm_xn_q4(s, true, q4_of<T>(m, SD_W12_QKV, l), h, n_new, qkv_cols(c), H, m->n1w[l], c.norm_eps, qkv_epi<bf16_t>(s, tab, l), st);
-            if (rc != SD_OK) return rc;
-        } else if (xn_q && w12_of<T>(m, SD_W12_QKV, l).codes) {
-            rc = launch_gemm_xn_w12(s, true, w12_of<T>(m, SD_W12_QKV, l), h, n_new, qkv_cols(c), H, m->n1w[l], c.norm_eps, qkv_epi<bf16_t>(s, tab, l), st);
-            if (rc != SD_OK) return rc;
         } else if (xn_q) {
-            rc = launch_gemm_xn<EPI_QKV_ROPE, H16>(s, m->wqkv[l], h, n_new, qkv_cols(c), H, m->n1w[l], c.norm_eps, qkv_epi<H16>(s, tab, l), st);
+            rc = launch_gemm_xn<EPI_QKV_ROPE, H16>(s, r_qkv, m->wqkv[l], h, n_new, qkv_cols(c), H, m->n1w[l], c.norm_eps, qkv_epi<H16>(s, tab, l), st);
             if (rc != SD_OK) return rc;
-        } else if (const unsigned *rec = q4_rows_of<T>(s, SD_W12_QKV, l, n_new, qkv_cols(c), H, true)) {
-            ProfScope ps(s, PC_GEMM, st);
-            rc = launch_gemm_q4_rows<EPI_QKV_ROPE>(s, rec, h, nullptr, n_new, qkv_cols(c), H, 1, qkv_epi<bf16_t>(s, tab, l), nullptr, st);
+        } else if (fp.rows_qkv.ok && r_qkv.fmt == WF_Q4) {
+            rc = launch_gemm_q4_rows<EPI_QKV_ROPE>(s, fp.rows_qkv, r_qkv.q4, h, nullptr, n_new, qkv_cols(c), H, qkv_epi<bf16_t>(s, tab, l), st);
             if (rc != SD_OK) return rc;
         } else if (fused) {
             const GemmEpiT<H16> e = qkv_epi<H16>(s, tab, l);
@@ -2051,18 +2091,11 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
                                          pre ? m->n2b[l] : m->n1b[l], pre ? RES_PRE : RES_POST, st)) != SD_OK)
             return rc;
         // ---- gate/up (fc1) -> SiLU * up / ReLU -> activation buffer
-        if (xn_o && q4_of<T>(m, SD_W12_GATE_UP, l)) {
-            rc = launch_gemm_xn_q4(s, false, q4_of<T>(m, SD_W12_GATE_UP, l), h, n_new, gu_cols(c), H, m->n2w[l], c.norm_eps, act_epi<bf16_t>(s, l), st);
+        if (xn_o) {
+            rc = launch_gemm_xn<EPI_ACT_SILU, H16>(s, r_gu, m->wgu[l], h, n_new, gu_cols(c), H, m->n2w[l], c.norm_eps, act_epi<H16>(s, l), st);
             if (rc != SD_OK) return rc;
-        } else if (xn_o && w12_of<T>(m, SD_W12_GATE_UP, l).codes) {
-            rc = launch_gemm_xn_w12(s, false, w12_of<T>(m, SD_W12_GATE_UP, l), h, n_new, gu_cols(c), H, m->n2w[l], c.norm_eps, act_epi<bf16_t>(s, l), st);
-            if (rc != SD_OK) return rc;
-        } else if (xn_o) {
-            rc = launch_gemm_xn<EPI_ACT_SILU, H16>(s, m->wgu[l], h, n_new, gu_cols(c), H, m->n2w[l], c.norm_eps, act_epi<H16>(s, l), st);
-            if (rc != SD_OK) return rc;
-        } else if (const unsigned *rec = q4_rows_of<T>(s, SD_W12_GATE_UP, l, n_new, gu_cols(c), H, true)) {
-            ProfScope ps(s, PC_GEMM, st);
-            rc = launch_gemm_q4_rows<EPI_ACT_SILU>(s, rec, h, nullptr, n_new, gu_cols(c), H, 1, act_epi<bf16_t>(s, l), nullptr, st);
+        } else if (fp.rows_gu.ok && r_gu.fmt == WF_Q4) {
+            rc = launch_gemm_q4_rows<EPI_ACT_SILU>(s, fp.rows_gu, r_gu.q4, h, nullptr, n_new, gu_cols(c), H, act_epi<bf16_t>(s, l), st);
             if (rc != SD_OK) return rc;
         } else if (fused) {
             const GemmEpiT<H16> e = act_epi<H16>(s, l);
@@ -2078,17 +2111,12 @@ static int forward_impl(sd_session *s, const RowTab &tab, int s_max, float *logi
         }
         // ---- down projection (fc2) + residual (+ the next norm).  With the norm-on-load seam its last k-slab's workgroups add
         // the residual and the next layer's QKV normalises on load (no residual+norm launch)
-        if (xn_d && q4_of<T>(m, SD_W12_DOWN, l)) {
-            if ((rc = launch_gemm_fin_q4(s, fp.down, q4_of<T>(m, SD_W12_DOWN, l), ac, n_new, H, I, st)) != SD_OK) return rc;
-        } else if (xn_d && w12_of<T>(m, SD_W12_DOWN, l).codes) {
-            if ((rc = launch_gemm_fin_w12(s, fp.down, w12_of<T>(m, SD_W12_DOWN, l), ac, n_new, H, I, st)) != SD_OK) return rc;
-        } else if (xn_d) {
-            if ((rc = launch_gemm_fin<H16>(s, fp.down, m->wdown[l], ac, n_new, H, I, nullptr, st)) != SD_OK) return rc;
+        if (xn_d) {
+            if ((rc = launch_gemm_fin<H16>(s, fp.down, r_down, m->wdown[l], ac, n_new, H, I, st)) != SD_OK) return rc;
         } else {
-            if (const unsigned *rec = q4_rows_of<T>(s, SD_W12_DOWN, l, n_new, H, I, false)) {
-                ProfScope ps(s, PC_GEMM, st);             // the EPI_PART instance: slabs for the residual+norm launch below
-                if ((rc = launch_gemm_q4_rows<EPI_PART>(s, rec, ac, s->part, n_new, H, I, 0, GemmEpiT<bf16_t>{}, &go.S, st)) != SD_OK) return rc;
-                go.stride_s = align_up(n_new, 16) * (size_t)H;
+            if (fp.rows_down.ok && r_down.fmt == WF_Q4) {       // the EPI_PART instance: slabs for the residual+norm launch below
+                if ((rc = launch_gemm_q4_rows<EPI_PART>(s, fp.rows_down, r_down.q4, ac, s->part, n_new, H, I, GemmEpiT<bf16_t>{}, st)) != SD_OK) return rc;
+                go = GemmOut{fp.rows_down.S, align_up(n_new, 16) * (size_t)H};
             } else if ((rc = run_gemm<H16>(s, fp.down, m->wdown[l], ac, n_new, H, I, &go, st)) != SD_OK) return rc;
             const float *dsrc = s->part;
             if ((rc = tp_reduce(s, &go, &dsrc, n_new, H, st)) != SD_OK) return rc;
@@ -2539,7 +2567,7 @@ extern "C" int sd_forward_route(const sd_model_config *cfg, const sd_pass_desc *
     SD_REQUIRE(p.n_logit_rows >= 0 && p.n_logit_rows <= p.n_rows, "sd_forward_route: n_logit_rows=%d of n_rows=%d", p.n_logit_rows, p.n_rows);
     SD_REQUIRE(p.max_rows >= 1 && p.cus >= 0 && (p.kv_fp8 | 1) == 1 && (p.tp | 1) == 1,
                "sd_forward_route: max_rows=%d cus=%d kv_fp8=%d tp=%d", p.max_rows, p.cus, p.kv_fp8, p.tp);
-    PlanCtx pc = {*cfg, read_tunables(), p.tp != 0, true, 0, p.cus ? p.cus : device_cus()};
+    PlanCtx pc = {*cfg, read_tunables(), p.tp != 0, true, 0, p.cus ? p.cus : device_cus(), false};   // (q4_rows: a model's mark, no config's)
     const int max_rows = std::min(p.max_rows, model_max_rows(pc.tun, pc.cfg));      // (as sd_session_create clamps it)
     SD_REQUIRE(p.n_rows <= max_rows, "sd_forward_route: n_rows=%d exceeds the session's max_rows %d", p.n_rows, max_rows);
     pc.part_floats = plan_scratch(pc.tun, pc.cfg, max_rows).part_floats;
@@ -2603,41 +2631,18 @@ extern "C" int sd_gemm_bf16(const void *w_packed, const void *x, int x_tiled, in
 #include "spec_loops.h"
 #include "tree_loop.h"
 
-// ---- the norm-on-load and the finishing GEMM on 12-bit weight records (forward declarations above launch_gemm_xn's users).
-// Last in the file: their kernels are the last of the code object.
-static int launch_gemm_xn_w12(sd_session *s, bool qkv, W12Arg W, const void *X, int M, int N, int K, const void *norm_w, float eps,
-                              GemmEpiT<bf16_t> e, hipStream_t st) {
-    ProfScope ps(s, PC_GEMM, st);
-    SD_REQUIRE(M <= 8 && N % 16 == 0 && K % 1024 == 0 && K <= 8192, "norm-on-load GEMM: M=%d N=%d K=%d", M, N, K);
-    e.nrm_ssq = s->ssq; e.nrm_w = (const bf16_t *)norm_w; e.nrm_nt = K / 16; e.nrm_eps = eps;
-    auto go = [&](auto epi, auto c) {
-        hipLaunchKernelGGL((gemm_bf16_stream_xn<decltype(epi)::value, decltype(c)::value, bf16_t, WFetchW12>), dim3(N / 16), dim3(256),
+// ---- the norm-on-load and the finishing GEMM on 12-bit weight records: the enqueue steps of launch_gemm_xn / launch_gemm_fin
+// (declared above them).  Last in the file: their kernels are the last of the code object.
+static void xn_enqueue_w12(int epi, W12Arg W, const void *X, int M, int N, int K, const GemmEpiT<bf16_t> &e, hipStream_t st) {
+    xn_by_epi_rows(epi, M, [&](auto epi_c, auto c) {
+        hipLaunchKernelGGL((gemm_bf16_stream_xn<decltype(epi_c)::value, decltype(c)::value, bf16_t, WFetchW12>), dim3(N / 16), dim3(256),
                            (size_t)K * sizeof(bf16_t), st, W, (const bf16_t *)X, (float *)nullptr, M, N, K, 1, K / 32, e);
-    };
-    auto by_rows = [&](auto epi) {
-        using std::integral_constant;
-        if (M <= 4) go(epi, integral_constant<int, 4>{});
-        else if (M == 5) go(epi, integral_constant<int, 3>{});
-        else go(epi, integral_constant<int, 2>{});
-    };
-    if (qkv) by_rows(std::integral_constant<int, EPI_QKV_ROPE>{});
-    else by_rows(std::integral_constant<int, EPI_ACT_SILU>{});
-    SD_LAUNCH_CHECK();
-    ++s->w12_launches;
-    return SD_OK;
+    });
 }
-static int launch_gemm_fin_w12(sd_session *s, const GemmRoute &pl, W12Arg W, const void *X, int M, int N, int K, hipStream_t st) {
-    ProfScope ps(s, PC_GEMM, st);
-    SD_REQUIRE(pl.kind == GK_STREAM && M <= 16 && (size_t)pl.S * 16 * N <= s->part_floats, "k-split GEMM with residual epilogue: M=%d N=%d K=%d", M, N, K);
-    GemmEpiT<bf16_t> e = {};
-    e.res_x = (bf16_t *)s->x; e.res_h = (bf16_t *)s->h; e.res_ssq = s->ssq;
-    const unsigned want = s->fin_epoch + (unsigned)(pl.S - 1) + (unsigned)s->skew_now;
+static void fin_enqueue_w12(sd_session *s, const GemmRoute &pl, W12Arg W, const void *X, int M, int N, int K, const GemmEpiT<bf16_t> &e,
+                            unsigned want, hipStream_t st) {
     hipLaunchKernelGGL((gemm_bf16_stream_fin<bf16_t, WFetchW12>), dim3((N / 16) * pl.S), dim3(256), 0, st, W, (const bf16_t *)X, s->part,
                        M, N, K, pl.S, pl.ksp, e, s->fin_ctr, want, s->wait_status);
-    SD_LAUNCH_CHECK();
-    s->fin_epoch += (unsigned)(pl.S - 1);
-    ++s->w12_launches;
-    return SD_OK;
 }
 extern "C" int sd_pack_weight_w12(const void *w_tiled, void *codes, void *meta, int N, int K, int *status_dev, void *stream) {
     SD_REQUIRE(w_tiled && codes && meta && status_dev && N > 0 && K > 0 && N % 16 == 0 && K % 32 == 0,
@@ -2734,43 +2739,23 @@ static int launch_attn_shared(sd_session *s, const T *q, const RowTab &tab, cons
     return SD_OK;
 }
 
-// ---- the norm-on-load and the finishing GEMM on 4-bit group-quantised records, their packer and expander (forward
-// declarations above launch_gemm_xn's users): new kernels go behind every other kernel of the code object
+// ---- the norm-on-load and the finishing GEMM on 4-bit group-quantised records (the enqueue steps of launch_gemm_xn /
+// launch_gemm_fin, declared above them), their packer and expander: new kernels go behind every other kernel of the code object
 #include "q4.h"
 #include "q4_rows.h"
-static int launch_gemm_xn_q4(sd_session *s, bool qkv, const unsigned *W, const void *X, int M, int N, int K, const void *norm_w, float eps,
-                             GemmEpiT<bf16_t> e, hipStream_t st) {
-    ProfScope ps(s, PC_GEMM, st);
-    SD_REQUIRE(M >= 1 && M <= 8 && N % 16 == 0 && K % 1024 == 0 && K <= 8192, "norm-on-load GEMM on 4-bit records: M=%d N=%d K=%d", M, N, K);
-    e.nrm_ssq = s->ssq; e.nrm_w = (const bf16_t *)norm_w; e.nrm_nt = K / 16; e.nrm_eps = eps;
-    auto go = [&](auto epi, auto c) {
-        hipLaunchKernelGGL((gemm_q4_stream_xn<decltype(epi)::value, decltype(c)::value>), dim3(N / 16), dim3(256),
+static int xn_enqueue_q4(int epi, const unsigned *W, const void *X, int M, int N, int K, const GemmEpiT<bf16_t> &e, hipStream_t st) {
+    SD_REQUIRE(M >= 1, "norm-on-load GEMM on 4-bit records: M=%d N=%d K=%d", M, N, K);
+    xn_by_epi_rows(epi, M, [&](auto epi_c, auto c) {
+        hipLaunchKernelGGL((gemm_q4_stream_xn<decltype(epi_c)::value, decltype(c)::value>), dim3(N / 16), dim3(256),
                            (size_t)K * sizeof(bf16_t), st, W, (const bf16_t *)X, M, N, K, e);
-    };
-    auto by_rows = [&](auto epi) {
-        using std::integral_constant;
-        if (M <= 4) go(epi, integral_constant<int, 4>{});
-        else if (M == 5) go(epi, integral_constant<int, 3>{});
-        else go(epi, integral_constant<int, 2>{});
-    };
-    if (qkv) by_rows(std::integral_constant<int, EPI_QKV_ROPE>{});
-    else by_rows(std::integral_constant<int, EPI_ACT_SILU>{});
-    SD_LAUNCH_CHECK();
-    ++s->q4_launches;
+    });
     return SD_OK;
 }
-static int launch_gemm_fin_q4(sd_session *s, const GemmRoute &pl, const unsigned *W, const void *X, int M, int N, int K, hipStream_t st) {
-    ProfScope ps(s, PC_GEMM, st);
-    SD_REQUIRE(pl.kind == GK_STREAM && M <= 16 && K % 128 == 0 && (size_t)pl.S * 16 * N <= s->part_floats,
-               "k-split GEMM with residual epilogue on 4-bit records: M=%d N=%d K=%d", M, N, K);
-    GemmEpiT<bf16_t> e = {};
-    e.res_x = (bf16_t *)s->x; e.res_h = (bf16_t *)s->h; e.res_ssq = s->ssq;
-    const unsigned want = s->fin_epoch + (unsigned)(pl.S - 1) + (unsigned)s->skew_now;
+static int fin_enqueue_q4(sd_session *s, const GemmRoute &pl, const unsigned *W, const void *X, int M, int N, int K,
+                          const GemmEpiT<bf16_t> &e, unsigned want, hipStream_t st) {
+    SD_REQUIRE(K % 128 == 0, "k-split GEMM with residual epilogue on 4-bit records: M=%d N=%d K=%d", M, N, K);
     hipLaunchKernelGGL(gemm_q4_stream_fin<0>, dim3((N / 16) * pl.S), dim3(256), 0, st, W, (const bf16_t *)X, s->part,
                        M, N, K, pl.S, pl.ksp, e, s->fin_ctr, want, s->wait_status);
-    SD_LAUNCH_CHECK();
-    s->fin_epoch += (unsigned)(pl.S - 1);
-    ++s->q4_launches;
     return SD_OK;
 }
 extern "C" int sd_pack_weight_q4(const void *q, const void *scales, const void *zeros, void *records, void *w_tiled_out, int N, int K,
@@ -2799,11 +2784,11 @@ extern "C" int sd_unpack_weight_q4(const void *records, void *w_tiled, int N, in
 // epilogue needs S == 1.  Unlike rows_plan it has no other kernel to leave a shape to, so it takes any row count from 1,
 // a matrix with fewer n-tiles than CUs (NG = the tiles: one each) and the best cut whatever its efficiency; the cost is
 // (record bytes + slab traffic) / (how evenly the n-tiles divide x the share of the CUs that get a workgroup).
-// slabs > 0: that many slabs or no plan (sd_gemm_q4_rows); part_cap > 0: the floats the slabs may take.
-static RowsPlan q4_rows_plan(int N, int K, int M, bool fused, int slabs, size_t part_cap) {
+// slabs > 0: that many slabs or no plan (sd_gemm_q4_rows); part_cap > 0: the floats the slabs may take; cus: the device's CUs.
+static RowsPlan q4_rows_plan(int N, int K, int M, bool fused, int slabs, size_t part_cap, int cus) {
     RowsPlan p = {};
     if (M < 1 || M > SD_Q4_ROWS_MAX || N < 16 || N % 16 || K < 128 || K % 128) return p;
-    const int G = device_cus(), NT = N / 16, KS = K / 32, KR = K / 128, Mpad = (int)align_up(M, 16);
+    const int G = cus, NT = N / 16, KS = K / 32, KR = K / 128, Mpad = (int)align_up(M, 16);
     const double wbytes = (double)NT * KR * (Q4_REC_DWORDS * 4), slab = 2.0 * Mpad * (double)N * 4.0;
     double best = 1e300;
     for (int S = 1; S <= (fused ? 1 : 16); S *= 2) {
@@ -2833,7 +2818,6 @@ static RowsPlan q4_rows_plan(int N, int K, int M, bool fused, int slabs, size_t 
     }
     return p;
 }
-static bool q4_rows_plan_ok(int N, int K, int M, bool fused) { return q4_rows_plan(N, K, M, fused, 0, 0).ok; }
 
 // gemm_q4_rows' instance of Mpad rows: MT = Mpad / 16 m-tiles, chunks of 8 k-steps at 1-2 m-tiles and 4 past that (as the
 // kernel has it), the activation panel (2 buffers x nwk k-groups x CH k-steps x MT KiB) reused as the fold buffer
@@ -2864,15 +2848,14 @@ static int q4_rows_go(const RowsPlan &pl, const unsigned *W, const void *X, floa
     SD_LAUNCH_CHECK();
     return SD_OK;
 }
-// a forward's launch: slabs == 1 for the fused epilogues; EPI_PART leaves *S_out slabs of [Mpad][N] floats in `part`
+// a forward's launch on the pass's plan (FwdPlan::rows_*): one slab for the fused epilogues; EPI_PART leaves pl.S slabs of
+// [Mpad][N] floats in `part`
 template <int EPI>
-static int launch_gemm_q4_rows(sd_session *s, const unsigned *W, const void *X, float *part, int M, int N, int K, int slabs,
-                               const GemmEpiT<bf16_t> &e, int *S_out, hipStream_t st) {
-    const RowsPlan pl = q4_rows_plan(N, K, M, EPI != EPI_PART, slabs, EPI == EPI_PART ? s->part_floats : 0);
-    SD_REQUIRE(pl.ok, "gemm_q4_rows: no record plan for M=%d N=%d K=%d", M, N, K);
+static int launch_gemm_q4_rows(sd_session *s, const RowsPlan &pl, const unsigned *W, const void *X, float *part, int M, int N, int K,
+                               const GemmEpiT<bf16_t> &e, hipStream_t st) {
+    ProfScope ps(s, PC_GEMM, st);
     const int rc = q4_rows_go<EPI>(pl, W, X, part, M, N, K, e, st);
     if (rc != SD_OK) return rc;
-    if (S_out) *S_out = pl.S;
     ++s->q4_launches;
     return SD_OK;
 }
@@ -2885,7 +2868,7 @@ extern "C" int sd_gemm_q4_rows(const void *records, const void *x_tiled, int M, 
     SD_REQUIRE(((uintptr_t)records & 127) == 0 && ((uintptr_t)x_tiled & 15) == 0,
                "sd_gemm_q4_rows: records must be 128-byte aligned (x_tiled 16-byte)");
     SD_REQUIRE(slabs >= 0, "sd_gemm_q4_rows: slabs=%d (0: the plan's choice)", slabs);
-    const RowsPlan pl = q4_rows_plan(N, K, M, false, slabs, 0);
+    const RowsPlan pl = q4_rows_plan(N, K, M, false, slabs, 0, device_cus());
     SD_REQUIRE(pl.ok, "sd_gemm_q4_rows: no record plan of %d slabs for N=%d K=%d (a power of two <= 16 and <= K / 128 that divides "
                "the CUs evenly, at most %d n-tiles per workgroup)", slabs, N, K, GR_MAX_TILES);
     const size_t Mpad = align_up(M, 16);

@@ -9,6 +9,8 @@ Session.forward, batch_forward, batch_prefill, the tree forward, Session.profile
     kv       SHA-256 of the written range [:, :, :, :cache_len] of every session's KV arena ("" where the API hides them)
     counts   launches per profile class of the measured pass (profile_read)
     prefill  [attn_prefill launches, of which blocked] of the case's first session
+    records  the cases on weight records: GEMM launches of the measured pass that streamed {"q4": 4-bit, "w12": 12-bit} records
+             (Session.q4_launches / w12_launches, summed over the sessions), so that each proves which kernels ran
 
 tests/test_gpu_forward_routes.py recomputes each case with run_case() and compares; a refactor of the host code that keeps
 every launch (kernel, grid, arguments) keeps every digest and every count.  main() also asserts from the counts that each
@@ -54,12 +56,14 @@ CONFIGS = {
 _MODELS = {}
 
 
-def model(name, dtype=BF16):
-    """One model per (config, dtype) for the whole process: weights from numpy's seeded generator, tensor by tensor."""
-    if (name, dtype) not in _MODELS:
+def model(name, dtype=BF16, q4=None, w12=None):
+    """One model per (config, dtype, q4, w12) for the whole process: weights from numpy's seeded generator, tensor by tensor.
+    w12=None leaves the 12-bit records to the memory rule; the cases on records say which they want."""
+    key = (name, dtype, q4, w12)
+    if key not in _MODELS:
         seed = 40 + sorted(CONFIGS).index(name)
-        _MODELS[name, dtype] = SpecDecModel.synthetic(ModelConfig(**CONFIGS[name]), seed=seed, dtype=dtype, method="numpy")
-    return _MODELS[name, dtype]
+        _MODELS[key] = SpecDecModel.synthetic(ModelConfig(**CONFIGS[name]), seed=seed, dtype=dtype, method="numpy", q4=q4, w12=w12)
+    return _MODELS[key]
 
 
 def tokens(n, seed=3):
@@ -80,32 +84,46 @@ def kv_sha(sessions):
     return h.hexdigest()
 
 
-def record(sessions, logits, counts):
+def record(sessions, logits, counts, records=None):
     s0 = sessions[0]
-    return {"logits": sha(logits), "kv": kv_sha(sessions), "counts": counts,
-            "prefill": [s0.prefill_attn_launches(), s0.prefill_attn_blocked_launches()]}
+    rec = {"logits": sha(logits), "kv": kv_sha(sessions), "counts": counts,
+           "prefill": [s0.prefill_attn_launches(), s0.prefill_attn_blocked_launches()]}
+    if records is not None:
+        rec["records"] = records
+    return rec
 
 
-def measured(ses, fn):
-    """fn() with the session's profile on: (what fn returned, {class: launches})."""
+def record_launches(sessions):
+    return {"q4": sum(s.q4_launches() for s in sessions), "w12": sum(s.w12_launches() for s in sessions)}
+
+
+def measured(ses, fn, sessions=None):
+    """fn() with the session's profile on: (what fn returned, {class: launches}); with `sessions`, also what their
+    record-launch counters gained over fn()."""
+    before = record_launches(sessions) if sessions else None
     ses.profile(True)
     out = fn()
     counts = {k: v[1] for k, v in ses.profile_read().items()}
     ses.profile(False)
-    return out, counts
+    if sessions is None:
+        return out, counts
+    after = record_launches(sessions)
+    return out, counts, {k: after[k] - before[k] for k in after}
 
 
-def decode(name, rows, dtype=BF16, ctx=12, kv_dtype=None, env=None):
-    """A `ctx`-token context pass, then the measured pass: `rows` new rows, logits for all of them."""
+def decode(name, rows, dtype=BF16, ctx=12, kv_dtype=None, env=None, q4=None, w12=None):
+    """A `ctx`-token context pass, then the measured pass: `rows` new rows, logits for all of them.  With q4 / w12 given the
+    model is built with them and the record says how many launches of the measured pass streamed records."""
     def run():
         with tunables(env):
-            ses = model(name, dtype).new_session(256, kv_dtype=kv_dtype)        # (the session keeps the tunables of its creation)
+            ses = model(name, dtype, q4, w12).new_session(256, kv_dtype=kv_dtype)   # (the session keeps the tunables of its creation)
         ids = tokens(ctx + rows)
         if ctx:
             ses.forward(ids[:ctx], 0)
         n_logits = min(rows, 64) if rows <= 64 else 1
-        logits, counts = measured(ses, lambda: ses.forward(ids[ctx:], n_logits).clone())
-        return record([ses], logits, counts)
+        on_records = q4 is not None or w12 is not None
+        logits, counts, *recs = measured(ses, lambda: ses.forward(ids[ctx:], n_logits).clone(), [ses] if on_records else None)
+        return record([ses], logits, counts, *recs)
     return run
 
 
@@ -123,16 +141,17 @@ def native_loop(name):
     return run
 
 
-def batched(n_streams, rows):
+def batched(n_streams, rows, q4=None):
     def run():
-        m = model("llama1k")
+        m = model("llama1k", q4=q4)
         sess = [m.new_session(64, max_rows=80) for _ in range(n_streams)]
         seqs = [tokens(6 + rows, seed=10 + i) for i in range(n_streams)]
         for s, q in zip(sess, seqs):
             s.forward(q[:6], 0)
         big = torch.empty((n_streams * rows, V), dtype=torch.float32, device="cuda")
-        logits, counts = measured(sess[0], lambda: batch_forward(sess, seqs, [rows] * n_streams, [rows] * n_streams, big).clone())
-        return record(sess, logits, counts)
+        logits, counts, *recs = measured(sess[0], lambda: batch_forward(sess, seqs, [rows] * n_streams, [rows] * n_streams, big).clone(),
+                                         sess if q4 is not None else None)
+        return record(sess, logits, counts, *recs)
     return run
 
 
@@ -227,6 +246,20 @@ CASES = {
     "prefill_128_blocked": decode("llama1k", 128, ctx=0, env={"SD_PREFILL_ATTN_BLOCK": "64"}),
     "tree_7nodes": tree,
     "tp2_loopback_5rows": tensor_parallel,
+    # weight records, <= 8 rows: both sides of the 12-bit choice, then the 4-bit records through the norm-on-load and the
+    # finishing kernels at C = 3 (5 rows) and C = 4 (1 row), hidden 1024 and 4096; the dequantised twin reads bf16 only
+    "llama1k_5rows_w12": decode("llama1k", 5, w12=True),
+    "llama1k_5rows_no_w12": decode("llama1k", 5, w12=False),
+    "llama1k_5rows_q4": decode("llama1k", 5, q4=True),
+    "llama4k_1row_q4": decode("llama4k", 1, q4=True),
+    "llama1k_5rows_q4_dequantised": decode("llama1k", 5, q4="dequantised", w12=False),
+    # 4-bit records on the row GEMM (9..80 rows): both edges and 1 / 3 / 5 m-tiles, the first row count past the range,
+    # and 8 rows, which stay with the <= 8-row record kernels
+    "q4rows_9rows": decode("llama1k", 9, q4="rows"),
+    "q4rows_batch_8x5": batched(8, 5, q4="rows"),
+    "q4rows_batch_16x5": batched(16, 5, q4="rows"),
+    "q4rows_81rows": decode("llama1k", 81, ctx=0, q4="rows"),
+    "q4rows_8rows": decode("llama1k", 8, q4="rows"),
 }
 
 # What the launch counts of the measured pass must say for the route a case is named for (2 layers).  Per layer the per-op
@@ -254,7 +287,23 @@ EXPECT = {
     "tree_7nodes": dict(PER_OP, norm_residual=3),                   # (7 rows: the down seam opens, the attention seam needs the fused launch)
     "tp2_loopback_5rows": dict(PER_OP, other=4),                    # (two all-reduces per layer)
 }
-EXPECT_PREFILL = {"batch_prefill_40_88": [2, 0], "prefill_128": [2, 0], "prefill_128_fp8kv": [2, 0], "prefill_128_blocked": [2, 2]}
+# The cases on weight records add the record launches of the measured pass to the counts.  <= 8 rows: the launches behind an
+# open seam read records - QKV of layer 1, gate/up of both layers, down of layer 0.  The row GEMM: QKV, gate/up and down of
+# both layers, with the per-op chain around them (its seams stay shut past 8 rows; 9 rows keep the fused attention + O).
+NO_RECORDS = {"q4": 0, "w12": 0}
+EXPECT.update({
+    "llama1k_5rows_w12": dict(FUSED_AO, norm_residual=1, q4=0, w12=4),
+    "llama1k_5rows_no_w12": dict(FUSED_AO, norm_residual=1, **NO_RECORDS),
+    "llama1k_5rows_q4": dict(FUSED_AO, norm_residual=1, q4=4, w12=0),
+    "llama4k_1row_q4": dict(FUSED_AO, norm_residual=1, q4=4, w12=0),
+    "llama1k_5rows_q4_dequantised": dict(FUSED_AO, norm_residual=1, **NO_RECORDS),
+    "q4rows_9rows": dict(FUSED_AO, q4=6, w12=0),
+    "q4rows_batch_8x5": dict(PER_OP, q4=6, w12=0),
+    "q4rows_batch_16x5": dict(PER_OP, q4=6, w12=0),
+    "q4rows_81rows": dict(PREFILL, **NO_RECORDS),
+    "q4rows_8rows": dict(FUSED_AO, norm_residual=1, q4=4, w12=0),
+})
+EXPECT_PREFILL = {"q4rows_81rows": [2, 0], "batch_prefill_40_88": [2, 0], "prefill_128": [2, 0], "prefill_128_fp8kv": [2, 0], "prefill_128_blocked": [2, 2]}
 
 
 def run_case(name):
@@ -273,10 +322,14 @@ def main():
         print(name, json.dumps(rec), flush=True)
         if rec != again:
             bad.append(f"{name}: not reproducible: {again}")
-        if rec["counts"] != EXPECT[name] or rec["prefill"] != EXPECT_PREFILL.get(name, [0, 0]):
-            bad.append(f"{name}: route: counts {rec['counts']} prefill {rec['prefill']}, expected {EXPECT[name]} "
-                       f"{EXPECT_PREFILL.get(name, [0, 0])}")
+        if dict(rec["counts"], **rec.get("records", {})) != EXPECT[name] or rec["prefill"] != EXPECT_PREFILL.get(name, [0, 0]):
+            bad.append(f"{name}: route: counts {rec['counts']} records {rec.get('records')} prefill {rec['prefill']}, expected "
+                       f"{EXPECT[name]} {EXPECT_PREFILL.get(name, [0, 0])}")
         recs[name] = rec
+    # the dequantised twin runs the bf16 kernels on the weights the records expand to: the same bits, no record launch
+    a, b = recs["llama1k_5rows_q4"], recs["llama1k_5rows_q4_dequantised"]
+    if (a["logits"], a["kv"]) != (b["logits"], b["kv"]):
+        bad.append("llama1k_5rows_q4 and llama1k_5rows_q4_dequantised differ")
     with open(out, "w") as f:
         json.dump(recs, f, indent=1, sort_keys=True)
         f.write("\n")

@@ -1,8 +1,9 @@
 """The forward pass, bit for bit, on every route it can take: each case of tests/golden/make_forward_routes.py is
 recomputed and compared with the record in tests/golden/forward_routes.json (SHA-256 of the logits and of the written KV
-range, launch counts per profile class, prefill-attention launch counters).  The record was made by that script at the
-commit before the forward pass's host code was restructured around a per-pass route; host-side changes that keep every
-launch as it is keep every digest."""
+range, launch counts per profile class, prefill-attention launch counters and, for the cases on 12-bit / 4-bit weight
+records, the launches that streamed them).  The record was made by that script at the commit before the forward pass's host
+code was restructured around a per-pass route, its cases on weight records at the commit before the record launchers got
+one host body per launch; host-side changes that keep every launch as it is keep every digest."""
 import importlib.util
 import json
 import os
@@ -31,5 +32,6 @@ def test_forward_route_is_bit_identical_to_the_record(routes, name):
     print(name, got)
     assert got["counts"] == RECORD[name]["counts"]
     assert got["prefill"] == RECORD[name]["prefill"]
+    assert got.get("records") == RECORD[name].get("records")     # the cases on weight records: which launches streamed them
     assert got["logits"] == RECORD[name]["logits"]
     assert got["kv"] == RECORD[name]["kv"]
